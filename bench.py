@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the EKF-SLAM update path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One "step" = one ``observe()`` (predict + update) of the headline workload
 (BASELINE.json configs[2]): n=1024 landmarks, m=32 detections per frame,
@@ -22,6 +22,16 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   cpu_baseline : the CPU oracle in the reference's own operation sequence
                  (oracle/ekf_numpy.py, mode="reference_ops") timed on this
                  host on a bounded sample of the same workload (N=1 only)
+
+--dump-outputs DIR writes what the timed call computed (rank 0's sequence) as
+DIR/<name>.npy, so that two builds can be compared output for output:
+  trajectory          float64 [K,7]  camera pose the timed call wrote per step
+  state               float64 [N]    filter state after the last timed step
+  covariance_diag     float64 [N]    its covariance diagonal
+  covariance          [N,N]          the covariance, in its own dtype, if the
+                                     files stay within 64 MB; otherwise
+  covariance_rows     [r,N]          r rows of it chosen with a fixed seed and
+  covariance_row_index float64 [r]   their row numbers
 """
 from __future__ import annotations
 
@@ -40,6 +50,7 @@ sys.path.insert(0, str(REPO))
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_PEAK_TFLOPS = {"float32": 157.3, "float64": 78.6}     # dense matrix peaks
 INIT_POSE = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0])
+DUMP_BYTES = 64 << 20        # --dump-outputs: all files together
 
 
 def parse_args(argv=None):
@@ -62,7 +73,12 @@ def parse_args(argv=None):
                          "at their sustained level); 0 = none")
     ap.add_argument("--cpu-frames", type=int, default=12,
                     help="steady-state frames of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (trajectory, state and covariance after the last step) as "
+                         "DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.landmarks is None:
         args.landmarks = 400 if args.filter == "ekf_rotations" else 1024
     if args.visible is None:
@@ -154,6 +170,31 @@ def cpu_baseline(n, m, frames, model="ekf"):
         "fast_mode": dict(fast_all, cores=int(threads),
                           sample="same frames, rank-k update P - K(HP) through BLAS (2 N^2 k flops instead of 2 N^3)"),
     }, cams
+
+
+def dump_outputs(out_dir, hip, traj_timed):
+    """What the timed observe_sequence call hands its caller, as of its last step, into out_dir/<name>.npy (see the module
+    docstring); at most DUMP_BYTES in all.  Returns {name: shape}."""
+    import torch
+    hip.sync()
+    dims = hip.dims
+    traj = traj_timed.cpu().numpy()
+    arrays = {"trajectory": traj[-((DUMP_BYTES // 4) // traj[:1].nbytes):],     # (last rows only past 16 MB)
+              "state": hip.get_state(), "covariance_diag": hip.get_cov_diag()}
+    left = DUMP_BYTES - 4096 - sum(a.nbytes for a in arrays.values())        # (4 KB: the .npy headers)
+    cov = hip.cov_t[:dims, :dims]                # the covariance the filter holds (what get_cov() returns, own dtype)
+    row_bytes = dims * cov.element_size()
+    if dims * row_bytes <= left:
+        arrays["covariance"] = cov.cpu().numpy()
+    else:
+        rows = np.sort(np.random.default_rng(0).choice(dims, size=left // (row_bytes + 8), replace=False))
+        arrays["covariance_rows"] = cov[torch.from_numpy(rows).to(cov.device)].cpu().numpy()
+        arrays["covariance_row_index"] = rows.astype(np.float64)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def main():
@@ -254,6 +295,7 @@ def main():
     elapsed = time.perf_counter() - t0
     mode_ran = hip.last_sequence_mode()
     hip.sync()                        # status word of the filter: raises if any frame of the timed region failed
+    dumped = dump_outputs(args.dump_outputs, hip, timed_args[2]) if args.dump_outputs and rank == 0 else None
     per_rank = [k_steps / own_elapsed]
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -424,6 +466,8 @@ def main():
                                   "does (PCIe-inclusive)"},
         "outputs_finite": finite,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": str(args.dump_outputs), "arrays": dumped}
     if world == 1 and args.cpu_frames > 0:
         base, cpu_cams = cpu_baseline(n, m, args.cpu_frames, args.filter)
         out["cpu_baseline"] = base

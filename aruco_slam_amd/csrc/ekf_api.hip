@@ -48,6 +48,13 @@ constexpr int kStageSlots = 64;   // pinned host ring for ekf_observe
 constexpr int kMacroSuper = EKF_MACRO_SUPER;    // macro-tile covariance update: super-tiles of 8 x 8 macro tiles per XCD (ekf_cov_macro.hip)
 constexpr int kMacroMinTiles = 3000;   // ... chosen from this many 128 x 128 tiles of the lower triangle (n >= 3300 or so; measured: n=2048 1225 tiles 98 vs 80 us for the wave-per-tile kernel, n=4096 4753 tiles 290 vs 323)
 constexpr int kTimedKernels = 4;
+// Detections per frame that the gather kernel and the fused front kernel take; with EKF_FLAG_WIDE_FRAMES (flags bit 3) a
+// configuration may allow up to kWideVisible, and every frame beyond the cap runs through the wide-frame path
+// (ekf_wide.hip).  The rule depends on the model and m only, so a filter that grows into the wide range continues bit
+// for bit like one built large.
+constexpr int kWideVisible = 1024;
+inline int visible_cap(int model) { return model == EKF_MODEL_ROTATIONS ? 50 : 64; }
+inline bool wide_frame(int model, int m) { return m > visible_cap(model); }
 constexpr int kEventPool = 2048;  // frames of timing events kept before folding
 
 struct Layout {
@@ -58,6 +65,7 @@ struct Layout {
     size_t off_jac, off_resid, off_y, off_lmcol, off_amat, off_sblk, off_lmat, off_dinv, off_lop, off_dop, off_wpanel, off_wpanel2, off_cov2, off_wdbg,
         off_idx, off_z, off_status, off_stamps, off_covstats, off_dx, off_diag, off_xyz, off_unc,
         off_xl, off_done, off_sync, off_wsup, total;
+    size_t off_wwork, off_xinv;   // wide frames beyond the stage kernels' size: A -> W in f64 [kmax][cap], X = L_BB^-1 (0: none)
     int wsup_ld;      // row length of the compact support-column copy of W (pipelined sequence mode; two copies, by frame parity)
     bool has_cov2;
     size_t off_tiles; // launch order of the macro-tile covariance update (f32, large problems)
@@ -71,7 +79,9 @@ Layout make_layout(const ekf_config& c) {
     L.rd = c.model == EKF_MODEL_ROTATIONS ? 7 : 3;
     L.lmd = c.model == EKF_MODEL_ROTATIONS ? 10 : 3;
     L.cap = round_up((int64_t)L.lmd * c.max_landmarks + EKF_CAM, 128);
-    L.kmax = (int)round_up(L.rd * c.max_visible, EKF_RB);
+    // (a configuration that admits wide frames pads the rows to whole block columns of the blocked factorisation)
+    const bool wide = c.max_visible > visible_cap(c.model);
+    L.kmax = (int)round_up(L.rd * c.max_visible, wide ? EKF_WIDE_BLOCK : EKF_RB);
     L.elem = c.cov_dtype == EKF_COV_F32 ? 4 : 8;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t at = o; o += align256(bytes); return at; };
@@ -127,6 +137,9 @@ Layout make_layout(const ekf_config& c) {
                           ? tmax * (tmax + 1) / 2 + 8 * kMacroSuper * kMacroSuper : 0;
         L.off_tiles = take((size_t)L.tiles_cap * 4);
     }
+    // wide frames beyond the stage kernels' size (ekf_wide.hip); configurations within the caps keep their sizes
+    L.off_wwork = wide ? take((size_t)L.kmax * L.cap * 8) : 0;
+    L.off_xinv = wide ? take((size_t)EKF_WIDE_BLOCK * EKF_WIDE_BLOCK * 8) : 0;
     L.total = o;
     return L;
 }
@@ -136,8 +149,11 @@ int check_config(const ekf_config* c) {
     if (c->max_landmarks < 1) return fail(EKF_ERR_INVALID, "max_landmarks must be >= 1");
     if (c->model != EKF_MODEL_EKF && c->model != EKF_MODEL_ROTATIONS)
         return fail(EKF_ERR_INVALID, "unknown model");
-    if (c->max_visible < 1 || c->max_visible > (c->model == EKF_MODEL_ROTATIONS ? 50 : 64))
-        return fail(EKF_ERR_INVALID, "max_visible must be in 1..64 (1..50 for EKF_MODEL_ROTATIONS)");
+    if (c->max_visible < 1 || c->max_visible > ((c->flags & EKF_FLAG_WIDE_FRAMES) ? kWideVisible : visible_cap(c->model)))
+        return fail(EKF_ERR_INVALID, (c->flags & EKF_FLAG_WIDE_FRAMES)
+                                         ? "max_visible must be in 1..1024 (EKF_FLAG_WIDE_FRAMES)"
+                                         : "max_visible must be in 1..64 (1..50 for EKF_MODEL_ROTATIONS; up to 1024 with "
+                                           "EKF_FLAG_WIDE_FRAMES)");
     if (c->cov_dtype != EKF_COV_F64 && c->cov_dtype != EKF_COV_F32)
         return fail(EKF_ERR_INVALID, "cov_dtype must be EKF_COV_F64 or EKF_COV_F32");
     if (c->quat_mode != EKF_QUAT_AS_WRITTEN && c->quat_mode != EKF_QUAT_SCALAR_FIRST)
@@ -358,6 +374,25 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, in
             HIP_TRY(hipEventRecord(ev[1], f->stream));
             HIP_TRY(hipEventRecord(ev[2], f->stream));
         }
+    } else if (wide_frame(fr.model, m)) {
+        // Wide frame (ekf_wide.hip).  Timing slots: 0 = measurement, A and S; 1 = factorisation; 2 = W, dx and injection.
+        // Up to kpad = 384 the factorisation and W are the stage kernels; beyond, the blocked factorisation works on a
+        // copy of A (rows padded to whole block columns), so that A stays in `amat` (ekf_debug_fetch item 4).
+        const bool blocked = fr.kpad > EKF_WIDE_REUSE_ROWS;
+        const int rp = blocked ? (int)round_up(fr.k, EKF_WIDE_BLOCK) : fr.kpad;
+        double* aw = blocked ? f->at<double>(f->lay.off_wwork) : nullptr;
+        if (blocked && !f->lay.off_wwork) return fail(EKF_ERR_STATE, "internal: no wide-frame workspace");
+        if (f32) ekf_launch_wide_front<float>(fr, aw, rp, f->stream); else ekf_launch_wide_front<double>(fr, aw, rp, f->stream);
+        if (ev_all) HIP_TRY(hipEventRecord(ev[1], f->stream));
+        if (blocked) ekf_launch_wide_factor(fr, aw, f->at<double>(f->lay.off_xinv), rp, f->stream);
+        else ekf_launch_solve(fr, f->stream);
+        if (ev_all) HIP_TRY(hipEventRecord(ev[2], f->stream));
+        if (blocked) {
+            if (f32) ekf_launch_wide_finish<float>(fr, aw, f->stream); else ekf_launch_wide_finish<double>(fr, aw, f->stream);
+        } else {
+            if (f32) ekf_launch_panel<float>(fr, f->stream); else ekf_launch_panel<double>(fr, f->stream);
+        }
+        if (fr.model == 1) ekf_launch_inject_rot(fr, f->n_lm, f->stream);
     } else {
         if (f32) ekf_launch_gather<float>(fr, f->stream); else ekf_launch_gather<double>(fr, f->stream);
         if (ev_all) HIP_TRY(hipEventRecord(ev[1], f->stream));
@@ -372,8 +407,25 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, in
     if (!f->timing && hipEventRecord(f->ev_front, f->stream) == hipSuccess) f->front_pending = true;
     // the covariance update is timed by its own start / stop time stamps (what rocprofv3 reports), not by
     // events recorded around the launch (those also hold ~4 us of dispatch gap)
-    if (f32) ekf_launch_cov_update<float>(fr, variant, f->stream, ev ? ev[3] : nullptr, ev ? ev[4] : nullptr);
-    else ekf_launch_cov_update<double>(fr, variant, f->stream, ev ? ev[3] : nullptr, ev ? ev[4] : nullptr);
+    if (fr.kpad > EKF_WIDE_REUSE_ROWS) {
+        // W has more rows than the covariance-update kernels take: P <- P + Q - sum_c W_c^T W_c over row chunks of at most
+        // 384 rows, in order, Q with the first chunk only.  Every kernel variant computes each chunk with the same bits,
+        // so the sequence does too.  Timed by events around the launches (dispatch gaps included).
+        if (ev) HIP_TRY(hipEventRecord(ev[3], f->stream));
+        for (int r0 = 0; r0 < fr.kpad; r0 += EKF_WIDE_REUSE_ROWS) {
+            EkfFrame cf = fr;
+            cf.wpanel = static_cast<char*>(fr.wpanel) + (size_t)r0 * fr.ldw * f->lay.elem;
+            cf.kpad = std::min(EKF_WIDE_REUSE_ROWS, fr.kpad - r0);
+            cf.k = std::min(cf.kpad, std::max(0, fr.k - r0));
+            if (r0 > 0) cf.nz.q_cam = cf.nz.q_err = cf.nz.q_lm = 0.0;
+            if (f32) ekf_launch_cov_update<float>(cf, variant, f->stream); else ekf_launch_cov_update<double>(cf, variant, f->stream);
+        }
+        if (ev) HIP_TRY(hipEventRecord(ev[4], f->stream));
+    } else if (f32) {
+        ekf_launch_cov_update<float>(fr, variant, f->stream, ev ? ev[3] : nullptr, ev ? ev[4] : nullptr);
+    } else {
+        ekf_launch_cov_update<double>(fr, variant, f->stream, ev ? ev[3] : nullptr, ev ? ev[4] : nullptr);
+    }
     HIP_TRY(hipGetLastError());
     f->last_m = m;
     return EKF_OK;
@@ -812,7 +864,8 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
     // 32.5k at n=100 m=9)
     const bool auto_on = !(dims_now > 9000 && kpad_now > 96) && !(f->cfg.model == EKF_MODEL_ROTATIONS && kpad_now > 64);
     const bool want = (f->cfg.flags & 2) != 0 || ((f->cfg.flags & 1) == 0 && auto_on);
-    bool pipelined = want && f->lay.has_cov2 && !f->timing && frames >= 2 && (f->cfg.flags & 4) == 0 && kpad_now <= 192;
+    bool pipelined = want && f->lay.has_cov2 && !f->timing && frames >= 2 && (f->cfg.flags & 4) == 0 && kpad_now <= 192 &&
+                     !wide_frame(f->cfg.model, m);      // (wide frames run in serial order)
     if (pipelined && f->la_ok < 0) {
         // The device-side gates need the two streams on DIFFERENT hardware queues (HIP maps streams to a small pool
         // of queues): a gate that shares its queue with the launch it waits for would wait for ever.  Probe once: a

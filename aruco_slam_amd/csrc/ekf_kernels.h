@@ -127,6 +127,19 @@ __device__ __forceinline__ int ekf_lm_column(const EkfFrame& fr, int lmd, int j,
     return EKF_CAM + lmd * i;
 }
 
+// EKF model: the camera part of the state injection (extended_kalman_filter.py:138-152) once the additive part is done:
+// err = dx[7:10], x = the new camera position state[0:3].  Shared by the panel kernel and the wide-frame finish kernel.
+__device__ inline void ekf_inject_camera(const EkfFrame& fr, const double err[3], const double x[3]) {
+    double q[4] = {fr.state[3], fr.state[4], fr.state[5], fr.state[6]};
+    ekf_quat_inject(q, err, fr.quat_mode);
+    for (int i = 0; i < 4; ++i) fr.state[3 + i] = q[i];
+    for (int i = 0; i < 3; ++i) fr.state[7 + i] = 0.0;   // :152
+    if (fr.traj_row) {
+        fr.traj_row[0] = x[0]; fr.traj_row[1] = x[1]; fr.traj_row[2] = x[2];
+        for (int i = 0; i < 4; ++i) fr.traj_row[3 + i] = q[i];
+    }
+}
+
 // fused gather + solve + panel (+ injection); see ekf_front_impl.h
 template <typename T> void ekf_launch_front(const EkfFrame& fr, hipStream_t s);
 template <typename T> void ekf_launch_gather(const EkfFrame& fr, hipStream_t s);
@@ -145,6 +158,16 @@ int ekf_cov_macro_table(int T, int S, uint32_t* out, int capacity);
 void ekf_launch_gate(unsigned long long* counter, unsigned long long target, int32_t* status, hipStream_t s,
                      int max_polls = 1 << 22);
 void ekf_launch_signal(unsigned long long* counter, unsigned long long value, hipStream_t s);
+
+// Wide frames (ekf_wide.hip): more detections than the gather kernel takes (EKF m > 64, EKF_Rotations m > 50).
+// kpad <= EKF_WIDE_REUSE_ROWS: measurement, A and S (into `sblk`), then the stage solve / panel kernels.  Beyond: S into
+// `lmat`, blocked Cholesky over block columns of EKF_WIDE_BLOCK rows (rows padded to rp = k rounded up to that), with A
+// copied to `aw` [rp][lda] f64 and turned into W there; `xinv`: EKF_WIDE_BLOCK^2 doubles.
+#define EKF_WIDE_REUSE_ROWS 384
+#define EKF_WIDE_BLOCK 64
+template <typename T> void ekf_launch_wide_front(const EkfFrame& fr, double* aw, int rp, hipStream_t s);
+void ekf_launch_wide_factor(const EkfFrame& fr, double* aw, double* xinv, int rp, hipStream_t s);
+template <typename T> void ekf_launch_wide_finish(const EkfFrame& fr, const double* aw, hipStream_t s);
 
 template <typename T>
 void ekf_launch_add_markers(void* cov, int64_t ld, double* state, int32_t dims,

@@ -287,15 +287,8 @@ __global__ __launch_bounds__(64) void ekf_panel_mfma_kernel(EkfFrame fr) {
         const double e0 = __shfl(part, 7), e1 = __shfl(part, 8), e2 = __shfl(part, 9);
         const double x0 = __shfl(nv, 0), x1 = __shfl(nv, 1), x2 = __shfl(nv, 2);
         if (lane == 0) {
-            double q[4] = {fr.state[3], fr.state[4], fr.state[5], fr.state[6]};
-            const double err[3] = {e0, e1, e2};
-            ekf_quat_inject(q, err, fr.quat_mode);
-            for (int i = 0; i < 4; ++i) fr.state[3 + i] = q[i];
-            for (int i = 0; i < 3; ++i) fr.state[7 + i] = 0.0;   // :152
-            if (fr.traj_row) {
-                fr.traj_row[0] = x0; fr.traj_row[1] = x1; fr.traj_row[2] = x2;
-                for (int i = 0; i < 4; ++i) fr.traj_row[3 + i] = q[i];
-            }
+            const double err[3] = {e0, e1, e2}, x[3] = {x0, x1, x2};
+            ekf_inject_camera(fr, err, x);
         }
     }
 }

@@ -17,6 +17,7 @@ from ._build import LIB_PATH
 
 EKF_COV_F64, EKF_COV_F32 = 0, 1
 EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST = 0, 1
+EKF_FLAG_WIDE_FRAMES = 8       # ekf_config.flags bit 3: up to 1024 detections per frame
 EKF_COVK_AUTO, EKF_COVK_VALU, EKF_COVK_MFMA, EKF_COVK_MFMA_TILE, EKF_COVK_MFMA_MACRO = 0, 1, 2, 3, 4
 
 # every symbol include/ekf_slam_hip.h declares
@@ -133,7 +134,9 @@ class HipEkf:
     """One filter instance = one C handle + the torch tensors it borrows."""
 
     KERNEL_NAMES = ("gather", "solve", "panel", "cov_update")
-    MAX_VISIBLE_LIMIT = {3: 64, 10: 50}      # detections per frame the kernels take (by landmark width: EKF / EKF_Rotations)
+    # detections per frame (by landmark width: EKF / EKF_Rotations).  Beyond 64 (50) a frame runs through the wide-frame
+    # path (EKF_FLAG_WIDE_FRAMES, set in every configuration made here: grow() carries it along in self.cfg)
+    MAX_VISIBLE_LIMIT = {3: 1024, 10: 1024}
 
     def __init__(self, max_landmarks: int, max_visible: int, cov_dtype="float64",
                  quat_mode="as_written", cov_kernel="auto", device="cuda:0", noise=None,
@@ -157,6 +160,7 @@ class HipEkf:
         cfg.flags = {None: 0, False: 1, True: 2}[lookahead]   # None: pipelined sequence mode where it wins (by size); False: never; True: always
         if not fused:
             cfg.flags |= 4        # separate gather / solve / panel launches
+        cfg.flags |= EKF_FLAG_WIDE_FRAMES
         self.fused = bool(fused)  # ("force" of earlier versions == True: there is no automatic fallback any more)
         self._last_m = 1
         cfg.model = {"ekf": 0, "ekf_rotations": 1}[model]

@@ -48,6 +48,8 @@ enum { EKF_MODEL_EKF = 0, EKF_MODEL_ROTATIONS = 1 };
  * one wave per 32 x 32 tile, and for the f32 covariance from 3000 tiles of 128 x 128 (n >= 3300 or so) one workgroup per
  * 128 x 128 macro tile with LDS-staged operands; MFMA_TILE / MFMA_MACRO force one of the two (tests, measurements; MACRO:
  * f32 only).  All of them give the same bits as the VALU reference kernel. */
+/* ekf_config.flags bit 3: more than 64 (EKF_MODEL_ROTATIONS: 50) detections per frame, up to 1024 */
+enum { EKF_FLAG_WIDE_FRAMES = 8 };
 enum { EKF_COVK_AUTO = 0, EKF_COVK_VALU = 1, EKF_COVK_MFMA = 2, EKF_COVK_MFMA_TILE = 3, EKF_COVK_MFMA_MACRO = 4 };
 
 enum {
@@ -63,7 +65,9 @@ enum {
 typedef struct ekf_config {
     int32_t max_landmarks;  /* capacity n_max */
     int32_t max_visible;    /* max observations per frame (<= 64; <= 50 for EKF_MODEL_ROTATIONS: k = 7 m <= 350 rows; beyond k = 192
-                             * the frame runs through the stage kernels, in serial order) */
+                             * the frame runs through the stage kernels, in serial order).  With EKF_FLAG_WIDE_FRAMES (flags
+                             * bit 3): <= 1024 for both models (k <= 3072 / 7168 rows); a frame with more than 64 (50)
+                             * detections then runs through the wide-frame path, in serial order, whatever else is set */
     int32_t cov_dtype;      /* EKF_COV_F64 / EKF_COV_F32 */
     int32_t quat_mode;      /* EKF_QUAT_* */
     int32_t cov_kernel;     /* EKF_COVK_*: covariance-update kernel */
@@ -77,7 +81,11 @@ typedef struct ekf_config {
                              * (ekf_query_sizes: + ld^2 elements).  One handle per process pipelines at a time
                              * (ekf_last_sequence_mode).
                              * bit 2: run gather / solve / panel as three separate launches instead of the fused front
-                             * kernel (same results, bit for bit; no pipelined mode).  bit 3 is ignored. */
+                             * kernel (same results, bit for bit; no pipelined mode).
+                             * bit 3 (EKF_FLAG_WIDE_FRAMES): max_visible may be up to 1024 (see there); the workspace
+                             * of such a configuration also holds an f64 copy of A = H (P+Q) that frames with more than
+                             * 384 rows turn into W (ekf_query_sizes: + 8 kmax ld bytes).  Without it, sizes and
+                             * limits are as before. */
     /* noise constants, defaults = extended_kalman_filter.py:21-27 */
     double initial_camera_uncertainty;   /* 0.1  */
     double initial_landmark_uncertainty; /* 0.7  */
@@ -189,7 +197,8 @@ int ekf_sync(ekf_filter *f);
 int ekf_set_fused(ekf_filter *f, int32_t enable);
 
 /* Per-kernel device timing with HIP events on the handle's stream.
- * which: 0 gather, 1 solve, 2 panel, 3 covariance update.
+ * which: 0 gather, 1 solve, 2 panel, 3 covariance update.  Wide frames: 0 measurement, A and S; 1 factorisation;
+ * 2 W, dx and injection; 3 covariance update (beyond 384 rows: all of its row-chunk launches, events around them).
  * enable: 0 off, 1 all four kernels (5 events per frame), 2 covariance update only
  * (2 events per frame: least perturbation of the pipeline).
  * ekf_get_kernel_timing synchronises, returns the mean duration [us] and the
@@ -199,7 +208,9 @@ int ekf_get_kernel_timing(ekf_filter *f, int32_t which, double *mean_us, int64_t
 
 /* Last frame's intermediates as host f64 (tests): what = 0 Jacobian blocks
  * [k,13], 1 residual [k], 2 Cholesky factor L [kpad,kpad], 3 whitened panel
- * W = L^-1 H P [kpad,dims], 4 A = H (P+Q) [k,dims].  `count` = capacity of out. */
+ * W = L^-1 H P [kpad,dims], 4 A = H (P+Q) [k,dims].  `count` = capacity of out.
+ * Items 2 and 3 need ekf_debug_fetch(f, -1, ..) before the frame (item 2 always holds L after a wide frame of more
+ * than 384 rows: the blocked factorisation works in place there); all five are valid after a wide frame. */
 int ekf_debug_fetch(ekf_filter *f, int32_t what, double *out, size_t count);
 
 /* Detection -> pose front end, batched (replaces the per-marker loop of cv2.solvePnP(..., SOLVEPNP_IPPE_SQUARE) in

@@ -213,6 +213,14 @@ struct ekf_filter {
     int ev_frames = 0;
     double t_sum_us[kTimedKernels] = {};
     int64_t t_cnt[kTimedKernels] = {};
+    // log replay (ekf_observe_log): pinned staging of the landmark indices, first-sighting slots and empty-frame rows, two
+    // buffers used by turns (a call waits only for the call before the previous one), each reused once the stream has passed
+    // its `log_pin_done`; what the last call did
+    char* log_pin[2] = {};
+    size_t log_pin_bytes[2] = {};
+    hipEvent_t log_pin_done[2] = {};
+    int log_pin_turn = 0;
+    int64_t log_stats[4] = {};
 
     int dims() const { return lay.lmd * n_lm + EKF_CAM; }
     template <typename P> P* at(size_t off) const { return reinterpret_cast<P*>(ws + off); }
@@ -489,6 +497,175 @@ int sync_and_check(ekf_filter* f, int state_count = 0) {
     return EKF_OK;
 }
 
+// Pipelined sequence mode for a frame of this size (ekf_observe_sequence_device; the log replay asks per frame), before the
+// frame count, the hardware-queue probe and the one-handle token.  Flags bit 1 forces it, bit 0 forbids it, otherwise it is
+// chosen where it was measured to win.  MFMA covariance update (f32 or f64) and the fused front kernel only.
+// tools/mode_select.py (profiles/r03_mode_select.txt: 2000 frames per call after a warm-up call, start-to-start of the
+// front kernels on the device clock, pipelined / serial in us per frame): n=32 m=3 11.1 / 16.1 - n=64 m=8 12.5 / 18.5 -
+// n=128 m=16 15.5 / 21.7 - C2 (n=256 m=16 f64) 15.9 / 21.5 - n=512 m=32 22.8 / 31.6 - n=1024 m=32 24.2 / 39.3: it wins at
+// every shape down to the smallest.  (Round 2's soak tool had it slower at C2: its timed region began with the handle's
+// very first pipelined call, which holds the one-time queue self-test.)  tools/pipeline_sweep.py, larger shapes:
+// n=1024 m=64 81.8 / 95.1 - n=2048 m=32 61.7 / 73.3 - n=2048 m=64 115.7 / 152.4 - n=4096 m=32 237 / 238 - n=4096 m=64
+// 398 / 371: there the front kernel's 273 workgroups hold every CU while they wait for the factorisation, and the update
+// cannot run beside them.
+bool pipeline_wanted(const ekf_filter* f, int dims, int kpad, int m) {
+    // (measured, profiles/r03_mode_select.txt.  EKF model: pipelined wins everywhere except N > 9000 with k > 96, where the front
+    // kernel's workgroups and the macro-tile update cannot share CUs.  EKF_Rotations: its chunks complete 10 + 10 m support rows
+    // per frame in the pipelined form; from k = 91 (m = 13) on the serial order is faster: 28.2k vs 24.3k updates/s at n=100
+    // m=13, 25.5k vs 16.4k at m=16, 15.7k vs 12.7k at n=200 m=21, 9.3k vs 9.1k at n=400 m=27; below, pipelined: 41.0k vs
+    // 32.5k at n=100 m=9)
+    const bool auto_on = !(dims > 9000 && kpad > 96) && !(f->cfg.model == EKF_MODEL_ROTATIONS && kpad > 64);
+    const bool want = (f->cfg.flags & 2) != 0 || ((f->cfg.flags & 1) == 0 && auto_on);
+    return want && f->lay.has_cov2 && !f->timing && (f->cfg.flags & 4) == 0 && kpad <= 192 &&
+           !wide_frame(f->cfg.model, m);      // (wide frames run in serial order)
+}
+
+// The device-side gates need the two streams on DIFFERENT hardware queues (HIP maps streams to a small pool
+// of queues): a gate that shares its queue with the launch it waits for would wait for ever.  Probe once: a
+// gate on the internal stream, the matching signal on the handle's stream, a short poll budget.
+// HIP deals its hardware queues to streams as they are created, so when the probe fails a FRESH internal stream usually
+// sits on another queue: up to eight are tried before the handle settles for the serial order.
+int probe_queues(ekf_filter* f) {
+    if (f->la_ok >= 0) return EKF_OK;
+    unsigned long long* probe = f->at<unsigned long long>(f->lay.off_sync) + 2;
+    int32_t* pstat = f->at<int32_t>(f->lay.off_sync) + 8;
+    f->la_ok = 0;
+    for (int attempt = 0; attempt < 8 && f->la_ok == 0; ++attempt) {
+        if (attempt > 0) {
+            hipStream_t fresh = nullptr;
+            HIP_TRY(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
+            HIP_TRY(hipStreamSynchronize(f->big));
+            (void)hipStreamDestroy(f->big);
+            f->big = fresh;
+        }
+        HIP_TRY(hipMemsetAsync(probe, 0, 64, f->stream));
+        HIP_TRY(hipStreamSynchronize(f->stream));
+        ekf_launch_gate(probe, 1ull, pstat, f->big, 1 << 14);
+        ekf_launch_signal(probe, 1ull, f->stream);
+        HIP_TRY(hipStreamSynchronize(f->big));
+        HIP_TRY(hipStreamSynchronize(f->stream));
+        int32_t ps = 0;
+        HIP_TRY(hipMemcpy(&ps, pstat, 4, hipMemcpyDeviceToHost));
+        f->la_ok = (ps == 0) ? 1 : 0;
+    }
+    return EKF_OK;
+}
+
+// one pipelining handle per process (see g_pipelining): take the token, or take it over from a handle whose streams
+// have drained; false: run in serial order
+bool take_pipelining_token(ekf_filter* f) {
+    ekf_filter* owner = nullptr;
+    if (!g_pipelining.compare_exchange_strong(owner, f) && owner != f) {
+        bool idle = hipStreamQuery(owner->stream) == hipSuccess && hipStreamQuery(owner->big) == hipSuccess;
+        (void)hipGetLastError();      // (hipErrorNotReady is not an error here)
+        if (!(idle && g_pipelining.compare_exchange_strong(owner, f))) return false;
+    }
+    return true;
+}
+
+// One frame of a pipelined run: its detections (device), their number, its trajectory row (or null).
+struct RunFrame {
+    const int32_t* idx;
+    const double* z;
+    int m;
+    double* traj_row;
+};
+
+// A run of `frames` >= 2 frames in the pipelined sequence mode; frame_at(t) describes frame t.  Every frame of a run has the
+// same state dimension and the same kpad (rows rounded up to EKF_RB): a front kernel completes its support rows from the
+// previous frame's W over ITS OWN kpad rows (ekf_front_impl.h: the S-block and chunk completions), and the support-column
+// copy W_sup the previous frame leaves behind is [kpad][wsup_ld].  The number of detections may differ from frame to
+// frame: next_m is separate from m, and the LDS claim and the grid are taken per frame.
+// The covariance starts in `cur` and ping-pongs with `other`.  With an odd number of frames it ends in `other`:
+// copy_back = true copies it into `cur` (ekf_observe_sequence_device: the caller's buffer), otherwise *end_buf says where
+// it is.  Advances la_base by `frames`.
+// One frame is a serial chain on one P, but the front kernel F(t+1) needs of P_{t+1}
+// only its support rows (camera + the landmarks of frame t+1's detections), and those follow from P_t and W_t:
+//     P_{t+1}[r][c] = (P_t[r][c] + Q[r == c]) + sum_k fma(-W_t[k][r], W_t[k][c])
+// -- per element the instruction sequence of the covariance update, so the bits are the same.  The covariance
+// therefore ping-pongs between two buffers: C(t) reads buf[t & 1] (P_t) and writes buf[(t + 1) & 1]; F(t+1) runs
+// BESIDE C(t) on the other stream, reads P_t from buf[t & 1] and W_t, and completes the entries it needs itself
+// (S-block workgroups: from the compact support columns W_sup the chunks of F(t) left behind; chunk workgroups:
+// on the matrix cores).  Nothing on the critical path F(t) -> F(t+1) waits for a covariance update.
+//   stream A (the handle's):  F(0) - F(1) - F(2) - ... - F(last) - C(last)
+//   stream B (internal)    :  gate - C(0) - signal - gate - C(1) - signal ...
+// Edges between the streams are ordered on the device (an event pair costs ~13 us per edge):
+//   F(t) complete   -> C(t) may start (it reads W_t and overwrites the buffer F(t) read, P_{t-1}): F(t+1) stores
+//                      "t+1 started" when it starts (it follows F(t) on stream A); a one-wave gate kernel in front
+//                      of C(t) polls that counter (the last update of a call follows its front kernel on stream A);
+//   C(t-1) complete -> F(t+1) may read buf[t & 1] and overwrite W_{t-1}: a one-thread kernel behind C(t-1) bumps a
+//                      second counter; F(t) does not finish before it has seen it (its measurement workgroup polls
+//                      at its end), and F(t+1) follows F(t) on stream A.
+// Kernel boundaries on each stream give the memory ordering; the counters only carry "that launch is over".
+// Every wait is bounded.  The front kernel claims (almost) all LDS of its CUs while its grid is small, so the
+// covariance update's workgroups run on the other CUs instead of next to the pivot chain.
+template <class FrameAt>
+int run_pipelined(ekf_filter* f, int frames, FrameAt frame_at, void* cur, void* other, bool copy_back, void** end_buf) {
+    const Layout& L = f->lay;
+    int rc = ensure_tiles(f);
+    if (rc) return rc;
+    void* wbuf[2] = {f->at<void>(L.off_wpanel), f->at<void>(L.off_wpanel2)};
+    void* cbuf[2] = {cur, other};
+    char* wsup0 = f->at<char>(L.off_wsup);
+    void* wsup[2] = {wsup0, wsup0 + (size_t)L.kmax * L.wsup_ld * L.elem};
+    unsigned long long* sync = f->at<unsigned long long>(L.off_sync);
+    int32_t* status = f->at<int32_t>(L.off_status);
+    const uint64_t base = f->la_base;
+    // (stream B needs no edge from stream A at the start: its first launch is the gate in front of C(0), which waits
+    // for "F(1) has started", i.e. for everything that is on stream A now and F(0); the previous run ended with
+    // stream A waiting for stream B)
+    RunFrame nx = frame_at(0);
+    for (int t = 0; t < frames; ++t) {
+        const int par = t & 1;
+        const RunFrame cf_t = nx;
+        EkfFrame fr = make_frame(f, cf_t.idx, cf_t.z, cf_t.m, cf_t.traj_row);
+        fr.cov = cbuf[0];
+        fr.wpanel = wbuf[par];
+        if (t > 0) {                                           // P_{t-1} + the completion from W_{t-1}
+            fr.cov = cbuf[par ^ 1];
+            fr.wprev = wbuf[par ^ 1];
+            fr.wsup_prev = wsup[par ^ 1];
+        }
+        const int nb = fr.kpad / EKF_RB;
+        const int grid = nb * (nb + 1) / 2 + 2 + fr.ncols / 64;
+        fr.wsup_ld = L.wsup_ld;
+        fr.la_sync = sync;
+        fr.la_signal = (t > 0) ? base + (uint64_t)t : 0;       // "F(t) has started": F(t-1) is complete
+        fr.la_gate = (t > 0) ? base + (uint64_t)t : 0;         // C(t-1) complete before F(t) ends
+        fr.lds_min = grid <= 100 ? 148 * 1024 : 0;
+        if (t + 1 < frames) {                                  // the next frame's detections: its support columns of W_t
+            nx = frame_at(t + 1);
+            fr.next_idx = nx.idx;
+            fr.next_m = nx.m;
+            fr.wsup = wsup[par];
+        }
+        bind_exchange(f, fr);
+        if (L.elem == 4) ekf_launch_front<float>(fr, f->stream); else ekf_launch_front<double>(fr, f->stream);
+        EkfFrame cu = fr;
+        cu.cov = cbuf[par];
+        cu.cov_out = cbuf[par ^ 1];
+        if (t + 1 < frames) {
+            ekf_launch_gate(sync, base + (uint64_t)t + 1, status, f->big);
+            if (L.elem == 4) ekf_launch_cov_update<float>(cu, 2, f->big); else ekf_launch_cov_update<double>(cu, 2, f->big);
+            ekf_launch_signal(sync + 1, base + (uint64_t)t + 1, f->big);
+        } else {
+            // The LAST update of the run goes on the handle's stream, straight behind its front kernel: stream order says
+            // that F(t) is over, and F(t) did not finish before it had seen C(t-1) complete (its end gate) -- no gate, no
+            // signal, and nothing to join afterwards (4 device-side hops of ~1.2 us per call).  The counters keep the
+            // values of frame t - 1; the next run's waits are for values beyond base + frames, which its own launches set.
+            if (L.elem == 4) ekf_launch_cov_update<float>(cu, 2, f->stream); else ekf_launch_cov_update<double>(cu, 2, f->stream);
+            // an odd number of frames leaves the covariance in the other buffer
+            if ((frames & 1) && copy_back)
+                HIP_TRY(hipMemcpyAsync(cbuf[0], cbuf[1], (size_t)L.cap * L.cap * L.elem, hipMemcpyDeviceToDevice, f->stream));
+        }
+        HIP_TRY(hipGetLastError());
+        f->last_m = cf_t.m;
+    }
+    if (end_buf) *end_buf = ((frames & 1) && !copy_back) ? cbuf[1] : cbuf[0];
+    f->la_base = base + (uint64_t)frames;
+    return EKF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -601,6 +778,10 @@ int ekf_destroy(ekf_filter* f) {
     if (f->pinned) (void)hipHostFree(f->pinned);
     if (f->readback) (void)hipHostFree(f->readback);
     if (f->tiles_host) (void)hipHostFree(f->tiles_host);
+    for (int i = 0; i < 2; ++i) {
+        if (f->log_pin_done[i]) (void)hipEventDestroy(f->log_pin_done[i]);
+        if (f->log_pin[i]) (void)hipHostFree(f->log_pin[i]);
+    }
     delete f;
     return EKF_OK;
 }
@@ -845,72 +1026,22 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
     if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
     if (!lm_index_dev || !z_dev) return fail(EKF_ERR_INVALID, "NULL detections");
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
-    // Pipelined mode (F(t+1) beside C(t), see below): flags bit 1 forces it, bit 0 forbids it, otherwise it is chosen where it
-    // was measured to win.  MFMA covariance update (f32 or f64) and the fused front kernel only.
-    // tools/mode_select.py (profiles/r03_mode_select.txt: 2000 frames per call after a warm-up call, start-to-start of the
-    // front kernels on the device clock, pipelined / serial in us per frame): n=32 m=3 11.1 / 16.1 - n=64 m=8 12.5 / 18.5 -
-    // n=128 m=16 15.5 / 21.7 - C2 (n=256 m=16 f64) 15.9 / 21.5 - n=512 m=32 22.8 / 31.6 - n=1024 m=32 24.2 / 39.3: it wins at
-    // every shape down to the smallest.  (Round 2's soak tool had it slower at C2: its timed region began with the handle's
-    // very first pipelined call, which holds the one-time queue self-test.)  tools/pipeline_sweep.py, larger shapes:
-    // n=1024 m=64 81.8 / 95.1 - n=2048 m=32 61.7 / 73.3 - n=2048 m=64 115.7 / 152.4 - n=4096 m=32 237 / 238 - n=4096 m=64
-    // 398 / 371: there the front kernel's 273 workgroups hold every CU while they wait for the factorisation, and the update
-    // cannot run beside them.
+    // Pipelined mode (F(t+1) beside C(t), see run_pipelined): the rule is pipeline_wanted's
     const int dims_now = f->dims();
     const int kpad_now = (int)round_up(f->lay.rd * m, EKF_RB);
-    // (measured, profiles/r03_mode_select.txt.  EKF model: pipelined wins everywhere except N > 9000 with k > 96, where the front
-    // kernel's workgroups and the macro-tile update cannot share CUs.  EKF_Rotations: its chunks complete 10 + 10 m support rows
-    // per frame in the pipelined form; from k = 91 (m = 13) on the serial order is faster: 28.2k vs 24.3k updates/s at n=100
-    // m=13, 25.5k vs 16.4k at m=16, 15.7k vs 12.7k at n=200 m=21, 9.3k vs 9.1k at n=400 m=27; below, pipelined: 41.0k vs
-    // 32.5k at n=100 m=9)
-    const bool auto_on = !(dims_now > 9000 && kpad_now > 96) && !(f->cfg.model == EKF_MODEL_ROTATIONS && kpad_now > 64);
-    const bool want = (f->cfg.flags & 2) != 0 || ((f->cfg.flags & 1) == 0 && auto_on);
-    bool pipelined = want && f->lay.has_cov2 && !f->timing && frames >= 2 && (f->cfg.flags & 4) == 0 && kpad_now <= 192 &&
-                     !wide_frame(f->cfg.model, m);      // (wide frames run in serial order)
-    if (pipelined && f->la_ok < 0) {
-        // The device-side gates need the two streams on DIFFERENT hardware queues (HIP maps streams to a small pool
-        // of queues): a gate that shares its queue with the launch it waits for would wait for ever.  Probe once: a
-        // gate on the internal stream, the matching signal on the handle's stream, a short poll budget.
-        // HIP deals its hardware queues to streams as they are created, so when the probe fails a FRESH internal stream usually
-        // sits on another queue: up to eight are tried before the handle settles for the serial order.
-        unsigned long long* probe = f->at<unsigned long long>(f->lay.off_sync) + 2;
-        int32_t* pstat = f->at<int32_t>(f->lay.off_sync) + 8;
-        f->la_ok = 0;
-        for (int attempt = 0; attempt < 8 && f->la_ok == 0; ++attempt) {
-            if (attempt > 0) {
-                hipStream_t fresh = nullptr;
-                HIP_TRY(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
-                HIP_TRY(hipStreamSynchronize(f->big));
-                (void)hipStreamDestroy(f->big);
-                f->big = fresh;
-            }
-            HIP_TRY(hipMemsetAsync(probe, 0, 64, f->stream));
-            HIP_TRY(hipStreamSynchronize(f->stream));
-            ekf_launch_gate(probe, 1ull, pstat, f->big, 1 << 14);
-            ekf_launch_signal(probe, 1ull, f->stream);
-            HIP_TRY(hipStreamSynchronize(f->big));
-            HIP_TRY(hipStreamSynchronize(f->stream));
-            int32_t ps = 0;
-            HIP_TRY(hipMemcpy(&ps, pstat, 4, hipMemcpyDeviceToHost));
-            f->la_ok = (ps == 0) ? 1 : 0;
-        }
+    bool pipelined = pipeline_wanted(f, dims_now, kpad_now, m) && frames >= 2;
+    if (pipelined) {
+        rc = probe_queues(f);
+        if (rc) return rc;
     }
     f->seq_mode = EKF_SEQ_SERIAL;
     if (pipelined && f->la_ok == 0) {
         pipelined = false;
         f->seq_mode = EKF_SEQ_SERIAL_ONE_QUEUE;
     }
-    if (pipelined) {
-        // one pipelining handle per process (see g_pipelining): take the token, or take it over from a handle whose streams
-        // have drained, or run this call in serial order
-        ekf_filter* owner = nullptr;
-        if (!g_pipelining.compare_exchange_strong(owner, f) && owner != f) {
-            bool idle = hipStreamQuery(owner->stream) == hipSuccess && hipStreamQuery(owner->big) == hipSuccess;
-            (void)hipGetLastError();      // (hipErrorNotReady is not an error here)
-            if (!(idle && g_pipelining.compare_exchange_strong(owner, f))) {
-                pipelined = false;
-                f->seq_mode = EKF_SEQ_SERIAL_OTHER_HANDLE;
-            }
-        }
+    if (pipelined && !take_pipelining_token(f)) {
+        pipelined = false;
+        f->seq_mode = EKF_SEQ_SERIAL_OTHER_HANDLE;
     }
     if (!pipelined) {
         for (int t = 0; t < frames; ++t) {
@@ -920,88 +1051,238 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
         }
         return EKF_OK;
     }
-    // Pipelined sequence mode.  One frame is a serial chain on one P, but the front kernel F(t+1) needs of P_{t+1}
-    // only its support rows (camera + the landmarks of frame t+1's detections), and those follow from P_t and W_t:
-    //     P_{t+1}[r][c] = (P_t[r][c] + Q[r == c]) + sum_k fma(-W_t[k][r], W_t[k][c])
-    // -- per element the instruction sequence of the covariance update, so the bits are the same.  The covariance
-    // therefore ping-pongs between two buffers: C(t) reads buf[t & 1] (P_t) and writes buf[(t + 1) & 1]; F(t+1) runs
-    // BESIDE C(t) on the other stream, reads P_t from buf[t & 1] and W_t, and completes the entries it needs itself
-    // (S-block workgroups: from the compact support columns W_sup the chunks of F(t) left behind; chunk workgroups:
-    // on the matrix cores).  Nothing on the critical path F(t) -> F(t+1) waits for a covariance update.
-    //   stream A (the handle's):  F(0) - F(1) - F(2) - ... - F(last) - C(last)
-    //   stream B (internal)    :  gate - C(0) - signal - gate - C(1) - signal ...
-    // Edges between the streams are ordered on the device (an event pair costs ~13 us per edge):
-    //   F(t) complete   -> C(t) may start (it reads W_t and overwrites the buffer F(t) read, P_{t-1}): F(t+1) stores
-    //                      "t+1 started" when it starts (it follows F(t) on stream A); a one-wave gate kernel in front
-    //                      of C(t) polls that counter (the last update of a call follows its front kernel on stream A);
-    //   C(t-1) complete -> F(t+1) may read buf[t & 1] and overwrite W_{t-1}: a one-thread kernel behind C(t-1) bumps a
-    //                      second counter; F(t) does not finish before it has seen it (its measurement workgroup polls
-    //                      at its end), and F(t+1) follows F(t) on stream A.
-    // Kernel boundaries on each stream give the memory ordering; the counters only carry "that launch is over".
-    // Every wait is bounded.  The front kernel claims (almost) all LDS of its CUs while its grid is small, so the
-    // covariance update's workgroups run on the other CUs instead of next to the pivot chain.
-    const Layout& L = f->lay;
-    rc = ensure_tiles(f);
+    const int rd = f->lay.rd;
+    rc = run_pipelined(
+        f, frames,
+        [&](int t) {
+            return RunFrame{lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd, m,
+                            trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr};
+        },
+        f->cov, f->at<void>(f->lay.off_cov2), true, nullptr);
     if (rc) return rc;
-    void* wbuf[2] = {f->at<void>(L.off_wpanel), f->at<void>(L.off_wpanel2)};
-    void* cbuf[2] = {f->cov, f->at<void>(L.off_cov2)};
-    char* wsup0 = f->at<char>(L.off_wsup);
-    void* wsup[2] = {wsup0, wsup0 + (size_t)L.kmax * L.wsup_ld * L.elem};
-    unsigned long long* sync = f->at<unsigned long long>(L.off_sync);
-    int32_t* status = f->at<int32_t>(L.off_status);
-    const uint64_t base = f->la_base;
-    const int nb_now = (int)round_up(L.rd * m, EKF_RB) / EKF_RB;
-    const int grid_now = nb_now * (nb_now + 1) / 2 + 2 + (int)round_up(f->dims(), 128) / 64;
-    const int la_lds = grid_now <= 100 ? 148 * 1024 : 0;
-    // (stream B needs no edge from stream A at the start: its first launch is the gate in front of C(0), which waits
-    // for "F(1) has started", i.e. for everything that is on stream A now and F(0); the previous call ended with
-    // stream A waiting for stream B)
-    for (int t = 0; t < frames; ++t) {
-        const int par = t & 1;
-        EkfFrame fr = make_frame(f, lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * L.rd, m,
-                                 trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr);
-        fr.wpanel = wbuf[par];
-        if (t > 0) {                                           // P_{t-1} + the completion from W_{t-1}
-            fr.cov = cbuf[par ^ 1];
-            fr.wprev = wbuf[par ^ 1];
-            fr.wsup_prev = wsup[par ^ 1];
-        }
-        fr.wsup_ld = L.wsup_ld;
-        fr.la_sync = sync;
-        fr.la_signal = (t > 0) ? base + (uint64_t)t : 0;       // "F(t) has started": F(t-1) is complete
-        fr.la_gate = (t > 0) ? base + (uint64_t)t : 0;         // C(t-1) complete before F(t) ends
-        fr.lds_min = la_lds;
-        if (t + 1 < frames) {                                  // the next frame's detections: its support columns of W_t
-            fr.next_idx = lm_index_dev + (size_t)(t + 1) * m;
-            fr.next_m = m;
-            fr.wsup = wsup[par];
-        }
-        bind_exchange(f, fr);
-        if (L.elem == 4) ekf_launch_front<float>(fr, f->stream); else ekf_launch_front<double>(fr, f->stream);
-        EkfFrame cf = fr;
-        cf.cov = cbuf[par];
-        cf.cov_out = cbuf[par ^ 1];
-        if (t + 1 < frames) {
-            ekf_launch_gate(sync, base + (uint64_t)t + 1, status, f->big);
-            if (L.elem == 4) ekf_launch_cov_update<float>(cf, 2, f->big); else ekf_launch_cov_update<double>(cf, 2, f->big);
-            ekf_launch_signal(sync + 1, base + (uint64_t)t + 1, f->big);
-        } else {
-            // The LAST update of the call runs on the handle's stream, straight behind its front kernel: stream order says
-            // that F(t) is over, and F(t) did not finish before it had seen C(t-1) complete (its end gate) -- no gate, no
-            // signal, and nothing to join afterwards (4 device-side hops of ~1.2 us per call).  The counters keep the
-            // values of frame t - 1; the next call's waits are for values beyond base + frames, which its own launches set.
-            if (L.elem == 4) ekf_launch_cov_update<float>(cf, 2, f->stream); else ekf_launch_cov_update<double>(cf, 2, f->stream);
-            // an odd number of frames leaves the covariance in the internal buffer: back into the caller's
-            if (frames & 1)
-                HIP_TRY(hipMemcpyAsync(f->cov, cbuf[1], (size_t)L.cap * L.cap * L.elem, hipMemcpyDeviceToDevice, f->stream));
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    f->la_base = base + (uint64_t)frames;
     f->seq_mode = EKF_SEQ_PIPELINED;
     f->front_pending = false;
     f->status_clean = false;       // (gate kernels raise status bits without the host word)
     f->last_m = m;
+    return EKF_OK;
+}
+
+// ---- log replay (BaseFilter.process_detections over a whole log): ekf_observe_log ---------------------------------------
+// log_ws: [z of every detection, rd doubles each | landmark indices [D] | first-sighting slots [<= D]]
+static size_t log_off_idx(int rd, int64_t D) { return align256((size_t)D * rd * 8); }
+static size_t log_off_slots(int rd, int64_t D) { return log_off_idx(rd, D) + align256((size_t)D * 4); }
+static size_t log_total(int rd, int64_t D) { return std::max<size_t>(256, log_off_slots(rd, D) + align256((size_t)D * 4)); }
+
+int ekf_log_workspace_bytes(const ekf_filter* f, int64_t detections, size_t* bytes) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!bytes || detections < 0) return fail(EKF_ERR_INVALID, "bad log size request");
+    *bytes = log_total(f->lay.rd, detections);
+    return EKF_OK;
+}
+
+int ekf_last_log_stats(const ekf_filter* f, int64_t out[4]) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
+    for (int i = 0; i < 4; ++i) out[i] = f->log_stats[i];
+    return EKF_OK;
+}
+
+int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames, const double* poses_dev,
+                    void* log_ws, size_t log_ws_bytes, double* trajectory_dev) {
+    int rc = check_ready(f);
+    if (rc) return rc;
+    // ---- validation on the host: nothing is enqueued before the whole log has passed
+    if (frames < 0) return fail(EKF_ERR_INVALID, "negative frame count");
+    if (frames > 0 && !offsets) return fail(EKF_ERR_INVALID, "offsets is NULL");
+    if (frames > 0 && offsets[0] != 0) return fail(EKF_ERR_INVALID, "offsets[0] must be 0");
+    for (int t = 0; t < frames; ++t)
+        if (offsets[t + 1] < offsets[t]) return fail(EKF_ERR_INVALID, "offsets must be non-decreasing");
+    const int64_t D = frames > 0 ? offsets[frames] : 0;
+    const int rd = f->lay.rd, lmd = f->lay.lmd;
+    if (D > 0 && (!lm_index || !poses_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
+    if (D > 0 && (!log_ws || log_ws_bytes < log_total(rd, D)))
+        return fail(EKF_ERR_INVALID, "log workspace missing or smaller than ekf_log_workspace_bytes");
+    if (D > 0 && (reinterpret_cast<uintptr_t>(log_ws) & 0xFF)) return fail(EKF_ERR_INVALID, "log workspace must be 256-byte aligned");
+    // per frame: first new slot, number of new landmarks; first sightings are numbered n, n+1, ... in order of occurrence
+    std::vector<int32_t> slots;
+    std::vector<int64_t> new_at((size_t)frames + 1, 0);
+    int n = f->n_lm;
+    int64_t max_m = 0;
+    for (int t = 0; t < frames; ++t) {
+        new_at[t] = (int64_t)slots.size();
+        for (int64_t d = offsets[t]; d < offsets[t + 1]; ++d) {
+            const int32_t i = lm_index[d];
+            if (i < 0) return fail(EKF_ERR_INVALID, "negative landmark index in the log");
+            if (i == n) {
+                slots.push_back((int32_t)d);
+                ++n;
+            } else if (i > n) {
+                return fail(EKF_ERR_INVALID, "landmark index beyond the next free one (first sightings must be numbered "
+                                             "n, n+1, ... in order of first occurrence)");
+            }
+        }
+        max_m = std::max<int64_t>(max_m, offsets[t + 1] - offsets[t]);
+    }
+    new_at[frames] = (int64_t)slots.size();
+    if (n > f->cfg.max_landmarks) return fail(EKF_ERR_CAPACITY, "the log needs more landmarks than max_landmarks");
+    if (max_m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "a frame of the log has more detections than max_visible");
+    for (int i = 0; i < 4; ++i) f->log_stats[i] = 0;
+    if (frames == 0) return EKF_OK;
+
+    // ---- host staging: [indices | slots | (row, source) pairs of empty frames: those before the first stepped frame of the
+    // call (source: the state now), the others (source: the row of the last stepped frame before them)]
+    std::vector<int32_t> lead, rest;
+    {
+        int last = -1;
+        for (int t = 0; t < frames; ++t) {
+            if (offsets[t + 1] > offsets[t]) last = t;
+            else if (trajectory_dev) {
+                std::vector<int32_t>& v = last < 0 ? lead : rest;
+                v.push_back(t);
+                v.push_back(last);
+            }
+        }
+    }
+    const size_t up_bytes = log_off_slots(rd, D) - log_off_idx(rd, D) + slots.size() * 4;
+    const size_t pin_need = align256(up_bytes) + align256(lead.size() * 4) + align256(rest.size() * 4) + 256;
+    const int turn = f->log_pin_turn;
+    if (!f->log_pin_done[turn]) HIP_TRY(hipEventCreateWithFlags(&f->log_pin_done[turn], hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(f->log_pin_done[turn]));      // (the staging of the call before the previous one is consumed)
+    if (pin_need > f->log_pin_bytes[turn]) {
+        if (f->log_pin[turn]) (void)hipHostFree(f->log_pin[turn]);
+        f->log_pin[turn] = nullptr;
+        f->log_pin_bytes[turn] = 0;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&f->log_pin[turn]), pin_need, hipHostMallocDefault));
+        f->log_pin_bytes[turn] = pin_need;
+    }
+    char* pin = f->log_pin[turn];
+    int32_t* pin_lead = reinterpret_cast<int32_t*>(pin + align256(up_bytes));
+    int32_t* pin_rest = reinterpret_cast<int32_t*>(pin + align256(up_bytes) + align256(lead.size() * 4));
+    char* ws = static_cast<char*>(log_ws);
+    double* z_all = reinterpret_cast<double*>(ws);
+    const int32_t* idx_all = reinterpret_cast<const int32_t*>(ws + log_off_idx(rd, D));
+    const int32_t* slots_all = reinterpret_cast<const int32_t*>(ws + log_off_slots(rd, D));
+    if (D > 0) {
+        std::memcpy(pin, lm_index, (size_t)D * 4);
+        if (!slots.empty()) std::memcpy(pin + (log_off_slots(rd, D) - log_off_idx(rd, D)), slots.data(), slots.size() * 4);
+    }
+    if (!lead.empty()) std::memcpy(pin_lead, lead.data(), lead.size() * 4);
+    if (!rest.empty()) std::memcpy(pin_rest, rest.data(), rest.size() * 4);
+
+    // ---- which frames may pipeline, in one pass: a run is >= 2 consecutive stepped frames that pipeline_wanted admits, of
+    // one kpad, none but the first with a first sighting (the front kernel clamps next-frame indices >= n_lm, and the new rows
+    // exist in neither covariance buffer).  candidate[t]: frame t may be in a run; joins[t]: it continues the run of the
+    // stepped frame before it.
+    std::vector<char> candidate((size_t)frames, 0), joins((size_t)frames, 0);
+    bool want_runs = false;
+    {
+        int prev_kpad = -1;          // kpad of the previous stepped frame if it was a candidate, else -1
+        int nn = f->n_lm;
+        for (int t = 0; t < frames; ++t) {
+            const int m = (int)(offsets[t + 1] - offsets[t]);
+            if (m == 0) continue;
+            const int nnew = (int)(new_at[t + 1] - new_at[t]);
+            nn += nnew;
+            const int kpad = (int)round_up(rd * m, EKF_RB);
+            candidate[t] = pipeline_wanted(f, lmd * nn + EKF_CAM, kpad, m);
+            joins[t] = candidate[t] && nnew == 0 && prev_kpad == kpad;
+            want_runs = want_runs || joins[t];
+            prev_kpad = candidate[t] ? kpad : -1;
+        }
+    }
+    bool pipe_ok = false;
+    if (want_runs) {
+        rc = probe_queues(f);
+        if (rc) return rc;
+        pipe_ok = f->la_ok == 1 && take_pipelining_token(f);
+    }
+
+    // ---- device work, all on the handle's stream (the pipelined runs use the internal one as ekf_observe_sequence_device)
+    f->front_pending = false;
+    f->mirror_fresh = false;
+    if (D > 0) {
+        HIP_TRY(hipMemcpyAsync(ws + log_off_idx(rd, D), pin, up_bytes, hipMemcpyHostToDevice, f->stream));
+        ekf_launch_log_prepare(poses_dev, D, rd, z_all, f->stream);
+    }
+    if (!lead.empty()) ekf_launch_log_fill_rows(trajectory_dev, pin_lead, (int32_t)(lead.size() / 2), f->state, f->stream);
+    // The covariance ping-pongs between the caller's buffer and the second one across runs: a run with an odd number of
+    // frames leaves it in the other buffer, and everything after it (serial frames, first sightings, the next run) works
+    // there; one copy at the end of the call brings it back.
+    void* const home = f->cov;
+    void* const spare = f->lay.has_cov2 ? f->at<void>(f->lay.off_cov2) : nullptr;
+    std::vector<int> run;
+    auto frame_of = [&](int t) {
+        const int64_t d0 = offsets[t];
+        return RunFrame{idx_all + d0, z_all + (size_t)d0 * rd, (int)(offsets[t + 1] - d0),
+                        trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr};
+    };
+    auto serial = [&](int t) {
+        const RunFrame r = frame_of(t);
+        f->log_stats[0] += 1;
+        return enqueue_frame(f, r.idx, r.z, r.m, r.traj_row, false);
+    };
+    auto flush = [&]() -> int {
+        int frc = EKF_OK;
+        if (run.size() == 1) {
+            frc = serial(run[0]);
+        } else if (run.size() >= 2) {
+            void* cur = f->cov;
+            void* end = cur;
+            frc = run_pipelined(f, (int)run.size(), [&](int i) { return frame_of(run[i]); }, cur, cur == home ? spare : home,
+                                false, &end);
+            f->cov = end;
+            f->log_stats[0] += (int64_t)run.size();
+            f->log_stats[1] += (int64_t)run.size();
+            f->log_stats[2] += 1;
+            f->status_clean = false;       // (gate kernels raise status bits without the host word)
+        }
+        run.clear();
+        return frc;
+    };
+    for (int t = 0; t < frames && rc == EKF_OK; ++t) {
+        const int m = (int)(offsets[t + 1] - offsets[t]);
+        if (m == 0) continue;                    // not stepped (no predict); its trajectory row is filled below
+        const int nnew = (int)(new_at[t + 1] - new_at[t]);
+        if (nnew > 0) {
+            // the run before ends first; the frame's new landmarks see the camera the previous frame left on the device
+            rc = flush();
+            if (rc) break;
+            if (f->lay.elem == 4)
+                ekf_launch_log_add_markers<float>(f->cfg.model, f->cov, f->ld, f->state, f->dims(), poses_dev,
+                                                  slots_all + new_at[t], f->cfg.initial_landmark_uncertainty, nnew, f->stream);
+            else
+                ekf_launch_log_add_markers<double>(f->cfg.model, f->cov, f->ld, f->state, f->dims(), poses_dev,
+                                                   slots_all + new_at[t], f->cfg.initial_landmark_uncertainty, nnew, f->stream);
+            f->n_lm += nnew;
+            f->log_stats[3] += nnew;
+        }
+        if (pipe_ok && candidate[t]) {
+            if (!joins[t]) rc = flush();
+            if (rc == EKF_OK) run.push_back(t);
+        } else {
+            rc = flush();
+            if (rc == EKF_OK) rc = serial(t);
+        }
+    }
+    if (rc == EKF_OK) rc = flush();
+    if (f->cov != home) {
+        // (also on an error: the caller's buffer is the filter's covariance again)
+        hipError_t e = hipMemcpyAsync(home, f->cov, (size_t)f->lay.cap * f->lay.cap * f->lay.elem, hipMemcpyDeviceToDevice,
+                                      f->stream);
+        f->cov = home;
+        if (e != hipSuccess && rc == EKF_OK) rc = fail(EKF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+    }
+    if (rc == EKF_OK && !rest.empty())
+        ekf_launch_log_fill_rows(trajectory_dev, pin_rest, (int32_t)(rest.size() / 2), f->state, f->stream);
+    // A state getter after the call must wait for the whole call (the last frame's state may come from a pipelined run, whose
+    // front kernels record no event): no shortcut through the event of an earlier serial frame of the call.
+    f->front_pending = false;
+    f->mirror_fresh = false;
+    // (the staging may be reused once the stream is here -- also after an error: its copy may have been enqueued)
+    f->log_pin_turn = turn ^ 1;
+    HIP_TRY(hipEventRecord(f->log_pin_done[turn], f->stream));
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
     return EKF_OK;
 }
 
@@ -1131,6 +1412,13 @@ int ekf_set_cov(ekf_filter* f, const double* cov, int32_t dims) {
     const Layout& L = f->lay;
     HIP_TRY(hipStreamSynchronize(f->stream));
     HIP_TRY(hipMemset(f->cov, 0, (size_t)L.cap * L.cap * L.elem));
+    // ... and the second covariance buffer of the pipelined mode: it may hold entries of a larger map from earlier frames,
+    // and what lies beyond the state dimension must be zero in both buffers (an odd pipelined run copies or leaves the
+    // whole second buffer as the covariance; new landmarks only write their diagonal)
+    if (L.has_cov2) {
+        HIP_TRY(hipStreamSynchronize(f->big));
+        HIP_TRY(hipMemset(f->at<void>(L.off_cov2), 0, (size_t)L.cap * L.cap * L.elem));
+    }
     // symmetrise on upload: the kernels keep P bitwise symmetric from then on
     if (L.elem == 8) {
         std::vector<double> tmp((size_t)dims * dims);

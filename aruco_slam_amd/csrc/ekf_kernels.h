@@ -177,6 +177,14 @@ void ekf_launch_inject_rot(const EkfFrame& fr, int n_lm, hipStream_t s);
 template <typename T>
 void ekf_launch_add_markers_rot(void* cov, int64_t ld, double* state, int32_t dims, const double* pose6_dev,
                                 const double* unc_dev, double default_unc, int32_t count, hipStream_t s);
+// Log replay (ekf_log.hip, ekf_observe_log): z of every detection of the log from its pose [count][6] (rd = 3: pose[0:3];
+// rd = 7: [pose[0:3] | quaternion of the xyz Euler angles pose[3:6], scalar first]); first sightings gathered from the
+// logged poses by slot (default uncertainty); trajectory rows of empty frames from pinned (row, source) pairs.
+void ekf_launch_log_prepare(const double* poses_dev, int64_t count, int rd, double* z_dev, hipStream_t s);
+template <typename T>
+void ekf_launch_log_add_markers(int model, void* cov, int64_t ld, double* state, int32_t dims, const double* poses_dev,
+                                const int32_t* slots_dev, double default_unc, int32_t count, hipStream_t s);
+void ekf_launch_log_fill_rows(double* traj_dev, const int32_t* pairs, int32_t count, const double* state, hipStream_t s);
 template <typename T>
 void ekf_launch_cov_diag(const void* cov, int64_t ld, double* out_dev, int32_t count, hipStream_t s);
 

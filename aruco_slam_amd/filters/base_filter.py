@@ -13,6 +13,7 @@ per-marker solvePnP that follows it is one batched HIP kernel
 from __future__ import annotations
 
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -53,6 +54,58 @@ def dictionary_size(aruco_dict) -> int:
         return ARUCO_DICT_SIZES[int(aruco_dict)]
     except (KeyError, TypeError, ValueError):
         return ARUCO_DICT_SIZES[DEFAULT_ARUCO_DICT]
+
+
+class DetectionLogPlan(NamedTuple):
+    index: np.ndarray          # int32 [D'] landmark index of every detection that is replayed
+    offsets: np.ndarray        # int64 [F+1] frame boundaries in `index` (frames without detections are empty)
+    keep: np.ndarray           # bool [D] rows of the input log that are replayed
+    new_landmarks: dict        # marker id -> landmark index of the ids the log adds, in order of first occurrence
+    num_landmarks: int         # landmarks after the log
+    widest: int                # most detections in one frame
+
+
+def plan_detection_log(landmarks, num_landmarks, ids, offsets, has_detections=None) -> DetectionLogPlan:
+    """Host side of ``process_detection_log``: check the CSR log and map marker ids to landmark indices as ``observe`` does
+    frame by frame (known ids keep their index, new ones are numbered ``num_landmarks``, ``+1``, ... in order of first
+    occurrence, duplicates of a new id inside its frame share its index).  ``landmarks`` is not modified.  Raises
+    ``ValueError`` for a malformed log."""
+    offsets = np.asarray(offsets)
+    if offsets.ndim != 1 or offsets.shape[0] < 1 or (offsets.size > 1 and offsets.dtype.kind not in "iu"):
+        raise ValueError("offsets must be a 1-D integer array of F+1 entries")
+    offsets = offsets.astype(np.int64)
+    ids = np.asarray(ids).reshape(-1)
+    if ids.size and ids.dtype.kind not in "iu":
+        raise ValueError("ids must be integers")
+    frames = offsets.shape[0] - 1
+    counts = np.diff(offsets)
+    if offsets[0] != 0 or (counts < 0).any():
+        raise ValueError("offsets must start at 0 and be non-decreasing")
+    if offsets[-1] != ids.shape[0]:
+        raise ValueError(f"offsets[-1] = {int(offsets[-1])} but there are {ids.shape[0]} ids")
+    if has_detections is None:
+        has = counts > 0
+    else:
+        has = np.asarray(has_detections, dtype=bool).reshape(-1)
+        if has.shape[0] != frames:
+            raise ValueError(f"has_detections must have {frames} entries")
+    empty = np.nonzero(has & (counts == 0))[0]
+    if empty.size:
+        raise ValueError(f"frame {int(empty[0])} has detections but no ids: observe() needs at least one detection")
+    keep = np.repeat(has, counts)
+    counts = np.where(has, counts, 0)
+    new, n = {}, int(num_landmarks)
+    index = np.empty(int(counts.sum()), dtype=np.int32)
+    for k, marker in enumerate(ids[keep].tolist()):
+        j = landmarks.get(marker)
+        if j is None:
+            j = new.get(marker)
+            if j is None:
+                j = new[marker] = n
+                n += 1
+        index[k] = j
+    return DetectionLogPlan(index, np.concatenate(([0], np.cumsum(counts))).astype(np.int64), keep, new, n,
+                            int(counts.max()) if frames else 0)
 
 
 class BaseFilter:
@@ -140,6 +193,42 @@ class BaseFilter:
             _, marker_poses = self.get_poses()
             camera_pose = self.get_cam_estimate(iteration)
         return None, camera_pose, marker_poses, detected_poses
+
+    def process_detection_log(self, ids, poses, offsets, has_detections=None) -> np.ndarray:
+        """``process_detections(ids_t, poses_t)`` with ``should_filter=True`` for every frame of a recorded log, in ONE call
+        that runs predict / update of every frame on the device (ekf_observe_log).  The log is a CSR batch as in a replay
+        file (``main/run_slam.py: detection_frames``): ``ids [D]``, ``poses [D,6]`` ``[tvec | rvec]`` (NumPy, or a
+        float64 tensor on the filter's device), ``offsets [F+1]``, ``has_detections [F]`` (None: every non-empty frame).
+        A frame without detections is not stepped.  Marker ids are mapped to landmark indices here (``plan_detection_log``);
+        the buffers grow first if the log needs more landmarks or detections per frame.  Returns the camera pose
+        ``state[0:7]`` after every frame, ``(F, 7)``.  A malformed log raises ``ValueError`` before anything runs, and the
+        filter (``landmarks`` included) is left as it was."""
+        import torch
+        backend = self.backend
+        plan = plan_detection_log(self.landmarks, self.num_landmarks, ids, offsets, has_detections)
+        if isinstance(poses, torch.Tensor):
+            if not poses.is_cuda or poses.device != backend.device:
+                raise ValueError(f"poses must be on {backend.device} (got {poses.device})")
+            if poses.dtype != torch.float64:
+                raise ValueError("poses must be float64")
+        else:
+            poses = np.asarray(poses, dtype=np.float64)
+        if tuple(poses.shape) != (plan.keep.shape[0], 6):
+            raise ValueError(f"poses must have shape ({plan.keep.shape[0]}, 6), got {tuple(poses.shape)}")
+        if not plan.keep.all():      # (rows of frames without detections, if there are any, are not part of the replay)
+            poses = poses[torch.from_numpy(plan.keep).to(poses.device)] if isinstance(poses, torch.Tensor) else poses[plan.keep]
+        if isinstance(poses, torch.Tensor):
+            poses = poses.contiguous()
+        if plan.num_landmarks > backend.max_landmarks:
+            backend.grow(plan.num_landmarks)
+        if plan.widest > backend.max_visible:
+            backend.grow(new_max_visible=min(backend.MAX_VISIBLE_LIMIT[backend.lm_dims], plan.widest))
+        traj = torch.empty((plan.offsets.shape[0] - 1, 7), dtype=torch.float64, device=backend.device)
+        backend.observe_log(plan.index, plan.offsets, poses, traj)
+        backend.sync()
+        self.landmarks.update(plan.new_landmarks)
+        self.num_landmarks = plan.num_landmarks
+        return traj.cpu().numpy()
 
     def save_map(self, filename: str) -> None:
         """Map text format of base_filter.py:214-247: three comment lines and a

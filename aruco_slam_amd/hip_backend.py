@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "ekf_get_cov", "ekf_set_state", "ekf_set_cov", "ekf_num_landmarks", "ekf_sync",
     "ekf_set_fused", "ekf_set_kernel_timing", "ekf_get_kernel_timing", "ekf_debug_fetch",
     "ekf_estimate_poses_device", "ekf_estimate_poses", "ekf_last_error_string",
+    "ekf_log_workspace_bytes", "ekf_observe_log", "ekf_last_log_stats",
 )
 
 
@@ -94,6 +95,9 @@ def load_library(path: str | Path | None = None):
         "ekf_debug_fetch": [vp, C.c_int32, dp, C.c_size_t],
         "ekf_estimate_poses_device": [vp, C.c_int32, C.c_double, dp, dp, C.c_int32, vp, vp],
         "ekf_estimate_poses": [dp, C.c_int32, C.c_double, dp, dp, C.c_int32, dp, vp],
+        "ekf_log_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],
+        "ekf_observe_log": [vp, ip, C.POINTER(C.c_int64), C.c_int32, vp, vp, C.c_size_t, vp],
+        "ekf_last_log_stats": [vp, C.POINTER(C.c_int64)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -273,6 +277,60 @@ class HipEkf:
         self._check(self.lib.ekf_observe_sequence_device(
             self.h, idx_t.data_ptr(), z_t.data_ptr(), m, frames,
             traj_t.data_ptr() if traj_t is not None else None))
+
+    def observe_log(self, lm_index, offsets, poses, traj=None):
+        """A whole detection log in one call (ekf_observe_log): lm_index int [D] landmark index of every detection (first
+        sightings numbered n, n+1, ... in order of first occurrence), offsets int [F+1], poses [D,6] ``[tvec | rvec]`` as a
+        NumPy array (uploaded once) or a contiguous float64 device tensor on this filter's device; traj: float64 device
+        tensor [F,7] that receives state[0:7] after every frame, or None.  Capacity must already suffice (grow() first)."""
+        torch = self._torch
+        idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offs.shape[0] < 1:
+            raise ValueError("offsets needs F+1 >= 1 entries")
+        frames = offs.shape[0] - 1
+        if isinstance(poses, torch.Tensor):
+            if not (poses.is_cuda and poses.device == self.device):
+                raise ValueError(f"poses must be on {self.device} (got {poses.device})")
+            if poses.dtype != torch.float64 or not poses.is_contiguous():
+                raise ValueError("poses must be a contiguous float64 tensor")
+        else:
+            poses = np.ascontiguousarray(poses, dtype=np.float64)
+        if tuple(poses.shape) != (idx.shape[0], 6):
+            raise ValueError(f"poses must have shape ({idx.shape[0]}, 6), got {tuple(poses.shape)}")
+        if traj is not None:
+            assert traj.is_cuda and traj.dtype == torch.float64 and traj.is_contiguous()
+            assert tuple(traj.shape) == (frames, 7)
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_log_workspace_bytes(self.h, idx.shape[0], C.byref(nbytes)))
+        # device tensors of the caller (poses, traj) were produced on its current stream
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            # (allocated and uploaded on the filter's stream: the caching allocator keeps them until it has passed them)
+            if isinstance(poses, torch.Tensor):
+                poses.record_stream(self.stream)
+                poses_t = poses
+            else:
+                poses_t = torch.from_numpy(poses).to(self.device, non_blocking=False)
+            ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
+            if traj is not None:
+                traj.record_stream(self.stream)
+            self._check(self.lib.ekf_observe_log(
+                self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), frames,
+                poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(), nbytes.value,
+                traj.data_ptr() if traj is not None else None))
+        self._log_keep = (poses_t, ws)     # (released by the next call; record_stream already guards the allocator)
+        m = np.diff(offs)
+        if m.size and m.max() > 0:
+            self._last_m = int(m[m > 0][-1])
+
+    LOG_STATS = ("frames_stepped", "frames_pipelined", "pipelined_runs", "markers_added")
+
+    def last_log_stats(self) -> dict:
+        """What the last observe_log call did (ekf_last_log_stats)."""
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.ekf_last_log_stats(self.h, out))
+        return dict(zip(self.LOG_STATS, (int(v) for v in out)))
 
     SEQUENCE_MODES = {0: "none", 1: "serial", 2: "pipelined", 3: "serial (the two streams share one hardware queue)",
                       4: "serial (another handle of the process is pipelining)"}

@@ -3,14 +3,18 @@
 
     python -m aruco_slam_amd.main.run_slam --video input_video.mp4 --filter ekf
     python -m aruco_slam_amd.main.run_slam --detections tests/golden/c1_detections.npz
+    python -m aruco_slam_amd.main.run_slam --detections tests/golden/c1_detections.npz --resident
 
 Same CLI (``--video``, ``--filter``), same outputs (``outputs/trajectory.txt``
 one line per frame, ``outputs/map.txt`` at exit).  The image has no OpenCV and
 no video, so frames can also come from a detections replay file
 (``--detections``): per frame a timestamp and the ``(ids, poses)`` the ArUco
 front-end would have produced (``ids`` absent on frames without detections, in
-which case the filter is not stepped -- base_filter.py:197-204).  The 2-D/3-D
-viewers are GUI code and are not part of this package.
+which case the filter is not stepped -- base_filter.py:197-204).  With
+``--resident`` the whole replay runs on the device in one call
+(``process_detection_log``) and the outputs are written afterwards, byte for
+byte what the frame-by-frame loop writes.  The 2-D/3-D viewers are GUI code
+and are not part of this package.
 """
 from __future__ import annotations
 
@@ -53,6 +57,20 @@ def detection_frames(path: str):
         yield float(det["timestamps_ms"][f]), ids, det["poses"][sl]
 
 
+def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryWriter) -> None:
+    """The whole replay file through ``process_detection_log``, then one trajectory line per frame.  Frames before the first
+    stepped one carry the camera pose the filter had before the call (the integer initial pose of a fresh filter), as the
+    frame-by-frame loop writes them."""
+    det = np.load(path, allow_pickle=False)
+    offsets, has = det["offsets"], det["has_detections"].astype(bool)
+    start_pose = tracker.get_poses()[0]
+    traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has)
+    stepped = has & (np.diff(offsets) > 0)
+    first = int(np.argmax(stepped)) if stepped.any() else len(has)
+    for f, timestamp in enumerate(det["timestamps_ms"]):
+        cam_traj_writer.write(float(timestamp), start_pose if f < first else traj[f])
+
+
 def main(cmdline_args: argparse.Namespace) -> None:
     initial_pose = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0])     # run_slam.py:85-88 (int64)
     tracker = init_tracker(cmdline_args.filter, initial_pose,
@@ -60,8 +78,13 @@ def main(cmdline_args: argparse.Namespace) -> None:
     out_dir = Path(getattr(cmdline_args, "output_dir", "outputs"))
     out_dir.mkdir(parents=True, exist_ok=True)
 
+    resident = getattr(cmdline_args, "resident", False)
+    if resident and not cmdline_args.detections:
+        raise ValueError("--resident replays a detections file: pass --detections <replay.npz>")
     with TrajectoryWriter(str(out_dir / "trajectory.txt")) as cam_traj_writer:
-        if cmdline_args.detections:
+        if resident:
+            replay_resident(tracker, cmdline_args.detections, cam_traj_writer)
+        elif cmdline_args.detections:
             for timestamp, ids, poses in detection_frames(cmdline_args.detections):
                 _, camera_pose, _, _ = tracker.process_detections(ids, poses)
                 cam_traj_writer.write(timestamp, camera_pose)
@@ -89,6 +112,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--detections", type=str, default=None,
                         help="replay file with pre-computed ArUco detections (.npz)")
     parser.add_argument("--output-dir", dest="output_dir", type=str, default="outputs")
+    parser.add_argument("--resident", action="store_true",
+                        help="with --detections: replay the whole file on the device in one call")
     return parser
 
 

@@ -103,3 +103,23 @@ def small_sequence(frames: int = 200, markers: int = 10, max_visible: int = 6,
         poses[:, 3:6] = rng.normal(0.0, 0.05, size=(m, 3))
         out.append((ts, marker_ids[pick].astype(np.int32), poses))
     return out
+
+
+def ragged_log(n: int, m_range, steady_frames: int, seed: int = 0, bootstrap_m: int | None = None, noise: float = 0.01,
+               rvec_sigma: float = 0.0) -> dict:
+    """A seeded ragged detection log in the layout of a replay file (``main/run_slam.py: detection_frames``): a bootstrap
+    segment that first-sights all ``n`` landmarks, ``bootstrap_m`` per frame (default: the top of ``m_range``), then
+    ``steady_frames`` frames that each see ``m ~ U[m_range]`` distinct landmarks.  Returns ids [D], poses [D,6],
+    offsets [F+1], has_detections [F] and the number of bootstrap frames."""
+    lo, hi = int(m_range[0]), int(m_range[1])
+    stream = SyntheticStream(n, min(n, bootstrap_m or hi), seed=seed, noise=noise, rvec_sigma=rvec_sigma)
+    frames = list(stream.bootstrap())
+    boot = len(frames)
+    for _ in range(steady_frames):
+        m = int(stream.rng.integers(lo, hi + 1))
+        frames.append(stream._observe(np.sort(stream.rng.choice(n, m, replace=False))))
+    counts = np.array([len(ids) for ids, _ in frames], dtype=np.int64)
+    return {"ids": np.concatenate([ids for ids, _ in frames]).astype(np.int32),
+            "poses": np.concatenate([p for _, p in frames]),
+            "offsets": np.concatenate(([0], np.cumsum(counts))).astype(np.int64),
+            "has_detections": counts > 0, "bootstrap_frames": boot}

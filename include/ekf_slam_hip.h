@@ -172,6 +172,42 @@ int ekf_observe_sequence_device(ekf_filter *f, const int32_t *lm_index_dev,
 enum { EKF_SEQ_NONE = 0, EKF_SEQ_SERIAL = 1, EKF_SEQ_PIPELINED = 2, EKF_SEQ_SERIAL_ONE_QUEUE = 3, EKF_SEQ_SERIAL_OTHER_HANDLE = 4 };
 int ekf_last_sequence_mode(const ekf_filter *f);
 
+/* Log replay: BaseFilter.process_detections with should_filter=True over a whole recorded log in one call
+ * (base_filter.py:196-212, extended_kalman_filter.py:58-156, ekf_with_rotations.py:66-181).  EKF_MODEL_EKF: the same bits
+ * as the per-frame ekf_add_markers / ekf_observe loop; EKF_MODEL_ROTATIONS: z is formed on the device, and its quaternion
+ * may differ from the host's in the last place (device sin / cos).
+ *
+ * ekf_log_workspace_bytes: device scratch a log of `detections` detections needs (caller-owned, like the workspace).
+ *
+ * ekf_observe_log:
+ *   lm_index [D]   HOST  landmark index of every detection, frame after frame.  An index >= the number of landmarks at the
+ *                        start of its frame is a first sighting; first sightings must be numbered n, n+1, ... in order of
+ *                        first occurrence (the Python id -> index dict assigns them).  Duplicates within a frame are legal.
+ *   offsets [F+1]  HOST  offsets[0] = 0, non-decreasing, offsets[F] = D.  An empty frame is NOT stepped (no predict); its
+ *                        trajectory row repeats the previous one (the camera state at the call for the first frames).
+ *   poses_dev [D,6] DEVICE  [tvec | rvec] exactly as logged; valid until the handle's stream has consumed it.
+ *   log_ws         DEVICE  256-byte aligned, ekf_log_workspace_bytes(D); valid until the stream has consumed it.
+ *   trajectory_dev [F,7] DEVICE or NULL  state[0:7] after every frame.
+ * Everything is validated on the host before anything is enqueued: a bad log returns EKF_ERR_INVALID, a log that needs more
+ * landmarks or more detections per frame than the buffers hold EKF_ERR_CAPACITY, and the filter is left untouched (the
+ * library never grows inside the call: ekf_grow first).
+ * Device work, on the handle's stream: one copy of the indices, one prepare kernel (z of the whole log), then frame after
+ * frame.  A frame with first sightings adds them with one gather launch, reading the camera state the previous frame left.
+ * Consecutive frames that the rule of ekf_observe_sequence_device would pipeline on their own, with one kpad (3 m or 7 m
+ * rounded up to 16) and no first sighting but in the first, run in the pipelined mode as one run; a first sighting or a
+ * change of kpad ends the run.  Wide frames and frames the rule keeps serial run in serial order.  Like every observe call,
+ * a frame whose tile count of the macro-tile covariance update (f32, 3000 tiles or more: state dimension >= ~9 700)
+ * differs from the last one synchronises the stream once, to rebuild the launch table.
+ * The host side stages the indices in pinned memory, two buffers used by turns: a call returns once its work is enqueued, and
+ * only waits for the device to have finished the call before the previous one.  A getter after the call waits for all of
+ * it (there is no shortcut through an earlier frame's event). */
+int ekf_log_workspace_bytes(const ekf_filter *f, int64_t detections, size_t *bytes);
+int ekf_observe_log(ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames,
+                    const double *poses_dev, void *log_ws, size_t log_ws_bytes, double *trajectory_dev);
+/* What the last ekf_observe_log did: out[0] frames stepped, out[1] frames run in the pipelined mode, out[2] pipelined runs,
+ * out[3] landmarks added. */
+int ekf_last_log_stats(const ekf_filter *f, int64_t out[4]);
+
 /* EKF.get_poses / get_lm_uncertainties (extended_kalman_filter.py:84-93).
  * Synchronise and copy to host.  ekf_get_camera / ekf_get_state directly after ekf_observe / ekf_observe_device wait
  * for the part of that frame that produces the state (and the status word) only -- the front kernel leaves the state in a

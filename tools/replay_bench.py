@@ -1,0 +1,121 @@
+"""Replay throughput: a seeded ragged synthetic log (synthetic.ragged_log: a bootstrap segment that first-sights every
+landmark, then steady frames with m ~ U[m_lo, m_hi]) through three entry points, one JSON line each:
+
+    per_frame   BaseFilter.process_detections, one frame at a time (the host round trip per frame)
+    log         BaseFilter.process_detection_log, the bootstrap segment in one call, the steady segment in another
+    sequence    HipEkf.observe_sequence at a fixed m = the mean m of the log (rectangular block, for reference)
+
+updates/s is steady frames per second of the steady segment; the bootstrap segment is reported separately.
+
+    python tools/replay_bench.py --n 1024 --m 24 40 --steady 2000 --dtype float32     # C3-like
+    python tools/replay_bench.py --n 256 --m 8 24 --steady 2000 --dtype float64       # C2-like
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+INIT = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0])
+
+
+def _segment(log, t0, t1):
+    offs = log["offsets"]
+    d0, d1 = int(offs[t0]), int(offs[t1])
+    return log["ids"][d0:d1], log["poses"][d0:d1], offs[t0:t1 + 1] - d0, log["has_detections"][t0:t1]
+
+
+def _filter(args):
+    from aruco_slam_amd.filters.extended_kalman_filter import EKF
+    return EKF(INIT, max_landmarks=args.n, max_visible=args.m[1], cov_dtype=args.dtype)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--n", type=int, default=1024)
+    ap.add_argument("--m", type=int, nargs=2, default=(24, 40), metavar=("LO", "HI"))
+    ap.add_argument("--steady", type=int, default=2000)
+    ap.add_argument("--dtype", default="float32", choices=("float32", "float64"))
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--variants", default="per_frame,log,sequence")
+    args = ap.parse_args()
+    import torch
+    from aruco_slam_amd.synthetic import SyntheticStream, ragged_log
+
+    log = ragged_log(args.n, args.m, args.steady, seed=args.seed)
+    boot = log["bootstrap_frames"]
+    frames = len(log["has_detections"])
+    m_steady = np.diff(log["offsets"])[boot:]
+    common = {"n": args.n, "m_range": list(args.m), "m_mean": float(m_steady.mean()), "dtype": args.dtype,
+              "bootstrap_frames": boot, "steady_frames": args.steady}
+
+    def emit(**kv):
+        print(json.dumps({**kv, **common}), flush=True)
+
+    rates = {}
+    for variant in args.variants.split(","):
+        flt = _filter(args)
+        b = flt.backend
+        if variant == "per_frame":
+            offs = log["offsets"]
+
+            def run(t0, t1):
+                for t in range(t0, t1):
+                    sl = slice(int(offs[t]), int(offs[t + 1]))
+                    flt.process_detections(log["ids"][sl], log["poses"][sl])
+            t = time.perf_counter()
+            run(0, boot)
+            b.sync()
+            t_boot = time.perf_counter() - t
+            t = time.perf_counter()
+            run(boot, frames)
+            b.sync()
+            t_steady = time.perf_counter() - t
+            rates[variant] = args.steady / t_steady
+            emit(variant=variant, updates_per_s=rates[variant], steady_s=t_steady, bootstrap_s=t_boot)
+        elif variant == "log":
+            t = time.perf_counter()
+            flt.process_detection_log(*_segment(log, 0, boot))
+            t_boot = time.perf_counter() - t
+            boot_stats = b.last_log_stats()
+            t = time.perf_counter()
+            flt.process_detection_log(*_segment(log, boot, frames))
+            t_steady = time.perf_counter() - t
+            st = b.last_log_stats()
+            rates[variant] = args.steady / t_steady
+            extra = {"speedup_vs_per_frame": rates[variant] / rates["per_frame"]} if "per_frame" in rates else {}
+            emit(variant=variant, updates_per_s=rates[variant], steady_s=t_steady, bootstrap_s=t_boot,
+                 frames_stepped=st["frames_stepped"], frames_pipelined=st["frames_pipelined"],
+                 pipelined_runs=st["pipelined_runs"], pipelined_fraction=st["frames_pipelined"] / max(1, st["frames_stepped"]),
+                 bootstrap=boot_stats, **extra)
+        elif variant == "sequence":
+            t = time.perf_counter()
+            flt.process_detection_log(*_segment(log, 0, boot))
+            t_boot = time.perf_counter() - t
+            m = int(round(common["m_mean"]))
+            stream = SyntheticStream(args.n, m, seed=args.seed + 1)
+            ids, zs = zip(*stream.steady(args.steady))
+            idx_t = torch.from_numpy(np.stack(ids).astype(np.int32)).to(b.device)
+            z_t = torch.from_numpy(np.stack(zs)[:, :, 0:3].copy()).to(b.device)
+            torch.cuda.synchronize(b.device)
+            t = time.perf_counter()
+            b.observe_sequence(idx_t, z_t)
+            b.sync()
+            t_steady = time.perf_counter() - t
+            rates[variant] = args.steady / t_steady
+            emit(variant=variant, m=m, updates_per_s=rates[variant], steady_s=t_steady, bootstrap_s=t_boot,
+                 mode=b.last_sequence_mode())
+        else:
+            raise SystemExit(f"unknown variant {variant}")
+        del flt, b
+        torch.cuda.synchronize()
+
+
+if __name__ == "__main__":
+    main()

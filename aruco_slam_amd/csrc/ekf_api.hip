@@ -228,6 +228,12 @@ struct ekf_filter {
 
 namespace {
 
+// fn(float{}) or fn(double{}), by the covariance dtype: the one place that picks the element type of a launch
+template <class F>
+auto by_cov_type(const ekf_filter* f, F&& fn) {
+    return f->lay.elem == 4 ? fn(float{}) : fn(double{});
+}
+
 int fold_timing(ekf_filter* f) {
     if (f->ev_frames == 0) return EKF_OK;
     HIP_TRY(hipStreamSynchronize(f->stream));
@@ -355,7 +361,6 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, in
     int trc = ensure_tiles(f);
     if (trc) return trc;
     EkfFrame fr = make_frame(f, idx_dev, z_dev, m, traj_row);
-    const bool f32 = f->cfg.cov_dtype == EKF_COV_F32;
     const int variant = f->cfg.cov_kernel == EKF_COVK_VALU ? 1 : 2;
     hipEvent_t* ev = nullptr;
     if (f->timing) {
@@ -377,7 +382,7 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, in
             fr.status_host = reinterpret_cast<int32_t*>(f->readback + 128);
             f->mirror_fresh = true;
         }
-        if (f32) ekf_launch_front<float>(fr, f->stream); else ekf_launch_front<double>(fr, f->stream);
+        by_cov_type(f, [&](auto elem) { ekf_launch_front<decltype(elem)>(fr, f->stream); });
         if (ev_all) {
             HIP_TRY(hipEventRecord(ev[1], f->stream));
             HIP_TRY(hipEventRecord(ev[2], f->stream));
@@ -390,23 +395,22 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, in
         const int rp = blocked ? (int)round_up(fr.k, EKF_WIDE_BLOCK) : fr.kpad;
         double* aw = blocked ? f->at<double>(f->lay.off_wwork) : nullptr;
         if (blocked && !f->lay.off_wwork) return fail(EKF_ERR_STATE, "internal: no wide-frame workspace");
-        if (f32) ekf_launch_wide_front<float>(fr, aw, rp, f->stream); else ekf_launch_wide_front<double>(fr, aw, rp, f->stream);
+        by_cov_type(f, [&](auto elem) { ekf_launch_wide_front<decltype(elem)>(fr, aw, rp, f->stream); });
         if (ev_all) HIP_TRY(hipEventRecord(ev[1], f->stream));
         if (blocked) ekf_launch_wide_factor(fr, aw, f->at<double>(f->lay.off_xinv), rp, f->stream);
         else ekf_launch_solve(fr, f->stream);
         if (ev_all) HIP_TRY(hipEventRecord(ev[2], f->stream));
-        if (blocked) {
-            if (f32) ekf_launch_wide_finish<float>(fr, aw, f->stream); else ekf_launch_wide_finish<double>(fr, aw, f->stream);
-        } else {
-            if (f32) ekf_launch_panel<float>(fr, f->stream); else ekf_launch_panel<double>(fr, f->stream);
-        }
+        by_cov_type(f, [&](auto elem) {
+            if (blocked) ekf_launch_wide_finish<decltype(elem)>(fr, aw, f->stream);
+            else ekf_launch_panel<decltype(elem)>(fr, f->stream);
+        });
         if (fr.model == 1) ekf_launch_inject_rot(fr, f->n_lm, f->stream);
     } else {
-        if (f32) ekf_launch_gather<float>(fr, f->stream); else ekf_launch_gather<double>(fr, f->stream);
+        by_cov_type(f, [&](auto elem) { ekf_launch_gather<decltype(elem)>(fr, f->stream); });
         if (ev_all) HIP_TRY(hipEventRecord(ev[1], f->stream));
         ekf_launch_solve(fr, f->stream);
         if (ev_all) HIP_TRY(hipEventRecord(ev[2], f->stream));
-        if (f32) ekf_launch_panel<float>(fr, f->stream); else ekf_launch_panel<double>(fr, f->stream);
+        by_cov_type(f, [&](auto elem) { ekf_launch_panel<decltype(elem)>(fr, f->stream); });
         if (fr.model == 1) ekf_launch_inject_rot(fr, f->n_lm, f->stream);
     }
     // The state (and the status word) are final here: a state getter that follows waits for this event only and
@@ -426,13 +430,13 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, in
             cf.kpad = std::min(EKF_WIDE_REUSE_ROWS, fr.kpad - r0);
             cf.k = std::min(cf.kpad, std::max(0, fr.k - r0));
             if (r0 > 0) cf.nz.q_cam = cf.nz.q_err = cf.nz.q_lm = 0.0;
-            if (f32) ekf_launch_cov_update<float>(cf, variant, f->stream); else ekf_launch_cov_update<double>(cf, variant, f->stream);
+            by_cov_type(f, [&](auto elem) { ekf_launch_cov_update<decltype(elem)>(cf, variant, f->stream); });
         }
         if (ev) HIP_TRY(hipEventRecord(ev[4], f->stream));
-    } else if (f32) {
-        ekf_launch_cov_update<float>(fr, variant, f->stream, ev ? ev[3] : nullptr, ev ? ev[4] : nullptr);
     } else {
-        ekf_launch_cov_update<double>(fr, variant, f->stream, ev ? ev[3] : nullptr, ev ? ev[4] : nullptr);
+        by_cov_type(f, [&](auto elem) {
+            ekf_launch_cov_update<decltype(elem)>(fr, variant, f->stream, ev ? ev[3] : nullptr, ev ? ev[4] : nullptr);
+        });
     }
     HIP_TRY(hipGetLastError());
     f->last_m = m;
@@ -563,6 +567,19 @@ bool take_pipelining_token(ekf_filter* f) {
     return true;
 }
 
+// Whether the runs of a call may pipeline (want_runs: the call has a run to pipeline): probe the queues, then take the token.
+// *mode: the EKF_SEQ_* value that explains the outcome (ekf_last_sequence_mode), EKF_SEQ_PIPELINED if they may.
+int choose_pipelining(ekf_filter* f, bool want_runs, int* mode) {
+    *mode = EKF_SEQ_SERIAL;
+    if (!want_runs) return EKF_OK;
+    int rc = probe_queues(f);
+    if (rc) return rc;
+    if (f->la_ok == 0) *mode = EKF_SEQ_SERIAL_ONE_QUEUE;
+    else if (!take_pipelining_token(f)) *mode = EKF_SEQ_SERIAL_OTHER_HANDLE;
+    else *mode = EKF_SEQ_PIPELINED;
+    return EKF_OK;
+}
+
 // One frame of a pipelined run: its detections (device), their number, its trajectory row (or null).
 struct RunFrame {
     const int32_t* idx;
@@ -576,9 +593,8 @@ struct RunFrame {
 // previous frame's W over ITS OWN kpad rows (ekf_front_impl.h: the S-block and chunk completions), and the support-column
 // copy W_sup the previous frame leaves behind is [kpad][wsup_ld].  The number of detections may differ from frame to
 // frame: next_m is separate from m, and the LDS claim and the grid are taken per frame.
-// The covariance starts in `cur` and ping-pongs with `other`.  With an odd number of frames it ends in `other`:
-// copy_back = true copies it into `cur` (ekf_observe_sequence_device: the caller's buffer), otherwise *end_buf says where
-// it is.  Advances la_base by `frames`.
+// The covariance starts in f->cov and ping-pongs with `other`; f->cov is where it ends (`other` after an odd number of
+// frames: run_frames copies it back at the end of the call).  Advances la_base by `frames`.
 // One frame is a serial chain on one P, but the front kernel F(t+1) needs of P_{t+1}
 // only its support rows (camera + the landmarks of frame t+1's detections), and those follow from P_t and W_t:
 //     P_{t+1}[r][c] = (P_t[r][c] + Q[r == c]) + sum_k fma(-W_t[k][r], W_t[k][c])
@@ -600,17 +616,19 @@ struct RunFrame {
 // Every wait is bounded.  The front kernel claims (almost) all LDS of its CUs while its grid is small, so the
 // covariance update's workgroups run on the other CUs instead of next to the pivot chain.
 template <class FrameAt>
-int run_pipelined(ekf_filter* f, int frames, FrameAt frame_at, void* cur, void* other, bool copy_back, void** end_buf) {
+int run_pipelined(ekf_filter* f, int frames, FrameAt frame_at, void* other) {
     const Layout& L = f->lay;
     int rc = ensure_tiles(f);
     if (rc) return rc;
     void* wbuf[2] = {f->at<void>(L.off_wpanel), f->at<void>(L.off_wpanel2)};
-    void* cbuf[2] = {cur, other};
+    void* cbuf[2] = {f->cov, other};
     char* wsup0 = f->at<char>(L.off_wsup);
     void* wsup[2] = {wsup0, wsup0 + (size_t)L.kmax * L.wsup_ld * L.elem};
     unsigned long long* sync = f->at<unsigned long long>(L.off_sync);
     int32_t* status = f->at<int32_t>(L.off_status);
     const uint64_t base = f->la_base;
+    f->front_pending = false;      // (no front kernel of a run records ev_front)
+    f->status_clean = false;       // (gate kernels raise status bits without the host word)
     // (stream B needs no edge from stream A at the start: its first launch is the gate in front of C(0), which waits
     // for "F(1) has started", i.e. for everything that is on stream A now and F(0); the previous run ended with
     // stream A waiting for stream B)
@@ -640,30 +658,117 @@ int run_pipelined(ekf_filter* f, int frames, FrameAt frame_at, void* cur, void* 
             fr.wsup = wsup[par];
         }
         bind_exchange(f, fr);
-        if (L.elem == 4) ekf_launch_front<float>(fr, f->stream); else ekf_launch_front<double>(fr, f->stream);
+        by_cov_type(f, [&](auto elem) { ekf_launch_front<decltype(elem)>(fr, f->stream); });
         EkfFrame cu = fr;
         cu.cov = cbuf[par];
         cu.cov_out = cbuf[par ^ 1];
         if (t + 1 < frames) {
             ekf_launch_gate(sync, base + (uint64_t)t + 1, status, f->big);
-            if (L.elem == 4) ekf_launch_cov_update<float>(cu, 2, f->big); else ekf_launch_cov_update<double>(cu, 2, f->big);
+            by_cov_type(f, [&](auto elem) { ekf_launch_cov_update<decltype(elem)>(cu, 2, f->big); });
             ekf_launch_signal(sync + 1, base + (uint64_t)t + 1, f->big);
         } else {
             // The LAST update of the run goes on the handle's stream, straight behind its front kernel: stream order says
             // that F(t) is over, and F(t) did not finish before it had seen C(t-1) complete (its end gate) -- no gate, no
             // signal, and nothing to join afterwards (4 device-side hops of ~1.2 us per call).  The counters keep the
             // values of frame t - 1; the next run's waits are for values beyond base + frames, which its own launches set.
-            if (L.elem == 4) ekf_launch_cov_update<float>(cu, 2, f->stream); else ekf_launch_cov_update<double>(cu, 2, f->stream);
-            // an odd number of frames leaves the covariance in the other buffer
-            if ((frames & 1) && copy_back)
-                HIP_TRY(hipMemcpyAsync(cbuf[0], cbuf[1], (size_t)L.cap * L.cap * L.elem, hipMemcpyDeviceToDevice, f->stream));
+            by_cov_type(f, [&](auto elem) { ekf_launch_cov_update<decltype(elem)>(cu, 2, f->stream); });
         }
         HIP_TRY(hipGetLastError());
         f->last_m = cf_t.m;
     }
-    if (end_buf) *end_buf = ((frames & 1) && !copy_back) ? cbuf[1] : cbuf[0];
+    f->cov = cbuf[frames & 1];
     f->la_base = base + (uint64_t)frames;
     return EKF_OK;
+}
+
+// Which frames of a call (ekf_observe_sequence_device, ekf_observe_log) may pipeline, in one pass: a run is >= 2 consecutive
+// stepped frames that pipeline_wanted admits, of one kpad, none but the first with a first sighting (the front kernel clamps
+// next-frame indices >= n_lm, and the new rows exist in neither covariance buffer).  m_of(t): the detections of frame t
+// (0: not stepped); nnew_of(t): how many of them are first sightings.
+struct RunPlan {
+    std::vector<char> candidate;   // frame t may be in a run
+    std::vector<char> joins;       // ... and continues the run of the stepped frame before it
+    bool want_runs = false;        // some frame joins a run
+};
+
+template <class MOf, class NNewOf>
+RunPlan plan_runs(const ekf_filter* f, int frames, MOf m_of, NNewOf nnew_of) {
+    RunPlan p;
+    p.candidate.assign((size_t)frames, 0);
+    p.joins.assign((size_t)frames, 0);
+    int prev_kpad = -1;          // kpad of the previous stepped frame if it was a candidate, else -1
+    int nn = f->n_lm;
+    for (int t = 0; t < frames; ++t) {
+        const int m = m_of(t);
+        if (m == 0) continue;
+        const int nnew = nnew_of(t);
+        nn += nnew;
+        const int kpad = (int)round_up(f->lay.rd * m, EKF_RB);
+        p.candidate[t] = pipeline_wanted(f, f->lay.lmd * nn + EKF_CAM, kpad, m);
+        p.joins[t] = p.candidate[t] && nnew == 0 && prev_kpad == kpad;
+        p.want_runs = p.want_runs || p.joins[t];
+        prev_kpad = p.candidate[t] ? kpad : -1;
+    }
+    return p;
+}
+
+// Steps the frames of a call in order: the runs of `plan` in the pipelined mode if pipe_ok (choose_pipelining), every other
+// stepped frame in serial order.  frame_of(t): frame t (m == 0: not stepped).  first_sightings(t): enqueues the add-marker
+// launch of frame t's first sightings and returns their number; the run before the frame ends first, so that the new
+// landmarks see the camera the previous frame left on the device.  stats (ekf_last_log_stats, or null): stepped frames,
+// pipelined frames, runs, new landmarks.
+// The covariance ping-pongs between the caller's buffer and the second one across runs: a run with an odd number of frames
+// leaves it in the other buffer, and everything after it (serial frames, first sightings, the next run) works there; one
+// copy at the end brings it back.
+template <class FrameOf, class FirstSightings>
+int run_frames(ekf_filter* f, int frames, FrameOf frame_of, FirstSightings first_sightings, const RunPlan& plan, bool pipe_ok,
+               int64_t* stats) {
+    void* const home = f->cov;
+    void* const spare = f->lay.has_cov2 ? f->at<void>(f->lay.off_cov2) : nullptr;
+    std::vector<int> run;
+    auto serial = [&](int t) {
+        const RunFrame r = frame_of(t);
+        if (stats) stats[0] += 1;
+        return enqueue_frame(f, r.idx, r.z, r.m, r.traj_row, false);
+    };
+    auto flush = [&]() -> int {
+        int rc = EKF_OK;
+        if (run.size() == 1) {
+            rc = serial(run[0]);
+        } else if (run.size() >= 2) {
+            rc = run_pipelined(f, (int)run.size(), [&](int i) { return frame_of(run[i]); }, f->cov == home ? spare : home);
+            if (stats) {
+                stats[0] += (int64_t)run.size();
+                stats[1] += (int64_t)run.size();
+                stats[2] += 1;
+            }
+        }
+        run.clear();
+        return rc;
+    };
+    int rc = EKF_OK;
+    for (int t = 0; t < frames && rc == EKF_OK; ++t) {
+        if (frame_of(t).m == 0) continue;
+        const bool in_run = pipe_ok && plan.candidate[t];
+        if (!(in_run && plan.joins[t])) {
+            rc = flush();
+            if (rc) break;
+        }
+        const int nnew = first_sightings(t);
+        f->n_lm += nnew;
+        if (stats) stats[3] += nnew;
+        if (in_run) run.push_back(t);
+        else rc = serial(t);
+    }
+    if (rc == EKF_OK) rc = flush();
+    if (f->cov != home) {
+        // (also on an error: the caller's buffer is the filter's covariance again)
+        hipError_t e = hipMemcpyAsync(home, f->cov, (size_t)f->lay.cap * f->lay.cap * f->lay.elem, hipMemcpyDeviceToDevice,
+                                      f->stream);
+        f->cov = home;
+        if (e != hipSuccess && rc == EKF_OK) rc = fail(EKF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+    }
+    return rc;
 }
 
 }  // namespace
@@ -915,10 +1020,10 @@ int ekf_reset(ekf_filter* f, const double initial_camera_pose[10]) {
                            f->stream));
     // P = 0.1 I_10  (extended_kalman_filter.py:48)
     char diag[8 * EKF_CAM];
-    for (int i = 0; i < EKF_CAM; ++i) {
-        if (L.elem == 4) reinterpret_cast<float*>(diag)[i] = (float)f->cfg.initial_camera_uncertainty;
-        else reinterpret_cast<double*>(diag)[i] = f->cfg.initial_camera_uncertainty;
-    }
+    by_cov_type(f, [&](auto elem) {
+        for (int i = 0; i < EKF_CAM; ++i)
+            reinterpret_cast<decltype(elem)*>(diag)[i] = (decltype(elem))f->cfg.initial_camera_uncertainty;
+    });
     HIP_TRY(hipMemcpy2DAsync(f->cov, (size_t)(L.cap + 1) * L.elem, diag, L.elem, L.elem, EKF_CAM,
                              hipMemcpyHostToDevice, f->stream));
     HIP_TRY(hipStreamSynchronize(f->stream));
@@ -954,20 +1059,11 @@ int ekf_add_markers(ekf_filter* f, const double* cam_frame_xyz, const double* di
             HIP_TRY(hipMemcpyAsync(f->at<double>(L.off_unc), hu, (size_t)chunk * ub,
                                    hipMemcpyHostToDevice, f->stream));
         const double* unc_dev = diag_uncertainty ? f->at<double>(L.off_unc) : nullptr;
-        if (rot) {
-            if (L.elem == 4)
-                ekf_launch_add_markers_rot<float>(f->cov, f->ld, f->state, f->dims(), f->at<double>(L.off_xyz),
-                                                  unc_dev, f->cfg.initial_landmark_uncertainty, chunk, f->stream);
-            else
-                ekf_launch_add_markers_rot<double>(f->cov, f->ld, f->state, f->dims(), f->at<double>(L.off_xyz),
-                                                   unc_dev, f->cfg.initial_landmark_uncertainty, chunk, f->stream);
-        } else if (L.elem == 4)
-            ekf_launch_add_markers<float>(f->cov, f->ld, f->state, f->dims(), f->at<double>(L.off_xyz),
-                                          unc_dev, f->cfg.initial_landmark_uncertainty, chunk, f->stream);
-        else
-            ekf_launch_add_markers<double>(f->cov, f->ld, f->state, f->dims(), f->at<double>(L.off_xyz),
-                                           unc_dev, f->cfg.initial_landmark_uncertainty, chunk,
-                                           f->stream);
+        by_cov_type(f, [&](auto elem) {
+            auto* launch = rot ? ekf_launch_add_markers_rot<decltype(elem)> : ekf_launch_add_markers<decltype(elem)>;
+            launch(f->cov, f->ld, f->state, f->dims(), f->at<double>(L.off_xyz), unc_dev, f->cfg.initial_landmark_uncertainty,
+                   chunk, f->stream);
+        });
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(f->slot_done[f->slot], f->stream));
         f->slot = (f->slot + 1) % kStageSlots;
@@ -1026,44 +1122,22 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
     if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
     if (!lm_index_dev || !z_dev) return fail(EKF_ERR_INVALID, "NULL detections");
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
-    // Pipelined mode (F(t+1) beside C(t), see run_pipelined): the rule is pipeline_wanted's
-    const int dims_now = f->dims();
-    const int kpad_now = (int)round_up(f->lay.rd * m, EKF_RB);
-    bool pipelined = pipeline_wanted(f, dims_now, kpad_now, m) && frames >= 2;
-    if (pipelined) {
-        rc = probe_queues(f);
-        if (rc) return rc;
-    }
-    f->seq_mode = EKF_SEQ_SERIAL;
-    if (pipelined && f->la_ok == 0) {
-        pipelined = false;
-        f->seq_mode = EKF_SEQ_SERIAL_ONE_QUEUE;
-    }
-    if (pipelined && !take_pipelining_token(f)) {
-        pipelined = false;
-        f->seq_mode = EKF_SEQ_SERIAL_OTHER_HANDLE;
-    }
-    if (!pipelined) {
-        for (int t = 0; t < frames; ++t) {
-            rc = enqueue_frame(f, lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * f->lay.rd, m,
-                               trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr, false);
-            if (rc) return rc;
-        }
-        return EKF_OK;
-    }
+    // Pipelined mode (F(t+1) beside C(t), see run_pipelined) for the whole call if pipeline_wanted admits the frame shape
     const int rd = f->lay.rd;
-    rc = run_pipelined(
+    const RunPlan plan = plan_runs(f, frames, [&](int) { return m; }, [](int) { return 0; });
+    int mode = EKF_SEQ_SERIAL;
+    rc = choose_pipelining(f, plan.want_runs, &mode);
+    if (rc) return rc;
+    f->seq_mode = mode == EKF_SEQ_PIPELINED ? EKF_SEQ_SERIAL : mode;     // (PIPELINED once the run is enqueued)
+    rc = run_frames(
         f, frames,
         [&](int t) {
             return RunFrame{lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd, m,
                             trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr};
         },
-        f->cov, f->at<void>(f->lay.off_cov2), true, nullptr);
+        [](int) { return 0; }, plan, mode == EKF_SEQ_PIPELINED, nullptr);
     if (rc) return rc;
-    f->seq_mode = EKF_SEQ_PIPELINED;
-    f->front_pending = false;
-    f->status_clean = false;       // (gate kernels raise status bits without the host word)
-    f->last_m = m;
+    f->seq_mode = mode;
     return EKF_OK;
 }
 
@@ -1098,7 +1172,7 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
     for (int t = 0; t < frames; ++t)
         if (offsets[t + 1] < offsets[t]) return fail(EKF_ERR_INVALID, "offsets must be non-decreasing");
     const int64_t D = frames > 0 ? offsets[frames] : 0;
-    const int rd = f->lay.rd, lmd = f->lay.lmd;
+    const int rd = f->lay.rd;
     if (D > 0 && (!lm_index || !poses_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
     if (D > 0 && (!log_ws || log_ws_bytes < log_total(rd, D)))
         return fail(EKF_ERR_INVALID, "log workspace missing or smaller than ekf_log_workspace_bytes");
@@ -1169,109 +1243,37 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
     if (!lead.empty()) std::memcpy(pin_lead, lead.data(), lead.size() * 4);
     if (!rest.empty()) std::memcpy(pin_rest, rest.data(), rest.size() * 4);
 
-    // ---- which frames may pipeline, in one pass: a run is >= 2 consecutive stepped frames that pipeline_wanted admits, of
-    // one kpad, none but the first with a first sighting (the front kernel clamps next-frame indices >= n_lm, and the new rows
-    // exist in neither covariance buffer).  candidate[t]: frame t may be in a run; joins[t]: it continues the run of the
-    // stepped frame before it.
-    std::vector<char> candidate((size_t)frames, 0), joins((size_t)frames, 0);
-    bool want_runs = false;
-    {
-        int prev_kpad = -1;          // kpad of the previous stepped frame if it was a candidate, else -1
-        int nn = f->n_lm;
-        for (int t = 0; t < frames; ++t) {
-            const int m = (int)(offsets[t + 1] - offsets[t]);
-            if (m == 0) continue;
-            const int nnew = (int)(new_at[t + 1] - new_at[t]);
-            nn += nnew;
-            const int kpad = (int)round_up(rd * m, EKF_RB);
-            candidate[t] = pipeline_wanted(f, lmd * nn + EKF_CAM, kpad, m);
-            joins[t] = candidate[t] && nnew == 0 && prev_kpad == kpad;
-            want_runs = want_runs || joins[t];
-            prev_kpad = candidate[t] ? kpad : -1;
-        }
-    }
-    bool pipe_ok = false;
-    if (want_runs) {
-        rc = probe_queues(f);
-        if (rc) return rc;
-        pipe_ok = f->la_ok == 1 && take_pipelining_token(f);
-    }
+    auto m_of = [&](int t) { return (int)(offsets[t + 1] - offsets[t]); };
+    auto nnew_of = [&](int t) { return (int)(new_at[t + 1] - new_at[t]); };
+    const RunPlan plan = plan_runs(f, frames, m_of, nnew_of);
+    int mode = EKF_SEQ_SERIAL;
+    rc = choose_pipelining(f, plan.want_runs, &mode);
+    if (rc) return rc;
 
     // ---- device work, all on the handle's stream (the pipelined runs use the internal one as ekf_observe_sequence_device)
-    f->front_pending = false;
-    f->mirror_fresh = false;
     if (D > 0) {
         HIP_TRY(hipMemcpyAsync(ws + log_off_idx(rd, D), pin, up_bytes, hipMemcpyHostToDevice, f->stream));
         ekf_launch_log_prepare(poses_dev, D, rd, z_all, f->stream);
     }
     if (!lead.empty()) ekf_launch_log_fill_rows(trajectory_dev, pin_lead, (int32_t)(lead.size() / 2), f->state, f->stream);
-    // The covariance ping-pongs between the caller's buffer and the second one across runs: a run with an odd number of
-    // frames leaves it in the other buffer, and everything after it (serial frames, first sightings, the next run) works
-    // there; one copy at the end of the call brings it back.
-    void* const home = f->cov;
-    void* const spare = f->lay.has_cov2 ? f->at<void>(f->lay.off_cov2) : nullptr;
-    std::vector<int> run;
-    auto frame_of = [&](int t) {
-        const int64_t d0 = offsets[t];
-        return RunFrame{idx_all + d0, z_all + (size_t)d0 * rd, (int)(offsets[t + 1] - d0),
-                        trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr};
-    };
-    auto serial = [&](int t) {
-        const RunFrame r = frame_of(t);
-        f->log_stats[0] += 1;
-        return enqueue_frame(f, r.idx, r.z, r.m, r.traj_row, false);
-    };
-    auto flush = [&]() -> int {
-        int frc = EKF_OK;
-        if (run.size() == 1) {
-            frc = serial(run[0]);
-        } else if (run.size() >= 2) {
-            void* cur = f->cov;
-            void* end = cur;
-            frc = run_pipelined(f, (int)run.size(), [&](int i) { return frame_of(run[i]); }, cur, cur == home ? spare : home,
-                                false, &end);
-            f->cov = end;
-            f->log_stats[0] += (int64_t)run.size();
-            f->log_stats[1] += (int64_t)run.size();
-            f->log_stats[2] += 1;
-            f->status_clean = false;       // (gate kernels raise status bits without the host word)
-        }
-        run.clear();
-        return frc;
-    };
-    for (int t = 0; t < frames && rc == EKF_OK; ++t) {
-        const int m = (int)(offsets[t + 1] - offsets[t]);
-        if (m == 0) continue;                    // not stepped (no predict); its trajectory row is filled below
-        const int nnew = (int)(new_at[t + 1] - new_at[t]);
-        if (nnew > 0) {
-            // the run before ends first; the frame's new landmarks see the camera the previous frame left on the device
-            rc = flush();
-            if (rc) break;
-            if (f->lay.elem == 4)
-                ekf_launch_log_add_markers<float>(f->cfg.model, f->cov, f->ld, f->state, f->dims(), poses_dev,
-                                                  slots_all + new_at[t], f->cfg.initial_landmark_uncertainty, nnew, f->stream);
-            else
-                ekf_launch_log_add_markers<double>(f->cfg.model, f->cov, f->ld, f->state, f->dims(), poses_dev,
-                                                   slots_all + new_at[t], f->cfg.initial_landmark_uncertainty, nnew, f->stream);
-            f->n_lm += nnew;
-            f->log_stats[3] += nnew;
-        }
-        if (pipe_ok && candidate[t]) {
-            if (!joins[t]) rc = flush();
-            if (rc == EKF_OK) run.push_back(t);
-        } else {
-            rc = flush();
-            if (rc == EKF_OK) rc = serial(t);
-        }
-    }
-    if (rc == EKF_OK) rc = flush();
-    if (f->cov != home) {
-        // (also on an error: the caller's buffer is the filter's covariance again)
-        hipError_t e = hipMemcpyAsync(home, f->cov, (size_t)f->lay.cap * f->lay.cap * f->lay.elem, hipMemcpyDeviceToDevice,
-                                      f->stream);
-        f->cov = home;
-        if (e != hipSuccess && rc == EKF_OK) rc = fail(EKF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-    }
+    rc = run_frames(
+        f, frames,
+        [&](int t) {
+            const int64_t d0 = offsets[t];
+            return RunFrame{idx_all + d0, z_all + (size_t)d0 * rd, m_of(t),
+                            trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr};
+        },
+        [&](int t) {
+            const int nnew = nnew_of(t);
+            if (nnew > 0)
+                by_cov_type(f, [&](auto elem) {
+                    ekf_launch_log_add_markers<decltype(elem)>(f->cfg.model, f->cov, f->ld, f->state, f->dims(), poses_dev,
+                                                               slots_all + new_at[t], f->cfg.initial_landmark_uncertainty, nnew,
+                                                               f->stream);
+                });
+            return nnew;
+        },
+        plan, mode == EKF_SEQ_PIPELINED, f->log_stats);
     if (rc == EKF_OK && !rest.empty())
         ekf_launch_log_fill_rows(trajectory_dev, pin_rest, (int32_t)(rest.size() / 2), f->state, f->stream);
     // A state getter after the call must wait for the whole call (the last frame's state may come from a pipelined run, whose
@@ -1360,8 +1362,7 @@ int ekf_get_cov_diag(ekf_filter* f, double* out, int32_t count) {
     if (rc) return rc;
     if (!out || count < 0 || count > f->dims()) return fail(EKF_ERR_INVALID, "bad diag request");
     double* scratch = f->at<double>(f->lay.off_diag);
-    if (f->lay.elem == 4) ekf_launch_cov_diag<float>(f->cov, f->ld, scratch, count, f->stream);
-    else ekf_launch_cov_diag<double>(f->cov, f->ld, scratch, count, f->stream);
+    by_cov_type(f, [&](auto elem) { ekf_launch_cov_diag<decltype(elem)>(f->cov, f->ld, scratch, count, f->stream); });
     HIP_TRY(hipGetLastError());
     rc = sync_and_check(f);
     if (rc) return rc;
@@ -1420,23 +1421,16 @@ int ekf_set_cov(ekf_filter* f, const double* cov, int32_t dims) {
         HIP_TRY(hipMemset(f->at<void>(L.off_cov2), 0, (size_t)L.cap * L.cap * L.elem));
     }
     // symmetrise on upload: the kernels keep P bitwise symmetric from then on
-    if (L.elem == 8) {
-        std::vector<double> tmp((size_t)dims * dims);
+    return by_cov_type(f, [&](auto elem) -> int {
+        using T = decltype(elem);
+        std::vector<T> tmp((size_t)dims * dims);
         for (int i = 0; i < dims; ++i)
             for (int j = 0; j < dims; ++j)
-                tmp[(size_t)i * dims + j] = 0.5 * (cov[(size_t)i * dims + j] + cov[(size_t)j * dims + i]);
-        HIP_TRY(hipMemcpy2D(f->cov, (size_t)f->ld * 8, tmp.data(), (size_t)dims * 8, (size_t)dims * 8,
+                tmp[(size_t)i * dims + j] = (T)(0.5 * (cov[(size_t)i * dims + j] + cov[(size_t)j * dims + i]));
+        HIP_TRY(hipMemcpy2D(f->cov, (size_t)f->ld * sizeof(T), tmp.data(), (size_t)dims * sizeof(T), (size_t)dims * sizeof(T),
                             dims, hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> tmp((size_t)dims * dims);
-        for (int i = 0; i < dims; ++i)
-            for (int j = 0; j < dims; ++j)
-                tmp[(size_t)i * dims + j] =
-                    (float)(0.5 * (cov[(size_t)i * dims + j] + cov[(size_t)j * dims + i]));
-        HIP_TRY(hipMemcpy2D(f->cov, (size_t)f->ld * 4, tmp.data(), (size_t)dims * 4, (size_t)dims * 4,
-                            dims, hipMemcpyHostToDevice));
-    }
-    return EKF_OK;
+        return EKF_OK;
+    });
 }
 
 int ekf_last_sequence_mode(const ekf_filter* f) { return f ? f->seq_mode : EKF_ERR_INVALID; }

@@ -42,10 +42,7 @@ inline int64_t round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 constexpr int kStageSlots = 64;   // pinned host ring for ekf_observe
-#ifndef EKF_MACRO_SUPER
-#define EKF_MACRO_SUPER 8
-#endif
-constexpr int kMacroSuper = EKF_MACRO_SUPER;    // macro-tile covariance update: super-tiles of 8 x 8 macro tiles per XCD (ekf_cov_macro.hip)
+constexpr int kMacroSuper = 8;    // macro-tile covariance update: super-tiles of 8 x 8 macro tiles per XCD (ekf_cov_macro.hip)
 constexpr int kMacroMinTiles = 3000;   // ... chosen from this many 128 x 128 tiles of the lower triangle (n >= 3300 or so; measured: n=2048 1225 tiles 98 vs 80 us for the wave-per-tile kernel, n=4096 4753 tiles 290 vs 323)
 constexpr int kTimedKernels = 4;
 // Detections per frame that the gather kernel and the fused front kernel take; with EKF_FLAG_WIDE_FRAMES (flags bit 3) a
@@ -63,7 +60,7 @@ struct Layout {
     int kmax;         // rd * max_visible rounded up to 16
     size_t elem;      // sizeof(cov element)
     size_t off_jac, off_resid, off_y, off_lmcol, off_amat, off_sblk, off_lmat, off_dinv, off_lop, off_dop, off_wpanel, off_wpanel2, off_cov2, off_wdbg,
-        off_idx, off_z, off_status, off_stamps, off_covstats, off_dx, off_diag, off_xyz, off_unc,
+        off_idx, off_z, off_status, off_stamps, off_dx, off_diag, off_xyz, off_unc,
         off_xl, off_done, off_sync, off_wsup, total;
     size_t off_wwork, off_xinv;   // wide frames beyond the stage kernels' size: A -> W in f64 [kmax][cap], X = L_BB^-1 (0: none)
     int wsup_ld;      // row length of the compact support-column copy of W (pipelined sequence mode; two copies, by frame parity)
@@ -109,7 +106,6 @@ Layout make_layout(const ekf_config& c) {
     L.off_z = take((size_t)c.max_visible * 7 * 8);
     L.off_status = take(256);
     L.off_stamps = take(64 * 8);
-    L.off_covstats = take(32 * 8);
     L.off_dx = take((size_t)L.cap * 8);
     L.off_diag = take((size_t)L.cap * 8);
     L.off_xyz = take((size_t)256 * 6 * 8);
@@ -293,7 +289,6 @@ EkfFrame make_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, 
     fr.status_host = nullptr;
     fr.cov_tiles = nullptr;
     fr.cov_grid = 0;
-    fr.cov_stats = f->debug_stamps ? f->at<unsigned long long>(L.off_covstats) : nullptr;
     if (f->tiles_T > 0 && f->tiles_T == (fr.dims + 127) / 128) {
         fr.cov_tiles = f->at<uint32_t>(L.off_tiles);
         fr.cov_grid = f->tiles_grid;
@@ -1517,15 +1512,6 @@ int ekf_debug_fetch(ekf_filter* f, int32_t what, double* out, size_t count) {
                 long long st[64];
                 HIP_TRY(hipMemcpy(st, f->at<long long>(L.off_stamps), sizeof(st), hipMemcpyDeviceToHost));
                 for (int i = 0; i < 64; ++i) out[i] = (double)st[i];
-            }
-            return EKF_OK;
-        case 6:      // counters of the macro-tile covariance update (diagnostic builds only), then cleared
-            if (count < 32) return fail(EKF_ERR_INVALID, "out too small");
-            {
-                unsigned long long st[32];
-                HIP_TRY(hipMemcpy(st, f->at<unsigned long long>(L.off_covstats), sizeof(st), hipMemcpyDeviceToHost));
-                for (int i = 0; i < 32; ++i) out[i] = (double)st[i];
-                HIP_TRY(hipMemset(f->at<unsigned long long>(L.off_covstats), 0, sizeof(st)));
             }
             return EKF_OK;
         default:

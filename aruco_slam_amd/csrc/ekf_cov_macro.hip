@@ -28,50 +28,25 @@
 typedef float cm_f32x16 __attribute__((ext_vector_type(16)));
 typedef float cm_f4 __attribute__((ext_vector_type(4)));
 
-#ifndef CM_NW
-#define CM_NW 8                         // waves per workgroup (4 or 8)
-#endif
+#define CM_NW 8                         // waves per workgroup
 #define CM_T (64 * CM_NW)
 #define CM_LD 132                       // floats per row of the epilogue image (528 B: b128 accesses stay conflict-free)
 #define CM_KC 16                        // rows of W per chunk
 #define CM_NBUF 5                       // chunk buffers ([A: 16 x 128 | B: 16 x 128] floats = 16 KB each): four chunks in flight
 #define CM_LDS_BYTES (CM_NBUF * 2 * CM_KC * 128 * 4)   // 80 KB (>= the 67,584 B of the epilogue image): two workgroups fill a CU's 160 KB
 
-#ifndef CM_D_DIRECT
-#define CM_D_DIRECT 0                   // 1: D straight from the accumulator registers (dword stores); 0: through LDS (16-byte stores)
-#endif
-#ifndef CM_STORE_MODE
-#define CM_STORE_MODE 2                 // 0 plain, 1 nontemporal, 2 write-through (sc1)
-#endif
-// timing ablations (tools/cov_macro_ab.sh; never set in the product build): bit 0 no MFMAs, bit 1 no P loads,
-// bit 2 no global stores, bit 3 no W staging
-#ifndef CM_ABLATE
-#define CM_ABLATE 0
-#endif
 // Two workgroups share a CU (one wave of each per SIMD) and the matrix pipe.  Started together they run in lockstep:
 // both stage, both multiply (each at half rate), both write their tile -- and the pipe idles during every epilogue
 // (measured: 51k cycles of loop + 4k before + 15k after it per pair of tiles, 70 % busy).  The second workgroup of the
 // FIRST round (wave slot 1 of its SIMDs) therefore starts one multiply phase late; its successors inherit the offset
 // (a slot is refilled when its workgroup ends), so from then on one workgroup's loads and stores run beside the
 // other's MFMAs.  Placement and slot numbers are a speed matter only.
-#ifndef CM_MID
 #define CM_MID 0                        // k-pair of a chunk in front of which the workgroup's barrier for the NEXT chunk sits
-#endif
-#ifndef CM_STAGGER
 #define CM_STAGGER 24000                // cycles (one tile's 384 MFMAs per wave: 24.6k)
-#endif
 
+// 16-byte write-through (sc1) store of the updated tile
 __device__ __forceinline__ void cm_store16(float* p, const cm_f4& v) {
-    if (CM_ABLATE & 4) { asm volatile("" ::"v"(p), "v"(v)); return; }
-    if (CM_STORE_MODE == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-    else if (CM_STORE_MODE == 1) __builtin_nontemporal_store(v, reinterpret_cast<cm_f4*>(p));
-    else *reinterpret_cast<cm_f4*>(p) = v;
-}
-__device__ __forceinline__ void cm_store4(float* p, float v) {
-    if (CM_ABLATE & 4) { asm volatile("" ::"v"(p), "v"(v)); return; }
-    if (CM_STORE_MODE == 2) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else if (CM_STORE_MODE == 1) __builtin_nontemporal_store(v, p);
-    else *p = v;
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
 // one 16-byte LDS-DMA per lane: 64 lanes x 16 B land at lds_wave_base + 16 lane
@@ -125,7 +100,6 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
     static_assert(NW == 8, "wait counts below are worked out for 8 waves");
     const uint32_t tl = tiles[blockIdx.x];
     if (tl == 0xFFFFFFFFu) return;
-    if ((CM_ABLATE & 16) && fr.dims > 0) return;          // (dispatch cost alone)
     const int I = (int)(tl >> 16), J = (int)(tl & 0xFFFFu);
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -135,16 +109,12 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
     const float* __restrict__ P = static_cast<const float*>(fr.cov);
     float* Pout = fr.cov_out ? static_cast<float*>(fr.cov_out) : static_cast<float*>(fr.cov);
     const int ld = (int)fr.ld, ldw = (int)fr.ldw;
-    constexpr int KPAD = 16 * KB, NCH = KB;       // chunks of 16 rows
+    constexpr int NCH = KB;                       // chunks of 16 rows
 
-    if (CM_STAGGER > 0 && blockIdx.x < 512 && ((__builtin_amdgcn_s_getreg((31 << 11) | 4) / (NW / 4)) & 1)) {      // HW_ID[3:0]: wave slot
+    if (blockIdx.x < 512 && ((__builtin_amdgcn_s_getreg((31 << 11) | 4) / (NW / 4)) & 1)) {      // HW_ID[3:0]: wave slot
         const long long t0 = __builtin_amdgcn_s_memtime();
         while (__builtin_amdgcn_s_memtime() - t0 < CM_STAGGER) __builtin_amdgcn_s_sleep(32);
     }
-#ifdef CM_STAMPS
-    const long long ts0 = __builtin_amdgcn_s_memtime(), tr0 = __builtin_amdgcn_s_memrealtime();
-    long long ts1 = 0;
-#endif
     // chunk c -> buffer c % 5: [A: 16 x 128 | B: 16 x 128] floats.  Wave w stages rows 2 w, 2 w + 1 of both (lanes 0-31: row r,
     // lanes 32-63: row r + 1; the k-major panel rows ARE the lane-linear image the DMA writes).
     const unsigned wlane = (unsigned)(lhi * ldw + 4 * l31);
@@ -152,7 +122,6 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
         float* buf = cm_sm + (c % CM_NBUF) * (2 * CM_KC * 128);
         const int rloc = 2 * wave;
         const float* src = wp + (int64_t)(CM_KC * c + rloc) * ldw;
-        if (CM_ABLATE & 8) return;
         cm_dma16(src + i0 + wlane, buf + rloc * 128);
         cm_dma16(src + j0 + wlane, buf + CM_KC * 128 + rloc * 128);
     };
@@ -172,15 +141,12 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
         const float* base = P + (int64_t)(i0 + 64 * wr + 32 * ti) * ld + j0 + CW * wc + 32 * tj;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
-            pt[ti][tj][reg] = (CM_ABLATE & 2) ? 0.0f : __builtin_nontemporal_load(base + (int64_t)((reg & 3) + 8 * (reg >> 2)) * ld + plane);
+            pt[ti][tj][reg] = __builtin_nontemporal_load(base + (int64_t)((reg & 3) + 8 * (reg >> 2)) * ld + plane);
     };
 #pragma unroll
     for (int c = 0; c < DEPTH && c < NCH; ++c) stage(c);
     cm_wait_vm<cm_younger(0, 0, NCH, DEPTH, DPW, NPB)>();
     __builtin_amdgcn_s_barrier();                    // chunk 0 is in LDS for every wave
-#ifdef CM_STAMPS
-    ts1 = __builtin_amdgcn_s_memtime();
-#endif
     // One stream of k-pairs over all chunks.  Operands of k-pair kp + 1 are requested BEFORE the MFMAs of k-pair kp are issued
     // (a wave's MFMAs issue in order, 64 cycles apart: requested behind them, as the compiler schedules a plain loop, the LDS
     // round trip of every k-pair lies open).  The workgroup's barrier for chunk c + 1 ("landed for every wave"; it also says
@@ -216,11 +182,7 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
         // behind them the compiler's `s_waitcnt lgkmcnt(0)` would wait for those too)
         if (TJ == 2) asm volatile("" : "+v"(ca[0]), "+v"(ca[1]), "+v"(cb[0]), "+v"(cb[TJ - 1]));
         else asm volatile("" : "+v"(ca[0]), "+v"(ca[1]), "+v"(cb[0]));
-        if ((CM_ABLATE & 32) && kp > 0) {      // (matrix pipe alone: no LDS reads)
-            na[0] = ca[0]; na[1] = ca[1];
-#pragma unroll
-            for (int tj = 0; tj < TJ; ++tj) nb[tj] = cb[tj];
-        } else if (kp + 1 < NKP) {
+        if (kp + 1 < NKP) {
             na[0] = pa(kp + 1)[0]; na[1] = pa(kp + 1)[32];
 #pragma unroll
             for (int tj = 0; tj < TJ; ++tj) nb[tj] = pb(kp + 1)[32 * tj];
@@ -229,12 +191,8 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
         const float a0 = -ca[0], a1 = -ca[1];
 #pragma unroll
         for (int tj = 0; tj < TJ; ++tj) {
-            if (CM_ABLATE & 1) {
-                acc[0][tj][kp & 15] += a0 * cb[tj]; acc[1][tj][kp & 15] += a1 * cb[tj];
-            } else {
-                acc[0][tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, cb[tj], acc[0][tj], 0, 0, 0);
-                acc[1][tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, cb[tj], acc[1][tj], 0, 0, 0);
-            }
+            acc[0][tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, cb[tj], acc[0][tj], 0, 0, 0);
+            acc[1][tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, cb[tj], acc[1][tj], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
         ca[0] = na[0]; ca[1] = na[1];
@@ -246,9 +204,6 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
     __builtin_amdgcn_s_barrier();                    // every wave has read the last chunk: the buffers become the epilogue image
 #pragma unroll
     for (int c = NCH; c < NPB; ++c) load_p(c);      // (small k: the batches no step has issued)
-#ifdef CM_STAMPS
-    const long long ts2 = __builtin_amdgcn_s_memtime();
-#endif
     // (the P tile is used from here on: without this the compiler starts the additions below -- `pt + 0` where the
     // sub-tile cannot be diagonal -- inside the chunk loop and waits there, vmcnt(0), for the batch it has just requested)
 #pragma unroll
@@ -276,16 +231,6 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
     float* img = cm_sm;                              // [128][CM_LD]: free since the barrier behind the loop
     constexpr int RPP = NT / 32, NPASS = 128 / RPP;  // rows per pass of the workgroup (32 lanes x 16 B per row), passes
     const int prow = tid >> 5, pcol = 4 * (tid & 31);
-#if CM_D_DIRECT
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < TJ; ++tj) {
-            float* ob = Pout + (int64_t)(i0 + 64 * wr + 32 * ti) * ld + j0 + CW * wc + 32 * tj;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) cm_store4(ob + (int64_t)((reg & 3) + 8 * (reg >> 2)) * ld + plane, acc[ti][tj][reg]);
-        }
-#else
     // image of the tile, [row][column]: one ds_write_b32 per register (lanes = 32 consecutive columns)
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti)
@@ -304,7 +249,6 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
         for (int it = 0; it < NPASS; ++it) cm_store16(ob + (int64_t)(RPP * it) * ld + (unsigned)(prow * ld + pcol), rowv[it]);
     }
     if (!dtile) __syncthreads();                     // (uniform: I, J are the workgroup's)
-#endif
     if (!dtile) {
     // image of the transposed tile, [column][row]: a lane holds four consecutive rows of one column: ds_write_b128
 #pragma unroll
@@ -326,21 +270,6 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
         for (int it = 0; it < NPASS; ++it) cm_store16(ob + (int64_t)(RPP * it) * ld + (unsigned)(prow * ld + pcol), rowv[it]);
     }
     }
-#ifdef CM_STAMPS
-    if (fr.cov_stats && tid == 0) {
-        const long long ts3 = __builtin_amdgcn_s_memtime(), tr1 = __builtin_amdgcn_s_memrealtime();
-        // [0] start, [1] end (100 MHz ticks), [2] HW_ID, [3] XCC_ID, [4] start -> chunk 0 landed, [5] chunk loop, [6] epilogue (cycles), [7] tile
-        double* tlrow = fr.amat + (int64_t)(blockIdx.x / 1500) * fr.lda + 8 * (blockIdx.x % 1500);
-        tlrow[0] = (double)tr0;
-        tlrow[1] = (double)tr1;
-        tlrow[2] = (double)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-        tlrow[3] = (double)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15);
-        tlrow[4] = (double)(ts1 - ts0);
-        tlrow[5] = (double)(ts2 - ts1);
-        tlrow[6] = (double)(ts3 - ts2);
-        tlrow[7] = (double)tl;
-    }
-#endif
 }
 
 // Host side: the launch order.  Block b runs on XCD b % 8 (observed placement; speed only), so the table deals whole
@@ -404,16 +333,11 @@ static void cm_go(const EkfFrame& fr, hipStream_t s, hipEvent_t e0, hipEvent_t e
 
 void ekf_launch_cov_update_macro(const EkfFrame& fr, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     switch (fr.kpad / 16) {
-#ifdef CM_ONLY_KB
-        case CM_ONLY_KB: return cm_go<CM_ONLY_KB>(fr, s, e0, e1);
-        default: return;
-#else
 #define CM_CASE(KB) case KB: return cm_go<KB>(fr, s, e0, e1);
         CM_CASE(1) CM_CASE(2) CM_CASE(3) CM_CASE(4) CM_CASE(5) CM_CASE(6) CM_CASE(7) CM_CASE(8) CM_CASE(9) CM_CASE(10)
         CM_CASE(11) CM_CASE(12) CM_CASE(13) CM_CASE(14) CM_CASE(15) CM_CASE(16) CM_CASE(17) CM_CASE(18) CM_CASE(19)
         CM_CASE(20) CM_CASE(21) CM_CASE(22) CM_CASE(23) CM_CASE(24)
 #undef CM_CASE
         default: return;      // (check_config keeps kpad <= 384)
-#endif
     }
 }

@@ -34,17 +34,11 @@
 // Stores of the updated covariance.  P is not read again inside the launch and every XCD's L2 is invalidated before the
 // next launch reads it, so keeping the 38.5 MB (n=1024) of written lines dirty in the L2s only postpones their way to
 // memory to the end of the launch, where the next kernel waits for it.  Write-through (sc1) stores stream them out while
-// the kernel still computes (tools/store_mode_probe.sh, n=1024, m=32, f32; kernel / serial frame / pipelined frame in us:
+// the kernel still computes (measured, n=1024, m=32, f32; kernel / serial frame / pipelined frame in us:
 // plain 16.7 / 40.0 / 36.1 - nontemporal 15.9 / 39.2 / 35.2 - write-through 15.2 / 38.1 / 34.6).
-// EKF_COV_STORE_MODE (experiments): 0 plain, 1 nontemporal, 2 write-through.
-#ifndef EKF_COV_STORE_MODE
-#define EKF_COV_STORE_MODE 2
-#endif
 template <typename T>
 __device__ __forceinline__ void ekf_cov_store(T* p, T v) {
-    if (EKF_COV_STORE_MODE == 1) __builtin_nontemporal_store(v, p);
-    else if (EKF_COV_STORE_MODE == 2) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -47,9 +47,6 @@
 
 #define FR_T 512
 #define FR_ALD 66          // row stride (doubles) of the A chunk in LDS
-#ifndef FR_DOT_RING
-#define FR_DOT_RING 2      // operand chunks (8 k-pairs) in flight, S-block role's support dots (pipelined mode)
-#endif
 // doubles of the chunk role's A region (pipelined mode: before A is built the region holds the staged operands of
 // the support-row product, W_sup [96][128] and W [96][64], and its result [128][64], all f32: 104 KB)
 #define FR_KS 96            // rows of W staged at a time
@@ -69,14 +66,9 @@ typedef double pf64x4 __attribute__((ext_vector_type(4)));
 // Stores of W / W_sup (read by later launches only): write-through, like the covariance update's (ekf_cov_update.hip) --
 // plain stores leave 1.2 MB of dirty lines for the end of the launch, where the next front kernel waits for them
 // (us per frame pipelined / serial at n=1024, m=32: plain 24.4 / 36.1, write-through 23.9 / 35.6).
-// FR_W_STORE_MODE (experiments): 0 plain, 2 write-through
-#ifndef FR_W_STORE_MODE
-#define FR_W_STORE_MODE 2
-#endif
 template <typename T>
 __device__ __forceinline__ void fr_w_store(T* p, T v) {
-    if (FR_W_STORE_MODE == 2) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 typedef float fr_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -768,7 +760,6 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
 #pragma unroll
         for (int r = 0; r < 4; ++r) t[b][r] = a_lds[(16 * b + g + 4 * r) * FR_ALD + 16 * wv + j];
     // the old state of this wave's columns (nobody writes it before the injection below)
-    const int scol = col0 + j;
     const double st_old = pre.st_old;
     const double q_old[4] = {pre.q_old[0], pre.q_old[1], pre.q_old[2], pre.q_old[3]};
     const double q_rn = (MODEL == 0 && col0 == 0) ? ekf_quat_rnorm(q_old) : 0.0;      // (here: not on the tail of the launch)
@@ -1013,11 +1004,6 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
     if (wv == 0 && lane == NB && fr_tag_stale(ekf_ldc(fr.xl + fr.xl_tag), fr.seqno)) ekf_raise(fr, EKF_ST_STALE_JAC);
 }
 
-#ifdef FR_CHUNK_DIAG      // (diagnostic builds: prologue stamps of chunk 0, role-level stamp mode, slots 41 .. 52)
-#define FR_DIAG(i) do { if (fr.stamps && !fr.stamps_heavy && chunk == 0 && tid == 0) fr.stamps[41 + (i)] = wall_clock64(); } while (0)
-#else
-#define FR_DIAG(i) do { } while (0)
-#endif
 template <typename T, int NU, int MODEL, int NB>
 __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, double* sm) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
@@ -1089,7 +1075,6 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
         }
         smask_l[tid] = mk;
     }
-    FR_DIAG(0);
     if (!fix) {
         // (camera rows and landmark rows together: requested before the index round trip, the ten camera-row values
         // were spilled one by one, each load waited for -- hipcc)
@@ -1167,7 +1152,6 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
 #pragma unroll
                 for (int n = 0; n < NBL; ++n) *reinterpret_cast<fr_f4*>(sB + 4 * (tid + FR_T * n)) = vb[n];
                 __syncthreads();
-                FR_DIAG(1 + 4 * round + 2 * (kb / (FR_KS / 16)));
                 if (kb == 0 && round == 0) jac_issue();      // (in flight during the matrix phase)
                 if (stp_c && round == 0 && kb == 0) fr.stamps[45] = wall_clock64();
                 if (tile_ok) {
@@ -1181,7 +1165,6 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
                         __builtin_amdgcn_sched_barrier(0);      // (the scheduler would hoist every LDS read of the stage: 16 registers per chunk)
                     }
                 }
-                FR_DIAG(2 + 4 * round + 2 * (kb / (FR_KS / 16)));
             }
             if (stp_c && round == 0) fr.stamps[46] = wall_clock64();
             if (tile_ok) {
@@ -1300,11 +1283,9 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
     // (pipelined mode: requested above, taken only now -- the support rows depend on nothing this launch computes, and
     // fetched "while the first stage is in flight" the Jacobian made the matrix phase wait ~3 us for the measurement
     // workgroup; fetched here as a whole it was 1.6 us of polling and bulk on the way to the A chunk)
-    FR_DIAG(10);
     if (!fix) jac_issue();
     jac_finish();
     __syncthreads();
-    FR_DIAG(11);
     FrPre<NB> pre;
     if (fr.stamps && fr.stamps_heavy && chunk == 0 && tid == 0 && NB <= 6) fr.stamps[14] = wall_clock64();
     // (the support rows become doubles BEFORE the substitution's first requests go out: they may come straight from

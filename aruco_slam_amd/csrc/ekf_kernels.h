@@ -105,7 +105,6 @@ struct EkfFrame {
     // tile (I << 16 | J) of block b, 0xFFFFFFFF = none; null: the wave-per-tile kernel (ekf_cov_update.hip)
     const uint32_t* cov_tiles;
     int32_t cov_grid;
-    unsigned long long* cov_stats;     // diagnostics of the macro-tile kernel (builds with CM_STAMPS only; else unused)
 };
 
 // raise sticky status bits (and tell the host mirror, if there is one, that the status word is no longer zero)

@@ -35,7 +35,7 @@
 //         publisher  : X_b, the L_ib and y_b of column b from LDS to memory; colready[b] when the stores are complete.
 //     Critical path per column: panel block (4 MFMAs) -> diagonal update (4 MFMAs) -> LDS -> chain (~3.3k cycles) -> LDS -- for
 //     the first block columns.  From b ~ 3 on the workers' [C] is longer than a chain and sets the period (NB = 12,
-//     tools/chunk_stamps.py svb: 2.9 us at b = 1 growing to 5.5 - 6.5 us from b = 5 on).  One worker at b = 6, first version
+//     per-column stamps of a diagnostic build: 2.9 us at b = 1 growing to 5.5 - 6.5 us from b = 5 on).  One worker at b = 6, first version
 //     (a request, a flag wait and four dependent MFMAs per history term): [A] 0.5, [B] 0.5, S blocks of column b + 2 0.6, six
 //     history terms 3.4, last term 0.4 us.  Now the requests of a row go out together (one round trip, ~0.9 us) and the terms
 //     run on four accumulators, one per k-slice: six terms 1.8 us; n=1024 m=64 pipelined 71.3 -> 65.0 us per frame, n=4096
@@ -45,14 +45,6 @@
 #include "ekf_solve_cw.h"
 
 #define SVB_WORKERS 6
-#ifdef SVB_DIAG      // (diagnostic builds, tools/chunk_stamps.py svb: per-column stamps of the publishing and the chain wave in
-                     // fr.stamps[0 .. 47], of worker SVB_DIAG_W during block column SVB_DIAG_B in [48 .. 55])
-#define SVB_STAMP(i) do { if (fr.stamps && lane == 0) fr.stamps[i] = wall_clock64(); } while (0)
-#define SVB_WSTAMP(i) do { if (fr.stamps && lane == 0 && widx == SVB_DIAG_W && b == SVB_DIAG_B) fr.stamps[48 + (i)] = wall_clock64(); } while (0)
-#else
-#define SVB_STAMP(i) do { } while (0)
-#define SVB_WSTAMP(i) do { } while (0)
-#endif
 
 __host__ __device__ constexpr int svb_lds_doubles(int nb) {
     // X (two slots) | L_ib of every row (NB + 1) | staged history of a pivot row (NB) | diagonal block | y (16 NB) | flags (3 NB + 8 ints)
@@ -100,7 +92,6 @@ __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double
     if (is_chain) {
         for (int b = 0; b < NB; ++b) {
             svb_wait(dready, b + 1);
-            SVB_STAMP(24 + b);
             sf64x4 m = sv_lds_get(dblk, lane);
             sf64x4 xop;
             int badnow;
@@ -143,9 +134,7 @@ __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double
                     io.put_y(b, (c >> 2) == 0 ? yi[0] : (c >> 2) == 1 ? yi[1] : (c >> 2) == 2 ? yi[2] : yi[3], c, g == (c & 3));
                 }
             }
-            SVB_STAMP(12 + b);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the column is in memory: it may be read back as history
-            SVB_STAMP(b);
             svb_post(colready + b, 1, lane);
         }
         return;
@@ -168,9 +157,7 @@ __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double
         svb_post(dready, 1, lane);
     }
     for (int b = 0; b < NB; ++b) {
-        SVB_WSTAMP(7);                                           // (the previous column's [C] is over)
         __syncthreads();                                         // X_b is there (and every reader of the previous column's LDS copies is done)
-        SVB_WSTAMP(0);
         const sf64x4 xop = sv_lds_get(xbuf + (b & 1) * 256, lane);
         // [A] the panel: L_ib = t_i(b) X_b^T
 #pragma unroll
@@ -184,7 +171,6 @@ __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double
                 svb_post(yflag + i, b + 1, lane);
             }
         }
-        SVB_WSTAMP(1);
         if (b + 1 >= NB) break;
         // [B] the last term of column b + 1; its diagonal block goes to the chain wave
 #pragma unroll
@@ -203,15 +189,12 @@ __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double
             }
         }
         const int p = b + 2;                                     // [C] column p = b + 2, beside chain b + 1
-        SVB_WSTAMP(2);
         if (p >= NB) continue;
         fetch_column(tnxt, p);
-        SVB_WSTAMP(3);
         if (b > 0) {
             // History terms q < b: every request of a batch -- the worker's share of the pivot row, then up to HD blocks of a
             // row -- goes out before the first result is used (one memory round trip per batch; first version: one per term)
             svb_wait(colready + (b - 1), 1);                       // (the publisher posts the columns in order)
-            SVB_WSTAMP(8);
             constexpr int PV = (NB - 2 + SVB_WORKERS - 1) / SVB_WORKERS;
             sf64x4 pv[PV];
 #pragma unroll
@@ -257,12 +240,11 @@ __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double
                         sf64x4 own[HD];
 #pragma unroll
                         for (int d = 0; d < HD; ++d) own[d] = io.hist_block(i, min(q0 + d, b - 1), lane);
-                        if (!staged) { stage(); SVB_WSTAMP(9); }
+                        if (!staged) stage();
 #pragma unroll
                         for (int d = 0; d < HD; ++d) {
                             if (q0 + d < b) {
                                 svb_wait(pflag + (q0 + d), p);
-                                if (d == 0 && q0 == 0) SVB_WSTAMP(10);
                                 term(sv_lds_get(prow + (q0 + d) * 256, lane), own[d]);
                             }
                         }
@@ -273,8 +255,6 @@ __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double
             }
             if (!staged) stage();
         }
-        SVB_WSTAMP(4);
-        SVB_WSTAMP(5);
         // ... and the term of the column that has just been finished (q = b), from the LDS copies
 #pragma unroll
         for (int s = 0; s < MR; ++s) {
@@ -287,7 +267,6 @@ __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double
                 }
             }
         }
-        SVB_WSTAMP(6);
     }
 }
 

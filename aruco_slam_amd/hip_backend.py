@@ -404,8 +404,8 @@ class HipEkf:
         rd = self.rows_per_detection
         k, kp, n = rd * m, -(-rd * m // 16) * 16, self.dims
         shape = {"jac": (k, 20 if rd == 7 else 13), "resid": (k,), "L": (kp, kp), "W": (kp, n), "A": (k, n),
-                 "stamps": (64,), "cov_stats": (32,)}[what]
-        code = {"jac": 0, "resid": 1, "L": 2, "W": 3, "A": 4, "stamps": 5, "cov_stats": 6}[what]
+                 "stamps": (64,)}[what]
+        code = {"jac": 0, "resid": 1, "L": 2, "W": 3, "A": 4, "stamps": 5}[what]
         out = np.empty(shape)
         self._check(self.lib.ekf_debug_fetch(self.h, code, _dptr(out), out.size))
         return out

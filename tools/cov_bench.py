@@ -43,22 +43,6 @@ def main():
             us, cnt = hip.kernel_timing()["cov_update"]
             hip.set_kernel_timing(0)
             hip.sync()
-            import os
-            if os.environ.get("COV_STATS"):      # (diagnostic builds of the macro-tile kernel: -DCM_STAMPS)
-                hip.debug_enable_stamps(light=True)
-                hip.debug_fetch("cov_stats", m)
-                nf = 10
-                hip.observe_sequence(idx[:nf], z[:nf])
-                hip.sync()
-                a = hip.debug_fetch("A", m)      # per-workgroup timeline of the last launch (diagnostic build)
-                nwg = int(os.environ.get("COV_GRID", "4800"))
-                rows = [a[b // 1500, 8 * (b % 1500): 8 * (b % 1500) + 8] for b in range(nwg)]
-                tl = np.array([r for r in rows if r[1] > 0])
-                if len(tl):
-                    np.save(os.environ.get("COV_TL", "gpurun_out/cov_timeline.npy"), tl)
-                    dur = (tl[:, 1] - tl[:, 0]) / 100
-                    print(f"   timeline: {len(tl)} workgroups, mean {dur.mean():.2f} us each; cycles start->chunk0 {tl[:, 4].mean():.0f}  loop {tl[:, 5].mean():.0f}"
-                          f"  epilogue {tl[:, 6].mean():.0f}")
             k = 3 * m
             tf = dims * dims * k / (us * 1e-6) / 1e12
             print(f"n={n} m={m} {kern:11s} cov_update {us:8.2f} us ({cnt} launches)  executed {tf:6.1f} TF = {tf / 157.3:.3f} of peak"

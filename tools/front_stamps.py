@@ -32,7 +32,7 @@ for b in range(0 if light else nb):
           "  (chain alone %d; from the barrier: next owner's panel posted +%d, next chain starts +%d)" % (
               (st[48+2*b]-st[47+2*b]) if b < 4 else (st[49+2*b]-st[48+2*b]), st[16+b]-st[2+2*b],
               ((st[47+2*(b+1)] if b+1 < 4 else st[48+2*(b+1)]) - st[2+2*b]) if b+1 < nb else 0))
-if light: print("chunk0: start",us(32)," A in LDS",us(33), "  (prologue detail: tools/chunk_stamps.py ... diag with a -DFR_CHUNK_DIAG build)")
+if light: print("chunk0: start",us(32)," A in LDS",us(33))
 else: print("chunk0: start",us(32)," indices in LDS",us(41)," operands staged",us(45)," MFMAs done",us(46)," tile done (wave 0)",us(42)," all tiles",us(43)," Jacobian in LDS",us(44)," picked",us(14)," prefetch issued",us(15)," A in LDS",us(33))
 for q in range(nb): print("  step",q,"done",us(34+q))
 print("  W/dx stored",us(34+nb))

@@ -1,0 +1,259 @@
+"""``EKFBatch``: many independent ``EKF`` filters replayed at once on one GPU (the batch C ABI of
+``include/ekf_slam_hip.h``, kernel ``csrc/ekf_batch.hip``).
+
+What users of a filter of this size run is many sequences: a set of recorded runs, a sweep of the noise constants, Monte-Carlo
+studies on re-noised detections.  Each member is ``BaseFilter.process_detection_log`` with ``should_filter=True`` over its
+own log, with its own initial pose, noise constants and marker-id -> landmark-index table; one workgroup owns one member, so
+a batch fills the GPU where a single filter of this size leaves it almost idle.  All members share the model (``EKF``), the
+quaternion convention, an f64 covariance and the capacity (``max_landmarks`` <= 82, ``max_visible`` <= 16).  A batch never
+grows; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .filters.base_filter import plan_detection_log
+from .hip_backend import EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError, _dptr, load_library
+
+NOISE_KEYS = ("initial_camera_uncertainty", "initial_landmark_uncertainty", "r_uncertainty", "q_cam", "q_err", "q_lm")
+EKF_ERR_NUMERIC = -5
+QUAT_MODES = {"as_written": EKF_QUAT_AS_WRITTEN, "scalar_first": EKF_QUAT_SCALAR_FIRST}
+
+
+def _iptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _lptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+class EKFBatch:
+    """``members`` filters.  ``initial_camera_pose``: [10] for all or [B, 10]; ``noise``: dict of scalars or length-B arrays
+    keyed by ``NOISE_KEYS`` (missing keys: the ``EKF`` constants)."""
+
+    def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
+                 quat_update: str = "as_written", noise=None, device: str = "cuda:0") -> None:
+        import torch
+        if quat_update not in QUAT_MODES:
+            raise ValueError(f"quat_update must be one of {sorted(QUAT_MODES)}, got {quat_update!r}")
+        unknown = set(noise or {}) - set(NOISE_KEYS)
+        if unknown:
+            raise ValueError(f"unknown noise constants {sorted(unknown)}; known: {list(NOISE_KEYS)}")
+        self._torch = torch
+        self.lib = load_library()
+        if not torch.cuda.is_available():
+            raise RuntimeError("the EKF update path needs a HIP device (no CPU fallback)")
+        self.members = int(members)
+        self.device = torch.device(device)
+        self.quat_update = quat_update
+        cfg = EkfConfig()
+        self._check(self.lib.ekf_default_config(C.byref(cfg)))
+        cfg.max_landmarks, cfg.max_visible = int(max_landmarks), int(max_visible)
+        cfg.quat_mode = QUAT_MODES[quat_update]
+        self.max_landmarks, self.max_visible = int(max_landmarks), int(max_visible)
+        defaults = np.array([getattr(cfg, k) for k in NOISE_KEYS])
+        self.noise = np.tile(defaults, (self.members, 1))
+        for key, val in (noise or {}).items():
+            self.noise[:, NOISE_KEYS.index(key)] = np.broadcast_to(np.asarray(val, dtype=np.float64), (self.members,))
+        self._initial_poses = np.ascontiguousarray(
+            np.broadcast_to(np.asarray(initial_camera_pose, dtype=np.float64), (self.members, 10)))
+        with torch.cuda.device(self.device):
+            self.stream = torch.cuda.Stream(device=self.device)
+            cfg.stream = self.stream.cuda_stream
+            ld, cb, sb, wb = C.c_int64(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+            self._check(self.lib.ekf_batch_query_sizes(C.byref(cfg), self.members, C.byref(ld), C.byref(cb), C.byref(sb),
+                                                       C.byref(wb)))
+            self.ld = ld.value
+            self.cov_t = torch.zeros((self.members, self.ld, self.ld), dtype=torch.float64, device=self.device)
+            self.state_t = torch.zeros((self.members, self.ld), dtype=torch.float64, device=self.device)
+            self.ws_t = torch.zeros((wb.value,), dtype=torch.uint8, device=self.device)
+            torch.cuda.synchronize(self.device)
+            handle = C.c_void_p()
+            self._check(self.lib.ekf_batch_create(C.byref(cfg), self.members, C.byref(handle)))
+            self.h = handle
+            self._check(self.lib.ekf_batch_bind_buffers(self.h, self.cov_t.data_ptr(), self.ld, self.state_t.data_ptr(),
+                                                        self.ws_t.data_ptr(), wb.value))
+            self._check(self.lib.ekf_batch_set_noise(self.h, _dptr(np.ascontiguousarray(self.noise))))
+        self.cfg = cfg
+        self.landmarks = [{} for _ in range(self.members)]
+        self.num_landmarks = [0] * self.members
+        self.reset()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise EkfError(rc, self.lib.ekf_last_error_string().decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ekf_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _member(self, b) -> int:
+        b = int(b)
+        if not 0 <= b < self.members:
+            raise IndexError(f"member {b} out of range 0..{self.members - 1}")
+        return b
+
+    # -- replay ------------------------------------------------------------------------------------------------------
+    def process_detection_logs(self, logs) -> list:
+        """One log per member (``None``: no log), each a dict of the replay layout ``ids [D]``, ``poses [D,6]``,
+        ``offsets [F+1]`` and optionally ``has_detections [F]``.  Returns the camera pose ``state[0:7]`` after every frame,
+        one ``(F_b, 7)`` array per member.  A malformed log raises ``ValueError``, a log that needs more landmarks or
+        detections per frame than the batch holds ``EkfError`` (EKF_ERR_CAPACITY); either way before anything runs, and no
+        member (``landmarks`` included) changes."""
+        if len(logs) != self.members:
+            raise ValueError(f"need {self.members} logs (None for a member without one), got {len(logs)}")
+        plans, index, offsets, frames, poses = [], [], [], [0], []
+        base = 0
+        for b, log in enumerate(logs):
+            if log is None:
+                plans.append(None)
+                frames.append(frames[-1])
+                continue
+            plan = plan_detection_log(self.landmarks[b], self.num_landmarks[b], log["ids"], log["offsets"],
+                                      log.get("has_detections"))
+            p = np.asarray(log["poses"], dtype=np.float64)
+            if p.shape != (plan.keep.shape[0], 6):
+                raise ValueError(f"member {b}: poses must have shape ({plan.keep.shape[0]}, 6), got {p.shape}")
+            plans.append(plan)
+            index.append(plan.index)
+            offsets.append(plan.offsets[1:] + base)
+            base += plan.index.shape[0]
+            frames.append(frames[-1] + plan.offsets.shape[0] - 1)
+            poses.append(p[plan.keep])
+        index = np.concatenate(index).astype(np.int32) if index else np.zeros(0, np.int32)
+        offsets = np.concatenate([np.zeros(1, np.int64)] + offsets).astype(np.int64)
+        poses = np.ascontiguousarray(np.concatenate(poses) if poses else np.zeros((0, 6)))
+        traj = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses)
+        counts = self._num_landmarks_device()
+        for b, plan in enumerate(plans):
+            if plan is not None:        # (a member that failed keeps the landmarks it added before it stopped)
+                self.landmarks[b].update((k, j) for k, j in plan.new_landmarks.items() if j < counts[b])
+            self.num_landmarks[b] = int(counts[b])
+        return [traj[frames[b]:frames[b + 1]] for b in range(self.members)]
+
+    def observe_indexed(self, lm_index, frame_offsets, member_frames, poses) -> np.ndarray:
+        """The C call behind ``process_detection_logs`` (landmark indices already assigned; ``landmarks`` is not
+        touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1], poses [D,6] on the host.  Returns the
+        trajectory [Ftot, 7]."""
+        torch = self._torch
+        idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
+        fo = np.ascontiguousarray(frame_offsets, dtype=np.int64).reshape(-1)
+        mf = np.ascontiguousarray(member_frames, dtype=np.int64).reshape(-1)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 6)
+        if mf.shape[0] != self.members + 1 or mf[0] != 0 or (np.diff(mf) < 0).any():
+            raise ValueError(f"member_frames must be {self.members + 1} non-decreasing offsets from 0")
+        frames = int(mf[-1])
+        if fo.shape[0] != frames + 1:
+            raise ValueError(f"frame_offsets must have {frames + 1} entries")
+        if poses.shape[0] != idx.shape[0] or (frames and fo[-1] != idx.shape[0]):
+            raise ValueError("frame_offsets, lm_index and poses do not match")
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_batch_log_workspace_bytes(self.h, idx.shape[0], frames, C.byref(nbytes)))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            poses_t = torch.from_numpy(poses).to(self.device)
+            ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
+            traj = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
+            self._check(self.lib.ekf_batch_observe_logs(self.h, _iptr(idx), _lptr(fo), _lptr(mf),
+                                                        poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
+                                                        nbytes.value, traj.data_ptr() if frames else None))
+            self.stream.synchronize()
+        return traj.cpu().numpy()
+
+    # -- per-member state ---------------------------------------------------------------------------------------------
+    def _num_landmarks_device(self) -> np.ndarray:
+        out = np.zeros(self.members, dtype=np.int32)
+        self._check(self.lib.ekf_batch_num_landmarks(self.h, _iptr(out)))
+        return out
+
+    def status(self) -> list:
+        """Per member: 0, or EKF_ERR_NUMERIC (-5) for a member stopped by a non-positive pivot of its innovation
+        covariance (until ``reset`` or ``set_member``)."""
+        out = np.zeros(self.members, dtype=np.int32)
+        self._check(self.lib.ekf_batch_status(self.h, _iptr(out)))
+        return [int(v) for v in out]
+
+    def get_state(self, b) -> np.ndarray:
+        b = self._member(b)
+        out = np.empty(3 * self.num_landmarks[b] + 10)
+        self._check(self.lib.ekf_batch_get_member(self.h, b, _dptr(out), out.shape[0], None, 0))
+        return out
+
+    def get_cov(self, b) -> np.ndarray:
+        b = self._member(b)
+        dims = 3 * self.num_landmarks[b] + 10
+        out = np.empty((dims, dims))
+        self._check(self.lib.ekf_batch_get_member(self.h, b, None, 0, _dptr(out), dims))
+        return out
+
+    def get_poses(self, b):
+        """``EKF.get_poses`` of member b: camera state [10], landmarks [n, 3]."""
+        state = self.get_state(b)
+        return state[:10], state[10:].reshape(-1, 3)
+
+    def get_lm_uncertainties(self, b) -> np.ndarray:
+        return np.diagonal(self.get_cov(b))[10:].reshape(-1, 3).copy()
+
+    def set_member(self, b, state, cov, marker_ids) -> None:
+        """Member b from host ``(state [3n+10], cov [3n+10, 3n+10], marker ids in landmark-index order)``; clears its
+        status.  cov is symmetrised on upload."""
+        b = self._member(b)
+        state = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
+        ids = [int(k) for k in marker_ids]
+        if state.shape[0] != 3 * len(ids) + 10:
+            raise ValueError(f"state has {state.shape[0]} entries, {3 * len(ids) + 10} expected for {len(ids)} markers")
+        cov = np.ascontiguousarray(cov, dtype=np.float64)
+        if cov.shape != (state.shape[0], state.shape[0]):
+            raise ValueError(f"cov must be {state.shape[0]} x {state.shape[0]}")
+        self._check(self.lib.ekf_batch_set_member(self.h, b, _dptr(state), len(ids), _dptr(cov)))
+        self.landmarks[b] = {k: i for i, k in enumerate(ids)}
+        self.num_landmarks[b] = len(ids)
+
+    def load_filter(self, b, ekf) -> None:
+        """Member b from an ordinary ``EKF``: its state, covariance and landmark table.  The filter must be an ``EKF`` (not
+        ``EKF_Rotations``) with the batch's quaternion convention.  The member keeps its own noise constants (a sweep loads
+        one filter into members that differ in nothing else)."""
+        from .filters.extended_kalman_filter import EKF
+        if not isinstance(ekf, EKF):
+            raise ValueError(f"a batch holds EKF filters, got {type(ekf).__name__}")
+        if ekf.backend.cfg.quat_mode != QUAT_MODES[self.quat_update]:
+            raise ValueError(f"the filter's quaternion convention differs from the batch's ({self.quat_update!r})")
+        ids = [k for k, _ in sorted(ekf.get_lm_estimates(), key=lambda kv: kv[1])]
+        self.set_member(b, np.asarray(ekf.state, dtype=np.float64), ekf.uncertainty, ids)
+
+    def to_filter(self, b):
+        """An ordinary ``EKF`` (f64 covariance) with member b's quaternion convention, noise constants, state, covariance and
+        landmark table; ``observe``, ``save_map`` and ``save_checkpoint`` work on it."""
+        from .filters.extended_kalman_filter import EKF
+        b = self._member(b)
+        state, cov = self.get_state(b), self.get_cov(b)
+        n = self.num_landmarks[b]
+        ekf = EKF(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
+                  quat_update=self.quat_update, device=str(self.device),
+                  noise=dict(zip(NOISE_KEYS, (float(v) for v in self.noise[b]))))
+        ekf.backend.set_state_cov(state, cov)
+        ekf.landmarks = dict(self.landmarks[b])
+        ekf.num_landmarks = n
+        return ekf
+
+    def reset(self, b=None) -> None:
+        """Member b (all members: None) back to its initial pose, no landmarks, status cleared."""
+        if b is None:
+            self._check(self.lib.ekf_batch_reset(self.h, -1, _dptr(self._initial_poses)))
+            members = range(self.members)
+        else:
+            b = self._member(b)
+            self._check(self.lib.ekf_batch_reset(self.h, b, _dptr(np.ascontiguousarray(self._initial_poses[b]))))
+            members = (b,)
+        for m in members:
+            self.landmarks[m] = {}
+            self.num_landmarks[m] = 0

@@ -187,6 +187,30 @@ void ekf_launch_log_fill_rows(double* traj_dev, const int32_t* pairs, int32_t co
 template <typename T>
 void ekf_launch_cov_diag(const void* cov, int64_t ld, double* out_dev, int32_t count, hipStream_t s);
 
+// Batch of independent EKF filters (ekf_batch.hip): one workgroup per member, frames [member_frames[b] + window_first,
+// + window_frames) of its log.  Everything is validated on the host (indices, first-sighting order, widths, capacity).
+#define EKF_BATCH_MAX_LANDMARKS 82   // N = 3 n + 10 <= 256: one column per thread of the 256-thread workgroup
+#define EKF_BATCH_MAX_VISIBLE 16     // k = 3 m <= 48 rows
+#define EKF_BATCH_ST_NUMERIC (-5)    // per-member status after a failed pivot (= EKF_ERR_NUMERIC)
+struct EkfBatchWindow {
+    double* P;                      // [B][ld][ld] f64
+    int64_t ld;
+    double* state;                  // [B][ld]
+    const double* noise;            // [B][6] in ekf_config order
+    int32_t* status;                // [B] 0 or EKF_BATCH_ST_NUMERIC (sticky)
+    int32_t* nlm;                   // [B] landmarks
+    const int32_t* lm_index;        // [D]
+    const int64_t* frame_offsets;   // [Ftot + 1] detection offsets, frame after frame, member after member
+    const int64_t* member_frames;   // [B + 1] frame offsets per member
+    const double* poses;            // [D][6] [tvec | rvec]; z = pose[0:3]
+    double* traj;                   // [Ftot][7] or null
+    int32_t quat_mode;
+    int32_t window_first, window_frames;
+    int32_t kmax, lda;              // LDS layout: rows of A / W, row length of A / W (> N; column N holds the residual)
+};
+extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);   // dynamic LDS of one launch (C linkage: the tests read it)
+void ekf_launch_batch_window(const EkfBatchWindow& a, int members, hipStream_t s);
+
 // Detection -> pose front end (ekf_pose_ippe.hip): pinhole camera + Brown-Conrady distortion k1 k2 p1 p2 k3 k4 k5 k6
 struct EkfCamera {
     double fx, fy, cx, cy;

@@ -36,14 +36,16 @@ class EKF(BaseFilter):
                  max_visible: int | None = None, cov_dtype: str = "float64",
                  quat_update: str = "as_written", cov_kernel: str = "auto",
                  device: str = "cuda:0", map_file=None, lookahead: bool | None = None,
-                 fused: bool = True) -> None:
+                 fused: bool = True, noise: dict | None = None) -> None:
         """Positional arguments as the reference (:40-43).  Keyword-only extras:
         initial capacity (default: the number of ids of ``aruco_dict`` -- DICT_5X5_50
         has 50, base_filter.py:81-82; the buffers grow when more markers or more
         detections per frame show up, as the reference's arrays do, :274-290), covariance
         storage dtype, and the quaternion-injection convention
         (``"as_written"`` reproduces :138-149 exactly, ``"scalar_first"`` is the
-        consistent one)."""
+        consistent one).  ``noise``: values that replace the module's noise constants, keyed by the
+        ``ekf_config`` field names (``initial_camera_uncertainty``, ``initial_landmark_uncertainty``,
+        ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``); None keeps the reference's constants."""
         super().__init__(initial_camera_pose, map_file, aruco_dict)
         self._initial_pose = np.array(initial_camera_pose)      # :46, dtype kept
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -54,12 +56,17 @@ class EKF(BaseFilter):
             max_landmarks = dictionary_size(aruco_dict)
         if max_visible is None:
             max_visible = min(max_landmarks, 64)
+        constants = {"initial_camera_uncertainty": INITIAL_CAMERA_UNCERTAINTY,
+                     "initial_landmark_uncertainty": INITIAL_LANDMARK_UNCERTAINTY,
+                     "r_uncertainty": R_UNCERTAINTY, "q_cam": Q_UNCERTAINTY_CAM,
+                     "q_err": Q_ERROR_UNCERTAINTY_CAM, "q_lm": Q_UNCERTAINTY_LM}
+        unknown = set(noise or {}) - set(constants)
+        if unknown:
+            raise ValueError(f"unknown noise constants {sorted(unknown)}; known: {sorted(constants)}")
+        constants.update(noise or {})
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype,
                            quat_mode=quat_update, cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
-                           noise={"initial_camera_uncertainty": INITIAL_CAMERA_UNCERTAINTY,
-                                  "initial_landmark_uncertainty": INITIAL_LANDMARK_UNCERTAINTY,
-                                  "r_uncertainty": R_UNCERTAINTY, "q_cam": Q_UNCERTAINTY_CAM,
-                                  "q_err": Q_ERROR_UNCERTAINTY_CAM, "q_lm": Q_UNCERTAINTY_LM})
+                           noise=constants)
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._load_initial_map()
 

@@ -29,6 +29,9 @@ EXPORTED_SYMBOLS = (
     "ekf_set_fused", "ekf_set_kernel_timing", "ekf_get_kernel_timing", "ekf_debug_fetch",
     "ekf_estimate_poses_device", "ekf_estimate_poses", "ekf_last_error_string",
     "ekf_log_workspace_bytes", "ekf_observe_log", "ekf_last_log_stats",
+    "ekf_batch_query_sizes", "ekf_batch_create", "ekf_batch_bind_buffers", "ekf_batch_destroy", "ekf_batch_set_noise",
+    "ekf_batch_reset", "ekf_batch_set_member", "ekf_batch_get_member", "ekf_batch_num_landmarks", "ekf_batch_status",
+    "ekf_batch_log_workspace_bytes", "ekf_batch_observe_logs",
 )
 
 
@@ -98,6 +101,19 @@ def load_library(path: str | Path | None = None):
         "ekf_log_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],
         "ekf_observe_log": [vp, ip, C.POINTER(C.c_int64), C.c_int32, vp, vp, C.c_size_t, vp],
         "ekf_last_log_stats": [vp, C.POINTER(C.c_int64)],
+        "ekf_batch_query_sizes": [C.POINTER(EkfConfig), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_size_t),
+                                  C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+        "ekf_batch_create": [C.POINTER(EkfConfig), C.c_int32, C.POINTER(vp)],
+        "ekf_batch_bind_buffers": [vp, vp, C.c_int64, vp, vp, C.c_size_t],
+        "ekf_batch_destroy": [vp],
+        "ekf_batch_set_noise": [vp, dp],
+        "ekf_batch_reset": [vp, C.c_int32, dp],
+        "ekf_batch_set_member": [vp, C.c_int32, dp, C.c_int32, dp],
+        "ekf_batch_get_member": [vp, C.c_int32, dp, C.c_int32, dp, C.c_int32],
+        "ekf_batch_num_landmarks": [vp, ip],
+        "ekf_batch_status": [vp, ip],
+        "ekf_batch_log_workspace_bytes": [vp, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)],
+        "ekf_batch_observe_logs": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, vp, C.c_size_t, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -263,6 +263,50 @@ int ekf_estimate_poses(const double *corners, int32_t count, double marker_size,
                        const double camera_matrix[9], const double *dist_coeffs, int32_t n_dist,
                        double *poses, void *stream);
 
+/* ---- Batch of independent filters: many detection logs replayed at once (parameter sweeps, evaluation sets, Monte-Carlo
+ * runs).  Every member is BaseFilter.process_detections with should_filter=True over its own log, exactly as
+ * ekf_observe_log does it; one workgroup owns one member for a window of frames, members never wait for each other.
+ *
+ * cfg: model must be EKF_MODEL_EKF, cov_dtype EKF_COV_F64, max_landmarks <= 82, max_visible <= 16 (N = 3 n + 10 <= 256,
+ * k = 3 m <= 48); flags and cov_kernel are ignored; the noise constants of cfg are every member's defaults.
+ * Memory is the caller's, as for single filters: cov [B, ld, ld] f64, state [B, ld] f64 (capacity padding exactly zero),
+ * a workspace of workspace_bytes, all 256-byte aligned.  ekf_batch_bind_buffers resets every member to the identity pose.
+ * A batch never grows. */
+typedef struct ekf_batch ekf_batch; /* opaque handle */
+int ekf_batch_query_sizes(const ekf_config *cfg, int32_t members, int64_t *ld, size_t *cov_bytes, size_t *state_bytes,
+                          size_t *workspace_bytes);
+int ekf_batch_create(const ekf_config *cfg, int32_t members, ekf_batch **out);
+int ekf_batch_bind_buffers(ekf_batch *b, double *cov_dev, int64_t ld, double *state_dev, void *ws_dev, size_t ws_bytes);
+int ekf_batch_destroy(ekf_batch *b);
+/* noise [B,6] per member in ekf_config order: initial_camera_uncertainty, initial_landmark_uncertainty, r_uncertainty,
+ * q_cam, q_err, q_lm (initial_camera_uncertainty takes effect at the next reset). */
+int ekf_batch_set_noise(ekf_batch *b, const double *noise);
+/* state = initial pose, P = initial_camera_uncertainty I_10, no landmarks, status cleared.
+ * member = -1: every member, initial_poses [B,10]; member >= 0: that member, initial_poses [10]. */
+int ekf_batch_reset(ekf_batch *b, int32_t member, const double *initial_poses);
+/* one member from host f64: state [3 n + 10], cov [3 n + 10, 3 n + 10] (symmetrised on upload); clears its status */
+int ekf_batch_set_member(ekf_batch *b, int32_t member, const double *state, int32_t num_landmarks, const double *cov);
+/* state[0:count] and, unless cov is NULL, the covariance [dims, dims] (dims = 3 n + 10) of one member; synchronises */
+int ekf_batch_get_member(ekf_batch *b, int32_t member, double *state, int32_t count, double *cov /* or NULL */, int32_t dims);
+int ekf_batch_num_landmarks(const ekf_batch *b, int32_t *out /* [B] */);
+/* out [B]: 0, or EKF_ERR_NUMERIC for a member whose innovation covariance had a non-positive or non-finite pivot: that
+ * member stopped at that frame (its update left state and covariance as they were, the frame's first sightings stay
+ * added) and its remaining trajectory rows are NaN, until ekf_batch_reset or ekf_batch_set_member.  Synchronises. */
+int ekf_batch_status(ekf_batch *b, int32_t *out /* [B] */);
+int ekf_batch_log_workspace_bytes(const ekf_batch *b, int64_t detections, int64_t frames, size_t *bytes);
+/* One log per member, in one call:
+ *   lm_index [D]            HOST  landmark index of every detection, same rules as ekf_observe_log, per member
+ *   frame_offsets [Ftot+1]  HOST  detection offsets, frame after frame, member after member
+ *   member_frames [B+1]     HOST  frame offsets per member (equal entries: no log for that member)
+ *   poses_dev [D,6]         DEVICE [tvec | rvec] as logged
+ *   log_ws                  DEVICE 256-byte aligned, ekf_batch_log_workspace_bytes(D, Ftot)
+ *   trajectory_dev [Ftot,7] DEVICE or NULL  state[0:7] after every frame
+ * Everything is validated on the host before anything is enqueued (EKF_ERR_INVALID / EKF_ERR_CAPACITY; no member
+ * changes).  Then, on the batch's stream, one copy of indices and offsets and one launch per window of 64 frames per
+ * member.  Returns once the work is enqueued; the getters synchronise. */
+int ekf_batch_observe_logs(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets, const int64_t *member_frames,
+                           const double *poses_dev, void *log_ws, size_t log_ws_bytes, double *trajectory_dev);
+
 const char *ekf_last_error_string(void);
 
 #ifdef __cplusplus

@@ -404,6 +404,12 @@ class HipEkf:
     def set_fused(self, enable: bool):
         """Fused front kernel (True) or the three stage kernels (False) from the next frame on."""
         self._check(self.lib.ekf_set_fused(self.h, int(bool(enable))))
+        # the library flips flags bit 2 of its own copy of the configuration; grow() sizes the new workspace from this one
+        # (the second covariance buffer of the pipelined sequence mode exists only without bit 2), so keep them in step
+        if enable:
+            self.cfg.flags &= ~4
+        else:
+            self.cfg.flags |= 4
         self.fused = bool(enable)
 
     def debug_enable_w(self):

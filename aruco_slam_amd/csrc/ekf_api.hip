@@ -1,23 +1,14 @@
-// C ABI of the EKF-SLAM HIP library (see include/ekf_slam_hip.h).
-// Host side only: argument checking, workspace carving, launch sequencing.
-#include "../../include/ekf_slam_hip.h"
-
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
+// C ABI of the EKF-SLAM HIP library (see include/ekf_slam_hip.h): the filter handle.  The batch handle is in
+// ekf_batch_api.hip.  Host side only: argument checking, workspace carving, launch sequencing.
 #include <atomic>
-#include <cmath>
-#include <cstdlib>
-#include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
 
+#include "ekf_host.h"
 #include "ekf_kernels.h"
 
-namespace {
-
 thread_local std::string g_err;
+
+namespace {
 
 // Pipelined sequence mode orders its two streams with device-side gates that spin.  HIP multiplexes streams onto a small
 // pool of hardware queues: with two handles pipelining at once, handle X's gate can sit in the queue in front of the
@@ -26,20 +17,7 @@ thread_local std::string g_err;
 // (same results, bit for bit) and says so (ekf_last_sequence_mode).
 std::atomic<ekf_filter*> g_pipelining{nullptr};
 
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return fail(EKF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-inline int64_t round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+void release_pipelining_token(ekf_filter* f) { (void)g_pipelining.compare_exchange_strong(f, nullptr); }
 
 constexpr int kStageSlots = 64;   // pinned host ring for ekf_observe
 constexpr int kMacroSuper = 8;    // macro-tile covariance update: super-tiles of 8 x 8 macro tiles per XCD (ekf_cov_macro.hip)
@@ -67,6 +45,7 @@ struct Layout {
     bool has_cov2;
     size_t off_tiles; // launch order of the macro-tile covariance update (f32, large problems)
     int tiles_cap;    // entries
+    size_t slot_bytes;   // one slot of the pinned staging ring (reserve_host_buffers)
     // fused front kernel: one exchange buffer per fused-frame parity (offsets / length in doubles)
     size_t xl_len, xl_dop, xl_y, xl_jac, xl_tag, xl_xs, xl_xr, xl_stag;
 };
@@ -80,36 +59,35 @@ Layout make_layout(const ekf_config& c) {
     const bool wide = c.max_visible > visible_cap(c.model);
     L.kmax = (int)round_up(L.rd * c.max_visible, wide ? EKF_WIDE_BLOCK : EKF_RB);
     L.elem = c.cov_dtype == EKF_COV_F32 ? 4 : 8;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += align256(bytes); return at; };
-    L.off_jac = take((size_t)L.kmax * EKF_JLD * 8);
-    L.off_resid = take((size_t)L.kmax * 8);
-    L.off_y = take((size_t)L.kmax * 8);
-    L.off_lmcol = take((size_t)c.max_visible * 4);
-    L.off_amat = take((size_t)L.kmax * L.cap * 8);
-    L.off_sblk = take((size_t)(L.kmax / EKF_RB) * (L.kmax / EKF_RB + 1) / 2 * 256 * 8);
-    L.off_lmat = take((size_t)L.kmax * L.kmax * 8);
-    L.off_dinv = take((size_t)L.kmax * EKF_RB * 8);
+    Carve w;
+    L.off_jac = w.take((size_t)L.kmax * EKF_JLD * 8);
+    L.off_resid = w.take((size_t)L.kmax * 8);
+    L.off_y = w.take((size_t)L.kmax * 8);
+    L.off_lmcol = w.take((size_t)c.max_visible * 4);
+    L.off_amat = w.take((size_t)L.kmax * L.cap * 8);
+    L.off_sblk = w.take((size_t)(L.kmax / EKF_RB) * (L.kmax / EKF_RB + 1) / 2 * 256 * 8);
+    L.off_lmat = w.take((size_t)L.kmax * L.kmax * 8);
+    L.off_dinv = w.take((size_t)L.kmax * EKF_RB * 8);
     {
         const size_t nb = (size_t)L.kmax / EKF_RB;
-        L.off_lop = take(nb * (nb - 1) / 2 * 256 * 8 + 256);
-        L.off_dop = take(nb * 256 * 8);
+        L.off_lop = w.take(nb * (nb - 1) / 2 * 256 * 8 + 256);
+        L.off_dop = w.take(nb * 256 * 8);
     }
-    L.off_wpanel = take((size_t)L.kmax * L.cap * L.elem);
-    L.off_wpanel2 = take((size_t)L.kmax * L.cap * L.elem);
+    L.off_wpanel = w.take((size_t)L.kmax * L.cap * L.elem);
+    L.off_wpanel2 = w.take((size_t)L.kmax * L.cap * L.elem);
     // pipelined sequence mode (MFMA update, fused front kernel): the second covariance buffer
     // (P_t is read, P_{t+1} written elsewhere, so that the next front kernel can read P_t beside the update)
     L.has_cov2 = c.cov_kernel != EKF_COVK_VALU && (c.flags & 5) == 0;
-    L.off_cov2 = L.has_cov2 ? take((size_t)L.cap * L.cap * L.elem) : 0;
-    L.off_wdbg = take((size_t)L.kmax * L.cap * 8);
-    L.off_idx = take((size_t)c.max_visible * 4);
-    L.off_z = take((size_t)c.max_visible * 7 * 8);
-    L.off_status = take(256);
-    L.off_stamps = take(64 * 8);
-    L.off_dx = take((size_t)L.cap * 8);
-    L.off_diag = take((size_t)L.cap * 8);
-    L.off_xyz = take((size_t)256 * 6 * 8);
-    L.off_unc = take((size_t)256 * 10 * 8);
+    L.off_cov2 = L.has_cov2 ? w.take((size_t)L.cap * L.cap * L.elem) : 0;
+    L.off_wdbg = w.take((size_t)L.kmax * L.cap * 8);
+    L.off_idx = w.take((size_t)c.max_visible * 4);
+    L.off_z = w.take((size_t)c.max_visible * 7 * 8);
+    L.off_status = w.take(256);
+    L.off_stamps = w.take(64 * 8);
+    L.off_dx = w.take((size_t)L.cap * 8);
+    L.off_diag = w.take((size_t)L.cap * 8);
+    L.off_xyz = w.take((size_t)256 * 6 * 8);
+    L.off_unc = w.take((size_t)256 * 10 * 8);
     {
         const size_t nb = (size_t)L.kmax / EKF_RB;
         L.xl_dop = nb * (nb - 1) / 2 * 256 + 64;
@@ -120,23 +98,26 @@ Layout make_layout(const ekf_config& c) {
         L.xl_xr = L.xl_xs + nb * (nb + 1) / 2 * 256;      // residual
         L.xl_stag = L.xl_xr + (size_t)round_up(L.kmax, 16);   // S-block tags [16 tc + i]
         L.xl_len = L.xl_stag + 256;
-        L.off_xl = take(2 * L.xl_len * 8);
-        L.off_done = take(256);
-        L.off_sync = take(256);
+        L.off_xl = w.take(2 * L.xl_len * 8);
+        L.off_done = w.take(256);
+        L.off_sync = w.take(256);
         L.wsup_ld = (int)round_up(EKF_CAM + (int64_t)L.lmd * c.max_visible, 32);
-        L.off_wsup = take((size_t)2 * L.kmax * L.wsup_ld * L.elem);
+        L.off_wsup = w.take((size_t)2 * L.kmax * L.wsup_ld * L.elem);
     }
     {
         // (the grid is 8 x the longest per-XCD list: the tile count plus, at worst, one super-tile per XCD)
         const int tmax = (int)(L.cap / 128);
         L.tiles_cap = (L.elem == 4 && c.cov_kernel != EKF_COVK_VALU && c.cov_kernel != EKF_COVK_MFMA_TILE)
                           ? tmax * (tmax + 1) / 2 + 8 * kMacroSuper * kMacroSuper : 0;
-        L.off_tiles = take((size_t)L.tiles_cap * 4);
+        L.off_tiles = w.take((size_t)L.tiles_cap * 4);
     }
     // wide frames beyond the stage kernels' size (ekf_wide.hip); configurations within the caps keep their sizes
-    L.off_wwork = wide ? take((size_t)L.kmax * L.cap * 8) : 0;
-    L.off_xinv = wide ? take((size_t)EKF_WIDE_BLOCK * EKF_WIDE_BLOCK * 8) : 0;
-    L.total = o;
+    L.off_wwork = wide ? w.take((size_t)L.kmax * L.cap * 8) : 0;
+    L.off_xinv = wide ? w.take((size_t)EKF_WIDE_BLOCK * EKF_WIDE_BLOCK * 8) : 0;
+    L.total = w.end;
+    // one slot of the pinned staging ring: a frame's detections as ekf_observe stages them, or 256 markers of ekf_add_markers
+    L.slot_bytes = std::max(align256((size_t)c.max_visible * 4) + align256((size_t)c.max_visible * 56),
+                            align256(256 * 48) + align256(256 * 80));
     return L;
 }
 
@@ -164,19 +145,35 @@ int check_config(const ekf_config* c) {
 
 }  // namespace
 
+// What a state getter may skip (sync_and_check).  Each entry point names what it did; the four flags follow from that alone.
+//   front_pending  ev_front marks where the state became final, and nothing that changes the state was enqueued since
+//   mirror_fresh   ... and the front kernel of that frame also wrote the state and the status word into the pinned mirror
+//   mirror_trust   entries no frame writes (EKF_Rotations: landmark error states) agree between mirror and device
+//   status_clean   the device status word was zero when it was last read
+// Only frame(true, true) -- a per-frame observe through the fused front kernel with timing off -- allows the zero-copy
+// getter (an event wait and no copy at all), while the mirror is trusted (a reset or a full read back since the last
+// state_set or new_workspace) and the status was clean at the last read back and is still zero in the mirror.
+struct GetterShortcut {
+    bool front_pending = false, mirror_fresh = false, mirror_trust = false, status_clean = false;
+    bool zero_copy() const { return mirror_fresh && mirror_trust && status_clean; }
+    void frame(bool recorded, bool mirrored) { front_pending = recorded; mirror_fresh = mirrored; }
+    void run() { front_pending = status_clean = false; }   // (no front kernel of a run records ev_front; gate kernels
+                                                           // raise status bits without the host word)
+    void log() { front_pending = mirror_fresh = false; }
+    void markers_added() { front_pending = false; }
+    void state_set() { front_pending = mirror_trust = false; }
+    void reset() { *this = {false, false, true, true}; }   // (state and mirror are both zero beyond what frames write)
+    void new_workspace() { *this = {}; }
+    void read_back(bool clean, bool full_state) { status_clean = clean; mirror_trust = mirror_trust || full_state; }
+};
+
 struct ekf_filter {
     ekf_config cfg{};
     Layout lay{};
     hipStream_t stream = nullptr;
     hipStream_t big = nullptr;          // internal stream: big covariance update in sequence mode
-    hipEvent_t ev_small[2] = {}, ev_big[2] = {};
     hipEvent_t ev_front = nullptr;      // recorded behind the front part of the last per-frame observe: the state is final there
-    bool front_pending = false;         // ... and nothing that changes the state has been enqueued since
-    // host mirror of the state (readback + 256) and of "the status word is not zero" (readback + 128), written by the fused
-    // front kernel of a per-frame observe: a state getter is then an event wait and a memcpy
-    bool mirror_fresh = false;          // the last frame wrote the mirror
-    bool mirror_trust = false;          // entries no frame writes (EKF_Rotations: landmark error states) agree with the device
-    bool status_clean = false;          // the device status word was zero when it was last read
+    GetterShortcut shortcut;
     int device = 0;
     void* cov = nullptr;
     int64_t ld = 0;
@@ -195,13 +192,12 @@ struct ekf_filter {
     int seq_mode = EKF_SEQ_NONE;   // what the last ekf_observe_sequence_device call did (ekf_last_sequence_mode)
     // macro-tile covariance update: launch-order table in the workspace, rebuilt when the tile count changes
     int tiles_T = -1, tiles_grid = 0;
-    uint32_t* tiles_host = nullptr;     // pinned staging copy
-    // pinned staging ring for host-pointer observes
-    char* pinned = nullptr;
-    size_t slot_bytes = 0;
+    // pinned host buffers sized by the capacity (reserve_host_buffers): the staging ring of host-pointer observes and
+    // markers (kStageSlots slots of lay.slot_bytes), the readback mirror [status words (256 B) | state (cap doubles)] (one
+    // sync per getter), the staging copy of the macro-tile table
+    PinnedBuffer ring, readback, tiles_host;
     int slot = 0;
     hipEvent_t slot_done[kStageSlots] = {};
-    char* readback = nullptr;           // pinned: [status words (256 B) | state (cap doubles)], one sync per getter
     // kernel timing
     bool timing = false;
     bool timing_cov_only = false;
@@ -212,8 +208,7 @@ struct ekf_filter {
     // log replay (ekf_observe_log): pinned staging of the landmark indices, first-sighting slots and empty-frame rows, two
     // buffers used by turns (a call waits only for the call before the previous one), each reused once the stream has passed
     // its `log_pin_done`; what the last call did
-    char* log_pin[2] = {};
-    size_t log_pin_bytes[2] = {};
+    PinnedBuffer log_pin[2];
     hipEvent_t log_pin_done[2] = {};
     int log_pin_turn = 0;
     int64_t log_stats[4] = {};
@@ -340,9 +335,9 @@ int ensure_tiles(ekf_filter* f) {
     if (f->tiles_T == T) return EKF_OK;
     HIP_TRY(hipStreamSynchronize(f->stream));
     HIP_TRY(hipStreamSynchronize(f->big));
-    const int grid = ekf_cov_macro_table(T, kMacroSuper, f->tiles_host, L.tiles_cap);
+    const int grid = ekf_cov_macro_table(T, kMacroSuper, f->tiles_host.at<uint32_t>(0), L.tiles_cap);
     if (grid <= 0) return fail(EKF_ERR_STATE, "macro-tile launch table does not fit the workspace");
-    HIP_TRY(hipMemcpy(f->at<uint32_t>(L.off_tiles), f->tiles_host, (size_t)grid * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(f->at<uint32_t>(L.off_tiles), f->tiles_host.get(), (size_t)grid * 4, hipMemcpyHostToDevice));
     f->tiles_T = T;
     f->tiles_grid = grid;
     return EKF_OK;
@@ -368,14 +363,13 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, in
     }
     hipEvent_t* ev_all = (ev && !f->timing_cov_only) ? ev : nullptr;
     if (ev_all) HIP_TRY(hipEventRecord(ev[0], f->stream));
-    f->mirror_fresh = false;
+    const bool mirrored = use_front_kernel(f, fr) && !f->timing && mirror;
     if (use_front_kernel(f, fr)) {
         // one launch: timing slot 0 = the whole front kernel, slots 1 and 2 stay empty
         bind_exchange(f, fr);
-        if (!f->timing && mirror) {
-            fr.state_host = reinterpret_cast<double*>(f->readback + 256);
-            fr.status_host = reinterpret_cast<int32_t*>(f->readback + 128);
-            f->mirror_fresh = true;
+        if (mirrored) {
+            fr.state_host = f->readback.at<double>(256);
+            fr.status_host = f->readback.at<int32_t>(128);
         }
         by_cov_type(f, [&](auto elem) { ekf_launch_front<decltype(elem)>(fr, f->stream); });
         if (ev_all) {
@@ -410,8 +404,7 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, in
     }
     // The state (and the status word) are final here: a state getter that follows waits for this event only and
     // reads back beside the covariance update (sync_and_check) -- what BaseFilter.process_frame does every frame.
-    f->front_pending = false;
-    if (!f->timing && hipEventRecord(f->ev_front, f->stream) == hipSuccess) f->front_pending = true;
+    f->shortcut.frame(!f->timing && hipEventRecord(f->ev_front, f->stream) == hipSuccess, mirrored);
     // the covariance update is timed by its own start / stop time stamps (what rocprofv3 reports), not by
     // events recorded around the launch (those also hold ~4 us of dispatch gap)
     if (fr.kpad > EKF_WIDE_REUSE_ROWS) {
@@ -449,30 +442,28 @@ int check_ready(ekf_filter* f) {
 // `state_count` > 0: the first state_count doubles of the state come back with the same synchronisation
 // (f->readback + 256): one stream sync per getter instead of a sync and two blocking copies
 int sync_and_check(ekf_filter* f, int state_count = 0) {
-    if (state_count > 0 && f->front_pending) {
+    if (state_count > 0 && f->shortcut.front_pending) {
         // State getter right after a per-frame observe: the state and the status word were final when the front part
         // of that frame ended; the covariance update behind it goes on while the host reads back (internal stream: idle
         // outside ekf_observe_sequence_device, ordered here by the host having seen the event) and prepares the next frame.
         HIP_TRY(hipEventSynchronize(f->ev_front));
         // ... and if the fused front kernel has written the state into the pinned mirror and nobody has raised a status
         // bit (their stores to host memory are complete with the kernel), there is nothing to copy at all
-        if (f->mirror_fresh && f->mirror_trust && f->status_clean &&
-            *reinterpret_cast<volatile int32_t*>(f->readback + 128) == 0)
+        if (f->shortcut.zero_copy() && *f->readback.at<volatile int32_t>(128) == 0)
             return EKF_OK;
-        HIP_TRY(hipMemcpyAsync(f->readback, f->at<int32_t>(f->lay.off_status), 32, hipMemcpyDeviceToHost, f->big));
-        HIP_TRY(hipMemcpyAsync(f->readback + 256, f->state, (size_t)state_count * 8, hipMemcpyDeviceToHost, f->big));
+        HIP_TRY(hipMemcpyAsync(f->readback.get(), f->at<int32_t>(f->lay.off_status), 32, hipMemcpyDeviceToHost, f->big));
+        HIP_TRY(hipMemcpyAsync(f->readback.at<double>(256), f->state, (size_t)state_count * 8, hipMemcpyDeviceToHost, f->big));
         HIP_TRY(hipStreamSynchronize(f->big));
     } else {
-        HIP_TRY(hipMemcpyAsync(f->readback, f->at<int32_t>(f->lay.off_status), 32, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(hipMemcpyAsync(f->readback.get(), f->at<int32_t>(f->lay.off_status), 32, hipMemcpyDeviceToHost, f->stream));
         if (state_count > 0)
-            HIP_TRY(hipMemcpyAsync(f->readback + 256, f->state, (size_t)state_count * 8, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(hipMemcpyAsync(f->readback.at<double>(256), f->state, (size_t)state_count * 8, hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(hipStreamSynchronize(f->stream));
-        ekf_filter* me = f;      // (everything this handle has enqueued is complete: its gates are gone)
-        (void)g_pipelining.compare_exchange_strong(me, nullptr);
+        release_pipelining_token(f);      // (everything this handle has enqueued is complete: its gates are gone)
     }
-    const int32_t st = reinterpret_cast<const int32_t*>(f->readback)[0];
-    f->status_clean = (st == 0);
-    if (state_count == f->dims()) f->mirror_trust = true;      // (a full copy has just refreshed the mirror)
+    const int32_t* info = f->readback.at<int32_t>(0);
+    const int32_t st = info[0];
+    f->shortcut.read_back(st == 0, state_count == f->dims());      // (a full copy has just refreshed the mirror)
     if (st != 0) {
         // (sticky until ekf_reset: after any of these the filter state is not trustworthy)
         if (st & EKF_ST_BAD_INDEX)
@@ -486,7 +477,6 @@ int sync_and_check(ekf_filter* f, int state_count = 0) {
         if (st & EKF_ST_TIMEOUT)   // a bounded wait inside the fused front kernel ran out (should never happen)
             return fail(EKF_ERR_NUMERIC, "internal: exchange wait timed out in the front kernel (status " +
                                              std::to_string(st) + ")");
-        const int32_t* info = reinterpret_cast<const int32_t*>(f->readback);
         if (info[2] >= 200)      // (ekf_solve_cw.h: a bounded wait on one of the factorisation's LDS flag words ran out; should never happen)
             return fail(EKF_ERR_NUMERIC, "internal: a wait inside the factorisation workgroup timed out (flag word " +
                                              std::to_string(info[2] - 200) + ")");
@@ -622,8 +612,7 @@ int run_pipelined(ekf_filter* f, int frames, FrameAt frame_at, void* other) {
     unsigned long long* sync = f->at<unsigned long long>(L.off_sync);
     int32_t* status = f->at<int32_t>(L.off_status);
     const uint64_t base = f->la_base;
-    f->front_pending = false;      // (no front kernel of a run records ev_front)
-    f->status_clean = false;       // (gate kernels raise status bits without the host word)
+    f->shortcut.run();
     // (stream B needs no edge from stream A at the start: its first launch is the gate in front of C(0), which waits
     // for "F(1) has started", i.e. for everything that is on stream A now and F(0); the previous run ended with
     // stream A waiting for stream B)
@@ -766,6 +755,46 @@ int run_frames(ekf_filter* f, int frames, FrameOf frame_of, FirstSightings first
     return rc;
 }
 
+// The pinned host buffers of a capacity (ekf_create, ekf_grow).  The readback mirror comes last: a failed allocation leaves
+// every buffer large enough for the old capacity, and the mirror -- what a state getter may return without a copy -- as it was.
+int reserve_host_buffers(ekf_filter* f, const Layout& L) {
+    int rc = f->ring.reserve(L.slot_bytes * kStageSlots);
+    if (rc == EKF_OK) rc = f->tiles_host.reserve((size_t)L.tiles_cap * 4);
+    if (rc == EKF_OK) rc = f->readback.reserve(256 + (size_t)L.cap * 8);
+    return rc;
+}
+
+// pinned host buffers, internal stream and events of a new handle
+int open_handle(ekf_filter* f) {
+    int rc = reserve_host_buffers(f, f->lay);
+    if (rc) return rc;
+    HIP_TRY(hipStreamCreateWithFlags(&f->big, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&f->ev_front, hipEventDisableTiming));
+    for (hipEvent_t& e : f->slot_done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return EKF_OK;
+}
+
+// A fresh workspace, in two steps.  clear_buffers enqueues it on the handle's stream: covariance, state and workspace zero
+// (capacity padding stays exactly zero), the exchange buffers of the fused front kernel armed (ekf_solve_device.h:
+// EKF_SENT_BITS) -- ekf_reset on the handle's buffers, ekf_grow on the new ones before it copies the old contents in.
+// restart_workspace follows once the workspace is the handle's and the stream is idle: everything that counts frames in
+// it starts again (the macro-tile table with it), and the pinned mirror is zero.
+int clear_buffers(const ekf_filter* f, void* cov, double* state, char* ws, const Layout& L) {
+    HIP_TRY(hipMemsetAsync(cov, 0, (size_t)L.cap * L.cap * L.elem, f->stream));
+    HIP_TRY(hipMemsetAsync(state, 0, (size_t)L.cap * 8, f->stream));
+    HIP_TRY(hipMemsetAsync(ws, 0, L.total, f->stream));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ws + L.off_xl), (int)0xFFFBADC0u, L.xl_len * 4, f->stream));
+    return EKF_OK;
+}
+
+void restart_workspace(ekf_filter* f) {
+    f->fseq = 0;
+    f->done_total = 0;
+    f->la_base = 0;
+    f->tiles_T = -1;
+    std::memset(f->readback.get(), 0, 256 + (size_t)f->lay.cap * 8);
+}
+
 }  // namespace
 
 extern "C" {
@@ -815,42 +844,10 @@ int ekf_create(const ekf_config* cfg, ekf_filter** out) {
     f->cfg = *cfg;
     f->lay = make_layout(*cfg);
     f->stream = static_cast<hipStream_t>(cfg->stream);
-    f->slot_bytes = align256((size_t)cfg->max_visible * 4) + align256((size_t)cfg->max_visible * 56);
-    if (f->slot_bytes < align256(256 * 48) + align256(256 * 80)) f->slot_bytes = align256(256 * 48) + align256(256 * 80);
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&f->pinned), f->slot_bytes * kStageSlots,
-                                 hipHostMallocDefault);
-    if (e != hipSuccess) {
-        delete f;
-        return fail(EKF_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-    }
-    e = hipHostMalloc(reinterpret_cast<void**>(&f->readback), 256 + (size_t)f->lay.cap * 8, hipHostMallocDefault);
-    if (e != hipSuccess) {
+    rc = open_handle(f);
+    if (rc) {
         ekf_destroy(f);
-        return fail(EKF_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-    }
-    if (f->lay.tiles_cap > 0) {
-        e = hipHostMalloc(reinterpret_cast<void**>(&f->tiles_host), (size_t)f->lay.tiles_cap * 4, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            ekf_destroy(f);
-            return fail(EKF_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        }
-    }
-    e = hipStreamCreateWithFlags(&f->big, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_front, hipEventDisableTiming);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipEventCreateWithFlags(&f->ev_small[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_big[i], hipEventDisableTiming);
-    }
-    if (e != hipSuccess) {
-        ekf_destroy(f);
-        return fail(EKF_ERR_HIP, std::string("stream/event create: ") + hipGetErrorString(e));
-    }
-    for (int i = 0; i < kStageSlots; ++i) {
-        e = hipEventCreateWithFlags(&f->slot_done[i], hipEventDisableTiming);
-        if (e != hipSuccess) {
-            ekf_destroy(f);
-            return fail(EKF_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-        }
+        return rc;
     }
     *out = f;
     return EKF_OK;
@@ -863,38 +860,23 @@ int ekf_destroy(ekf_filter* f) {
         (void)hipStreamSynchronize(f->big);
         (void)hipStreamDestroy(f->big);
     }
-    {
-        ekf_filter* me = f;
-        (void)g_pipelining.compare_exchange_strong(me, nullptr);
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (f->ev_small[i]) (void)hipEventDestroy(f->ev_small[i]);
-        if (f->ev_big[i]) (void)hipEventDestroy(f->ev_big[i]);
-    }
+    release_pipelining_token(f);
     if (f->ev_front) (void)hipEventDestroy(f->ev_front);
     for (auto& e : f->ev) (void)hipEventDestroy(e);
     for (int i = 0; i < kStageSlots; ++i)
         if (f->slot_done[i]) (void)hipEventDestroy(f->slot_done[i]);
-    if (f->pinned) (void)hipHostFree(f->pinned);
-    if (f->readback) (void)hipHostFree(f->readback);
-    if (f->tiles_host) (void)hipHostFree(f->tiles_host);
-    for (int i = 0; i < 2; ++i) {
-        if (f->log_pin_done[i]) (void)hipEventDestroy(f->log_pin_done[i]);
-        if (f->log_pin[i]) (void)hipHostFree(f->log_pin[i]);
-    }
-    delete f;
+    for (auto& e : f->log_pin_done)
+        if (e) (void)hipEventDestroy(e);
+    delete f;      // (the pinned buffers with it)
     return EKF_OK;
 }
 
 int ekf_bind_buffers(ekf_filter* f, void* cov_dev, int64_t ld, double* state_dev, void* workspace_dev,
                      size_t workspace_bytes) {
     if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
-    if (!cov_dev || !state_dev || !workspace_dev) return fail(EKF_ERR_INVALID, "NULL device buffer");
+    int rc = check_device_buffers({cov_dev, state_dev, workspace_dev}, workspace_bytes, f->lay.total, "ekf_query_sizes");
+    if (rc) return rc;
     if (ld != f->lay.cap) return fail(EKF_ERR_INVALID, "ld must equal the value from ekf_query_sizes");
-    if (workspace_bytes < f->lay.total) return fail(EKF_ERR_INVALID, "workspace too small");
-    if ((reinterpret_cast<uintptr_t>(cov_dev) | reinterpret_cast<uintptr_t>(workspace_dev) |
-         reinterpret_cast<uintptr_t>(state_dev)) & 0xFF)
-        return fail(EKF_ERR_INVALID, "device buffers must be 256-byte aligned");
     f->cov = cov_dev;
     f->ld = ld;
     f->state = state_dev;
@@ -911,81 +893,44 @@ int ekf_grow(ekf_filter* f, int32_t new_max_landmarks, int32_t new_max_visible, 
     if (!f->bound || !f->is_reset) return fail(EKF_ERR_STATE, "ekf_grow needs a bound, reset filter");
     if (new_max_landmarks < f->cfg.max_landmarks || new_max_visible < f->cfg.max_visible)
         return fail(EKF_ERR_INVALID, "ekf_grow cannot shrink the capacity");
-    if (!cov_dev || !state_dev || !workspace_dev) return fail(EKF_ERR_INVALID, "NULL device buffer");
     ekf_config ncfg = f->cfg;
     ncfg.max_landmarks = new_max_landmarks;
     ncfg.max_visible = new_max_visible;
-    {
-        int rc = check_config(&ncfg);
-        if (rc) return rc;
-    }
+    int rc = check_config(&ncfg);
+    if (rc) return rc;
     const Layout nl = make_layout(ncfg);
+    rc = check_device_buffers({cov_dev, state_dev, workspace_dev}, workspace_bytes, nl.total,
+                              "ekf_query_sizes for the new capacity");
+    if (rc) return rc;
     if (ld != nl.cap) return fail(EKF_ERR_INVALID, "ld must equal the value from ekf_query_sizes for the new capacity");
-    if (workspace_bytes < nl.total) return fail(EKF_ERR_INVALID, "workspace too small for the new capacity");
-    if ((reinterpret_cast<uintptr_t>(cov_dev) | reinterpret_cast<uintptr_t>(workspace_dev) |
-         reinterpret_cast<uintptr_t>(state_dev)) & 0xFF)
-        return fail(EKF_ERR_INVALID, "device buffers must be 256-byte aligned");
     if (cov_dev == f->cov || state_dev == f->state || workspace_dev == static_cast<void*>(f->ws))
         return fail(EKF_ERR_INVALID, "ekf_grow needs NEW buffers (the old ones are read)");
     HIP_TRY(hipSetDevice(f->device));
     HIP_TRY(hipStreamSynchronize(f->stream));
     HIP_TRY(hipStreamSynchronize(f->big));
-    {
-        ekf_filter* me = f;
-        (void)g_pipelining.compare_exchange_strong(me, nullptr);
-    }
+    release_pipelining_token(f);
     const Layout& ol = f->lay;
     char* nws = static_cast<char*>(workspace_dev);
-    // pinned host buffers that are sized by the capacity
-    size_t nslot = align256((size_t)ncfg.max_visible * 4) + align256((size_t)ncfg.max_visible * 56);
-    if (nslot < align256(256 * 48) + align256(256 * 80)) nslot = align256(256 * 48) + align256(256 * 80);
-    if (nslot != f->slot_bytes) {       // (every slot's event is complete: the stream has just been synchronised)
-        char* npin = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&npin), nslot * kStageSlots, hipHostMallocDefault));
-        (void)hipHostFree(f->pinned);
-        f->pinned = npin;
-        f->slot_bytes = nslot;
-    }
-    char* nread = nullptr;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&nread), 256 + (size_t)nl.cap * 8, hipHostMallocDefault));
-    uint32_t* ntiles = nullptr;
-    if (nl.tiles_cap > 0) {
-        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ntiles), (size_t)nl.tiles_cap * 4, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            (void)hipHostFree(nread);
-            return fail(EKF_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        }
-    }
     // new buffers: zero (capacity padding stays exactly zero), exchange buffers armed, then the old contents
-    HIP_TRY(hipMemsetAsync(cov_dev, 0, (size_t)nl.cap * nl.cap * nl.elem, f->stream));
-    HIP_TRY(hipMemsetAsync(state_dev, 0, (size_t)nl.cap * 8, f->stream));
-    HIP_TRY(hipMemsetAsync(nws, 0, nl.total, f->stream));
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nws + nl.off_xl), (int)0xFFFBADC0u, nl.xl_len * 4, f->stream));
+    rc = clear_buffers(f, cov_dev, state_dev, nws, nl);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(state_dev, f->state, (size_t)ol.cap * 8, hipMemcpyDeviceToDevice, f->stream));
     HIP_TRY(hipMemcpy2DAsync(cov_dev, (size_t)nl.cap * nl.elem, f->cov, (size_t)ol.cap * ol.elem, (size_t)ol.cap * ol.elem,
                              (size_t)ol.cap, hipMemcpyDeviceToDevice, f->stream));
     HIP_TRY(hipMemcpyAsync(nws + nl.off_status, f->ws + ol.off_status, 32, hipMemcpyDeviceToDevice, f->stream));   // (sticky bits stay)
     HIP_TRY(hipStreamSynchronize(f->stream));
-    (void)hipHostFree(f->readback);
-    if (f->tiles_host) (void)hipHostFree(f->tiles_host);
-    f->readback = nread;
-    std::memset(f->readback, 0, 256 + (size_t)nl.cap * 8);
-    f->tiles_host = ntiles;
+    // (every slot's event is complete: the stream has just been synchronised.  On failure the filter goes on at the old
+    // capacity: nothing of it has changed but the size of some pinned buffers.)
+    rc = reserve_host_buffers(f, nl);
+    if (rc) return rc;
     f->cfg = ncfg;
     f->lay = nl;
     f->cov = cov_dev;
     f->ld = ld;
     f->state = state_dev;
     f->ws = nws;
-    // the workspace is new: everything that counts frames in it starts again (as after ekf_reset)
-    f->fseq = 0;
-    f->done_total = 0;
-    f->la_base = 0;
-    f->tiles_T = -1;
-    f->front_pending = false;
-    f->mirror_fresh = false;
-    f->mirror_trust = false;
-    f->status_clean = false;
+    restart_workspace(f);
+    f->shortcut.new_workspace();
     return EKF_OK;
 }
 
@@ -996,21 +941,10 @@ int ekf_reset(ekf_filter* f, const double initial_camera_pose[10]) {
     HIP_TRY(hipSetDevice(f->device));
     const Layout& L = f->lay;
     HIP_TRY(hipStreamSynchronize(f->stream));
-    HIP_TRY(hipMemsetAsync(f->cov, 0, (size_t)L.cap * L.cap * L.elem, f->stream));
-    HIP_TRY(hipMemsetAsync(f->state, 0, (size_t)L.cap * 8, f->stream));
-    HIP_TRY(hipMemsetAsync(f->ws, 0, L.total, f->stream));
-    // arm the exchange buffers of the fused front kernel (ekf_solve_device.h: EKF_SENT_BITS)
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f->at<char>(L.off_xl)), (int)0xFFFBADC0u,
-                              L.xl_len * 4, f->stream));
-    f->fseq = 0;
-    f->done_total = 0;
-    f->la_base = 0;
-    f->tiles_T = -1;               // (the workspace, the table with it, has just been cleared)
-    f->front_pending = false;
-    std::memset(f->readback, 0, 256 + (size_t)L.cap * 8);      // (the stream is idle: synchronised above)
-    f->mirror_fresh = false;
-    f->mirror_trust = true;        // state and mirror are both zero beyond what frames write
-    f->status_clean = true;
+    int rc = clear_buffers(f, f->cov, f->state, f->ws, L);
+    if (rc) return rc;
+    restart_workspace(f);          // (the stream is idle: synchronised above)
+    f->shortcut.reset();
     HIP_TRY(hipMemcpyAsync(f->state, initial_camera_pose, 10 * sizeof(double), hipMemcpyHostToDevice,
                            f->stream));
     // P = 0.1 I_10  (extended_kalman_filter.py:48)
@@ -1036,11 +970,11 @@ int ekf_add_markers(ekf_filter* f, const double* cam_frame_xyz, const double* di
     if (f->n_lm + count > f->cfg.max_landmarks)
         return fail(EKF_ERR_CAPACITY, "more landmarks than max_landmarks");
     const Layout& L = f->lay;
-    f->front_pending = false;
+    f->shortcut.markers_added();
     int done = 0;
     while (done < count) {
         const int chunk = std::min(256, count - done);
-        char* slot = f->pinned + (size_t)f->slot * f->slot_bytes;
+        char* slot = f->ring.get() + (size_t)f->slot * L.slot_bytes;
         HIP_TRY(hipEventSynchronize(f->slot_done[f->slot]));
         double* hx = reinterpret_cast<double*>(slot);
         double* hu = reinterpret_cast<double*>(slot + align256(256 * 48));
@@ -1078,7 +1012,7 @@ int ekf_observe(ekf_filter* f, const int32_t* lm_index, const double* z, int32_t
         if (lm_index[i] < 0 || lm_index[i] >= f->n_lm)
             return fail(EKF_ERR_INVALID, "landmark index out of range");
     const Layout& L = f->lay;
-    char* slot = f->pinned + (size_t)f->slot * f->slot_bytes;
+    char* slot = f->ring.get() + (size_t)f->slot * L.slot_bytes;
     HIP_TRY(hipEventSynchronize(f->slot_done[f->slot]));
     int32_t* hidx = reinterpret_cast<int32_t*>(slot);
     double* hz = reinterpret_cast<double*>(slot + align256((size_t)f->cfg.max_visible * 4));
@@ -1137,15 +1071,30 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
 }
 
 // ---- log replay (BaseFilter.process_detections over a whole log): ekf_observe_log ---------------------------------------
+}  // extern "C"
+
+namespace {
+
 // log_ws: [z of every detection, rd doubles each | landmark indices [D] | first-sighting slots [<= D]]
-static size_t log_off_idx(int rd, int64_t D) { return align256((size_t)D * rd * 8); }
-static size_t log_off_slots(int rd, int64_t D) { return log_off_idx(rd, D) + align256((size_t)D * 4); }
-static size_t log_total(int rd, int64_t D) { return std::max<size_t>(256, log_off_slots(rd, D) + align256((size_t)D * 4)); }
+struct LogLayout {
+    size_t idx, slots, total;
+};
+
+LogLayout log_layout(int rd, int64_t D) {
+    Carve w;
+    w.take((size_t)D * rd * 8);
+    const size_t idx = w.take((size_t)D * 4), slots = w.take((size_t)D * 4);
+    return {idx, slots, std::max<size_t>(256, w.end)};
+}
+
+}  // namespace
+
+extern "C" {
 
 int ekf_log_workspace_bytes(const ekf_filter* f, int64_t detections, size_t* bytes) {
     if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
     if (!bytes || detections < 0) return fail(EKF_ERR_INVALID, "bad log size request");
-    *bytes = log_total(f->lay.rd, detections);
+    *bytes = log_layout(f->lay.rd, detections).total;
     return EKF_OK;
 }
 
@@ -1163,38 +1112,14 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
     // ---- validation on the host: nothing is enqueued before the whole log has passed
     if (frames < 0) return fail(EKF_ERR_INVALID, "negative frame count");
     if (frames > 0 && !offsets) return fail(EKF_ERR_INVALID, "offsets is NULL");
-    if (frames > 0 && offsets[0] != 0) return fail(EKF_ERR_INVALID, "offsets[0] must be 0");
-    for (int t = 0; t < frames; ++t)
-        if (offsets[t + 1] < offsets[t]) return fail(EKF_ERR_INVALID, "offsets must be non-decreasing");
+    if (frames > 0 && (rc = check_offsets(offsets, frames, "offsets"))) return rc;
     const int64_t D = frames > 0 ? offsets[frames] : 0;
     const int rd = f->lay.rd;
+    const LogLayout LL = log_layout(rd, D);
     if (D > 0 && (!lm_index || !poses_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
-    if (D > 0 && (!log_ws || log_ws_bytes < log_total(rd, D)))
-        return fail(EKF_ERR_INVALID, "log workspace missing or smaller than ekf_log_workspace_bytes");
-    if (D > 0 && (reinterpret_cast<uintptr_t>(log_ws) & 0xFF)) return fail(EKF_ERR_INVALID, "log workspace must be 256-byte aligned");
-    // per frame: first new slot, number of new landmarks; first sightings are numbered n, n+1, ... in order of occurrence
-    std::vector<int32_t> slots;
-    std::vector<int64_t> new_at((size_t)frames + 1, 0);
-    int n = f->n_lm;
-    int64_t max_m = 0;
-    for (int t = 0; t < frames; ++t) {
-        new_at[t] = (int64_t)slots.size();
-        for (int64_t d = offsets[t]; d < offsets[t + 1]; ++d) {
-            const int32_t i = lm_index[d];
-            if (i < 0) return fail(EKF_ERR_INVALID, "negative landmark index in the log");
-            if (i == n) {
-                slots.push_back((int32_t)d);
-                ++n;
-            } else if (i > n) {
-                return fail(EKF_ERR_INVALID, "landmark index beyond the next free one (first sightings must be numbered "
-                                             "n, n+1, ... in order of first occurrence)");
-            }
-        }
-        max_m = std::max<int64_t>(max_m, offsets[t + 1] - offsets[t]);
-    }
-    new_at[frames] = (int64_t)slots.size();
-    if (n > f->cfg.max_landmarks) return fail(EKF_ERR_CAPACITY, "the log needs more landmarks than max_landmarks");
-    if (max_m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "a frame of the log has more detections than max_visible");
+    if (D > 0 && (rc = check_device_buffers({log_ws}, log_ws_bytes, LL.total, "ekf_log_workspace_bytes"))) return rc;
+    LogCheck lc;
+    if ((rc = check_log(lm_index, offsets, frames, f->n_lm, f->cfg, "the log", &lc))) return rc;
     for (int i = 0; i < 4; ++i) f->log_stats[i] = 0;
     if (frames == 0) return EKF_OK;
 
@@ -1212,34 +1137,31 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
             }
         }
     }
-    const size_t up_bytes = log_off_slots(rd, D) - log_off_idx(rd, D) + slots.size() * 4;
-    const size_t pin_need = align256(up_bytes) + align256(lead.size() * 4) + align256(rest.size() * 4) + 256;
+    const size_t up_bytes = LL.slots - LL.idx + lc.slots.size() * 4;
+    Carve p;
+    p.take(up_bytes);
+    const size_t lead_at = p.take(lead.size() * 4), rest_at = p.take(rest.size() * 4);
+    p.take(256);
     const int turn = f->log_pin_turn;
     if (!f->log_pin_done[turn]) HIP_TRY(hipEventCreateWithFlags(&f->log_pin_done[turn], hipEventDisableTiming));
     HIP_TRY(hipEventSynchronize(f->log_pin_done[turn]));      // (the staging of the call before the previous one is consumed)
-    if (pin_need > f->log_pin_bytes[turn]) {
-        if (f->log_pin[turn]) (void)hipHostFree(f->log_pin[turn]);
-        f->log_pin[turn] = nullptr;
-        f->log_pin_bytes[turn] = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&f->log_pin[turn]), pin_need, hipHostMallocDefault));
-        f->log_pin_bytes[turn] = pin_need;
-    }
-    char* pin = f->log_pin[turn];
-    int32_t* pin_lead = reinterpret_cast<int32_t*>(pin + align256(up_bytes));
-    int32_t* pin_rest = reinterpret_cast<int32_t*>(pin + align256(up_bytes) + align256(lead.size() * 4));
+    if ((rc = f->log_pin[turn].reserve(p.end))) return rc;
+    char* pin = f->log_pin[turn].get();
+    int32_t* pin_lead = f->log_pin[turn].at<int32_t>(lead_at);
+    int32_t* pin_rest = f->log_pin[turn].at<int32_t>(rest_at);
     char* ws = static_cast<char*>(log_ws);
     double* z_all = reinterpret_cast<double*>(ws);
-    const int32_t* idx_all = reinterpret_cast<const int32_t*>(ws + log_off_idx(rd, D));
-    const int32_t* slots_all = reinterpret_cast<const int32_t*>(ws + log_off_slots(rd, D));
+    const int32_t* idx_all = reinterpret_cast<const int32_t*>(ws + LL.idx);
+    const int32_t* slots_all = reinterpret_cast<const int32_t*>(ws + LL.slots);
     if (D > 0) {
         std::memcpy(pin, lm_index, (size_t)D * 4);
-        if (!slots.empty()) std::memcpy(pin + (log_off_slots(rd, D) - log_off_idx(rd, D)), slots.data(), slots.size() * 4);
+        if (!lc.slots.empty()) std::memcpy(pin + (LL.slots - LL.idx), lc.slots.data(), lc.slots.size() * 4);
     }
     if (!lead.empty()) std::memcpy(pin_lead, lead.data(), lead.size() * 4);
     if (!rest.empty()) std::memcpy(pin_rest, rest.data(), rest.size() * 4);
 
     auto m_of = [&](int t) { return (int)(offsets[t + 1] - offsets[t]); };
-    auto nnew_of = [&](int t) { return (int)(new_at[t + 1] - new_at[t]); };
+    auto nnew_of = [&](int t) { return (int)(lc.new_at[t + 1] - lc.new_at[t]); };
     const RunPlan plan = plan_runs(f, frames, m_of, nnew_of);
     int mode = EKF_SEQ_SERIAL;
     rc = choose_pipelining(f, plan.want_runs, &mode);
@@ -1247,7 +1169,7 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
 
     // ---- device work, all on the handle's stream (the pipelined runs use the internal one as ekf_observe_sequence_device)
     if (D > 0) {
-        HIP_TRY(hipMemcpyAsync(ws + log_off_idx(rd, D), pin, up_bytes, hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(hipMemcpyAsync(ws + LL.idx, pin, up_bytes, hipMemcpyHostToDevice, f->stream));
         ekf_launch_log_prepare(poses_dev, D, rd, z_all, f->stream);
     }
     if (!lead.empty()) ekf_launch_log_fill_rows(trajectory_dev, pin_lead, (int32_t)(lead.size() / 2), f->state, f->stream);
@@ -1263,7 +1185,7 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
             if (nnew > 0)
                 by_cov_type(f, [&](auto elem) {
                     ekf_launch_log_add_markers<decltype(elem)>(f->cfg.model, f->cov, f->ld, f->state, f->dims(), poses_dev,
-                                                               slots_all + new_at[t], f->cfg.initial_landmark_uncertainty, nnew,
+                                                               slots_all + lc.new_at[t], f->cfg.initial_landmark_uncertainty, nnew,
                                                                f->stream);
                 });
             return nnew;
@@ -1273,8 +1195,7 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
         ekf_launch_log_fill_rows(trajectory_dev, pin_rest, (int32_t)(rest.size() / 2), f->state, f->stream);
     // A state getter after the call must wait for the whole call (the last frame's state may come from a pipelined run, whose
     // front kernels record no event): no shortcut through the event of an earlier serial frame of the call.
-    f->front_pending = false;
-    f->mirror_fresh = false;
+    f->shortcut.log();
     // (the staging may be reused once the stream is here -- also after an error: its copy may have been enqueued)
     f->log_pin_turn = turn ^ 1;
     HIP_TRY(hipEventRecord(f->log_pin_done[turn], f->stream));
@@ -1346,7 +1267,7 @@ int ekf_get_state(ekf_filter* f, double* out, int32_t count) {
     if (!out || count < 0 || count > f->dims()) return fail(EKF_ERR_INVALID, "bad state request");
     rc = sync_and_check(f, count);
     if (rc) return rc;
-    std::memcpy(out, f->readback + 256, (size_t)count * 8);
+    std::memcpy(out, f->readback.at<double>(256), (size_t)count * 8);
     return EKF_OK;
 }
 
@@ -1390,8 +1311,7 @@ int ekf_set_state(ekf_filter* f, const double* state, int32_t num_landmarks) {
     if (!state || num_landmarks < 0) return fail(EKF_ERR_INVALID, "bad state");
     if (num_landmarks > f->cfg.max_landmarks)
         return fail(EKF_ERR_CAPACITY, "more landmarks than max_landmarks");
-    f->front_pending = false;
-    f->mirror_trust = false;
+    f->shortcut.state_set();
     HIP_TRY(hipStreamSynchronize(f->stream));
     HIP_TRY(hipMemset(f->state, 0, (size_t)f->lay.cap * 8));
     HIP_TRY(hipMemcpy(f->state, state, (size_t)(f->lay.lmd * num_landmarks + EKF_CAM) * 8,
@@ -1517,355 +1437,6 @@ int ekf_debug_fetch(ekf_filter* f, int32_t what, double* out, size_t count) {
         default:
             return fail(EKF_ERR_INVALID, "unknown debug item");
     }
-}
-
-
-// ---- batch of independent filters (ekf_batch.hip): one workgroup per member ---------------------------------------------
-}  // extern "C"
-
-struct ekf_batch {
-    ekf_config cfg{};
-    int32_t members = 0;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int64_t ld = 0;
-    double* cov = nullptr;
-    double* state = nullptr;
-    char* ws = nullptr;
-    bool bound = false;
-    std::vector<double> noise;      // [B][6] host copy (initial_camera_uncertainty is used on the host, by reset)
-    std::vector<int32_t> nlm;       // [B] host copy, refreshed after every call
-    std::vector<int32_t> status;    // [B]
-    char* pin = nullptr;            // pinned staging of a call's indices and offsets
-    size_t pin_bytes = 0;
-};
-
-namespace {
-
-constexpr int kBatchWindow = 64;   // frames per member and launch: every dispatch stays short
-
-int64_t batch_ld(const ekf_config& c) { return round_up(EKF_LM * (int64_t)c.max_landmarks + EKF_CAM, 32); }
-size_t batch_off_status(int32_t members) { return align256((size_t)members * 6 * 8); }
-size_t batch_off_nlm(int32_t members) { return batch_off_status(members) + align256((size_t)members * 4); }
-size_t batch_ws_total(int32_t members) { return batch_off_nlm(members) + align256((size_t)members * 4); }
-
-int check_batch_config(const ekf_config* c, int32_t members) {
-    if (!c) return fail(EKF_ERR_INVALID, "config is NULL");
-    if (members < 1) return fail(EKF_ERR_INVALID, "a batch needs at least one member");
-    if (c->model != EKF_MODEL_EKF) return fail(EKF_ERR_INVALID, "batches exist for EKF_MODEL_EKF only");
-    if (c->cov_dtype != EKF_COV_F64) return fail(EKF_ERR_INVALID, "batches keep an f64 covariance (EKF_COV_F64)");
-    if (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_MAX_LANDMARKS)
-        return fail(EKF_ERR_INVALID, "batch max_landmarks must be in 1..82");
-    if (c->max_visible < 1 || c->max_visible > EKF_BATCH_MAX_VISIBLE)
-        return fail(EKF_ERR_INVALID, "batch max_visible must be in 1..16");
-    if (c->quat_mode != EKF_QUAT_AS_WRITTEN && c->quat_mode != EKF_QUAT_SCALAR_FIRST)
-        return fail(EKF_ERR_INVALID, "unknown quat_mode");
-    return EKF_OK;
-}
-
-int check_noise(const double* nz) {
-    for (int i = 0; i < 6; ++i)
-        if (!std::isfinite(nz[i]) || nz[i] < 0.0) return fail(EKF_ERR_INVALID, "noise constants must be finite and >= 0");
-    if (!(nz[2] > 0.0)) return fail(EKF_ERR_INVALID, "r_uncertainty must be > 0");
-    return EKF_OK;
-}
-
-int batch_ready(const ekf_batch* b) {
-    if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
-    if (!b->bound) return fail(EKF_ERR_STATE, "ekf_batch_bind_buffers has not been called");
-    HIP_TRY(hipSetDevice(b->device));
-    return EKF_OK;
-}
-
-int batch_member(const ekf_batch* b, int32_t member) {
-    if (member < 0 || member >= b->members) return fail(EKF_ERR_INVALID, "member index out of range");
-    return EKF_OK;
-}
-
-// status and landmark counts of every member back to the host (the stream is idle afterwards)
-int batch_refresh(ekf_batch* b) {
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(b->status.data(), b->ws + batch_off_status(b->members), (size_t)b->members * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b->nlm.data(), b->ws + batch_off_nlm(b->members), (size_t)b->members * 4, hipMemcpyDeviceToHost));
-    return EKF_OK;
-}
-
-// host copies of status and landmark count of one member -> device
-int batch_put_member_words(ekf_batch* b, int32_t member) {
-    HIP_TRY(hipMemcpy(b->ws + batch_off_status(b->members) + 4 * (size_t)member, &b->status[member], 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->ws + batch_off_nlm(b->members) + 4 * (size_t)member, &b->nlm[member], 4, hipMemcpyHostToDevice));
-    return EKF_OK;
-}
-
-// log workspace: [landmark indices [D] | frame offsets [Ftot+1] | member frame offsets [B+1]]
-size_t batch_log_off_frames(int64_t D) { return align256((size_t)D * 4); }
-size_t batch_log_off_members(int64_t D, int64_t F) { return batch_log_off_frames(D) + align256((size_t)(F + 1) * 8); }
-size_t batch_log_total(int64_t D, int64_t F, int32_t B) { return batch_log_off_members(D, F) + align256((size_t)(B + 1) * 8); }
-
-}  // namespace
-
-extern "C" {
-
-int ekf_batch_query_sizes(const ekf_config* cfg, int32_t members, int64_t* ld, size_t* cov_bytes, size_t* state_bytes,
-                          size_t* workspace_bytes) {
-    int rc = check_batch_config(cfg, members);
-    if (rc) return rc;
-    const int64_t l = batch_ld(*cfg);
-    if (ld) *ld = l;
-    if (cov_bytes) *cov_bytes = (size_t)members * l * l * 8;
-    if (state_bytes) *state_bytes = (size_t)members * l * 8;
-    if (workspace_bytes) *workspace_bytes = batch_ws_total(members);
-    return EKF_OK;
-}
-
-int ekf_batch_create(const ekf_config* cfg, int32_t members, ekf_batch** out) {
-    int rc = check_batch_config(cfg, members);
-    if (rc) return rc;
-    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
-    const double nz[6] = {cfg->initial_camera_uncertainty, cfg->initial_landmark_uncertainty, cfg->r_uncertainty,
-                          cfg->q_cam, cfg->q_err, cfg->q_lm};
-    rc = check_noise(nz);
-    if (rc) return rc;
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev < 1) return fail(EKF_ERR_HIP, "no HIP device visible");
-    ekf_batch* b = new ekf_batch();
-    if (hipGetDevice(&b->device) != hipSuccess) b->device = 0;   // the caller's current device
-    b->cfg = *cfg;
-    b->members = members;
-    b->stream = static_cast<hipStream_t>(cfg->stream);
-    b->ld = batch_ld(*cfg);
-    b->noise.resize((size_t)members * 6);
-    for (int32_t m = 0; m < members; ++m)
-        for (int i = 0; i < 6; ++i) b->noise[(size_t)m * 6 + i] = nz[i];
-    b->nlm.assign(members, 0);
-    b->status.assign(members, 0);
-    *out = b;
-    return EKF_OK;
-}
-
-int ekf_batch_destroy(ekf_batch* b) {
-    if (!b) return EKF_OK;
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->pin) (void)hipHostFree(b->pin);
-    delete b;
-    return EKF_OK;
-}
-
-// Borrow the caller's buffers and reset every member to the identity pose (ekf_batch_reset to set the initial poses).
-int ekf_batch_bind_buffers(ekf_batch* b, double* cov_dev, int64_t ld, double* state_dev, void* ws_dev, size_t ws_bytes) {
-    if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
-    if (!cov_dev || !state_dev || !ws_dev) return fail(EKF_ERR_INVALID, "NULL device buffer");
-    if (ld != b->ld) return fail(EKF_ERR_INVALID, "ld must equal the value from ekf_batch_query_sizes");
-    if (ws_bytes < batch_ws_total(b->members)) return fail(EKF_ERR_INVALID, "workspace too small");
-    if ((reinterpret_cast<uintptr_t>(cov_dev) | reinterpret_cast<uintptr_t>(state_dev) | reinterpret_cast<uintptr_t>(ws_dev)) & 0xFF)
-        return fail(EKF_ERR_INVALID, "device buffers must be 256-byte aligned");
-    HIP_TRY(hipSetDevice(b->device));
-    b->cov = cov_dev;
-    b->state = state_dev;
-    b->ws = static_cast<char*>(ws_dev);
-    b->bound = true;
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(b->ws, b->noise.data(), b->noise.size() * 8, hipMemcpyHostToDevice));
-    std::vector<double> poses((size_t)b->members * 10, 0.0);
-    for (int32_t m = 0; m < b->members; ++m) poses[(size_t)m * 10 + 3] = 1.0;
-    return ekf_batch_reset(b, -1, poses.data());
-}
-
-int ekf_batch_set_noise(ekf_batch* b, const double* noise) {
-    int rc = batch_ready(b);
-    if (rc) return rc;
-    if (!noise) return fail(EKF_ERR_INVALID, "noise is NULL");
-    for (int32_t m = 0; m < b->members; ++m) {
-        rc = check_noise(noise + 6 * (size_t)m);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    std::memcpy(b->noise.data(), noise, b->noise.size() * 8);
-    HIP_TRY(hipMemcpy(b->ws, b->noise.data(), b->noise.size() * 8, hipMemcpyHostToDevice));
-    return EKF_OK;
-}
-
-// state = initial pose, P = initial_camera_uncertainty I_10 (the member's own), no landmarks, status cleared.
-// member = -1: every member, initial_poses [B,10]; otherwise initial_poses [10].
-int ekf_batch_reset(ekf_batch* b, int32_t member, const double* initial_poses) {
-    int rc = batch_ready(b);
-    if (rc) return rc;
-    if (!initial_poses) return fail(EKF_ERR_INVALID, "initial poses are NULL");
-    if (member != -1 && (rc = batch_member(b, member))) return rc;
-    const int32_t lo = member < 0 ? 0 : member, hi = member < 0 ? b->members : member + 1;
-    const int64_t ld = b->ld;
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemset(b->cov + (size_t)lo * ld * ld, 0, (size_t)(hi - lo) * ld * ld * 8));
-    HIP_TRY(hipMemset(b->state + (size_t)lo * ld, 0, (size_t)(hi - lo) * ld * 8));
-    HIP_TRY(hipMemcpy2D(b->state + (size_t)lo * ld, (size_t)ld * 8, initial_poses, 10 * 8, 10 * 8, hi - lo,
-                        hipMemcpyHostToDevice));
-    std::vector<double> diag((size_t)(hi - lo) * EKF_CAM);
-    for (int32_t m = lo; m < hi; ++m) {
-        for (int i = 0; i < EKF_CAM; ++i) diag[(size_t)(m - lo) * EKF_CAM + i] = b->noise[(size_t)m * 6];
-        b->nlm[m] = 0;
-        b->status[m] = 0;
-    }
-    // P = icu I_10: the diagonal of every member's matrix is a strided run of ld + 1 elements
-    for (int32_t m = lo; m < hi; ++m)
-        HIP_TRY(hipMemcpy2D(b->cov + (size_t)m * ld * ld, (size_t)(ld + 1) * 8, diag.data() + (size_t)(m - lo) * EKF_CAM, 8, 8,
-                            EKF_CAM, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->ws + batch_off_status(b->members) + 4 * (size_t)lo, b->status.data() + lo, (size_t)(hi - lo) * 4,
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->ws + batch_off_nlm(b->members) + 4 * (size_t)lo, b->nlm.data() + lo, (size_t)(hi - lo) * 4,
-                      hipMemcpyHostToDevice));
-    return EKF_OK;
-}
-
-// (state [3 n + 10], P [3 n + 10, 3 n + 10]) of one member from the host; P is symmetrised ((P + P^T) / 2) on upload.
-// The member's status is cleared.
-int ekf_batch_set_member(ekf_batch* b, int32_t member, const double* state, int32_t num_landmarks, const double* cov) {
-    int rc = batch_ready(b);
-    if (rc) return rc;
-    if ((rc = batch_member(b, member))) return rc;
-    if (!state || !cov || num_landmarks < 0) return fail(EKF_ERR_INVALID, "bad member state");
-    if (num_landmarks > b->cfg.max_landmarks) return fail(EKF_ERR_CAPACITY, "more landmarks than max_landmarks");
-    const int64_t ld = b->ld;
-    const int dims = EKF_LM * num_landmarks + EKF_CAM;
-    std::vector<double> st((size_t)ld, 0.0), p((size_t)ld * ld, 0.0);
-    std::memcpy(st.data(), state, (size_t)dims * 8);
-    for (int i = 0; i < dims; ++i)
-        for (int j = 0; j < dims; ++j) p[(size_t)i * ld + j] = 0.5 * (cov[(size_t)i * dims + j] + cov[(size_t)j * dims + i]);
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(b->state + (size_t)member * ld, st.data(), st.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->cov + (size_t)member * ld * ld, p.data(), p.size() * 8, hipMemcpyHostToDevice));
-    b->nlm[member] = num_landmarks;
-    b->status[member] = 0;
-    return batch_put_member_words(b, member);
-}
-
-// state[0:count] and, if cov is not NULL, P [dims, dims] with dims = 3 n + 10 of one member.  Synchronises.
-int ekf_batch_get_member(ekf_batch* b, int32_t member, double* state, int32_t count, double* cov, int32_t dims) {
-    int rc = batch_ready(b);
-    if (rc) return rc;
-    if ((rc = batch_member(b, member))) return rc;
-    if ((rc = batch_refresh(b))) return rc;
-    const int n = EKF_LM * b->nlm[member] + EKF_CAM;
-    if (count < 0 || count > n || (count > 0 && !state)) return fail(EKF_ERR_INVALID, "bad state request");
-    if (cov && dims != n) return fail(EKF_ERR_INVALID, "dims must equal the member's state dimension");
-    const int64_t ld = b->ld;
-    if (count > 0) HIP_TRY(hipMemcpy(state, b->state + (size_t)member * ld, (size_t)count * 8, hipMemcpyDeviceToHost));
-    if (cov)
-        HIP_TRY(hipMemcpy2D(cov, (size_t)dims * 8, b->cov + (size_t)member * ld * ld, (size_t)ld * 8, (size_t)dims * 8, dims,
-                            hipMemcpyDeviceToHost));
-    return EKF_OK;
-}
-
-int ekf_batch_num_landmarks(const ekf_batch* b, int32_t* out) {
-    int rc = batch_ready(b);
-    if (rc) return rc;
-    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
-    if ((rc = batch_refresh(const_cast<ekf_batch*>(b)))) return rc;
-    std::memcpy(out, b->nlm.data(), b->nlm.size() * 4);
-    return EKF_OK;
-}
-
-int ekf_batch_status(ekf_batch* b, int32_t* out) {
-    int rc = batch_ready(b);
-    if (rc) return rc;
-    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
-    if ((rc = batch_refresh(b))) return rc;
-    std::memcpy(out, b->status.data(), b->status.size() * 4);
-    return EKF_OK;
-}
-
-int ekf_batch_log_workspace_bytes(const ekf_batch* b, int64_t detections, int64_t frames, size_t* bytes) {
-    if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
-    if (!bytes || detections < 0 || frames < 0) return fail(EKF_ERR_INVALID, "bad log size request");
-    *bytes = batch_log_total(detections, frames, b->members);
-    return EKF_OK;
-}
-
-int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, const int64_t* member_frames,
-                           const double* poses_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev) {
-    int rc = batch_ready(b);
-    if (rc) return rc;
-    // ---- validation on the host: nothing is enqueued before every log has passed
-    const int32_t B = b->members;
-    if (!member_frames || !frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
-    if (member_frames[0] != 0) return fail(EKF_ERR_INVALID, "member_frames[0] must be 0");
-    for (int32_t m = 0; m < B; ++m)
-        if (member_frames[m + 1] < member_frames[m]) return fail(EKF_ERR_INVALID, "member_frames must be non-decreasing");
-    const int64_t F = member_frames[B];
-    if (frame_offsets[0] != 0) return fail(EKF_ERR_INVALID, "frame_offsets[0] must be 0");
-    for (int64_t t = 0; t < F; ++t)
-        if (frame_offsets[t + 1] < frame_offsets[t]) return fail(EKF_ERR_INVALID, "frame_offsets must be non-decreasing");
-    const int64_t D = frame_offsets[F];
-    if (D > 0 && (!lm_index || !poses_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
-    if (!log_ws || log_ws_bytes < batch_log_total(D, F, B))
-        return fail(EKF_ERR_INVALID, "log workspace missing or smaller than ekf_batch_log_workspace_bytes");
-    if (reinterpret_cast<uintptr_t>(log_ws) & 0xFF) return fail(EKF_ERR_INVALID, "log workspace must be 256-byte aligned");
-    if ((rc = batch_refresh(b))) return rc;      // (landmark counts as the previous call left them)
-    int32_t n_max = 0, widest = 0;
-    int64_t frames_max = 0;
-    for (int32_t m = 0; m < B; ++m) {
-        int n = b->nlm[m];
-        for (int64_t t = member_frames[m]; t < member_frames[m + 1]; ++t) {
-            for (int64_t d = frame_offsets[t]; d < frame_offsets[t + 1]; ++d) {
-                const int32_t i = lm_index[d];
-                if (i < 0) return fail(EKF_ERR_INVALID, "negative landmark index in member " + std::to_string(m) + "'s log");
-                if (i == n) ++n;
-                else if (i > n)
-                    return fail(EKF_ERR_INVALID, "landmark index beyond the next free one in member " + std::to_string(m) +
-                                                     "'s log (first sightings must be numbered n, n+1, ... in order of first "
-                                                     "occurrence)");
-            }
-            const int64_t w = frame_offsets[t + 1] - frame_offsets[t];
-            if (w > b->cfg.max_visible)
-                return fail(EKF_ERR_CAPACITY, "a frame of member " + std::to_string(m) + "'s log has more detections than max_visible");
-            widest = std::max<int32_t>(widest, (int32_t)w);
-        }
-        if (n > b->cfg.max_landmarks)
-            return fail(EKF_ERR_CAPACITY, "member " + std::to_string(m) + "'s log needs more landmarks than max_landmarks");
-        n_max = std::max(n_max, n);
-        frames_max = std::max(frames_max, member_frames[m + 1] - member_frames[m]);
-    }
-    if (F == 0) return EKF_OK;
-
-    // ---- staging: one copy of indices and offsets (the stream is idle: batch_refresh synchronised it)
-    const size_t up = batch_log_total(D, F, B);
-    if (up > b->pin_bytes) {
-        if (b->pin) (void)hipHostFree(b->pin);
-        b->pin = nullptr;
-        b->pin_bytes = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->pin), up, hipHostMallocDefault));
-        b->pin_bytes = up;
-    }
-    if (D > 0) std::memcpy(b->pin, lm_index, (size_t)D * 4);
-    std::memcpy(b->pin + batch_log_off_frames(D), frame_offsets, (size_t)(F + 1) * 8);
-    std::memcpy(b->pin + batch_log_off_members(D, F), member_frames, (size_t)(B + 1) * 8);
-    char* ws = static_cast<char*>(log_ws);
-    HIP_TRY(hipMemcpyAsync(ws, b->pin, up, hipMemcpyHostToDevice, b->stream));
-
-    // ---- windows: every member's frames [w, w + kBatchWindow) of its log per launch, state carried in HBM.  LDS is
-    // sized for the widest frame and the largest map of the call (a layout choice only: the arithmetic is the same)
-    EkfBatchWindow a{};
-    a.P = b->cov;
-    a.ld = b->ld;
-    a.state = b->state;
-    a.noise = reinterpret_cast<const double*>(b->ws);
-    a.status = reinterpret_cast<int32_t*>(b->ws + batch_off_status(B));
-    a.nlm = reinterpret_cast<int32_t*>(b->ws + batch_off_nlm(B));
-    a.lm_index = reinterpret_cast<const int32_t*>(ws);
-    a.frame_offsets = reinterpret_cast<const int64_t*>(ws + batch_log_off_frames(D));
-    a.member_frames = reinterpret_cast<const int64_t*>(ws + batch_log_off_members(D, F));
-    a.poses = poses_dev;
-    a.traj = trajectory_dev;
-    a.quat_mode = b->cfg.quat_mode;
-    a.kmax = std::max(3, 3 * widest);
-    a.lda = (int32_t)round_up(EKF_LM * n_max + EKF_CAM + 1, 4);
-    a.window_frames = kBatchWindow;
-    for (int64_t w = 0; w < frames_max; w += kBatchWindow) {
-        a.window_first = (int32_t)w;
-        ekf_launch_batch_window(a, B, b->stream);
-        HIP_TRY(hipGetLastError());
-    }
-    return EKF_OK;
 }
 
 }  // extern "C"

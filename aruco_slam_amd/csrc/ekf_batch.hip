@@ -1,4 +1,4 @@
-// Batch of independent EKF filters (ekf_batch_observe_logs, ekf_api.hip): ONE workgroup owns ONE member for a window of its
+// Batch of independent EKF filters (ekf_batch_observe_logs, ekf_batch_api.hip): ONE workgroup owns ONE member for a window of its
 // log's frames.  Per stepped frame, the algebra of DESIGN section 2 with everything but P in LDS:
 //   first sightings (ekf_add_marker_xyz, the frame's pre-update camera), h and dh of every detection (ekf_measure),
 //   A = H (P+Q) [k, N], S = A[:,supp] H^T + R I (lower triangle), S = L L^T (left-looking, in LDS),

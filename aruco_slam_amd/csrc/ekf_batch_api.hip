@@ -1,0 +1,341 @@
+// C ABI of the batch of independent filters (ekf_batch_*, see include/ekf_slam_hip.h; kernel: ekf_batch.hip, one workgroup
+// per member).  Host side only: argument checking, workspace carving, launch sequencing.
+#include <cmath>
+#include <cstring>
+
+#include "ekf_host.h"
+#include "ekf_kernels.h"
+
+struct ekf_batch {
+    ekf_config cfg{};
+    int32_t members = 0;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int64_t ld = 0;
+    double* cov = nullptr;
+    double* state = nullptr;
+    char* ws = nullptr;
+    bool bound = false;
+    std::vector<double> noise;      // [B][6] host copy (initial_camera_uncertainty is used on the host, by reset)
+    std::vector<int32_t> nlm;       // [B] host copy, refreshed after every call
+    std::vector<int32_t> status;    // [B]
+    PinnedBuffer pin;               // pinned staging of a call's indices and offsets
+};
+
+namespace {
+
+constexpr int kBatchWindow = 64;   // frames per member and launch: every dispatch stays short
+
+int64_t batch_ld(const ekf_config& c) { return round_up(EKF_LM * (int64_t)c.max_landmarks + EKF_CAM, 32); }
+
+// workspace: [noise [B][6] | status [B] | landmark counts [B]]
+struct BatchLayout {
+    size_t status, nlm, total;
+};
+
+BatchLayout batch_layout(int32_t members) {
+    Carve w;
+    w.take((size_t)members * 6 * 8);
+    const size_t status = w.take((size_t)members * 4), nlm = w.take((size_t)members * 4);
+    return {status, nlm, w.end};
+}
+
+// log workspace: [landmark indices [D] | frame offsets [Ftot+1] | member frame offsets [B+1]]
+struct BatchLogLayout {
+    size_t frames, members, total;
+};
+
+BatchLogLayout batch_log_layout(int64_t D, int64_t F, int32_t B) {
+    Carve w;
+    w.take((size_t)D * 4);
+    const size_t frames = w.take((size_t)(F + 1) * 8), members = w.take((size_t)(B + 1) * 8);
+    return {frames, members, w.end};
+}
+
+int check_batch_config(const ekf_config* c, int32_t members) {
+    if (!c) return fail(EKF_ERR_INVALID, "config is NULL");
+    if (members < 1) return fail(EKF_ERR_INVALID, "a batch needs at least one member");
+    if (c->model != EKF_MODEL_EKF) return fail(EKF_ERR_INVALID, "batches exist for EKF_MODEL_EKF only");
+    if (c->cov_dtype != EKF_COV_F64) return fail(EKF_ERR_INVALID, "batches keep an f64 covariance (EKF_COV_F64)");
+    if (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_MAX_LANDMARKS)
+        return fail(EKF_ERR_INVALID, "batch max_landmarks must be in 1..82");
+    if (c->max_visible < 1 || c->max_visible > EKF_BATCH_MAX_VISIBLE)
+        return fail(EKF_ERR_INVALID, "batch max_visible must be in 1..16");
+    if (c->quat_mode != EKF_QUAT_AS_WRITTEN && c->quat_mode != EKF_QUAT_SCALAR_FIRST)
+        return fail(EKF_ERR_INVALID, "unknown quat_mode");
+    return EKF_OK;
+}
+
+int check_noise(const double* nz) {
+    for (int i = 0; i < 6; ++i)
+        if (!std::isfinite(nz[i]) || nz[i] < 0.0) return fail(EKF_ERR_INVALID, "noise constants must be finite and >= 0");
+    if (!(nz[2] > 0.0)) return fail(EKF_ERR_INVALID, "r_uncertainty must be > 0");
+    return EKF_OK;
+}
+
+int batch_ready(const ekf_batch* b) {
+    if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
+    if (!b->bound) return fail(EKF_ERR_STATE, "ekf_batch_bind_buffers has not been called");
+    HIP_TRY(hipSetDevice(b->device));
+    return EKF_OK;
+}
+
+int batch_member(const ekf_batch* b, int32_t member) {
+    if (member < 0 || member >= b->members) return fail(EKF_ERR_INVALID, "member index out of range");
+    return EKF_OK;
+}
+
+// status and landmark counts of every member back to the host (the stream is idle afterwards)
+int batch_refresh(ekf_batch* b) {
+    const BatchLayout L = batch_layout(b->members);
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->status.data(), b->ws + L.status, (size_t)b->members * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b->nlm.data(), b->ws + L.nlm, (size_t)b->members * 4, hipMemcpyDeviceToHost));
+    return EKF_OK;
+}
+
+// host copies of status and landmark count of members [lo, hi) -> device
+int batch_put_member_words(ekf_batch* b, int32_t lo, int32_t hi) {
+    const BatchLayout L = batch_layout(b->members);
+    HIP_TRY(hipMemcpy(b->ws + L.status + 4 * (size_t)lo, b->status.data() + lo, (size_t)(hi - lo) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->ws + L.nlm + 4 * (size_t)lo, b->nlm.data() + lo, (size_t)(hi - lo) * 4, hipMemcpyHostToDevice));
+    return EKF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ekf_batch_query_sizes(const ekf_config* cfg, int32_t members, int64_t* ld, size_t* cov_bytes, size_t* state_bytes,
+                          size_t* workspace_bytes) {
+    int rc = check_batch_config(cfg, members);
+    if (rc) return rc;
+    const int64_t l = batch_ld(*cfg);
+    if (ld) *ld = l;
+    if (cov_bytes) *cov_bytes = (size_t)members * l * l * 8;
+    if (state_bytes) *state_bytes = (size_t)members * l * 8;
+    if (workspace_bytes) *workspace_bytes = batch_layout(members).total;
+    return EKF_OK;
+}
+
+int ekf_batch_create(const ekf_config* cfg, int32_t members, ekf_batch** out) {
+    int rc = check_batch_config(cfg, members);
+    if (rc) return rc;
+    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
+    const double nz[6] = {cfg->initial_camera_uncertainty, cfg->initial_landmark_uncertainty, cfg->r_uncertainty,
+                          cfg->q_cam, cfg->q_err, cfg->q_lm};
+    rc = check_noise(nz);
+    if (rc) return rc;
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (ndev < 1) return fail(EKF_ERR_HIP, "no HIP device visible");
+    ekf_batch* b = new ekf_batch();
+    if (hipGetDevice(&b->device) != hipSuccess) b->device = 0;   // the caller's current device
+    b->cfg = *cfg;
+    b->members = members;
+    b->stream = static_cast<hipStream_t>(cfg->stream);
+    b->ld = batch_ld(*cfg);
+    b->noise.resize((size_t)members * 6);
+    for (int32_t m = 0; m < members; ++m)
+        for (int i = 0; i < 6; ++i) b->noise[(size_t)m * 6 + i] = nz[i];
+    b->nlm.assign(members, 0);
+    b->status.assign(members, 0);
+    *out = b;
+    return EKF_OK;
+}
+
+int ekf_batch_destroy(ekf_batch* b) {
+    if (!b) return EKF_OK;
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    delete b;
+    return EKF_OK;
+}
+
+// Borrow the caller's buffers and reset every member to the identity pose (ekf_batch_reset to set the initial poses).
+int ekf_batch_bind_buffers(ekf_batch* b, double* cov_dev, int64_t ld, double* state_dev, void* ws_dev, size_t ws_bytes) {
+    if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
+    int rc = check_device_buffers({cov_dev, state_dev, ws_dev}, ws_bytes, batch_layout(b->members).total,
+                                  "ekf_batch_query_sizes");
+    if (rc) return rc;
+    if (ld != b->ld) return fail(EKF_ERR_INVALID, "ld must equal the value from ekf_batch_query_sizes");
+    HIP_TRY(hipSetDevice(b->device));
+    b->cov = cov_dev;
+    b->state = state_dev;
+    b->ws = static_cast<char*>(ws_dev);
+    b->bound = true;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->ws, b->noise.data(), b->noise.size() * 8, hipMemcpyHostToDevice));
+    std::vector<double> poses((size_t)b->members * 10, 0.0);
+    for (int32_t m = 0; m < b->members; ++m) poses[(size_t)m * 10 + 3] = 1.0;
+    return ekf_batch_reset(b, -1, poses.data());
+}
+
+int ekf_batch_set_noise(ekf_batch* b, const double* noise) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (!noise) return fail(EKF_ERR_INVALID, "noise is NULL");
+    for (int32_t m = 0; m < b->members; ++m) {
+        rc = check_noise(noise + 6 * (size_t)m);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    std::memcpy(b->noise.data(), noise, b->noise.size() * 8);
+    HIP_TRY(hipMemcpy(b->ws, b->noise.data(), b->noise.size() * 8, hipMemcpyHostToDevice));
+    return EKF_OK;
+}
+
+// state = initial pose, P = initial_camera_uncertainty I_10 (the member's own), no landmarks, status cleared.
+// member = -1: every member, initial_poses [B,10]; otherwise initial_poses [10].
+int ekf_batch_reset(ekf_batch* b, int32_t member, const double* initial_poses) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (!initial_poses) return fail(EKF_ERR_INVALID, "initial poses are NULL");
+    if (member != -1 && (rc = batch_member(b, member))) return rc;
+    const int32_t lo = member < 0 ? 0 : member, hi = member < 0 ? b->members : member + 1;
+    const int64_t ld = b->ld;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemset(b->cov + (size_t)lo * ld * ld, 0, (size_t)(hi - lo) * ld * ld * 8));
+    HIP_TRY(hipMemset(b->state + (size_t)lo * ld, 0, (size_t)(hi - lo) * ld * 8));
+    HIP_TRY(hipMemcpy2D(b->state + (size_t)lo * ld, (size_t)ld * 8, initial_poses, 10 * 8, 10 * 8, hi - lo,
+                        hipMemcpyHostToDevice));
+    std::vector<double> diag((size_t)(hi - lo) * EKF_CAM);
+    for (int32_t m = lo; m < hi; ++m) {
+        for (int i = 0; i < EKF_CAM; ++i) diag[(size_t)(m - lo) * EKF_CAM + i] = b->noise[(size_t)m * 6];
+        b->nlm[m] = 0;
+        b->status[m] = 0;
+    }
+    // P = icu I_10: the diagonal of every member's matrix is a strided run of ld + 1 elements
+    for (int32_t m = lo; m < hi; ++m)
+        HIP_TRY(hipMemcpy2D(b->cov + (size_t)m * ld * ld, (size_t)(ld + 1) * 8, diag.data() + (size_t)(m - lo) * EKF_CAM, 8, 8,
+                            EKF_CAM, hipMemcpyHostToDevice));
+    return batch_put_member_words(b, lo, hi);
+}
+
+// (state [3 n + 10], P [3 n + 10, 3 n + 10]) of one member from the host; P is symmetrised ((P + P^T) / 2) on upload.
+// The member's status is cleared.
+int ekf_batch_set_member(ekf_batch* b, int32_t member, const double* state, int32_t num_landmarks, const double* cov) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if ((rc = batch_member(b, member))) return rc;
+    if (!state || !cov || num_landmarks < 0) return fail(EKF_ERR_INVALID, "bad member state");
+    if (num_landmarks > b->cfg.max_landmarks) return fail(EKF_ERR_CAPACITY, "more landmarks than max_landmarks");
+    const int64_t ld = b->ld;
+    const int dims = EKF_LM * num_landmarks + EKF_CAM;
+    std::vector<double> st((size_t)ld, 0.0), p((size_t)ld * ld, 0.0);
+    std::memcpy(st.data(), state, (size_t)dims * 8);
+    for (int i = 0; i < dims; ++i)
+        for (int j = 0; j < dims; ++j) p[(size_t)i * ld + j] = 0.5 * (cov[(size_t)i * dims + j] + cov[(size_t)j * dims + i]);
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->state + (size_t)member * ld, st.data(), st.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->cov + (size_t)member * ld * ld, p.data(), p.size() * 8, hipMemcpyHostToDevice));
+    b->nlm[member] = num_landmarks;
+    b->status[member] = 0;
+    return batch_put_member_words(b, member, member + 1);
+}
+
+// state[0:count] and, if cov is not NULL, P [dims, dims] with dims = 3 n + 10 of one member.  Synchronises.
+int ekf_batch_get_member(ekf_batch* b, int32_t member, double* state, int32_t count, double* cov, int32_t dims) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if ((rc = batch_member(b, member))) return rc;
+    if ((rc = batch_refresh(b))) return rc;
+    const int n = EKF_LM * b->nlm[member] + EKF_CAM;
+    if (count < 0 || count > n || (count > 0 && !state)) return fail(EKF_ERR_INVALID, "bad state request");
+    if (cov && dims != n) return fail(EKF_ERR_INVALID, "dims must equal the member's state dimension");
+    const int64_t ld = b->ld;
+    if (count > 0) HIP_TRY(hipMemcpy(state, b->state + (size_t)member * ld, (size_t)count * 8, hipMemcpyDeviceToHost));
+    if (cov)
+        HIP_TRY(hipMemcpy2D(cov, (size_t)dims * 8, b->cov + (size_t)member * ld * ld, (size_t)ld * 8, (size_t)dims * 8, dims,
+                            hipMemcpyDeviceToHost));
+    return EKF_OK;
+}
+
+int ekf_batch_num_landmarks(const ekf_batch* b, int32_t* out) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
+    if ((rc = batch_refresh(const_cast<ekf_batch*>(b)))) return rc;
+    std::memcpy(out, b->nlm.data(), b->nlm.size() * 4);
+    return EKF_OK;
+}
+
+int ekf_batch_status(ekf_batch* b, int32_t* out) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
+    if ((rc = batch_refresh(b))) return rc;
+    std::memcpy(out, b->status.data(), b->status.size() * 4);
+    return EKF_OK;
+}
+
+int ekf_batch_log_workspace_bytes(const ekf_batch* b, int64_t detections, int64_t frames, size_t* bytes) {
+    if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
+    if (!bytes || detections < 0 || frames < 0) return fail(EKF_ERR_INVALID, "bad log size request");
+    *bytes = batch_log_layout(detections, frames, b->members).total;
+    return EKF_OK;
+}
+
+int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, const int64_t* member_frames,
+                           const double* poses_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    // ---- validation on the host: nothing is enqueued before every log has passed
+    const int32_t B = b->members;
+    if (!member_frames || !frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
+    if ((rc = check_offsets(member_frames, B, "member_frames"))) return rc;
+    const int64_t F = member_frames[B];
+    if ((rc = check_offsets(frame_offsets, F, "frame_offsets"))) return rc;
+    const int64_t D = frame_offsets[F];
+    if (D > 0 && (!lm_index || !poses_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
+    const BatchLogLayout LL = batch_log_layout(D, F, B);
+    if ((rc = check_device_buffers({log_ws}, log_ws_bytes, LL.total, "ekf_batch_log_workspace_bytes"))) return rc;
+    if ((rc = batch_refresh(b))) return rc;      // (landmark counts as the previous call left them)
+    int32_t n_max = 0, widest = 0;
+    int64_t frames_max = 0;
+    LogCheck lc;
+    for (int32_t m = 0; m < B; ++m) {
+        const int64_t f0 = member_frames[m], frames = member_frames[m + 1] - f0;
+        rc = check_log(lm_index, frame_offsets + f0, frames, b->nlm[m], b->cfg, "member " + std::to_string(m) + "'s log", &lc);
+        if (rc) return rc;
+        n_max = std::max(n_max, (int32_t)lc.n);
+        widest = std::max(widest, (int32_t)lc.widest);
+        frames_max = std::max(frames_max, frames);
+    }
+    if (F == 0) return EKF_OK;
+
+    // ---- staging: one copy of indices and offsets (the stream is idle: batch_refresh synchronised it)
+    if ((rc = b->pin.reserve(LL.total))) return rc;
+    if (D > 0) std::memcpy(b->pin.get(), lm_index, (size_t)D * 4);
+    std::memcpy(b->pin.get() + LL.frames, frame_offsets, (size_t)(F + 1) * 8);
+    std::memcpy(b->pin.get() + LL.members, member_frames, (size_t)(B + 1) * 8);
+    char* ws = static_cast<char*>(log_ws);
+    HIP_TRY(hipMemcpyAsync(ws, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
+
+    // ---- windows: every member's frames [w, w + kBatchWindow) of its log per launch, state carried in HBM.  LDS is
+    // sized for the widest frame and the largest map of the call (a layout choice only: the arithmetic is the same)
+    const BatchLayout L = batch_layout(B);
+    EkfBatchWindow a{};
+    a.P = b->cov;
+    a.ld = b->ld;
+    a.state = b->state;
+    a.noise = reinterpret_cast<const double*>(b->ws);
+    a.status = reinterpret_cast<int32_t*>(b->ws + L.status);
+    a.nlm = reinterpret_cast<int32_t*>(b->ws + L.nlm);
+    a.lm_index = reinterpret_cast<const int32_t*>(ws);
+    a.frame_offsets = reinterpret_cast<const int64_t*>(ws + LL.frames);
+    a.member_frames = reinterpret_cast<const int64_t*>(ws + LL.members);
+    a.poses = poses_dev;
+    a.traj = trajectory_dev;
+    a.quat_mode = b->cfg.quat_mode;
+    a.kmax = std::max(3, 3 * widest);
+    a.lda = (int32_t)round_up(EKF_LM * n_max + EKF_CAM + 1, 4);
+    a.window_frames = kBatchWindow;
+    for (int64_t w = 0; w < frames_max; w += kBatchWindow) {
+        a.window_first = (int32_t)w;
+        ekf_launch_batch_window(a, B, b->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return EKF_OK;
+}
+
+}  // extern "C"

@@ -118,6 +118,8 @@ def test_batch_config_limits_are_checked():
         bad.max_visible = 16
         setattr(bad, field, value)
         assert lib.ekf_batch_query_sizes(ctypes.byref(bad), 8, None, None, None, None) == -1, field
+        if field in ("max_landmarks", "max_visible"):      # (batch errors reach the library's one error slot)
+            assert field.encode() in lib.ekf_last_error_string(), field
     assert lib.ekf_batch_query_sizes(ctypes.byref(cfg), 0, None, None, None, None) == -1
 
 

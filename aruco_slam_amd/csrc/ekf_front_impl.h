@@ -57,9 +57,8 @@ __host__ __device__ inline size_t fr_chunk_a_len(int kpad, bool fix, int elem) {
     const size_t st = elem == 4 ? (size_t)(FR_KS * 128 + FR_KS * 64 + 128 * 64) / 2 : (size_t)(2 * FR_KS64 * 64 + 64 * 64);
     return (fix && a < st) ? st : a;
 }
-// NB >= 2: the four waves that do not substitute fetch whole block columns of the factor into LDS slots instead
+// NB >= 2: the four waves that do not substitute fetch whole block columns of the factor into LDS slots
 // (fr_panel_stage), see fr_panel.
-#define FR_STAGED_MIN_NB 2
 #define FR_SLOTS 4
 
 typedef double pf64x4 __attribute__((ext_vector_type(4)));
@@ -73,9 +72,6 @@ __device__ __forceinline__ void fr_w_store(T* p, T v) {
 typedef float fr_f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ void ekf_poll_sleep() { __builtin_amdgcn_s_sleep(4); }
-// every exchange read is a coherent load (`coherent` kept for readability at the call sites: first
-// attempt vs retry)
-__device__ __forceinline__ double ekf_ldt(const double* p, bool /*coherent*/) { return ekf_ldc(p); }
 
 // ---------------------------------------------------------------------------------------------
 // measurement model of every detection into LDS (one thread per detection), shared by the measurement
@@ -532,17 +528,16 @@ __device__ __forceinline__ void fr_role_factor(const EkfFrame& fr, double* v_sm)
 // t[b] starts as A_b and ends as W_b; per finished block column q of the factor:
 //   W_q = Dinv_q t[q] ;  t[i] += (-L_iq) W_q  for i > q ;  dx += W_q^T y_q
 // (same fma sequence per t[i] and for dx as the left-looking stand-alone panel kernel).
-// Only wave 0 of the workgroup polls memory for block column q (4 loads per round, so the
-// factorisation's stores are not stuck behind a storm of polls); the other waves watch an LDS word.
+// NB >= 2: the block columns come through LDS slots that the other four waves of the workgroup fill (fr_panel_stage).
+// NB == 1: only wave 0 of the workgroup polls memory for Dinv_0 / y_0 (4 loads per round, so the factorisation's
+// stores are not stuck behind a storm of polls); the other waves watch an LDS word.
 // What a wave of the substitution requests BEFORE the A chunk is built (the requests are in flight during that
-// build): the first blocks of -L of block column 0, (wave 0) Dinv_0 / y_0, and which of the next frame's support
-// slots its column feeds.  A word that has not been published yet arrives as the sentinel and is fetched again.
+// build): (NB == 1, wave 0) Dinv_0 / y_0, and which of the next frame's support slots its column feeds.  A word that
+// has not been published yet arrives as the sentinel and is fetched again.
 template <int NB>
 struct FrPre {
-    static constexpr bool STAGED = NB >= FR_STAGED_MIN_NB;
     static constexpr int SLOT = NB * 256 + 16;      // doubles per staged block column: Dinv | -L blocks below the diagonal | y
-    static constexpr int LG = (NB >= 11) ? 4 : 6;
-    double lqa[LG][4], dqn[4], yqn[4];
+    double dqn[4], yqn[4];
     unsigned long long smask;       // next-frame detections whose landmark owns this lane's column (duplicates possible)
     int sdim;
     double st_old, q_old[4];        // EKF model: the old state of this lane's column / the old camera quaternion (wave 0)
@@ -550,12 +545,7 @@ struct FrPre {
 template <int NB, int MODEL>
 __device__ __forceinline__ void fr_panel_pre(const EkfFrame& fr, FrPre<NB>& pre, const unsigned long long* smask_l, int wv, int col0, int lane) {
     const int j = lane & 15, g = lane >> 4;
-    const double* __restrict__ xlop = fr.xl;
-    if constexpr (!FrPre<NB>::STAGED) {
-#pragma unroll
-        for (int i = 1; i < NB && i < 1 + FrPre<NB>::LG; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) pre.lqa[i - 1][r] = ekf_ldc(xlop + sv_lop_index(i, 0) + r * 64 + lane);
+    if constexpr (NB == 1) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             pre.dqn[r] = (wv == 0) ? ekf_ldc(fr.xl + fr.xl_dop + (size_t)r * 64 + lane) : 0.0;
@@ -578,7 +568,7 @@ __device__ __forceinline__ void fr_panel_pre(const EkfFrame& fr, FrPre<NB>& pre,
     pre.sdim = (mycol >= EKF_CAM) ? (mycol - EKF_CAM) % EkfModel<MODEL>::LMD : 0;
 }
 
-// Staged substitution (NB >= FR_STAGED_MIN_NB), the waves 4 .. 7 of a chunk workgroup: wave w fetches the block columns
+// Staged substitution (NB >= 2), the waves 4 .. 7 of a chunk workgroup: wave w fetches the block columns
 // q = w, w + 4, w + 8 .. of the factor -- Dinv_q and y_q, then the -L_iq below them: four columns in flight per
 // workgroup -- polls until every word has been published (sentinel), and puts the column into slot
 // q % FR_SLOTS of the A-chunk region of LDS (free once the substituting waves hold their columns of A in registers: the
@@ -594,7 +584,7 @@ __device__ __forceinline__ void fr_panel_stage(const EkfFrame& fr, double* slots
     // poll -> last substitution step -> W / dx / state.  One wave polling with one request in flight sees it a memory round
     // trip and a half after it was published on average (2.2 us per round trip beside the previous frame's covariance
     // update); the loaders that have no column left poll it as well, out of phase, and whoever has it first places it.
-    constexpr bool HELP = NB >= 2 && NB <= 8;
+    constexpr bool HELP = NB <= 8;
     const double* __restrict__ xlop = fr.xl;
     const double* __restrict__ xdop = fr.xl + fr.xl_dop;
     const double* __restrict__ xy = fr.xl + fr.xl_y;
@@ -740,9 +730,6 @@ template <typename T, int NB, int MODEL>
 __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds, volatile ekf_lds_int* sync, double* pshare,
                                          int wv, int col0, int lane, int& spin_fail, FrPre<NB>& pre) {
     const int j = lane & 15, g = lane >> 4;
-    const double* __restrict__ xlop = fr.xl;
-    const double* __restrict__ xdop = fr.xl + fr.xl_dop;
-    const double* __restrict__ xy = fr.xl + fr.xl_y;
     long long* stp = (fr.stamps && col0 == 0 && lane == 0) ? fr.stamps + 34 : nullptr;
     T* __restrict__ wp = static_cast<T*>(fr.wpanel);
     // pipelined sequence mode: the columns of W that the NEXT frame's front kernel needs for its support rows
@@ -764,14 +751,7 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
     const double q_old[4] = {pre.q_old[0], pre.q_old[1], pre.q_old[2], pre.q_old[3]};
     const double q_rn = (MODEL == 0 && col0 == 0) ? ekf_quat_rnorm(q_old) : 0.0;      // (here: not on the tail of the launch)
     double part = 0.0;
-    // Prefetch (a chunk that is BEHIND the factorisation -- every chunk in the pipelined sequence mode, whose
-    // prologue is longer -- finds everything published already; fetching Dinv / y, then -L, then computing cost two
-    // dependent memory round trips per block column, 2.2 - 2.8 us): the first LG blocks of -L of block column q + 1
-    // and (wave 0) its Dinv / y are requested during step q.  A word that has not been published yet reads as the
-    // sentinel: such a column goes through the polling path exactly as before.
-    constexpr int LG = FrPre<NB>::LG;
-    constexpr bool AHEAD = NB <= 8;                 // two register sets for -L
-    if constexpr (FrPre<NB>::STAGED) {
+    if constexpr (NB > 1) {
         // block columns come through LDS (fr_panel_stage); `pshare` holds the slot flags
         constexpr int SLOT = FrPre<NB>::SLOT;
         volatile ekf_lds_int* flags = ekf_lds_flags(pshare);
@@ -830,34 +810,19 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
             if (stp) stp[q] = wall_clock64();
         }
     } else {
-    auto& lqa = pre.lqa;
-    auto& dqn = pre.dqn;
-    auto& yqn = pre.yqn;
-    double lqb[AHEAD ? LG : 1][4];
-    auto issue_l = [&](auto& lq, int q) {
-#pragma unroll
-        for (int i = q + 1; i < NB && i < q + 1 + LG; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) lq[i - q - 1][r] = ekf_ldc(xlop + sv_lop_index(i, q) + r * 64 + lane);
-    };
-    auto issue_d = [&](int q) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            dqn[r] = ekf_ldc(xdop + (size_t)(q * 4 + r) * 64 + lane);
-            yqn[r] = ekf_ldc(xy + 16 * q + g + 4 * r);
-        }
-    };
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
+        // NB == 1, one block column.  Wave 0 takes Dinv_0 / y_0 as requested in fr_panel_pre (a chunk that is BEHIND the
+        // factorisation -- every chunk in the pipelined sequence mode, whose prologue is longer -- finds them published
+        // already) and shares them through `pshare`: sync[0] = block columns shared so far, sync[1] = reads of the shared
+        // slot acknowledged
+        const double* __restrict__ xdop = fr.xl + fr.xl_dop;
+        const double* __restrict__ xy = fr.xl + fr.xl_y;
         double dq[4], yq[4];
-        if (!AHEAD && q > 0) issue_l(lqa, q);
         if (wv == 0) {
-            // sync[0] = block columns shared so far, sync[1] = reads of the shared slot acknowledged
             bool pend = false;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                dq[r] = dqn[r];
-                yq[r] = yqn[r];
+                dq[r] = pre.dqn[r];
+                yq[r] = pre.yqn[r];
                 pend = pend || ekf_is_sent(dq[r]) || ekf_is_sent(yq[r]);
             }
             if (__any(pend)) {
@@ -868,8 +833,8 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
                     pend = false;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        dq[r] = ekf_ldc(xdop + (size_t)(q * 4 + r) * 64 + lane);
-                        yq[r] = ekf_ldc(xy + 16 * q + g + 4 * r);
+                        dq[r] = ekf_ldc(xdop + (size_t)r * 64 + lane);
+                        yq[r] = ekf_ldc(xy + g + 4 * r);
                         pend = pend || ekf_is_sent(dq[r]) || ekf_is_sent(yq[r]);
                     }
                     if (!__any(pend)) break;
@@ -878,7 +843,7 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
                 }
             }
             int it = 0;
-            while (sync[1] < 3 * q) {                  // the slot's previous content has been read
+            while (sync[1] < 0) {                      // (the slot has had no content before: the wait never loops)
                 if (++it > 64 * EKF_SPIN_MAX) { spin_fail = 1; break; }
                 __builtin_amdgcn_s_sleep(1);
             }
@@ -889,11 +854,10 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
                 pshare[(4 + r) * 64 + lane] = yq[r];
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");     // the slot before the word that announces it
-            if (lane == 0) sync[0] = q + 1;
-            if (q + 1 < NB) issue_d(q + 1);
+            if (lane == 0) sync[0] = 1;
         } else {
             int it = 0;
-            while (sync[0] < q + 1) {
+            while (sync[0] < 1) {
                 if (++it > 64 * EKF_SPIN_MAX) { spin_fail = 1; break; }
                 __builtin_amdgcn_s_sleep(1);
             }
@@ -906,17 +870,13 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");     // the reads before the acknowledgement
             if (lane == 0) __hip_atomic_fetch_add(const_cast<ekf_lds_int*>(sync) + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        if (AHEAD && q + 1 < NB) {                   // (before this step's W stores: a wait for a load also waits for every older store)
-            if ((q & 1) == 0) issue_l(lqb, q + 1);
-            else issue_l(lqa, q + 1);
-        }
         pf64x4 wq = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) wq = __builtin_amdgcn_mfma_f64_16x16x4f64(dq[r], t[q][r], wq, 0, 0, 0);
-        t[q] = wq;
+        for (int r = 0; r < 4; ++r) wq = __builtin_amdgcn_mfma_f64_16x16x4f64(dq[r], t[0][r], wq, 0, 0, 0);
+        t[0] = wq;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {                   // W rows of block q are final
-            const int row = 16 * q + g + 4 * r;
+        for (int r = 0; r < 4; ++r) {                   // W rows of block 0 are final
+            const int row = g + 4 * r;
             fr_w_store(wp + (int64_t)row * fr.ldw + col0 + j, (T)wq[r]);
             if (fr.wdbg) fr.wdbg[(int64_t)row * fr.ldw + col0 + j] = wq[r];
             if (cslot >= 0) fr_w_store(wsup + (int64_t)row * fr.wsup_ld + cslot, (T)wq[r]);
@@ -926,42 +886,9 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
                 fr_w_store(wsup + (int64_t)row * fr.wsup_ld + EKF_CAM + LMD * jj + sdim, (T)wq[r]);
             }
         }
-        // t[i] += (-L_iq) W_q for i > q, at most LG blocks of -L in registers at a time (the whole
-        // kernel has to stay clear of register spills); the first LG were requested a step ago
-        auto apply = [&](auto& lq, int i0, bool fresh) {
-            int it = 0;
-            for (;; fresh = true) {      // normally one pass
-                bool pend = false;
-#pragma unroll
-                for (int i = i0; i < NB && i < i0 + LG; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if (fresh) lq[i - i0][r] = ekf_ldc(xlop + sv_lop_index(i, q) + r * 64 + lane);
-                        pend = pend || ekf_is_sent(lq[i - i0][r]);
-                    }
-                if (!__any(pend)) break;
-                if (++it > EKF_SPIN_MAX) { spin_fail = 1; break; }
-                ekf_poll_sleep();
-            }
-#pragma unroll
-            for (int i = i0; i < NB && i < i0 + LG; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    t[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(lq[i - i0][r], wq[r], t[i], 0, 0, 0);
-        };
-        if (q + 1 < NB) {
-            if (AHEAD && (q & 1)) apply(lqb, q + 1, false);
-            else apply(lqa, q + 1, false);
-        }
-#pragma unroll
-        for (int i0 = q + 1 + LG; i0 < NB; i0 += LG) {
-            double lq[LG][4];
-            apply(lq, i0, true);
-        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) part = __builtin_fma(wq[r], yq[r], part);
-        if (stp) stp[q] = wall_clock64();
-    }
+        if (stp) stp[0] = wall_clock64();
     }
     part += __shfl_xor(part, 16);
     part += __shfl_xor(part, 32);                    // dx[col0 + j] in every lane group
@@ -1065,7 +992,7 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
         nidx[tid - 64] = ((unsigned)ni >= (unsigned)fr.n_lm) ? 0 : ni;
     }
     if (tid == 0) { flag[1] = 0; flag[2] = 0; }
-    if (FrPre<NB>::STAGED && tid < 16) ekf_lds_flags(pshare)[tid] = 0;      // (staged substitution: slot flags)
+    if (NB > 1 && tid < 16) ekf_lds_flags(pshare)[tid] = 0;      // (staged substitution: slot flags)
     __syncthreads();
     if (fr.wsup && tid < 64) {      // next-frame detections whose landmark owns column c (duplicates possible)
         unsigned long long mk = 0ull;
@@ -1333,7 +1260,7 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
         const int lane = tid & 63, col0 = chunk0 + 16 * g;
         fr_panel<T, NB, MODEL>(fr, a_lds, ekf_lds_flags(flag + 1), pshare, g, col0, lane, spin_fail, pre);
         if (spin_fail && (tid & 63) == 0) ekf_raise(fr, EKF_ST_TIMEOUT);
-    } else if constexpr (FrPre<NB>::STAGED) {
+    } else if constexpr (NB > 1) {
         fr_panel_stage<NB>(fr, a_lds, ekf_lds_flags(pshare), g - 4, tid & 63);
     }
     if (MODEL == 0) return;

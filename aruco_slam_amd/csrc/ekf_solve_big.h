@@ -70,7 +70,7 @@ __device__ __forceinline__ void svb_post(volatile ekf_lds_int* word, int value, 
 // put_dinv / put_l / put_y as in sv_factor.
 template <int NB, class IO>
 __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double* lds, int& bad, int& badcol) {
-    static_assert(NB >= 2 && NB <= 24, "block columns");
+    static_assert(NB >= 9 && NB <= 24, "block columns");
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int NR = NB + 1;                                   // block rows, the residual row included
@@ -151,7 +151,7 @@ __device__ __forceinline__ void sv_factor_big(const EkfFrame& fr, IO& io, double
         }
     };
     fetch_column(tcur, 0);
-    if (NB > 1) fetch_column(tnxt, 1);
+    fetch_column(tnxt, 1);
     if (widx == 0) {                                             // row 0: the first diagonal block
         sv_lds_put(dblk, tcur[0], lane);
         svb_post(dready, 1, lane);

@@ -1,6 +1,7 @@
 // Blocked Cholesky of S for FEW block columns (NB <= 6, k <= 96 rows: the headline shapes), one workgroup of 8 waves, with ONE
 // wave running every pivot chain.  Same arithmetic as sv_factor (ekf_solve_device.h) -- every block receives the same MFMA
-// sequences in the same order, so the factor has the same bits -- but a different choreography:
+// sequences in the same order, so the factor has the same bits -- but a different choreography (sv_factor, which now serves
+// NB = 7, 8, was measured here at C3, when it still served NB <= 6):
 //
 //   sv_factor      the chain of block column b runs on the wave that owns row b.  Between two chains: LDS put of X_b -> hardware
 //                  barrier (every wave has to arrive) -> the owner of row b + 1 gets X_b from LDS -> its panel (4 dependent f64

@@ -8,7 +8,6 @@
 // flush) and readiness is carried by the data itself: an exchange buffer holds EKF_SENT (a NaN
 // payload no computation produces) until the producer overwrites it.
 #define EKF_SENT_BITS 0xFFFBADC0FFFBADC0ull
-#define EKF_SENT_WORD 0xFFFBADC0u
 #define EKF_SPIN_MAX 400000
 __device__ __forceinline__ double ekf_sent() { return __longlong_as_double((long long)EKF_SENT_BITS); }
 __device__ __forceinline__ bool ekf_is_sent(double v) { return __double_as_longlong(v) == (long long)EKF_SENT_BITS; }
@@ -18,7 +17,6 @@ __device__ __forceinline__ double ekf_ldc(const double* p) {
 __device__ __forceinline__ void ekf_stc(double* p, double v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool COH> __device__ __forceinline__ double ekf_ldx(const double* p) { return COH ? ekf_ldc(p) : *p; }
 
 typedef double sf64x4 __attribute__((ext_vector_type(4)));
 
@@ -99,10 +97,6 @@ __device__ __forceinline__ double sv_rcp(double d) {
     return __builtin_fma(r0, p, r0);
 }
 
-// value of lane J of each 16-lane row, in every lane of that row (one v_mov_b64_dpp row_newbcast)
-template <int J> __device__ __forceinline__ double sv_row_bcast(double v) {
-    return __builtin_amdgcn_update_dpp(v, v, 0x150 + J, 0xf, 0xf, false);
-}
 // the values of 16-lane group G0, in all four groups (gfx950 cross-row swaps; semantics checked by
 // tools/probes/permlane_probe.hip:  permlane16_swap(D, S) -> D' = [D.r0 S.r0 D.r2 S.r2], S' = [D.r1 S.r1 D.r3 S.r3];
 // permlane32_swap(D, S) -> D' = [D.lo32 S.lo32], S' = [D.hi32 S.hi32])
@@ -116,16 +110,6 @@ template <int G0> __device__ __forceinline__ double sv_group_bcast(double v) {
     return __hiloint2double(sv_group_bcast32<G0>(__double2hiint(v)), sv_group_bcast32<G0>(__double2loint(v)));
 }
 
-// The 16-pivot chain: LDL^T of one 16 x 16 block by rank-1 updates, entirely in the vector ALU of one
-// wave (on MI355X an f64 MFMA costs as many cycles as the vector FMAs it replaces -- 64 cycles per
-// 16x16x4 -- so a rank-1 update through the matrix pipe would waste three quarters of it).
-// C layout: lane (c, g), register rr <-> M[g + 4 rr][c].  Pivot J (R = J / 4, G0 = J % 4):
-//     M[i][c] -= M[i][J] * M[J][c] / d_J
-//   * column J by row index, M[g + 4 rr][J], sits in lane (J, g): a row broadcast (DPP) of register rr;
-//   * row J by column index, M[J][c], sits in register R of group G0: a group broadcast (two swaps per dword);
-//   * U = (L'^-1)^T is carried along:  U[i][c] -= U[i][J] * L'[c][J]  needs the same two kinds of operand
-//     and no other; at the end U in C layout IS L'^-1 in OP layout, i.e. `dop` order: no transpose.
-// Only columns c > J are touched (exact zeros above the diagonal of L'^-1, row J of it stays intact).
 // the values of 16-lane group G0 in all four groups through the LDS crossbar (ds_bpermute: two instructions
 // to issue, ~80 cycles until the data is back -- time the chain spends on other instructions; the swap
 // version above costs the same ~75 cycles, but as ISSUE time)
@@ -230,8 +214,9 @@ __device__ __forceinline__ int sv_chain_t(SvChain& s, sf64x4& xop, int c, int g)
 // every piece of its straight-line code once per launch, i.e. from a cold instruction cache (120 - 150 KB of code at
 // k = 96, a 64 KB cache shared by two CUs), and the chain is the serial part everything else waits for.  Inlined, each
 // of the NB chains was a fresh 4.4 KB of code.  As a function the first call warms the cache for the others -- and
-// sv_factor makes that first call on an idle wave while the S blocks are still on their way.  (The callee starts with
-// `s_waitcnt vmcnt(0)`, as every function does: free, as long as the calling wave has no store in flight -- see PUB.)
+// sv_factor makes that first call on its last wave before that wave requests its blocks.  (The callee starts with
+// `s_waitcnt vmcnt(0)`, as every function does: free, as long as the calling wave has no store in flight -- not so in
+// sv_factor, whose chain owners publish their own blocks, see there.)
 struct SvChainRes {
     sf64x4 xop;
     int bad;
@@ -349,9 +334,11 @@ struct SvIoPlain {
     }
 };
 
-// The factorisation.  `lds`: sv_lds_doubles(NB) doubles.  Every wave of the workgroup calls it.
+// The factorisation for 7 and 8 block columns (sv_factor_any: fewer go to sv_factor_cw, more to sv_factor_big).
+// `lds`: sv_lds_doubles(NB) doubles.  Every wave of the workgroup calls it.
 template <int NB, class IO>
 __device__ __forceinline__ void sv_factor(const EkfFrame& fr, IO& io, double* lds, int& bad, int& badcol) {
+    static_assert(NB >= 7 && NB <= 8, "block columns");
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
     constexpr int N0 = NB < 8 ? NB : 8;             // blocks a row i <= 7 can have
     constexpr bool TWO = NB >= 8;                   // rows 8 .. NB exist: second row per wave
@@ -382,28 +369,21 @@ __device__ __forceinline__ void sv_factor(const EkfFrame& fr, IO& io, double* ld
     // do (b even: row b + 1, whose blocks are all covered by the urgent updates below).
     const int i0 = 2 * (wave & 3) + (wave >> 2), i1 = i0 + 8;
     const bool has0 = i0 <= NB, has1 = TWO && i1 <= NB;
-    // Up to NB = 6 the last wave owns no row: it does ALL the publishing (Dinv, -L, y: from the LDS copies the other
-    // waves leave anyway), so that no wave that computes ever has a global store in flight.  A wait for ANYTHING that
-    // counts in vmcnt -- and hipcc places conservative `s_waitcnt vmcnt(0)` wherever a register with a formally
-    // pending load is reused, e.g. at the top of the next chain -- also waits for every older store of the wave, and
-    // the acknowledgement of a write-through store takes 1 - 2k cycles beside the covariance update's traffic: with
-    // every row publishing its own block, that was the larger part of the hand-over between two chains.
-    constexpr bool PUB = NB <= 6;
-    const bool is_pub = PUB && wave == SV_NW - 1;
+    // Every wave owns a row, and every row publishes its own blocks straight from its registers: Dinv_b the chain's
+    // owner, -L_ib / y_b the row's panel.  That is on the critical path: a wait for ANYTHING that counts in vmcnt -- and
+    // hipcc places conservative `s_waitcnt vmcnt(0)` wherever a register with a formally pending load is reused, e.g. at
+    // the top of the next chain -- also waits for every older store of the wave, and the acknowledgement of a
+    // write-through store takes 1 - 2k cycles beside the covariance update's traffic: with every row publishing its own
+    // block, that was the larger part of the hand-over between two chains (sv_factor_cw has a wave that only publishes).
     sf64x4 z0[N0], z1[N1];
-    // optional time stamps (debug): [0] start, [1] blocks in registers, [2 + 2 b] chain phase of block column b
-    // over (barrier), [3 + 2 b] panel + urgent update over; [47 + 2 b], [48 + 2 b] the chain alone (b < 4)
+    // optional time stamps (debug): [0] start, [1] blocks in registers (wave 0), [24 + w] the same for wave w; of block
+    // column 0: [2] chain phase over (barrier), [3] panel + urgent update over, [47], [48] the chain alone, [16] row 1's
+    // panel posted
     long long* stp = (fr.stamps && fr.stamps_heavy && lane == 0) ? fr.stamps : nullptr;
     // Inside the loop the stamps stay in registers and are stored at the very end: a stamp that is stored at once is a
     // global store, and the wave that took it later waits for its acknowledgement -- it perturbs what it measures.
-    constexpr int NTS = NB <= 6 ? NB : 1;
-    long long ts_cs[NTS], ts_ce[NTS], ts_bar[NTS], ts_pan[NTS], ts_ph3[NTS];
-#pragma unroll
-    for (int q = 0; q < NTS; ++q) ts_cs[q] = ts_ce[q] = ts_bar[q] = ts_pan[q] = ts_ph3[q] = 0;
+    long long ts_cs = 0, ts_ce = 0, ts_bar = 0, ts_pan = 0, ts_ph3 = 0;
     if (stp && wave == 0) stp[0] = clock64();
-    // (light stamps: taken by the publishing wave, whose stores delay nobody)
-    long long* stl = (fr.stamps && !fr.stamps_heavy && is_pub && lane == 0) ? fr.stamps : nullptr;
-    if (stl) stl[0] = clock64();
     if (wave == SV_NW - 1) {      // warm the instruction cache (per CU) with the chain's code: identity block, result unused
         sf64x4 idm;
 #pragma unroll
@@ -415,7 +395,7 @@ __device__ __forceinline__ void sv_factor(const EkfFrame& fr, IO& io, double* ld
     // beside the first chain
     io.template load_cols<NB, N0, N1, 0, 1>(z0, z1, i0, i1, has0, has1, lane, g);
     if (stp && wave == 0) stp[1] = clock64();
-    if (stp && NB <= 10) stp[24 + wave] = clock64();            // (each wave: its blocks are in registers)
+    if (stp) stp[24 + wave] = clock64();                        // (each wave: its blocks are in registers)
     sf64x4 y0 = {0.0, 0.0, 0.0, 0.0}, y1 = {0.0, 0.0, 0.0, 0.0};      // OP(L_ib) of the wave's rows, column b
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -423,9 +403,9 @@ __device__ __forceinline__ void sv_factor(const EkfFrame& fr, IO& io, double* ld
         // ---- phase 1
         if (wave == owner) {
             SvChain s;
-            s.m = (b < 8) ? z0[b < N0 ? b : 0] : z1[b < N1 ? b : 0];
+            s.m = z0[b];
             sf64x4 xop;
-            if (stp && b < NTS) ts_cs[b < NTS ? b : 0] = clock64();
+            if (stp && b == 0) ts_cs = clock64();
             int badnow;
             if (fr.wdbg) badnow = sv_chain_t<true>(s, xop, c, g);      // (tests: also L' and the pivots)
             else {
@@ -433,11 +413,11 @@ __device__ __forceinline__ void sv_factor(const EkfFrame& fr, IO& io, double* ld
                 xop = res.xop;
                 badnow = res.bad;
             }
-            if (stp && b < NTS) ts_ce[b < NTS ? b : 0] = clock64();
+            if (stp && b == 0) ts_ce = clock64();
             if (badnow && !bad) badcol = 100 + b;
             bad |= badnow;
             sv_lds_put(xbuf0 + (b & 1) * 256, xop, lane);
-            if (!PUB) io.put_dinv(b, xop, lane);
+            io.put_dinv(b, xop, lane);
             if (fr.wdbg) {                            // dense L for tests only: L_bb = L' D^1/2
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -464,13 +444,12 @@ __device__ __forceinline__ void sv_factor(const EkfFrame& fr, IO& io, double* ld
                 }
         }
         __syncthreads();
-        if (stp && b < NTS) ts_bar[b < NTS ? b : 0] = clock64();
-        if (stl) stl[2 + 2 * b] = clock64();
+        if (stp && b == 0) ts_bar = clock64();
         // ---- phase 2: panel
         {
             const sf64x4 xop = sv_lds_get(xbuf0 + (b & 1) * 256, lane);
             if (has0 && i0 > b) {
-                y0 = sv_mm(xop, z0[b < N0 ? b : 0]);
+                y0 = sv_mm(xop, z0[b]);
                 sv_lds_put(ybuf + i0 * 256, y0, lane);
                 post_row(i0, b);
             }
@@ -480,28 +459,15 @@ __device__ __forceinline__ void sv_factor(const EkfFrame& fr, IO& io, double* ld
                 post_row(i1, b);
             }
         }
-        if (stp && b < NTS) ts_pan[b < NTS ? b : 0] = clock64();
+        if (stp && b == 0) ts_pan = clock64();
         // publication / emission: -L blocks in `lop` order (the registers as they are), y of the residual row
-        if (!PUB) {
-            if (has0 && i0 > b) {
-                if (i0 < NB) io.put_l(i0, b, y0, lane);
-                else io.put_y(b, (c >> 2) == 0 ? y0[0] : (c >> 2) == 1 ? y0[1] : (c >> 2) == 2 ? y0[2] : y0[3], c, g == (c & 3));
-            }
-            if (has1 && i1 > b) {
-                if (i1 < NB) io.put_l(i1, b, y1, lane);
-                else io.put_y(b, (c >> 2) == 0 ? y1[0] : (c >> 2) == 1 ? y1[1] : (c >> 2) == 2 ? y1[2] : y1[3], c, g == (c & 3));
-            }
-        } else if (is_pub) {
-            // (X_b stays in its slot until chain b + 2 is over and L_ib in its slot until the panel of step b + 1: both
-            // come after the next barrier, which this wave only reaches when it has read them)
-            io.put_dinv(b, sv_lds_get(xbuf0 + (b & 1) * 256, lane), lane);
-#pragma unroll
-            for (int i = b + 1; i <= NB; ++i) {
-                wait_row(i, b);
-                const sf64x4 yi = sv_lds_get(ybuf + i * 256, lane);
-                if (i < NB) io.put_l(i, b, yi, lane);
-                else io.put_y(b, (c >> 2) == 0 ? yi[0] : (c >> 2) == 1 ? yi[1] : (c >> 2) == 2 ? yi[2] : yi[3], c, g == (c & 3));
-            }
+        if (has0 && i0 > b) {
+            if (i0 < NB) io.put_l(i0, b, y0, lane);
+            else io.put_y(b, (c >> 2) == 0 ? y0[0] : (c >> 2) == 1 ? y0[1] : (c >> 2) == 2 ? y0[2] : y0[3], c, g == (c & 3));
+        }
+        if (has1 && i1 > b) {
+            if (i1 < NB) io.put_l(i1, b, y1, lane);
+            else io.put_y(b, (c >> 2) == 0 ? y1[0] : (c >> 2) == 1 ? y1[1] : (c >> 2) == 2 ? y1[2] : y1[3], c, g == (c & 3));
         }
         if (fr.wdbg) {
 #pragma unroll
@@ -517,11 +483,11 @@ __device__ __forceinline__ void sv_factor(const EkfFrame& fr, IO& io, double* ld
         for (int du = 1; du <= 2; ++du) {
             const int tc = b + du;
             if (tc < NB) {
-                if (has0 && i0 > b && tc < N0 && tc <= min(i0, NB - 1)) {
-                    if (i0 == tc) sv_mm_sub(z0[tc < N0 ? tc : 0], y0, y0);
+                if (has0 && i0 > b && tc <= min(i0, NB - 1)) {
+                    if (i0 == tc) sv_mm_sub(z0[tc], y0, y0);
                     else {
                         wait_row(tc, b);
-                        sv_mm_sub(z0[tc < N0 ? tc : 0], sv_lds_get(ybuf + tc * 256, lane), y0);
+                        sv_mm_sub(z0[tc], sv_lds_get(ybuf + tc * 256, lane), y0);
                     }
                 }
                 if (has1 && i1 > b && tc <= min(i1, NB - 1)) {
@@ -533,20 +499,15 @@ __device__ __forceinline__ void sv_factor(const EkfFrame& fr, IO& io, double* ld
                 }
             }
         }
-        if (stp && b < NTS) ts_ph3[b < NTS ? b : 0] = clock64();
+        if (stp && b == 0) ts_ph3 = clock64();
     }
-    if (stp) {      // [2 + 2 b] barrier, [3 + 2 b] end of step (wave 0); chain start / end (its owner); [16 + b] panel posted (row b + 1)
-#pragma unroll
-        for (int b = 0; b < NTS; ++b) {
-            if (wave == 0) {
-                stp[2 + 2 * b] = ts_bar[b];
-                stp[3 + 2 * b] = ts_ph3[b];
-            }
-            if (wave == ((b & 7) >> 1) + 4 * (b & 1)) {
-                stp[(b < 4 ? 47 : 48) + 2 * b] = ts_cs[b];
-                stp[(b < 4 ? 48 : 49) + 2 * b] = ts_ce[b];
-            }
-            if (has0 && i0 == b + 1) stp[16 + b] = ts_pan[b];
+    if (stp) {      // block column 0: barrier, end of step and the chain (wave 0 runs it); panel posted (row 1)
+        if (wave == 0) {
+            stp[2] = ts_bar;
+            stp[3] = ts_ph3;
+            stp[47] = ts_cs;
+            stp[48] = ts_ce;
         }
+        if (has0 && i0 == 1) stp[16] = ts_pan;
     }
 }

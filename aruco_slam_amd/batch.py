@@ -1,12 +1,13 @@
-"""``EKFBatch``: many independent ``EKF`` filters replayed at once on one GPU (the batch C ABI of
-``include/ekf_slam_hip.h``, kernel ``csrc/ekf_batch.hip``).
+"""``EKFBatch``: many independent ``EKF`` or ``EKF_Rotations`` filters replayed at once on one GPU (the batch C ABI of
+``include/ekf_slam_hip.h``, kernels ``csrc/ekf_batch.hip`` and ``csrc/ekf_batch_rot.hip``).
 
 What users of a filter of this size run is many sequences: a set of recorded runs, a sweep of the noise constants, Monte-Carlo
 studies on re-noised detections.  Each member is ``BaseFilter.process_detection_log`` with ``should_filter=True`` over its
 own log, with its own initial pose, noise constants and marker-id -> landmark-index table; one workgroup owns one member, so
-a batch fills the GPU where a single filter of this size leaves it almost idle.  All members share the model (``EKF``), the
-quaternion convention, an f64 covariance and the capacity (``max_landmarks`` <= 82, ``max_visible`` <= 16).  A batch never
-grows; there is no CPU fallback.
+a batch fills the GPU where a single filter of this size leaves it almost idle.  All members share the model, the quaternion
+convention, an f64 covariance and the capacity: ``model="ekf"`` (``EKF``) holds ``max_landmarks`` <= 82 and ``max_visible``
+<= 16, ``model="ekf_rotations"`` (``EKF_Rotations``, scalar-first quaternions only) ``max_landmarks`` <= 24 and
+``max_visible`` <= 8.  A batch never grows; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -20,6 +21,8 @@ from .hip_backend import EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, 
 NOISE_KEYS = ("initial_camera_uncertainty", "initial_landmark_uncertainty", "r_uncertainty", "q_cam", "q_err", "q_lm")
 EKF_ERR_NUMERIC = -5
 QUAT_MODES = {"as_written": EKF_QUAT_AS_WRITTEN, "scalar_first": EKF_QUAT_SCALAR_FIRST}
+MODELS = {"ekf": 0, "ekf_rotations": 1}
+LM_DIMS = {"ekf": 3, "ekf_rotations": 10}      # landmark dims: a member's state is [LM_DIMS n + 10]
 
 
 def _iptr(a: np.ndarray):
@@ -31,14 +34,22 @@ def _lptr(a: np.ndarray):
 
 
 class EKFBatch:
-    """``members`` filters.  ``initial_camera_pose``: [10] for all or [B, 10]; ``noise``: dict of scalars or length-B arrays
-    keyed by ``NOISE_KEYS`` (missing keys: the ``EKF`` constants)."""
+    """``members`` filters of ``model`` (``"ekf"``: ``EKF``, ``"ekf_rotations"``: ``EKF_Rotations``).
+    ``initial_camera_pose``: [10] for all or [B, 10]; ``quat_update``: None for the model's convention (``"as_written"`` for
+    ``EKF``; ``EKF_Rotations`` has only ``"scalar_first"``); ``noise``: dict of scalars or length-B arrays keyed by
+    ``NOISE_KEYS`` (missing keys: the model's constants)."""
 
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
-                 quat_update: str = "as_written", noise=None, device: str = "cuda:0") -> None:
+                 quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf") -> None:
         import torch
+        if model not in MODELS:
+            raise ValueError(f"model must be one of {sorted(MODELS)}, got {model!r}")
+        if quat_update is None:
+            quat_update = "scalar_first" if model == "ekf_rotations" else "as_written"
         if quat_update not in QUAT_MODES:
             raise ValueError(f"quat_update must be one of {sorted(QUAT_MODES)}, got {quat_update!r}")
+        if model == "ekf_rotations" and quat_update != "scalar_first":
+            raise ValueError(f"EKF_Rotations batches take quat_update \"scalar_first\" (or None), got {quat_update!r}")
         unknown = set(noise or {}) - set(NOISE_KEYS)
         if unknown:
             raise ValueError(f"unknown noise constants {sorted(unknown)}; known: {list(NOISE_KEYS)}")
@@ -48,11 +59,20 @@ class EKFBatch:
             raise RuntimeError("the EKF update path needs a HIP device (no CPU fallback)")
         self.members = int(members)
         self.device = torch.device(device)
+        self.model = model
+        self.lm_dims = LM_DIMS[model]
         self.quat_update = quat_update
         cfg = EkfConfig()
         self._check(self.lib.ekf_default_config(C.byref(cfg)))
         cfg.max_landmarks, cfg.max_visible = int(max_landmarks), int(max_visible)
         cfg.quat_mode = QUAT_MODES[quat_update]
+        cfg.model = MODELS[model]
+        if model == "ekf_rotations":
+            from .filters import ekf_with_rotations as rot
+            for key, val in zip(NOISE_KEYS, (rot.INITIAL_CAMERA_UNCERTAINTY, rot.INITIAL_LANDMARK_UNCERTAINTY,
+                                             rot.R_UNCERTAINTY, rot.Q_UNCERTAINTY_CAM, rot.Q_ERROR_UNCERTAINTY_CAM,
+                                             rot.Q_UNCERTAINTY_LM_XYZ)):
+                setattr(cfg, key, val)
         self.max_landmarks, self.max_visible = int(max_landmarks), int(max_visible)
         defaults = np.array([getattr(cfg, k) for k in NOISE_KEYS])
         self.noise = np.tile(defaults, (self.members, 1))
@@ -184,33 +204,35 @@ class EKFBatch:
 
     def get_state(self, b) -> np.ndarray:
         b = self._member(b)
-        out = np.empty(3 * self.num_landmarks[b] + 10)
+        out = np.empty(self.lm_dims * self.num_landmarks[b] + 10)
         self._check(self.lib.ekf_batch_get_member(self.h, b, _dptr(out), out.shape[0], None, 0))
         return out
 
     def get_cov(self, b) -> np.ndarray:
         b = self._member(b)
-        dims = 3 * self.num_landmarks[b] + 10
+        dims = self.lm_dims * self.num_landmarks[b] + 10
         out = np.empty((dims, dims))
         self._check(self.lib.ekf_batch_get_member(self.h, b, None, 0, _dptr(out), dims))
         return out
 
     def get_poses(self, b):
-        """``EKF.get_poses`` of member b: camera state [10], landmarks [n, 3]."""
+        """``get_poses`` of the model's filter for member b: camera state [10], landmarks [n, 3] (EKF) or [n, 10]
+        (EKF_Rotations)."""
         state = self.get_state(b)
-        return state[:10], state[10:].reshape(-1, 3)
+        return state[:10], state[10:].reshape(-1, self.lm_dims)
 
     def get_lm_uncertainties(self, b) -> np.ndarray:
-        return np.diagonal(self.get_cov(b))[10:].reshape(-1, 3).copy()
+        return np.diagonal(self.get_cov(b))[10:].reshape(-1, self.lm_dims).copy()
 
     def set_member(self, b, state, cov, marker_ids) -> None:
-        """Member b from host ``(state [3n+10], cov [3n+10, 3n+10], marker ids in landmark-index order)``; clears its
-        status.  cov is symmetrised on upload."""
+        """Member b from host ``(state [l n + 10], cov [l n + 10, l n + 10], marker ids in landmark-index order)`` with
+        l = ``lm_dims`` (3 for EKF, 10 for EKF_Rotations); clears its status.  cov is symmetrised on upload."""
         b = self._member(b)
         state = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
         ids = [int(k) for k in marker_ids]
-        if state.shape[0] != 3 * len(ids) + 10:
-            raise ValueError(f"state has {state.shape[0]} entries, {3 * len(ids) + 10} expected for {len(ids)} markers")
+        dims = self.lm_dims * len(ids) + 10
+        if state.shape[0] != dims:
+            raise ValueError(f"state has {state.shape[0]} entries, {dims} expected for {len(ids)} markers")
         cov = np.ascontiguousarray(cov, dtype=np.float64)
         if cov.shape != (state.shape[0], state.shape[0]):
             raise ValueError(f"cov must be {state.shape[0]} x {state.shape[0]}")
@@ -218,28 +240,39 @@ class EKFBatch:
         self.landmarks[b] = {k: i for i, k in enumerate(ids)}
         self.num_landmarks[b] = len(ids)
 
-    def load_filter(self, b, ekf) -> None:
-        """Member b from an ordinary ``EKF``: its state, covariance and landmark table.  The filter must be an ``EKF`` (not
-        ``EKF_Rotations``) with the batch's quaternion convention.  The member keeps its own noise constants (a sweep loads
-        one filter into members that differ in nothing else)."""
+    def _filter_class(self):
+        from .filters.ekf_with_rotations import EKF_Rotations
         from .filters.extended_kalman_filter import EKF
-        if not isinstance(ekf, EKF):
-            raise ValueError(f"a batch holds EKF filters, got {type(ekf).__name__}")
+        return EKF_Rotations if self.model == "ekf_rotations" else EKF
+
+    def load_filter(self, b, ekf) -> None:
+        """Member b from an ordinary filter of the batch's model (``EKF`` or ``EKF_Rotations``): its state, covariance and
+        landmark table, with the batch's quaternion convention.  The member keeps its own noise constants (a sweep loads
+        one filter into members that differ in nothing else)."""
+        cls = self._filter_class()
+        if not isinstance(ekf, cls):
+            raise ValueError(f"a batch of model {self.model!r} holds {cls.__name__} filters, got {type(ekf).__name__}")
         if ekf.backend.cfg.quat_mode != QUAT_MODES[self.quat_update]:
             raise ValueError(f"the filter's quaternion convention differs from the batch's ({self.quat_update!r})")
         ids = [k for k, _ in sorted(ekf.get_lm_estimates(), key=lambda kv: kv[1])]
         self.set_member(b, np.asarray(ekf.state, dtype=np.float64), ekf.uncertainty, ids)
 
     def to_filter(self, b):
-        """An ordinary ``EKF`` (f64 covariance) with member b's quaternion convention, noise constants, state, covariance and
-        landmark table; ``observe``, ``save_map`` and ``save_checkpoint`` work on it."""
-        from .filters.extended_kalman_filter import EKF
+        """An ordinary filter of the batch's model (``EKF`` or ``EKF_Rotations``, f64 covariance) with member b's quaternion
+        convention, noise constants, state, covariance and landmark table; ``observe`` (and for ``EKF`` ``save_map`` and
+        ``save_checkpoint``) work on it."""
         b = self._member(b)
         state, cov = self.get_state(b), self.get_cov(b)
         n = self.num_landmarks[b]
-        ekf = EKF(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
-                  quat_update=self.quat_update, device=str(self.device),
-                  noise=dict(zip(NOISE_KEYS, (float(v) for v in self.noise[b]))))
+        noise = dict(zip(NOISE_KEYS, (float(v) for v in self.noise[b])))
+        if self.model == "ekf_rotations":
+            from .filters.ekf_with_rotations import EKF_Rotations
+            ekf = EKF_Rotations(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
+                                device=str(self.device), noise=noise)
+        else:
+            from .filters.extended_kalman_filter import EKF
+            ekf = EKF(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
+                      quat_update=self.quat_update, device=str(self.device), noise=noise)
         ekf.backend.set_state_cov(state, cov)
         ekf.landmarks = dict(self.landmarks[b])
         ekf.num_landmarks = n

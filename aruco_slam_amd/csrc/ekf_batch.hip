@@ -1,199 +1,12 @@
-// Batch of independent EKF filters (ekf_batch_observe_logs, ekf_batch_api.hip): ONE workgroup owns ONE member for a window of its
-// log's frames.  Per stepped frame, the algebra of DESIGN section 2 with everything but P in LDS:
-//   first sightings (ekf_add_marker_xyz, the frame's pre-update camera), h and dh of every detection (ekf_measure),
-//   A = H (P+Q) [k, N], S = A[:,supp] H^T + R I (lower triangle), S = L L^T (left-looking, in LDS),
-//   W = L^-1 A and y = L^-1 (z - h) (y is column N of A), dx = W^T y and the injection (ekf_quat_inject),
-//   P <- (P+Q) - W^T W in global memory.
-// P of a member is read and written by its own workgroup only: workgroup barriers are the only ordering.
-#include "ekf_kernels.h"
-#include "ekf_markers.h"
+// Batch of independent EKF filters (ekf_batch_observe_logs, ekf_batch_api.hip): the window kernel of the EKF model (the
+// frame body is ekf_batch_impl.h, shared with the EKF_Rotations kernel of ekf_batch_rot.hip).
+#include "ekf_batch_impl.h"
 
-// dynamic LDS, doubles: A/W [kmax][lda] | L [kmax][kmax] (strictly lower part used) | dinv [kmax] | J [kmax][13] | dx [lda],
-// then ints: first state column per detection [16] | failure flag
-extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda) {
-    return 8 * ((size_t)kmax * lda + (size_t)kmax * kmax + kmax + (size_t)kmax * EKF_JCOLS + lda) + 4 * (EKF_BATCH_MAX_VISIBLE + 4);
-}
+extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda) { return ekf_batch_lds_bytes_of<0>(kmax, lda); }
 
-__global__ __launch_bounds__(256) void ekf_batch_window_kernel(EkfBatchWindow a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-    const int64_t t_end = a.member_frames[b + 1];
-    const int64_t t0 = a.member_frames[b] + a.window_first;
-    const int64_t t1 = t0 + a.window_frames < t_end ? t0 + a.window_frames : t_end;
-    if (t0 >= t1) return;
-    const int kmax = a.kmax, lda = a.lda;
-    double* A = reinterpret_cast<double*>(smem);
-    double* L = A + (size_t)kmax * lda;
-    double* dinv = L + (size_t)kmax * kmax;
-    double* J = dinv + kmax;
-    double* dx = J + (size_t)kmax * EKF_JCOLS;
-    int* col0 = reinterpret_cast<int*>(dx + lda);
-    int* flag = col0 + EKF_BATCH_MAX_VISIBLE;
-
-    const int64_t ld = a.ld;
-    double* P = a.P + (size_t)b * ld * ld;
-    double* st = a.state + (size_t)b * ld;
-    const double* nzb = a.noise + 6 * b;      // ekf_config order: icu, ilu, r, q_cam, q_err, q_lm
-    const EkfNoise nz{nzb[3], nzb[4], nzb[5], nzb[2]};
-    const double lm_unc = nzb[1];
-    int n = a.nlm[b];
-    bool failed = a.status[b] != 0;
-    if (tid == 0) *flag = 0;
-
-    for (int64_t t = t0; t < t1; ++t) {
-        const int64_t d0 = a.frame_offsets[t];
-        const int m = (int)(a.frame_offsets[t + 1] - d0);
-        if (failed || m == 0) {      // not stepped: the row repeats the state (NaN once the member has failed)
-            if (a.traj && tid < 7) a.traj[7 * t + tid] = failed ? __builtin_nan("") : st[tid];
-            continue;
-        }
-        const int32_t* idx = a.lm_index + d0;
-        const double* pose = a.poses + 6 * d0;
-        // first sightings (validated on the host: numbered n0, n0+1, ... in order of first occurrence), all with the
-        // camera state the previous frame left, before predict
-        const int n0 = n;
-        for (int j = 0; j < m; ++j) n = max(n, idx[j] + 1);
-        if (tid < m && idx[tid] >= n0) {
-            bool first = true;
-            for (int e = 0; e < tid; ++e) first = first && idx[e] != idx[tid];
-            if (first) ekf_add_marker_xyz(P, ld, st, EKF_LM * n0 + EKF_CAM, idx[tid] - n0, pose + 6 * tid, nullptr, lm_unc);
-        }
-        const int N = EKF_LM * n + EKF_CAM, k = 3 * m;
-        __syncthreads();
-        // h, dh and z - h (column N of A)
-        if (tid < m) {
-            const int c0 = EKF_CAM + EKF_LM * idx[tid];
-            col0[tid] = c0;
-            double cam[EKF_CAM], lm[3], h[3], Jt[3][EKF_JCOLS];
-            for (int q = 0; q < EKF_CAM; ++q) cam[q] = st[q];
-            for (int q = 0; q < 3; ++q) lm[q] = st[c0 + q];
-            ekf_measure(cam, lm, h, Jt);
-            for (int r = 0; r < 3; ++r) {
-                for (int s = 0; s < EKF_JCOLS; ++s) J[(3 * tid + r) * EKF_JCOLS + s] = Jt[r][s];
-                A[(3 * tid + r) * lda + N] = pose[6 * tid + r] - h[r];
-            }
-        }
-        __syncthreads();
-        // A = H (P+Q): thread c owns column c; the support rows of P are read once per detection
-        for (int c = tid; c < N; c += nt) {
-            double pc[EKF_CAM];
-            for (int s = 0; s < EKF_CAM; ++s) pc[s] = P[(int64_t)s * ld + c] + (s == c ? ekf_qdiag(s, N, nz) : 0.0);
-            for (int j = 0; j < m; ++j) {
-                const int c0 = col0[j];
-                double pl[3];
-                for (int q = 0; q < 3; ++q) pl[q] = P[(int64_t)(c0 + q) * ld + c] + (c0 + q == c ? ekf_qdiag(c, N, nz) : 0.0);
-                for (int r = 0; r < 3; ++r) {
-                    const double* Jr = J + (3 * j + r) * EKF_JCOLS;
-                    double acc = 0.0;
-                    for (int s = 0; s < EKF_CAM; ++s) acc = fma(Jr[s], pc[s], acc);
-                    for (int q = 0; q < 3; ++q) acc = fma(Jr[EKF_CAM + q], pl[q], acc);
-                    A[(3 * j + r) * lda + c] = acc;
-                }
-            }
-        }
-        __syncthreads();
-        // S = A[:,supp] H^T + R I, lower triangle, into L
-        for (int e = tid; e < k * k; e += nt) {
-            const int r = e / k, rr = e - r * k;
-            if (rr > r) continue;
-            const double* Ar = A + r * lda;
-            const double* Jr = J + rr * EKF_JCOLS;
-            const int c0 = col0[rr / 3];
-            double acc = 0.0;
-            for (int s = 0; s < EKF_CAM; ++s) acc = fma(Ar[s], Jr[s], acc);
-            for (int q = 0; q < 3; ++q) acc = fma(Ar[c0 + q], Jr[EKF_CAM + q], acc);
-            L[r * kmax + rr] = acc + (r == rr ? nz.r_unc : 0.0);
-        }
-        __syncthreads();
-        // S = L L^T, left-looking, one column per step: every thread of the column recomputes the pivot with the same
-        // operations (same bits), so the pivot needs no extra barrier; S_jj stays in place, 1 / L_jj goes to dinv
-        for (int j = 0; j < k; ++j) {
-            if (tid >= j && tid < k) {
-                const double* Lj = L + j * kmax;
-                const double* Li = L + tid * kmax;
-                double djj = Lj[j], v = Li[j];
-                for (int l = 0; l < j; ++l) {
-                    djj = fma(-Lj[l], Lj[l], djj);
-                    v = fma(-Li[l], Lj[l], v);
-                }
-                if (!(djj > 0.0) || !isfinite(djj)) {
-                    if (tid == j) *flag = 1;
-                } else if (tid == j) {
-                    dinv[j] = 1.0 / sqrt(djj);
-                } else {
-                    L[tid * kmax + j] = v / sqrt(djj);
-                }
-            }
-            __syncthreads();
-            if (*flag) break;
-        }
-        if (*flag) {      // the member stops here: the update of this frame changes neither state nor P
-            failed = true;
-            if (tid == 0) a.status[b] = EKF_BATCH_ST_NUMERIC;
-            if (a.traj && tid < 7) a.traj[7 * t + tid] = __builtin_nan("");
-            continue;
-        }
-        // W = L^-1 A and y = L^-1 (z - h): thread c substitutes column c (c = N: the residual) in place
-        for (int c = tid; c <= N; c += nt) {
-            for (int i = 0; i < k; ++i) {
-                const double* Li = L + i * kmax;
-                double v = A[i * lda + c];
-                for (int l = 0; l < i; ++l) v = fma(-Li[l], A[l * lda + c], v);
-                A[i * lda + c] = v * dinv[i];
-            }
-        }
-        __syncthreads();
-        // dx = W^T y
-        for (int c = tid; c < N; c += nt) {
-            double acc = 0.0;
-            for (int i = 0; i < k; ++i) acc = fma(A[i * lda + c], A[i * lda + N], acc);
-            dx[c] = acc;
-        }
-        __syncthreads();
-        // injection (extended_kalman_filter.py:133-152): dx[3:7] dropped, every landmark moves, error state reset
-        if (tid == 0) {
-            double q[4] = {st[3], st[4], st[5], st[6]};
-            const double err[3] = {dx[7], dx[8], dx[9]};
-            ekf_quat_inject(q, err, a.quat_mode);
-            for (int r = 0; r < 4; ++r) st[3 + r] = q[r];
-            for (int r = 7; r < 10; ++r) st[r] = 0.0;
-        }
-        for (int c = tid; c < N; c += nt)
-            if (c < 3 || c >= EKF_CAM) st[c] += dx[c];
-        // P <- (P+Q) - W^T W: thread c owns column c; entry (i,c) and (c,i) run the same l-ascending fma chain (the two
-        // factors of each fma swap places, which does not change its result), so P stays bitwise symmetric.  The next row
-        // block of the column is loaded before the fma chain of this one: its loads overlap the chain instead of each
-        // block's read-modify-write of P waiting for its own load
-        for (int c = tid; c < N; c += nt) {
-            double pv[4], pn[4];
-            for (int u = 0; u < 4; ++u) pv[u] = u < N ? P[(int64_t)u * ld + c] : 0.0;
-            for (int i0 = 0; i0 < N; i0 += 4) {
-                for (int u = 0; u < 4; ++u) pn[u] = i0 + 4 + u < N ? P[(int64_t)(i0 + 4 + u) * ld + c] : 0.0;
-                double acc[4] = {0.0, 0.0, 0.0, 0.0};
-                for (int l = 0; l < k; ++l) {
-                    const double* Wl = A + l * lda;
-                    const double w = Wl[c];
-                    for (int u = 0; u < 4; ++u) acc[u] = fma(Wl[i0 + u], w, acc[u]);
-                }
-                for (int u = 0; u < 4 && i0 + u < N; ++u) {
-                    const int i = i0 + u;
-                    P[(int64_t)i * ld + c] = (pv[u] + (i == c ? ekf_qdiag(c, N, nz) : 0.0)) - acc[u];
-                }
-                for (int u = 0; u < 4; ++u) pv[u] = pn[u];
-            }
-        }
-        __syncthreads();
-        if (a.traj && tid < 7) a.traj[7 * t + tid] = st[tid];
-    }
-    if (tid == 0) a.nlm[b] = n;
-}
+__global__ __launch_bounds__(256) void ekf_batch_window_kernel(EkfBatchWindow a) { ekf_batch_window<0>(a); }
 
 void ekf_launch_batch_window(const EkfBatchWindow& a, int members, hipStream_t s) {
     static bool once = false;
-    if (!once) {   // > 64 KB of dynamic LDS needs the opt-in
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ekf_batch_window_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        once = true;
-    }
-    hipLaunchKernelGGL(ekf_batch_window_kernel, dim3(members), dim3(256), ekf_batch_lds_bytes(a.kmax, a.lda), s, a);
+    ekf_batch_launch<0>(ekf_batch_window_kernel, once, a, members, s);
 }

@@ -1,5 +1,5 @@
-// C ABI of the batch of independent filters (ekf_batch_*, see include/ekf_slam_hip.h; kernel: ekf_batch.hip, one workgroup
-// per member).  Host side only: argument checking, workspace carving, launch sequencing.
+// C ABI of the batch of independent filters (ekf_batch_*, see include/ekf_slam_hip.h; kernels: ekf_batch.hip (EKF) and
+// ekf_batch_rot.hip (EKF_Rotations), one workgroup per member).  Host side only: argument checking, workspace carving, launch sequencing.
 #include <cmath>
 #include <cstring>
 
@@ -26,7 +26,11 @@ namespace {
 
 constexpr int kBatchWindow = 64;   // frames per member and launch: every dispatch stays short
 
-int64_t batch_ld(const ekf_config& c) { return round_up(EKF_LM * (int64_t)c.max_landmarks + EKF_CAM, 32); }
+// landmark dims and measurement rows per detection of the batch's model
+int batch_lmd(const ekf_config& c) { return c.model == EKF_MODEL_ROTATIONS ? 10 : EKF_LM; }
+int batch_rd(const ekf_config& c) { return c.model == EKF_MODEL_ROTATIONS ? 7 : 3; }
+
+int64_t batch_ld(const ekf_config& c) { return round_up(batch_lmd(c) * (int64_t)c.max_landmarks + EKF_CAM, 32); }
 
 // workspace: [noise [B][6] | status [B] | landmark counts [B]]
 struct BatchLayout {
@@ -55,7 +59,18 @@ BatchLogLayout batch_log_layout(int64_t D, int64_t F, int32_t B) {
 int check_batch_config(const ekf_config* c, int32_t members) {
     if (!c) return fail(EKF_ERR_INVALID, "config is NULL");
     if (members < 1) return fail(EKF_ERR_INVALID, "a batch needs at least one member");
-    if (c->model != EKF_MODEL_EKF) return fail(EKF_ERR_INVALID, "batches exist for EKF_MODEL_EKF only");
+    if (c->model == EKF_MODEL_ROTATIONS) {
+        if (c->cov_dtype != EKF_COV_F64)
+            return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batches keep an f64 covariance (cov_dtype EKF_COV_F64)");
+        if (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_ROT_MAX_LANDMARKS)
+            return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batch max_landmarks must be in 1..24");
+        if (c->max_visible < 1 || c->max_visible > EKF_BATCH_ROT_MAX_VISIBLE)
+            return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batch max_visible must be in 1..8");
+        if (c->quat_mode != EKF_QUAT_SCALAR_FIRST)
+            return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batch quat_mode must be EKF_QUAT_SCALAR_FIRST");
+        return EKF_OK;
+    }
+    if (c->model != EKF_MODEL_EKF) return fail(EKF_ERR_INVALID, "batches exist for EKF_MODEL_EKF and EKF_MODEL_ROTATIONS only");
     if (c->cov_dtype != EKF_COV_F64) return fail(EKF_ERR_INVALID, "batches keep an f64 covariance (EKF_COV_F64)");
     if (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_MAX_LANDMARKS)
         return fail(EKF_ERR_INVALID, "batch max_landmarks must be in 1..82");
@@ -211,7 +226,7 @@ int ekf_batch_reset(ekf_batch* b, int32_t member, const double* initial_poses) {
     return batch_put_member_words(b, lo, hi);
 }
 
-// (state [3 n + 10], P [3 n + 10, 3 n + 10]) of one member from the host; P is symmetrised ((P + P^T) / 2) on upload.
+// (state [lmd n + 10], P [lmd n + 10, lmd n + 10]) of one member (lmd = 3: EKF, 10: EKF_Rotations) from the host; P is symmetrised ((P + P^T) / 2) on upload.
 // The member's status is cleared.
 int ekf_batch_set_member(ekf_batch* b, int32_t member, const double* state, int32_t num_landmarks, const double* cov) {
     int rc = batch_ready(b);
@@ -220,7 +235,7 @@ int ekf_batch_set_member(ekf_batch* b, int32_t member, const double* state, int3
     if (!state || !cov || num_landmarks < 0) return fail(EKF_ERR_INVALID, "bad member state");
     if (num_landmarks > b->cfg.max_landmarks) return fail(EKF_ERR_CAPACITY, "more landmarks than max_landmarks");
     const int64_t ld = b->ld;
-    const int dims = EKF_LM * num_landmarks + EKF_CAM;
+    const int dims = batch_lmd(b->cfg) * num_landmarks + EKF_CAM;
     std::vector<double> st((size_t)ld, 0.0), p((size_t)ld * ld, 0.0);
     std::memcpy(st.data(), state, (size_t)dims * 8);
     for (int i = 0; i < dims; ++i)
@@ -233,13 +248,13 @@ int ekf_batch_set_member(ekf_batch* b, int32_t member, const double* state, int3
     return batch_put_member_words(b, member, member + 1);
 }
 
-// state[0:count] and, if cov is not NULL, P [dims, dims] with dims = 3 n + 10 of one member.  Synchronises.
+// state[0:count] and, if cov is not NULL, P [dims, dims] with dims = lmd n + 10 of one member.  Synchronises.
 int ekf_batch_get_member(ekf_batch* b, int32_t member, double* state, int32_t count, double* cov, int32_t dims) {
     int rc = batch_ready(b);
     if (rc) return rc;
     if ((rc = batch_member(b, member))) return rc;
     if ((rc = batch_refresh(b))) return rc;
-    const int n = EKF_LM * b->nlm[member] + EKF_CAM;
+    const int n = batch_lmd(b->cfg) * b->nlm[member] + EKF_CAM;
     if (count < 0 || count > n || (count > 0 && !state)) return fail(EKF_ERR_INVALID, "bad state request");
     if (cov && dims != n) return fail(EKF_ERR_INVALID, "dims must equal the member's state dimension");
     const int64_t ld = b->ld;
@@ -327,12 +342,17 @@ int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t*
     a.poses = poses_dev;
     a.traj = trajectory_dev;
     a.quat_mode = b->cfg.quat_mode;
-    a.kmax = std::max(3, 3 * widest);
-    a.lda = (int32_t)round_up(EKF_LM * n_max + EKF_CAM + 1, 4);
+    const int rd = batch_rd(b->cfg);
+    a.kmax = std::max(rd, rd * widest);
+    a.lda = (int32_t)round_up(batch_lmd(b->cfg) * n_max + EKF_CAM + 1, 4);
     a.window_frames = kBatchWindow;
+    const bool rot = b->cfg.model == EKF_MODEL_ROTATIONS;
     for (int64_t w = 0; w < frames_max; w += kBatchWindow) {
         a.window_first = (int32_t)w;
-        ekf_launch_batch_window(a, B, b->stream);
+        if (rot)
+            ekf_launch_batch_rot_window(a, B, b->stream);
+        else
+            ekf_launch_batch_window(a, B, b->stream);
         HIP_TRY(hipGetLastError());
     }
     return EKF_OK;

@@ -110,6 +110,21 @@ __device__ inline void ekf_quat_inject(double q[4], const double err[3], int mod
 }
 
 
+// EKF_Rotations injection of one 10-dim block (ekf_with_rotations.py:146-177): multiplicative scalar-first quaternion update
+// from the block's error state dx[7:10], additive on xyz, the additive quaternion components dx[3:7] dropped.  camera: the
+// camera block, whose error state is reset (:157); a landmark's error state is never written.  Shared by the single-filter
+// injection kernel (ekf_small_kernels.hip) and the batch (ekf_batch_impl.h).
+__device__ inline void ekf_inject_rot_block(double* st, const double* dx, bool camera) {
+    double q[4] = {st[3], st[4], st[5], st[6]};
+    const double err[3] = {dx[7], dx[8], dx[9]};
+    ekf_quat_inject(q, err, 1);
+    const double x0 = st[0] + dx[0], x1 = st[1] + dx[1], x2 = st[2] + dx[2];
+    st[0] = x0; st[1] = x1; st[2] = x2;
+    for (int e = 0; e < 4; ++e) st[3 + e] = q[e];
+    if (camera)
+        for (int e = 0; e < 3; ++e) st[7 + e] = 0.0;
+}
+
 // EKF_Rotations measurement: h = [R(q_c)^-1 (l - c) ; q_c^-1 (x) q_l] and its 7 x 20 Jacobian in the
 // column order [c(3) qc(4) ec(3) | l(3) ql(4) el(3)] (ekf_with_rotations.py:363-422), at ec = el = 0
 // (the camera error state is reset every update, the landmarks' error states are never written).

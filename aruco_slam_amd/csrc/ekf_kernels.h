@@ -187,10 +187,13 @@ void ekf_launch_log_fill_rows(double* traj_dev, const int32_t* pairs, int32_t co
 template <typename T>
 void ekf_launch_cov_diag(const void* cov, int64_t ld, double* out_dev, int32_t count, hipStream_t s);
 
-// Batch of independent EKF filters (ekf_batch.hip): one workgroup per member, frames [member_frames[b] + window_first,
-// + window_frames) of its log.  Everything is validated on the host (indices, first-sighting order, widths, capacity).
-#define EKF_BATCH_MAX_LANDMARKS 82   // N = 3 n + 10 <= 256: one column per thread of the 256-thread workgroup
-#define EKF_BATCH_MAX_VISIBLE 16     // k = 3 m <= 48 rows
+// Batch of independent filters (ekf_batch.hip: EKF, ekf_batch_rot.hip: EKF_Rotations; frame body ekf_batch_impl.h): one
+// workgroup per member, frames [member_frames[b] + window_first, + window_frames) of its log.  Everything is validated on
+// the host (indices, first-sighting order, widths, capacity).
+#define EKF_BATCH_MAX_LANDMARKS 82   // EKF: N = 3 n + 10 <= 256: one column per thread of the 256-thread workgroup
+#define EKF_BATCH_MAX_VISIBLE 16     // EKF: k = 3 m <= 48 rows
+#define EKF_BATCH_ROT_MAX_LANDMARKS 24   // EKF_Rotations: N = 10 n + 10 <= 256
+#define EKF_BATCH_ROT_MAX_VISIBLE 8      // EKF_Rotations: k = 7 m <= 56 rows
 #define EKF_BATCH_ST_NUMERIC (-5)    // per-member status after a failed pivot (= EKF_ERR_NUMERIC)
 struct EkfBatchWindow {
     double* P;                      // [B][ld][ld] f64
@@ -202,14 +205,17 @@ struct EkfBatchWindow {
     const int32_t* lm_index;        // [D]
     const int64_t* frame_offsets;   // [Ftot + 1] detection offsets, frame after frame, member after member
     const int64_t* member_frames;   // [B + 1] frame offsets per member
-    const double* poses;            // [D][6] [tvec | rvec]; z = pose[0:3]
+    const double* poses;            // [D][6] [tvec | rvec]; z = pose[0:3] (EKF), ekf_pose_z (EKF_Rotations)
     double* traj;                   // [Ftot][7] or null
-    int32_t quat_mode;
+    int32_t quat_mode;              // (EKF; EKF_Rotations is scalar-first)
     int32_t window_first, window_frames;
     int32_t kmax, lda;              // LDS layout: rows of A / W, row length of A / W (> N; column N holds the residual)
 };
-extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);   // dynamic LDS of one launch (C linkage: the tests read it)
+// dynamic LDS of one launch (C linkage: the tests read them)
+extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);
+extern "C" size_t ekf_batch_rot_lds_bytes(int kmax, int lda);
 void ekf_launch_batch_window(const EkfBatchWindow& a, int members, hipStream_t s);
+void ekf_launch_batch_rot_window(const EkfBatchWindow& a, int members, hipStream_t s);
 
 // Detection -> pose front end (ekf_pose_ippe.hip): pinhole camera + Brown-Conrady distortion k1 k2 p1 p2 k3 k4 k5 k6
 struct EkfCamera {

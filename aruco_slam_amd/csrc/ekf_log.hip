@@ -5,28 +5,12 @@
 #include "ekf_kernels.h"
 #include "ekf_markers.h"
 
-// z of detection d: EKF pose[0:3]; EKF_Rotations [pose[0:3] | quaternion of from_euler("xyz", pose[3:6]), scalar first]
-// (ekf_with_rotations.py:216-224).  The quaternion is the host's euler_xyz_to_quat (filters/ekf_with_rotations.py) operation
-// for operation -- half angles, q = qz (qy qx) -- with contraction off, so only sin / cos can differ in the last place.
+// z of detection d (ekf_pose_z, ekf_markers.h)
 __global__ __launch_bounds__(256) void ekf_log_prepare_kernel(const double* __restrict__ poses, int64_t count, int rd,
                                                               double* __restrict__ z) {
-#pragma clang fp contract(off)
     const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= count) return;
-    const double* p = poses + 6 * d;
-    double* zd = z + rd * d;
-    zd[0] = p[0];
-    zd[1] = p[1];
-    zd[2] = p[2];
-    if (rd == 7) {
-        const double ax = 0.5 * p[3], ay = 0.5 * p[4], az = 0.5 * p[5];
-        const double cx = cos(ax), sx = sin(ax), cy = cos(ay), sy = sin(ay), cz = cos(az), sz = sin(az);
-        const double w1 = cy * cx, x1 = cy * sx, y1 = sy * cx, z1 = -(sy * sx);
-        zd[3] = cz * w1 - sz * z1;
-        zd[4] = cz * x1 - sz * y1;
-        zd[5] = cz * y1 + sz * x1;
-        zd[6] = cz * z1 + sz * w1;
-    }
+    ekf_pose_z(poses + 6 * d, rd, z + rd * d);
 }
 
 void ekf_launch_log_prepare(const double* poses_dev, int64_t count, int rd, double* z_dev, hipStream_t s) {

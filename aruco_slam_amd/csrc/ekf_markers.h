@@ -4,6 +4,26 @@
 #pragma once
 #include "ekf_device.h"
 
+// z of one detection from its logged pose [tvec | rvec] (rd = 3: pose[0:3]; rd = 7: [pose[0:3] | quaternion of
+// from_euler("xyz", pose[3:6]), scalar first], ekf_with_rotations.py:216-224).  The quaternion is the host's euler_xyz_to_quat
+// (filters/ekf_with_rotations.py) operation for operation -- half angles, q = qz (qy qx) -- with contraction off, so only
+// sin / cos can differ in the last place.  Shared by the log replay (ekf_log.hip) and the batch (ekf_batch_impl.h).
+__device__ inline void ekf_pose_z(const double* p, int rd, double* zd) {
+#pragma clang fp contract(off)
+    zd[0] = p[0];
+    zd[1] = p[1];
+    zd[2] = p[2];
+    if (rd == 7) {
+        const double ax = 0.5 * p[3], ay = 0.5 * p[4], az = 0.5 * p[5];
+        const double cx = cos(ax), sx = sin(ax), cy = cos(ay), sy = sin(ay), cz = cos(az), sz = sin(az);
+        const double w1 = cy * cx, x1 = cy * sx, y1 = sy * cx, z1 = -(sy * sx);
+        zd[3] = cz * w1 - sz * z1;
+        zd[4] = cz * x1 - sz * y1;
+        zd[5] = cz * y1 + sz * x1;
+        zd[6] = cz * z1 + sz * w1;
+    }
+}
+
 // EKF: t_ml = R(q)^-1 p + c with the camera state in `state`; landmark j goes to column dims + 3 j.
 // p = pose[0:3] of the detection; unc = its 3 variances or null (default_unc on the diagonal).
 template <typename T>
@@ -24,6 +44,16 @@ __device__ inline void ekf_add_marker_xyz(T* P, int64_t ld, double* state, int d
         const double var = unc ? unc[d] : default_unc;
         P[(int64_t)(c0 + d) * ld + c0 + d] = (T)var;
     }
+}
+
+// SciPy's from_matrix branch for the largest diagonal entry I of mm (x y z w); compile-time indices keep mm and qx in
+// registers wherever ekf_add_marker_pose is inlined
+template <int I> __device__ inline void ekf_quat_branch(const double (&mm)[3][3], double tr, double qx[4]) {
+    constexpr int J = (I + 1) % 3, K = (I + 2) % 3;
+    qx[I] = 1.0 - tr + 2.0 * mm[I][I];
+    qx[J] = mm[J][I] + mm[I][J];
+    qx[K] = mm[K][I] + mm[I][K];
+    qx[3] = mm[K][J] - mm[J][K];
 }
 
 // EKF_Rotations: pose = [tvec | rvec], rvec read as extrinsic xyz Euler angles (:307-310); q_ml = from_matrix(R(q)^-1 R_cl)
@@ -55,12 +85,12 @@ __device__ inline void ekf_add_marker_pose(T* P, int64_t ld, double* state, int 
     for (int e = 1; e < 4; ++e)
         if (dec[e] > dec[ch]) ch = e;
     double qx[4];
-    if (ch != 3) {
-        const int i2 = ch, j2 = (ch + 1) % 3, k2 = (ch + 2) % 3;
-        qx[i2] = 1.0 - tr + 2.0 * mm[i2][i2];
-        qx[j2] = mm[j2][i2] + mm[i2][j2];
-        qx[k2] = mm[k2][i2] + mm[i2][k2];
-        qx[3] = mm[k2][j2] - mm[j2][k2];
+    if (ch == 0) {
+        ekf_quat_branch<0>(mm, tr, qx);
+    } else if (ch == 1) {
+        ekf_quat_branch<1>(mm, tr, qx);
+    } else if (ch == 2) {
+        ekf_quat_branch<2>(mm, tr, qx);
     } else {
         qx[0] = mm[2][1] - mm[1][2];
         qx[1] = mm[0][2] - mm[2][0];

@@ -345,20 +345,9 @@ __global__ void ekf_inject_rot_kernel(EkfFrame fr, int n_lm) {
     if (i > n_lm) return;
     const int c0 = (i == 0) ? 0 : EKF_CAM + 10 * (i - 1);
     double* st = fr.state + c0;
-    const double* dx = fr.dxvec + c0;
-    double q[4] = {st[3], st[4], st[5], st[6]};
-    const double err[3] = {dx[7], dx[8], dx[9]};
-    ekf_quat_inject(q, err, 1);
-    const double x0 = st[0] + dx[0], x1 = st[1] + dx[1], x2 = st[2] + dx[2];
-    st[0] = x0; st[1] = x1; st[2] = x2;
-    for (int e = 0; e < 4; ++e) st[3 + e] = q[e];
-    if (i == 0) {
-        for (int e = 0; e < 3; ++e) st[7 + e] = 0.0;         // :157
-        if (fr.traj_row) {
-            fr.traj_row[0] = x0; fr.traj_row[1] = x1; fr.traj_row[2] = x2;
-            for (int e = 0; e < 4; ++e) fr.traj_row[3 + e] = q[e];
-        }
-    }
+    ekf_inject_rot_block(st, fr.dxvec + c0, i == 0);
+    if (i == 0 && fr.traj_row)
+        for (int e = 0; e < 7; ++e) fr.traj_row[e] = st[e];
 }
 void ekf_launch_inject_rot(const EkfFrame& fr, int n_lm, hipStream_t s) {
     hipLaunchKernelGGL(ekf_inject_rot_kernel, dim3((n_lm + 1 + 127) / 128), dim3(128), 0, s, fr, n_lm);

@@ -45,7 +45,10 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
 
     def __init__(self, initial_camera_pose, *, max_landmarks: int | None = None, max_visible: int | None = None,
                  cov_dtype: str = "float64", cov_kernel: str = "auto", device: str = "cuda:0",
-                 lookahead: bool | None = None, fused: bool = True) -> None:
+                 lookahead: bool | None = None, fused: bool = True, noise: dict | None = None) -> None:
+        """``noise``: values that replace the module's noise constants, keyed by the ``ekf_config`` field names
+        (``initial_camera_uncertainty``, ``initial_landmark_uncertainty``, ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``);
+        None keeps the reference's constants."""
         super().__init__(initial_camera_pose, None)
         self._initial_pose = np.array(initial_camera_pose)
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -56,13 +59,17 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
             max_landmarks = dictionary_size(None)    # (the reference's EKF_Rotations takes no aruco_dict: DICT_5X5_50)
         if max_visible is None:
             max_visible = min(max_landmarks, 27)     # 7 rows per detection, k <= 192: the fused front kernel (grows to 50)
+        constants = {"initial_camera_uncertainty": INITIAL_CAMERA_UNCERTAINTY,
+                     "initial_landmark_uncertainty": INITIAL_LANDMARK_UNCERTAINTY,
+                     "r_uncertainty": R_UNCERTAINTY, "q_cam": Q_UNCERTAINTY_CAM,
+                     "q_err": Q_ERROR_UNCERTAINTY_CAM, "q_lm": Q_UNCERTAINTY_LM_XYZ}
+        unknown = set(noise or {}) - set(constants)
+        if unknown:
+            raise ValueError(f"unknown noise constants {sorted(unknown)}; known: {sorted(constants)}")
+        constants.update(noise or {})
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype, quat_mode="scalar_first",
                            cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
-                           model="ekf_rotations",
-                           noise={"initial_camera_uncertainty": INITIAL_CAMERA_UNCERTAINTY,
-                                  "initial_landmark_uncertainty": INITIAL_LANDMARK_UNCERTAINTY,
-                                  "r_uncertainty": R_UNCERTAINTY, "q_cam": Q_UNCERTAINTY_CAM,
-                                  "q_err": Q_ERROR_UNCERTAINTY_CAM, "q_lm": Q_UNCERTAINTY_LM_XYZ})
+                           model="ekf_rotations", noise=constants)
         self._hip.reset(self._initial_pose.astype(np.float64))
 
     @property

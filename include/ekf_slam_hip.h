@@ -267,8 +267,13 @@ int ekf_estimate_poses(const double *corners, int32_t count, double marker_size,
  * runs).  Every member is BaseFilter.process_detections with should_filter=True over its own log, exactly as
  * ekf_observe_log does it; one workgroup owns one member for a window of frames, members never wait for each other.
  *
- * cfg: model must be EKF_MODEL_EKF, cov_dtype EKF_COV_F64, max_landmarks <= 82, max_visible <= 16 (N = 3 n + 10 <= 256,
- * k = 3 m <= 48); flags and cov_kernel are ignored; the noise constants of cfg are every member's defaults.
+ * cfg, by model (every member of a batch has the batch's model):
+ *   EKF_MODEL_EKF:       cov_dtype EKF_COV_F64, max_landmarks <= 82, max_visible <= 16 (N = 3 n + 10 <= 256, k = 3 m <= 48),
+ *                        either quat_mode;
+ *   EKF_MODEL_ROTATIONS: cov_dtype EKF_COV_F64, max_landmarks <= 24, max_visible <= 8 (N = 10 n + 10 <= 256, k = 7 m <= 56),
+ *                        quat_mode EKF_QUAT_SCALAR_FIRST (EKF_Rotations' convention);
+ * anything else is EKF_ERR_INVALID.  flags and cov_kernel are ignored; the noise constants of cfg are every member's defaults.
+ * Below, lmd = 3 (EKF) or 10 (EKF_Rotations) landmark dims: a member's state is [lmd n + 10].
  * Memory is the caller's, as for single filters: cov [B, ld, ld] f64, state [B, ld] f64 (capacity padding exactly zero),
  * a workspace of workspace_bytes, all 256-byte aligned.  ekf_batch_bind_buffers resets every member to the identity pose.
  * A batch never grows. */
@@ -284,9 +289,9 @@ int ekf_batch_set_noise(ekf_batch *b, const double *noise);
 /* state = initial pose, P = initial_camera_uncertainty I_10, no landmarks, status cleared.
  * member = -1: every member, initial_poses [B,10]; member >= 0: that member, initial_poses [10]. */
 int ekf_batch_reset(ekf_batch *b, int32_t member, const double *initial_poses);
-/* one member from host f64: state [3 n + 10], cov [3 n + 10, 3 n + 10] (symmetrised on upload); clears its status */
+/* one member from host f64: state [lmd n + 10], cov [lmd n + 10, lmd n + 10] (symmetrised on upload); clears its status */
 int ekf_batch_set_member(ekf_batch *b, int32_t member, const double *state, int32_t num_landmarks, const double *cov);
-/* state[0:count] and, unless cov is NULL, the covariance [dims, dims] (dims = 3 n + 10) of one member; synchronises */
+/* state[0:count] and, unless cov is NULL, the covariance [dims, dims] (dims = lmd n + 10) of one member; synchronises */
 int ekf_batch_get_member(ekf_batch *b, int32_t member, double *state, int32_t count, double *cov /* or NULL */, int32_t dims);
 int ekf_batch_num_landmarks(const ekf_batch *b, int32_t *out /* [B] */);
 /* out [B]: 0, or EKF_ERR_NUMERIC for a member whose innovation covariance had a non-positive or non-finite pivot: that

@@ -1,7 +1,8 @@
 """Aggregate throughput of EKFBatch (aruco_slam_amd/batch.py) against one filter's process_detection_log.
 
-Seeded synthetic.ragged_log logs, one seed per member: n = 50 landmarks (DICT_5X5_50), m ~ U[1, 10] per frame, a bootstrap
-segment that first-sights every landmark, then 500 steady frames.  For every batch size: one warm-up call of the same shape,
+Seeded synthetic.ragged_log logs, one seed per member, a bootstrap segment that first-sights every landmark, then 500 steady
+frames.  --model ekf (EKF): n = 50 landmarks (DICT_5X5_50), m ~ U[1, 10] per frame.  --model ekf_rotations (EKF_Rotations):
+n = 24 (the batch's largest map), m ~ U[1, 8], marker orientations with rvec_sigma = 0.05.  For every batch size: one warm-up call of the same shape,
 then one timed call (host clock around the call, which ends in a synchronise).  The rate is stepped steady frames of all
 members over wall time; the bootstrap frames run in the warm-up call, so the timed call is the steady segment alone.
 Beside it, the single-filter rate of process_detection_log on member 0's steady segment (same timing rule).  One JSON line
@@ -37,29 +38,35 @@ def split(log, t):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--members", type=int, nargs="*", default=[1, 16, 64, 256, 1024])
-    ap.add_argument("--landmarks", type=int, default=50)
+    ap.add_argument("--model", choices=("ekf", "ekf_rotations"), default="ekf")
+    ap.add_argument("--landmarks", type=int, default=None, help="default: 50 (ekf), 24 (ekf_rotations)")
     ap.add_argument("--steady", type=int, default=500)
     ap.add_argument("--out", default=str(REPO / "profiles" / "batch" / "batch_bench.jsonl"))
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.batch import EKFBatch
+    from aruco_slam_amd.filters.ekf_with_rotations import EKF_Rotations
     from aruco_slam_amd.filters.extended_kalman_filter import EKF
     from aruco_slam_amd.synthetic import ragged_log
     if not torch.cuda.is_available():
         raise SystemExit("batch_bench needs a HIP device")
-    n = args.landmarks
+    rot = args.model == "ekf_rotations"
+    n = args.landmarks or (24 if rot else 50)
+    m_hi = 8 if rot else 10
+    visible = 8 if rot else 16
     logs = [split(lg, lg["bootstrap_frames"]) for lg in
-            (ragged_log(n, (1, 10), args.steady, seed=s) for s in range(max(args.members)))]
+            (ragged_log(n, (1, m_hi), args.steady, seed=s, rvec_sigma=0.05 if rot else 0.0)
+             for s in range(max(args.members)))]
     lines = []
     # one filter: bootstrap segment as warm-up, then the steady segment timed
-    flt = EKF(INIT, max_landmarks=n, max_visible=16, cov_dtype="float64")
+    flt = (EKF_Rotations if rot else EKF)(INIT, max_landmarks=n, max_visible=visible, cov_dtype="float64")
     boot, steady = logs[0]
     flt.process_detection_log(boot["ids"], boot["poses"], boot["offsets"], boot["has_detections"])
     t0 = time.perf_counter()
     flt.process_detection_log(steady["ids"], steady["poses"], steady["offsets"], steady["has_detections"])
     single = args.steady / (time.perf_counter() - t0)
     for B in args.members:
-        batch = EKFBatch(B, INIT, max_landmarks=n, max_visible=16)
+        batch = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model)
         batch.process_detection_logs([lg[0] for lg in logs[:B]])           # warm-up: bootstrap frames, same launch shape
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -67,7 +74,8 @@ def main():
         wall = time.perf_counter() - t0
         assert batch.status() == [0] * B
         rate = B * args.steady / wall
-        line = {"tool": "batch_bench", "members": B, "n": n, "m": [1, 10], "steady_frames": args.steady,
+        line = {"tool": "batch_bench", **({"model": args.model} if rot else {}), "members": B, "n": n, "m": [1, m_hi],
+                "steady_frames": args.steady,
                 "wall_s": round(wall, 6), "aggregate_frames_per_s": round(rate, 1),
                 "single_filter_frames_per_s": round(single, 1), "ratio": round(rate / single, 2)}
         print(json.dumps(line), flush=True)

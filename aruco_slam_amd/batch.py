@@ -7,7 +7,9 @@ own log, with its own initial pose, noise constants and marker-id -> landmark-in
 a batch fills the GPU where a single filter of this size leaves it almost idle.  All members share the model, the quaternion
 convention, an f64 covariance and the capacity: ``model="ekf"`` (``EKF``) holds ``max_landmarks`` <= 82 and ``max_visible``
 <= 16, ``model="ekf_rotations"`` (``EKF_Rotations``, scalar-first quaternions only) ``max_landmarks`` <= 24 and
-``max_visible`` <= 8.  A batch never grows; there is no CPU fallback.
+``max_visible`` <= 8.  With ``large_maps`` (``EKF_FLAG_BATCH_LARGE_MAPS``, kernel ``csrc/ekf_batch_large.hip``) the maps
+grow to dictionary size: ``max_landmarks`` <= 338 (``EKF``) or <= 101 (``EKF_Rotations``), same ``max_visible``.  A batch
+never grows; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -16,13 +18,25 @@ import ctypes as C
 import numpy as np
 
 from .filters.base_filter import plan_detection_log
-from .hip_backend import EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError, _dptr, load_library
+from .hip_backend import (EKF_FLAG_BATCH_LARGE_MAPS, EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError,
+                          _dptr, load_library)
 
 NOISE_KEYS = ("initial_camera_uncertainty", "initial_landmark_uncertainty", "r_uncertainty", "q_cam", "q_err", "q_lm")
 EKF_ERR_NUMERIC = -5
 QUAT_MODES = {"as_written": EKF_QUAT_AS_WRITTEN, "scalar_first": EKF_QUAT_SCALAR_FIRST}
 MODELS = {"ekf": 0, "ekf_rotations": 1}
 LM_DIMS = {"ekf": 3, "ekf_rotations": 10}      # landmark dims: a member's state is [LM_DIMS n + 10]
+# max_landmarks of the one-column kernels (N <= 256) and of the large-map kernel (N <= 1024)
+COLUMN_MAX_LANDMARKS = {"ekf": 82, "ekf_rotations": 24}
+LARGE_MAX_LANDMARKS = {"ekf": 338, "ekf_rotations": 101}
+
+
+def use_large_maps(model: str, max_landmarks: int, large_maps: bool | None = None) -> bool:
+    """Whether a batch sets ``EKF_FLAG_BATCH_LARGE_MAPS``: ``None`` only when ``max_landmarks`` exceeds the one-column
+    kernel's limit of the model, ``True`` / ``False`` always / never (then a larger map raises as the library rules)."""
+    if large_maps is None:
+        return int(max_landmarks) > COLUMN_MAX_LANDMARKS[model]
+    return bool(large_maps)
 
 
 def _iptr(a: np.ndarray):
@@ -37,10 +51,12 @@ class EKFBatch:
     """``members`` filters of ``model`` (``"ekf"``: ``EKF``, ``"ekf_rotations"``: ``EKF_Rotations``).
     ``initial_camera_pose``: [10] for all or [B, 10]; ``quat_update``: None for the model's convention (``"as_written"`` for
     ``EKF``; ``EKF_Rotations`` has only ``"scalar_first"``); ``noise``: dict of scalars or length-B arrays keyed by
-    ``NOISE_KEYS`` (missing keys: the model's constants)."""
+    ``NOISE_KEYS`` (missing keys: the model's constants); ``large_maps``: see ``use_large_maps`` (the choice is kept in
+    ``self.large_maps``)."""
 
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
-                 quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf") -> None:
+                 quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf",
+                 large_maps: bool | None = None) -> None:
         import torch
         if model not in MODELS:
             raise ValueError(f"model must be one of {sorted(MODELS)}, got {model!r}")
@@ -67,6 +83,9 @@ class EKFBatch:
         cfg.max_landmarks, cfg.max_visible = int(max_landmarks), int(max_visible)
         cfg.quat_mode = QUAT_MODES[quat_update]
         cfg.model = MODELS[model]
+        self.large_maps = use_large_maps(model, max_landmarks, large_maps)
+        if self.large_maps:
+            cfg.flags |= EKF_FLAG_BATCH_LARGE_MAPS
         if model == "ekf_rotations":
             from .filters import ekf_with_rotations as rot
             for key, val in zip(NOISE_KEYS, (rot.INITIAL_CAMERA_UNCERTAINTY, rot.INITIAL_LANDMARK_UNCERTAINTY,

@@ -1,5 +1,5 @@
 // C ABI of the batch of independent filters (ekf_batch_*, see include/ekf_slam_hip.h; kernels: ekf_batch.hip (EKF) and
-// ekf_batch_rot.hip (EKF_Rotations), one workgroup per member).  Host side only: argument checking, workspace carving, launch sequencing.
+// ekf_batch_rot.hip (EKF_Rotations), or with EKF_FLAG_BATCH_LARGE_MAPS ekf_batch_large.hip (both), one workgroup per member).  Host side only: argument checking, workspace carving, launch sequencing.
 #include <cmath>
 #include <cstring>
 
@@ -32,16 +32,22 @@ int batch_rd(const ekf_config& c) { return c.model == EKF_MODEL_ROTATIONS ? 7 : 
 
 int64_t batch_ld(const ekf_config& c) { return round_up(batch_lmd(c) * (int64_t)c.max_landmarks + EKF_CAM, 32); }
 
-// workspace: [noise [B][6] | status [B] | landmark counts [B]]
+bool batch_large(const ekf_config& c) { return (c.flags & EKF_FLAG_BATCH_LARGE_MAPS) != 0; }
+
+// A / W of one member of a large-maps batch: [rd max_visible][ld] doubles
+int64_t batch_w_stride(const ekf_config& c) { return (int64_t)batch_rd(c) * c.max_visible * batch_ld(c); }
+
+// workspace: [noise [B][6] | status [B] | landmark counts [B] | large maps only: A / W [B][w_stride]]
 struct BatchLayout {
-    size_t status, nlm, total;
+    size_t status, nlm, w, total;
 };
 
-BatchLayout batch_layout(int32_t members) {
+BatchLayout batch_layout(const ekf_config& c, int32_t members) {
     Carve w;
     w.take((size_t)members * 6 * 8);
     const size_t status = w.take((size_t)members * 4), nlm = w.take((size_t)members * 4);
-    return {status, nlm, w.end};
+    const size_t wm = w.take(batch_large(c) ? (size_t)members * batch_w_stride(c) * 8 : 0);
+    return {status, nlm, wm, w.end};
 }
 
 // log workspace: [landmark indices [D] | frame offsets [Ftot+1] | member frame offsets [B+1]]
@@ -59,10 +65,14 @@ BatchLogLayout batch_log_layout(int64_t D, int64_t F, int32_t B) {
 int check_batch_config(const ekf_config* c, int32_t members) {
     if (!c) return fail(EKF_ERR_INVALID, "config is NULL");
     if (members < 1) return fail(EKF_ERR_INVALID, "a batch needs at least one member");
+    const bool large = batch_large(*c);
     if (c->model == EKF_MODEL_ROTATIONS) {
         if (c->cov_dtype != EKF_COV_F64)
             return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batches keep an f64 covariance (cov_dtype EKF_COV_F64)");
-        if (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_ROT_MAX_LANDMARKS)
+        if (large && (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_ROT_LARGE_MAX_LANDMARKS))
+            return fail(EKF_ERR_INVALID,
+                        "EKF_MODEL_ROTATIONS batch max_landmarks must be in 1..101 (EKF_FLAG_BATCH_LARGE_MAPS)");
+        if (!large && (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_ROT_MAX_LANDMARKS))
             return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batch max_landmarks must be in 1..24");
         if (c->max_visible < 1 || c->max_visible > EKF_BATCH_ROT_MAX_VISIBLE)
             return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batch max_visible must be in 1..8");
@@ -72,7 +82,9 @@ int check_batch_config(const ekf_config* c, int32_t members) {
     }
     if (c->model != EKF_MODEL_EKF) return fail(EKF_ERR_INVALID, "batches exist for EKF_MODEL_EKF and EKF_MODEL_ROTATIONS only");
     if (c->cov_dtype != EKF_COV_F64) return fail(EKF_ERR_INVALID, "batches keep an f64 covariance (EKF_COV_F64)");
-    if (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_MAX_LANDMARKS)
+    if (large && (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_LARGE_MAX_LANDMARKS))
+        return fail(EKF_ERR_INVALID, "batch max_landmarks must be in 1..338 (EKF_FLAG_BATCH_LARGE_MAPS)");
+    if (!large && (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_MAX_LANDMARKS))
         return fail(EKF_ERR_INVALID, "batch max_landmarks must be in 1..82");
     if (c->max_visible < 1 || c->max_visible > EKF_BATCH_MAX_VISIBLE)
         return fail(EKF_ERR_INVALID, "batch max_visible must be in 1..16");
@@ -102,7 +114,7 @@ int batch_member(const ekf_batch* b, int32_t member) {
 
 // status and landmark counts of every member back to the host (the stream is idle afterwards)
 int batch_refresh(ekf_batch* b) {
-    const BatchLayout L = batch_layout(b->members);
+    const BatchLayout L = batch_layout(b->cfg, b->members);
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipMemcpy(b->status.data(), b->ws + L.status, (size_t)b->members * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(b->nlm.data(), b->ws + L.nlm, (size_t)b->members * 4, hipMemcpyDeviceToHost));
@@ -111,7 +123,7 @@ int batch_refresh(ekf_batch* b) {
 
 // host copies of status and landmark count of members [lo, hi) -> device
 int batch_put_member_words(ekf_batch* b, int32_t lo, int32_t hi) {
-    const BatchLayout L = batch_layout(b->members);
+    const BatchLayout L = batch_layout(b->cfg, b->members);
     HIP_TRY(hipMemcpy(b->ws + L.status + 4 * (size_t)lo, b->status.data() + lo, (size_t)(hi - lo) * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->ws + L.nlm + 4 * (size_t)lo, b->nlm.data() + lo, (size_t)(hi - lo) * 4, hipMemcpyHostToDevice));
     return EKF_OK;
@@ -129,7 +141,7 @@ int ekf_batch_query_sizes(const ekf_config* cfg, int32_t members, int64_t* ld, s
     if (ld) *ld = l;
     if (cov_bytes) *cov_bytes = (size_t)members * l * l * 8;
     if (state_bytes) *state_bytes = (size_t)members * l * 8;
-    if (workspace_bytes) *workspace_bytes = batch_layout(members).total;
+    if (workspace_bytes) *workspace_bytes = batch_layout(*cfg, members).total;
     return EKF_OK;
 }
 
@@ -169,7 +181,7 @@ int ekf_batch_destroy(ekf_batch* b) {
 // Borrow the caller's buffers and reset every member to the identity pose (ekf_batch_reset to set the initial poses).
 int ekf_batch_bind_buffers(ekf_batch* b, double* cov_dev, int64_t ld, double* state_dev, void* ws_dev, size_t ws_bytes) {
     if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
-    int rc = check_device_buffers({cov_dev, state_dev, ws_dev}, ws_bytes, batch_layout(b->members).total,
+    int rc = check_device_buffers({cov_dev, state_dev, ws_dev}, ws_bytes, batch_layout(b->cfg, b->members).total,
                                   "ekf_batch_query_sizes");
     if (rc) return rc;
     if (ld != b->ld) return fail(EKF_ERR_INVALID, "ld must equal the value from ekf_batch_query_sizes");
@@ -328,7 +340,7 @@ int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t*
 
     // ---- windows: every member's frames [w, w + kBatchWindow) of its log per launch, state carried in HBM.  LDS is
     // sized for the widest frame and the largest map of the call (a layout choice only: the arithmetic is the same)
-    const BatchLayout L = batch_layout(B);
+    const BatchLayout L = batch_layout(b->cfg, B);
     EkfBatchWindow a{};
     a.P = b->cov;
     a.ld = b->ld;
@@ -347,9 +359,14 @@ int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t*
     a.lda = (int32_t)round_up(batch_lmd(b->cfg) * n_max + EKF_CAM + 1, 4);
     a.window_frames = kBatchWindow;
     const bool rot = b->cfg.model == EKF_MODEL_ROTATIONS;
+    // large maps: every call runs ekf_batch_large.hip, whatever the map size (A / W in the workspace)
+    EkfBatchLargeWindow g{a, reinterpret_cast<double*>(b->ws + L.w), batch_w_stride(b->cfg)};
     for (int64_t w = 0; w < frames_max; w += kBatchWindow) {
         a.window_first = (int32_t)w;
-        if (rot)
+        g.w.window_first = (int32_t)w;
+        if (batch_large(b->cfg))
+            ekf_launch_batch_large_window(rot ? 1 : 0, g, B, b->stream);
+        else if (rot)
             ekf_launch_batch_rot_window(a, B, b->stream);
         else
             ekf_launch_batch_window(a, B, b->stream);

@@ -216,6 +216,17 @@ extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);
 extern "C" size_t ekf_batch_rot_lds_bytes(int kmax, int lda);
 void ekf_launch_batch_window(const EkfBatchWindow& a, int members, hipStream_t s);
 void ekf_launch_batch_rot_window(const EkfBatchWindow& a, int members, hipStream_t s);
+// Dictionary-sized maps (ekf_batch_large.hip, EKF_FLAG_BATCH_LARGE_MAPS): N <= 1024, ld <= 1024; A / W of a member in the
+// batch workspace, [k][ld] at w_stride doubles per member (kmax and window fields of `w` as above, w.lda unused)
+#define EKF_BATCH_LARGE_MAX_LANDMARKS 338       // EKF: N = 3 n + 10 <= 1024
+#define EKF_BATCH_ROT_LARGE_MAX_LANDMARKS 101   // EKF_Rotations: N = 10 n + 10 <= 1020
+struct EkfBatchLargeWindow {
+    EkfBatchWindow w;
+    double* W;                      // [B][w_stride]
+    int64_t w_stride;
+};
+extern "C" size_t ekf_batch_large_lds_bytes(int model, int kmax);
+void ekf_launch_batch_large_window(int model, const EkfBatchLargeWindow& g, int members, hipStream_t s);
 
 // Detection -> pose front end (ekf_pose_ippe.hip): pinhole camera + Brown-Conrady distortion k1 k2 p1 p2 k3 k4 k5 k6
 struct EkfCamera {

@@ -50,6 +50,8 @@ enum { EKF_MODEL_EKF = 0, EKF_MODEL_ROTATIONS = 1 };
  * f32 only).  All of them give the same bits as the VALU reference kernel. */
 /* ekf_config.flags bit 3: more than 64 (EKF_MODEL_ROTATIONS: 50) detections per frame, up to 1024 */
 enum { EKF_FLAG_WIDE_FRAMES = 8 };
+/* ekf_config.flags bit 4, read by ekf_batch_* only: dictionary-sized maps in a batch (see there) */
+enum { EKF_FLAG_BATCH_LARGE_MAPS = 16 };
 enum { EKF_COVK_AUTO = 0, EKF_COVK_VALU = 1, EKF_COVK_MFMA = 2, EKF_COVK_MFMA_TILE = 3, EKF_COVK_MFMA_MACRO = 4 };
 
 enum {
@@ -85,7 +87,8 @@ typedef struct ekf_config {
                              * bit 3 (EKF_FLAG_WIDE_FRAMES): max_visible may be up to 1024 (see there); the workspace
                              * of such a configuration also holds an f64 copy of A = H (P+Q) that frames with more than
                              * 384 rows turn into W (ekf_query_sizes: + 8 kmax ld bytes).  Without it, sizes and
-                             * limits are as before. */
+                             * limits are as before.
+                             * bit 4 (EKF_FLAG_BATCH_LARGE_MAPS): batches only, see ekf_batch_query_sizes. */
     /* noise constants, defaults = extended_kalman_filter.py:21-27 */
     double initial_camera_uncertainty;   /* 0.1  */
     double initial_landmark_uncertainty; /* 0.7  */
@@ -272,7 +275,13 @@ int ekf_estimate_poses(const double *corners, int32_t count, double marker_size,
  *                        either quat_mode;
  *   EKF_MODEL_ROTATIONS: cov_dtype EKF_COV_F64, max_landmarks <= 24, max_visible <= 8 (N = 10 n + 10 <= 256, k = 7 m <= 56),
  *                        quat_mode EKF_QUAT_SCALAR_FIRST (EKF_Rotations' convention);
- * anything else is EKF_ERR_INVALID.  flags and cov_kernel are ignored; the noise constants of cfg are every member's defaults.
+ * anything else is EKF_ERR_INVALID.
+ * flags bit 4 (EKF_FLAG_BATCH_LARGE_MAPS): dictionary-sized maps, N <= 1024 and ld = round_up(N, 32) <= 1024:
+ *   EKF_MODEL_EKF max_landmarks <= 338, EKF_MODEL_ROTATIONS max_landmarks <= 101; max_visible and every other rule as
+ *   above.  Every call then runs the large-map kernel (A / W in HBM, LDS independent of the map), whatever the map size,
+ *   with the same arithmetic in the same order: where both kernels run, the results are the same bits.  The workspace
+ *   grows by members * rd * max_visible * ld * 8 bytes (rd = 3: EKF, 7: EKF_Rotations).
+ * The other flag bits and cov_kernel are ignored; the noise constants of cfg are every member's defaults.
  * Below, lmd = 3 (EKF) or 10 (EKF_Rotations) landmark dims: a member's state is [lmd n + 10].
  * Memory is the caller's, as for single filters: cov [B, ld, ld] f64, state [B, ld] f64 (capacity padding exactly zero),
  * a workspace of workspace_bytes, all 256-byte aligned.  ekf_batch_bind_buffers resets every member to the identity pose.

@@ -2,12 +2,15 @@
 
 Seeded synthetic.ragged_log logs, one seed per member, a bootstrap segment that first-sights every landmark, then 500 steady
 frames.  --model ekf (EKF): n = 50 landmarks (DICT_5X5_50), m ~ U[1, 10] per frame.  --model ekf_rotations (EKF_Rotations):
-n = 24 (the batch's largest map), m ~ U[1, 8], marker orientations with rvec_sigma = 0.05.  For every batch size: one warm-up call of the same shape,
+n = 24 (the batch's largest map), m ~ U[1, 8], marker orientations with rvec_sigma = 0.05.  --large-maps: the large-map
+kernel (EKF_FLAG_BATCH_LARGE_MAPS, csrc/ekf_batch_large.hip) with n = 250 (EKF, m ~ U[1, 10]) or n = 100 (EKF_Rotations,
+m ~ U[1, 8]) by default.  For every batch size: one warm-up call of the same shape,
 then one timed call (host clock around the call, which ends in a synchronise).  The rate is stepped steady frames of all
 members over wall time; the bootstrap frames run in the warm-up call, so the timed call is the steady segment alone.
 Beside it, the single-filter rate of process_detection_log on member 0's steady segment (same timing rule).  One JSON line
 per point, printed and appended to profiles/batch/batch_bench.jsonl (--out).
-Kernel times: a separate `rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --members 256` run.
+Kernel times: a separate `rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --members 256` run (the large-map
+ones in profiles/batch/rocprof_large_*.json).
 """
 from __future__ import annotations
 
@@ -39,7 +42,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--members", type=int, nargs="*", default=[1, 16, 64, 256, 1024])
     ap.add_argument("--model", choices=("ekf", "ekf_rotations"), default="ekf")
-    ap.add_argument("--landmarks", type=int, default=None, help="default: 50 (ekf), 24 (ekf_rotations)")
+    ap.add_argument("--landmarks", type=int, default=None,
+                    help="default: 50 (ekf), 24 (ekf_rotations); with --large-maps 250 (ekf), 100 (ekf_rotations)")
+    ap.add_argument("--large-maps", action="store_true", help="run the large-map kernel (EKFBatch(large_maps=True))")
     ap.add_argument("--steady", type=int, default=500)
     ap.add_argument("--out", default=str(REPO / "profiles" / "batch" / "batch_bench.jsonl"))
     args = ap.parse_args()
@@ -51,7 +56,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("batch_bench needs a HIP device")
     rot = args.model == "ekf_rotations"
-    n = args.landmarks or (24 if rot else 50)
+    n = args.landmarks or ((100 if rot else 250) if args.large_maps else (24 if rot else 50))
     m_hi = 8 if rot else 10
     visible = 8 if rot else 16
     logs = [split(lg, lg["bootstrap_frames"]) for lg in
@@ -66,7 +71,8 @@ def main():
     flt.process_detection_log(steady["ids"], steady["poses"], steady["offsets"], steady["has_detections"])
     single = args.steady / (time.perf_counter() - t0)
     for B in args.members:
-        batch = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model)
+        batch = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model,
+                         large_maps=True if args.large_maps else None)
         batch.process_detection_logs([lg[0] for lg in logs[:B]])           # warm-up: bootstrap frames, same launch shape
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -74,10 +80,14 @@ def main():
         wall = time.perf_counter() - t0
         assert batch.status() == [0] * B
         rate = B * args.steady / wall
-        line = {"tool": "batch_bench", **({"model": args.model} if rot else {}), "members": B, "n": n, "m": [1, m_hi],
+        line = {"tool": "batch_bench", **({"model": args.model} if rot else {}),
+                **({"large_maps": True} if args.large_maps else {}), "members": B, "n": n, "m": [1, m_hi],
                 "steady_frames": args.steady,
                 "wall_s": round(wall, 6), "aggregate_frames_per_s": round(rate, 1),
                 "single_filter_frames_per_s": round(single, 1), "ratio": round(rate / single, 2)}
+        if args.large_maps:     # every stepped frame reads and writes the member's N x N f64 covariance once
+            dims = (10 if rot else 3) * n + 10
+            line["p_stream_tb_per_s"] = round(rate * 2 * dims * dims * 8 / 1e12, 3)
         print(json.dumps(line), flush=True)
         lines.append(line)
         del batch

@@ -8,8 +8,11 @@ a batch fills the GPU where a single filter of this size leaves it almost idle. 
 convention, an f64 covariance and the capacity: ``model="ekf"`` (``EKF``) holds ``max_landmarks`` <= 82 and ``max_visible``
 <= 16, ``model="ekf_rotations"`` (``EKF_Rotations``, scalar-first quaternions only) ``max_landmarks`` <= 24 and
 ``max_visible`` <= 8.  With ``large_maps`` (``EKF_FLAG_BATCH_LARGE_MAPS``, kernel ``csrc/ekf_batch_large.hip``) the maps
-grow to dictionary size: ``max_landmarks`` <= 338 (``EKF``) or <= 101 (``EKF_Rotations``), same ``max_visible``.  A batch
-never grows; there is no CPU fallback.
+grow to dictionary size: ``max_landmarks`` <= 338 (``EKF``) or <= 101 (``EKF_Rotations``), same ``max_visible``.  With
+``wide_frames`` (``EKF_FLAG_BATCH_WIDE_FRAMES``, kernel ``csrc/ekf_batch_wide.hip``) a frame may hold as many detections as
+a default single filter takes: ``max_visible`` <= 64 (``EKF``) or <= 50 (``EKF_Rotations``), on the large-map limits of
+``max_landmarks``; a frame is factorised in blocks of 16 / 8 detections, and one of at most 16 / 8 detections gives the same
+bits as a batch without the flag.  A batch never grows; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from .filters.base_filter import plan_detection_log
-from .hip_backend import (EKF_FLAG_BATCH_LARGE_MAPS, EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError,
+from .hip_backend import (EKF_FLAG_BATCH_LARGE_MAPS, EKF_FLAG_BATCH_WIDE_FRAMES, EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError,
                           _dptr, load_library)
 
 NOISE_KEYS = ("initial_camera_uncertainty", "initial_landmark_uncertainty", "r_uncertainty", "q_cam", "q_err", "q_lm")
@@ -29,6 +32,9 @@ LM_DIMS = {"ekf": 3, "ekf_rotations": 10}      # landmark dims: a member's state
 # max_landmarks of the one-column kernels (N <= 256) and of the large-map kernel (N <= 1024)
 COLUMN_MAX_LANDMARKS = {"ekf": 82, "ekf_rotations": 24}
 LARGE_MAX_LANDMARKS = {"ekf": 338, "ekf_rotations": 101}
+# max_visible of the kernels without wide frames and of the wide-frame kernel (the single filter's default limits)
+COLUMN_MAX_VISIBLE = {"ekf": 16, "ekf_rotations": 8}
+WIDE_MAX_VISIBLE = {"ekf": 64, "ekf_rotations": 50}
 
 
 def use_large_maps(model: str, max_landmarks: int, large_maps: bool | None = None) -> bool:
@@ -37,6 +43,14 @@ def use_large_maps(model: str, max_landmarks: int, large_maps: bool | None = Non
     if large_maps is None:
         return int(max_landmarks) > COLUMN_MAX_LANDMARKS[model]
     return bool(large_maps)
+
+
+def use_wide_frames(model: str, max_visible: int, wide_frames: bool | None = None) -> bool:
+    """Whether a batch sets ``EKF_FLAG_BATCH_WIDE_FRAMES``: ``None`` only when ``max_visible`` exceeds the limit of the
+    model without the flag (16 / 8), ``True`` / ``False`` always / never (then a wider frame raises as the library rules)."""
+    if wide_frames is None:
+        return int(max_visible) > COLUMN_MAX_VISIBLE[model]
+    return bool(wide_frames)
 
 
 def _iptr(a: np.ndarray):
@@ -52,11 +66,11 @@ class EKFBatch:
     ``initial_camera_pose``: [10] for all or [B, 10]; ``quat_update``: None for the model's convention (``"as_written"`` for
     ``EKF``; ``EKF_Rotations`` has only ``"scalar_first"``); ``noise``: dict of scalars or length-B arrays keyed by
     ``NOISE_KEYS`` (missing keys: the model's constants); ``large_maps``: see ``use_large_maps`` (the choice is kept in
-    ``self.large_maps``)."""
+    ``self.large_maps``); ``wide_frames``: see ``use_wide_frames`` (kept in ``self.wide_frames``)."""
 
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
                  quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf",
-                 large_maps: bool | None = None) -> None:
+                 large_maps: bool | None = None, wide_frames: bool | None = None) -> None:
         import torch
         if model not in MODELS:
             raise ValueError(f"model must be one of {sorted(MODELS)}, got {model!r}")
@@ -86,6 +100,9 @@ class EKFBatch:
         self.large_maps = use_large_maps(model, max_landmarks, large_maps)
         if self.large_maps:
             cfg.flags |= EKF_FLAG_BATCH_LARGE_MAPS
+        self.wide_frames = use_wide_frames(model, max_visible, wide_frames)
+        if self.wide_frames:
+            cfg.flags |= EKF_FLAG_BATCH_WIDE_FRAMES
         if model == "ekf_rotations":
             from .filters import ekf_with_rotations as rot
             for key, val in zip(NOISE_KEYS, (rot.INITIAL_CAMERA_UNCERTAINTY, rot.INITIAL_LANDMARK_UNCERTAINTY,

@@ -1,5 +1,6 @@
 // C ABI of the batch of independent filters (ekf_batch_*, see include/ekf_slam_hip.h; kernels: ekf_batch.hip (EKF) and
-// ekf_batch_rot.hip (EKF_Rotations), or with EKF_FLAG_BATCH_LARGE_MAPS ekf_batch_large.hip (both), one workgroup per member).  Host side only: argument checking, workspace carving, launch sequencing.
+// ekf_batch_rot.hip (EKF_Rotations), with EKF_FLAG_BATCH_LARGE_MAPS ekf_batch_large.hip (both), with
+// EKF_FLAG_BATCH_WIDE_FRAMES ekf_batch_wide.hip (both); one workgroup per member).  Host side only: argument checking, workspace carving, launch sequencing.
 #include <cmath>
 #include <cstring>
 
@@ -33,11 +34,12 @@ int batch_rd(const ekf_config& c) { return c.model == EKF_MODEL_ROTATIONS ? 7 : 
 int64_t batch_ld(const ekf_config& c) { return round_up(batch_lmd(c) * (int64_t)c.max_landmarks + EKF_CAM, 32); }
 
 bool batch_large(const ekf_config& c) { return (c.flags & EKF_FLAG_BATCH_LARGE_MAPS) != 0; }
+bool batch_wide(const ekf_config& c) { return (c.flags & EKF_FLAG_BATCH_WIDE_FRAMES) != 0; }
 
-// A / W of one member of a large-maps batch: [rd max_visible][ld] doubles
+// A / W of one member of a large-maps or wide-frames batch: [rd max_visible][ld] doubles
 int64_t batch_w_stride(const ekf_config& c) { return (int64_t)batch_rd(c) * c.max_visible * batch_ld(c); }
 
-// workspace: [noise [B][6] | status [B] | landmark counts [B] | large maps only: A / W [B][w_stride]]
+// workspace: [noise [B][6] | status [B] | landmark counts [B] | large maps or wide frames only: A / W [B][w_stride]]
 struct BatchLayout {
     size_t status, nlm, w, total;
 };
@@ -46,7 +48,7 @@ BatchLayout batch_layout(const ekf_config& c, int32_t members) {
     Carve w;
     w.take((size_t)members * 6 * 8);
     const size_t status = w.take((size_t)members * 4), nlm = w.take((size_t)members * 4);
-    const size_t wm = w.take(batch_large(c) ? (size_t)members * batch_w_stride(c) * 8 : 0);
+    const size_t wm = w.take(batch_large(c) || batch_wide(c) ? (size_t)members * batch_w_stride(c) * 8 : 0);
     return {status, nlm, wm, w.end};
 }
 
@@ -65,16 +67,18 @@ BatchLogLayout batch_log_layout(int64_t D, int64_t F, int32_t B) {
 int check_batch_config(const ekf_config* c, int32_t members) {
     if (!c) return fail(EKF_ERR_INVALID, "config is NULL");
     if (members < 1) return fail(EKF_ERR_INVALID, "a batch needs at least one member");
-    const bool large = batch_large(*c);
+    const bool wide = batch_wide(*c), large = batch_large(*c) || wide;      // (wide frames take the large-map limits)
     if (c->model == EKF_MODEL_ROTATIONS) {
         if (c->cov_dtype != EKF_COV_F64)
             return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batches keep an f64 covariance (cov_dtype EKF_COV_F64)");
         if (large && (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_ROT_LARGE_MAX_LANDMARKS))
-            return fail(EKF_ERR_INVALID,
-                        "EKF_MODEL_ROTATIONS batch max_landmarks must be in 1..101 (EKF_FLAG_BATCH_LARGE_MAPS)");
+            return fail(EKF_ERR_INVALID, wide ? "EKF_MODEL_ROTATIONS batch max_landmarks must be in 1..101 (EKF_FLAG_BATCH_WIDE_FRAMES)"
+                                              : "EKF_MODEL_ROTATIONS batch max_landmarks must be in 1..101 (EKF_FLAG_BATCH_LARGE_MAPS)");
         if (!large && (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_ROT_MAX_LANDMARKS))
             return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batch max_landmarks must be in 1..24");
-        if (c->max_visible < 1 || c->max_visible > EKF_BATCH_ROT_MAX_VISIBLE)
+        if (wide && (c->max_visible < 1 || c->max_visible > EKF_BATCH_ROT_WIDE_MAX_VISIBLE))
+            return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batch max_visible must be in 1..50 (EKF_FLAG_BATCH_WIDE_FRAMES)");
+        if (!wide && (c->max_visible < 1 || c->max_visible > EKF_BATCH_ROT_MAX_VISIBLE))
             return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batch max_visible must be in 1..8");
         if (c->quat_mode != EKF_QUAT_SCALAR_FIRST)
             return fail(EKF_ERR_INVALID, "EKF_MODEL_ROTATIONS batch quat_mode must be EKF_QUAT_SCALAR_FIRST");
@@ -83,10 +87,13 @@ int check_batch_config(const ekf_config* c, int32_t members) {
     if (c->model != EKF_MODEL_EKF) return fail(EKF_ERR_INVALID, "batches exist for EKF_MODEL_EKF and EKF_MODEL_ROTATIONS only");
     if (c->cov_dtype != EKF_COV_F64) return fail(EKF_ERR_INVALID, "batches keep an f64 covariance (EKF_COV_F64)");
     if (large && (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_LARGE_MAX_LANDMARKS))
-        return fail(EKF_ERR_INVALID, "batch max_landmarks must be in 1..338 (EKF_FLAG_BATCH_LARGE_MAPS)");
+        return fail(EKF_ERR_INVALID, wide ? "batch max_landmarks must be in 1..338 (EKF_FLAG_BATCH_WIDE_FRAMES)"
+                                          : "batch max_landmarks must be in 1..338 (EKF_FLAG_BATCH_LARGE_MAPS)");
     if (!large && (c->max_landmarks < 1 || c->max_landmarks > EKF_BATCH_MAX_LANDMARKS))
         return fail(EKF_ERR_INVALID, "batch max_landmarks must be in 1..82");
-    if (c->max_visible < 1 || c->max_visible > EKF_BATCH_MAX_VISIBLE)
+    if (wide && (c->max_visible < 1 || c->max_visible > EKF_BATCH_WIDE_MAX_VISIBLE))
+        return fail(EKF_ERR_INVALID, "batch max_visible must be in 1..64 (EKF_FLAG_BATCH_WIDE_FRAMES)");
+    if (!wide && (c->max_visible < 1 || c->max_visible > EKF_BATCH_MAX_VISIBLE))
         return fail(EKF_ERR_INVALID, "batch max_visible must be in 1..16");
     if (c->quat_mode != EKF_QUAT_AS_WRITTEN && c->quat_mode != EKF_QUAT_SCALAR_FIRST)
         return fail(EKF_ERR_INVALID, "unknown quat_mode");
@@ -357,14 +364,21 @@ int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t*
     const int rd = batch_rd(b->cfg);
     a.kmax = std::max(rd, rd * widest);
     a.lda = (int32_t)round_up(batch_lmd(b->cfg) * n_max + EKF_CAM + 1, 4);
-    a.window_frames = kBatchWindow;
-    const bool rot = b->cfg.model == EKF_MODEL_ROTATIONS;
-    // large maps: every call runs ekf_batch_large.hip, whatever the map size (A / W in the workspace)
+    const bool rot = b->cfg.model == EKF_MODEL_ROTATIONS, wide = batch_wide(b->cfg);
+    // wide frames: a frame of m detections costs about ceil(m / block) sweeps of P (block = 16 / 8 detections), so the
+    // window shrinks with the call's widest frame and one launch stays about as long as a large-map window
+    const int block = rot ? EKF_BATCH_ROT_MAX_VISIBLE : EKF_BATCH_MAX_VISIBLE;
+    const int window = wide ? std::max(1, kBatchWindow / ((std::max(widest, 1) + block - 1) / block)) : kBatchWindow;
+    a.window_frames = window;
+    // large maps or wide frames: every call runs ekf_batch_large.hip or ekf_batch_wide.hip, whatever the map size and the
+    // frame widths (A / W in the workspace)
     EkfBatchLargeWindow g{a, reinterpret_cast<double*>(b->ws + L.w), batch_w_stride(b->cfg)};
-    for (int64_t w = 0; w < frames_max; w += kBatchWindow) {
+    for (int64_t w = 0; w < frames_max; w += window) {
         a.window_first = (int32_t)w;
         g.w.window_first = (int32_t)w;
-        if (batch_large(b->cfg))
+        if (wide)
+            ekf_launch_batch_wide_window(rot ? 1 : 0, g, B, b->stream);
+        else if (batch_large(b->cfg))
             ekf_launch_batch_large_window(rot ? 1 : 0, g, B, b->stream);
         else if (rot)
             ekf_launch_batch_rot_window(a, B, b->stream);

@@ -1,0 +1,366 @@
+// Batch of independent filters with wide frames (ekf_batch_observe_logs with EKF_FLAG_BATCH_WIDE_FRAMES, ekf_batch_api.hip):
+// the window kernels of both models for up to 64 (EKF, k = 3 m <= 192) or 50 (EKF_Rotations, k = 7 m <= 350) detections
+// per frame, on maps up to N = 1024 (EKF n <= 338, EKF_Rotations n <= 101).  ONE workgroup of 256 threads owns ONE member
+// for a window of its log's frames, as in ekf_batch_large.hip, and A / W [k][ld] lives in the member's slice of the batch
+// workspace (HBM).  A frame's detections are split, in log order, into blocks of MB = 16 (EKF) / 8 (EKF_Rotations)
+// detections, kb <= KW = 48 / 56 rows each.  For block j (rows r0 .. r0 + kb):
+//   h and dh of its detections (J of the block and y_j = z_j - h_j),
+//   A_j = H_j (P+Q),
+//   for every earlier block i: the off-diagonal factor block L_ji = H_j W_i^T (only the support columns of the stored W_i
+//     rows are read: W H^T = L^T - L^-1 R with L^-1 R lower triangular), then A_j <- A_j - L_ji W_i and y_j <- y_j - L_ji y_i,
+//     one l-ascending fma chain per entry over all earlier rows,
+//   S_jj = A_j[:,supp] H_j^T + R I, S_jj = L_jj L_jj^T, W_j = L_jj^-1 A_j and y_j <- L_jj^-1 y_j: the code of
+//     ekf_batch_large.hip on kb rows; W_j stays in the workspace.
+// Only then: dx = W^T y over all k rows, the injection, and P <- (P+Q) - W^T W as one read-modify-write sweep of P per block
+// (Q added by the first).  Entry (i,c) and (c,i) run the same operations in every sweep, so P stays bitwise symmetric and
+// its padding zero.  With one block (m <= MB) every operation is the one of ekf_batch_large.hip, in the same order: the
+// same bits.  Nothing touches P or the state before the last pivot of the frame has passed, so a failing pivot in any block
+// leaves them as the frame found them (its first sightings stay added, as everywhere).
+// LDS holds the block's L_jj (and, in turn, each L_ji), 1 / L_jj, J of the block, y [kmax] and the region R of
+// 256 x round_up(kb, 4) doubles of ekf_batch_large.hip: 123,920 bytes at the EKF's kmax = 192, 152,256 at EKF_Rotations'
+// kmax = 350.  The off-diagonal factor rows are not stored: each L_ji is formed from W rows in HBM when it is used.
+// P of a member is read and written by its own workgroup only: workgroup barriers are the only ordering.
+#include "ekf_batch_impl.h"
+
+namespace {
+
+constexpr int kWideThreads = 256;
+constexpr int kRowBlock = 8;        // rows of P per fma block
+
+template <int MODEL> struct WideCaps;
+template <> struct WideCaps<0> { static constexpr int MAX_VISIBLE = EKF_BATCH_WIDE_MAX_VISIBLE; };
+template <> struct WideCaps<1> { static constexpr int MAX_VISIBLE = EKF_BATCH_ROT_WIDE_MAX_VISIBLE; };
+
+// detections per block (the one-column kernels' max_visible) and rows of a full block (48 / 56, a multiple of 4)
+template <int MODEL> constexpr int wide_mb() { return EkfBatchCaps<MODEL>::MAX_VISIBLE; }
+template <int MODEL> constexpr int wide_kw() { return EkfModel<MODEL>::RD * wide_mb<MODEL>(); }
+static_assert(wide_kw<0>() % 4 == 0 && wide_kw<1>() % 4 == 0, "a full block pads to no extra rows");
+
+// dynamic LDS, doubles: R [256][round_up(kb, 4)] | L [kb][kb] | dinv [kb] | J [kb][JC] | y [kmax] with kb = min(kmax, KW),
+// then ints: first state column per detection [MAX_VISIBLE] | failure flag
+template <int MODEL> size_t wide_lds_bytes_of(int kmax) {
+    const size_t kb = (size_t)(kmax < wide_kw<MODEL>() ? kmax : wide_kw<MODEL>());
+    const size_t kbp = (kb + 3) / 4 * 4;
+    return 8 * ((size_t)kWideThreads * kbp + kb * kb + kb + kb * EkfModel<MODEL>::JC + (size_t)kmax) +
+           4 * (WideCaps<MODEL>::MAX_VISIBLE + 4);
+}
+
+typedef double ekf_d2 __attribute__((ext_vector_type(2)));
+
+template <int MODEL> __device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow& g) {
+    constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
+    constexpr int MB = wide_mb<MODEL>(), KW = wide_kw<MODEL>();
+    const EkfBatchWindow& a = g.w;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int b = blockIdx.x, tid = threadIdx.x, nt = kWideThreads;
+    const int64_t t_end = a.member_frames[b + 1];
+    const int64_t t0 = a.member_frames[b] + a.window_first;
+    const int64_t t1 = t0 + a.window_frames < t_end ? t0 + a.window_frames : t_end;
+    if (t0 >= t1) return;
+    const int kmax = a.kmax, kbmax = kmax < KW ? kmax : KW, kbpmax = (kbmax + 3) & ~3;
+    double* R = reinterpret_cast<double*>(smem);
+    double* L = R + (size_t)nt * kbpmax;
+    double* dinv = L + (size_t)kbmax * kbmax;
+    double* J = dinv + kbmax;
+    double* y = J + (size_t)kbmax * JC;
+    int* col0 = reinterpret_cast<int*>(y + kmax);
+    int* flag = col0 + WideCaps<MODEL>::MAX_VISIBLE;
+
+    const int64_t ld = a.ld;
+    double* P = a.P + (size_t)b * ld * ld;
+    double* st = a.state + (size_t)b * ld;
+    double* A = g.W + (size_t)b * g.w_stride;      // A, then W: [k][ld]
+    const double* nzb = a.noise + 6 * b;      // ekf_config order: icu, ilu, r, q_cam, q_err, q_lm
+    const EkfNoise nz{nzb[3], nzb[4], nzb[5], nzb[2]};
+    const double lm_unc = nzb[1];
+    int n = a.nlm[b];
+    bool failed = a.status[b] != 0;
+    if (tid == 0) *flag = 0;
+
+    for (int64_t t = t0; t < t1; ++t) {
+        const int64_t d0 = a.frame_offsets[t];
+        const int m = (int)(a.frame_offsets[t + 1] - d0);
+        if (failed || m == 0) {      // not stepped: the row repeats the state (NaN once the member has failed)
+            if (a.traj && tid < 7) a.traj[7 * t + tid] = failed ? __builtin_nan("") : st[tid];
+            continue;
+        }
+        const int32_t* idx = a.lm_index + d0;
+        const double* pose = a.poses + 6 * d0;
+        // first sightings, all with the camera state the previous frame left, before predict
+        const int n0 = n;
+        for (int j = 0; j < m; ++j) n = max(n, idx[j] + 1);
+        if (tid < m && idx[tid] >= n0) {
+            bool first = true;
+            for (int e = 0; e < tid; ++e) first = first && idx[e] != idx[tid];
+            if (first) {
+                if constexpr (MODEL == 0)
+                    ekf_add_marker_xyz(P, ld, st, EKF_LM * n0 + EKF_CAM, idx[tid] - n0, pose + 6 * tid, nullptr, lm_unc);
+                else
+                    ekf_add_marker_pose(P, ld, st, LMD * n0 + EKF_CAM, idx[tid] - n0, pose + 6 * tid, nullptr, lm_unc);
+            }
+        }
+        const int N = LMD * n + EKF_CAM, k = RD * m;
+        // ---- the factorisation, block after block of detections; W_j and y_j of every block that passed stay behind
+        for (int j0 = 0; j0 < m; j0 += MB) {
+            const int mb = min(MB, m - j0), kb = RD * mb, r0 = RD * j0;
+            double* Aj = A + (int64_t)r0 * ld;
+            __syncthreads();      // (first sightings, or the previous block's W_j and y_j, are in place)
+            // h, dh and y = z - h of the block's detections
+            if (tid < mb) {
+                const int d = j0 + tid;
+                const int c0 = EKF_CAM + LMD * idx[d];
+                col0[d] = c0;
+                double cam[EKF_CAM], lm[LMD], h[RD], z[RD];
+                for (int q = 0; q < EKF_CAM; ++q) cam[q] = st[q];
+                for (int q = 0; q < LMD; ++q) lm[q] = st[c0 + q];
+                if constexpr (MODEL == 0) {
+                    double Jt[3][EKF_JCOLS];
+                    ekf_measure(cam, lm, h, Jt);
+                    for (int r = 0; r < 3; ++r)
+                        for (int s = 0; s < EKF_JCOLS; ++s) J[(3 * tid + r) * EKF_JCOLS + s] = Jt[r][s];
+                    for (int r = 0; r < 3; ++r) z[r] = pose[6 * d + r];
+                } else {
+                    ekf_measure_rot(cam, lm, h, reinterpret_cast<double(*)[JC]>(J + (size_t)RD * tid * JC));
+                    ekf_pose_z(pose + 6 * d, RD, z);
+                }
+                for (int r = 0; r < RD; ++r) y[r0 + RD * tid + r] = z[r] - h[r];
+            }
+            __syncthreads();
+            // A_j = H_j (P+Q): thread c owns column c
+            for (int c = tid; c < N; c += nt) {
+                double pc[EKF_CAM];
+                for (int s = 0; s < EKF_CAM; ++s) pc[s] = P[(int64_t)s * ld + c] + (s == c ? ekf_qdiag(s, N, nz) : 0.0);
+                for (int jj = 0; jj < mb; ++jj) {
+                    const int c0 = col0[j0 + jj];
+                    double pl[LMD];
+                    for (int q = 0; q < LMD; ++q)
+                        pl[q] = P[(int64_t)(c0 + q) * ld + c] + (c0 + q == c ? ekf_qdiag(c, N, nz) : 0.0);
+                    for (int r = 0; r < RD; ++r) {
+                        const double* Jr = J + (RD * jj + r) * JC;
+                        double acc = 0.0;
+                        for (int s = 0; s < EKF_CAM; ++s) acc = fma(Jr[s], pc[s], acc);
+                        for (int q = 0; q < LMD; ++q) acc = fma(Jr[EKF_CAM + q], pl[q], acc);
+                        Aj[(int64_t)(RD * jj + r) * ld + c] = acc;
+                    }
+                }
+            }
+            // earlier blocks i (always full: KW rows at q0): L_ji = H_j W_i^T into L, then A_j -= L_ji W_i, y_j -= L_ji y_i
+            for (int q0 = 0; q0 < r0; q0 += KW) {
+                __syncthreads();      // (A_j, or the previous L_ji's use of L, is done)
+                for (int e = tid; e < kb * KW; e += nt) {
+                    const int r = e / KW, l = e - r * KW;
+                    const double* Wl = A + (int64_t)(q0 + l) * ld;
+                    const double* Jr = J + r * JC;
+                    const int c0 = col0[j0 + r / RD];
+                    double acc = 0.0;
+                    for (int s = 0; s < EKF_CAM; ++s) acc = fma(Wl[s], Jr[s], acc);
+                    for (int q = 0; q < LMD; ++q) acc = fma(Wl[c0 + q], Jr[EKF_CAM + q], acc);
+                    L[r * kbmax + l] = acc;
+                }
+                __syncthreads();
+                for (int c = tid; c <= N; c += nt) {
+                    double w[KW];
+#pragma unroll
+                    for (int l = 0; l < KW; ++l) w[l] = c == N ? y[q0 + l] : A[(int64_t)(q0 + l) * ld + c];
+                    for (int r = 0; r < kb; ++r) {
+                        const double* Lr = L + r * kbmax;
+                        double v = c == N ? y[r0 + r] : Aj[(int64_t)r * ld + c];
+#pragma unroll
+                        for (int l = 0; l < KW; ++l) v = fma(-Lr[l], w[l], v);
+                        if (c == N)
+                            y[r0 + r] = v;
+                        else
+                            Aj[(int64_t)r * ld + c] = v;
+                    }
+                }
+            }
+            __syncthreads();
+            // S_jj = A_j[:,supp] H_j^T + R I, lower triangle, into L
+            for (int e = tid; e < kb * kb; e += nt) {
+                const int r = e / kb, rr = e - r * kb;
+                if (rr > r) continue;
+                const double* Ar = Aj + (int64_t)r * ld;
+                const double* Jr = J + rr * JC;
+                const int c0 = col0[j0 + rr / RD];
+                double acc = 0.0;
+                for (int s = 0; s < EKF_CAM; ++s) acc = fma(Ar[s], Jr[s], acc);
+                for (int q = 0; q < LMD; ++q) acc = fma(Ar[c0 + q], Jr[EKF_CAM + q], acc);
+                L[r * kbmax + rr] = acc + (r == rr ? nz.r_unc : 0.0);
+            }
+            __syncthreads();
+            // S_jj = L_jj L_jj^T, left-looking, as ekf_batch_large.hip
+            for (int j = 0; j < kb; ++j) {
+                if (tid >= j && tid < kb) {
+                    const double* Lj = L + j * kbmax;
+                    const double* Li = L + tid * kbmax;
+                    double djj = Lj[j], v = Li[j];
+                    for (int l = 0; l < j; ++l) {
+                        djj = fma(-Lj[l], Lj[l], djj);
+                        v = fma(-Li[l], Lj[l], v);
+                    }
+                    if (!(djj > 0.0) || !isfinite(djj)) {
+                        if (tid == j) *flag = 1;
+                    } else if (tid == j) {
+                        dinv[j] = 1.0 / sqrt(djj);
+                    } else {
+                        L[tid * kbmax + j] = v / sqrt(djj);
+                    }
+                }
+                __syncthreads();
+                if (*flag) break;
+            }
+            if (*flag) break;
+            // W_j = L_jj^-1 A_j and y_j <- L_jj^-1 y_j: thread c substitutes column c (c = N: y_j) in its slice of R
+            for (int c = tid; c <= N; c += nt) {
+                double* v = c == N ? y + r0 : R + tid;
+                const int vs = c == N ? 1 : nt;
+                if (c < N)
+                    for (int i = 0; i < kb; ++i) v[i * vs] = Aj[(int64_t)i * ld + c];
+                for (int i = 0; i < kb; ++i) {
+                    const double* Li = L + i * kbmax;
+                    double s = v[i * vs];
+                    for (int l = 0; l < i; ++l) s = fma(-Li[l], v[l * vs], s);
+                    v[i * vs] = s * dinv[i];
+                }
+                if (c < N)
+                    for (int i = 0; i < kb; ++i) Aj[(int64_t)i * ld + c] = v[i * vs];
+            }
+        }
+        if (*flag) {      // the member stops here: the update of this frame changes neither state nor P
+            failed = true;
+            if (tid == 0) a.status[b] = EKF_BATCH_ST_NUMERIC;
+            if (a.traj && tid < 7) a.traj[7 * t + tid] = __builtin_nan("");
+            continue;
+        }
+        __syncthreads();
+        // dx = W^T y over all k rows (into R: every thread's slice is done)
+        double* dx = R;
+        for (int c = tid; c < N; c += nt) {
+            double acc = 0.0;
+            for (int i = 0; i < k; ++i) acc = fma(A[(int64_t)i * ld + c], y[i], acc);
+            dx[c] = acc;
+        }
+        __syncthreads();
+        if constexpr (MODEL == 0) {
+            // injection (extended_kalman_filter.py:133-152): dx[3:7] dropped, every landmark moves, error state reset
+            if (tid == 0) {
+                double q[4] = {st[3], st[4], st[5], st[6]};
+                const double err[3] = {dx[7], dx[8], dx[9]};
+                ekf_quat_inject(q, err, a.quat_mode);
+                for (int r = 0; r < 4; ++r) st[3 + r] = q[r];
+                for (int r = 7; r < 10; ++r) st[r] = 0.0;
+            }
+            for (int c = tid; c < N; c += nt)
+                if (c < 3 || c >= EKF_CAM) st[c] += dx[c];
+        } else {
+            // injection (ekf_with_rotations.py:146-177): thread 0 the camera block, thread i landmark i - 1 (n <= 101 < nt)
+            if (tid <= n) {
+                const int c0 = tid == 0 ? 0 : EKF_CAM + LMD * (tid - 1);
+                ekf_inject_rot_block(st + c0, dx + c0, tid == 0);
+            }
+        }
+        // P <- (P+Q) - W^T W, one sweep per block of rows: the covariance update of ekf_batch_large.hip on W_j (Q with the
+        // first).  Rows l in [kb, kbp) of the panel and of w are zero: fma(0, 0, acc) = acc (acc is never -0).
+        double* WT = R;      // [256 rows of the panel][kbp]
+        for (int j0 = 0; j0 < m; j0 += MB) {
+            const int kb = RD * min(MB, m - j0), kbp = (kb + 3) & ~3;
+            const double* Wj = A + (int64_t)RD * j0 * ld;
+            for (int cb = 0; cb < N; cb += nt) {
+                const int c = cb + tid;
+                const bool own = c < N;
+                const int cc = own ? c : N - 1;      // (loads stay inside the member's matrix)
+                const double qc = ekf_qdiag(cc, N, nz);
+                double w[KW];
+#pragma unroll
+                for (int l = 0; l < KW; ++l) {
+                    const double v = Wj[(int64_t)min(l, kb - 1) * ld + cc];
+                    w[l] = l < kb ? v : 0.0;
+                }
+                for (int i0 = 0; i0 < N; i0 += nt) {
+                    const int rows = min(nt, N - i0);
+                    __syncthreads();      // (the previous panel, or dx, is no longer read)
+                    for (int l = 0; l < kbp; ++l)
+                        WT[tid * kbp + l] = l < kb && tid < rows ? Wj[(int64_t)l * ld + i0 + tid] : 0.0;
+                    __syncthreads();
+                    double* Pc = P + (int64_t)i0 * ld + cc;
+                    auto load = [&](double (&p)[kRowBlock], int ib) {
+#pragma unroll
+                        for (int u = 0; u < kRowBlock; ++u) p[u] = ib + u < rows ? Pc[(int64_t)(ib + u) * ld] : 0.0;
+                    };
+                    auto step = [&](const double (&p)[kRowBlock], int ib) {
+                        if (ib >= rows) return;
+                        double acc[kRowBlock];
+#pragma unroll
+                        for (int u = 0; u < kRowBlock; ++u) acc[u] = 0.0;
+#pragma unroll
+                        for (int l0 = 0; l0 < KW; l0 += 4) {
+                            if (l0 < kbp) {
+#pragma unroll
+                                for (int u = 0; u < kRowBlock; ++u) {
+                                    const ekf_d2* Wr = reinterpret_cast<const ekf_d2*>(WT + (ib + u) * kbp + l0);
+                                    const ekf_d2 lo = Wr[0], hi = Wr[1];
+                                    acc[u] = fma(lo.x, w[l0], acc[u]);
+                                    acc[u] = fma(lo.y, w[l0 + 1], acc[u]);
+                                    acc[u] = fma(hi.x, w[l0 + 2], acc[u]);
+                                    acc[u] = fma(hi.y, w[l0 + 3], acc[u]);
+                                }
+                            }
+                        }
+                        if (!own) return;
+#pragma unroll
+                        for (int u = 0; u < kRowBlock; ++u) {
+                            const int i = i0 + ib + u;
+                            const double pq = j0 == 0 ? p[u] + (i == c ? qc : 0.0) : p[u];
+                            if (ib + u < rows) Pc[(int64_t)(ib + u) * ld] = pq - acc[u];
+                        }
+                    };
+                    // three blocks rotate through pa, pb, pc: two are in flight while the third is consumed
+                    double pa[kRowBlock], pb[kRowBlock], pc[kRowBlock];
+                    load(pa, 0);
+                    load(pb, kRowBlock);
+                    for (int ib = 0; ib < rows; ib += 3 * kRowBlock) {
+                        load(pc, ib + 2 * kRowBlock);
+                        step(pa, ib);
+                        load(pa, ib + 3 * kRowBlock);
+                        step(pb, ib + kRowBlock);
+                        load(pb, ib + 4 * kRowBlock);
+                        step(pc, ib + 2 * kRowBlock);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (a.traj && tid < 7) a.traj[7 * t + tid] = st[tid];
+    }
+    if (tid == 0) a.nlm[b] = n;
+}
+
+template <int MODEL>
+void wide_launch(void (*kernel)(EkfBatchLargeWindow), bool& once, const EkfBatchLargeWindow& g, int members,
+                 hipStream_t s) {
+    if (!once) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  160 * 1024);
+        once = true;
+    }
+    hipLaunchKernelGGL(kernel, dim3(members), dim3(kWideThreads), wide_lds_bytes_of<MODEL>(g.w.kmax), s, g);
+}
+
+}  // namespace
+
+extern "C" size_t ekf_batch_wide_lds_bytes(int model, int kmax) {
+    return model == 1 ? wide_lds_bytes_of<1>(kmax) : wide_lds_bytes_of<0>(kmax);
+}
+
+__global__ __launch_bounds__(256) void ekf_batch_wide_window_kernel(EkfBatchLargeWindow g) { ekf_batch_wide_window<0>(g); }
+__global__ __launch_bounds__(256) void ekf_batch_wide_rot_window_kernel(EkfBatchLargeWindow g) {
+    ekf_batch_wide_window<1>(g);
+}
+
+void ekf_launch_batch_wide_window(int model, const EkfBatchLargeWindow& g, int members, hipStream_t s) {
+    static bool once[2] = {false, false};
+    if (model == 1)
+        wide_launch<1>(ekf_batch_wide_rot_window_kernel, once[1], g, members, s);
+    else
+        wide_launch<0>(ekf_batch_wide_window_kernel, once[0], g, members, s);
+}

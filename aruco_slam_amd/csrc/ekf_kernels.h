@@ -227,6 +227,12 @@ struct EkfBatchLargeWindow {
 };
 extern "C" size_t ekf_batch_large_lds_bytes(int model, int kmax);
 void ekf_launch_batch_large_window(int model, const EkfBatchLargeWindow& g, int members, hipStream_t s);
+// Wide frames (ekf_batch_wide.hip, EKF_FLAG_BATCH_WIDE_FRAMES): up to 64 / 50 detections per frame on the large-map limits,
+// same EkfBatchLargeWindow (A / W [k][ld] of a member in the workspace, w_stride = rd max_visible ld)
+#define EKF_BATCH_WIDE_MAX_VISIBLE 64       // EKF: k = 3 m <= 192 rows
+#define EKF_BATCH_ROT_WIDE_MAX_VISIBLE 50   // EKF_Rotations: k = 7 m <= 350 rows
+extern "C" size_t ekf_batch_wide_lds_bytes(int model, int kmax);
+void ekf_launch_batch_wide_window(int model, const EkfBatchLargeWindow& g, int members, hipStream_t s);
 
 // Detection -> pose front end (ekf_pose_ippe.hip): pinhole camera + Brown-Conrady distortion k1 k2 p1 p2 k3 k4 k5 k6
 struct EkfCamera {

@@ -19,6 +19,7 @@ EKF_COV_F64, EKF_COV_F32 = 0, 1
 EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST = 0, 1
 EKF_FLAG_WIDE_FRAMES = 8       # ekf_config.flags bit 3: up to 1024 detections per frame
 EKF_FLAG_BATCH_LARGE_MAPS = 16  # ekf_config.flags bit 4 (batches): up to 1024 state dims per member
+EKF_FLAG_BATCH_WIDE_FRAMES = 32  # ekf_config.flags bit 5 (batches): up to 64 (EKF) / 50 (EKF_Rotations) detections per frame
 EKF_COVK_AUTO, EKF_COVK_VALU, EKF_COVK_MFMA, EKF_COVK_MFMA_TILE, EKF_COVK_MFMA_MACRO = 0, 1, 2, 3, 4
 
 # every symbol include/ekf_slam_hip.h declares

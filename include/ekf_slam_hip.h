@@ -52,6 +52,8 @@ enum { EKF_MODEL_EKF = 0, EKF_MODEL_ROTATIONS = 1 };
 enum { EKF_FLAG_WIDE_FRAMES = 8 };
 /* ekf_config.flags bit 4, read by ekf_batch_* only: dictionary-sized maps in a batch (see there) */
 enum { EKF_FLAG_BATCH_LARGE_MAPS = 16 };
+/* ekf_config.flags bit 5, read by ekf_batch_* only: up to 64 (EKF_MODEL_ROTATIONS: 50) detections per frame in a batch */
+enum { EKF_FLAG_BATCH_WIDE_FRAMES = 32 };
 enum { EKF_COVK_AUTO = 0, EKF_COVK_VALU = 1, EKF_COVK_MFMA = 2, EKF_COVK_MFMA_TILE = 3, EKF_COVK_MFMA_MACRO = 4 };
 
 enum {
@@ -88,7 +90,8 @@ typedef struct ekf_config {
                              * of such a configuration also holds an f64 copy of A = H (P+Q) that frames with more than
                              * 384 rows turn into W (ekf_query_sizes: + 8 kmax ld bytes).  Without it, sizes and
                              * limits are as before.
-                             * bit 4 (EKF_FLAG_BATCH_LARGE_MAPS): batches only, see ekf_batch_query_sizes. */
+                             * bit 4 (EKF_FLAG_BATCH_LARGE_MAPS), bit 5 (EKF_FLAG_BATCH_WIDE_FRAMES): batches only,
+                             * see ekf_batch_query_sizes. */
     /* noise constants, defaults = extended_kalman_filter.py:21-27 */
     double initial_camera_uncertainty;   /* 0.1  */
     double initial_landmark_uncertainty; /* 0.7  */
@@ -281,6 +284,15 @@ int ekf_estimate_poses(const double *corners, int32_t count, double marker_size,
  *   above.  Every call then runs the large-map kernel (A / W in HBM, LDS independent of the map), whatever the map size,
  *   with the same arithmetic in the same order: where both kernels run, the results are the same bits.  The workspace
  *   grows by members * rd * max_visible * ld * 8 bytes (rd = 3: EKF, 7: EKF_Rotations).
+ * flags bit 5 (EKF_FLAG_BATCH_WIDE_FRAMES): wide frames, max_visible <= 64 (EKF_MODEL_EKF, k = 3 m <= 192) or <= 50
+ *   (EKF_MODEL_ROTATIONS, k = 7 m <= 350), the single filter's limits without EKF_FLAG_WIDE_FRAMES; max_landmarks follows
+ *   the large-map limits above (338 / 101, N <= 1024, ld = round_up(N, 32)) whether bit 4 is set or not; every other rule
+ *   as above.  Every call then runs the wide-frame kernel, whatever the frame widths and the map size.  It keeps A / W
+ *   [k][ld] in HBM (the workspace, as bit 4: members * rd * max_visible * ld * 8 bytes more, with this max_visible) and
+ *   factorises a frame in blocks of 16 (EKF) / 8 (EKF_Rotations) detections in log order; the off-diagonal factor rows
+ *   L_ji = H_j W_i^T are formed from the W rows in HBM as they are needed, one block at a time in LDS, and not stored.
+ *   A frame of at most 16 / 8 detections is one block and gives the same bits as without the flag.  P and the state are
+ *   written only after every pivot of the frame has passed, so a failing pivot in any block leaves them as they were.
  * The other flag bits and cov_kernel are ignored; the noise constants of cfg are every member's defaults.
  * Below, lmd = 3 (EKF) or 10 (EKF_Rotations) landmark dims: a member's state is [lmd n + 10].
  * Memory is the caller's, as for single filters: cov [B, ld, ld] f64, state [B, ld] f64 (capacity padding exactly zero),
@@ -317,7 +329,9 @@ int ekf_batch_log_workspace_bytes(const ekf_batch *b, int64_t detections, int64_
  *   trajectory_dev [Ftot,7] DEVICE or NULL  state[0:7] after every frame
  * Everything is validated on the host before anything is enqueued (EKF_ERR_INVALID / EKF_ERR_CAPACITY; no member
  * changes).  Then, on the batch's stream, one copy of indices and offsets and one launch per window of 64 frames per
- * member.  Returns once the work is enqueued; the getters synchronise. */
+ * member (with EKF_FLAG_BATCH_WIDE_FRAMES: 64 / ceil(widest frame of the call / 16) frames, EKF_Rotations
+ * 64 / ceil(widest / 8); where windows split does not change any result).  Returns once the work is enqueued; the
+ * getters synchronise. */
 int ekf_batch_observe_logs(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets, const int64_t *member_frames,
                            const double *poses_dev, void *log_ws, size_t log_ws_bytes, double *trajectory_dev);
 

@@ -1,0 +1,156 @@
+"""Wide batch frames (``EKF_FLAG_BATCH_WIDE_FRAMES``) without a GPU: the limits the flag opens in the batch C ABI, the
+workspace it adds, the register / LDS budget of the wide-frame kernels and the Python choice of the flag."""
+import ctypes
+import re
+import subprocess
+import tempfile
+from pathlib import Path
+
+import pytest
+
+TOP = {0: (338, 64, 3), 1: (101, 50, 7)}      # model: (max_landmarks, max_visible, rows per detection) with the flag
+
+
+def _lib():
+    from aruco_slam_amd import _build, hip_backend
+    _build.build()
+    return hip_backend, hip_backend.load_library()
+
+
+def _config(hb, lib, model, wide=True, large=False, **fields):
+    cfg = hb.EkfConfig()
+    lib.ekf_default_config(ctypes.byref(cfg))
+    cfg.model, cfg.max_landmarks, cfg.max_visible = model, TOP[model][0], TOP[model][1]
+    if model == 1:
+        cfg.quat_mode = hb.EKF_QUAT_SCALAR_FIRST
+    if wide:
+        cfg.flags |= hb.EKF_FLAG_BATCH_WIDE_FRAMES
+    if large:
+        cfg.flags |= hb.EKF_FLAG_BATCH_LARGE_MAPS
+    for k, v in fields.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
+def _sizes(lib, cfg, members=4):
+    ld, cov, state, ws = ctypes.c_int64(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    rc = lib.ekf_batch_query_sizes(ctypes.byref(cfg), members, ctypes.byref(ld), ctypes.byref(cov), ctypes.byref(state),
+                                   ctypes.byref(ws))
+    return rc, ld.value, cov.value, state.value, ws.value
+
+
+def test_flag_value():
+    from aruco_slam_amd import hip_backend
+    assert hip_backend.EKF_FLAG_BATCH_WIDE_FRAMES == 32
+    header = (Path(__file__).resolve().parent.parent / "include" / "ekf_slam_hip.h").read_text()
+    assert re.search(r"EKF_FLAG_BATCH_WIDE_FRAMES = 32\b", header)
+
+
+@pytest.mark.parametrize("model", [0, 1])
+@pytest.mark.parametrize("large", [False, True])
+def test_wide_frame_limits_are_checked(model, large):
+    hb, lib = _lib()
+    rc, ld, cov, state, _ = _sizes(lib, _config(hb, lib, model, large=large))
+    assert rc == 0, lib.ekf_last_error_string()
+    assert ld == 1024 and cov == 4 * 1024 * 1024 * 8 and state == 4 * 1024 * 8
+    lm, vis, _ = TOP[model]
+    bad_cases = [("max_visible", vis + 1), ("max_visible", 0), ("max_landmarks", lm + 1), ("max_landmarks", 0),
+                 ("cov_dtype", hb.EKF_COV_F32)]
+    if model == 1:
+        bad_cases.append(("quat_mode", hb.EKF_QUAT_AS_WRITTEN))
+    else:
+        bad_cases.append(("quat_mode", 7))
+    for field, value in bad_cases:
+        bad = _config(hb, lib, model, large=large, **{field: value})
+        assert lib.ekf_batch_query_sizes(ctypes.byref(bad), 4, None, None, None, None) == -1, field
+        msg = lib.ekf_last_error_string()
+        assert field.encode() in msg or (field == "cov_dtype" and b"EKF_COV_F64" in msg), (field, msg)
+        if field == "max_visible":
+            assert b"EKF_FLAG_BATCH_WIDE_FRAMES" in msg and f"1..{vis}".encode() in msg, msg
+        handle = ctypes.c_void_p()
+        assert lib.ekf_batch_create(ctypes.byref(bad), 4, ctypes.byref(handle)) == -1 and not handle.value, field
+
+
+@pytest.mark.parametrize("model", [0, 1])
+def test_without_the_flag_nothing_changes(model):
+    hb, lib = _lib()
+    vis = 16 if model == 0 else 8
+    for large in (False, True):
+        bad = _config(hb, lib, model, wide=False, large=large, max_landmarks=10, max_visible=vis + 1)
+        assert lib.ekf_batch_query_sizes(ctypes.byref(bad), 4, None, None, None, None) == -1
+        msg = lib.ekf_last_error_string()
+        assert b"max_visible" in msg and f"1..{vis}".encode() in msg and b"WIDE" not in msg, msg
+    # sizes without the flag: as the one-column and the large-map kernels define them
+    for large, lm in ((False, 10), (True, 10), (True, TOP[model][0])):
+        rc, ld, cov, state, ws = _sizes(lib, _config(hb, lib, model, wide=False, large=large, max_landmarks=lm,
+                                                      max_visible=vis))
+        assert rc == 0
+        lmd, rd = (3, 3) if model == 0 else (10, 7)
+        assert ld == -(-(lmd * lm + 10) // 32) * 32
+        fixed = 4 * (6 * 8 + 4 + 4)
+        w = 4 * rd * vis * ld * 8 if large else 0
+        assert fixed + w <= ws < fixed + w + 3 * 256, (large, lm, ws)
+
+
+@pytest.mark.parametrize("model", [0, 1])
+def test_workspace_growth_follows_the_formula(model):
+    """members * rd * max_visible * ld * 8 bytes beyond the flagless workspace, with or without bit 4 beside bit 5."""
+    hb, lib = _lib()
+    _, top_vis, rd = TOP[model]
+    for lm in (1, 30, TOP[model][0]):
+        for vis in (1, 17, top_vis):
+            for members in (1, 5):
+                plain = _sizes(lib, _config(hb, lib, model, wide=False, large=True, max_landmarks=lm, max_visible=1),
+                               members)
+                assert plain[0] == 0
+                w_plain = members * rd * 1 * plain[1] * 8
+                for large in (False, True):
+                    wide = _sizes(lib, _config(hb, lib, model, large=large, max_landmarks=lm, max_visible=vis), members)
+                    assert wide[0] == 0 and wide[1:4] == plain[1:4]
+                    w = members * rd * vis * wide[1] * 8
+                    assert w <= wide[4] - (plain[4] - w_plain) < w + 256, (lm, vis, members, large)
+
+
+def test_wide_frame_kernels_use_no_scratch_and_fit_the_lds():
+    """ekf_batch_wide.hip compiled alone: two kernels, no scratch memory, no spills, no static LDS.  The dynamic LDS of
+    the largest kmax of each model fits the 160 KiB of a CU."""
+    from aruco_slam_amd import _build
+    assert "ekf_batch_wide.hip" in _build.SOURCES
+    with tempfile.TemporaryDirectory() as tmp:
+        out = Path(tmp) / "batch_wide.s"
+        subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
+                        str(_build.CSRC / "ekf_batch_wide.hip"), "-o", str(out)], check=True, capture_output=True)
+        text = out.read_text()
+    names = re.findall(r"\.name:\s+(\S*_kernel\S*)\n", text)
+    assert len(names) == 2, names
+    assert any("ekf_batch_wide_window_kernel" in n for n in names)
+    assert any("ekf_batch_wide_rot_window_kernel" in n for n in names)
+    for kernel in ("ekf_batch_wide_window_kernel", "ekf_batch_wide_rot_window_kernel"):
+        pat = r"\.name:\s+(\S*" + kernel + r"\S*)\n(?:.*\n)*?\s+\.{}:\s+(\d+)"
+        for field in ("private_segment_fixed_size", "vgpr_spill_count"):
+            found = re.findall(pat.format(field), text)
+            assert len(found) == 1 and int(found[0][1]) == 0, (kernel, field, found)
+    assert re.findall(r"\.group_segment_fixed_size:\s+(\d+)", text) == ["0", "0"]
+    _, lib = _lib()
+    lds = lib.ekf_batch_wide_lds_bytes
+    lds.argtypes, lds.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_size_t
+    for model, kw, jc in ((0, 48, 13), (1, 56, 20)):
+        _, vis, rd = TOP[model]
+        kmax = rd * vis
+        need = 8 * (256 * kw + kw * kw + kw * jc + kmax)       # at least the column / panel region, L, J and y
+        assert need < lds(model, kmax) <= 160 * 1024, (model, lds(model, kmax))
+        assert lds(model, kmax - rd) < lds(model, kmax)
+        # up to one block the budget is the large-map kernel's (same regions, y in place of nothing larger)
+        large = lib.ekf_batch_large_lds_bytes
+        large.argtypes, large.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_size_t
+        assert lds(model, kw) <= large(model, kw) + 4 * (vis - (16 if model == 0 else 8))
+
+
+@pytest.mark.parametrize("model,plain,top", [("ekf", 16, 64), ("ekf_rotations", 8, 50)])
+def test_python_flag_choice(model, plain, top):
+    from aruco_slam_amd import batch
+    assert batch.COLUMN_MAX_VISIBLE[model] == plain and batch.WIDE_MAX_VISIBLE[model] == top
+    for m, want_none in ((1, False), (plain, False), (plain + 1, True), (top, True)):
+        assert batch.use_wide_frames(model, m, None) is want_none, m
+        assert batch.use_wide_frames(model, m, True) is True, m
+        assert batch.use_wide_frames(model, m, False) is False, m

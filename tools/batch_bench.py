@@ -4,13 +4,14 @@ Seeded synthetic.ragged_log logs, one seed per member, a bootstrap segment that 
 frames.  --model ekf (EKF): n = 50 landmarks (DICT_5X5_50), m ~ U[1, 10] per frame.  --model ekf_rotations (EKF_Rotations):
 n = 24 (the batch's largest map), m ~ U[1, 8], marker orientations with rvec_sigma = 0.05.  --large-maps: the large-map
 kernel (EKF_FLAG_BATCH_LARGE_MAPS, csrc/ekf_batch_large.hip) with n = 250 (EKF, m ~ U[1, 10]) or n = 100 (EKF_Rotations,
-m ~ U[1, 8]) by default.  For every batch size: one warm-up call of the same shape,
+m ~ U[1, 8]) by default.  --max-visible M: m ~ U[1, M]; above 16 (EKF) / 8 (EKF_Rotations) the batch runs the wide-frame
+kernel (EKF_FLAG_BATCH_WIDE_FRAMES, csrc/ekf_batch_wide.hip) and the single filter takes max_visible = M.  For every batch size: one warm-up call of the same shape,
 then one timed call (host clock around the call, which ends in a synchronise).  The rate is stepped steady frames of all
 members over wall time; the bootstrap frames run in the warm-up call, so the timed call is the steady segment alone.
 Beside it, the single-filter rate of process_detection_log on member 0's steady segment (same timing rule).  One JSON line
 per point, printed and appended to profiles/batch/batch_bench.jsonl (--out).
 Kernel times: a separate `rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --members 256` run (the large-map
-ones in profiles/batch/rocprof_large_*.json).
+ones in profiles/batch/rocprof_large_*.json, the wide-frame ones in profiles/batch/rocprof_wide_*.json).
 """
 from __future__ import annotations
 
@@ -43,8 +44,10 @@ def main():
     ap.add_argument("--members", type=int, nargs="*", default=[1, 16, 64, 256, 1024])
     ap.add_argument("--model", choices=("ekf", "ekf_rotations"), default="ekf")
     ap.add_argument("--landmarks", type=int, default=None,
-                    help="default: 50 (ekf), 24 (ekf_rotations); with --large-maps 250 (ekf), 100 (ekf_rotations)")
+                    help="default: 50 (ekf), 24 (ekf_rotations); with --large-maps or wide frames 250 (ekf), 100 (ekf_rotations)")
     ap.add_argument("--large-maps", action="store_true", help="run the large-map kernel (EKFBatch(large_maps=True))")
+    ap.add_argument("--max-visible", type=int, default=None,
+                    help="m ~ U[1, M] (default: 10 for ekf, 8 for ekf_rotations); above 16 / 8 the wide-frame kernel runs")
     ap.add_argument("--steady", type=int, default=500)
     ap.add_argument("--out", default=str(REPO / "profiles" / "batch" / "batch_bench.jsonl"))
     args = ap.parse_args()
@@ -56,9 +59,10 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("batch_bench needs a HIP device")
     rot = args.model == "ekf_rotations"
-    n = args.landmarks or ((100 if rot else 250) if args.large_maps else (24 if rot else 50))
-    m_hi = 8 if rot else 10
-    visible = 8 if rot else 16
+    m_hi = args.max_visible or (8 if rot else 10)
+    wide = m_hi > (8 if rot else 16)
+    n = args.landmarks or ((100 if rot else 250) if args.large_maps or wide else (24 if rot else 50))
+    visible = max(m_hi, 8 if rot else 16)
     logs = [split(lg, lg["bootstrap_frames"]) for lg in
             (ragged_log(n, (1, m_hi), args.steady, seed=s, rvec_sigma=0.05 if rot else 0.0)
              for s in range(max(args.members)))]
@@ -81,13 +85,20 @@ def main():
         assert batch.status() == [0] * B
         rate = B * args.steady / wall
         line = {"tool": "batch_bench", **({"model": args.model} if rot else {}),
-                **({"large_maps": True} if args.large_maps else {}), "members": B, "n": n, "m": [1, m_hi],
+                **({"large_maps": True} if args.large_maps else {}),
+                **({"wide_frames": True} if batch.wide_frames else {}), "members": B, "n": n, "m": [1, m_hi],
                 "steady_frames": args.steady,
                 "wall_s": round(wall, 6), "aggregate_frames_per_s": round(rate, 1),
                 "single_filter_frames_per_s": round(single, 1), "ratio": round(rate / single, 2)}
-        if args.large_maps:     # every stepped frame reads and writes the member's N x N f64 covariance once
+        if args.large_maps or batch.wide_frames:     # every stepped frame reads and writes the member's N x N f64 covariance
+            # once (wide frames: once per block)
             dims = (10 if rot else 3) * n + 10
-            line["p_stream_tb_per_s"] = round(rate * 2 * dims * dims * 8 / 1e12, 3)
+            sweeps = 1.0
+            if batch.wide_frames:       # one read-modify-write of P per block of 16 / 8 detections
+                m = np.diff(np.concatenate([lg[1]["offsets"] for lg in logs[:1]]))
+                sweeps = float(np.ceil(m[m > 0] / (8 if rot else 16)).mean())
+                line["p_sweeps_per_frame"] = round(sweeps, 3)
+            line["p_stream_tb_per_s"] = round(rate * 2 * dims * dims * 8 * sweeps / 1e12, 3)
         print(json.dumps(line), flush=True)
         lines.append(line)
         del batch

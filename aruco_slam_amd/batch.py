@@ -13,10 +13,16 @@ grow to dictionary size: ``max_landmarks`` <= 338 (``EKF``) or <= 101 (``EKF_Rot
 a default single filter takes: ``max_visible`` <= 64 (``EKF``) or <= 50 (``EKF_Rotations``), on the large-map limits of
 ``max_landmarks``; a frame is factorised in blocks of 16 / 8 detections, and one of at most 16 / 8 detections gives the same
 bits as a batch without the flag.  A batch never grows; there is no CPU fallback.
+
+Monte-Carlo studies need no host-side re-noising: ``replay_replicas`` replays ONE log in every member, each as a numbered
+replica whose detection noise the device draws (``csrc/ekf_batch_replicas.hip``; ``replica_poses`` returns exactly the
+poses a replica consumed).  Runs and sweeps are judged by the filter's own statistics: with ``nis`` / ``cam_cov`` both replay
+calls also return every frame's normalised innovation squared and camera covariance P[0:10, 0:10].
 """
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -51,6 +57,85 @@ def use_wide_frames(model: str, max_visible: int, wide_frames: bool | None = Non
     if wide_frames is None:
         return int(max_visible) > COLUMN_MAX_VISIBLE[model]
     return bool(wide_frames)
+
+
+RD = {"ekf": 3, "ekf_rotations": 7}         # measurement rows per detection: a frame of m detections has RD m rows
+
+
+class BatchReplay(NamedTuple):
+    """``process_detection_logs(..., nis=True / cam_cov=True)``: per-member lists.  ``trajectory[b]`` [F_b, 7]; ``nis[b]``
+    [F_b] (None unless asked); ``dof[b]`` [F_b] the frame's row count (3 m or 7 m, duplicate detections counted, 0 for an
+    empty frame); ``cam_cov[b]`` [F_b, 10, 10] (None unless asked)."""
+    trajectory: list
+    nis: list | None
+    dof: list
+    cam_cov: list | None
+
+
+class ReplicaReplay(NamedTuple):
+    """``replay_replicas``: ``trajectory`` [B, F, 7], ``nis`` [B, F] (None unless asked), ``dof`` [F], ``cam_cov``
+    [B, F, 10, 10] (None unless asked)."""
+    trajectory: np.ndarray
+    nis: np.ndarray | None
+    dof: np.ndarray
+    cam_cov: np.ndarray | None
+
+
+def replica_sigma(sigma, replicas: int) -> np.ndarray:
+    """``sigma`` (a scalar, [6] or [replicas, 6]; finite, >= 0) as a contiguous [replicas, 6] array; ``ValueError``
+    otherwise."""
+    s = np.asarray(sigma, dtype=np.float64)
+    if s.ndim == 0 or s.shape == (6,):
+        s = np.broadcast_to(s, (replicas, 6))
+    elif s.shape != (replicas, 6):
+        raise ValueError(f"sigma must be a scalar, [6] or [{replicas}, 6], got shape {s.shape}")
+    if not np.isfinite(s).all() or (s < 0).any():
+        raise ValueError("sigma must be finite and >= 0")
+    return np.ascontiguousarray(s)
+
+
+def _replica_range(first_replica, replicas: int) -> int:
+    r0 = int(first_replica)
+    if r0 < 0 or r0 + int(replicas) > 2 ** 32:
+        raise ValueError(f"first_replica must be >= 0 with first_replica + {replicas} <= 2**32, got {r0}")
+    return r0
+
+
+def replica_poses(poses, sigma, seed: int, *, replicas: int | None = None, first_replica: int = 0,
+                  device: str = "cuda:0") -> np.ndarray:
+    """The noisy poses [R, D, 6] that replicas ``first_replica`` .. ``first_replica + R - 1`` of a log with ``poses`` [D, 6]
+    consume in ``EKFBatch.replay_replicas`` (``ekf_batch_replica_poses``, the same device code): ``poses[d][c] +
+    sigma[r][c] g_c(seed, r, d)`` with the Philox4x32-10 / Box-Muller normals defined in ``include/ekf_slam_hip.h``.
+    ``sigma``: a scalar, [6] or [R, 6]; R = ``replicas``, or sigma's rows."""
+    import torch
+    lib = load_library()
+    if not torch.cuda.is_available():
+        raise RuntimeError("replica noise is generated on a HIP device (no CPU fallback)")
+    poses = np.ascontiguousarray(poses, dtype=np.float64)
+    if poses.ndim != 2 or poses.shape[1] != 6:
+        raise ValueError(f"poses must have shape (D, 6), got {poses.shape}")
+    if replicas is None:
+        s = np.asarray(sigma)
+        if s.ndim != 2:
+            raise ValueError("give replicas= unless sigma is [R, 6]")
+        replicas = s.shape[0]
+    sig = replica_sigma(sigma, int(replicas))
+    r0 = _replica_range(first_replica, replicas)
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2**64)")
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        src = torch.from_numpy(poses).to(dev)
+        out = torch.empty((int(replicas), poses.shape[0], 6), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        rc = lib.ekf_batch_replica_poses(src.data_ptr() if poses.shape[0] else None, poses.shape[0], _dptr(sig),
+                                         int(replicas), seed, r0, out.data_ptr() if out.numel() else None,
+                                         stream.cuda_stream)
+        if rc != 0:
+            raise EkfError(rc, lib.ekf_last_error_string().decode())
+        stream.synchronize()
+    return out.cpu().numpy()
 
 
 def _iptr(a: np.ndarray):
@@ -160,12 +245,16 @@ class EKFBatch:
         return b
 
     # -- replay ------------------------------------------------------------------------------------------------------
-    def process_detection_logs(self, logs) -> list:
+    def process_detection_logs(self, logs, *, nis: bool = False, cam_cov: bool = False):
         """One log per member (``None``: no log), each a dict of the replay layout ``ids [D]``, ``poses [D,6]``,
         ``offsets [F+1]`` and optionally ``has_detections [F]``.  Returns the camera pose ``state[0:7]`` after every frame,
         one ``(F_b, 7)`` array per member.  A malformed log raises ``ValueError``, a log that needs more landmarks or
         detections per frame than the batch holds ``EkfError`` (EKF_ERR_CAPACITY); either way before anything runs, and no
-        member (``landmarks`` included) changes."""
+        member (``landmarks`` included) changes.
+        With ``nis`` or ``cam_cov`` it returns a ``BatchReplay`` of per-member lists instead: the trajectories, each
+        frame's normalised innovation squared (z-h)^T S^-1 (z-h) (0 for a frame that is not stepped), its row count
+        ``dof`` (the NIS's chi^2 degrees of freedom; approximate for EKF_Rotations, whose unit-quaternion rows are not
+        independent) and P[0:10, 0:10] after it.  A member's failing frame and every later one give NaN."""
         if len(logs) != self.members:
             raise ValueError(f"need {self.members} logs (None for a member without one), got {len(logs)}")
         plans, index, offsets, frames, poses = [], [], [], [0], []
@@ -189,18 +278,80 @@ class EKFBatch:
         index = np.concatenate(index).astype(np.int32) if index else np.zeros(0, np.int32)
         offsets = np.concatenate([np.zeros(1, np.int64)] + offsets).astype(np.int64)
         poses = np.ascontiguousarray(np.concatenate(poses) if poses else np.zeros((0, 6)))
-        traj = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses)
+        if nis or cam_cov:
+            traj, nis_v, cov_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses, nis=nis,
+                                                      cam_cov=cam_cov)
+        else:
+            traj = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses)
+        self._adopt_plans(plans)
+        split = [slice(frames[b], frames[b + 1]) for b in range(self.members)]
+        if not (nis or cam_cov):
+            return [traj[sl] for sl in split]
+        dof = RD[self.model] * np.diff(offsets)
+        return BatchReplay([traj[sl] for sl in split], [nis_v[sl] for sl in split] if nis else None,
+                           [dof[sl] for sl in split], [cov_v[sl] for sl in split] if cam_cov else None)
+
+    def _adopt_plans(self, plans) -> None:
+        """Landmark tables after a call, from the planned first sightings and the device's counts."""
         counts = self._num_landmarks_device()
         for b, plan in enumerate(plans):
             if plan is not None:        # (a member that failed keeps the landmarks it added before it stopped)
                 self.landmarks[b].update((k, j) for k, j in plan.new_landmarks.items() if j < counts[b])
             self.num_landmarks[b] = int(counts[b])
-        return [traj[frames[b]:frames[b + 1]] for b in range(self.members)]
 
-    def observe_indexed(self, lm_index, frame_offsets, member_frames, poses) -> np.ndarray:
+    def replay_replicas(self, log, sigma, seed: int, *, first_replica: int = 0, nis: bool = False,
+                        cam_cov: bool = False) -> ReplicaReplay:
+        """Monte-Carlo replicas of ONE log: member b replays ``log`` (the layout of ``process_detection_logs``) as replica
+        ``first_replica + b``, every detection's pose re-noised on the device as ``pose + sigma[b] * g`` with the
+        standard normals g of ``replica_poses`` (Philox4x32-10 / Box-Muller, defined in ``include/ekf_slam_hip.h``; a
+        replica's noise depends on its number, the detection and ``seed`` only, not on the batch size).  ``sigma``: a
+        scalar, [6] or [B, 6] over ``[tvec | rvec]`` (EKF reads only the tvec); each member keeps its own noise
+        constants, so a sweep x Monte-Carlo grid is one call.  The log is planned once: every member's landmark table must
+        be the same (after ``reset()`` they are all empty), else ``ValueError``.
+        Returns a ``ReplicaReplay``: ``trajectory`` [B, F, 7], ``dof`` [F] (the frame's row count 3 m / 7 m, duplicate
+        detections counted) and, if asked, ``nis`` [B, F] and ``cam_cov`` [B, F, 10, 10] as in ``process_detection_logs``.
+        Mean NIS over replicas against the chi^2(dof) bounds tunes the noise constants without ground truth; for
+        EKF_Rotations the unit-quaternion rows make that chi^2 reading approximate.  Bad arguments raise before anything
+        runs, and no member changes."""
+        sig = replica_sigma(sigma, self.members)
+        r0 = _replica_range(first_replica, self.members)
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2**64)")
+        if any(t != self.landmarks[0] for t in self.landmarks[1:]) or len(set(self.num_landmarks)) > 1:
+            raise ValueError("replay_replicas needs every member's landmark table to be the same (reset() first)")
+        plan = plan_detection_log(self.landmarks[0], self.num_landmarks[0], log["ids"], log["offsets"],
+                                  log.get("has_detections"))
+        p = np.asarray(log["poses"], dtype=np.float64)
+        if p.shape != (plan.keep.shape[0], 6):
+            raise ValueError(f"poses must have shape ({plan.keep.shape[0]}, 6), got {p.shape}")
+        poses = np.ascontiguousarray(p[plan.keep])
+        idx = np.ascontiguousarray(plan.index, dtype=np.int32)
+        fo = np.ascontiguousarray(plan.offsets, dtype=np.int64)
+        F, D, B = fo.shape[0] - 1, idx.shape[0], self.members
+        torch = self._torch
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_batch_replica_workspace_bytes(self.h, D, F, C.byref(nbytes)))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            poses_t = torch.from_numpy(poses).to(self.device)
+            ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=self.device)
+            traj = torch.empty((B, F, 7), dtype=torch.float64, device=self.device)
+            nis_t = torch.empty((B, F), dtype=torch.float64, device=self.device) if nis else None
+            cov_t = torch.empty((B, F, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
+            ptr = (lambda t: t.data_ptr() if t is not None and F else None)
+            self._check(self.lib.ekf_batch_observe_replicas(self.h, _iptr(idx), _lptr(fo), F, ptr(poses_t) if D else None,
+                                                            _dptr(sig), seed, r0, ws.data_ptr(), nbytes.value, ptr(traj),
+                                                            ptr(nis_t), ptr(cov_t)))
+            self.stream.synchronize()
+        self._adopt_plans([plan] * B)
+        return ReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None,
+                             RD[self.model] * np.diff(fo), cov_t.cpu().numpy() if cam_cov else None)
+
+    def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False):
         """The C call behind ``process_detection_logs`` (landmark indices already assigned; ``landmarks`` is not
         touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1], poses [D,6] on the host.  Returns the
-        trajectory [Ftot, 7]."""
+        trajectory [Ftot, 7]; with ``nis`` or ``cam_cov`` the tuple (trajectory, nis [Ftot] or None, cam_cov [Ftot, 10, 10]
+        or None)."""
         torch = self._torch
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
         fo = np.ascontiguousarray(frame_offsets, dtype=np.int64).reshape(-1)
@@ -219,11 +370,20 @@ class EKFBatch:
             poses_t = torch.from_numpy(poses).to(self.device)
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
             traj = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
-            self._check(self.lib.ekf_batch_observe_logs(self.h, _iptr(idx), _lptr(fo), _lptr(mf),
-                                                        poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
-                                                        nbytes.value, traj.data_ptr() if frames else None))
+            if not (nis or cam_cov):
+                self._check(self.lib.ekf_batch_observe_logs(self.h, _iptr(idx), _lptr(fo), _lptr(mf),
+                                                            poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
+                                                            nbytes.value, traj.data_ptr() if frames else None))
+                self.stream.synchronize()
+                return traj.cpu().numpy()
+            nis_t = torch.empty((frames,), dtype=torch.float64, device=self.device) if nis else None
+            cov_t = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
+            ptr = (lambda t: t.data_ptr() if t is not None and frames else None)
+            self._check(self.lib.ekf_batch_observe_logs_diag(self.h, _iptr(idx), _lptr(fo), _lptr(mf),
+                                                             poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
+                                                             nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t)))
             self.stream.synchronize()
-        return traj.cpu().numpy()
+        return (traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, cov_t.cpu().numpy() if cam_cov else None)
 
     # -- per-member state ---------------------------------------------------------------------------------------------
     def _num_landmarks_device(self) -> np.ndarray:

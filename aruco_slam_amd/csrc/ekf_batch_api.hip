@@ -1,6 +1,7 @@
 // C ABI of the batch of independent filters (ekf_batch_*, see include/ekf_slam_hip.h; kernels: ekf_batch.hip (EKF) and
 // ekf_batch_rot.hip (EKF_Rotations), with EKF_FLAG_BATCH_LARGE_MAPS ekf_batch_large.hip (both), with
-// EKF_FLAG_BATCH_WIDE_FRAMES ekf_batch_wide.hip (both); one workgroup per member).  Host side only: argument checking, workspace carving, launch sequencing.
+// EKF_FLAG_BATCH_WIDE_FRAMES ekf_batch_wide.hip (both); one workgroup per member; the noisy poses of replicas:
+// ekf_batch_replicas.hip).  Host side only: argument checking, workspace carving, launch sequencing.
 #include <cmath>
 #include <cstring>
 
@@ -133,6 +134,85 @@ int batch_put_member_words(ekf_batch* b, int32_t lo, int32_t hi) {
     const BatchLayout L = batch_layout(b->cfg, b->members);
     HIP_TRY(hipMemcpy(b->ws + L.status + 4 * (size_t)lo, b->status.data() + lo, (size_t)(hi - lo) * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->ws + L.nlm + 4 * (size_t)lo, b->nlm.data() + lo, (size_t)(hi - lo) * 4, hipMemcpyHostToDevice));
+    return EKF_OK;
+}
+
+// what the logs of a call ask of the window kernels' layout
+struct BatchShape {
+    int32_t n_max = 0, widest = 0;
+    int64_t frames_max = 0;
+    void add(const LogCheck& lc, int64_t frames) {
+        n_max = std::max(n_max, (int32_t)lc.n);
+        widest = std::max(widest, (int32_t)lc.widest);
+        frames_max = std::max(frames_max, frames);
+    }
+};
+
+int check_sigma(const double* sigma, int64_t rows) {
+    for (int64_t i = 0; i < 6 * rows; ++i)
+        if (!std::isfinite(sigma[i]) || sigma[i] < 0.0) return fail(EKF_ERR_INVALID, "sigma must be finite and >= 0");
+    return EKF_OK;
+}
+
+// replica workspace: [noisy poses [B D][6] | the log layout of B tiled copies of the log (B D detections, B F frames)]
+struct BatchReplicaLayout {
+    size_t poses;
+    BatchLogLayout log;
+    size_t total;
+};
+
+BatchReplicaLayout batch_replica_layout(int64_t D, int64_t F, int32_t B) {
+    const BatchLogLayout log = batch_log_layout((int64_t)B * D, (int64_t)B * F, B);
+    return {log.total, log, log.total + align256((size_t)B * D * 6 * 8)};
+}
+
+// The windows of a call whose indices and offsets are on the device (ws, layout LL): every member's frames
+// [w, w + window) of its log per launch, state carried in HBM.  LDS is sized for the widest frame and the largest map of
+// the call (a layout choice only: the arithmetic is the same)
+int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, const BatchShape& sh, const double* poses_dev,
+                      double* trajectory_dev, double* nis_dev, double* cam_cov_dev) {
+    const int32_t B = b->members;
+    const BatchLayout L = batch_layout(b->cfg, B);
+    EkfBatchWindow a{};
+    a.P = b->cov;
+    a.ld = b->ld;
+    a.state = b->state;
+    a.noise = reinterpret_cast<const double*>(b->ws);
+    a.status = reinterpret_cast<int32_t*>(b->ws + L.status);
+    a.nlm = reinterpret_cast<int32_t*>(b->ws + L.nlm);
+    a.lm_index = reinterpret_cast<const int32_t*>(ws);
+    a.frame_offsets = reinterpret_cast<const int64_t*>(ws + LL.frames);
+    a.member_frames = reinterpret_cast<const int64_t*>(ws + LL.members);
+    a.poses = poses_dev;
+    a.traj = trajectory_dev;
+    a.nis = nis_dev;
+    a.cam_cov = cam_cov_dev;
+    a.quat_mode = b->cfg.quat_mode;
+    const int rd = batch_rd(b->cfg);
+    a.kmax = std::max(rd, rd * sh.widest);
+    a.lda = (int32_t)round_up(batch_lmd(b->cfg) * sh.n_max + EKF_CAM + 1, 4);
+    const bool rot = b->cfg.model == EKF_MODEL_ROTATIONS, wide = batch_wide(b->cfg);
+    // wide frames: a frame of m detections costs about ceil(m / block) sweeps of P (block = 16 / 8 detections), so the
+    // window shrinks with the call's widest frame and one launch stays about as long as a large-map window
+    const int block = rot ? EKF_BATCH_ROT_MAX_VISIBLE : EKF_BATCH_MAX_VISIBLE;
+    const int window = wide ? std::max(1, kBatchWindow / ((std::max(sh.widest, 1) + block - 1) / block)) : kBatchWindow;
+    a.window_frames = window;
+    // large maps or wide frames: every call runs ekf_batch_large.hip or ekf_batch_wide.hip, whatever the map size and the
+    // frame widths (A / W in the workspace)
+    EkfBatchLargeWindow g{a, reinterpret_cast<double*>(b->ws + L.w), batch_w_stride(b->cfg)};
+    for (int64_t w = 0; w < sh.frames_max; w += window) {
+        a.window_first = (int32_t)w;
+        g.w.window_first = (int32_t)w;
+        if (wide)
+            ekf_launch_batch_wide_window(rot ? 1 : 0, g, B, b->stream);
+        else if (batch_large(b->cfg))
+            ekf_launch_batch_large_window(rot ? 1 : 0, g, B, b->stream);
+        else if (rot)
+            ekf_launch_batch_rot_window(a, B, b->stream);
+        else
+            ekf_launch_batch_window(a, B, b->stream);
+        HIP_TRY(hipGetLastError());
+    }
     return EKF_OK;
 }
 
@@ -311,6 +391,13 @@ int ekf_batch_log_workspace_bytes(const ekf_batch* b, int64_t detections, int64_
 
 int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, const int64_t* member_frames,
                            const double* poses_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev) {
+    return ekf_batch_observe_logs_diag(b, lm_index, frame_offsets, member_frames, poses_dev, log_ws, log_ws_bytes,
+                                       trajectory_dev, nullptr, nullptr);
+}
+
+int ekf_batch_observe_logs_diag(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets,
+                                const int64_t* member_frames, const double* poses_dev, void* log_ws, size_t log_ws_bytes,
+                                double* trajectory_dev, double* nis_dev, double* cam_cov_dev) {
     int rc = batch_ready(b);
     if (rc) return rc;
     // ---- validation on the host: nothing is enqueued before every log has passed
@@ -324,16 +411,13 @@ int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t*
     const BatchLogLayout LL = batch_log_layout(D, F, B);
     if ((rc = check_device_buffers({log_ws}, log_ws_bytes, LL.total, "ekf_batch_log_workspace_bytes"))) return rc;
     if ((rc = batch_refresh(b))) return rc;      // (landmark counts as the previous call left them)
-    int32_t n_max = 0, widest = 0;
-    int64_t frames_max = 0;
+    BatchShape sh;
     LogCheck lc;
     for (int32_t m = 0; m < B; ++m) {
         const int64_t f0 = member_frames[m], frames = member_frames[m + 1] - f0;
         rc = check_log(lm_index, frame_offsets + f0, frames, b->nlm[m], b->cfg, "member " + std::to_string(m) + "'s log", &lc);
         if (rc) return rc;
-        n_max = std::max(n_max, (int32_t)lc.n);
-        widest = std::max(widest, (int32_t)lc.widest);
-        frames_max = std::max(frames_max, frames);
+        sh.add(lc, frames);
     }
     if (F == 0) return EKF_OK;
 
@@ -344,49 +428,87 @@ int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t*
     std::memcpy(b->pin.get() + LL.members, member_frames, (size_t)(B + 1) * 8);
     char* ws = static_cast<char*>(log_ws);
     HIP_TRY(hipMemcpyAsync(ws, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
+    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev);
+}
 
-    // ---- windows: every member's frames [w, w + kBatchWindow) of its log per launch, state carried in HBM.  LDS is
-    // sized for the widest frame and the largest map of the call (a layout choice only: the arithmetic is the same)
-    const BatchLayout L = batch_layout(b->cfg, B);
-    EkfBatchWindow a{};
-    a.P = b->cov;
-    a.ld = b->ld;
-    a.state = b->state;
-    a.noise = reinterpret_cast<const double*>(b->ws);
-    a.status = reinterpret_cast<int32_t*>(b->ws + L.status);
-    a.nlm = reinterpret_cast<int32_t*>(b->ws + L.nlm);
-    a.lm_index = reinterpret_cast<const int32_t*>(ws);
-    a.frame_offsets = reinterpret_cast<const int64_t*>(ws + LL.frames);
-    a.member_frames = reinterpret_cast<const int64_t*>(ws + LL.members);
-    a.poses = poses_dev;
-    a.traj = trajectory_dev;
-    a.quat_mode = b->cfg.quat_mode;
-    const int rd = batch_rd(b->cfg);
-    a.kmax = std::max(rd, rd * widest);
-    a.lda = (int32_t)round_up(batch_lmd(b->cfg) * n_max + EKF_CAM + 1, 4);
-    const bool rot = b->cfg.model == EKF_MODEL_ROTATIONS, wide = batch_wide(b->cfg);
-    // wide frames: a frame of m detections costs about ceil(m / block) sweeps of P (block = 16 / 8 detections), so the
-    // window shrinks with the call's widest frame and one launch stays about as long as a large-map window
-    const int block = rot ? EKF_BATCH_ROT_MAX_VISIBLE : EKF_BATCH_MAX_VISIBLE;
-    const int window = wide ? std::max(1, kBatchWindow / ((std::max(widest, 1) + block - 1) / block)) : kBatchWindow;
-    a.window_frames = window;
-    // large maps or wide frames: every call runs ekf_batch_large.hip or ekf_batch_wide.hip, whatever the map size and the
-    // frame widths (A / W in the workspace)
-    EkfBatchLargeWindow g{a, reinterpret_cast<double*>(b->ws + L.w), batch_w_stride(b->cfg)};
-    for (int64_t w = 0; w < frames_max; w += window) {
-        a.window_first = (int32_t)w;
-        g.w.window_first = (int32_t)w;
-        if (wide)
-            ekf_launch_batch_wide_window(rot ? 1 : 0, g, B, b->stream);
-        else if (batch_large(b->cfg))
-            ekf_launch_batch_large_window(rot ? 1 : 0, g, B, b->stream);
-        else if (rot)
-            ekf_launch_batch_rot_window(a, B, b->stream);
-        else
-            ekf_launch_batch_window(a, B, b->stream);
+int ekf_batch_replica_poses(const double* poses_dev, int64_t detections, const double* sigma, int32_t replicas,
+                            uint64_t seed, uint32_t first_replica, double* out_dev, void* stream) {
+    if (detections < 0 || replicas < 0) return fail(EKF_ERR_INVALID, "bad replica request");
+    if ((uint64_t)first_replica + (uint64_t)replicas > (1ull << 32))
+        return fail(EKF_ERR_INVALID, "first_replica + replicas must not exceed 2^32");
+    if (replicas == 0) return EKF_OK;
+    if (!sigma) return fail(EKF_ERR_INVALID, "sigma is NULL");
+    int rc = check_sigma(sigma, replicas);
+    if (rc) return rc;
+    if (detections == 0) return EKF_OK;
+    if (!poses_dev || !out_dev) return fail(EKF_ERR_INVALID, "NULL poses or output");
+    ekf_launch_replica_poses(poses_dev, detections, sigma, replicas, seed, first_replica, out_dev,
+                             static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return EKF_OK;
+}
+
+int ekf_batch_replica_workspace_bytes(const ekf_batch* b, int64_t detections, int64_t frames, size_t* bytes) {
+    if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
+    if (!bytes || detections < 0 || frames < 0) return fail(EKF_ERR_INVALID, "bad log size request");
+    *bytes = batch_replica_layout(detections, frames, b->members).total;
+    return EKF_OK;
+}
+
+int ekf_batch_observe_replicas(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, int64_t frames,
+                               const double* poses_dev, const double* sigma, uint64_t seed, uint32_t first_replica,
+                               void* ws, size_t ws_bytes, double* trajectory_dev, double* nis_dev, double* cam_cov_dev) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    // ---- validation on the host: nothing is enqueued before the log has passed for every member
+    const int32_t B = b->members;
+    if (frames < 0) return fail(EKF_ERR_INVALID, "frames must be >= 0");
+    if (!frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
+    if ((rc = check_offsets(frame_offsets, frames, "frame_offsets"))) return rc;
+    const int64_t D = frame_offsets[frames];
+    if (D > 0 && (!lm_index || !poses_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
+    if (!sigma) return fail(EKF_ERR_INVALID, "sigma is NULL");
+    if ((rc = check_sigma(sigma, B))) return rc;
+    if ((uint64_t)first_replica + (uint64_t)B > (1ull << 32))
+        return fail(EKF_ERR_INVALID, "first_replica + members must not exceed 2^32");
+    const BatchReplicaLayout RL = batch_replica_layout(D, frames, B);
+    if ((rc = check_device_buffers({ws}, ws_bytes, RL.total, "ekf_batch_replica_workspace_bytes"))) return rc;
+    if ((rc = batch_refresh(b))) return rc;
+    BatchShape sh;
+    LogCheck lc;
+    for (int32_t m = 0; m < B; ++m) {
+        if (m > 0 && b->nlm[m] == b->nlm[m - 1]) {      // (the same log on the same landmark count: the same verdict)
+            sh.add(lc, frames);
+            continue;
+        }
+        rc = check_log(lm_index, frame_offsets, frames, b->nlm[m], b->cfg, "the log (member " + std::to_string(m) + ")", &lc);
+        if (rc) return rc;
+        sh.add(lc, frames);
+    }
+    if (frames == 0) return EKF_OK;
+
+    // ---- staging: the log's indices and offsets tiled member after member (member b: detections b D .., frames b F ..)
+    const int64_t Ft = (int64_t)B * frames, Dt = (int64_t)B * D;
+    const BatchLogLayout& LL = RL.log;
+    if ((rc = b->pin.reserve(LL.total))) return rc;
+    int32_t* idx = b->pin.at<int32_t>(0);
+    int64_t* fo = b->pin.at<int64_t>(LL.frames);
+    int64_t* mf = b->pin.at<int64_t>(LL.members);
+    for (int32_t m = 0; m < B; ++m) {
+        if (D > 0) std::memcpy(idx + (size_t)m * D, lm_index, (size_t)D * 4);
+        for (int64_t t = 0; t < frames; ++t) fo[(size_t)m * frames + t] = (int64_t)m * D + frame_offsets[t];
+        mf[m] = (int64_t)m * frames;
+    }
+    fo[Ft] = Dt;
+    mf[B] = Ft;
+    char* w = static_cast<char*>(ws);
+    HIP_TRY(hipMemcpyAsync(w, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
+    double* noisy = reinterpret_cast<double*>(w + RL.poses);
+    if (D > 0) {
+        ekf_launch_replica_poses(poses_dev, D, sigma, B, seed, first_replica, noisy, b->stream);
         HIP_TRY(hipGetLastError());
     }
-    return EKF_OK;
+    return batch_run_windows(b, w, LL, sh, noisy, trajectory_dev, nis_dev, cam_cov_dev);
 }
 
 }  // extern "C"

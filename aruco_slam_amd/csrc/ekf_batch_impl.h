@@ -23,6 +23,31 @@ template <int MODEL> inline size_t ekf_batch_lds_bytes_of(int kmax, int lda) {
            4 * (EkfBatchCaps<MODEL>::MAX_VISIBLE + 4);
 }
 
+// Per-frame outputs of every window kernel (traj, nis, cam_cov; each may be null).  A frame that is not stepped repeats the
+// state and P[0:10, 0:10] with nis = 0; once the member has failed (its failing frame included) all three are NaN.
+__device__ __forceinline__ void ekf_batch_rows_unstepped(const EkfBatchWindow& a, int64_t t, int tid, const double* st,
+                                                         const double* P, bool failed) {
+    const double nan = __builtin_nan("");
+    if (a.traj && tid < 7) a.traj[7 * t + tid] = failed ? nan : st[tid];
+    if (a.nis && tid == 0) a.nis[t] = failed ? nan : 0.0;
+    if (a.cam_cov && tid < EKF_CAM * EKF_CAM)
+        a.cam_cov[EKF_CAM * EKF_CAM * t + tid] = failed ? nan : P[(int64_t)(tid / EKF_CAM) * a.ld + tid % EKF_CAM];
+}
+
+// After a stepped frame, behind the barrier that ends the covariance update: y [k] (stride ys) is the whitened residual
+// L^-1 (z - h) of the frame; nis is one thread's i-ascending fma chain over it (the same bits wherever y has the same bits).
+__device__ __forceinline__ void ekf_batch_rows_stepped(const EkfBatchWindow& a, int64_t t, int tid, const double* st,
+                                                       const double* P, const double* y, int ys, int k) {
+    if (a.traj && tid < 7) a.traj[7 * t + tid] = st[tid];
+    if (a.nis && tid == 0) {
+        double acc = 0.0;
+        for (int i = 0; i < k; ++i) acc = fma(y[i * ys], y[i * ys], acc);
+        a.nis[t] = acc;
+    }
+    if (a.cam_cov && tid < EKF_CAM * EKF_CAM)
+        a.cam_cov[EKF_CAM * EKF_CAM * t + tid] = P[(int64_t)(tid / EKF_CAM) * a.ld + tid % EKF_CAM];
+}
+
 template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -53,8 +78,8 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t d0 = a.frame_offsets[t];
         const int m = (int)(a.frame_offsets[t + 1] - d0);
-        if (failed || m == 0) {      // not stepped: the row repeats the state (NaN once the member has failed)
-            if (a.traj && tid < 7) a.traj[7 * t + tid] = failed ? __builtin_nan("") : st[tid];
+        if (failed || m == 0) {      // not stepped: the rows repeat the state (NaN once the member has failed)
+            ekf_batch_rows_unstepped(a, t, tid, st, P, failed);
             continue;
         }
         const int32_t* idx = a.lm_index + d0;
@@ -153,7 +178,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
         if (*flag) {      // the member stops here: the update of this frame changes neither state nor P
             failed = true;
             if (tid == 0) a.status[b] = EKF_BATCH_ST_NUMERIC;
-            if (a.traj && tid < 7) a.traj[7 * t + tid] = __builtin_nan("");
+            ekf_batch_rows_unstepped(a, t, tid, st, P, true);
             continue;
         }
         // W = L^-1 A and y = L^-1 (z - h): thread c substitutes column c (c = N: the residual) in place
@@ -214,7 +239,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
             }
         }
         __syncthreads();
-        if (a.traj && tid < 7) a.traj[7 * t + tid] = st[tid];
+        ekf_batch_rows_stepped(a, t, tid, st, P, A + N, lda, k);      // (y is column N of A)
     }
     if (tid == 0) a.nlm[b] = n;
 }

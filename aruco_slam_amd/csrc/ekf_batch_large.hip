@@ -66,8 +66,8 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_large_window(cons
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t d0 = a.frame_offsets[t];
         const int m = (int)(a.frame_offsets[t + 1] - d0);
-        if (failed || m == 0) {      // not stepped: the row repeats the state (NaN once the member has failed)
-            if (a.traj && tid < 7) a.traj[7 * t + tid] = failed ? __builtin_nan("") : st[tid];
+        if (failed || m == 0) {      // not stepped: the rows repeat the state (NaN once the member has failed)
+            ekf_batch_rows_unstepped(a, t, tid, st, P, failed);
             continue;
         }
         const int32_t* idx = a.lm_index + d0;
@@ -162,7 +162,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_large_window(cons
         if (*flag) {      // the member stops here: the update of this frame changes neither state nor P
             failed = true;
             if (tid == 0) a.status[b] = EKF_BATCH_ST_NUMERIC;
-            if (a.traj && tid < 7) a.traj[7 * t + tid] = __builtin_nan("");
+            ekf_batch_rows_unstepped(a, t, tid, st, P, true);
             continue;
         }
         // W = L^-1 A and y = L^-1 (z - h): thread c substitutes column c (c = N: y) in place; a column of A is copied to
@@ -275,7 +275,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_large_window(cons
             }
         }
         __syncthreads();
-        if (a.traj && tid < 7) a.traj[7 * t + tid] = st[tid];
+        ekf_batch_rows_stepped(a, t, tid, st, P, y, 1, k);
     }
     if (tid == 0) a.nlm[b] = n;
 }

@@ -17,7 +17,7 @@
 // same bits.  Nothing touches P or the state before the last pivot of the frame has passed, so a failing pivot in any block
 // leaves them as the frame found them (its first sightings stay added, as everywhere).
 // LDS holds the block's L_jj (and, in turn, each L_ji), 1 / L_jj, J of the block, y [kmax] and the region R of
-// 256 x round_up(kb, 4) doubles of ekf_batch_large.hip: 123,920 bytes at the EKF's kmax = 192, 152,256 at EKF_Rotations'
+// 256 x round_up(kb, 4) doubles of ekf_batch_large.hip: 123,920 bytes at the EKF's kmax = 192, 152,200 at EKF_Rotations'
 // kmax = 350.  The off-diagonal factor rows are not stored: each L_ji is formed from W rows in HBM when it is used.
 // P of a member is read and written by its own workgroup only: workgroup barriers are the only ordering.
 #include "ekf_batch_impl.h"
@@ -80,8 +80,8 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_wide_window(const
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t d0 = a.frame_offsets[t];
         const int m = (int)(a.frame_offsets[t + 1] - d0);
-        if (failed || m == 0) {      // not stepped: the row repeats the state (NaN once the member has failed)
-            if (a.traj && tid < 7) a.traj[7 * t + tid] = failed ? __builtin_nan("") : st[tid];
+        if (failed || m == 0) {      // not stepped: the rows repeat the state (NaN once the member has failed)
+            ekf_batch_rows_unstepped(a, t, tid, st, P, failed);
             continue;
         }
         const int32_t* idx = a.lm_index + d0;
@@ -229,7 +229,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_wide_window(const
         if (*flag) {      // the member stops here: the update of this frame changes neither state nor P
             failed = true;
             if (tid == 0) a.status[b] = EKF_BATCH_ST_NUMERIC;
-            if (a.traj && tid < 7) a.traj[7 * t + tid] = __builtin_nan("");
+            ekf_batch_rows_unstepped(a, t, tid, st, P, true);
             continue;
         }
         __syncthreads();
@@ -330,7 +330,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_wide_window(const
             }
         }
         __syncthreads();
-        if (a.traj && tid < 7) a.traj[7 * t + tid] = st[tid];
+        ekf_batch_rows_stepped(a, t, tid, st, P, y, 1, k);
     }
     if (tid == 0) a.nlm[b] = n;
 }

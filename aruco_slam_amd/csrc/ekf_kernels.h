@@ -207,6 +207,8 @@ struct EkfBatchWindow {
     const int64_t* member_frames;   // [B + 1] frame offsets per member
     const double* poses;            // [D][6] [tvec | rvec]; z = pose[0:3] (EKF), ekf_pose_z (EKF_Rotations)
     double* traj;                   // [Ftot][7] or null
+    double* nis;                    // [Ftot] or null: y^T y = (z-h)^T S^-1 (z-h) of every stepped frame (0: empty frame)
+    double* cam_cov;                // [Ftot][10][10] or null: P[0:10, 0:10] after every frame
     int32_t quat_mode;              // (EKF; EKF_Rotations is scalar-first)
     int32_t window_first, window_frames;
     int32_t kmax, lda;              // LDS layout: rows of A / W, row length of A / W (> N; column N holds the residual)
@@ -233,6 +235,12 @@ void ekf_launch_batch_large_window(int model, const EkfBatchLargeWindow& g, int 
 #define EKF_BATCH_ROT_WIDE_MAX_VISIBLE 50   // EKF_Rotations: k = 7 m <= 350 rows
 extern "C" size_t ekf_batch_wide_lds_bytes(int model, int kmax);
 void ekf_launch_batch_wide_window(int model, const EkfBatchLargeWindow& g, int members, hipStream_t s);
+// Replicas of one log (ekf_batch_replicas.hip): out[r][d][c] = poses[d][c] + sigma[r][c] g_c(seed, r0 + r, d), c < 6, for
+// `count` <= EKF_REPLICA_CHUNK replicas per launch (sigma travels in the kernel arguments); g: Philox4x32-10 + Box-Muller,
+// the definition in include/ekf_slam_hip.h (ekf_batch_replica_poses)
+#define EKF_REPLICA_CHUNK 64
+void ekf_launch_replica_poses(const double* poses_dev, int64_t D, const double* sigma, int32_t count, uint64_t seed,
+                              uint32_t r0, double* out_dev, hipStream_t s);
 
 // Detection -> pose front end (ekf_pose_ippe.hip): pinhole camera + Brown-Conrady distortion k1 k2 p1 p2 k3 k4 k5 k6
 struct EkfCamera {

@@ -33,7 +33,8 @@ EXPORTED_SYMBOLS = (
     "ekf_log_workspace_bytes", "ekf_observe_log", "ekf_last_log_stats",
     "ekf_batch_query_sizes", "ekf_batch_create", "ekf_batch_bind_buffers", "ekf_batch_destroy", "ekf_batch_set_noise",
     "ekf_batch_reset", "ekf_batch_set_member", "ekf_batch_get_member", "ekf_batch_num_landmarks", "ekf_batch_status",
-    "ekf_batch_log_workspace_bytes", "ekf_batch_observe_logs",
+    "ekf_batch_log_workspace_bytes", "ekf_batch_observe_logs", "ekf_batch_observe_logs_diag", "ekf_batch_replica_poses",
+    "ekf_batch_replica_workspace_bytes", "ekf_batch_observe_replicas",
 )
 
 
@@ -116,6 +117,12 @@ def load_library(path: str | Path | None = None):
         "ekf_batch_status": [vp, ip],
         "ekf_batch_log_workspace_bytes": [vp, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)],
         "ekf_batch_observe_logs": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, vp, C.c_size_t, vp],
+        "ekf_batch_observe_logs_diag": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, vp, C.c_size_t, vp, vp,
+                                        vp],
+        "ekf_batch_replica_poses": [vp, C.c_int64, dp, C.c_int32, C.c_uint64, C.c_uint32, vp, vp],
+        "ekf_batch_replica_workspace_bytes": [vp, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)],
+        "ekf_batch_observe_replicas": [vp, ip, C.POINTER(C.c_int64), C.c_int64, vp, dp, C.c_uint64, C.c_uint32, vp,
+                                       C.c_size_t, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

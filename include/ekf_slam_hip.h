@@ -270,7 +270,7 @@ int ekf_estimate_poses(const double *corners, int32_t count, double marker_size,
                        double *poses, void *stream);
 
 /* ---- Batch of independent filters: many detection logs replayed at once (parameter sweeps, evaluation sets, Monte-Carlo
- * runs).  Every member is BaseFilter.process_detections with should_filter=True over its own log, exactly as
+ * runs: ekf_batch_observe_replicas below).  Every member is BaseFilter.process_detections with should_filter=True over its own log, exactly as
  * ekf_observe_log does it; one workgroup owns one member for a window of frames, members never wait for each other.
  *
  * cfg, by model (every member of a batch has the batch's model):
@@ -334,6 +334,51 @@ int ekf_batch_log_workspace_bytes(const ekf_batch *b, int64_t detections, int64_
  * getters synchronise. */
 int ekf_batch_observe_logs(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets, const int64_t *member_frames,
                            const double *poses_dev, void *log_ws, size_t log_ws_bytes, double *trajectory_dev);
+/* ekf_batch_observe_logs with the filter's own statistics per frame, next to the trajectory rows (either may be NULL;
+ * with both NULL this IS ekf_batch_observe_logs, to the bit):
+ *   nis_dev [Ftot]              DEVICE  normalised innovation squared (z-h)^T S^-1 (z-h) = y^T y, y = L^-1 (z-h) the
+ *                                       whitened residual, summed i = 0 .. k-1 in one fma chain; 0 for a frame without
+ *                                       detections.  Its expected value is the frame's row count k = 3 m (EKF) or 7 m
+ *                                       (EKF_MODEL_ROTATIONS, where the unit-quaternion rows make the chi^2 reading
+ *                                       approximate).
+ *   cam_cov_dev [Ftot,10,10]    DEVICE  P[0:10, 0:10] after every frame (repeated by a frame without detections).
+ * A member's failing frame and every later one give NaN, as the trajectory rows. */
+int ekf_batch_observe_logs_diag(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets,
+                                const int64_t *member_frames, const double *poses_dev, void *log_ws, size_t log_ws_bytes,
+                                double *trajectory_dev, double *nis_dev, double *cam_cov_dev);
+
+/* ---- Monte-Carlo replicas of ONE log with detection noise generated on the device.
+ * Noise definition (part of the ABI): replica r, detection d, pose component c < 6 ([tvec | rvec]) gets
+ *     pose[d][c] + sigma[r][c] * g_c(seed, r, d)
+ * where g_0 .. g_5 are standard normals from three Philox4x32-10 calls (Salmon et al., SC 2011, the published constants)
+ * with key (seed_lo, seed_hi) = (seed & 0xffffffff, seed >> 32) and counter (d_lo, d_hi, r, j), j = 0, 1, 2: each call
+ * gives words x0 .. x3, u_a = (((x0 << 32 | x1) >> 11) + 0.5) 2^-53 and u_b likewise from (x2, x3), then
+ *     g_{2j} = sqrt(-2 ln u_a) cos(2 pi u_b),  g_{2j+1} = sqrt(-2 ln u_a) sin(2 pi u_b)
+ * (f64 throughout; evaluated as pose + sigma * (sqrt(..) * cos(..))).  The noise of (r, d) depends on nothing else: not on
+ * how many replicas a call holds nor on which replicas share it.  EKF reads only the tvec; EKF_MODEL_ROTATIONS reads both.
+ * A first sighting is placed from its noisy pose (that pose is the detection).
+ *
+ * ekf_batch_replica_poses: out_dev [R, D, 6] = the poses replicas first_replica .. first_replica + R - 1 consume, from
+ * poses_dev [D, 6] (DEVICE) and sigma [R, 6] (HOST, finite, >= 0), enqueued on `stream`; first_replica + R <= 2^32.
+ * No handle: it is the code ekf_batch_observe_replicas runs. */
+int ekf_batch_replica_poses(const double *poses_dev, int64_t detections, const double *sigma, int32_t replicas, uint64_t seed,
+                            uint32_t first_replica, double *out_dev, void *stream);
+/* bytes of the replica workspace for a log of `detections` and `frames`: B D (48 + 4) + B (F + 1) 8 bytes and change */
+int ekf_batch_replica_workspace_bytes(const ekf_batch *b, int64_t detections, int64_t frames, size_t *bytes);
+/* Member b replays the log as replica first_replica + b, with its own sigma[b] and noise constants:
+ *   lm_index [D], frame_offsets [F+1]   HOST  the log, rules of ekf_batch_observe_logs, checked for every member
+ *   poses_dev [D,6]                     DEVICE the log's poses
+ *   sigma [B,6]                         HOST  finite, >= 0 (sigma = 0: exactly the log's poses)
+ *   ws                                  DEVICE 256-byte aligned, ekf_batch_replica_workspace_bytes(D, F)
+ *   trajectory_dev [B,F,7], nis_dev [B,F], cam_cov_dev [B,F,10,10]   DEVICE or NULL, as ekf_batch_observe_logs_diag
+ * first_replica + B <= 2^32.  Everything is validated on the host before anything is enqueued (EKF_ERR_INVALID /
+ * EKF_ERR_CAPACITY; no member changes).  Then, on the batch's stream: one copy of the log's indices and offsets tiled B
+ * times (member b: frames b F .., detections b D ..), the noise kernel writing the B D noisy poses into ws, and the window
+ * launches of ekf_batch_observe_logs: every member gives the bits of ekf_batch_observe_logs on the poses
+ * ekf_batch_replica_poses returns for its replica.  Returns once the work is enqueued. */
+int ekf_batch_observe_replicas(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets, int64_t frames,
+                               const double *poses_dev, const double *sigma, uint64_t seed, uint32_t first_replica, void *ws,
+                               size_t ws_bytes, double *trajectory_dev, double *nis_dev, double *cam_cov_dev);
 
 const char *ekf_last_error_string(void);
 

@@ -12,6 +12,12 @@ Beside it, the single-filter rate of process_detection_log on member 0's steady 
 per point, printed and appended to profiles/batch/batch_bench.jsonl (--out).
 Kernel times: a separate `rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --members 256` run (the large-map
 ones in profiles/batch/rocprof_large_*.json, the wide-frame ones in profiles/batch/rocprof_wide_*.json).
+--replicas: Monte-Carlo replicas of ONE log (member 0's whole log, bootstrap included) with sigma = 0.01 on the tvec, for
+B in {16, 64, 256, 1024} by default: the rate of EKFBatch.replay_replicas (noise drawn on the device) against
+process_detection_logs on B copies of the log re-noised on the host (numpy draws included in its wall time, and reported
+apart).  Same timing rule: one warm-up call, a reset, one timed call.  --nis / --cam-cov ask both paths for the per-frame
+outputs.  Kernel times: `rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --replicas --members 256
+[--nis --cam-cov]` (profiles/batch/rocprof_replicas_*.json).
 """
 from __future__ import annotations
 
@@ -41,7 +47,8 @@ def split(log, t):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--members", type=int, nargs="*", default=[1, 16, 64, 256, 1024])
+    ap.add_argument("--members", type=int, nargs="*", default=None,
+                    help="default: 1 16 64 256 1024 (--replicas: 16 64 256 1024)")
     ap.add_argument("--model", choices=("ekf", "ekf_rotations"), default="ekf")
     ap.add_argument("--landmarks", type=int, default=None,
                     help="default: 50 (ekf), 24 (ekf_rotations); with --large-maps or wide frames 250 (ekf), 100 (ekf_rotations)")
@@ -50,6 +57,9 @@ def main():
                     help="m ~ U[1, M] (default: 10 for ekf, 8 for ekf_rotations); above 16 / 8 the wide-frame kernel runs")
     ap.add_argument("--steady", type=int, default=500)
     ap.add_argument("--out", default=str(REPO / "profiles" / "batch" / "batch_bench.jsonl"))
+    ap.add_argument("--replicas", action="store_true", help="replay_replicas against host-noised process_detection_logs")
+    ap.add_argument("--nis", action="store_true", help="--replicas: ask for the per-frame NIS")
+    ap.add_argument("--cam-cov", action="store_true", help="--replicas: ask for the per-frame camera covariance")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.batch import EKFBatch
@@ -63,6 +73,9 @@ def main():
     wide = m_hi > (8 if rot else 16)
     n = args.landmarks or ((100 if rot else 250) if args.large_maps or wide else (24 if rot else 50))
     visible = max(m_hi, 8 if rot else 16)
+    if args.replicas:
+        return replicas(args, n, m_hi, visible)
+    args.members = args.members or [1, 16, 64, 256, 1024]
     logs = [split(lg, lg["bootstrap_frames"]) for lg in
             (ragged_log(n, (1, m_hi), args.steady, seed=s, rvec_sigma=0.05 if rot else 0.0)
              for s in range(max(args.members)))]
@@ -102,11 +115,67 @@ def main():
         print(json.dumps(line), flush=True)
         lines.append(line)
         del batch
-    out = Path(args.out)
+    append(args.out, lines)
+
+
+def append(path, lines):
+    out = Path(path)
     out.parent.mkdir(parents=True, exist_ok=True)
     with out.open("a") as fh:
         for line in lines:
             fh.write(json.dumps(line) + "\n")
+
+
+def replicas(args, n, m_hi, visible):
+    import torch
+    from aruco_slam_amd.batch import EKFBatch
+    from aruco_slam_amd.synthetic import ragged_log
+    rot = args.model == "ekf_rotations"
+    log = ragged_log(n, (1, m_hi), args.steady, seed=0, rvec_sigma=0.05 if rot else 0.0)
+    log = {k: log[k] for k in ("ids", "poses", "offsets", "has_detections")}
+    frames, dets = len(log["offsets"]) - 1, int(log["offsets"][-1])
+    sigma = np.array([0.01, 0.01, 0.01, 0.0, 0.0, 0.0])
+    outs = {"nis": args.nis, "cam_cov": args.cam_cov}
+    rng = np.random.default_rng(1)
+    lines = []
+    for B in args.members or [16, 64, 256, 1024]:
+        batch = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model,
+                         large_maps=True if args.large_maps else None)
+
+        def host_logs():
+            return [dict(log, poses=log["poses"] + sigma * rng.standard_normal(log["poses"].shape)) for _ in range(B)]
+
+        batch.replay_replicas(log, sigma, 1, **outs)          # warm-up
+        batch.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        batch.replay_replicas(log, sigma, 2, **outs)
+        wall_rep = time.perf_counter() - t0
+        assert batch.status() == [0] * B
+        batch.reset()
+        kw = outs if args.nis or args.cam_cov else {}
+        batch.process_detection_logs(host_logs(), **kw)      # warm-up
+        batch.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        noisy = host_logs()
+        t1 = time.perf_counter()
+        batch.process_detection_logs(noisy, **kw)
+        wall_host = time.perf_counter() - t0
+        assert batch.status() == [0] * B
+        line = {"tool": "batch_bench", "replicas": True, **({"model": args.model} if rot else {}),
+                **({"large_maps": True} if args.large_maps else {}),
+                **({"wide_frames": True} if batch.wide_frames else {}), "members": B, "n": n, "m": [1, m_hi],
+                "frames": frames, "detections": dets, "nis": args.nis, "cam_cov": args.cam_cov,
+                "replay_replicas_wall_s": round(wall_rep, 6),
+                "replay_replicas_frames_per_s": round(B * frames / wall_rep, 1),
+                "host_noised_wall_s": round(wall_host, 6), "host_noise_draw_s": round(t1 - t0, 6),
+                "host_noised_frames_per_s": round(B * frames / wall_host, 1),
+                "speedup": round(wall_host / wall_rep, 2)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del batch
+    append(args.out, lines)
 
 
 if __name__ == "__main__":

@@ -18,6 +18,11 @@ Monte-Carlo studies need no host-side re-noising: ``replay_replicas`` replays ON
 replica whose detection noise the device draws (``csrc/ekf_batch_replicas.hip``; ``replica_poses`` returns exactly the
 poses a replica consumed).  Runs and sweeps are judged by the filter's own statistics: with ``nis`` / ``cam_cov`` both replay
 calls also return every frame's normalised innovation squared and camera covariance P[0:10, 0:10].
+
+Outliers (IPPE's flipped poses, mis-decoded ids) are kept out by the per-detection chi-square gate: ``gate`` / ``set_gate``
+make every member reject the detections whose own Mahalanobis distance d^2 = r^T S_d^-1 r exceeds its threshold before the
+frame is updated, and ``mahal=True`` returns every detection's d^2, gate or no gate (``ekf_batch_set_gate`` in
+``include/ekf_slam_hip.h`` has the exact semantics).
 """
 from __future__ import annotations
 
@@ -79,6 +84,51 @@ class ReplicaReplay(NamedTuple):
     nis: np.ndarray | None
     dof: np.ndarray
     cam_cov: np.ndarray | None
+
+
+class GatedBatchReplay(NamedTuple):
+    """``process_detection_logs`` with ``mahal=True`` or a gate set: ``BatchReplay``'s fields (``dof[b]`` counts the
+    surviving detections only), then per member ``mahal[b]`` [D_b], every detection's d^2 aligned with the log's own
+    detections (0: exempt first sighting; NaN: not tested, dropped by the planner included), and ``rejected[b]`` [D_b]
+    bool, ``mahal[b] > gate[b]``."""
+    trajectory: list
+    nis: list | None
+    dof: list
+    cam_cov: list | None
+    mahal: list
+    rejected: list
+
+
+class GatedReplicaReplay(NamedTuple):
+    """``replay_replicas`` with ``mahal=True`` or a gate set: ``ReplicaReplay``'s fields with ``dof`` [B, F] counting each
+    member's surviving detections, then ``mahal`` [B, D] and ``rejected`` [B, D] as in ``GatedBatchReplay``."""
+    trajectory: np.ndarray
+    nis: np.ndarray | None
+    dof: np.ndarray
+    cam_cov: np.ndarray | None
+    mahal: np.ndarray
+    rejected: np.ndarray
+
+
+def gate_array(gate, members: int):
+    """``gate`` (None, a scalar or [members]) as None or a contiguous [members] array; every entry must be > 0 (``inf``:
+    that member's gate is off); ``ValueError`` otherwise."""
+    if gate is None:
+        return None
+    g = np.asarray(gate, dtype=np.float64)
+    if g.ndim == 0:
+        g = np.broadcast_to(g, (members,))
+    elif g.shape != (members,):
+        raise ValueError(f"gate must be a scalar or [{members}], got shape {g.shape}")
+    if not (g > 0).all():
+        raise ValueError("gate must be > 0 (inf: off) and not NaN")
+    return np.ascontiguousarray(g)
+
+
+def _surviving_dof(rd: int, offsets: np.ndarray, rejected: np.ndarray) -> np.ndarray:
+    """Rows per frame over the detections that were not rejected (offsets [F+1] into rejected [D])."""
+    kept = np.concatenate([np.zeros(1, np.int64), np.cumsum(~rejected, dtype=np.int64)])
+    return rd * (kept[offsets[1:]] - kept[offsets[:-1]])
 
 
 def replica_sigma(sigma, replicas: int) -> np.ndarray:
@@ -151,12 +201,16 @@ class EKFBatch:
     ``initial_camera_pose``: [10] for all or [B, 10]; ``quat_update``: None for the model's convention (``"as_written"`` for
     ``EKF``; ``EKF_Rotations`` has only ``"scalar_first"``); ``noise``: dict of scalars or length-B arrays keyed by
     ``NOISE_KEYS`` (missing keys: the model's constants); ``large_maps``: see ``use_large_maps`` (the choice is kept in
-    ``self.large_maps``); ``wide_frames``: see ``use_wide_frames`` (kept in ``self.wide_frames``)."""
+    ``self.large_maps``); ``wide_frames``: see ``use_wide_frames`` (kept in ``self.wide_frames``); ``gate``: see
+    ``set_gate`` (kept in ``self.gate``)."""
+
+    gate = None        # [B] chi-square gate per member, or None: no gate (set_gate)
 
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
                  quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf",
-                 large_maps: bool | None = None, wide_frames: bool | None = None) -> None:
+                 large_maps: bool | None = None, wide_frames: bool | None = None, gate=None) -> None:
         import torch
+        gate = gate_array(gate, int(members))
         if model not in MODELS:
             raise ValueError(f"model must be one of {sorted(MODELS)}, got {model!r}")
         if quat_update is None:
@@ -221,6 +275,8 @@ class EKFBatch:
         self.cfg = cfg
         self.landmarks = [{} for _ in range(self.members)]
         self.num_landmarks = [0] * self.members
+        self.gate = None
+        self.set_gate(gate)
         self.reset()
 
     def _check(self, rc):
@@ -238,6 +294,27 @@ class EKFBatch:
         except Exception:
             pass
 
+    def set_gate(self, gate) -> None:
+        """The chi-square gate of every member: ``None`` (no gate), a scalar or [B]; ``inf`` switches one member's gate
+        off.  Persistent like the noise constants, so a threshold sweep is one call.  Before a frame is updated, every
+        detection's own d^2 = r^T S_d^-1 r (r = z - h, S_d = H_d (P+Q) H_d^T + R I, after the frame's first sightings) is
+        compared with the member's gate and the frame runs on the survivors only; first sightings are exempt.  The usual
+        thresholds are chi^2 quantiles of the detection's row count: 3 dof for ``EKF`` (95 %: 7.815, 99 %: 11.345, 99.9 %:
+        16.266), 7 dof for ``EKF_Rotations`` (14.067, 18.475, 24.322; approximate, as for NIS: the unit-quaternion rows
+        are not independent).  ``mahal=True`` on a replay call returns the distances with the gate off, to choose a
+        threshold from data.  A bad gate raises ``ValueError`` and nothing changes."""
+        g = gate_array(gate, self.members)
+        self._check(self.lib.ekf_batch_set_gate(self.h, _dptr(g) if g is not None else None))
+        self.gate = g
+
+    def _rejected(self, mahal: np.ndarray, member) -> np.ndarray:
+        """``mahal > gate`` of the detections' members (NaN and 0 are never rejected)."""
+        gate = self.gate
+        if gate is None:
+            return np.zeros(mahal.shape, dtype=bool)
+        with np.errstate(invalid="ignore"):
+            return mahal > gate[member]
+
     def _member(self, b) -> int:
         b = int(b)
         if not 0 <= b < self.members:
@@ -245,7 +322,7 @@ class EKFBatch:
         return b
 
     # -- replay ------------------------------------------------------------------------------------------------------
-    def process_detection_logs(self, logs, *, nis: bool = False, cam_cov: bool = False):
+    def process_detection_logs(self, logs, *, nis: bool = False, cam_cov: bool = False, mahal: bool = False):
         """One log per member (``None``: no log), each a dict of the replay layout ``ids [D]``, ``poses [D,6]``,
         ``offsets [F+1]`` and optionally ``has_detections [F]``.  Returns the camera pose ``state[0:7]`` after every frame,
         one ``(F_b, 7)`` array per member.  A malformed log raises ``ValueError``, a log that needs more landmarks or
@@ -254,7 +331,10 @@ class EKFBatch:
         With ``nis`` or ``cam_cov`` it returns a ``BatchReplay`` of per-member lists instead: the trajectories, each
         frame's normalised innovation squared (z-h)^T S^-1 (z-h) (0 for a frame that is not stepped), its row count
         ``dof`` (the NIS's chi^2 degrees of freedom; approximate for EKF_Rotations, whose unit-quaternion rows are not
-        independent) and P[0:10, 0:10] after it.  A member's failing frame and every later one give NaN."""
+        independent) and P[0:10, 0:10] after it.  A member's failing frame and every later one give NaN.
+        With ``mahal``, or with a gate set (``set_gate``), it returns a ``GatedBatchReplay``: the same fields with ``dof``
+        over the surviving detections, every detection's d^2 and whether the gate rejected it."""
+        gated = mahal or self.gate is not None
         if len(logs) != self.members:
             raise ValueError(f"need {self.members} logs (None for a member without one), got {len(logs)}")
         plans, index, offsets, frames, poses = [], [], [], [0], []
@@ -278,13 +358,33 @@ class EKFBatch:
         index = np.concatenate(index).astype(np.int32) if index else np.zeros(0, np.int32)
         offsets = np.concatenate([np.zeros(1, np.int64)] + offsets).astype(np.int64)
         poses = np.ascontiguousarray(np.concatenate(poses) if poses else np.zeros((0, 6)))
-        if nis or cam_cov:
+        if gated:
+            traj, nis_v, cov_v, mahal_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses,
+                                                               nis=nis, cam_cov=cam_cov, mahal=True)
+        elif nis or cam_cov:
             traj, nis_v, cov_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses, nis=nis,
                                                       cam_cov=cam_cov)
         else:
             traj = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses)
         self._adopt_plans(plans)
         split = [slice(frames[b], frames[b + 1]) for b in range(self.members)]
+        if gated:
+            member = np.repeat(np.arange(self.members), np.diff(offsets[np.asarray(frames)]))
+            rej_v = self._rejected(mahal_v, member)
+            dof = _surviving_dof(RD[self.model], offsets, rej_v)
+            mahal_l, rej_l = [], []
+            for b, plan in enumerate(plans):      # back to the log's own detections (the planner's drops: NaN)
+                keep = np.zeros(0, dtype=bool) if plan is None else np.asarray(plan.keep, dtype=bool)
+                dsl = slice(offsets[frames[b]], offsets[frames[b + 1]])
+                full = np.full(keep.shape[0], np.nan)
+                full[keep] = mahal_v[dsl]
+                rej = np.zeros(keep.shape[0], dtype=bool)
+                rej[keep] = rej_v[dsl]
+                mahal_l.append(full)
+                rej_l.append(rej)
+            return GatedBatchReplay([traj[sl] for sl in split], [nis_v[sl] for sl in split] if nis else None,
+                                    [dof[sl] for sl in split], [cov_v[sl] for sl in split] if cam_cov else None,
+                                    mahal_l, rej_l)
         if not (nis or cam_cov):
             return [traj[sl] for sl in split]
         dof = RD[self.model] * np.diff(offsets)
@@ -300,7 +400,7 @@ class EKFBatch:
             self.num_landmarks[b] = int(counts[b])
 
     def replay_replicas(self, log, sigma, seed: int, *, first_replica: int = 0, nis: bool = False,
-                        cam_cov: bool = False) -> ReplicaReplay:
+                        cam_cov: bool = False, mahal: bool = False):
         """Monte-Carlo replicas of ONE log: member b replays ``log`` (the layout of ``process_detection_logs``) as replica
         ``first_replica + b``, every detection's pose re-noised on the device as ``pose + sigma[b] * g`` with the
         standard normals g of ``replica_poses`` (Philox4x32-10 / Box-Muller, defined in ``include/ekf_slam_hip.h``; a
@@ -312,7 +412,10 @@ class EKFBatch:
         detections counted) and, if asked, ``nis`` [B, F] and ``cam_cov`` [B, F, 10, 10] as in ``process_detection_logs``.
         Mean NIS over replicas against the chi^2(dof) bounds tunes the noise constants without ground truth; for
         EKF_Rotations the unit-quaternion rows make that chi^2 reading approximate.  Bad arguments raise before anything
-        runs, and no member changes."""
+        runs, and no member changes.
+        With ``mahal``, or with a gate set (``set_gate``), it returns a ``GatedReplicaReplay`` instead: ``dof`` [B, F] over
+        each member's surviving detections, ``mahal`` [B, D] and ``rejected`` [B, D] aligned with the log's detections."""
+        gated = mahal or self.gate is not None
         sig = replica_sigma(sigma, self.members)
         r0 = _replica_range(first_replica, self.members)
         seed = int(seed)
@@ -338,20 +441,40 @@ class EKFBatch:
             traj = torch.empty((B, F, 7), dtype=torch.float64, device=self.device)
             nis_t = torch.empty((B, F), dtype=torch.float64, device=self.device) if nis else None
             cov_t = torch.empty((B, F, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
+            mahal_t = torch.empty((B, D), dtype=torch.float64, device=self.device) if gated else None
             ptr = (lambda t: t.data_ptr() if t is not None and F else None)
-            self._check(self.lib.ekf_batch_observe_replicas(self.h, _iptr(idx), _lptr(fo), F, ptr(poses_t) if D else None,
-                                                            _dptr(sig), seed, r0, ws.data_ptr(), nbytes.value, ptr(traj),
-                                                            ptr(nis_t), ptr(cov_t)))
+            if gated:
+                self._check(self.lib.ekf_batch_observe_replicas_gated(
+                    self.h, _iptr(idx), _lptr(fo), F, ptr(poses_t) if D else None, _dptr(sig), seed, r0, ws.data_ptr(),
+                    nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t), mahal_t.data_ptr() if D else None))
+            else:
+                self._check(self.lib.ekf_batch_observe_replicas(self.h, _iptr(idx), _lptr(fo), F,
+                                                                ptr(poses_t) if D else None, _dptr(sig), seed, r0,
+                                                                ws.data_ptr(), nbytes.value, ptr(traj), ptr(nis_t),
+                                                                ptr(cov_t)))
             self.stream.synchronize()
         self._adopt_plans([plan] * B)
+        if gated:
+            keep = np.asarray(plan.keep, dtype=bool)
+            mahal_v = mahal_t.cpu().numpy()
+            rej_v = self._rejected(mahal_v, np.arange(B)[:, None])
+            full = np.full((B, keep.shape[0]), np.nan)
+            full[:, keep] = mahal_v
+            rej = np.zeros((B, keep.shape[0]), dtype=bool)
+            rej[:, keep] = rej_v
+            dof = np.stack([_surviving_dof(RD[self.model], fo, r) for r in rej_v]) if B else np.zeros((0, F), np.int64)
+            return GatedReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, dof,
+                                      cov_t.cpu().numpy() if cam_cov else None, full, rej)
         return ReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None,
                              RD[self.model] * np.diff(fo), cov_t.cpu().numpy() if cam_cov else None)
 
-    def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False):
+    def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False,
+                        mahal: bool = False):
         """The C call behind ``process_detection_logs`` (landmark indices already assigned; ``landmarks`` is not
         touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1], poses [D,6] on the host.  Returns the
         trajectory [Ftot, 7]; with ``nis`` or ``cam_cov`` the tuple (trajectory, nis [Ftot] or None, cam_cov [Ftot, 10, 10]
-        or None)."""
+        or None); with ``mahal`` the tuple (trajectory, nis or None, cam_cov or None, mahal [D]).  A gate that is set acts
+        on every call, whatever it returns."""
         torch = self._torch
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
         fo = np.ascontiguousarray(frame_offsets, dtype=np.int64).reshape(-1)
@@ -370,7 +493,7 @@ class EKFBatch:
             poses_t = torch.from_numpy(poses).to(self.device)
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
             traj = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
-            if not (nis or cam_cov):
+            if not (nis or cam_cov or mahal):
                 self._check(self.lib.ekf_batch_observe_logs(self.h, _iptr(idx), _lptr(fo), _lptr(mf),
                                                             poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
                                                             nbytes.value, traj.data_ptr() if frames else None))
@@ -379,6 +502,14 @@ class EKFBatch:
             nis_t = torch.empty((frames,), dtype=torch.float64, device=self.device) if nis else None
             cov_t = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
             ptr = (lambda t: t.data_ptr() if t is not None and frames else None)
+            if mahal:
+                mahal_t = torch.empty((idx.shape[0],), dtype=torch.float64, device=self.device)
+                self._check(self.lib.ekf_batch_observe_logs_gated(
+                    self.h, _iptr(idx), _lptr(fo), _lptr(mf), poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
+                    nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t), mahal_t.data_ptr() if idx.shape[0] else None))
+                self.stream.synchronize()
+                return (traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None,
+                        cov_t.cpu().numpy() if cam_cov else None, mahal_t.cpu().numpy())
             self._check(self.lib.ekf_batch_observe_logs_diag(self.h, _iptr(idx), _lptr(fo), _lptr(mf),
                                                              poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
                                                              nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t)))

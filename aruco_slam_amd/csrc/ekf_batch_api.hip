@@ -21,6 +21,7 @@ struct ekf_batch {
     std::vector<double> noise;      // [B][6] host copy (initial_camera_uncertainty is used on the host, by reset)
     std::vector<int32_t> nlm;       // [B] host copy, refreshed after every call
     std::vector<int32_t> status;    // [B]
+    std::vector<double> gate;       // [B] chi^2 gate per member (+inf: off); empty: no gate set (ekf_batch_set_gate)
     PinnedBuffer pin;               // pinned staging of a call's indices and offsets
 };
 
@@ -53,17 +54,20 @@ BatchLayout batch_layout(const ekf_config& c, int32_t members) {
     return {status, nlm, wm, w.end};
 }
 
-// log workspace: [landmark indices [D] | frame offsets [Ftot+1] | member frame offsets [B+1]]
+// log workspace: [landmark indices [D] | frame offsets [Ftot+1] | member frame offsets [B+1] | with a gate set: gates [B]]
 struct BatchLogLayout {
-    size_t frames, members, total;
+    size_t frames, members, gate, total;
 };
 
-BatchLogLayout batch_log_layout(int64_t D, int64_t F, int32_t B) {
+BatchLogLayout batch_log_layout(int64_t D, int64_t F, int32_t B, bool gated) {
     Carve w;
     w.take((size_t)D * 4);
     const size_t frames = w.take((size_t)(F + 1) * 8), members = w.take((size_t)(B + 1) * 8);
-    return {frames, members, w.end};
+    const size_t gate = w.take(gated ? (size_t)B * 8 : 0);
+    return {frames, members, gate, w.end};
 }
+
+bool batch_gated(const ekf_batch* b) { return !b->gate.empty(); }
 
 int check_batch_config(const ekf_config* c, int32_t members) {
     if (!c) return fail(EKF_ERR_INVALID, "config is NULL");
@@ -161,8 +165,8 @@ struct BatchReplicaLayout {
     size_t total;
 };
 
-BatchReplicaLayout batch_replica_layout(int64_t D, int64_t F, int32_t B) {
-    const BatchLogLayout log = batch_log_layout((int64_t)B * D, (int64_t)B * F, B);
+BatchReplicaLayout batch_replica_layout(int64_t D, int64_t F, int32_t B, bool gated) {
+    const BatchLogLayout log = batch_log_layout((int64_t)B * D, (int64_t)B * F, B, gated);
     return {log.total, log, log.total + align256((size_t)B * D * 6 * 8)};
 }
 
@@ -170,7 +174,7 @@ BatchReplicaLayout batch_replica_layout(int64_t D, int64_t F, int32_t B) {
 // [w, w + window) of its log per launch, state carried in HBM.  LDS is sized for the widest frame and the largest map of
 // the call (a layout choice only: the arithmetic is the same)
 int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, const BatchShape& sh, const double* poses_dev,
-                      double* trajectory_dev, double* nis_dev, double* cam_cov_dev) {
+                      double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev) {
     const int32_t B = b->members;
     const BatchLayout L = batch_layout(b->cfg, B);
     EkfBatchWindow a{};
@@ -188,6 +192,8 @@ int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, co
     a.nis = nis_dev;
     a.cam_cov = cam_cov_dev;
     a.quat_mode = b->cfg.quat_mode;
+    a.gate = batch_gated(b) ? reinterpret_cast<const double*>(ws + LL.gate) : nullptr;
+    a.mahal = mahal_dev;
     const int rd = batch_rd(b->cfg);
     a.kmax = std::max(rd, rd * sh.widest);
     a.lda = (int32_t)round_up(batch_lmd(b->cfg) * sh.n_max + EKF_CAM + 1, 4);
@@ -282,6 +288,21 @@ int ekf_batch_bind_buffers(ekf_batch* b, double* cov_dev, int64_t ld, double* st
     std::vector<double> poses((size_t)b->members * 10, 0.0);
     for (int32_t m = 0; m < b->members; ++m) poses[(size_t)m * 10 + 3] = 1.0;
     return ekf_batch_reset(b, -1, poses.data());
+}
+
+// gate [B]: finite and > 0, or +inf (that member's gate is off); NULL: no gate.  Persistent; nothing changes on error.
+int ekf_batch_set_gate(ekf_batch* b, const double* gate) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (gate)
+        for (int32_t m = 0; m < b->members; ++m)
+            if (!(gate[m] > 0.0)) return fail(EKF_ERR_INVALID, "a gate must be > 0 (+inf: off) and not NaN");
+    // (host copy only: every observe call stages the gates with its indices, so nothing on the stream reads this)
+    if (gate)
+        b->gate.assign(gate, gate + b->members);
+    else
+        b->gate.clear();
+    return EKF_OK;
 }
 
 int ekf_batch_set_noise(ekf_batch* b, const double* noise) {
@@ -385,19 +406,26 @@ int ekf_batch_status(ekf_batch* b, int32_t* out) {
 int ekf_batch_log_workspace_bytes(const ekf_batch* b, int64_t detections, int64_t frames, size_t* bytes) {
     if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
     if (!bytes || detections < 0 || frames < 0) return fail(EKF_ERR_INVALID, "bad log size request");
-    *bytes = batch_log_layout(detections, frames, b->members).total;
+    *bytes = batch_log_layout(detections, frames, b->members, batch_gated(b)).total;
     return EKF_OK;
 }
 
 int ekf_batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, const int64_t* member_frames,
                            const double* poses_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev) {
-    return ekf_batch_observe_logs_diag(b, lm_index, frame_offsets, member_frames, poses_dev, log_ws, log_ws_bytes,
-                                       trajectory_dev, nullptr, nullptr);
+    return ekf_batch_observe_logs_gated(b, lm_index, frame_offsets, member_frames, poses_dev, log_ws, log_ws_bytes,
+                                        trajectory_dev, nullptr, nullptr, nullptr);
 }
 
 int ekf_batch_observe_logs_diag(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets,
                                 const int64_t* member_frames, const double* poses_dev, void* log_ws, size_t log_ws_bytes,
                                 double* trajectory_dev, double* nis_dev, double* cam_cov_dev) {
+    return ekf_batch_observe_logs_gated(b, lm_index, frame_offsets, member_frames, poses_dev, log_ws, log_ws_bytes,
+                                        trajectory_dev, nis_dev, cam_cov_dev, nullptr);
+}
+
+int ekf_batch_observe_logs_gated(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets,
+                                 const int64_t* member_frames, const double* poses_dev, void* log_ws, size_t log_ws_bytes,
+                                 double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev) {
     int rc = batch_ready(b);
     if (rc) return rc;
     // ---- validation on the host: nothing is enqueued before every log has passed
@@ -408,7 +436,7 @@ int ekf_batch_observe_logs_diag(ekf_batch* b, const int32_t* lm_index, const int
     if ((rc = check_offsets(frame_offsets, F, "frame_offsets"))) return rc;
     const int64_t D = frame_offsets[F];
     if (D > 0 && (!lm_index || !poses_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
-    const BatchLogLayout LL = batch_log_layout(D, F, B);
+    const BatchLogLayout LL = batch_log_layout(D, F, B, batch_gated(b));
     if ((rc = check_device_buffers({log_ws}, log_ws_bytes, LL.total, "ekf_batch_log_workspace_bytes"))) return rc;
     if ((rc = batch_refresh(b))) return rc;      // (landmark counts as the previous call left them)
     BatchShape sh;
@@ -426,9 +454,10 @@ int ekf_batch_observe_logs_diag(ekf_batch* b, const int32_t* lm_index, const int
     if (D > 0) std::memcpy(b->pin.get(), lm_index, (size_t)D * 4);
     std::memcpy(b->pin.get() + LL.frames, frame_offsets, (size_t)(F + 1) * 8);
     std::memcpy(b->pin.get() + LL.members, member_frames, (size_t)(B + 1) * 8);
+    if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
     char* ws = static_cast<char*>(log_ws);
     HIP_TRY(hipMemcpyAsync(ws, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
-    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev);
+    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
 }
 
 int ekf_batch_replica_poses(const double* poses_dev, int64_t detections, const double* sigma, int32_t replicas,
@@ -451,13 +480,21 @@ int ekf_batch_replica_poses(const double* poses_dev, int64_t detections, const d
 int ekf_batch_replica_workspace_bytes(const ekf_batch* b, int64_t detections, int64_t frames, size_t* bytes) {
     if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
     if (!bytes || detections < 0 || frames < 0) return fail(EKF_ERR_INVALID, "bad log size request");
-    *bytes = batch_replica_layout(detections, frames, b->members).total;
+    *bytes = batch_replica_layout(detections, frames, b->members, batch_gated(b)).total;
     return EKF_OK;
 }
 
 int ekf_batch_observe_replicas(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, int64_t frames,
                                const double* poses_dev, const double* sigma, uint64_t seed, uint32_t first_replica,
                                void* ws, size_t ws_bytes, double* trajectory_dev, double* nis_dev, double* cam_cov_dev) {
+    return ekf_batch_observe_replicas_gated(b, lm_index, frame_offsets, frames, poses_dev, sigma, seed, first_replica, ws,
+                                            ws_bytes, trajectory_dev, nis_dev, cam_cov_dev, nullptr);
+}
+
+int ekf_batch_observe_replicas_gated(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, int64_t frames,
+                                     const double* poses_dev, const double* sigma, uint64_t seed, uint32_t first_replica,
+                                     void* ws, size_t ws_bytes, double* trajectory_dev, double* nis_dev,
+                                     double* cam_cov_dev, double* mahal_dev) {
     int rc = batch_ready(b);
     if (rc) return rc;
     // ---- validation on the host: nothing is enqueued before the log has passed for every member
@@ -471,7 +508,7 @@ int ekf_batch_observe_replicas(ekf_batch* b, const int32_t* lm_index, const int6
     if ((rc = check_sigma(sigma, B))) return rc;
     if ((uint64_t)first_replica + (uint64_t)B > (1ull << 32))
         return fail(EKF_ERR_INVALID, "first_replica + members must not exceed 2^32");
-    const BatchReplicaLayout RL = batch_replica_layout(D, frames, B);
+    const BatchReplicaLayout RL = batch_replica_layout(D, frames, B, batch_gated(b));
     if ((rc = check_device_buffers({ws}, ws_bytes, RL.total, "ekf_batch_replica_workspace_bytes"))) return rc;
     if ((rc = batch_refresh(b))) return rc;
     BatchShape sh;
@@ -501,6 +538,7 @@ int ekf_batch_observe_replicas(ekf_batch* b, const int32_t* lm_index, const int6
     }
     fo[Ft] = Dt;
     mf[B] = Ft;
+    if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
     char* w = static_cast<char*>(ws);
     HIP_TRY(hipMemcpyAsync(w, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
     double* noisy = reinterpret_cast<double*>(w + RL.poses);
@@ -508,7 +546,7 @@ int ekf_batch_observe_replicas(ekf_batch* b, const int32_t* lm_index, const int6
         ekf_launch_replica_poses(poses_dev, D, sigma, B, seed, first_replica, noisy, b->stream);
         HIP_TRY(hipGetLastError());
     }
-    return batch_run_windows(b, w, LL, sh, noisy, trajectory_dev, nis_dev, cam_cov_dev);
+    return batch_run_windows(b, w, LL, sh, noisy, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
 }
 
 }  // extern "C"

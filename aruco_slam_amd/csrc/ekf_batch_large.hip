@@ -61,21 +61,23 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_large_window(cons
     const double lm_unc = nzb[1];
     int n = a.nlm[b];
     bool failed = a.status[b] != 0;
+    const bool gated = a.mahal || (a.gate && a.gate[b] < __builtin_inf());
     if (tid == 0) *flag = 0;
 
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t d0 = a.frame_offsets[t];
-        const int m = (int)(a.frame_offsets[t + 1] - d0);
-        if (failed || m == 0) {      // not stepped: the rows repeat the state (NaN once the member has failed)
+        const int mf = (int)(a.frame_offsets[t + 1] - d0);
+        if (failed || mf == 0) {      // not stepped: the rows repeat the state (NaN once the member has failed)
             ekf_batch_rows_unstepped(a, t, tid, st, P, failed);
+            ekf_batch_mahal_untested(a, d0, mf, tid, nt);
             continue;
         }
         const int32_t* idx = a.lm_index + d0;
         const double* pose = a.poses + 6 * d0;
         // first sightings, all with the camera state the previous frame left, before predict
         const int n0 = n;
-        for (int j = 0; j < m; ++j) n = max(n, idx[j] + 1);
-        if (tid < m && idx[tid] >= n0) {
+        for (int j = 0; j < mf; ++j) n = max(n, idx[j] + 1);
+        if (tid < mf && idx[tid] >= n0) {
             bool first = true;
             for (int e = 0; e < tid; ++e) first = first && idx[e] != idx[tid];
             if (first) {
@@ -85,11 +87,24 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_large_window(cons
                     ekf_add_marker_pose(P, ld, st, LMD * n0 + EKF_CAM, idx[tid] - n0, pose + 6 * tid, nullptr, lm_unc);
             }
         }
-        const int N = LMD * n + EKF_CAM, k = RD * m, kp = (k + 3) & ~3;
+        const int N = LMD * n + EKF_CAM;
         __syncthreads();
+        // the gate: the frame runs on the m detections that stay, in log order (mask: which ones)
+        int m = mf;
+        uint64_t mask = ~0ull;
+        if (gated) {
+            mask = ekf_batch_gate<MODEL>(a, b, d0, mf, n0, N, tid, nt, st, P, ld, nz, R, flag + 1);
+            m = __popcll(mask);
+            if (m == 0) {      // no survivor: an empty frame
+                ekf_batch_rows_unstepped(a, t, tid, st, P, false);
+                continue;
+            }
+        }
+        const int k = RD * m, kp = (k + 3) & ~3;
         // h, dh and y = z - h
         if (tid < m) {
-            const int c0 = EKF_CAM + LMD * idx[tid];
+            const int src = gated ? ekf_batch_survivor(mask, tid) : tid;
+            const int c0 = EKF_CAM + LMD * idx[src];
             col0[tid] = c0;
             double cam[EKF_CAM], lm[LMD], h[RD], z[RD];
             for (int q = 0; q < EKF_CAM; ++q) cam[q] = st[q];
@@ -99,10 +114,10 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_large_window(cons
                 ekf_measure(cam, lm, h, Jt);
                 for (int r = 0; r < 3; ++r)
                     for (int s = 0; s < EKF_JCOLS; ++s) J[(3 * tid + r) * EKF_JCOLS + s] = Jt[r][s];
-                for (int r = 0; r < 3; ++r) z[r] = pose[6 * tid + r];
+                for (int r = 0; r < 3; ++r) z[r] = pose[6 * src + r];
             } else {
                 ekf_measure_rot(cam, lm, h, reinterpret_cast<double(*)[JC]>(J + (size_t)RD * tid * JC));
-                ekf_pose_z(pose + 6 * tid, RD, z);
+                ekf_pose_z(pose + 6 * src, RD, z);
             }
             for (int r = 0; r < RD; ++r) y[RD * tid + r] = z[r] - h[r];
         }

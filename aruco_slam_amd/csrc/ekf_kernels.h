@@ -212,6 +212,8 @@ struct EkfBatchWindow {
     int32_t quat_mode;              // (EKF; EKF_Rotations is scalar-first)
     int32_t window_first, window_frames;
     int32_t kmax, lda;              // LDS layout: rows of A / W, row length of A / W (> N; column N holds the residual)
+    const double* gate;             // [B] or null: chi^2 gate on every detection's own d^2 (+inf: off); ekf_batch_gate
+    double* mahal;                  // [D] or null: d^2 per detection (0: exempt first sighting, NaN: not tested)
 };
 // dynamic LDS of one launch (C linkage: the tests read them)
 extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);

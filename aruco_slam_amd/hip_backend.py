@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "ekf_batch_reset", "ekf_batch_set_member", "ekf_batch_get_member", "ekf_batch_num_landmarks", "ekf_batch_status",
     "ekf_batch_log_workspace_bytes", "ekf_batch_observe_logs", "ekf_batch_observe_logs_diag", "ekf_batch_replica_poses",
     "ekf_batch_replica_workspace_bytes", "ekf_batch_observe_replicas",
+    "ekf_batch_set_gate", "ekf_batch_observe_logs_gated", "ekf_batch_observe_replicas_gated",
 )
 
 
@@ -123,6 +124,11 @@ def load_library(path: str | Path | None = None):
         "ekf_batch_replica_workspace_bytes": [vp, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)],
         "ekf_batch_observe_replicas": [vp, ip, C.POINTER(C.c_int64), C.c_int64, vp, dp, C.c_uint64, C.c_uint32, vp,
                                        C.c_size_t, vp, vp, vp],
+        "ekf_batch_set_gate": [vp, dp],
+        "ekf_batch_observe_logs_gated": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, vp, C.c_size_t, vp, vp,
+                                         vp, vp],
+        "ekf_batch_observe_replicas_gated": [vp, ip, C.POINTER(C.c_int64), C.c_int64, vp, dp, C.c_uint64, C.c_uint32, vp,
+                                             C.c_size_t, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -380,6 +380,45 @@ int ekf_batch_observe_replicas(ekf_batch *b, const int32_t *lm_index, const int6
                                const double *poses_dev, const double *sigma, uint64_t seed, uint32_t first_replica, void *ws,
                                size_t ws_bytes, double *trajectory_dev, double *nis_dev, double *cam_cov_dev);
 
+/* ---- Per-detection chi-square gate (individual compatibility) and Mahalanobis distance output.
+ * Semantics (part of the ABI).  Member b has a constant gate[b]: +inf, or no gate set, is off; otherwise finite and > 0.
+ * For every detection d of a frame that would be stepped, AFTER the frame's first sightings are added and BEFORE anything
+ * else of the frame (rd = 3: EKF, 7: EKF_MODEL_ROTATIONS):
+ *   1. r_d = z_d - h_d(x);
+ *   2. S_d = H_d (P+Q) H_d^T + r_uncertainty I  [rd, rd], with P the covariance the previous frame left plus this frame's
+ *      first sightings: the diagonal block the joint S would have, independent of the other detections;
+ *   3. S_d = L_d L_d^T and d^2_d = |L_d^-1 r_d|^2, by ONE device routine of fixed operation order (ascending fma chains):
+ *      every window kernel gives the same bits for it;
+ *   4. a detection that is the first occurrence of a landmark first sighted in this frame is exempt: d^2 = 0 is reported
+ *      and it is never rejected (its z = h by construction);
+ *   5. a detection is rejected iff every pivot of S_d was positive and finite and d^2 > gate[b]; after a failed pivot the
+ *      detection is kept, its distance is NaN, and the joint factorisation fails as it does without a gate;
+ *   6. the frame runs on the surviving detections, in log order: state, P, landmark count, trajectory, nis and cam_cov are
+ *      bit for bit those of replaying, with the gate off, the log from which the rejected detections have been deleted
+ *      (with EKF_FLAG_BATCH_WIDE_FRAMES the blocks of 16 / 8 detections are formed from the survivors).  A frame with no
+ *      survivor is not stepped (no predict, its rows repeat, nis = 0), exactly like a frame without detections;
+ *   7. nis is over the survivors: its degrees of freedom are rd times their number.
+ * chi^2 quantiles users want for gate: 3 dof (EKF) 7.815 (95 %), 11.345 (99 %), 16.266 (99.9 %); 7 dof
+ * (EKF_MODEL_ROTATIONS, approximate: the unit-quaternion rows are not independent) 14.067, 18.475, 24.322.
+ *
+ * ekf_batch_set_gate: gate [B] HOST, or NULL = no gate.  Persistent like ekf_batch_set_noise and honoured by every
+ * observe call of the batch; NaN, <= 0 or -inf gives EKF_ERR_INVALID and nothing changes.  While a gate is set the log and
+ * replica workspaces hold the B gates too (8 B bytes and change more): size them after setting the gate.
+ * The ..._gated calls are ekf_batch_observe_logs_diag / ekf_batch_observe_replicas with one more nullable output:
+ *   mahal_dev [D] (logs) or [B,D] (replicas)  DEVICE  d^2 of every tested detection, indexed like lm_index; 0 for an exempt
+ *       detection; NaN after a failed pivot, for every frame AFTER a member's failing frame (the failing frame keeps the
+ *       values that were computed) and for frames not stepped for other reasons.  It may be requested with the gate off:
+ *       the distances are reported and nothing is rejected.  rejected = mahal > gate[b].
+ * With no gate set and mahal_dev NULL they are the calls above, to the bit. */
+int ekf_batch_set_gate(ekf_batch *b, const double *gate /* [B] or NULL */);
+int ekf_batch_observe_logs_gated(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets,
+                                 const int64_t *member_frames, const double *poses_dev, void *log_ws, size_t log_ws_bytes,
+                                 double *trajectory_dev, double *nis_dev, double *cam_cov_dev, double *mahal_dev);
+int ekf_batch_observe_replicas_gated(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets, int64_t frames,
+                                     const double *poses_dev, const double *sigma, uint64_t seed, uint32_t first_replica,
+                                     void *ws, size_t ws_bytes, double *trajectory_dev, double *nis_dev,
+                                     double *cam_cov_dev, double *mahal_dev);
+
 const char *ekf_last_error_string(void);
 
 #ifdef __cplusplus

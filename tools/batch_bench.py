@@ -60,6 +60,10 @@ def main():
     ap.add_argument("--replicas", action="store_true", help="replay_replicas against host-noised process_detection_logs")
     ap.add_argument("--nis", action="store_true", help="--replicas: ask for the per-frame NIS")
     ap.add_argument("--cam-cov", action="store_true", help="--replicas: ask for the per-frame camera covariance")
+    ap.add_argument("--gate", type=float, default=None,
+                    help="chi-square gate of every member (EKFBatch(gate=X)); 1e300 tests every detection and rejects none. "
+                         "With a gate the wall times include the copy of mahal and the host's rejected / dof bookkeeping: "
+                         "compare window-kernel times of a rocprofv3 kernel trace, not wall_s")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.batch import EKFBatch
@@ -89,7 +93,7 @@ def main():
     single = args.steady / (time.perf_counter() - t0)
     for B in args.members:
         batch = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model,
-                         large_maps=True if args.large_maps else None)
+                         large_maps=True if args.large_maps else None, **({} if args.gate is None else {"gate": args.gate}))
         batch.process_detection_logs([lg[0] for lg in logs[:B]])           # warm-up: bootstrap frames, same launch shape
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -100,7 +104,7 @@ def main():
         line = {"tool": "batch_bench", **({"model": args.model} if rot else {}),
                 **({"large_maps": True} if args.large_maps else {}),
                 **({"wide_frames": True} if batch.wide_frames else {}), "members": B, "n": n, "m": [1, m_hi],
-                "steady_frames": args.steady,
+                "steady_frames": args.steady, **({} if args.gate is None else {"gate": args.gate}),
                 "wall_s": round(wall, 6), "aggregate_frames_per_s": round(rate, 1),
                 "single_filter_frames_per_s": round(single, 1), "ratio": round(rate / single, 2)}
         if args.large_maps or batch.wide_frames:     # every stepped frame reads and writes the member's N x N f64 covariance
@@ -140,7 +144,7 @@ def replicas(args, n, m_hi, visible):
     lines = []
     for B in args.members or [16, 64, 256, 1024]:
         batch = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model,
-                         large_maps=True if args.large_maps else None)
+                         large_maps=True if args.large_maps else None, **({} if args.gate is None else {"gate": args.gate}))
 
         def host_logs():
             return [dict(log, poses=log["poses"] + sigma * rng.standard_normal(log["poses"].shape)) for _ in range(B)]
@@ -167,6 +171,7 @@ def replicas(args, n, m_hi, visible):
                 **({"large_maps": True} if args.large_maps else {}),
                 **({"wide_frames": True} if batch.wide_frames else {}), "members": B, "n": n, "m": [1, m_hi],
                 "frames": frames, "detections": dets, "nis": args.nis, "cam_cov": args.cam_cov,
+                **({} if args.gate is None else {"gate": args.gate}),
                 "replay_replicas_wall_s": round(wall_rep, 6),
                 "replay_replicas_frames_per_s": round(B * frames / wall_rep, 1),
                 "host_noised_wall_s": round(wall_host, 6), "host_noise_draw_s": round(t1 - t0, 6),

@@ -100,7 +100,7 @@ Layout make_layout(const ekf_config& c) {
         L.xl_len = L.xl_stag + 256;
         L.off_xl = w.take(2 * L.xl_len * 8);
         L.off_done = w.take(256);
-        L.off_sync = w.take(256);
+        L.off_sync = w.take(EKF_SYNC_WORDS * 8);      // [0], [1] the two cross-stream counters, [2..9] the queue probe, then the update's arrival counts
         L.wsup_ld = (int)round_up(EKF_CAM + (int64_t)L.lmd * c.max_visible, 32);
         L.off_wsup = w.take((size_t)2 * L.kmax * L.wsup_ld * L.elem);
     }
@@ -277,6 +277,9 @@ EkfFrame make_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, 
     fr.dxvec = f->at<double>(L.off_dx);
     fr.stamps = (f->debug_w || f->debug_stamps) ? f->at<long long>(L.off_stamps) : nullptr;
     fr.stamps_heavy = f->debug_stamps_light ? 0 : 1;
+    // (role-level stamps only: the per-frame ring of the end gate borrows the W debug copy, which is idle in that mode)
+    fr.gate_log = (fr.stamps && !fr.stamps_heavy && !f->debug_w && (size_t)L.kmax * L.cap >= 4 * EKF_GATE_LOG_FRAMES)
+                      ? f->at<long long>(L.off_wdbg) : nullptr;
     fr.nz = EkfNoise{f->cfg.q_cam, f->cfg.q_err, f->cfg.q_lm, f->cfg.r_uncertainty};
     fr.quat_mode = f->cfg.quat_mode;
     fr.n_lm = f->n_lm;
@@ -589,15 +592,24 @@ struct RunFrame {
 // (S-block workgroups: from the compact support columns W_sup the chunks of F(t) left behind; chunk workgroups:
 // on the matrix cores).  Nothing on the critical path F(t) -> F(t+1) waits for a covariance update.
 //   stream A (the handle's):  F(0) - F(1) - F(2) - ... - F(last) - C(last)
-//   stream B (internal)    :  gate - C(0) - signal - gate - C(1) - signal ...
+//   stream B (internal)    :  gate - C(0) - gate - C(1) - ...
 // Edges between the streams are ordered on the device (an event pair costs ~13 us per edge):
 //   F(t) complete   -> C(t) may start (it reads W_t and overwrites the buffer F(t) read, P_{t-1}): F(t+1) stores
 //                      "t+1 started" when it starts (it follows F(t) on stream A); a one-wave gate kernel in front
 //                      of C(t) polls that counter (the last update of a call follows its front kernel on stream A);
-//   C(t-1) complete -> F(t+1) may read buf[t & 1] and overwrite W_{t-1}: a one-thread kernel behind C(t-1) bumps a
-//                      second counter; F(t) does not finish before it has seen it (its measurement workgroup polls
+//   C(t-1) complete -> F(t+1) may read buf[t & 1] and overwrite W_{t-1}: C(t-1) stores a second counter ITSELF (no
+//                      launch of its own, no kernel boundary in front of it: ekf_kernels.h, ekf_cov_arrive): every
+//                      workgroup waits for the acknowledgement of its stores and counts itself, the last one stores
+//                      the frame's value; F(t) does not finish before it has seen it (its measurement workgroup polls
 //                      at its end), and F(t+1) follows F(t) on stream A.
-// Kernel boundaries on each stream give the memory ordering; the counters only carry "that launch is over".
+// Memory ordering.  F(t) -> C(t): kernel boundaries (F(t) is over when F(t+1) starts, C(t) starts behind the gate).
+// C(t-1) -> F(t+1): NOT a kernel boundary of stream B any more -- C(t-1) may still be a launch when the signal is out.
+// The argument is: (1) every store to cov_out is a write-through (sc1) store (ekf_cov_store, cm_store16), and a wave
+// counts as arrived only behind `s_waitcnt vmcnt(0)`, i.e. once its stores are acknowledged by the device's coherence
+// point, so all of P_t is in memory before the signal is stored; (2) the consumer of the signal is the OPEN launch F(t),
+// which reads nothing of P_t: the data is read only by LATER launches (F(t+1) on stream A, C(t) on stream B), whose
+// kernel-start acquire drops whatever stale lines their L2s hold.  The W panel F(t+1) overwrites was read by C(t-1)
+// before the stores that depend on it.  The counters only carry "those stores are complete".
 // Every wait is bounded.  The front kernel claims (almost) all LDS of its CUs while its grid is small, so the
 // covariance update's workgroups run on the other CUs instead of next to the pivot chain.
 template <class FrameAt>
@@ -648,13 +660,14 @@ int run_pipelined(ekf_filter* f, int frames, FrameAt frame_at, void* other) {
         cu.cov_out = cbuf[par ^ 1];
         if (t + 1 < frames) {
             ekf_launch_gate(sync, base + (uint64_t)t + 1, status, f->big);
+            cu.cov_signal = base + (uint64_t)t + 1;            // "C(t) complete", stored by the update's last workgroup
             by_cov_type(f, [&](auto elem) { ekf_launch_cov_update<decltype(elem)>(cu, 2, f->big); });
-            ekf_launch_signal(sync + 1, base + (uint64_t)t + 1, f->big);
         } else {
             // The LAST update of the run goes on the handle's stream, straight behind its front kernel: stream order says
             // that F(t) is over, and F(t) did not finish before it had seen C(t-1) complete (its end gate) -- no gate, no
-            // signal, and nothing to join afterwards (4 device-side hops of ~1.2 us per call).  The counters keep the
-            // values of frame t - 1; the next run's waits are for values beyond base + frames, which its own launches set.
+            // signal (cov_signal stays 0: no atomic), and nothing to join afterwards (4 device-side hops of ~1.2 us per
+            // call).  The counters keep the values of frame t - 1; the next run's waits are for values beyond
+            // base + frames, which its own launches set.
             by_cov_type(f, [&](auto elem) { ekf_launch_cov_update<decltype(elem)>(cu, 2, f->stream); });
         }
         HIP_TRY(hipGetLastError());
@@ -1383,6 +1396,9 @@ int ekf_get_kernel_timing(ekf_filter* f, int32_t which, double* mean_us, int64_t
     return EKF_OK;
 }
 
+// Items 0 - 4: include/ekf_slam_hip.h.  Diagnostics beyond the public list: 5 = the 64 in-kernel time stamps (after
+// what = -2: all of them, -3: role level only), 6 = the end-gate ring of the pipelined mode, [EKF_GATE_LOG_FRAMES][4]
+// (EkfFrame::gate_log; role-level stamps only: it borrows the W debug copy; hip_backend.GATE_LOG_FRAMES is the same number).
 int ekf_debug_fetch(ekf_filter* f, int32_t what, double* out, size_t count) {
     int rc = check_ready(f);
     if (rc) return rc;
@@ -1432,6 +1448,16 @@ int ekf_debug_fetch(ekf_filter* f, int32_t what, double* out, size_t count) {
                 long long st[64];
                 HIP_TRY(hipMemcpy(st, f->at<long long>(L.off_stamps), sizeof(st), hipMemcpyDeviceToHost));
                 for (int i = 0; i < 64; ++i) out[i] = (double)st[i];
+            }
+            return EKF_OK;
+        case 6:      // the end-gate ring of the pipelined mode (EkfFrame::gate_log), [EKF_GATE_LOG_FRAMES][4]
+            if (count < 4 * EKF_GATE_LOG_FRAMES) return fail(EKF_ERR_INVALID, "out too small");
+            if (!(f->debug_stamps && f->debug_stamps_light) || f->debug_w || (size_t)L.kmax * L.cap < 4 * EKF_GATE_LOG_FRAMES)
+                return fail(EKF_ERR_STATE, "the gate log needs role-level stamps (ekf_debug_fetch(f,-3,..)) and kmax * cap >= 8192");
+            {
+                std::vector<long long> st(4 * EKF_GATE_LOG_FRAMES);
+                HIP_TRY(hipMemcpy(st.data(), f->at<long long>(L.off_wdbg), st.size() * 8, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < st.size(); ++i) out[i] = (double)st[i];
             }
             return EKF_OK;
         default:

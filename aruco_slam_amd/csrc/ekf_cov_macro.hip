@@ -99,7 +99,10 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
     constexpr int DEPTH = CM_NBUF - 1;             // chunks in flight
     static_assert(NW == 8, "wait counts below are worked out for 8 waves");
     const uint32_t tl = tiles[blockIdx.x];
-    if (tl == 0xFFFFFFFFu) return;
+    if (tl == 0xFFFFFFFFu) {                         // (a workgroup without a tile still counts as arrived)
+        if (fr.cov_signal) ekf_cov_arrive(fr);
+        return;
+    }
     const int I = (int)(tl >> 16), J = (int)(tl & 0xFFFFu);
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -270,6 +273,7 @@ void ekf_cov_update_macro_f32(EkfFrame fr, const uint32_t* __restrict__ tiles) {
         for (int it = 0; it < NPASS; ++it) cm_store16(ob + (int64_t)(RPP * it) * ld + (unsigned)(prow * ld + pcol), rowv[it]);
     }
     }
+    if (fr.cov_signal) ekf_cov_arrive(fr);           // pipelined sequence mode: "complete" without a launch of its own
 }
 
 // Host side: the launch order.  Block b runs on XCD b % 8 (observed placement; speed only), so the table deals whole

@@ -121,7 +121,10 @@ void ekf_cov_update_mfma_f32(EkfFrame fr, int nitems) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int l31 = lane & 31, lhi = lane >> 5;
     const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-    if (item >= nitems) return;
+    if (item >= nitems) {                        // (a wave without a tile still counts towards its workgroup's arrival)
+        if (fr.cov_signal) ekf_cov_arrive(fr);
+        return;
+    }
     int I, J;
     ekf_tri_decode(item, I, J);
     const int i0 = 32 * I, j0 = 32 * J;
@@ -225,6 +228,7 @@ void ekf_cov_update_mfma_f32(EkfFrame fr, int nitems) {
         for (int it = 0; it < 16; ++it)          // column 2 it + lhi of D = row of D^T
             stf(pm + (int64_t)(2 * it) * ld, mlane, tr[wave][l31][2 * it + lhi]);
     }
+    if (fr.cov_signal) ekf_cov_arrive(fr);
 }
 
 // --------------------------------------------------------------------------
@@ -235,7 +239,10 @@ __global__ __launch_bounds__(256) void ekf_cov_update_mfma_f64(EkfFrame fr, int 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int c = lane & 15, g = lane >> 4;
     const int item = blockIdx.x * 4 + wave;
-    if (item >= nitems) return;
+    if (item >= nitems) {                        // (a wave without a tile still counts towards its workgroup's arrival)
+        if (fr.cov_signal) ekf_cov_arrive(fr);
+        return;
+    }
     int I, J;
     ekf_tri_decode(item, I, J);
     const int i0 = 32 * I, j0 = 32 * J;
@@ -304,6 +311,7 @@ __global__ __launch_bounds__(256) void ekf_cov_update_mfma_f64(EkfFrame fr, int 
             ekf_cov_store(Pout + (int64_t)(j0 + cc) * ld + i0 + l31, tr[wave][l31][cc]);
         }
     }
+    if (fr.cov_signal) ekf_cov_arrive(fr);
 }
 
 // --------------------------------------------------------------------------
@@ -357,12 +365,14 @@ __global__ __launch_bounds__(256) void ekf_cov_update_mfma_f64_split(EkfFrame fr
         for (int cc = threadIdx.x >> 5; cc < 32; cc += 8)          // column cc of D = row of D^T
             ekf_cov_store(Pout + (int64_t)(j0 + cc) * ld + i0 + l31, tr[l31][cc]);
     }
+    if (fr.cov_signal) ekf_cov_arrive(fr);
 }
 
 // Pipelined sequence mode: ordering between the two streams on the device (an event pair costs ~13 us per edge,
 // stream write / wait values ~7 us, a resident one-wave kernel that polls a counter ~1.2 us:
 // tools/probes/xstream_probe.hip).  The gate keeps whatever follows it on its stream from starting before
-// `counter >= target`; the wait is bounded (status bit instead of a hang).
+// `counter >= target`; the wait is bounded (status bit instead of a hang).  "C(t) complete" is stored by the update
+// itself (ekf_kernels.h: ekf_cov_arrive); the signal kernel serves the one-time hardware-queue probe only.
 __global__ void ekf_gate_kernel(unsigned long long* counter, unsigned long long target, int32_t* status, int max_polls) {
     if (threadIdx.x != 0) return;
     int it = 0;

@@ -323,7 +323,11 @@ __device__ __forceinline__ void fr_role_measure(const EkfFrame& fr, double* sm) 
     int* lmc = reinterpret_cast<int*>(rsd + fr.kpad);
     const int tid = threadIdx.x;
     // (role-level stamps: the start of each of the last 16 launches, by frame number)
-    if (fr.stamps && !fr.stamps_heavy && tid == 0) fr.stamps[16 + ((long long)fr.seqno & 15)] = wall_clock64();
+    if (fr.stamps && !fr.stamps_heavy && tid == 0) {
+        const long long now = wall_clock64();
+        fr.stamps[16 + ((long long)fr.seqno & 15)] = now;
+        if (fr.gate_log) fr.gate_log[4 * ((long long)fr.seqno & (EKF_GATE_LOG_FRAMES - 1))] = now;
+    }
     // pipelined sequence mode: this launch has started, i.e. everything before it on its stream is complete
     if (fr.la_signal && tid == 0)
         __hip_atomic_store(fr.la_sync, fr.la_signal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -347,10 +351,18 @@ __device__ __forceinline__ void fr_role_measure(const EkfFrame& fr, double* sm) 
     // pipelined sequence mode: keep this launch open until the covariance update of the previous frame (other
     // stream) is complete -- whatever follows this launch on its stream may then read P
     if (fr.la_gate && tid == 0) {
+        // (diagnostics: the stamps stay in registers while the gate polls and are stored behind it)
+        const long long g0 = fr.gate_log ? wall_clock64() : 0;
         int it = 0;
         while (__hip_atomic_load(fr.la_sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < fr.la_gate) {
             if (++it > (1 << 22)) { ekf_raise(fr, EKF_ST_GATE_TIMEOUT); break; }
             __builtin_amdgcn_s_sleep(8);
+        }
+        if (fr.gate_log) {
+            long long* row = fr.gate_log + 4 * ((long long)fr.seqno & (EKF_GATE_LOG_FRAMES - 1));
+            row[1] = g0;
+            row[2] = wall_clock64();
+            row[3] = it;
         }
     }
 }

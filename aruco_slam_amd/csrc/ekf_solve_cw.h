@@ -21,6 +21,12 @@
 //   xready      = b + 1 once X_b is in xbuf[b]                         (chain wave -> workers, publisher)
 //   yflag[i]    = b + 1 once L_ib is in ybuf[i][b]                     (row i's owner, or the chain wave for i = b + 1)
 //   dready[i]   = 1 once P / D of row i are in dep[i]                  (row i's owner -> chain wave)
+//   rready      = 1 once the residual row's last block is in rlast     (its owner -> chain wave)
+// The LAST block column leaves through the chain wave itself: it has no further chain to run (so stores in flight on it
+// delay nobody), Dinv_(NB-1) is in its registers, and the residual row's last panel y_(NB-1) = X_(NB-1) S'_(NB)(NB-1) is
+// one product on the block the row's owner has left in rlast -- the same product on the same operands as in the owner's
+// row_step, so the bits are the same; the hops chain -> LDS -> publishing wave and chain -> LDS -> owner -> LDS ->
+// publishing wave fall off the tail of the factorisation.
 // Critical path per block column: chain -> (P, D from LDS) -> 4 MFMAs -> 4 MFMAs -> chain.
 #pragma once
 #include <type_traits>
@@ -29,8 +35,8 @@
 #define SVC_WORKERS 6
 
 __host__ __device__ constexpr int svc_lds_doubles(int nb) {
-    // X_b [nb] | L_ib [nb + 1][nb] | hand-over blocks P, D [nb][2] | flags (2 nb + 2 ints)
-    return nb * 256 + (nb + 1) * nb * 256 + nb * 512 + (2 * nb + 2 + 1) / 2 + 8;
+    // X_b [nb] | L_ib [nb + 1][nb] | hand-over blocks P, D [nb][2] | the residual row's last block | flags (2 nb + 3 ints)
+    return nb * 256 + (nb + 1) * nb * 256 + nb * 512 + 256 + (2 * nb + 3 + 1) / 2 + 8;
 }
 
 // (bounded: a poster that never comes would be a bug, not a hang -- the caller then reports the factorisation as failed)
@@ -75,10 +81,12 @@ __device__ __forceinline__ void sv_factor_cw(const EkfFrame& fr, IO& io, double*
     double* xbuf = lds;                                          // [NB][256]          OP(X_b)
     double* ybuf = xbuf + NB * 256;                              // [NB + 1][NB][256]  OP(L_ib)
     double* dep = ybuf + (NB + 1) * NB * 256;                    // [NB][2][256]       P = S'_i(i-1), D = S'_ii of row i
-    volatile ekf_lds_int* xready = ekf_lds_flags(dep + NB * 512);
+    double* rlast = dep + NB * 512;                              // [256]              S'_(NB)(NB-1) of the residual row, complete
+    volatile ekf_lds_int* xready = ekf_lds_flags(rlast + 256);
     volatile ekf_lds_int* yflag = xready + 1;                    // [NB + 1]
     volatile ekf_lds_int* dready = yflag + (NB + 1);             // [NB]
-    for (int e = tid; e < 2 * NB + 2; e += SV_T) xready[e] = 0;
+    volatile ekf_lds_int* rready = dready + NB;                  // 1 once rlast is there
+    for (int e = tid; e < 2 * NB + 3; e += SV_T) xready[e] = 0;
     __syncthreads();
     const bool is_chain = wave == 0, is_pub = wave == 4;
     // a wait that ran out: the factorisation counts as failed (status bit through the caller), block column code 200 + flag
@@ -130,6 +138,14 @@ __device__ __forceinline__ void sv_factor_cw(const EkfFrame& fr, IO& io, double*
                 p = sv_lds_get(dep + (b + 1) * 512, lane);
                 d = sv_lds_get(dep + (b + 1) * 512 + 256, lane);
             }
+            if (b + 1 == NB) {                                   // the last block column: published from here
+                io.put_dinv(b, xop, lane);
+                svc_wait(rready, 1);
+                const sf64x4 yi = sv_mm(xop, sv_lds_get(rlast, lane));
+                io.put_y(b, (c >> 2) == 0 ? yi[0] : (c >> 2) == 1 ? yi[1] : (c >> 2) == 2 ? yi[2] : yi[3], c, g == (c & 3));
+                if (fr.stamps && !fr.stamps_heavy && lane == 0) fr.stamps[1] = clock64();      // (its stores are issued)
+                break;
+            }
             sv_lds_put(xbuf + b * 256, xop, lane);
             svc_post_in_order(xready, b + 1, lane);
             if (b + 1 < NB) {
@@ -148,7 +164,7 @@ __device__ __forceinline__ void sv_factor_cw(const EkfFrame& fr, IO& io, double*
     }
     if (is_pub) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
+        for (int b = 0; b + 1 < NB; ++b) {                      // (the last block column: the chain wave)
             svc_wait(xready, b + 1);
             if (stl) stl[2 + 2 * b] = clock64();
             io.put_dinv(b, sv_lds_get(xbuf + b * 256, lane), lane);
@@ -172,6 +188,10 @@ __device__ __forceinline__ void sv_factor_cw(const EkfFrame& fr, IO& io, double*
     if (has0 && i0 == 0) {                                       // row 0: the first diagonal block
         sv_lds_put(dep + 256, z0[0], lane);
         svc_post(dready, 1, lane);
+    }
+    if (NB == 1 && has0 && i0 == 1) {                            // one block column: the residual row's only block, as loaded
+        sv_lds_put(rlast, z0[0], lane);
+        svc_post(rready, 1, lane);
     }
     if (NB > 1) io.template load_cols<NB, NB, NB, 1, NB>(z0, z1, i0, i1, has0, has1, lane, g);
     if (NB > 1 && has0 && i0 == 1) {                             // row 1: nothing to wait for
@@ -209,8 +229,14 @@ __device__ __forceinline__ void sv_factor_cw(const EkfFrame& fr, IO& io, double*
             }
             return true;
         });
+        if constexpr (b + 2 == NB) {
+            if (i == NB) {                                       // the residual row's last block is complete: the chain wave's
+                sv_lds_put(rlast, z[NB - 1], lane);
+                svc_post(rready, 1, lane);
+            }
+        }
     };
-    svc_static_for<0, NB>([&](auto bc) {
+    svc_static_for<0, NB - 1>([&](auto bc) {                     // (block column NB - 1 has the residual row's panel only: the chain wave's)
         constexpr int b = decltype(bc)::value;
         if (!((has0 && i0 > b) || (has1 && i1 > b))) return false;      // nothing left for this worker
         svc_wait(xready, b + 1);

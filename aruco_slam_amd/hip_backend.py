@@ -22,6 +22,9 @@ EKF_FLAG_BATCH_LARGE_MAPS = 16  # ekf_config.flags bit 4 (batches): up to 1024 s
 EKF_FLAG_BATCH_WIDE_FRAMES = 32  # ekf_config.flags bit 5 (batches): up to 64 (EKF) / 50 (EKF_Rotations) detections per frame
 EKF_COVK_AUTO, EKF_COVK_VALU, EKF_COVK_MFMA, EKF_COVK_MFMA_TILE, EKF_COVK_MFMA_MACRO = 0, 1, 2, 3, 4
 
+# frames in the end-gate ring of ekf_debug_fetch item 6 (csrc/ekf_kernels.h: EKF_GATE_LOG_FRAMES)
+GATE_LOG_FRAMES = 2048
+
 # every symbol include/ekf_slam_hip.h declares
 EXPORTED_SYMBOLS = (
     "ekf_default_config", "ekf_query_sizes", "ekf_create", "ekf_destroy", "ekf_bind_buffers",
@@ -441,8 +444,8 @@ class HipEkf:
         rd = self.rows_per_detection
         k, kp, n = rd * m, -(-rd * m // 16) * 16, self.dims
         shape = {"jac": (k, 20 if rd == 7 else 13), "resid": (k,), "L": (kp, kp), "W": (kp, n), "A": (k, n),
-                 "stamps": (64,)}[what]
-        code = {"jac": 0, "resid": 1, "L": 2, "W": 3, "A": 4, "stamps": 5}[what]
+                 "stamps": (64,), "gate_log": (GATE_LOG_FRAMES, 4)}[what]
+        code = {"jac": 0, "resid": 1, "L": 2, "W": 3, "A": 4, "stamps": 5, "gate_log": 6}[what]
         out = np.empty(shape)
         self._check(self.lib.ekf_debug_fetch(self.h, code, _dptr(out), out.size))
         return out

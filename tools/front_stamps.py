@@ -25,7 +25,8 @@ print("fused front kernel timeline, us since the earliest stamp (100 MHz wall cl
 print("S-block wg0 start",us(60),"  measure wg published",us(55),"  S-block wg nS-1 stored",us(61))
 print("factor: start",us(62)," end",us(63))
 if not light: print("  cycles: blocks into registers",st[1]-st[0], " per wave:", [int(st[24+w]-st[0]) for w in range(8)])
-if light: print('  X_b in LDS, seen by the publishing wave (cycles since the start of the factorisation):', [int(st[2+2*b]-st[0]) for b in range(nb)])
+if light: print('  X_b in LDS, seen by the publishing wave (cycles since the start of the factorisation):', [int(st[2+2*b]-st[0]) for b in range(nb - 1)],
+                ' last block column (Dinv, y) stored by the chain wave:', int(st[1]-st[0]))
 for b in range(0 if light else nb):
     prev = st[1] if b == 0 else st[3+2*(b-1)]
     print("  col",b," chain phase + barrier",st[2+2*b]-prev," panel + barrier + urgent update",st[3+2*b]-st[2+2*b],

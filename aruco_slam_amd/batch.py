@@ -7,9 +7,9 @@ own log, with its own initial pose, noise constants and marker-id -> landmark-in
 a batch fills the GPU where a single filter of this size leaves it almost idle.  All members share the model, the quaternion
 convention, an f64 covariance and the capacity: ``model="ekf"`` (``EKF``) holds ``max_landmarks`` <= 82 and ``max_visible``
 <= 16, ``model="ekf_rotations"`` (``EKF_Rotations``, scalar-first quaternions only) ``max_landmarks`` <= 24 and
-``max_visible`` <= 8.  With ``large_maps`` (``EKF_FLAG_BATCH_LARGE_MAPS``, kernel ``csrc/ekf_batch_large.hip``) the maps
+``max_visible`` <= 8.  With ``large_maps`` (``EKF_FLAG_BATCH_LARGE_MAPS``, kernel ``csrc/ekf_batch_wide.hip``) the maps
 grow to dictionary size: ``max_landmarks`` <= 338 (``EKF``) or <= 101 (``EKF_Rotations``), same ``max_visible``.  With
-``wide_frames`` (``EKF_FLAG_BATCH_WIDE_FRAMES``, kernel ``csrc/ekf_batch_wide.hip``) a frame may hold as many detections as
+``wide_frames`` (``EKF_FLAG_BATCH_WIDE_FRAMES``, the same kernel) a frame may hold as many detections as
 a default single filter takes: ``max_visible`` <= 64 (``EKF``) or <= 50 (``EKF_Rotations``), on the large-map limits of
 ``max_landmarks``; a frame is factorised in blocks of 16 / 8 detections, and one of at most 16 / 8 detections gives the same
 bits as a batch without the flag.  A batch never grows; there is no CPU fallback.

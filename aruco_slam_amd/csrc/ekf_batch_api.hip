@@ -1,7 +1,7 @@
 // C ABI of the batch of independent filters (ekf_batch_*, see include/ekf_slam_hip.h; kernels: ekf_batch.hip (EKF) and
-// ekf_batch_rot.hip (EKF_Rotations), with EKF_FLAG_BATCH_LARGE_MAPS ekf_batch_large.hip (both), with
-// EKF_FLAG_BATCH_WIDE_FRAMES ekf_batch_wide.hip (both); one workgroup per member; the noisy poses of replicas:
-// ekf_batch_replicas.hip).  Host side only: argument checking, workspace carving, launch sequencing.
+// ekf_batch_rot.hip (EKF_Rotations), with EKF_FLAG_BATCH_LARGE_MAPS or EKF_FLAG_BATCH_WIDE_FRAMES ekf_batch_wide.hip
+// (both models); one workgroup per member; the noisy poses of replicas: ekf_batch_replicas.hip).  Host side only: argument
+// checking, workspace carving, launch sequencing.
 #include <cmath>
 #include <cstring>
 
@@ -197,22 +197,22 @@ int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, co
     const int rd = batch_rd(b->cfg);
     a.kmax = std::max(rd, rd * sh.widest);
     a.lda = (int32_t)round_up(batch_lmd(b->cfg) * sh.n_max + EKF_CAM + 1, 4);
-    const bool rot = b->cfg.model == EKF_MODEL_ROTATIONS, wide = batch_wide(b->cfg);
-    // wide frames: a frame of m detections costs about ceil(m / block) sweeps of P (block = 16 / 8 detections), so the
-    // window shrinks with the call's widest frame and one launch stays about as long as a large-map window
+    const bool rot = b->cfg.model == EKF_MODEL_ROTATIONS;
+    // a frame of m detections costs about ceil(m / block) sweeps of P in ekf_batch_wide.hip (block = 16 / 8 detections), so
+    // the window shrinks with the call's widest frame and every launch stays about as long.  Without the wide flag no frame
+    // is wider than one block: 64 frames
     const int block = rot ? EKF_BATCH_ROT_MAX_VISIBLE : EKF_BATCH_MAX_VISIBLE;
-    const int window = wide ? std::max(1, kBatchWindow / ((std::max(sh.widest, 1) + block - 1) / block)) : kBatchWindow;
+    const int window = std::max(1, kBatchWindow / ((std::max(sh.widest, 1) + block - 1) / block));
     a.window_frames = window;
-    // large maps or wide frames: every call runs ekf_batch_large.hip or ekf_batch_wide.hip, whatever the map size and the
-    // frame widths (A / W in the workspace)
+    // large maps or wide frames: every call runs ekf_batch_wide.hip, whatever the map size and the frame widths (A / W in
+    // the workspace)
+    const bool hbm = batch_large(b->cfg) || batch_wide(b->cfg);
     EkfBatchLargeWindow g{a, reinterpret_cast<double*>(b->ws + L.w), batch_w_stride(b->cfg)};
     for (int64_t w = 0; w < sh.frames_max; w += window) {
         a.window_first = (int32_t)w;
         g.w.window_first = (int32_t)w;
-        if (wide)
-            ekf_launch_batch_wide_window(rot ? 1 : 0, g, B, b->stream);
-        else if (batch_large(b->cfg))
-            ekf_launch_batch_large_window(rot ? 1 : 0, g, B, b->stream);
+        if (hbm)
+            ekf_launch_batch_wide_window(rot ? 1 : 0, !batch_wide(b->cfg), g, B, b->stream);
         else if (rot)
             ekf_launch_batch_rot_window(a, B, b->stream);
         else

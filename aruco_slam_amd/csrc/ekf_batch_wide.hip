@@ -1,24 +1,32 @@
-// Batch of independent filters with wide frames (ekf_batch_observe_logs with EKF_FLAG_BATCH_WIDE_FRAMES, ekf_batch_api.hip):
-// the window kernels of both models for up to 64 (EKF, k = 3 m <= 192) or 50 (EKF_Rotations, k = 7 m <= 350) detections
-// per frame, on maps up to N = 1024 (EKF n <= 338, EKF_Rotations n <= 101).  ONE workgroup of 256 threads owns ONE member
-// for a window of its log's frames, as in ekf_batch_large.hip, and A / W [k][ld] lives in the member's slice of the batch
-// workspace (HBM).  A frame's detections are split, in log order, into blocks of MB = 16 (EKF) / 8 (EKF_Rotations)
-// detections, kb <= KW = 48 / 56 rows each.  For block j (rows r0 .. r0 + kb):
+// Batch of independent filters, HBM-resident window kernel (ekf_batch_observe_logs with EKF_FLAG_BATCH_LARGE_MAPS or
+// EKF_FLAG_BATCH_WIDE_FRAMES, ekf_batch_api.hip): the window kernels of both models on maps up to N = lmd n + 10 = 1024 (EKF
+// n <= 338, EKF_Rotations n <= 101) and frames of up to 64 (EKF, k = 3 m <= 192) or 50 (EKF_Rotations, k = 7 m <= 350)
+// detections.  ONE workgroup of 256 threads owns ONE member for a window of its log's frames, as in ekf_batch_impl.h, and a
+// frame runs the algebra of that kernel with the same operation order per entry (so where both run, the bits are the same).
+// What moves is the data: A, then W, [k][ld] lives in the member's slice of the batch workspace (HBM), y [k] in LDS.
+// A frame's detections are split, in log order, into blocks of MB = 16 (EKF) / 8 (EKF_Rotations) detections, kb <= KW =
+// 48 / 56 rows each; a frame of a batch without the wide flag is one block, and such a batch runs the ONE_BLOCK instances
+// of the same body (ekf_batch_one_block_window_kernel / _rot_).  After the first sightings, for block j (rows
+// r0 .. r0 + kb):
 //   h and dh of its detections (J of the block and y_j = z_j - h_j),
-//   A_j = H_j (P+Q),
+//   A_j = H_j (P+Q), thread c owning column c,
 //   for every earlier block i: the off-diagonal factor block L_ji = H_j W_i^T (only the support columns of the stored W_i
 //     rows are read: W H^T = L^T - L^-1 R with L^-1 R lower triangular), then A_j <- A_j - L_ji W_i and y_j <- y_j - L_ji y_i,
 //     one l-ascending fma chain per entry over all earlier rows,
-//   S_jj = A_j[:,supp] H_j^T + R I, S_jj = L_jj L_jj^T, W_j = L_jj^-1 A_j and y_j <- L_jj^-1 y_j: the code of
-//     ekf_batch_large.hip on kb rows; W_j stays in the workspace.
+//   S_jj = A_j[:,supp] H_j^T + R I (lower triangle), S_jj = L_jj L_jj^T (left-looking, in LDS),
+//   W_j = L_jj^-1 A_j and y_j <- L_jj^-1 y_j; W_j stays in the workspace.
 // Only then: dx = W^T y over all k rows, the injection, and P <- (P+Q) - W^T W as one read-modify-write sweep of P per block
 // (Q added by the first).  Entry (i,c) and (c,i) run the same operations in every sweep, so P stays bitwise symmetric and
-// its padding zero.  With one block (m <= MB) every operation is the one of ekf_batch_large.hip, in the same order: the
-// same bits.  Nothing touches P or the state before the last pivot of the frame has passed, so a failing pivot in any block
-// leaves them as the frame found them (its first sightings stay added, as everywhere).
-// LDS holds the block's L_jj (and, in turn, each L_ji), 1 / L_jj, J of the block, y [kmax] and the region R of
-// 256 x round_up(kb, 4) doubles of ekf_batch_large.hip: 123,920 bytes at the EKF's kmax = 192, 152,200 at EKF_Rotations'
-// kmax = 350.  The off-diagonal factor rows are not stored: each L_ji is formed from W rows in HBM when it is used.
+// its padding zero.  Nothing touches P or the state before the last pivot of the frame has passed, so a failing pivot in
+// any block leaves them as the frame found them (its first sightings stay added, as everywhere).
+// LDS holds the block's L_jj (and, in turn, each L_ji), 1 / L_jj, J of the block, y [kmax] and one region R of
+// 256 x round_up(kb, 4) doubles that serves three phases in turn: each thread's private copy of the column it substitutes,
+// then dx, then a panel of 256 rows of W_j^T for the covariance sweep.  LDS thus depends on kmax only: 122,768 / 149,848
+// bytes with one block (kmax = 48 / 56), 123,920 at the EKF's kmax = 192, 152,200 at EKF_Rotations' kmax = 350.  The
+// off-diagonal factor rows are not stored: each L_ji is formed from W rows in HBM when it is used.
+// Covariance sweep: thread t owns column c = c0 + t for column blocks c0 = 0, 256, ...; it keeps W_j[:,c] in registers and
+// streams its column of P in blocks of 8 rows with two blocks loaded ahead (24 doubles in flight per thread), against the
+// panel of W_j^T rows in LDS (broadcast reads).  Entry (i,c) runs the l-ascending fma chain of ekf_batch_impl.h.
 // P of a member is read and written by its own workgroup only: workgroup barriers are the only ordering.
 #include "ekf_batch_impl.h"
 
@@ -56,7 +64,10 @@ static_assert(wide_gate_fits<0>() && wide_gate_fits<1>(), "the gate's scratch mu
 
 typedef double ekf_d2 __attribute__((ext_vector_type(2)));
 
-template <int MODEL> __device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow& g) {
+// ONE_BLOCK: no frame of the launch is wider than one block (a batch without the wide flag: the host admits no wider frame),
+// so the loops over blocks run once, with j0 = 0, and the loop over earlier blocks is gone: the same operations on the same
+// data, with less control around them (the large-map shapes run 3 to 4 % faster than in the general instance)
+template <int MODEL, bool ONE_BLOCK> __device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow& g) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     constexpr int MB = wide_mb<MODEL>(), KW = wide_kw<MODEL>();
     const EkfBatchWindow& a = g.w;
@@ -123,10 +134,10 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_wide_window(const
                 continue;
             }
         }
-        const int k = RD * m;
+        const int k = RD * m, blocks_end = ONE_BLOCK ? 1 : m;
         // ---- the factorisation, block after block of detections; W_j and y_j of every block that passed stay behind
-        for (int j0 = 0; j0 < m; j0 += MB) {
-            const int mb = min(MB, m - j0), kb = RD * mb, r0 = RD * j0;
+        for (int j0 = 0; j0 < blocks_end; j0 += MB) {
+            const int mb = ONE_BLOCK ? m : min(MB, m - j0), kb = RD * mb, r0 = RD * j0;
             double* Aj = A + (int64_t)r0 * ld;
             __syncthreads();      // (first sightings, or the previous block's W_j and y_j, are in place)
             // h, dh and y = z - h of the block's detections
@@ -213,7 +224,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_wide_window(const
                 L[r * kbmax + rr] = acc + (r == rr ? nz.r_unc : 0.0);
             }
             __syncthreads();
-            // S_jj = L_jj L_jj^T, left-looking, as ekf_batch_large.hip
+            // S_jj = L_jj L_jj^T, left-looking, as ekf_batch_impl.h (pivots recomputed by every thread of the column)
             for (int j = 0; j < kb; ++j) {
                 if (tid >= j && tid < kb) {
                     const double* Lj = L + j * kbmax;
@@ -235,7 +246,9 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_wide_window(const
                 if (*flag) break;
             }
             if (*flag) break;
-            // W_j = L_jj^-1 A_j and y_j <- L_jj^-1 y_j: thread c substitutes column c (c = N: y_j) in its slice of R
+            // W_j = L_jj^-1 A_j and y_j <- L_jj^-1 y_j: thread c substitutes column c (c = N: y_j).  A column of A_j is
+            // copied to the thread's own slice of R ([i][thread]: the lanes of a wave read consecutive doubles),
+            // substituted there and written back once
             for (int c = tid; c <= N; c += nt) {
                 double* v = c == N ? y + r0 : R + tid;
                 const int vs = c == N ? 1 : nt;
@@ -284,11 +297,12 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_wide_window(const
                 ekf_inject_rot_block(st + c0, dx + c0, tid == 0);
             }
         }
-        // P <- (P+Q) - W^T W, one sweep per block of rows: the covariance update of ekf_batch_large.hip on W_j (Q with the
-        // first).  Rows l in [kb, kbp) of the panel and of w are zero: fma(0, 0, acc) = acc (acc is never -0).
+        // P <- (P+Q) - W^T W, one sweep per block of rows W_j (Q with the first).  Rows l in [kb, kbp) of the panel and of
+        // w are zero: fma(0, 0, acc) = acc (acc is never -0), so padding the chain to a multiple of 4 leaves every
+        // entry's bits as they are.
         double* WT = R;      // [256 rows of the panel][kbp]
-        for (int j0 = 0; j0 < m; j0 += MB) {
-            const int kb = RD * min(MB, m - j0), kbp = (kb + 3) & ~3;
+        for (int j0 = 0; j0 < blocks_end; j0 += MB) {
+            const int kb = ONE_BLOCK ? k : RD * min(MB, m - j0), kbp = (kb + 3) & ~3;
             const double* Wj = A + (int64_t)RD * j0 * ld;
             for (int cb = 0; cb < N; cb += nt) {
                 const int c = cb + tid;
@@ -377,15 +391,25 @@ extern "C" size_t ekf_batch_wide_lds_bytes(int model, int kmax) {
     return model == 1 ? wide_lds_bytes_of<1>(kmax) : wide_lds_bytes_of<0>(kmax);
 }
 
-__global__ __launch_bounds__(256) void ekf_batch_wide_window_kernel(EkfBatchLargeWindow g) { ekf_batch_wide_window<0>(g); }
+__global__ __launch_bounds__(256) void ekf_batch_wide_window_kernel(EkfBatchLargeWindow g) {
+    ekf_batch_wide_window<0, false>(g);
+}
 __global__ __launch_bounds__(256) void ekf_batch_wide_rot_window_kernel(EkfBatchLargeWindow g) {
-    ekf_batch_wide_window<1>(g);
+    ekf_batch_wide_window<1, false>(g);
+}
+__global__ __launch_bounds__(256) void ekf_batch_one_block_window_kernel(EkfBatchLargeWindow g) {
+    ekf_batch_wide_window<0, true>(g);
+}
+__global__ __launch_bounds__(256) void ekf_batch_one_block_rot_window_kernel(EkfBatchLargeWindow g) {
+    ekf_batch_wide_window<1, true>(g);
 }
 
-void ekf_launch_batch_wide_window(int model, const EkfBatchLargeWindow& g, int members, hipStream_t s) {
-    static bool once[2] = {false, false};
+void ekf_launch_batch_wide_window(int model, bool one_block, const EkfBatchLargeWindow& g, int members, hipStream_t s) {
+    static bool once[2][2] = {{false, false}, {false, false}};
     if (model == 1)
-        wide_launch<1>(ekf_batch_wide_rot_window_kernel, once[1], g, members, s);
+        wide_launch<1>(one_block ? ekf_batch_one_block_rot_window_kernel : ekf_batch_wide_rot_window_kernel,
+                       once[1][one_block], g, members, s);
     else
-        wide_launch<0>(ekf_batch_wide_window_kernel, once[0], g, members, s);
+        wide_launch<0>(one_block ? ekf_batch_one_block_window_kernel : ekf_batch_wide_window_kernel, once[0][one_block], g,
+                       members, s);
 }

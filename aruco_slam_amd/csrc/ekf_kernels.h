@@ -261,8 +261,9 @@ extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);
 extern "C" size_t ekf_batch_rot_lds_bytes(int kmax, int lda);
 void ekf_launch_batch_window(const EkfBatchWindow& a, int members, hipStream_t s);
 void ekf_launch_batch_rot_window(const EkfBatchWindow& a, int members, hipStream_t s);
-// Dictionary-sized maps (ekf_batch_large.hip, EKF_FLAG_BATCH_LARGE_MAPS): N <= 1024, ld <= 1024; A / W of a member in the
-// batch workspace, [k][ld] at w_stride doubles per member (kmax and window fields of `w` as above, w.lda unused)
+// Dictionary-sized maps (EKF_FLAG_BATCH_LARGE_MAPS) and wide frames (EKF_FLAG_BATCH_WIDE_FRAMES), one kernel per model in
+// ekf_batch_wide.hip: N <= 1024, ld <= 1024; A / W of a member in the batch workspace, [k][ld] at w_stride = rd max_visible ld
+// doubles per member (kmax and window fields of `w` as above, w.lda unused)
 #define EKF_BATCH_LARGE_MAX_LANDMARKS 338       // EKF: N = 3 n + 10 <= 1024
 #define EKF_BATCH_ROT_LARGE_MAX_LANDMARKS 101   // EKF_Rotations: N = 10 n + 10 <= 1020
 struct EkfBatchLargeWindow {
@@ -270,14 +271,13 @@ struct EkfBatchLargeWindow {
     double* W;                      // [B][w_stride]
     int64_t w_stride;
 };
-extern "C" size_t ekf_batch_large_lds_bytes(int model, int kmax);
-void ekf_launch_batch_large_window(int model, const EkfBatchLargeWindow& g, int members, hipStream_t s);
-// Wide frames (ekf_batch_wide.hip, EKF_FLAG_BATCH_WIDE_FRAMES): up to 64 / 50 detections per frame on the large-map limits,
-// same EkfBatchLargeWindow (A / W [k][ld] of a member in the workspace, w_stride = rd max_visible ld)
+// wide frames: up to 64 / 50 detections per frame, in blocks of EKF_BATCH_MAX_VISIBLE / EKF_BATCH_ROT_MAX_VISIBLE (a frame of
+// a large-map batch is one block)
 #define EKF_BATCH_WIDE_MAX_VISIBLE 64       // EKF: k = 3 m <= 192 rows
 #define EKF_BATCH_ROT_WIDE_MAX_VISIBLE 50   // EKF_Rotations: k = 7 m <= 350 rows
 extern "C" size_t ekf_batch_wide_lds_bytes(int model, int kmax);
-void ekf_launch_batch_wide_window(int model, const EkfBatchLargeWindow& g, int members, hipStream_t s);
+// one_block: no frame is wider than one block (a batch without the wide flag): the instance without the loops over blocks
+void ekf_launch_batch_wide_window(int model, bool one_block, const EkfBatchLargeWindow& g, int members, hipStream_t s);
 // Replicas of one log (ekf_batch_replicas.hip): out[r][d][c] = poses[d][c] + sigma[r][c] g_c(seed, r0 + r, d), c < 6, for
 // `count` <= EKF_REPLICA_CHUNK replicas per launch (sigma travels in the kernel arguments); g: Philox4x32-10 + Box-Muller,
 // the definition in include/ekf_slam_hip.h (ekf_batch_replica_poses)

@@ -32,8 +32,8 @@ def test_new_symbols_are_declared_and_exported(lib):
 @pytest.mark.parametrize("src,pattern,count", [
     ("ekf_batch.hip", r"ekf_batch_window_kernel", 1),
     ("ekf_batch_rot.hip", r"ekf_batch_rot_window_kernel", 1),
-    ("ekf_batch_large.hip", r"ekf_batch_large_(rot_)?window_kernel", 2),
     ("ekf_batch_wide.hip", r"ekf_batch_wide_(rot_)?window_kernel", 2),
+    ("ekf_batch_wide.hip", r"ekf_batch_one_block_(rot_)?window_kernel", 2),
 ])
 def test_gated_kernels_use_no_scratch_no_spill_no_static_lds(src, pattern, count):
     text = (Path(__file__).resolve().parent.parent / "aruco_slam_amd" / "csrc" / "ekf_batch_impl.h").read_text()

@@ -1,9 +1,13 @@
-"""Dictionary-sized batch maps (``EKFBatch(large_maps=True)``, kernel ekf_batch_large.hip) on an MI355X: the same bits as the
-one-column kernels where both run, the extended-precision step up to N = 1024, the single-filter path at n = 250 / 100, the
-covariance invariants, composition and window independence, capacity errors and interop with ``EKF``."""
+"""Dictionary-sized batch maps (``EKFBatch(large_maps=True)``, the one-block instances of the kernels of ekf_batch_wide.hip)
+on an MI355X: the same bits as the one-column kernels where both run and pinned bits just above them, the extended-precision
+step up to N = 1024, the single-filter path at n = 250 / 100, the covariance invariants, composition and window independence,
+capacity errors and interop with ``EKF``."""
+import hashlib
+
 import numpy as np
 import pytest
 
+import gating_util as gu
 import update_sweep_util as sw
 from conftest import rel_err, report
 
@@ -82,6 +86,56 @@ def test_same_bits_as_the_one_column_kernel(model, n, quat):
             assert np.array_equal(x, y, equal_nan=True), b      # (the failed member keeps its NaN first sighting)
         assert one.landmarks[b] == big.landmarks[b] and one.num_landmarks[b] == big.num_landmarks[b]
     assert np.array_equal(one.cov_t.cpu().numpy(), big.cov_t.cpu().numpy(), equal_nan=True)
+
+
+# Above 82 / 24 landmarks no second kernel computes the same frames, so the bits are pinned: sha256[:16] of
+# test_bits_just_past_one_column_block's two runs, taken on an MI355X with the library of the last commit that had the
+# large-map kernels in a file of their own (ekf_batch_large.hip); the kernels of ekf_batch_wide.hip give the same
+PINNED_MAPS = {"ekf": 86, "ekf_rotations": 26}        # N = 268 / 270: two column blocks, two row panels per sweep
+PINNED_DIGESTS = {
+    ("ekf", "plain"): "f6dc9b8398a35b36",
+    ("ekf", "gated"): "48871a8c83b8a545",
+    ("ekf_rotations", "plain"): "0c4c85672220a5be",
+    ("ekf_rotations", "gated"): "ffd82db6d36be9be",
+}
+
+
+def _pinned_logs(model):
+    """Four short logs: bootstrap frames of 16 / 8 first sightings, six steady frames; member 1 with gating_util's gross
+    outliers (frames of up to 16 / 8 detections) and an empty frame that reaches the kernel, member 3 on half the map."""
+    n, hi = PINNED_MAPS[model], VISIBLE[model]
+    logs = [_ragged(model, n if j < 3 else n // 2, (1, hi - 2), 6, seed=40 + j, bootstrap_m=hi) for j in range(4)]
+    logs[1] = gu.dirty_log(model, logs[1], seed=1)[0]
+    assert max(int(np.diff(lg["offsets"]).max()) for lg in logs) == hi and (np.diff(logs[1]["offsets"]) == 0).sum() == 1
+    return [{k: v for k, v in lg.items() if k != "has_detections"} for lg in logs]
+
+
+def _pinned_digest(batch, *fields):
+    h = hashlib.sha256()
+    for field in fields:
+        for x in field:
+            h.update(np.ascontiguousarray(x, dtype=np.float64).tobytes())
+    for b in range(batch.members):
+        for x in _snapshot(batch, b):
+            h.update(x.tobytes())
+    return h.hexdigest()[:16]
+
+
+@pytest.mark.parametrize("model", ["ekf", "ekf_rotations"])
+def test_bits_just_past_one_column_block(model):
+    logs = _pinned_logs(model)
+    kw = {"max_landmarks": PINNED_MAPS[model], "quat_update": "scalar_first" if model == "ekf" else None}
+    plain = _batch(4, model, **kw)
+    assert plain.large_maps and plain.ld > 256
+    digest = _pinned_digest(plain, plain.process_detection_logs(logs))
+    gated = _batch(4, model, gate=np.array([np.inf, gu.GATES[model], np.inf, np.inf]), **kw)
+    out = gated.process_detection_logs(logs, nis=True, cam_cov=True, mahal=True)
+    digest_gated = _pinned_digest(gated, out.trajectory, out.nis, out.cam_cov, out.mahal)
+    report(f"batch_large_pinned[{model}]", plain=digest, gated=digest_gated)
+    assert plain.status() == gated.status() == [0] * 4 and plain.num_landmarks[0] == PINNED_MAPS[model]
+    assert out.rejected[1].any() and not out.rejected[1].all() and not any(out.rejected[b].any() for b in (0, 2, 3))
+    assert digest == PINNED_DIGESTS[(model, "plain")]
+    assert digest_gated == PINNED_DIGESTS[(model, "gated")]
 
 
 @pytest.mark.parametrize("model,sizes,top", [("ekf", (83, 167, 253, 338), 338), ("ekf_rotations", (25, 60, 101), 101)])

@@ -94,8 +94,8 @@ def _kernel_resources(src, pattern):
     ("ekf_batch_replicas.hip", r"ekf_replica_poses_kernel", 1),
     ("ekf_batch.hip", r"ekf_batch_window_kernel", 1),
     ("ekf_batch_rot.hip", r"ekf_batch_rot_window_kernel", 1),
-    ("ekf_batch_large.hip", r"ekf_batch_large_(rot_)?window_kernel", 2),
     ("ekf_batch_wide.hip", r"ekf_batch_wide_(rot_)?window_kernel", 2),
+    ("ekf_batch_wide.hip", r"ekf_batch_one_block_(rot_)?window_kernel", 2),
 ])
 def test_kernels_use_no_scratch_no_spill_no_static_lds(src, pattern, count):
     """No scratch memory, no VGPR spills (SGPR spills go to VGPR lanes, as before these outputs), no static LDS."""
@@ -107,19 +107,20 @@ def test_kernels_use_no_scratch_no_spill_no_static_lds(src, pattern, count):
 
 def test_window_kernels_dynamic_lds_is_unchanged(lib):
     """The new outputs live in HBM only: the LDS of every window kernel is what the layouts documented before them give
-    (ekf_batch_impl.h; ekf_batch_large.hip: 149,680 bytes at kmax = 56; ekf_batch_wide.hip: 123,920 at the EKF's kmax = 192,
-    and at the rotations' kmax = 350 R | L | 1 / L_jj | J of a 56-row block, y [350] and 50 + 4 ints: 152,200)."""
+    (ekf_batch_impl.h; ekf_batch_wide.hip: R | L | 1 / L_jj | J of a block of at most 48 / 56 rows, y [kmax] and 64 + 4 /
+    50 + 4 ints: with one block, as in a large-map call, 122,768 bytes at the EKF's kmax = 48 and 149,848 at the rotations'
+    kmax = 56; 123,920 at the EKF's kmax = 192 and 152,200 at the rotations' kmax = 350)."""
     f = {}
     for name, args in (("ekf_batch_lds_bytes", [ctypes.c_int, ctypes.c_int]),
                        ("ekf_batch_rot_lds_bytes", [ctypes.c_int, ctypes.c_int]),
-                       ("ekf_batch_large_lds_bytes", [ctypes.c_int, ctypes.c_int]),
                        ("ekf_batch_wide_lds_bytes", [ctypes.c_int, ctypes.c_int])):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, ctypes.c_size_t
         f[name] = fn
     assert f["ekf_batch_lds_bytes"](48, 260) == 8 * (48 * 260 + 48 * 48 + 48 + 48 * 13 + 260) + 4 * (16 + 4)
     assert f["ekf_batch_rot_lds_bytes"](56, 260) == 8 * (56 * 260 + 56 * 56 + 56 + 56 * 20 + 260) + 4 * (8 + 4)
-    assert f["ekf_batch_large_lds_bytes"](1, 56) == 149680
+    assert f["ekf_batch_wide_lds_bytes"](0, 48) == 8 * (256 * 48 + 48 * 48 + 48 + 48 * 13 + 48) + 4 * (64 + 4) == 122768
+    assert f["ekf_batch_wide_lds_bytes"](1, 56) == 8 * (256 * 56 + 56 * 56 + 56 + 56 * 20 + 56) + 4 * (50 + 4) == 149848
     assert f["ekf_batch_wide_lds_bytes"](0, 192) == 123920
     assert f["ekf_batch_wide_lds_bytes"](1, 350) == 8 * (256 * 56 + 56 * 56 + 56 + 56 * 20 + 350) + 4 * (50 + 4) == 152200
 

@@ -112,8 +112,9 @@ def test_workspace_growth_follows_the_formula(model):
 
 
 def test_wide_frame_kernels_use_no_scratch_and_fit_the_lds():
-    """ekf_batch_wide.hip compiled alone: two kernels, no scratch memory, no spills, no static LDS.  The dynamic LDS of
-    the largest kmax of each model fits the 160 KiB of a CU."""
+    """ekf_batch_wide.hip compiled alone: two kernels and their two one-block instances (the ones a large-map batch
+    runs), no scratch memory, no spills, no static LDS.  The dynamic LDS of the largest kmax of each model fits the
+    160 KiB of a CU."""
     from aruco_slam_amd import _build
     assert "ekf_batch_wide.hip" in _build.SOURCES
     with tempfile.TemporaryDirectory() as tmp:
@@ -122,15 +123,17 @@ def test_wide_frame_kernels_use_no_scratch_and_fit_the_lds():
                         str(_build.CSRC / "ekf_batch_wide.hip"), "-o", str(out)], check=True, capture_output=True)
         text = out.read_text()
     names = re.findall(r"\.name:\s+(\S*_kernel\S*)\n", text)
-    assert len(names) == 2, names
-    assert any("ekf_batch_wide_window_kernel" in n for n in names)
-    assert any("ekf_batch_wide_rot_window_kernel" in n for n in names)
-    for kernel in ("ekf_batch_wide_window_kernel", "ekf_batch_wide_rot_window_kernel"):
+    kernels = ("ekf_batch_wide_window_kernel", "ekf_batch_wide_rot_window_kernel", "ekf_batch_one_block_window_kernel",
+               "ekf_batch_one_block_rot_window_kernel")
+    assert len(names) == 4, names
+    for kernel in kernels:
+        assert any(kernel in n for n in names), kernel
+    for kernel in kernels:
         pat = r"\.name:\s+(\S*" + kernel + r"\S*)\n(?:.*\n)*?\s+\.{}:\s+(\d+)"
         for field in ("private_segment_fixed_size", "vgpr_spill_count"):
             found = re.findall(pat.format(field), text)
             assert len(found) == 1 and int(found[0][1]) == 0, (kernel, field, found)
-    assert re.findall(r"\.group_segment_fixed_size:\s+(\d+)", text) == ["0", "0"]
+    assert re.findall(r"\.group_segment_fixed_size:\s+(\d+)", text) == ["0"] * 4
     _, lib = _lib()
     lds = lib.ekf_batch_wide_lds_bytes
     lds.argtypes, lds.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_size_t
@@ -140,10 +143,9 @@ def test_wide_frame_kernels_use_no_scratch_and_fit_the_lds():
         need = 8 * (256 * kw + kw * kw + kw * jc + kmax)       # at least the column / panel region, L, J and y
         assert need < lds(model, kmax) <= 160 * 1024, (model, lds(model, kmax))
         assert lds(model, kmax - rd) < lds(model, kmax)
-        # up to one block the budget is the large-map kernel's (same regions, y in place of nothing larger)
-        large = lib.ekf_batch_large_lds_bytes
-        large.argtypes, large.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_size_t
-        assert lds(model, kw) <= large(model, kw) + 4 * (vis - (16 if model == 0 else 8))
+        # up to one block, as in a large-map call, the budget is the layout's regions and nothing more: R [256][kw] |
+        # L [kw][kw] | 1 / L_jj [kw] | J [kw][jc] | y [kw] doubles and one first column per detection + 4 ints
+        assert lds(model, kw) <= 8 * (256 * kw + kw * kw + kw + kw * jc + kw) + 4 * (vis + 4)
 
 
 @pytest.mark.parametrize("model,plain,top", [("ekf", 16, 64), ("ekf_rotations", 8, 50)])

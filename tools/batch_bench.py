@@ -2,10 +2,11 @@
 
 Seeded synthetic.ragged_log logs, one seed per member, a bootstrap segment that first-sights every landmark, then 500 steady
 frames.  --model ekf (EKF): n = 50 landmarks (DICT_5X5_50), m ~ U[1, 10] per frame.  --model ekf_rotations (EKF_Rotations):
-n = 24 (the batch's largest map), m ~ U[1, 8], marker orientations with rvec_sigma = 0.05.  --large-maps: the large-map
-kernel (EKF_FLAG_BATCH_LARGE_MAPS, csrc/ekf_batch_large.hip) with n = 250 (EKF, m ~ U[1, 10]) or n = 100 (EKF_Rotations,
-m ~ U[1, 8]) by default.  --max-visible M: m ~ U[1, M]; above 16 (EKF) / 8 (EKF_Rotations) the batch runs the wide-frame
-kernel (EKF_FLAG_BATCH_WIDE_FRAMES, csrc/ekf_batch_wide.hip) and the single filter takes max_visible = M.  For every batch size: one warm-up call of the same shape,
+n = 24 (the batch's largest map), m ~ U[1, 8], marker orientations with rvec_sigma = 0.05.  --large-maps: large maps
+(EKF_FLAG_BATCH_LARGE_MAPS: the kernel of csrc/ekf_batch_wide.hip, one block per frame) with n = 250 (EKF, m ~ U[1, 10]) or
+n = 100 (EKF_Rotations, m ~ U[1, 8]) by default.  --max-visible M: m ~ U[1, M]; above 16 (EKF) / 8 (EKF_Rotations) the batch
+takes wide frames (EKF_FLAG_BATCH_WIDE_FRAMES, the same kernel with several blocks per frame) and the single filter takes
+max_visible = M.  For every batch size: one warm-up call of the same shape,
 then one timed call (host clock around the call, which ends in a synchronise).  The rate is stepped steady frames of all
 members over wall time; the bootstrap frames run in the warm-up call, so the timed call is the steady segment alone.
 Beside it, the single-filter rate of process_detection_log on member 0's steady segment (same timing rule).  One JSON line

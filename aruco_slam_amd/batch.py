@@ -19,6 +19,14 @@ replica whose detection noise the device draws (``csrc/ekf_batch_replicas.hip``;
 poses a replica consumed).  Runs and sweeps are judged by the filter's own statistics: with ``nis`` / ``cam_cov`` both replay
 calls also return every frame's normalised innovation squared and camera covariance P[0:10, 0:10].
 
+The detector's noise is on the four pixel corners of a marker, and IPPE turns it into what pose noise never gives: a depth
+error that grows with distance, an error that depends on the marker's tilt and, now and then, the other of its two
+solutions.  ``replay_corner_replicas`` replays a log of ``corners`` the same way, the noise drawn in pixels and every pose
+estimated on the device (``csrc/ekf_batch_corner_replicas.hip``, the IPPE of ``hip_backend.estimate_poses``), and returns
+``flipped``: which (replica, detection) pairs got the flipped solution, the ground truth for tuning the gate below.
+``replica_corner_poses`` / ``replica_corners`` return what a replica consumed.  With ``set_camera``,
+``process_detection_logs`` takes logs of ``corners`` as well.
+
 Outliers (IPPE's flipped poses, mis-decoded ids) are kept out by the per-detection chi-square gate: ``gate`` / ``set_gate``
 make every member reject the detections whose own Mahalanobis distance d^2 = r^T S_d^-1 r exceeds its threshold before the
 frame is updated, and ``mahal=True`` returns every detection's d^2, gate or no gate (``ekf_batch_set_gate`` in
@@ -110,6 +118,21 @@ class GatedReplicaReplay(NamedTuple):
     rejected: np.ndarray
 
 
+class CornerReplicaReplay(NamedTuple):
+    """``replay_corner_replicas``: ``trajectory`` [B, F, 7], ``nis`` [B, F] and ``cam_cov`` [B, F, 10, 10] (None unless
+    asked), ``dof`` [F], ``mahal`` and ``rejected`` None; with ``mahal=True`` or a gate set ``dof`` [B, F] counts each
+    member's surviving detections and ``mahal`` / ``rejected`` are [B, D] as in ``GatedReplicaReplay``.  ``flipped`` [B, D]
+    bool, aligned with the log's own detections: IPPE returned the candidate farther from the clean pose (the definition
+    in ``include/ekf_slam_hip.h``); False for the detections the planner dropped."""
+    trajectory: np.ndarray
+    nis: np.ndarray | None
+    dof: np.ndarray
+    cam_cov: np.ndarray | None
+    mahal: np.ndarray | None
+    rejected: np.ndarray | None
+    flipped: np.ndarray
+
+
 def gate_array(gate, members: int):
     """``gate`` (None, a scalar or [members]) as None or a contiguous [members] array; every entry must be > 0 (``inf``:
     that member's gate is off); ``ValueError`` otherwise."""
@@ -142,6 +165,37 @@ def replica_sigma(sigma, replicas: int) -> np.ndarray:
     if not np.isfinite(s).all() or (s < 0).any():
         raise ValueError("sigma must be finite and >= 0")
     return np.ascontiguousarray(s)
+
+
+def replica_sigma_px(sigma_px, replicas: int) -> np.ndarray:
+    """``sigma_px`` (a scalar or [replicas]; finite, >= 0) as a contiguous [replicas] array; ``ValueError`` otherwise."""
+    s = np.asarray(sigma_px, dtype=np.float64)
+    if s.ndim == 0:
+        s = np.broadcast_to(s, (replicas,))
+    elif s.shape != (replicas,):
+        raise ValueError(f"sigma_px must be a scalar or [{replicas}], got shape {s.shape}")
+    if not np.isfinite(s).all() or (s < 0).any():
+        raise ValueError("sigma_px must be finite and >= 0")
+    return np.ascontiguousarray(s)
+
+
+def camera_arrays(camera_matrix, dist_coeffs=None, marker_size: float = 0.16):
+    """The camera of the pose front end as the C ABI takes it: (camera matrix [9], distortion coefficients [0..8],
+    marker size); ``ValueError`` for another shape, non-finite values, focal lengths or a marker size that are not > 0."""
+    k = np.asarray(camera_matrix, dtype=np.float64)
+    if k.shape != (3, 3):
+        raise ValueError(f"camera_matrix must be 3 x 3, got shape {k.shape}")
+    d = np.asarray([] if dist_coeffs is None else dist_coeffs, dtype=np.float64).reshape(-1)
+    if d.size > 8:
+        raise ValueError(f"0..8 distortion coefficients (k1 k2 p1 p2 k3 k4 k5 k6) are supported, got {d.size}")
+    if not (np.isfinite(k).all() and np.isfinite(d).all()):
+        raise ValueError("camera_matrix and dist_coeffs must be finite")
+    if not (k[0, 0] > 0 and k[1, 1] > 0):
+        raise ValueError("focal lengths must be > 0")
+    size = float(marker_size)
+    if not (np.isfinite(size) and size > 0):
+        raise ValueError(f"marker_size must be > 0, got {marker_size}")
+    return np.ascontiguousarray(k.reshape(9)), np.ascontiguousarray(d), size
 
 
 def _replica_range(first_replica, replicas: int) -> int:
@@ -188,6 +242,64 @@ def replica_poses(poses, sigma, seed: int, *, replicas: int | None = None, first
     return out.cpu().numpy()
 
 
+def _replica_corner_outputs(want, corners, sigma_px, seed, camera_matrix, dist_coeffs, marker_size, replicas, first_replica,
+                            device):
+    """``ekf_batch_replica_corners`` with the outputs named in ``want`` (of "poses", "flipped", "noisy"), as host arrays."""
+    import torch
+    lib = load_library()
+    if not torch.cuda.is_available():
+        raise RuntimeError("replica noise is generated on a HIP device (no CPU fallback)")
+    corners = np.ascontiguousarray(corners, dtype=np.float64)
+    if corners.ndim != 3 or corners.shape[1:] != (4, 2):
+        raise ValueError(f"corners must have shape (D, 4, 2), got {corners.shape}")
+    if replicas is None:
+        if np.ndim(sigma_px) != 1:
+            raise ValueError("give replicas= unless sigma_px is [R]")
+        replicas = np.shape(sigma_px)[0]
+    R, D = int(replicas), corners.shape[0]
+    sig = replica_sigma_px(sigma_px, R)
+    r0 = _replica_range(first_replica, R)
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2**64)")
+    k, d, size = camera_arrays(camera_matrix, dist_coeffs, marker_size)
+    dev = torch.device(device)
+    shapes = {"poses": ((R, D, 6), torch.float64), "flipped": ((R, D), torch.uint8), "noisy": ((R, D, 4, 2), torch.float64)}
+    with torch.cuda.device(dev):
+        src = torch.from_numpy(corners).to(dev)
+        out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=dev) for name in want}
+        ptr = (lambda name: out[name].data_ptr() if name in out and out[name].numel() else None)
+        stream = torch.cuda.current_stream(dev)
+        rc = lib.ekf_batch_replica_corners(src.data_ptr() if D else None, D, _dptr(sig), R, seed, r0, size, _dptr(k),
+                                           _dptr(d) if d.size else None, int(d.size), ptr("poses"), ptr("flipped"),
+                                           ptr("noisy"), stream.cuda_stream)
+        if rc != 0:
+            raise EkfError(rc, lib.ekf_last_error_string().decode())
+        stream.synchronize()
+    return {name: t.cpu().numpy() for name, t in out.items()}
+
+
+def replica_corner_poses(corners, sigma_px, seed: int, camera_matrix, dist_coeffs=None, marker_size: float = 0.16, *,
+                         replicas: int | None = None, first_replica: int = 0, flipped: bool = False,
+                         device: str = "cuda:0"):
+    """The poses [R, D, 6] that replicas ``first_replica`` .. ``first_replica + R - 1`` of a log with ``corners`` [D, 4, 2]
+    (pixels) consume in ``EKFBatch.replay_corner_replicas`` (``ekf_batch_replica_corners``, the same device code): IPPE of
+    ``corners[d][i] + sigma_px[r] (g_u, g_v)`` with the Philox4x32-10 / Box-Muller normals defined in
+    ``include/ekf_slam_hip.h``.  ``sigma_px``: a scalar or [R]; R = ``replicas``, or sigma_px's length.  With ``flipped``
+    it returns ``(poses, flipped [R, D] bool)``: the pairs for which IPPE returned the candidate farther from the pose of
+    the clean corners."""
+    out = _replica_corner_outputs(("poses", "flipped") if flipped else ("poses",), corners, sigma_px, seed, camera_matrix,
+                                  dist_coeffs, marker_size, replicas, first_replica, device)
+    return (out["poses"], out["flipped"].astype(bool)) if flipped else out["poses"]
+
+
+def replica_corners(corners, sigma_px, seed: int, camera_matrix, dist_coeffs=None, marker_size: float = 0.16, *,
+                    replicas: int | None = None, first_replica: int = 0, device: str = "cuda:0") -> np.ndarray:
+    """The noisy corners [R, D, 4, 2] behind ``replica_corner_poses`` (same arguments)."""
+    return _replica_corner_outputs(("noisy",), corners, sigma_px, seed, camera_matrix, dist_coeffs, marker_size, replicas,
+                                   first_replica, device)["noisy"]
+
+
 def _iptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
@@ -205,6 +317,7 @@ class EKFBatch:
     ``set_gate`` (kept in ``self.gate``)."""
 
     gate = None        # [B] chi-square gate per member, or None: no gate (set_gate)
+    camera = None      # (camera matrix [9], distortion coefficients, marker size) of corner logs, or None (set_camera)
 
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
                  quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf",
@@ -307,6 +420,12 @@ class EKFBatch:
         self._check(self.lib.ekf_batch_set_gate(self.h, _dptr(g) if g is not None else None))
         self.gate = g
 
+    def set_camera(self, camera_matrix, dist_coeffs=None, marker_size: float = 0.16) -> None:
+        """The camera and marker size of logs that carry ``corners`` (``process_detection_logs``,
+        ``replay_corner_replicas``): the arguments of ``hip_backend.estimate_poses``, kept on the host.  Bad values raise
+        ``ValueError`` and nothing changes."""
+        self.camera = camera_arrays(camera_matrix, dist_coeffs, marker_size)
+
     def _rejected(self, mahal: np.ndarray, member) -> np.ndarray:
         """``mahal > gate`` of the detections' members (NaN and 0 are never rejected)."""
         gate = self.gate
@@ -324,8 +443,10 @@ class EKFBatch:
     # -- replay ------------------------------------------------------------------------------------------------------
     def process_detection_logs(self, logs, *, nis: bool = False, cam_cov: bool = False, mahal: bool = False):
         """One log per member (``None``: no log), each a dict of the replay layout ``ids [D]``, ``poses [D,6]``,
-        ``offsets [F+1]`` and optionally ``has_detections [F]``.  Returns the camera pose ``state[0:7]`` after every frame,
-        one ``(F_b, 7)`` array per member.  A malformed log raises ``ValueError``, a log that needs more landmarks or
+        ``offsets [F+1]`` and optionally ``has_detections [F]``.  After ``set_camera`` a log may carry ``corners [D,4,2]``
+        (pixels) instead of ``poses``: the corner logs of a call are estimated by one ``ekf_estimate_poses_device`` launch on
+        the batch's stream and their poses never leave the device; a log with both keys or with neither is a ``ValueError``.
+        Returns the camera pose ``state[0:7]`` after every frame, one ``(F_b, 7)`` array per member.  A malformed log raises ``ValueError``, a log that needs more landmarks or
         detections per frame than the batch holds ``EkfError`` (EKF_ERR_CAPACITY); either way before anything runs, and no
         member (``landmarks`` included) changes.
         With ``nis`` or ``cam_cov`` it returns a ``BatchReplay`` of per-member lists instead: the trajectories, each
@@ -338,6 +459,7 @@ class EKFBatch:
         if len(logs) != self.members:
             raise ValueError(f"need {self.members} logs (None for a member without one), got {len(logs)}")
         plans, index, offsets, frames, poses = [], [], [], [0], []
+        corner_parts = []       # (first row, kept corners [n,4,2]) of every log that carries corners
         base = 0
         for b, log in enumerate(logs):
             if log is None:
@@ -346,9 +468,20 @@ class EKFBatch:
                 continue
             plan = plan_detection_log(self.landmarks[b], self.num_landmarks[b], log["ids"], log["offsets"],
                                       log.get("has_detections"))
-            p = np.asarray(log["poses"], dtype=np.float64)
-            if p.shape != (plan.keep.shape[0], 6):
-                raise ValueError(f"member {b}: poses must have shape ({plan.keep.shape[0]}, 6), got {p.shape}")
+            if ("poses" in log) == ("corners" in log):
+                raise ValueError(f"member {b}: a log carries either poses [D,6] or corners [D,4,2]")
+            if "corners" in log:
+                if self.camera is None:
+                    raise ValueError(f"member {b}: a log of corners needs set_camera() first")
+                c = np.asarray(log["corners"], dtype=np.float64)
+                if c.shape != (plan.keep.shape[0], 4, 2):
+                    raise ValueError(f"member {b}: corners must have shape ({plan.keep.shape[0]}, 4, 2), got {c.shape}")
+                corner_parts.append((base, c[plan.keep]))
+                p = np.zeros((plan.keep.shape[0], 6))       # (filled on the device: _estimate_corner_logs)
+            else:
+                p = np.asarray(log["poses"], dtype=np.float64)
+                if p.shape != (plan.keep.shape[0], 6):
+                    raise ValueError(f"member {b}: poses must have shape ({plan.keep.shape[0]}, 6), got {p.shape}")
             plans.append(plan)
             index.append(plan.index)
             offsets.append(plan.offsets[1:] + base)
@@ -358,6 +491,8 @@ class EKFBatch:
         index = np.concatenate(index).astype(np.int32) if index else np.zeros(0, np.int32)
         offsets = np.concatenate([np.zeros(1, np.int64)] + offsets).astype(np.int64)
         poses = np.ascontiguousarray(np.concatenate(poses) if poses else np.zeros((0, 6)))
+        if sum(c.shape[0] for _, c in corner_parts):
+            poses = self._estimate_corner_logs(poses, corner_parts)
         if gated:
             traj, nis_v, cov_v, mahal_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses,
                                                                nis=nis, cam_cov=cam_cov, mahal=True)
@@ -391,6 +526,29 @@ class EKFBatch:
         return BatchReplay([traj[sl] for sl in split], [nis_v[sl] for sl in split] if nis else None,
                            [dof[sl] for sl in split], [cov_v[sl] for sl in split] if cam_cov else None)
 
+    def _estimate_corner_logs(self, poses: np.ndarray, corner_parts):
+        """``poses`` [D, 6] of a call as a device tensor whose rows ``first .. first + n`` of every ``(first, corners
+        [n,4,2])`` in ``corner_parts`` hold the IPPE poses of those corners: one ``ekf_estimate_poses_device`` launch for
+        all of them on the batch's stream, then one device-to-device copy per corner log (none if every log has corners)."""
+        torch = self._torch
+        k, d, size = self.camera
+        corners = np.ascontiguousarray(np.concatenate([c for _, c in corner_parts]))
+        count = corners.shape[0]
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            corners_t = torch.from_numpy(corners).to(self.device)
+            est = torch.empty((count, 6), dtype=torch.float64, device=self.device)
+            self._check(self.lib.ekf_estimate_poses_device(corners_t.data_ptr(), count, size, _dptr(k),
+                                                           _dptr(d) if d.size else None, int(d.size), est.data_ptr(),
+                                                           self.stream.cuda_stream))
+            if count == poses.shape[0]:
+                return est
+            poses_t = torch.from_numpy(poses).to(self.device)
+            at = 0
+            for first, c in corner_parts:
+                poses_t[first:first + c.shape[0]].copy_(est[at:at + c.shape[0]])
+                at += c.shape[0]
+        return poses_t
+
     def _adopt_plans(self, plans) -> None:
         """Landmark tables after a call, from the planned first sightings and the device's counts."""
         counts = self._num_landmarks_device()
@@ -421,16 +579,7 @@ class EKFBatch:
         seed = int(seed)
         if not 0 <= seed < 2 ** 64:
             raise ValueError("seed must be in [0, 2**64)")
-        if any(t != self.landmarks[0] for t in self.landmarks[1:]) or len(set(self.num_landmarks)) > 1:
-            raise ValueError("replay_replicas needs every member's landmark table to be the same (reset() first)")
-        plan = plan_detection_log(self.landmarks[0], self.num_landmarks[0], log["ids"], log["offsets"],
-                                  log.get("has_detections"))
-        p = np.asarray(log["poses"], dtype=np.float64)
-        if p.shape != (plan.keep.shape[0], 6):
-            raise ValueError(f"poses must have shape ({plan.keep.shape[0]}, 6), got {p.shape}")
-        poses = np.ascontiguousarray(p[plan.keep])
-        idx = np.ascontiguousarray(plan.index, dtype=np.int32)
-        fo = np.ascontiguousarray(plan.offsets, dtype=np.int64)
+        plan, poses, idx, fo = self._plan_replica_log(log, "poses", (6,), "replay_replicas")
         F, D, B = fo.shape[0] - 1, idx.shape[0], self.members
         torch = self._torch
         nbytes = C.c_size_t()
@@ -455,23 +604,97 @@ class EKFBatch:
             self.stream.synchronize()
         self._adopt_plans([plan] * B)
         if gated:
-            keep = np.asarray(plan.keep, dtype=bool)
-            mahal_v = mahal_t.cpu().numpy()
-            rej_v = self._rejected(mahal_v, np.arange(B)[:, None])
-            full = np.full((B, keep.shape[0]), np.nan)
-            full[:, keep] = mahal_v
-            rej = np.zeros((B, keep.shape[0]), dtype=bool)
-            rej[:, keep] = rej_v
-            dof = np.stack([_surviving_dof(RD[self.model], fo, r) for r in rej_v]) if B else np.zeros((0, F), np.int64)
+            full, rej, dof = self._replica_gate_outputs(plan, fo, mahal_t.cpu().numpy())
             return GatedReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, dof,
                                       cov_t.cpu().numpy() if cam_cov else None, full, rej)
         return ReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None,
                              RD[self.model] * np.diff(fo), cov_t.cpu().numpy() if cam_cov else None)
 
+    def _plan_replica_log(self, log, key: str, tail: tuple, what: str):
+        """The one log of a replica call planned on the members' common landmark table: (plan, the kept rows of
+        ``log[key]`` [D, *tail], landmark indices [D], frame offsets [F+1]); ``ValueError`` if the tables differ or the
+        array has another shape."""
+        if any(t != self.landmarks[0] for t in self.landmarks[1:]) or len(set(self.num_landmarks)) > 1:
+            raise ValueError(f"{what} needs every member's landmark table to be the same (reset() first)")
+        plan = plan_detection_log(self.landmarks[0], self.num_landmarks[0], log["ids"], log["offsets"],
+                                  log.get("has_detections"))
+        v = np.asarray(log[key], dtype=np.float64)
+        if v.shape != (plan.keep.shape[0],) + tail:
+            raise ValueError(f"{key} must have shape {(plan.keep.shape[0],) + tail}, got {v.shape}")
+        return (plan, np.ascontiguousarray(v[plan.keep]), np.ascontiguousarray(plan.index, dtype=np.int32),
+                np.ascontiguousarray(plan.offsets, dtype=np.int64))
+
+    def _replica_gate_outputs(self, plan, fo: np.ndarray, mahal_v: np.ndarray):
+        """(mahal [B, D], rejected [B, D], dof [B, F]) of a replica call from the device's distances over the planned
+        detections: back on the log's own detections (the planner's drops: NaN / False)."""
+        B, keep = self.members, np.asarray(plan.keep, dtype=bool)
+        rej_v = self._rejected(mahal_v, np.arange(B)[:, None])
+        full = np.full((B, keep.shape[0]), np.nan)
+        full[:, keep] = mahal_v
+        rej = np.zeros((B, keep.shape[0]), dtype=bool)
+        rej[:, keep] = rej_v
+        dof = np.stack([_surviving_dof(RD[self.model], fo, r) for r in rej_v]) if B else np.zeros((0, fo.shape[0] - 1), np.int64)
+        return full, rej, dof
+
+    def replay_corner_replicas(self, log, sigma_px, seed: int, *, first_replica: int = 0, nis: bool = False,
+                               cam_cov: bool = False, mahal: bool = False) -> CornerReplicaReplay:
+        """``replay_replicas`` with the noise where the detector has it: ``log`` carries ``corners`` [D, 4, 2] (pixels)
+        instead of ``poses``, member b replays it as replica ``first_replica + b`` with every corner moved by
+        ``sigma_px[b] * (g_u, g_v)`` pixels and every pose estimated from the noisy corners by IPPE on the device, with
+        the camera of ``set_camera`` (``replica_corner_poses`` returns exactly the poses a replica consumed; the noise
+        and the flip are defined in ``include/ekf_slam_hip.h``).  ``sigma_px``: a scalar or [B].  The same landmark-table
+        precondition as ``replay_replicas``; bad arguments raise before anything runs, and no member changes.
+        Returns a ``CornerReplicaReplay``: the fields of ``replay_replicas`` (``mahal`` and ``rejected`` None, and ``dof``
+        [F], unless ``mahal=True`` or a gate is set: then ``dof`` is [B, F]) and ``flipped`` [B, D] bool aligned with
+        the log's own detections: the (replica, detection) pairs whose IPPE solution flipped, the outliers a gate should
+        catch.  Very large ``sigma_px`` can make a quadrilateral degenerate: its pose is non-finite, as from
+        ``estimate_poses``, and the member stops there (``status``)."""
+        gated = mahal or self.gate is not None
+        sig = replica_sigma_px(sigma_px, self.members)
+        r0 = _replica_range(first_replica, self.members)
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2**64)")
+        if self.camera is None:
+            raise ValueError("replay_corner_replicas needs set_camera() first")
+        if "poses" in log:
+            raise ValueError("replay_corner_replicas takes a log of corners [D,4,2], not of poses (replay_replicas)")
+        plan, corners, idx, fo = self._plan_replica_log(log, "corners", (4, 2), "replay_corner_replicas")
+        k, d, size = self.camera
+        F, D, B = fo.shape[0] - 1, idx.shape[0], self.members
+        torch = self._torch
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_batch_replica_workspace_bytes(self.h, D, F, C.byref(nbytes)))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            corners_t = torch.from_numpy(corners).to(self.device)
+            ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=self.device)
+            traj = torch.empty((B, F, 7), dtype=torch.float64, device=self.device)
+            nis_t = torch.empty((B, F), dtype=torch.float64, device=self.device) if nis else None
+            cov_t = torch.empty((B, F, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
+            mahal_t = torch.empty((B, D), dtype=torch.float64, device=self.device) if gated else None
+            flip_t = torch.zeros((B, D), dtype=torch.uint8, device=self.device)
+            ptr = (lambda t: t.data_ptr() if t is not None and F else None)
+            self._check(self.lib.ekf_batch_observe_corner_replicas(
+                self.h, _iptr(idx), _lptr(fo), F, corners_t.data_ptr() if D else None, _dptr(sig), seed, r0, size, _dptr(k),
+                _dptr(d) if d.size else None, int(d.size), ws.data_ptr(), nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t),
+                mahal_t.data_ptr() if gated and D else None, flip_t.data_ptr() if D else None))
+            self.stream.synchronize()
+        self._adopt_plans([plan] * B)
+        keep = np.asarray(plan.keep, dtype=bool)
+        flipped = np.zeros((B, keep.shape[0]), dtype=bool)
+        flipped[:, keep] = flip_t.cpu().numpy().astype(bool)
+        full = rej = None
+        dof = RD[self.model] * np.diff(fo)
+        if gated:
+            full, rej, dof = self._replica_gate_outputs(plan, fo, mahal_t.cpu().numpy())
+        return CornerReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, dof,
+                                   cov_t.cpu().numpy() if cam_cov else None, full, rej, flipped)
+
     def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False,
                         mahal: bool = False):
         """The C call behind ``process_detection_logs`` (landmark indices already assigned; ``landmarks`` is not
-        touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1], poses [D,6] on the host.  Returns the
+        touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1] on the host, poses [D,6] on the host or a contiguous
+        float64 tensor on the batch's device, produced on the batch's stream.  Returns the
         trajectory [Ftot, 7]; with ``nis`` or ``cam_cov`` the tuple (trajectory, nis [Ftot] or None, cam_cov [Ftot, 10, 10]
         or None); with ``mahal`` the tuple (trajectory, nis or None, cam_cov or None, mahal [D]).  A gate that is set acts
         on every call, whatever it returns."""
@@ -479,7 +702,13 @@ class EKFBatch:
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
         fo = np.ascontiguousarray(frame_offsets, dtype=np.int64).reshape(-1)
         mf = np.ascontiguousarray(member_frames, dtype=np.int64).reshape(-1)
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 6)
+        on_device = isinstance(poses, torch.Tensor)
+        if on_device:
+            if not poses.is_cuda or poses.dtype != torch.float64 or not poses.is_contiguous() or poses.ndim != 2 \
+                    or poses.shape[1] != 6:
+                raise ValueError(f"device poses must be a contiguous float64 [D, 6] tensor on {self.device}")
+        else:
+            poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 6)
         if mf.shape[0] != self.members + 1 or mf[0] != 0 or (np.diff(mf) < 0).any():
             raise ValueError(f"member_frames must be {self.members + 1} non-decreasing offsets from 0")
         frames = int(mf[-1])
@@ -490,7 +719,8 @@ class EKFBatch:
         nbytes = C.c_size_t()
         self._check(self.lib.ekf_batch_log_workspace_bytes(self.h, idx.shape[0], frames, C.byref(nbytes)))
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            poses_t = torch.from_numpy(poses).to(self.device)
+            # (a device tensor comes from this batch's stream: _estimate_corner_logs)
+            poses_t = poses if on_device else torch.from_numpy(poses).to(self.device)
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
             traj = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
             if not (nis or cam_cov or mahal):

@@ -515,19 +515,20 @@ bool pipeline_wanted(const ekf_filter* f, int dims, int kpad, int m) {
 // The device-side gates need the two streams on DIFFERENT hardware queues (HIP maps streams to a small pool
 // of queues): a gate that shares its queue with the launch it waits for would wait for ever.  Probe once: a
 // gate on the internal stream, the matching signal on the handle's stream, a short poll budget.
-// HIP deals its hardware queues to streams as they are created, so when the probe fails a FRESH internal stream usually
-// sits on another queue: up to eight are tried before the handle settles for the serial order.
+// HIP gives a new stream the hardware queue that carries the fewest streams, so when the probe fails a FRESH internal stream
+// usually sits on another queue: up to sixteen are tried before the handle settles for the serial order.  The streams that
+// failed stay alive until the probe is over: destroyed at once, each would leave the shared queue the emptiest again, and
+// the next fresh stream would land on it again (seen when many streams of the process had come and gone before).
 int probe_queues(ekf_filter* f) {
     if (f->la_ok >= 0) return EKF_OK;
     unsigned long long* probe = f->at<unsigned long long>(f->lay.off_sync) + 2;
     int32_t* pstat = f->at<int32_t>(f->lay.off_sync) + 8;
-    f->la_ok = 0;
-    for (int attempt = 0; attempt < 8 && f->la_ok == 0; ++attempt) {
-        if (attempt > 0) {
+    std::vector<hipStream_t> failed;
+    auto attempt = [&](bool fresh_stream) {
+        if (fresh_stream) {
             hipStream_t fresh = nullptr;
             HIP_TRY(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
-            HIP_TRY(hipStreamSynchronize(f->big));
-            (void)hipStreamDestroy(f->big);
+            failed.push_back(f->big);
             f->big = fresh;
         }
         HIP_TRY(hipMemsetAsync(probe, 0, 64, f->stream));
@@ -539,8 +540,16 @@ int probe_queues(ekf_filter* f) {
         int32_t ps = 0;
         HIP_TRY(hipMemcpy(&ps, pstat, 4, hipMemcpyDeviceToHost));
         f->la_ok = (ps == 0) ? 1 : 0;
+        return (int)EKF_OK;
+    };
+    f->la_ok = 0;
+    int rc = EKF_OK;
+    for (int i = 0; i < 16 && f->la_ok == 0 && rc == EKF_OK; ++i) rc = attempt(i > 0);
+    for (hipStream_t s : failed) {      // (each was synchronised at the end of its own attempt)
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
     }
-    return EKF_OK;
+    return rc;
 }
 
 // one pipelining handle per process (see g_pipelining): take the token, or take it over from a handle whose streams
@@ -1218,19 +1227,6 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
 }
 
 // ---- detection -> pose front end (base_filter.py:92-171): stateless, no filter handle -------------------------
-static int make_camera(const double camera_matrix[9], const double* dist_coeffs, int32_t n_dist, EkfCamera* cam) {
-    if (!camera_matrix) return fail(EKF_ERR_INVALID, "camera matrix is NULL");
-    if (n_dist < 0 || n_dist > 8 || (n_dist > 0 && !dist_coeffs))
-        return fail(EKF_ERR_INVALID, "0..8 distortion coefficients (k1 k2 p1 p2 k3 k4 k5 k6) are supported");
-    if (!(camera_matrix[0] > 0.0) || !(camera_matrix[4] > 0.0)) return fail(EKF_ERR_INVALID, "focal lengths must be > 0");
-    cam->fx = camera_matrix[0];
-    cam->fy = camera_matrix[4];
-    cam->cx = camera_matrix[2];
-    cam->cy = camera_matrix[5];
-    for (int i = 0; i < 8; ++i) cam->k[i] = (i < n_dist) ? dist_coeffs[i] : 0.0;
-    return EKF_OK;
-}
-
 int ekf_estimate_poses_device(const double* corners_dev, int32_t count, double marker_size, const double camera_matrix[9],
                               const double* dist_coeffs, int32_t n_dist, double* poses_dev, void* stream) {
     if (count < 0) return fail(EKF_ERR_INVALID, "negative marker count");

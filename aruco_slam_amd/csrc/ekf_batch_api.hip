@@ -1,6 +1,7 @@
 // C ABI of the batch of independent filters (ekf_batch_*, see include/ekf_slam_hip.h; kernels: ekf_batch.hip (EKF) and
 // ekf_batch_rot.hip (EKF_Rotations), with EKF_FLAG_BATCH_LARGE_MAPS or EKF_FLAG_BATCH_WIDE_FRAMES ekf_batch_wide.hip
-// (both models); one workgroup per member; the noisy poses of replicas: ekf_batch_replicas.hip).  Host side only: argument
+// (both models); one workgroup per member; the noisy poses of replicas: ekf_batch_replicas.hip, or, from noisy corners,
+// ekf_batch_corner_replicas.hip).  Host side only: argument
 // checking, workspace carving, launch sequencing.
 #include <cmath>
 #include <cstring>
@@ -220,6 +221,76 @@ int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, co
         HIP_TRY(hipGetLastError());
     }
     return EKF_OK;
+}
+
+// sigma_px [rows] finite and >= 0, marker_size > 0, a valid camera (make_camera): the noise arguments of the corner replicas
+int check_corner_noise(const double* sigma_px, int64_t rows, double marker_size, const double camera_matrix[9],
+                       const double* dist_coeffs, int32_t n_dist, EkfCamera* cam) {
+    if (!sigma_px) return fail(EKF_ERR_INVALID, "sigma_px is NULL");
+    for (int64_t i = 0; i < rows; ++i)
+        if (!std::isfinite(sigma_px[i]) || sigma_px[i] < 0.0) return fail(EKF_ERR_INVALID, "sigma_px must be finite and >= 0");
+    if (!(marker_size > 0.0)) return fail(EKF_ERR_INVALID, "marker_size must be > 0");
+    return make_camera(camera_matrix, dist_coeffs, n_dist, cam);
+}
+
+// The replica calls: the log is checked for every member, its indices and offsets are tiled B times into ws, `launch` writes
+// the B D poses the members consume into ws, and the windows run on them.  `input_dev`: the log's poses or corners;
+// `check_noise_args`: the call's own noise arguments (host side, before anything is enqueued).
+template <typename Check, typename Launch>
+int batch_observe_replicas(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, int64_t frames,
+                           const void* input_dev, uint32_t first_replica, void* ws, size_t ws_bytes, double* trajectory_dev,
+                           double* nis_dev, double* cam_cov_dev, double* mahal_dev, Check check_noise_args, Launch launch) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    // ---- validation on the host: nothing is enqueued before the log has passed for every member
+    const int32_t B = b->members;
+    if (frames < 0) return fail(EKF_ERR_INVALID, "frames must be >= 0");
+    if (!frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
+    if ((rc = check_offsets(frame_offsets, frames, "frame_offsets"))) return rc;
+    const int64_t D = frame_offsets[frames];
+    if (D > 0 && (!lm_index || !input_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
+    if ((rc = check_noise_args(B))) return rc;
+    if ((uint64_t)first_replica + (uint64_t)B > (1ull << 32))
+        return fail(EKF_ERR_INVALID, "first_replica + members must not exceed 2^32");
+    const BatchReplicaLayout RL = batch_replica_layout(D, frames, B, batch_gated(b));
+    if ((rc = check_device_buffers({ws}, ws_bytes, RL.total, "ekf_batch_replica_workspace_bytes"))) return rc;
+    if ((rc = batch_refresh(b))) return rc;
+    BatchShape sh;
+    LogCheck lc;
+    for (int32_t m = 0; m < B; ++m) {
+        if (m > 0 && b->nlm[m] == b->nlm[m - 1]) {      // (the same log on the same landmark count: the same verdict)
+            sh.add(lc, frames);
+            continue;
+        }
+        rc = check_log(lm_index, frame_offsets, frames, b->nlm[m], b->cfg, "the log (member " + std::to_string(m) + ")", &lc);
+        if (rc) return rc;
+        sh.add(lc, frames);
+    }
+    if (frames == 0) return EKF_OK;
+
+    // ---- staging: the log's indices and offsets tiled member after member (member b: detections b D .., frames b F ..)
+    const int64_t Ft = (int64_t)B * frames, Dt = (int64_t)B * D;
+    const BatchLogLayout& LL = RL.log;
+    if ((rc = b->pin.reserve(LL.total))) return rc;
+    int32_t* idx = b->pin.at<int32_t>(0);
+    int64_t* fo = b->pin.at<int64_t>(LL.frames);
+    int64_t* mf = b->pin.at<int64_t>(LL.members);
+    for (int32_t m = 0; m < B; ++m) {
+        if (D > 0) std::memcpy(idx + (size_t)m * D, lm_index, (size_t)D * 4);
+        for (int64_t t = 0; t < frames; ++t) fo[(size_t)m * frames + t] = (int64_t)m * D + frame_offsets[t];
+        mf[m] = (int64_t)m * frames;
+    }
+    fo[Ft] = Dt;
+    mf[B] = Ft;
+    if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
+    char* w = static_cast<char*>(ws);
+    HIP_TRY(hipMemcpyAsync(w, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
+    double* noisy = reinterpret_cast<double*>(w + RL.poses);
+    if (D > 0) {
+        launch(D, noisy);
+        HIP_TRY(hipGetLastError());
+    }
+    return batch_run_windows(b, w, LL, sh, noisy, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
 }
 
 }  // namespace
@@ -495,58 +566,52 @@ int ekf_batch_observe_replicas_gated(ekf_batch* b, const int32_t* lm_index, cons
                                      const double* poses_dev, const double* sigma, uint64_t seed, uint32_t first_replica,
                                      void* ws, size_t ws_bytes, double* trajectory_dev, double* nis_dev,
                                      double* cam_cov_dev, double* mahal_dev) {
-    int rc = batch_ready(b);
-    if (rc) return rc;
-    // ---- validation on the host: nothing is enqueued before the log has passed for every member
-    const int32_t B = b->members;
-    if (frames < 0) return fail(EKF_ERR_INVALID, "frames must be >= 0");
-    if (!frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
-    if ((rc = check_offsets(frame_offsets, frames, "frame_offsets"))) return rc;
-    const int64_t D = frame_offsets[frames];
-    if (D > 0 && (!lm_index || !poses_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
-    if (!sigma) return fail(EKF_ERR_INVALID, "sigma is NULL");
-    if ((rc = check_sigma(sigma, B))) return rc;
-    if ((uint64_t)first_replica + (uint64_t)B > (1ull << 32))
-        return fail(EKF_ERR_INVALID, "first_replica + members must not exceed 2^32");
-    const BatchReplicaLayout RL = batch_replica_layout(D, frames, B, batch_gated(b));
-    if ((rc = check_device_buffers({ws}, ws_bytes, RL.total, "ekf_batch_replica_workspace_bytes"))) return rc;
-    if ((rc = batch_refresh(b))) return rc;
-    BatchShape sh;
-    LogCheck lc;
-    for (int32_t m = 0; m < B; ++m) {
-        if (m > 0 && b->nlm[m] == b->nlm[m - 1]) {      // (the same log on the same landmark count: the same verdict)
-            sh.add(lc, frames);
-            continue;
-        }
-        rc = check_log(lm_index, frame_offsets, frames, b->nlm[m], b->cfg, "the log (member " + std::to_string(m) + ")", &lc);
-        if (rc) return rc;
-        sh.add(lc, frames);
-    }
-    if (frames == 0) return EKF_OK;
+    return batch_observe_replicas(
+        b, lm_index, frame_offsets, frames, poses_dev, first_replica, ws, ws_bytes, trajectory_dev, nis_dev, cam_cov_dev,
+        mahal_dev,
+        [&](int32_t B) {
+            if (!sigma) return fail(EKF_ERR_INVALID, "sigma is NULL");
+            return check_sigma(sigma, B);
+        },
+        [&](int64_t D, double* noisy) {
+            ekf_launch_replica_poses(poses_dev, D, sigma, b->members, seed, first_replica, noisy, b->stream);
+        });
+}
 
-    // ---- staging: the log's indices and offsets tiled member after member (member b: detections b D .., frames b F ..)
-    const int64_t Ft = (int64_t)B * frames, Dt = (int64_t)B * D;
-    const BatchLogLayout& LL = RL.log;
-    if ((rc = b->pin.reserve(LL.total))) return rc;
-    int32_t* idx = b->pin.at<int32_t>(0);
-    int64_t* fo = b->pin.at<int64_t>(LL.frames);
-    int64_t* mf = b->pin.at<int64_t>(LL.members);
-    for (int32_t m = 0; m < B; ++m) {
-        if (D > 0) std::memcpy(idx + (size_t)m * D, lm_index, (size_t)D * 4);
-        for (int64_t t = 0; t < frames; ++t) fo[(size_t)m * frames + t] = (int64_t)m * D + frame_offsets[t];
-        mf[m] = (int64_t)m * frames;
-    }
-    fo[Ft] = Dt;
-    mf[B] = Ft;
-    if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
-    char* w = static_cast<char*>(ws);
-    HIP_TRY(hipMemcpyAsync(w, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
-    double* noisy = reinterpret_cast<double*>(w + RL.poses);
-    if (D > 0) {
-        ekf_launch_replica_poses(poses_dev, D, sigma, B, seed, first_replica, noisy, b->stream);
-        HIP_TRY(hipGetLastError());
-    }
-    return batch_run_windows(b, w, LL, sh, noisy, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
+int ekf_batch_replica_corners(const double* corners_dev, int64_t detections, const double* sigma_px, int32_t replicas,
+                              uint64_t seed, uint32_t first_replica, double marker_size, const double camera_matrix[9],
+                              const double* dist_coeffs, int32_t n_dist, double* poses_dev, uint8_t* flipped_dev,
+                              double* noisy_corners_dev, void* stream) {
+    if (detections < 0 || replicas < 0) return fail(EKF_ERR_INVALID, "bad replica request");
+    if ((uint64_t)first_replica + (uint64_t)replicas > (1ull << 32))
+        return fail(EKF_ERR_INVALID, "first_replica + replicas must not exceed 2^32");
+    if (replicas == 0) return EKF_OK;
+    EkfCamera cam;
+    int rc = check_corner_noise(sigma_px, replicas, marker_size, camera_matrix, dist_coeffs, n_dist, &cam);
+    if (rc) return rc;
+    if (detections == 0) return EKF_OK;
+    if (!corners_dev) return fail(EKF_ERR_INVALID, "NULL corners");
+    ekf_launch_corner_replicas(corners_dev, detections, sigma_px, replicas, seed, first_replica, marker_size, cam, poses_dev,
+                               flipped_dev, noisy_corners_dev, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return EKF_OK;
+}
+
+int ekf_batch_observe_corner_replicas(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, int64_t frames,
+                                      const double* corners_dev, const double* sigma_px, uint64_t seed,
+                                      uint32_t first_replica, double marker_size, const double camera_matrix[9],
+                                      const double* dist_coeffs, int32_t n_dist, void* ws, size_t ws_bytes,
+                                      double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev,
+                                      uint8_t* flipped_dev) {
+    EkfCamera cam;
+    return batch_observe_replicas(
+        b, lm_index, frame_offsets, frames, corners_dev, first_replica, ws, ws_bytes, trajectory_dev, nis_dev, cam_cov_dev,
+        mahal_dev,
+        [&](int32_t B) { return check_corner_noise(sigma_px, B, marker_size, camera_matrix, dist_coeffs, n_dist, &cam); },
+        [&](int64_t D, double* noisy) {
+            ekf_launch_corner_replicas(corners_dev, D, sigma_px, b->members, seed, first_replica, marker_size, cam, noisy,
+                                       flipped_dev, nullptr, b->stream);
+        });
 }
 
 }  // extern "C"

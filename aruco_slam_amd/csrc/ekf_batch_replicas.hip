@@ -7,6 +7,7 @@
 // else: not on how many replicas a call holds nor which ones share it.  Three Philox calls, three f64 log and sin / cos
 // pairs and 48 bytes stored per thread; sigma of the launch's replicas travels in the kernel arguments.
 #include "ekf_kernels.h"
+#include "ekf_philox.h"
 
 namespace {
 
@@ -22,27 +23,6 @@ struct ReplicaArgs {
     double sigma[EKF_REPLICA_CHUNK][6];
 };
 static_assert(sizeof(ReplicaArgs) <= 4096, "kernel arguments");
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011): the published round constants
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
-        const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = lo1;
-        c[2] = n2;
-        c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
-// (0, 1]: (v + 0.5) 2^-53 in f64 for v the top 53 bits of (hi << 32 | lo) (never 0, so log(u) is finite)
-__device__ __forceinline__ double unit_open(uint32_t hi, uint32_t lo) {
-    const uint64_t v = ((uint64_t)hi << 32 | lo) >> 11;
-    return ((double)v + 0.5) * 0x1.0p-53;
-}
 
 __global__ __launch_bounds__(kReplicaThreads) void ekf_replica_poses_kernel(ReplicaArgs p) {
     const int64_t e = (int64_t)blockIdx.x * kReplicaThreads + threadIdx.x;

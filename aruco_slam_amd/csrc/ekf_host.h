@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ekf_kernels.h"
+
 #include <algorithm>
 #include <cstdint>
 #include <initializer_list>
@@ -119,6 +121,20 @@ int check_log(const int32_t* lm_index, const int64_t* offsets, int64_t frames, i
     out->new_at[frames] = (int64_t)out->slots.size();
     if (out->n > cfg.max_landmarks) return fail(EKF_ERR_CAPACITY, log + " needs more landmarks than max_landmarks");
     if (out->widest > cfg.max_visible) return fail(EKF_ERR_CAPACITY, "a frame of " + log + " has more detections than max_visible");
+    return EKF_OK;
+}
+
+// The camera of the pose front end from the C ABI's arguments (row-major 3x3 matrix, 0..8 distortion coefficients).
+int make_camera(const double camera_matrix[9], const double* dist_coeffs, int32_t n_dist, EkfCamera* cam) {
+    if (!camera_matrix) return fail(EKF_ERR_INVALID, "camera matrix is NULL");
+    if (n_dist < 0 || n_dist > 8 || (n_dist > 0 && !dist_coeffs))
+        return fail(EKF_ERR_INVALID, "0..8 distortion coefficients (k1 k2 p1 p2 k3 k4 k5 k6) are supported");
+    if (!(camera_matrix[0] > 0.0) || !(camera_matrix[4] > 0.0)) return fail(EKF_ERR_INVALID, "focal lengths must be > 0");
+    cam->fx = camera_matrix[0];
+    cam->fy = camera_matrix[4];
+    cam->cx = camera_matrix[2];
+    cam->cy = camera_matrix[5];
+    for (int i = 0; i < 8; ++i) cam->k[i] = (i < n_dist) ? dist_coeffs[i] : 0.0;
     return EKF_OK;
 }
 

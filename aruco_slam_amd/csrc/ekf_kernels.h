@@ -293,3 +293,10 @@ struct EkfCamera {
 // one [tvec | rvec] per marker from its four pixel corners [count][4][2] (IPPE for a square of side marker_size)
 void ekf_launch_ippe_square(const double* corners_dev, int count, double marker_size, const EkfCamera& cam,
                             double* poses_dev, hipStream_t s);
+// Replicas with pixel noise on the marker corners (ekf_batch_corner_replicas.hip): for `count` replicas from r0 on, the noisy
+// corners [count][D][4][2], their IPPE poses [count][D][6] and the flip labels [count][D] (each output may be null);
+// sigma_px [count] on the host, chunked by EKF_REPLICA_CHUNK; the definition in include/ekf_slam_hip.h
+// (ekf_batch_replica_corners)
+void ekf_launch_corner_replicas(const double* corners_dev, int64_t D, const double* sigma_px, int32_t count, uint64_t seed,
+                                uint32_t r0, double marker_size, const EkfCamera& cam, double* poses_dev,
+                                uint8_t* flipped_dev, double* noisy_dev, hipStream_t s);

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "ekf_batch_log_workspace_bytes", "ekf_batch_observe_logs", "ekf_batch_observe_logs_diag", "ekf_batch_replica_poses",
     "ekf_batch_replica_workspace_bytes", "ekf_batch_observe_replicas",
     "ekf_batch_set_gate", "ekf_batch_observe_logs_gated", "ekf_batch_observe_replicas_gated",
+    "ekf_batch_replica_corners", "ekf_batch_observe_corner_replicas",
 )
 
 
@@ -132,6 +133,10 @@ def load_library(path: str | Path | None = None):
                                          vp, vp],
         "ekf_batch_observe_replicas_gated": [vp, ip, C.POINTER(C.c_int64), C.c_int64, vp, dp, C.c_uint64, C.c_uint32, vp,
                                              C.c_size_t, vp, vp, vp, vp],
+        "ekf_batch_replica_corners": [vp, C.c_int64, dp, C.c_int32, C.c_uint64, C.c_uint32, C.c_double, dp, dp, C.c_int32,
+                                      vp, vp, vp, vp],
+        "ekf_batch_observe_corner_replicas": [vp, ip, C.POINTER(C.c_int64), C.c_int64, vp, dp, C.c_uint64, C.c_uint32,
+                                              C.c_double, dp, dp, C.c_int32, vp, C.c_size_t, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

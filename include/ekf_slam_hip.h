@@ -419,6 +419,47 @@ int ekf_batch_observe_replicas_gated(ekf_batch *b, const int32_t *lm_index, cons
                                      void *ws, size_t ws_bytes, double *trajectory_dev, double *nis_dev,
                                      double *cam_cov_dev, double *mahal_dev);
 
+/* ---- Monte-Carlo replicas with the noise on the marker corners, in pixels, where the detector has it: IPPE turns it into
+ * what pose noise never gives (a depth error that grows with distance, an error that depends on the marker's tilt, and now
+ * and then the other of its two solutions), and every such flip is labelled.
+ * Noise and flip definition (part of the ABI).  Replica r, detection d, corner i = 0 .. 3 (the detector's order, as
+ * ekf_estimate_poses takes them):
+ *     noisy[r][d][i] = corners[d][i] + sigma_px[r] * (g_u, g_v)        in pixels, before undistortion
+ * with (g_u, g_v) = (sqrt(-2 ln u_a) cos(2 pi u_b), sqrt(-2 ln u_a) sin(2 pi u_b)) from ONE Philox4x32-10 call with key
+ * (seed_lo, seed_hi) and counter (d_lo, d_hi, r, 4 + i), u_a / u_b from its words exactly as for the pose noise above
+ * (evaluated as corner + sigma_px * (sqrt(..) * cos(..))).  Counter words 4 .. 7 keep this stream disjoint from the pose
+ * stream (words 0 .. 2).  The noise of (r, d) depends on nothing else: not on how many replicas a call holds nor on which
+ * replicas share it.
+ * The pose of (r, d) is IPPE-square of the noisy corners, the steps of ekf_estimate_poses by the same device code:
+ * sigma_px = 0 gives the bits of ekf_estimate_poses on the corners as logged.
+ * flipped[r][d] is defined with three rotations: R_clean, the rotation IPPE returns for the corners as logged; R_a, the
+ * returned candidate (the smaller reprojection error) for the noisy corners; R_b, the other candidate for the noisy corners:
+ *     flipped = trace(R_a R_clean^T) < trace(R_b R_clean^T),
+ * the rejected candidate was the one nearer to the clean pose.
+ *
+ * ekf_batch_replica_corners: what replicas first_replica .. first_replica + R - 1 consume, from corners_dev [D,4,2] (DEVICE,
+ * pixels) and sigma_px [R] (HOST, finite, >= 0), enqueued on `stream`; first_replica + R <= 2^32; marker_size > 0; camera
+ * arguments as ekf_estimate_poses (n_dist <= 8).  Outputs, each DEVICE or NULL: poses_dev [R,D,6] = [tvec | rvec],
+ * flipped_dev [R,D] bytes (0 / 1), noisy_corners_dev [R,D,4,2].  R = 0 does nothing.  No handle: it is the code
+ * ekf_batch_observe_corner_replicas runs.  Corners noisy enough to give a degenerate quadrilateral give the non-finite
+ * poses ekf_estimate_poses would give. */
+int ekf_batch_replica_corners(const double *corners_dev, int64_t detections, const double *sigma_px, int32_t replicas,
+                              uint64_t seed, uint32_t first_replica, double marker_size, const double camera_matrix[9],
+                              const double *dist_coeffs, int32_t n_dist, double *poses_dev, uint8_t *flipped_dev,
+                              double *noisy_corners_dev, void *stream);
+/* ekf_batch_observe_replicas_gated on a log of corners: member b replays the log as replica first_replica + b with its own
+ * sigma_px[b] (HOST [B]); corners_dev [D,4,2] DEVICE; ws as ekf_batch_replica_workspace_bytes(D, F), unchanged: the poses
+ * the kernel estimates take the place of the noisy poses.  Outputs as there, and flipped_dev [B,D] bytes DEVICE or NULL,
+ * indexed like lm_index.  Everything, the noise and camera arguments included, is validated on the host before anything is
+ * enqueued; a gate that is set acts as in every observe call.  Every member gives the bits of ekf_batch_observe_logs_gated
+ * on the poses ekf_batch_replica_corners returns for its replica. */
+int ekf_batch_observe_corner_replicas(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets, int64_t frames,
+                                      const double *corners_dev, const double *sigma_px, uint64_t seed,
+                                      uint32_t first_replica, double marker_size, const double camera_matrix[9],
+                                      const double *dist_coeffs, int32_t n_dist, void *ws, size_t ws_bytes,
+                                      double *trajectory_dev, double *nis_dev, double *cam_cov_dev, double *mahal_dev,
+                                      uint8_t *flipped_dev);
+
 const char *ekf_last_error_string(void);
 
 #ifdef __cplusplus

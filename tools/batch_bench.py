@@ -19,6 +19,12 @@ process_detection_logs on B copies of the log re-noised on the host (numpy draws
 apart).  Same timing rule: one warm-up call, a reset, one timed call.  --nis / --cam-cov ask both paths for the per-frame
 outputs.  Kernel times: `rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --replicas --members 256
 [--nis --cam-cov]` (profiles/batch/rocprof_replicas_*.json).
+--replicas --corners [--sigma-px X]: the same ONE-log study with the noise on the marker corners, X pixels (default 0.5):
+a synthetic.corner_log scene seen through the calibrated camera of tests/golden/calibration.npz, the rate of
+EKFBatch.replay_corner_replicas (corner noise, IPPE and flip labels on the device) beside replay_replicas on the log's clean
+poses (sigma = 0.01 on the tvec), and the share of flipped detections.  Lines carry "corners": true.  Kernel times:
+`rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --replicas --corners --members 256`
+(profiles/batch/rocprof_corner_replicas_*.json).
 """
 from __future__ import annotations
 
@@ -61,6 +67,9 @@ def main():
     ap.add_argument("--replicas", action="store_true", help="replay_replicas against host-noised process_detection_logs")
     ap.add_argument("--nis", action="store_true", help="--replicas: ask for the per-frame NIS")
     ap.add_argument("--cam-cov", action="store_true", help="--replicas: ask for the per-frame camera covariance")
+    ap.add_argument("--corners", action="store_true",
+                    help="--replicas: pixel noise on the marker corners (replay_corner_replicas) beside pose noise")
+    ap.add_argument("--sigma-px", type=float, default=0.5, help="--corners: the corner noise in pixels")
     ap.add_argument("--gate", type=float, default=None,
                     help="chi-square gate of every member (EKFBatch(gate=X)); 1e300 tests every detection and rejects none. "
                          "With a gate the wall times include the copy of mahal and the host's rejected / dof bookkeeping: "
@@ -78,8 +87,10 @@ def main():
     wide = m_hi > (8 if rot else 16)
     n = args.landmarks or ((100 if rot else 250) if args.large_maps or wide else (24 if rot else 50))
     visible = max(m_hi, 8 if rot else 16)
+    if args.corners and not args.replicas:
+        raise SystemExit("--corners goes with --replicas")
     if args.replicas:
-        return replicas(args, n, m_hi, visible)
+        return (corner_replicas if args.corners else replicas)(args, n, m_hi, visible)
     args.members = args.members or [1, 16, 64, 256, 1024]
     logs = [split(lg, lg["bootstrap_frames"]) for lg in
             (ragged_log(n, (1, m_hi), args.steady, seed=s, rvec_sigma=0.05 if rot else 0.0)
@@ -178,6 +189,55 @@ def replicas(args, n, m_hi, visible):
                 "host_noised_wall_s": round(wall_host, 6), "host_noise_draw_s": round(t1 - t0, 6),
                 "host_noised_frames_per_s": round(B * frames / wall_host, 1),
                 "speedup": round(wall_host / wall_rep, 2)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del batch
+    append(args.out, lines)
+
+
+def corner_replicas(args, n, m_hi, visible):
+    import torch
+    from aruco_slam_amd.batch import EKFBatch
+    from aruco_slam_amd.synthetic import corner_log
+    rot = args.model == "ekf_rotations"
+    cal = np.load(REPO / "tests" / "golden" / "calibration.npz", allow_pickle=False)
+    k, dist = cal["camera_matrix"], cal["dist_coeffs"].reshape(-1)
+    full = corner_log(n, (1, m_hi), args.steady, 0, k, dist)
+    log = {key: full[key] for key in ("ids", "corners", "offsets", "has_detections")}
+    pose_log = {"ids": full["ids"], "poses": full["poses_clean"] + 0.0, "offsets": full["offsets"],
+                "has_detections": full["has_detections"]}
+    frames, dets = len(log["offsets"]) - 1, int(log["offsets"][-1])
+    sigma = np.array([0.01, 0.01, 0.01, 0.0, 0.0, 0.0])
+    outs = {"nis": args.nis, "cam_cov": args.cam_cov}
+    lines = []
+    for B in args.members or [16, 64, 256, 1024]:
+        batch = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model,
+                         large_maps=True if args.large_maps else None, **({} if args.gate is None else {"gate": args.gate}))
+        batch.set_camera(k, dist)
+        batch.replay_corner_replicas(log, args.sigma_px, 1, **outs)          # warm-up
+        batch.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = batch.replay_corner_replicas(log, args.sigma_px, 2, **outs)
+        wall_corner = time.perf_counter() - t0
+        stopped = sum(1 for v in batch.status() if v != 0)      # (a flipped pose can stop an EKF_Rotations member)
+        batch.reset()
+        batch.replay_replicas(pose_log, sigma, 1, **outs)          # warm-up
+        batch.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        batch.replay_replicas(pose_log, sigma, 2, **outs)
+        wall_pose = time.perf_counter() - t0
+        line = {"tool": "batch_bench", "replicas": True, "corners": True, **({"model": args.model} if rot else {}),
+                **({"large_maps": True} if args.large_maps else {}),
+                **({"wide_frames": True} if batch.wide_frames else {}), "members": B, "n": n, "m": [1, m_hi],
+                "frames": frames, "detections": dets, "nis": args.nis, "cam_cov": args.cam_cov,
+                **({} if args.gate is None else {"gate": args.gate}), "sigma_px": args.sigma_px,
+                "flipped_share": round(float(got.flipped.mean()), 5), "members_stopped": stopped,
+                "replay_corner_replicas_wall_s": round(wall_corner, 6),
+                "replay_corner_replicas_frames_per_s": round(B * frames / wall_corner, 1),
+                "replay_replicas_wall_s": round(wall_pose, 6),
+                "replay_replicas_frames_per_s": round(B * frames / wall_pose, 1)}
         print(json.dumps(line), flush=True)
         lines.append(line)
         del batch

@@ -805,7 +805,9 @@ class EKFBatch:
     def load_filter(self, b, ekf) -> None:
         """Member b from an ordinary filter of the batch's model (``EKF`` or ``EKF_Rotations``): its state, covariance and
         landmark table, with the batch's quaternion convention.  The member keeps its own noise constants (a sweep loads
-        one filter into members that differ in nothing else)."""
+        one filter into members that differ in nothing else) and takes the filter's gate, if the filter was built with one:
+        a filter whose gate is ``inf`` switches that member's gate OFF, also where the member had a finite one (``set_gate``
+        afterwards to keep it); a filter built without ``gate=`` leaves the member's gate as it is."""
         cls = self._filter_class()
         if not isinstance(ekf, cls):
             raise ValueError(f"a batch of model {self.model!r} holds {cls.__name__} filters, got {type(ekf).__name__}")
@@ -813,23 +815,28 @@ class EKFBatch:
             raise ValueError(f"the filter's quaternion convention differs from the batch's ({self.quat_update!r})")
         ids = [k for k, _ in sorted(ekf.get_lm_estimates(), key=lambda kv: kv[1])]
         self.set_member(b, np.asarray(ekf.state, dtype=np.float64), ekf.uncertainty, ids)
+        if ekf.gate is not None and not (self.gate is None and np.isinf(ekf.gate)):
+            gates = np.full(self.members, np.inf) if self.gate is None else self.gate.copy()
+            gates[self._member(b)] = ekf.gate
+            self.set_gate(gates)
 
     def to_filter(self, b):
         """An ordinary filter of the batch's model (``EKF`` or ``EKF_Rotations``, f64 covariance) with member b's quaternion
-        convention, noise constants, state, covariance and landmark table; ``observe`` (and for ``EKF`` ``save_map`` and
-        ``save_checkpoint``) work on it."""
+        convention, noise constants, gate (a batch with a gate gives a filter built with ``gate=``), state, covariance and
+        landmark table; ``observe`` (and for ``EKF`` ``save_map`` and ``save_checkpoint``) work on it."""
         b = self._member(b)
         state, cov = self.get_state(b), self.get_cov(b)
         n = self.num_landmarks[b]
         noise = dict(zip(NOISE_KEYS, (float(v) for v in self.noise[b])))
+        gate = None if self.gate is None else float(self.gate[b])
         if self.model == "ekf_rotations":
             from .filters.ekf_with_rotations import EKF_Rotations
             ekf = EKF_Rotations(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
-                                device=str(self.device), noise=noise)
+                                device=str(self.device), noise=noise, gate=gate)
         else:
             from .filters.extended_kalman_filter import EKF
             ekf = EKF(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
-                      quat_update=self.quat_update, device=str(self.device), noise=noise)
+                      quat_update=self.quat_update, device=str(self.device), noise=noise, gate=gate)
         ekf.backend.set_state_cov(state, cov)
         ekf.landmarks = dict(self.landmarks[b])
         ekf.num_landmarks = n

@@ -46,6 +46,10 @@ struct Layout {
     size_t off_tiles; // launch order of the macro-tile covariance update (f32, large problems)
     int tiles_cap;    // entries
     size_t slot_bytes;   // one slot of the pinned staging ring (reserve_host_buffers)
+    // EKF_FLAG_GATE: the survivors of a gated frame (indices, z) and its distances; in a slot of the staging ring the exempt
+    // mask and the host copy of the distances behind the detections (0: no gate scratch)
+    bool has_gate;
+    size_t off_gidx, off_gz, off_gmahal, slot_exempt, slot_mahal;
     // fused front kernel: one exchange buffer per fused-frame parity (offsets / length in doubles)
     size_t xl_len, xl_dop, xl_y, xl_jac, xl_tag, xl_xs, xl_xr, xl_stag;
 };
@@ -114,9 +118,17 @@ Layout make_layout(const ekf_config& c) {
     // wide frames beyond the stage kernels' size (ekf_wide.hip); configurations within the caps keep their sizes
     L.off_wwork = wide ? w.take((size_t)L.kmax * L.cap * 8) : 0;
     L.off_xinv = wide ? w.take((size_t)EKF_WIDE_BLOCK * EKF_WIDE_BLOCK * 8) : 0;
+    // the per-detection gate (ekf_gate.hip); configurations without the flag keep their sizes
+    L.has_gate = (c.flags & EKF_FLAG_GATE) != 0;
+    L.off_gidx = L.has_gate ? w.take((size_t)c.max_visible * 4) : 0;
+    L.off_gz = L.has_gate ? w.take((size_t)c.max_visible * 7 * 8) : 0;
+    L.off_gmahal = L.has_gate ? w.take((size_t)c.max_visible * 8) : 0;
     L.total = w.end;
     // one slot of the pinned staging ring: a frame's detections as ekf_observe stages them, or 256 markers of ekf_add_markers
-    L.slot_bytes = std::max(align256((size_t)c.max_visible * 4) + align256((size_t)c.max_visible * 56),
+    const size_t det_bytes = align256((size_t)c.max_visible * 4) + align256((size_t)c.max_visible * 56);
+    L.slot_exempt = det_bytes;
+    L.slot_mahal = det_bytes + align256((size_t)c.max_visible);
+    L.slot_bytes = std::max(L.has_gate ? L.slot_mahal + align256((size_t)c.max_visible * 8) : det_bytes,
                             align256(256 * 48) + align256(256 * 80));
     return L;
 }
@@ -212,7 +224,14 @@ struct ekf_filter {
     hipEvent_t log_pin_done[2] = {};
     int log_pin_turn = 0;
     int64_t log_stats[4] = {};
+    // per-detection gate (EKF_FLAG_GATE): the threshold (+inf: off; persistent across ekf_reset), the pinned mirror the gate
+    // kernel leaves [survivors, some pivot failed (not read here: diagnostic)] in, the event behind it, what the last observe call tested / rejected
+    double gate = __builtin_inf();
+    PinnedBuffer gate_pin;
+    hipEvent_t ev_gate = nullptr;
+    int64_t gate_stats[2] = {};
 
+    bool gate_on() const { return lay.has_gate && gate < __builtin_inf(); }
     int dims() const { return lay.lmd * n_lm + EKF_CAM; }
     template <typename P> P* at(size_t off) const { return reinterpret_cast<P*>(ws + off); }
 };
@@ -793,6 +812,105 @@ int open_handle(ekf_filter* f) {
     HIP_TRY(hipStreamCreateWithFlags(&f->big, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&f->ev_front, hipEventDisableTiming));
     for (hipEvent_t& e : f->slot_done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (f->lay.has_gate) {
+        if ((rc = f->gate_pin.reserve(256))) return rc;
+        std::memset(f->gate_pin.get(), 0, 256);
+        HIP_TRY(hipEventCreateWithFlags(&f->ev_gate, hipEventDisableTiming));
+    }
+    return EKF_OK;
+}
+
+// ---- the per-detection gate (include/ekf_slam_hip.h: ekf_set_gate) ---------------------------------------------------------
+// One gated frame: the gate kernel on the frame's detections (device or pinned host pointers), a wait for the survivor count
+// in the pinned mirror -- the one host round trip a gated frame costs --, then the ordinary frame on the compacted arrays:
+// the same launches as the same call on the frame with the rejected detections deleted.  No survivor: nothing is stepped.
+// exempt [m] (pinned host or device) or null; n_exempt: how many of them are set (statistics); mahal_dev / mahal_host [m] or
+// null.  *survivors: how many detections stayed.
+int gated_frame(ekf_filter* f, const int32_t* idx, const double* z, int m, const uint8_t* exempt, int n_exempt,
+                double* mahal_dev, double* mahal_host, double* traj_row, bool mirror, int* survivors) {
+    const Layout& L = f->lay;
+    EkfGateArgs g{};
+    g.cov = f->cov;
+    g.ld = f->ld;
+    g.state = f->state;
+    g.n_lm = f->n_lm;
+    g.dims = f->dims();
+    g.m = m;
+    g.idx = idx;
+    g.z = z;
+    g.exempt = exempt;
+    g.nz = EkfNoise{f->cfg.q_cam, f->cfg.q_err, f->cfg.q_lm, f->cfg.r_uncertainty};
+    g.gate = f->gate;
+    g.mahal = mahal_dev ? mahal_dev : f->at<double>(L.off_gmahal);
+    g.mahal_host = mahal_host;
+    g.out_idx = f->at<int32_t>(L.off_gidx);
+    g.out_z = f->at<double>(L.off_gz);
+    g.status = f->at<int32_t>(L.off_status);
+    g.status_host = f->readback.at<int32_t>(128);
+    g.result_host = f->gate_pin.at<int32_t>(0);
+    by_cov_type(f, [&](auto elem) { ekf_launch_frame_gate<decltype(elem)>(f->cfg.model, g, f->stream); });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f->ev_gate, f->stream));
+    HIP_TRY(hipEventSynchronize(f->ev_gate));
+    const int s = *f->gate_pin.at<volatile int32_t>(0);
+    if (s < 0 || s > m) return fail(EKF_ERR_STATE, "internal: survivor count of the gate kernel out of range");
+    f->gate_stats[0] += m - n_exempt;
+    f->gate_stats[1] += m - s;
+    if (survivors) *survivors = s;
+    if (s == 0) return EKF_OK;
+    return enqueue_frame(f, g.out_idx, g.out_z, s, traj_row, mirror);
+}
+
+// trajectory row of a frame that is not stepped: the camera state as it is on the device
+int repeat_row(ekf_filter* f, double* traj_row) {
+    if (traj_row) HIP_TRY(hipMemcpyAsync(traj_row, f->state, 7 * 8, hipMemcpyDeviceToDevice, f->stream));
+    return EKF_OK;
+}
+
+// ekf_observe / ekf_observe_gated: the frame's detections (host) through a slot of the pinned staging ring
+int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, int32_t m, bool gated, const uint8_t* exempt,
+                 double* mahal, int32_t* survivors) {
+    if (m < 1) return fail(EKF_ERR_INVALID, "observe needs at least one detection");
+    if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
+    if (!lm_index || !z) return fail(EKF_ERR_INVALID, "NULL detections");
+    for (int i = 0; i < m; ++i)
+        if (lm_index[i] < 0 || lm_index[i] >= f->n_lm)
+            return fail(EKF_ERR_INVALID, "landmark index out of range");
+    const Layout& L = f->lay;
+    char* slot = f->ring.get() + (size_t)f->slot * L.slot_bytes;
+    HIP_TRY(hipEventSynchronize(f->slot_done[f->slot]));
+    int32_t* hidx = reinterpret_cast<int32_t*>(slot);
+    double* hz = reinterpret_cast<double*>(slot + align256((size_t)f->cfg.max_visible * 4));
+    const size_t zb = (size_t)m * L.rd * 8;
+    std::memcpy(hidx, lm_index, (size_t)m * 4);
+    std::memcpy(hz, z, zb);
+    // one copy: the pinned slot mirrors the device staging layout [indices, padded to 256 B | z]
+    static_assert(sizeof(int32_t) == 4, "layout");
+    if (L.off_z - L.off_idx != align256((size_t)f->cfg.max_visible * 4)) return fail(EKF_ERR_STATE, "staging layout");
+    // The kernels read the frame's detections (128 + 768 bytes at m = 32) straight from the pinned slot: a host-to-device
+    // copy in front of them costs more (API call + DMA start, ~8 us before the front kernel begins) than the PCIe reads
+    // cost the kernel's first round trip.  The slot is not reused before this frame's event (64-slot ring).
+    int rc;
+    if (gated) {
+        uint8_t* hex = nullptr;
+        int n_exempt = 0;
+        if (exempt) {
+            hex = reinterpret_cast<uint8_t*>(slot + L.slot_exempt);
+            std::memcpy(hex, exempt, (size_t)m);
+            for (int i = 0; i < m; ++i) n_exempt += exempt[i] != 0;
+        }
+        double* hm = mahal ? reinterpret_cast<double*>(slot + L.slot_mahal) : nullptr;
+        int s = 0;
+        rc = gated_frame(f, hidx, hz, m, hex, n_exempt, nullptr, hm, nullptr, true, &s);
+        if (rc) return rc;
+        if (mahal) std::memcpy(mahal, hm, (size_t)m * 8);      // (complete: the gate kernel's event has been waited for)
+        if (survivors) *survivors = s;
+    } else {
+        rc = enqueue_frame(f, hidx, hz, m, nullptr, true);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipEventRecord(f->slot_done[f->slot], f->stream));
+    f->slot = (f->slot + 1) % kStageSlots;
     return EKF_OK;
 }
 
@@ -884,6 +1002,7 @@ int ekf_destroy(ekf_filter* f) {
     }
     release_pipelining_token(f);
     if (f->ev_front) (void)hipEventDestroy(f->ev_front);
+    if (f->ev_gate) (void)hipEventDestroy(f->ev_gate);
     for (auto& e : f->ev) (void)hipEventDestroy(e);
     for (int i = 0; i < kStageSlots; ++i)
         if (f->slot_done[i]) (void)hipEventDestroy(f->slot_done[i]);
@@ -1027,30 +1146,35 @@ int ekf_add_markers(ekf_filter* f, const double* cam_frame_xyz, const double* di
 int ekf_observe(ekf_filter* f, const int32_t* lm_index, const double* z, int32_t m) {
     int rc = check_ready(f);
     if (rc) return rc;
-    if (m < 1) return fail(EKF_ERR_INVALID, "observe needs at least one detection");
-    if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
-    if (!lm_index || !z) return fail(EKF_ERR_INVALID, "NULL detections");
-    for (int i = 0; i < m; ++i)
-        if (lm_index[i] < 0 || lm_index[i] >= f->n_lm)
-            return fail(EKF_ERR_INVALID, "landmark index out of range");
-    const Layout& L = f->lay;
-    char* slot = f->ring.get() + (size_t)f->slot * L.slot_bytes;
-    HIP_TRY(hipEventSynchronize(f->slot_done[f->slot]));
-    int32_t* hidx = reinterpret_cast<int32_t*>(slot);
-    double* hz = reinterpret_cast<double*>(slot + align256((size_t)f->cfg.max_visible * 4));
-    const size_t zb = (size_t)m * L.rd * 8;
-    std::memcpy(hidx, lm_index, (size_t)m * 4);
-    std::memcpy(hz, z, zb);
-    // one copy: the pinned slot mirrors the device staging layout [indices, padded to 256 B | z]
-    static_assert(sizeof(int32_t) == 4, "layout");
-    if (L.off_z - L.off_idx != align256((size_t)f->cfg.max_visible * 4)) return fail(EKF_ERR_STATE, "staging layout");
-    // The kernels read the frame's detections (128 + 768 bytes at m = 32) straight from the pinned slot: a host-to-device
-    // copy in front of them costs more (API call + DMA start, ~8 us before the front kernel begins) than the PCIe reads
-    // cost the kernel's first round trip.  The slot is not reused before this frame's event (64-slot ring).
-    rc = enqueue_frame(f, hidx, hz, m, nullptr, true);
+    f->gate_stats[0] = f->gate_stats[1] = 0;
+    return observe_host(f, lm_index, z, m, f->gate_on(), nullptr, nullptr, nullptr);
+}
+
+int ekf_observe_gated(ekf_filter* f, const int32_t* lm_index, const double* z, int32_t m, const uint8_t* exempt, double* mahal,
+                      int32_t* survivors) {
+    int rc = check_ready(f);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(f->slot_done[f->slot], f->stream));
-    f->slot = (f->slot + 1) % kStageSlots;
+    if (!f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
+    f->gate_stats[0] = f->gate_stats[1] = 0;
+    const bool gated = f->gate_on() || mahal;
+    rc = observe_host(f, lm_index, z, m, gated, exempt, mahal, survivors);
+    if (rc == EKF_OK && !gated && survivors) *survivors = m;
+    return rc;
+}
+
+int ekf_set_gate(ekf_filter* f, double gate) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
+    if (!(gate > 0.0)) return fail(EKF_ERR_INVALID, "the gate must be > 0 (+inf: off) and not NaN");
+    f->gate = gate;
+    return EKF_OK;
+}
+
+int ekf_last_gate_stats(const ekf_filter* f, int64_t out[2]) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
+    out[0] = f->gate_stats[0];
+    out[1] = f->gate_stats[1];
     return EKF_OK;
 }
 
@@ -1062,6 +1186,8 @@ int ekf_observe_device(ekf_filter* f, const int32_t* lm_index_dev, const double*
     if (!lm_index_dev || !z_dev) return fail(EKF_ERR_INVALID, "NULL detections");
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
     // the indices are device-resident: range-checked by the kernels (EKF_ERR_INVALID at the next sync)
+    f->gate_stats[0] = f->gate_stats[1] = 0;
+    if (f->gate_on()) return gated_frame(f, lm_index_dev, z_dev, m, nullptr, 0, nullptr, nullptr, nullptr, true, nullptr);
     return enqueue_frame(f, lm_index_dev, z_dev, m, nullptr, true);
 }
 
@@ -1073,8 +1199,25 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
     if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
     if (!lm_index_dev || !z_dev) return fail(EKF_ERR_INVALID, "NULL detections");
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
-    // Pipelined mode (F(t+1) beside C(t), see run_pipelined) for the whole call if pipeline_wanted admits the frame shape
     const int rd = f->lay.rd;
+    f->gate_stats[0] = f->gate_stats[1] = 0;
+    if (f->gate_on()) {
+        // a gate is set: frame by frame in serial order, each frame on its survivors (gating inside a pipelined run would
+        // need the mask inside the front kernel)
+        f->seq_mode = EKF_SEQ_SERIAL;
+        f->shortcut.log();      // (a getter after the call waits for all of it)
+        for (int t = 0; t < frames; ++t) {
+            double* row = trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr;
+            int s = 0;
+            rc = gated_frame(f, lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd, m, nullptr, 0, nullptr, nullptr, row,
+                             false, &s);
+            if (rc == EKF_OK && s == 0) rc = repeat_row(f, row);
+            if (rc) return rc;
+        }
+        f->shortcut.log();
+        return EKF_OK;
+    }
+    // Pipelined mode (F(t+1) beside C(t), see run_pipelined) for the whole call if pipeline_wanted admits the frame shape
     const RunPlan plan = plan_runs(f, frames, [&](int) { return m; }, [](int) { return 0; });
     int mode = EKF_SEQ_SERIAL;
     rc = choose_pipelining(f, plan.want_runs, &mode);
@@ -1129,8 +1272,17 @@ int ekf_last_log_stats(const ekf_filter* f, int64_t out[4]) {
 
 int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames, const double* poses_dev,
                     void* log_ws, size_t log_ws_bytes, double* trajectory_dev) {
+    return ekf_observe_log_gated(f, lm_index, offsets, frames, poses_dev, log_ws, log_ws_bytes, trajectory_dev, nullptr);
+}
+
+int ekf_observe_log_gated(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
+                          const double* poses_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev,
+                          double* mahal_dev) {
     int rc = check_ready(f);
     if (rc) return rc;
+    if (mahal_dev && !f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
+    // a gate that is set, or distances asked for: frame by frame in serial order, each frame on its survivors
+    const bool gated = f->gate_on() || mahal_dev;
     // ---- validation on the host: nothing is enqueued before the whole log has passed
     if (frames < 0) return fail(EKF_ERR_INVALID, "negative frame count");
     if (frames > 0 && !offsets) return fail(EKF_ERR_INVALID, "offsets is NULL");
@@ -1143,6 +1295,7 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
     LogCheck lc;
     if ((rc = check_log(lm_index, offsets, frames, f->n_lm, f->cfg, "the log", &lc))) return rc;
     for (int i = 0; i < 4; ++i) f->log_stats[i] = 0;
+    f->gate_stats[0] = f->gate_stats[1] = 0;
     if (frames == 0) return EKF_OK;
 
     // ---- host staging: [indices | slots | (row, source) pairs of empty frames: those before the first stepped frame of the
@@ -1152,7 +1305,7 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
         int last = -1;
         for (int t = 0; t < frames; ++t) {
             if (offsets[t + 1] > offsets[t]) last = t;
-            else if (trajectory_dev) {
+            else if (trajectory_dev && !gated) {      // (gated: which frames are stepped is known frame by frame)
                 std::vector<int32_t>& v = last < 0 ? lead : rest;
                 v.push_back(t);
                 v.push_back(last);
@@ -1164,6 +1317,7 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
     p.take(up_bytes);
     const size_t lead_at = p.take(lead.size() * 4), rest_at = p.take(rest.size() * 4);
     p.take(256);
+    const size_t exempt_at = gated ? p.take((size_t)D) : 0;      // rule 4: the first occurrence of every first sighting
     const int turn = f->log_pin_turn;
     if (!f->log_pin_done[turn]) HIP_TRY(hipEventCreateWithFlags(&f->log_pin_done[turn], hipEventDisableTiming));
     HIP_TRY(hipEventSynchronize(f->log_pin_done[turn]));      // (the staging of the call before the previous one is consumed)
@@ -1181,13 +1335,19 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
     }
     if (!lead.empty()) std::memcpy(pin_lead, lead.data(), lead.size() * 4);
     if (!rest.empty()) std::memcpy(pin_rest, rest.data(), rest.size() * 4);
+    uint8_t* pin_exempt = f->log_pin[turn].at<uint8_t>(exempt_at);
+    if (gated && D > 0) {
+        std::memset(pin_exempt, 0, (size_t)D);
+        for (int32_t d : lc.slots) pin_exempt[d] = 1;
+    }
 
     auto m_of = [&](int t) { return (int)(offsets[t + 1] - offsets[t]); };
     auto nnew_of = [&](int t) { return (int)(lc.new_at[t + 1] - lc.new_at[t]); };
-    const RunPlan plan = plan_runs(f, frames, m_of, nnew_of);
+    const RunPlan plan = gated ? RunPlan{} : plan_runs(f, frames, m_of, nnew_of);
     int mode = EKF_SEQ_SERIAL;
     rc = choose_pipelining(f, plan.want_runs, &mode);
     if (rc) return rc;
+    if (gated) f->seq_mode = EKF_SEQ_SERIAL;
 
     // ---- device work, all on the handle's stream (the pipelined runs use the internal one as ekf_observe_sequence_device)
     if (D > 0) {
@@ -1195,24 +1355,40 @@ int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offse
         ekf_launch_log_prepare(poses_dev, D, rd, z_all, f->stream);
     }
     if (!lead.empty()) ekf_launch_log_fill_rows(trajectory_dev, pin_lead, (int32_t)(lead.size() / 2), f->state, f->stream);
-    rc = run_frames(
-        f, frames,
-        [&](int t) {
-            const int64_t d0 = offsets[t];
-            return RunFrame{idx_all + d0, z_all + (size_t)d0 * rd, m_of(t),
-                            trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr};
-        },
-        [&](int t) {
-            const int nnew = nnew_of(t);
-            if (nnew > 0)
-                by_cov_type(f, [&](auto elem) {
-                    ekf_launch_log_add_markers<decltype(elem)>(f->cfg.model, f->cov, f->ld, f->state, f->dims(), poses_dev,
-                                                               slots_all + lc.new_at[t], f->cfg.initial_landmark_uncertainty, nnew,
-                                                               f->stream);
-                });
-            return nnew;
-        },
-        plan, mode == EKF_SEQ_PIPELINED, f->log_stats);
+    auto frame_of = [&](int t) {
+        const int64_t d0 = offsets[t];
+        return RunFrame{idx_all + d0, z_all + (size_t)d0 * rd, m_of(t), trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr};
+    };
+    auto first_sightings = [&](int t) {
+        const int nnew = nnew_of(t);
+        if (nnew > 0)
+            by_cov_type(f, [&](auto elem) {
+                ekf_launch_log_add_markers<decltype(elem)>(f->cfg.model, f->cov, f->ld, f->state, f->dims(), poses_dev,
+                                                           slots_all + lc.new_at[t], f->cfg.initial_landmark_uncertainty, nnew,
+                                                           f->stream);
+            });
+        return nnew;
+    };
+    if (gated) {
+        // first sightings, the gate on the prior they leave, the frame on its survivors; a frame without detections or
+        // without a survivor is not stepped, and its row repeats the camera state
+        for (int t = 0; t < frames && rc == EKF_OK; ++t) {
+            const RunFrame r = frame_of(t);
+            int s = 0;
+            if (r.m > 0) {
+                const int nnew = first_sightings(t);
+                f->n_lm += nnew;
+                f->log_stats[3] += nnew;
+                const int64_t d0 = offsets[t];
+                rc = gated_frame(f, r.idx, r.z, r.m, pin_exempt + d0, nnew, mahal_dev ? mahal_dev + d0 : nullptr, nullptr,
+                                 r.traj_row, false, &s);
+                if (rc == EKF_OK && s > 0) f->log_stats[0] += 1;
+            }
+            if (rc == EKF_OK && s == 0) rc = repeat_row(f, r.traj_row);
+        }
+    } else {
+        rc = run_frames(f, frames, frame_of, first_sightings, plan, mode == EKF_SEQ_PIPELINED, f->log_stats);
+    }
     if (rc == EKF_OK && !rest.empty())
         ekf_launch_log_fill_rows(trajectory_dev, pin_rest, (int32_t)(rest.size() / 2), f->state, f->stream);
     // A state getter after the call must wait for the whole call (the last frame's state may come from a pipelined run, whose

@@ -225,6 +225,29 @@ template <typename T>
 void ekf_launch_log_add_markers(int model, void* cov, int64_t ld, double* state, int32_t dims, const double* poses_dev,
                                 const int32_t* slots_dev, double default_unc, int32_t count, hipStream_t s);
 void ekf_launch_log_fill_rows(double* traj_dev, const int32_t* pairs, int32_t count, const double* state, hipStream_t s);
+// Per-detection chi-square gate of one frame (ekf_gate.hip; EKF_FLAG_GATE): d^2 of every detection on the prior, and the
+// survivors compacted in log order.  One workgroup of EKF_GATE_THREADS threads, whatever m.
+#define EKF_GATE_THREADS 256
+struct EkfGateArgs {
+    const void* cov;            // P, f32 or f64 (widened on load), leading dimension ld
+    int64_t ld;
+    const double* state;
+    int32_t n_lm, dims, m;
+    const int32_t* idx;         // [m] landmark indices (device, or pinned host)
+    const double* z;            // [m, rd]
+    const uint8_t* exempt;      // [m] or null: non-zero = d^2 = 0 is reported and the detection is never rejected
+    EkfNoise nz;
+    double gate;                // +inf: nothing is rejected
+    double* mahal;              // [m] or null
+    double* mahal_host;         // [m] pinned host or null: the same values for a host caller
+    int32_t* out_idx;           // [<= m] indices of the survivors, in log order
+    double* out_z;              // [<= m, rd]
+    int32_t* status;            // the filter's status words ([0] != 0: nothing is tested any more, everything stays)
+    int32_t* status_host;       // pinned mirror of "the status word is no longer zero", or null
+    int32_t* result_host;       // pinned: [0] survivors (what the host waits for), [1] some pivot failed (diagnostic only: the
+                                // frame's own factorisation reports the failure, as it does without a gate)
+};
+template <typename T> void ekf_launch_frame_gate(int model, const EkfGateArgs& a, hipStream_t s);
 template <typename T>
 void ekf_launch_cov_diag(const void* cov, int64_t ld, double* out_dev, int32_t count, hipStream_t s);
 

@@ -127,6 +127,10 @@ class BaseFilter:
             self.detector = self.init_aruco_detector(aruco_dict)
         self.camera_pose = initial_pose
         self._map_file = map_file
+        # per detection of the last observed frame, indexed like its ``ids`` (filters built with ``gate=``; else None):
+        # Mahalanobis distance d^2 (0: a marker the frame added, NaN: not tested) and whether the gate rejected it
+        self.last_mahal = None
+        self.last_rejected = None
 
     def _load_initial_map(self):
         """Subclasses call this once their back-end exists (the reference calls
@@ -194,7 +198,35 @@ class BaseFilter:
             camera_pose = self.get_cam_estimate(iteration)
         return None, camera_pose, marker_poses, detected_poses
 
-    def process_detection_log(self, ids, poses, offsets, has_detections=None) -> np.ndarray:
+    # -- the per-detection chi-square gate (ekf_set_gate) ----------------------------------------
+    @property
+    def gate(self):
+        """The gate: None (a filter built without it), ``inf`` (off) or the threshold on d^2."""
+        return self.backend.gate
+
+    def set_gate(self, gate) -> None:
+        """Reject every detection whose own squared Mahalanobis distance on the prior exceeds ``gate`` before the frame
+        is updated (one flipped IPPE pose otherwise bends the whole map); None or ``inf``: off.  The filter must have been
+        constructed with ``gate=`` (``inf`` will do).  A bad gate raises ``ValueError`` and nothing changes."""
+        self.backend.set_gate(gate)
+
+    @staticmethod
+    def _first_occurrences(ids, fresh):
+        """bool [m]: the first detection of every marker in ``fresh`` (the markers the frame has just added)."""
+        left, out = set(fresh), np.zeros(len(ids), dtype=bool)
+        for j, marker in enumerate(ids):
+            if marker in left:
+                left.discard(marker)
+                out[j] = True
+        return out
+
+    def _observe_gated(self, index, z, exempt) -> None:
+        backend = self.backend
+        d2 = backend.observe(index, z, exempt=exempt, mahal=True)
+        self.last_mahal = d2
+        self.last_rejected = d2 > backend.gate      # (NaN and 0 compare false; gate inf: nothing)
+
+    def process_detection_log(self, ids, poses, offsets, has_detections=None, mahal=False):
         """``process_detections(ids_t, poses_t)`` with ``should_filter=True`` for every frame of a recorded log, in ONE call
         that runs predict / update of every frame on the device (ekf_observe_log).  The log is a CSR batch as in a replay
         file (``main/run_slam.py: detection_frames``): ``ids [D]``, ``poses [D,6]`` ``[tvec | rvec]`` (NumPy, or a
@@ -202,7 +234,10 @@ class BaseFilter:
         A frame without detections is not stepped.  Marker ids are mapped to landmark indices here (``plan_detection_log``);
         the buffers grow first if the log needs more landmarks or detections per frame.  Returns the camera pose
         ``state[0:7]`` after every frame, ``(F, 7)``.  A malformed log raises ``ValueError`` before anything runs, and the
-        filter (``landmarks`` included) is left as it was."""
+        filter (``landmarks`` included) is left as it was.  A gate that is set (``set_gate``) acts on every frame, with
+        the first occurrence of every marker the log adds exempt; ``mahal=True`` (a filter built with ``gate=``) returns
+        ``(trajectory, d2 [D])`` with every detection's squared Mahalanobis distance, indexed like ``ids`` (NaN for the
+        rows of frames without detections), gate or no gate; ``d2 > gate`` are the rejected ones."""
         import torch
         backend = self.backend
         plan = plan_detection_log(self.landmarks, self.num_landmarks, ids, offsets, has_detections)
@@ -224,11 +259,16 @@ class BaseFilter:
         if plan.widest > backend.max_visible:
             backend.grow(new_max_visible=min(backend.MAX_VISIBLE_LIMIT[backend.lm_dims], plan.widest))
         traj = torch.empty((plan.offsets.shape[0] - 1, 7), dtype=torch.float64, device=backend.device)
-        backend.observe_log(plan.index, plan.offsets, poses, traj)
+        mahal_t = torch.empty((plan.index.shape[0],), dtype=torch.float64, device=backend.device) if mahal else None
+        backend.observe_log(plan.index, plan.offsets, poses, traj, mahal_t)
         backend.sync()
         self.landmarks.update(plan.new_landmarks)
         self.num_landmarks = plan.num_landmarks
-        return traj.cpu().numpy()
+        if not mahal:
+            return traj.cpu().numpy()
+        d2 = np.full(plan.keep.shape[0], np.nan)
+        d2[plan.keep] = mahal_t.cpu().numpy()
+        return traj.cpu().numpy(), d2
 
     def save_map(self, filename: str) -> None:
         """Map text format of base_filter.py:214-247: three comment lines and a
@@ -273,17 +313,25 @@ class BaseFilter:
         """Full filter state for an exact resume: state vector, dense covariance (float64 copy of
         the device matrix) and the marker-id -> index table, as a plain ``.npz``."""
         ids = [k for k, _ in sorted(self.get_lm_estimates(), key=lambda kv: kv[1])]
+        gate = self.backend.gate
         np.savez(filename, state=np.asarray(self.state, dtype=np.float64),
                  cov=np.asarray(self.uncertainty, dtype=np.float64),
-                 marker_ids=np.asarray(ids, dtype=np.int64), filter=type(self).__name__)
+                 marker_ids=np.asarray(ids, dtype=np.int64), filter=type(self).__name__,
+                 gate=np.float64(np.inf if gate is None else gate))
 
     def load_checkpoint(self, filename: str) -> None:
         """Inverse of ``save_checkpoint`` on a filter of the same class; the device covariance
-        is overwritten bit-for-bit when the stored values fit the covariance dtype."""
+        is overwritten bit-for-bit when the stored values fit the covariance dtype.  The gate is part of the checkpoint: a
+        filter built with ``gate=`` takes the stored one, so a checkpoint saved without a gate (stored as ``inf``) switches
+        this filter's gate OFF -- call ``set_gate`` afterwards to keep your own; a stored finite gate needs a filter built
+        with ``gate=`` (``ValueError`` otherwise).  Checkpoints from before the gate leave it as it is."""
         with np.load(filename, allow_pickle=False) as ck:
             if str(ck["filter"]) != type(self).__name__:
                 raise ValueError(f"checkpoint of {ck['filter']} loaded into {type(self).__name__}")
             state, cov, ids = ck["state"], ck["cov"], ck["marker_ids"]
+            gate = float(ck["gate"]) if "gate" in ck.files else None      # (checkpoints from before the gate: as it is)
+        if gate is not None and (np.isfinite(gate) or self.backend.can_gate):
+            self.set_gate(gate)      # (a finite gate needs a filter built with gate=: ValueError otherwise)
         if len(ids) == 0:
             return
         self.backend.set_state_cov(state, cov)

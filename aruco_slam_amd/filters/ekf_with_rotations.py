@@ -45,10 +45,13 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
 
     def __init__(self, initial_camera_pose, *, max_landmarks: int | None = None, max_visible: int | None = None,
                  cov_dtype: str = "float64", cov_kernel: str = "auto", device: str = "cuda:0",
-                 lookahead: bool | None = None, fused: bool = True, noise: dict | None = None) -> None:
+                 lookahead: bool | None = None, fused: bool = True, noise: dict | None = None,
+                 gate: float | None = None) -> None:
         """``noise``: values that replace the module's noise constants, keyed by the ``ekf_config`` field names
         (``initial_camera_uncertainty``, ``initial_landmark_uncertainty``, ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``);
-        None keeps the reference's constants."""
+        None keeps the reference's constants.  ``gate``: the chi-square gate on every detection's own Mahalanobis
+        distance (``set_gate``; 7 degrees of freedom, approximate: 14.067 / 18.475 / 24.322 for 95 / 99 / 99.9 %);
+        ``inf``: off, but the distances are reported (``last_mahal``); None: a filter without the gate."""
         super().__init__(initial_camera_pose, None)
         self._initial_pose = np.array(initial_camera_pose)
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -69,7 +72,7 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         constants.update(noise or {})
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype, quat_mode="scalar_first",
                            cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
-                           model="ekf_rotations", noise=constants)
+                           model="ekf_rotations", noise=constants, gate=gate)
         self._hip.reset(self._initial_pose.astype(np.float64))
 
     @property
@@ -106,7 +109,12 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
                 known[idx] = self.num_landmarks
                 self.num_landmarks += 1
             index = [known[i] for i in ids]
+            if self._hip.can_gate:      # the markers added just now are exempt from the gate (their z = h by construction)
+                z = np.hstack((poses[:, XYZ_DIMS], euler_xyz_to_quat(poses[:, 3:6])))
+                return self._observe_gated(index, z, self._first_occurrences(ids, fresh))
         z = np.hstack((poses[:, XYZ_DIMS], euler_xyz_to_quat(poses[:, 3:6])))      # :216-224
+        if self._hip.can_gate:
+            return self._observe_gated(index, z, None)
         self._hip.observe(index, z)
 
     # -- :275-335 --------------------------------------------------------------

@@ -36,7 +36,7 @@ class EKF(BaseFilter):
                  max_visible: int | None = None, cov_dtype: str = "float64",
                  quat_update: str = "as_written", cov_kernel: str = "auto",
                  device: str = "cuda:0", map_file=None, lookahead: bool | None = None,
-                 fused: bool = True, noise: dict | None = None) -> None:
+                 fused: bool = True, noise: dict | None = None, gate: float | None = None) -> None:
         """Positional arguments as the reference (:40-43).  Keyword-only extras:
         initial capacity (default: the number of ids of ``aruco_dict`` -- DICT_5X5_50
         has 50, base_filter.py:81-82; the buffers grow when more markers or more
@@ -45,7 +45,10 @@ class EKF(BaseFilter):
         (``"as_written"`` reproduces :138-149 exactly, ``"scalar_first"`` is the
         consistent one).  ``noise``: values that replace the module's noise constants, keyed by the
         ``ekf_config`` field names (``initial_camera_uncertainty``, ``initial_landmark_uncertainty``,
-        ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``); None keeps the reference's constants."""
+        ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``); None keeps the reference's constants.
+        ``gate``: the chi-square gate on every detection's own Mahalanobis distance (``set_gate``; 3 degrees of
+        freedom: 7.815 / 11.345 / 16.266 for 95 / 99 / 99.9 %); ``inf``: off, but the distances are reported
+        (``last_mahal``); None: a filter without the gate."""
         super().__init__(initial_camera_pose, map_file, aruco_dict)
         self._initial_pose = np.array(initial_camera_pose)      # :46, dtype kept
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -66,7 +69,7 @@ class EKF(BaseFilter):
         constants.update(noise or {})
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype,
                            quat_mode=quat_update, cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
-                           noise=constants)
+                           noise=constants, gate=gate)
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._load_initial_map()
 
@@ -110,6 +113,10 @@ class EKF(BaseFilter):
                 known[idx] = self.num_landmarks
                 self.num_landmarks += 1
             index = [known[i] for i in ids]
+            if self._hip.can_gate:      # the markers added just now are exempt from the gate (their z = h by construction)
+                return self._observe_gated(index, poses[:, XYZ_DIMS], self._first_occurrences(ids, fresh))
+        if self._hip.can_gate:
+            return self._observe_gated(index, poses[:, XYZ_DIMS], None)
         self._hip.observe(index, poses[:, XYZ_DIMS])
 
     # -- :239-290 --------------------------------------------------------------

@@ -20,6 +20,7 @@ EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST = 0, 1
 EKF_FLAG_WIDE_FRAMES = 8       # ekf_config.flags bit 3: up to 1024 detections per frame
 EKF_FLAG_BATCH_LARGE_MAPS = 16  # ekf_config.flags bit 4 (batches): up to 1024 state dims per member
 EKF_FLAG_BATCH_WIDE_FRAMES = 32  # ekf_config.flags bit 5 (batches): up to 64 (EKF) / 50 (EKF_Rotations) detections per frame
+EKF_FLAG_GATE = 64             # ekf_config.flags bit 6: the per-detection chi-square gate of the single filter
 EKF_COVK_AUTO, EKF_COVK_VALU, EKF_COVK_MFMA, EKF_COVK_MFMA_TILE, EKF_COVK_MFMA_MACRO = 0, 1, 2, 3, 4
 
 # frames in the end-gate ring of ekf_debug_fetch item 6 (csrc/ekf_kernels.h: EKF_GATE_LOG_FRAMES)
@@ -40,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "ekf_batch_replica_workspace_bytes", "ekf_batch_observe_replicas",
     "ekf_batch_set_gate", "ekf_batch_observe_logs_gated", "ekf_batch_observe_replicas_gated",
     "ekf_batch_replica_corners", "ekf_batch_observe_corner_replicas",
+    "ekf_set_gate", "ekf_observe_gated", "ekf_observe_log_gated", "ekf_last_gate_stats",
 )
 
 
@@ -109,6 +111,10 @@ def load_library(path: str | Path | None = None):
         "ekf_log_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],
         "ekf_observe_log": [vp, ip, C.POINTER(C.c_int64), C.c_int32, vp, vp, C.c_size_t, vp],
         "ekf_last_log_stats": [vp, C.POINTER(C.c_int64)],
+        "ekf_set_gate": [vp, C.c_double],
+        "ekf_observe_gated": [vp, ip, dp, C.c_int32, C.POINTER(C.c_uint8), dp, ip],
+        "ekf_observe_log_gated": [vp, ip, C.POINTER(C.c_int64), C.c_int32, vp, vp, C.c_size_t, vp, vp],
+        "ekf_last_gate_stats": [vp, C.POINTER(C.c_int64)],
         "ekf_batch_query_sizes": [C.POINTER(EkfConfig), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_size_t),
                                   C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
         "ekf_batch_create": [C.POINTER(EkfConfig), C.c_int32, C.POINTER(vp)],
@@ -149,6 +155,16 @@ def load_library(path: str | Path | None = None):
     return lib
 
 
+def check_gate(gate):
+    """``gate`` (None, or a number > 0; ``inf``: off) as None or a float; ``ValueError`` otherwise."""
+    if gate is None:
+        return None
+    g = float(gate)
+    if not g > 0.0:
+        raise ValueError("gate must be > 0 (inf: off) and not NaN")
+    return g
+
+
 def _dptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
@@ -183,7 +199,10 @@ class HipEkf:
 
     def __init__(self, max_landmarks: int, max_visible: int, cov_dtype="float64",
                  quat_mode="as_written", cov_kernel="auto", device="cuda:0", noise=None,
-                 lookahead=None, model="ekf", fused=True):
+                 lookahead=None, model="ekf", fused=True, gate=None):
+        """``gate``: None = a filter without the per-detection gate (sizes and results as ever); a number > 0 = the
+        chi-square gate on every detection's own d^2 (``set_gate``; ``inf``: the filter can gate and report distances, but
+        the gate is off)."""
         import torch
         self._torch = torch
         self.lib = load_library()
@@ -204,6 +223,9 @@ class HipEkf:
         if not fused:
             cfg.flags |= 4        # separate gather / solve / panel launches
         cfg.flags |= EKF_FLAG_WIDE_FRAMES
+        gate = check_gate(gate)
+        if gate is not None:
+            cfg.flags |= EKF_FLAG_GATE
         self.fused = bool(fused)  # ("force" of earlier versions == True: there is no automatic fallback any more)
         self._last_m = 1
         cfg.model = {"ekf": 0, "ekf_rotations": 1}[model]
@@ -231,6 +253,32 @@ class HipEkf:
                                                   self.state_t.data_ptr(), self.ws_t.data_ptr(),
                                                   wb.value))
         self.cfg = cfg
+        self.gate = None       # None: built without the gate; inf: off
+        if gate is not None:
+            self.set_gate(gate)
+
+    @property
+    def can_gate(self) -> bool:
+        return bool(self.cfg.flags & EKF_FLAG_GATE)
+
+    def set_gate(self, gate) -> None:
+        """The chi-square gate on every detection's own Mahalanobis distance (ekf_set_gate): a number > 0, ``inf`` or
+        None = off.  Needs a filter constructed with ``gate=`` (``inf`` will do); persistent across ``reset``."""
+        g = check_gate(gate)
+        if g is None:
+            if not self.can_gate:
+                return
+            g = float("inf")
+        if not self.can_gate:
+            raise ValueError("this filter was built without the gate: construct it with gate=... (gate=float('inf'): off)")
+        self._check(self.lib.ekf_set_gate(self.h, g))
+        self.gate = g
+
+    def last_gate_stats(self) -> dict:
+        """Detections the last observe call tested and rejected (ekf_last_gate_stats)."""
+        out = (C.c_int64 * 2)()
+        self._check(self.lib.ekf_last_gate_stats(self.h, out))
+        return {"tested": int(out[0]), "rejected": int(out[1])}
 
     def _check(self, rc):
         if rc != 0:
@@ -296,15 +344,29 @@ class HipEkf:
         self._check(self.lib.ekf_add_markers(self.h, _dptr(xyz), _dptr(unc) if unc is not None else None,
                                              xyz.shape[0]))
 
-    def observe(self, lm_index, z):
+    def observe(self, lm_index, z, exempt=None, mahal=False):
+        """One frame.  With ``exempt`` (bool [m]: detections the gate leaves alone, d^2 = 0) or ``mahal=True`` the frame
+        goes through ekf_observe_gated (a filter built with ``gate=``) and returns every detection's d^2 [m]; a set gate
+        acts either way."""
         idx = np.ascontiguousarray(lm_index, dtype=np.int32)
         z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1, self.rows_per_detection)
         assert idx.shape[0] == z.shape[0]
         self._last_m = idx.shape[0]
         if idx.shape[0] > self.max_visible:      # the reference takes any number of detections per frame (:158-200)
             self.grow(new_max_visible=min(self.MAX_VISIBLE_LIMIT[self.lm_dims], max(2 * self.max_visible, idx.shape[0])))
-        self._check(self.lib.ekf_observe(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z),
-                                         idx.shape[0]))
+        if exempt is None and not mahal:
+            self._check(self.lib.ekf_observe(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z),
+                                             idx.shape[0]))
+            return None
+        ex = None
+        if exempt is not None:
+            ex = np.ascontiguousarray(exempt, dtype=np.uint8).reshape(-1)
+            assert ex.shape[0] == idx.shape[0]
+        d2 = np.empty(idx.shape[0]) if mahal else None
+        self._check(self.lib.ekf_observe_gated(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z), idx.shape[0],
+                                               ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None,
+                                               _dptr(d2) if mahal else None, None))
+        return d2
 
     def observe_sequence(self, idx_t, z_t, traj_t=None):
         """idx_t int32 [F,m], z_t float64 [F,m,3] device tensors (resident
@@ -317,11 +379,13 @@ class HipEkf:
             self.h, idx_t.data_ptr(), z_t.data_ptr(), m, frames,
             traj_t.data_ptr() if traj_t is not None else None))
 
-    def observe_log(self, lm_index, offsets, poses, traj=None):
+    def observe_log(self, lm_index, offsets, poses, traj=None, mahal=None):
         """A whole detection log in one call (ekf_observe_log): lm_index int [D] landmark index of every detection (first
         sightings numbered n, n+1, ... in order of first occurrence), offsets int [F+1], poses [D,6] ``[tvec | rvec]`` as a
         NumPy array (uploaded once) or a contiguous float64 device tensor on this filter's device; traj: float64 device
-        tensor [F,7] that receives state[0:7] after every frame, or None.  Capacity must already suffice (grow() first)."""
+        tensor [F,7] that receives state[0:7] after every frame, or None; mahal: float64 device tensor [D] that receives
+        every detection's d^2 (ekf_observe_log_gated; a filter built with ``gate=``), or None.  Capacity must already
+        suffice (grow() first)."""
         torch = self._torch
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
         offs = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
@@ -340,6 +404,9 @@ class HipEkf:
         if traj is not None:
             assert traj.is_cuda and traj.dtype == torch.float64 and traj.is_contiguous()
             assert tuple(traj.shape) == (frames, 7)
+        if mahal is not None:
+            assert mahal.is_cuda and mahal.dtype == torch.float64 and mahal.is_contiguous()
+            assert tuple(mahal.shape) == (idx.shape[0],)
         nbytes = C.c_size_t()
         self._check(self.lib.ekf_log_workspace_bytes(self.h, idx.shape[0], C.byref(nbytes)))
         # device tensors of the caller (poses, traj) were produced on its current stream
@@ -354,10 +421,13 @@ class HipEkf:
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
             if traj is not None:
                 traj.record_stream(self.stream)
-            self._check(self.lib.ekf_observe_log(
+            if mahal is not None:
+                mahal.record_stream(self.stream)
+            self._check(self.lib.ekf_observe_log_gated(
                 self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), frames,
                 poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(), nbytes.value,
-                traj.data_ptr() if traj is not None else None))
+                traj.data_ptr() if traj is not None else None,
+                mahal.data_ptr() if mahal is not None and idx.shape[0] else None))
         self._log_keep = (poses_t, ws)     # (released by the next call; record_stream already guards the allocator)
         m = np.diff(offs)
         if m.size and m.max() > 0:

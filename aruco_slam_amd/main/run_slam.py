@@ -73,8 +73,10 @@ def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryW
 
 def main(cmdline_args: argparse.Namespace) -> None:
     initial_pose = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0])     # run_slam.py:85-88 (int64)
-    tracker = init_tracker(cmdline_args.filter, initial_pose,
-                           **getattr(cmdline_args, "filter_kwargs", {}))
+    kwargs = dict(getattr(cmdline_args, "filter_kwargs", {}))
+    if getattr(cmdline_args, "gate", None) is not None:
+        kwargs["gate"] = cmdline_args.gate      # (acts in the frame loop and in the resident replay alike)
+    tracker = init_tracker(cmdline_args.filter, initial_pose, **kwargs)
     out_dir = Path(getattr(cmdline_args, "output_dir", "outputs"))
     out_dir.mkdir(parents=True, exist_ok=True)
 
@@ -114,6 +116,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--output-dir", dest="output_dir", type=str, default="outputs")
     parser.add_argument("--resident", action="store_true",
                         help="with --detections: replay the whole file on the device in one call")
+    parser.add_argument("--gate", type=float, default=None,
+                        help="chi-square gate on every detection's own squared Mahalanobis distance: detections beyond "
+                             "it are left out of their frame (ekf: 3 degrees of freedom, 11.345 = 99 %%; ekf_rotations: 7, "
+                             "18.475)")
     return parser
 
 

@@ -54,6 +54,8 @@ enum { EKF_FLAG_WIDE_FRAMES = 8 };
 enum { EKF_FLAG_BATCH_LARGE_MAPS = 16 };
 /* ekf_config.flags bit 5, read by ekf_batch_* only: up to 64 (EKF_MODEL_ROTATIONS: 50) detections per frame in a batch */
 enum { EKF_FLAG_BATCH_WIDE_FRAMES = 32 };
+/* ekf_config.flags bit 6, read by ekf_* (the single filter) only: the per-detection chi-square gate (ekf_set_gate) */
+enum { EKF_FLAG_GATE = 64 };
 enum { EKF_COVK_AUTO = 0, EKF_COVK_VALU = 1, EKF_COVK_MFMA = 2, EKF_COVK_MFMA_TILE = 3, EKF_COVK_MFMA_MACRO = 4 };
 
 enum {
@@ -91,7 +93,10 @@ typedef struct ekf_config {
                              * 384 rows turn into W (ekf_query_sizes: + 8 kmax ld bytes).  Without it, sizes and
                              * limits are as before.
                              * bit 4 (EKF_FLAG_BATCH_LARGE_MAPS), bit 5 (EKF_FLAG_BATCH_WIDE_FRAMES): batches only,
-                             * see ekf_batch_query_sizes. */
+                             * see ekf_batch_query_sizes.
+                             * bit 6 (EKF_FLAG_GATE): the filter can gate its detections (ekf_set_gate); the workspace
+                             * then also holds the survivors of a frame and its distances (ekf_query_sizes: + 68
+                             * max_visible bytes and change).  Without it, sizes, layout and results are as before. */
     /* noise constants, defaults = extended_kalman_filter.py:21-27 */
     double initial_camera_uncertainty;   /* 0.1  */
     double initial_landmark_uncertainty; /* 0.7  */
@@ -459,6 +464,44 @@ int ekf_batch_observe_corner_replicas(ekf_batch *b, const int32_t *lm_index, con
                                       const double *dist_coeffs, int32_t n_dist, void *ws, size_t ws_bytes,
                                       double *trajectory_dev, double *nis_dev, double *cam_cov_dev, double *mahal_dev,
                                       uint8_t *flipped_dev);
+
+/* ---- The same gate for the single filter (ekf_config.flags bit 6, EKF_FLAG_GATE).  Without the flag ekf_set_gate,
+ * ekf_observe_gated and ekf_observe_log_gated with mahal_dev given return EKF_ERR_STATE; ekf_observe_log_gated with
+ * mahal_dev NULL is ekf_observe_log, and ekf_last_gate_stats reports 0 / 0.
+ * Semantics: rules 1 - 7 of "Per-detection chi-square gate" above, with "member" read as "filter" and the one constant
+ * gate of the handle: per detection S_d = H_d (P+Q) H_d^T + r_uncertainty I from the (10 + lmd)^2 support block of the
+ * prior P, d^2 = |L_d^-1 r_d|^2; a detection is rejected iff every pivot was positive and finite and d^2 > gate; after a
+ * failed pivot the detection is kept, its distance is NaN and the frame fails as it does without a gate
+ * (EKF_ERR_NUMERIC at the next synchronising call); the frame runs on the survivors in log order; a frame with no survivor
+ * is not stepped (no predict; its trajectory row repeats); an exempt detection reports d^2 = 0 and is never rejected.
+ * Once the filter carries a sticky error, nothing is tested any more: the distances are NaN and every detection stays.
+ * State, P, landmark count and trajectory of a gated frame are bit for bit those of the same call on the frame with the
+ * rejected detections deleted, at every map size, either covariance dtype (all gate arithmetic is f64: an f32 P is widened
+ * on load) and every frame width: one kernel (ekf_gate.hip) in front of everything else of the frame tests the detections
+ * and compacts the survivors, the host waits for their number, and the frame's ordinary kernels run on them.  A gated
+ * frame therefore costs one host round trip, and gated sequence and log calls run frame by frame in serial order
+ * (ekf_last_sequence_mode: EKF_SEQ_SERIAL; ekf_last_log_stats: 0 pipelined frames).
+ *
+ * ekf_set_gate: +inf is off, the state after ekf_create; NaN, <= 0 or -inf gives EKF_ERR_INVALID and nothing changes.  The
+ *   gate is persistent: ekf_reset and ekf_grow keep it.  ekf_observe, ekf_observe_device and
+ *   ekf_observe_sequence_device honour a set gate, with no exemptions; ekf_observe_log too, with those below.
+ * ekf_observe_gated: ekf_observe (host pointers) with exempt [m] bytes or NULL (non-zero: exempt; BaseFilter.observe passes
+ *   the markers it has just added), mahal [m] or NULL (d^2 of every detection) and survivors or NULL (how many stayed).
+ *   With the gate off and mahal requested, the distances are reported and nothing is rejected.
+ * ekf_observe_log_gated: ekf_observe_log with mahal_dev [D] DEVICE or NULL, indexed like lm_index.  The first occurrence
+ *   of a landmark first sighted in its frame is exempt (rule 4; decided on the host).  mahal_dev: 0 for an exempt
+ *   detection, NaN after a failed pivot and for every frame after the failing one; a frame whose detections were all
+ *   rejected keeps their distances.  With the gate off and mahal_dev NULL it IS ekf_observe_log, to the bit, pipelined runs
+ *   included.
+ * ekf_last_gate_stats: out[0] detections tested (exempt ones not counted), out[1] detections rejected by the last observe
+ *   call of any kind. */
+int ekf_set_gate(ekf_filter *f, double gate);
+int ekf_observe_gated(ekf_filter *f, const int32_t *lm_index, const double *z, int32_t m, const uint8_t *exempt /* [m] or NULL */,
+                      double *mahal /* [m] host or NULL */, int32_t *survivors /* or NULL */);
+int ekf_observe_log_gated(ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames,
+                          const double *poses_dev, void *log_ws, size_t log_ws_bytes, double *trajectory_dev,
+                          double *mahal_dev /* [D] or NULL */);
+int ekf_last_gate_stats(const ekf_filter *f, int64_t out[2]);
 
 const char *ekf_last_error_string(void);
 

@@ -9,6 +9,8 @@ updates/s is steady frames per second of the steady segment; the bootstrap segme
 
     python tools/replay_bench.py --n 1024 --m 24 40 --steady 2000 --dtype float32     # C3-like
     python tools/replay_bench.py --n 256 --m 8 24 --steady 2000 --dtype float64       # C2-like
+    python tools/replay_bench.py --gate 1e300      # every frame through the gate kernel, nothing rejected: the price of
+                                                   # the host round trip per frame and of losing the pipelined mode
 """
 from __future__ import annotations
 
@@ -33,7 +35,7 @@ def _segment(log, t0, t1):
 
 def _filter(args):
     from aruco_slam_amd.filters.extended_kalman_filter import EKF
-    return EKF(INIT, max_landmarks=args.n, max_visible=args.m[1], cov_dtype=args.dtype)
+    return EKF(INIT, max_landmarks=args.n, max_visible=args.m[1], cov_dtype=args.dtype, gate=args.gate)
 
 
 def main():
@@ -44,6 +46,7 @@ def main():
     ap.add_argument("--dtype", default="float32", choices=("float32", "float64"))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--variants", default="per_frame,log,sequence")
+    ap.add_argument("--gate", type=float, default=None, help="chi-square gate on every detection (default: a filter without)")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.synthetic import SyntheticStream, ragged_log
@@ -52,7 +55,7 @@ def main():
     boot = log["bootstrap_frames"]
     frames = len(log["has_detections"])
     m_steady = np.diff(log["offsets"])[boot:]
-    common = {"n": args.n, "m_range": list(args.m), "m_mean": float(m_steady.mean()), "dtype": args.dtype,
+    common = {"n": args.n, "m_range": list(args.m), "m_mean": float(m_steady.mean()), "dtype": args.dtype, "gate": args.gate,
               "bootstrap_frames": boot, "steady_frames": args.steady}
 
     def emit(**kv):

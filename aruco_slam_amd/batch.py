@@ -797,6 +797,50 @@ class EKFBatch:
         self.landmarks[b] = {k: i for i, k in enumerate(ids)}
         self.num_landmarks[b] = len(ids)
 
+    def remove_markers(self, per_member_ids) -> None:
+        """Take landmarks out of the members' maps (``ekf_batch_remove_markers``; ``BaseFilter.remove_markers`` per member,
+        in one launch): ``per_member_ids`` is a list of B marker-id lists (empty or None: that member is left alone), or a
+        dict ``member -> ids``.  Every member's other landmarks keep their order and move up; ``landmarks`` and
+        ``num_landmarks`` follow.  An unknown id raises ``KeyError`` and a duplicate ``ValueError`` before anything runs, and
+        no member changes."""
+        from .filters.map_management import renumber_landmarks
+        torch = self._torch
+        if isinstance(per_member_ids, dict):
+            lists = [[] for _ in range(self.members)]
+            for b, ids in per_member_ids.items():
+                lists[self._member(b)] = [int(k) for k in ids]
+        else:
+            if len(per_member_ids) != self.members:
+                raise ValueError(f"need {self.members} id lists (empty for a member that keeps its map), got {len(per_member_ids)}")
+            lists = [[] if ids is None else [int(k) for k in ids] for ids in per_member_ids]
+        index, tables = [], []
+        for b, ids in enumerate(lists):
+            for marker in ids:
+                if marker not in self.landmarks[b]:
+                    raise KeyError(f"member {b}: marker {marker} is not in the map")
+            if len(set(ids)) != len(ids):
+                raise ValueError(f"member {b}: duplicate marker id in the removal list")
+            index.append([self.landmarks[b][marker] for marker in ids])
+            tables.append(renumber_landmarks(self.landmarks[b], index[-1]))
+        offsets = np.concatenate([[0], np.cumsum([len(i) for i in index])]).astype(np.int64)
+        if offsets[-1] == 0:
+            return
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(i, dtype=np.int32) for i in index]), dtype=np.int32)
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_batch_remove_workspace_bytes(self.h, int(offsets[-1]), C.byref(nbytes)))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            cov_t, state_t = torch.empty_like(self.cov_t), torch.empty_like(self.state_t)
+            ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
+            self._check(self.lib.ekf_batch_remove_markers(self.h, _iptr(flat), _lptr(offsets), cov_t.data_ptr(), self.ld,
+                                                          state_t.data_ptr(), ws.data_ptr(), nbytes.value))
+            # (the old tensors may come from another stream: the allocator keeps them until this one has passed the call)
+            self.cov_t.record_stream(self.stream)
+            self.state_t.record_stream(self.stream)
+        self.cov_t, self.state_t = cov_t, state_t
+        for b, ids in enumerate(lists):
+            self.landmarks[b] = tables[b]
+            self.num_landmarks[b] -= len(ids)
+
     def _filter_class(self):
         from .filters.ekf_with_rotations import EKF_Rotations
         from .filters.extended_kalman_filter import EKF

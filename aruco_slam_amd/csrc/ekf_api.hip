@@ -5,6 +5,7 @@
 
 #include "ekf_host.h"
 #include "ekf_kernels.h"
+#include "ekf_remove.h"
 
 thread_local std::string g_err;
 
@@ -176,6 +177,7 @@ struct GetterShortcut {
     void state_set() { front_pending = mirror_trust = false; }
     void reset() { *this = {false, false, true, true}; }   // (state and mirror are both zero beyond what frames write)
     void new_workspace() { *this = {}; }
+    void removed() { front_pending = mirror_fresh = false; mirror_trust = true; }   // (the removal launch writes the whole new state into the mirror)
     void read_back(bool clean, bool full_state) { status_clean = clean; mirror_trust = mirror_trust || full_state; }
 };
 
@@ -230,6 +232,11 @@ struct ekf_filter {
     PinnedBuffer gate_pin;
     hipEvent_t ev_gate = nullptr;
     int64_t gate_stats[2] = {};
+    // landmark removal (ekf_remove_markers): pinned staging of the index map, two buffers used by turns as for the log
+    // replay: a call waits only for the upload of the call before the previous one
+    PinnedBuffer remove_pin[2];
+    hipEvent_t remove_done[2] = {};
+    int remove_turn = 0;
 
     bool gate_on() const { return lay.has_gate && gate < __builtin_inf(); }
     int dims() const { return lay.lmd * n_lm + EKF_CAM; }
@@ -1003,6 +1010,8 @@ int ekf_destroy(ekf_filter* f) {
     release_pipelining_token(f);
     if (f->ev_front) (void)hipEventDestroy(f->ev_front);
     if (f->ev_gate) (void)hipEventDestroy(f->ev_gate);
+    for (auto& e : f->remove_done)
+        if (e) (void)hipEventDestroy(e);
     for (auto& e : f->ev) (void)hipEventDestroy(e);
     for (int i = 0; i < kStageSlots; ++i)
         if (f->slot_done[i]) (void)hipEventDestroy(f->slot_done[i]);
@@ -1072,6 +1081,69 @@ int ekf_grow(ekf_filter* f, int32_t new_max_landmarks, int32_t new_max_visible, 
     f->ws = nws;
     restart_workspace(f);
     f->shortcut.new_workspace();
+    return EKF_OK;
+}
+
+int ekf_remove_workspace_bytes(const ekf_filter* f, int32_t count, size_t* bytes) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!bytes || count < 0) return fail(EKF_ERR_INVALID, "bad removal size request");
+    *bytes = align256((size_t)f->lay.cap * 4);      // the index map [cap], whatever the count
+    return EKF_OK;
+}
+
+// Semantics: include/ekf_slam_hip.h.  Everything is checked before anything is enqueued or rebound; then, on the handle's
+// stream: the index map (pinned staging -> remove_ws) and ONE launch: the gather into the new buffers, the fringe of the
+// second covariance buffer, the pinned mirror of the state.
+int ekf_remove_markers(ekf_filter* f, const int32_t* lm_index, int32_t count, void* cov_dev_new, int64_t ld,
+                       double* state_dev_new, void* remove_ws, size_t remove_ws_bytes) {
+    int rc = check_ready(f);
+    if (rc) return rc;
+    if (count < 0 || (count > 0 && !lm_index)) return fail(EKF_ERR_INVALID, "bad removal list");
+    const Layout& L = f->lay;
+    const size_t need = align256((size_t)L.cap * 4);
+    rc = check_device_buffers({cov_dev_new, state_dev_new, remove_ws}, need, need, "ekf_remove_workspace_bytes");
+    if (rc) return rc;
+    if (ld != L.cap) return fail(EKF_ERR_INVALID, "ld must equal the value from ekf_query_sizes");
+    if (cov_dev_new == f->cov || state_dev_new == f->state)
+        return fail(EKF_ERR_INVALID, "ekf_remove_markers needs NEW buffers (the old ones are read)");
+    if (remove_ws_bytes < need) return fail(EKF_ERR_CAPACITY, "remove_ws smaller than ekf_remove_workspace_bytes");
+    std::vector<int32_t> sorted;
+    const std::string bad = ekf_remove_build_map(lm_index, count, f->n_lm, L.lmd, L.cap, nullptr, sorted);
+    if (!bad.empty()) return fail(EKF_ERR_INVALID, bad);
+    if (count == 0) return EKF_OK;
+    const int turn = f->remove_turn;
+    PinnedBuffer& pin = f->remove_pin[turn];
+    hipEvent_t& done = f->remove_done[turn];
+    if ((rc = pin.reserve(need))) return rc;
+    if (!done) HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(done));      // (the upload of the call before the previous one: long complete in practice)
+    (void)ekf_remove_build_map(lm_index, count, f->n_lm, L.lmd, L.cap, pin.at<int32_t>(0), sorted);
+    HIP_TRY(hipMemcpyAsync(remove_ws, pin.get(), (size_t)L.cap * 4, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipEventRecord(done, f->stream));
+    f->remove_turn = turn ^ 1;
+    const int64_t n_old = f->dims(), n_new = n_old - (int64_t)L.lmd * count;
+    EkfRemoveArgs a{};
+    a.cov_src = f->cov;
+    a.cov_dst = cov_dev_new;
+    a.state_src = f->state;
+    a.state_dst = state_dev_new;
+    a.ld = L.cap;
+    a.map = static_cast<const int32_t*>(remove_ws);
+    // the whole new state also goes into the pinned mirror (what the front kernel does every frame), and the second
+    // covariance buffer of the pipelined mode, zero beyond the (rounded) state dimension and rewritten inside it by every
+    // pipelined run (ekf_set_cov), gets the rows and columns the map has just lost back to zero
+    a.state_host = f->readback.at<double>(256);
+    a.n_new = (int32_t)n_new;
+    if (L.has_cov2) {
+        a.cov2 = f->at<void>(L.off_cov2);
+        a.fringe_hi = (int32_t)std::min<int64_t>(round_up(n_old, 128), L.cap);
+    }
+    by_cov_type(f, [&](auto elem) { ekf_launch_remove<decltype(elem)>(a, 1, f->stream); });
+    HIP_TRY(hipGetLastError());
+    f->shortcut.removed();
+    f->cov = cov_dev_new;
+    f->state = state_dev_new;
+    f->n_lm -= count;
     return EKF_OK;
 }
 

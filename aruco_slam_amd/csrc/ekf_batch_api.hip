@@ -8,6 +8,7 @@
 
 #include "ekf_host.h"
 #include "ekf_kernels.h"
+#include "ekf_remove.h"
 
 struct ekf_batch {
     ekf_config cfg{};
@@ -612,6 +613,70 @@ int ekf_batch_observe_corner_replicas(ekf_batch* b, const int32_t* lm_index, con
             ekf_launch_corner_replicas(corners_dev, D, sigma_px, b->members, seed, first_replica, marker_size, cam, noisy,
                                        flipped_dev, nullptr, b->stream);
         });
+}
+
+// removal workspace: [index maps [B][ld] | landmark counts after the call [B]]
+static size_t batch_remove_counts_at(const ekf_batch* b) { return align256((size_t)b->members * b->ld * 4); }
+static size_t batch_remove_bytes(const ekf_batch* b) { return batch_remove_counts_at(b) + align256((size_t)b->members * 4); }
+
+int ekf_batch_remove_workspace_bytes(const ekf_batch* b, int64_t total, size_t* bytes) {
+    if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
+    if (!bytes || total < 0) return fail(EKF_ERR_INVALID, "bad removal size request");
+    *bytes = batch_remove_bytes(b);      // every member's index map, whatever the counts
+    return EKF_OK;
+}
+
+// Semantics: include/ekf_slam_hip.h (ekf_remove_markers, per member).  One launch of the single filter's kernel with the
+// member on blockIdx.y; it also stores the new landmark counts on the device.
+int ekf_batch_remove_markers(ekf_batch* b, const int32_t* lm_index, const int64_t* offsets, double* cov_dev_new, int64_t ld,
+                             double* state_dev_new, void* remove_ws, size_t remove_ws_bytes) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    const int32_t B = b->members;
+    if (!offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
+    if ((rc = check_offsets(offsets, B, "offsets"))) return rc;
+    const int64_t total = offsets[B];
+    if (total > 0 && !lm_index) return fail(EKF_ERR_INVALID, "bad removal list");
+    const size_t need = batch_remove_bytes(b), counts_at = batch_remove_counts_at(b);
+    if ((rc = check_device_buffers({cov_dev_new, state_dev_new, remove_ws}, need, need, "ekf_batch_remove_workspace_bytes")))
+        return rc;
+    if (ld != b->ld) return fail(EKF_ERR_INVALID, "ld must equal the value from ekf_batch_query_sizes");
+    if (cov_dev_new == b->cov || state_dev_new == b->state)
+        return fail(EKF_ERR_INVALID, "ekf_batch_remove_markers needs NEW buffers (the old ones are read)");
+    if (remove_ws_bytes < need) return fail(EKF_ERR_CAPACITY, "remove_ws smaller than ekf_batch_remove_workspace_bytes");
+    if ((rc = batch_refresh(b))) return rc;      // (landmark counts as the previous call left them; the stream is idle)
+    const int lmd = batch_lmd(b->cfg);
+    std::vector<int32_t> sorted;
+    for (int32_t m = 0; m < B; ++m) {
+        const std::string bad = ekf_remove_build_map(lm_index + offsets[m], offsets[m + 1] - offsets[m], b->nlm[m], lmd, b->ld,
+                                                     nullptr, sorted);
+        if (!bad.empty()) return fail(EKF_ERR_INVALID, bad + " (member " + std::to_string(m) + ")");
+    }
+    if (total == 0) return EKF_OK;
+    if ((rc = b->pin.reserve(need))) return rc;
+    int32_t* counts = b->pin.at<int32_t>(counts_at);
+    for (int32_t m = 0; m < B; ++m) {
+        const int64_t cnt = offsets[m + 1] - offsets[m];
+        (void)ekf_remove_build_map(lm_index + offsets[m], cnt, b->nlm[m], lmd, b->ld, b->pin.at<int32_t>(0) + (size_t)m * b->ld,
+                                   sorted);
+        counts[m] = b->nlm[m] - (int32_t)cnt;
+    }
+    char* ws = static_cast<char*>(remove_ws);
+    HIP_TRY(hipMemcpyAsync(ws, b->pin.get(), counts_at + (size_t)B * 4, hipMemcpyHostToDevice, b->stream));
+    EkfRemoveArgs a{};
+    a.cov_src = b->cov;
+    a.cov_dst = cov_dev_new;
+    a.state_src = b->state;
+    a.state_dst = state_dev_new;
+    a.ld = b->ld;
+    a.map = reinterpret_cast<const int32_t*>(ws);
+    a.nlm = reinterpret_cast<int32_t*>(b->ws + batch_layout(b->cfg, B).nlm);
+    a.nlm_new = reinterpret_cast<const int32_t*>(ws + counts_at);
+    ekf_launch_remove<double>(a, B, b->stream);
+    HIP_TRY(hipGetLastError());
+    b->cov = cov_dev_new;
+    b->state = state_dev_new;
+    return EKF_OK;
 }
 
 }  // extern "C"

@@ -111,6 +111,10 @@ def plan_detection_log(landmarks, num_landmarks, ids, offsets, has_detections=No
 class BaseFilter:
     """Front-end + abstract back-end API (names and semantics of the reference)."""
 
+    # (class-level defaults: subclasses that build themselves without this constructor prune nothing)
+    _tentative = None       # confirm=(hits, window): the TentativeLandmarks policy (_init_confirm)
+    _pruned = False         # landmarks have been removed: with none left, `state` is still the device's
+
     def __init__(self, initial_pose, map_file=None, aruco_dict=None) -> None:
         self.calib_matrix = None
         self.dist_coeffs = None
@@ -131,6 +135,19 @@ class BaseFilter:
         # Mahalanobis distance d^2 (0: a marker the frame added, NaN: not tested) and whether the gate rejected it
         self.last_mahal = None
         self.last_rejected = None
+
+    def _init_confirm(self, confirm) -> None:
+        """``confirm=(hits, window)`` of the subclass constructors, once the initial map is loaded: a landmark that is not
+        seen again in ``hits`` later frames within ``window`` frames of its first sighting is removed again
+        (``map_management.TentativeLandmarks``, fed by ``process_detections``).  None: off, nothing changes.  Landmarks the
+        filter holds already (map file) are confirmed from the start, and so are the landmarks a ``process_detection_log``
+        replay adds: the replay is one device call that the policy does not see frame by frame."""
+        if confirm is None:
+            return
+        from .map_management import TentativeLandmarks
+        hits, window = confirm
+        self._tentative = TentativeLandmarks(hits, window)
+        self._tentative.confirm(self.landmarks)
 
     def _load_initial_map(self):
         """Subclasses call this once their back-end exists (the reference calls
@@ -191,6 +208,8 @@ class BaseFilter:
             detected_poses = np.array([])
         elif should_filter:
             self.observe(ids, detected_poses)
+        if should_filter and self._tentative is not None:
+            self._prune_tentative(ids)
         if should_filter:
             camera_pose, marker_poses = self.get_poses()
         else:
@@ -209,6 +228,49 @@ class BaseFilter:
         is updated (one flipped IPPE pose otherwise bends the whole map); None or ``inf``: off.  The filter must have been
         constructed with ``gate=`` (``inf`` will do).  A bad gate raises ``ValueError`` and nothing changes."""
         self.backend.set_gate(gate)
+
+    # -- map pruning (ekf_remove_markers) ----------------------------------------------------------
+    def remove_marker(self, marker_id) -> None:
+        """``remove_markers([marker_id])``."""
+        self.remove_markers([marker_id])
+
+    def remove_markers(self, ids) -> None:
+        """Take the landmarks of these marker ids out of the map: their rows and columns of P and their state entries are
+        deleted on the device (marginalisation; nothing else changes, nothing is synchronised), the other landmarks keep
+        their order and move up (new index = old index - removed indices below it).  An unknown id raises ``KeyError``
+        and a duplicate ``ValueError`` before anything runs.  A removed id that is seen again is a first sighting: a new
+        landmark at the end, exempt from the gate like any other."""
+        ids = [int(i) for i in np.asarray(ids).reshape(-1).tolist()] if isinstance(ids, np.ndarray) else [int(i) for i in ids]
+        for marker in ids:
+            if marker not in self.landmarks:
+                raise KeyError(f"marker {marker} is not in the map")
+        if len(set(ids)) != len(ids):
+            raise ValueError("duplicate marker id in the removal list")
+        if not ids:
+            return
+        self.backend.remove_markers([self.landmarks[marker] for marker in ids])
+        self._drop_from_table(ids)
+
+    def _drop_from_table(self, ids) -> None:
+        """Host side of a removal the back-end has enqueued: the id table, the count and the policy."""
+        from .map_management import renumber_landmarks
+        self.landmarks = renumber_landmarks(self.landmarks, [self.landmarks[marker] for marker in ids])
+        self.num_landmarks -= len(ids)
+        self._pruned = True
+        if self._tentative is not None:
+            self._tentative.forget(ids)
+
+    def _prune_tentative(self, ids) -> None:
+        """End of a frame of ``process_detections`` under ``confirm=``: feed the policy the frame's ids and which of its
+        detections the gate let through, and remove what it gives up on (one ``remove_markers`` call, if any)."""
+        if ids is None:
+            stale = self._tentative.end_frame()
+        else:
+            ids = [int(i) for i in np.asarray(ids).reshape(-1).tolist()]
+            rejected = self.last_rejected if self.backend.can_gate else None
+            stale = self._tentative.end_frame(ids, None if rejected is None else ~np.asarray(rejected, dtype=bool))
+        if stale:
+            self.remove_markers(stale)
 
     @staticmethod
     def _first_occurrences(ids, fresh):
@@ -264,6 +326,8 @@ class BaseFilter:
         backend.sync()
         self.landmarks.update(plan.new_landmarks)
         self.num_landmarks = plan.num_landmarks
+        if self._tentative is not None:      # (confirm=: the policy sees per-frame calls only; what a replay adds stays)
+            self._tentative.confirm(plan.new_landmarks)
         if not mahal:
             return traj.cpu().numpy()
         d2 = np.full(plan.keep.shape[0], np.nan)
@@ -299,6 +363,8 @@ class BaseFilter:
             pose = np.array(lines[i + 1].strip().split(", "), np.float64)
             uncertainty = np.array(lines[i + 2].strip().split(", "), np.float64)
             self.add_marker(id_, pose, uncertainty)
+        if self._tentative is not None:      # landmarks restored from a map file are confirmed from the start
+            self._tentative.confirm(self.landmarks)
 
     def reset(self) -> None:
         """Back to the state of a freshly constructed filter (initial pose, no landmarks, status cleared): the way out
@@ -307,6 +373,9 @@ class BaseFilter:
         self.backend.reset(np.asarray(self._initial_pose, dtype=np.float64))
         self.landmarks = {}
         self.num_landmarks = 0
+        self._pruned = False
+        if self._tentative is not None:
+            self._tentative.clear()
 
     # -- resume (no reference counterpart: its map restore is the dead :249-272) -----
     def save_checkpoint(self, filename: str) -> None:
@@ -337,6 +406,9 @@ class BaseFilter:
         self.backend.set_state_cov(state, cov)
         self.landmarks = {int(k): i for i, k in enumerate(ids)}
         self.num_landmarks = len(ids)
+        if self._tentative is not None:      # a checkpoint's landmarks are confirmed, like a map file's
+            self._tentative.forget(list(self._tentative.tentative))
+            self._tentative.confirm(self.landmarks)
 
     # -- abstract back-end API, base_filter.py:327-381 ------------------------
     def observe(self, ids, poses) -> None:

@@ -46,12 +46,14 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
     def __init__(self, initial_camera_pose, *, max_landmarks: int | None = None, max_visible: int | None = None,
                  cov_dtype: str = "float64", cov_kernel: str = "auto", device: str = "cuda:0",
                  lookahead: bool | None = None, fused: bool = True, noise: dict | None = None,
-                 gate: float | None = None) -> None:
+                 gate: float | None = None, confirm: tuple | None = None) -> None:
         """``noise``: values that replace the module's noise constants, keyed by the ``ekf_config`` field names
         (``initial_camera_uncertainty``, ``initial_landmark_uncertainty``, ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``);
         None keeps the reference's constants.  ``gate``: the chi-square gate on every detection's own Mahalanobis
         distance (``set_gate``; 7 degrees of freedom, approximate: 14.067 / 18.475 / 24.322 for 95 / 99 / 99.9 %);
-        ``inf``: off, but the distances are reported (``last_mahal``); None: a filter without the gate."""
+        ``inf``: off, but the distances are reported (``last_mahal``); None: a filter without the gate.
+        ``confirm``: ``(hits, window)`` = a new landmark must be used again in ``hits`` later frames within ``window``
+        frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off."""
         super().__init__(initial_camera_pose, None)
         self._initial_pose = np.array(initial_camera_pose)
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -74,10 +76,11 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
                            cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
                            model="ekf_rotations", noise=constants, gate=gate)
         self._hip.reset(self._initial_pose.astype(np.float64))
+        self._init_confirm(confirm)
 
     @property
     def state(self) -> np.ndarray:
-        if self.num_landmarks == 0:
+        if self.num_landmarks == 0 and not self._pruned:
             return self._initial_pose
         return self._hip.get_state()
 

@@ -36,7 +36,7 @@ class EKF(BaseFilter):
                  max_visible: int | None = None, cov_dtype: str = "float64",
                  quat_update: str = "as_written", cov_kernel: str = "auto",
                  device: str = "cuda:0", map_file=None, lookahead: bool | None = None,
-                 fused: bool = True, noise: dict | None = None, gate: float | None = None) -> None:
+                 fused: bool = True, noise: dict | None = None, gate: float | None = None, confirm: tuple | None = None) -> None:
         """Positional arguments as the reference (:40-43).  Keyword-only extras:
         initial capacity (default: the number of ids of ``aruco_dict`` -- DICT_5X5_50
         has 50, base_filter.py:81-82; the buffers grow when more markers or more
@@ -48,7 +48,9 @@ class EKF(BaseFilter):
         ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``); None keeps the reference's constants.
         ``gate``: the chi-square gate on every detection's own Mahalanobis distance (``set_gate``; 3 degrees of
         freedom: 7.815 / 11.345 / 16.266 for 95 / 99 / 99.9 %); ``inf``: off, but the distances are reported
-        (``last_mahal``); None: a filter without the gate."""
+        (``last_mahal``); None: a filter without the gate.
+        ``confirm``: ``(hits, window)`` = a new landmark must be used again in ``hits`` later frames within ``window``
+        frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off."""
         super().__init__(initial_camera_pose, map_file, aruco_dict)
         self._initial_pose = np.array(initial_camera_pose)      # :46, dtype kept
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -72,11 +74,12 @@ class EKF(BaseFilter):
                            noise=constants, gate=gate)
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._load_initial_map()
+        self._init_confirm(confirm)
 
     # -- attributes the base class / callers read (base_filter.py:293-304) ---
     @property
     def state(self) -> np.ndarray:
-        if self.num_landmarks == 0:
+        if self.num_landmarks == 0 and not self._pruned:
             # the reference keeps the caller's (int64) array until the first
             # hstack (:46, :274): D7 in SURVEY appendix A
             return self._initial_pose

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "ekf_batch_set_gate", "ekf_batch_observe_logs_gated", "ekf_batch_observe_replicas_gated",
     "ekf_batch_replica_corners", "ekf_batch_observe_corner_replicas",
     "ekf_set_gate", "ekf_observe_gated", "ekf_observe_log_gated", "ekf_last_gate_stats",
+    "ekf_remove_workspace_bytes", "ekf_remove_markers", "ekf_batch_remove_workspace_bytes", "ekf_batch_remove_markers",
 )
 
 
@@ -115,6 +116,10 @@ def load_library(path: str | Path | None = None):
         "ekf_observe_gated": [vp, ip, dp, C.c_int32, C.POINTER(C.c_uint8), dp, ip],
         "ekf_observe_log_gated": [vp, ip, C.POINTER(C.c_int64), C.c_int32, vp, vp, C.c_size_t, vp, vp],
         "ekf_last_gate_stats": [vp, C.POINTER(C.c_int64)],
+        "ekf_remove_workspace_bytes": [vp, C.c_int32, C.POINTER(C.c_size_t)],
+        "ekf_remove_markers": [vp, ip, C.c_int32, vp, C.c_int64, vp, vp, C.c_size_t],
+        "ekf_batch_remove_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],
+        "ekf_batch_remove_markers": [vp, ip, C.POINTER(C.c_int64), vp, C.c_int64, vp, vp, C.c_size_t],
         "ekf_batch_query_sizes": [C.POINTER(EkfConfig), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_size_t),
                                   C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
         "ekf_batch_create": [C.POINTER(EkfConfig), C.c_int32, C.POINTER(vp)],
@@ -332,6 +337,39 @@ class HipEkf:
         self.cov_t, self.state_t, self.ws_t, self.ld = cov_t, state_t, ws_t, ld.value
         self.cfg = ncfg
         self.max_landmarks, self.max_visible = int(new_max_landmarks), int(new_max_visible)
+
+    def remove_markers(self, indices):
+        """Delete the landmarks with these indices (distinct, any order) from state and covariance on the device
+        (ekf_remove_markers): new tensors of the filter's own sizes, allocated on the filter's stream, receive the kept
+        rows and columns, the library borrows them, and ``cov_t`` / ``state_t`` are swapped.  Kept landmarks keep their
+        order: new index = old index - (removed indices below it).  Nothing is synchronised."""
+        torch = self._torch
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            cov_t, state_t = torch.empty_like(self.cov_t), torch.empty_like(self.state_t)
+        self._remove_into(indices, cov_t, state_t)
+
+    def _remove_into(self, indices, cov_t, state_t):
+        """``remove_markers`` into tensors of the caller (shapes and dtypes of ``cov_t`` / ``state_t``), which the filter
+        keeps; an empty list leaves them unwritten and unused."""
+        torch = self._torch
+        idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        assert cov_t.shape == self.cov_t.shape and cov_t.dtype == self.cov_t.dtype and cov_t.is_contiguous()
+        assert state_t.shape == self.state_t.shape and state_t.dtype == self.state_t.dtype
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_remove_workspace_bytes(self.h, idx.shape[0], C.byref(nbytes)))
+        # (the new tensors may have been filled on the caller's current stream)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
+            self._check(self.lib.ekf_remove_markers(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.shape[0],
+                                                    cov_t.data_ptr(), self.ld, state_t.data_ptr(), ws.data_ptr(),
+                                                    nbytes.value))
+            if idx.shape[0] == 0:
+                return
+            # (old and new tensors may come from another stream: the allocator keeps them until this one has passed the call)
+            for t in (cov_t, state_t, self.cov_t, self.state_t):
+                t.record_stream(self.stream)
+        self.cov_t, self.state_t = cov_t, state_t
 
     def add_markers(self, xyz, uncertainty=None):
         xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 6 if self.lm_dims == 10 else 3)

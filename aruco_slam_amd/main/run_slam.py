@@ -76,6 +76,10 @@ def main(cmdline_args: argparse.Namespace) -> None:
     kwargs = dict(getattr(cmdline_args, "filter_kwargs", {}))
     if getattr(cmdline_args, "gate", None) is not None:
         kwargs["gate"] = cmdline_args.gate      # (acts in the frame loop and in the resident replay alike)
+    if getattr(cmdline_args, "confirm", None) is not None:
+        if getattr(cmdline_args, "resident", False):
+            raise ValueError("--confirm prunes between frames: it does not go with --resident (one device call for the log)")
+        kwargs["confirm"] = cmdline_args.confirm      # (with or without --gate)
     tracker = init_tracker(cmdline_args.filter, initial_pose, **kwargs)
     out_dir = Path(getattr(cmdline_args, "output_dir", "outputs"))
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -107,6 +111,15 @@ def main(cmdline_args: argparse.Namespace) -> None:
     tracker.save_map(str(out_dir / "map.txt"))
 
 
+def confirm_pair(text: str):
+    """``H,W`` of ``--confirm`` as a pair of integers."""
+    try:
+        hits, window = (int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--confirm takes H,W (two integers), got {text!r}") from None
+    return hits, window
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="Run the SLAM system")
     parser.add_argument("--video", type=str, help="Path to video file", default="input_video.mp4")
@@ -120,6 +133,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="chi-square gate on every detection's own squared Mahalanobis distance: detections beyond "
                              "it are left out of their frame (ekf: 3 degrees of freedom, 11.345 = 99 %%; ekf_rotations: 7, "
                              "18.475)")
+    parser.add_argument("--confirm", type=confirm_pair, default=None, metavar="H,W",
+                        help="a new landmark must be used again in H later frames within W frames of its first sighting, "
+                             "or it is removed from the map again (default: off)")
     return parser
 
 

@@ -503,6 +503,45 @@ int ekf_observe_log_gated(ekf_filter *f, const int32_t *lm_index, const int64_t 
                           double *mahal_dev /* [D] or NULL */);
 int ekf_last_gate_stats(const ekf_filter *f, int64_t out[2]);
 
+/* ---- Landmark removal (map pruning).  Deleting landmarks from a Gaussian is marginalisation: their rows and columns of P
+ * and their entries of the state go, nothing else changes.  The calling pattern is that of ekf_grow at unchanged capacity:
+ * the caller hands in a second covariance and a second state buffer of the sizes ekf_query_sizes gives for the filter's own
+ * configuration (which are what they were), the library gathers what is kept into them on the handle's stream (one launch)
+ * and borrows them from then on; the old ones may be freed once the stream has passed the call.  remove_ws: caller-owned
+ * device scratch for the index map, 256-byte aligned, ekf_remove_workspace_bytes(count); valid until the stream has passed
+ * the call.
+ * Semantics (part of the ABI):
+ *   1. lm_index [count] HOST holds distinct indices in [0, num_landmarks), in any order.  A duplicate, an index out of
+ *      range, a negative count, a NULL or misaligned buffer, a new buffer that is the current one, or a wrong ld returns
+ *      EKF_ERR_INVALID; a remove_ws smaller than ekf_remove_workspace_bytes returns EKF_ERR_CAPACITY; both before anything
+ *      is enqueued: the filter, its buffers and its bindings are untouched.  count == 0 returns EKF_OK and does nothing: no
+ *      rebinding, the new buffers are not written.
+ *   2. Kept landmarks keep their relative order: new index = old index - (number of removed indices below it);
+ *      num_landmarks drops by count.  Removing every landmark leaves the camera block (state[0:10], P[0:10, 0:10]).
+ *   3. The whole new covariance buffer [ld, ld] and the whole new state buffer are written: the kept N' x N' block and N'
+ *      state entries (N' = lmd (n - count) + 10) are bit for bit the old values, everything else is exactly zero (the
+ *      capacity padding every update kernel relies on).  The result is bit for bit the filter ekf_set_state + ekf_set_cov
+ *      build from the host arrays with those rows and columns deleted (P is bitwise symmetric, so the upload's
+ *      (P + P^T) / 2 is the identity on it), either model, either covariance dtype, and every later call of any kind
+ *      continues bit for bit as on that twin.
+ *   4. Pure data movement, enqueued on the handle's stream.  The call does not wait for the device's work: the only host
+ *      wait it can make is for its own staging, the index map goes through two pinned buffers used by turns, so a call
+ *      waits for the upload of the removal before the previous one and for nothing else.  The sticky status word, the gate,
+ *      the noise constants and the sequence-mode state stay as they are; NaNs of a failed filter move like any other value.
+ *      The pinned host mirror of the state is refreshed by the launch, so a getter after the call returns the new state.
+ * ekf_batch_remove_markers: the same per member, ragged like the log calls: member b removes
+ * lm_index[offsets[b] : offsets[b + 1]] (offsets [B+1] HOST, offsets[0] = 0, non-decreasing), checked against the landmark
+ * counts the library reads back from the device first (this call waits for the batch's stream, as every batch call does).
+ * Members with an empty list are copied unchanged; no list at all (offsets[B] == 0) does nothing.  cov_dev_new [B, ld, ld],
+ * state_dev_new [B, ld] as ekf_batch_query_sizes sizes them; the launch also stores the new landmark counts on the device;
+ * a member's status stays.  One-column, large-map and wide-frame batches alike. */
+int ekf_remove_workspace_bytes(const ekf_filter *f, int32_t count, size_t *bytes);
+int ekf_remove_markers(ekf_filter *f, const int32_t *lm_index /* [count] HOST */, int32_t count, void *cov_dev_new, int64_t ld,
+                       double *state_dev_new, void *remove_ws, size_t remove_ws_bytes);
+int ekf_batch_remove_workspace_bytes(const ekf_batch *b, int64_t total, size_t *bytes);
+int ekf_batch_remove_markers(ekf_batch *b, const int32_t *lm_index /* [total] HOST */, const int64_t *offsets /* [B+1] HOST */,
+                             double *cov_dev_new, int64_t ld, double *state_dev_new, void *remove_ws, size_t remove_ws_bytes);
+
 const char *ekf_last_error_string(void);
 
 #ifdef __cplusplus

@@ -15,9 +15,16 @@
 //      value gamma, and the two rotations whose upper-left 2x2 block is A / gamma;
 //   4. for either rotation the translation by linear least squares over the four corners;
 //   5. the solution with the smaller reprojection error (normalised image plane) is returned as [tvec | rvec],
-//      rvec = axis * angle of the rotation.
+//      rvec = axis * angle of the rotation, through its unit quaternion (largest of trace, R00, R11, R22; angle =
+//      2 atan2(|v|, w)): exact to rounding for every angle in [0, pi].  A marker that faces a level camera is a rotation
+//      by pi or close to it; cv::Rodrigues switches formulas inside |sin| < 1e-5 and is off by up to about 2e-5 rad there,
+//      so a cv2 run differs by that much inside cv's own window.
+// A degenerate detection (the pixel corners are not those of a strictly convex quadrilateral, or a coordinate is NaN or
+// Inf) gets six NaN (ippe_corners_valid, ippe_square_pose in ekf_ippe_device.h).
 // No fixture of the reference pins these numbers ("parity unpinned"): tests compare the kernel with a NumPy
-// restatement of the same steps (oracle/ippe_numpy.py) and with the poses the corners were projected from.
+// restatement of the same steps (oracle/ippe_numpy.py), with the poses the corners were projected from, and over a table
+// of edge geometries with an extended-precision restatement under a conditioned bound (oracle/ippe_extended.py,
+// tests/pose_sweep_util.py).
 // One KNOWN structural difference to the reference's call: base_filter.py passes float32 corners and object points, and
 // cv::undistortPoints returns CV_32F for float32 input, so OpenCV's normalised points are rounded to f32 before IPPE;
 // this kernel stays in f64 throughout.  Expect ~1e-7 relative differences in tvec / rvec against a cv2 run (the

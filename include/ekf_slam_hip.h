@@ -266,6 +266,13 @@ int ekf_debug_fetch(ekf_filter *f, int32_t what, double *out, size_t count);
  * bottom-right, bottom-left = object points (-s/2, s/2), (s/2, s/2), (s/2, -s/2), (-s/2, -s/2), base_filter.py:113-121);
  * camera_matrix: row-major 3x3 (fx, cx, fy, cy are read); dist_coeffs: n_dist <= 8 values k1 k2 p1 p2 k3 k4 k5 k6;
  * poses [count,6] = [tvec | rvec] per marker, the layout observe() takes (base_filter.py:166-171).
+ * rvec = axis * angle, through the unit quaternion of the rotation: exact to rounding for every angle in [0, pi], the
+ * angle pi of a marker that faces a level camera included (cv::Rodrigues has a window |sin| < 1e-5 there: a cv2 run differs
+ * by up to about 2e-5 rad inside it).
+ * A degenerate detection -- the four pixel corners are not those of a strictly convex quadrilateral (collinear,
+ * coincident, a consecutive triple spanning less than 1e-9 of the squared side lengths), or a coordinate is NaN or Inf --
+ * gets six NaN: a pose is valid exactly if all six values are finite.  The call still returns EKF_OK and no other marker of
+ * the batch is affected.  count = 0 does nothing.
  * The `_device` form enqueues one kernel on `stream` (device pointers); the host form copies, runs and synchronises. */
 int ekf_estimate_poses_device(const double *corners_dev, int32_t count, double marker_size,
                               const double camera_matrix[9], const double *dist_coeffs, int32_t n_dist,

@@ -239,6 +239,7 @@ struct ekf_filter {
     int remove_turn = 0;
 
     bool gate_on() const { return lay.has_gate && gate < __builtin_inf(); }
+    void reset_gate_stats() { gate_stats[0] = gate_stats[1] = 0; }      // every observe call counts from zero
     int dims() const { return lay.lmd * n_lm + EKF_CAM; }
     template <typename P> P* at(size_t off) const { return reinterpret_cast<P*>(ws + off); }
 };
@@ -874,6 +875,14 @@ int repeat_row(ekf_filter* f, double* traj_row) {
     return EKF_OK;
 }
 
+// A gated frame of a sequence or of a log (device arrays, no host mirror): the frame on its survivors, or, with none left,
+// its trajectory row alone
+int gated_frame_or_row(ekf_filter* f, const int32_t* idx, const double* z, int m, const uint8_t* exempt, int n_exempt,
+                       double* mahal_dev, double* traj_row, int* survivors) {
+    const int rc = gated_frame(f, idx, z, m, exempt, n_exempt, mahal_dev, nullptr, traj_row, false, survivors);
+    return rc == EKF_OK && *survivors == 0 ? repeat_row(f, traj_row) : rc;
+}
+
 // ekf_observe / ekf_observe_gated: the frame's detections (host) through a slot of the pinned staging ring
 int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, int32_t m, bool gated, const uint8_t* exempt,
                  double* mahal, int32_t* survivors) {
@@ -1218,7 +1227,7 @@ int ekf_add_markers(ekf_filter* f, const double* cam_frame_xyz, const double* di
 int ekf_observe(ekf_filter* f, const int32_t* lm_index, const double* z, int32_t m) {
     int rc = check_ready(f);
     if (rc) return rc;
-    f->gate_stats[0] = f->gate_stats[1] = 0;
+    f->reset_gate_stats();
     return observe_host(f, lm_index, z, m, f->gate_on(), nullptr, nullptr, nullptr);
 }
 
@@ -1227,7 +1236,7 @@ int ekf_observe_gated(ekf_filter* f, const int32_t* lm_index, const double* z, i
     int rc = check_ready(f);
     if (rc) return rc;
     if (!f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
-    f->gate_stats[0] = f->gate_stats[1] = 0;
+    f->reset_gate_stats();
     const bool gated = f->gate_on() || mahal;
     rc = observe_host(f, lm_index, z, m, gated, exempt, mahal, survivors);
     if (rc == EKF_OK && !gated && survivors) *survivors = m;
@@ -1258,7 +1267,7 @@ int ekf_observe_device(ekf_filter* f, const int32_t* lm_index_dev, const double*
     if (!lm_index_dev || !z_dev) return fail(EKF_ERR_INVALID, "NULL detections");
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
     // the indices are device-resident: range-checked by the kernels (EKF_ERR_INVALID at the next sync)
-    f->gate_stats[0] = f->gate_stats[1] = 0;
+    f->reset_gate_stats();
     if (f->gate_on()) return gated_frame(f, lm_index_dev, z_dev, m, nullptr, 0, nullptr, nullptr, nullptr, true, nullptr);
     return enqueue_frame(f, lm_index_dev, z_dev, m, nullptr, true);
 }
@@ -1272,18 +1281,16 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
     if (!lm_index_dev || !z_dev) return fail(EKF_ERR_INVALID, "NULL detections");
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
     const int rd = f->lay.rd;
-    f->gate_stats[0] = f->gate_stats[1] = 0;
+    f->reset_gate_stats();
     if (f->gate_on()) {
         // a gate is set: frame by frame in serial order, each frame on its survivors (gating inside a pipelined run would
         // need the mask inside the front kernel)
         f->seq_mode = EKF_SEQ_SERIAL;
         f->shortcut.log();      // (a getter after the call waits for all of it)
         for (int t = 0; t < frames; ++t) {
-            double* row = trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr;
             int s = 0;
-            rc = gated_frame(f, lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd, m, nullptr, 0, nullptr, nullptr, row,
-                             false, &s);
-            if (rc == EKF_OK && s == 0) rc = repeat_row(f, row);
+            rc = gated_frame_or_row(f, lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd, m, nullptr, 0, nullptr,
+                                    trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr, &s);
             if (rc) return rc;
         }
         f->shortcut.log();
@@ -1367,7 +1374,7 @@ int ekf_observe_log_gated(ekf_filter* f, const int32_t* lm_index, const int64_t*
     LogCheck lc;
     if ((rc = check_log(lm_index, offsets, frames, f->n_lm, f->cfg, "the log", &lc))) return rc;
     for (int i = 0; i < 4; ++i) f->log_stats[i] = 0;
-    f->gate_stats[0] = f->gate_stats[1] = 0;
+    f->reset_gate_stats();
     if (frames == 0) return EKF_OK;
 
     // ---- host staging: [indices | slots | (row, source) pairs of empty frames: those before the first stepped frame of the
@@ -1446,17 +1453,18 @@ int ekf_observe_log_gated(ekf_filter* f, const int32_t* lm_index, const int64_t*
         // without a survivor is not stepped, and its row repeats the camera state
         for (int t = 0; t < frames && rc == EKF_OK; ++t) {
             const RunFrame r = frame_of(t);
-            int s = 0;
-            if (r.m > 0) {
-                const int nnew = first_sightings(t);
-                f->n_lm += nnew;
-                f->log_stats[3] += nnew;
-                const int64_t d0 = offsets[t];
-                rc = gated_frame(f, r.idx, r.z, r.m, pin_exempt + d0, nnew, mahal_dev ? mahal_dev + d0 : nullptr, nullptr,
-                                 r.traj_row, false, &s);
-                if (rc == EKF_OK && s > 0) f->log_stats[0] += 1;
+            if (r.m == 0) {
+                rc = repeat_row(f, r.traj_row);
+                continue;
             }
-            if (rc == EKF_OK && s == 0) rc = repeat_row(f, r.traj_row);
+            const int nnew = first_sightings(t);
+            f->n_lm += nnew;
+            f->log_stats[3] += nnew;
+            const int64_t d0 = offsets[t];
+            int s = 0;
+            rc = gated_frame_or_row(f, r.idx, r.z, r.m, pin_exempt + d0, nnew, mahal_dev ? mahal_dev + d0 : nullptr, r.traj_row,
+                                    &s);
+            if (rc == EKF_OK && s > 0) f->log_stats[0] += 1;
         }
     } else {
         rc = run_frames(f, frames, frame_of, first_sightings, plan, mode == EKF_SEQ_PIPELINED, f->log_stats);

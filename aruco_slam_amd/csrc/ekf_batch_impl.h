@@ -9,7 +9,7 @@
 // MODEL 1 (EKF_Rotations): RD = 7, LMD = 10, JC = 20 (ekf_batch_rot.hip).  Each model is instantiated in its own file.
 // P of a member is read and written by its own workgroup only: workgroup barriers are the only ordering.
 #pragma once
-#include "ekf_kernels.h"
+#include "ekf_gate_device.h"
 #include "ekf_markers.h"
 
 template <int MODEL> struct EkfBatchCaps;
@@ -57,115 +57,44 @@ __device__ __forceinline__ void ekf_batch_mahal_untested(const EkfBatchWindow& a
 // Individual-compatibility gate of one frame (include/ekf_slam_hip.h, ekf_batch_set_gate), the ONE place every window kernel
 // takes its per-detection distances from.  Called by the whole workgroup behind the barrier that follows the frame's first
 // sightings, before anything else of the frame; n0 is the landmark count the previous frame left, N the state dimension
-// with the first sightings.  For detection d (thread d, m <= 64: wave 0):
-//   r_d = z_d - h_d(x), S_d = H_d (P+Q) H_d^T + R I [RD, RD] from the (10 + LMD)^2 support block of P,
-//   S_d = L_d L_d^T and d^2 = |L_d^-1 r_d|^2, every sum one ascending fma chain.
+// with the first sightings.  Detection d (thread d, m <= 64: wave 0) gets the d^2 of ekf_gate_device.h on the prior P: the
+// three stages the single filter's gate kernel (ekf_gate.hip) runs as well.
 // The first occurrence of a landmark first sighted in this frame is exempt (d^2 = 0, kept); a failed pivot keeps the
 // detection and reports NaN; otherwise the detection is rejected iff d^2 > gate[b].  Returns the 64-bit mask of the
 // detections that stay (bit d), shared through `words` (two spare ints of LDS).
-// `scr` is LDS nothing else uses yet: per detection J [RD][JC] | T = H_d (P+Q)[:, supp] [RD][JC] | S_d [RD][RD] | r_d [RD],
-// DOUBLES = 90 (EKF) / 336 (EKF_Rotations) per detection from the base of the dynamic LDS.  It fits every launch the host
-// makes (kmax >= RD w for the widest frame w, lda >= 10 + LMD + 1):
-//   one-column (A | L | dinv | J): EKF 90 w <= 42 w + 9 w^2 + 3 w + 39 w, rotations 336 w <= 147 w + 49 w^2 + 7 w + 140 w;
-//   large maps (R alone): DOUBLES w <= 256 RD w;  wide frames: the same up to a full block, beyond it the static_assert
+// `scr` is LDS nothing else uses yet: G = EkfGateScratch<MODEL>::DOUBLES (90 EKF / 336 EKF_Rotations) doubles per detection
+// from the base of the dynamic LDS.  G w fits every launch the host makes for a widest frame of w detections
+// (kmax >= RD w, lda >= 10 + LMD + 1, so A | L | dinv | J hold at least RD w (11 + LMD) + (RD w)^2 + RD w + RD w JC):
+//   one-column: EKF 90 w <= 42 w + 9 w^2 + 3 w + 39 w, rotations 336 w <= 147 w + 49 w^2 + 7 w + 140 w;
+//   large maps (R alone): G w <= 256 RD w;  wide frames: the same up to a full block, beyond it the static_assert
 //   of ekf_batch_wide.hip on the widest frame the kernel admits.
-template <int MODEL> struct EkfBatchGate {
-    static constexpr int RD = EkfModel<MODEL>::RD, JC = EkfModel<MODEL>::JC;
-    static constexpr int DOUBLES = 2 * RD * JC + RD * RD + RD;      // scratch per detection
-};
-
 template <int MODEL>
 __device__ __forceinline__ uint64_t ekf_batch_gate(const EkfBatchWindow& a, int b, int64_t d0, int m, int n0, int N, int tid,
                                                    int nt, const double* st, const double* P, int64_t ld,
                                                    const EkfNoise& nz, double* scr, int* words) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
-    constexpr int SCR = EkfBatchGate<MODEL>::DOUBLES;
+    constexpr int SCR = EkfGateScratch<MODEL>::DOUBLES;
     const int32_t* idx = a.lm_index + d0;
     const double* pose = a.poses + 6 * d0;
     // h, dh and r = z - h of every detection (the exempt ones included: the wave does not diverge)
     if (tid < m) {
-        double* Jd = scr + (size_t)tid * SCR;
-        double* rd = Jd + 2 * RD * JC + RD * RD;
-        const int c0 = EKF_CAM + LMD * idx[tid];
-        double cam[EKF_CAM], lm[LMD], h[RD], z[RD];
-        for (int q = 0; q < EKF_CAM; ++q) cam[q] = st[q];
-        for (int q = 0; q < LMD; ++q) lm[q] = st[c0 + q];
-        if constexpr (MODEL == 0) {
-            double Jt[3][EKF_JCOLS];
-            ekf_measure(cam, lm, h, Jt);
-            for (int r = 0; r < 3; ++r)
-                for (int s = 0; s < EKF_JCOLS; ++s) Jd[r * EKF_JCOLS + s] = Jt[r][s];
+        double z[RD];
+        if constexpr (MODEL == 0)
             for (int r = 0; r < 3; ++r) z[r] = pose[6 * tid + r];
-        } else {
-            ekf_measure_rot(cam, lm, h, reinterpret_cast<double(*)[JC]>(Jd));
+        else
             ekf_pose_z(pose + 6 * tid, RD, z);
-        }
-        for (int r = 0; r < RD; ++r) rd[r] = z[r] - h[r];
+        ekf_gate_measure<MODEL>(st, EKF_CAM + LMD * idx[tid], z, scr + (size_t)tid * SCR);
     }
     __syncthreads();
-    // T[:, ci] = H_d (P+Q)[supp, supp[ci]]: one thread per (detection, support column), the column's loads in one round
     for (int task = tid; task < m * JC; task += nt) {
-        const int d = task / JC, ci = task - d * JC;
-        const int c0 = EKF_CAM + LMD * idx[d];
-        const int c = ci < EKF_CAM ? ci : c0 + ci - EKF_CAM;
-        const double* Jd = scr + (size_t)d * SCR;
-        double pc[JC];
-#pragma unroll
-        for (int si = 0; si < JC; ++si) {
-            const int s = si < EKF_CAM ? si : c0 + si - EKF_CAM;
-            pc[si] = P[(int64_t)s * ld + c] + (si == ci ? ekf_qdiag(c, N, nz) : 0.0);
-        }
-#pragma unroll 1
-        for (int r = 0; r < RD; ++r) {      // (not unrolled, here and below: the stage stays small in registers and code)
-            double acc = 0.0;
-#pragma unroll
-            for (int si = 0; si < JC; ++si) acc = fma(Jd[r * JC + si], pc[si], acc);
-            scr[(size_t)d * SCR + RD * JC + r * JC + ci] = acc;
-        }
+        const int d = task / JC;
+        ekf_gate_project<MODEL>(P, ld, EKF_CAM + LMD * idx[d], task - d * JC, N, nz, scr + (size_t)d * SCR);
     }
     __syncthreads();
     bool keep = false;
     if (tid < m) {
-        const double* Jd = scr + (size_t)tid * SCR;
-        const double* Td = Jd + RD * JC;
-        double* Sd = scr + (size_t)tid * SCR + 2 * RD * JC;
-        double* rd = Sd + RD * RD;
-        // S_d = T H_d^T + R I, lower triangle
-#pragma unroll 1
-        for (int r = 0; r < RD; ++r)
-#pragma unroll 1
-            for (int rr = 0; rr <= r; ++rr) {
-                double acc = 0.0;
-#pragma unroll 4
-                for (int ci = 0; ci < JC; ++ci) acc = fma(Td[r * JC + ci], Jd[rr * JC + ci], acc);
-                Sd[r * RD + rr] = acc + (r == rr ? nz.r_unc : 0.0);
-            }
-        // S_d = L L^T row by row (L_ii on the diagonal) with y = L^-1 r behind each row; d^2 = y^T y
-        bool ok = true;
-        double d2 = 0.0;
-#pragma unroll 1
-        for (int i = 0; i < RD && ok; ++i) {
-            double* Li = Sd + i * RD;
-#pragma unroll 1
-            for (int j = 0; j < i; ++j) {
-                const double* Lj = Sd + j * RD;
-                double v = Li[j];
-                for (int l = 0; l < j; ++l) v = fma(-Li[l], Lj[l], v);
-                Li[j] = v / Lj[j];
-            }
-            double dii = Li[i], y = rd[i];
-            for (int l = 0; l < i; ++l) {
-                dii = fma(-Li[l], Li[l], dii);
-                y = fma(-Li[l], rd[l], y);
-            }
-            ok = dii > 0.0 && isfinite(dii);
-            if (ok) {
-                Li[i] = sqrt(dii);
-                y = y / Li[i];
-                rd[i] = y;
-                d2 = fma(y, y, d2);
-            }
-        }
+        double d2;
+        const bool ok = ekf_gate_distance<MODEL>(nz.r_unc, scr + (size_t)tid * SCR, d2);
         bool exempt = idx[tid] >= n0;
         for (int e = 0; e < tid; ++e) exempt = exempt && idx[e] != idx[tid];
         const double out = exempt ? 0.0 : ok ? d2 : __builtin_nan("");

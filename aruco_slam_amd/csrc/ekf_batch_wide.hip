@@ -57,7 +57,7 @@ template <int MODEL> size_t wide_lds_bytes_of(int kmax) {
 // R | L | dinv | J of a KW-row block and y of at least KW rows
 template <int MODEL> constexpr bool wide_gate_fits() {
     constexpr int KW = wide_kw<MODEL>();
-    return EkfBatchGate<MODEL>::DOUBLES * WideCaps<MODEL>::MAX_VISIBLE <=
+    return EkfGateScratch<MODEL>::DOUBLES * WideCaps<MODEL>::MAX_VISIBLE <=
            kWideThreads * KW + KW * KW + KW + KW * EkfModel<MODEL>::JC + KW;
 }
 static_assert(wide_gate_fits<0>() && wide_gate_fits<1>(), "the gate's scratch must fit the wide kernels' LDS");

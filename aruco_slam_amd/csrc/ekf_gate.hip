@@ -1,9 +1,7 @@
 // Per-detection chi-square gate of the single filter (include/ekf_slam_hip.h: ekf_set_gate, ekf_observe_gated,
 // ekf_observe_log_gated): ONE launch per frame on the handle's stream, in front of everything else of the frame.
-// For detection d of the frame, on the prior P the previous frame left (first sightings added):
-//   r_d = z_d - h_d(x), S_d = H_d (P+Q) H_d^T + R I [RD, RD] from the (10 + LMD)^2 support block of P,
-//   S_d = L_d L_d^T and d^2 = |L_d^-1 r_d|^2, every sum one ascending fma chain, all of it in f64 (an f32 P is widened on
-//   load): the stages of ekf_batch_gate (ekf_batch_impl.h), operation for operation.
+// For detection d of the frame, on the prior P the previous frame left (first sightings added), d^2 is the distance of
+// ekf_gate_device.h: the three stages the batch runs as well, so filter and batch test a detection with the same code.
 // An exempt detection reports d^2 = 0 and stays; a failed pivot keeps the detection and reports NaN; otherwise the detection
 // is rejected iff d^2 > gate.  The survivors' indices and z go, in log order, into the workspace scratch the frame's own
 // kernels then read; their number and "some pivot failed" go into a pinned host mirror.
@@ -11,27 +9,22 @@
 // popcount prefix compact it; the running base makes the order stable across chunks).  A detection's arithmetic is one
 // thread's (stages 1 and 3) or one thread's per support column (stage 2) and touches nothing of the other detections: the
 // result depends neither on the chunk a detection falls into nor on m.
-#include "ekf_kernels.h"
+#include "ekf_gate_device.h"
 
 template <int MODEL> struct EkfGateShape;
-// static LDS: CHUNK * DOUBLES * 8 bytes = 46080 (EKF), 43008 (EKF_Rotations)
+// static LDS: CHUNK * EkfGateScratch<MODEL>::DOUBLES * 8 bytes = 46080 (EKF), 43008 (EKF_Rotations)
 template <> struct EkfGateShape<0> { static constexpr int CHUNK = 64; };
 template <> struct EkfGateShape<1> { static constexpr int CHUNK = 16; };
 
 template <typename T, int MODEL>
 __global__ __launch_bounds__(EKF_GATE_THREADS) void ekf_frame_gate_kernel(const EkfGateArgs a) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
-    constexpr int CHUNK = EkfGateShape<MODEL>::CHUNK;
-    // per detection: J [RD][JC] | T = H_d (P+Q)[:, supp] [RD][JC] | S_d [RD][RD] | r_d [RD]
-    constexpr int SCR = 2 * RD * JC + RD * RD + RD;
+    constexpr int CHUNK = EkfGateShape<MODEL>::CHUNK, SCR = EkfGateScratch<MODEL>::DOUBLES;
     static_assert(CHUNK <= 64, "one wave holds the decisions of a chunk");
     __shared__ double scr[CHUNK * SCR];
     __shared__ int col0[CHUNK];
     const int tid = threadIdx.x, nt = blockDim.x;
     const T* P = static_cast<const T*>(a.cov);
-    const double* st = a.state;
-    const int64_t ld = a.ld;
-    const int N = a.dims;
     // a sticky error from an earlier frame: nothing is tested any more (d^2 = NaN) and every detection stays, so the frame
     // runs as it does without a gate
     const bool dead = a.status[0] != 0;
@@ -47,83 +40,21 @@ __global__ __launch_bounds__(EKF_GATE_THREADS) void ekf_frame_gate_kernel(const 
                 if (a.status_host) __hip_atomic_store(a.status_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 i = 0;
             }
-            const int c0 = EKF_CAM + LMD * i;
-            col0[tid] = c0;
-            double* Jd = scr + (size_t)tid * SCR;
-            double* rd = Jd + 2 * RD * JC + RD * RD;
-            double cam[EKF_CAM], lm[LMD], h[RD];
-            for (int q = 0; q < EKF_CAM; ++q) cam[q] = st[q];
-            for (int q = 0; q < LMD; ++q) lm[q] = st[c0 + q];
-            // (the rows go to LDS as the model produces them: a register copy of 7 x 20 would spill)
-            ekf_measure_model<MODEL>(cam, lm, h, reinterpret_cast<double(*)[JC]>(Jd));
-            for (int r = 0; r < RD; ++r) rd[r] = a.z[(size_t)(d0 + tid) * RD + r] - h[r];
+            col0[tid] = EKF_CAM + LMD * i;
+            ekf_gate_measure<MODEL>(a.state, col0[tid], a.z + (size_t)(d0 + tid) * RD, scr + (size_t)tid * SCR);
         }
         __syncthreads();
-        // T[:, ci] = H_d (P+Q)[supp, supp[ci]]: one thread per (detection, support column), the column's loads in one round
         for (int task = tid; task < mc * JC && !dead; task += nt) {
-            const int d = task / JC, ci = task - d * JC;
-            const int c0 = col0[d];
-            const int c = ci < EKF_CAM ? ci : c0 + ci - EKF_CAM;
-            const double* Jd = scr + (size_t)d * SCR;
-            double pc[JC];
-#pragma unroll
-            for (int si = 0; si < JC; ++si) {
-                const int s = si < EKF_CAM ? si : c0 + si - EKF_CAM;
-                pc[si] = (double)P[(int64_t)s * ld + c] + (si == ci ? ekf_qdiag(c, N, a.nz) : 0.0);
-            }
-#pragma unroll 1
-            for (int r = 0; r < RD; ++r) {
-                double acc = 0.0;
-#pragma unroll
-                for (int si = 0; si < JC; ++si) acc = fma(Jd[r * JC + si], pc[si], acc);
-                scr[(size_t)d * SCR + RD * JC + r * JC + ci] = acc;
-            }
+            const int d = task / JC;
+            ekf_gate_project<MODEL>(P, a.ld, col0[d], task - d * JC, a.dims, a.nz, scr + (size_t)d * SCR);
         }
         __syncthreads();
         bool keep = false, bad = false;
         if (tid < mc) {
             double out = __builtin_nan("");
             if (!dead) {
-                const double* Jd = scr + (size_t)tid * SCR;
-                const double* Td = Jd + RD * JC;
-                double* Sd = scr + (size_t)tid * SCR + 2 * RD * JC;
-                double* rd = Sd + RD * RD;
-                // S_d = T H_d^T + R I, lower triangle
-#pragma unroll 1
-                for (int r = 0; r < RD; ++r)
-#pragma unroll 1
-                    for (int rr = 0; rr <= r; ++rr) {
-                        double acc = 0.0;
-#pragma unroll 4
-                        for (int ci = 0; ci < JC; ++ci) acc = fma(Td[r * JC + ci], Jd[rr * JC + ci], acc);
-                        Sd[r * RD + rr] = acc + (r == rr ? a.nz.r_unc : 0.0);
-                    }
-                // S_d = L L^T row by row (L_ii on the diagonal) with y = L^-1 r behind each row; d^2 = y^T y
-                bool ok = true;
-                double d2 = 0.0;
-#pragma unroll 1
-                for (int i = 0; i < RD && ok; ++i) {
-                    double* Li = Sd + i * RD;
-#pragma unroll 1
-                    for (int j = 0; j < i; ++j) {
-                        const double* Lj = Sd + j * RD;
-                        double v = Li[j];
-                        for (int l = 0; l < j; ++l) v = fma(-Li[l], Lj[l], v);
-                        Li[j] = v / Lj[j];
-                    }
-                    double dii = Li[i], y = rd[i];
-                    for (int l = 0; l < i; ++l) {
-                        dii = fma(-Li[l], Li[l], dii);
-                        y = fma(-Li[l], rd[l], y);
-                    }
-                    ok = dii > 0.0 && isfinite(dii);
-                    if (ok) {
-                        Li[i] = sqrt(dii);
-                        y = y / Li[i];
-                        rd[i] = y;
-                        d2 = fma(y, y, d2);
-                    }
-                }
+                double d2;
+                const bool ok = ekf_gate_distance<MODEL>(a.nz.r_unc, scr + (size_t)tid * SCR, d2);
                 const bool exempt = a.exempt && a.exempt[d0 + tid] != 0;
                 out = exempt ? 0.0 : ok ? d2 : __builtin_nan("");
                 bad = !exempt && !ok;

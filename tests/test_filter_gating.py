@@ -420,6 +420,56 @@ def test_agrees_with_a_one_member_batch(model):
     report(f"filter_gating_vs_batch_{model}", worst_over_tol=worst)
 
 
+@pytest.mark.parametrize("model,family,m", [("ekf", "column", 1), ("ekf", "column", 16), ("ekf", "wide", 64),
+                                            ("ekf_rotations", "column", 1), ("ekf_rotations", "column", 8),
+                                            ("ekf_rotations", "wide", 17), ("ekf_rotations", "wide", 33)])
+def test_same_prior_same_bits_as_a_one_member_batch(model, family, m):
+    """Filter and batch run one code on a detection (ekf_gate_device.h): from the same prior, one further frame gives the
+    same d^2 bit for bit and the same rejected set.  The prior is the bootstrap of a clean log without its last landmark
+    on a one-member batch, handed over by ``to_filter`` (f64 and bitwise symmetric: the upload is exact).  The frame of m
+    detections: known landmarks (repeating once m exceeds the map), in the middle a duplicate of one grossly off, at the
+    end the first sighting of the landmark held back (exempt: exactly 0 in both) and a second detection of it grossly off
+    (tested against what the first one placed); m = 1 is one known landmark.  m = 16 / 8 fill a one-column frame, m = 64
+    fills the filter's chunk (four blocks in the batch), m = 17 and 33 cross the chunk of 16 once and twice."""
+    from aruco_slam_amd.batch import EKFBatch
+    kw, n, _m_range = gu.FAMILIES[(model, family)]
+    kw = dict(kw, max_visible=max(kw["max_visible"], m))
+    gate = gu.GATES[model]
+    clean = gu.clean_log(model, family, seed=LOG_SEED)
+    end = int(clean["offsets"][int(clean["bootstrap_frames"])])
+    boot = {"ids": clean["ids"][:end], "poses": clean["poses"][:end],
+            "offsets": clean["offsets"][:int(clean["bootstrap_frames"]) + 1]}
+    # the frame's poses: every landmark as the log's steady frames first see it (the camera has moved: r = z - h is far
+    # from zero, which it is not for the bootstrap's own poses)
+    first = end + np.unique(clean["ids"][end:], return_index=True)[1]
+    assert clean["ids"][first].tolist() == list(range(n))
+    seen = clean["poses"][first]
+    new = n - 1
+    batch = EKFBatch(1, INIT, model=model, gate=gate, **kw)
+    batch.process_detection_logs([gu.delete(boot, boot["ids"] == new)])
+    assert batch.status() == [0] and batch.num_landmarks == [n - 1]
+    flt = batch.to_filter(0)
+    if m == 1:
+        ids, poses, tested = np.array([0], np.int32), seen[[0]], np.array([True])
+    else:
+        ids = np.arange(m - 3) % (n - 1)
+        poses, rng, at = seen[ids], np.random.default_rng(m), m // 2
+        ids = np.concatenate((ids[:at], ids[[0]], ids[at:], [new, new])).astype(np.int32)
+        poses = np.vstack((poses[:at], gu._outlier(model, poses[0], rng, 0), poses[at:], seen[[new]],
+                           gu._outlier(model, seen[new], rng, 1)))
+        tested = np.arange(m) != m - 2
+    offsets = np.array([0, m], np.int64)
+    out = batch.process_detection_logs([{"ids": ids, "poses": poses, "offsets": offsets}], mahal=True)
+    _traj, d2 = flt.process_detection_log(ids, poses, offsets, mahal=True)
+    want = out.mahal[0]
+    assert d2.shape == want.shape == (m,) and batch.status() == [0]
+    assert np.isfinite(want).all() and (want[tested] > 0).all() and (want[~tested] == 0).all()
+    assert np.array_equal(d2, want), (model, m, np.flatnonzero(d2 != want), d2[d2 != want], want[d2 != want])
+    assert np.array_equal(d2 > gate, out.rejected[0])
+    if m > 1:
+        assert out.rejected[0][[m // 2, m - 1]].all() and not out.rejected[0][m - 2]
+
+
 def test_to_filter_and_load_filter_and_checkpoints_carry_the_gate(tmp_path):
     from aruco_slam_amd.batch import EKFBatch
     batch = EKFBatch(2, INIT, max_landmarks=8, max_visible=4, gate=[7.815, np.inf])

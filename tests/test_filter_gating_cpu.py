@@ -84,8 +84,10 @@ def test_gate_kernel_uses_no_scratch_and_no_spill_and_its_own_lds_only():
         want = next(v for k, v in lds.items() if k in name)
         assert res["private_segment_fixed_size"] == 0 and res["vgpr_spill_count"] == 0, (name, res)
         assert res["group_segment_fixed_size"] == want, (name, res)
-    text = (Path(__file__).resolve().parent.parent / "aruco_slam_amd" / "csrc" / "ekf_gate.hip").read_text()
-    assert "ekf_measure_model<MODEL>" in text          # (the measurement model is ekf_device.h's, not a copy)
+    csrc = Path(__file__).resolve().parent.parent / "aruco_slam_amd" / "csrc"
+    # (the kernel's measurement stage is the shared core's, and that one's model is ekf_device.h's, not a copy)
+    assert "ekf_gate_measure<MODEL>" in (csrc / "ekf_gate.hip").read_text()
+    assert "ekf_measure_model<MODEL>" in (csrc / "ekf_gate_device.h").read_text()
 
 
 def test_gate_values_are_checked_on_the_host():

@@ -41,7 +41,7 @@ import numpy as np
 
 from .filters.base_filter import plan_detection_log
 from .hip_backend import (EKF_FLAG_BATCH_LARGE_MAPS, EKF_FLAG_BATCH_WIDE_FRAMES, EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError,
-                          _dptr, load_library)
+                          _dptr, load_library, row_noise_array)
 
 NOISE_KEYS = ("initial_camera_uncertainty", "initial_landmark_uncertainty", "r_uncertainty", "q_cam", "q_err", "q_lm")
 EKF_ERR_NUMERIC = -5
@@ -300,6 +300,35 @@ def replica_corners(corners, sigma_px, seed: int, camera_matrix, dist_coeffs=Non
                                    first_replica, device)["noisy"]
 
 
+def corner_row_noise(log, sigma_px, seed: int, replicas: int, camera_matrix, dist_coeffs=None, marker_size: float = 0.16,
+                     model: str = "ekf", *, device: str = "cuda:0") -> np.ndarray:
+    """Per-detection measurement noise [D, RD] of a log of ``corners`` [D, 4, 2] from its own Monte-Carlo front end: the
+    variance over ``replicas`` corner replicas (``replica_corner_poses`` with one ``sigma_px`` for all of them: pixel
+    noise on the corners, IPPE on the device) of the z each model forms from a pose -- ``EKF``: the tvec; ``EKF_Rotations``:
+    ``[tvec | quaternion of the xyz Euler angles rvec]``, the mapping ``EKF_Rotations.observe`` uses.  ``numpy.var`` over
+    the replica axis (host arithmetic on device-drawn poses).  Depth rows grow with distance and tilt, and a detection whose
+    IPPE solution flips in some replicas gets large quaternion rows: what ``noise=`` of the observe calls and ``"noise"``
+    of a batch log take.  A variance that comes out zero (``sigma_px = 0``) is not a valid row."""
+    if model not in MODELS:
+        raise ValueError(f"model must be one of {sorted(MODELS)}, got {model!r}")
+    if int(replicas) < 2:
+        raise ValueError("a variance needs at least 2 replicas")
+    poses = replica_corner_poses(log["corners"], float(sigma_px), seed, camera_matrix, dist_coeffs, marker_size,
+                                 replicas=int(replicas), device=device)
+    return np.var(replica_z(poses, model), axis=0)
+
+
+def replica_z(poses, model: str) -> np.ndarray:
+    """z [..., RD] of poses [..., 6] as the model's filter forms it (``EKF``: tvec; ``EKF_Rotations``: tvec and the
+    scalar-first quaternion of the xyz Euler angles)."""
+    poses = np.asarray(poses, dtype=np.float64)
+    if model == "ekf":
+        return poses[..., :3].copy()
+    from .filters.ekf_with_rotations import euler_xyz_to_quat
+    quat = euler_xyz_to_quat(poses[..., 3:6].reshape(-1, 3)).reshape(poses.shape[:-1] + (4,))
+    return np.concatenate((poses[..., :3], quat), axis=-1)
+
+
 def _iptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
@@ -314,14 +343,15 @@ class EKFBatch:
     ``EKF``; ``EKF_Rotations`` has only ``"scalar_first"``); ``noise``: dict of scalars or length-B arrays keyed by
     ``NOISE_KEYS`` (missing keys: the model's constants); ``large_maps``: see ``use_large_maps`` (the choice is kept in
     ``self.large_maps``); ``wide_frames``: see ``use_wide_frames`` (kept in ``self.wide_frames``); ``gate``: see
-    ``set_gate`` (kept in ``self.gate``)."""
+    ``set_gate`` (kept in ``self.gate``); ``row_noise``: the logs may carry per-detection measurement noise (``"noise"`` in
+    ``process_detection_logs``, ``noise=`` of ``observe_indexed``; kept in ``self.row_noise``)."""
 
     gate = None        # [B] chi-square gate per member, or None: no gate (set_gate)
     camera = None      # (camera matrix [9], distortion coefficients, marker size) of corner logs, or None (set_camera)
 
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
                  quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf",
-                 large_maps: bool | None = None, wide_frames: bool | None = None, gate=None) -> None:
+                 large_maps: bool | None = None, wide_frames: bool | None = None, gate=None, row_noise: bool = False) -> None:
         import torch
         gate = gate_array(gate, int(members))
         if model not in MODELS:
@@ -340,6 +370,7 @@ class EKFBatch:
         if not torch.cuda.is_available():
             raise RuntimeError("the EKF update path needs a HIP device (no CPU fallback)")
         self.members = int(members)
+        self.row_noise = bool(row_noise)
         self.device = torch.device(device)
         self.model = model
         self.lm_dims = LM_DIMS[model]
@@ -454,11 +485,17 @@ class EKFBatch:
         ``dof`` (the NIS's chi^2 degrees of freedom; approximate for EKF_Rotations, whose unit-quaternion rows are not
         independent) and P[0:10, 0:10] after it.  A member's failing frame and every later one give NaN.
         With ``mahal``, or with a gate set (``set_gate``), it returns a ``GatedBatchReplay``: the same fields with ``dof``
-        over the surviving detections, every detection's d^2 and whether the gate rejected it."""
+        over the surviving detections, every detection's d^2 and whether the gate rejected it.
+        A log may carry ``noise`` ([D] or [D, RD], aligned with ``ids``; a batch built with ``row_noise=True``): the
+        variances of its detections' measurement rows, in place of the member's ``r_uncertainty``.  A member whose log
+        carries none keeps its constant (the same bits as without any ``noise`` in the call)."""
         gated = mahal or self.gate is not None
         if len(logs) != self.members:
             raise ValueError(f"need {self.members} logs (None for a member without one), got {len(logs)}")
         plans, index, offsets, frames, poses = [], [], [], [0], []
+        rows, any_rows = [], any(log is not None and log.get("noise") is not None for log in logs)
+        if any_rows and not self.row_noise:
+            raise ValueError("a log with noise needs a batch built with row_noise=True")
         corner_parts = []       # (first row, kept corners [n,4,2]) of every log that carries corners
         base = 0
         for b, log in enumerate(logs):
@@ -482,6 +519,12 @@ class EKFBatch:
                 p = np.asarray(log["poses"], dtype=np.float64)
                 if p.shape != (plan.keep.shape[0], 6):
                     raise ValueError(f"member {b}: poses must have shape ({plan.keep.shape[0]}, 6), got {p.shape}")
+            if any_rows:
+                if log.get("noise") is not None:
+                    r = row_noise_array(log["noise"], plan.keep.shape[0], RD[self.model], f"member {b}: noise")
+                else:
+                    r = np.full((plan.keep.shape[0], RD[self.model]), self.noise[b, NOISE_KEYS.index("r_uncertainty")])
+                rows.append(r[plan.keep])
             plans.append(plan)
             index.append(plan.index)
             offsets.append(plan.offsets[1:] + base)
@@ -493,14 +536,15 @@ class EKFBatch:
         poses = np.ascontiguousarray(np.concatenate(poses) if poses else np.zeros((0, 6)))
         if sum(c.shape[0] for _, c in corner_parts):
             poses = self._estimate_corner_logs(poses, corner_parts)
+        with_rows = {"noise": np.concatenate(rows)} if any_rows and rows else {}      # (no rows: the call as it ever was)
         if gated:
             traj, nis_v, cov_v, mahal_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses,
-                                                               nis=nis, cam_cov=cam_cov, mahal=True)
+                                                               nis=nis, cam_cov=cam_cov, mahal=True, **with_rows)
         elif nis or cam_cov:
             traj, nis_v, cov_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses, nis=nis,
-                                                      cam_cov=cam_cov)
+                                                      cam_cov=cam_cov, **with_rows)
         else:
-            traj = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses)
+            traj = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses, **with_rows)
         self._adopt_plans(plans)
         split = [slice(frames[b], frames[b + 1]) for b in range(self.members)]
         if gated:
@@ -691,15 +735,20 @@ class EKFBatch:
                                    cov_t.cpu().numpy() if cam_cov else None, full, rej, flipped)
 
     def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False,
-                        mahal: bool = False):
+                        mahal: bool = False, noise=None):
         """The C call behind ``process_detection_logs`` (landmark indices already assigned; ``landmarks`` is not
         touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1] on the host, poses [D,6] on the host or a contiguous
         float64 tensor on the batch's device, produced on the batch's stream.  Returns the
         trajectory [Ftot, 7]; with ``nis`` or ``cam_cov`` the tuple (trajectory, nis [Ftot] or None, cam_cov [Ftot, 10, 10]
         or None); with ``mahal`` the tuple (trajectory, nis or None, cam_cov or None, mahal [D]).  A gate that is set acts
-        on every call, whatever it returns."""
+        on every call, whatever it returns.  ``noise``: [D] or [D, RD] row variances indexed like lm_index (a batch built
+        with ``row_noise=True``; ekf_batch_observe_logs_rows), or None: every member's ``r_uncertainty``."""
         torch = self._torch
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
+        if noise is not None:
+            if not self.row_noise:
+                raise ValueError("noise= needs a batch built with row_noise=True")
+            noise = row_noise_array(noise, idx.shape[0], RD[self.model])
         fo = np.ascontiguousarray(frame_offsets, dtype=np.int64).reshape(-1)
         mf = np.ascontiguousarray(member_frames, dtype=np.int64).reshape(-1)
         on_device = isinstance(poses, torch.Tensor)
@@ -723,6 +772,21 @@ class EKFBatch:
             poses_t = poses if on_device else torch.from_numpy(poses).to(self.device)
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
             traj = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
+            if noise is not None:
+                rows_t = torch.from_numpy(noise).to(self.device)
+                nis_t = torch.empty((frames,), dtype=torch.float64, device=self.device) if nis else None
+                cov_t = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
+                mahal_t = torch.empty((idx.shape[0],), dtype=torch.float64, device=self.device) if mahal else None
+                ptr = (lambda t: t.data_ptr() if t is not None and frames else None)
+                self._check(self.lib.ekf_batch_observe_logs_rows(
+                    self.h, _iptr(idx), _lptr(fo), _lptr(mf), poses_t.data_ptr() if idx.shape[0] else None,
+                    rows_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(), nbytes.value, ptr(traj), ptr(nis_t),
+                    ptr(cov_t), mahal_t.data_ptr() if mahal and idx.shape[0] else None))
+                self.stream.synchronize()
+                out = (traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, cov_t.cpu().numpy() if cam_cov else None)
+                if mahal:
+                    return out + (mahal_t.cpu().numpy(),)
+                return out if (nis or cam_cov) else out[0]
             if not (nis or cam_cov or mahal):
                 self._check(self.lib.ekf_batch_observe_logs(self.h, _iptr(idx), _lptr(fo), _lptr(mf),
                                                             poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
@@ -857,6 +921,8 @@ class EKFBatch:
             raise ValueError(f"a batch of model {self.model!r} holds {cls.__name__} filters, got {type(ekf).__name__}")
         if ekf.backend.cfg.quat_mode != QUAT_MODES[self.quat_update]:
             raise ValueError(f"the filter's quaternion convention differs from the batch's ({self.quat_update!r})")
+        if ekf.backend.can_row_noise and not self.row_noise:
+            raise ValueError("the filter takes per-detection noise: load it into a batch built with row_noise=True")
         ids = [k for k, _ in sorted(ekf.get_lm_estimates(), key=lambda kv: kv[1])]
         self.set_member(b, np.asarray(ekf.state, dtype=np.float64), ekf.uncertainty, ids)
         if ekf.gate is not None and not (self.gate is None and np.isinf(ekf.gate)):
@@ -866,7 +932,8 @@ class EKFBatch:
 
     def to_filter(self, b):
         """An ordinary filter of the batch's model (``EKF`` or ``EKF_Rotations``, f64 covariance) with member b's quaternion
-        convention, noise constants, gate (a batch with a gate gives a filter built with ``gate=``), state, covariance and
+        convention, noise constants, gate (a batch with a gate gives a filter built with ``gate=``), per-detection-noise
+        capability (a batch built with ``row_noise=True`` gives a filter built the same way), state, covariance and
         landmark table; ``observe`` (and for ``EKF`` ``save_map`` and ``save_checkpoint``) work on it."""
         b = self._member(b)
         state, cov = self.get_state(b), self.get_cov(b)
@@ -876,11 +943,11 @@ class EKFBatch:
         if self.model == "ekf_rotations":
             from .filters.ekf_with_rotations import EKF_Rotations
             ekf = EKF_Rotations(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
-                                device=str(self.device), noise=noise, gate=gate)
+                                device=str(self.device), noise=noise, gate=gate, row_noise=self.row_noise)
         else:
             from .filters.extended_kalman_filter import EKF
             ekf = EKF(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
-                      quat_update=self.quat_update, device=str(self.device), noise=noise, gate=gate)
+                      quat_update=self.quat_update, device=str(self.device), noise=noise, gate=gate, row_noise=self.row_noise)
         ekf.backend.set_state_cov(state, cov)
         ekf.landmarks = dict(self.landmarks[b])
         ekf.num_landmarks = n

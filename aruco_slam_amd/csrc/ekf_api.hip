@@ -1,6 +1,7 @@
 // C ABI of the EKF-SLAM HIP library (see include/ekf_slam_hip.h): the filter handle.  The batch handle is in
 // ekf_batch_api.hip.  Host side only: argument checking, workspace carving, launch sequencing.
 #include <atomic>
+#include <cmath>
 #include <cstring>
 
 #include "ekf_host.h"
@@ -51,6 +52,10 @@ struct Layout {
     // mask and the host copy of the distances behind the detections (0: no gate scratch)
     bool has_gate;
     size_t off_gidx, off_gz, off_gmahal, slot_exempt, slot_mahal;
+    // EKF_FLAG_ROW_NOISE: with the gate, the survivors' rows [max_visible][rd]; in a slot of the staging ring the frame's rows
+    // behind everything else, where the kernels read them as they read the indices and z (0: none)
+    bool has_rows;
+    size_t off_grow, slot_rows;
     // fused front kernel: one exchange buffer per fused-frame parity (offsets / length in doubles)
     size_t xl_len, xl_dop, xl_y, xl_jac, xl_tag, xl_xs, xl_xr, xl_stag;
 };
@@ -124,12 +129,16 @@ Layout make_layout(const ekf_config& c) {
     L.off_gidx = L.has_gate ? w.take((size_t)c.max_visible * 4) : 0;
     L.off_gz = L.has_gate ? w.take((size_t)c.max_visible * 7 * 8) : 0;
     L.off_gmahal = L.has_gate ? w.take((size_t)c.max_visible * 8) : 0;
+    // per-detection measurement noise; configurations without the flag keep their sizes
+    L.has_rows = (c.flags & EKF_FLAG_ROW_NOISE) != 0;
+    L.off_grow = L.has_rows && L.has_gate ? w.take((size_t)c.max_visible * L.rd * 8) : 0;
     L.total = w.end;
     // one slot of the pinned staging ring: a frame's detections as ekf_observe stages them, or 256 markers of ekf_add_markers
     const size_t det_bytes = align256((size_t)c.max_visible * 4) + align256((size_t)c.max_visible * 56);
     L.slot_exempt = det_bytes;
     L.slot_mahal = det_bytes + align256((size_t)c.max_visible);
-    L.slot_bytes = std::max(L.has_gate ? L.slot_mahal + align256((size_t)c.max_visible * 8) : det_bytes,
+    L.slot_rows = L.has_gate ? L.slot_mahal + align256((size_t)c.max_visible * 8) : det_bytes;
+    L.slot_bytes = std::max(L.has_rows ? L.slot_rows + align256((size_t)c.max_visible * L.rd * 8) : L.slot_rows,
                             align256(256 * 48) + align256(256 * 80));
     return L;
 }
@@ -268,7 +277,7 @@ int fold_timing(ekf_filter* f) {
     return EKF_OK;
 }
 
-EkfFrame make_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, int m,
+EkfFrame make_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, const double* rows_dev, int m,
                     double* traj_row) {
     EkfFrame fr{};
     const Layout& L = f->lay;
@@ -283,13 +292,13 @@ EkfFrame make_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, 
     fr.kpad = (int)round_up(fr.k, EKF_RB);
     fr.idx = idx_dev;
     fr.z = z_dev;
+    fr.rrow = rows_dev;
     fr.jac = f->at<double>(L.off_jac);
     fr.resid = f->at<double>(L.off_resid);
     fr.lmcol = f->at<int32_t>(L.off_lmcol);
     fr.amat = f->at<double>(L.off_amat);
     fr.lda = L.cap;
     fr.sblk = f->at<double>(L.off_sblk);
-    fr.sblk_rows = L.kmax;
     fr.lmat = f->at<double>(L.off_lmat);
     fr.ldl = L.kmax;
     fr.dinv = f->at<double>(L.off_dinv);
@@ -376,11 +385,12 @@ int ensure_tiles(ekf_filter* f) {
 // predict + update for one frame: the front kernel (or gather / solve / panel) and the covariance update
 // `mirror`: the frame also leaves its state in the pinned host mirror (per-frame entry points: a state getter usually follows;
 // frames of a sequence call do not -- no getter can run between them, and the mirror is 8 N bytes over PCIe per frame)
-int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, int m,
+// rows_dev [m][rd] (device, or pinned host) or null: per-detection noise
+int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, const double* rows_dev, int m,
                   double* traj_row, bool mirror) {
     int trc = ensure_tiles(f);
     if (trc) return trc;
-    EkfFrame fr = make_frame(f, idx_dev, z_dev, m, traj_row);
+    EkfFrame fr = make_frame(f, idx_dev, z_dev, rows_dev, m, traj_row);
     const int variant = f->cfg.cov_kernel == EKF_COVK_VALU ? 1 : 2;
     hipEvent_t* ev = nullptr;
     if (f->timing) {
@@ -610,6 +620,7 @@ struct RunFrame {
     const double* z;
     int m;
     double* traj_row;
+    const double* rows = nullptr;      // [m][rd] or null: per-detection noise
 };
 
 // A run of `frames` >= 2 frames in the pipelined sequence mode; frame_at(t) describes frame t.  Every frame of a run has the
@@ -668,7 +679,7 @@ int run_pipelined(ekf_filter* f, int frames, FrameAt frame_at, void* other) {
     for (int t = 0; t < frames; ++t) {
         const int par = t & 1;
         const RunFrame cf_t = nx;
-        EkfFrame fr = make_frame(f, cf_t.idx, cf_t.z, cf_t.m, cf_t.traj_row);
+        EkfFrame fr = make_frame(f, cf_t.idx, cf_t.z, cf_t.rows, cf_t.m, cf_t.traj_row);
         fr.cov = cbuf[0];
         fr.wpanel = wbuf[par];
         if (t > 0) {                                           // P_{t-1} + the completion from W_{t-1}
@@ -762,7 +773,7 @@ int run_frames(ekf_filter* f, int frames, FrameOf frame_of, FirstSightings first
     auto serial = [&](int t) {
         const RunFrame r = frame_of(t);
         if (stats) stats[0] += 1;
-        return enqueue_frame(f, r.idx, r.z, r.m, r.traj_row, false);
+        return enqueue_frame(f, r.idx, r.z, r.rows, r.m, r.traj_row, false);
     };
     auto flush = [&]() -> int {
         int rc = EKF_OK;
@@ -834,8 +845,9 @@ int open_handle(ekf_filter* f) {
 // the same launches as the same call on the frame with the rejected detections deleted.  No survivor: nothing is stepped.
 // exempt [m] (pinned host or device) or null; n_exempt: how many of them are set (statistics); mahal_dev / mahal_host [m] or
 // null.  *survivors: how many detections stayed.
-int gated_frame(ekf_filter* f, const int32_t* idx, const double* z, int m, const uint8_t* exempt, int n_exempt,
-                double* mahal_dev, double* mahal_host, double* traj_row, bool mirror, int* survivors) {
+// rows [m][rd] or null: per-detection noise; the gate tests with them and compacts them with the survivors.
+int gated_frame(ekf_filter* f, const int32_t* idx, const double* z, const double* rows, int m, const uint8_t* exempt,
+                int n_exempt, double* mahal_dev, double* mahal_host, double* traj_row, bool mirror, int* survivors) {
     const Layout& L = f->lay;
     EkfGateArgs g{};
     g.cov = f->cov;
@@ -853,6 +865,8 @@ int gated_frame(ekf_filter* f, const int32_t* idx, const double* z, int m, const
     g.mahal_host = mahal_host;
     g.out_idx = f->at<int32_t>(L.off_gidx);
     g.out_z = f->at<double>(L.off_gz);
+    g.rows = rows;
+    g.out_rows = rows ? f->at<double>(L.off_grow) : nullptr;
     g.status = f->at<int32_t>(L.off_status);
     g.status_host = f->readback.at<int32_t>(128);
     g.result_host = f->gate_pin.at<int32_t>(0);
@@ -866,7 +880,7 @@ int gated_frame(ekf_filter* f, const int32_t* idx, const double* z, int m, const
     f->gate_stats[1] += m - s;
     if (survivors) *survivors = s;
     if (s == 0) return EKF_OK;
-    return enqueue_frame(f, g.out_idx, g.out_z, s, traj_row, mirror);
+    return enqueue_frame(f, g.out_idx, g.out_z, g.out_rows, s, traj_row, mirror);
 }
 
 // trajectory row of a frame that is not stepped: the camera state as it is on the device
@@ -877,15 +891,16 @@ int repeat_row(ekf_filter* f, double* traj_row) {
 
 // A gated frame of a sequence or of a log (device arrays, no host mirror): the frame on its survivors, or, with none left,
 // its trajectory row alone
-int gated_frame_or_row(ekf_filter* f, const int32_t* idx, const double* z, int m, const uint8_t* exempt, int n_exempt,
-                       double* mahal_dev, double* traj_row, int* survivors) {
-    const int rc = gated_frame(f, idx, z, m, exempt, n_exempt, mahal_dev, nullptr, traj_row, false, survivors);
+int gated_frame_or_row(ekf_filter* f, const int32_t* idx, const double* z, const double* rows, int m, const uint8_t* exempt,
+                       int n_exempt, double* mahal_dev, double* traj_row, int* survivors) {
+    const int rc = gated_frame(f, idx, z, rows, m, exempt, n_exempt, mahal_dev, nullptr, traj_row, false, survivors);
     return rc == EKF_OK && *survivors == 0 ? repeat_row(f, traj_row) : rc;
 }
 
 // ekf_observe / ekf_observe_gated: the frame's detections (host) through a slot of the pinned staging ring
-int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, int32_t m, bool gated, const uint8_t* exempt,
-                 double* mahal, int32_t* survivors) {
+// rows [m][rd] (host) or null: per-detection noise, staged behind everything else of the slot
+int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m, bool gated,
+                 const uint8_t* exempt, double* mahal, int32_t* survivors) {
     if (m < 1) return fail(EKF_ERR_INVALID, "observe needs at least one detection");
     if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
     if (!lm_index || !z) return fail(EKF_ERR_INVALID, "NULL detections");
@@ -893,6 +908,12 @@ int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, int32_
         if (lm_index[i] < 0 || lm_index[i] >= f->n_lm)
             return fail(EKF_ERR_INVALID, "landmark index out of range");
     const Layout& L = f->lay;
+    if (rows) {
+        if (!L.has_rows) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_ROW_NOISE");
+        for (size_t i = 0; i < (size_t)m * L.rd; ++i)
+            if (!(rows[i] > 0.0) || !std::isfinite(rows[i]))
+                return fail(EKF_ERR_INVALID, "a row variance must be finite and > 0");
+    }
     char* slot = f->ring.get() + (size_t)f->slot * L.slot_bytes;
     HIP_TRY(hipEventSynchronize(f->slot_done[f->slot]));
     int32_t* hidx = reinterpret_cast<int32_t*>(slot);
@@ -900,6 +921,11 @@ int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, int32_
     const size_t zb = (size_t)m * L.rd * 8;
     std::memcpy(hidx, lm_index, (size_t)m * 4);
     std::memcpy(hz, z, zb);
+    double* hrows = nullptr;
+    if (rows) {
+        hrows = reinterpret_cast<double*>(slot + L.slot_rows);
+        std::memcpy(hrows, rows, zb);
+    }
     // one copy: the pinned slot mirrors the device staging layout [indices, padded to 256 B | z]
     static_assert(sizeof(int32_t) == 4, "layout");
     if (L.off_z - L.off_idx != align256((size_t)f->cfg.max_visible * 4)) return fail(EKF_ERR_STATE, "staging layout");
@@ -917,12 +943,12 @@ int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, int32_
         }
         double* hm = mahal ? reinterpret_cast<double*>(slot + L.slot_mahal) : nullptr;
         int s = 0;
-        rc = gated_frame(f, hidx, hz, m, hex, n_exempt, nullptr, hm, nullptr, true, &s);
+        rc = gated_frame(f, hidx, hz, hrows, m, hex, n_exempt, nullptr, hm, nullptr, true, &s);
         if (rc) return rc;
         if (mahal) std::memcpy(mahal, hm, (size_t)m * 8);      // (complete: the gate kernel's event has been waited for)
         if (survivors) *survivors = s;
     } else {
-        rc = enqueue_frame(f, hidx, hz, m, nullptr, true);
+        rc = enqueue_frame(f, hidx, hz, hrows, m, nullptr, true);
         if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(f->slot_done[f->slot], f->stream));
@@ -1228,7 +1254,7 @@ int ekf_observe(ekf_filter* f, const int32_t* lm_index, const double* z, int32_t
     int rc = check_ready(f);
     if (rc) return rc;
     f->reset_gate_stats();
-    return observe_host(f, lm_index, z, m, f->gate_on(), nullptr, nullptr, nullptr);
+    return observe_host(f, lm_index, z, nullptr, m, f->gate_on(), nullptr, nullptr, nullptr);
 }
 
 int ekf_observe_gated(ekf_filter* f, const int32_t* lm_index, const double* z, int32_t m, const uint8_t* exempt, double* mahal,
@@ -1238,7 +1264,19 @@ int ekf_observe_gated(ekf_filter* f, const int32_t* lm_index, const double* z, i
     if (!f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
     f->reset_gate_stats();
     const bool gated = f->gate_on() || mahal;
-    rc = observe_host(f, lm_index, z, m, gated, exempt, mahal, survivors);
+    rc = observe_host(f, lm_index, z, nullptr, m, gated, exempt, mahal, survivors);
+    if (rc == EKF_OK && !gated && survivors) *survivors = m;
+    return rc;
+}
+
+int ekf_observe_rows(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m,
+                     const uint8_t* exempt, double* mahal, int32_t* survivors) {
+    int rc = check_ready(f);
+    if (rc) return rc;
+    if ((exempt || mahal) && !f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
+    f->reset_gate_stats();
+    const bool gated = f->gate_on() || mahal;
+    rc = observe_host(f, lm_index, z, rows, m, gated, exempt, mahal, survivors);
     if (rc == EKF_OK && !gated && survivors) *survivors = m;
     return rc;
 }
@@ -1268,14 +1306,20 @@ int ekf_observe_device(ekf_filter* f, const int32_t* lm_index_dev, const double*
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
     // the indices are device-resident: range-checked by the kernels (EKF_ERR_INVALID at the next sync)
     f->reset_gate_stats();
-    if (f->gate_on()) return gated_frame(f, lm_index_dev, z_dev, m, nullptr, 0, nullptr, nullptr, nullptr, true, nullptr);
-    return enqueue_frame(f, lm_index_dev, z_dev, m, nullptr, true);
+    if (f->gate_on()) return gated_frame(f, lm_index_dev, z_dev, nullptr, m, nullptr, 0, nullptr, nullptr, nullptr, true, nullptr);
+    return enqueue_frame(f, lm_index_dev, z_dev, nullptr, m, nullptr, true);
 }
 
 int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, const double* z_dev,
                                 int32_t m, int32_t frames, double* trajectory_dev) {
+    return ekf_observe_sequence_device_rows(f, lm_index_dev, z_dev, nullptr, m, frames, trajectory_dev);
+}
+
+int ekf_observe_sequence_device_rows(ekf_filter* f, const int32_t* lm_index_dev, const double* z_dev, const double* rows_dev,
+                                     int32_t m, int32_t frames, double* trajectory_dev) {
     int rc = check_ready(f);
     if (rc) return rc;
+    if (rows_dev && !f->lay.has_rows) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_ROW_NOISE");
     if (m < 1 || frames < 0) return fail(EKF_ERR_INVALID, "bad sequence shape");
     if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
     if (!lm_index_dev || !z_dev) return fail(EKF_ERR_INVALID, "NULL detections");
@@ -1289,7 +1333,8 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
         f->shortcut.log();      // (a getter after the call waits for all of it)
         for (int t = 0; t < frames; ++t) {
             int s = 0;
-            rc = gated_frame_or_row(f, lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd, m, nullptr, 0, nullptr,
+            rc = gated_frame_or_row(f, lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd,
+                                    rows_dev ? rows_dev + (size_t)t * m * rd : nullptr, m, nullptr, 0, nullptr,
                                     trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr, &s);
             if (rc) return rc;
         }
@@ -1306,7 +1351,8 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
         f, frames,
         [&](int t) {
             return RunFrame{lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd, m,
-                            trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr};
+                            trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr,
+                            rows_dev ? rows_dev + (size_t)t * m * rd : nullptr};
         },
         [](int) { return 0; }, plan, mode == EKF_SEQ_PIPELINED, nullptr);
     if (rc) return rc;
@@ -1351,14 +1397,21 @@ int ekf_last_log_stats(const ekf_filter* f, int64_t out[4]) {
 
 int ekf_observe_log(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames, const double* poses_dev,
                     void* log_ws, size_t log_ws_bytes, double* trajectory_dev) {
-    return ekf_observe_log_gated(f, lm_index, offsets, frames, poses_dev, log_ws, log_ws_bytes, trajectory_dev, nullptr);
+    return ekf_observe_log_rows(f, lm_index, offsets, frames, poses_dev, nullptr, log_ws, log_ws_bytes, trajectory_dev, nullptr);
 }
 
 int ekf_observe_log_gated(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
                           const double* poses_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev,
                           double* mahal_dev) {
+    return ekf_observe_log_rows(f, lm_index, offsets, frames, poses_dev, nullptr, log_ws, log_ws_bytes, trajectory_dev, mahal_dev);
+}
+
+int ekf_observe_log_rows(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
+                         const double* poses_dev, const double* rows_dev, void* log_ws, size_t log_ws_bytes,
+                         double* trajectory_dev, double* mahal_dev) {
     int rc = check_ready(f);
     if (rc) return rc;
+    if (rows_dev && !f->lay.has_rows) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_ROW_NOISE");
     if (mahal_dev && !f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
     // a gate that is set, or distances asked for: frame by frame in serial order, each frame on its survivors
     const bool gated = f->gate_on() || mahal_dev;
@@ -1436,7 +1489,8 @@ int ekf_observe_log_gated(ekf_filter* f, const int32_t* lm_index, const int64_t*
     if (!lead.empty()) ekf_launch_log_fill_rows(trajectory_dev, pin_lead, (int32_t)(lead.size() / 2), f->state, f->stream);
     auto frame_of = [&](int t) {
         const int64_t d0 = offsets[t];
-        return RunFrame{idx_all + d0, z_all + (size_t)d0 * rd, m_of(t), trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr};
+        return RunFrame{idx_all + d0, z_all + (size_t)d0 * rd, m_of(t), trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr,
+                        rows_dev ? rows_dev + (size_t)d0 * rd : nullptr};
     };
     auto first_sightings = [&](int t) {
         const int nnew = nnew_of(t);
@@ -1462,8 +1516,8 @@ int ekf_observe_log_gated(ekf_filter* f, const int32_t* lm_index, const int64_t*
             f->log_stats[3] += nnew;
             const int64_t d0 = offsets[t];
             int s = 0;
-            rc = gated_frame_or_row(f, r.idx, r.z, r.m, pin_exempt + d0, nnew, mahal_dev ? mahal_dev + d0 : nullptr, r.traj_row,
-                                    &s);
+            rc = gated_frame_or_row(f, r.idx, r.z, r.rows, r.m, pin_exempt + d0, nnew, mahal_dev ? mahal_dev + d0 : nullptr,
+                                    r.traj_row, &s);
             if (rc == EKF_OK && s > 0) f->log_stats[0] += 1;
         }
     } else {

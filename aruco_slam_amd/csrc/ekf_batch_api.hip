@@ -176,7 +176,8 @@ BatchReplicaLayout batch_replica_layout(int64_t D, int64_t F, int32_t B, bool ga
 // [w, w + window) of its log per launch, state carried in HBM.  LDS is sized for the widest frame and the largest map of
 // the call (a layout choice only: the arithmetic is the same)
 int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, const BatchShape& sh, const double* poses_dev,
-                      double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev) {
+                      double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev,
+                      const double* rows_dev = nullptr) {
     const int32_t B = b->members;
     const BatchLayout L = batch_layout(b->cfg, B);
     EkfBatchWindow a{};
@@ -196,6 +197,7 @@ int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, co
     a.quat_mode = b->cfg.quat_mode;
     a.gate = batch_gated(b) ? reinterpret_cast<const double*>(ws + LL.gate) : nullptr;
     a.mahal = mahal_dev;
+    a.row_noise = rows_dev;      // (per-detection noise: data of the call, no workspace of its own)
     const int rd = batch_rd(b->cfg);
     a.kmax = std::max(rd, rd * sh.widest);
     a.lda = (int32_t)round_up(batch_lmd(b->cfg) * sh.n_max + EKF_CAM + 1, 4);
@@ -498,6 +500,14 @@ int ekf_batch_observe_logs_diag(ekf_batch* b, const int32_t* lm_index, const int
 int ekf_batch_observe_logs_gated(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets,
                                  const int64_t* member_frames, const double* poses_dev, void* log_ws, size_t log_ws_bytes,
                                  double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev) {
+    return ekf_batch_observe_logs_rows(b, lm_index, frame_offsets, member_frames, poses_dev, nullptr, log_ws, log_ws_bytes,
+                                       trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
+}
+
+int ekf_batch_observe_logs_rows(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets,
+                                const int64_t* member_frames, const double* poses_dev, const double* rows_dev, void* log_ws,
+                                size_t log_ws_bytes, double* trajectory_dev, double* nis_dev, double* cam_cov_dev,
+                                double* mahal_dev) {
     int rc = batch_ready(b);
     if (rc) return rc;
     // ---- validation on the host: nothing is enqueued before every log has passed
@@ -529,7 +539,7 @@ int ekf_batch_observe_logs_gated(ekf_batch* b, const int32_t* lm_index, const in
     if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
     char* ws = static_cast<char*>(log_ws);
     HIP_TRY(hipMemcpyAsync(ws, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
-    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
+    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev);
 }
 
 int ekf_batch_replica_poses(const double* poses_dev, int64_t detections, const double* sigma, int32_t replicas,

@@ -2,7 +2,7 @@
 // ONE workgroup owns ONE member for a window of its log's frames.  Per stepped frame, the algebra of DESIGN section 2 with
 // everything but P in LDS:
 //   first sightings (the frame's pre-update camera), h and dh of every detection,
-//   A = H (P+Q) [k, N], S = A[:,supp] H^T + R I (lower triangle), S = L L^T (left-looking, in LDS),
+//   A = H (P+Q) [k, N], S = A[:,supp] H^T + R I (or + diag(row_noise)) (lower triangle), S = L L^T (left-looking, in LDS),
 //   W = L^-1 A and y = L^-1 (z - h) (y is column N of A), dx = W^T y and the injection,
 //   P <- (P+Q) - W^T W in global memory.
 // MODEL 0 (EKF): RD = 3 rows per detection, LMD = 3 landmark dims, JC = 13 Jacobian columns (ekf_batch.hip).
@@ -94,7 +94,8 @@ __device__ __forceinline__ uint64_t ekf_batch_gate(const EkfBatchWindow& a, int 
     bool keep = false;
     if (tid < m) {
         double d2;
-        const bool ok = ekf_gate_distance<MODEL>(nz.r_unc, scr + (size_t)tid * SCR, d2);
+        const bool ok = ekf_gate_distance<MODEL>(nz.r_unc, a.row_noise ? a.row_noise + (size_t)(d0 + tid) * RD : nullptr,
+                                                    scr + (size_t)tid * SCR, d2);
         bool exempt = idx[tid] >= n0;
         for (int e = 0; e < tid; ++e) exempt = exempt && idx[e] != idx[tid];
         const double out = exempt ? 0.0 : ok ? d2 : __builtin_nan("");
@@ -116,6 +117,17 @@ __device__ __forceinline__ uint64_t ekf_batch_gate(const EkfBatchWindow& a, int 
 __device__ __forceinline__ int ekf_batch_survivor(uint64_t mask, int slot) {
     for (int i = 0; i < slot; ++i) mask &= mask - 1;
     return __builtin_ctzll(mask);
+}
+
+// Variance of measurement row r of a frame's stacked survivors (detections from d0 on): the member's constant, or, with
+// per-detection noise, the row of the survivor's detection in the log -- rows are indexed like lm_index, gate or no gate.
+template <int RD>
+__device__ __forceinline__ double ekf_batch_row_noise(const EkfBatchWindow& a, int64_t d0, bool gated, uint64_t mask, int r,
+                                                      double r_unc) {
+    if (!a.row_noise) return r_unc;
+    const int slot = r / RD;
+    const int src = gated ? ekf_batch_survivor(mask, slot) : slot;
+    return a.row_noise[(size_t)(d0 + src) * RD + (r - slot * RD)];
 }
 
 template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
@@ -235,7 +247,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
             double acc = 0.0;
             for (int s = 0; s < EKF_CAM; ++s) acc = fma(Ar[s], Jr[s], acc);
             for (int q = 0; q < LMD; ++q) acc = fma(Ar[c0 + q], Jr[EKF_CAM + q], acc);
-            L[r * kmax + rr] = acc + (r == rr ? nz.r_unc : 0.0);
+            L[r * kmax + rr] = acc + (r == rr ? ekf_batch_row_noise<RD>(a, d0, gated, mask, r, nz.r_unc) : 0.0);
         }
         __syncthreads();
         // S = L L^T, left-looking, one column per step: every thread of the column recomputes the pivot with the same

@@ -221,7 +221,7 @@ template <int MODEL, bool ONE_BLOCK> __device__ __forceinline__ void ekf_batch_w
                 double acc = 0.0;
                 for (int s = 0; s < EKF_CAM; ++s) acc = fma(Ar[s], Jr[s], acc);
                 for (int q = 0; q < LMD; ++q) acc = fma(Ar[c0 + q], Jr[EKF_CAM + q], acc);
-                L[r * kbmax + rr] = acc + (r == rr ? nz.r_unc : 0.0);
+                L[r * kbmax + rr] = acc + (r == rr ? ekf_batch_row_noise<RD>(a, d0, gated, mask, r0 + r, nz.r_unc) : 0.0);
             }
             __syncthreads();
             // S_jj = L_jj L_jj^T, left-looking, as ekf_batch_impl.h (pivots recomputed by every thread of the column)

@@ -106,7 +106,10 @@ __device__ __forceinline__ void fr_measure(const EkfFrame& fr, const double* cam
 // ---------------------------------------------------------------------------------------------
 // role: one block of S
 // ---------------------------------------------------------------------------------------------
-template <typename T, int MODEL, int NB>
+// ROWS: the frame carries per-detection noise (fr.rrow).  A template parameter of the kernel, not a test inside the role:
+// the kernels without rows are, instruction for instruction, what they were before rows existed (a test and a second copy
+// of the role inside one kernel moved the code behind it, and the frame by 0.4 us).
+template <typename T, int MODEL, int NB, bool ROWS>
 __device__ __forceinline__ void fr_role_sblock(const EkfFrame& fr, int sb, int nS, double* sm) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     constexpr int NSLOT = EKF_CAM + LMD * EkfModel<MODEL>::NDET16;
@@ -124,6 +127,13 @@ __device__ __forceinline__ void fr_role_sblock(const EkfFrame& fr, int sb, int n
     int bi = 0, bj = sb;
     while (bj > bi) { bj -= bi + 1; ++bi; }
     const int j0 = (16 * bi) / RD, jc0 = (16 * bj) / RD;
+    // Per-detection noise: only the 16 diagonal entries of a diagonal block take a row's variance.  Their loads are issued
+    // here, in front of the index loads, and parked in LDS behind the barrier that follows those (rsd is the residual of
+    // workgroup 0's OTHER role: free in this one), so no round trip stands in front of the emission and nothing stays in a
+    // register across the role.
+    [[maybe_unused]] double rnoise = 0.0;
+    if constexpr (ROWS)
+        if (bi == bj && tid < 16 && 16 * bi + tid < k) rnoise = fr.rrow[16 * bi + tid];
     // Pipelined sequence mode: `cov` is P of the PREVIOUS frame (the covariance update that produces the current P
     // runs beside this launch).  The entries this block needs are completed on the fly,
     //     P_cur[r][c] = (P_prev[r][c] + Q[r == c]) + sum_k fma(-W[k][r], W[k][c]),     k ascending from zero,
@@ -163,6 +173,8 @@ __device__ __forceinline__ void fr_role_sblock(const EkfFrame& fr, int sb, int n
     };
     if (dotw) dot_operands(dtile, 0);      // (they do not depend on the indices: in flight beside the index -> P round trips)
     if (tid < m) lmc[tid] = ekf_lm_column(fr, LMD, tid, false);
+    if constexpr (ROWS)
+        if (bi == bj && tid < 16) rsd[tid] = rnoise;
     __syncthreads();
     // this thread's entry of U (slot, c2): its P values are requested before the measurement model
     // is evaluated, so the two dependent memory round trips overlap
@@ -284,7 +296,9 @@ __device__ __forceinline__ void fr_role_sblock(const EkfFrame& fr, int sb, int n
         } else {
             const double* h1 = hs + r1 * JC;
             const int s1 = EKF_CAM + LMD * (r1 / RD - j0);
-            double acc = (r1 == r2) ? fr.nz.r_unc : 0.0;
+            double acc;
+            if constexpr (ROWS) acc = (r1 == r2) ? rsd[i] : 0.0;
+            else acc = (r1 == r2) ? fr.nz.r_unc : 0.0;
 #pragma unroll
             for (int a = 0; a < EKF_CAM; ++a) acc = __builtin_fma(h1[a], us[a * 16 + c2], acc);
 #pragma unroll
@@ -1320,24 +1334,24 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
 
 // One instantiation per number of 16-row blocks NB = kpad / 16: the forward substitution is unrolled
 // over NB, and a kernel that carried all twelve variants spilled registers.
-template <typename T, int NU, int MODEL, int NB>
+template <typename T, int NU, int MODEL, int NB, bool ROWS>
 __global__ __launch_bounds__(FR_T) void ekf_front_kernel(EkfFrame fr) {
     extern __shared__ __attribute__((aligned(16))) double fr_sm[];
     const int nb = fr.kpad / EKF_RB, nS = nb * (nb + 1) / 2;
     const int bx = blockIdx.x;
     if (bx == 0) fr_role_measure<MODEL>(fr, fr_sm);
-    else if (bx <= nS) fr_role_sblock<T, MODEL, NB>(fr, bx - 1, nS, fr_sm);
+    else if (bx <= nS) fr_role_sblock<T, MODEL, NB, ROWS>(fr, bx - 1, nS, fr_sm);
     else if (bx == nS + 1) fr_role_factor<NB>(fr, fr_sm);
     else fr_role_chunk<T, NU, MODEL, NB>(fr, bx - nS - 2, fr_sm);
 }
 
-template <typename T, int NU, int MODEL, int NB>
-static void ekf_front_go(const EkfFrame& fr, hipStream_t s) {
+template <typename T, int NU, int MODEL, int NB, bool ROWS>
+static void ekf_front_go_rows(const EkfFrame& fr, hipStream_t s) {
     constexpr int LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     constexpr int NSLOT = EKF_CAM + LMD * EkfModel<MODEL>::NDET16;
     static bool once = false;
     if (!once) {   // > 64 KB of dynamic LDS needs the opt-in
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ekf_front_kernel<T, NU, MODEL, NB>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ekf_front_kernel<T, NU, MODEL, NB, ROWS>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         once = true;
     }
@@ -1351,7 +1365,14 @@ static void ekf_front_go(const EkfFrame& fr, hipStream_t s) {
     size_t lds = lds_s > lds_c ? lds_s : lds_c;
     if (lds_f > lds) lds = lds_f;
     if ((size_t)fr.lds_min > lds) lds = (size_t)fr.lds_min;
-    hipLaunchKernelGGL((ekf_front_kernel<T, NU, MODEL, NB>), dim3(nS + 2 + fr.ncols / 64), dim3(FR_T), lds, s, fr);
+    hipLaunchKernelGGL((ekf_front_kernel<T, NU, MODEL, NB, ROWS>), dim3(nS + 2 + fr.ncols / 64), dim3(FR_T), lds, s, fr);
+}
+
+// the instance with or without per-detection noise, by the frame
+template <typename T, int NU, int MODEL, int NB>
+static void ekf_front_go(const EkfFrame& fr, hipStream_t s) {
+    if (fr.rrow) ekf_front_go_rows<T, NU, MODEL, NB, true>(fr, s);
+    else ekf_front_go_rows<T, NU, MODEL, NB, false>(fr, s);
 }
 
 template <typename T>

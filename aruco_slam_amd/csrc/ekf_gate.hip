@@ -54,7 +54,8 @@ __global__ __launch_bounds__(EKF_GATE_THREADS) void ekf_frame_gate_kernel(const 
             double out = __builtin_nan("");
             if (!dead) {
                 double d2;
-                const bool ok = ekf_gate_distance<MODEL>(a.nz.r_unc, scr + (size_t)tid * SCR, d2);
+                const bool ok = ekf_gate_distance<MODEL>(a.nz.r_unc, a.rows ? a.rows + (size_t)(d0 + tid) * RD : nullptr,
+                                                            scr + (size_t)tid * SCR, d2);
                 const bool exempt = a.exempt && a.exempt[d0 + tid] != 0;
                 out = exempt ? 0.0 : ok ? d2 : __builtin_nan("");
                 bad = !exempt && !ok;
@@ -70,6 +71,8 @@ __global__ __launch_bounds__(EKF_GATE_THREADS) void ekf_frame_gate_kernel(const 
                 const int pos = base + __popcll(mask & ((1ull << tid) - 1ull));
                 a.out_idx[pos] = a.idx[d0 + tid];
                 for (int r = 0; r < RD; ++r) a.out_z[(size_t)pos * RD + r] = a.z[(size_t)(d0 + tid) * RD + r];
+                if (a.rows)
+                    for (int r = 0; r < RD; ++r) a.out_rows[(size_t)pos * RD + r] = a.rows[(size_t)(d0 + tid) * RD + r];
             }
             base += __popcll(mask);
         }

@@ -1,7 +1,7 @@
 // Per-detection chi-square distance: the arithmetic of ONE detection, shared by the single filter's gate kernel
 // (ekf_gate.hip) and the batch's gate stage (ekf_batch_impl.h: ekf_batch_gate).  For a detection of landmark columns
 // c0 .. c0 + LMD - 1, on the prior P with N state dimensions:
-//   r = z - h(x), S_d = H_d (P+Q) H_d^T + R I [RD, RD] from the (10 + LMD)^2 support block of P,
+//   r = z - h(x), S_d = H_d (P+Q) H_d^T + R I (or + diag(rows_d)) [RD, RD] from the (10 + LMD)^2 support block of P,
 //   S_d = L L^T and d^2 = |L^-1 r|^2, every sum one ascending fma chain, all of it in f64.
 // Three stages, each one thread's work on the detection's scratch; the caller owns the threads, the barriers between the
 // stages, where z comes from, who is exempt and what a distance decides.  The stages touch nothing but their arguments, so
@@ -56,7 +56,9 @@ __device__ __forceinline__ void ekf_gate_project(const T* P, int64_t ld, int c0,
 
 // Stage 3, one thread per detection, behind a barrier after stage 2: S_d, its factor and d^2.  Returns whether every
 // pivot was positive and finite; only then is d2 the distance.
-template <int MODEL> __device__ __forceinline__ bool ekf_gate_distance(double r_unc, double* scr, double& d2) {
+// rows: the variances of the detection's RD measurement rows (per-detection noise), or null: r_unc on every row.
+template <int MODEL>
+__device__ __forceinline__ bool ekf_gate_distance(double r_unc, const double* rows, double* scr, double& d2) {
     using G = EkfGateScratch<MODEL>;
     constexpr int RD = G::RD, JC = G::JC;
     const double* Jd = scr + G::J;
@@ -71,7 +73,7 @@ template <int MODEL> __device__ __forceinline__ bool ekf_gate_distance(double r_
             double acc = 0.0;
 #pragma unroll 4
             for (int ci = 0; ci < JC; ++ci) acc = fma(Td[r * JC + ci], Jd[rr * JC + ci], acc);
-            Sd[r * RD + rr] = acc + (r == rr ? r_unc : 0.0);
+            Sd[r * RD + rr] = acc + (r == rr ? (rows ? rows[r] : r_unc) : 0.0);
         }
     // S_d = L L^T row by row (L_ii on the diagonal) with y = L^-1 r behind each row; d^2 = y^T y
     bool ok = true;

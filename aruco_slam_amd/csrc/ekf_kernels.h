@@ -33,7 +33,11 @@ struct EkfFrame {
     int64_t lda;
     double* sblk;          // S = Hs (P+Q)[supp,supp] Hs^T + R in 16x16 blocks (lower block triangle), block (i, tc) at
                            // (i (i + 1) / 2 + tc) * 256 in OP memory order (ekf_solve_device.h); diagonal blocks symmetric
-    int32_t sblk_rows;     // (unused)
+    // Per-detection measurement noise (EKF_FLAG_ROW_NOISE; include/ekf_slam_hip.h): the variance of every measurement row of
+    // the frame, [k] in the order of z (device, or pinned host), S = H (P+Q) H^T + diag(rrow); null: the constant nz.r_unc.
+    // (It takes the eight bytes of a retired int32 and the padding behind it: every other argument is where it was, and
+    // the kernel arguments keep their size.)
+    const double* rrow;
     double* lmat;          // Cholesky factor L of S, [kmax, ldl] f64 (lower)
     int32_t ldl;
     double* dinv;          // inverse of the 16x16 diagonal blocks of L, [kmax/16,16,16]
@@ -111,6 +115,9 @@ struct EkfFrame {
     const uint32_t* cov_tiles;
     int32_t cov_grid;
 };
+
+// variance of measurement row r: the one thing of a frame the rows change (the diagonal of S)
+__device__ __forceinline__ double ekf_row_noise(const EkfFrame& fr, int r) { return fr.rrow ? fr.rrow[r] : fr.nz.r_unc; }
 
 // raise sticky status bits (and tell the host mirror, if there is one, that the status word is no longer zero)
 __device__ __forceinline__ void ekf_raise(const EkfFrame& fr, int bits) {
@@ -242,6 +249,8 @@ struct EkfGateArgs {
     double* mahal_host;         // [m] pinned host or null: the same values for a host caller
     int32_t* out_idx;           // [<= m] indices of the survivors, in log order
     double* out_z;              // [<= m, rd]
+    const double* rows;         // [m, rd] or null: per-detection noise, the variances of every detection's rows
+    double* out_rows;           // [<= m, rd]: the survivors' rows (rows != null)
     int32_t* status;            // the filter's status words ([0] != 0: nothing is tested any more, everything stays)
     int32_t* status_host;       // pinned mirror of "the status word is no longer zero", or null
     int32_t* result_host;       // pinned: [0] survivors (what the host waits for), [1] some pivot failed (diagnostic only: the
@@ -278,6 +287,7 @@ struct EkfBatchWindow {
     int32_t kmax, lda;              // LDS layout: rows of A / W, row length of A / W (> N; column N holds the residual)
     const double* gate;             // [B] or null: chi^2 gate on every detection's own d^2 (+inf: off); ekf_batch_gate
     double* mahal;                  // [D] or null: d^2 per detection (0: exempt first sighting, NaN: not tested)
+    const double* row_noise;        // [D][RD] or null: per-detection noise, indexed like lm_index (null: the member's r_uncertainty)
 };
 // dynamic LDS of one launch (C linkage: the tests read them)
 extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);

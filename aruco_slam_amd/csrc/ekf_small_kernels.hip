@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void ekf_gather_kernel(EkfFrame fr) {
             } else {
                 const double* h1 = hs + r1 * JC;
                 const int s1 = EKF_CAM + LMD * (r1 / RD - j0);
-                double acc = (r1 == r2) ? fr.nz.r_unc : 0.0;
+                double acc = (r1 == r2) ? ekf_row_noise(fr, r1) : 0.0;
 #pragma unroll
                 for (int a = 0; a < EKF_CAM; ++a) acc = __builtin_fma(h1[a], us[a * 16 + c2], acc);
 #pragma unroll

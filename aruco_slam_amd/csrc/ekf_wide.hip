@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void ekf_wide_s_kernel(EkfFrame fr) {
         const double* ar = fr.amat + (int64_t)r1 * fr.lda;
         const double* h2 = fr.jac + (size_t)r2 * EKF_JLD;
         const int c20 = fr.lmcol[r2 / RD];
-        double acc = (r1 == r2) ? fr.nz.r_unc : 0.0;
+        double acc = (r1 == r2) ? ekf_row_noise(fr, r1) : 0.0;
 #pragma unroll
         for (int b = 0; b < JC; ++b) acc = __builtin_fma(ar[(b < EKF_CAM) ? b : c20 + (b - EKF_CAM)], h2[b], acc);
         v = acc;

@@ -200,12 +200,15 @@ class BaseFilter:
             ids, detected_poses, should_filter, iteration)
         return frame, camera_pose, marker_poses, detected_poses
 
-    def process_detections(self, ids, detected_poses, should_filter=True, iteration=0):
+    def process_detections(self, ids, detected_poses, should_filter=True, iteration=0, noise=None):
         """The part of ``process_frame`` behind the detector
         (base_filter.py:196-212): ``ids`` is None for a frame without
-        detections, in which case the filter is NOT stepped (no predict)."""
+        detections, in which case the filter is NOT stepped (no predict).  ``noise``: the frame's per-detection
+        measurement noise, as ``observe`` takes it (a filter built with ``row_noise=True``)."""
         if ids is None:
             detected_poses = np.array([])
+        elif should_filter and noise is not None:
+            self.observe(ids, detected_poses, noise=noise)
         elif should_filter:
             self.observe(ids, detected_poses)
         if should_filter and self._tentative is not None:
@@ -282,13 +285,25 @@ class BaseFilter:
                 out[j] = True
         return out
 
-    def _observe_gated(self, index, z, exempt) -> None:
+    def _frame_noise(self, noise, count: int):
+        """``noise=`` of ``observe``: None, or the frame's row variances [count, rd] from [count] (one variance per
+        detection, broadcast over its rows) or [count, rd].  ``ValueError`` for anything else, for an entry that is not
+        finite and > 0, and for a filter built without ``row_noise=True``; checked before the frame changes anything."""
+        if noise is None:
+            return None
+        from ..hip_backend import row_noise_array
         backend = self.backend
-        d2 = backend.observe(index, z, exempt=exempt, mahal=True)
+        if not backend.can_row_noise:
+            raise ValueError("noise= needs a filter built with row_noise=True")
+        return row_noise_array(noise, count, backend.rows_per_detection)
+
+    def _observe_gated(self, index, z, exempt, rows=None) -> None:
+        backend = self.backend
+        d2 = backend.observe(index, z, exempt=exempt, mahal=True, rows=rows)
         self.last_mahal = d2
         self.last_rejected = d2 > backend.gate      # (NaN and 0 compare false; gate inf: nothing)
 
-    def process_detection_log(self, ids, poses, offsets, has_detections=None, mahal=False):
+    def process_detection_log(self, ids, poses, offsets, has_detections=None, mahal=False, noise=None):
         """``process_detections(ids_t, poses_t)`` with ``should_filter=True`` for every frame of a recorded log, in ONE call
         that runs predict / update of every frame on the device (ekf_observe_log).  The log is a CSR batch as in a replay
         file (``main/run_slam.py: detection_frames``): ``ids [D]``, ``poses [D,6]`` ``[tvec | rvec]`` (NumPy, or a
@@ -299,7 +314,8 @@ class BaseFilter:
         filter (``landmarks`` included) is left as it was.  A gate that is set (``set_gate``) acts on every frame, with
         the first occurrence of every marker the log adds exempt; ``mahal=True`` (a filter built with ``gate=``) returns
         ``(trajectory, d2 [D])`` with every detection's squared Mahalanobis distance, indexed like ``ids`` (NaN for the
-        rows of frames without detections), gate or no gate; ``d2 > gate`` are the rejected ones."""
+        rows of frames without detections), gate or no gate; ``d2 > gate`` are the rejected ones.  ``noise``: per-detection
+        measurement noise of the log, [D] or [D, rd] aligned with ``ids`` (a filter built with ``row_noise=True``)."""
         import torch
         backend = self.backend
         plan = plan_detection_log(self.landmarks, self.num_landmarks, ids, offsets, has_detections)
@@ -312,6 +328,9 @@ class BaseFilter:
             poses = np.asarray(poses, dtype=np.float64)
         if tuple(poses.shape) != (plan.keep.shape[0], 6):
             raise ValueError(f"poses must have shape ({plan.keep.shape[0]}, 6), got {tuple(poses.shape)}")
+        rows = self._frame_noise(noise, plan.keep.shape[0])
+        if rows is not None:
+            rows = rows[plan.keep]
         if not plan.keep.all():      # (rows of frames without detections, if there are any, are not part of the replay)
             poses = poses[torch.from_numpy(plan.keep).to(poses.device)] if isinstance(poses, torch.Tensor) else poses[plan.keep]
         if isinstance(poses, torch.Tensor):
@@ -322,7 +341,7 @@ class BaseFilter:
             backend.grow(new_max_visible=min(backend.MAX_VISIBLE_LIMIT[backend.lm_dims], plan.widest))
         traj = torch.empty((plan.offsets.shape[0] - 1, 7), dtype=torch.float64, device=backend.device)
         mahal_t = torch.empty((plan.index.shape[0],), dtype=torch.float64, device=backend.device) if mahal else None
-        backend.observe_log(plan.index, plan.offsets, poses, traj, mahal_t)
+        backend.observe_log(plan.index, plan.offsets, poses, traj, mahal_t, rows)
         backend.sync()
         self.landmarks.update(plan.new_landmarks)
         self.num_landmarks = plan.num_landmarks
@@ -386,19 +405,23 @@ class BaseFilter:
         np.savez(filename, state=np.asarray(self.state, dtype=np.float64),
                  cov=np.asarray(self.uncertainty, dtype=np.float64),
                  marker_ids=np.asarray(ids, dtype=np.int64), filter=type(self).__name__,
-                 gate=np.float64(np.inf if gate is None else gate))
+                 gate=np.float64(np.inf if gate is None else gate), row_noise=np.bool_(self.backend.can_row_noise))
 
     def load_checkpoint(self, filename: str) -> None:
         """Inverse of ``save_checkpoint`` on a filter of the same class; the device covariance
         is overwritten bit-for-bit when the stored values fit the covariance dtype.  The gate is part of the checkpoint: a
         filter built with ``gate=`` takes the stored one, so a checkpoint saved without a gate (stored as ``inf``) switches
         this filter's gate OFF -- call ``set_gate`` afterwards to keep your own; a stored finite gate needs a filter built
-        with ``gate=`` (``ValueError`` otherwise).  Checkpoints from before the gate leave it as it is."""
+        with ``gate=`` (``ValueError`` otherwise).  Checkpoints from before the gate leave it as it is.  A checkpoint of a
+        filter built with ``row_noise=True`` needs one built the same way (``ValueError`` otherwise)."""
         with np.load(filename, allow_pickle=False) as ck:
             if str(ck["filter"]) != type(self).__name__:
                 raise ValueError(f"checkpoint of {ck['filter']} loaded into {type(self).__name__}")
             state, cov, ids = ck["state"], ck["cov"], ck["marker_ids"]
             gate = float(ck["gate"]) if "gate" in ck.files else None      # (checkpoints from before the gate: as it is)
+            row_noise = bool(ck["row_noise"]) if "row_noise" in ck.files else False
+        if row_noise and not self.backend.can_row_noise:
+            raise ValueError("the checkpoint is of a filter with per-detection noise: build this one with row_noise=True")
         if gate is not None and (np.isfinite(gate) or self.backend.can_gate):
             self.set_gate(gate)      # (a finite gate needs a filter built with gate=: ValueError otherwise)
         if len(ids) == 0:
@@ -411,7 +434,7 @@ class BaseFilter:
             self._tentative.confirm(self.landmarks)
 
     # -- abstract back-end API, base_filter.py:327-381 ------------------------
-    def observe(self, ids, poses) -> None:
+    def observe(self, ids, poses, noise=None) -> None:
         raise NotImplementedError(NOT_IMPLEMENTED_ERROR)
 
     def get_poses(self):

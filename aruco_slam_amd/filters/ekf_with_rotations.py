@@ -46,14 +46,15 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
     def __init__(self, initial_camera_pose, *, max_landmarks: int | None = None, max_visible: int | None = None,
                  cov_dtype: str = "float64", cov_kernel: str = "auto", device: str = "cuda:0",
                  lookahead: bool | None = None, fused: bool = True, noise: dict | None = None,
-                 gate: float | None = None, confirm: tuple | None = None) -> None:
+                 gate: float | None = None, confirm: tuple | None = None, row_noise: bool = False) -> None:
         """``noise``: values that replace the module's noise constants, keyed by the ``ekf_config`` field names
         (``initial_camera_uncertainty``, ``initial_landmark_uncertainty``, ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``);
         None keeps the reference's constants.  ``gate``: the chi-square gate on every detection's own Mahalanobis
         distance (``set_gate``; 7 degrees of freedom, approximate: 14.067 / 18.475 / 24.322 for 95 / 99 / 99.9 %);
         ``inf``: off, but the distances are reported (``last_mahal``); None: a filter without the gate.
         ``confirm``: ``(hits, window)`` = a new landmark must be used again in ``hits`` later frames within ``window``
-        frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off."""
+        frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off.
+        ``row_noise``: the filter takes per-detection measurement noise (``observe(..., noise=)``)."""
         super().__init__(initial_camera_pose, None)
         self._initial_pose = np.array(initial_camera_pose)
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -74,7 +75,7 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         constants.update(noise or {})
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype, quat_mode="scalar_first",
                            cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
-                           model="ekf_rotations", noise=constants, gate=gate)
+                           model="ekf_rotations", noise=constants, gate=gate, row_noise=row_noise)
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._init_confirm(confirm)
 
@@ -89,7 +90,10 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         return self._hip.get_cov()
 
     # -- :66-90 ----------------------------------------------------------------
-    def observe(self, ids, poses) -> None:
+    def observe(self, ids, poses, noise=None) -> None:
+        """``noise`` (a filter built with ``row_noise=True``): the frame's measurement noise, [m] (one variance per
+        detection) or [m, 7] (x y z, then qw qx qy qz, the order of z) instead of ``r_uncertainty``; anything else raises
+        ``ValueError`` before the frame changes anything."""
         if isinstance(ids, np.ndarray) and ids.dtype.kind in "iu":
             ids = ids.reshape(-1).tolist()
         else:
@@ -97,6 +101,7 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         if not ids:
             raise ValueError("observe() needs at least one detection")
         poses = np.asarray(poses, dtype=np.float64).reshape(len(ids), -1)
+        rows = self._frame_noise(noise, len(ids))
         known = self.landmarks
         try:                                   # steady state: every marker of the frame is in the map already
             index = [known[i] for i in ids]
@@ -114,11 +119,11 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
             index = [known[i] for i in ids]
             if self._hip.can_gate:      # the markers added just now are exempt from the gate (their z = h by construction)
                 z = np.hstack((poses[:, XYZ_DIMS], euler_xyz_to_quat(poses[:, 3:6])))
-                return self._observe_gated(index, z, self._first_occurrences(ids, fresh))
+                return self._observe_gated(index, z, self._first_occurrences(ids, fresh), rows)
         z = np.hstack((poses[:, XYZ_DIMS], euler_xyz_to_quat(poses[:, 3:6])))      # :216-224
         if self._hip.can_gate:
-            return self._observe_gated(index, z, None)
-        self._hip.observe(index, z)
+            return self._observe_gated(index, z, None, rows)
+        self._hip.observe(index, z, rows=rows)
 
     # -- :275-335 --------------------------------------------------------------
     def add_marker(self, idx, pose, uncertainity=None) -> None:

@@ -36,7 +36,8 @@ class EKF(BaseFilter):
                  max_visible: int | None = None, cov_dtype: str = "float64",
                  quat_update: str = "as_written", cov_kernel: str = "auto",
                  device: str = "cuda:0", map_file=None, lookahead: bool | None = None,
-                 fused: bool = True, noise: dict | None = None, gate: float | None = None, confirm: tuple | None = None) -> None:
+                 fused: bool = True, noise: dict | None = None, gate: float | None = None, confirm: tuple | None = None,
+                 row_noise: bool = False) -> None:
         """Positional arguments as the reference (:40-43).  Keyword-only extras:
         initial capacity (default: the number of ids of ``aruco_dict`` -- DICT_5X5_50
         has 50, base_filter.py:81-82; the buffers grow when more markers or more
@@ -50,7 +51,8 @@ class EKF(BaseFilter):
         freedom: 7.815 / 11.345 / 16.266 for 95 / 99 / 99.9 %); ``inf``: off, but the distances are reported
         (``last_mahal``); None: a filter without the gate.
         ``confirm``: ``(hits, window)`` = a new landmark must be used again in ``hits`` later frames within ``window``
-        frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off."""
+        frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off.
+        ``row_noise``: the filter takes per-detection measurement noise (``observe(..., noise=)``)."""
         super().__init__(initial_camera_pose, map_file, aruco_dict)
         self._initial_pose = np.array(initial_camera_pose)      # :46, dtype kept
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -71,7 +73,7 @@ class EKF(BaseFilter):
         constants.update(noise or {})
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype,
                            quat_mode=quat_update, cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
-                           noise=constants, gate=gate)
+                           noise=constants, gate=gate, row_noise=row_noise)
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._load_initial_map()
         self._init_confirm(confirm)
@@ -90,9 +92,11 @@ class EKF(BaseFilter):
         return self._hip.get_cov()
 
     # -- :58-82 ----------------------------------------------------------------
-    def observe(self, ids, poses) -> None:
+    def observe(self, ids, poses, noise=None) -> None:
         """Add unseen markers, predict, update.  ``ids``: iterable of marker
-        ids; ``poses``: (m, 6) ``[tvec | rvec]``, only ``pose[0:3]`` is used."""
+        ids; ``poses``: (m, 6) ``[tvec | rvec]``, only ``pose[0:3]`` is used.  ``noise`` (a filter built with
+        ``row_noise=True``): the frame's measurement noise, [m] (one variance per detection) or [m, 3] (x, y, z in the
+        camera frame) instead of ``r_uncertainty``; anything else raises ``ValueError`` before the frame changes anything."""
         if isinstance(ids, np.ndarray) and ids.dtype.kind in "iu":
             ids = ids.reshape(-1).tolist()     # (what process_frame passes: ids.flatten(), base_filter.py:199)
         else:
@@ -100,6 +104,7 @@ class EKF(BaseFilter):
         if not ids:
             raise ValueError("observe() needs at least one detection")
         poses = np.asarray(poses, dtype=np.float64).reshape(len(ids), -1)
+        rows = self._frame_noise(noise, len(ids))
         known = self.landmarks
         try:                                   # steady state: every marker of the frame is in the map already
             index = [known[i] for i in ids]
@@ -117,10 +122,10 @@ class EKF(BaseFilter):
                 self.num_landmarks += 1
             index = [known[i] for i in ids]
             if self._hip.can_gate:      # the markers added just now are exempt from the gate (their z = h by construction)
-                return self._observe_gated(index, poses[:, XYZ_DIMS], self._first_occurrences(ids, fresh))
+                return self._observe_gated(index, poses[:, XYZ_DIMS], self._first_occurrences(ids, fresh), rows)
         if self._hip.can_gate:
-            return self._observe_gated(index, poses[:, XYZ_DIMS], None)
-        self._hip.observe(index, poses[:, XYZ_DIMS])
+            return self._observe_gated(index, poses[:, XYZ_DIMS], None, rows)
+        self._hip.observe(index, poses[:, XYZ_DIMS], rows=rows)
 
     # -- :239-290 --------------------------------------------------------------
     def add_marker(self, idx, pose, uncertainity=None) -> None:

@@ -57,6 +57,13 @@ def detection_frames(path: str):
         yield float(det["timestamps_ms"][f]), ids, det["poses"][sl]
 
 
+def detection_noise(path: str):
+    """The optional ``noise`` array of a replay file: per-detection measurement noise, [sum m] (one variance per detection)
+    or [sum m, RD] (one per measurement row), aligned with ``ids``; None for a file without one."""
+    det = np.load(path, allow_pickle=False)
+    return np.asarray(det["noise"], dtype=np.float64) if "noise" in det.files else None
+
+
 def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryWriter) -> None:
     """The whole replay file through ``process_detection_log``, then one trajectory line per frame.  Frames before the first
     stepped one carry the camera pose the filter had before the call (the integer initial pose of a fresh filter), as the
@@ -64,7 +71,11 @@ def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryW
     det = np.load(path, allow_pickle=False)
     offsets, has = det["offsets"], det["has_detections"].astype(bool)
     start_pose = tracker.get_poses()[0]
-    traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has)
+    noise = detection_noise(path)
+    if noise is None:
+        traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has)
+    else:
+        traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has, noise=noise)
     stepped = has & (np.diff(offsets) > 0)
     first = int(np.argmax(stepped)) if stepped.any() else len(has)
     for f, timestamp in enumerate(det["timestamps_ms"]):
@@ -80,6 +91,9 @@ def main(cmdline_args: argparse.Namespace) -> None:
         if getattr(cmdline_args, "resident", False):
             raise ValueError("--confirm prunes between frames: it does not go with --resident (one device call for the log)")
         kwargs["confirm"] = cmdline_args.confirm      # (with or without --gate)
+    noise = detection_noise(cmdline_args.detections) if cmdline_args.detections else None
+    if noise is not None:
+        kwargs["row_noise"] = True      # (the file carries per-detection noise: frame loop and resident replay use it)
     tracker = init_tracker(cmdline_args.filter, initial_pose, **kwargs)
     out_dir = Path(getattr(cmdline_args, "output_dir", "outputs"))
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -91,8 +105,12 @@ def main(cmdline_args: argparse.Namespace) -> None:
         if resident:
             replay_resident(tracker, cmdline_args.detections, cam_traj_writer)
         elif cmdline_args.detections:
-            for timestamp, ids, poses in detection_frames(cmdline_args.detections):
-                _, camera_pose, _, _ = tracker.process_detections(ids, poses)
+            offs = np.load(cmdline_args.detections, allow_pickle=False)["offsets"]
+            for f, (timestamp, ids, poses) in enumerate(detection_frames(cmdline_args.detections)):
+                if noise is None or ids is None:
+                    _, camera_pose, _, _ = tracker.process_detections(ids, poses)
+                else:
+                    _, camera_pose, _, _ = tracker.process_detections(ids, poses, noise=noise[int(offs[f]):int(offs[f + 1])])
                 cam_traj_writer.write(timestamp, camera_pose)
         else:
             if cv2 is None:

@@ -56,6 +56,8 @@ enum { EKF_FLAG_BATCH_LARGE_MAPS = 16 };
 enum { EKF_FLAG_BATCH_WIDE_FRAMES = 32 };
 /* ekf_config.flags bit 6, read by ekf_* (the single filter) only: the per-detection chi-square gate (ekf_set_gate) */
 enum { EKF_FLAG_GATE = 64 };
+/* ekf_config.flags bit 7, read by ekf_* (the single filter) only: per-detection measurement noise (ekf_observe_rows) */
+enum { EKF_FLAG_ROW_NOISE = 128 };
 enum { EKF_COVK_AUTO = 0, EKF_COVK_VALU = 1, EKF_COVK_MFMA = 2, EKF_COVK_MFMA_TILE = 3, EKF_COVK_MFMA_MACRO = 4 };
 
 enum {
@@ -96,7 +98,12 @@ typedef struct ekf_config {
                              * see ekf_batch_query_sizes.
                              * bit 6 (EKF_FLAG_GATE): the filter can gate its detections (ekf_set_gate); the workspace
                              * then also holds the survivors of a frame and its distances (ekf_query_sizes: + 68
-                             * max_visible bytes and change).  Without it, sizes, layout and results are as before. */
+                             * max_visible bytes and change).  Without it, sizes, layout and results are as before.
+                             * bit 7 (EKF_FLAG_ROW_NOISE): the filter takes per-detection measurement noise
+                             * (ekf_observe_rows); with bit 6 the workspace then also holds the survivors' rows of a
+                             * gated frame (ekf_query_sizes: + 8 rd max_visible bytes, padded to 256; without bit 6
+                             * the size does not change: host rows are staged in pinned memory, device rows are read
+                             * where they are).  Without it, sizes, layout and results are as before. */
     /* noise constants, defaults = extended_kalman_filter.py:21-27 */
     double initial_camera_uncertainty;   /* 0.1  */
     double initial_landmark_uncertainty; /* 0.7  */
@@ -509,6 +516,51 @@ int ekf_observe_log_gated(ekf_filter *f, const int32_t *lm_index, const int64_t 
                           const double *poses_dev, void *log_ws, size_t log_ws_bytes, double *trajectory_dev,
                           double *mahal_dev /* [D] or NULL */);
 int ekf_last_gate_stats(const ekf_filter *f, int64_t out[2]);
+
+/* ---- Per-detection measurement noise (heteroscedastic R; ekf_config.flags bit 7, EKF_FLAG_ROW_NOISE for the single filter;
+ * a batch needs no flag).  Every update forms S = H (P+Q) H^T + r_uncertainty I.  With rows it forms
+ *     S = H (P+Q) H^T + diag(rows)
+ * Semantics (part of the ABI):
+ *   1. Detection d of a frame may carry rows[d][0 .. rd-1], the variances of its rd measurement rows in the order of z:
+ *      x y z in the camera frame (EKF, rd = 3), then qw qx qy qz (EKF_MODEL_ROTATIONS, rd = 7).  Nothing else of the frame
+ *      changes.  The per-detection S_d of the gate (rule 2 there) uses the same rows.
+ *   2. Rows are data of the frame, like z; they are not state of the handle.  rows = NULL is the call without rows: the same
+ *      code path, the same bits.  First sightings are added as before (initial_landmark_uncertainty).
+ *   3. Rows all equal to c, whatever the filter's r_uncertainty, give bit for bit the plain call on a filter configured with
+ *      r_uncertainty = c: state, P, trajectory and d^2; every path, model and covariance dtype.
+ *   4. Gate and rows compose: a gated frame with rows is bit for bit the ungated call on the survivors with the survivors'
+ *      rows (the gate kernel compacts the rows together with lm_index and z).
+ *   5. Host-pointer entry points reject a row that is NaN, Inf or <= 0 with EKF_ERR_INVALID before anything is enqueued.
+ *      Device arrays are the caller's contract: an S they make non-positive-definite fails as without rows
+ *      (EKF_ERR_NUMERIC, sticky).
+ *   6. Every rule of the calls they extend holds with rows present: the EKF log replay is bitwise the per-frame loop, the
+ *      pipelined sequence is bitwise the serial order, batch large-map and wide-frame kernels are bitwise the one-column
+ *      kernel where both run.
+ * rows given to a filter created without EKF_FLAG_ROW_NOISE: EKF_ERR_STATE.
+ * ekf_observe_rows: ekf_observe_gated with rows [m, rd] HOST or NULL.  Usable without EKF_FLAG_GATE when exempt and mahal
+ *   are NULL (survivors, if given, is then m).
+ * ekf_observe_sequence_device_rows: ekf_observe_sequence_device with rows_dev [frames, m, rd] DEVICE or NULL; pipelined
+ *   where that call would be.
+ * ekf_observe_log_rows: ekf_observe_log_gated with rows_dev [D, rd] DEVICE or NULL, indexed like lm_index; with no gate set
+ *   and mahal_dev NULL the runs pipeline as ekf_observe_log plans them.
+ * ekf_batch_observe_logs_rows: ekf_batch_observe_logs_gated with rows_dev [D, rd] DEVICE or NULL, indexed like lm_index;
+ *   valid for the one-column, large-map and wide-frame kernels; nis, cam_cov and mahal stay available.  The batch workspace
+ *   does not change, so a batch takes rows without a flag.
+ * The replica entry points (ekf_batch_observe_replicas*, ekf_batch_observe_corner_replicas) keep the constant
+ * r_uncertainty of their members. */
+int ekf_observe_rows(ekf_filter *f, const int32_t *lm_index, const double *z, const double *rows /* [m, rd] host or NULL */,
+                     int32_t m, const uint8_t *exempt /* [m] or NULL */, double *mahal /* [m] host or NULL */,
+                     int32_t *survivors /* or NULL */);
+int ekf_observe_sequence_device_rows(ekf_filter *f, const int32_t *lm_index_dev, const double *z_dev,
+                                     const double *rows_dev /* [frames, m, rd] or NULL */, int32_t m, int32_t frames,
+                                     double *trajectory_dev);
+int ekf_observe_log_rows(ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames,
+                         const double *poses_dev, const double *rows_dev /* [D, rd] or NULL */, void *log_ws,
+                         size_t log_ws_bytes, double *trajectory_dev, double *mahal_dev /* [D] or NULL */);
+int ekf_batch_observe_logs_rows(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets,
+                                const int64_t *member_frames, const double *poses_dev,
+                                const double *rows_dev /* [D, rd] or NULL */, void *log_ws, size_t log_ws_bytes,
+                                double *trajectory_dev, double *nis_dev, double *cam_cov_dev, double *mahal_dev);
 
 /* ---- Landmark removal (map pruning).  Deleting landmarks from a Gaussian is marginalisation: their rows and columns of P
  * and their entries of the state go, nothing else changes.  The calling pattern is that of ekf_grow at unchanged capacity:

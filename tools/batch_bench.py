@@ -74,6 +74,9 @@ def main():
                     help="chi-square gate of every member (EKFBatch(gate=X)); 1e300 tests every detection and rejects none. "
                          "With a gate the wall times include the copy of mahal and the host's rejected / dof bookkeeping: "
                          "compare window-kernel times of a rocprofv3 kernel trace, not wall_s")
+    ap.add_argument("--row-noise", action="store_true",
+                    help="also time the same logs with per-detection noise (EKFBatch(row_noise=True), log-uniform rows in "
+                         "[0.3, 3]) and report its frames/s beside the figure without")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.batch import EKFBatch
@@ -119,6 +122,21 @@ def main():
                 "steady_frames": args.steady, **({} if args.gate is None else {"gate": args.gate}),
                 "wall_s": round(wall, 6), "aggregate_frames_per_s": round(rate, 1),
                 "single_filter_frames_per_s": round(single, 1), "ratio": round(rate / single, 2)}
+        if args.row_noise:
+            rd, rng = (7 if rot else 3), np.random.default_rng(99)
+            noisy = [tuple(dict(part, noise=np.exp(rng.uniform(np.log(0.3), np.log(3.0), (len(part["ids"]), rd))))
+                           for part in lg) for lg in logs[:B]]
+            rows = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model, row_noise=True,
+                            large_maps=True if args.large_maps else None, **({} if args.gate is None else {"gate": args.gate}))
+            rows.process_detection_logs([lg[0] for lg in noisy])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rows.process_detection_logs([lg[1] for lg in noisy])
+            wall_rows = time.perf_counter() - t0
+            assert rows.status() == [0] * B
+            line["row_noise_wall_s"] = round(wall_rows, 6)
+            line["row_noise_frames_per_s"] = round(B * args.steady / wall_rows, 1)
+            del rows
         if args.large_maps or batch.wide_frames:     # every stepped frame reads and writes the member's N x N f64 covariance
             # once (wide frames: once per block)
             dims = (10 if rot else 3) * n + 10

@@ -11,6 +11,7 @@ updates/s is steady frames per second of the steady segment; the bootstrap segme
     python tools/replay_bench.py --n 256 --m 8 24 --steady 2000 --dtype float64       # C2-like
     python tools/replay_bench.py --gate 1e300      # every frame through the gate kernel, nothing rejected: the price of
                                                    # the host round trip per frame and of losing the pipelined mode
+    python tools/replay_bench.py --row-noise       # every detection with its own row variances (log-uniform in [0.3, 3])
 """
 from __future__ import annotations
 
@@ -35,7 +36,7 @@ def _segment(log, t0, t1):
 
 def _filter(args):
     from aruco_slam_amd.filters.extended_kalman_filter import EKF
-    return EKF(INIT, max_landmarks=args.n, max_visible=args.m[1], cov_dtype=args.dtype, gate=args.gate)
+    return EKF(INIT, max_landmarks=args.n, max_visible=args.m[1], cov_dtype=args.dtype, gate=args.gate, row_noise=args.row_noise)
 
 
 def main():
@@ -47,6 +48,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--variants", default="per_frame,log,sequence")
     ap.add_argument("--gate", type=float, default=None, help="chi-square gate on every detection (default: a filter without)")
+    ap.add_argument("--row-noise", action="store_true", help="per-detection measurement noise on every detection (noise=)")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.synthetic import SyntheticStream, ragged_log
@@ -55,7 +57,15 @@ def main():
     boot = log["bootstrap_frames"]
     frames = len(log["has_detections"])
     m_steady = np.diff(log["offsets"])[boot:]
+    noise = None
+    if args.row_noise:
+        noise = np.exp(np.random.default_rng(args.seed + 7).uniform(np.log(0.3), np.log(3.0), (len(log["ids"]), 3)))
+
+    def seg_noise(t0, t1):
+        return {} if noise is None else {"noise": noise[int(log["offsets"][t0]):int(log["offsets"][t1])]}
+
     common = {"n": args.n, "m_range": list(args.m), "m_mean": float(m_steady.mean()), "dtype": args.dtype, "gate": args.gate,
+              "row_noise": bool(args.row_noise),
               "bootstrap_frames": boot, "steady_frames": args.steady}
 
     def emit(**kv):
@@ -71,7 +81,7 @@ def main():
             def run(t0, t1):
                 for t in range(t0, t1):
                     sl = slice(int(offs[t]), int(offs[t + 1]))
-                    flt.process_detections(log["ids"][sl], log["poses"][sl])
+                    flt.process_detections(log["ids"][sl], log["poses"][sl], **({} if noise is None else {"noise": noise[sl]}))
             t = time.perf_counter()
             run(0, boot)
             b.sync()
@@ -84,11 +94,11 @@ def main():
             emit(variant=variant, updates_per_s=rates[variant], steady_s=t_steady, bootstrap_s=t_boot)
         elif variant == "log":
             t = time.perf_counter()
-            flt.process_detection_log(*_segment(log, 0, boot))
+            flt.process_detection_log(*_segment(log, 0, boot), **seg_noise(0, boot))
             t_boot = time.perf_counter() - t
             boot_stats = b.last_log_stats()
             t = time.perf_counter()
-            flt.process_detection_log(*_segment(log, boot, frames))
+            flt.process_detection_log(*_segment(log, boot, frames), **seg_noise(boot, frames))
             t_steady = time.perf_counter() - t
             st = b.last_log_stats()
             rates[variant] = args.steady / t_steady
@@ -106,9 +116,13 @@ def main():
             ids, zs = zip(*stream.steady(args.steady))
             idx_t = torch.from_numpy(np.stack(ids).astype(np.int32)).to(b.device)
             z_t = torch.from_numpy(np.stack(zs)[:, :, 0:3].copy()).to(b.device)
+            rows_t = None
+            if args.row_noise:
+                rows_t = torch.from_numpy(np.exp(np.random.default_rng(args.seed + 8).uniform(
+                    np.log(0.3), np.log(3.0), tuple(z_t.shape)))).to(b.device)
             torch.cuda.synchronize(b.device)
             t = time.perf_counter()
-            b.observe_sequence(idx_t, z_t)
+            b.observe_sequence(idx_t, z_t, rows=rows_t)
             b.sync()
             t_steady = time.perf_counter() - t
             rates[variant] = args.steady / t_steady

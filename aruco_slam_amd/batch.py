@@ -40,8 +40,8 @@ from typing import NamedTuple
 import numpy as np
 
 from .filters.base_filter import plan_detection_log
-from .hip_backend import (EKF_FLAG_BATCH_LARGE_MAPS, EKF_FLAG_BATCH_WIDE_FRAMES, EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError,
-                          _dptr, load_library, row_noise_array)
+from .hip_backend import (EKF_FLAG_BATCH_LARGE_MAPS, EKF_FLAG_BATCH_WIDE_FRAMES, EKF_FLAG_FRAME_SCALE, EKF_QUAT_AS_WRITTEN,
+                          EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError, _dptr, frame_scale_array, load_library, row_noise_array)
 
 NOISE_KEYS = ("initial_camera_uncertainty", "initial_landmark_uncertainty", "r_uncertainty", "q_cam", "q_err", "q_lm")
 EKF_ERR_NUMERIC = -5
@@ -344,14 +344,17 @@ class EKFBatch:
     ``NOISE_KEYS`` (missing keys: the model's constants); ``large_maps``: see ``use_large_maps`` (the choice is kept in
     ``self.large_maps``); ``wide_frames``: see ``use_wide_frames`` (kept in ``self.wide_frames``); ``gate``: see
     ``set_gate`` (kept in ``self.gate``); ``row_noise``: the logs may carry per-detection measurement noise (``"noise"`` in
-    ``process_detection_logs``, ``noise=`` of ``observe_indexed``; kept in ``self.row_noise``)."""
+    ``process_detection_logs``, ``noise=`` of ``observe_indexed``; kept in ``self.row_noise``); ``frame_scale``: the logs
+    may carry a process-noise scale per frame (``"scale"`` in ``process_detection_logs``, ``scale=`` of ``observe_indexed``)
+    and every member keeps a pending scale (``pending_scale``; kept in ``self.frame_scale``)."""
 
     gate = None        # [B] chi-square gate per member, or None: no gate (set_gate)
     camera = None      # (camera matrix [9], distortion coefficients, marker size) of corner logs, or None (set_camera)
 
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
                  quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf",
-                 large_maps: bool | None = None, wide_frames: bool | None = None, gate=None, row_noise: bool = False) -> None:
+                 large_maps: bool | None = None, wide_frames: bool | None = None, gate=None, row_noise: bool = False,
+                 frame_scale: bool = False) -> None:
         import torch
         gate = gate_array(gate, int(members))
         if model not in MODELS:
@@ -371,6 +374,7 @@ class EKFBatch:
             raise RuntimeError("the EKF update path needs a HIP device (no CPU fallback)")
         self.members = int(members)
         self.row_noise = bool(row_noise)
+        self.frame_scale = bool(frame_scale)
         self.device = torch.device(device)
         self.model = model
         self.lm_dims = LM_DIMS[model]
@@ -386,6 +390,8 @@ class EKFBatch:
         self.wide_frames = use_wide_frames(model, max_visible, wide_frames)
         if self.wide_frames:
             cfg.flags |= EKF_FLAG_BATCH_WIDE_FRAMES
+        if self.frame_scale:
+            cfg.flags |= EKF_FLAG_FRAME_SCALE
         if model == "ekf_rotations":
             from .filters import ekf_with_rotations as rot
             for key, val in zip(NOISE_KEYS, (rot.INITIAL_CAMERA_UNCERTAINTY, rot.INITIAL_LANDMARK_UNCERTAINTY,
@@ -488,7 +494,10 @@ class EKFBatch:
         over the surviving detections, every detection's d^2 and whether the gate rejected it.
         A log may carry ``noise`` ([D] or [D, RD], aligned with ``ids``; a batch built with ``row_noise=True``): the
         variances of its detections' measurement rows, in place of the member's ``r_uncertainty``.  A member whose log
-        carries none keeps its constant (the same bits as without any ``noise`` in the call)."""
+        carries none keeps its constant (the same bits as without any ``noise`` in the call).
+        A log may carry ``scale`` ([F], one per frame, empty frames included; a batch built with ``frame_scale=True``): the
+        frames' process-noise scales.  A frame that is not stepped leaves its scale in the member's pending scale, which the
+        next stepped frame adds to its own.  Either every log of a call carries scales or none does."""
         gated = mahal or self.gate is not None
         if len(logs) != self.members:
             raise ValueError(f"need {self.members} logs (None for a member without one), got {len(logs)}")
@@ -496,6 +505,13 @@ class EKFBatch:
         rows, any_rows = [], any(log is not None and log.get("noise") is not None for log in logs)
         if any_rows and not self.row_noise:
             raise ValueError("a log with noise needs a batch built with row_noise=True")
+        with_scale = [log is not None and log.get("scale") is not None for log in logs]
+        if any(with_scale):
+            if not self.frame_scale:
+                raise ValueError("a log with scale needs a batch built with frame_scale=True")
+            if not all(w for w, log in zip(with_scale, logs) if log is not None):
+                raise ValueError("either every log of a call carries scale or none does")
+        scales = []
         corner_parts = []       # (first row, kept corners [n,4,2]) of every log that carries corners
         base = 0
         for b, log in enumerate(logs):
@@ -525,6 +541,8 @@ class EKFBatch:
                 else:
                     r = np.full((plan.keep.shape[0], RD[self.model]), self.noise[b, NOISE_KEYS.index("r_uncertainty")])
                 rows.append(r[plan.keep])
+            if with_scale[b]:
+                scales.append(frame_scale_array(log["scale"], plan.offsets.shape[0] - 1, f"member {b}: scale"))
             plans.append(plan)
             index.append(plan.index)
             offsets.append(plan.offsets[1:] + base)
@@ -537,6 +555,8 @@ class EKFBatch:
         if sum(c.shape[0] for _, c in corner_parts):
             poses = self._estimate_corner_logs(poses, corner_parts)
         with_rows = {"noise": np.concatenate(rows)} if any_rows and rows else {}      # (no rows: the call as it ever was)
+        if scales:
+            with_rows["scale"] = np.concatenate(scales)
         if gated:
             traj, nis_v, cov_v, mahal_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses,
                                                                nis=nis, cam_cov=cam_cov, mahal=True, **with_rows)
@@ -735,20 +755,24 @@ class EKFBatch:
                                    cov_t.cpu().numpy() if cam_cov else None, full, rej, flipped)
 
     def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False,
-                        mahal: bool = False, noise=None):
+                        mahal: bool = False, noise=None, scale=None):
         """The C call behind ``process_detection_logs`` (landmark indices already assigned; ``landmarks`` is not
         touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1] on the host, poses [D,6] on the host or a contiguous
         float64 tensor on the batch's device, produced on the batch's stream.  Returns the
         trajectory [Ftot, 7]; with ``nis`` or ``cam_cov`` the tuple (trajectory, nis [Ftot] or None, cam_cov [Ftot, 10, 10]
         or None); with ``mahal`` the tuple (trajectory, nis or None, cam_cov or None, mahal [D]).  A gate that is set acts
         on every call, whatever it returns.  ``noise``: [D] or [D, RD] row variances indexed like lm_index (a batch built
-        with ``row_noise=True``; ekf_batch_observe_logs_rows), or None: every member's ``r_uncertainty``."""
+        with ``row_noise=True``; ekf_batch_observe_logs_rows), or None: every member's ``r_uncertainty``.  ``scale``:
+        [Ftot] process-noise scales, one per frame, indexed like frame_offsets (a batch built with ``frame_scale=True``;
+        ekf_batch_observe_logs_scaled), or None: no frame carries one."""
         torch = self._torch
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
         if noise is not None:
             if not self.row_noise:
                 raise ValueError("noise= needs a batch built with row_noise=True")
             noise = row_noise_array(noise, idx.shape[0], RD[self.model])
+        if scale is not None and not self.frame_scale:
+            raise ValueError("scale= needs a batch built with frame_scale=True")
         fo = np.ascontiguousarray(frame_offsets, dtype=np.int64).reshape(-1)
         mf = np.ascontiguousarray(member_frames, dtype=np.int64).reshape(-1)
         on_device = isinstance(poses, torch.Tensor)
@@ -765,6 +789,8 @@ class EKFBatch:
             raise ValueError(f"frame_offsets must have {frames + 1} entries")
         if poses.shape[0] != idx.shape[0] or (frames and fo[-1] != idx.shape[0]):
             raise ValueError("frame_offsets, lm_index and poses do not match")
+        if scale is not None:
+            scale = frame_scale_array(scale, frames)
         nbytes = C.c_size_t()
         self._check(self.lib.ekf_batch_log_workspace_bytes(self.h, idx.shape[0], frames, C.byref(nbytes)))
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
@@ -772,15 +798,17 @@ class EKFBatch:
             poses_t = poses if on_device else torch.from_numpy(poses).to(self.device)
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
             traj = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
-            if noise is not None:
-                rows_t = torch.from_numpy(noise).to(self.device)
+            if noise is not None or scale is not None:
+                rows_t = torch.from_numpy(noise).to(self.device) if noise is not None else None
+                scale_t = torch.from_numpy(scale).to(self.device) if scale is not None else None
                 nis_t = torch.empty((frames,), dtype=torch.float64, device=self.device) if nis else None
                 cov_t = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
                 mahal_t = torch.empty((idx.shape[0],), dtype=torch.float64, device=self.device) if mahal else None
                 ptr = (lambda t: t.data_ptr() if t is not None and frames else None)
-                self._check(self.lib.ekf_batch_observe_logs_rows(
+                self._check(self.lib.ekf_batch_observe_logs_scaled(
                     self.h, _iptr(idx), _lptr(fo), _lptr(mf), poses_t.data_ptr() if idx.shape[0] else None,
-                    rows_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(), nbytes.value, ptr(traj), ptr(nis_t),
+                    rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None, ptr(scale_t), ws.data_ptr(),
+                    nbytes.value, ptr(traj), ptr(nis_t),
                     ptr(cov_t), mahal_t.data_ptr() if mahal and idx.shape[0] else None))
                 self.stream.synchronize()
                 out = (traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, cov_t.cpu().numpy() if cam_cov else None)
@@ -842,8 +870,33 @@ class EKFBatch:
         state = self.get_state(b)
         return state[:10], state[10:].reshape(-1, self.lm_dims)
 
-    def get_lm_uncertainties(self, b) -> np.ndarray:
-        return np.diagonal(self.get_cov(b))[10:].reshape(-1, self.lm_dims).copy()
+    def get_lm_uncertainties(self, b, predicted: bool = False) -> np.ndarray:
+        """diag(P) of member b's landmarks; ``predicted=True`` adds fl(pending scale * q_lm) on the host."""
+        out = np.diagonal(self.get_cov(b))[10:].reshape(-1, self.lm_dims).copy()
+        if predicted:
+            out += float(self.pending_scale[self._member(b)]) * float(self.noise[self._member(b), NOISE_KEYS.index("q_lm")])
+        return out
+
+    @property
+    def pending_scale(self) -> np.ndarray:
+        """[B]: every member's pending process-noise scale (ekf_batch_get_pending_scale; zeros for a batch built without
+        ``frame_scale=True``).  Synchronises."""
+        out = np.zeros(self.members)
+        self._check(self.lib.ekf_batch_get_pending_scale(self.h, -1, _dptr(out)))
+        return out
+
+    def set_pending_scale(self, pending, b=None) -> None:
+        """The pending scale of member b (a number), or of every member (None: a number or [B]); a batch built with
+        ``frame_scale=True``.  Values that are not finite and >= 0 raise ``ValueError`` and nothing changes."""
+        if not self.frame_scale:
+            raise ValueError("a pending scale needs a batch built with frame_scale=True")
+        if b is None:
+            v = frame_scale_array(np.broadcast_to(np.asarray(pending, dtype=np.float64), (self.members,)), self.members,
+                                  "pending")
+            self._check(self.lib.ekf_batch_set_pending_scale(self.h, -1, _dptr(v)))
+        else:
+            v = np.array([frame_scale_array(pending, None, "pending")])
+            self._check(self.lib.ekf_batch_set_pending_scale(self.h, self._member(b), _dptr(v)))
 
     def set_member(self, b, state, cov, marker_ids) -> None:
         """Member b from host ``(state [l n + 10], cov [l n + 10, l n + 10], marker ids in landmark-index order)`` with
@@ -923,8 +976,13 @@ class EKFBatch:
             raise ValueError(f"the filter's quaternion convention differs from the batch's ({self.quat_update!r})")
         if ekf.backend.can_row_noise and not self.row_noise:
             raise ValueError("the filter takes per-detection noise: load it into a batch built with row_noise=True")
+        if ekf.backend.can_frame_scale and not self.frame_scale:
+            raise ValueError("the filter takes per-frame scales: load it into a batch built with frame_scale=True")
+        pending = ekf.backend.pending_scale
         ids = [k for k, _ in sorted(ekf.get_lm_estimates(), key=lambda kv: kv[1])]
         self.set_member(b, np.asarray(ekf.state, dtype=np.float64), ekf.uncertainty, ids)
+        if self.frame_scale:      # (set_member has zeroed it; a filter without the capability has 0)
+            self.set_pending_scale(pending, b)
         if ekf.gate is not None and not (self.gate is None and np.isinf(ekf.gate)):
             gates = np.full(self.members, np.inf) if self.gate is None else self.gate.copy()
             gates[self._member(b)] = ekf.gate
@@ -933,8 +991,8 @@ class EKFBatch:
     def to_filter(self, b):
         """An ordinary filter of the batch's model (``EKF`` or ``EKF_Rotations``, f64 covariance) with member b's quaternion
         convention, noise constants, gate (a batch with a gate gives a filter built with ``gate=``), per-detection-noise
-        capability (a batch built with ``row_noise=True`` gives a filter built the same way), state, covariance and
-        landmark table; ``observe`` (and for ``EKF`` ``save_map`` and ``save_checkpoint``) work on it."""
+        capability (a batch built with ``row_noise=True`` gives a filter built the same way), per-frame-scale capability and
+        pending scale (likewise, ``frame_scale=True``), state, covariance and landmark table; ``observe`` (and for ``EKF`` ``save_map`` and ``save_checkpoint``) work on it."""
         b = self._member(b)
         state, cov = self.get_state(b), self.get_cov(b)
         n = self.num_landmarks[b]
@@ -943,12 +1001,17 @@ class EKFBatch:
         if self.model == "ekf_rotations":
             from .filters.ekf_with_rotations import EKF_Rotations
             ekf = EKF_Rotations(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
-                                device=str(self.device), noise=noise, gate=gate, row_noise=self.row_noise)
+                                device=str(self.device), noise=noise, gate=gate, row_noise=self.row_noise,
+                                frame_scale=self.frame_scale)
         else:
             from .filters.extended_kalman_filter import EKF
             ekf = EKF(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
-                      quat_update=self.quat_update, device=str(self.device), noise=noise, gate=gate, row_noise=self.row_noise)
+                      quat_update=self.quat_update, device=str(self.device), noise=noise, gate=gate, row_noise=self.row_noise,
+                      frame_scale=self.frame_scale)
+        pending = float(self.pending_scale[b]) if self.frame_scale else 0.0
         ekf.backend.set_state_cov(state, cov)
+        if self.frame_scale:
+            ekf.backend.pending_scale = pending
         ekf.landmarks = dict(self.landmarks[b])
         ekf.num_landmarks = n
         return ekf

@@ -247,6 +247,11 @@ struct ekf_filter {
     hipEvent_t remove_done[2] = {};
     int remove_turn = 0;
 
+    // per-frame process-noise scale (EKF_FLAG_FRAME_SCALE): the pending scale p of the ABI's rules, kept on the host -- the
+    // host launches every frame and knows which ones are stepped (a gated frame: after its round trip).  0 without the flag.
+    double pending = 0.0;
+
+    bool has_scale() const { return (cfg.flags & EKF_FLAG_FRAME_SCALE) != 0; }
     bool gate_on() const { return lay.has_gate && gate < __builtin_inf(); }
     void reset_gate_stats() { gate_stats[0] = gate_stats[1] = 0; }      // every observe call counts from zero
     int dims() const { return lay.lmd * n_lm + EKF_CAM; }
@@ -277,8 +282,18 @@ int fold_timing(ekf_filter* f) {
     return EKF_OK;
 }
 
+// The noise of a frame that runs with the scale s_eff: Q_eff = fl(s_eff q) per entry -- one f64 multiplication each, rounded
+// here, before any kernel adds it to anything (a device-side v + s q would contract into an fma) -- and r_uncertainty.
+// s_eff = 1 (every frame of a filter without EKF_FLAG_FRAME_SCALE) gives the constants themselves.
+EkfNoise frame_noise(const ekf_filter* f, double s_eff) {
+    return EkfNoise{s_eff * f->cfg.q_cam, s_eff * f->cfg.q_err, s_eff * f->cfg.q_lm, f->cfg.r_uncertainty};
+}
+
+// a scale of a frame: finite and >= 0
+bool scale_ok(double s) { return std::isfinite(s) && s >= 0.0; }
+
 EkfFrame make_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, const double* rows_dev, int m,
-                    double* traj_row) {
+                    double* traj_row, double s_eff) {
     EkfFrame fr{};
     const Layout& L = f->lay;
     fr.cov = f->cov;
@@ -316,7 +331,10 @@ EkfFrame make_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, 
     // (role-level stamps only: the per-frame ring of the end gate borrows the W debug copy, which is idle in that mode)
     fr.gate_log = (fr.stamps && !fr.stamps_heavy && !f->debug_w && (size_t)L.kmax * L.cap >= 4 * EKF_GATE_LOG_FRAMES)
                       ? f->at<long long>(L.off_wdbg) : nullptr;
-    fr.nz = EkfNoise{f->cfg.q_cam, f->cfg.q_err, f->cfg.q_lm, f->cfg.r_uncertainty};
+    fr.nz = frame_noise(f, s_eff);
+    fr.qprev_cam = fr.nz.q_cam;
+    fr.qprev_err = fr.nz.q_err;
+    fr.qprev_lm = fr.nz.q_lm;
     fr.quat_mode = f->cfg.quat_mode;
     fr.n_lm = f->n_lm;
     fr.state_host = nullptr;
@@ -386,11 +404,12 @@ int ensure_tiles(ekf_filter* f) {
 // `mirror`: the frame also leaves its state in the pinned host mirror (per-frame entry points: a state getter usually follows;
 // frames of a sequence call do not -- no getter can run between them, and the mirror is 8 N bytes over PCIe per frame)
 // rows_dev [m][rd] (device, or pinned host) or null: per-detection noise
+// s_eff: the frame's process-noise scale (1: the constants)
 int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, const double* rows_dev, int m,
-                  double* traj_row, bool mirror) {
+                  double* traj_row, bool mirror, double s_eff) {
     int trc = ensure_tiles(f);
     if (trc) return trc;
-    EkfFrame fr = make_frame(f, idx_dev, z_dev, rows_dev, m, traj_row);
+    EkfFrame fr = make_frame(f, idx_dev, z_dev, rows_dev, m, traj_row, s_eff);
     const int variant = f->cfg.cov_kernel == EKF_COVK_VALU ? 1 : 2;
     hipEvent_t* ev = nullptr;
     if (f->timing) {
@@ -621,6 +640,7 @@ struct RunFrame {
     int m;
     double* traj_row;
     const double* rows = nullptr;      // [m][rd] or null: per-detection noise
+    double s_eff = 1.0;                // the frame's process-noise scale (pending part included)
 };
 
 // A run of `frames` >= 2 frames in the pipelined sequence mode; frame_at(t) describes frame t.  Every frame of a run has the
@@ -676,13 +696,17 @@ int run_pipelined(ekf_filter* f, int frames, FrameAt frame_at, void* other) {
     // for "F(1) has started", i.e. for everything that is on stream A now and F(0); the previous run ended with
     // stream A waiting for stream B)
     RunFrame nx = frame_at(0);
+    EkfNoise nz_before{};      // the noise frame t - 1 ran with: what its covariance update adds to the diagonal
     for (int t = 0; t < frames; ++t) {
         const int par = t & 1;
         const RunFrame cf_t = nx;
-        EkfFrame fr = make_frame(f, cf_t.idx, cf_t.z, cf_t.rows, cf_t.m, cf_t.traj_row);
+        EkfFrame fr = make_frame(f, cf_t.idx, cf_t.z, cf_t.rows, cf_t.m, cf_t.traj_row, cf_t.s_eff);
         fr.cov = cbuf[0];
         fr.wpanel = wbuf[par];
-        if (t > 0) {                                           // P_{t-1} + the completion from W_{t-1}
+        if (t > 0) {                                           // P_{t-1} + the completion from W_{t-1}, with Q_{t-1}
+            fr.qprev_cam = nz_before.q_cam;
+            fr.qprev_err = nz_before.q_err;
+            fr.qprev_lm = nz_before.q_lm;
             fr.cov = cbuf[par ^ 1];
             fr.wprev = wbuf[par ^ 1];
             fr.wsup_prev = wsup[par ^ 1];
@@ -719,6 +743,7 @@ int run_pipelined(ekf_filter* f, int frames, FrameAt frame_at, void* other) {
         }
         HIP_TRY(hipGetLastError());
         f->last_m = cf_t.m;
+        nz_before = fr.nz;
     }
     f->cov = cbuf[frames & 1];
     f->la_base = base + (uint64_t)frames;
@@ -773,7 +798,7 @@ int run_frames(ekf_filter* f, int frames, FrameOf frame_of, FirstSightings first
     auto serial = [&](int t) {
         const RunFrame r = frame_of(t);
         if (stats) stats[0] += 1;
-        return enqueue_frame(f, r.idx, r.z, r.rows, r.m, r.traj_row, false);
+        return enqueue_frame(f, r.idx, r.z, r.rows, r.m, r.traj_row, false, r.s_eff);
     };
     auto flush = [&]() -> int {
         int rc = EKF_OK;
@@ -846,8 +871,10 @@ int open_handle(ekf_filter* f) {
 // exempt [m] (pinned host or device) or null; n_exempt: how many of them are set (statistics); mahal_dev / mahal_host [m] or
 // null.  *survivors: how many detections stayed.
 // rows [m][rd] or null: per-detection noise; the gate tests with them and compacts them with the survivors.
+// s_eff: the frame's process-noise scale; the gate's S_d and the frame on the survivors use the same Q_eff.
 int gated_frame(ekf_filter* f, const int32_t* idx, const double* z, const double* rows, int m, const uint8_t* exempt,
-                int n_exempt, double* mahal_dev, double* mahal_host, double* traj_row, bool mirror, int* survivors) {
+                int n_exempt, double* mahal_dev, double* mahal_host, double* traj_row, bool mirror, int* survivors,
+                double s_eff) {
     const Layout& L = f->lay;
     EkfGateArgs g{};
     g.cov = f->cov;
@@ -859,7 +886,7 @@ int gated_frame(ekf_filter* f, const int32_t* idx, const double* z, const double
     g.idx = idx;
     g.z = z;
     g.exempt = exempt;
-    g.nz = EkfNoise{f->cfg.q_cam, f->cfg.q_err, f->cfg.q_lm, f->cfg.r_uncertainty};
+    g.nz = frame_noise(f, s_eff);
     g.gate = f->gate;
     g.mahal = mahal_dev ? mahal_dev : f->at<double>(L.off_gmahal);
     g.mahal_host = mahal_host;
@@ -880,7 +907,27 @@ int gated_frame(ekf_filter* f, const int32_t* idx, const double* z, const double
     f->gate_stats[1] += m - s;
     if (survivors) *survivors = s;
     if (s == 0) return EKF_OK;
-    return enqueue_frame(f, g.out_idx, g.out_z, g.out_rows, s, traj_row, mirror);
+    return enqueue_frame(f, g.out_idx, g.out_z, g.out_rows, s, traj_row, mirror, s_eff);
+}
+
+// Rules 3 and 4 of the per-frame scale (include/ekf_slam_hip.h), kept on the host.  `scale`: the frame's scale, or null: the
+// frame carries none -- stepped, it runs with p + 1 (p = 0: the constants, the call as it ever was); not stepped, it leaves
+// p alone.  A filter without EKF_FLAG_FRAME_SCALE has p = 0 and every frame runs with the constants.
+double frame_scale(const ekf_filter* f, const double* scale) {
+    return f->has_scale() ? f->pending + (scale ? *scale : 1.0) : 1.0;
+}
+void frame_scale_done(ekf_filter* f, const double* scale, double s_eff, bool stepped) {
+    if (!f->has_scale()) return;
+    if (stepped) f->pending = 0.0;
+    else if (scale) f->pending = s_eff;
+}
+// scale [count] of a call (host, or null): the flag and the values, before anything is enqueued
+int check_scales(const ekf_filter* f, const double* scale, int64_t count) {
+    if (!scale) return EKF_OK;
+    if (!f->has_scale()) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_FRAME_SCALE");
+    for (int64_t i = 0; i < count; ++i)
+        if (!scale_ok(scale[i])) return fail(EKF_ERR_INVALID, "a frame's scale must be finite and >= 0");
+    return EKF_OK;
 }
 
 // trajectory row of a frame that is not stepped: the camera state as it is on the device
@@ -892,15 +939,16 @@ int repeat_row(ekf_filter* f, double* traj_row) {
 // A gated frame of a sequence or of a log (device arrays, no host mirror): the frame on its survivors, or, with none left,
 // its trajectory row alone
 int gated_frame_or_row(ekf_filter* f, const int32_t* idx, const double* z, const double* rows, int m, const uint8_t* exempt,
-                       int n_exempt, double* mahal_dev, double* traj_row, int* survivors) {
-    const int rc = gated_frame(f, idx, z, rows, m, exempt, n_exempt, mahal_dev, nullptr, traj_row, false, survivors);
+                       int n_exempt, double* mahal_dev, double* traj_row, int* survivors, double s_eff) {
+    const int rc = gated_frame(f, idx, z, rows, m, exempt, n_exempt, mahal_dev, nullptr, traj_row, false, survivors, s_eff);
     return rc == EKF_OK && *survivors == 0 ? repeat_row(f, traj_row) : rc;
 }
 
 // ekf_observe / ekf_observe_gated: the frame's detections (host) through a slot of the pinned staging ring
 // rows [m][rd] (host) or null: per-detection noise, staged behind everything else of the slot
+// scale: the frame's process-noise scale, or null (checked by the caller: check_scales)
 int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m, bool gated,
-                 const uint8_t* exempt, double* mahal, int32_t* survivors) {
+                 const uint8_t* exempt, double* mahal, int32_t* survivors, const double* scale = nullptr) {
     if (m < 1) return fail(EKF_ERR_INVALID, "observe needs at least one detection");
     if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
     if (!lm_index || !z) return fail(EKF_ERR_INVALID, "NULL detections");
@@ -933,6 +981,7 @@ int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, const 
     // copy in front of them costs more (API call + DMA start, ~8 us before the front kernel begins) than the PCIe reads
     // cost the kernel's first round trip.  The slot is not reused before this frame's event (64-slot ring).
     int rc;
+    const double s_eff = frame_scale(f, scale);
     if (gated) {
         uint8_t* hex = nullptr;
         int n_exempt = 0;
@@ -943,13 +992,15 @@ int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, const 
         }
         double* hm = mahal ? reinterpret_cast<double*>(slot + L.slot_mahal) : nullptr;
         int s = 0;
-        rc = gated_frame(f, hidx, hz, hrows, m, hex, n_exempt, nullptr, hm, nullptr, true, &s);
+        rc = gated_frame(f, hidx, hz, hrows, m, hex, n_exempt, nullptr, hm, nullptr, true, &s, s_eff);
         if (rc) return rc;
         if (mahal) std::memcpy(mahal, hm, (size_t)m * 8);      // (complete: the gate kernel's event has been waited for)
         if (survivors) *survivors = s;
+        frame_scale_done(f, scale, s_eff, s > 0);      // (no survivor: the frame is not stepped, its scale stays pending)
     } else {
-        rc = enqueue_frame(f, hidx, hz, hrows, m, nullptr, true);
+        rc = enqueue_frame(f, hidx, hz, hrows, m, nullptr, true, s_eff);
         if (rc) return rc;
+        frame_scale_done(f, scale, s_eff, true);
     }
     HIP_TRY(hipEventRecord(f->slot_done[f->slot], f->stream));
     f->slot = (f->slot + 1) % kStageSlots;
@@ -1206,6 +1257,7 @@ int ekf_reset(ekf_filter* f, const double initial_camera_pose[10]) {
     HIP_TRY(hipStreamSynchronize(f->stream));
     f->n_lm = 0;
     f->last_m = 0;
+    f->pending = 0.0;
     f->is_reset = true;
     return EKF_OK;
 }
@@ -1269,16 +1321,52 @@ int ekf_observe_gated(ekf_filter* f, const int32_t* lm_index, const double* z, i
     return rc;
 }
 
-int ekf_observe_rows(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m,
-                     const uint8_t* exempt, double* mahal, int32_t* survivors) {
+namespace {
+int observe_rows_scaled(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m,
+                        const uint8_t* exempt, double* mahal, int32_t* survivors, const double* scale) {
     int rc = check_ready(f);
     if (rc) return rc;
     if ((exempt || mahal) && !f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
+    if ((rc = check_scales(f, scale, 1))) return rc;
     f->reset_gate_stats();
     const bool gated = f->gate_on() || mahal;
-    rc = observe_host(f, lm_index, z, rows, m, gated, exempt, mahal, survivors);
+    rc = observe_host(f, lm_index, z, rows, m, gated, exempt, mahal, survivors, scale);
     if (rc == EKF_OK && !gated && survivors) *survivors = m;
     return rc;
+}
+}  // namespace
+
+int ekf_observe_rows(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m,
+                     const uint8_t* exempt, double* mahal, int32_t* survivors) {
+    return observe_rows_scaled(f, lm_index, z, rows, m, exempt, mahal, survivors, nullptr);
+}
+
+int ekf_observe_scaled(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m,
+                       const uint8_t* exempt, double* mahal, int32_t* survivors, double scale) {
+    return observe_rows_scaled(f, lm_index, z, rows, m, exempt, mahal, survivors, &scale);
+}
+
+int ekf_advance(ekf_filter* f, double scale) {
+    int rc = check_ready(f);
+    if (rc) return rc;
+    if ((rc = check_scales(f, &scale, 1))) return rc;
+    f->pending = f->pending + scale;
+    return EKF_OK;
+}
+
+int ekf_get_pending_scale(const ekf_filter* f, double* out) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
+    *out = f->pending;
+    return EKF_OK;
+}
+
+int ekf_set_pending_scale(ekf_filter* f, double pending) {
+    int rc = check_ready(f);
+    if (rc) return rc;
+    if ((rc = check_scales(f, &pending, 1))) return rc;
+    f->pending = pending;
+    return EKF_OK;
 }
 
 int ekf_set_gate(ekf_filter* f, double gate) {
@@ -1306,8 +1394,12 @@ int ekf_observe_device(ekf_filter* f, const int32_t* lm_index_dev, const double*
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
     // the indices are device-resident: range-checked by the kernels (EKF_ERR_INVALID at the next sync)
     f->reset_gate_stats();
-    if (f->gate_on()) return gated_frame(f, lm_index_dev, z_dev, nullptr, m, nullptr, 0, nullptr, nullptr, nullptr, true, nullptr);
-    return enqueue_frame(f, lm_index_dev, z_dev, nullptr, m, nullptr, true);
+    const double s_eff = frame_scale(f, nullptr);
+    int s = m;
+    rc = f->gate_on() ? gated_frame(f, lm_index_dev, z_dev, nullptr, m, nullptr, 0, nullptr, nullptr, nullptr, true, &s, s_eff)
+                      : enqueue_frame(f, lm_index_dev, z_dev, nullptr, m, nullptr, true, s_eff);
+    if (rc == EKF_OK) frame_scale_done(f, nullptr, s_eff, s > 0);
+    return rc;
 }
 
 int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, const double* z_dev,
@@ -1317,10 +1409,16 @@ int ekf_observe_sequence_device(ekf_filter* f, const int32_t* lm_index_dev, cons
 
 int ekf_observe_sequence_device_rows(ekf_filter* f, const int32_t* lm_index_dev, const double* z_dev, const double* rows_dev,
                                      int32_t m, int32_t frames, double* trajectory_dev) {
+    return ekf_observe_sequence_device_scaled(f, lm_index_dev, z_dev, rows_dev, nullptr, m, frames, trajectory_dev);
+}
+
+int ekf_observe_sequence_device_scaled(ekf_filter* f, const int32_t* lm_index_dev, const double* z_dev, const double* rows_dev,
+                                       const double* scale, int32_t m, int32_t frames, double* trajectory_dev) {
     int rc = check_ready(f);
     if (rc) return rc;
     if (rows_dev && !f->lay.has_rows) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_ROW_NOISE");
     if (m < 1 || frames < 0) return fail(EKF_ERR_INVALID, "bad sequence shape");
+    if ((rc = check_scales(f, scale, frames))) return rc;
     if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
     if (!lm_index_dev || !z_dev) return fail(EKF_ERR_INVALID, "NULL detections");
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
@@ -1333,13 +1431,22 @@ int ekf_observe_sequence_device_rows(ekf_filter* f, const int32_t* lm_index_dev,
         f->shortcut.log();      // (a getter after the call waits for all of it)
         for (int t = 0; t < frames; ++t) {
             int s = 0;
+            const double* sc = scale ? scale + t : nullptr;
+            const double s_eff = frame_scale(f, sc);
             rc = gated_frame_or_row(f, lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd,
                                     rows_dev ? rows_dev + (size_t)t * m * rd : nullptr, m, nullptr, 0, nullptr,
-                                    trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr, &s);
+                                    trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr, &s, s_eff);
             if (rc) return rc;
+            frame_scale_done(f, sc, s_eff, s > 0);
         }
         f->shortcut.log();
         return EKF_OK;
+    }
+    // every frame is stepped: the pending scale goes into the first one (rule 3), and none is left
+    std::vector<double> s_effs((size_t)frames, 1.0);
+    for (int t = 0; t < frames; ++t) {
+        s_effs[t] = frame_scale(f, scale ? scale + t : nullptr);
+        frame_scale_done(f, scale ? scale + t : nullptr, s_effs[t], true);
     }
     // Pipelined mode (F(t+1) beside C(t), see run_pipelined) for the whole call if pipeline_wanted admits the frame shape
     const RunPlan plan = plan_runs(f, frames, [&](int) { return m; }, [](int) { return 0; });
@@ -1352,7 +1459,7 @@ int ekf_observe_sequence_device_rows(ekf_filter* f, const int32_t* lm_index_dev,
         [&](int t) {
             return RunFrame{lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd, m,
                             trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr,
-                            rows_dev ? rows_dev + (size_t)t * m * rd : nullptr};
+                            rows_dev ? rows_dev + (size_t)t * m * rd : nullptr, s_effs[t]};
         },
         [](int) { return 0; }, plan, mode == EKF_SEQ_PIPELINED, nullptr);
     if (rc) return rc;
@@ -1409,6 +1516,13 @@ int ekf_observe_log_gated(ekf_filter* f, const int32_t* lm_index, const int64_t*
 int ekf_observe_log_rows(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
                          const double* poses_dev, const double* rows_dev, void* log_ws, size_t log_ws_bytes,
                          double* trajectory_dev, double* mahal_dev) {
+    return ekf_observe_log_scaled(f, lm_index, offsets, frames, poses_dev, rows_dev, nullptr, log_ws, log_ws_bytes,
+                                  trajectory_dev, mahal_dev);
+}
+
+int ekf_observe_log_scaled(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
+                           const double* poses_dev, const double* rows_dev, const double* scale, void* log_ws,
+                           size_t log_ws_bytes, double* trajectory_dev, double* mahal_dev) {
     int rc = check_ready(f);
     if (rc) return rc;
     if (rows_dev && !f->lay.has_rows) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_ROW_NOISE");
@@ -1417,6 +1531,7 @@ int ekf_observe_log_rows(ekf_filter* f, const int32_t* lm_index, const int64_t* 
     const bool gated = f->gate_on() || mahal_dev;
     // ---- validation on the host: nothing is enqueued before the whole log has passed
     if (frames < 0) return fail(EKF_ERR_INVALID, "negative frame count");
+    if ((rc = check_scales(f, scale, frames))) return rc;
     if (frames > 0 && !offsets) return fail(EKF_ERR_INVALID, "offsets is NULL");
     if (frames > 0 && (rc = check_offsets(offsets, frames, "offsets"))) return rc;
     const int64_t D = frames > 0 ? offsets[frames] : 0;
@@ -1475,6 +1590,14 @@ int ekf_observe_log_rows(ekf_filter* f, const int32_t* lm_index, const int64_t* 
 
     auto m_of = [&](int t) { return (int)(offsets[t + 1] - offsets[t]); };
     auto nnew_of = [&](int t) { return (int)(lc.new_at[t + 1] - lc.new_at[t]); };
+    // Without a gate the host knows which frames are stepped: rules 3 and 4 run over the whole log here, an empty frame's
+    // scale goes into the pending scale and the next stepped frame takes it.  (Gated: frame by frame below.)
+    std::vector<double> s_effs((size_t)frames, 1.0);
+    if (!gated)
+        for (int t = 0; t < frames; ++t) {
+            s_effs[t] = frame_scale(f, scale ? scale + t : nullptr);
+            frame_scale_done(f, scale ? scale + t : nullptr, s_effs[t], m_of(t) > 0);
+        }
     const RunPlan plan = gated ? RunPlan{} : plan_runs(f, frames, m_of, nnew_of);
     int mode = EKF_SEQ_SERIAL;
     rc = choose_pipelining(f, plan.want_runs, &mode);
@@ -1490,7 +1613,7 @@ int ekf_observe_log_rows(ekf_filter* f, const int32_t* lm_index, const int64_t* 
     auto frame_of = [&](int t) {
         const int64_t d0 = offsets[t];
         return RunFrame{idx_all + d0, z_all + (size_t)d0 * rd, m_of(t), trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr,
-                        rows_dev ? rows_dev + (size_t)d0 * rd : nullptr};
+                        rows_dev ? rows_dev + (size_t)d0 * rd : nullptr, s_effs[t]};
     };
     auto first_sightings = [&](int t) {
         const int nnew = nnew_of(t);
@@ -1507,8 +1630,11 @@ int ekf_observe_log_rows(ekf_filter* f, const int32_t* lm_index, const int64_t* 
         // without a survivor is not stepped, and its row repeats the camera state
         for (int t = 0; t < frames && rc == EKF_OK; ++t) {
             const RunFrame r = frame_of(t);
+            const double* sc = scale ? scale + t : nullptr;
+            const double s_eff = frame_scale(f, sc);
             if (r.m == 0) {
                 rc = repeat_row(f, r.traj_row);
+                frame_scale_done(f, sc, s_eff, false);
                 continue;
             }
             const int nnew = first_sightings(t);
@@ -1517,8 +1643,9 @@ int ekf_observe_log_rows(ekf_filter* f, const int32_t* lm_index, const int64_t* 
             const int64_t d0 = offsets[t];
             int s = 0;
             rc = gated_frame_or_row(f, r.idx, r.z, r.rows, r.m, pin_exempt + d0, nnew, mahal_dev ? mahal_dev + d0 : nullptr,
-                                    r.traj_row, &s);
+                                    r.traj_row, &s, s_eff);
             if (rc == EKF_OK && s > 0) f->log_stats[0] += 1;
+            if (rc == EKF_OK) frame_scale_done(f, sc, s_eff, s > 0);
         }
     } else {
         rc = run_frames(f, frames, frame_of, first_sightings, plan, mode == EKF_SEQ_PIPELINED, f->log_stats);
@@ -1636,6 +1763,7 @@ int ekf_set_state(ekf_filter* f, const double* state, int32_t num_landmarks) {
     HIP_TRY(hipMemcpy(f->state, state, (size_t)(f->lay.lmd * num_landmarks + EKF_CAM) * 8,
                       hipMemcpyHostToDevice));
     f->n_lm = num_landmarks;
+    f->pending = 0.0;
     return EKF_OK;
 }
 

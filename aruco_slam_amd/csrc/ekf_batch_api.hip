@@ -39,13 +39,15 @@ int64_t batch_ld(const ekf_config& c) { return round_up(batch_lmd(c) * (int64_t)
 
 bool batch_large(const ekf_config& c) { return (c.flags & EKF_FLAG_BATCH_LARGE_MAPS) != 0; }
 bool batch_wide(const ekf_config& c) { return (c.flags & EKF_FLAG_BATCH_WIDE_FRAMES) != 0; }
+bool batch_scaled(const ekf_config& c) { return (c.flags & EKF_FLAG_FRAME_SCALE) != 0; }
 
 // A / W of one member of a large-maps or wide-frames batch: [rd max_visible][ld] doubles
 int64_t batch_w_stride(const ekf_config& c) { return (int64_t)batch_rd(c) * c.max_visible * batch_ld(c); }
 
-// workspace: [noise [B][6] | status [B] | landmark counts [B] | large maps or wide frames only: A / W [B][w_stride]]
+// workspace: [noise [B][6] | status [B] | landmark counts [B] | large maps or wide frames only: A / W [B][w_stride] |
+// EKF_FLAG_FRAME_SCALE only: pending scales [B]]
 struct BatchLayout {
-    size_t status, nlm, w, total;
+    size_t status, nlm, w, total, pending;
 };
 
 BatchLayout batch_layout(const ekf_config& c, int32_t members) {
@@ -53,7 +55,15 @@ BatchLayout batch_layout(const ekf_config& c, int32_t members) {
     w.take((size_t)members * 6 * 8);
     const size_t status = w.take((size_t)members * 4), nlm = w.take((size_t)members * 4);
     const size_t wm = w.take(batch_large(c) || batch_wide(c) ? (size_t)members * batch_w_stride(c) * 8 : 0);
-    return {status, nlm, wm, w.end};
+    const size_t pending = w.take(batch_scaled(c) ? (size_t)members * 8 : 0);
+    return {status, nlm, wm, w.end, pending};
+}
+
+// zero the pending scale of members [lo, hi) (the stream is idle); nothing without EKF_FLAG_FRAME_SCALE
+int batch_zero_pending(ekf_batch* b, int32_t lo, int32_t hi) {
+    if (!batch_scaled(b->cfg)) return EKF_OK;
+    HIP_TRY(hipMemset(b->ws + batch_layout(b->cfg, b->members).pending + 8 * (size_t)lo, 0, (size_t)(hi - lo) * 8));
+    return EKF_OK;
 }
 
 // log workspace: [landmark indices [D] | frame offsets [Ftot+1] | member frame offsets [B+1] | with a gate set: gates [B]]
@@ -177,7 +187,7 @@ BatchReplicaLayout batch_replica_layout(int64_t D, int64_t F, int32_t B, bool ga
 // the call (a layout choice only: the arithmetic is the same)
 int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, const BatchShape& sh, const double* poses_dev,
                       double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev,
-                      const double* rows_dev = nullptr) {
+                      const double* rows_dev = nullptr, const double* scale_dev = nullptr) {
     const int32_t B = b->members;
     const BatchLayout L = batch_layout(b->cfg, B);
     EkfBatchWindow a{};
@@ -198,6 +208,8 @@ int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, co
     a.gate = batch_gated(b) ? reinterpret_cast<const double*>(ws + LL.gate) : nullptr;
     a.mahal = mahal_dev;
     a.row_noise = rows_dev;      // (per-detection noise: data of the call, no workspace of its own)
+    a.pending = batch_scaled(b->cfg) ? reinterpret_cast<double*>(b->ws + L.pending) : nullptr;
+    a.scale = scale_dev;         // (per-frame scales: data of the call; checked by the caller: the flag is set)
     const int rd = batch_rd(b->cfg);
     a.kmax = std::max(rd, rd * sh.widest);
     a.lda = (int32_t)round_up(batch_lmd(b->cfg) * sh.n_max + EKF_CAM + 1, 4);
@@ -417,6 +429,7 @@ int ekf_batch_reset(ekf_batch* b, int32_t member, const double* initial_poses) {
     for (int32_t m = lo; m < hi; ++m)
         HIP_TRY(hipMemcpy2D(b->cov + (size_t)m * ld * ld, (size_t)(ld + 1) * 8, diag.data() + (size_t)(m - lo) * EKF_CAM, 8, 8,
                             EKF_CAM, hipMemcpyHostToDevice));
+    if ((rc = batch_zero_pending(b, lo, hi))) return rc;
     return batch_put_member_words(b, lo, hi);
 }
 
@@ -439,6 +452,7 @@ int ekf_batch_set_member(ekf_batch* b, int32_t member, const double* state, int3
     HIP_TRY(hipMemcpy(b->cov + (size_t)member * ld * ld, p.data(), p.size() * 8, hipMemcpyHostToDevice));
     b->nlm[member] = num_landmarks;
     b->status[member] = 0;
+    if ((rc = batch_zero_pending(b, member, member + 1))) return rc;
     return batch_put_member_words(b, member, member + 1);
 }
 
@@ -508,8 +522,17 @@ int ekf_batch_observe_logs_rows(ekf_batch* b, const int32_t* lm_index, const int
                                 const int64_t* member_frames, const double* poses_dev, const double* rows_dev, void* log_ws,
                                 size_t log_ws_bytes, double* trajectory_dev, double* nis_dev, double* cam_cov_dev,
                                 double* mahal_dev) {
+    return ekf_batch_observe_logs_scaled(b, lm_index, frame_offsets, member_frames, poses_dev, rows_dev, nullptr, log_ws,
+                                         log_ws_bytes, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
+}
+
+int ekf_batch_observe_logs_scaled(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets,
+                                  const int64_t* member_frames, const double* poses_dev, const double* rows_dev,
+                                  const double* scale_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev,
+                                  double* nis_dev, double* cam_cov_dev, double* mahal_dev) {
     int rc = batch_ready(b);
     if (rc) return rc;
+    if (scale_dev && !batch_scaled(b->cfg)) return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_FRAME_SCALE");
     // ---- validation on the host: nothing is enqueued before every log has passed
     const int32_t B = b->members;
     if (!member_frames || !frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
@@ -539,7 +562,40 @@ int ekf_batch_observe_logs_rows(ekf_batch* b, const int32_t* lm_index, const int
     if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
     char* ws = static_cast<char*>(log_ws);
     HIP_TRY(hipMemcpyAsync(ws, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
-    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev);
+    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev, scale_dev);
+}
+
+// member = -1: every member, [B]; member >= 0: that one, [1].  Both wait for the batch's stream.
+int ekf_batch_get_pending_scale(ekf_batch* b, int32_t member, double* out) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
+    if (member != -1 && (rc = batch_member(b, member))) return rc;
+    const int32_t lo = member < 0 ? 0 : member, hi = member < 0 ? b->members : member + 1;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (!batch_scaled(b->cfg)) {
+        for (int32_t m = lo; m < hi; ++m) out[m - lo] = 0.0;
+        return EKF_OK;
+    }
+    HIP_TRY(hipMemcpy(out, b->ws + batch_layout(b->cfg, b->members).pending + 8 * (size_t)lo, (size_t)(hi - lo) * 8,
+                      hipMemcpyDeviceToHost));
+    return EKF_OK;
+}
+
+int ekf_batch_set_pending_scale(ekf_batch* b, int32_t member, const double* pending) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (!pending) return fail(EKF_ERR_INVALID, "pending is NULL");
+    if (member != -1 && (rc = batch_member(b, member))) return rc;
+    if (!batch_scaled(b->cfg)) return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_FRAME_SCALE");
+    const int32_t lo = member < 0 ? 0 : member, hi = member < 0 ? b->members : member + 1;
+    for (int32_t m = lo; m < hi; ++m)
+        if (!std::isfinite(pending[m - lo]) || pending[m - lo] < 0.0)
+            return fail(EKF_ERR_INVALID, "a pending scale must be finite and >= 0");
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->ws + batch_layout(b->cfg, b->members).pending + 8 * (size_t)lo, pending, (size_t)(hi - lo) * 8,
+                      hipMemcpyHostToDevice));
+    return EKF_OK;
 }
 
 int ekf_batch_replica_poses(const double* poses_dev, int64_t detections, const double* sigma, int32_t replicas,

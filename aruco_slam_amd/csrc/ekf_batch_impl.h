@@ -130,6 +130,26 @@ __device__ __forceinline__ double ekf_batch_row_noise(const EkfBatchWindow& a, i
     return a.row_noise[(size_t)(d0 + src) * RD + (r - slot * RD)];
 }
 
+// Per-frame process-noise scale (include/ekf_slam_hip.h, "Per-frame process-noise scale"): the scale a stepped frame runs
+// with, s_eff = p + s (a frame without a scale: s = 1), and its noise Q_eff = fl(s_eff q) per entry -- an explicitly rounded
+// multiply, once per frame, before any add sees it (the compiler would contract v + s q into an fma, which is not the bits
+// of a filter configured with the products).  A batch without EKF_FLAG_FRAME_SCALE keeps the member's constants as they are.
+__device__ __forceinline__ double ekf_batch_frame_scale(const EkfBatchWindow& a, int64_t t, bool scaled, double pend) {
+    return scaled ? pend + (a.scale ? a.scale[t] : 1.0) : 1.0;
+}
+// (__dmul_rn is a plain product once it is inlined, open to contraction with the add that consumes it: the empty asm makes
+// the rounded product opaque to the optimiser)
+__device__ __forceinline__ double ekf_mul_rounded(double x, double y) {
+    double v = __dmul_rn(x, y);
+    asm volatile("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ EkfNoise ekf_batch_frame_noise(const EkfNoise& nz0, bool scaled, double s_eff) {
+    if (!scaled) return nz0;
+    return EkfNoise{ekf_mul_rounded(s_eff, nz0.q_cam), ekf_mul_rounded(s_eff, nz0.q_err), ekf_mul_rounded(s_eff, nz0.q_lm),
+                    nz0.r_unc};
+}
+
 template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -151,8 +171,11 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
     double* P = a.P + (size_t)b * ld * ld;
     double* st = a.state + (size_t)b * ld;
     const double* nzb = a.noise + 6 * b;      // ekf_config order: icu, ilu, r, q_cam, q_err, q_lm
-    const EkfNoise nz{nzb[3], nzb[4], nzb[5], nzb[2]};
+    const EkfNoise nz0{nzb[3], nzb[4], nzb[5], nzb[2]};
     const double lm_unc = nzb[1];
+    // per-frame process-noise scale: the member's pending scale travels through the window in `pend`
+    const bool scaled = a.pending != nullptr;
+    double pend = scaled ? a.pending[b] : 0.0;
     int n = a.nlm[b];
     bool failed = a.status[b] != 0;
     const bool gated = a.mahal || (a.gate && a.gate[b] < __builtin_inf());
@@ -162,6 +185,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
         const int64_t d0 = a.frame_offsets[t];
         const int mf = (int)(a.frame_offsets[t + 1] - d0);
         if (failed || mf == 0) {      // not stepped: the rows repeat the state (NaN once the member has failed)
+            if (scaled && !failed && a.scale) pend = pend + a.scale[t];      // (rule 4: the frame's scale stays pending)
             ekf_batch_rows_unstepped(a, t, tid, st, P, failed);
             ekf_batch_mahal_untested(a, d0, mf, tid, nt);
             continue;
@@ -184,6 +208,8 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
         }
         const int N = LMD * n + EKF_CAM;
         __syncthreads();
+        const double s_eff = ekf_batch_frame_scale(a, t, scaled, pend);
+        const EkfNoise nz = ekf_batch_frame_noise(nz0, scaled, s_eff);
         // the gate: the frame runs on the m detections that stay, in log order (mask: which ones)
         int m = mf;
         uint64_t mask = ~0ull;
@@ -191,10 +217,12 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
             mask = ekf_batch_gate<MODEL>(a, b, d0, mf, n0, N, tid, nt, st, P, ld, nz, A, flag + 1);
             m = __popcll(mask);
             if (m == 0) {      // no survivor: an empty frame
+                if (scaled && a.scale) pend = s_eff;      // (rule 4: p = p + s, the addition s_eff has made)
                 ekf_batch_rows_unstepped(a, t, tid, st, P, false);
                 continue;
             }
         }
+        pend = 0.0;      // (rule 3: the frame is stepped)
         const int k = RD * m;
         // h, dh and z - h (column N of A)
         if (tid < m) {
@@ -339,6 +367,7 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
         ekf_batch_rows_stepped(a, t, tid, st, P, A + N, lda, k);      // (y is column N of A)
     }
     if (tid == 0) a.nlm[b] = n;
+    if (tid == 0 && scaled) a.pending[b] = pend;
 }
 
 // one launch of `kernel` per window (> 64 KB of dynamic LDS needs the opt-in, once per kernel: `once`)

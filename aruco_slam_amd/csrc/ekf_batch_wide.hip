@@ -91,8 +91,11 @@ template <int MODEL, bool ONE_BLOCK> __device__ __forceinline__ void ekf_batch_w
     double* st = a.state + (size_t)b * ld;
     double* A = g.W + (size_t)b * g.w_stride;      // A, then W: [k][ld]
     const double* nzb = a.noise + 6 * b;      // ekf_config order: icu, ilu, r, q_cam, q_err, q_lm
-    const EkfNoise nz{nzb[3], nzb[4], nzb[5], nzb[2]};
+    const EkfNoise nz0{nzb[3], nzb[4], nzb[5], nzb[2]};
     const double lm_unc = nzb[1];
+    // per-frame process-noise scale: the member's pending scale travels through the window in `pend`
+    const bool scaled = a.pending != nullptr;
+    double pend = scaled ? a.pending[b] : 0.0;
     int n = a.nlm[b];
     bool failed = a.status[b] != 0;
     const bool gated = a.mahal || (a.gate && a.gate[b] < __builtin_inf());
@@ -102,6 +105,7 @@ template <int MODEL, bool ONE_BLOCK> __device__ __forceinline__ void ekf_batch_w
         const int64_t d0 = a.frame_offsets[t];
         const int mf = (int)(a.frame_offsets[t + 1] - d0);
         if (failed || mf == 0) {      // not stepped: the rows repeat the state (NaN once the member has failed)
+            if (scaled && !failed && a.scale) pend = pend + a.scale[t];      // (rule 4: the frame's scale stays pending)
             ekf_batch_rows_unstepped(a, t, tid, st, P, failed);
             ekf_batch_mahal_untested(a, d0, mf, tid, nt);
             continue;
@@ -122,6 +126,8 @@ template <int MODEL, bool ONE_BLOCK> __device__ __forceinline__ void ekf_batch_w
             }
         }
         const int N = LMD * n + EKF_CAM;
+        const double s_eff = ekf_batch_frame_scale(a, t, scaled, pend);
+        const EkfNoise nz = ekf_batch_frame_noise(nz0, scaled, s_eff);
         // the gate, before the blocking: the blocks are formed from the m detections that stay, in log order
         int m = mf;
         uint64_t mask = ~0ull;
@@ -130,10 +136,12 @@ template <int MODEL, bool ONE_BLOCK> __device__ __forceinline__ void ekf_batch_w
             mask = ekf_batch_gate<MODEL>(a, b, d0, mf, n0, N, tid, nt, st, P, ld, nz, R, flag + 1);
             m = __popcll(mask);
             if (m == 0) {      // no survivor: an empty frame
+                if (scaled && a.scale) pend = s_eff;      // (rule 4: p = p + s, the addition s_eff has made)
                 ekf_batch_rows_unstepped(a, t, tid, st, P, false);
                 continue;
             }
         }
+        pend = 0.0;      // (rule 3: the frame is stepped)
         const int k = RD * m, blocks_end = ONE_BLOCK ? 1 : m;
         // ---- the factorisation, block after block of detections; W_j and y_j of every block that passed stay behind
         for (int j0 = 0; j0 < blocks_end; j0 += MB) {
@@ -372,6 +380,7 @@ template <int MODEL, bool ONE_BLOCK> __device__ __forceinline__ void ekf_batch_w
         ekf_batch_rows_stepped(a, t, tid, st, P, y, 1, k);
     }
     if (tid == 0) a.nlm[b] = n;
+    if (tid == 0 && scaled) a.pending[b] = pend;
 }
 
 template <int MODEL>

@@ -109,7 +109,18 @@ __device__ __forceinline__ void fr_measure(const EkfFrame& fr, const double* cam
 // ROWS: the frame carries per-detection noise (fr.rrow).  A template parameter of the kernel, not a test inside the role:
 // the kernels without rows are, instruction for instruction, what they were before rows existed (a test and a second copy
 // of the role inside one kernel moved the code behind it, and the frame by 0.4 us).
-template <typename T, int MODEL, int NB, bool ROWS>
+// QPREV: a frame of a pipelined run whose process noise differs from the previous frame's (per-frame scales,
+// EKF_FLAG_FRAME_SCALE).  What the roles complete of P_{t+1} takes the Q the previous frame's covariance update adds
+// (fr.qprev_*); what they predict with stays fr.nz.  A template parameter for the same reason: every frame whose Q is its
+// predecessor's -- every frame of a filter without scales -- runs the instances without it, which read fr.nz at those
+// sites as they always did.  QPREV instances exist with ROWS only; without rows they park the constant where the rows
+// would be (rows all equal to c are r_uncertainty = c, bit for bit).
+template <bool QPREV> __device__ __forceinline__ double fr_qdiag_prev(const EkfFrame& fr, int i) {
+    if constexpr (QPREV) return ekf_qdiag_prev(fr, i);
+    else return ekf_qdiag(i, fr.dims, fr.nz);
+}
+
+template <typename T, int MODEL, int NB, bool ROWS, bool QPREV>
 __device__ __forceinline__ void fr_role_sblock(const EkfFrame& fr, int sb, int nS, double* sm) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     constexpr int NSLOT = EKF_CAM + LMD * EkfModel<MODEL>::NDET16;
@@ -132,8 +143,11 @@ __device__ __forceinline__ void fr_role_sblock(const EkfFrame& fr, int sb, int n
     // workgroup 0's OTHER role: free in this one), so no round trip stands in front of the emission and nothing stays in a
     // register across the role.
     [[maybe_unused]] double rnoise = 0.0;
-    if constexpr (ROWS)
+    if constexpr (ROWS && !QPREV) {
         if (bi == bj && tid < 16 && 16 * bi + tid < k) rnoise = fr.rrow[16 * bi + tid];
+    } else if constexpr (ROWS) {
+        if (bi == bj && tid < 16 && 16 * bi + tid < k) rnoise = fr.rrow ? fr.rrow[16 * bi + tid] : fr.nz.r_unc;
+    }
     // Pipelined sequence mode: `cov` is P of the PREVIOUS frame (the covariance update that produces the current P
     // runs beside this launch).  The entries this block needs are completed on the fly,
     //     P_cur[r][c] = (P_prev[r][c] + Q[r == c]) + sum_k fma(-W[k][r], W[k][c]),     k ascending from zero,
@@ -257,11 +271,11 @@ __device__ __forceinline__ void fr_role_sblock(const EkfFrame& fr, int sb, int n
                     const int col = (b < EKF_CAM) ? b : uc20[n] + (b - EKF_CAM);
                     const int cs = (b < EKF_CAM) ? b : cdet + (b - EKF_CAM);
                     if constexpr (sizeof(T) == 4) {
-                        const float q = (col == urho[n]) ? (float)ekf_qdiag(urho[n], fr.dims, fr.nz) : 0.0f;
+                        const float q = (col == urho[n]) ? (float)fr_qdiag_prev<QPREV>(fr, urho[n]) : 0.0f;
                         pv[n][b] = (T)(((float)pv[n][b] + q) + dots[uslot * DLD16 + cs]);
                     } else {      // (the f64 update: v = P; if (diagonal) v += Q; v += acc)
                         double v = (double)pv[n][b];
-                        if (col == urho[n]) v += ekf_qdiag(urho[n], fr.dims, fr.nz);
+                        if (col == urho[n]) v += fr_qdiag_prev<QPREV>(fr, urho[n]);
                         pv[n][b] = (T)(v + dots64[uslot * DLD64 + cs]);
                     }
                 }
@@ -957,7 +971,7 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
     if (wv == 0 && lane == NB && fr_tag_stale(ekf_ldc(fr.xl + fr.xl_tag), fr.seqno)) ekf_raise(fr, EKF_ST_STALE_JAC);
 }
 
-template <typename T, int NU, int MODEL, int NB>
+template <typename T, int NU, int MODEL, int NB, bool QPREV>
 __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, double* sm) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     constexpr int NWV = FR_T / 64;
@@ -1124,7 +1138,7 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {      // (a diagonal entry's row is this lane's column)
                     const int rl = (reg & 3) + 8 * (reg >> 2) + 4 * lhi;
-                    const float q = ((dmask >> reg) & 1u) ? (float)ekf_qdiag(chunk0 + jl + l31, fr.dims, fr.nz) : 0.0f;
+                    const float q = ((dmask >> reg) & 1u) ? (float)fr_qdiag_prev<QPREV>(fr, chunk0 + jl + l31) : 0.0f;
                     pl[(32 * tile_l + rl) * 64 + jl + l31] = (pt[reg] + q) + acc[reg];
                 }
             }
@@ -1211,7 +1225,7 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
                     for (int r = 0; r < 4; ++r) {      // C / D layout: column c, row g + 4 r
                         const int colg = chunk0 + 16 * (ct0 + t2) + lc;
                         double v = pt[t2][r];
-                        if (prw[r] == colg) v += ekf_qdiag(prw[r], fr.dims, fr.nz);
+                        if (prw[r] == colg) v += fr_qdiag_prev<QPREV>(fr, prw[r]);
                         v += t2 ? acc1[r] : acc0[r];
                         pl[(16 * trow + lg + 4 * r) * 64 + 16 * (ct0 + t2) + lc] = v;
                     }
@@ -1334,24 +1348,24 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
 
 // One instantiation per number of 16-row blocks NB = kpad / 16: the forward substitution is unrolled
 // over NB, and a kernel that carried all twelve variants spilled registers.
-template <typename T, int NU, int MODEL, int NB, bool ROWS>
+template <typename T, int NU, int MODEL, int NB, bool ROWS, bool QPREV>
 __global__ __launch_bounds__(FR_T) void ekf_front_kernel(EkfFrame fr) {
     extern __shared__ __attribute__((aligned(16))) double fr_sm[];
     const int nb = fr.kpad / EKF_RB, nS = nb * (nb + 1) / 2;
     const int bx = blockIdx.x;
     if (bx == 0) fr_role_measure<MODEL>(fr, fr_sm);
-    else if (bx <= nS) fr_role_sblock<T, MODEL, NB, ROWS>(fr, bx - 1, nS, fr_sm);
+    else if (bx <= nS) fr_role_sblock<T, MODEL, NB, ROWS, QPREV>(fr, bx - 1, nS, fr_sm);
     else if (bx == nS + 1) fr_role_factor<NB>(fr, fr_sm);
-    else fr_role_chunk<T, NU, MODEL, NB>(fr, bx - nS - 2, fr_sm);
+    else fr_role_chunk<T, NU, MODEL, NB, QPREV>(fr, bx - nS - 2, fr_sm);
 }
 
-template <typename T, int NU, int MODEL, int NB, bool ROWS>
+template <typename T, int NU, int MODEL, int NB, bool ROWS, bool QPREV>
 static void ekf_front_go_rows(const EkfFrame& fr, hipStream_t s) {
     constexpr int LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     constexpr int NSLOT = EKF_CAM + LMD * EkfModel<MODEL>::NDET16;
     static bool once = false;
     if (!once) {   // > 64 KB of dynamic LDS needs the opt-in
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ekf_front_kernel<T, NU, MODEL, NB, ROWS>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ekf_front_kernel<T, NU, MODEL, NB, ROWS, QPREV>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         once = true;
     }
@@ -1365,14 +1379,17 @@ static void ekf_front_go_rows(const EkfFrame& fr, hipStream_t s) {
     size_t lds = lds_s > lds_c ? lds_s : lds_c;
     if (lds_f > lds) lds = lds_f;
     if ((size_t)fr.lds_min > lds) lds = (size_t)fr.lds_min;
-    hipLaunchKernelGGL((ekf_front_kernel<T, NU, MODEL, NB, ROWS>), dim3(nS + 2 + fr.ncols / 64), dim3(FR_T), lds, s, fr);
+    hipLaunchKernelGGL((ekf_front_kernel<T, NU, MODEL, NB, ROWS, QPREV>), dim3(nS + 2 + fr.ncols / 64), dim3(FR_T), lds, s, fr);
 }
 
-// the instance with or without per-detection noise, by the frame
+// the instance with or without per-detection noise, by the frame; a frame of a pipelined run that completes its rows of P
+// with another Q than it predicts with takes the QPREV instance
 template <typename T, int NU, int MODEL, int NB>
 static void ekf_front_go(const EkfFrame& fr, hipStream_t s) {
-    if (fr.rrow) ekf_front_go_rows<T, NU, MODEL, NB, true>(fr, s);
-    else ekf_front_go_rows<T, NU, MODEL, NB, false>(fr, s);
+    const bool qprev = fr.wprev && (fr.qprev_cam != fr.nz.q_cam || fr.qprev_err != fr.nz.q_err || fr.qprev_lm != fr.nz.q_lm);
+    if (qprev) ekf_front_go_rows<T, NU, MODEL, NB, true, true>(fr, s);
+    else if (fr.rrow) ekf_front_go_rows<T, NU, MODEL, NB, true, false>(fr, s);
+    else ekf_front_go_rows<T, NU, MODEL, NB, false, false>(fr, s);
 }
 
 template <typename T>

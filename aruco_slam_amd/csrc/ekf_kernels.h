@@ -84,7 +84,7 @@ struct EkfFrame {
     int32_t lds_min;           // front kernel: claim at least this much LDS (keeps other kernels' workgroups off its CUs)
     void* wsup;                // pipelined mode, written by the chunks: W[:, support rows of the NEXT frame], [kpad][wsup_ld] in cov dtype (null: none)
     int32_t wsup_ld;
-    EkfNoise nz;
+    EkfNoise nz;               // this frame's noise: Q_eff = fl(s_eff q) per entry (formed on the host), and r_unc
     int32_t quat_mode;
     // fused front kernel (ekf_front_impl.h): exchange buffers between its workgroups.  ONE buffer per
     // fused-frame parity holds everything that travels between workgroups inside a launch:
@@ -114,7 +114,18 @@ struct EkfFrame {
     // tile (I << 16 | J) of block b, 0xFFFFFFFF = none; null: the wave-per-tile kernel (ekf_cov_update.hip)
     const uint32_t* cov_tiles;
     int32_t cov_grid;
+    // Pipelined sequence mode with per-frame process-noise scales (EKF_FLAG_FRAME_SCALE): the front kernel completes rows of
+    // P_{t+1} with the PREVIOUS frame's Q (the covariance update it stands in for ran with that frame's nz) and predicts
+    // with its own.  q_cam / q_err / q_lm of the previous frame of the run; equal to nz's without scales, and read only by
+    // the front-kernel instances a frame with another Q than its predecessor's runs (ekf_front_impl.h: QPREV).  At the end:
+    // every other argument is where it was (the kernel arguments grow from 504 to 528 bytes).
+    double qprev_cam, qprev_err, qprev_lm;
 };
+
+// process-noise diagonal of state dimension i as the PREVIOUS frame of a pipelined run added it (ekf_qdiag on its Q_eff)
+__device__ __forceinline__ double ekf_qdiag_prev(const EkfFrame& fr, int i) {
+    return ekf_qdiag(i, fr.dims, EkfNoise{fr.qprev_cam, fr.qprev_err, fr.qprev_lm, 0.0});
+}
 
 // variance of measurement row r: the one thing of a frame the rows change (the diagonal of S)
 __device__ __forceinline__ double ekf_row_noise(const EkfFrame& fr, int r) { return fr.rrow ? fr.rrow[r] : fr.nz.r_unc; }
@@ -288,6 +299,11 @@ struct EkfBatchWindow {
     const double* gate;             // [B] or null: chi^2 gate on every detection's own d^2 (+inf: off); ekf_batch_gate
     double* mahal;                  // [D] or null: d^2 per detection (0: exempt first sighting, NaN: not tested)
     const double* row_noise;        // [D][RD] or null: per-detection noise, indexed like lm_index (null: the member's r_uncertainty)
+    // Per-frame process-noise scale (EKF_FLAG_FRAME_SCALE; include/ekf_slam_hip.h): pending [B] is every member's pending
+    // scale, loaded at the start of a window and stored at its end (null: a batch without the flag, the constants as they
+    // are); scale [Ftot] is every frame's scale, indexed like frame_offsets (null: 1 for every frame)
+    double* pending;
+    const double* scale;
 };
 // dynamic LDS of one launch (C linkage: the tests read them)
 extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);

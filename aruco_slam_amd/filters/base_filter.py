@@ -200,15 +200,22 @@ class BaseFilter:
             ids, detected_poses, should_filter, iteration)
         return frame, camera_pose, marker_poses, detected_poses
 
-    def process_detections(self, ids, detected_poses, should_filter=True, iteration=0, noise=None):
+    def process_detections(self, ids, detected_poses, should_filter=True, iteration=0, noise=None, scale=None):
         """The part of ``process_frame`` behind the detector
         (base_filter.py:196-212): ``ids`` is None for a frame without
         detections, in which case the filter is NOT stepped (no predict).  ``noise``: the frame's per-detection
-        measurement noise, as ``observe`` takes it (a filter built with ``row_noise=True``)."""
+        measurement noise, as ``observe`` takes it (a filter built with ``row_noise=True``).  ``scale``: the frame's
+        process-noise scale, as ``observe`` takes it (a filter built with ``frame_scale=True``); a frame without
+        detections advances the pending scale by it (``advance``), so the time it took is not lost."""
         if ids is None:
             detected_poses = np.array([])
-        elif should_filter and noise is not None:
-            self.observe(ids, detected_poses, noise=noise)
+            if should_filter and scale is not None:
+                self.advance(scale)
+        elif should_filter and (noise is not None or scale is not None):
+            extra = {} if noise is None else {"noise": noise}
+            if scale is not None:
+                extra["scale"] = scale
+            self.observe(ids, detected_poses, **extra)
         elif should_filter:
             self.observe(ids, detected_poses)
         if should_filter and self._tentative is not None:
@@ -231,6 +238,38 @@ class BaseFilter:
         is updated (one flipped IPPE pose otherwise bends the whole map); None or ``inf``: off.  The filter must have been
         constructed with ``gate=`` (``inf`` will do).  A bad gate raises ``ValueError`` and nothing changes."""
         self.backend.set_gate(gate)
+
+    # -- per-frame process-noise scale (ekf_advance, ekf_observe_scaled) ----------------------------
+    def advance(self, scale) -> None:
+        """Time passes without a frame: ``scale`` (a number >= 0, in the unit of the frames' scales) is added to the pending
+        scale, and the next stepped frame runs with pending + its own scale.  A filter built with ``frame_scale=True``;
+        anything else raises ``ValueError`` and nothing changes."""
+        self.backend.advance(self._frame_scale(scale))
+
+    @property
+    def pending_scale(self) -> float:
+        """The process-noise scale accumulated by frames that were not stepped (no detections, or none that survived the
+        gate) and by ``advance`` since the last stepped frame; 0 after a stepped frame, after ``reset`` and for a filter built
+        without ``frame_scale=True``."""
+        return self.backend.pending_scale
+
+    def _frame_scale(self, scale):
+        """``scale=`` of ``observe`` / ``advance``: None, or a float.  ``ValueError`` for anything that is not a finite
+        number >= 0 and for a filter built without ``frame_scale=True``; checked before the frame changes anything."""
+        if scale is None:
+            return None
+        from ..hip_backend import frame_scale_array
+        if not self.backend.can_frame_scale:
+            raise ValueError("scale= needs a filter built with frame_scale=True")
+        return frame_scale_array(scale)
+
+    def _lm_variances(self, lm_dims: int, predicted: bool) -> np.ndarray:
+        """The landmark part of diag(P), [n, lm_dims]: P of the last stepped frame, or with ``predicted`` what the next
+        stepped frame would start from if no more time passed, diag(P) + fl(pending_scale q_lm) (formed on the host)."""
+        out = self.backend.get_cov_diag()[CAM_DIMS:].reshape(-1, lm_dims)
+        if predicted:
+            out = out + self.backend.pending_scale * float(self.backend.cfg.q_lm)
+        return out
 
     # -- map pruning (ekf_remove_markers) ----------------------------------------------------------
     def remove_marker(self, marker_id) -> None:
@@ -297,13 +336,13 @@ class BaseFilter:
             raise ValueError("noise= needs a filter built with row_noise=True")
         return row_noise_array(noise, count, backend.rows_per_detection)
 
-    def _observe_gated(self, index, z, exempt, rows=None) -> None:
+    def _observe_gated(self, index, z, exempt, rows=None, scale=None) -> None:
         backend = self.backend
-        d2 = backend.observe(index, z, exempt=exempt, mahal=True, rows=rows)
+        d2 = backend.observe(index, z, exempt=exempt, mahal=True, rows=rows, scale=scale)
         self.last_mahal = d2
         self.last_rejected = d2 > backend.gate      # (NaN and 0 compare false; gate inf: nothing)
 
-    def process_detection_log(self, ids, poses, offsets, has_detections=None, mahal=False, noise=None):
+    def process_detection_log(self, ids, poses, offsets, has_detections=None, mahal=False, noise=None, scale=None):
         """``process_detections(ids_t, poses_t)`` with ``should_filter=True`` for every frame of a recorded log, in ONE call
         that runs predict / update of every frame on the device (ekf_observe_log).  The log is a CSR batch as in a replay
         file (``main/run_slam.py: detection_frames``): ``ids [D]``, ``poses [D,6]`` ``[tvec | rvec]`` (NumPy, or a
@@ -315,7 +354,9 @@ class BaseFilter:
         the first occurrence of every marker the log adds exempt; ``mahal=True`` (a filter built with ``gate=``) returns
         ``(trajectory, d2 [D])`` with every detection's squared Mahalanobis distance, indexed like ``ids`` (NaN for the
         rows of frames without detections), gate or no gate; ``d2 > gate`` are the rejected ones.  ``noise``: per-detection
-        measurement noise of the log, [D] or [D, rd] aligned with ``ids`` (a filter built with ``row_noise=True``)."""
+        measurement noise of the log, [D] or [D, rd] aligned with ``ids`` (a filter built with ``row_noise=True``).
+        ``scale``: the frames' process-noise scales, [F], one per frame of the log (a filter built with
+        ``frame_scale=True``): a frame that is not stepped leaves its scale pending for the next stepped one."""
         import torch
         backend = self.backend
         plan = plan_detection_log(self.landmarks, self.num_landmarks, ids, offsets, has_detections)
@@ -331,6 +372,11 @@ class BaseFilter:
         rows = self._frame_noise(noise, plan.keep.shape[0])
         if rows is not None:
             rows = rows[plan.keep]
+        if scale is not None:
+            from ..hip_backend import frame_scale_array
+            if not backend.can_frame_scale:
+                raise ValueError("scale= needs a filter built with frame_scale=True")
+            scale = frame_scale_array(scale, plan.offsets.shape[0] - 1)
         if not plan.keep.all():      # (rows of frames without detections, if there are any, are not part of the replay)
             poses = poses[torch.from_numpy(plan.keep).to(poses.device)] if isinstance(poses, torch.Tensor) else poses[plan.keep]
         if isinstance(poses, torch.Tensor):
@@ -341,7 +387,7 @@ class BaseFilter:
             backend.grow(new_max_visible=min(backend.MAX_VISIBLE_LIMIT[backend.lm_dims], plan.widest))
         traj = torch.empty((plan.offsets.shape[0] - 1, 7), dtype=torch.float64, device=backend.device)
         mahal_t = torch.empty((plan.index.shape[0],), dtype=torch.float64, device=backend.device) if mahal else None
-        backend.observe_log(plan.index, plan.offsets, poses, traj, mahal_t, rows)
+        backend.observe_log(plan.index, plan.offsets, poses, traj, mahal_t, rows, scale)
         backend.sync()
         self.landmarks.update(plan.new_landmarks)
         self.num_landmarks = plan.num_landmarks
@@ -405,7 +451,8 @@ class BaseFilter:
         np.savez(filename, state=np.asarray(self.state, dtype=np.float64),
                  cov=np.asarray(self.uncertainty, dtype=np.float64),
                  marker_ids=np.asarray(ids, dtype=np.int64), filter=type(self).__name__,
-                 gate=np.float64(np.inf if gate is None else gate), row_noise=np.bool_(self.backend.can_row_noise))
+                 gate=np.float64(np.inf if gate is None else gate), row_noise=np.bool_(self.backend.can_row_noise),
+                 frame_scale=np.bool_(self.backend.can_frame_scale), pending_scale=np.float64(self.backend.pending_scale))
 
     def load_checkpoint(self, filename: str) -> None:
         """Inverse of ``save_checkpoint`` on a filter of the same class; the device covariance
@@ -413,20 +460,30 @@ class BaseFilter:
         filter built with ``gate=`` takes the stored one, so a checkpoint saved without a gate (stored as ``inf``) switches
         this filter's gate OFF -- call ``set_gate`` afterwards to keep your own; a stored finite gate needs a filter built
         with ``gate=`` (``ValueError`` otherwise).  Checkpoints from before the gate leave it as it is.  A checkpoint of a
-        filter built with ``row_noise=True`` needs one built the same way (``ValueError`` otherwise)."""
+        filter built with ``row_noise=True`` needs one built the same way (``ValueError`` otherwise), and so does one of a
+        filter built with ``frame_scale=True``, whose pending scale is restored; a checkpoint without it leaves the pending
+        scale 0."""
         with np.load(filename, allow_pickle=False) as ck:
             if str(ck["filter"]) != type(self).__name__:
                 raise ValueError(f"checkpoint of {ck['filter']} loaded into {type(self).__name__}")
             state, cov, ids = ck["state"], ck["cov"], ck["marker_ids"]
             gate = float(ck["gate"]) if "gate" in ck.files else None      # (checkpoints from before the gate: as it is)
             row_noise = bool(ck["row_noise"]) if "row_noise" in ck.files else False
+            frame_scale = bool(ck["frame_scale"]) if "frame_scale" in ck.files else False
+            pending = float(ck["pending_scale"]) if "pending_scale" in ck.files else 0.0
+        if frame_scale and not self.backend.can_frame_scale:
+            raise ValueError("the checkpoint is of a filter with per-frame scales: build this one with frame_scale=True")
         if row_noise and not self.backend.can_row_noise:
             raise ValueError("the checkpoint is of a filter with per-detection noise: build this one with row_noise=True")
         if gate is not None and (np.isfinite(gate) or self.backend.can_gate):
             self.set_gate(gate)      # (a finite gate needs a filter built with gate=: ValueError otherwise)
         if len(ids) == 0:
+            if self.backend.can_frame_scale:
+                self.backend.pending_scale = pending
             return
         self.backend.set_state_cov(state, cov)
+        if self.backend.can_frame_scale:      # (set_state_cov has zeroed it)
+            self.backend.pending_scale = pending
         self.landmarks = {int(k): i for i, k in enumerate(ids)}
         self.num_landmarks = len(ids)
         if self._tentative is not None:      # a checkpoint's landmarks are confirmed, like a map file's
@@ -434,13 +491,13 @@ class BaseFilter:
             self._tentative.confirm(self.landmarks)
 
     # -- abstract back-end API, base_filter.py:327-381 ------------------------
-    def observe(self, ids, poses, noise=None) -> None:
+    def observe(self, ids, poses, noise=None, scale=None) -> None:
         raise NotImplementedError(NOT_IMPLEMENTED_ERROR)
 
     def get_poses(self):
         raise NotImplementedError(NOT_IMPLEMENTED_ERROR)
 
-    def get_lm_uncertainties(self):
+    def get_lm_uncertainties(self, predicted=False):
         raise NotImplementedError(NOT_IMPLEMENTED_ERROR)
 
     def get_lm_estimates(self):

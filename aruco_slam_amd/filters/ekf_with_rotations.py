@@ -46,7 +46,8 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
     def __init__(self, initial_camera_pose, *, max_landmarks: int | None = None, max_visible: int | None = None,
                  cov_dtype: str = "float64", cov_kernel: str = "auto", device: str = "cuda:0",
                  lookahead: bool | None = None, fused: bool = True, noise: dict | None = None,
-                 gate: float | None = None, confirm: tuple | None = None, row_noise: bool = False) -> None:
+                 gate: float | None = None, confirm: tuple | None = None, row_noise: bool = False,
+                 frame_scale: bool = False) -> None:
         """``noise``: values that replace the module's noise constants, keyed by the ``ekf_config`` field names
         (``initial_camera_uncertainty``, ``initial_landmark_uncertainty``, ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``);
         None keeps the reference's constants.  ``gate``: the chi-square gate on every detection's own Mahalanobis
@@ -54,7 +55,8 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         ``inf``: off, but the distances are reported (``last_mahal``); None: a filter without the gate.
         ``confirm``: ``(hits, window)`` = a new landmark must be used again in ``hits`` later frames within ``window``
         frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off.
-        ``row_noise``: the filter takes per-detection measurement noise (``observe(..., noise=)``)."""
+        ``row_noise``: the filter takes per-detection measurement noise (``observe(..., noise=)``).
+        ``frame_scale``: frames may carry a process-noise scale (``observe(..., scale=)``, ``advance``)."""
         super().__init__(initial_camera_pose, None)
         self._initial_pose = np.array(initial_camera_pose)
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -75,7 +77,8 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         constants.update(noise or {})
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype, quat_mode="scalar_first",
                            cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
-                           model="ekf_rotations", noise=constants, gate=gate, row_noise=row_noise)
+                           model="ekf_rotations", noise=constants, gate=gate, row_noise=row_noise,
+                           frame_scale=frame_scale)
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._init_confirm(confirm)
 
@@ -90,10 +93,11 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         return self._hip.get_cov()
 
     # -- :66-90 ----------------------------------------------------------------
-    def observe(self, ids, poses, noise=None) -> None:
+    def observe(self, ids, poses, noise=None, scale=None) -> None:
         """``noise`` (a filter built with ``row_noise=True``): the frame's measurement noise, [m] (one variance per
         detection) or [m, 7] (x y z, then qw qx qy qz, the order of z) instead of ``r_uncertainty``; anything else raises
-        ``ValueError`` before the frame changes anything."""
+        ``ValueError`` before the frame changes anything.  ``scale`` (a filter built with ``frame_scale=True``): the frame's
+        process-noise scale, a number >= 0."""
         if isinstance(ids, np.ndarray) and ids.dtype.kind in "iu":
             ids = ids.reshape(-1).tolist()
         else:
@@ -102,6 +106,7 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
             raise ValueError("observe() needs at least one detection")
         poses = np.asarray(poses, dtype=np.float64).reshape(len(ids), -1)
         rows = self._frame_noise(noise, len(ids))
+        scale = self._frame_scale(scale)
         known = self.landmarks
         try:                                   # steady state: every marker of the frame is in the map already
             index = [known[i] for i in ids]
@@ -119,11 +124,11 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
             index = [known[i] for i in ids]
             if self._hip.can_gate:      # the markers added just now are exempt from the gate (their z = h by construction)
                 z = np.hstack((poses[:, XYZ_DIMS], euler_xyz_to_quat(poses[:, 3:6])))
-                return self._observe_gated(index, z, self._first_occurrences(ids, fresh), rows)
+                return self._observe_gated(index, z, self._first_occurrences(ids, fresh), rows, scale)
         z = np.hstack((poses[:, XYZ_DIMS], euler_xyz_to_quat(poses[:, 3:6])))      # :216-224
         if self._hip.can_gate:
-            return self._observe_gated(index, z, None, rows)
-        self._hip.observe(index, z, rows=rows)
+            return self._observe_gated(index, z, None, rows, scale)
+        self._hip.observe(index, z, rows=rows, scale=scale)
 
     # -- :275-335 --------------------------------------------------------------
     def add_marker(self, idx, pose, uncertainity=None) -> None:
@@ -136,8 +141,10 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         state = self.state
         return state[:CAM_DIMS], state[CAM_DIMS:].reshape(-1, LM_DIMS)
 
-    def get_lm_uncertainties(self) -> np.ndarray:
-        return self._hip.get_cov_diag()[CAM_DIMS:].reshape(-1, LM_DIMS)
+    def get_lm_uncertainties(self, predicted: bool = False) -> np.ndarray:
+        """diag(P) of the landmarks, [n, LM_DIMS]: P of the last stepped frame; ``predicted=True`` adds the process noise
+        of the pending scale, fl(pending_scale q_lm), on the host."""
+        return self._lm_variances(LM_DIMS, predicted)
 
     def get_lm_estimates(self):
         return self.landmarks.items()

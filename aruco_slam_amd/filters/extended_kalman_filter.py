@@ -37,7 +37,7 @@ class EKF(BaseFilter):
                  quat_update: str = "as_written", cov_kernel: str = "auto",
                  device: str = "cuda:0", map_file=None, lookahead: bool | None = None,
                  fused: bool = True, noise: dict | None = None, gate: float | None = None, confirm: tuple | None = None,
-                 row_noise: bool = False) -> None:
+                 row_noise: bool = False, frame_scale: bool = False) -> None:
         """Positional arguments as the reference (:40-43).  Keyword-only extras:
         initial capacity (default: the number of ids of ``aruco_dict`` -- DICT_5X5_50
         has 50, base_filter.py:81-82; the buffers grow when more markers or more
@@ -52,7 +52,9 @@ class EKF(BaseFilter):
         (``last_mahal``); None: a filter without the gate.
         ``confirm``: ``(hits, window)`` = a new landmark must be used again in ``hits`` later frames within ``window``
         frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off.
-        ``row_noise``: the filter takes per-detection measurement noise (``observe(..., noise=)``)."""
+        ``row_noise``: the filter takes per-detection measurement noise (``observe(..., noise=)``).
+        ``frame_scale``: frames may carry a process-noise scale (``observe(..., scale=)``, ``advance``): time between
+        frames, in units of a nominal frame period, multiplies Q, and time without an update is kept for the next one."""
         super().__init__(initial_camera_pose, map_file, aruco_dict)
         self._initial_pose = np.array(initial_camera_pose)      # :46, dtype kept
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -73,7 +75,7 @@ class EKF(BaseFilter):
         constants.update(noise or {})
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype,
                            quat_mode=quat_update, cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
-                           noise=constants, gate=gate, row_noise=row_noise)
+                           noise=constants, gate=gate, row_noise=row_noise, frame_scale=frame_scale)
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._load_initial_map()
         self._init_confirm(confirm)
@@ -92,11 +94,13 @@ class EKF(BaseFilter):
         return self._hip.get_cov()
 
     # -- :58-82 ----------------------------------------------------------------
-    def observe(self, ids, poses, noise=None) -> None:
+    def observe(self, ids, poses, noise=None, scale=None) -> None:
         """Add unseen markers, predict, update.  ``ids``: iterable of marker
         ids; ``poses``: (m, 6) ``[tvec | rvec]``, only ``pose[0:3]`` is used.  ``noise`` (a filter built with
         ``row_noise=True``): the frame's measurement noise, [m] (one variance per detection) or [m, 3] (x, y, z in the
-        camera frame) instead of ``r_uncertainty``; anything else raises ``ValueError`` before the frame changes anything."""
+        camera frame) instead of ``r_uncertainty``; anything else raises ``ValueError`` before the frame changes anything.
+        ``scale`` (a filter built with ``frame_scale=True``): the frame's process-noise scale, a number >= 0; the frame
+        runs with Q times (pending scale + scale)."""
         if isinstance(ids, np.ndarray) and ids.dtype.kind in "iu":
             ids = ids.reshape(-1).tolist()     # (what process_frame passes: ids.flatten(), base_filter.py:199)
         else:
@@ -105,6 +109,7 @@ class EKF(BaseFilter):
             raise ValueError("observe() needs at least one detection")
         poses = np.asarray(poses, dtype=np.float64).reshape(len(ids), -1)
         rows = self._frame_noise(noise, len(ids))
+        scale = self._frame_scale(scale)
         known = self.landmarks
         try:                                   # steady state: every marker of the frame is in the map already
             index = [known[i] for i in ids]
@@ -122,10 +127,10 @@ class EKF(BaseFilter):
                 self.num_landmarks += 1
             index = [known[i] for i in ids]
             if self._hip.can_gate:      # the markers added just now are exempt from the gate (their z = h by construction)
-                return self._observe_gated(index, poses[:, XYZ_DIMS], self._first_occurrences(ids, fresh), rows)
+                return self._observe_gated(index, poses[:, XYZ_DIMS], self._first_occurrences(ids, fresh), rows, scale)
         if self._hip.can_gate:
-            return self._observe_gated(index, poses[:, XYZ_DIMS], None, rows)
-        self._hip.observe(index, poses[:, XYZ_DIMS], rows=rows)
+            return self._observe_gated(index, poses[:, XYZ_DIMS], None, rows, scale)
+        self._hip.observe(index, poses[:, XYZ_DIMS], rows=rows, scale=scale)
 
     # -- :239-290 --------------------------------------------------------------
     def add_marker(self, idx, pose, uncertainity=None) -> None:
@@ -139,8 +144,10 @@ class EKF(BaseFilter):
         state = self.state
         return state[:CAM_DIMS], state[CAM_DIMS:].reshape(-1, LM_DIMS)
 
-    def get_lm_uncertainties(self) -> np.ndarray:
-        return self._hip.get_cov_diag()[CAM_DIMS:].reshape(-1, LM_DIMS)
+    def get_lm_uncertainties(self, predicted: bool = False) -> np.ndarray:
+        """diag(P) of the landmarks, [n, LM_DIMS]: P of the last stepped frame; ``predicted=True`` adds the process noise
+        of the pending scale, fl(pending_scale q_lm), on the host."""
+        return self._lm_variances(LM_DIMS, predicted)
 
     def get_lm_estimates(self):
         return self.landmarks.items()

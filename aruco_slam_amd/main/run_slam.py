@@ -15,6 +15,12 @@ which case the filter is not stepped -- base_filter.py:197-204).  With
 (``process_detection_log``) and the outputs are written afterwards, byte for
 byte what the frame-by-frame loop writes.  The 2-D/3-D viewers are GUI code
 and are not part of this package.
+
+    python -m aruco_slam_amd.main.run_slam --detections replay.npz --frame-period 33.3 --gate 7.815
+
+``--frame-period MS`` makes the predict step time-aware: every frame's process noise is scaled by the time since the
+previous frame in units of ``MS`` (a replay file's ``timestamps_ms``), and frames without an update leave their time
+pending for the next one, so a gated filter finds its way back after a detection dropout.
 """
 from __future__ import annotations
 
@@ -64,7 +70,21 @@ def detection_noise(path: str):
     return np.asarray(det["noise"], dtype=np.float64) if "noise" in det.files else None
 
 
-def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryWriter) -> None:
+def frame_scales(path: str, frame_period_ms: float) -> np.ndarray:
+    """The per-frame process-noise scales of a replay file for ``--frame-period``: ``(t_f - t_{f-1}) / frame_period_ms``
+    from its ``timestamps_ms``, 1 for frame 0.  Timestamps that decrease, or a period that is not a finite number > 0,
+    raise ``ValueError``."""
+    period = float(frame_period_ms)
+    if not (np.isfinite(period) and period > 0.0):
+        raise ValueError(f"--frame-period must be > 0, got {frame_period_ms}")
+    stamps = np.asarray(np.load(path, allow_pickle=False)["timestamps_ms"], dtype=np.float64)
+    steps = np.diff(stamps)
+    if not np.isfinite(stamps).all() or (steps < 0).any():
+        raise ValueError("timestamps_ms must be finite and must not decrease")
+    return np.concatenate((np.ones(min(1, stamps.shape[0])), steps / period))
+
+
+def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryWriter, scales=None) -> None:
     """The whole replay file through ``process_detection_log``, then one trajectory line per frame.  Frames before the first
     stepped one carry the camera pose the filter had before the call (the integer initial pose of a fresh filter), as the
     frame-by-frame loop writes them."""
@@ -72,10 +92,10 @@ def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryW
     offsets, has = det["offsets"], det["has_detections"].astype(bool)
     start_pose = tracker.get_poses()[0]
     noise = detection_noise(path)
-    if noise is None:
-        traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has)
-    else:
-        traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has, noise=noise)
+    extra = {} if noise is None else {"noise": noise}
+    if scales is not None:
+        extra["scale"] = scales
+    traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has, **extra)
     stepped = has & (np.diff(offsets) > 0)
     first = int(np.argmax(stepped)) if stepped.any() else len(has)
     for f, timestamp in enumerate(det["timestamps_ms"]):
@@ -94,6 +114,12 @@ def main(cmdline_args: argparse.Namespace) -> None:
     noise = detection_noise(cmdline_args.detections) if cmdline_args.detections else None
     if noise is not None:
         kwargs["row_noise"] = True      # (the file carries per-detection noise: frame loop and resident replay use it)
+    scales = None
+    if getattr(cmdline_args, "frame_period", None) is not None:
+        if not cmdline_args.detections:
+            raise ValueError("--frame-period reads the timestamps of a detections file: pass --detections <replay.npz>")
+        scales = frame_scales(cmdline_args.detections, cmdline_args.frame_period)
+        kwargs["frame_scale"] = True
     tracker = init_tracker(cmdline_args.filter, initial_pose, **kwargs)
     out_dir = Path(getattr(cmdline_args, "output_dir", "outputs"))
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -103,14 +129,14 @@ def main(cmdline_args: argparse.Namespace) -> None:
         raise ValueError("--resident replays a detections file: pass --detections <replay.npz>")
     with TrajectoryWriter(str(out_dir / "trajectory.txt")) as cam_traj_writer:
         if resident:
-            replay_resident(tracker, cmdline_args.detections, cam_traj_writer)
+            replay_resident(tracker, cmdline_args.detections, cam_traj_writer, scales)
         elif cmdline_args.detections:
             offs = np.load(cmdline_args.detections, allow_pickle=False)["offsets"]
             for f, (timestamp, ids, poses) in enumerate(detection_frames(cmdline_args.detections)):
-                if noise is None or ids is None:
-                    _, camera_pose, _, _ = tracker.process_detections(ids, poses)
-                else:
-                    _, camera_pose, _, _ = tracker.process_detections(ids, poses, noise=noise[int(offs[f]):int(offs[f + 1])])
+                extra = {} if scales is None else {"scale": scales[f]}
+                if noise is not None and ids is not None:
+                    extra["noise"] = noise[int(offs[f]):int(offs[f + 1])]
+                _, camera_pose, _, _ = tracker.process_detections(ids, poses, **extra)
                 cam_traj_writer.write(timestamp, camera_pose)
         else:
             if cv2 is None:
@@ -151,6 +177,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="chi-square gate on every detection's own squared Mahalanobis distance: detections beyond "
                              "it are left out of their frame (ekf: 3 degrees of freedom, 11.345 = 99 %%; ekf_rotations: 7, "
                              "18.475)")
+    parser.add_argument("--frame-period", dest="frame_period", type=float, default=None, metavar="MS",
+                        help="with --detections: scale every frame's process noise by the time since the previous frame "
+                             "in units of MS milliseconds (33.3 for a 30 fps video), from the file's timestamps_ms; frames "
+                             "without an update leave their time pending for the next one (default: off)")
     parser.add_argument("--confirm", type=confirm_pair, default=None, metavar="H,W",
                         help="a new landmark must be used again in H later frames within W frames of its first sighting, "
                              "or it is removed from the map again (default: off)")

@@ -58,6 +58,8 @@ enum { EKF_FLAG_BATCH_WIDE_FRAMES = 32 };
 enum { EKF_FLAG_GATE = 64 };
 /* ekf_config.flags bit 7, read by ekf_* (the single filter) only: per-detection measurement noise (ekf_observe_rows) */
 enum { EKF_FLAG_ROW_NOISE = 128 };
+/* ekf_config.flags bit 8: per-frame process-noise scale (ekf_observe_scaled, ekf_advance; ekf_batch_observe_logs_scaled) */
+enum { EKF_FLAG_FRAME_SCALE = 256 };
 enum { EKF_COVK_AUTO = 0, EKF_COVK_VALU = 1, EKF_COVK_MFMA = 2, EKF_COVK_MFMA_TILE = 3, EKF_COVK_MFMA_MACRO = 4 };
 
 enum {
@@ -103,7 +105,11 @@ typedef struct ekf_config {
                              * (ekf_observe_rows); with bit 6 the workspace then also holds the survivors' rows of a
                              * gated frame (ekf_query_sizes: + 8 rd max_visible bytes, padded to 256; without bit 6
                              * the size does not change: host rows are staged in pinned memory, device rows are read
-                             * where they are).  Without it, sizes, layout and results are as before. */
+                             * where they are).  Without it, sizes, layout and results are as before.
+                             * bit 8 (EKF_FLAG_FRAME_SCALE): frames may carry a process-noise scale and the filter keeps a
+                             * pending scale (see "Per-frame process-noise scale").  The single filter's sizes do not
+                             * change (the pending scale lives on the host); a batch's workspace grows by 8 bytes per
+                             * member, padded to 256.  Without it, sizes, layout and results are as before. */
     /* noise constants, defaults = extended_kalman_filter.py:21-27 */
     double initial_camera_uncertainty;   /* 0.1  */
     double initial_landmark_uncertainty; /* 0.7  */
@@ -600,6 +606,76 @@ int ekf_remove_markers(ekf_filter *f, const int32_t *lm_index /* [count] HOST */
 int ekf_batch_remove_workspace_bytes(const ekf_batch *b, int64_t total, size_t *bytes);
 int ekf_batch_remove_markers(ekf_batch *b, const int32_t *lm_index /* [total] HOST */, const int64_t *offsets /* [B+1] HOST */,
                              double *cov_dev_new, int64_t ld, double *state_dev_new, void *remove_ws, size_t remove_ws_bytes);
+
+/* ---- Per-frame process-noise scale (time-aware predict; ekf_config.flags bit 8, EKF_FLAG_FRAME_SCALE, single filter and
+ * batch).  Every update steps the covariance with P + Q, Q = diag(q_cam, 0 (quaternion), q_err, q_lm ...).  With a scale the
+ * frame's Q is multiplied by the time that has passed, in units the caller chooses (frames of a nominal rate, say), and time
+ * that passes without an update is kept and added to the next update.
+ * Semantics (part of the ABI):
+ *   1. A frame may carry a scale s (f64, finite, >= 0).  It is data of the frame, like z and the rows, not a noise constant.
+ *      A frame WITHOUT a scale (the calls that take none; scale = NULL in those that do) is the frame as it ever was:
+ *      stepped, it runs with s_eff = p + 1 (and p = 0 afterwards); not stepped, it leaves p alone.
+ *   2. The filter (every member of a batch) carries one more number, the pending scale p: f64, >= 0, 0 after create and
+ *      after reset.
+ *   3. A frame that is STEPPED runs with s_eff = p + s (one f64 addition) and
+ *          Q_eff = diag(fl(s_eff q_cam), 0 (quaternion), fl(s_eff q_err), fl(s_eff q_lm) ...),
+ *      every entry one f64 multiplication, rounded before it is added to anything.  Q_eff is used wherever the frame uses Q:
+ *      the gate's S_d, A = H (P+Q), S, and the diagonal of the covariance update.  After the frame p = 0.
+ *   4. A frame that is NOT stepped (no detections, or no detection survived the gate) sets p = p + s and changes nothing
+ *      else: its trajectory row repeats, its nis is 0, its distances are reported as ever.  A failed filter or a failed
+ *      member ignores scales, as it ignores everything.
+ *   5. Bit rules.  (a) No scale given (p = 0), or every scale exactly 1.0 with no frame that is not stepped, is bit for bit
+ *      the call without scales.  (b) A stepped frame with s_eff is bit for bit the plain frame on a filter configured with
+ *      (fl(s_eff q_cam), fl(s_eff q_err), fl(s_eff q_lm)): state, P, trajectory, d^2 and nis.  (c) A log is bit for bit the
+ *      log with its frames that are not stepped deleted and their scales folded into the next stepped frame by rule 3's
+ *      addition, in log order.  (d) Rule 6 of the gate and rules 3, 4 and 6 of the per-detection noise hold unchanged with
+ *      scales present.  (e) With scales present the log replay is bitwise the per-frame loop, the pipelined sequence is
+ *      bitwise the serial order, and the batch large-map and wide-frame kernels are bitwise the one-column kernel where
+ *      both run.
+ *   6. s = 0 is legal: that frame adds no process noise.  First sightings are added as before (initial_landmark_uncertainty)
+ *      and, under rule 3, see the whole s_eff on their diagonal like every other state dimension.
+ *   7. The covariance getters return P of the last stepped frame; p is reported separately (ekf_get_pending_scale).
+ * Without EKF_FLAG_FRAME_SCALE a call that is given a scale returns EKF_ERR_STATE (ekf_get_pending_scale reports 0); a scale
+ * that is NaN, Inf or negative gives EKF_ERR_INVALID; both before anything is enqueued.
+ * Single filter: the scales are HOST data and p is kept on the host, which launches every frame and already plans empty
+ * frames and the gate's round trips.  ekf_reset and ekf_set_state zero p; ekf_grow and ekf_remove_markers keep it.
+ *   ekf_advance: rule 4 with no frame (time passes, nothing is observed): p = p + scale.
+ *   ekf_observe_scaled: ekf_observe_rows with the frame's scale.
+ *   ekf_observe_sequence_device_scaled: ekf_observe_sequence_device_rows with scale [frames] HOST or NULL; pipelined where
+ *     that call would be (the front kernel of frame t+1 completes its rows of P_{t+1} with frame t's Q_eff and predicts with
+ *     its own).
+ *   ekf_observe_log_scaled: ekf_observe_log_rows with scale [F] HOST or NULL, one entry per frame, empty frames included.
+ * Batch: the flag gives every member a pending scale on the device ([B] doubles in the batch workspace), loaded by a window
+ * kernel at its start and stored at its end.  ekf_batch_reset zeroes it (of the members it resets), ekf_batch_set_member
+ * zeroes the member's, ekf_batch_remove_markers keeps it.
+ *   ekf_batch_observe_logs_scaled: ekf_batch_observe_logs_rows with scale_dev [Ftot] DEVICE or NULL, indexed like the frames
+ *     (frame_offsets); the caller's contract, like rows_dev: finite and >= 0.  The kernels form fl(s_eff q) with an explicitly
+ *     rounded multiply once per frame.
+ *   ekf_batch_get_pending_scale / ekf_batch_set_pending_scale: member = -1: every member, [B]; member >= 0: that one, [1].
+ *     Both synchronise.
+ * The replica entry points keep scale 1, as they keep the constant r_uncertainty (a member's pending scale goes into its
+ * first stepped frame, by rule 1). */
+int ekf_advance(ekf_filter *f, double scale);
+int ekf_get_pending_scale(const ekf_filter *f, double *out);
+int ekf_set_pending_scale(ekf_filter *f, double pending);
+int ekf_observe_scaled(ekf_filter *f, const int32_t *lm_index, const double *z, const double *rows /* [m, rd] host or NULL */,
+                       int32_t m, const uint8_t *exempt /* [m] or NULL */, double *mahal /* [m] host or NULL */,
+                       int32_t *survivors /* or NULL */, double scale);
+int ekf_observe_sequence_device_scaled(ekf_filter *f, const int32_t *lm_index_dev, const double *z_dev,
+                                       const double *rows_dev /* [frames, m, rd] or NULL */,
+                                       const double *scale /* [frames] HOST or NULL */, int32_t m, int32_t frames,
+                                       double *trajectory_dev);
+int ekf_observe_log_scaled(ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames,
+                           const double *poses_dev, const double *rows_dev /* [D, rd] or NULL */,
+                           const double *scale /* [F] HOST or NULL */, void *log_ws, size_t log_ws_bytes,
+                           double *trajectory_dev, double *mahal_dev /* [D] or NULL */);
+int ekf_batch_observe_logs_scaled(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets,
+                                  const int64_t *member_frames, const double *poses_dev,
+                                  const double *rows_dev /* [D, rd] or NULL */, const double *scale_dev /* [Ftot] or NULL */,
+                                  void *log_ws, size_t log_ws_bytes, double *trajectory_dev, double *nis_dev,
+                                  double *cam_cov_dev, double *mahal_dev);
+int ekf_batch_get_pending_scale(ekf_batch *b, int32_t member, double *out);
+int ekf_batch_set_pending_scale(ekf_batch *b, int32_t member, const double *pending);
 
 const char *ekf_last_error_string(void);
 

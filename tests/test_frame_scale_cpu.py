@@ -1,0 +1,178 @@
+"""Per-frame process-noise scale on the CPU: the restatements of ``frame_scale_util`` against the oracle they wrap, the
+conditions the lock-out fixture was chosen for, the premise of the one-step bounds, and the argument checks that need no
+device.  ``test_frame_scale.py`` / ``test_batch_frame_scale.py`` run the same cases on the GPU."""
+import numpy as np
+import pytest
+
+import frame_scale_util as fs
+import gating_util as gu
+import row_noise_util as rn
+import update_sweep_util as sw
+from conftest import report
+
+MODELS = ["ekf", "ekf_rotations"]
+QM = {"ekf": "ekf", "ekf_rotations": "rot"}
+
+
+# ---- the restatements -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("model", ["ekf", "rot"])
+def test_scale_one_is_the_extended_step_bit_for_bit(model):
+    from oracle.ekf_extended import extended_step
+    state, p, lm_ids, ids, poses = sw.dense_prior(model, 20, 6, 11)
+    want = extended_step(sw.oracle_at(model, state, p, lm_ids), ids, poses, factors=True)
+    got = fs.extended_step_scaled(sw.oracle_at(model, state, p, lm_ids), ids, poses, 1.0, factors=True)
+    assert set(want) == set(got)
+    for key in want:
+        assert np.array_equal(np.asarray(want[key]), np.asarray(got[key])), key
+    other = fs.extended_step_scaled(sw.oracle_at(model, state, p, lm_ids), ids, poses, 2.5)
+    assert not np.array_equal(other["P1"], want["P1"])      # (the wrapper is read)
+    # ... and with rows
+    rows = np.full((6, rn.RD[model]), 0.9)
+    a = rn.extended_step_rows(sw.oracle_at(model, state, p, lm_ids), ids, poses, rows)
+    b = fs.extended_step_scaled(sw.oracle_at(model, state, p, lm_ids), ids, poses, 1.0, rows=rows)
+    assert np.array_equal(a["P1"], b["P1"]) and np.array_equal(a["x1"], b["x1"])
+
+
+def test_the_wrapper_multiplies_once_and_leaves_the_oracle_as_it_was():
+    state, p, lm_ids, _ids, _poses = sw.dense_prior("ekf", 5, 2, 3)
+    orc = sw.oracle_at("ekf", state, p, lm_ids)
+    base = orc.process_noise_diag()
+    with fs.scaled(orc, 0.3) as wrapped:
+        assert np.array_equal(wrapped.process_noise_diag(), np.float64(0.3) * base)
+    assert np.array_equal(orc.process_noise_diag(), base)
+    want = {"q_cam": 0.3 * 0.3, "q_err": 0.3 * 0.5, "q_lm": 0.3 * 0.01}
+    assert fs.scaled_constants("ekf", 0.3) == want
+    assert fs.scaled_constants("ekf_rotations", 7.5)["q_cam"] == 7.5 * 0.2
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_replay_without_scales_is_the_existing_gated_replay(model):
+    """scale=None (no frame carries one) on gating_util's dirty log -- empty frames and frames whose detections are all
+    rejected included -- and scales all 1 on the clean log (every frame stepped): d^2 and decisions bit for bit."""
+    clean = gu.clean_log(model, "column", seed=0)
+    dirty, marks = gu.dirty_log(model, clean, seed=0)
+    gate = gu.GATES[model]
+    d2, rej = gu.oracle_gated_replay(model, dirty, gate)
+    got = fs.oracle_scaled_replay(model, dirty, None, gate)
+    assert np.array_equal(got["d2"], d2) and np.array_equal(got["rejected"], rej) and np.array_equal(rej, marks)
+    assert got["pending"] == 0.0 and not got["stepped"].all()
+    d2c, rejc = gu.oracle_gated_replay(model, clean, gate)
+    ones = fs.oracle_scaled_replay(model, clean, np.ones(len(clean["offsets"]) - 1), gate)
+    assert ones["stepped"].all() and np.array_equal(ones["d2"], d2c) and not rejc.any()
+    # with scales 1 on the dirty log the frames that are not stepped count: the next frame runs with more than 1
+    counted = fs.oracle_scaled_replay(model, dirty, np.ones(len(dirty["offsets"]) - 1), gate)
+    assert np.nanmax(counted["s_eff"]) >= 2.0
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_folding_a_log_is_the_log(model):
+    """Bit rule 5(c) on the oracle: the ragged log with empty frames and scales against its folded form."""
+    log, scale = fs.ragged_scaled_log(model)
+    assert (np.diff(log["offsets"]) == 0).sum() >= 8 and (scale == 0).sum() == 2
+    full = fs.oracle_scaled_replay(model, log, scale)
+    folded, fscale, left = fs.fold_log(log, scale)
+    assert left == full["pending"] == scale[-1] and len(fscale) == full["stepped"].sum()
+    assert np.array_equal(fscale, full["s_eff"][full["stepped"]])
+    short = fs.oracle_scaled_replay(model, folded, fscale)
+    assert np.array_equal(np.asarray(short["orc"].state), np.asarray(full["orc"].state))
+    assert np.array_equal(short["orc"].uncertainty, full["orc"].uncertainty)
+    assert np.array_equal(short["trajectory"], full["trajectory"][full["stepped"]])
+
+
+# ---- the lock-out fixture -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("model", MODELS)
+def test_lockout_fixture_conditions(model):
+    """Without scales every detection of every frame after the gap has d^2 >= 2 gate: the filter is locked out for the rest
+    of the run.  With the scales of the timestamps the first frame after the gap has every d^2 <= gate / 2, and the run ends
+    within LOCKOUT_FACTOR of the position error of the same log without the jump.  The factor-2 margins are conditions, not
+    measurements: they keep device rounding from flipping a decision."""
+    gate = fs.LOCKOUT_GATES[model]
+    log = fs.lockout_log(model)
+    offs, fa = log["offsets"], log["first_after"]
+    counts = np.diff(offs)
+    gap = fs.LOCKOUT[model][0]
+    assert (counts[:fs.LOCKOUT_BEFORE] >= 3).all() and (counts[:fs.LOCKOUT_BEFORE] <= 4).all()
+    assert (counts[fs.LOCKOUT_BEFORE:fa] == 0).all() and fa - fs.LOCKOUT_BEFORE == gap and len(counts) - fa >= 20
+    assert len(set(log["ids"][:int(offs[fs.LOCKOUT_BEFORE])].tolist())) == 10      # (no first sighting after the gap)
+    assert np.allclose(np.diff(log["timestamps_ms"]), fs.FRAME_MS) and np.allclose(log["scale"], 1.0, rtol=1e-12)
+    after = slice(int(offs[fa]), None)
+    first = slice(int(offs[fa]), int(offs[fa + 1]))
+
+    plain = fs.oracle_scaled_replay(model, log, None, gate)
+    assert not plain["rejected"][:int(offs[fa])].any()
+    assert plain["rejected"][after].all() and not plain["stepped"][fa:].any()
+    assert (plain["d2"][after] >= 2.0 * gate).all(), plain["d2"][after].min() / gate
+
+    timed = fs.oracle_scaled_replay(model, log, log["scale"], gate)
+    assert (timed["d2"][first] <= 0.5 * gate).all(), timed["d2"][first].max() / gate
+    assert timed["stepped"][fa] and abs(timed["s_eff"][fa] - (gap + 1)) < 1e-9
+    assert not timed["rejected"].any() and timed["pending"] == 0.0
+    tested = timed["d2"] > 0
+    assert (np.abs(timed["d2"][tested] / gate - 1.0) > 100 * gu.FREE_MARGIN).all()      # (no decision near the gate)
+
+    still = fs.lockout_log(model, jump=0.0)
+    base = fs.oracle_scaled_replay(model, still, still["scale"], gate)
+    err, err0 = fs.position_error(timed, log), fs.position_error(base, still)
+    report(f"frame_scale_lockout[{model}]", d2_unscaled_over_gate=float(plain["d2"][after].min() / gate),
+           d2_scaled_over_gate=float(timed["d2"][first].max() / gate), position_error=err, position_error_no_jump=err0,
+           factor=err / err0)
+    assert err <= fs.LOCKOUT_FACTOR * err0, (err, err0)
+    assert fs.position_error(plain, log) > 0.9 * fs.LOCKOUT[model][1]      # (locked out: the camera stays where it was)
+
+
+# ---- the one-step cases ---------------------------------------------------------------------------------------------------
+def test_step_cases_keep_the_premise_of_the_componentwise_bounds():
+    """kappa(S) <= 1e3 (update_sweep_util.KAPPA_MAX) for every case and both covariance dtypes, asserted on the reference
+    alone; every scale differs from 1 and lies in its case's range."""
+    refs = fs.step_references()
+    groups = {c[0] for c in fs.STEP_CASES}
+    assert groups == {"ekf_fused", "ekf_stage", "ekf_wide", "ekf_blocked", "rot_fused", "rot_stage", "rot_wide"}
+    assert sorted(c[3] for c in fs.STEP_CASES if c[0] == "ekf_fused") == [1, 5, 6, 16, 33, 64]
+    assert sorted(c[3] for c in fs.STEP_CASES if c[1] == "rot") == [1, 9, 28, 51]
+    worst = 0.0
+    for (case, dt), (_prior, s, ref) in refs.items():
+        lo, hi = case[6]
+        assert lo <= s <= hi and s != 1.0 and 0.25 <= lo and hi <= 8.0, (case, s)
+        assert ref["kappa"] <= sw.KAPPA_MAX, (case[:4], dt, s, ref["kappa"])
+        worst = max(worst, ref["kappa"])
+    report("frame_scale_step_cases", cases=len(refs), kappa_max=worst)
+
+
+# ---- host validation that needs no device ---------------------------------------------------------------------------------
+def test_scale_arrays_are_validated_on_the_host():
+    from aruco_slam_amd.hip_backend import frame_scale_array
+    assert frame_scale_array(0.0) == 0.0 and frame_scale_array(np.float32(2.0)) == 2.0
+    out = frame_scale_array([0.0, 1.5, 3], 3)
+    assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"] and out.tolist() == [0.0, 1.5, 3.0]
+    for bad in (np.nan, np.inf, -np.inf, -1e-300, "x", [1.0], None):
+        with pytest.raises(ValueError, match="scale"):
+            frame_scale_array(bad)
+    for bad in ([1.0, 2.0], np.ones((3, 1)), [1.0, np.nan, 1.0], [1.0, -1.0, 1.0], [np.inf, 1.0, 1.0], 1.0):
+        with pytest.raises(ValueError, match="scale"):
+            frame_scale_array(bad, 3)
+
+
+def test_run_slam_scales_from_timestamps(tmp_path):
+    from aruco_slam_amd.main import run_slam
+    stamps = np.array([100.0, 133.3, 166.6, 266.5, 266.5])
+    np.savez(tmp_path / "a.npz", timestamps_ms=stamps)
+    got = run_slam.frame_scales(str(tmp_path / "a.npz"), 33.3)
+    assert got[0] == 1.0 and np.array_equal(got[1:], np.diff(stamps) / 33.3) and got[-1] == 0.0
+    np.savez(tmp_path / "b.npz", timestamps_ms=np.array([100.0, 133.3, 120.0]))
+    with pytest.raises(ValueError, match="decrease"):
+        run_slam.frame_scales(str(tmp_path / "b.npz"), 33.3)
+    for bad in (0.0, -1.0, np.nan, np.inf):
+        with pytest.raises(ValueError, match="frame-period"):
+            run_slam.frame_scales(str(tmp_path / "a.npz"), bad)
+    args = run_slam.build_parser().parse_args(["--detections", "x.npz", "--frame-period", "33.3"])
+    assert args.frame_period == 33.3 and run_slam.build_parser().parse_args([]).frame_period is None
+
+
+def test_the_abi_declares_the_new_entry_points():
+    from aruco_slam_amd import hip_backend
+    header = (sw.REPO / "include" / "ekf_slam_hip.h").read_text()
+    for name in ("ekf_advance", "ekf_get_pending_scale", "ekf_set_pending_scale", "ekf_observe_scaled",
+                 "ekf_observe_sequence_device_scaled", "ekf_observe_log_scaled", "ekf_batch_observe_logs_scaled",
+                 "ekf_batch_get_pending_scale", "ekf_batch_set_pending_scale"):
+        assert name in hip_backend.EXPORTED_SYMBOLS and f"int {name}(" in header, name
+    assert hip_backend.EKF_FLAG_FRAME_SCALE == 256 and "EKF_FLAG_FRAME_SCALE = 256" in header

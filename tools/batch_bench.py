@@ -77,6 +77,9 @@ def main():
     ap.add_argument("--row-noise", action="store_true",
                     help="also time the same logs with per-detection noise (EKFBatch(row_noise=True), log-uniform rows in "
                          "[0.3, 3]) and report its frames/s beside the figure without")
+    ap.add_argument("--frame-scale", action="store_true",
+                    help="also time the same logs with a process-noise scale on every frame (EKFBatch(frame_scale=True), "
+                         "log-uniform scales in [0.5, 2]) and report its frames/s beside the figure without")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.batch import EKFBatch
@@ -137,6 +140,21 @@ def main():
             line["row_noise_wall_s"] = round(wall_rows, 6)
             line["row_noise_frames_per_s"] = round(B * args.steady / wall_rows, 1)
             del rows
+        if args.frame_scale:
+            rng = np.random.default_rng(98)
+            timed = [tuple(dict(part, scale=np.exp(rng.uniform(np.log(0.5), np.log(2.0), len(part["offsets"]) - 1)))
+                           for part in lg) for lg in logs[:B]]
+            scaled = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model, frame_scale=True,
+                              large_maps=True if args.large_maps else None, **({} if args.gate is None else {"gate": args.gate}))
+            scaled.process_detection_logs([lg[0] for lg in timed])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            scaled.process_detection_logs([lg[1] for lg in timed])
+            wall_scaled = time.perf_counter() - t0
+            assert scaled.status() == [0] * B
+            line["frame_scale_wall_s"] = round(wall_scaled, 6)
+            line["frame_scale_frames_per_s"] = round(B * args.steady / wall_scaled, 1)
+            del scaled
         if args.large_maps or batch.wide_frames:     # every stepped frame reads and writes the member's N x N f64 covariance
             # once (wide frames: once per block)
             dims = (10 if rot else 3) * n + 10

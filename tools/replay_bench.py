@@ -12,6 +12,7 @@ updates/s is steady frames per second of the steady segment; the bootstrap segme
     python tools/replay_bench.py --gate 1e300      # every frame through the gate kernel, nothing rejected: the price of
                                                    # the host round trip per frame and of losing the pipelined mode
     python tools/replay_bench.py --row-noise       # every detection with its own row variances (log-uniform in [0.3, 3])
+    python tools/replay_bench.py --frame-scale     # every frame with its own process-noise scale (log-uniform in [0.5, 2])
 """
 from __future__ import annotations
 
@@ -36,7 +37,8 @@ def _segment(log, t0, t1):
 
 def _filter(args):
     from aruco_slam_amd.filters.extended_kalman_filter import EKF
-    return EKF(INIT, max_landmarks=args.n, max_visible=args.m[1], cov_dtype=args.dtype, gate=args.gate, row_noise=args.row_noise)
+    return EKF(INIT, max_landmarks=args.n, max_visible=args.m[1], cov_dtype=args.dtype, gate=args.gate, row_noise=args.row_noise,
+               frame_scale=args.frame_scale)
 
 
 def main():
@@ -49,6 +51,7 @@ def main():
     ap.add_argument("--variants", default="per_frame,log,sequence")
     ap.add_argument("--gate", type=float, default=None, help="chi-square gate on every detection (default: a filter without)")
     ap.add_argument("--row-noise", action="store_true", help="per-detection measurement noise on every detection (noise=)")
+    ap.add_argument("--frame-scale", action="store_true", help="a process-noise scale on every frame (scale=)")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.synthetic import SyntheticStream, ragged_log
@@ -61,11 +64,18 @@ def main():
     if args.row_noise:
         noise = np.exp(np.random.default_rng(args.seed + 7).uniform(np.log(0.3), np.log(3.0), (len(log["ids"]), 3)))
 
+    scale = None
+    if args.frame_scale:
+        scale = np.exp(np.random.default_rng(args.seed + 9).uniform(np.log(0.5), np.log(2.0), frames))
+
     def seg_noise(t0, t1):
-        return {} if noise is None else {"noise": noise[int(log["offsets"][t0]):int(log["offsets"][t1])]}
+        kw = {} if noise is None else {"noise": noise[int(log["offsets"][t0]):int(log["offsets"][t1])]}
+        if scale is not None:
+            kw["scale"] = scale[t0:t1]
+        return kw
 
     common = {"n": args.n, "m_range": list(args.m), "m_mean": float(m_steady.mean()), "dtype": args.dtype, "gate": args.gate,
-              "row_noise": bool(args.row_noise),
+              "row_noise": bool(args.row_noise), "frame_scale": bool(args.frame_scale),
               "bootstrap_frames": boot, "steady_frames": args.steady}
 
     def emit(**kv):
@@ -81,7 +91,10 @@ def main():
             def run(t0, t1):
                 for t in range(t0, t1):
                     sl = slice(int(offs[t]), int(offs[t + 1]))
-                    flt.process_detections(log["ids"][sl], log["poses"][sl], **({} if noise is None else {"noise": noise[sl]}))
+                    kw = {} if noise is None else {"noise": noise[sl]}
+                    if scale is not None:
+                        kw["scale"] = scale[t]
+                    flt.process_detections(log["ids"][sl], log["poses"][sl], **kw)
             t = time.perf_counter()
             run(0, boot)
             b.sync()
@@ -122,7 +135,7 @@ def main():
                     np.log(0.3), np.log(3.0), tuple(z_t.shape)))).to(b.device)
             torch.cuda.synchronize(b.device)
             t = time.perf_counter()
-            b.observe_sequence(idx_t, z_t, rows=rows_t)
+            b.observe_sequence(idx_t, z_t, rows=rows_t, scale=None if scale is None else scale[boot:boot + args.steady])
             b.sync()
             t_steady = time.perf_counter() - t
             rates[variant] = args.steady / t_steady

@@ -40,8 +40,9 @@ from typing import NamedTuple
 import numpy as np
 
 from .filters.base_filter import plan_detection_log
-from .hip_backend import (EKF_FLAG_BATCH_LARGE_MAPS, EKF_FLAG_BATCH_WIDE_FRAMES, EKF_FLAG_FRAME_SCALE, EKF_QUAT_AS_WRITTEN,
-                          EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError, _dptr, frame_scale_array, load_library, row_noise_array)
+from .hip_backend import (EKF_FLAG_BATCH_LARGE_MAPS, EKF_FLAG_BATCH_WIDE_FRAMES, EKF_FLAG_FRAME_SCALE, EKF_FLAG_MOTION,
+                          EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError, _dptr, frame_scale_array,
+                          load_library, motion_array, row_noise_array)
 
 NOISE_KEYS = ("initial_camera_uncertainty", "initial_landmark_uncertainty", "r_uncertainty", "q_cam", "q_err", "q_lm")
 EKF_ERR_NUMERIC = -5
@@ -346,7 +347,9 @@ class EKFBatch:
     ``set_gate`` (kept in ``self.gate``); ``row_noise``: the logs may carry per-detection measurement noise (``"noise"`` in
     ``process_detection_logs``, ``noise=`` of ``observe_indexed``; kept in ``self.row_noise``); ``frame_scale``: the logs
     may carry a process-noise scale per frame (``"scale"`` in ``process_detection_logs``, ``scale=`` of ``observe_indexed``)
-    and every member keeps a pending scale (``pending_scale``; kept in ``self.frame_scale``)."""
+    and every member keeps a pending scale (``pending_scale``; kept in ``self.frame_scale``); ``motion``: the logs may carry
+    the camera's motion before every frame (``"motion"`` in ``process_detection_logs``, ``motion=`` of ``observe_indexed``;
+    kept in ``self.motion``)."""
 
     gate = None        # [B] chi-square gate per member, or None: no gate (set_gate)
     camera = None      # (camera matrix [9], distortion coefficients, marker size) of corner logs, or None (set_camera)
@@ -354,7 +357,7 @@ class EKFBatch:
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
                  quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf",
                  large_maps: bool | None = None, wide_frames: bool | None = None, gate=None, row_noise: bool = False,
-                 frame_scale: bool = False) -> None:
+                 frame_scale: bool = False, motion: bool = False) -> None:
         import torch
         gate = gate_array(gate, int(members))
         if model not in MODELS:
@@ -375,6 +378,7 @@ class EKFBatch:
         self.members = int(members)
         self.row_noise = bool(row_noise)
         self.frame_scale = bool(frame_scale)
+        self.motion = bool(motion)
         self.device = torch.device(device)
         self.model = model
         self.lm_dims = LM_DIMS[model]
@@ -392,6 +396,8 @@ class EKFBatch:
             cfg.flags |= EKF_FLAG_BATCH_WIDE_FRAMES
         if self.frame_scale:
             cfg.flags |= EKF_FLAG_FRAME_SCALE
+        if self.motion:
+            cfg.flags |= EKF_FLAG_MOTION
         if model == "ekf_rotations":
             from .filters import ekf_with_rotations as rot
             for key, val in zip(NOISE_KEYS, (rot.INITIAL_CAMERA_UNCERTAINTY, rot.INITIAL_LANDMARK_UNCERTAINTY,
@@ -497,7 +503,10 @@ class EKFBatch:
         carries none keeps its constant (the same bits as without any ``noise`` in the call).
         A log may carry ``scale`` ([F], one per frame, empty frames included; a batch built with ``frame_scale=True``): the
         frames' process-noise scales.  A frame that is not stepped leaves its scale in the member's pending scale, which the
-        next stepped frame adds to its own.  Either every log of a call carries scales or none does."""
+        next stepped frame adds to its own.  Either every log of a call carries scales or none does.
+        A log may carry ``motion`` ([F, 6], one row per frame, empty frames included; a batch built with ``motion=True``):
+        the camera's motion ``(d, w)`` before every frame, in the camera frame of the previous pose.  A frame that is not
+        stepped is still moved.  Either every log of a call carries motions or none does."""
         gated = mahal or self.gate is not None
         if len(logs) != self.members:
             raise ValueError(f"need {self.members} logs (None for a member without one), got {len(logs)}")
@@ -511,7 +520,13 @@ class EKFBatch:
                 raise ValueError("a log with scale needs a batch built with frame_scale=True")
             if not all(w for w, log in zip(with_scale, logs) if log is not None):
                 raise ValueError("either every log of a call carries scale or none does")
-        scales = []
+        with_motion = [log is not None and log.get("motion") is not None for log in logs]
+        if any(with_motion):
+            if not self.motion:
+                raise ValueError("a log with motion needs a batch built with motion=True")
+            if not all(w for w, log in zip(with_motion, logs) if log is not None):
+                raise ValueError("either every log of a call carries motion or none does")
+        scales, motions = [], []
         corner_parts = []       # (first row, kept corners [n,4,2]) of every log that carries corners
         base = 0
         for b, log in enumerate(logs):
@@ -543,6 +558,8 @@ class EKFBatch:
                 rows.append(r[plan.keep])
             if with_scale[b]:
                 scales.append(frame_scale_array(log["scale"], plan.offsets.shape[0] - 1, f"member {b}: scale"))
+            if with_motion[b]:
+                motions.append(motion_array(log["motion"], plan.offsets.shape[0] - 1, f"member {b}: motion"))
             plans.append(plan)
             index.append(plan.index)
             offsets.append(plan.offsets[1:] + base)
@@ -557,6 +574,8 @@ class EKFBatch:
         with_rows = {"noise": np.concatenate(rows)} if any_rows and rows else {}      # (no rows: the call as it ever was)
         if scales:
             with_rows["scale"] = np.concatenate(scales)
+        if motions:
+            with_rows["motion"] = np.concatenate(motions)
         if gated:
             traj, nis_v, cov_v, mahal_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses,
                                                                nis=nis, cam_cov=cam_cov, mahal=True, **with_rows)
@@ -755,7 +774,7 @@ class EKFBatch:
                                    cov_t.cpu().numpy() if cam_cov else None, full, rej, flipped)
 
     def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False,
-                        mahal: bool = False, noise=None, scale=None):
+                        mahal: bool = False, noise=None, scale=None, motion=None):
         """The C call behind ``process_detection_logs`` (landmark indices already assigned; ``landmarks`` is not
         touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1] on the host, poses [D,6] on the host or a contiguous
         float64 tensor on the batch's device, produced on the batch's stream.  Returns the
@@ -764,7 +783,8 @@ class EKFBatch:
         on every call, whatever it returns.  ``noise``: [D] or [D, RD] row variances indexed like lm_index (a batch built
         with ``row_noise=True``; ekf_batch_observe_logs_rows), or None: every member's ``r_uncertainty``.  ``scale``:
         [Ftot] process-noise scales, one per frame, indexed like frame_offsets (a batch built with ``frame_scale=True``;
-        ekf_batch_observe_logs_scaled), or None: no frame carries one."""
+        ekf_batch_observe_logs_scaled), or None: no frame carries one.  ``motion``: [Ftot, 6] camera motions, one per
+        frame, indexed like frame_offsets (a batch built with ``motion=True``; ekf_batch_observe_logs_moved), or None."""
         torch = self._torch
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
         if noise is not None:
@@ -773,6 +793,8 @@ class EKFBatch:
             noise = row_noise_array(noise, idx.shape[0], RD[self.model])
         if scale is not None and not self.frame_scale:
             raise ValueError("scale= needs a batch built with frame_scale=True")
+        if motion is not None and not self.motion:
+            raise ValueError("motion= needs a batch built with motion=True")
         fo = np.ascontiguousarray(frame_offsets, dtype=np.int64).reshape(-1)
         mf = np.ascontiguousarray(member_frames, dtype=np.int64).reshape(-1)
         on_device = isinstance(poses, torch.Tensor)
@@ -791,6 +813,8 @@ class EKFBatch:
             raise ValueError("frame_offsets, lm_index and poses do not match")
         if scale is not None:
             scale = frame_scale_array(scale, frames)
+        if motion is not None:
+            motion = motion_array(motion, frames)
         nbytes = C.c_size_t()
         self._check(self.lib.ekf_batch_log_workspace_bytes(self.h, idx.shape[0], frames, C.byref(nbytes)))
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
@@ -798,16 +822,18 @@ class EKFBatch:
             poses_t = poses if on_device else torch.from_numpy(poses).to(self.device)
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
             traj = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
-            if noise is not None or scale is not None:
+            if noise is not None or scale is not None or motion is not None:
                 rows_t = torch.from_numpy(noise).to(self.device) if noise is not None else None
                 scale_t = torch.from_numpy(scale).to(self.device) if scale is not None else None
+                motion_t = torch.from_numpy(motion).to(self.device) if motion is not None else None
                 nis_t = torch.empty((frames,), dtype=torch.float64, device=self.device) if nis else None
                 cov_t = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
                 mahal_t = torch.empty((idx.shape[0],), dtype=torch.float64, device=self.device) if mahal else None
                 ptr = (lambda t: t.data_ptr() if t is not None and frames else None)
-                self._check(self.lib.ekf_batch_observe_logs_scaled(
+                self._check(self.lib.ekf_batch_observe_logs_moved(
                     self.h, _iptr(idx), _lptr(fo), _lptr(mf), poses_t.data_ptr() if idx.shape[0] else None,
-                    rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None, ptr(scale_t), ws.data_ptr(),
+                    rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None, ptr(scale_t), ptr(motion_t),
+                    ws.data_ptr(),
                     nbytes.value, ptr(traj), ptr(nis_t),
                     ptr(cov_t), mahal_t.data_ptr() if mahal and idx.shape[0] else None))
                 self.stream.synchronize()
@@ -978,6 +1004,8 @@ class EKFBatch:
             raise ValueError("the filter takes per-detection noise: load it into a batch built with row_noise=True")
         if ekf.backend.can_frame_scale and not self.frame_scale:
             raise ValueError("the filter takes per-frame scales: load it into a batch built with frame_scale=True")
+        if ekf.backend.can_motion and not self.motion:
+            raise ValueError("the filter takes camera motions: load it into a batch built with motion=True")
         pending = ekf.backend.pending_scale
         ids = [k for k, _ in sorted(ekf.get_lm_estimates(), key=lambda kv: kv[1])]
         self.set_member(b, np.asarray(ekf.state, dtype=np.float64), ekf.uncertainty, ids)
@@ -992,7 +1020,7 @@ class EKFBatch:
         """An ordinary filter of the batch's model (``EKF`` or ``EKF_Rotations``, f64 covariance) with member b's quaternion
         convention, noise constants, gate (a batch with a gate gives a filter built with ``gate=``), per-detection-noise
         capability (a batch built with ``row_noise=True`` gives a filter built the same way), per-frame-scale capability and
-        pending scale (likewise, ``frame_scale=True``), state, covariance and landmark table; ``observe`` (and for ``EKF`` ``save_map`` and ``save_checkpoint``) work on it."""
+        pending scale (likewise, ``frame_scale=True``), camera-motion capability (likewise, ``motion=True``), state, covariance and landmark table; ``observe`` (and for ``EKF`` ``save_map`` and ``save_checkpoint``) work on it."""
         b = self._member(b)
         state, cov = self.get_state(b), self.get_cov(b)
         n = self.num_landmarks[b]
@@ -1002,12 +1030,12 @@ class EKFBatch:
             from .filters.ekf_with_rotations import EKF_Rotations
             ekf = EKF_Rotations(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
                                 device=str(self.device), noise=noise, gate=gate, row_noise=self.row_noise,
-                                frame_scale=self.frame_scale)
+                                frame_scale=self.frame_scale, motion=self.motion)
         else:
             from .filters.extended_kalman_filter import EKF
             ekf = EKF(state[:10], max_landmarks=max(n, 1), max_visible=self.max_visible, cov_dtype="float64",
                       quat_update=self.quat_update, device=str(self.device), noise=noise, gate=gate, row_noise=self.row_noise,
-                      frame_scale=self.frame_scale)
+                      frame_scale=self.frame_scale, motion=self.motion)
         pending = float(self.pending_scale[b]) if self.frame_scale else 0.0
         ekf.backend.set_state_cov(state, cov)
         if self.frame_scale:

@@ -187,6 +187,7 @@ struct GetterShortcut {
     void reset() { *this = {false, false, true, true}; }   // (state and mirror are both zero beyond what frames write)
     void new_workspace() { *this = {}; }
     void removed() { front_pending = mirror_fresh = false; mirror_trust = true; }   // (the removal launch writes the whole new state into the mirror)
+    void moved() { front_pending = mirror_fresh = false; }   // (the motion launch changes the camera state behind ev_front and leaves the mirror alone: the next getter copies)
     void read_back(bool clean, bool full_state) { status_clean = clean; mirror_trust = mirror_trust || full_state; }
 };
 
@@ -252,6 +253,7 @@ struct ekf_filter {
     double pending = 0.0;
 
     bool has_scale() const { return (cfg.flags & EKF_FLAG_FRAME_SCALE) != 0; }
+    bool has_motion() const { return (cfg.flags & EKF_FLAG_MOTION) != 0; }
     bool gate_on() const { return lay.has_gate && gate < __builtin_inf(); }
     void reset_gate_stats() { gate_stats[0] = gate_stats[1] = 0; }      // every observe call counts from zero
     int dims() const { return lay.lmd * n_lm + EKF_CAM; }
@@ -930,6 +932,39 @@ int check_scales(const ekf_filter* f, const double* scale, int64_t count) {
     return EKF_OK;
 }
 
+// motion [count][6] of a call (host, or null): the flag and the values, before anything is enqueued
+int check_motions(const ekf_filter* f, const double* motion, int64_t count) {
+    if (!motion) return EKF_OK;
+    if (!f->has_motion()) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_MOTION");
+    for (int64_t i = 0; i < 6 * count; ++i)
+        if (!std::isfinite(motion[i])) return fail(EKF_ERR_INVALID, "a motion must be finite");
+    return EKF_OK;
+}
+
+// The motion of one frame (include/ekf_slam_hip.h, the motion rules): null, or six exact zeros: nothing is enqueued (bit
+// rule 6(a)).  Otherwise the launch of ekf_motion.hip on the handle's stream, behind everything the frame before left there
+// (a frame that is not stepped takes its trajectory row from the state afterwards: repeat_row).  Returns whether something
+// was enqueued in *moved (or null).
+int enqueue_motion(ekf_filter* f, const double* u, bool* moved = nullptr) {
+    if (moved) *moved = false;
+    if (!u) return EKF_OK;
+    bool zero = true;
+    for (int i = 0; i < 6; ++i) zero = zero && u[i] == 0.0;
+    if (zero) return EKF_OK;
+    EkfMotionArgs a{};
+    a.cov = f->cov;
+    a.ld = f->ld;
+    a.state = f->state;
+    a.dims = f->dims();
+    for (int i = 0; i < 6; ++i) a.u[i] = u[i];
+    a.status = f->at<int32_t>(f->lay.off_status);
+    by_cov_type(f, [&](auto elem) { ekf_launch_motion<decltype(elem)>(a, f->stream); });
+    HIP_TRY(hipGetLastError());
+    f->shortcut.moved();
+    if (moved) *moved = true;
+    return EKF_OK;
+}
+
 // trajectory row of a frame that is not stepped: the camera state as it is on the device
 int repeat_row(ekf_filter* f, double* traj_row) {
     if (traj_row) HIP_TRY(hipMemcpyAsync(traj_row, f->state, 7 * 8, hipMemcpyDeviceToDevice, f->stream));
@@ -947,8 +982,11 @@ int gated_frame_or_row(ekf_filter* f, const int32_t* idx, const double* z, const
 // ekf_observe / ekf_observe_gated: the frame's detections (host) through a slot of the pinned staging ring
 // rows [m][rd] (host) or null: per-detection noise, staged behind everything else of the slot
 // scale: the frame's process-noise scale, or null (checked by the caller: check_scales)
+// motion: the frame's camera motion [6], or null (checked by the caller: check_motions); applied once the frame has passed
+// every check, in front of the gate
 int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m, bool gated,
-                 const uint8_t* exempt, double* mahal, int32_t* survivors, const double* scale = nullptr) {
+                 const uint8_t* exempt, double* mahal, int32_t* survivors, const double* scale = nullptr,
+                 const double* motion = nullptr) {
     if (m < 1) return fail(EKF_ERR_INVALID, "observe needs at least one detection");
     if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
     if (!lm_index || !z) return fail(EKF_ERR_INVALID, "NULL detections");
@@ -980,7 +1018,8 @@ int observe_host(ekf_filter* f, const int32_t* lm_index, const double* z, const 
     // The kernels read the frame's detections (128 + 768 bytes at m = 32) straight from the pinned slot: a host-to-device
     // copy in front of them costs more (API call + DMA start, ~8 us before the front kernel begins) than the PCIe reads
     // cost the kernel's first round trip.  The slot is not reused before this frame's event (64-slot ring).
-    int rc;
+    int rc = enqueue_motion(f, motion);
+    if (rc) return rc;
     const double s_eff = frame_scale(f, scale);
     if (gated) {
         uint8_t* hex = nullptr;
@@ -1323,14 +1362,16 @@ int ekf_observe_gated(ekf_filter* f, const int32_t* lm_index, const double* z, i
 
 namespace {
 int observe_rows_scaled(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m,
-                        const uint8_t* exempt, double* mahal, int32_t* survivors, const double* scale) {
+                        const uint8_t* exempt, double* mahal, int32_t* survivors, const double* scale,
+                        const double* motion = nullptr) {
     int rc = check_ready(f);
     if (rc) return rc;
     if ((exempt || mahal) && !f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
     if ((rc = check_scales(f, scale, 1))) return rc;
+    if ((rc = check_motions(f, motion, 1))) return rc;
     f->reset_gate_stats();
     const bool gated = f->gate_on() || mahal;
-    rc = observe_host(f, lm_index, z, rows, m, gated, exempt, mahal, survivors, scale);
+    rc = observe_host(f, lm_index, z, rows, m, gated, exempt, mahal, survivors, scale, motion);
     if (rc == EKF_OK && !gated && survivors) *survivors = m;
     return rc;
 }
@@ -1344,6 +1385,19 @@ int ekf_observe_rows(ekf_filter* f, const int32_t* lm_index, const double* z, co
 int ekf_observe_scaled(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m,
                        const uint8_t* exempt, double* mahal, int32_t* survivors, double scale) {
     return observe_rows_scaled(f, lm_index, z, rows, m, exempt, mahal, survivors, &scale);
+}
+
+int ekf_observe_moved(ekf_filter* f, const int32_t* lm_index, const double* z, const double* rows, int32_t m,
+                      const uint8_t* exempt, double* mahal, int32_t* survivors, double scale, const double* motion) {
+    return observe_rows_scaled(f, lm_index, z, rows, m, exempt, mahal, survivors, &scale, motion);
+}
+
+int ekf_move(ekf_filter* f, const double motion[6]) {
+    int rc = check_ready(f);
+    if (rc) return rc;
+    if (!motion) return fail(EKF_ERR_INVALID, "motion is NULL");
+    if ((rc = check_motions(f, motion, 1))) return rc;
+    return enqueue_motion(f, motion);
 }
 
 int ekf_advance(ekf_filter* f, double scale) {
@@ -1414,28 +1468,40 @@ int ekf_observe_sequence_device_rows(ekf_filter* f, const int32_t* lm_index_dev,
 
 int ekf_observe_sequence_device_scaled(ekf_filter* f, const int32_t* lm_index_dev, const double* z_dev, const double* rows_dev,
                                        const double* scale, int32_t m, int32_t frames, double* trajectory_dev) {
+    return ekf_observe_sequence_device_moved(f, lm_index_dev, z_dev, rows_dev, scale, nullptr, m, frames, trajectory_dev);
+}
+
+int ekf_observe_sequence_device_moved(ekf_filter* f, const int32_t* lm_index_dev, const double* z_dev, const double* rows_dev,
+                                      const double* scale, const double* motion, int32_t m, int32_t frames,
+                                      double* trajectory_dev) {
     int rc = check_ready(f);
     if (rc) return rc;
     if (rows_dev && !f->lay.has_rows) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_ROW_NOISE");
     if (m < 1 || frames < 0) return fail(EKF_ERR_INVALID, "bad sequence shape");
     if ((rc = check_scales(f, scale, frames))) return rc;
+    if ((rc = check_motions(f, motion, frames))) return rc;
     if (m > f->cfg.max_visible) return fail(EKF_ERR_CAPACITY, "more detections than max_visible");
     if (!lm_index_dev || !z_dev) return fail(EKF_ERR_INVALID, "NULL detections");
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
     const int rd = f->lay.rd;
     f->reset_gate_stats();
-    if (f->gate_on()) {
+    if (f->gate_on() || motion) {
         // a gate is set: frame by frame in serial order, each frame on its survivors (gating inside a pipelined run would
-        // need the mask inside the front kernel)
+        // need the mask inside the front kernel).  Motions: serial order as well -- a front kernel of a run completes
+        // P_{t+1} from P_t and W_t, and a motion between the two frames changes rows of it
         f->seq_mode = EKF_SEQ_SERIAL;
         f->shortcut.log();      // (a getter after the call waits for all of it)
         for (int t = 0; t < frames; ++t) {
-            int s = 0;
+            int s = m;
             const double* sc = scale ? scale + t : nullptr;
+            if ((rc = enqueue_motion(f, motion ? motion + (size_t)t * 6 : nullptr))) return rc;
             const double s_eff = frame_scale(f, sc);
-            rc = gated_frame_or_row(f, lm_index_dev + (size_t)t * m, z_dev + (size_t)t * m * rd,
-                                    rows_dev ? rows_dev + (size_t)t * m * rd : nullptr, m, nullptr, 0, nullptr,
-                                    trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr, &s, s_eff);
+            const int32_t* idx_t = lm_index_dev + (size_t)t * m;
+            const double* z_t = z_dev + (size_t)t * m * rd;
+            const double* rows_t = rows_dev ? rows_dev + (size_t)t * m * rd : nullptr;
+            double* row_t = trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr;
+            rc = f->gate_on() ? gated_frame_or_row(f, idx_t, z_t, rows_t, m, nullptr, 0, nullptr, row_t, &s, s_eff)
+                              : enqueue_frame(f, idx_t, z_t, rows_t, m, row_t, false, s_eff);
             if (rc) return rc;
             frame_scale_done(f, sc, s_eff, s > 0);
         }
@@ -1523,15 +1589,26 @@ int ekf_observe_log_rows(ekf_filter* f, const int32_t* lm_index, const int64_t* 
 int ekf_observe_log_scaled(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
                            const double* poses_dev, const double* rows_dev, const double* scale, void* log_ws,
                            size_t log_ws_bytes, double* trajectory_dev, double* mahal_dev) {
+    return ekf_observe_log_moved(f, lm_index, offsets, frames, poses_dev, rows_dev, scale, nullptr, log_ws, log_ws_bytes,
+                                 trajectory_dev, mahal_dev);
+}
+
+int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
+                          const double* poses_dev, const double* rows_dev, const double* scale, const double* motion,
+                          void* log_ws, size_t log_ws_bytes, double* trajectory_dev, double* mahal_dev) {
     int rc = check_ready(f);
     if (rc) return rc;
     if (rows_dev && !f->lay.has_rows) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_ROW_NOISE");
     if (mahal_dev && !f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
     // a gate that is set, or distances asked for: frame by frame in serial order, each frame on its survivors
     const bool gated = f->gate_on() || mahal_dev;
+    // frame by frame in serial order: a gated call, and a call with motions (a motion between two frames of a pipelined run
+    // would change rows of the P_{t+1} the next front kernel completes from P_t and W_t)
+    const bool by_frame = gated || motion;
     // ---- validation on the host: nothing is enqueued before the whole log has passed
     if (frames < 0) return fail(EKF_ERR_INVALID, "negative frame count");
     if ((rc = check_scales(f, scale, frames))) return rc;
+    if ((rc = check_motions(f, motion, frames))) return rc;
     if (frames > 0 && !offsets) return fail(EKF_ERR_INVALID, "offsets is NULL");
     if (frames > 0 && (rc = check_offsets(offsets, frames, "offsets"))) return rc;
     const int64_t D = frames > 0 ? offsets[frames] : 0;
@@ -1552,7 +1629,8 @@ int ekf_observe_log_scaled(ekf_filter* f, const int32_t* lm_index, const int64_t
         int last = -1;
         for (int t = 0; t < frames; ++t) {
             if (offsets[t + 1] > offsets[t]) last = t;
-            else if (trajectory_dev && !gated) {      // (gated: which frames are stepped is known frame by frame)
+            else if (trajectory_dev && !by_frame) {      // (gated: which frames are stepped is known frame by frame; motions:
+                                                         // an empty frame's row is the moved pose)
                 std::vector<int32_t>& v = last < 0 ? lead : rest;
                 v.push_back(t);
                 v.push_back(last);
@@ -1598,11 +1676,11 @@ int ekf_observe_log_scaled(ekf_filter* f, const int32_t* lm_index, const int64_t
             s_effs[t] = frame_scale(f, scale ? scale + t : nullptr);
             frame_scale_done(f, scale ? scale + t : nullptr, s_effs[t], m_of(t) > 0);
         }
-    const RunPlan plan = gated ? RunPlan{} : plan_runs(f, frames, m_of, nnew_of);
+    const RunPlan plan = by_frame ? RunPlan{} : plan_runs(f, frames, m_of, nnew_of);
     int mode = EKF_SEQ_SERIAL;
     rc = choose_pipelining(f, plan.want_runs, &mode);
     if (rc) return rc;
-    if (gated) f->seq_mode = EKF_SEQ_SERIAL;
+    if (by_frame) f->seq_mode = EKF_SEQ_SERIAL;
 
     // ---- device work, all on the handle's stream (the pipelined runs use the internal one as ekf_observe_sequence_device)
     if (D > 0) {
@@ -1625,27 +1703,30 @@ int ekf_observe_log_scaled(ekf_filter* f, const int32_t* lm_index, const int64_t
             });
         return nnew;
     };
-    if (gated) {
-        // first sightings, the gate on the prior they leave, the frame on its survivors; a frame without detections or
-        // without a survivor is not stepped, and its row repeats the camera state
+    if (by_frame) {
+        // the motion, first sightings (placed from the moved camera), the gate on the prior they leave, the frame on its
+        // survivors; a frame without detections or without a survivor is not stepped, and its row repeats the camera state
+        // (Without a gate the scales were folded over the whole log above: s_effs.)
         for (int t = 0; t < frames && rc == EKF_OK; ++t) {
             const RunFrame r = frame_of(t);
             const double* sc = scale ? scale + t : nullptr;
-            const double s_eff = frame_scale(f, sc);
+            if ((rc = enqueue_motion(f, motion ? motion + (size_t)t * 6 : nullptr))) break;
+            const double s_eff = gated ? frame_scale(f, sc) : s_effs[t];
             if (r.m == 0) {
                 rc = repeat_row(f, r.traj_row);
-                frame_scale_done(f, sc, s_eff, false);
+                if (gated) frame_scale_done(f, sc, s_eff, false);
                 continue;
             }
             const int nnew = first_sightings(t);
             f->n_lm += nnew;
             f->log_stats[3] += nnew;
             const int64_t d0 = offsets[t];
-            int s = 0;
-            rc = gated_frame_or_row(f, r.idx, r.z, r.rows, r.m, pin_exempt + d0, nnew, mahal_dev ? mahal_dev + d0 : nullptr,
-                                    r.traj_row, &s, s_eff);
+            int s = r.m;
+            rc = gated ? gated_frame_or_row(f, r.idx, r.z, r.rows, r.m, pin_exempt + d0, nnew,
+                                            mahal_dev ? mahal_dev + d0 : nullptr, r.traj_row, &s, s_eff)
+                       : enqueue_frame(f, r.idx, r.z, r.rows, r.m, r.traj_row, false, s_eff);
             if (rc == EKF_OK && s > 0) f->log_stats[0] += 1;
-            if (rc == EKF_OK) frame_scale_done(f, sc, s_eff, s > 0);
+            if (rc == EKF_OK && gated) frame_scale_done(f, sc, s_eff, s > 0);
         }
     } else {
         rc = run_frames(f, frames, frame_of, first_sightings, plan, mode == EKF_SEQ_PIPELINED, f->log_stats);

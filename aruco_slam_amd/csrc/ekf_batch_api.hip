@@ -187,7 +187,8 @@ BatchReplicaLayout batch_replica_layout(int64_t D, int64_t F, int32_t B, bool ga
 // the call (a layout choice only: the arithmetic is the same)
 int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, const BatchShape& sh, const double* poses_dev,
                       double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev,
-                      const double* rows_dev = nullptr, const double* scale_dev = nullptr) {
+                      const double* rows_dev = nullptr, const double* scale_dev = nullptr,
+                      const double* motion_dev = nullptr) {
     const int32_t B = b->members;
     const BatchLayout L = batch_layout(b->cfg, B);
     EkfBatchWindow a{};
@@ -210,6 +211,7 @@ int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, co
     a.row_noise = rows_dev;      // (per-detection noise: data of the call, no workspace of its own)
     a.pending = batch_scaled(b->cfg) ? reinterpret_cast<double*>(b->ws + L.pending) : nullptr;
     a.scale = scale_dev;         // (per-frame scales: data of the call; checked by the caller: the flag is set)
+    a.motion = motion_dev;       // (per-frame camera motions: data of the call, likewise)
     const int rd = batch_rd(b->cfg);
     a.kmax = std::max(rd, rd * sh.widest);
     a.lda = (int32_t)round_up(batch_lmd(b->cfg) * sh.n_max + EKF_CAM + 1, 4);
@@ -530,8 +532,18 @@ int ekf_batch_observe_logs_scaled(ekf_batch* b, const int32_t* lm_index, const i
                                   const int64_t* member_frames, const double* poses_dev, const double* rows_dev,
                                   const double* scale_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev,
                                   double* nis_dev, double* cam_cov_dev, double* mahal_dev) {
+    return ekf_batch_observe_logs_moved(b, lm_index, frame_offsets, member_frames, poses_dev, rows_dev, scale_dev, nullptr,
+                                        log_ws, log_ws_bytes, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
+}
+
+int ekf_batch_observe_logs_moved(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets,
+                                 const int64_t* member_frames, const double* poses_dev, const double* rows_dev,
+                                 const double* scale_dev, const double* motion_dev, void* log_ws, size_t log_ws_bytes,
+                                 double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev) {
     int rc = batch_ready(b);
     if (rc) return rc;
+    if (motion_dev && (b->cfg.flags & EKF_FLAG_MOTION) == 0)
+        return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_MOTION");
     if (scale_dev && !batch_scaled(b->cfg)) return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_FRAME_SCALE");
     // ---- validation on the host: nothing is enqueued before every log has passed
     const int32_t B = b->members;
@@ -562,7 +574,8 @@ int ekf_batch_observe_logs_scaled(ekf_batch* b, const int32_t* lm_index, const i
     if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
     char* ws = static_cast<char*>(log_ws);
     HIP_TRY(hipMemcpyAsync(ws, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
-    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev, scale_dev);
+    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev, scale_dev,
+                             motion_dev);
 }
 
 // member = -1: every member, [B]; member >= 0: that one, [1].  Both wait for the batch's stream.

@@ -11,6 +11,7 @@
 #pragma once
 #include "ekf_gate_device.h"
 #include "ekf_markers.h"
+#include "ekf_motion_device.h"
 
 template <int MODEL> struct EkfBatchCaps;
 template <> struct EkfBatchCaps<0> { static constexpr int MAX_VISIBLE = EKF_BATCH_MAX_VISIBLE; };
@@ -150,7 +151,70 @@ __device__ __forceinline__ EkfNoise ekf_batch_frame_noise(const EkfNoise& nz0, b
                     nz0.r_unc};
 }
 
-template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
+// Camera motion of one member at the top of a frame (EkfBatchWindow::motion; the stage functions of ekf_motion_device.h, the
+// ones the single filter's launch runs): the member's P and state are in HBM in every window kernel.  u = motion[t]; six
+// exact zeros: nothing happens, no arithmetic.  All nt threads of the workgroup call it (u is uniform).  scr: 45 doubles of
+// LDS nobody uses between frames (the start of the dynamic LDS).  Thread 0 forms F from the OLD camera state into scr; behind
+// a barrier thread c moves the strip columns c, c + nt, ... (a column and its mirror row are its own), and thread i < 10
+// forms row i of B = F P_cc -- entry (i, j) is entry i of ekf_motion_column(P_cc[:, j]), the value the single filter's
+// launch leaves in its LDS copy of B -- keeps it in registers and, once every thread has read P_cc and the old state
+// (barrier), applies F to it and stores the lower triangle and its mirror; thread 0 stores c' and q'.
+__device__ __forceinline__ void ekf_batch_motion(const double* __restrict__ u, double* st, double* P, int64_t ld, int N,
+                                                 int tid, int nt, void* scr) {
+    bool moves = false;
+    for (int i = 0; i < 6; ++i) moves = moves || u[i] != 0.0;
+    if (!moves) return;
+    EkfMotionF& f = *reinterpret_cast<EkfMotionF*>(scr);
+    __syncthreads();      // (the frame before is over: its LDS is free, its state and P are in place)
+    if (tid == 0) ekf_motion_form(st, u, f);
+    __syncthreads();
+    double in[EKF_CAM], out[EKF_CAM], brow[EKF_CAM];
+    for (int j = EKF_CAM + tid; j < N; j += nt) {
+#pragma unroll
+        for (int k = 0; k < EKF_CAM; ++k) in[k] = P[(int64_t)k * ld + j];
+        ekf_motion_column(f, in, out);
+#pragma unroll
+        for (int k = 0; k < EKF_CAM; ++k) {
+            P[(int64_t)k * ld + j] = out[k];
+            P[(int64_t)j * ld + k] = out[k];
+        }
+    }
+    if (tid < EKF_CAM) {
+#pragma unroll
+        for (int j = 0; j < EKF_CAM; ++j) {
+#pragma unroll
+            for (int k = 0; k < EKF_CAM; ++k) in[k] = P[(int64_t)k * ld + j];
+            ekf_motion_column(f, in, out);
+            double v = out[0];
+#pragma unroll
+            for (int k = 1; k < EKF_CAM; ++k) v = k == tid ? out[k] : v;
+            brow[j] = v;
+        }
+    }
+    __syncthreads();      // (P_cc and the old state have been read by everyone who needs them)
+    if (tid < EKF_CAM) {
+        ekf_motion_column(f, brow, out);
+#pragma unroll
+        for (int k = 0; k < EKF_CAM; ++k)
+            if (k <= tid) {
+                P[(int64_t)tid * ld + k] = out[k];
+                P[(int64_t)k * ld + tid] = out[k];
+            }
+    }
+    if (tid == 0) {
+        for (int i = 0; i < 3; ++i) st[i] = f.c1[i];
+        for (int i = 0; i < 4; ++i) st[3 + i] = f.q1[i];
+    }
+    __syncthreads();
+}
+
+// MOVED: the instance with the motion stage at the top of the frame (a.motion != null).  A call without motions runs the
+// instance without it, which is the kernel as it was: the stage's registers would cost every batch an occupancy step
+// (one-column EKF kernel: 167 -> 256 VGPRs; measured -11 % / -19 % frames per second with the stage compiled in and off).
+void ekf_launch_batch_moved_window(int model, const EkfBatchWindow& a, int members, hipStream_t s);            // ekf_batch_moved.hip
+void ekf_launch_batch_moved_wide_window(int model, bool one_block, const EkfBatchLargeWindow& g, int members,
+                                        hipStream_t s);                                                      // ekf_batch_wide_moved.hip
+template <int MODEL, bool MOVED = false> __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -184,6 +248,10 @@ template <int MODEL> __device__ __forceinline__ void ekf_batch_window(const EkfB
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t d0 = a.frame_offsets[t];
         const int mf = (int)(a.frame_offsets[t + 1] - d0);
+        // the camera's motion first: first sightings, gate, predict and update see the moved prior, and a frame that is not
+        // stepped is still moved (a failed member ignores motions)
+        if constexpr (MOVED)
+            if (!failed) ekf_batch_motion(a.motion + 6 * t, st, P, ld, LMD * n + EKF_CAM, tid, nt, smem);
         if (failed || mf == 0) {      // not stepped: the rows repeat the state (NaN once the member has failed)
             if (scaled && !failed && a.scale) pend = pend + a.scale[t];      // (rule 4: the frame's scale stays pending)
             ekf_batch_rows_unstepped(a, t, tid, st, P, failed);

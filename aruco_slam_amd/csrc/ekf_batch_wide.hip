@@ -67,7 +67,9 @@ typedef double ekf_d2 __attribute__((ext_vector_type(2)));
 // ONE_BLOCK: no frame of the launch is wider than one block (a batch without the wide flag: the host admits no wider frame),
 // so the loops over blocks run once, with j0 = 0, and the loop over earlier blocks is gone: the same operations on the same
 // data, with less control around them (the large-map shapes run 3 to 4 % faster than in the general instance)
-template <int MODEL, bool ONE_BLOCK> __device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow& g) {
+// MOVED: the instance with the motion stage (ekf_batch_impl.h: why it is an instance of its own)
+template <int MODEL, bool ONE_BLOCK, bool MOVED = false>
+__device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow& g) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     constexpr int MB = wide_mb<MODEL>(), KW = wide_kw<MODEL>();
     const EkfBatchWindow& a = g.w;
@@ -104,6 +106,9 @@ template <int MODEL, bool ONE_BLOCK> __device__ __forceinline__ void ekf_batch_w
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t d0 = a.frame_offsets[t];
         const int mf = (int)(a.frame_offsets[t + 1] - d0);
+        // the camera's motion first (ekf_batch_impl.h: ekf_batch_motion), as in the one-column kernel
+        if constexpr (MOVED)
+            if (!failed) ekf_batch_motion(a.motion + 6 * t, st, P, ld, LMD * n + EKF_CAM, tid, nt, smem);
         if (failed || mf == 0) {      // not stepped: the rows repeat the state (NaN once the member has failed)
             if (scaled && !failed && a.scale) pend = pend + a.scale[t];      // (rule 4: the frame's scale stays pending)
             ekf_batch_rows_unstepped(a, t, tid, st, P, failed);
@@ -396,6 +401,7 @@ void wide_launch(void (*kernel)(EkfBatchLargeWindow), bool& once, const EkfBatch
 
 }  // namespace
 
+#ifndef EKF_BATCH_WIDE_MOVED
 extern "C" size_t ekf_batch_wide_lds_bytes(int model, int kmax) {
     return model == 1 ? wide_lds_bytes_of<1>(kmax) : wide_lds_bytes_of<0>(kmax);
 }
@@ -414,6 +420,7 @@ __global__ __launch_bounds__(256) void ekf_batch_one_block_rot_window_kernel(Ekf
 }
 
 void ekf_launch_batch_wide_window(int model, bool one_block, const EkfBatchLargeWindow& g, int members, hipStream_t s) {
+    if (g.w.motion) return ekf_launch_batch_moved_wide_window(model, one_block, g, members, s);      // (ekf_batch_wide_moved.hip)
     static bool once[2][2] = {{false, false}, {false, false}};
     if (model == 1)
         wide_launch<1>(one_block ? ekf_batch_one_block_rot_window_kernel : ekf_batch_wide_rot_window_kernel,
@@ -422,3 +429,27 @@ void ekf_launch_batch_wide_window(int model, bool one_block, const EkfBatchLarge
         wide_launch<0>(one_block ? ekf_batch_one_block_window_kernel : ekf_batch_wide_window_kernel, once[0][one_block], g,
                        members, s);
 }
+#else      // ekf_batch_wide_moved.hip: the instances with the motion stage
+__global__ __launch_bounds__(256) void ekf_batch_moved_wide_window_kernel(EkfBatchLargeWindow g) {
+    ekf_batch_wide_window<0, false, true>(g);
+}
+__global__ __launch_bounds__(256) void ekf_batch_moved_wide_rot_window_kernel(EkfBatchLargeWindow g) {
+    ekf_batch_wide_window<1, false, true>(g);
+}
+__global__ __launch_bounds__(256) void ekf_batch_moved_one_block_window_kernel(EkfBatchLargeWindow g) {
+    ekf_batch_wide_window<0, true, true>(g);
+}
+__global__ __launch_bounds__(256) void ekf_batch_moved_one_block_rot_window_kernel(EkfBatchLargeWindow g) {
+    ekf_batch_wide_window<1, true, true>(g);
+}
+
+void ekf_launch_batch_moved_wide_window(int model, bool one_block, const EkfBatchLargeWindow& g, int members, hipStream_t s) {
+    static bool once[2][2] = {{false, false}, {false, false}};
+    if (model == 1)
+        wide_launch<1>(one_block ? ekf_batch_moved_one_block_rot_window_kernel : ekf_batch_moved_wide_rot_window_kernel,
+                       once[1][one_block], g, members, s);
+    else
+        wide_launch<0>(one_block ? ekf_batch_moved_one_block_window_kernel : ekf_batch_moved_wide_window_kernel,
+                       once[0][one_block], g, members, s);
+}
+#endif

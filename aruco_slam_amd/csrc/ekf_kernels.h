@@ -268,6 +268,21 @@ struct EkfGateArgs {
                                 // frame's own factorisation reports the failure, as it does without a gate)
 };
 template <typename T> void ekf_launch_frame_gate(int model, const EkfGateArgs& a, hipStream_t s);
+// Camera motion between frames (ekf_motion.hip; EKF_FLAG_MOTION; arithmetic: ekf_motion_device.h): the camera moves by
+// u = (d, w) in its own frame, P <- F~ P F~^T on rows and columns 0 .. 9.  One thread per column of the strip P[0:10, 10:N]
+// (EKF_MOTION_THREADS per workgroup); workgroup 0 also owns the 10 x 10 block.  Every workgroup forms F from the OLD camera
+// state, so the new one is stored only once all of them are over: by the one workgroup itself when the grid is one
+// workgroup, by a second one-thread launch behind the first otherwise.
+#define EKF_MOTION_THREADS 256
+struct EkfMotionArgs {
+    void* cov;                  // P, f32 or f64 (widened on load, rounded once on store), leading dimension ld
+    int64_t ld;
+    double* state;
+    int32_t dims;               // N: nothing at or beyond it is read or written
+    double u[6];                // the motion (d, w)
+    const int32_t* status;      // the filter's status words ([0] != 0: a failed filter ignores motions)
+};
+template <typename T> void ekf_launch_motion(const EkfMotionArgs& a, hipStream_t s);
 template <typename T>
 void ekf_launch_cov_diag(const void* cov, int64_t ld, double* out_dev, int32_t count, hipStream_t s);
 
@@ -304,6 +319,9 @@ struct EkfBatchWindow {
     // are); scale [Ftot] is every frame's scale, indexed like frame_offsets (null: 1 for every frame)
     double* pending;
     const double* scale;
+    // Camera motion per frame (EKF_FLAG_MOTION; include/ekf_slam_hip.h, "Odometry input"): motion [Ftot][6], every frame's
+    // (d, w), indexed like frame_offsets; null: no motion stage (a batch without the flag, or a call without motions)
+    const double* motion;
 };
 // dynamic LDS of one launch (C linkage: the tests read them)
 extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);

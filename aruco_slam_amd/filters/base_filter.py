@@ -114,6 +114,7 @@ class BaseFilter:
     # (class-level defaults: subclasses that build themselves without this constructor prune nothing)
     _tentative = None       # confirm=(hits, window): the TentativeLandmarks policy (_init_confirm)
     _pruned = False         # landmarks have been removed: with none left, `state` is still the device's
+    _moved = False          # the camera has been moved (move, motion=): with no landmark yet, `state` is the device's
 
     def __init__(self, initial_pose, map_file=None, aruco_dict=None) -> None:
         self.calib_matrix = None
@@ -200,21 +201,29 @@ class BaseFilter:
             ids, detected_poses, should_filter, iteration)
         return frame, camera_pose, marker_poses, detected_poses
 
-    def process_detections(self, ids, detected_poses, should_filter=True, iteration=0, noise=None, scale=None):
+    def process_detections(self, ids, detected_poses, should_filter=True, iteration=0, noise=None, scale=None, motion=None):
         """The part of ``process_frame`` behind the detector
         (base_filter.py:196-212): ``ids`` is None for a frame without
         detections, in which case the filter is NOT stepped (no predict).  ``noise``: the frame's per-detection
         measurement noise, as ``observe`` takes it (a filter built with ``row_noise=True``).  ``scale``: the frame's
         process-noise scale, as ``observe`` takes it (a filter built with ``frame_scale=True``); a frame without
-        detections advances the pending scale by it (``advance``), so the time it took is not lost."""
+        detections advances the pending scale by it (``advance``), so the time it took is not lost.  ``motion``: the
+        camera's motion since the previous frame, as ``observe`` takes it (a filter built with ``motion=True``); a frame
+        without detections moves the camera all the same."""
         if ids is None:
             detected_poses = np.array([])
-            if should_filter and scale is not None:
-                self.advance(scale)
-        elif should_filter and (noise is not None or scale is not None):
+            if should_filter:
+                scale, motion = self._frame_scale(scale), self._frame_motion(motion)      # (both checked before either acts)
+                if motion is not None:
+                    self._move(motion)
+                if scale is not None:
+                    self.advance(scale)
+        elif should_filter and (noise is not None or scale is not None or motion is not None):
             extra = {} if noise is None else {"noise": noise}
             if scale is not None:
                 extra["scale"] = scale
+            if motion is not None:
+                extra["motion"] = motion
             self.observe(ids, detected_poses, **extra)
         elif should_filter:
             self.observe(ids, detected_poses)
@@ -262,6 +271,30 @@ class BaseFilter:
         if not self.backend.can_frame_scale:
             raise ValueError("scale= needs a filter built with frame_scale=True")
         return frame_scale_array(scale)
+
+    # -- odometry input: the camera's motion between frames (ekf_move) ---------------------------------
+    def move(self, d, w) -> None:
+        """The camera has moved by the translation ``d`` and the rotation vector ``w`` (radians), both in its own frame
+        before the move: the pose is moved and P is propagated through the move's Jacobian on the device (nothing is
+        synchronised).  A filter built with ``motion=True``; anything that is not two finite 3-vectors raises
+        ``ValueError`` and nothing changes."""
+        if np.shape(d) != (3,) or np.shape(w) != (3,):
+            raise ValueError(f"motion: d and w must have shape (3,), got {np.shape(d)} and {np.shape(w)}")
+        self._move(self._frame_motion(np.concatenate((d, w))))
+
+    def _move(self, motion) -> None:
+        self.backend.move(motion)
+        self._moved = True
+
+    def _frame_motion(self, motion):
+        """``motion=`` of ``observe`` / ``process_detections``: None, or a float64 [6] array.  ``ValueError`` for another
+        shape, a NaN or Inf entry and a filter built without ``motion=True``; checked before the frame changes anything."""
+        if motion is None:
+            return None
+        from ..hip_backend import motion_array
+        if not self.backend.can_motion:
+            raise ValueError("motion= needs a filter built with motion=True")
+        return motion_array(motion)
 
     def _lm_variances(self, lm_dims: int, predicted: bool) -> np.ndarray:
         """The landmark part of diag(P), [n, lm_dims]: P of the last stepped frame, or with ``predicted`` what the next
@@ -342,7 +375,8 @@ class BaseFilter:
         self.last_mahal = d2
         self.last_rejected = d2 > backend.gate      # (NaN and 0 compare false; gate inf: nothing)
 
-    def process_detection_log(self, ids, poses, offsets, has_detections=None, mahal=False, noise=None, scale=None):
+    def process_detection_log(self, ids, poses, offsets, has_detections=None, mahal=False, noise=None, scale=None,
+                              motion=None):
         """``process_detections(ids_t, poses_t)`` with ``should_filter=True`` for every frame of a recorded log, in ONE call
         that runs predict / update of every frame on the device (ekf_observe_log).  The log is a CSR batch as in a replay
         file (``main/run_slam.py: detection_frames``): ``ids [D]``, ``poses [D,6]`` ``[tvec | rvec]`` (NumPy, or a
@@ -356,7 +390,9 @@ class BaseFilter:
         rows of frames without detections), gate or no gate; ``d2 > gate`` are the rejected ones.  ``noise``: per-detection
         measurement noise of the log, [D] or [D, rd] aligned with ``ids`` (a filter built with ``row_noise=True``).
         ``scale``: the frames' process-noise scales, [F], one per frame of the log (a filter built with
-        ``frame_scale=True``): a frame that is not stepped leaves its scale pending for the next stepped one."""
+        ``frame_scale=True``): a frame that is not stepped leaves its scale pending for the next stepped one.
+        ``motion``: the camera's motion before every frame, [F, 6], one row per frame of the log, empty frames included (a
+        filter built with ``motion=True``); such a replay runs its frames in serial order."""
         import torch
         backend = self.backend
         plan = plan_detection_log(self.landmarks, self.num_landmarks, ids, offsets, has_detections)
@@ -377,6 +413,11 @@ class BaseFilter:
             if not backend.can_frame_scale:
                 raise ValueError("scale= needs a filter built with frame_scale=True")
             scale = frame_scale_array(scale, plan.offsets.shape[0] - 1)
+        if motion is not None:
+            from ..hip_backend import motion_array
+            if not backend.can_motion:
+                raise ValueError("motion= needs a filter built with motion=True")
+            motion = motion_array(motion, plan.offsets.shape[0] - 1)
         if not plan.keep.all():      # (rows of frames without detections, if there are any, are not part of the replay)
             poses = poses[torch.from_numpy(plan.keep).to(poses.device)] if isinstance(poses, torch.Tensor) else poses[plan.keep]
         if isinstance(poses, torch.Tensor):
@@ -387,8 +428,10 @@ class BaseFilter:
             backend.grow(new_max_visible=min(backend.MAX_VISIBLE_LIMIT[backend.lm_dims], plan.widest))
         traj = torch.empty((plan.offsets.shape[0] - 1, 7), dtype=torch.float64, device=backend.device)
         mahal_t = torch.empty((plan.index.shape[0],), dtype=torch.float64, device=backend.device) if mahal else None
-        backend.observe_log(plan.index, plan.offsets, poses, traj, mahal_t, rows, scale)
+        backend.observe_log(plan.index, plan.offsets, poses, traj, mahal_t, rows, scale, motion)
         backend.sync()
+        if motion is not None and motion.any():
+            self._moved = True
         self.landmarks.update(plan.new_landmarks)
         self.num_landmarks = plan.num_landmarks
         if self._tentative is not None:      # (confirm=: the policy sees per-frame calls only; what a replay adds stays)
@@ -439,6 +482,7 @@ class BaseFilter:
         self.landmarks = {}
         self.num_landmarks = 0
         self._pruned = False
+        self._moved = False
         if self._tentative is not None:
             self._tentative.clear()
 
@@ -452,7 +496,8 @@ class BaseFilter:
                  cov=np.asarray(self.uncertainty, dtype=np.float64),
                  marker_ids=np.asarray(ids, dtype=np.int64), filter=type(self).__name__,
                  gate=np.float64(np.inf if gate is None else gate), row_noise=np.bool_(self.backend.can_row_noise),
-                 frame_scale=np.bool_(self.backend.can_frame_scale), pending_scale=np.float64(self.backend.pending_scale))
+                 frame_scale=np.bool_(self.backend.can_frame_scale), pending_scale=np.float64(self.backend.pending_scale),
+                 motion=np.bool_(self.backend.can_motion))
 
     def load_checkpoint(self, filename: str) -> None:
         """Inverse of ``save_checkpoint`` on a filter of the same class; the device covariance
@@ -471,6 +516,9 @@ class BaseFilter:
             row_noise = bool(ck["row_noise"]) if "row_noise" in ck.files else False
             frame_scale = bool(ck["frame_scale"]) if "frame_scale" in ck.files else False
             pending = float(ck["pending_scale"]) if "pending_scale" in ck.files else 0.0
+            motion = bool(ck["motion"]) if "motion" in ck.files else False
+        if motion and not self.backend.can_motion:
+            raise ValueError("the checkpoint is of a filter with camera motions: build this one with motion=True")
         if frame_scale and not self.backend.can_frame_scale:
             raise ValueError("the checkpoint is of a filter with per-frame scales: build this one with frame_scale=True")
         if row_noise and not self.backend.can_row_noise:
@@ -491,7 +539,7 @@ class BaseFilter:
             self._tentative.confirm(self.landmarks)
 
     # -- abstract back-end API, base_filter.py:327-381 ------------------------
-    def observe(self, ids, poses, noise=None, scale=None) -> None:
+    def observe(self, ids, poses, noise=None, scale=None, motion=None) -> None:
         raise NotImplementedError(NOT_IMPLEMENTED_ERROR)
 
     def get_poses(self):

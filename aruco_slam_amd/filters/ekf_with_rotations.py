@@ -47,7 +47,7 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
                  cov_dtype: str = "float64", cov_kernel: str = "auto", device: str = "cuda:0",
                  lookahead: bool | None = None, fused: bool = True, noise: dict | None = None,
                  gate: float | None = None, confirm: tuple | None = None, row_noise: bool = False,
-                 frame_scale: bool = False) -> None:
+                 frame_scale: bool = False, motion: bool = False) -> None:
         """``noise``: values that replace the module's noise constants, keyed by the ``ekf_config`` field names
         (``initial_camera_uncertainty``, ``initial_landmark_uncertainty``, ``r_uncertainty``, ``q_cam``, ``q_err``, ``q_lm``);
         None keeps the reference's constants.  ``gate``: the chi-square gate on every detection's own Mahalanobis
@@ -56,7 +56,8 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         ``confirm``: ``(hits, window)`` = a new landmark must be used again in ``hits`` later frames within ``window``
         frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off.
         ``row_noise``: the filter takes per-detection measurement noise (``observe(..., noise=)``).
-        ``frame_scale``: frames may carry a process-noise scale (``observe(..., scale=)``, ``advance``)."""
+        ``frame_scale``: frames may carry a process-noise scale (``observe(..., scale=)``, ``advance``).
+        ``motion``: frames may carry the camera's motion since the previous frame (``observe(..., motion=)``, ``move``)."""
         super().__init__(initial_camera_pose, None)
         self._initial_pose = np.array(initial_camera_pose)
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -78,13 +79,13 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype, quat_mode="scalar_first",
                            cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
                            model="ekf_rotations", noise=constants, gate=gate, row_noise=row_noise,
-                           frame_scale=frame_scale)
+                           frame_scale=frame_scale, motion=motion)
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._init_confirm(confirm)
 
     @property
     def state(self) -> np.ndarray:
-        if self.num_landmarks == 0 and not self._pruned:
+        if self.num_landmarks == 0 and not self._pruned and not self._moved:
             return self._initial_pose
         return self._hip.get_state()
 
@@ -93,11 +94,12 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         return self._hip.get_cov()
 
     # -- :66-90 ----------------------------------------------------------------
-    def observe(self, ids, poses, noise=None, scale=None) -> None:
+    def observe(self, ids, poses, noise=None, scale=None, motion=None) -> None:
         """``noise`` (a filter built with ``row_noise=True``): the frame's measurement noise, [m] (one variance per
         detection) or [m, 7] (x y z, then qw qx qy qz, the order of z) instead of ``r_uncertainty``; anything else raises
         ``ValueError`` before the frame changes anything.  ``scale`` (a filter built with ``frame_scale=True``): the frame's
-        process-noise scale, a number >= 0."""
+        process-noise scale, a number >= 0.  ``motion`` (a filter built with ``motion=True``): ``(d, w)``, the camera's
+        motion since the previous frame in its own frame; the same as ``move(d, w)`` followed by the call without it: the arguments are validated first, then the camera moves, then the frame runs -- an error the frame itself raises afterwards (capacity, a sticky device error) leaves the camera moved."""
         if isinstance(ids, np.ndarray) and ids.dtype.kind in "iu":
             ids = ids.reshape(-1).tolist()
         else:
@@ -107,6 +109,9 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         poses = np.asarray(poses, dtype=np.float64).reshape(len(ids), -1)
         rows = self._frame_noise(noise, len(ids))
         scale = self._frame_scale(scale)
+        motion = self._frame_motion(motion)
+        if motion is not None:      # the camera moves first: first sightings are placed from the moved camera
+            self._move(motion)
         known = self.landmarks
         try:                                   # steady state: every marker of the frame is in the map already
             index = [known[i] for i in ids]

@@ -37,7 +37,7 @@ class EKF(BaseFilter):
                  quat_update: str = "as_written", cov_kernel: str = "auto",
                  device: str = "cuda:0", map_file=None, lookahead: bool | None = None,
                  fused: bool = True, noise: dict | None = None, gate: float | None = None, confirm: tuple | None = None,
-                 row_noise: bool = False, frame_scale: bool = False) -> None:
+                 row_noise: bool = False, frame_scale: bool = False, motion: bool = False) -> None:
         """Positional arguments as the reference (:40-43).  Keyword-only extras:
         initial capacity (default: the number of ids of ``aruco_dict`` -- DICT_5X5_50
         has 50, base_filter.py:81-82; the buffers grow when more markers or more
@@ -54,7 +54,9 @@ class EKF(BaseFilter):
         frames of its first sighting, or ``process_detections`` removes it again (``remove_markers``); None: off.
         ``row_noise``: the filter takes per-detection measurement noise (``observe(..., noise=)``).
         ``frame_scale``: frames may carry a process-noise scale (``observe(..., scale=)``, ``advance``): time between
-        frames, in units of a nominal frame period, multiplies Q, and time without an update is kept for the next one."""
+        frames, in units of a nominal frame period, multiplies Q, and time without an update is kept for the next one.
+        ``motion``: frames may carry the camera's motion since the previous frame (``observe(..., motion=)``, ``move``):
+        odometry moves the prior instead of leaving the update to catch up with a camera the model holds still."""
         super().__init__(initial_camera_pose, map_file, aruco_dict)
         self._initial_pose = np.array(initial_camera_pose)      # :46, dtype kept
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -75,7 +77,8 @@ class EKF(BaseFilter):
         constants.update(noise or {})
         self._hip = HipEkf(max_landmarks, max_visible, cov_dtype=cov_dtype,
                            quat_mode=quat_update, cov_kernel=cov_kernel, device=device, lookahead=lookahead, fused=fused,
-                           noise=constants, gate=gate, row_noise=row_noise, frame_scale=frame_scale)
+                           noise=constants, gate=gate, row_noise=row_noise, frame_scale=frame_scale,
+                           motion=motion)
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._load_initial_map()
         self._init_confirm(confirm)
@@ -83,7 +86,7 @@ class EKF(BaseFilter):
     # -- attributes the base class / callers read (base_filter.py:293-304) ---
     @property
     def state(self) -> np.ndarray:
-        if self.num_landmarks == 0 and not self._pruned:
+        if self.num_landmarks == 0 and not self._pruned and not self._moved:
             # the reference keeps the caller's (int64) array until the first
             # hstack (:46, :274): D7 in SURVEY appendix A
             return self._initial_pose
@@ -94,13 +97,15 @@ class EKF(BaseFilter):
         return self._hip.get_cov()
 
     # -- :58-82 ----------------------------------------------------------------
-    def observe(self, ids, poses, noise=None, scale=None) -> None:
+    def observe(self, ids, poses, noise=None, scale=None, motion=None) -> None:
         """Add unseen markers, predict, update.  ``ids``: iterable of marker
         ids; ``poses``: (m, 6) ``[tvec | rvec]``, only ``pose[0:3]`` is used.  ``noise`` (a filter built with
         ``row_noise=True``): the frame's measurement noise, [m] (one variance per detection) or [m, 3] (x, y, z in the
         camera frame) instead of ``r_uncertainty``; anything else raises ``ValueError`` before the frame changes anything.
         ``scale`` (a filter built with ``frame_scale=True``): the frame's process-noise scale, a number >= 0; the frame
-        runs with Q times (pending scale + scale)."""
+        runs with Q times (pending scale + scale).  ``motion`` (a filter built with ``motion=True``): six numbers
+        ``(d, w)``, the camera's translation and rotation vector since the previous frame in its own frame; the same as
+        ``move(d, w)`` followed by the call without it: the arguments are validated first, then the camera moves, then the frame runs -- an error the frame itself raises afterwards (capacity, a sticky device error) leaves the camera moved."""
         if isinstance(ids, np.ndarray) and ids.dtype.kind in "iu":
             ids = ids.reshape(-1).tolist()     # (what process_frame passes: ids.flatten(), base_filter.py:199)
         else:
@@ -110,6 +115,9 @@ class EKF(BaseFilter):
         poses = np.asarray(poses, dtype=np.float64).reshape(len(ids), -1)
         rows = self._frame_noise(noise, len(ids))
         scale = self._frame_scale(scale)
+        motion = self._frame_motion(motion)
+        if motion is not None:      # the camera moves first: first sightings are placed from the moved camera
+            self._move(motion)
         known = self.landmarks
         try:                                   # steady state: every marker of the frame is in the map already
             index = [known[i] for i in ids]

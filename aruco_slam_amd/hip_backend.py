@@ -23,6 +23,7 @@ EKF_FLAG_BATCH_WIDE_FRAMES = 32  # ekf_config.flags bit 5 (batches): up to 64 (E
 EKF_FLAG_GATE = 64             # ekf_config.flags bit 6: the per-detection chi-square gate of the single filter
 EKF_FLAG_ROW_NOISE = 128       # ekf_config.flags bit 7: per-detection measurement noise of the single filter (rows=)
 EKF_FLAG_FRAME_SCALE = 256     # ekf_config.flags bit 8: per-frame process-noise scale and the pending scale (scale=)
+EKF_FLAG_MOTION = 512          # ekf_config.flags bit 9: per-frame camera motion of the single filter (motion=, move)
 EKF_COVK_AUTO, EKF_COVK_VALU, EKF_COVK_MFMA, EKF_COVK_MFMA_TILE, EKF_COVK_MFMA_MACRO = 0, 1, 2, 3, 4
 
 # frames in the end-gate ring of ekf_debug_fetch item 6 (csrc/ekf_kernels.h: EKF_GATE_LOG_FRAMES)
@@ -49,6 +50,8 @@ EXPORTED_SYMBOLS = (
     "ekf_advance", "ekf_get_pending_scale", "ekf_set_pending_scale", "ekf_observe_scaled",
     "ekf_observe_sequence_device_scaled", "ekf_observe_log_scaled", "ekf_batch_observe_logs_scaled",
     "ekf_batch_get_pending_scale", "ekf_batch_set_pending_scale",
+    "ekf_move", "ekf_observe_moved", "ekf_observe_sequence_device_moved", "ekf_observe_log_moved",
+    "ekf_batch_observe_logs_moved",
 )
 
 
@@ -137,6 +140,12 @@ def load_library(path: str | Path | None = None):
                                           vp, vp, vp],
         "ekf_batch_get_pending_scale": [vp, C.c_int32, dp],
         "ekf_batch_set_pending_scale": [vp, C.c_int32, dp],
+        "ekf_move": [vp, dp],
+        "ekf_observe_moved": [vp, ip, dp, dp, C.c_int32, C.POINTER(C.c_uint8), dp, ip, C.c_double, dp],
+        "ekf_observe_sequence_device_moved": [vp, vp, vp, vp, dp, dp, C.c_int32, C.c_int32, vp],
+        "ekf_observe_log_moved": [vp, ip, C.POINTER(C.c_int64), C.c_int32, vp, vp, dp, dp, vp, C.c_size_t, vp, vp],
+        "ekf_batch_observe_logs_moved": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, vp, vp, vp, vp, C.c_size_t,
+                                         vp, vp, vp, vp],
         "ekf_remove_workspace_bytes": [vp, C.c_int32, C.POINTER(C.c_size_t)],
         "ekf_remove_markers": [vp, ip, C.c_int32, vp, C.c_int64, vp, vp, C.c_size_t],
         "ekf_batch_remove_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],
@@ -223,6 +232,22 @@ def frame_scale_array(scale, count: int | None = None, what: str = "scale"):
     return float(v) if count is None else np.ascontiguousarray(v)
 
 
+def motion_array(motion, count: int | None = None, what: str = "motion"):
+    """Camera motions as the C ABI takes them: ``(d, w)`` -- six numbers, a translation and a rotation vector in the camera
+    frame of the previous pose -- as a contiguous float64 [6] (``count`` None) or [count, 6] array.  Another shape, or an
+    entry that is NaN or Inf, raises ``ValueError``."""
+    shape = (6,) if count is None else (count, 6)
+    try:
+        v = np.asarray(motion, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what} must be numbers of shape {shape}") from e
+    if v.shape != shape:
+        raise ValueError(f"{what} must have shape {shape}, got {v.shape}")
+    if not np.isfinite(v).all():
+        raise ValueError(f"{what} must be finite")
+    return np.ascontiguousarray(v)
+
+
 def _dptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
@@ -257,14 +282,16 @@ class HipEkf:
 
     def __init__(self, max_landmarks: int, max_visible: int, cov_dtype="float64",
                  quat_mode="as_written", cov_kernel="auto", device="cuda:0", noise=None,
-                 lookahead=None, model="ekf", fused=True, gate=None, row_noise=False, frame_scale=False):
+                 lookahead=None, model="ekf", fused=True, gate=None, row_noise=False, frame_scale=False, motion=False):
         """``gate``: None = a filter without the per-detection gate (sizes and results as ever); a number > 0 = the
         chi-square gate on every detection's own d^2 (``set_gate``; ``inf``: the filter can gate and report distances, but
         the gate is off).
         ``row_noise``: the filter takes per-detection measurement noise (``rows=`` of the observe calls); without it,
         sizes and results as ever.
         ``frame_scale``: frames may carry a process-noise scale (``scale=`` of the observe calls, ``advance``) and the
-        filter keeps a pending scale; without it, results as ever."""
+        filter keeps a pending scale; without it, results as ever.
+        ``motion``: frames may carry a camera motion (``motion=`` of the observe calls, ``move``); without it, results as
+        ever."""
         import torch
         self._torch = torch
         self.lib = load_library()
@@ -292,6 +319,8 @@ class HipEkf:
             cfg.flags |= EKF_FLAG_ROW_NOISE
         if frame_scale:
             cfg.flags |= EKF_FLAG_FRAME_SCALE
+        if motion:
+            cfg.flags |= EKF_FLAG_MOTION
         self.fused = bool(fused)  # ("force" of earlier versions == True: there is no automatic fallback any more)
         self._last_m = 1
         cfg.model = {"ekf": 0, "ekf_rotations": 1}[model]
@@ -334,6 +363,22 @@ class HipEkf:
     @property
     def can_frame_scale(self) -> bool:
         return bool(self.cfg.flags & EKF_FLAG_FRAME_SCALE)
+
+    @property
+    def can_motion(self) -> bool:
+        return bool(self.cfg.flags & EKF_FLAG_MOTION)
+
+    def _motion(self, motion, count: int | None = None):
+        """``motion`` of a call as a contiguous [6] (``count`` None) or [count, 6] array (``motion_array``); a filter built
+        without ``motion=True`` raises ``ValueError``."""
+        if not self.can_motion:
+            raise ValueError("this filter was built without camera motions: construct it with motion=True")
+        return motion_array(motion, count)
+
+    def move(self, motion) -> None:
+        """The camera moves by ``motion = (d, w)`` in its own frame (ekf_move): state and P on the device, nothing is
+        synchronised; six exact zeros enqueue nothing."""
+        self._check(self.lib.ekf_move(self.h, _dptr(self._motion(motion))))
 
     def _scale(self, scale, count: int | None = None):
         """``scale`` of an observe call as a float (``count`` None) or a contiguous [count] array (``frame_scale_array``);
@@ -482,14 +527,16 @@ class HipEkf:
         self._check(self.lib.ekf_add_markers(self.h, _dptr(xyz), _dptr(unc) if unc is not None else None,
                                              xyz.shape[0]))
 
-    def observe(self, lm_index, z, exempt=None, mahal=False, rows=None, scale=None):
+    def observe(self, lm_index, z, exempt=None, mahal=False, rows=None, scale=None, motion=None):
         """One frame.  With ``exempt`` (bool [m]: detections the gate leaves alone, d^2 = 0) or ``mahal=True`` the frame
         goes through ekf_observe_gated (a filter built with ``gate=``) and returns every detection's d^2 [m]; a set gate
         acts either way.
         ``rows`` ([m] or [m, rd] variances; a filter built with ``row_noise=True``): the frame's measurement noise is
         diag(rows) instead of r_uncertainty I (ekf_observe_rows).
         ``scale`` (a number >= 0; a filter built with ``frame_scale=True``): the frame's process-noise scale
-        (ekf_observe_scaled); None: the frame carries none."""
+        (ekf_observe_scaled); None: the frame carries none.
+        ``motion`` ([6] = (d, w); a filter built with ``motion=True``): the camera moves first (ekf_observe_moved; without
+        a scale ekf_move and then the call without it, which is the same thing); None: the frame carries none."""
         idx = np.ascontiguousarray(lm_index, dtype=np.int32)
         z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1, self.rows_per_detection)
         assert idx.shape[0] == z.shape[0]
@@ -500,6 +547,11 @@ class HipEkf:
             rows = self._rows(rows, idx.shape[0])
         if scale is not None:
             scale = self._scale(scale)
+        if motion is not None:
+            motion = self._motion(motion)
+            if scale is None:
+                self._check(self.lib.ekf_move(self.h, _dptr(motion)))
+                motion = None
         if exempt is None and not mahal and rows is None and scale is None:
             self._check(self.lib.ekf_observe(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z),
                                              idx.shape[0]))
@@ -510,10 +562,11 @@ class HipEkf:
             assert ex.shape[0] == idx.shape[0]
         d2 = np.empty(idx.shape[0]) if mahal else None
         if scale is not None:
-            self._check(self.lib.ekf_observe_scaled(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z),
-                                                    _dptr(rows) if rows is not None else None, idx.shape[0],
-                                                    ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None,
-                                                    _dptr(d2) if mahal else None, None, scale))
+            self._check(self.lib.ekf_observe_moved(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z),
+                                                   _dptr(rows) if rows is not None else None, idx.shape[0],
+                                                   ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None,
+                                                   _dptr(d2) if mahal else None, None, scale,
+                                                   _dptr(motion) if motion is not None else None))
             return d2
         if rows is not None:
             self._check(self.lib.ekf_observe_rows(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z), _dptr(rows),
@@ -526,15 +579,30 @@ class HipEkf:
                                                _dptr(d2) if mahal else None, None))
         return d2
 
-    def observe_sequence(self, idx_t, z_t, traj_t=None, rows=None, scale=None):
+    def observe_sequence(self, idx_t, z_t, traj_t=None, rows=None, scale=None, motion=None):
         """idx_t int32 [F,m], z_t float64 [F,m,3] device tensors (resident
         detections); traj_t float64 [F,7] or None; rows: float64 device tensor [F,m,rd] of row variances (the caller's
         contract: finite, > 0; a filter built with ``row_noise=True``) or None; scale: [F] numbers >= 0 on the host (a
-        filter built with ``frame_scale=True``; ekf_observe_sequence_device_scaled) or None."""
+        filter built with ``frame_scale=True``; ekf_observe_sequence_device_scaled) or None; motion: [F, 6] camera motions
+        on the host (a filter built with ``motion=True``; ekf_observe_sequence_device_moved: serial order) or None."""
         frames, m = idx_t.shape
         assert idx_t.is_cuda and z_t.is_cuda and idx_t.is_contiguous() and z_t.is_contiguous()
         assert tuple(z_t.shape) == (frames, m, self.rows_per_detection)
         self._last_m = m
+        if motion is not None:
+            motion = self._motion(motion, frames)
+            if scale is not None:
+                scale = self._scale(scale, frames)
+            if rows is not None:
+                if not self.can_row_noise:
+                    raise ValueError("this filter was built without per-detection noise: construct it with row_noise=True")
+                assert rows.is_cuda and rows.dtype == self._torch.float64 and rows.is_contiguous()
+                assert tuple(rows.shape) == tuple(z_t.shape)
+            self._check(self.lib.ekf_observe_sequence_device_moved(
+                self.h, idx_t.data_ptr(), z_t.data_ptr(), rows.data_ptr() if rows is not None else None,
+                _dptr(scale) if scale is not None else None, _dptr(motion), m, frames,
+                traj_t.data_ptr() if traj_t is not None else None))
+            return
         if scale is not None:
             scale = self._scale(scale, frames)
             if rows is not None:
@@ -559,7 +627,7 @@ class HipEkf:
             self.h, idx_t.data_ptr(), z_t.data_ptr(), m, frames,
             traj_t.data_ptr() if traj_t is not None else None))
 
-    def observe_log(self, lm_index, offsets, poses, traj=None, mahal=None, rows=None, scale=None):
+    def observe_log(self, lm_index, offsets, poses, traj=None, mahal=None, rows=None, scale=None, motion=None):
         """A whole detection log in one call (ekf_observe_log): lm_index int [D] landmark index of every detection (first
         sightings numbered n, n+1, ... in order of first occurrence), offsets int [F+1], poses [D,6] ``[tvec | rvec]`` as a
         NumPy array (uploaded once) or a contiguous float64 device tensor on this filter's device; traj: float64 device
@@ -567,7 +635,8 @@ class HipEkf:
         every detection's d^2 (ekf_observe_log_gated; a filter built with ``gate=``), or None; rows: [D] or [D, rd] row
         variances, indexed like lm_index (NumPy, validated and uploaded; a filter built with ``row_noise=True``), or None;
         scale: [F] numbers >= 0, one per frame, empty frames included (a filter built with ``frame_scale=True``;
-        ekf_observe_log_scaled), or None.
+        ekf_observe_log_scaled), or None; motion: [F, 6] camera motions, one per frame, empty frames included (a filter
+        built with ``motion=True``; ekf_observe_log_moved: serial order), or None.
         Capacity must already suffice (grow() first)."""
         torch = self._torch
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
@@ -594,6 +663,8 @@ class HipEkf:
             rows = self._rows(rows, idx.shape[0])
         if scale is not None:
             scale = self._scale(scale, frames)
+        if motion is not None:
+            motion = self._motion(motion, frames)
         nbytes = C.c_size_t()
         self._check(self.lib.ekf_log_workspace_bytes(self.h, idx.shape[0], C.byref(nbytes)))
         # device tensors of the caller (poses, traj) were produced on its current stream
@@ -611,11 +682,12 @@ class HipEkf:
             if mahal is not None:
                 mahal.record_stream(self.stream)
             rows_t = torch.from_numpy(rows).to(self.device, non_blocking=False) if rows is not None else None
-            self._check(self.lib.ekf_observe_log_scaled(
+            self._check(self.lib.ekf_observe_log_moved(
                 self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), frames,
                 poses_t.data_ptr() if idx.shape[0] else None,
                 rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None,
-                _dptr(scale) if scale is not None and frames else None, ws.data_ptr(), nbytes.value,
+                _dptr(scale) if scale is not None and frames else None,
+                _dptr(motion) if motion is not None and frames else None, ws.data_ptr(), nbytes.value,
                 traj.data_ptr() if traj is not None else None,
                 mahal.data_ptr() if mahal is not None and idx.shape[0] else None))
         self._log_keep = (poses_t, ws, rows_t)     # (released by the next call; record_stream already guards the allocator)

@@ -70,6 +70,17 @@ def detection_noise(path: str):
     return np.asarray(det["noise"], dtype=np.float64) if "noise" in det.files else None
 
 
+def detection_motion(path: str):
+    """The optional ``motion`` array of a replay file: the camera's motion ``(d, w)`` before every frame, in the camera frame
+    of the previous pose, [F, 6] with one row per frame (empty frames included); None for a file without one.  Another shape
+    or an entry that is not finite raises ``ValueError``."""
+    det = np.load(path, allow_pickle=False)
+    if "motion" not in det.files:
+        return None
+    from ..hip_backend import motion_array
+    return motion_array(det["motion"], len(det["timestamps_ms"]))
+
+
 def frame_scales(path: str, frame_period_ms: float) -> np.ndarray:
     """The per-frame process-noise scales of a replay file for ``--frame-period``: ``(t_f - t_{f-1}) / frame_period_ms``
     from its ``timestamps_ms``, 1 for frame 0.  Timestamps that decrease, or a period that is not a finite number > 0,
@@ -84,10 +95,10 @@ def frame_scales(path: str, frame_period_ms: float) -> np.ndarray:
     return np.concatenate((np.ones(min(1, stamps.shape[0])), steps / period))
 
 
-def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryWriter, scales=None) -> None:
+def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryWriter, scales=None, motion=None) -> None:
     """The whole replay file through ``process_detection_log``, then one trajectory line per frame.  Frames before the first
     stepped one carry the camera pose the filter had before the call (the integer initial pose of a fresh filter), as the
-    frame-by-frame loop writes them."""
+    frame-by-frame loop writes them; from the first frame with a motion on, the row is the (moved) pose of the device."""
     det = np.load(path, allow_pickle=False)
     offsets, has = det["offsets"], det["has_detections"].astype(bool)
     start_pose = tracker.get_poses()[0]
@@ -95,8 +106,12 @@ def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryW
     extra = {} if noise is None else {"noise": noise}
     if scales is not None:
         extra["scale"] = scales
+    if motion is not None:
+        extra["motion"] = motion
     traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has, **extra)
     stepped = has & (np.diff(offsets) > 0)
+    if motion is not None:
+        stepped = stepped | motion.any(axis=1)
     first = int(np.argmax(stepped)) if stepped.any() else len(has)
     for f, timestamp in enumerate(det["timestamps_ms"]):
         cam_traj_writer.write(float(timestamp), start_pose if f < first else traj[f])
@@ -120,6 +135,9 @@ def main(cmdline_args: argparse.Namespace) -> None:
             raise ValueError("--frame-period reads the timestamps of a detections file: pass --detections <replay.npz>")
         scales = frame_scales(cmdline_args.detections, cmdline_args.frame_period)
         kwargs["frame_scale"] = True
+    motion = detection_motion(cmdline_args.detections) if cmdline_args.detections else None
+    if motion is not None:
+        kwargs["motion"] = True      # (the file carries odometry: frame loop and resident replay move the camera first)
     tracker = init_tracker(cmdline_args.filter, initial_pose, **kwargs)
     out_dir = Path(getattr(cmdline_args, "output_dir", "outputs"))
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -129,13 +147,15 @@ def main(cmdline_args: argparse.Namespace) -> None:
         raise ValueError("--resident replays a detections file: pass --detections <replay.npz>")
     with TrajectoryWriter(str(out_dir / "trajectory.txt")) as cam_traj_writer:
         if resident:
-            replay_resident(tracker, cmdline_args.detections, cam_traj_writer, scales)
+            replay_resident(tracker, cmdline_args.detections, cam_traj_writer, scales, motion)
         elif cmdline_args.detections:
             offs = np.load(cmdline_args.detections, allow_pickle=False)["offsets"]
             for f, (timestamp, ids, poses) in enumerate(detection_frames(cmdline_args.detections)):
                 extra = {} if scales is None else {"scale": scales[f]}
                 if noise is not None and ids is not None:
                     extra["noise"] = noise[int(offs[f]):int(offs[f + 1])]
+                if motion is not None:
+                    extra["motion"] = motion[f]
                 _, camera_pose, _, _ = tracker.process_detections(ids, poses, **extra)
                 cam_traj_writer.write(timestamp, camera_pose)
         else:

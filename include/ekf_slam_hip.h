@@ -60,6 +60,8 @@ enum { EKF_FLAG_GATE = 64 };
 enum { EKF_FLAG_ROW_NOISE = 128 };
 /* ekf_config.flags bit 8: per-frame process-noise scale (ekf_observe_scaled, ekf_advance; ekf_batch_observe_logs_scaled) */
 enum { EKF_FLAG_FRAME_SCALE = 256 };
+/* ekf_config.flags bit 9: per-frame camera motion (ekf_move, ekf_observe_moved; ekf_batch_observe_logs_moved) */
+enum { EKF_FLAG_MOTION = 512 };
 enum { EKF_COVK_AUTO = 0, EKF_COVK_VALU = 1, EKF_COVK_MFMA = 2, EKF_COVK_MFMA_TILE = 3, EKF_COVK_MFMA_MACRO = 4 };
 
 enum {
@@ -109,7 +111,9 @@ typedef struct ekf_config {
                              * bit 8 (EKF_FLAG_FRAME_SCALE): frames may carry a process-noise scale and the filter keeps a
                              * pending scale (see "Per-frame process-noise scale").  The single filter's sizes do not
                              * change (the pending scale lives on the host); a batch's workspace grows by 8 bytes per
-                             * member, padded to 256.  Without it, sizes, layout and results are as before. */
+                             * member, padded to 256.  Without it, sizes, layout and results are as before.
+                             * bit 9 (EKF_FLAG_MOTION): frames may carry a camera motion (see "Odometry input").  No size
+                             * and no layout changes. */
     /* noise constants, defaults = extended_kalman_filter.py:21-27 */
     double initial_camera_uncertainty;   /* 0.1  */
     double initial_landmark_uncertainty; /* 0.7  */
@@ -676,6 +680,80 @@ int ekf_batch_observe_logs_scaled(ekf_batch *b, const int32_t *lm_index, const i
                                   double *cam_cov_dev, double *mahal_dev);
 int ekf_batch_get_pending_scale(ekf_batch *b, int32_t member, double *out);
 int ekf_batch_set_pending_scale(ekf_batch *b, int32_t member, const double *pending);
+
+/* ---- Odometry input: per-frame camera motion in the predict step (ekf_config.flags bit 9, EKF_FLAG_MOTION; single filter
+ * and batch).  Every update predicts with a camera that stands still, x_{t+1|t} = x_t; with the reference's noise constants
+ * the gain on the camera is small, and a moving camera is tracked with a lag that grows with its speed.  A motion makes the
+ * camera's movement between two frames data of the frame: wheel or visual odometry, an IMU pre-integration, a commanded
+ * motion.
+ * Semantics (part of the ABI):
+ *   1. A frame may carry a motion u = (d, w): six f64, d a translation and w a rotation vector (radians), both expressed in
+ *      the camera frame of the previous pose.  It is data of the frame, not state of the handle.
+ *   2. State.  R(q) is the normalised rotation matrix of the scalar-first quaternion q = state[3:7], the camera-to-map
+ *      rotation of the measurement model h = R(q)^T (l - c), whatever ekf_config.quat_mode says about the injection.
+ *      delta = (cos(|w|/2), sin(|w|/2) w/|w|), and delta = (1, 0, 0, 0) exactly when w = 0.  The move is c' = c + R(q) d, then
+ *      q' = q (x) delta (Hamilton product; then normalised, q' / |q'|, as the injection normalises its product; with w = 0
+ *      q' = q, bit for bit).  The error state stays 0 and the landmarks are untouched.
+ *   3. Covariance.  P <- F~ P F~^T, F~ = diag(F, I), F the 10 x 10 Jacobian of (c, q, e) -> (c + R((1,e) (x) q) d, q (x) delta, e)
+ *      at e = 0 in the state's column order [c q e]:
+ *          F = [ I   G      G E(q) ]      G    = d(R(q) d)/dq  (3 x 4, R normalised)
+ *              [ 0   Rm(d)  0      ]      E(q) = d((1,e) (x) q)/de at 0  (4 x 3)
+ *              [ 0   0      I      ]      Rm(delta): a (x) delta = Rm(delta) a
+ *      Only rows and columns 0 .. 9 of P change.  All arithmetic is f64, every sum one ascending fma chain (the order is
+ *      stated in csrc/ekf_motion_device.h); an f32 P is widened on load and rounded once on store.  P stays bitwise
+ *      symmetric (one triangle of the 10 x 10 block is computed and mirrored; every strip entry and its mirror are stores of
+ *      the same value), nothing at or beyond N is written, and the capacity padding stays exactly zero.
+ *   4. Order inside a frame: the motion first, then first sightings (placed from the moved camera), then the gate (on the
+ *      moved prior), then predict and update with Q_eff as ever.  A frame that is not stepped (no detections, or none
+ *      survived the gate) is still moved: its trajectory row is the moved pose.  The pending scale is untouched by a motion.
+ *   5. A failed filter ignores motions, as it ignores everything.
+ *   6. Bit rules.  (a) motion = NULL, or a motion whose six numbers are all exactly 0, is the call without it: nothing is
+ *      enqueued for it, the same bits.  (b) ekf_observe_moved(..., u) is ekf_move(u) followed by ekf_observe_scaled(...).
+ *      (c) A log replay is the per-frame loop, and a sequence call is the loop (EKF_Rotations: as without motions, a log
+ *      replay forms z from the logged poses on the device, so it is bit for bit the loop that is fed the same z, and
+ *      agrees with a loop whose z was formed on the host to rounding).  (d) The batch large-map and wide-frame kernels are
+ *      bit for bit the one-column kernel where both run.  (e) With w = 0 the quaternion and its four
+ *      rows and columns of P are unchanged bit for bit, apart from the G terms in the position rows and columns.  (f) Gate,
+ *      rows and scales compose: a gated frame with a motion is bit for bit the ungated call with the same motion on the
+ *      survivors, and rule 5(b) of the frame scale holds on a moved frame.
+ *   7. The host-pointer entry points reject a NaN or Inf motion with EKF_ERR_INVALID and a motion given to a handle without
+ *      the flag with EKF_ERR_STATE, both before anything is enqueued.
+ * The flag changes no size and no layout: a motion travels in the kernel arguments.
+ *   ekf_move: the motion alone (rules 2 and 3), on the handle's stream; a state getter that follows returns the moved pose.
+ *   ekf_observe_moved: ekf_observe_scaled with the frame's motion [6] HOST or NULL.  Like ekf_observe_scaled it always
+ *     carries a scale, so the handle needs EKF_FLAG_FRAME_SCALE as well (EKF_ERR_STATE otherwise); a handle with
+ *     EKF_FLAG_MOTION alone calls ekf_move and then the observe call of its choice, which rule 6(b) makes the same thing.
+ *     The frame's landmarks are in the map
+ *     already; a caller with first sightings calls ekf_move, ekf_add_markers and then an observe call (rule 4).
+ *   ekf_observe_sequence_device_moved: ekf_observe_sequence_device_scaled with motion [frames, 6] HOST or NULL.
+ *   ekf_observe_log_moved: ekf_observe_log_scaled with motion [F, 6] HOST or NULL, one row per frame, empty frames included.
+ * A pipelined run completes P_{t+1} from P_t and W_t inside the next front kernel, which a motion between the two frames
+ * invalidates: a sequence or log call that is given a motion array (not NULL) runs its frames in serial order, reports
+ * EKF_SEQ_SERIAL, and ekf_last_log_stats reports 0 pipelined frames, as gated calls do.  A call without one pipelines as ever.
+ * Batch: a motion stage at the top of the frame in all three window kernels runs the same stage functions on the member's
+ * P; an empty frame with a motion moves the member and its trajectory row, a failed member ignores motions.  The flag
+ * changes no size.
+ *   ekf_batch_observe_logs_moved: ekf_batch_observe_logs_scaled with motion_dev [Ftot, 6] DEVICE or NULL, indexed like the
+ *     frames (frame_offsets); the caller's contract, like rows_dev and scale_dev: finite.  Without the flag: EKF_ERR_STATE.
+ * The replica entry points take no motion, as they take no rows and no scales. */
+int ekf_move(ekf_filter *f, const double motion[6]);
+int ekf_observe_moved(ekf_filter *f, const int32_t *lm_index, const double *z, const double *rows /* [m, rd] host or NULL */,
+                      int32_t m, const uint8_t *exempt /* [m] or NULL */, double *mahal /* [m] host or NULL */,
+                      int32_t *survivors /* or NULL */, double scale, const double *motion /* [6] HOST or NULL */);
+int ekf_observe_sequence_device_moved(ekf_filter *f, const int32_t *lm_index_dev, const double *z_dev,
+                                      const double *rows_dev /* [frames, m, rd] or NULL */,
+                                      const double *scale /* [frames] HOST or NULL */,
+                                      const double *motion /* [frames, 6] HOST or NULL */, int32_t m, int32_t frames,
+                                      double *trajectory_dev);
+int ekf_observe_log_moved(ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames,
+                          const double *poses_dev, const double *rows_dev /* [D, rd] or NULL */,
+                          const double *scale /* [F] HOST or NULL */, const double *motion /* [F, 6] HOST or NULL */,
+                          void *log_ws, size_t log_ws_bytes, double *trajectory_dev, double *mahal_dev /* [D] or NULL */);
+int ekf_batch_observe_logs_moved(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets,
+                                 const int64_t *member_frames, const double *poses_dev,
+                                 const double *rows_dev /* [D, rd] or NULL */, const double *scale_dev /* [Ftot] or NULL */,
+                                 const double *motion_dev /* [Ftot, 6] or NULL */, void *log_ws, size_t log_ws_bytes,
+                                 double *trajectory_dev, double *nis_dev, double *cam_cov_dev, double *mahal_dev);
 
 const char *ekf_last_error_string(void);
 

@@ -80,6 +80,9 @@ def main():
     ap.add_argument("--frame-scale", action="store_true",
                     help="also time the same logs with a process-noise scale on every frame (EKFBatch(frame_scale=True), "
                          "log-uniform scales in [0.5, 2]) and report its frames/s beside the figure without")
+    ap.add_argument("--motion", action="store_true",
+                    help="also time the same logs with a small camera motion on every frame (EKFBatch(motion=True), "
+                         "N(0, 1e-3^2) per component) and report its frames/s beside the figure without")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.batch import EKFBatch
@@ -155,6 +158,21 @@ def main():
             line["frame_scale_wall_s"] = round(wall_scaled, 6)
             line["frame_scale_frames_per_s"] = round(B * args.steady / wall_scaled, 1)
             del scaled
+        if args.motion:
+            rng = np.random.default_rng(99)
+            timed = [tuple(dict(part, motion=rng.normal(0.0, 1e-3, (len(part["offsets"]) - 1, 6))) for part in lg)
+                     for lg in logs[:B]]
+            moved = EKFBatch(B, INIT, max_landmarks=n, max_visible=visible, model=args.model, motion=True,
+                             large_maps=True if args.large_maps else None, **({} if args.gate is None else {"gate": args.gate}))
+            moved.process_detection_logs([lg[0] for lg in timed])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            moved.process_detection_logs([lg[1] for lg in timed])
+            wall_moved = time.perf_counter() - t0
+            assert moved.status() == [0] * B
+            line["motion_wall_s"] = round(wall_moved, 6)
+            line["motion_frames_per_s"] = round(B * args.steady / wall_moved, 1)
+            del moved
         if args.large_maps or batch.wide_frames:     # every stepped frame reads and writes the member's N x N f64 covariance
             # once (wide frames: once per block)
             dims = (10 if rot else 3) * n + 10

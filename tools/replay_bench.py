@@ -13,6 +13,8 @@ updates/s is steady frames per second of the steady segment; the bootstrap segme
                                                    # the host round trip per frame and of losing the pipelined mode
     python tools/replay_bench.py --row-noise       # every detection with its own row variances (log-uniform in [0.3, 3])
     python tools/replay_bench.py --frame-scale     # every frame with its own process-noise scale (log-uniform in [0.5, 2])
+    python tools/replay_bench.py --motion          # every frame with a small camera motion (N(0, 1e-3^2) per component): the
+                                                   # price of the motion launch per frame and of losing the pipelined mode
 """
 from __future__ import annotations
 
@@ -38,7 +40,7 @@ def _segment(log, t0, t1):
 def _filter(args):
     from aruco_slam_amd.filters.extended_kalman_filter import EKF
     return EKF(INIT, max_landmarks=args.n, max_visible=args.m[1], cov_dtype=args.dtype, gate=args.gate, row_noise=args.row_noise,
-               frame_scale=args.frame_scale)
+               frame_scale=args.frame_scale, motion=args.motion)
 
 
 def main():
@@ -52,6 +54,7 @@ def main():
     ap.add_argument("--gate", type=float, default=None, help="chi-square gate on every detection (default: a filter without)")
     ap.add_argument("--row-noise", action="store_true", help="per-detection measurement noise on every detection (noise=)")
     ap.add_argument("--frame-scale", action="store_true", help="a process-noise scale on every frame (scale=)")
+    ap.add_argument("--motion", action="store_true", help="a camera motion on every frame (motion=)")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.synthetic import SyntheticStream, ragged_log
@@ -68,14 +71,20 @@ def main():
     if args.frame_scale:
         scale = np.exp(np.random.default_rng(args.seed + 9).uniform(np.log(0.5), np.log(2.0), frames))
 
+    motion = None
+    if args.motion:
+        motion = np.random.default_rng(args.seed + 11).normal(0.0, 1e-3, (frames, 6))
+
     def seg_noise(t0, t1):
         kw = {} if noise is None else {"noise": noise[int(log["offsets"][t0]):int(log["offsets"][t1])]}
         if scale is not None:
             kw["scale"] = scale[t0:t1]
+        if motion is not None:
+            kw["motion"] = motion[t0:t1]
         return kw
 
     common = {"n": args.n, "m_range": list(args.m), "m_mean": float(m_steady.mean()), "dtype": args.dtype, "gate": args.gate,
-              "row_noise": bool(args.row_noise), "frame_scale": bool(args.frame_scale),
+              "row_noise": bool(args.row_noise), "frame_scale": bool(args.frame_scale), "motion": bool(args.motion),
               "bootstrap_frames": boot, "steady_frames": args.steady}
 
     def emit(**kv):
@@ -94,6 +103,8 @@ def main():
                     kw = {} if noise is None else {"noise": noise[sl]}
                     if scale is not None:
                         kw["scale"] = scale[t]
+                    if motion is not None:
+                        kw["motion"] = motion[t]
                     flt.process_detections(log["ids"][sl], log["poses"][sl], **kw)
             t = time.perf_counter()
             run(0, boot)
@@ -135,7 +146,8 @@ def main():
                     np.log(0.3), np.log(3.0), tuple(z_t.shape)))).to(b.device)
             torch.cuda.synchronize(b.device)
             t = time.perf_counter()
-            b.observe_sequence(idx_t, z_t, rows=rows_t, scale=None if scale is None else scale[boot:boot + args.steady])
+            b.observe_sequence(idx_t, z_t, rows=rows_t, scale=None if scale is None else scale[boot:boot + args.steady],
+                               motion=None if motion is None else motion[boot:boot + args.steady])
             b.sync()
             t_steady = time.perf_counter() - t
             rates[variant] = args.steady / t_steady

@@ -252,6 +252,10 @@ struct ekf_filter {
     // host launches every frame and knows which ones are stepped (a gated frame: after its round trip).  0 without the flag.
     double pending = 0.0;
 
+    // frozen map (ekf_set_map_frozen; include/ekf_slam_hip.h, "Localisation mode"): frames inject the camera only and run the
+    // camera-strip update (ekf_cov_strip.hip) in place of the covariance update, in serial order; off after create and reset
+    bool frozen = false;
+
     bool has_scale() const { return (cfg.flags & EKF_FLAG_FRAME_SCALE) != 0; }
     bool has_motion() const { return (cfg.flags & EKF_FLAG_MOTION) != 0; }
     bool gate_on() const { return lay.has_gate && gate < __builtin_inf(); }
@@ -341,6 +345,7 @@ EkfFrame make_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, 
     fr.n_lm = f->n_lm;
     fr.state_host = nullptr;
     fr.status_host = nullptr;
+    fr.frozen = f->frozen ? 1 : 0;
     fr.cov_tiles = nullptr;
     fr.cov_grid = 0;
     if (f->tiles_T > 0 && f->tiles_T == (fr.dims + 127) / 128) {
@@ -409,8 +414,10 @@ int ensure_tiles(ekf_filter* f) {
 // s_eff: the frame's process-noise scale (1: the constants)
 int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, const double* rows_dev, int m,
                   double* traj_row, bool mirror, double s_eff) {
-    int trc = ensure_tiles(f);
-    if (trc) return trc;
+    if (!f->frozen) {      // (a frozen frame runs the camera strip: no macro-tile table)
+        int trc = ensure_tiles(f);
+        if (trc) return trc;
+    }
     EkfFrame fr = make_frame(f, idx_dev, z_dev, rows_dev, m, traj_row, s_eff);
     const int variant = f->cfg.cov_kernel == EKF_COVK_VALU ? 1 : 2;
     hipEvent_t* ev = nullptr;
@@ -424,7 +431,11 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, co
     }
     hipEvent_t* ev_all = (ev && !f->timing_cov_only) ? ev : nullptr;
     if (ev_all) HIP_TRY(hipEventRecord(ev[0], f->stream));
-    const bool mirrored = use_front_kernel(f, fr) && !f->timing && mirror;
+    // (a frozen frame writes the camera only, so it is not mirrored: the mirror's landmark entries come from mirrored mapping
+    // frames, removals and full read backs alone, and add_markers, a log or a sequence call may have changed the device's
+    // since -- which the next mirrored mapping frame repairs by writing every entry, and a frozen one would not.  The getter
+    // behind a frozen frame copies the state from the device.)
+    const bool mirrored = use_front_kernel(f, fr) && !f->timing && mirror && !f->frozen;
     if (use_front_kernel(f, fr)) {
         // one launch: timing slot 0 = the whole front kernel, slots 1 and 2 stay empty
         bind_exchange(f, fr);
@@ -454,14 +465,14 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, co
             if (blocked) ekf_launch_wide_finish<decltype(elem)>(fr, aw, f->stream);
             else ekf_launch_panel<decltype(elem)>(fr, f->stream);
         });
-        if (fr.model == 1) ekf_launch_inject_rot(fr, f->n_lm, f->stream);
+        if (fr.model == 1) ekf_launch_inject_rot(fr, f->frozen ? 0 : f->n_lm, f->stream);      // (frozen map: block 0 only)
     } else {
         by_cov_type(f, [&](auto elem) { ekf_launch_gather<decltype(elem)>(fr, f->stream); });
         if (ev_all) HIP_TRY(hipEventRecord(ev[1], f->stream));
         ekf_launch_solve(fr, f->stream);
         if (ev_all) HIP_TRY(hipEventRecord(ev[2], f->stream));
         by_cov_type(f, [&](auto elem) { ekf_launch_panel<decltype(elem)>(fr, f->stream); });
-        if (fr.model == 1) ekf_launch_inject_rot(fr, f->n_lm, f->stream);
+        if (fr.model == 1) ekf_launch_inject_rot(fr, f->frozen ? 0 : f->n_lm, f->stream);
     }
     // The state (and the status word) are final here: a state getter that follows waits for this event only and
     // reads back beside the covariance update (sync_and_check) -- what BaseFilter.process_frame does every frame.
@@ -479,13 +490,22 @@ int enqueue_frame(ekf_filter* f, const int32_t* idx_dev, const double* z_dev, co
             cf.kpad = std::min(EKF_WIDE_REUSE_ROWS, fr.kpad - r0);
             cf.k = std::min(cf.kpad, std::max(0, fr.k - r0));
             if (r0 > 0) cf.nz.q_cam = cf.nz.q_err = cf.nz.q_lm = 0.0;
-            by_cov_type(f, [&](auto elem) { ekf_launch_cov_update<decltype(elem)>(cf, variant, f->stream); });
+            const bool ok = by_cov_type(f, [&](auto elem) {
+                if (f->frozen) return ekf_launch_cov_strip<decltype(elem)>(cf, variant, f->stream);      // (the same chunks in the same order)
+                ekf_launch_cov_update<decltype(elem)>(cf, variant, f->stream);
+                return true;
+            });
+            if (!ok) return fail(EKF_ERR_STATE, "internal: a row chunk larger than the strip kernel takes");
         }
         if (ev) HIP_TRY(hipEventRecord(ev[4], f->stream));
     } else {
-        by_cov_type(f, [&](auto elem) {
+        // frozen map: the camera strip, in place, in the covariance update's timing slot
+        const bool ok = by_cov_type(f, [&](auto elem) {
+            if (f->frozen) return ekf_launch_cov_strip<decltype(elem)>(fr, variant, f->stream, ev ? ev[3] : nullptr, ev ? ev[4] : nullptr);
             ekf_launch_cov_update<decltype(elem)>(fr, variant, f->stream, ev ? ev[3] : nullptr, ev ? ev[4] : nullptr);
+            return true;
         });
+        if (!ok) return fail(EKF_ERR_STATE, "internal: more rows than the strip kernel takes in one launch");
     }
     HIP_TRY(hipGetLastError());
     f->last_m = m;
@@ -626,7 +646,7 @@ bool take_pipelining_token(ekf_filter* f) {
 // *mode: the EKF_SEQ_* value that explains the outcome (ekf_last_sequence_mode), EKF_SEQ_PIPELINED if they may.
 int choose_pipelining(ekf_filter* f, bool want_runs, int* mode) {
     *mode = EKF_SEQ_SERIAL;
-    if (!want_runs) return EKF_OK;
+    if (!want_runs || f->frozen) return EKF_OK;      // (a frozen map: frame by frame in serial order)
     int rc = probe_queues(f);
     if (rc) return rc;
     if (f->la_ok == 0) *mode = EKF_SEQ_SERIAL_ONE_QUEUE;
@@ -1297,6 +1317,7 @@ int ekf_reset(ekf_filter* f, const double initial_camera_pose[10]) {
     f->n_lm = 0;
     f->last_m = 0;
     f->pending = 0.0;
+    f->frozen = false;      // (a reset filter has no map)
     f->is_reset = true;
     return EKF_OK;
 }
@@ -1485,7 +1506,8 @@ int ekf_observe_sequence_device_moved(ekf_filter* f, const int32_t* lm_index_dev
     if (f->n_lm < 1) return fail(EKF_ERR_STATE, "observe before any landmark was added");
     const int rd = f->lay.rd;
     f->reset_gate_stats();
-    if (f->gate_on() || motion) {
+    if (f->gate_on() || motion || f->frozen) {
+        // a frozen map: frame by frame in serial order, the camera strip behind every front part.
         // a gate is set: frame by frame in serial order, each frame on its survivors (gating inside a pipelined run would
         // need the mask inside the front kernel).  Motions: serial order as well -- a front kernel of a run completes
         // P_{t+1} from P_t and W_t, and a motion between the two frames changes rows of it
@@ -1604,7 +1626,8 @@ int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t*
     const bool gated = f->gate_on() || mahal_dev;
     // frame by frame in serial order: a gated call, and a call with motions (a motion between two frames of a pipelined run
     // would change rows of the P_{t+1} the next front kernel completes from P_t and W_t)
-    const bool by_frame = gated || motion;
+    // ... and a call on a frozen map
+    const bool by_frame = gated || motion || f->frozen;
     // ---- validation on the host: nothing is enqueued before the whole log has passed
     if (frames < 0) return fail(EKF_ERR_INVALID, "negative frame count");
     if ((rc = check_scales(f, scale, frames))) return rc;
@@ -1618,6 +1641,8 @@ int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t*
     if (D > 0 && (rc = check_device_buffers({log_ws}, log_ws_bytes, LL.total, "ekf_log_workspace_bytes"))) return rc;
     LogCheck lc;
     if ((rc = check_log(lm_index, offsets, frames, f->n_lm, f->cfg, "the log", &lc))) return rc;
+    if (f->frozen && !lc.slots.empty())
+        return fail(EKF_ERR_STATE, "the map is frozen: a log with first sightings would add landmarks (ekf_set_map_frozen)");
     for (int i = 0; i < 4; ++i) f->log_stats[i] = 0;
     f->reset_gate_stats();
     if (frames == 0) return EKF_OK;
@@ -1877,6 +1902,15 @@ int ekf_set_cov(ekf_filter* f, const double* cov, int32_t dims) {
 }
 
 int ekf_last_sequence_mode(const ekf_filter* f) { return f ? f->seq_mode : EKF_ERR_INVALID; }
+
+int ekf_set_map_frozen(ekf_filter* f, int32_t frozen) {
+    int rc = check_ready(f);
+    if (rc) return rc;
+    f->frozen = frozen != 0;
+    return EKF_OK;
+}
+
+int ekf_get_map_frozen(const ekf_filter* f) { return f ? (f->frozen ? 1 : 0) : EKF_ERR_INVALID; }
 
 int ekf_set_fused(ekf_filter* f, int32_t enable) {
     if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");

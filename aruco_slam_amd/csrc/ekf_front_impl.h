@@ -600,7 +600,8 @@ __device__ __forceinline__ void fr_panel_pre(const EkfFrame& fr, FrPre<NB>& pre,
 #pragma unroll
     for (int i = 0; i < 4; ++i) pre.q_old[i] = 0.0;
     if (MODEL == 0) {
-        if (mycol < fr.dims) pre.st_old = fr.state[mycol];
+        // (frozen map: a landmark column is not injected and needs no old state)
+        if (mycol < fr.dims && !(fr.frozen && mycol >= EKF_CAM)) pre.st_old = fr.state[mycol];
         if (col0 == 0)
             for (int i = 0; i < 4; ++i) pre.q_old[i] = fr.state[3 + i];
     }
@@ -939,7 +940,7 @@ __device__ __forceinline__ void fr_panel(const EkfFrame& fr, const double* a_lds
         // extended_kalman_filter.py:133-152.  Nobody reads the state any more: its only readers
         // in this launch are the S-block workgroups, which the factorisation has waited for.
         double nv = 0.0;
-        if (g == 0 && (col < 3 || (col >= EKF_CAM && col < fr.dims))) {
+        if (g == 0 && (col < 3 || (col >= EKF_CAM && col < fr.dims && !fr.frozen))) {      // (frozen map: the camera only)
             nv = st_old + part;
             fr.state[col] = nv;
             if (fr.state_host) fr.state_host[col] = nv;
@@ -1319,7 +1320,8 @@ __device__ __forceinline__ void fr_role_chunk(const EkfFrame& fr, int chunk, dou
     }
     __syncthreads();
     if (!flag[0]) return;
-    for (int i = tid; i <= fr.n_lm; i += FR_T) {
+    const int blocks = fr.frozen ? 0 : fr.n_lm;         // (frozen map: block 0, the camera, only)
+    for (int i = tid; i <= blocks; i += FR_T) {
         const int c0 = (i == 0) ? 0 : EKF_CAM + 10 * (i - 1);
         double* st = fr.state + c0;
         const double* dx = fr.dxvec + c0;

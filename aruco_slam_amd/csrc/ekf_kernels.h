@@ -120,6 +120,11 @@ struct EkfFrame {
     // the front-kernel instances a frame with another Q than its predecessor's runs (ekf_front_impl.h: QPREV).  At the end:
     // every other argument is where it was (the kernel arguments grow from 504 to 528 bytes).
     double qprev_cam, qprev_err, qprev_lm;
+    // Frozen map (include/ekf_slam_hip.h, "Localisation mode"): non-zero = the injection writes the camera only -- dx[0:3], the
+    // quaternion rule on dx[7:10], state[7:10] = 0; EKF_Rotations: block 0 -- and every landmark entry of the state and of
+    // the pinned mirror keeps its bits.  Everything up to W and dx is the mapping frame's.  At the end, as the qprev fields
+    // before it: every other argument is where it was (the kernel arguments grow from 528 to 536 bytes).
+    int32_t frozen;
 };
 
 // process-noise diagonal of state dimension i as the PREVIOUS frame of a pipelined run added it (ekf_qdiag on its Q_eff)
@@ -207,6 +212,14 @@ template <typename T> void ekf_launch_panel(const EkfFrame& fr, hipStream_t s);
 // e0 / e1 (optional): events that receive the kernel's own start / stop time stamps (hipExtLaunchKernelGGL)
 template <typename T> void ekf_launch_cov_update(const EkfFrame& fr, int variant, hipStream_t s,
                                                  hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// Frozen map (ekf_cov_strip.hip): the camera strip of the same update, in place: rows and columns 0 .. 9 of P get the value
+// the full update gives them (the same fma chain per element), P[10:N, 10:N] is neither read nor written.  e0 / e1 as above.
+// variant: the covariance update the handle runs (1 = VALU reference kernel, 2 = MFMA): the strip takes its chain step, which
+// differs between the two for the f32 covariance.  false: nothing was launched, fr.kpad exceeds EKF_WIDE_REUSE_ROWS (the
+// caller chunks such a frame).
+#define EKF_STRIP_THREADS 256
+template <typename T> bool ekf_launch_cov_strip(const EkfFrame& fr, int variant, hipStream_t s, hipEvent_t e0 = nullptr,
+                                                hipEvent_t e1 = nullptr);
 // f32, large problems: one workgroup per 128 x 128 macro tile, launch order fr.cov_tiles / fr.cov_grid (ekf_cov_macro.hip)
 void ekf_launch_cov_update_macro(const EkfFrame& fr, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // launch order for T x T macro tiles (lower triangle), super-tiles of S x S dealt to the 8 XCDs: returns the grid size

@@ -280,7 +280,7 @@ __global__ __launch_bounds__(64) void ekf_panel_mfma_kernel(EkfFrame fr) {
         return;
     }
     double nv = 0.0;
-    if (g == 0 && (col < 3 || (col >= EKF_CAM && col < fr.dims))) {
+    if (g == 0 && (col < 3 || (col >= EKF_CAM && col < fr.dims && !fr.frozen))) {      // (frozen map: the camera only)
         nv = fr.state[col] + part;                   // extended_kalman_filter.py:134-135
         fr.state[col] = nv;
     }

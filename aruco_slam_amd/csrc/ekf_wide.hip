@@ -357,7 +357,7 @@ __global__ __launch_bounds__(1024) void ekf_wide_finish_kernel(EkfFrame fr, cons
         return;
     }
     double nv = 0.0;
-    if (col < 3 || (col >= EKF_CAM && col < fr.dims)) {
+    if (col < 3 || (col >= EKF_CAM && col < fr.dims && !fr.frozen)) {      // (frozen map: the camera only)
         nv = fr.state[col] + dx;                       // extended_kalman_filter.py:134-135
         fr.state[col] = nv;
     }

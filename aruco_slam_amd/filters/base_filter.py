@@ -63,13 +63,16 @@ class DetectionLogPlan(NamedTuple):
     new_landmarks: dict        # marker id -> landmark index of the ids the log adds, in order of first occurrence
     num_landmarks: int         # landmarks after the log
     widest: int                # most detections in one frame
+    ignored: tuple = ()        # frozen map: the marker ids of the rows that were dropped because the map does not hold them, in order
 
 
-def plan_detection_log(landmarks, num_landmarks, ids, offsets, has_detections=None) -> DetectionLogPlan:
+def plan_detection_log(landmarks, num_landmarks, ids, offsets, has_detections=None, frozen=False) -> DetectionLogPlan:
     """Host side of ``process_detection_log``: check the CSR log and map marker ids to landmark indices as ``observe`` does
     frame by frame (known ids keep their index, new ones are numbered ``num_landmarks``, ``+1``, ... in order of first
     occurrence, duplicates of a new id inside its frame share its index).  ``landmarks`` is not modified.  Raises
-    ``ValueError`` for a malformed log."""
+    ``ValueError`` for a malformed log.  ``frozen`` (a frozen map): detections of ids that are not in ``landmarks`` are
+    dropped as ``observe`` drops them -- their rows get ``keep = False``, ``ignored`` lists their ids in order,
+    ``new_landmarks`` is empty -- and a frame left with nothing is an empty frame."""
     offsets = np.asarray(offsets)
     if offsets.ndim != 1 or offsets.shape[0] < 1 or (offsets.size > 1 and offsets.dtype.kind not in "iu"):
         raise ValueError("offsets must be a 1-D integer array of F+1 entries")
@@ -94,6 +97,13 @@ def plan_detection_log(landmarks, num_landmarks, ids, offsets, has_detections=No
         raise ValueError(f"frame {int(empty[0])} has detections but no ids: observe() needs at least one detection")
     keep = np.repeat(has, counts)
     counts = np.where(has, counts, 0)
+    ignored = ()
+    if frozen:
+        unknown = keep & ~np.fromiter((marker in landmarks for marker in ids.tolist()), dtype=bool, count=ids.shape[0])
+        ignored = tuple(ids[unknown].tolist())
+        keep = keep & ~unknown
+        kept = np.concatenate(([0], np.cumsum(keep))).astype(np.int64)
+        counts = kept[offsets[1:]] - kept[offsets[:-1]]
     new, n = {}, int(num_landmarks)
     index = np.empty(int(counts.sum()), dtype=np.int32)
     for k, marker in enumerate(ids[keep].tolist()):
@@ -105,7 +115,7 @@ def plan_detection_log(landmarks, num_landmarks, ids, offsets, has_detections=No
                 n += 1
         index[k] = j
     return DetectionLogPlan(index, np.concatenate(([0], np.cumsum(counts))).astype(np.int64), keep, new, n,
-                            int(counts.max()) if frames else 0)
+                            int(counts.max()) if frames else 0, ignored)
 
 
 class BaseFilter:
@@ -115,6 +125,7 @@ class BaseFilter:
     _tentative = None       # confirm=(hits, window): the TentativeLandmarks policy (_init_confirm)
     _pruned = False         # landmarks have been removed: with none left, `state` is still the device's
     _moved = False          # the camera has been moved (move, motion=): with no landmark yet, `state` is the device's
+    last_ignored = ()       # frozen map: the marker ids the last observe / log call dropped because the map does not hold them
 
     def __init__(self, initial_pose, map_file=None, aruco_dict=None) -> None:
         self.calib_matrix = None
@@ -227,7 +238,7 @@ class BaseFilter:
             self.observe(ids, detected_poses, **extra)
         elif should_filter:
             self.observe(ids, detected_poses)
-        if should_filter and self._tentative is not None:
+        if should_filter and self._tentative is not None and not self.map_frozen:      # (a frozen map is not pruned either)
             self._prune_tentative(ids)
         if should_filter:
             camera_pose, marker_poses = self.get_poses()
@@ -235,6 +246,52 @@ class BaseFilter:
             _, marker_poses = self.get_poses()
             camera_pose = self.get_cam_estimate(iteration)
         return None, camera_pose, marker_poses, detected_poses
+
+    # -- localisation mode: a frozen map (ekf_set_map_frozen) -------------------------------------
+    @property
+    def map_frozen(self) -> bool:
+        """Whether the map is frozen: frames localise the camera on the map as it is (Schmidt-Kalman update: the camera,
+        P_cc and the cross-covariances change, the landmarks and their covariance block keep their bits)."""
+        return bool(getattr(getattr(self, "backend", None), "map_frozen", False))
+
+    def freeze_map(self) -> None:
+        """Freeze the map from the next frame on: ``observe`` / ``process_detections`` / ``process_detection_log`` update
+        the camera only and drop detections of markers the map does not hold (``last_ignored``) instead of adding them.
+        P stays a valid joint covariance: ``unfreeze_map`` goes on mapping from it.  Explicit ``add_marker``,
+        ``remove_markers`` and ``load_checkpoint`` work as ever; ``reset`` unfreezes."""
+        self.backend.set_map_frozen(True)
+
+    def unfreeze_map(self) -> None:
+        """Back to mapping, from the state and the covariance the frozen frames left."""
+        self.backend.set_map_frozen(False)
+
+    def _observe_frozen(self, ids, poses, rows, scale, motion) -> None:
+        """``observe`` on a frozen map, arguments validated: detections of unknown ids are dropped (``last_ignored``, in
+        order), the rest is the frame.  A frame left with nothing is not stepped: it is still moved, and its scale goes
+        to the pending scale.  ``last_mahal`` / ``last_rejected`` stay indexed like ``ids`` (NaN / False for a dropped
+        detection)."""
+        known = self.landmarks
+        sel = np.fromiter((marker in known for marker in ids), dtype=bool, count=len(ids))
+        self.last_ignored = tuple(marker for marker, k in zip(ids, sel) if not k)
+        if motion is not None:
+            self._move(motion)
+        backend = self.backend
+        if backend.can_gate:
+            self.last_mahal, self.last_rejected = np.full(len(ids), np.nan), np.zeros(len(ids), dtype=bool)
+        if not sel.any():
+            if scale is not None:
+                backend.advance(scale)
+            return
+        index = [known[marker] for marker, k in zip(ids, sel) if k]
+        z = self._measurements(poses[sel])
+        rows = None if rows is None else rows[sel]
+        if not backend.can_gate:
+            backend.observe(index, z, rows=rows, scale=scale)
+            return
+        self._observe_gated(index, z, None, rows, scale)
+        d2, rejected = np.full(len(ids), np.nan), np.zeros(len(ids), dtype=bool)
+        d2[sel], rejected[sel] = self.last_mahal, self.last_rejected
+        self.last_mahal, self.last_rejected = d2, rejected
 
     # -- the per-detection chi-square gate (ekf_set_gate) ----------------------------------------
     @property
@@ -392,10 +449,12 @@ class BaseFilter:
         ``scale``: the frames' process-noise scales, [F], one per frame of the log (a filter built with
         ``frame_scale=True``): a frame that is not stepped leaves its scale pending for the next stepped one.
         ``motion``: the camera's motion before every frame, [F, 6], one row per frame of the log, empty frames included (a
-        filter built with ``motion=True``); such a replay runs its frames in serial order."""
+        filter built with ``motion=True``); such a replay runs its frames in serial order.
+        On a frozen map (``freeze_map``) detections of ids the map does not hold are dropped (``last_ignored``; their d2 is
+        NaN), nothing is added, and the replay runs its frames in serial order."""
         import torch
         backend = self.backend
-        plan = plan_detection_log(self.landmarks, self.num_landmarks, ids, offsets, has_detections)
+        plan = plan_detection_log(self.landmarks, self.num_landmarks, ids, offsets, has_detections, self.map_frozen)
         if isinstance(poses, torch.Tensor):
             if not poses.is_cuda or poses.device != backend.device:
                 raise ValueError(f"poses must be on {backend.device} (got {poses.device})")
@@ -432,6 +491,7 @@ class BaseFilter:
         backend.sync()
         if motion is not None and motion.any():
             self._moved = True
+        self.last_ignored = plan.ignored
         self.landmarks.update(plan.new_landmarks)
         self.num_landmarks = plan.num_landmarks
         if self._tentative is not None:      # (confirm=: the policy sees per-frame calls only; what a replay adds stays)
@@ -483,6 +543,7 @@ class BaseFilter:
         self.num_landmarks = 0
         self._pruned = False
         self._moved = False
+        self.last_ignored = ()      # (the back-end's reset has unfrozen the map)
         if self._tentative is not None:
             self._tentative.clear()
 
@@ -497,7 +558,7 @@ class BaseFilter:
                  marker_ids=np.asarray(ids, dtype=np.int64), filter=type(self).__name__,
                  gate=np.float64(np.inf if gate is None else gate), row_noise=np.bool_(self.backend.can_row_noise),
                  frame_scale=np.bool_(self.backend.can_frame_scale), pending_scale=np.float64(self.backend.pending_scale),
-                 motion=np.bool_(self.backend.can_motion))
+                 motion=np.bool_(self.backend.can_motion), map_frozen=np.bool_(self.backend.map_frozen))
 
     def load_checkpoint(self, filename: str) -> None:
         """Inverse of ``save_checkpoint`` on a filter of the same class; the device covariance
@@ -507,7 +568,7 @@ class BaseFilter:
         with ``gate=`` (``ValueError`` otherwise).  Checkpoints from before the gate leave it as it is.  A checkpoint of a
         filter built with ``row_noise=True`` needs one built the same way (``ValueError`` otherwise), and so does one of a
         filter built with ``frame_scale=True``, whose pending scale is restored; a checkpoint without it leaves the pending
-        scale 0."""
+        scale 0.  Whether the map was frozen is part of the checkpoint; one from before that loads as not frozen."""
         with np.load(filename, allow_pickle=False) as ck:
             if str(ck["filter"]) != type(self).__name__:
                 raise ValueError(f"checkpoint of {ck['filter']} loaded into {type(self).__name__}")
@@ -517,6 +578,7 @@ class BaseFilter:
             frame_scale = bool(ck["frame_scale"]) if "frame_scale" in ck.files else False
             pending = float(ck["pending_scale"]) if "pending_scale" in ck.files else 0.0
             motion = bool(ck["motion"]) if "motion" in ck.files else False
+            frozen = bool(ck["map_frozen"]) if "map_frozen" in ck.files else False      # (older checkpoints: not frozen)
         if motion and not self.backend.can_motion:
             raise ValueError("the checkpoint is of a filter with camera motions: build this one with motion=True")
         if frame_scale and not self.backend.can_frame_scale:
@@ -525,6 +587,7 @@ class BaseFilter:
             raise ValueError("the checkpoint is of a filter with per-detection noise: build this one with row_noise=True")
         if gate is not None and (np.isfinite(gate) or self.backend.can_gate):
             self.set_gate(gate)      # (a finite gate needs a filter built with gate=: ValueError otherwise)
+        self.backend.set_map_frozen(frozen)
         if len(ids) == 0:
             if self.backend.can_frame_scale:
                 self.backend.pending_scale = pending

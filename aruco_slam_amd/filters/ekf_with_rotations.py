@@ -110,6 +110,9 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         rows = self._frame_noise(noise, len(ids))
         scale = self._frame_scale(scale)
         motion = self._frame_motion(motion)
+        self.last_ignored = ()
+        if self.map_frozen:         # localisation: nothing is added, unknown ids are dropped
+            return self._observe_frozen(ids, poses, rows, scale, motion)
         if motion is not None:      # the camera moves first: first sightings are placed from the moved camera
             self._move(motion)
         known = self.landmarks
@@ -134,6 +137,10 @@ class EKF_Rotations(BaseFilter):  # noqa: N801  (name of the reference class)
         if self._hip.can_gate:
             return self._observe_gated(index, z, None, rows, scale)
         self._hip.observe(index, z, rows=rows, scale=scale)
+
+    def _measurements(self, poses) -> np.ndarray:
+        """z of the detections of a frame, [m, 7]: position and scalar-first quaternion in the camera frame (:216-224)."""
+        return np.hstack((poses[:, XYZ_DIMS], euler_xyz_to_quat(poses[:, 3:6])))
 
     # -- :275-335 --------------------------------------------------------------
     def add_marker(self, idx, pose, uncertainity=None) -> None:

@@ -37,7 +37,7 @@ class EKF(BaseFilter):
                  quat_update: str = "as_written", cov_kernel: str = "auto",
                  device: str = "cuda:0", map_file=None, lookahead: bool | None = None,
                  fused: bool = True, noise: dict | None = None, gate: float | None = None, confirm: tuple | None = None,
-                 row_noise: bool = False, frame_scale: bool = False, motion: bool = False) -> None:
+                 row_noise: bool = False, frame_scale: bool = False, motion: bool = False, localize: bool = False) -> None:
         """Positional arguments as the reference (:40-43).  Keyword-only extras:
         initial capacity (default: the number of ids of ``aruco_dict`` -- DICT_5X5_50
         has 50, base_filter.py:81-82; the buffers grow when more markers or more
@@ -56,7 +56,11 @@ class EKF(BaseFilter):
         ``frame_scale``: frames may carry a process-noise scale (``observe(..., scale=)``, ``advance``): time between
         frames, in units of a nominal frame period, multiplies Q, and time without an update is kept for the next one.
         ``motion``: frames may carry the camera's motion since the previous frame (``observe(..., motion=)``, ``move``):
-        odometry moves the prior instead of leaving the update to catch up with a camera the model holds still."""
+        odometry moves the prior instead of leaving the update to catch up with a camera the model holds still.
+        ``localize``: with ``map_file``, run in the map made earlier without changing it: the same as loading the map and
+        then calling ``freeze_map()`` (``ValueError`` without a ``map_file``)."""
+        if localize and map_file is None:
+            raise ValueError("localize=True needs a map_file: there is no map to localise in")
         super().__init__(initial_camera_pose, map_file, aruco_dict)
         self._initial_pose = np.array(initial_camera_pose)      # :46, dtype kept
         if self._initial_pose.shape != (CAM_DIMS,):
@@ -82,6 +86,8 @@ class EKF(BaseFilter):
         self._hip.reset(self._initial_pose.astype(np.float64))
         self._load_initial_map()
         self._init_confirm(confirm)
+        if localize:
+            self.freeze_map()
 
     # -- attributes the base class / callers read (base_filter.py:293-304) ---
     @property
@@ -116,6 +122,9 @@ class EKF(BaseFilter):
         rows = self._frame_noise(noise, len(ids))
         scale = self._frame_scale(scale)
         motion = self._frame_motion(motion)
+        self.last_ignored = ()
+        if self.map_frozen:         # localisation: nothing is added, unknown ids are dropped
+            return self._observe_frozen(ids, poses, rows, scale, motion)
         if motion is not None:      # the camera moves first: first sightings are placed from the moved camera
             self._move(motion)
         known = self.landmarks
@@ -139,6 +148,10 @@ class EKF(BaseFilter):
         if self._hip.can_gate:
             return self._observe_gated(index, poses[:, XYZ_DIMS], None, rows, scale)
         self._hip.observe(index, poses[:, XYZ_DIMS], rows=rows, scale=scale)
+
+    def _measurements(self, poses) -> np.ndarray:
+        """z of the detections of a frame, [m, 3]: the marker positions in the camera frame."""
+        return poses[:, XYZ_DIMS]
 
     # -- :239-290 --------------------------------------------------------------
     def add_marker(self, idx, pose, uncertainity=None) -> None:

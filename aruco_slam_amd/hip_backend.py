@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "ekf_batch_get_pending_scale", "ekf_batch_set_pending_scale",
     "ekf_move", "ekf_observe_moved", "ekf_observe_sequence_device_moved", "ekf_observe_log_moved",
     "ekf_batch_observe_logs_moved",
+    "ekf_set_map_frozen", "ekf_get_map_frozen",
 )
 
 
@@ -146,6 +147,8 @@ def load_library(path: str | Path | None = None):
         "ekf_observe_log_moved": [vp, ip, C.POINTER(C.c_int64), C.c_int32, vp, vp, dp, dp, vp, C.c_size_t, vp, vp],
         "ekf_batch_observe_logs_moved": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, vp, vp, vp, vp, C.c_size_t,
                                          vp, vp, vp, vp],
+        "ekf_set_map_frozen": [vp, C.c_int32],
+        "ekf_get_map_frozen": [vp],
         "ekf_remove_workspace_bytes": [vp, C.c_int32, C.POINTER(C.c_size_t)],
         "ekf_remove_markers": [vp, ip, C.c_int32, vp, C.c_int64, vp, vp, C.c_size_t],
         "ekf_batch_remove_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],
@@ -348,6 +351,7 @@ class HipEkf:
                                                   self.state_t.data_ptr(), self.ws_t.data_ptr(),
                                                   wb.value))
         self.cfg = cfg
+        self._map_frozen = False      # (off after ekf_create)
         self.gate = None       # None: built without the gate; inf: off
         if gate is not None:
             self.set_gate(gate)
@@ -367,6 +371,18 @@ class HipEkf:
     @property
     def can_motion(self) -> bool:
         return bool(self.cfg.flags & EKF_FLAG_MOTION)
+
+    @property
+    def map_frozen(self) -> bool:
+        """Whether the map is frozen (ekf_set_map_frozen): frames update the camera, P_cc and the cross-covariances and
+        leave the landmarks and P_ll alone.  The handle's flag as this object set it (``observe`` asks every frame)."""
+        return self._map_frozen
+
+    def set_map_frozen(self, frozen) -> None:
+        """Freeze (localisation on the map as it is: the Schmidt-Kalman update of the camera) or unfreeze the map from the
+        next frame on (ekf_set_map_frozen).  Persistent until ``reset``; nothing is enqueued."""
+        self._check(self.lib.ekf_set_map_frozen(self.h, int(bool(frozen))))
+        self._map_frozen = self.lib.ekf_get_map_frozen(self.h) == 1
 
     def _motion(self, motion, count: int | None = None):
         """``motion`` of a call as a contiguous [6] (``count`` None) or [count, 6] array (``motion_array``); a filter built
@@ -458,6 +474,7 @@ class HipEkf:
         p = np.ascontiguousarray(initial_pose, dtype=np.float64)
         assert p.shape == (10,)
         self._check(self.lib.ekf_reset(self.h, _dptr(p)))
+        self._map_frozen = False      # (ekf_reset clears the flag: a reset filter has no map)
 
     def grow(self, new_max_landmarks: int | None = None, new_max_visible: int | None = None):
         """Move the filter into buffers for a larger capacity (ekf_grow): new tensors sized by ekf_query_sizes, the library

@@ -21,6 +21,12 @@ and are not part of this package.
 ``--frame-period MS`` makes the predict step time-aware: every frame's process noise is scaled by the time since the
 previous frame in units of ``MS`` (a replay file's ``timestamps_ms``), and frames without an update leave their time
 pending for the next one, so a gated filter finds its way back after a detection dropout.
+
+    python -m aruco_slam_amd.main.run_slam --detections replay.npz --map outputs/map.txt --localize
+
+``--map FILE`` starts from a map written earlier (the reference's ``LOAD_MAP`` / ``MAP_FILE``), with or without
+``--resident``; ``--localize`` freezes it: the camera is tracked in the map as it is, markers the map does not hold are
+ignored, and the ``map.txt`` written at exit is the one that was loaded.
 """
 from __future__ import annotations
 
@@ -120,6 +126,9 @@ def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryW
 def main(cmdline_args: argparse.Namespace) -> None:
     initial_pose = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0])     # run_slam.py:85-88 (int64)
     kwargs = dict(getattr(cmdline_args, "filter_kwargs", {}))
+    map_file = getattr(cmdline_args, "map", None)
+    if getattr(cmdline_args, "localize", False) and map_file is None:
+        raise ValueError("--localize tracks the camera in an existing map: pass --map <map.txt>")
     if getattr(cmdline_args, "gate", None) is not None:
         kwargs["gate"] = cmdline_args.gate      # (acts in the frame loop and in the resident replay alike)
     if getattr(cmdline_args, "confirm", None) is not None:
@@ -139,6 +148,10 @@ def main(cmdline_args: argparse.Namespace) -> None:
     if motion is not None:
         kwargs["motion"] = True      # (the file carries odometry: frame loop and resident replay move the camera first)
     tracker = init_tracker(cmdline_args.filter, initial_pose, **kwargs)
+    if map_file is not None:
+        tracker.load_map(map_file)
+    if getattr(cmdline_args, "localize", False):
+        tracker.freeze_map()
     out_dir = Path(getattr(cmdline_args, "output_dir", "outputs"))
     out_dir.mkdir(parents=True, exist_ok=True)
 
@@ -204,6 +217,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--confirm", type=confirm_pair, default=None, metavar="H,W",
                         help="a new landmark must be used again in H later frames within W frames of its first sighting, "
                              "or it is removed from the map again (default: off)")
+    parser.add_argument("--map", type=str, default=None, metavar="FILE",
+                        help="start from a map written earlier (map.txt) instead of an empty one")
+    parser.add_argument("--localize", action="store_true",
+                        help="with --map: freeze the map and only track the camera in it; markers that are not in the map "
+                             "are ignored and the map is written back unchanged")
     return parser
 
 

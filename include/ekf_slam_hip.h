@@ -755,6 +755,44 @@ int ekf_batch_observe_logs_moved(ekf_batch *b, const int32_t *lm_index, const in
                                  const double *motion_dev /* [Ftot, 6] or NULL */, void *log_ws, size_t log_ws_bytes,
                                  double *trajectory_dev, double *nis_dev, double *cam_cov_dev, double *mahal_dev);
 
+/* ---- Localisation mode: a frozen map, Schmidt-Kalman ("consider") update of the camera (single filter).  A filter can build
+ * a map, restore one (ekf_set_state / ekf_set_cov, ekf_add_markers with the stored variances), prune it and gate against it;
+ * frozen, it uses the map without changing it.  The landmarks stay in the state and in S as uncertain quantities, but
+ * their gain rows are zero: the camera state, P_cc and the cross-covariances P_cl are updated, the landmark state and P_ll
+ * are not, and P stays a valid joint covariance, so the filter can be unfrozen and go on mapping.
+ * With W = L^-1 H (P+Q) the Schmidt update of the camera rows is the arithmetic the full update runs on rows 0 .. 9, and
+ * the rest of the full update is not done: a frozen frame writes about 2 * 10 * N elements of P instead of N^2.
+ * Semantics (part of the ABI).  A filter has a persistent boolean, "map frozen", off after ekf_create.  While it is on:
+ *   1. The frame sees exactly the prior a mapping frame sees: the motion first, then the gate on P+Q, then A = H (P+Q), S,
+ *      L, y, W with the frame's Q_eff, rows and scale.  Everything up to and including W and dx has the bits of the mapping
+ *      frame.
+ *   2. State.  Only the camera is injected: dx[0:3], the quaternion rule on dx[7:10] and state[7:10] = 0, as ever, in either
+ *      quaternion mode; EKF_MODEL_ROTATIONS: block 0 of the injection only.  state[10:] keeps its bits, and so does the
+ *      pinned host mirror of it.
+ *   3. Covariance.  For r < 10 and every c < N, P[r][c] and P[c][r] get the value the full update gives that element: the
+ *      same dtype, the same k-ascending fma chain from zero over kpad rows, v = P (+ Q on the diagonal) and then v + acc.  A
+ *      frame beyond 384 rows runs the same row chunks in the same order, Q with the first chunk only.  P[10:N, 10:N] is
+ *      neither predicted (no Q_lm is added) nor downdated: it keeps its bits.  The capacity padding stays exactly zero.  The
+ *      update is in place on the current buffer.  q_lm therefore acts as a per-frame inflation of the map's uncertainty
+ *      inside S and inside the gate that does not accumulate: every frozen frame sees P_ll + Q_lm, and none stores it.
+ *   4. A frozen filter adds nothing through observation: an entry point that would add landmarks as part of an observe
+ *      call -- ekf_observe_log* with first-sighting slots -- returns EKF_ERR_STATE before anything is enqueued.  Explicit
+ *      ekf_add_markers, ekf_remove_markers, ekf_set_state, ekf_set_cov and ekf_grow work as ever and keep the flag.
+ *      ekf_reset clears it: a reset filter has no map.
+ *   5. A frozen frame that is not stepped (empty, or nothing survived the gate) behaves as an unstepped frame does: it is
+ *      still moved, and its scale goes to the pending scale.  Gate, rows, scale and motion compose exactly as for mapping
+ *      frames: a gated frozen frame is bit for bit the ungated frozen frame on the survivors.
+ *   6. Run order.  Frozen sequence and log calls run frame by frame in serial order: ekf_last_sequence_mode reports
+ *      EKF_SEQ_SERIAL (1) and ekf_last_log_stats 0 pipelined frames, as for gated and moved calls.  A filter that is not
+ *      frozen runs the kernels and the pipelined mode it ran before, to the bit.
+ *   7. Unfreezing.  Mapping continues from the state and P the frozen frames left, bit for bit like a filter that
+ *      ekf_set_state / ekf_set_cov restore from those arrays.
+ * No config flag, no size and no layout change: the flag travels in the kernel arguments.
+ *   ekf_set_map_frozen: frozen != 0 freezes, 0 unfreezes, from the next frame on (a bound, reset filter).
+ *   ekf_get_map_frozen: 1 / 0, or EKF_ERR_INVALID for a NULL handle. */
+int ekf_set_map_frozen(ekf_filter *f, int32_t frozen);
+int ekf_get_map_frozen(const ekf_filter *f);
+
 const char *ekf_last_error_string(void);
 
 #ifdef __cplusplus

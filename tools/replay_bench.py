@@ -15,6 +15,10 @@ updates/s is steady frames per second of the steady segment; the bootstrap segme
     python tools/replay_bench.py --frame-scale     # every frame with its own process-noise scale (log-uniform in [0.5, 2])
     python tools/replay_bench.py --motion          # every frame with a small camera motion (N(0, 1e-3^2) per component): the
                                                    # price of the motion launch per frame and of losing the pipelined mode
+    python tools/replay_bench.py --frozen          # localisation: after the bootstrap the steady segment is replayed on a frozen
+                                                   # map (camera-strip update) and, on a second filter of the same build, as
+                                                   # mapping frames in serial order: us per frame of both, and the kernel's own
+                                                   # time from the covariance update's timing slot
 """
 from __future__ import annotations
 
@@ -37,10 +41,41 @@ def _segment(log, t0, t1):
     return log["ids"][d0:d1], log["poses"][d0:d1], offs[t0:t1 + 1] - d0, log["has_detections"][t0:t1]
 
 
-def _filter(args):
+def _filter(args, **kw):
     from aruco_slam_amd.filters.extended_kalman_filter import EKF
     return EKF(INIT, max_landmarks=args.n, max_visible=args.m[1], cov_dtype=args.dtype, gate=args.gate, row_noise=args.row_noise,
-               frame_scale=args.frame_scale, motion=args.motion)
+               frame_scale=args.frame_scale, motion=args.motion, **kw)
+
+
+def _frozen_vs_mapping(args, log, boot, frames, seg_noise, emit):
+    """--frozen: the steady segment as one log call on a frozen map and, on a second filter, as mapping frames in serial
+    order (lookahead=False: what a frozen call runs), each after the same bootstrap and one untimed pass over the first 50
+    frames; then 200 frames more with the kernel's own start / stop stamps (timing slot 3)."""
+    out = {}
+    for name, frozen in (("mapping_serial", False), ("frozen", True)):
+        flt = _filter(args, lookahead=False)
+        b = flt.backend
+        flt.process_detection_log(*_segment(log, 0, boot), **seg_noise(0, boot))
+        if frozen:
+            flt.freeze_map()
+        warm = min(frames, boot + 50)
+        flt.process_detection_log(*_segment(log, boot, warm), **seg_noise(boot, warm))
+        t = time.perf_counter()
+        flt.process_detection_log(*_segment(log, boot, frames), **seg_noise(boot, frames))
+        dt = time.perf_counter() - t
+        st = b.last_log_stats()
+        b.set_kernel_timing(2)
+        timed = min(frames, boot + 200)
+        flt.process_detection_log(*_segment(log, boot, timed), **seg_noise(boot, timed))
+        kern_us, launches = b.kernel_timing()["cov_update"]
+        b.set_kernel_timing(0)
+        out[name] = {"us_per_frame": 1e6 * dt / (frames - boot), "cov_slot_us": kern_us, "cov_slot_launches": launches,
+                     "frames_stepped": st["frames_stepped"], "frames_pipelined": st["frames_pipelined"],
+                     "ignored": len(flt.last_ignored)}
+        del flt, b
+    emit(variant="frozen", frozen_us_per_frame=out["frozen"]["us_per_frame"],
+         mapping_serial_us_per_frame=out["mapping_serial"]["us_per_frame"], strip_kernel_us=out["frozen"]["cov_slot_us"],
+         cov_update_kernel_us=out["mapping_serial"]["cov_slot_us"], detail=out)
 
 
 def main():
@@ -55,6 +90,8 @@ def main():
     ap.add_argument("--row-noise", action="store_true", help="per-detection measurement noise on every detection (noise=)")
     ap.add_argument("--frame-scale", action="store_true", help="a process-noise scale on every frame (scale=)")
     ap.add_argument("--motion", action="store_true", help="a camera motion on every frame (motion=)")
+    ap.add_argument("--frozen", action="store_true",
+                    help="replay the steady segment on a frozen map and as mapping frames in serial order, instead of the variants")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.synthetic import SyntheticStream, ragged_log
@@ -90,6 +127,9 @@ def main():
     def emit(**kv):
         print(json.dumps({**kv, **common}), flush=True)
 
+    if args.frozen:
+        _frozen_vs_mapping(args, log, boot, frames, seg_noise, emit)
+        return
     rates = {}
     for variant in args.variants.split(","):
         flt = _filter(args)

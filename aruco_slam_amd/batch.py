@@ -31,6 +31,12 @@ Outliers (IPPE's flipped poses, mis-decoded ids) are kept out by the per-detecti
 make every member reject the detections whose own Mahalanobis distance d^2 = r^T S_d^-1 r exceeds its threshold before the
 frame is updated, and ``mahal=True`` returns every detection's d^2, gate or no gate (``ekf_batch_set_gate`` in
 ``include/ekf_slam_hip.h`` has the exact semantics).
+
+Localisation studies run on a surveyed map that must not move: ``freeze_map`` / ``unfreeze_map`` / ``map_frozen`` give every
+member the single filter's localisation mode (``BaseFilter.freeze_map``; "Localisation mode of a batch" in
+``include/ekf_slam_hip.h``).  A frozen member updates its camera, P_cc and the cross-covariances and leaves its landmarks and
+P_ll alone; its frames cost the 10 x N camera strip of P instead of the N x N sweep.  Frozen and mapping members run side by
+side in one call.  Detections of ids a frozen member's map does not hold are dropped and reported in ``last_ignored``.
 """
 from __future__ import annotations
 
@@ -352,6 +358,10 @@ class EKFBatch:
     kept in ``self.motion``)."""
 
     gate = None        # [B] chi-square gate per member, or None: no gate (set_gate)
+    # per member, the marker ids the last process_detection_logs / replay_replicas / replay_corner_replicas call dropped
+    # because the member's map is frozen and does not hold them (a tuple per member, in log order; () for a mapping member)
+    last_ignored = ()
+    _frozen = None     # [B] bool mirror of the handle's "map frozen" flags as this object set them, or None: none is frozen
     camera = None      # (camera matrix [9], distortion coefficients, marker size) of corner logs, or None (set_camera)
 
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
@@ -432,6 +442,7 @@ class EKFBatch:
         self.landmarks = [{} for _ in range(self.members)]
         self.num_landmarks = [0] * self.members
         self.gate = None
+        self.last_ignored = [()] * self.members
         self.set_gate(gate)
         self.reset()
 
@@ -462,6 +473,39 @@ class EKFBatch:
         g = gate_array(gate, self.members)
         self._check(self.lib.ekf_batch_set_gate(self.h, _dptr(g) if g is not None else None))
         self.gate = g
+
+    # -- localisation mode ----------------------------------------------------------------------------------------------
+    @property
+    def map_frozen(self) -> np.ndarray:
+        """[B] bool: which members' maps are frozen (the handle's flags, ``ekf_batch_get_map_frozen``, as this object set
+        them: a copy)."""
+        return np.zeros(self.members, dtype=bool) if self._frozen is None else self._frozen.copy()
+
+    def _set_map_frozen(self, b, value: bool) -> None:
+        flags = self.map_frozen
+        if b is None:
+            flags[:] = value
+        else:
+            flags[self._member(b)] = value
+        self._check(self.lib.ekf_batch_set_map_frozen(self.h, _iptr(np.ascontiguousarray(flags, dtype=np.int32))))
+        out = np.zeros(self.members, dtype=np.int32)
+        self._check(self.lib.ekf_batch_get_map_frozen(self.h, _iptr(out)))
+        self._frozen = out != 0
+
+    def freeze_map(self, b=None) -> None:
+        """Freeze the map of member b (None: of every member) from the next call on: localisation on the map as it is, the
+        Schmidt-Kalman update of the camera (``BaseFilter.freeze_map``).  The member's frames update the camera state,
+        P[0:10, :] and P[:, 0:10] with the bits of its mapping frame and leave the landmarks and P[10:, 10:] alone.
+        Persistent until ``unfreeze_map`` or ``reset``; ``set_member``, ``remove_markers``, ``set_gate`` and
+        ``set_pending_scale`` keep it.  Detections of ids the map does not hold are dropped by the replay calls (reported in
+        ``last_ignored``); ``observe_indexed`` with an index beyond a frozen member's landmarks raises ``EkfError``
+        (EKF_ERR_STATE) and nothing changes."""
+        self._set_map_frozen(b, True)
+
+    def unfreeze_map(self, b=None) -> None:
+        """Member b (None: every member) maps again, from the state and P its frozen frames left: bit for bit the member
+        ``set_member`` restores from those arrays."""
+        self._set_map_frozen(b, False)
 
     def set_camera(self, camera_matrix, dist_coeffs=None, marker_size: float = 0.16) -> None:
         """The camera and marker size of logs that carry ``corners`` (``process_detection_logs``,
@@ -506,8 +550,14 @@ class EKFBatch:
         next stepped frame adds to its own.  Either every log of a call carries scales or none does.
         A log may carry ``motion`` ([F, 6], one row per frame, empty frames included; a batch built with ``motion=True``):
         the camera's motion ``(d, w)`` before every frame, in the camera frame of the previous pose.  A frame that is not
-        stepped is still moved.  Either every log of a call carries motions or none does."""
+        stepped is still moved.  Either every log of a call carries motions or none does.
+        A member whose map is frozen (``freeze_map``) drops the detections of ids its map does not hold, as a frozen filter's
+        ``process_detection_log`` does: a frame left with nothing is a frame that is not stepped, ``self.last_ignored[b]``
+        lists the dropped ids of member b in log order (() for a mapping member and after a call that raised), and ``mahal``
+        / ``rejected`` stay indexed like the log's own rows (NaN / False for a dropped one)."""
         gated = mahal or self.gate is not None
+        frozen = self.map_frozen
+        self.last_ignored = [()] * self.members
         if len(logs) != self.members:
             raise ValueError(f"need {self.members} logs (None for a member without one), got {len(logs)}")
         plans, index, offsets, frames, poses = [], [], [], [0], []
@@ -535,7 +585,7 @@ class EKFBatch:
                 frames.append(frames[-1])
                 continue
             plan = plan_detection_log(self.landmarks[b], self.num_landmarks[b], log["ids"], log["offsets"],
-                                      log.get("has_detections"))
+                                      log.get("has_detections"), frozen=bool(frozen[b]))
             if ("poses" in log) == ("corners" in log):
                 raise ValueError(f"member {b}: a log carries either poses [D,6] or corners [D,4,2]")
             if "corners" in log:
@@ -585,6 +635,7 @@ class EKFBatch:
         else:
             traj = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses, **with_rows)
         self._adopt_plans(plans)
+        self.last_ignored = [() if plan is None else tuple(plan.ignored) for plan in plans]
         split = [slice(frames[b], frames[b + 1]) for b in range(self.members)]
         if gated:
             member = np.repeat(np.arange(self.members), np.diff(offsets[np.asarray(frames)]))
@@ -653,7 +704,8 @@ class EKFBatch:
         detections counted) and, if asked, ``nis`` [B, F] and ``cam_cov`` [B, F, 10, 10] as in ``process_detection_logs``.
         Mean NIS over replicas against the chi^2(dof) bounds tunes the noise constants without ground truth; for
         EKF_Rotations the unit-quaternion rows make that chi^2 reading approximate.  Bad arguments raise before anything
-        runs, and no member changes.
+        runs, and no member changes.  Either every member's map is frozen or none is (``ValueError`` otherwise: the log is
+        planned once); with all of them frozen the log is planned as a frozen filter plans it (``last_ignored``).
         With ``mahal``, or with a gate set (``set_gate``), it returns a ``GatedReplicaReplay`` instead: ``dof`` [B, F] over
         each member's surviving detections, ``mahal`` [B, D] and ``rejected`` [B, D] aligned with the log's detections."""
         gated = mahal or self.gate is not None
@@ -686,6 +738,7 @@ class EKFBatch:
                                                                 ptr(cov_t)))
             self.stream.synchronize()
         self._adopt_plans([plan] * B)
+        self.last_ignored = [tuple(plan.ignored)] * B
         if gated:
             full, rej, dof = self._replica_gate_outputs(plan, fo, mahal_t.cpu().numpy())
             return GatedReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, dof,
@@ -699,8 +752,13 @@ class EKFBatch:
         array has another shape."""
         if any(t != self.landmarks[0] for t in self.landmarks[1:]) or len(set(self.num_landmarks)) > 1:
             raise ValueError(f"{what} needs every member's landmark table to be the same (reset() first)")
+        frozen = self.map_frozen
+        if frozen.any() != frozen.all():
+            raise ValueError(f"{what} plans its one log once: every member's map must be frozen, or none "
+                             "(freeze_map() / unfreeze_map() without a member)")
+        self.last_ignored = [()] * self.members
         plan = plan_detection_log(self.landmarks[0], self.num_landmarks[0], log["ids"], log["offsets"],
-                                  log.get("has_detections"))
+                                  log.get("has_detections"), frozen=bool(frozen.all()))
         v = np.asarray(log[key], dtype=np.float64)
         if v.shape != (plan.keep.shape[0],) + tail:
             raise ValueError(f"{key} must have shape {(plan.keep.shape[0],) + tail}, got {v.shape}")
@@ -763,6 +821,7 @@ class EKFBatch:
                 mahal_t.data_ptr() if gated and D else None, flip_t.data_ptr() if D else None))
             self.stream.synchronize()
         self._adopt_plans([plan] * B)
+        self.last_ignored = [tuple(plan.ignored)] * B
         keep = np.asarray(plan.keep, dtype=bool)
         flipped = np.zeros((B, keep.shape[0]), dtype=bool)
         flipped[:, keep] = flip_t.cpu().numpy().astype(bool)
@@ -994,7 +1053,8 @@ class EKFBatch:
         landmark table, with the batch's quaternion convention.  The member keeps its own noise constants (a sweep loads
         one filter into members that differ in nothing else) and takes the filter's gate, if the filter was built with one:
         a filter whose gate is ``inf`` switches that member's gate OFF, also where the member had a finite one (``set_gate``
-        afterwards to keep it); a filter built without ``gate=`` leaves the member's gate as it is."""
+        afterwards to keep it); a filter built without ``gate=`` leaves the member's gate as it is.  The member takes the
+        filter's ``map_frozen``."""
         cls = self._filter_class()
         if not isinstance(ekf, cls):
             raise ValueError(f"a batch of model {self.model!r} holds {cls.__name__} filters, got {type(ekf).__name__}")
@@ -1011,6 +1071,7 @@ class EKFBatch:
         self.set_member(b, np.asarray(ekf.state, dtype=np.float64), ekf.uncertainty, ids)
         if self.frame_scale:      # (set_member has zeroed it; a filter without the capability has 0)
             self.set_pending_scale(pending, b)
+        self._set_map_frozen(b, bool(ekf.map_frozen))      # (the member takes the filter's flag, on or off)
         if ekf.gate is not None and not (self.gate is None and np.isinf(ekf.gate)):
             gates = np.full(self.members, np.inf) if self.gate is None else self.gate.copy()
             gates[self._member(b)] = ekf.gate
@@ -1020,7 +1081,8 @@ class EKFBatch:
         """An ordinary filter of the batch's model (``EKF`` or ``EKF_Rotations``, f64 covariance) with member b's quaternion
         convention, noise constants, gate (a batch with a gate gives a filter built with ``gate=``), per-detection-noise
         capability (a batch built with ``row_noise=True`` gives a filter built the same way), per-frame-scale capability and
-        pending scale (likewise, ``frame_scale=True``), camera-motion capability (likewise, ``motion=True``), state, covariance and landmark table; ``observe`` (and for ``EKF`` ``save_map`` and ``save_checkpoint``) work on it."""
+        pending scale (likewise, ``frame_scale=True``), camera-motion capability (likewise, ``motion=True``), state, covariance,
+        landmark table and ``map_frozen`` (a frozen member gives a frozen filter); ``observe`` (and for ``EKF`` ``save_map`` and ``save_checkpoint``) work on it."""
         b = self._member(b)
         state, cov = self.get_state(b), self.get_cov(b)
         n = self.num_landmarks[b]
@@ -1042,10 +1104,12 @@ class EKFBatch:
             ekf.backend.pending_scale = pending
         ekf.landmarks = dict(self.landmarks[b])
         ekf.num_landmarks = n
+        if self.map_frozen[b]:
+            ekf.freeze_map()
         return ekf
 
     def reset(self, b=None) -> None:
-        """Member b (all members: None) back to its initial pose, no landmarks, status cleared."""
+        """Member b (all members: None) back to its initial pose, no landmarks, status cleared, map not frozen."""
         if b is None:
             self._check(self.lib.ekf_batch_reset(self.h, -1, _dptr(self._initial_poses)))
             members = range(self.members)
@@ -1053,6 +1117,11 @@ class EKFBatch:
             b = self._member(b)
             self._check(self.lib.ekf_batch_reset(self.h, b, _dptr(np.ascontiguousarray(self._initial_poses[b]))))
             members = (b,)
+        ignored = list(self.last_ignored) if len(self.last_ignored) == self.members else [()] * self.members
         for m in members:
             self.landmarks[m] = {}
             self.num_landmarks[m] = 0
+            ignored[m] = ()
+            if self._frozen is not None:      # (ekf_batch_reset has cleared the member's flag)
+                self._frozen[m] = False
+        self.last_ignored = ignored

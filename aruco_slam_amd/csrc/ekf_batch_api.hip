@@ -1,7 +1,8 @@
 // C ABI of the batch of independent filters (ekf_batch_*, see include/ekf_slam_hip.h; kernels: ekf_batch.hip (EKF) and
 // ekf_batch_rot.hip (EKF_Rotations), with EKF_FLAG_BATCH_LARGE_MAPS or EKF_FLAG_BATCH_WIDE_FRAMES ekf_batch_wide.hip
 // (both models); one workgroup per member; the noisy poses of replicas: ekf_batch_replicas.hip, or, from noisy corners,
-// ekf_batch_corner_replicas.hip).  Host side only: argument
+// ekf_batch_corner_replicas.hip; with a frozen member the FROZEN instances of ekf_batch_frozen.hip and
+// ekf_batch_wide_frozen.hip).  Host side only: argument
 // checking, workspace carving, launch sequencing.
 #include <cmath>
 #include <cstring>
@@ -24,6 +25,7 @@ struct ekf_batch {
     std::vector<int32_t> nlm;       // [B] host copy, refreshed after every call
     std::vector<int32_t> status;    // [B]
     std::vector<double> gate;       // [B] chi^2 gate per member (+inf: off); empty: no gate set (ekf_batch_set_gate)
+    std::vector<int32_t> frozen;    // [B] "map frozen" per member (ekf_batch_set_map_frozen); the device copy: BatchLayout::frozen
     PinnedBuffer pin;               // pinned staging of a call's indices and offsets
 };
 
@@ -45,18 +47,19 @@ bool batch_scaled(const ekf_config& c) { return (c.flags & EKF_FLAG_FRAME_SCALE)
 int64_t batch_w_stride(const ekf_config& c) { return (int64_t)batch_rd(c) * c.max_visible * batch_ld(c); }
 
 // workspace: [noise [B][6] | status [B] | landmark counts [B] | large maps or wide frames only: A / W [B][w_stride] |
-// EKF_FLAG_FRAME_SCALE only: pending scales [B]]
+// EKF_FLAG_FRAME_SCALE only: pending scales [B]]; the "map frozen" flags [B] lie directly behind the status words, in their
+// piece
 struct BatchLayout {
-    size_t status, nlm, w, total, pending;
+    size_t status, nlm, w, total, pending, frozen;
 };
 
 BatchLayout batch_layout(const ekf_config& c, int32_t members) {
     Carve w;
     w.take((size_t)members * 6 * 8);
-    const size_t status = w.take((size_t)members * 4), nlm = w.take((size_t)members * 4);
+    const size_t status = w.take((size_t)members * 8), nlm = w.take((size_t)members * 4);      // (status | frozen)
     const size_t wm = w.take(batch_large(c) || batch_wide(c) ? (size_t)members * batch_w_stride(c) * 8 : 0);
     const size_t pending = w.take(batch_scaled(c) ? (size_t)members * 8 : 0);
-    return {status, nlm, wm, w.end, pending};
+    return {status, nlm, wm, w.end, pending, status + (size_t)members * 4};
 }
 
 // zero the pending scale of members [lo, hi) (the stream is idle); nothing without EKF_FLAG_FRAME_SCALE
@@ -80,6 +83,28 @@ BatchLogLayout batch_log_layout(int64_t D, int64_t F, int32_t B, bool gated) {
 }
 
 bool batch_gated(const ekf_batch* b) { return !b->gate.empty(); }
+
+bool batch_any_frozen(const ekf_batch* b) {
+    for (int32_t f : b->frozen)
+        if (f) return true;
+    return false;
+}
+
+// host copies of the "map frozen" flags of members [lo, hi) -> device (the stream is idle)
+int batch_put_frozen(ekf_batch* b, int32_t lo, int32_t hi) {
+    const BatchLayout L = batch_layout(b->cfg, b->members);
+    HIP_TRY(hipMemcpy(b->ws + L.frozen + 4 * (size_t)lo, b->frozen.data() + lo, (size_t)(hi - lo) * 4, hipMemcpyHostToDevice));
+    return EKF_OK;
+}
+
+// A frozen member adds nothing through observation (include/ekf_slam_hip.h, "Localisation mode"): an index at or beyond its
+// landmark count is refused, before check_log would read it as a first sighting.
+int check_frozen_log(const int32_t* lm_index, const int64_t* offsets, int64_t frames, int n_lm, const std::string& log) {
+    for (int64_t d = offsets[0]; d < offsets[frames]; ++d)
+        if (lm_index[d] >= n_lm)
+            return fail(EKF_ERR_STATE, log + " holds a first sighting, and the member's map is frozen");
+    return EKF_OK;
+}
 
 int check_batch_config(const ekf_config* c, int32_t members) {
     if (!c) return fail(EKF_ERR_INVALID, "config is NULL");
@@ -212,6 +237,8 @@ int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, co
     a.pending = batch_scaled(b->cfg) ? reinterpret_cast<double*>(b->ws + L.pending) : nullptr;
     a.scale = scale_dev;         // (per-frame scales: data of the call; checked by the caller: the flag is set)
     a.motion = motion_dev;       // (per-frame camera motions: data of the call, likewise)
+    // (no member frozen: null, and every launcher runs the instance it ran before the flag existed)
+    a.frozen = batch_any_frozen(b) ? reinterpret_cast<const int32_t*>(b->ws + L.frozen) : nullptr;
     const int rd = batch_rd(b->cfg);
     a.kmax = std::max(rd, rd * sh.widest);
     a.lda = (int32_t)round_up(batch_lmd(b->cfg) * sh.n_max + EKF_CAM + 1, 4);
@@ -275,10 +302,12 @@ int batch_observe_replicas(ekf_batch* b, const int32_t* lm_index, const int64_t*
     BatchShape sh;
     LogCheck lc;
     for (int32_t m = 0; m < B; ++m) {
-        if (m > 0 && b->nlm[m] == b->nlm[m - 1]) {      // (the same log on the same landmark count: the same verdict)
+        if (m > 0 && b->nlm[m] == b->nlm[m - 1] && b->frozen[m] == b->frozen[m - 1]) {      // (the same log on the same landmark count and flag: the same verdict)
             sh.add(lc, frames);
             continue;
         }
+        if (b->frozen[m] && (rc = check_frozen_log(lm_index, frame_offsets, frames, b->nlm[m], "the log (member " + std::to_string(m) + ")")))
+            return rc;
         rc = check_log(lm_index, frame_offsets, frames, b->nlm[m], b->cfg, "the log (member " + std::to_string(m) + ")", &lc);
         if (rc) return rc;
         sh.add(lc, frames);
@@ -348,6 +377,7 @@ int ekf_batch_create(const ekf_config* cfg, int32_t members, ekf_batch** out) {
         for (int i = 0; i < 6; ++i) b->noise[(size_t)m * 6 + i] = nz[i];
     b->nlm.assign(members, 0);
     b->status.assign(members, 0);
+    b->frozen.assign(members, 0);
     *out = b;
     return EKF_OK;
 }
@@ -426,13 +456,31 @@ int ekf_batch_reset(ekf_batch* b, int32_t member, const double* initial_poses) {
         for (int i = 0; i < EKF_CAM; ++i) diag[(size_t)(m - lo) * EKF_CAM + i] = b->noise[(size_t)m * 6];
         b->nlm[m] = 0;
         b->status[m] = 0;
+        b->frozen[m] = 0;      // (a reset member maps again)
     }
     // P = icu I_10: the diagonal of every member's matrix is a strided run of ld + 1 elements
     for (int32_t m = lo; m < hi; ++m)
         HIP_TRY(hipMemcpy2D(b->cov + (size_t)m * ld * ld, (size_t)(ld + 1) * 8, diag.data() + (size_t)(m - lo) * EKF_CAM, 8, 8,
                             EKF_CAM, hipMemcpyHostToDevice));
     if ((rc = batch_zero_pending(b, lo, hi))) return rc;
+    if ((rc = batch_put_frozen(b, lo, hi))) return rc;
     return batch_put_member_words(b, lo, hi);
+}
+
+// frozen [B] on the host (non-zero: frozen), or NULL: no member.  Persistent; nothing changes on error.  Waits for the stream.
+int ekf_batch_set_map_frozen(ekf_batch* b, const int32_t* frozen) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (int32_t m = 0; m < b->members; ++m) b->frozen[m] = frozen && frozen[m] ? 1 : 0;
+    return batch_put_frozen(b, 0, b->members);
+}
+
+int ekf_batch_get_map_frozen(const ekf_batch* b, int32_t* out) {
+    if (!b) return fail(EKF_ERR_INVALID, "batch handle is NULL");
+    if (!out) return fail(EKF_ERR_INVALID, "out is NULL");
+    std::memcpy(out, b->frozen.data(), b->frozen.size() * 4);
+    return EKF_OK;
 }
 
 // (state [lmd n + 10], P [lmd n + 10, lmd n + 10]) of one member (lmd = 3: EKF, 10: EKF_Rotations) from the host; P is symmetrised ((P + P^T) / 2) on upload.
@@ -560,6 +608,8 @@ int ekf_batch_observe_logs_moved(ekf_batch* b, const int32_t* lm_index, const in
     LogCheck lc;
     for (int32_t m = 0; m < B; ++m) {
         const int64_t f0 = member_frames[m], frames = member_frames[m + 1] - f0;
+        if (b->frozen[m] && (rc = check_frozen_log(lm_index, frame_offsets + f0, frames, b->nlm[m], "member " + std::to_string(m) + "'s log")))
+            return rc;
         rc = check_log(lm_index, frame_offsets + f0, frames, b->nlm[m], b->cfg, "member " + std::to_string(m) + "'s log", &lc);
         if (rc) return rc;
         sh.add(lc, frames);

@@ -214,7 +214,47 @@ __device__ __forceinline__ void ekf_batch_motion(const double* __restrict__ u, d
 void ekf_launch_batch_moved_window(int model, const EkfBatchWindow& a, int members, hipStream_t s);            // ekf_batch_moved.hip
 void ekf_launch_batch_moved_wide_window(int model, bool one_block, const EkfBatchLargeWindow& g, int members,
                                         hipStream_t s);                                                      // ekf_batch_wide_moved.hip
-template <int MODEL, bool MOVED = false> __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
+// FROZEN: the instance a batch with at least one frozen member runs (a.frozen != null; include/ekf_slam_hip.h, "Localisation
+// mode").  The member's flag is a workgroup-uniform run-time branch: a frozen member forms dx[0:10] only, injects the camera
+// only and updates the camera strip of P (ekf_batch_strip below); a member that is not frozen runs the statements of the
+// instance without the branch, so it has that instance's bits.  Instances of their own for the reason MOVED has them, with
+// and without the motion stage.
+void ekf_launch_batch_frozen_window(int model, const EkfBatchWindow& a, int members, hipStream_t s);           // ekf_batch_frozen.hip
+void ekf_launch_batch_frozen_wide_window(int model, bool one_block, const EkfBatchLargeWindow& g, int members,
+                                         hipStream_t s);                                                     // ekf_batch_wide_frozen.hip
+
+// The camera strip of P <- (P+Q) - W^T W for a frozen member of the one-column kernel, W [k][lda] in LDS: thread c owns
+// column c and keeps the ten entries P[0:10][c] in registers; entry (i, c) runs the l-ascending chain fma(W[l][i], W[l][c],
+// acc) from zero and is stored as (P[i][c] + q(i == c)) - acc, the operations the full sweep runs on that entry (and, with
+// the factors swapped, on its mirror).  Column c >= 10 also stores the mirror P[c][0:10] (80 contiguous bytes per thread);
+// the 10 x 10 block is written by the row stores of threads 0 .. 9 alone, so no address has two writers.  W[l][0:10] is one
+// address for the whole wave (LDS broadcast); P[10:N, 10:N] is neither read nor written.
+__device__ __forceinline__ void ekf_batch_strip(double* P, int64_t ld, const double* W, int lda, int k, int N,
+                                                const EkfNoise& nz, int tid, int nt) {
+    for (int c = tid; c < N; c += nt) {
+        double pv[EKF_CAM], acc[EKF_CAM];
+#pragma unroll
+        for (int i = 0; i < EKF_CAM; ++i) {
+            pv[i] = P[(int64_t)i * ld + c];
+            acc[i] = 0.0;
+        }
+        for (int l = 0; l < k; ++l) {
+            const double* Wl = W + l * lda;
+            const double w = Wl[c];
+#pragma unroll
+            for (int i = 0; i < EKF_CAM; ++i) acc[i] = fma(Wl[i], w, acc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < EKF_CAM; ++i) {
+            const double v = (pv[i] + (i == c ? ekf_qdiag(c, N, nz) : 0.0)) - acc[i];
+            P[(int64_t)i * ld + c] = v;
+            if (c >= EKF_CAM) P[(int64_t)c * ld + i] = v;
+        }
+    }
+}
+
+template <int MODEL, bool MOVED = false, bool FROZEN = false>
+__device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -243,6 +283,9 @@ template <int MODEL, bool MOVED = false> __device__ __forceinline__ void ekf_bat
     int n = a.nlm[b];
     bool failed = a.status[b] != 0;
     const bool gated = a.mahal || (a.gate && a.gate[b] < __builtin_inf());
+    // a frozen member (the host admits no first sighting in its log): camera-only injection, camera strip of P
+    bool frozen = false;
+    if constexpr (FROZEN) frozen = a.frozen[b] != 0;
     if (tid == 0) *flag = 0;
 
     for (int64_t t = t0; t < t1; ++t) {
@@ -384,8 +427,9 @@ template <int MODEL, bool MOVED = false> __device__ __forceinline__ void ekf_bat
             }
         }
         __syncthreads();
-        // dx = W^T y
-        for (int c = tid; c < N; c += nt) {
+        // dx = W^T y (a frozen member: the camera's ten entries, all that is injected)
+        const int nx = frozen ? EKF_CAM : N;
+        for (int c = tid; c < nx; c += nt) {
             double acc = 0.0;
             for (int i = 0; i < k; ++i) acc = fma(A[i * lda + c], A[i * lda + N], acc);
             dx[c] = acc;
@@ -400,11 +444,11 @@ template <int MODEL, bool MOVED = false> __device__ __forceinline__ void ekf_bat
                 for (int r = 0; r < 4; ++r) st[3 + r] = q[r];
                 for (int r = 7; r < 10; ++r) st[r] = 0.0;
             }
-            for (int c = tid; c < N; c += nt)
+            for (int c = tid; c < nx; c += nt)
                 if (c < 3 || c >= EKF_CAM) st[c] += dx[c];
         } else {
             // injection (ekf_with_rotations.py:146-177): thread 0 the camera block, thread i landmark i - 1 (n <= 24 < nt)
-            if (tid <= n) {
+            if (tid <= (frozen ? 0 : n)) {
                 const int c0 = tid == 0 ? 0 : EKF_CAM + LMD * (tid - 1);
                 ekf_inject_rot_block(st + c0, dx + c0, tid == 0);
             }
@@ -413,7 +457,9 @@ template <int MODEL, bool MOVED = false> __device__ __forceinline__ void ekf_bat
         // factors of each fma swap places, which does not change its result), so P stays bitwise symmetric.  The next row
         // block of the column is loaded before the fma chain of this one: its loads overlap the chain instead of each
         // block's read-modify-write of P waiting for its own load
-        for (int c = tid; c < N; c += nt) {
+        // (a frozen member: the camera strip instead, and no column of the full sweep)
+        if (frozen) ekf_batch_strip(P, ld, A, lda, k, N, nz, tid, nt);
+        for (int c = tid; c < (frozen ? 0 : N); c += nt) {
             double pv[4], pn[4];
             for (int u = 0; u < 4; ++u) pv[u] = u < N ? P[(int64_t)u * ld + c] : 0.0;
             for (int i0 = 0; i0 < N; i0 += 4) {

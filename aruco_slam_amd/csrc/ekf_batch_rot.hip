@@ -9,6 +9,7 @@ extern "C" size_t ekf_batch_rot_lds_bytes(int kmax, int lda) { return ekf_batch_
 __global__ __launch_bounds__(256) void ekf_batch_rot_window_kernel(EkfBatchWindow a) { ekf_batch_window<1>(a); }
 
 void ekf_launch_batch_rot_window(const EkfBatchWindow& a, int members, hipStream_t s) {
+    if (a.frozen) return ekf_launch_batch_frozen_window(1, a, members, s);    // (ekf_batch_frozen.hip)
     if (a.motion) return ekf_launch_batch_moved_window(1, a, members, s);      // (ekf_batch_moved.hip)
     static bool once = false;
     ekf_batch_launch<1>(ekf_batch_rot_window_kernel, once, a, members, s);

@@ -68,7 +68,14 @@ typedef double ekf_d2 __attribute__((ext_vector_type(2)));
 // so the loops over blocks run once, with j0 = 0, and the loop over earlier blocks is gone: the same operations on the same
 // data, with less control around them (the large-map shapes run 3 to 4 % faster than in the general instance)
 // MOVED: the instance with the motion stage (ekf_batch_impl.h: why it is an instance of its own)
-template <int MODEL, bool ONE_BLOCK, bool MOVED = false>
+// FROZEN: the instance of a batch with frozen members (ekf_batch_impl.h; ekf_batch_wide_frozen.hip).  A frozen member forms
+// dx[0:10] only, injects the camera only, and in place of every block's sweep of P runs one strip pass over W_j, in the block
+// order of the sweep and with Q in the first pass: the ten camera columns of W_j (rows padded with zeros to kbp, as the
+// sweep's panel is) are staged into R as [kbp][10], thread t owns column c = c0 + t, keeps W_j[:, c] in registers (read
+// coalesced along c) and P[0:10][c] with them, runs the sweep's chain fma(W_j[l][i], W_j[l][c], acc) per entry against the
+// staged rows (one LDS address per wave: broadcast), and stores the column entries and, for c >= 10, the mirror
+// P[c][0:10].  P[0:10][c] is read and written by its own thread in every pass; the mirror entries are only written.
+template <int MODEL, bool ONE_BLOCK, bool MOVED = false, bool FROZEN = false>
 __device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow& g) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     constexpr int MB = wide_mb<MODEL>(), KW = wide_kw<MODEL>();
@@ -101,6 +108,8 @@ __device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow&
     int n = a.nlm[b];
     bool failed = a.status[b] != 0;
     const bool gated = a.mahal || (a.gate && a.gate[b] < __builtin_inf());
+    bool frozen = false;
+    if constexpr (FROZEN) frozen = a.frozen[b] != 0;
     if (tid == 0) *flag = 0;
 
     for (int64_t t = t0; t < t1; ++t) {
@@ -284,9 +293,10 @@ __device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow&
             continue;
         }
         __syncthreads();
-        // dx = W^T y over all k rows (into R: every thread's slice is done)
+        // dx = W^T y over all k rows (into R: every thread's slice is done); a frozen member: the camera's ten entries
         double* dx = R;
-        for (int c = tid; c < N; c += nt) {
+        const int nx = frozen ? EKF_CAM : N;
+        for (int c = tid; c < nx; c += nt) {
             double acc = 0.0;
             for (int i = 0; i < k; ++i) acc = fma(A[(int64_t)i * ld + c], y[i], acc);
             dx[c] = acc;
@@ -301,11 +311,11 @@ __device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow&
                 for (int r = 0; r < 4; ++r) st[3 + r] = q[r];
                 for (int r = 7; r < 10; ++r) st[r] = 0.0;
             }
-            for (int c = tid; c < N; c += nt)
+            for (int c = tid; c < nx; c += nt)
                 if (c < 3 || c >= EKF_CAM) st[c] += dx[c];
         } else {
             // injection (ekf_with_rotations.py:146-177): thread 0 the camera block, thread i landmark i - 1 (n <= 101 < nt)
-            if (tid <= n) {
+            if (tid <= (frozen ? 0 : n)) {
                 const int c0 = tid == 0 ? 0 : EKF_CAM + LMD * (tid - 1);
                 ekf_inject_rot_block(st + c0, dx + c0, tid == 0);
             }
@@ -313,8 +323,54 @@ __device__ __forceinline__ void ekf_batch_wide_window(const EkfBatchLargeWindow&
         // P <- (P+Q) - W^T W, one sweep per block of rows W_j (Q with the first).  Rows l in [kb, kbp) of the panel and of
         // w are zero: fma(0, 0, acc) = acc (acc is never -0), so padding the chain to a multiple of 4 leaves every
         // entry's bits as they are.
+        // A frozen member: the strip passes instead (FROZEN above), and no block of the full sweep.
+        if (frozen) {
+            double* WC = R;      // [kbp][10]: the camera columns of W_j
+            for (int j0 = 0; j0 < blocks_end; j0 += MB) {
+                const int kb = ONE_BLOCK ? k : RD * min(MB, m - j0), kbp = (kb + 3) & ~3;
+                const double* Wj = A + (int64_t)RD * j0 * ld;
+                __syncthreads();      // (dx, or the previous block's camera columns, are no longer read)
+                for (int e = tid; e < kbp * EKF_CAM; e += nt) {
+                    const int l = e / EKF_CAM, i = e - l * EKF_CAM;
+                    WC[e] = l < kb ? Wj[(int64_t)l * ld + i] : 0.0;
+                }
+                __syncthreads();
+                for (int c = tid; c < N; c += nt) {
+                    const double qc = ekf_qdiag(c, N, nz);
+                    double w[KW], p[EKF_CAM], acc[EKF_CAM];
+#pragma unroll
+                    for (int l = 0; l < KW; ++l) {
+                        const double v = Wj[(int64_t)min(l, kb - 1) * ld + c];
+                        w[l] = l < kb ? v : 0.0;
+                    }
+#pragma unroll
+                    for (int i = 0; i < EKF_CAM; ++i) {
+                        p[i] = P[(int64_t)i * ld + c];
+                        acc[i] = 0.0;
+                    }
+#pragma unroll
+                    for (int l0 = 0; l0 < KW; l0 += 4) {
+                        if (l0 < kbp) {
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const double* Wr = WC + (l0 + u) * EKF_CAM;
+#pragma unroll
+                                for (int i = 0; i < EKF_CAM; ++i) acc[i] = fma(Wr[i], w[l0 + u], acc[i]);
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < EKF_CAM; ++i) {
+                        const double pq = j0 == 0 ? p[i] + (i == c ? qc : 0.0) : p[i];
+                        const double v = pq - acc[i];
+                        P[(int64_t)i * ld + c] = v;
+                        if (c >= EKF_CAM) P[(int64_t)c * ld + i] = v;
+                    }
+                }
+            }
+        }
         double* WT = R;      // [256 rows of the panel][kbp]
-        for (int j0 = 0; j0 < blocks_end; j0 += MB) {
+        for (int j0 = 0; j0 < (frozen ? 0 : blocks_end); j0 += MB) {
             const int kb = ONE_BLOCK ? k : RD * min(MB, m - j0), kbp = (kb + 3) & ~3;
             const double* Wj = A + (int64_t)RD * j0 * ld;
             for (int cb = 0; cb < N; cb += nt) {
@@ -401,7 +457,37 @@ void wide_launch(void (*kernel)(EkfBatchLargeWindow), bool& once, const EkfBatch
 
 }  // namespace
 
-#ifndef EKF_BATCH_WIDE_MOVED
+#if defined(EKF_BATCH_WIDE_FROZEN)      // ekf_batch_wide_frozen.hip: the instances of a batch with frozen members
+#define EKF_WIDE_FROZEN_KERNEL(name, model, one_block, moved)                                   \
+    __global__ __launch_bounds__(256) void name(EkfBatchLargeWindow g) {                        \
+        ekf_batch_wide_window<model, one_block, moved, true>(g);                                \
+    }
+EKF_WIDE_FROZEN_KERNEL(ekf_batch_frozen_wide_window_kernel, 0, false, false)
+EKF_WIDE_FROZEN_KERNEL(ekf_batch_frozen_wide_rot_window_kernel, 1, false, false)
+EKF_WIDE_FROZEN_KERNEL(ekf_batch_frozen_one_block_window_kernel, 0, true, false)
+EKF_WIDE_FROZEN_KERNEL(ekf_batch_frozen_one_block_rot_window_kernel, 1, true, false)
+EKF_WIDE_FROZEN_KERNEL(ekf_batch_frozen_moved_wide_window_kernel, 0, false, true)
+EKF_WIDE_FROZEN_KERNEL(ekf_batch_frozen_moved_wide_rot_window_kernel, 1, false, true)
+EKF_WIDE_FROZEN_KERNEL(ekf_batch_frozen_moved_one_block_window_kernel, 0, true, true)
+EKF_WIDE_FROZEN_KERNEL(ekf_batch_frozen_moved_one_block_rot_window_kernel, 1, true, true)
+#undef EKF_WIDE_FROZEN_KERNEL
+
+void ekf_launch_batch_frozen_wide_window(int model, bool one_block, const EkfBatchLargeWindow& g, int members,
+                                         hipStream_t s) {
+    static bool once[2][2][2] = {};
+    // [model][one_block][moved]
+    static void (*const kernels[2][2][2])(EkfBatchLargeWindow) = {
+        {{ekf_batch_frozen_wide_window_kernel, ekf_batch_frozen_moved_wide_window_kernel},
+         {ekf_batch_frozen_one_block_window_kernel, ekf_batch_frozen_moved_one_block_window_kernel}},
+        {{ekf_batch_frozen_wide_rot_window_kernel, ekf_batch_frozen_moved_wide_rot_window_kernel},
+         {ekf_batch_frozen_one_block_rot_window_kernel, ekf_batch_frozen_moved_one_block_rot_window_kernel}}};
+    const int mi = model == 1 ? 1 : 0, moved = g.w.motion != nullptr;
+    if (mi == 1)
+        wide_launch<1>(kernels[1][one_block][moved], once[1][one_block][moved], g, members, s);
+    else
+        wide_launch<0>(kernels[0][one_block][moved], once[0][one_block][moved], g, members, s);
+}
+#elif !defined(EKF_BATCH_WIDE_MOVED)
 extern "C" size_t ekf_batch_wide_lds_bytes(int model, int kmax) {
     return model == 1 ? wide_lds_bytes_of<1>(kmax) : wide_lds_bytes_of<0>(kmax);
 }
@@ -420,6 +506,7 @@ __global__ __launch_bounds__(256) void ekf_batch_one_block_rot_window_kernel(Ekf
 }
 
 void ekf_launch_batch_wide_window(int model, bool one_block, const EkfBatchLargeWindow& g, int members, hipStream_t s) {
+    if (g.w.frozen) return ekf_launch_batch_frozen_wide_window(model, one_block, g, members, s);     // (ekf_batch_wide_frozen.hip)
     if (g.w.motion) return ekf_launch_batch_moved_wide_window(model, one_block, g, members, s);      // (ekf_batch_wide_moved.hip)
     static bool once[2][2] = {{false, false}, {false, false}};
     if (model == 1)

@@ -335,6 +335,11 @@ struct EkfBatchWindow {
     // Camera motion per frame (EKF_FLAG_MOTION; include/ekf_slam_hip.h, "Odometry input"): motion [Ftot][6], every frame's
     // (d, w), indexed like frame_offsets; null: no motion stage (a batch without the flag, or a call without motions)
     const double* motion;
+    // Frozen maps (include/ekf_slam_hip.h, "Localisation mode"; ekf_batch_set_map_frozen): frozen [B], non-zero = that
+    // member's frames update the camera strip of P and inject the camera only; null: no member of the batch is frozen, and
+    // the launchers run the instances without the branch (the FROZEN instances live in ekf_batch_frozen.hip and
+    // ekf_batch_wide_frozen.hip)
+    const int32_t* frozen;
 };
 // dynamic LDS of one launch (C linkage: the tests read them)
 extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);

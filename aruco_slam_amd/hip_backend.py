@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "ekf_move", "ekf_observe_moved", "ekf_observe_sequence_device_moved", "ekf_observe_log_moved",
     "ekf_batch_observe_logs_moved",
     "ekf_set_map_frozen", "ekf_get_map_frozen",
+    "ekf_batch_set_map_frozen", "ekf_batch_get_map_frozen",
 )
 
 
@@ -149,6 +150,8 @@ def load_library(path: str | Path | None = None):
                                          vp, vp, vp, vp],
         "ekf_set_map_frozen": [vp, C.c_int32],
         "ekf_get_map_frozen": [vp],
+        "ekf_batch_set_map_frozen": [vp, ip],
+        "ekf_batch_get_map_frozen": [vp, ip],
         "ekf_remove_workspace_bytes": [vp, C.c_int32, C.POINTER(C.c_size_t)],
         "ekf_remove_markers": [vp, ip, C.c_int32, vp, C.c_int64, vp, vp, C.c_size_t],
         "ekf_batch_remove_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],

@@ -755,7 +755,8 @@ int ekf_batch_observe_logs_moved(ekf_batch *b, const int32_t *lm_index, const in
                                  const double *motion_dev /* [Ftot, 6] or NULL */, void *log_ws, size_t log_ws_bytes,
                                  double *trajectory_dev, double *nis_dev, double *cam_cov_dev, double *mahal_dev);
 
-/* ---- Localisation mode: a frozen map, Schmidt-Kalman ("consider") update of the camera (single filter).  A filter can build
+/* ---- Localisation mode: a frozen map, Schmidt-Kalman ("consider") update of the camera (the single filter here; the members
+ * of a batch: "Localisation mode of a batch" below).  A filter can build
  * a map, restore one (ekf_set_state / ekf_set_cov, ekf_add_markers with the stored variances), prune it and gate against it;
  * frozen, it uses the map without changing it.  The landmarks stay in the state and in S as uncertain quantities, but
  * their gain rows are zero: the camera state, P_cc and the cross-covariances P_cl are updated, the landmark state and P_ll
@@ -792,6 +793,36 @@ int ekf_batch_observe_logs_moved(ekf_batch *b, const int32_t *lm_index, const in
  *   ekf_get_map_frozen: 1 / 0, or EKF_ERR_INVALID for a NULL handle. */
 int ekf_set_map_frozen(ekf_filter *f, int32_t frozen);
 int ekf_get_map_frozen(const ekf_filter *f);
+
+/* ---- Localisation mode of a batch: per-member frozen maps.  Every member of an ekf_batch has its own persistent boolean
+ * "map frozen": off after ekf_batch_create; ekf_batch_reset clears it for the members it resets; ekf_batch_set_member,
+ * ekf_batch_remove_markers, ekf_batch_set_gate, ekf_batch_set_noise and ekf_batch_set_pending_scale keep it.  No config flag.
+ * A frozen member's frame follows rules 1, 2, 3 and 5 above with the batch's arithmetic:
+ *   - the motion, the first-sighting check, the gate on P+Q, A, S, L, y, W, dx[0:10] and the per-frame outputs (trajectory
+ *     row, NIS, dof, cam_cov, mahal) have the bits of the member's mapping frame from the same prior;
+ *   - only the camera is injected (EKF: dx[0:3], the quaternion rule, state[7:10] = 0; EKF_MODEL_ROTATIONS: block 0);
+ *   - for r < 10 and every c < N, P[r][c] and P[c][r] get the value the member's mapping frame gives that element (the same
+ *     l-ascending fma chain from zero, then (P + Q on the diagonal) - acc; in the HBM-resident kernel one pass per block of
+ *     detections in block order, Q in the first pass); state[10:] and P[10:N, 10:N] keep their bits, the padding stays
+ *     zero and P stays bitwise symmetric;
+ *   - a frame that is not stepped is still moved and leaves its scale pending; a frame whose pivot fails leaves state and P
+ *     as it found them and sets the member's status (EKF_ERR_NUMERIC), as for a mapping member.
+ * A frozen member adds nothing through observation: if, in any ekf_batch_observe_logs*, ekf_batch_observe_replicas* or
+ * ekf_batch_observe_corner_replicas call, the log of a frozen member holds an index at or beyond that member's landmark
+ * count, the call returns EKF_ERR_STATE before anything is enqueued, and no member changes.
+ * Unfreezing: mapping continues from the state and P the frozen frames left, bit for bit the member ekf_batch_set_member
+ * restores from those arrays.  Frozen and mapping members run side by side in one call; a batch in which no member is
+ * frozen launches the kernel instances it launched before the flag existed and produces the same bits.
+ * Storage: the flags live on the host in the handle and, for the kernels, as [B] int32 in the batch workspace, directly
+ * behind the [B] status words and in their 256-byte-aligned piece: that piece holds 8 B bytes instead of 4 B, so
+ * workspace_bytes of ekf_batch_query_sizes grows by exactly round_up(8 B, 256) - round_up(4 B, 256) bytes (nothing for
+ * B <= 32).  cov_bytes, state_bytes, ld and what ekf_batch_log_workspace_bytes, ekf_batch_replica_workspace_bytes and
+ * ekf_batch_remove_workspace_bytes report do not change.
+ *   ekf_batch_set_map_frozen: frozen[b] != 0 freezes member b, 0 unfreezes it, from the next call on; NULL: no member is
+ *     frozen.  Waits for the batch's stream.
+ *   ekf_batch_get_map_frozen: out[b] = 1 / 0. */
+int ekf_batch_set_map_frozen(ekf_batch *b, const int32_t *frozen /* [B] HOST, or NULL: none */);
+int ekf_batch_get_map_frozen(const ekf_batch *b, int32_t *out /* [B] */);
 
 const char *ekf_last_error_string(void);
 

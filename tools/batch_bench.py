@@ -25,6 +25,13 @@ EKFBatch.replay_corner_replicas (corner noise, IPPE and flip labels on the devic
 poses (sigma = 0.01 on the tvec), and the share of flipped detections.  Lines carry "corners": true.  Kernel times:
 `rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --replicas --corners --members 256`
 (profiles/batch/rocprof_corner_replicas_*.json).
+--frozen: localisation against mapping on the same build (EKFBatch.freeze_map).  The chosen shape runs twice in one process
+on identical logs, from an identical restored map: a mapping bootstrap (the logs' bootstrap segments; with --replicas one
+member's), get_state / get_cov, then set_member into two batches, one with every member frozen, the other mapping; each runs
+the steady segment once as a warm-up, is restored again and runs it timed.  Lines carry "frozen": true and the frames/s of
+both.  Composes with --replicas, --corners, --large-maps, --max-visible, --model and --motion (motions on every frame of both
+batches).  Kernel times: `rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --frozen --members 256 ...`
+(profiles/batch_frozen/).
 """
 from __future__ import annotations
 
@@ -42,12 +49,12 @@ sys.path.insert(0, str(REPO))
 INIT = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0], dtype=np.float64)
 
 
-def split(log, t):
+def split(log, t, key="poses"):
     offs = log["offsets"]
     d = int(offs[t])
 
     def part(t0, t1, d0, d1):
-        return {"ids": log["ids"][d0:d1], "poses": log["poses"][d0:d1], "offsets": offs[t0:t1 + 1] - d0,
+        return {"ids": log["ids"][d0:d1], key: log[key][d0:d1], "offsets": offs[t0:t1 + 1] - d0,
                 "has_detections": log["has_detections"][t0:t1]}
     return part(0, t, 0, d), part(t, len(offs) - 1, d, int(offs[-1]))
 
@@ -83,6 +90,9 @@ def main():
     ap.add_argument("--motion", action="store_true",
                     help="also time the same logs with a small camera motion on every frame (EKFBatch(motion=True), "
                          "N(0, 1e-3^2) per component) and report its frames/s beside the figure without")
+    ap.add_argument("--frozen", action="store_true",
+                    help="the shape twice from one restored map: every member frozen (freeze_map) against mapping; "
+                         "frames/s of both")
     args = ap.parse_args()
     import torch
     from aruco_slam_amd.batch import EKFBatch
@@ -98,6 +108,8 @@ def main():
     visible = max(m_hi, 8 if rot else 16)
     if args.corners and not args.replicas:
         raise SystemExit("--corners goes with --replicas")
+    if args.frozen:
+        return frozen(args, n, m_hi, visible)
     if args.replicas:
         return (corner_replicas if args.corners else replicas)(args, n, m_hi, visible)
     args.members = args.members or [1, 16, 64, 256, 1024]
@@ -194,6 +206,88 @@ def append(path, lines):
     with out.open("a") as fh:
         for line in lines:
             fh.write(json.dumps(line) + "\n")
+
+
+def frozen(args, n, m_hi, visible):
+    """--frozen: see the module docstring."""
+    import torch
+    from aruco_slam_amd.batch import EKFBatch
+    from aruco_slam_amd.synthetic import corner_log, ragged_log
+    rot = args.model == "ekf_rotations"
+    rvs = 0.05 if rot else 0.0
+    sigma = np.array([0.01, 0.01, 0.01, 0.0, 0.0, 0.0])
+    key = "corners" if args.corners else "poses"
+    if args.corners:
+        cal = np.load(REPO / "tests" / "golden" / "calibration.npz", allow_pickle=False)
+        cam = (cal["camera_matrix"], cal["dist_coeffs"].reshape(-1))
+    members = args.members or ([16, 64, 256, 1024] if args.replicas else [1, 16, 64, 256, 1024])
+    if args.corners:
+        one = corner_log(n, (1, m_hi), args.steady, 0, *cam)
+        boot_src = split(dict(one, poses=one["poses_clean"] + 0.0), one["bootstrap_frames"])[0]
+        logs = [(boot_src, split(one, one["bootstrap_frames"], "corners")[1])]
+    else:
+        count = 1 if args.replicas else max(members)
+        logs = [split(lg, lg["bootstrap_frames"]) for lg in (ragged_log(n, (1, m_hi), args.steady, seed=s, rvec_sigma=rvs)
+                                                             for s in range(count))]
+    if args.motion:
+        rng = np.random.default_rng(99)
+        logs = [tuple(dict(part, motion=rng.normal(0.0, 1e-3, (len(part["offsets"]) - 1, 6))) for part in lg) for lg in logs]
+    kw = dict(max_landmarks=n, max_visible=visible, model=args.model, large_maps=True if args.large_maps else None,
+              motion=args.motion and not args.replicas, **({} if args.gate is None else {"gate": args.gate}))
+    lines = []
+    for B in members:
+        # the mapping bootstrap, once: every member's map (--replicas: one map for all)
+        boot = EKFBatch(len(logs[:B]), INIT, **kw)
+        boot.process_detection_logs([lg[0] for lg in logs[:B]])
+        assert boot.status() == [0] * boot.members
+        maps = [(boot.get_state(b), boot.get_cov(b),
+                 [k for k, _ in sorted(boot.landmarks[b].items(), key=lambda kv: kv[1])]) for b in range(boot.members)]
+        del boot
+
+        def restore(batch):
+            for b in range(B):
+                batch.set_member(b, *maps[b % len(maps)])
+
+        def run(batch, seed):
+            if args.corners:
+                batch.replay_corner_replicas(logs[0][1], args.sigma_px, seed)
+            elif args.replicas:
+                batch.replay_replicas({k: v for k, v in logs[0][1].items() if k != "motion"}, sigma, seed)
+            else:
+                batch.process_detection_logs([lg[1] for lg in logs[:B]])
+
+        rates, stopped = {}, {}
+        for name in ("mapping", "frozen"):
+            batch = EKFBatch(B, INIT, **kw)
+            if args.corners:
+                batch.set_camera(*cam)
+            restore(batch)
+            if name == "frozen":
+                batch.freeze_map()
+            run(batch, 1)          # warm-up
+            restore(batch)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(batch, 2)
+            wall = time.perf_counter() - t0
+            stopped[name] = sum(1 for v in batch.status() if v != 0)
+            assert args.corners or stopped[name] == 0      # (a flipped pose can stop a member of a corner study)
+            assert batch.map_frozen.all() == (name == "frozen")
+            rates[name] = (wall, B * args.steady / wall)
+            del batch
+        line = {"tool": "batch_bench", "frozen": True, **({"model": args.model} if rot else {}),
+                **({"replicas": True} if args.replicas else {}), **({"corners": True, "sigma_px": args.sigma_px} if args.corners else {}),
+                **({"large_maps": True} if args.large_maps else {}), **({"motion": True} if kw["motion"] else {}),
+                **({"wide_frames": True} if m_hi > (8 if rot else 16) else {}),
+                "members": B, "n": n, "m": [1, m_hi], "steady_frames": args.steady,
+                **({} if args.gate is None else {"gate": args.gate}),
+                **({"members_stopped": stopped} if args.corners else {}),
+                "mapping_wall_s": round(rates["mapping"][0], 6), "mapping_frames_per_s": round(rates["mapping"][1], 1),
+                "frozen_wall_s": round(rates["frozen"][0], 6), "frozen_frames_per_s": round(rates["frozen"][1], 1),
+                "frozen_over_mapping": round(rates["frozen"][1] / rates["mapping"][1], 3)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    append(args.out, lines)
 
 
 def replicas(args, n, m_hi, visible):

@@ -256,6 +256,27 @@ struct ekf_filter {
     // camera-strip update (ekf_cov_strip.hip) in place of the covariance update, in serial order; off after create and reset
     bool frozen = false;
 
+    // offline smoothing (include/ekf_slam_hip.h, "Offline smoothing"): the host-side table of the last recorded replay
+    // (ekf_observe_log_recorded): per record the frame, N_r, where it lies in the caller's history buffer, s_eff (0: the frame
+    // was only moved) and the motion; per frame its record (-1: before the first).  ekf_smooth_history reads it; `valid`
+    // falls with ekf_remove_markers and ekf_reset.
+    struct HistoryRec {
+        int32_t frame, dims;
+        size_t off;            // bytes from the start of the history buffer
+        double s_eff;
+        double u[6];
+        int32_t stepped, moved;
+    };
+    struct History {
+        bool valid = false;
+        const void* buf = nullptr;
+        size_t bytes = 0;
+        int32_t frames = 0;
+        std::vector<HistoryRec> recs;
+        std::vector<int32_t> frame_rec;
+        std::vector<EkfSmoothRec> table;      // what the kernels read, uploaded by ekf_smooth_history
+    } hist;
+
     bool has_scale() const { return (cfg.flags & EKF_FLAG_FRAME_SCALE) != 0; }
     bool has_motion() const { return (cfg.flags & EKF_FLAG_MOTION) != 0; }
     bool gate_on() const { return lay.has_gate && gate < __builtin_inf(); }
@@ -1286,6 +1307,7 @@ int ekf_remove_markers(ekf_filter* f, const int32_t* lm_index, int32_t count, vo
     by_cov_type(f, [&](auto elem) { ekf_launch_remove<decltype(elem)>(a, 1, f->stream); });
     HIP_TRY(hipGetLastError());
     f->shortcut.removed();
+    f->hist.valid = false;      // (the records no longer describe this filter's map)
     f->cov = cov_dev_new;
     f->state = state_dev_new;
     f->n_lm -= count;
@@ -1318,6 +1340,7 @@ int ekf_reset(ekf_filter* f, const double initial_camera_pose[10]) {
     f->last_m = 0;
     f->pending = 0.0;
     f->frozen = false;      // (a reset filter has no map)
+    f->hist.valid = false;
     f->is_reset = true;
     return EKF_OK;
 }
@@ -1572,9 +1595,63 @@ LogLayout log_layout(int rd, int64_t D) {
     return {idx, slots, std::max<size_t>(256, w.end)};
 }
 
+// ---- offline smoothing: what is supported, and the sizes of a history ----------------------------------------------------
+// (include/ekf_slam_hip.h, "Offline smoothing": the refusals)
+int smoothing_supported(const ekf_filter* f) {
+    if (f->cfg.model != EKF_MODEL_EKF) return fail(EKF_ERR_STATE, "smoothing: EKF_MODEL_ROTATIONS is not supported");
+    if (f->cfg.cov_dtype != EKF_COV_F64) return fail(EKF_ERR_STATE, "smoothing needs the f64 covariance");
+    if (f->cfg.quat_mode != EKF_QUAT_SCALAR_FIRST)
+        return fail(EKF_ERR_STATE, "smoothing needs EKF_QUAT_SCALAR_FIRST (the as-written injection has no inverse)");
+    if (f->frozen) return fail(EKF_ERR_STATE, "smoothing: the map is frozen");
+    return EKF_OK;
+}
+
+// one record: state [dims] and the packed lower triangle, f64, in a 256-byte aligned piece
+size_t history_record_bytes(int64_t dims) { return align256((size_t)(dims + dims * (dims + 1) / 2) * 8); }
+
+// upper bound from the log alone: the header and one record per frame at the dims that frame ends with
+void history_bound(int lmd, int n_lm, const LogCheck& lc, int64_t frames, size_t* bytes) {
+    size_t total = 256;
+    for (int64_t t = 0; t < frames; ++t) total += history_record_bytes(EKF_CAM + (int64_t)lmd * (n_lm + lc.new_at[t + 1]));
+    *bytes = total;
+}
+
+// smoothing workspace: [status 256 | table | xs | xp | yv | wv | cv | xinv | M], the vectors and M sized by the largest record
+// rounded up to whole block columns (the resident tier uses the first two pieces only)
+struct SmoothLayout {
+    size_t table, xs, xp, yv, wv, cv, xinv, M, total;
+};
+SmoothLayout smooth_layout(size_t records, int64_t nmax) {
+    const size_t npad = (size_t)round_up(std::max<int64_t>(nmax, 1), EKF_WIDE_BLOCK);
+    Carve w;
+    w.take(256);
+    SmoothLayout L{};
+    L.table = w.take(std::max<size_t>(records, 1) * sizeof(EkfSmoothRec));
+    L.xs = w.take(npad * 8);
+    L.xp = w.take(npad * 8);
+    L.yv = w.take(npad * 8);
+    L.wv = w.take(npad * 8);
+    L.cv = w.take(npad * 8);
+    L.xinv = w.take((size_t)EKF_WIDE_BLOCK * EKF_WIDE_BLOCK * 8);
+    L.M = w.take(npad * npad * 8);
+    L.total = w.end;
+    return L;
+}
+
+int64_t history_nmax(const ekf_filter* f) {
+    int64_t nmax = 0;
+    for (const auto& h : f->hist.recs) nmax = std::max<int64_t>(nmax, h.dims);
+    return nmax;
+}
+
 }  // namespace
 
 extern "C" {
+
+static int observe_log_run(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
+                           const double* poses_dev, const double* rows_dev, const double* scale, const double* motion,
+                           void* log_ws, size_t log_ws_bytes, double* trajectory_dev, double* mahal_dev, bool record,
+                           void* history_dev, size_t history_bytes);
 
 int ekf_log_workspace_bytes(const ekf_filter* f, int64_t detections, size_t* bytes) {
     if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
@@ -1618,8 +1695,28 @@ int ekf_observe_log_scaled(ekf_filter* f, const int32_t* lm_index, const int64_t
 int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
                           const double* poses_dev, const double* rows_dev, const double* scale, const double* motion,
                           void* log_ws, size_t log_ws_bytes, double* trajectory_dev, double* mahal_dev) {
+    return observe_log_run(f, lm_index, offsets, frames, poses_dev, rows_dev, scale, motion, log_ws, log_ws_bytes,
+                           trajectory_dev, mahal_dev, false, nullptr, 0);
+}
+
+int ekf_observe_log_recorded(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
+                             const double* poses_dev, const double* rows_dev, const double* scale, const double* motion,
+                             void* log_ws, size_t log_ws_bytes, double* trajectory_dev, double* mahal_dev,
+                             void* history_dev, size_t history_bytes) {
+    return observe_log_run(f, lm_index, offsets, frames, poses_dev, rows_dev, scale, motion, log_ws, log_ws_bytes,
+                           trajectory_dev, mahal_dev, true, history_dev, history_bytes);
+}
+
+// The log replay.  record: the by-frame serial loop, and behind every frame that changed the filter -- stepped, or moved by a
+// non-zero motion -- one pack launch that copies state and the lower triangle of P into the next record of the history
+// (recording only reads: every other launch is the one the plain call enqueues, in its order).
+static int observe_log_run(ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames,
+                           const double* poses_dev, const double* rows_dev, const double* scale, const double* motion,
+                           void* log_ws, size_t log_ws_bytes, double* trajectory_dev, double* mahal_dev, bool record,
+                           void* history_dev, size_t history_bytes) {
     int rc = check_ready(f);
     if (rc) return rc;
+    if (record && (rc = smoothing_supported(f))) return rc;
     if (rows_dev && !f->lay.has_rows) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_ROW_NOISE");
     if (mahal_dev && !f->lay.has_gate) return fail(EKF_ERR_STATE, "the filter was created without EKF_FLAG_GATE");
     // a gate that is set, or distances asked for: frame by frame in serial order, each frame on its survivors
@@ -1627,7 +1724,7 @@ int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t*
     // frame by frame in serial order: a gated call, and a call with motions (a motion between two frames of a pipelined run
     // would change rows of the P_{t+1} the next front kernel completes from P_t and W_t)
     // ... and a call on a frozen map
-    const bool by_frame = gated || motion || f->frozen;
+    const bool by_frame = gated || motion || f->frozen || record;
     // ---- validation on the host: nothing is enqueued before the whole log has passed
     if (frames < 0) return fail(EKF_ERR_INVALID, "negative frame count");
     if ((rc = check_scales(f, scale, frames))) return rc;
@@ -1643,6 +1740,17 @@ int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t*
     if ((rc = check_log(lm_index, offsets, frames, f->n_lm, f->cfg, "the log", &lc))) return rc;
     if (f->frozen && !lc.slots.empty())
         return fail(EKF_ERR_STATE, "the map is frozen: a log with first sightings would add landmarks (ekf_set_map_frozen)");
+    if (record) {
+        size_t need = 0;
+        history_bound(f->lay.lmd, f->n_lm, lc, frames, &need);
+        if ((rc = check_device_buffers({history_dev}, history_bytes, need, "ekf_history_bytes"))) return rc;
+        f->hist = ekf_filter::History{};
+        f->hist.buf = history_dev;
+        f->hist.bytes = history_bytes;
+        f->hist.frames = frames;
+        f->hist.frame_rec.assign((size_t)frames, -1);
+        f->hist.valid = true;
+    }
     for (int i = 0; i < 4; ++i) f->log_stats[i] = 0;
     f->reset_gate_stats();
     if (frames == 0) return EKF_OK;
@@ -1713,6 +1821,26 @@ int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t*
         ekf_launch_log_prepare(poses_dev, D, rd, z_all, f->stream);
     }
     if (!lead.empty()) ekf_launch_log_fill_rows(trajectory_dev, pin_lead, (int32_t)(lead.size() / 2), f->state, f->stream);
+    // recording: the camera state at the call (the rows of the frames before the first record), then record after record
+    size_t hist_at = 256;
+    if (record) HIP_TRY(hipMemcpyAsync(history_dev, f->state, 7 * 8, hipMemcpyDeviceToDevice, f->stream));
+    auto record_frame = [&](int t, bool moved, bool stepped, double s_eff) {
+        if (record && (moved || stepped)) {
+            ekf_filter::HistoryRec h{};
+            h.frame = t;
+            h.dims = f->dims();
+            h.off = hist_at;
+            h.s_eff = stepped ? s_eff : 0.0;
+            for (int i = 0; i < 6; ++i) h.u[i] = (moved && motion) ? motion[(size_t)t * 6 + i] : 0.0;
+            h.stepped = stepped;
+            h.moved = moved;
+            ekf_launch_history_pack(static_cast<const double*>(f->cov), f->ld, f->state, h.dims,
+                                    reinterpret_cast<double*>(static_cast<char*>(history_dev) + h.off), f->stream);
+            hist_at += history_record_bytes(h.dims);
+            f->hist.recs.push_back(h);
+        }
+        if (record) f->hist.frame_rec[t] = (int32_t)f->hist.recs.size() - 1;
+    };
     auto frame_of = [&](int t) {
         const int64_t d0 = offsets[t];
         return RunFrame{idx_all + d0, z_all + (size_t)d0 * rd, m_of(t), trajectory_dev ? trajectory_dev + (size_t)t * 7 : nullptr,
@@ -1735,11 +1863,13 @@ int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t*
         for (int t = 0; t < frames && rc == EKF_OK; ++t) {
             const RunFrame r = frame_of(t);
             const double* sc = scale ? scale + t : nullptr;
-            if ((rc = enqueue_motion(f, motion ? motion + (size_t)t * 6 : nullptr))) break;
+            bool moved = false;
+            if ((rc = enqueue_motion(f, motion ? motion + (size_t)t * 6 : nullptr, &moved))) break;
             const double s_eff = gated ? frame_scale(f, sc) : s_effs[t];
             if (r.m == 0) {
                 rc = repeat_row(f, r.traj_row);
                 if (gated) frame_scale_done(f, sc, s_eff, false);
+                if (rc == EKF_OK) record_frame(t, moved, false, s_eff);
                 continue;
             }
             const int nnew = first_sightings(t);
@@ -1752,6 +1882,7 @@ int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t*
                        : enqueue_frame(f, r.idx, r.z, r.rows, r.m, r.traj_row, false, s_eff);
             if (rc == EKF_OK && s > 0) f->log_stats[0] += 1;
             if (rc == EKF_OK && gated) frame_scale_done(f, sc, s_eff, s > 0);
+            if (rc == EKF_OK) record_frame(t, moved, s > 0, s_eff);
         }
     } else {
         rc = run_frames(f, frames, frame_of, first_sightings, plan, mode == EKF_SEQ_PIPELINED, f->log_stats);
@@ -1763,9 +1894,162 @@ int ekf_observe_log_moved(ekf_filter* f, const int32_t* lm_index, const int64_t*
     f->shortcut.log();
     // (the staging may be reused once the stream is here -- also after an error: its copy may have been enqueued)
     f->log_pin_turn = turn ^ 1;
+    if (rc) f->hist.valid = f->hist.valid && !record;      // (a recorded call that failed leaves no history)
     HIP_TRY(hipEventRecord(f->log_pin_done[turn], f->stream));
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
+    return EKF_OK;
+}
+
+// ---- offline smoothing (include/ekf_slam_hip.h, "Offline smoothing"; kernels: ekf_smooth.hip) ---------------------------
+int ekf_history_record_bytes(int32_t dims, size_t* bytes) {
+    if (!bytes || dims < EKF_CAM) return fail(EKF_ERR_INVALID, "bad record size request");
+    *bytes = history_record_bytes(dims);
+    return EKF_OK;
+}
+
+int ekf_history_bytes(const ekf_filter* f, const int32_t* lm_index, const int64_t* offsets, int32_t frames, size_t* bytes) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!bytes || frames < 0) return fail(EKF_ERR_INVALID, "bad history size request");
+    int rc;
+    if (frames > 0 && !offsets) return fail(EKF_ERR_INVALID, "offsets is NULL");
+    if (frames > 0 && (rc = check_offsets(offsets, frames, "offsets"))) return rc;
+    if (frames > 0 && offsets[frames] > 0 && !lm_index) return fail(EKF_ERR_INVALID, "NULL detections");
+    LogCheck lc;
+    if ((rc = check_log(lm_index, offsets, frames, f->n_lm, f->cfg, "the log", &lc))) return rc;
+    history_bound(f->lay.lmd, f->n_lm, lc, frames, bytes);
+    return EKF_OK;
+}
+
+int ekf_history_info(const ekf_filter* f, int32_t* records, int32_t capacity, int32_t* frame, int32_t* dims, double* s_eff,
+                     double* motion, int32_t* stepped, int32_t* frame_record) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!records || capacity < 0) return fail(EKF_ERR_INVALID, "bad history info request");
+    if (!f->hist.valid) return fail(EKF_ERR_STATE, "no recorded replay (ekf_observe_log_recorded), or the filter has changed since");
+    const int32_t R = (int32_t)f->hist.recs.size();
+    *records = R;
+    const bool arrays = frame || dims || s_eff || motion || stepped;
+    if (arrays && capacity < R) return fail(EKF_ERR_CAPACITY, "fewer entries than records");
+    for (int32_t r = 0; r < R && arrays; ++r) {
+        const auto& h = f->hist.recs[r];
+        if (frame) frame[r] = h.frame;
+        if (dims) dims[r] = h.dims;
+        if (s_eff) s_eff[r] = h.s_eff;
+        if (motion)
+            for (int i = 0; i < 6; ++i) motion[6 * (size_t)r + i] = h.u[i];
+        if (stepped) stepped[r] = h.stepped;
+    }
+    if (frame_record)
+        for (int32_t t = 0; t < f->hist.frames; ++t) frame_record[t] = f->hist.frame_rec[t];
+    return EKF_OK;
+}
+
+int ekf_history_record(ekf_filter* f, const void* history_dev, int32_t r, double* state_out, double* cov_out, int32_t dims) {
+    int rc = check_ready(f);
+    if (rc) return rc;
+    if (!f->hist.valid || history_dev != f->hist.buf)
+        return fail(EKF_ERR_STATE, "not the history of this handle's last recorded replay");
+    if (r < 0 || r >= (int32_t)f->hist.recs.size()) return fail(EKF_ERR_INVALID, "no such record");
+    const auto& h = f->hist.recs[r];
+    if (dims != h.dims) return fail(EKF_ERR_INVALID, "dims must equal the record's (ekf_history_info)");
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    const size_t N = (size_t)h.dims;
+    std::vector<double> packed(N + N * (N + 1) / 2);
+    HIP_TRY(hipMemcpy(packed.data(), static_cast<const char*>(history_dev) + h.off, packed.size() * 8, hipMemcpyDeviceToHost));
+    if (state_out) std::memcpy(state_out, packed.data(), N * 8);
+    if (cov_out) {
+        const double* tri = packed.data() + N;
+        size_t e = 0;
+        for (size_t j = 0; j < N; ++j)
+            for (size_t i = j; i < N; ++i, ++e) cov_out[i * N + j] = cov_out[j * N + i] = tri[e];
+    }
+    return EKF_OK;
+}
+
+int ekf_smooth_workspace_bytes(const ekf_filter* f, size_t* bytes) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!bytes) return fail(EKF_ERR_INVALID, "bytes is NULL");
+    if (!f->hist.valid) return fail(EKF_ERR_STATE, "no recorded replay (ekf_observe_log_recorded), or the filter has changed since");
+    *bytes = smooth_layout(f->hist.recs.size(), history_nmax(f)).total;
+    return EKF_OK;
+}
+
+int ekf_smooth_history(ekf_filter* f, const void* history_dev, size_t history_bytes, void* ws, size_t ws_bytes, int32_t flags,
+                       double* smoothed_dev) {
+    int rc = check_ready(f);
+    if (rc) return rc;
+    if ((rc = smoothing_supported(f))) return rc;
+    if (!f->hist.valid) return fail(EKF_ERR_STATE, "no recorded replay (ekf_observe_log_recorded), or the filter has changed since");
+    if (history_dev != f->hist.buf || history_bytes < f->hist.bytes)
+        return fail(EKF_ERR_STATE, "not the history of this handle's last recorded replay");
+    const int32_t F = f->hist.frames, R = (int32_t)f->hist.recs.size();
+    if (F == 0) return EKF_OK;
+    if (!smoothed_dev) return fail(EKF_ERR_INVALID, "smoothed_dev is NULL");
+    const int64_t nmax = history_nmax(f);
+    const SmoothLayout L = smooth_layout((size_t)R, nmax);
+    if ((rc = check_device_buffers({ws}, ws_bytes, L.total, "ekf_smooth_workspace_bytes"))) return rc;
+    const bool resident = nmax <= EKF_SMOOTH_RESIDENT_DIMS && !(flags & 1);
+    // (the backward substitution keeps y in LDS: 64 KiB without an attribute, less its static kilobyte)
+    if (!resident && round_up(nmax, EKF_WIDE_BLOCK) > 8064)
+        return fail(EKF_ERR_CAPACITY, "the blocked smoothing tier takes records of up to 8064 dims");
+    const double* hist = static_cast<const double*>(history_dev);
+    if (R == 0) {      // nothing changed the filter: every row is the camera state at the call
+        ekf_launch_smooth_rows(hist, smoothed_dev, 0, F, f->stream);
+        HIP_TRY(hipGetLastError());
+        return EKF_OK;
+    }
+    std::vector<EkfSmoothRec>& table = f->hist.table;
+    table.assign((size_t)R, EkfSmoothRec{});
+    for (int32_t r = 0; r < R; ++r) {
+        const auto& h = f->hist.recs[r];
+        EkfSmoothRec& e = table[r];
+        e.off = (int64_t)(h.off / 8);
+        e.dims = h.dims;
+        e.moved = h.moved;
+        for (int i = 0; i < 6; ++i) e.u[i] = h.u[i];
+        const EkfNoise nz = frame_noise(f, h.s_eff);
+        e.q[0] = nz.q_cam;
+        e.q[1] = nz.q_err;
+        e.q[2] = nz.q_lm;
+        e.frame0 = h.frame;
+        e.frame1 = r + 1 < R ? f->hist.recs[r + 1].frame : F;
+    }
+    char* w = static_cast<char*>(ws);
+    int32_t* status = reinterpret_cast<int32_t*>(w);
+    EkfSmoothRec* table_dev = reinterpret_cast<EkfSmoothRec*>(w + L.table);
+    HIP_TRY(hipMemsetAsync(w, 0, 256, f->stream));
+    HIP_TRY(hipMemcpyAsync(table_dev, table.data(), (size_t)R * sizeof(EkfSmoothRec), hipMemcpyHostToDevice, f->stream));
+    const int32_t lead = table[0].frame0;
+    if (resident) {
+        HIP_TRY(ekf_launch_smooth_resident(hist, table_dev, R, (int32_t)nmax, lead, smoothed_dev, status, f->stream));
+    } else {
+        EkfSmoothBlocked a{};
+        a.history = hist;
+        a.M = reinterpret_cast<double*>(w + L.M);
+        a.xs = reinterpret_cast<double*>(w + L.xs);
+        a.xp = reinterpret_cast<double*>(w + L.xp);
+        a.yv = reinterpret_cast<double*>(w + L.yv);
+        a.wv = reinterpret_cast<double*>(w + L.wv);
+        a.cv = reinterpret_cast<double*>(w + L.cv);
+        a.xinv = reinterpret_cast<double*>(w + L.xinv);
+        a.smoothed = smoothed_dev;
+        a.status = status;
+        const EkfSmoothRec& last = table[R - 1];
+        HIP_TRY(hipMemcpyAsync(a.xs, hist + last.off, (size_t)last.dims * 8, hipMemcpyDeviceToDevice, f->stream));
+        ekf_launch_smooth_rows(hist + last.off, smoothed_dev, last.frame0, last.frame1, f->stream);
+        ekf_launch_smooth_rows(hist, smoothed_dev, 0, lead, f->stream);
+        for (int32_t r = R - 2; r >= 0; --r) {
+            a.rec = table[r];
+            a.next = table[r + 1];
+            ekf_launch_smooth_blocked_step(a, f->stream);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    // the pass has its own status word: a P_p that is not positive definite is reported here and leaves nothing on the filter
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    int32_t st = 0;
+    HIP_TRY(hipMemcpy(&st, status, 4, hipMemcpyDeviceToHost));
+    if (st != 0) return fail(EKF_ERR_NUMERIC, "smoothing: a predicted covariance P_p is not positive definite");
     return EKF_OK;
 }
 

@@ -299,6 +299,38 @@ template <typename T> void ekf_launch_motion(const EkfMotionArgs& a, hipStream_t
 template <typename T>
 void ekf_launch_cov_diag(const void* cov, int64_t ld, double* out_dev, int32_t count, hipStream_t s);
 
+// Offline smoothing (ekf_smooth.hip; include/ekf_slam_hip.h: the smoothing rules; arithmetic: ekf_smooth_device.h).
+// A history is [256 B: state[0:7] at the start of the recorded call | records]; record r at `off` doubles from the start of
+// the history: state[0:dims], then the lower triangle of P packed column by column (ekf_smooth_tri), all f64.
+#define EKF_SMOOTH_RESIDENT_DIMS 160      // resident tier: every record has at most this many dims (n <= 50)
+#define EKF_SMOOTH_THREADS 512
+struct EkfSmoothRec {
+    int64_t off;                // doubles from the start of the history
+    int32_t dims;               // N_r
+    int32_t moved;              // the transition INTO this record starts with the motion u (0: u is zero)
+    double u[6];
+    double q[3];                // Q_eff of the transition into this record: fl(s_eff q_cam), fl(s_eff q_err), fl(s_eff q_lm)
+    int32_t frame0, frame1;     // output rows [frame0, frame1) take this record's smoothed pose
+};
+// the pack launch of a recorded replay: state[0:dims] and the lower triangle of P (f64, leading dimension ld) into a record
+void ekf_launch_history_pack(const double* cov, int64_t ld, const double* state, int32_t dims, double* record, hipStream_t s);
+// trajectory rows [f0, f1) <- src[0:7]
+void ekf_launch_smooth_rows(const double* src, double* smoothed, int32_t f0, int32_t f1, hipStream_t s);
+// Resident tier: ONE launch of ONE workgroup runs the whole backward pass; P_p as a packed triangle of nmax dims in dynamic
+// LDS.  status[0] |= EKF_ST_NOT_SPD when a pivot of a P_p is not positive.  Returns the error of the attribute call.
+hipError_t ekf_launch_smooth_resident(const double* history, const EkfSmoothRec* table_dev, int32_t records, int32_t nmax,
+                                      int32_t lead_frames, double* smoothed, int32_t* status, hipStream_t s);
+// Blocked tier: one backward step, r+1 -> r, as a short launch sequence.  Workspace pieces (all device): M [npad][npad] with
+// npad = dims of `rec` rounded up to EKF_WIDE_BLOCK, xs (x^s, in and out), xp, yv [npad], wv, cv, xinv [64 * 64].
+struct EkfSmoothBlocked {
+    const double* history;
+    EkfSmoothRec rec, next;     // record r and record r + 1
+    double *M, *xs, *xp, *yv, *wv, *cv, *xinv;
+    double* smoothed;
+    int32_t* status;            // [0] sticky EKF_ST_NOT_SPD, [1..2] diagnostics of the factorisation kernels
+};
+void ekf_launch_smooth_blocked_step(const EkfSmoothBlocked& a, hipStream_t s);
+
 // Batch of independent filters (ekf_batch.hip: EKF, ekf_batch_rot.hip: EKF_Rotations; frame body ekf_batch_impl.h): one
 // workgroup per member, frames [member_frames[b] + window_first, + window_frames) of its log.  Everything is validated on
 // the host (indices, first-sighting order, widths, capacity).

@@ -1,0 +1,327 @@
+// Offline smoothing: the Rauch-Tung-Striebel backward pass over the records of a recorded replay (include/ekf_slam_hip.h:
+// the smoothing rules; per-element arithmetic: ekf_smooth_device.h).  Only the smoothed STATE is formed, so a
+// backward step r+1 -> r is one Cholesky solve and one matrix-vector product:
+//   x_p = move(x_r, u),  P_p = F~ P_r F~^T + diag(Q_eff),  delta = x^s_{r+1} (-) x_p,  y = P_p^-1 delta,
+//   c = P_r (F~^T y),  x^s_r = inject(x_r, c).
+//   pack     : one record of a recorded replay: state and the lower triangle of P, packed column by column
+//   resident : every record has N <= 160: ONE launch of ONE workgroup runs the whole pass, P_p as a packed triangle in LDS
+//   blocked  : any N: per step expand / move / prepare / the blocked Cholesky of ekf_wide.hip (ncols = 0: the right-hand
+//              side rides along as its residual) / backward substitution / matrix-vector product and injection
+// Nothing here writes the filter: the history, the table and the workspace are the caller's, and the status word is the
+// pass's own.
+#include "ekf_kernels.h"
+#include "ekf_smooth_device.h"
+
+#include <algorithm>
+
+namespace {
+
+// ---- pack ---------------------------------------------------------------------------------------------------------------
+// Workgroup j copies column j of the lower triangle: P[j][i], i >= j (P is bitwise symmetric, and row j is contiguous).
+__global__ __launch_bounds__(256) void ekf_history_pack_kernel(const double* __restrict__ P, int64_t ld,
+                                                               const double* __restrict__ state, int N,
+                                                               double* __restrict__ rec) {
+    const int j = blockIdx.x;
+    double* tri = rec + N + ekf_smooth_col(N, j);
+    for (int i = j + threadIdx.x; i < N; i += 256) tri[i - j] = P[(int64_t)j * ld + i];
+    if (j == 0)
+        for (int i = threadIdx.x; i < N; i += 256) rec[i] = state[i];
+}
+
+__global__ __launch_bounds__(64) void ekf_smooth_rows_kernel(const double* __restrict__ src, double* __restrict__ out,
+                                                             int f0, int f1) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e < 7 * (f1 - f0)) out[(int64_t)7 * f0 + e] = src[e % 7];
+}
+
+// the camera part of x^s_r = inject(x_r, c) and the error dims; xr, cv: the record's state and c (any memory)
+__device__ __forceinline__ void ekf_smooth_inject_camera(const double* xr, const double* c7, double* xs) {
+    double q[4] = {xr[3], xr[4], xr[5], xr[6]};
+    ekf_smooth_quat_inject(q, c7);
+    for (int i = 0; i < 4; ++i) xs[3 + i] = q[i];
+    for (int i = 0; i < 3; ++i) xs[7 + i] = 0.0;
+}
+
+// ---- resident tier ------------------------------------------------------------------------------------------------------
+// LDS: the packed triangle of nmax dims (dynamic; 103 040 B at 160) and six vectors of 160 doubles.  A Cholesky column j:
+// every thread reads the pivot, threads scale the column (the diagonal of L goes to ld_s: nobody overwrites what others
+// still read), a barrier, then wave w of the 8 updates the trailing columns j+1+w, j+9+w, ... -- lanes down a column, which is
+// contiguous -- and the wave whose turn the "column N" is carries the right-hand side along (forward substitution).  The
+// backward substitution runs in ONE wave with y in registers; then P_r is read again from the history into the triangle's
+// LDS (L is no longer needed) for c = P_r w.
+__global__ __launch_bounds__(EKF_SMOOTH_THREADS) void ekf_smooth_resident_kernel(const double* __restrict__ hist,
+                                                                                 const EkfSmoothRec* __restrict__ table,
+                                                                                 int R, int lead_frames,
+                                                                                 double* __restrict__ smoothed,
+                                                                                 int32_t* status) {
+    extern __shared__ double tri[];
+    __shared__ double xs[EKF_SMOOTH_RESIDENT_DIMS], xr[EKF_SMOOTH_RESIDENT_DIMS], xp[EKF_SMOOTH_RESIDENT_DIMS];
+    __shared__ double dv[EKF_SMOOTH_RESIDENT_DIMS], wv[EKF_SMOOTH_RESIDENT_DIMS], ld_s[EKF_SMOOTH_RESIDENT_DIMS];
+    __shared__ EkfMotionF F;
+    __shared__ double bmat[EKF_CAM][EKF_CAM];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    {
+        const EkfSmoothRec last = table[R - 1];
+        if (tid < last.dims) xs[tid] = hist[last.off + tid];
+        __syncthreads();
+        for (int e = tid; e < 7 * (last.frame1 - last.frame0); e += EKF_SMOOTH_THREADS)
+            smoothed[(int64_t)7 * last.frame0 + e] = xs[e % 7];
+        for (int e = tid; e < 7 * lead_frames; e += EKF_SMOOTH_THREADS) smoothed[e] = hist[e % 7];
+    }
+    for (int r = R - 2; r >= 0; --r) {
+        const EkfSmoothRec rec = table[r], nx = table[r + 1];
+        const int N = rec.dims, T = (int)ekf_smooth_tri_count(N);
+        const double* __restrict__ xg = hist + rec.off;
+        const double* __restrict__ pg = xg + N;
+        __syncthreads();      // (the step before is over: xs is complete, tri and the vectors are free)
+        for (int e = tid; e < T; e += EKF_SMOOTH_THREADS) tri[e] = pg[e];
+        if (tid < N) xr[tid] = xp[tid] = xg[tid];
+        __syncthreads();
+        if (nx.moved) {
+            if (tid == 0) ekf_motion_form(xr, nx.u, F);
+            __syncthreads();
+            double in[EKF_CAM], out[EKF_CAM];
+            const int j = EKF_CAM + tid;
+            if (j < N) {      // the strip: P[0:10, j] = P[j, 0:10], one thread per column
+#pragma unroll
+                for (int k = 0; k < EKF_CAM; ++k) in[k] = tri[ekf_smooth_tri(N, j, k)];
+                ekf_motion_column(F, in, out);
+#pragma unroll
+                for (int k = 0; k < EKF_CAM; ++k) tri[ekf_smooth_tri(N, j, k)] = out[k];
+            }
+            if (tid < EKF_CAM) {      // the block: B = F P_cc, then row i of F P_cc F^T = F B[i, :]^T
+#pragma unroll
+                for (int k = 0; k < EKF_CAM; ++k) in[k] = tri[ekf_smooth_sym(N, k, tid)];
+                ekf_motion_column(F, in, out);
+#pragma unroll
+                for (int k = 0; k < EKF_CAM; ++k) bmat[k][tid] = out[k];
+            }
+            __syncthreads();
+            if (tid < EKF_CAM) {
+#pragma unroll
+                for (int k = 0; k < EKF_CAM; ++k) in[k] = bmat[tid][k];
+                ekf_motion_column(F, in, out);
+                for (int k = 0; k <= tid; ++k) tri[ekf_smooth_tri(N, tid, k)] = out[k];
+            }
+            if (tid == 0) {
+                for (int i = 0; i < 3; ++i) xp[i] = F.c1[i];
+                for (int i = 0; i < 4; ++i) xp[3 + i] = F.q1[i];
+            }
+            __syncthreads();
+        }
+        if (tid < N) {
+            tri[ekf_smooth_tri(N, tid, tid)] += ekf_smooth_qdiag(tid, nx.q);
+            dv[tid] = ekf_smooth_residual(tid, xs, xp);
+        }
+        __syncthreads();
+        // right-looking Cholesky of P_p in place, the right-hand side with it
+        bool bad = false;
+        for (int j = 0; j < N; ++j) {
+            const int cj = (int)ekf_smooth_col(N, j);
+            const double d = tri[cj];
+            const double l = sqrt(d);
+            bad = bad || !(d > 0.0);
+            const int i = j + 1 + tid;
+            if (i < N) tri[cj + i - j] = tri[cj + i - j] / l;
+            if (tid == EKF_SMOOTH_THREADS - 1) {
+                ld_s[j] = l;
+                dv[j] = dv[j] / l;
+            }
+            __syncthreads();
+            for (int c = j + 1 + wave; c < N; c += EKF_SMOOTH_THREADS / 64) {
+                const double lc = tri[cj + c - j];
+                const int cc = (int)ekf_smooth_col(N, c);
+                for (int i2 = c + lane; i2 < N; i2 += 64)
+                    tri[cc + i2 - c] = __builtin_fma(-tri[cj + i2 - j], lc, tri[cc + i2 - c]);
+            }
+            if (((N - j - 1) & (EKF_SMOOTH_THREADS / 64 - 1)) == wave) {
+                const double yj = dv[j];
+                for (int i2 = j + 1 + lane; i2 < N; i2 += 64) dv[i2] = __builtin_fma(-tri[cj + i2 - j], yj, dv[i2]);
+            }
+            __syncthreads();
+        }
+        if (bad) {      // (every thread saw the same pivots)
+            if (tid == 0) atomicOr(status, EKF_ST_NOT_SPD);
+            return;
+        }
+        // L^T y' = y: wave 0, y in registers (lane l holds rows l, l + 64, l + 128), column by column from the last
+        if (wave == 0) {
+            double y0 = lane < N ? dv[lane] : 0.0, y1 = lane + 64 < N ? dv[lane + 64] : 0.0,
+                   y2 = lane + 128 < N ? dv[lane + 128] : 0.0;
+            for (int j = N - 1; j >= 0; --j) {
+                const int part = j >> 6, jl = j & 63;
+                double v = part == 0 ? y0 : (part == 1 ? y1 : y2);
+                if (lane == jl) v = v / ld_s[j];
+                const double zj = __shfl(v, jl);
+                if (lane == jl) {
+                    if (part == 0) y0 = zj; else if (part == 1) y1 = zj; else y2 = zj;
+                }
+                // L[j][i], i < j: column i of the triangle, row j
+                if (lane < j) y0 = __builtin_fma(-tri[ekf_smooth_tri(N, j, lane)], zj, y0);
+                if (lane + 64 < j) y1 = __builtin_fma(-tri[ekf_smooth_tri(N, j, lane + 64)], zj, y1);
+                if (lane + 128 < j) y2 = __builtin_fma(-tri[ekf_smooth_tri(N, j, lane + 128)], zj, y2);
+            }
+            if (lane < N) dv[lane] = y0;
+            if (lane + 64 < N) dv[lane + 64] = y1;
+            if (lane + 128 < N) dv[lane + 128] = y2;
+        }
+        __syncthreads();
+        // w = F~^T y, and P_r again (through L2) where L was
+        if (tid == 0) {
+            double y10[EKF_CAM], w10[EKF_CAM];
+            for (int i = 0; i < EKF_CAM; ++i) y10[i] = dv[i];
+            ekf_smooth_ft(F, nx.moved, y10, w10);
+            for (int i = 0; i < EKF_CAM; ++i) wv[i] = w10[i];
+        } else if (tid >= EKF_CAM && tid < N) {
+            wv[tid] = dv[tid];
+        }
+        for (int e = tid; e < T; e += EKF_SMOOTH_THREADS) tri[e] = pg[e];
+        __syncthreads();
+        double c = 0.0;
+        if (tid < N) {
+            for (int j = 0; j < N; ++j) c = __builtin_fma(tri[ekf_smooth_sym(N, tid, j)], wv[j], c);
+        }
+        __syncthreads();      // (everybody has read wv and dv)
+        if (tid < N) dv[tid] = c;
+        __syncthreads();
+        if (tid < N && (tid < 3 || tid >= EKF_CAM)) xs[tid] = ekf_smooth_inject_add(xr[tid], c);
+        if (tid == 3) ekf_smooth_inject_camera(xr, dv + 7, xs);
+        __syncthreads();
+        for (int e = tid; e < 7 * (rec.frame1 - rec.frame0); e += EKF_SMOOTH_THREADS)
+            smoothed[(int64_t)7 * rec.frame0 + e] = xs[e % 7];
+    }
+}
+
+// ---- blocked tier -------------------------------------------------------------------------------------------------------
+// expand: M = P_r unpacked and mirrored, identity beyond N (the padding of the blocked factorisation); xp = x_r
+__global__ __launch_bounds__(256) void ekf_smooth_expand_kernel(EkfSmoothBlocked a, int npad) {
+    const int N = a.rec.dims, i = blockIdx.x;
+    const double* __restrict__ xg = a.history + a.rec.off;
+    const double* __restrict__ pg = xg + N;
+    for (int j = threadIdx.x; j < npad; j += 256)
+        a.M[(int64_t)i * npad + j] = (i < N && j < N) ? pg[ekf_smooth_sym(N, i, j)] : (i == j ? 1.0 : 0.0);
+    if (i == 0)
+        for (int j = threadIdx.x; j < N; j += 256) a.xp[j] = xg[j];
+}
+
+// prepare: Q_eff on the diagonal, delta into the right-hand side (zero in the padding)
+__global__ __launch_bounds__(256) void ekf_smooth_prepare_kernel(EkfSmoothBlocked a, int npad) {
+    const int N = a.rec.dims, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= npad) return;
+    if (i < N) a.M[(int64_t)i * npad + i] += ekf_smooth_qdiag(i, a.next.q);
+    a.yv[i] = i < N ? ekf_smooth_residual(i, a.xs, a.xp) : 0.0;
+}
+
+// L^T y' = y over block columns of EKF_WIDE_BLOCK from the last: wave 0 solves the diagonal block with y in registers,
+// then every thread takes the block's contribution out of the rows above it (row j of L is contiguous: coalesced).
+// y lives in dynamic LDS [npad].  At the end w = F~^T y' (F formed again from x_r: the same function on the same input).
+__global__ __launch_bounds__(EKF_SMOOTH_THREADS) void ekf_smooth_backsub_kernel(EkfSmoothBlocked a, int npad) {
+    extern __shared__ double y[];
+    __shared__ double zs[EKF_WIDE_BLOCK];
+    __shared__ EkfMotionF F;
+    const int tid = threadIdx.x, lane = tid & 63, N = a.rec.dims;
+    if (a.status[0] != 0) return;
+    for (int i = tid; i < npad; i += EKF_SMOOTH_THREADS) y[i] = a.yv[i];
+    if (tid == 0 && a.next.moved) ekf_motion_form(a.history + a.rec.off, a.next.u, F);
+    __syncthreads();
+    for (int B = npad / EKF_WIDE_BLOCK - 1; B >= 0; --B) {
+        const int j0 = EKF_WIDE_BLOCK * B;
+        if (tid < 64) {
+            double v = y[j0 + lane];
+            for (int jj = EKF_WIDE_BLOCK - 1; jj >= 0; --jj) {
+                const double* lrow = a.M + (int64_t)(j0 + jj) * npad + j0;
+                if (lane == jj) v = v / lrow[jj];
+                const double zj = __shfl(v, jj);
+                if (lane < jj) v = __builtin_fma(-lrow[lane], zj, v);
+            }
+            y[j0 + lane] = v;
+            zs[lane] = v;
+        }
+        __syncthreads();
+        for (int i = tid; i < j0; i += EKF_SMOOTH_THREADS) {
+            double acc = y[i];
+            for (int jj = EKF_WIDE_BLOCK - 1; jj >= 0; --jj)
+                acc = __builtin_fma(-a.M[(int64_t)(j0 + jj) * npad + i], zs[jj], acc);
+            y[i] = acc;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double y10[EKF_CAM], w10[EKF_CAM];
+        for (int i = 0; i < EKF_CAM; ++i) y10[i] = y[i];
+        ekf_smooth_ft(F, a.next.moved, y10, w10);
+        for (int i = 0; i < EKF_CAM; ++i) a.wv[i] = w10[i];
+    }
+    for (int i = EKF_CAM + tid; i < N; i += EKF_SMOOTH_THREADS) a.wv[i] = y[i];
+}
+
+// c = P_r w (one ascending chain per row, P_r from the packed record), x^s_r = inject(x_r, c), the record's output rows
+__global__ __launch_bounds__(EKF_SMOOTH_THREADS) void ekf_smooth_finish_kernel(EkfSmoothBlocked a) {
+    __shared__ double c10[EKF_CAM], x10[EKF_CAM];
+    const int tid = threadIdx.x, N = a.rec.dims;
+    if (a.status[0] != 0) return;
+    const double* __restrict__ xg = a.history + a.rec.off;
+    const double* __restrict__ pg = xg + N;
+    for (int i = tid; i < N; i += EKF_SMOOTH_THREADS) {
+        double c = 0.0;
+        for (int j = 0; j < N; ++j) c = __builtin_fma(pg[ekf_smooth_sym(N, i, j)], a.wv[j], c);
+        a.cv[i] = c;
+        if (i < EKF_CAM) c10[i] = c;
+        if (i < 3) x10[i] = ekf_smooth_inject_add(xg[i], c);
+        if (i >= EKF_CAM) a.xs[i] = ekf_smooth_inject_add(xg[i], c);
+    }
+    __syncthreads();
+    if (tid == 0) ekf_smooth_inject_camera(xg, c10 + 7, x10);
+    __syncthreads();
+    if (tid < EKF_CAM) a.xs[tid] = x10[tid];
+    for (int e = tid; e < 7 * (a.rec.frame1 - a.rec.frame0); e += EKF_SMOOTH_THREADS)
+        a.smoothed[(int64_t)7 * a.rec.frame0 + e] = x10[e % 7];
+}
+
+}  // namespace
+
+void ekf_launch_history_pack(const double* cov, int64_t ld, const double* state, int32_t dims, double* record, hipStream_t s) {
+    hipLaunchKernelGGL(ekf_history_pack_kernel, dim3(dims), dim3(256), 0, s, cov, ld, state, dims, record);
+}
+
+void ekf_launch_smooth_rows(const double* src, double* smoothed, int32_t f0, int32_t f1, hipStream_t s) {
+    if (f1 <= f0) return;
+    hipLaunchKernelGGL(ekf_smooth_rows_kernel, dim3((7 * (f1 - f0) + 63) / 64), dim3(64), 0, s, src, smoothed, f0, f1);
+}
+
+hipError_t ekf_launch_smooth_resident(const double* history, const EkfSmoothRec* table_dev, int32_t records, int32_t nmax,
+                                      int32_t lead_frames, double* smoothed, int32_t* status, hipStream_t s) {
+    const size_t lds = (size_t)ekf_smooth_tri_count(nmax) * 8;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ekf_smooth_resident_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ekf_smooth_resident_kernel, dim3(1), dim3(EKF_SMOOTH_THREADS), lds, s, history, table_dev, records,
+                       lead_frames, smoothed, status);
+    return hipSuccess;
+}
+
+void ekf_launch_smooth_blocked_step(const EkfSmoothBlocked& a, hipStream_t s) {
+    const int N = a.rec.dims, npad = (N + EKF_WIDE_BLOCK - 1) / EKF_WIDE_BLOCK * EKF_WIDE_BLOCK;
+    hipLaunchKernelGGL(ekf_smooth_expand_kernel, dim3(npad), dim3(256), 0, s, a, npad);
+    if (a.next.moved) {      // the filter's own move on (M, xp): P_p before Q, x_p
+        EkfMotionArgs m{};
+        m.cov = a.M;
+        m.ld = npad;
+        m.state = a.xp;
+        m.dims = N;
+        for (int i = 0; i < 6; ++i) m.u[i] = a.next.u[i];
+        m.status = a.status;
+        ekf_launch_motion<double>(m, s);
+    }
+    hipLaunchKernelGGL(ekf_smooth_prepare_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, a, npad);
+    // the blocked Cholesky of the wide frames with no columns of A: L over M, y = L^-1 delta over the right-hand side
+    EkfFrame fr{};
+    fr.lmat = a.M;
+    fr.ldl = npad;
+    fr.yvec = a.yv;
+    fr.ncols = 0;
+    fr.status = a.status;
+    ekf_launch_wide_factor(fr, nullptr, a.xinv, npad, s);
+    hipLaunchKernelGGL(ekf_smooth_backsub_kernel, dim3(1), dim3(EKF_SMOOTH_THREADS), (size_t)npad * 8, s, a, npad);
+    hipLaunchKernelGGL(ekf_smooth_finish_kernel, dim3(1), dim3(EKF_SMOOTH_THREADS), 0, s, a);
+}

@@ -452,6 +452,11 @@ class BaseFilter:
         filter built with ``motion=True``); such a replay runs its frames in serial order.
         On a frozen map (``freeze_map``) detections of ids the map does not hold are dropped (``last_ignored``; their d2 is
         NaN), nothing is added, and the replay runs its frames in serial order."""
+        return self._replay_detection_log(ids, poses, offsets, has_detections, mahal, noise, scale, motion, False)
+
+    def _replay_detection_log(self, ids, poses, offsets, has_detections, mahal, noise, scale, motion, smooth):
+        """``process_detection_log``; ``smooth``: the replay is recorded (``observe_log(history=)``), the backward pass runs
+        over the records, and the smoothed trajectory comes back behind the filtered one (``EKF.smooth_detection_log``)."""
         import torch
         backend = self.backend
         plan = plan_detection_log(self.landmarks, self.num_landmarks, ids, offsets, has_detections, self.map_frozen)
@@ -487,7 +492,9 @@ class BaseFilter:
             backend.grow(new_max_visible=min(backend.MAX_VISIBLE_LIMIT[backend.lm_dims], plan.widest))
         traj = torch.empty((plan.offsets.shape[0] - 1, 7), dtype=torch.float64, device=backend.device)
         mahal_t = torch.empty((plan.index.shape[0],), dtype=torch.float64, device=backend.device) if mahal else None
-        backend.observe_log(plan.index, plan.offsets, poses, traj, mahal_t, rows, scale, motion)
+        history = backend.new_history(plan.index, plan.offsets) if smooth else None
+        backend.observe_log(plan.index, plan.offsets, poses, traj, mahal_t, rows, scale, motion,
+                            **({"history": history} if smooth else {}))
         backend.sync()
         if motion is not None and motion.any():
             self._moved = True
@@ -496,11 +503,15 @@ class BaseFilter:
         self.num_landmarks = plan.num_landmarks
         if self._tentative is not None:      # (confirm=: the policy sees per-frame calls only; what a replay adds stays)
             self._tentative.confirm(plan.new_landmarks)
-        if not mahal:
-            return traj.cpu().numpy()
-        d2 = np.full(plan.keep.shape[0], np.nan)
-        d2[plan.keep] = mahal_t.cpu().numpy()
-        return traj.cpu().numpy(), d2
+        out = (traj.cpu().numpy(),)
+        if smooth:
+            self._smoothed = backend.smooth_history(history, traj.shape[0]).cpu().numpy()
+            out += (self._smoothed,)
+        if mahal:
+            d2 = np.full(plan.keep.shape[0], np.nan)
+            d2[plan.keep] = mahal_t.cpu().numpy()
+            out += (d2,)
+        return out[0] if len(out) == 1 else out
 
     def save_map(self, filename: str) -> None:
         """Map text format of base_filter.py:214-247: three comment lines and a

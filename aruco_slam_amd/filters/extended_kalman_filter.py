@@ -173,6 +173,36 @@ class EKF(BaseFilter):
     def get_lm_estimates(self):
         return self.landmarks.items()
 
+    # -- offline smoothing (the reference's run_offline.py flow) ------
+    def smooth_detection_log(self, ids, poses, offsets, has_detections=None, noise=None, scale=None, motion=None,
+                             mahal=False):
+        """``process_detection_log`` with a Rauch-Tung-Striebel backward pass behind it: the replay is recorded on the
+        device, the pass runs over the records, and ``(filtered [F, 7], smoothed [F, 7])`` come back (plus ``d2 [D]`` with
+        ``mahal=True``).  The log is planned, the buffers grow and everything is validated as in ``process_detection_log``,
+        and the filter is left exactly where that call leaves it, bit for bit.  The smoothed log stays with the filter:
+        ``get_cam_estimate(i)`` returns its row i.  Needs ``quat_update="scalar_first"`` and the float64 covariance; a
+        frozen map is refused (``ValueError``, before anything runs)."""
+        from ..hip_backend import EKF_COV_F64, EKF_QUAT_SCALAR_FIRST
+        backend = self.backend
+        if backend.cfg.quat_mode != EKF_QUAT_SCALAR_FIRST:
+            raise ValueError('smoothing needs quat_update="scalar_first": the as-written injection has no inverse')
+        if backend.cfg.cov_dtype != EKF_COV_F64:
+            raise ValueError('smoothing needs cov_dtype="float64"')
+        if self.map_frozen:
+            raise ValueError("smoothing a frozen map is not supported: unfreeze_map() first")
+        return self._replay_detection_log(ids, poses, offsets, has_detections, mahal, noise, scale, motion, True)
+
+    def get_cam_estimate(self, iteration: int):
+        """Row ``iteration`` of the last smoothed log as ``process_detections(should_filter=False, iteration=i)`` expects
+        it: ``[xyz, q, 0, 0, 0]``.  ``IndexError`` outside the log; ``NotImplementedError`` when nothing has been smoothed."""
+        smoothed = getattr(self, "_smoothed", None)
+        if smoothed is None:
+            return super().get_cam_estimate(iteration)
+        i = int(iteration)
+        if not 0 <= i < smoothed.shape[0]:
+            raise IndexError(f"frame {iteration} is outside the smoothed log of {smoothed.shape[0]} frames")
+        return np.concatenate((smoothed[i], np.zeros(3)))
+
     # -- extras: resident-detection batch entry, used by bench / replay --------
     @property
     def backend(self) -> HipEkf:

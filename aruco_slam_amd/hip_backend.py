@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = (
     "ekf_batch_observe_logs_moved",
     "ekf_set_map_frozen", "ekf_get_map_frozen",
     "ekf_batch_set_map_frozen", "ekf_batch_get_map_frozen",
+    "ekf_observe_log_recorded", "ekf_history_record_bytes", "ekf_history_bytes", "ekf_history_info", "ekf_history_record",
+    "ekf_smooth_workspace_bytes", "ekf_smooth_history",
 )
 
 
@@ -152,6 +154,14 @@ def load_library(path: str | Path | None = None):
         "ekf_get_map_frozen": [vp],
         "ekf_batch_set_map_frozen": [vp, ip],
         "ekf_batch_get_map_frozen": [vp, ip],
+        "ekf_observe_log_recorded": [vp, ip, C.POINTER(C.c_int64), C.c_int32, vp, vp, dp, dp, vp, C.c_size_t, vp, vp, vp,
+                                     C.c_size_t],
+        "ekf_history_record_bytes": [C.c_int32, C.POINTER(C.c_size_t)],
+        "ekf_history_bytes": [vp, ip, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_size_t)],
+        "ekf_history_info": [vp, ip, C.c_int32, ip, ip, dp, dp, ip, ip],
+        "ekf_history_record": [vp, vp, C.c_int32, dp, dp, C.c_int32],
+        "ekf_smooth_workspace_bytes": [vp, C.POINTER(C.c_size_t)],
+        "ekf_smooth_history": [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int32, vp],
         "ekf_remove_workspace_bytes": [vp, C.c_int32, C.POINTER(C.c_size_t)],
         "ekf_remove_markers": [vp, ip, C.c_int32, vp, C.c_int64, vp, vp, C.c_size_t],
         "ekf_batch_remove_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],
@@ -355,7 +365,8 @@ class HipEkf:
                                                   wb.value))
         self.cfg = cfg
         self._map_frozen = False      # (off after ekf_create)
-        self.gate = None       # None: built without the gate; inf: off
+        self._history_frames = 0      # frames of the last recorded replay (observe_log(history=))
+        self.gate = None      # None: built without the gate; inf: off
         if gate is not None:
             self.set_gate(gate)
 
@@ -647,7 +658,7 @@ class HipEkf:
             self.h, idx_t.data_ptr(), z_t.data_ptr(), m, frames,
             traj_t.data_ptr() if traj_t is not None else None))
 
-    def observe_log(self, lm_index, offsets, poses, traj=None, mahal=None, rows=None, scale=None, motion=None):
+    def observe_log(self, lm_index, offsets, poses, traj=None, mahal=None, rows=None, scale=None, motion=None, history=None):
         """A whole detection log in one call (ekf_observe_log): lm_index int [D] landmark index of every detection (first
         sightings numbered n, n+1, ... in order of first occurrence), offsets int [F+1], poses [D,6] ``[tvec | rvec]`` as a
         NumPy array (uploaded once) or a contiguous float64 device tensor on this filter's device; traj: float64 device
@@ -656,7 +667,9 @@ class HipEkf:
         variances, indexed like lm_index (NumPy, validated and uploaded; a filter built with ``row_noise=True``), or None;
         scale: [F] numbers >= 0, one per frame, empty frames included (a filter built with ``frame_scale=True``;
         ekf_observe_log_scaled), or None; motion: [F, 6] camera motions, one per frame, empty frames included (a filter
-        built with ``motion=True``; ekf_observe_log_moved: serial order), or None.
+        built with ``motion=True``; ekf_observe_log_moved: serial order), or None; history: a uint8 device tensor of at
+        least ``history_bytes(lm_index, offsets)`` bytes that receives the records of the call (ekf_observe_log_recorded:
+        serial order, the same bits; ``smooth_history`` runs the backward pass over it), or None.
         Capacity must already suffice (grow() first)."""
         torch = self._torch
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
@@ -702,18 +715,75 @@ class HipEkf:
             if mahal is not None:
                 mahal.record_stream(self.stream)
             rows_t = torch.from_numpy(rows).to(self.device, non_blocking=False) if rows is not None else None
-            self._check(self.lib.ekf_observe_log_moved(
-                self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), frames,
-                poses_t.data_ptr() if idx.shape[0] else None,
-                rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None,
-                _dptr(scale) if scale is not None and frames else None,
-                _dptr(motion) if motion is not None and frames else None, ws.data_ptr(), nbytes.value,
-                traj.data_ptr() if traj is not None else None,
-                mahal.data_ptr() if mahal is not None and idx.shape[0] else None))
+            args = (self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), frames,
+                    poses_t.data_ptr() if idx.shape[0] else None,
+                    rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None,
+                    _dptr(scale) if scale is not None and frames else None,
+                    _dptr(motion) if motion is not None and frames else None, ws.data_ptr(), nbytes.value,
+                    traj.data_ptr() if traj is not None else None,
+                    mahal.data_ptr() if mahal is not None and idx.shape[0] else None)
+            if history is None:
+                self._check(self.lib.ekf_observe_log_moved(*args))
+            else:
+                assert history.is_cuda and history.dtype == torch.uint8 and history.is_contiguous()
+                history.record_stream(self.stream)
+                self._check(self.lib.ekf_observe_log_recorded(*args, history.data_ptr(), history.numel()))
+                self._history_frames = frames
         self._log_keep = (poses_t, ws, rows_t)     # (released by the next call; record_stream already guards the allocator)
         m = np.diff(offs)
         if m.size and m.max() > 0:
             self._last_m = int(m[m > 0][-1])
+
+    # -- offline smoothing (include/ekf_slam_hip.h, "Offline smoothing") --------------------------------------------------
+    def history_bytes(self, lm_index, offsets) -> int:
+        """Upper bound of the history a recorded replay of this log needs, from the log alone (ekf_history_bytes)."""
+        idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        out = C.c_size_t()
+        self._check(self.lib.ekf_history_bytes(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               offs.ctypes.data_as(C.POINTER(C.c_int64)), offs.shape[0] - 1, C.byref(out)))
+        return out.value
+
+    def new_history(self, lm_index, offsets):
+        """A uint8 device tensor of ``history_bytes`` bytes, allocated on the filter's stream."""
+        torch = self._torch
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            return torch.empty((self.history_bytes(lm_index, offsets),), dtype=torch.uint8, device=self.device)
+
+    def history_info(self) -> dict:
+        """The table of the last recorded replay (ekf_history_info): {"frame", "dims", "s_eff", "motion" [R, 6], "stepped"}
+        per record and "frame_record" [F] (-1: before the first record)."""
+        count = C.c_int32()
+        self._check(self.lib.ekf_history_info(self.h, C.byref(count), 0, None, None, None, None, None, None))
+        r = count.value
+        frame, dims, stepped = (np.zeros(max(r, 1), dtype=np.int32) for _ in range(3))
+        s_eff, motion = np.zeros(max(r, 1)), np.zeros((max(r, 1), 6))
+        frec = np.zeros(max(self._history_frames, 1), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.ekf_history_info(self.h, C.byref(count), max(r, 1), frame.ctypes.data_as(ip), dims.ctypes.data_as(ip),
+                                              _dptr(s_eff), _dptr(motion), stepped.ctypes.data_as(ip), frec.ctypes.data_as(ip)))
+        return {"frame": frame[:r], "dims": dims[:r], "s_eff": s_eff[:r], "motion": motion[:r], "stepped": stepped[:r].astype(bool),
+                "frame_record": frec[:self._history_frames]}
+
+    def history_record(self, history, r: int, dims: int):
+        """(state [dims], P [dims, dims]) of record r, unpacked and mirrored (ekf_history_record)."""
+        state, cov = np.empty(dims), np.empty((dims, dims))
+        self._check(self.lib.ekf_history_record(self.h, history.data_ptr(), int(r), _dptr(state), _dptr(cov), int(dims)))
+        return state, cov
+
+    def smooth_history(self, history, frames: int, blocked: bool = False):
+        """The backward pass over the last recorded replay (ekf_smooth_history): a float64 device tensor [frames, 7] of
+        smoothed poses.  ``blocked``: force the blocked tier (flags bit 0).  Waits for the filter's stream."""
+        torch = self._torch
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_smooth_workspace_bytes(self.h, C.byref(nbytes)))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
+            out = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
+            history.record_stream(self.stream)
+            self._check(self.lib.ekf_smooth_history(self.h, history.data_ptr(), history.numel(), ws.data_ptr(), nbytes.value,
+                                                    int(bool(blocked)), out.data_ptr() if frames else None))
+        return out
 
     LOG_STATS = ("frames_stepped", "frames_pipelined", "pipelined_runs", "markers_added")
 

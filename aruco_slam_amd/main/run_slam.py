@@ -27,6 +27,11 @@ pending for the next one, so a gated filter finds its way back after a detection
 ``--map FILE`` starts from a map written earlier (the reference's ``LOAD_MAP`` / ``MAP_FILE``), with or without
 ``--resident``; ``--localize`` freezes it: the camera is tracked in the map as it is, markers the map does not hold are
 ignored, and the ``map.txt`` written at exit is the one that was loaded.
+
+    python -m aruco_slam_amd.main.run_slam --detections replay.npz --resident --smooth
+
+``--smooth`` is the offline mode (the reference's ``main/run_offline.py``): the replay is recorded on the device, a backward
+pass runs over it, and ``trajectory.txt`` carries for every frame the pose that the whole log supports.
 """
 from __future__ import annotations
 
@@ -101,10 +106,12 @@ def frame_scales(path: str, frame_period_ms: float) -> np.ndarray:
     return np.concatenate((np.ones(min(1, stamps.shape[0])), steps / period))
 
 
-def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryWriter, scales=None, motion=None) -> None:
+def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryWriter, scales=None, motion=None,
+                    smooth: bool = False) -> None:
     """The whole replay file through ``process_detection_log``, then one trajectory line per frame.  Frames before the first
     stepped one carry the camera pose the filter had before the call (the integer initial pose of a fresh filter), as the
-    frame-by-frame loop writes them; from the first frame with a motion on, the row is the (moved) pose of the device."""
+    frame-by-frame loop writes them; from the first frame with a motion on, the row is the (moved) pose of the device.
+    ``smooth``: the replay goes through ``smooth_detection_log`` and the lines carry the smoothed poses."""
     det = np.load(path, allow_pickle=False)
     offsets, has = det["offsets"], det["has_detections"].astype(bool)
     start_pose = tracker.get_poses()[0]
@@ -114,7 +121,10 @@ def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryW
         extra["scale"] = scales
     if motion is not None:
         extra["motion"] = motion
-    traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has, **extra)
+    if smooth:
+        _filtered, traj = tracker.smooth_detection_log(det["ids"], det["poses"], offsets, has, **extra)
+    else:
+        traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has, **extra)
     stepped = has & (np.diff(offsets) > 0)
     if motion is not None:
         stepped = stepped | motion.any(axis=1)
@@ -129,6 +139,15 @@ def main(cmdline_args: argparse.Namespace) -> None:
     map_file = getattr(cmdline_args, "map", None)
     if getattr(cmdline_args, "localize", False) and map_file is None:
         raise ValueError("--localize tracks the camera in an existing map: pass --map <map.txt>")
+    smooth = getattr(cmdline_args, "smooth", False)
+    if smooth:
+        if not (getattr(cmdline_args, "resident", False) and cmdline_args.detections):
+            raise ValueError("--smooth runs a backward pass over a recorded replay: pass --detections <replay.npz> --resident")
+        if getattr(cmdline_args, "localize", False):
+            raise ValueError("--smooth does not go with --localize: a frozen map is not smoothed")
+        if cmdline_args.filter != "ekf":
+            raise ValueError("--smooth is implemented for --filter ekf")
+        kwargs.setdefault("quat_update", "scalar_first")      # (the as-written injection has no inverse)
     if getattr(cmdline_args, "gate", None) is not None:
         kwargs["gate"] = cmdline_args.gate      # (acts in the frame loop and in the resident replay alike)
     if getattr(cmdline_args, "confirm", None) is not None:
@@ -160,7 +179,7 @@ def main(cmdline_args: argparse.Namespace) -> None:
         raise ValueError("--resident replays a detections file: pass --detections <replay.npz>")
     with TrajectoryWriter(str(out_dir / "trajectory.txt")) as cam_traj_writer:
         if resident:
-            replay_resident(tracker, cmdline_args.detections, cam_traj_writer, scales, motion)
+            replay_resident(tracker, cmdline_args.detections, cam_traj_writer, scales, motion, smooth)
         elif cmdline_args.detections:
             offs = np.load(cmdline_args.detections, allow_pickle=False)["offsets"]
             for f, (timestamp, ids, poses) in enumerate(detection_frames(cmdline_args.detections)):
@@ -222,6 +241,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--localize", action="store_true",
                         help="with --map: freeze the map and only track the camera in it; markers that are not in the map "
                              "are ignored and the map is written back unchanged")
+    parser.add_argument("--smooth", action="store_true",
+                        help="with --detections --resident: write the smoothed trajectory (a Rauch-Tung-Striebel backward "
+                             "pass over the recorded replay: every pose uses the whole log; the filter runs with the "
+                             "scalar-first quaternion update)")
     return parser
 
 

@@ -824,6 +824,71 @@ int ekf_get_map_frozen(const ekf_filter *f);
 int ekf_batch_set_map_frozen(ekf_batch *b, const int32_t *frozen /* [B] HOST, or NULL: none */);
 int ekf_batch_get_map_frozen(const ekf_batch *b, int32_t *out /* [B] */);
 
+/* ---- Offline smoothing: a Rauch-Tung-Striebel backward pass over a recorded log replay.  A recorded replay
+ * keeps, on the device, the filter as it was right after every frame that changed it; the backward pass turns those records
+ * into the trajectory that ALL the data supports.  Only the smoothed state is formed -- no smoothed covariance.
+ *
+ * The smoothing rules.
+ *   A RECORD r holds the state x_r (N_r doubles) and P_r right after a frame that changed the filter: a frame that was
+ *   stepped, or moved by a non-zero motion, or both.  The TRANSITION into record r+1 is what that frame did before its
+ *   update: (1) the move u_{r+1} (possibly zero), (2) the first sightings, appended with a block-diagonal P (uncorrelated
+ *   with the old dims), (3) the predict with Q_eff = fl(s_eff q) if the frame was stepped (s_eff = 0 if it was only moved).
+ *   Backward step for r = R-2 .. 0, x^s_{R-1} = x_{R-1}, N = N_r (the dims a later frame added are dropped, which is exact
+ *   under the block-diagonal augmentation):
+ *     prediction   x_p = move(x_r, u_{r+1}) (x_p = x_r for a zero motion); P_p = F~ P_r F~^T + diag(Q_eff), F~ of the motion
+ *                  rules above (rows and columns 0 .. 9 only); Q_eff is 0 on the quaternion dims 3 .. 6.
+ *     residual     delta[0:3] = x^s_{r+1}[0:3] - x_p[0:3], delta[10:N] likewise, delta[3:7] = 0 (the filter never applies an
+ *                  additive quaternion correction), delta[7:10] = 2 vec(dq) / dq_w with dq = q^s_{r+1} (x) q_p^-1: the exact
+ *                  inverse of the scalar-first injection q <- normalise((1, e/2) (x) q).
+ *     solve        y = P_p^-1 delta by a Cholesky factorisation in f64 and the two substitutions; c = P_r F~^T y.
+ *     inject       x^s_r = inject(x_r, c) with the filter's own injection: additive on 0 .. 2 and 10 .. N-1, c[3:7] dropped,
+ *                  the quaternion rule on c[7:10], the error dims stay 0.
+ *     output       frame t of the log gets x^s[0:7] of the last record at or before t; frames before the first record repeat
+ *                  the camera state at the start of the recorded call, as the filtered trajectory does.
+ *   Every sum is one ascending fma chain: two runs over the same history give the same bits.
+ * Supported: EKF_MODEL_EKF with EKF_COV_F64 and EKF_QUAT_SCALAR_FIRST; mapping logs with any mix of gate, per-detection
+ * noise, frame scale and motion.  REFUSED with EKF_ERR_STATE before anything is enqueued: EKF_QUAT_AS_WRITTEN (the
+ * as-written injection reads scalar-first arrays as scalar-last and writes scalar-first: it is not a group action and has
+ * no inverse), the f32 covariance, EKF_MODEL_ROTATIONS, a frozen map, and a filter that ekf_remove_markers (or ekf_reset)
+ * touched between the recording and the smoothing.
+ *
+ * Recording.  ekf_observe_log_recorded takes the arguments of ekf_observe_log_moved plus the history buffer.  It runs the
+ * frame-by-frame serial replay (ekf_last_sequence_mode: 1) and enqueues, behind every frame that changed the filter, ONE
+ * pack launch that copies state[0:N] and the lower triangle of P -- packed column by column, f64 -- into the next record
+ * (256-byte aligned).  Bit rule: trajectory, final state, final P, d^2 and ekf_last_log_stats are bit for bit those of the
+ * same call through ekf_observe_log_moved / ekf_observe_log_gated: recording only reads.  The handle keeps the table of the
+ * call on the host (per record: frame, N_r, offset, s_eff, motion; per frame: its record).
+ *   history layout  [256 B: state[0:7] at the start of the call | record 0 | record 1 | ...], record = [state N | triangle
+ *                   N (N + 1) / 2] doubles, rounded up to 256 bytes (ekf_history_record_bytes)
+ *   ekf_history_bytes   an upper bound from the log alone: the header and one record per frame at the dims that frame
+ *                       ends with (the log is checked as ekf_observe_log checks it)
+ *   ekf_history_info    *records = R and, where the arrays are not NULL (capacity >= R entries each): per record the frame,
+ *                       N_r, s_eff (0: only moved), the motion [6] and whether it was stepped; frame_record [frames]: the
+ *                       record of every frame (-1: before the first).  Host getter.
+ *   ekf_history_record  record r unpacked and mirrored: state_out [dims], cov_out [dims][dims] (either may be NULL); waits
+ *                       for the handle's stream.  Host getter.
+ *
+ * The backward pass.  ekf_smooth_history runs on the handle's stream, over the handle's LAST recorded call and that buffer
+ * (anything else: EKF_ERR_STATE), and writes smoothed_dev [frames][7].  It never writes the filter: state and P keep their
+ * bits, and its status word is its own -- a P_p that is not positive definite returns EKF_ERR_NUMERIC and leaves no sticky
+ * error on the filter.  It waits for the stream before it returns.  Two tiers, chosen per call by the largest record:
+ *   resident   every N_r <= 160 (n <= 50): ONE launch of ONE workgroup runs the whole pass, P_p as a packed triangle in LDS
+ *   blocked    any larger N_r (up to 8064 dims), or flags bit 0: per step a short launch sequence around the blocked f64
+ *              Cholesky of the wide frames
+ * Not in this interface: recording from per-frame ekf_observe calls, smoothed covariances, ekf_batch. */
+int ekf_observe_log_recorded(ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames,
+                             const double *poses_dev, const double *rows_dev, const double *scale, const double *motion,
+                             void *log_ws, size_t log_ws_bytes, double *trajectory_dev, double *mahal_dev,
+                             void *history_dev, size_t history_bytes);
+int ekf_history_record_bytes(int32_t dims, size_t *bytes);
+int ekf_history_bytes(const ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames, size_t *bytes);
+int ekf_history_info(const ekf_filter *f, int32_t *records, int32_t capacity, int32_t *frame, int32_t *dims, double *s_eff,
+                     double *motion /* [capacity][6] */, int32_t *stepped, int32_t *frame_record /* [frames] */);
+int ekf_history_record(ekf_filter *f, const void *history_dev, int32_t r, double *state_out, double *cov_out, int32_t dims);
+int ekf_smooth_workspace_bytes(const ekf_filter *f, size_t *bytes);
+int ekf_smooth_history(ekf_filter *f, const void *history_dev, size_t history_bytes, void *ws, size_t ws_bytes, int32_t flags,
+                       double *smoothed_dev /* [frames][7] */);
+
 const char *ekf_last_error_string(void);
 
 #ifdef __cplusplus

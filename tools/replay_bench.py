@@ -19,6 +19,10 @@ updates/s is steady frames per second of the steady segment; the bootstrap segme
                                                    # map (camera-strip update) and, on a second filter of the same build, as
                                                    # mapping frames in serial order: us per frame of both, and the kernel's own
                                                    # time from the covariance update's timing slot
+    python tools/replay_bench.py --smooth          # offline smoothing: for n = 10, 50 (resident tier) and 51, 338 (blocked tier)
+                                                   # the backward pass in us per record, next to the plain by-frame replay
+                                                   # and the recorded replay of the same log on the same build (us per
+                                                   # frame); writes profiles/smooth/summary.json
 """
 from __future__ import annotations
 
@@ -78,6 +82,59 @@ def _frozen_vs_mapping(args, log, boot, frames, seg_noise, emit):
          cov_update_kernel_us=out["mapping_serial"]["cov_slot_us"], detail=out)
 
 
+def _smooth_bench(args):
+    """--smooth: per map size a mapping log (float64, scalar-first) replayed by frame without and with recording, then the
+    backward pass (HipEkf.smooth_history).  The plain by-frame replay is the call with all-zero motions: they enqueue nothing
+    and select the serial frame loop the recorded call runs.  One untimed round, then `reps` timed ones on a reset filter;
+    median and range."""
+    import torch
+    from aruco_slam_amd.filters.extended_kalman_filter import EKF
+    from aruco_slam_amd.synthetic import ragged_log
+    rows = []
+    for n, tier in ((10, "resident"), (50, "resident"), (51, "blocked"), (338, "blocked")):
+        m = (min(4, n), min(12, n))
+        log = ragged_log(n, m, args.steady, seed=args.seed)
+        frames = len(log["has_detections"])
+        zero = np.zeros((frames, 6))
+        flt = EKF(INIT, max_landmarks=n, max_visible=m[1], cov_dtype="float64", quat_update="scalar_first", motion=True)
+        b = flt.backend
+        plan_args = (log["ids"], log["poses"], log["offsets"], log["has_detections"])
+        t_plain, t_rec, t_smooth, records = [], [], [], 0
+        for rep in range(args.reps + 1):
+            flt.reset()
+            t = time.perf_counter()
+            flt.process_detection_log(*plan_args, motion=zero)
+            t_plain.append(time.perf_counter() - t)
+            flt.reset()
+            from aruco_slam_amd.filters.base_filter import plan_detection_log
+            plan = plan_detection_log(flt.landmarks, flt.num_landmarks, log["ids"], log["offsets"], log["has_detections"])
+            history = b.new_history(plan.index, plan.offsets)
+            traj = torch.empty((frames, 7), dtype=torch.float64, device=b.device)
+            torch.cuda.synchronize(b.device)
+            t = time.perf_counter()
+            b.observe_log(plan.index, plan.offsets, log["poses"], traj, motion=zero, history=history)
+            b.sync()
+            t_rec.append(time.perf_counter() - t)
+            records = len(b.history_info()["frame"])
+            t = time.perf_counter()
+            b.smooth_history(history, frames)
+            t_smooth.append(time.perf_counter() - t)
+            del history
+        def stat(v, per):
+            v = 1e6 * np.array(v[1:]) / per
+            return {"median_us": float(np.median(v)), "min_us": float(v.min()), "max_us": float(v.max())}
+        row = {"n": n, "dims": 3 * n + 10, "tier": tier, "frames": frames, "records": records, "m_range": list(m),
+               "reps": args.reps, "history_bytes_per_record": 8 * ((3 * n + 10) + (3 * n + 10) * (3 * n + 11) // 2),
+               "smooth_per_record": stat(t_smooth, records), "plain_by_frame_per_frame": stat(t_plain, frames),
+               "recorded_per_frame": stat(t_rec, frames)}
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del flt, b
+    out = Path(__file__).resolve().parent.parent / "profiles" / "smooth"
+    out.mkdir(parents=True, exist_ok=True)
+    (out / "summary.json").write_text(json.dumps({"steady_frames": args.steady, "rows": rows}, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--n", type=int, default=1024)
@@ -92,7 +149,13 @@ def main():
     ap.add_argument("--motion", action="store_true", help="a camera motion on every frame (motion=)")
     ap.add_argument("--frozen", action="store_true",
                     help="replay the steady segment on a frozen map and as mapping frames in serial order, instead of the variants")
+    ap.add_argument("--smooth", action="store_true",
+                    help="offline smoothing: backward pass per record vs by-frame replay per frame, four map sizes")
+    ap.add_argument("--reps", type=int, default=5, help="--smooth: timed rounds (after one untimed)")
     args = ap.parse_args()
+    if args.smooth:
+        _smooth_bench(args)
+        return
     import torch
     from aruco_slam_amd.synthetic import SyntheticStream, ragged_log
 

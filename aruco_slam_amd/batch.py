@@ -37,6 +37,12 @@ member the single filter's localisation mode (``BaseFilter.freeze_map``; "Locali
 ``include/ekf_slam_hip.h``).  A frozen member updates its camera, P_cc and the cross-covariances and leaves its landmarks and
 P_ll alone; its frames cost the 10 x N camera strip of P instead of the N x N sweep.  Frozen and mapping members run side by
 side in one call.  Detections of ids a frozen member's map does not hold are dropped and reported in ``last_ignored``.
+
+Offline studies ask for the trajectory that a whole log supports: ``smooth_detection_logs`` replays the logs recorded --
+the window kernel packs every member behind each frame that changed it -- and runs one Rauch-Tung-Striebel backward pass per
+member, one workgroup each ("Batch smoothing" in ``include/ekf_slam_hip.h``; ``EKF.smooth_detection_log`` per member, in one
+call).  ``smooth_replicas`` does the same for Monte-Carlo replicas of one log, ``history_records`` returns what was recorded.
+``model="ekf"`` with ``quat_update="scalar_first"``, at most 50 landmarks per member, without ``large_maps`` / ``wide_frames``.
 """
 from __future__ import annotations
 
@@ -363,6 +369,9 @@ class EKFBatch:
     last_ignored = ()
     _frozen = None     # [B] bool mirror of the handle's "map frozen" flags as this object set them, or None: none is frozen
     camera = None      # (camera matrix [9], distortion coefficients, marker size) of corner logs, or None (set_camera)
+    last_history = None          # uint8 device tensor: the history of the last recorded call (smooth_detection_logs), or None
+    _history_frames = None       # [B + 1]: member_frames of that call
+    last_smooth_status = None    # [B] int32 of the last backward pass: 0, or EKF_ERR_NUMERIC (smooth_history)
 
     def __init__(self, members: int, initial_camera_pose, *, max_landmarks: int = 50, max_visible: int = 16,
                  quat_update: str | None = None, noise=None, device: str = "cuda:0", model: str = "ekf",
@@ -528,7 +537,8 @@ class EKFBatch:
         return b
 
     # -- replay ------------------------------------------------------------------------------------------------------
-    def process_detection_logs(self, logs, *, nis: bool = False, cam_cov: bool = False, mahal: bool = False):
+    def process_detection_logs(self, logs, *, nis: bool = False, cam_cov: bool = False, mahal: bool = False,
+                               record: bool = False):
         """One log per member (``None``: no log), each a dict of the replay layout ``ids [D]``, ``poses [D,6]``,
         ``offsets [F+1]`` and optionally ``has_detections [F]``.  After ``set_camera`` a log may carry ``corners [D,4,2]``
         (pixels) instead of ``poses``: the corner logs of a call are estimated by one ``ekf_estimate_poses_device`` launch on
@@ -626,6 +636,8 @@ class EKFBatch:
             with_rows["scale"] = np.concatenate(scales)
         if motions:
             with_rows["motion"] = np.concatenate(motions)
+        if record:      # (the recorded call: the same outputs, and the history in last_history)
+            with_rows["record"] = True
         if gated:
             traj, nis_v, cov_v, mahal_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses,
                                                                nis=nis, cam_cov=cam_cov, mahal=True, **with_rows)
@@ -832,8 +844,96 @@ class EKFBatch:
         return CornerReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, dof,
                                    cov_t.cpu().numpy() if cam_cov else None, full, rej, flipped)
 
+    # -- offline smoothing ---------------------------------------------------------------------------------------------
+    def smooth_detection_logs(self, logs, *, mahal: bool = False):
+        """``process_detection_logs(logs)`` recorded, then one Rauch-Tung-Striebel backward pass per member on the device
+        ("Batch smoothing" in ``include/ekf_slam_hip.h``): returns ``(filtered, smoothed)``, per-member lists of
+        ``(F_b, 7)``.  ``filtered`` has the bits of ``process_detection_logs`` and the batch is left where that call
+        leaves it; ``smoothed[b][t]`` is the camera pose of frame t that ALL of member b's data supports.  The logs may carry
+        what ``process_detection_logs`` takes (noise, scale, motion, corners after ``set_camera``, ``None`` members).  With
+        ``mahal`` or a gate set a third value ``(mahal, rejected)`` follows, the per-member lists of ``GatedBatchReplay``.
+        A member that failed in the replay has NaN rows from its failing frame on; ``last_smooth_status[b]`` is
+        EKF_ERR_NUMERIC (-5) for a member whose backward pass met a covariance that is not positive definite (all its rows
+        NaN), else 0.  A batch of ``model="ekf"``, ``quat_update="scalar_first"``, without ``large_maps`` / ``wide_frames``,
+        mapping members of at most 50 landmarks; anything else raises ``EkfError`` (EKF_ERR_STATE) and nothing changes."""
+        gated = mahal or self.gate is not None
+        out = self.process_detection_logs(logs, mahal=mahal, record=True)
+        filtered = out.trajectory if gated else out
+        smoothed = self.smooth_history()
+        return (filtered, smoothed, (out.mahal, out.rejected)) if gated else (filtered, smoothed)
+
+    def smooth_history(self, history=None) -> list:
+        """The backward pass over the last recorded call (``ekf_batch_smooth_history``; ``history``: its buffer, default
+        ``self.last_history``): per member the smoothed rows ``(F_b, 7)``.  Sets ``last_smooth_status``.  Reads the members
+        only; the same history gives the same bits every time."""
+        torch = self._torch
+        history = self.last_history if history is None else history
+        if history is None:
+            raise ValueError("no recorded call yet (smooth_detection_logs, or observe_indexed(record=True))")
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_batch_smooth_workspace_bytes(self.h, C.byref(nbytes)))
+        mf = self._history_frames
+        frames = int(mf[-1])
+        status = np.zeros(self.members, dtype=np.int32)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            ws = torch.empty((max(nbytes.value, 256),), dtype=torch.uint8, device=self.device)
+            out = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
+            self._check(self.lib.ekf_batch_smooth_history(self.h, history.data_ptr(), history.numel(), ws.data_ptr(),
+                                                          ws.numel(), out.data_ptr() if frames else None, _iptr(status)))
+            self.stream.synchronize()
+        self.last_smooth_status = status
+        rows = out.cpu().numpy()
+        return [rows[mf[b]:mf[b + 1]] for b in range(self.members)]
+
+    def history_records(self, b) -> list:
+        """The records of member b in the last recorded call, as ``tests/smooth_util.device_records`` lists a single filter's:
+        dicts ``frame`` (within the member's log), ``dims``, ``s_eff``, ``u`` [6], ``stepped``, ``x`` [N], ``P`` [N, N]."""
+        b = self._member(b)
+        ip = C.POINTER(C.c_int32)
+        count = C.c_int32()
+        self._check(self.lib.ekf_batch_history_info(self.h, b, C.byref(count), 0, None, None, None, None, None, None))
+        r = count.value
+        frame, dims, stepped = (np.zeros(max(r, 1), dtype=np.int32) for _ in range(3))
+        s_eff, motion = np.zeros(max(r, 1)), np.zeros((max(r, 1), 6))
+        self._check(self.lib.ekf_batch_history_info(self.h, b, C.byref(count), max(r, 1), frame.ctypes.data_as(ip),
+                                                    dims.ctypes.data_as(ip), _dptr(s_eff), _dptr(motion),
+                                                    stepped.ctypes.data_as(ip), None))
+        records = []
+        for i in range(r):
+            n = int(dims[i])
+            x, p = np.empty(n), np.empty((n, n))
+            self._check(self.lib.ekf_batch_history_record(self.h, self.last_history.data_ptr(), b, i, _dptr(x), _dptr(p), n))
+            records.append({"frame": int(frame[i]), "dims": n, "s_eff": float(s_eff[i]), "u": motion[i].copy(),
+                            "stepped": bool(stepped[i]), "x": x, "P": p})
+        return records
+
+    def smooth_replicas(self, log, sigma, seed: int, *, first_replica: int = 0):
+        """``replay_replicas(log, sigma, seed)`` recorded and smoothed: every member replays ONE log as replica
+        ``first_replica + b`` (the poses of ``replica_poses``, drawn on the device) and gets its own backward pass.  Returns
+        ``(filtered [B, F, 7], smoothed [B, F, 7])``; ``filtered`` has the bits of ``replay_replicas``' trajectories on an
+        equal batch.  "How much does smoothing buy at this noise level, this gate, these noise constants" is one call."""
+        torch = self._torch
+        B = self.members
+        sig = replica_sigma(sigma, B)
+        r0 = _replica_range(first_replica, B)
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2**64)")
+        plan, poses, idx, fo = self._plan_replica_log(log, "poses", (6,), "smooth_replicas")
+        F, D = fo.shape[0] - 1, idx.shape[0]
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            src = torch.from_numpy(poses).to(self.device)
+            noisy = torch.empty((B * D, 6), dtype=torch.float64, device=self.device)
+            self._check(self.lib.ekf_batch_replica_poses(src.data_ptr() if D else None, D, _dptr(sig), B, seed, r0,
+                                                         noisy.data_ptr() if D else None, self.stream.cuda_stream))
+        offsets = np.concatenate([fo[:-1] + b * D for b in range(B)] + [np.array([B * D], dtype=np.int64)])
+        traj = self.observe_indexed(np.tile(idx, B), offsets, F * np.arange(B + 1, dtype=np.int64), noisy, record=True)
+        self._adopt_plans([plan] * B)
+        self.last_ignored = [tuple(plan.ignored)] * B
+        return traj.reshape(B, F, 7), np.stack(self.smooth_history()) if B else np.zeros((0, F, 7))
+
     def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False,
-                        mahal: bool = False, noise=None, scale=None, motion=None):
+                        mahal: bool = False, noise=None, scale=None, motion=None, record: bool = False):
         """The C call behind ``process_detection_logs`` (landmark indices already assigned; ``landmarks`` is not
         touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1] on the host, poses [D,6] on the host or a contiguous
         float64 tensor on the batch's device, produced on the batch's stream.  Returns the
@@ -843,7 +943,10 @@ class EKFBatch:
         with ``row_noise=True``; ekf_batch_observe_logs_rows), or None: every member's ``r_uncertainty``.  ``scale``:
         [Ftot] process-noise scales, one per frame, indexed like frame_offsets (a batch built with ``frame_scale=True``;
         ekf_batch_observe_logs_scaled), or None: no frame carries one.  ``motion``: [Ftot, 6] camera motions, one per
-        frame, indexed like frame_offsets (a batch built with ``motion=True``; ekf_batch_observe_logs_moved), or None."""
+        frame, indexed like frame_offsets (a batch built with ``motion=True``; ekf_batch_observe_logs_moved), or None.
+        ``record``: the recorded call (ekf_batch_observe_logs_recorded): the same outputs, bit for bit, and the history of
+        the call in ``self.last_history`` for ``smooth_history`` / ``history_records`` (True: a buffer of
+        ``ekf_batch_history_bytes`` is allocated; a uint8 tensor on the batch's device: that buffer)."""
         torch = self._torch
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
         if noise is not None:
@@ -876,12 +979,17 @@ class EKFBatch:
             motion = motion_array(motion, frames)
         nbytes = C.c_size_t()
         self._check(self.lib.ekf_batch_log_workspace_bytes(self.h, idx.shape[0], frames, C.byref(nbytes)))
+        hbytes = C.c_size_t()
+        recording = isinstance(record, torch.Tensor) or bool(record)
+        if recording:
+            self._check(self.lib.ekf_batch_history_bytes(self.h, _iptr(idx), _lptr(fo), _lptr(mf), int(motion is not None),
+                                                         C.byref(hbytes)))
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             # (a device tensor comes from this batch's stream: _estimate_corner_logs)
             poses_t = poses if on_device else torch.from_numpy(poses).to(self.device)
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
             traj = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
-            if noise is not None or scale is not None or motion is not None:
+            if noise is not None or scale is not None or motion is not None or recording:
                 rows_t = torch.from_numpy(noise).to(self.device) if noise is not None else None
                 scale_t = torch.from_numpy(scale).to(self.device) if scale is not None else None
                 motion_t = torch.from_numpy(motion).to(self.device) if motion is not None else None
@@ -889,12 +997,17 @@ class EKFBatch:
                 cov_t = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
                 mahal_t = torch.empty((idx.shape[0],), dtype=torch.float64, device=self.device) if mahal else None
                 ptr = (lambda t: t.data_ptr() if t is not None and frames else None)
-                self._check(self.lib.ekf_batch_observe_logs_moved(
-                    self.h, _iptr(idx), _lptr(fo), _lptr(mf), poses_t.data_ptr() if idx.shape[0] else None,
-                    rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None, ptr(scale_t), ptr(motion_t),
-                    ws.data_ptr(),
-                    nbytes.value, ptr(traj), ptr(nis_t),
-                    ptr(cov_t), mahal_t.data_ptr() if mahal and idx.shape[0] else None))
+                args = (self.h, _iptr(idx), _lptr(fo), _lptr(mf), poses_t.data_ptr() if idx.shape[0] else None,
+                        rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None, ptr(scale_t), ptr(motion_t),
+                        ws.data_ptr(), nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t),
+                        mahal_t.data_ptr() if mahal and idx.shape[0] else None)
+                if recording:
+                    history = record if isinstance(record, torch.Tensor) else \
+                        torch.empty((max(hbytes.value, 256),), dtype=torch.uint8, device=self.device)
+                    self._check(self.lib.ekf_batch_observe_logs_recorded(*args, history.data_ptr(), history.numel()))
+                    self.last_history, self._history_frames = history, mf.copy()
+                else:
+                    self._check(self.lib.ekf_batch_observe_logs_moved(*args))
                 self.stream.synchronize()
                 out = (traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, cov_t.cpu().numpy() if cam_cov else None)
                 if mahal:

@@ -10,6 +10,7 @@
 #include "ekf_host.h"
 #include "ekf_kernels.h"
 #include "ekf_remove.h"
+#include "ekf_batch_smooth_host.h"
 
 struct ekf_batch {
     ekf_config cfg{};
@@ -27,6 +28,18 @@ struct ekf_batch {
     std::vector<double> gate;       // [B] chi^2 gate per member (+inf: off); empty: no gate set (ekf_batch_set_gate)
     std::vector<int32_t> frozen;    // [B] "map frozen" per member (ekf_batch_set_map_frozen); the device copy: BatchLayout::frozen
     PinnedBuffer pin;               // pinned staging of a call's indices and offsets
+    // Batch smoothing (include/ekf_slam_hip.h, "Batch smoothing"): the plan of the last recorded call (host side, from the
+    // logs alone) and, once something asks for them (`fetched`), the words the device wrote and the tables built from them.
+    // ekf_batch_reset, ekf_batch_set_member and ekf_batch_remove_markers clear `valid`.
+    struct History {
+        bool valid = false, fetched = false, with_motion = false;
+        const void* buf = nullptr;
+        BatchHistoryPlan plan;
+        std::vector<int64_t> member_frames;       // [B + 1]
+        std::vector<int32_t> flag;                // [Ftot] as the device wrote them
+        std::vector<double> s_eff, motion;        // [Ftot], [Ftot][6] (zeros without motions)
+        BatchSmoothTables tab;
+    } hist;
 };
 
 namespace {
@@ -213,7 +226,7 @@ BatchReplicaLayout batch_replica_layout(int64_t D, int64_t F, int32_t B, bool ga
 int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, const BatchShape& sh, const double* poses_dev,
                       double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev,
                       const double* rows_dev = nullptr, const double* scale_dev = nullptr,
-                      const double* motion_dev = nullptr) {
+                      const double* motion_dev = nullptr, const EkfBatchRecord* record = nullptr) {
     const int32_t B = b->members;
     const BatchLayout L = batch_layout(b->cfg, B);
     EkfBatchWindow a{};
@@ -256,7 +269,9 @@ int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, co
     for (int64_t w = 0; w < sh.frames_max; w += window) {
         a.window_first = (int32_t)w;
         g.w.window_first = (int32_t)w;
-        if (hbm)
+        if (record)      // (a recorded call: EKF, the one-column kernel, no frozen member -- checked by the caller)
+            ekf_launch_batch_recorded_window(a, *record, B, b->stream);
+        else if (hbm)
             ekf_launch_batch_wide_window(rot ? 1 : 0, !batch_wide(b->cfg), g, B, b->stream);
         else if (rot)
             ekf_launch_batch_rot_window(a, B, b->stream);
@@ -339,9 +354,69 @@ int batch_observe_replicas(ekf_batch* b, const int32_t* lm_index, const int64_t*
     return batch_run_windows(b, w, LL, sh, noisy, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
 }
 
+// ---- batch smoothing (include/ekf_slam_hip.h, "Batch smoothing": the refusals) ------------------------------------------
+int batch_smoothing_supported(const ekf_batch* b) {
+    if (b->cfg.model != EKF_MODEL_EKF) return fail(EKF_ERR_STATE, "batch smoothing: EKF_MODEL_ROTATIONS is not supported");
+    if (b->cfg.quat_mode != EKF_QUAT_SCALAR_FIRST)
+        return fail(EKF_ERR_STATE, "batch smoothing needs EKF_QUAT_SCALAR_FIRST (the as-written injection has no inverse)");
+    if (batch_large(b->cfg) || batch_wide(b->cfg))
+        return fail(EKF_ERR_STATE, "batch smoothing: the window kernels of EKF_FLAG_BATCH_LARGE_MAPS / EKF_FLAG_BATCH_WIDE_FRAMES do not record");
+    return EKF_OK;
+}
+
+// member m with a log of `frames` frames that check_log has passed (lc)
+int batch_recordable(const ekf_batch* b, int32_t m, int64_t frames, const LogCheck& lc) {
+    if (frames > 0 && b->frozen[m])
+        return fail(EKF_ERR_STATE, "batch smoothing: member " + std::to_string(m) + "'s map is frozen");
+    if (EKF_CAM + EKF_LM * lc.n > EKF_SMOOTH_RESIDENT_DIMS)
+        return fail(EKF_ERR_STATE, "batch smoothing: member " + std::to_string(m) + " would pass 50 landmarks (the resident tier)");
+    return EKF_OK;
+}
+
+// the words the device wrote in the last recorded call, and the tables from them (waits for the stream; once per recording)
+int batch_history_fetch(ekf_batch* b) {
+    ekf_batch::History& h = b->hist;
+    if (!h.valid)
+        return fail(EKF_ERR_STATE, "no recorded call (ekf_batch_observe_logs_recorded), or a member has been reset, set or pruned since");
+    if (h.fetched) return EKF_OK;
+    const size_t F = h.plan.slot.size();
+    const char* hist = static_cast<const char*>(h.buf);
+    h.flag.assign(F, 0);
+    h.s_eff.assign(F, 0.0);
+    h.motion.assign(F * 6, 0.0);
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (F > 0) {
+        HIP_TRY(hipMemcpy(h.flag.data(), hist + h.plan.flag_at, F * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h.s_eff.data(), hist + h.plan.seff_at, F * 8, hipMemcpyDeviceToHost));
+        if (h.with_motion) HIP_TRY(hipMemcpy(h.motion.data(), hist + h.plan.motion_at, F * 48, hipMemcpyDeviceToHost));
+    }
+    batch_smooth_tables(b->members, h.member_frames.data(), h.plan.head.data(), h.plan.slot.data(), h.plan.dims.data(),
+                        h.flag.data(), h.s_eff.data(), h.with_motion ? h.motion.data() : nullptr, b->noise.data(), &h.tab);
+    h.fetched = true;
+    return EKF_OK;
+}
+
+// smoothing workspace: [status [B] | tables | members]
+struct BatchSmoothLayout {
+    size_t tables, members, total;
+};
+BatchSmoothLayout batch_smooth_layout(size_t records, int32_t B) {
+    Carve w;
+    w.take((size_t)B * 4);
+    const size_t tables = w.take(std::max<size_t>(records, 1) * sizeof(EkfSmoothRec));
+    const size_t members = w.take((size_t)B * sizeof(EkfBatchSmoothMember));
+    return {tables, members, w.end};
+}
+
 }  // namespace
 
 extern "C" {
+
+static int batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, const int64_t* member_frames,
+                              const double* poses_dev, const double* rows_dev, const double* scale_dev,
+                              const double* motion_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev,
+                              double* nis_dev, double* cam_cov_dev, double* mahal_dev, bool record, void* history_dev,
+                              size_t history_bytes);
 
 int ekf_batch_query_sizes(const ekf_config* cfg, int32_t members, int64_t* ld, size_t* cov_bytes, size_t* state_bytes,
                           size_t* workspace_bytes) {
@@ -446,6 +521,7 @@ int ekf_batch_reset(ekf_batch* b, int32_t member, const double* initial_poses) {
     if (member != -1 && (rc = batch_member(b, member))) return rc;
     const int32_t lo = member < 0 ? 0 : member, hi = member < 0 ? b->members : member + 1;
     const int64_t ld = b->ld;
+    b->hist.valid = false;      // (batch smoothing: the recording no longer describes the batch)
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipMemset(b->cov + (size_t)lo * ld * ld, 0, (size_t)(hi - lo) * ld * ld * 8));
     HIP_TRY(hipMemset(b->state + (size_t)lo * ld, 0, (size_t)(hi - lo) * ld * 8));
@@ -497,6 +573,7 @@ int ekf_batch_set_member(ekf_batch* b, int32_t member, const double* state, int3
     std::memcpy(st.data(), state, (size_t)dims * 8);
     for (int i = 0; i < dims; ++i)
         for (int j = 0; j < dims; ++j) p[(size_t)i * ld + j] = 0.5 * (cov[(size_t)i * dims + j] + cov[(size_t)j * dims + i]);
+    b->hist.valid = false;      // (batch smoothing: the recording no longer describes the batch)
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipMemcpy(b->state + (size_t)member * ld, st.data(), st.size() * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->cov + (size_t)member * ld * ld, p.data(), p.size() * 8, hipMemcpyHostToDevice));
@@ -588,8 +665,29 @@ int ekf_batch_observe_logs_moved(ekf_batch* b, const int32_t* lm_index, const in
                                  const int64_t* member_frames, const double* poses_dev, const double* rows_dev,
                                  const double* scale_dev, const double* motion_dev, void* log_ws, size_t log_ws_bytes,
                                  double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev) {
+    return batch_observe_logs(b, lm_index, frame_offsets, member_frames, poses_dev, rows_dev, scale_dev, motion_dev, log_ws,
+                              log_ws_bytes, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, false, nullptr, 0);
+}
+
+int ekf_batch_observe_logs_recorded(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets,
+                                    const int64_t* member_frames, const double* poses_dev, const double* rows_dev,
+                                    const double* scale_dev, const double* motion_dev, void* log_ws, size_t log_ws_bytes,
+                                    double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev,
+                                    void* history_dev, size_t history_bytes) {
+    return batch_observe_logs(b, lm_index, frame_offsets, member_frames, poses_dev, rows_dev, scale_dev, motion_dev, log_ws,
+                              log_ws_bytes, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, true, history_dev, history_bytes);
+}
+
+// The log call.  record: the RECORDED window kernels, which pack the member into the frame's slot of the history behind every
+// frame that changed it (recording only reads the members: every output has the bits of the plain call).
+static int batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, const int64_t* member_frames,
+                              const double* poses_dev, const double* rows_dev, const double* scale_dev,
+                              const double* motion_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev,
+                              double* nis_dev, double* cam_cov_dev, double* mahal_dev, bool record, void* history_dev,
+                              size_t history_bytes) {
     int rc = batch_ready(b);
     if (rc) return rc;
+    if (record && (rc = batch_smoothing_supported(b))) return rc;
     if (motion_dev && (b->cfg.flags & EKF_FLAG_MOTION) == 0)
         return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_MOTION");
     if (scale_dev && !batch_scaled(b->cfg)) return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_FRAME_SCALE");
@@ -606,6 +704,7 @@ int ekf_batch_observe_logs_moved(ekf_batch* b, const int32_t* lm_index, const in
     if ((rc = batch_refresh(b))) return rc;      // (landmark counts as the previous call left them)
     BatchShape sh;
     LogCheck lc;
+    BatchHistoryPlan plan;
     for (int32_t m = 0; m < B; ++m) {
         const int64_t f0 = member_frames[m], frames = member_frames[m + 1] - f0;
         if (b->frozen[m] && (rc = check_frozen_log(lm_index, frame_offsets + f0, frames, b->nlm[m], "member " + std::to_string(m) + "'s log")))
@@ -613,19 +712,53 @@ int ekf_batch_observe_logs_moved(ekf_batch* b, const int32_t* lm_index, const in
         rc = check_log(lm_index, frame_offsets + f0, frames, b->nlm[m], b->cfg, "member " + std::to_string(m) + "'s log", &lc);
         if (rc) return rc;
         sh.add(lc, frames);
+        if (record) {
+            if ((rc = batch_recordable(b, m, frames, lc))) return rc;
+            batch_history_add_member(plan, frame_offsets + f0, frames, batch_lmd(b->cfg), b->nlm[m], lc, motion_dev != nullptr);
+        }
+    }
+    if (record) {
+        batch_history_finish(plan, motion_dev != nullptr);
+        if (history_dev && history_bytes < plan.total)
+            return fail(EKF_ERR_CAPACITY, "history smaller than ekf_batch_history_bytes");
+        if ((rc = check_device_buffers({history_dev}, history_bytes, plan.total, "ekf_batch_history_bytes"))) return rc;
+        b->hist = ekf_batch::History{};
+        b->hist.valid = true;
+        b->hist.with_motion = motion_dev != nullptr;
+        b->hist.buf = history_dev;
+        b->hist.member_frames.assign(member_frames, member_frames + B + 1);
+        b->hist.plan = std::move(plan);
     }
     if (F == 0) return EKF_OK;
 
-    // ---- staging: one copy of indices and offsets (the stream is idle: batch_refresh synchronised it)
-    if ((rc = b->pin.reserve(LL.total))) return rc;
+    // ---- staging: one copy of indices and offsets (the stream is idle: batch_refresh synchronised it); a recorded call: the
+    // headers' and slots' offsets behind them, into the history's own pieces
+    const BatchHistoryPlan& hp = b->hist.plan;
+    const size_t pin_head = LL.total, pin_slot = pin_head + align256((size_t)B * 8);
+    if ((rc = b->pin.reserve(record ? pin_slot + align256((size_t)F * 8) : LL.total))) return rc;
     if (D > 0) std::memcpy(b->pin.get(), lm_index, (size_t)D * 4);
     std::memcpy(b->pin.get() + LL.frames, frame_offsets, (size_t)(F + 1) * 8);
     std::memcpy(b->pin.get() + LL.members, member_frames, (size_t)(B + 1) * 8);
     if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
     char* ws = static_cast<char*>(log_ws);
     HIP_TRY(hipMemcpyAsync(ws, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
-    return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev, scale_dev,
-                             motion_dev);
+    if (!record)
+        return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev,
+                                 scale_dev, motion_dev);
+    char* hist = static_cast<char*>(history_dev);
+    std::memcpy(b->pin.get() + pin_head, hp.head.data(), (size_t)B * 8);
+    std::memcpy(b->pin.get() + pin_slot, hp.slot.data(), (size_t)F * 8);
+    HIP_TRY(hipMemcpyAsync(hist + hp.head_at, b->pin.get() + pin_head, (size_t)B * 8, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(hist + hp.slot_at, b->pin.get() + pin_slot, (size_t)F * 8, hipMemcpyHostToDevice, b->stream));
+    if (motion_dev)      // (the tables need the motions on the host: they come back with the flags, from the history)
+        HIP_TRY(hipMemcpyAsync(hist + hp.motion_at, motion_dev, (size_t)F * 48, hipMemcpyDeviceToDevice, b->stream));
+    const EkfBatchRecord r{reinterpret_cast<double*>(hist), reinterpret_cast<const int64_t*>(hist + hp.head_at),
+                           reinterpret_cast<const int64_t*>(hist + hp.slot_at), reinterpret_cast<int32_t*>(hist + hp.flag_at),
+                           reinterpret_cast<double*>(hist + hp.seff_at)};
+    rc = batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev, scale_dev,
+                           motion_dev, &r);
+    if (rc) b->hist.valid = false;      // (a recorded call that failed leaves no history)
+    return rc;
 }
 
 // member = -1: every member, [B]; member >= 0: that one, [1].  Both wait for the batch's stream.
@@ -805,6 +938,167 @@ int ekf_batch_remove_markers(ekf_batch* b, const int32_t* lm_index, const int64_
     HIP_TRY(hipGetLastError());
     b->cov = cov_dev_new;
     b->state = state_dev_new;
+    b->hist.valid = false;      // (batch smoothing: the recording no longer describes the batch)
+    return EKF_OK;
+}
+
+// ---- batch smoothing (include/ekf_slam_hip.h, "Batch smoothing"; kernels: ekf_batch_recorded.hip, ekf_smooth.hip) ---------
+int ekf_batch_history_bytes(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, const int64_t* member_frames,
+                            int32_t with_motion, size_t* bytes) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (!bytes) return fail(EKF_ERR_INVALID, "bytes is NULL");
+    const int32_t B = b->members;
+    if (!member_frames || !frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
+    if ((rc = check_offsets(member_frames, B, "member_frames"))) return rc;
+    const int64_t F = member_frames[B];
+    if ((rc = check_offsets(frame_offsets, F, "frame_offsets"))) return rc;
+    if (frame_offsets[F] > 0 && !lm_index) return fail(EKF_ERR_INVALID, "NULL detections");
+    if ((rc = batch_refresh(b))) return rc;
+    BatchHistoryPlan plan;
+    LogCheck lc;
+    for (int32_t m = 0; m < B; ++m) {
+        const int64_t f0 = member_frames[m], frames = member_frames[m + 1] - f0;
+        if (b->frozen[m] && (rc = check_frozen_log(lm_index, frame_offsets + f0, frames, b->nlm[m], "member " + std::to_string(m) + "'s log")))
+            return rc;
+        rc = check_log(lm_index, frame_offsets + f0, frames, b->nlm[m], b->cfg, "member " + std::to_string(m) + "'s log", &lc);
+        if (rc) return rc;
+        batch_history_add_member(plan, frame_offsets + f0, frames, batch_lmd(b->cfg), b->nlm[m], lc, with_motion != 0);
+    }
+    batch_history_finish(plan, with_motion != 0);
+    *bytes = plan.total;
+    return EKF_OK;
+}
+
+int ekf_batch_history_info(ekf_batch* b, int32_t member, int32_t* records, int32_t capacity, int32_t* frame, int32_t* dims,
+                           double* s_eff, double* motion, int32_t* stepped, int32_t* frame_record) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if ((rc = batch_member(b, member))) return rc;
+    if (!records || capacity < 0) return fail(EKF_ERR_INVALID, "bad history info request");
+    if ((rc = batch_history_fetch(b))) return rc;
+    const ekf_batch::History& h = b->hist;
+    const EkfBatchSmoothMember& mem = h.tab.members[member];
+    const int32_t R = mem.records;
+    *records = R;
+    const bool arrays = frame || dims || s_eff || motion || stepped;
+    if (arrays && capacity < R) return fail(EKF_ERR_CAPACITY, "fewer entries than records");
+    for (int32_t r = 0; r < R && arrays; ++r) {
+        const size_t e = (size_t)mem.table + r;
+        const int32_t t = h.tab.rec_frame[e];
+        if (frame) frame[r] = t - mem.frame0;
+        if (dims) dims[r] = h.tab.tables[e].dims;
+        if (s_eff) s_eff[r] = h.tab.rec_stepped[e] ? h.s_eff[t] : 0.0;
+        if (motion)
+            for (int i = 0; i < 6; ++i) motion[6 * (size_t)r + i] = h.tab.tables[e].u[i];
+        if (stepped) stepped[r] = h.tab.rec_stepped[e];
+    }
+    if (frame_record) {
+        int32_t r = -1;
+        for (int32_t t = mem.frame0; t < mem.frame1; ++t) {
+            if (r + 1 < R && h.tab.rec_frame[(size_t)mem.table + r + 1] == t) ++r;
+            frame_record[t - mem.frame0] = r;
+        }
+    }
+    return EKF_OK;
+}
+
+int ekf_batch_history_record(ekf_batch* b, const void* history_dev, int32_t member, int32_t r, double* state_out,
+                             double* cov_out, int32_t dims) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if ((rc = batch_member(b, member))) return rc;
+    if (!b->hist.valid || history_dev != b->hist.buf)
+        return fail(EKF_ERR_STATE, "not the history of this handle's last recorded call");
+    if ((rc = batch_history_fetch(b))) return rc;
+    const EkfBatchSmoothMember& mem = b->hist.tab.members[member];
+    if (r < 0 || r >= mem.records) return fail(EKF_ERR_INVALID, "no such record");
+    const EkfSmoothRec& e = b->hist.tab.tables[(size_t)mem.table + r];
+    if (dims != e.dims) return fail(EKF_ERR_INVALID, "dims must equal the record's (ekf_batch_history_info)");
+    const size_t N = (size_t)e.dims;
+    std::vector<double> packed(N + N * (N + 1) / 2);
+    HIP_TRY(hipMemcpy(packed.data(), static_cast<const double*>(history_dev) + e.off, packed.size() * 8, hipMemcpyDeviceToHost));
+    if (state_out) std::memcpy(state_out, packed.data(), N * 8);
+    if (cov_out) {
+        const double* tri = packed.data() + N;
+        size_t at = 0;
+        for (size_t j = 0; j < N; ++j)
+            for (size_t i = j; i < N; ++i, ++at) cov_out[i * N + j] = cov_out[j * N + i] = tri[at];
+    }
+    return EKF_OK;
+}
+
+// The table builder of the pass without a handle and without a device (what ekf_batch_smooth_history uploads).
+int ekf_batch_history_table(int32_t members, const int64_t* member_frames, const int64_t* slot, const int32_t* dims,
+                            const int32_t* flag, const double* s_eff, const double* motion, const double* noise,
+                            int32_t capacity, int32_t* total, int32_t* member_rows, int32_t* rec_member, int32_t* rec_rows,
+                            double* rec_q, int32_t* rec_moved) {
+    if (members < 1 || !member_frames || !slot || !dims || !flag || !s_eff || !noise || !total || !member_rows || capacity < 0)
+        return fail(EKF_ERR_INVALID, "bad table request");
+    std::vector<int64_t> head((size_t)members, 0);
+    BatchSmoothTables tab;
+    batch_smooth_tables(members, member_frames, head.data(), slot, dims, flag, s_eff, motion, noise, &tab);
+    *total = (int32_t)tab.tables.size();
+    for (int32_t m = 0; m < members; ++m) {
+        const EkfBatchSmoothMember& mem = tab.members[m];
+        const int32_t row[5] = {mem.records, mem.frame0, mem.lead1, mem.nan0, mem.frame1};
+        std::memcpy(member_rows + 5 * (size_t)m, row, sizeof row);
+    }
+    if (!rec_member && !rec_rows && !rec_q && !rec_moved) return EKF_OK;
+    if (capacity < *total) return fail(EKF_ERR_CAPACITY, "fewer entries than records");
+    for (int32_t m = 0; m < members; ++m)
+        for (int32_t r = 0; r < tab.members[m].records; ++r) {
+            const size_t e = (size_t)tab.members[m].table + r;
+            if (rec_member) rec_member[e] = m;
+            if (rec_rows) rec_rows[2 * e] = tab.tables[e].frame0, rec_rows[2 * e + 1] = tab.tables[e].frame1;
+            if (rec_q)
+                for (int i = 0; i < 3; ++i) rec_q[3 * e + i] = tab.tables[e].q[i];
+            if (rec_moved) rec_moved[e] = tab.tables[e].moved;
+        }
+    return EKF_OK;
+}
+
+int ekf_batch_smooth_workspace_bytes(ekf_batch* b, size_t* bytes) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (!bytes) return fail(EKF_ERR_INVALID, "bytes is NULL");
+    if ((rc = batch_history_fetch(b))) return rc;
+    *bytes = batch_smooth_layout(b->hist.tab.tables.size(), b->members).total;
+    return EKF_OK;
+}
+
+int ekf_batch_smooth_history(ekf_batch* b, const void* history_dev, size_t history_bytes, void* ws, size_t ws_bytes,
+                             double* smoothed_dev, int32_t* status_out) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if ((rc = batch_smoothing_supported(b))) return rc;
+    if (!b->hist.valid)
+        return fail(EKF_ERR_STATE, "no recorded call (ekf_batch_observe_logs_recorded), or a member has been reset, set or pruned since");
+    if (history_dev != b->hist.buf || history_bytes < b->hist.plan.total)
+        return fail(EKF_ERR_STATE, "not the history of this handle's last recorded call");
+    if ((rc = batch_history_fetch(b))) return rc;
+    const int32_t B = b->members;
+    const BatchSmoothTables& tab = b->hist.tab;
+    if (status_out) std::memset(status_out, 0, (size_t)B * 4);
+    if (b->hist.member_frames[B] == 0) return EKF_OK;
+    if (!smoothed_dev) return fail(EKF_ERR_INVALID, "smoothed_dev is NULL");
+    const BatchSmoothLayout L = batch_smooth_layout(tab.tables.size(), B);
+    if ((rc = check_device_buffers({ws}, ws_bytes, L.total, "ekf_batch_smooth_workspace_bytes"))) return rc;
+    char* w = static_cast<char*>(ws);
+    int32_t* status = reinterpret_cast<int32_t*>(w);
+    EkfSmoothRec* tables_dev = reinterpret_cast<EkfSmoothRec*>(w + L.tables);
+    EkfBatchSmoothMember* members_dev = reinterpret_cast<EkfBatchSmoothMember*>(w + L.members);
+    if (!tab.tables.empty())
+        HIP_TRY(hipMemcpyAsync(tables_dev, tab.tables.data(), tab.tables.size() * sizeof(EkfSmoothRec), hipMemcpyHostToDevice,
+                               b->stream));
+    HIP_TRY(hipMemcpyAsync(members_dev, tab.members.data(), (size_t)B * sizeof(EkfBatchSmoothMember), hipMemcpyHostToDevice,
+                           b->stream));
+    HIP_TRY(ekf_launch_batch_smooth(static_cast<const double*>(history_dev), tables_dev, members_dev, B, tab.nmax, smoothed_dev,
+                                    status, b->stream));
+    HIP_TRY(hipGetLastError());
+    // every member has its own status word: a P_p that is not positive definite is reported there and nowhere else
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (status_out) HIP_TRY(hipMemcpy(status_out, status, (size_t)B * 4, hipMemcpyDeviceToHost));
     return EKF_OK;
 }
 

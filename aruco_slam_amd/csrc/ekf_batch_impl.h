@@ -12,6 +12,7 @@
 #include "ekf_gate_device.h"
 #include "ekf_markers.h"
 #include "ekf_motion_device.h"
+#include "ekf_smooth_device.h"
 
 template <int MODEL> struct EkfBatchCaps;
 template <> struct EkfBatchCaps<0> { static constexpr int MAX_VISIBLE = EKF_BATCH_MAX_VISIBLE; };
@@ -253,8 +254,34 @@ __device__ __forceinline__ void ekf_batch_strip(double* P, int64_t ld, const dou
     }
 }
 
-template <int MODEL, bool MOVED = false, bool FROZEN = false>
-__device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
+// RECORDED: the instances of a recorded call (ekf_batch_observe_logs_recorded; ekf_batch_recorded.hip), instances of their
+// own for the reason MOVED has them.  The end of a frame that changed the member -- it was stepped, or moved by a non-zero
+// motion -- packs st[0:N] and the lower triangle of P into the frame's slot (the record layout of ekf_smooth.hip: column j of
+// the triangle is row j of the bitwise-symmetric P from its diagonal on, contiguous).  Wave w of the workgroup copies columns
+// w, w + nt / 64, ...; its lanes walk down the column, so consecutive lanes read and write consecutive doubles.  Every frame
+// of the call gets its flag and s_eff.  Called by the whole workgroup behind the barrier that ends the frame's writes to st
+// and P; the stage only reads the member, and its own barrier keeps the next frame's writes behind its reads.
+__device__ __forceinline__ void ekf_batch_record(const EkfBatchRecord& r, int64_t t, int tid, int nt, const double* st,
+                                                 const double* P, int64_t ld, int N, int flag, double s_eff) {
+    if (tid == 0) {
+        r.flag[t] = flag;
+        r.s_eff[t] = s_eff;
+    }
+    if (flag <= 0 || r.slot[t] < 0) return;      // (uniform: flag and slot are the same for every thread)
+    double* rec = r.history + r.slot[t];
+    for (int i = tid; i < N; i += nt) rec[i] = st[i];
+    double* tri = rec + N;
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int j = wave; j < N; j += nt >> 6) {
+        double* col = tri + ekf_smooth_col(N, j) - j;
+        const double* row = P + (int64_t)j * ld;
+        for (int i = j + lane; i < N; i += 64) col[i] = row[i];
+    }
+    __syncthreads();
+}
+
+template <int MODEL, bool MOVED = false, bool FROZEN = false, bool RECORDED = false>
+__device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a, const EkfBatchRecord* rec = nullptr) {
     constexpr int RD = EkfModel<MODEL>::RD, LMD = EkfModel<MODEL>::LMD, JC = EkfModel<MODEL>::JC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -287,10 +314,17 @@ __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
     bool frozen = false;
     if constexpr (FROZEN) frozen = a.frozen[b] != 0;
     if (tid == 0) *flag = 0;
+    if constexpr (RECORDED)      // the member's camera at the start of the call: the rows before its first record
+        if (a.window_first == 0 && tid < 7) rec->history[rec->head[b] + tid] = st[tid];
 
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t d0 = a.frame_offsets[t];
         const int mf = (int)(a.frame_offsets[t + 1] - d0);
+        // recording: was the member moved by this frame (a failed member ignores motions)
+        bool moved = false;
+        if constexpr (RECORDED && MOVED)
+            if (!failed)
+                for (int i = 0; i < 6; ++i) moved = moved || a.motion[6 * t + i] != 0.0;
         // the camera's motion first: first sightings, gate, predict and update see the moved prior, and a frame that is not
         // stepped is still moved (a failed member ignores motions)
         if constexpr (MOVED)
@@ -299,6 +333,7 @@ __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
             if (scaled && !failed && a.scale) pend = pend + a.scale[t];      // (rule 4: the frame's scale stays pending)
             ekf_batch_rows_unstepped(a, t, tid, st, P, failed);
             ekf_batch_mahal_untested(a, d0, mf, tid, nt);
+            if constexpr (RECORDED) ekf_batch_record(*rec, t, tid, nt, st, P, ld, LMD * n + EKF_CAM, failed ? -1 : moved ? 2 : 0, 0.0);
             continue;
         }
         const int32_t* idx = a.lm_index + d0;
@@ -330,6 +365,7 @@ __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
             if (m == 0) {      // no survivor: an empty frame
                 if (scaled && a.scale) pend = s_eff;      // (rule 4: p = p + s, the addition s_eff has made)
                 ekf_batch_rows_unstepped(a, t, tid, st, P, false);
+                if constexpr (RECORDED) ekf_batch_record(*rec, t, tid, nt, st, P, ld, N, moved ? 2 : 0, 0.0);
                 continue;
             }
         }
@@ -415,6 +451,7 @@ __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
             failed = true;
             if (tid == 0) a.status[b] = EKF_BATCH_ST_NUMERIC;
             ekf_batch_rows_unstepped(a, t, tid, st, P, true);
+            if constexpr (RECORDED) ekf_batch_record(*rec, t, tid, nt, st, P, ld, N, -1, 0.0);      // (the failing frame never records)
             continue;
         }
         // W = L^-1 A and y = L^-1 (z - h): thread c substitutes column c (c = N: the residual) in place
@@ -479,6 +516,7 @@ __device__ __forceinline__ void ekf_batch_window(const EkfBatchWindow& a) {
         }
         __syncthreads();
         ekf_batch_rows_stepped(a, t, tid, st, P, A + N, lda, k);      // (y is column N of A)
+        if constexpr (RECORDED) ekf_batch_record(*rec, t, tid, nt, st, P, ld, N, 1, s_eff);
     }
     if (tid == 0) a.nlm[b] = n;
     if (tid == 0 && scaled) a.pending[b] = pend;

@@ -330,6 +330,22 @@ struct EkfSmoothBlocked {
     int32_t* status;            // [0] sticky EKF_ST_NOT_SPD, [1..2] diagnostics of the factorisation kernels
 };
 void ekf_launch_smooth_blocked_step(const EkfSmoothBlocked& a, hipStream_t s);
+// Batch smoothing (include/ekf_slam_hip.h, "Batch smoothing"): workgroup b of ekf_batch_smooth_kernel runs the resident pass
+// over member b's records.  Offsets of the table entries count doubles from the start of the WHOLE history buffer, their
+// frame0 / frame1 are rows of smoothed [Ftot][7].
+struct EkfBatchSmoothMember {
+    int64_t table;              // the member's first entry in the tables
+    int64_t head;               // doubles from the start of the history: the member's camera state at the start of the call
+    int32_t records;            // R_b (0: only the lead rows are written)
+    int32_t frame0, frame1;     // the member's rows of smoothed
+    int32_t lead1;              // rows [frame0, lead1) repeat the start camera (before the first record)
+    int32_t nan0;               // rows [nan0, frame1) are NaN: the member failed in the replay at that frame
+    int32_t pad;
+};
+// status [B] (device) <- 0, or EKF_BATCH_ST_NUMERIC where a P_p of the member is not positive definite (all its rows: NaN).
+// nmax: the dims of the call's largest record (<= EKF_SMOOTH_RESIDENT_DIMS).  Returns the error of the attribute call.
+hipError_t ekf_launch_batch_smooth(const double* history, const EkfSmoothRec* tables_dev, const EkfBatchSmoothMember* members_dev,
+                                   int32_t members, int32_t nmax, double* smoothed, int32_t* status, hipStream_t s);
 
 // Batch of independent filters (ekf_batch.hip: EKF, ekf_batch_rot.hip: EKF_Rotations; frame body ekf_batch_impl.h): one
 // workgroup per member, frames [member_frames[b] + window_first, + window_frames) of its log.  Everything is validated on
@@ -378,6 +394,16 @@ extern "C" size_t ekf_batch_lds_bytes(int kmax, int lda);
 extern "C" size_t ekf_batch_rot_lds_bytes(int kmax, int lda);
 void ekf_launch_batch_window(const EkfBatchWindow& a, int members, hipStream_t s);
 void ekf_launch_batch_rot_window(const EkfBatchWindow& a, int members, hipStream_t s);
+// Recording (include/ekf_slam_hip.h, "Batch smoothing"; ekf_batch_recorded.hip): a second kernel argument of the RECORDED
+// instances only, so the other instances keep their arguments.  All offsets count doubles from `history`.
+struct EkfBatchRecord {
+    double* history;                // the caller's history buffer
+    const int64_t* head;            // [B] the member's header: state[0:7] at the start of the call (written by window 0)
+    const int64_t* slot;            // [Ftot] the frame's record slot, -1: the frame has none (it cannot change the member)
+    int32_t* flag;                  // [Ftot] 0: no record, 1: stepped, 2: moved only, -1: the member has failed
+    double* s_eff;                  // [Ftot] the scale the frame was stepped with (1 without frame scales; 0: not stepped)
+};
+void ekf_launch_batch_recorded_window(const EkfBatchWindow& a, const EkfBatchRecord& r, int members, hipStream_t s);
 // Dictionary-sized maps (EKF_FLAG_BATCH_LARGE_MAPS) and wide frames (EKF_FLAG_BATCH_WIDE_FRAMES), one kernel per model in
 // ekf_batch_wide.hip: N <= 1024, ld <= 1024; A / W of a member in the batch workspace, [k][ld] at w_stride = rd max_visible ld
 // doubles per member (kmax and window fields of `w` as above, w.lda unused)

@@ -5,6 +5,7 @@
 //   c = P_r (F~^T y),  x^s_r = inject(x_r, c).
 //   pack     : one record of a recorded replay: state and the lower triangle of P, packed column by column
 //   resident : every record has N <= 160: ONE launch of ONE workgroup runs the whole pass, P_p as a packed triangle in LDS
+//   batch    : the resident pass, one workgroup per member of an ekf_batch over the member's own records (grid = members)
 //   blocked  : any N: per step expand / move / prepare / the blocked Cholesky of ekf_wide.hip (ncols = 0: the right-hand
 //              side rides along as its residual) / backward substitution / matrix-vector product and injection
 // Nothing here writes the filter: the history, the table and the workspace are the caller's, and the status word is the
@@ -49,12 +50,13 @@ __device__ __forceinline__ void ekf_smooth_inject_camera(const double* xr, const
 // contiguous -- and the wave whose turn the "column N" is carries the right-hand side along (forward substitution).  The
 // backward substitution runs in ONE wave with y in registers; then P_r is read again from the history into the triangle's
 // LDS (L is no longer needed) for c = P_r w.
-__global__ __launch_bounds__(EKF_SMOOTH_THREADS) void ekf_smooth_resident_kernel(const double* __restrict__ hist,
-                                                                                 const EkfSmoothRec* __restrict__ table,
-                                                                                 int R, int lead_frames,
-                                                                                 double* __restrict__ smoothed,
-                                                                                 int32_t* status) {
-    extern __shared__ double tri[];
+// The pass itself, for the single filter's kernel and for the batch's (one workgroup of EKF_SMOOTH_THREADS runs it over ONE
+// table of R >= 1 records): offsets of the table count doubles from `hist`, rows [lead0, lead1) of `smoothed` repeat
+// head[0:7], `tri` is the dynamic LDS.  Returns false at the first P_p with a pivot that is not positive (every thread saw
+// the same pivots, so all of them return together); the rows written until then stay.
+__device__ __forceinline__ bool ekf_smooth_resident_pass(const double* __restrict__ hist, const double* __restrict__ head,
+                                                         const EkfSmoothRec* __restrict__ table, int R, int lead0, int lead1,
+                                                         double* __restrict__ smoothed, double* tri) {
     __shared__ double xs[EKF_SMOOTH_RESIDENT_DIMS], xr[EKF_SMOOTH_RESIDENT_DIMS], xp[EKF_SMOOTH_RESIDENT_DIMS];
     __shared__ double dv[EKF_SMOOTH_RESIDENT_DIMS], wv[EKF_SMOOTH_RESIDENT_DIMS], ld_s[EKF_SMOOTH_RESIDENT_DIMS];
     __shared__ EkfMotionF F;
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(EKF_SMOOTH_THREADS) void ekf_smooth_resident_kernel
         __syncthreads();
         for (int e = tid; e < 7 * (last.frame1 - last.frame0); e += EKF_SMOOTH_THREADS)
             smoothed[(int64_t)7 * last.frame0 + e] = xs[e % 7];
-        for (int e = tid; e < 7 * lead_frames; e += EKF_SMOOTH_THREADS) smoothed[e] = hist[e % 7];
+        for (int e = tid; e < 7 * (lead1 - lead0); e += EKF_SMOOTH_THREADS) smoothed[(int64_t)7 * lead0 + e] = head[e % 7];
     }
     for (int r = R - 2; r >= 0; --r) {
         const EkfSmoothRec rec = table[r], nx = table[r + 1];
@@ -140,10 +142,7 @@ __global__ __launch_bounds__(EKF_SMOOTH_THREADS) void ekf_smooth_resident_kernel
             }
             __syncthreads();
         }
-        if (bad) {      // (every thread saw the same pivots)
-            if (tid == 0) atomicOr(status, EKF_ST_NOT_SPD);
-            return;
-        }
+        if (bad) return false;      // (every thread saw the same pivots)
         // L^T y' = y: wave 0, y in registers (lane l holds rows l, l + 64, l + 128), column by column from the last
         if (wave == 0) {
             double y0 = lane < N ? dv[lane] : 0.0, y1 = lane + 64 < N ? dv[lane + 64] : 0.0,
@@ -190,6 +189,42 @@ __global__ __launch_bounds__(EKF_SMOOTH_THREADS) void ekf_smooth_resident_kernel
         for (int e = tid; e < 7 * (rec.frame1 - rec.frame0); e += EKF_SMOOTH_THREADS)
             smoothed[(int64_t)7 * rec.frame0 + e] = xs[e % 7];
     }
+    return true;
+}
+
+// the single filter: one workgroup, one table; a bad pivot sets the pass's status word and ends the pass there
+__global__ __launch_bounds__(EKF_SMOOTH_THREADS) void ekf_smooth_resident_kernel(const double* __restrict__ hist,
+                                                                                 const EkfSmoothRec* __restrict__ table,
+                                                                                 int R, int lead_frames,
+                                                                                 double* __restrict__ smoothed,
+                                                                                 int32_t* status) {
+    extern __shared__ double tri[];
+    if (!ekf_smooth_resident_pass(hist, hist, table, R, 0, lead_frames, smoothed, tri) && threadIdx.x == 0)
+        atomicOr(status, EKF_ST_NOT_SPD);
+}
+
+// the batch: workgroup b runs the pass over member b's table and writes the member's own status word; nothing is shared
+// between workgroups.  A bad pivot: every row of the member is NaN.  A member that failed in the replay: NaN from its failing
+// frame on (its last record's rows end there).  No records: the lead rows only.
+__global__ __launch_bounds__(EKF_SMOOTH_THREADS) void ekf_batch_smooth_kernel(const double* __restrict__ hist,
+                                                                              const EkfSmoothRec* __restrict__ tables,
+                                                                              const EkfBatchSmoothMember* __restrict__ members,
+                                                                              double* __restrict__ smoothed,
+                                                                              int32_t* __restrict__ status) {
+    extern __shared__ double tri[];
+    const EkfBatchSmoothMember m = members[blockIdx.x];
+    const int tid = threadIdx.x;
+    const double nan = __builtin_nan("");
+    bool ok = true;
+    if (m.records > 0)
+        ok = ekf_smooth_resident_pass(hist, hist + m.head, tables + m.table, m.records, m.frame0, m.lead1, smoothed, tri);
+    else
+        for (int e = tid; e < 7 * (m.lead1 - m.frame0); e += EKF_SMOOTH_THREADS)
+            smoothed[(int64_t)7 * m.frame0 + e] = hist[m.head + e % 7];
+    const int n0 = ok ? m.nan0 : m.frame0;
+    __syncthreads();      // (the NaN rows of a bad member overwrite rows other threads of the pass have written)
+    for (int e = tid; e < 7 * (m.frame1 - n0); e += EKF_SMOOTH_THREADS) smoothed[(int64_t)7 * n0 + e] = nan;
+    if (tid == 0) status[blockIdx.x] = ok ? 0 : EKF_BATCH_ST_NUMERIC;
 }
 
 // ---- blocked tier -------------------------------------------------------------------------------------------------------
@@ -297,6 +332,17 @@ hipError_t ekf_launch_smooth_resident(const double* history, const EkfSmoothRec*
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ekf_smooth_resident_kernel, dim3(1), dim3(EKF_SMOOTH_THREADS), lds, s, history, table_dev, records,
                        lead_frames, smoothed, status);
+    return hipSuccess;
+}
+
+hipError_t ekf_launch_batch_smooth(const double* history, const EkfSmoothRec* tables_dev, const EkfBatchSmoothMember* members_dev,
+                                   int32_t members, int32_t nmax, double* smoothed, int32_t* status, hipStream_t s) {
+    const size_t lds = (size_t)ekf_smooth_tri_count(nmax) * 8;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ekf_batch_smooth_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ekf_batch_smooth_kernel, dim3(members), dim3(EKF_SMOOTH_THREADS), lds, s, history, tables_dev,
+                       members_dev, smoothed, status);
     return hipSuccess;
 }
 

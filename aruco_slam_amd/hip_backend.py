@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = (
     "ekf_batch_set_map_frozen", "ekf_batch_get_map_frozen",
     "ekf_observe_log_recorded", "ekf_history_record_bytes", "ekf_history_bytes", "ekf_history_info", "ekf_history_record",
     "ekf_smooth_workspace_bytes", "ekf_smooth_history",
+    "ekf_batch_history_bytes", "ekf_batch_observe_logs_recorded", "ekf_batch_history_info", "ekf_batch_history_record",
+    "ekf_batch_history_table", "ekf_batch_smooth_workspace_bytes", "ekf_batch_smooth_history",
 )
 
 
@@ -162,6 +164,15 @@ def load_library(path: str | Path | None = None):
         "ekf_history_record": [vp, vp, C.c_int32, dp, dp, C.c_int32],
         "ekf_smooth_workspace_bytes": [vp, C.POINTER(C.c_size_t)],
         "ekf_smooth_history": [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int32, vp],
+        "ekf_batch_history_bytes": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_size_t)],
+        "ekf_batch_observe_logs_recorded": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, vp, vp, vp, vp, C.c_size_t,
+                                            vp, vp, vp, vp, vp, C.c_size_t],
+        "ekf_batch_history_info": [vp, C.c_int32, ip, C.c_int32, ip, ip, dp, dp, ip, ip],
+        "ekf_batch_history_record": [vp, vp, C.c_int32, C.c_int32, dp, dp, C.c_int32],
+        "ekf_batch_history_table": [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), ip, ip, dp, dp, dp, C.c_int32, ip,
+                                    ip, ip, ip, dp, ip],
+        "ekf_batch_smooth_workspace_bytes": [vp, C.POINTER(C.c_size_t)],
+        "ekf_batch_smooth_history": [vp, vp, C.c_size_t, vp, C.c_size_t, vp, ip],
         "ekf_remove_workspace_bytes": [vp, C.c_int32, C.POINTER(C.c_size_t)],
         "ekf_remove_markers": [vp, ip, C.c_int32, vp, C.c_int64, vp, vp, C.c_size_t],
         "ekf_batch_remove_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],

@@ -875,7 +875,8 @@ int ekf_batch_get_map_frozen(const ekf_batch *b, int32_t *out /* [B] */);
  *   resident   every N_r <= 160 (n <= 50): ONE launch of ONE workgroup runs the whole pass, P_p as a packed triangle in LDS
  *   blocked    any larger N_r (up to 8064 dims), or flags bit 0: per step a short launch sequence around the blocked f64
  *              Cholesky of the wide frames
- * Not in this interface: recording from per-frame ekf_observe calls, smoothed covariances, ekf_batch. */
+ * Not in this interface: recording from per-frame ekf_observe calls, smoothed covariances (ekf_batch: "Batch smoothing"
+ * below). */
 int ekf_observe_log_recorded(ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames,
                              const double *poses_dev, const double *rows_dev, const double *scale, const double *motion,
                              void *log_ws, size_t log_ws_bytes, double *trajectory_dev, double *mahal_dev,
@@ -888,6 +889,78 @@ int ekf_history_record(ekf_filter *f, const void *history_dev, int32_t r, double
 int ekf_smooth_workspace_bytes(const ekf_filter *f, size_t *bytes);
 int ekf_smooth_history(ekf_filter *f, const void *history_dev, size_t history_bytes, void *ws, size_t ws_bytes, int32_t flags,
                        double *smoothed_dev /* [frames][7] */);
+
+/* ---- Batch smoothing: recorded replays of an ekf_batch, one backward pass per member.  The smoothing rules
+ * above, applied per member with the member's own q_cam / q_err / q_lm, with these additions.
+ *   When a frame is recorded.  A member's frame is recorded when it changed the member: it was stepped, or moved by a motion
+ *   with any non-zero component, or both.  Which frames the gate left unstepped and -- the motions being a device array --
+ *   which motions are non-zero is known on the device only.  So the HOST gives a record slot to every frame that can change
+ *   the member: every frame with detections, and every frame at all when the call carries motions; a slot has the size of
+ *   the dims that frame ends with (first sightings are validated on the host, so the plan knows them).  The DEVICE writes,
+ *   for every frame of the call, flag (0: no record, 1: stepped, 2: moved only, -1: the member has failed, at this frame or
+ *   before) and s_eff as f64 (the scale the frame was stepped with: 1.0 in a batch without EKF_FLAG_FRAME_SCALE; 0 for a frame
+ *   that was not stepped).  The frame on which a member fails (EKF_ERR_NUMERIC) writes no record, and no later frame does.
+ *   History layout.  One region per member, member after member: [256 B: state[0:7] at the start of the call | slots], a slot
+ *   [state N | triangle N (N + 1) / 2] doubles packed column by column and rounded up to 256 bytes (ekf_history_record_bytes,
+ *   unchanged); a member without a log has its 256 bytes.  Behind the last region the words of the call, each piece rounded up
+ *   to 256 bytes: the regions' offsets [B] i64, the slots' offsets [Ftot] i64, flag [Ftot] i32, s_eff [Ftot] f64 and, in a
+ *   call with motions, a copy of the motions [Ftot][6] f64.
+ *   Smoothed rows.  After the replay the host reads flag, s_eff and the motions back and builds one table per member: frame,
+ *   dims, slot, Q_eff = fl(s_eff q) with the member's q, the motion.  Frame t gets x^s[0:7] of the member's last record at or
+ *   before it; frames before the first record repeat the member's camera at the start of the call.  A member that failed in
+ *   the replay has NaN rows from its failing frame on, as its trajectory has; its records before that frame are smoothed from
+ *   the last good one.  A member with a P_p that is not positive definite has NaN on ALL its rows and EKF_ERR_NUMERIC in its
+ *   entry of the pass's status [B]; no other member notices, the call still returns EKF_OK, and the pass never writes state, P
+ *   or the replay status of any member.
+ *   One workgroup per member runs the resident pass of the single filter (the same device function) over the member's own
+ *   records; more members than compute units run as further rounds of workgroups; nothing synchronises across workgroups.
+ *   Every sum is one ascending fma chain in a fixed thread: a member's smoothed rows do not depend on the batch around it.
+ * Bit rule of the recording: trajectory, nis, cam_cov, d^2, state, P, landmark counts, pending scales and status of a recorded
+ * call are bit for bit those of ekf_batch_observe_logs_moved: recording only reads the members.  A call that does not record
+ * launches the kernels it launched before.
+ * Supported: EKF_MODEL_EKF, EKF_QUAT_SCALAR_FIRST, mapping members that end the call with at most 50 landmarks (every record
+ * has N_r <= 160: the resident tier), the one-column window kernel (max_visible <= 16), any mix of per-member gate, row noise,
+ * frame scale, motion, per-member noise constants and initial poses, members without a log.
+ * REFUSED with EKF_ERR_STATE before anything is enqueued, nothing changed: EKF_MODEL_ROTATIONS, EKF_QUAT_AS_WRITTEN, a batch
+ * with EKF_FLAG_BATCH_LARGE_MAPS or EKF_FLAG_BATCH_WIDE_FRAMES, a frozen member with a log, a plan that takes a member past 50
+ * landmarks; a history buffer smaller than ekf_batch_history_bytes: EKF_ERR_CAPACITY.
+ * Binding: the pass and the getters run over the handle's LAST recorded call and that buffer only (EKF_ERR_STATE otherwise),
+ * and are refused after ekf_batch_reset, ekf_batch_set_member or ekf_batch_remove_markers touched any member since.
+ *   ekf_batch_history_bytes          the size of the history from the logs alone (checked as ekf_batch_observe_logs checks
+ *                                    them); with_motion != 0: the call will carry motions.  Waits for the stream.
+ *   ekf_batch_observe_logs_recorded  ekf_batch_observe_logs_moved plus the history buffer; rows, scale, motion, nis, cam_cov
+ *                                    and mahal may each be NULL.
+ *   ekf_batch_history_info           the fields of ekf_history_info for one member, frames counted within its log.  Waits for
+ *                                    the stream (the first getter after a recording copies the call's words back).
+ *   ekf_batch_history_record         record r of a member, unpacked and mirrored.
+ *   ekf_batch_history_table          the table builder alone, no handle and no device: from flag / s_eff / motion (or NULL)
+ *                                    [Ftot], slot / dims [Ftot], member_frames [B + 1] and noise [B][6] (ekf_config order) it
+ *                                    gives per member (records, first row, end of the lead rows, first NaN row, end row) and,
+ *                                    per record in member order, its member, its rows [frame0, frame1), Q_eff [3], moved.
+ *   ekf_batch_smooth_workspace_bytes, ekf_batch_smooth_history: the pass; smoothed_dev [Ftot][7], status_out [B] on the host
+ *                                    (or NULL).  Waits for the stream before it returns.
+ * Not in this interface: a blocked tier for batches (members beyond 50 landmarks), recording in the HBM-resident window
+ * kernels (large maps, wide frames), smoothed covariances, smoothed landmark outputs. */
+int ekf_batch_history_bytes(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets, const int64_t *member_frames,
+                            int32_t with_motion, size_t *bytes);
+int ekf_batch_observe_logs_recorded(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets,
+                                    const int64_t *member_frames, const double *poses_dev, const double *rows_dev,
+                                    const double *scale_dev, const double *motion_dev, void *log_ws, size_t log_ws_bytes,
+                                    double *trajectory_dev, double *nis_dev, double *cam_cov_dev, double *mahal_dev,
+                                    void *history_dev, size_t history_bytes);
+int ekf_batch_history_info(ekf_batch *b, int32_t member, int32_t *records, int32_t capacity, int32_t *frame, int32_t *dims,
+                           double *s_eff, double *motion /* [capacity][6] */, int32_t *stepped,
+                           int32_t *frame_record /* [F_b] */);
+int ekf_batch_history_record(ekf_batch *b, const void *history_dev, int32_t member, int32_t r, double *state_out,
+                             double *cov_out, int32_t dims);
+int ekf_batch_history_table(int32_t members, const int64_t *member_frames, const int64_t *slot, const int32_t *dims,
+                            const int32_t *flag, const double *s_eff, const double *motion, const double *noise,
+                            int32_t capacity, int32_t *total, int32_t *member_rows /* [B][5] */,
+                            int32_t *rec_member /* [capacity] */, int32_t *rec_rows /* [capacity][2] */,
+                            double *rec_q /* [capacity][3] */, int32_t *rec_moved /* [capacity] */);
+int ekf_batch_smooth_workspace_bytes(ekf_batch *b, size_t *bytes);
+int ekf_batch_smooth_history(ekf_batch *b, const void *history_dev, size_t history_bytes, void *ws, size_t ws_bytes,
+                             double *smoothed_dev /* [Ftot][7] */, int32_t *status_out /* [B] host, or NULL */);
 
 const char *ekf_last_error_string(void);
 

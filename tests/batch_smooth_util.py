@@ -1,0 +1,138 @@
+"""Helpers of the batch smoothing tests (``test_batch_smooth_cpu.py`` here, ``test_batch_smooth.py`` on the GPU): the logs
+of ``smooth_util`` in the layout ``EKFBatch.process_detection_logs`` takes, the size of a batch history restated in Python,
+the single-filter oracle of ``smooth_util`` with a member's own noise constants, and the replica fixture."""
+from __future__ import annotations
+
+import contextlib
+
+import numpy as np
+
+import motion_util as mu
+import replica_util as ru
+import smooth_util as su
+import update_sweep_util as sw
+
+INIT = sw.INIT
+GROWING = (16, 34, 2)                    # smooth_util.growing_scene(16, 34, tail=2): 37 frames, widest 16, N grows to 160
+REPLICA_SIGMA, REPLICA_SEED = 0.005, 11  # smooth_replicas on the tracking log: 5 mm more on every tvec component
+REPLICAS = 4
+
+
+def scene_log(name, *, with_motion=None, with_scale=None, seed=None):
+    """The named scene as a log dict of ``process_detection_logs``.  "tracking" and "growing" carry no odometry and no
+    scales; with_motion / with_scale = True gives them exact-zero motions / scales of 1 (a batch call carries them for every
+    member or for none), which is the same filter.  "ragged" carries its own unless told False."""
+    if name == "growing":
+        log, motion, scale = su.growing_scene(GROWING[0], GROWING[1], tail=GROWING[2]), None, None
+    elif name == "ragged" and seed is not None:
+        log = mu.ragged_motion_log("ekf", seed=seed)
+        motion, scale = log["motion"], su.RAGGED_SCALE
+    else:
+        log, motion, scale = su.scene(name)
+    frames = len(log["offsets"]) - 1
+    out = {"ids": log["ids"], "poses": log["poses"], "offsets": log["offsets"], "has_detections": np.diff(log["offsets"]) > 0}
+    if "truth" in log:
+        out["truth"] = log["truth"]
+    if with_motion or (with_motion is None and motion is not None):
+        out["motion"] = np.zeros((frames, 6)) if motion is None else np.asarray(motion)
+    if with_scale or (with_scale is None and scale is not None):
+        out["scale"] = np.ones(frames) if scale is None else np.asarray(scale)
+    return out
+
+
+def prefix(log, frames):
+    """The first ``frames`` frames of a log dict."""
+    d1 = int(log["offsets"][frames])
+    out = {"ids": log["ids"][:d1], "poses": log["poses"][:d1], "offsets": log["offsets"][:frames + 1],
+           "has_detections": log["has_detections"][:frames]}
+    for key in ("motion", "scale"):
+        if key in log:
+            out[key] = log[key][:frames]
+    return out
+
+
+def suffix(log, first):
+    """The frames from ``first`` on."""
+    d0 = int(log["offsets"][first])
+    out = {"ids": log["ids"][d0:], "poses": log["poses"][d0:], "offsets": log["offsets"][first:] - d0,
+           "has_detections": log["has_detections"][first:]}
+    for key in ("motion", "scale"):
+        if key in log:
+            out[key] = log[key][first:]
+    return out
+
+
+def initial_poses(members):
+    """[B, 10]: the identity pose, then poses shifted and turned a little (unit quaternions, zero error state)."""
+    out = np.tile(INIT, (members, 1))
+    for b in range(1, members):
+        out[b, 0:3] = [0.1 * b, -0.05 * b, 0.02 * b]
+        q = np.array([1.0, 0.01 * b, -0.02 * b, 0.015 * b])
+        out[b, 3:7] = q / np.linalg.norm(q)
+    return out
+
+
+def record_bytes(dims):
+    return -(-(dims + dims * (dims + 1) // 2) * 8 // 256) * 256
+
+
+def history_bytes(members, with_motion):
+    """``ekf_batch_history_bytes`` restated.  members: per member the list of (dims the frame ends with, the frame has
+    detections).  One region per member, [256 B | a slot per frame with detections, or per frame at all with motions], then
+    the words of the call, each piece rounded up to 256 bytes: regions' offsets [B] i64, slots' offsets [F] i64, flag [F]
+    i32, s_eff [F] f64 and with motions a copy of them [F][6] f64."""
+    up = lambda n: -(-n // 256) * 256
+    frames = sum(len(m) for m in members)
+    total = sum(256 + sum(record_bytes(d) for d, has in m if has or with_motion) for m in members)
+    return total + up(8 * len(members)) + up(8 * frames) + up(4 * frames) + up(8 * frames) + (up(48 * frames) if with_motion else 0)
+
+
+@contextlib.contextmanager
+def member_noise(q_cam, q_err, q_lm):
+    """The oracle of ``smooth_util`` with a member's own process-noise constants."""
+    old = su.Q_CAM, su.Q_ERR, su.Q_LM
+    su.Q_CAM, su.Q_ERR, su.Q_LM = float(q_cam), float(q_err), float(q_lm)
+    try:
+        yield
+    finally:
+        su.Q_CAM, su.Q_ERR, su.Q_LM = old
+
+
+def member_oracle(records, frames, start, noise_row):
+    """``smooth_util.smooth_records`` for one member; noise_row: its constants in ``batch.NOISE_KEYS`` order."""
+    with member_noise(noise_row[3], noise_row[4], noise_row[5]):
+        return su.smooth_records(records, frames, start)
+
+
+def table_from_flags(lib, member_frames, slot, dims, flag, s_eff, motion, noise):
+    """``ekf_batch_history_table`` (no handle, no device): (member_rows [B, 5], rec_member [R], rec_rows [R, 2], rec_q [R, 3],
+    rec_moved [R])."""
+    import ctypes as C
+    mf = np.ascontiguousarray(member_frames, dtype=np.int64)
+    members = mf.shape[0] - 1
+    slot, dims, flag = (np.ascontiguousarray(slot, dtype=np.int64), np.ascontiguousarray(dims, dtype=np.int32),
+                        np.ascontiguousarray(flag, dtype=np.int32))
+    s_eff, noise = np.ascontiguousarray(s_eff, dtype=np.float64), np.ascontiguousarray(noise, dtype=np.float64)
+    motion = None if motion is None else np.ascontiguousarray(motion, dtype=np.float64)
+    ip, lp, dp = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    cap = max(int((flag > 0).sum()), 1)
+    total = C.c_int32()
+    rows = np.zeros((members, 5), dtype=np.int32)
+    rec_member, rec_rows, rec_moved = np.zeros(cap, np.int32), np.zeros((cap, 2), np.int32), np.zeros(cap, np.int32)
+    rec_q = np.zeros((cap, 3))
+    rc = lib.ekf_batch_history_table(members, mf.ctypes.data_as(lp), slot.ctypes.data_as(lp), dims.ctypes.data_as(ip),
+                                     flag.ctypes.data_as(ip), s_eff.ctypes.data_as(dp),
+                                     None if motion is None else motion.ctypes.data_as(dp), noise.ctypes.data_as(dp), cap,
+                                     C.byref(total), rows.ctypes.data_as(ip), rec_member.ctypes.data_as(ip),
+                                     rec_rows.ctypes.data_as(ip), rec_q.ctypes.data_as(dp), rec_moved.ctypes.data_as(ip))
+    assert rc == 0, rc
+    r = total.value
+    return rows, rec_member[:r], rec_rows[:r], rec_q[:r], rec_moved[:r]
+
+
+def replica_logs():
+    """The tracking log as replicas 0 .. REPLICAS - 1 consume it in ``smooth_replicas(log, REPLICA_SIGMA, REPLICA_SEED)``: the
+    host mirror of the device's noise (``replica_util``)."""
+    log = scene_log("tracking")
+    poses = ru.replica_poses(log["poses"], np.full((REPLICAS, 6), REPLICA_SIGMA), REPLICA_SEED, REPLICAS)
+    return log, [{**log, "poses": poses[r]} for r in range(REPLICAS)]

@@ -32,6 +32,13 @@ the steady segment once as a warm-up, is restored again and runs it timed.  Line
 both.  Composes with --replicas, --corners, --large-maps, --max-visible, --model and --motion (motions on every frame of both
 batches).  Kernel times: `rocprofv3 --kernel-trace --stats -- python tools/batch_bench.py --frozen --members 256 ...`
 (profiles/batch_frozen/).
+--smooth: batch smoothing (EKFBatch.smooth_detection_logs; EKF, scalar_first, n <= 50).  Every member replays its whole
+ragged log (bootstrap and --steady frames, default 200 here; every frame is a record) from a reset batch.  One untimed round,
+then five timed ones of: the plain replay, the recorded replay (us per frame, aggregate, and the bytes/s the history implies),
+and the batched backward pass (EKFBatch.smooth_history: us per record per member, aggregate records/s); median and
+min .. max.  Beside them the same work the only way there was before: EKF.smooth_detection_log, one filter after the other,
+timed over --single-members of the logs and scaled to the batch size.  Default members: 16 256.  Lines go to
+profiles/batch_smooth/batch_bench.jsonl.
 """
 from __future__ import annotations
 
@@ -93,7 +100,14 @@ def main():
     ap.add_argument("--frozen", action="store_true",
                     help="the shape twice from one restored map: every member frozen (freeze_map) against mapping; "
                          "frames/s of both")
+    ap.add_argument("--smooth", action="store_true",
+                    help="batch smoothing: recorded against plain replay, the batched backward pass, and the same logs "
+                         "through a loop of single filters (EKF.smooth_detection_log)")
+    ap.add_argument("--single-members", type=int, default=8,
+                    help="--smooth: how many members the single-filter loop really runs (its time per member is reported)")
     args = ap.parse_args()
+    if args.smooth:
+        return smooth(args)
     import torch
     from aruco_slam_amd.batch import EKFBatch
     from aruco_slam_amd.filters.ekf_with_rotations import EKF_Rotations
@@ -288,6 +302,78 @@ def frozen(args, n, m_hi, visible):
         print(json.dumps(line), flush=True)
         lines.append(line)
     append(args.out, lines)
+
+
+def smooth(args):
+    """--smooth: see the module docstring."""
+    import torch
+    from aruco_slam_amd.batch import EKFBatch
+    from aruco_slam_amd.filters.extended_kalman_filter import EKF
+    from aruco_slam_amd.synthetic import ragged_log
+    if not torch.cuda.is_available():
+        raise SystemExit("batch_bench needs a HIP device")
+    n = args.landmarks or 50
+    m_hi = args.max_visible or 10
+    if n > 50 or m_hi > 16 or args.model != "ekf":
+        raise SystemExit("--smooth: EKF, at most 50 landmarks and 16 detections per frame (the resident tier)")
+    steady = args.steady if args.steady != 500 else 200
+    members = args.members or [16, 256]
+    logs = []
+    for s in range(max(members)):
+        lg = ragged_log(n, (1, m_hi), steady, seed=s)
+        logs.append({k: lg[k] for k in ("ids", "poses", "offsets", "has_detections")})
+    kw = dict(max_landmarks=n, max_visible=16, quat_update="scalar_first")
+    median = lambda v: float(np.median(v))
+    lines = []
+    # the loop of single filters: what smoothing many logs costs without the batch
+    single = []
+    for lg in logs[:max(1, args.single_members) + 1]:      # (the first one is the warm-up)
+        flt = EKF(INIT, max_landmarks=n, max_visible=16, cov_dtype="float64", quat_update="scalar_first")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        flt.smooth_detection_log(lg["ids"], lg["poses"], lg["offsets"], lg["has_detections"])
+        single.append(time.perf_counter() - t0)
+        del flt
+    single = single[1:] or single
+    for B in members:
+        frames = sum(len(lg["offsets"]) - 1 for lg in logs[:B])
+        walls = {"plain": [], "recorded": [], "pass": []}
+        batch = EKFBatch(B, INIT, **kw)
+        for rnd in range(6):      # one untimed round, five timed
+            for name in ("plain", "recorded"):
+                batch.reset()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                batch.process_detection_logs(logs[:B], record=name == "recorded")
+                walls[name].append(time.perf_counter() - t0)
+            assert batch.status() == [0] * B
+            t0 = time.perf_counter()
+            batch.smooth_history()
+            walls["pass"].append(time.perf_counter() - t0)
+            assert not batch.last_smooth_status.any()
+        records = [len(batch.history_records(b)) for b in range(min(B, 4))]
+        per_member = float(np.mean(records))      # (every frame of these logs is a record)
+        hist_bytes = int(batch.last_history.numel())
+        stat = {k: (median(v[1:]), min(v[1:]), max(v[1:])) for k, v in walls.items()}
+        line = {"tool": "batch_bench", "smooth": True, "members": B, "n": n, "m": [1, m_hi], "frames_per_member": frames / B,
+                "records_per_member": per_member, "rounds": 5, "history_bytes": hist_bytes,
+                "plain_us_per_frame": round(1e6 * stat["plain"][0] / frames, 3),
+                "recorded_us_per_frame": round(1e6 * stat["recorded"][0] / frames, 3),
+                "plain_wall_s": [round(x, 6) for x in stat["plain"]], "recorded_wall_s": [round(x, 6) for x in stat["recorded"]],
+                "recording_bytes_per_s": round(hist_bytes / max(stat["recorded"][0], 1e-12), 1),
+                "pass_wall_s": [round(x, 6) for x in stat["pass"]],
+                "pass_us_per_record_per_member": round(1e6 * stat["pass"][0] / per_member, 3),
+                "pass_records_per_s": round(B * per_member / stat["pass"][0], 1),
+                "single_loop_members_timed": len(single), "single_smooth_s_per_member": round(median(single), 6),
+                "single_loop_s_for_these_members": round(median(single) * B, 4),
+                "batch_smooth_s": round(stat["recorded"][0] + stat["pass"][0], 6),
+                "speedup_over_single_loop": round(median(single) * B / (stat["recorded"][0] + stat["pass"][0]), 2)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del batch
+    out = args.out if args.out != str(REPO / "profiles" / "batch" / "batch_bench.jsonl") else \
+        str(REPO / "profiles" / "batch_smooth" / "batch_bench.jsonl")
+    append(out, lines)
 
 
 def replicas(args, n, m_hi, visible):

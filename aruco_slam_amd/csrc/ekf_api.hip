@@ -1644,6 +1644,55 @@ int64_t history_nmax(const ekf_filter* f) {
     return nmax;
 }
 
+// the table the smoothing kernels read, from the records of the last recorded replay (F: the frames of that call)
+void smooth_table(ekf_filter* f, int32_t F) {
+    const int32_t R = (int32_t)f->hist.recs.size();
+    std::vector<EkfSmoothRec>& table = f->hist.table;
+    table.assign((size_t)R, EkfSmoothRec{});
+    for (int32_t r = 0; r < R; ++r) {
+        const auto& h = f->hist.recs[r];
+        EkfSmoothRec& e = table[r];
+        e.off = (int64_t)(h.off / 8);
+        e.dims = h.dims;
+        e.moved = h.moved;
+        for (int i = 0; i < 6; ++i) e.u[i] = h.u[i];
+        const EkfNoise nz = frame_noise(f, h.s_eff);
+        e.q[0] = nz.q_cam;
+        e.q[1] = nz.q_err;
+        e.q[2] = nz.q_lm;
+        e.frame0 = h.frame;
+        e.frame1 = r + 1 < R ? f->hist.recs[r + 1].frame : F;
+    }
+}
+
+// the covariance pass: the blocked step's pieces with one xinv per block column, then A, Z, T and P^s, all [npad][npad]
+struct SmoothCovLayout {
+    SmoothLayout s;
+    size_t A, Z, T, Ps, total;
+    int64_t npad;
+};
+SmoothCovLayout smooth_cov_layout(size_t records, int64_t nmax) {
+    const size_t npad = (size_t)round_up(std::max<int64_t>(nmax, 1), EKF_WIDE_BLOCK);
+    Carve w;
+    w.take(256);
+    SmoothCovLayout L{};
+    L.npad = (int64_t)npad;
+    L.s.table = w.take(std::max<size_t>(records, 1) * sizeof(EkfSmoothRec));
+    L.s.xs = w.take(npad * 8);
+    L.s.xp = w.take(npad * 8);
+    L.s.yv = w.take(npad * 8);
+    L.s.wv = w.take(npad * 8);
+    L.s.cv = w.take(npad * 8);
+    L.s.xinv = w.take(npad / EKF_WIDE_BLOCK * EKF_WIDE_BLOCK * EKF_WIDE_BLOCK * 8);
+    L.s.M = w.take(npad * npad * 8);
+    L.A = w.take(npad * npad * 8);
+    L.Z = w.take(npad * npad * 8);
+    L.T = w.take(npad * npad * 8);
+    L.Ps = w.take(npad * npad * 8);
+    L.s.total = L.total = w.end;
+    return L;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1998,22 +2047,8 @@ int ekf_smooth_history(ekf_filter* f, const void* history_dev, size_t history_by
         HIP_TRY(hipGetLastError());
         return EKF_OK;
     }
-    std::vector<EkfSmoothRec>& table = f->hist.table;
-    table.assign((size_t)R, EkfSmoothRec{});
-    for (int32_t r = 0; r < R; ++r) {
-        const auto& h = f->hist.recs[r];
-        EkfSmoothRec& e = table[r];
-        e.off = (int64_t)(h.off / 8);
-        e.dims = h.dims;
-        e.moved = h.moved;
-        for (int i = 0; i < 6; ++i) e.u[i] = h.u[i];
-        const EkfNoise nz = frame_noise(f, h.s_eff);
-        e.q[0] = nz.q_cam;
-        e.q[1] = nz.q_err;
-        e.q[2] = nz.q_lm;
-        e.frame0 = h.frame;
-        e.frame1 = r + 1 < R ? f->hist.recs[r + 1].frame : F;
-    }
+    smooth_table(f, F);
+    const std::vector<EkfSmoothRec>& table = f->hist.table;
     char* w = static_cast<char*>(ws);
     int32_t* status = reinterpret_cast<int32_t*>(w);
     EkfSmoothRec* table_dev = reinterpret_cast<EkfSmoothRec*>(w + L.table);
@@ -2046,6 +2081,90 @@ int ekf_smooth_history(ekf_filter* f, const void* history_dev, size_t history_by
     }
     HIP_TRY(hipGetLastError());
     // the pass has its own status word: a P_p that is not positive definite is reported here and leaves nothing on the filter
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    int32_t st = 0;
+    HIP_TRY(hipMemcpy(&st, status, 4, hipMemcpyDeviceToHost));
+    if (st != 0) return fail(EKF_ERR_NUMERIC, "smoothing: a predicted covariance P_p is not positive definite");
+    return EKF_OK;
+}
+
+// ---- smoothed covariances (include/ekf_slam_hip.h, "Smoothed covariances"; kernels: ekf_smooth_cov.hip) -------------------
+int ekf_smooth_cov_workspace_bytes(const ekf_filter* f, size_t* bytes) {
+    if (!f) return fail(EKF_ERR_INVALID, "filter handle is NULL");
+    if (!bytes) return fail(EKF_ERR_INVALID, "bytes is NULL");
+    if (!f->hist.valid) return fail(EKF_ERR_STATE, "no recorded replay (ekf_observe_log_recorded), or the filter has changed since");
+    *bytes = smooth_cov_layout(f->hist.recs.size(), history_nmax(f)).total;
+    return EKF_OK;
+}
+
+int ekf_smooth_history_cov(ekf_filter* f, const void* history_dev, size_t history_bytes, void* ws, size_t ws_bytes, int32_t flags,
+                           double* smoothed_dev, double* cam_cov_dev, double* filt_cam_cov_dev, double* first_cov_dev) {
+    (void)flags;      // (the covariance pass has one tier)
+    int rc = check_ready(f);
+    if (rc) return rc;
+    if ((rc = smoothing_supported(f))) return rc;
+    if (!f->hist.valid) return fail(EKF_ERR_STATE, "no recorded replay (ekf_observe_log_recorded), or the filter has changed since");
+    if (history_dev != f->hist.buf || history_bytes < f->hist.bytes)
+        return fail(EKF_ERR_STATE, "not the history of this handle's last recorded replay");
+    const int32_t F = f->hist.frames, R = (int32_t)f->hist.recs.size();
+    if (F == 0) return EKF_OK;
+    if (!smoothed_dev || !cam_cov_dev) return fail(EKF_ERR_INVALID, "smoothed_dev or cam_cov_dev is NULL");
+    const int64_t nmax = history_nmax(f);
+    const SmoothCovLayout L = smooth_cov_layout((size_t)R, nmax);
+    if ((rc = check_device_buffers({ws}, ws_bytes, L.total, "ekf_smooth_cov_workspace_bytes"))) return rc;
+    if (L.npad > 8064) return fail(EKF_ERR_CAPACITY, "the covariance pass takes records of up to 8064 dims");
+    const double* hist = static_cast<const double*>(history_dev);
+    if (R == 0) {      // nothing changed the filter: the start pose on every row, and no covariance was ever recorded
+        ekf_launch_smooth_rows(hist, smoothed_dev, 0, F, f->stream);
+        ekf_launch_smooth_cov_nan(cam_cov_dev, filt_cam_cov_dev, 0, F, f->stream);
+        HIP_TRY(hipGetLastError());
+        return EKF_OK;
+    }
+    smooth_table(f, F);
+    const std::vector<EkfSmoothRec>& table = f->hist.table;
+    char* w = static_cast<char*>(ws);
+    int32_t* status = reinterpret_cast<int32_t*>(w);
+    EkfSmoothRec* table_dev = reinterpret_cast<EkfSmoothRec*>(w + L.s.table);
+    HIP_TRY(hipMemsetAsync(w, 0, 256, f->stream));
+    HIP_TRY(hipMemcpyAsync(table_dev, table.data(), (size_t)R * sizeof(EkfSmoothRec), hipMemcpyHostToDevice, f->stream));
+    EkfSmoothCov a{};
+    a.b.history = hist;
+    a.b.M = reinterpret_cast<double*>(w + L.s.M);
+    a.b.xs = reinterpret_cast<double*>(w + L.s.xs);
+    a.b.xp = reinterpret_cast<double*>(w + L.s.xp);
+    a.b.yv = reinterpret_cast<double*>(w + L.s.yv);
+    a.b.wv = reinterpret_cast<double*>(w + L.s.wv);
+    a.b.cv = reinterpret_cast<double*>(w + L.s.cv);
+    a.b.xinv = reinterpret_cast<double*>(w + L.s.xinv);
+    a.b.smoothed = smoothed_dev;
+    a.b.status = status;
+    a.A = reinterpret_cast<double*>(w + L.A);
+    a.Z = reinterpret_cast<double*>(w + L.Z);
+    a.T = reinterpret_cast<double*>(w + L.T);
+    a.Ps = reinterpret_cast<double*>(w + L.Ps);
+    a.ldp = L.npad;
+    a.cam_cov = cam_cov_dev;
+    a.filt_cam_cov = filt_cam_cov_dev;
+    a.first_cov = first_cov_dev;
+    const EkfSmoothRec& last = table[R - 1];
+    const int32_t lead = table[0].frame0;
+    // (P^s keeps its leading dimension over the pass; zero first, so that what a smaller record leaves unwritten is finite)
+    HIP_TRY(hipMemsetAsync(a.Ps, 0, (size_t)L.npad * L.npad * 8, f->stream));
+    HIP_TRY(hipMemcpyAsync(a.b.xs, hist + last.off, (size_t)last.dims * 8, hipMemcpyDeviceToDevice, f->stream));
+    ekf_launch_smooth_rows(hist + last.off, smoothed_dev, last.frame0, last.frame1, f->stream);
+    ekf_launch_smooth_rows(hist, smoothed_dev, 0, lead, f->stream);
+    ekf_launch_smooth_cov_nan(cam_cov_dev, filt_cam_cov_dev, 0, lead, f->stream);
+    a.b.rec = last;
+    a.first = R == 1;
+    ekf_launch_smooth_cov_last(a, f->stream);
+    for (int32_t r = R - 2; r >= 0; --r) {
+        a.b.rec = table[r];
+        a.b.next = table[r + 1];
+        a.first = r == 0;
+        ekf_launch_smooth_cov_step(a, f->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    // the pass has its own status word, as ekf_smooth_history: nothing sticky is left on the filter
     HIP_TRY(hipStreamSynchronize(f->stream));
     int32_t st = 0;
     HIP_TRY(hipMemcpy(&st, status, 4, hipMemcpyDeviceToHost));

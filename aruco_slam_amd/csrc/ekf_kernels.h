@@ -233,11 +233,12 @@ void ekf_launch_signal(unsigned long long* counter, unsigned long long value, hi
 // Wide frames (ekf_wide.hip): more detections than the gather kernel takes (EKF m > 64, EKF_Rotations m > 50).
 // kpad <= EKF_WIDE_REUSE_ROWS: measurement, A and S (into `sblk`), then the stage solve / panel kernels.  Beyond: S into
 // `lmat`, blocked Cholesky over block columns of EKF_WIDE_BLOCK rows (rows padded to rp = k rounded up to that), with A
-// copied to `aw` [rp][lda] f64 and turned into W there; `xinv`: EKF_WIDE_BLOCK^2 doubles.
+// copied to `aw` [rp][lda] f64 and turned into W there; `xinv`: EKF_WIDE_BLOCK^2 doubles (per block column, xinv_stride
+// doubles apart, when xinv_stride != 0: the covariance smoother reads every L_BB^-1 again).
 #define EKF_WIDE_REUSE_ROWS 384
 #define EKF_WIDE_BLOCK 64
 template <typename T> void ekf_launch_wide_front(const EkfFrame& fr, double* aw, int rp, hipStream_t s);
-void ekf_launch_wide_factor(const EkfFrame& fr, double* aw, double* xinv, int rp, hipStream_t s);
+void ekf_launch_wide_factor(const EkfFrame& fr, double* aw, double* xinv, int rp, hipStream_t s, int64_t xinv_stride = 0);
 template <typename T> void ekf_launch_wide_finish(const EkfFrame& fr, const double* aw, hipStream_t s);
 
 template <typename T>
@@ -330,6 +331,30 @@ struct EkfSmoothBlocked {
     int32_t* status;            // [0] sticky EKF_ST_NOT_SPD, [1..2] diagnostics of the factorisation kernels
 };
 void ekf_launch_smooth_blocked_step(const EkfSmoothBlocked& a, hipStream_t s);
+// The step's two halves around the factorisation, for whoever factors with right-hand sides of its own (ekf_smooth_cov.hip):
+// prepare = expand / move / Q_eff and delta (M = P_p, xp, yv), solve = backward substitution and finish (xs, the rows).
+void ekf_launch_smooth_blocked_prepare(const EkfSmoothBlocked& a, hipStream_t s);
+void ekf_launch_smooth_blocked_solve(const EkfSmoothBlocked& a, hipStream_t s);
+
+// Smoothed covariances (ekf_smooth_cov.hip; include/ekf_slam_hip.h: the covariance rule): the blocked step with A = F~ P_r
+// riding along the factorisation, then Z = L^-T W, T = P^s_{r+1} Z, D = -W^T W + Z^T T (lower tiles) and
+// P^s_r = P_r + D mirrored over P^s_{r+1}.  Workspace pieces beyond the blocked step's (all device, npad = dims of `rec`
+// rounded up to EKF_WIDE_BLOCK): xinv [npad / 64][64 * 64] (b.xinv), A, Z, T [npad][npad], Ps [ldp][ldp] with ldp fixed
+// over the pass (zero at the start, so that its padding is finite).
+struct EkfSmoothCov {
+    EkfSmoothBlocked b;
+    double *A, *Z, *T, *Ps;
+    int64_t ldp;
+    double* cam_cov;            // [frames][10][10]
+    double* filt_cam_cov;       // [frames][10][10] or NULL
+    double* first_cov;          // [N_0][N_0] or NULL; written at the step whose `rec` is record 0 (first != 0)
+    int32_t first;
+};
+// P^s_{R-1} = P_{R-1}: b.rec is the LAST record (b.next unused); Ps and the record's output rows
+void ekf_launch_smooth_cov_last(const EkfSmoothCov& a, hipStream_t s);
+void ekf_launch_smooth_cov_step(const EkfSmoothCov& a, hipStream_t s);
+// covariance rows [f0, f1) of cam_cov (and filt_cam_cov) <- NaN: frames before the first record
+void ekf_launch_smooth_cov_nan(double* cam_cov, double* filt_cam_cov, int32_t f0, int32_t f1, hipStream_t s);
 // Batch smoothing (include/ekf_slam_hip.h, "Batch smoothing"): workgroup b of ekf_batch_smooth_kernel runs the resident pass
 // over member b's records.  Offsets of the table entries count doubles from the start of the WHOLE history buffer, their
 // frame0 / frame1 are rows of smoothed [Ftot][7].

@@ -346,7 +346,7 @@ hipError_t ekf_launch_batch_smooth(const double* history, const EkfSmoothRec* ta
     return hipSuccess;
 }
 
-void ekf_launch_smooth_blocked_step(const EkfSmoothBlocked& a, hipStream_t s) {
+void ekf_launch_smooth_blocked_prepare(const EkfSmoothBlocked& a, hipStream_t s) {
     const int N = a.rec.dims, npad = (N + EKF_WIDE_BLOCK - 1) / EKF_WIDE_BLOCK * EKF_WIDE_BLOCK;
     hipLaunchKernelGGL(ekf_smooth_expand_kernel, dim3(npad), dim3(256), 0, s, a, npad);
     if (a.next.moved) {      // the filter's own move on (M, xp): P_p before Q, x_p
@@ -360,6 +360,17 @@ void ekf_launch_smooth_blocked_step(const EkfSmoothBlocked& a, hipStream_t s) {
         ekf_launch_motion<double>(m, s);
     }
     hipLaunchKernelGGL(ekf_smooth_prepare_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, a, npad);
+}
+
+void ekf_launch_smooth_blocked_solve(const EkfSmoothBlocked& a, hipStream_t s) {
+    const int N = a.rec.dims, npad = (N + EKF_WIDE_BLOCK - 1) / EKF_WIDE_BLOCK * EKF_WIDE_BLOCK;
+    hipLaunchKernelGGL(ekf_smooth_backsub_kernel, dim3(1), dim3(EKF_SMOOTH_THREADS), (size_t)npad * 8, s, a, npad);
+    hipLaunchKernelGGL(ekf_smooth_finish_kernel, dim3(1), dim3(EKF_SMOOTH_THREADS), 0, s, a);
+}
+
+void ekf_launch_smooth_blocked_step(const EkfSmoothBlocked& a, hipStream_t s) {
+    const int N = a.rec.dims, npad = (N + EKF_WIDE_BLOCK - 1) / EKF_WIDE_BLOCK * EKF_WIDE_BLOCK;
+    ekf_launch_smooth_blocked_prepare(a, s);
     // the blocked Cholesky of the wide frames with no columns of A: L over M, y = L^-1 delta over the right-hand side
     EkfFrame fr{};
     fr.lmat = a.M;
@@ -368,6 +379,5 @@ void ekf_launch_smooth_blocked_step(const EkfSmoothBlocked& a, hipStream_t s) {
     fr.ncols = 0;
     fr.status = a.status;
     ekf_launch_wide_factor(fr, nullptr, a.xinv, npad, s);
-    hipLaunchKernelGGL(ekf_smooth_backsub_kernel, dim3(1), dim3(EKF_SMOOTH_THREADS), (size_t)npad * 8, s, a, npad);
-    hipLaunchKernelGGL(ekf_smooth_finish_kernel, dim3(1), dim3(EKF_SMOOTH_THREADS), 0, s, a);
+    ekf_launch_smooth_blocked_solve(a, s);
 }

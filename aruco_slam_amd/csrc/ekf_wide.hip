@@ -320,9 +320,10 @@ __global__ __launch_bounds__(256) void ekf_wide_update_kernel(EkfFrame fr, doubl
     }
 }
 
-void ekf_launch_wide_factor(const EkfFrame& fr, double* aw, double* xinv, int rp, hipStream_t s) {
+// xinv_stride (doubles): block column B leaves its X = L_BB^-1 at xinv + B * xinv_stride (0: every block in the same place)
+void ekf_launch_wide_factor(const EkfFrame& fr, double* aw, double* xinv, int rp, hipStream_t s, int64_t xinv_stride) {
     const int nbw = rp / WB, nchunk = fr.ncols / 64;
-    for (int B = 0; B < nbw; ++B) {
+    for (int B = 0; B < nbw; ++B, xinv += xinv_stride) {
         const int nrem = nbw - B - 1;
         hipLaunchKernelGGL(ekf_wide_potrf_kernel, dim3(1), dim3(256), 0, s, fr, xinv, B);
         hipLaunchKernelGGL(ekf_wide_panel_kernel, dim3(nrem + nchunk + 1), dim3(256), 0, s, fr, aw, xinv, B, nbw);

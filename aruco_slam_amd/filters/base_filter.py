@@ -456,7 +456,8 @@ class BaseFilter:
 
     def _replay_detection_log(self, ids, poses, offsets, has_detections, mahal, noise, scale, motion, smooth):
         """``process_detection_log``; ``smooth``: the replay is recorded (``observe_log(history=)``), the backward pass runs
-        over the records, and the smoothed trajectory comes back behind the filtered one (``EKF.smooth_detection_log``)."""
+        over the records, and the smoothed trajectory comes back behind the filtered one (``EKF.smooth_detection_log``);
+        ``smooth="cov"``: the pass forms the covariances too, and ``filtered_cov``, ``smoothed_cov`` [F, 10, 10] follow."""
         import torch
         backend = self.backend
         plan = plan_detection_log(self.landmarks, self.num_landmarks, ids, offsets, has_detections, self.map_frozen)
@@ -505,8 +506,15 @@ class BaseFilter:
             self._tentative.confirm(plan.new_landmarks)
         out = (traj.cpu().numpy(),)
         if smooth:
-            self._smoothed = backend.smooth_history(history, traj.shape[0]).cpu().numpy()
-            out += (self._smoothed,)
+            self._smoothed_cov = None
+            if smooth == "cov":
+                res = backend.smooth_history_cov(history, traj.shape[0])
+                self._smoothed = res["smoothed"].cpu().numpy()
+                self._smoothed_cov = res["cam_cov"].cpu().numpy()
+                out += (self._smoothed, res["filt_cam_cov"].cpu().numpy(), self._smoothed_cov)
+            else:
+                self._smoothed = backend.smooth_history(history, traj.shape[0]).cpu().numpy()
+                out += (self._smoothed,)
         if mahal:
             d2 = np.full(plan.keep.shape[0], np.nan)
             d2[plan.keep] = mahal_t.cpu().numpy()

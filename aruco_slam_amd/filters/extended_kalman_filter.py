@@ -8,6 +8,8 @@ dictionary stays here on the host; state and covariance live in HBM.
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from ..hip_backend import HipEkf
@@ -27,6 +29,15 @@ XYZ_DIMS = slice(0, 3)
 QUAT_DIMS = slice(3, 7)
 ERROR_DIMS = slice(7, 10)
 LM_DIMS = 3
+
+
+def _cov_keyword(plain):
+    """Gives ``smooth_detection_log`` its keyword-only option ``cov``: ``cov=True`` runs the same replay with
+    the covariance pass behind it; without it the call is the plain method, positional arguments as they were."""
+    @functools.wraps(plain)
+    def call(self, *args, cov=False, **kw):
+        return self._smooth_log("cov", *args, **kw) if cov else plain(self, *args, **kw)
+    return call
 
 
 class EKF(BaseFilter):
@@ -174,6 +185,7 @@ class EKF(BaseFilter):
         return self.landmarks.items()
 
     # -- offline smoothing (the reference's run_offline.py flow) ------
+    @_cov_keyword
     def smooth_detection_log(self, ids, poses, offsets, has_detections=None, noise=None, scale=None, motion=None,
                              mahal=False):
         """``process_detection_log`` with a Rauch-Tung-Striebel backward pass behind it: the replay is recorded on the
@@ -181,7 +193,15 @@ class EKF(BaseFilter):
         ``mahal=True``).  The log is planned, the buffers grow and everything is validated as in ``process_detection_log``,
         and the filter is left exactly where that call leaves it, bit for bit.  The smoothed log stays with the filter:
         ``get_cam_estimate(i)`` returns its row i.  Needs ``quat_update="scalar_first"`` and the float64 covariance; a
-        frozen map is refused (``ValueError``, before anything runs)."""
+        frozen map is refused (``ValueError``, before anything runs).
+        Keyword-only ``cov=True`` (default False): the pass forms the smoothed covariances as well and the
+        call returns ``(filtered, smoothed, filtered_cov [F, 10, 10], smoothed_cov [F, 10, 10])`` (plus ``d2``): the camera
+        blocks of P_r and of P^s_r of every frame's record, NaN for frames before the first record;
+        ``get_cam_estimate_cov(i)`` returns row i."""
+        return self._smooth_log(True, ids, poses, offsets, has_detections, noise, scale, motion, mahal)
+
+    def _smooth_log(self, mode, ids, poses, offsets, has_detections=None, noise=None, scale=None, motion=None, mahal=False):
+        """``smooth_detection_log``; mode True: poses only, "cov": with the covariances."""
         from ..hip_backend import EKF_COV_F64, EKF_QUAT_SCALAR_FIRST
         backend = self.backend
         if backend.cfg.quat_mode != EKF_QUAT_SCALAR_FIRST:
@@ -190,7 +210,7 @@ class EKF(BaseFilter):
             raise ValueError('smoothing needs cov_dtype="float64"')
         if self.map_frozen:
             raise ValueError("smoothing a frozen map is not supported: unfreeze_map() first")
-        return self._replay_detection_log(ids, poses, offsets, has_detections, mahal, noise, scale, motion, True)
+        return self._replay_detection_log(ids, poses, offsets, has_detections, mahal, noise, scale, motion, mode)
 
     def get_cam_estimate(self, iteration: int):
         """Row ``iteration`` of the last smoothed log as ``process_detections(should_filter=False, iteration=i)`` expects
@@ -202,6 +222,17 @@ class EKF(BaseFilter):
         if not 0 <= i < smoothed.shape[0]:
             raise IndexError(f"frame {iteration} is outside the smoothed log of {smoothed.shape[0]} frames")
         return np.concatenate((smoothed[i], np.zeros(3)))
+
+    def get_cam_estimate_cov(self, iteration: int):
+        """Row ``iteration`` of the last smoothed covariance, [10, 10] (``smooth_detection_log(cov=True)``).  ``IndexError``
+        outside the log; ``NotImplementedError`` when nothing has been smoothed with ``cov``."""
+        cov = getattr(self, "_smoothed_cov", None)
+        if cov is None:
+            raise NotImplementedError("no smoothed covariance: call smooth_detection_log(..., cov=True) first")
+        i = int(iteration)
+        if not 0 <= i < cov.shape[0]:
+            raise IndexError(f"frame {iteration} is outside the smoothed log of {cov.shape[0]} frames")
+        return cov[i].copy()
 
     # -- extras: resident-detection batch entry, used by bench / replay --------
     @property

@@ -55,7 +55,7 @@ EXPORTED_SYMBOLS = (
     "ekf_set_map_frozen", "ekf_get_map_frozen",
     "ekf_batch_set_map_frozen", "ekf_batch_get_map_frozen",
     "ekf_observe_log_recorded", "ekf_history_record_bytes", "ekf_history_bytes", "ekf_history_info", "ekf_history_record",
-    "ekf_smooth_workspace_bytes", "ekf_smooth_history",
+    "ekf_smooth_workspace_bytes", "ekf_smooth_history", "ekf_smooth_cov_workspace_bytes", "ekf_smooth_history_cov",
     "ekf_batch_history_bytes", "ekf_batch_observe_logs_recorded", "ekf_batch_history_info", "ekf_batch_history_record",
     "ekf_batch_history_table", "ekf_batch_smooth_workspace_bytes", "ekf_batch_smooth_history",
 )
@@ -164,6 +164,8 @@ def load_library(path: str | Path | None = None):
         "ekf_history_record": [vp, vp, C.c_int32, dp, dp, C.c_int32],
         "ekf_smooth_workspace_bytes": [vp, C.POINTER(C.c_size_t)],
         "ekf_smooth_history": [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int32, vp],
+        "ekf_smooth_cov_workspace_bytes": [vp, C.POINTER(C.c_size_t)],
+        "ekf_smooth_history_cov": [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int32, vp, vp, vp, vp],
         "ekf_batch_history_bytes": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_size_t)],
         "ekf_batch_observe_logs_recorded": [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, vp, vp, vp, vp, C.c_size_t,
                                             vp, vp, vp, vp, vp, C.c_size_t],
@@ -794,6 +796,32 @@ class HipEkf:
             history.record_stream(self.stream)
             self._check(self.lib.ekf_smooth_history(self.h, history.data_ptr(), history.numel(), ws.data_ptr(), nbytes.value,
                                                     int(bool(blocked)), out.data_ptr() if frames else None))
+        return out
+
+    def smooth_history_cov(self, history, frames: int, ws_bytes=None):
+        """The backward pass with the smoothed covariances (ekf_smooth_history_cov): float64 device tensors {"smoothed"
+        [frames, 7], "cam_cov" [frames, 10, 10] (P^s[0:10, 0:10] of every frame's record), "filt_cam_cov" [frames, 10, 10]
+        (P_r[0:10, 0:10]), "first_cov" [N_0, N_0] (P^s_0; None without records)}.  Covariance rows of frames before the
+        first record are NaN.  ``ws_bytes``: the workspace size to pass (default: what the library asks for).  Waits for
+        the filter's stream."""
+        torch = self._torch
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_smooth_cov_workspace_bytes(self.h, C.byref(nbytes)))
+        count = C.c_int32()
+        self._check(self.lib.ekf_history_info(self.h, C.byref(count), 0, None, None, None, None, None, None))
+        n0 = int(self.history_info()["dims"][0]) if count.value else 0
+        given = nbytes.value if ws_bytes is None else int(ws_bytes)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            ws = torch.empty((max(given, nbytes.value),), dtype=torch.uint8, device=self.device)
+            out = {"smoothed": torch.empty((frames, 7), dtype=torch.float64, device=self.device),
+                   "cam_cov": torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device),
+                   "filt_cam_cov": torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device),
+                   "first_cov": torch.empty((n0, n0), dtype=torch.float64, device=self.device) if n0 else None}
+            history.record_stream(self.stream)
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+            self._check(self.lib.ekf_smooth_history_cov(self.h, history.data_ptr(), history.numel(), ws.data_ptr(), given, 0,
+                                                        ptr(out["smoothed"]), ptr(out["cam_cov"]), ptr(out["filt_cam_cov"]),
+                                                        ptr(out["first_cov"])))
         return out
 
     LOG_STATS = ("frames_stepped", "frames_pipelined", "pipelined_runs", "markers_added")

@@ -107,11 +107,12 @@ def frame_scales(path: str, frame_period_ms: float) -> np.ndarray:
 
 
 def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryWriter, scales=None, motion=None,
-                    smooth: bool = False) -> None:
+                    smooth: bool = False, smooth_cov=None) -> None:
     """The whole replay file through ``process_detection_log``, then one trajectory line per frame.  Frames before the first
     stepped one carry the camera pose the filter had before the call (the integer initial pose of a fresh filter), as the
     frame-by-frame loop writes them; from the first frame with a motion on, the row is the (moved) pose of the device.
-    ``smooth``: the replay goes through ``smooth_detection_log`` and the lines carry the smoothed poses."""
+    ``smooth``: the replay goes through ``smooth_detection_log`` and the lines carry the smoothed poses; ``smooth_cov``: a
+    file name, the pass forms the covariances too and ``smoothed_cov``, ``filtered_cov`` [F, 10, 10] are written there."""
     det = np.load(path, allow_pickle=False)
     offsets, has = det["offsets"], det["has_detections"].astype(bool)
     start_pose = tracker.get_poses()[0]
@@ -121,7 +122,11 @@ def replay_resident(tracker: BaseFilter, path: str, cam_traj_writer: TrajectoryW
         extra["scale"] = scales
     if motion is not None:
         extra["motion"] = motion
-    if smooth:
+    if smooth and smooth_cov:
+        _filtered, traj, filtered_cov, smoothed_cov = tracker.smooth_detection_log(det["ids"], det["poses"], offsets, has,
+                                                                                   cov=True, **extra)
+        np.savez(smooth_cov, smoothed_cov=smoothed_cov, filtered_cov=filtered_cov)
+    elif smooth:
         _filtered, traj = tracker.smooth_detection_log(det["ids"], det["poses"], offsets, has, **extra)
     else:
         traj = tracker.process_detection_log(det["ids"], det["poses"], offsets, has, **extra)
@@ -140,6 +145,9 @@ def main(cmdline_args: argparse.Namespace) -> None:
     if getattr(cmdline_args, "localize", False) and map_file is None:
         raise ValueError("--localize tracks the camera in an existing map: pass --map <map.txt>")
     smooth = getattr(cmdline_args, "smooth", False)
+    smooth_cov = getattr(cmdline_args, "smooth_cov", None)
+    if smooth_cov and not smooth:
+        raise ValueError("--smooth-cov writes the covariances of the smoothed trajectory: pass --smooth")
     if smooth:
         if not (getattr(cmdline_args, "resident", False) and cmdline_args.detections):
             raise ValueError("--smooth runs a backward pass over a recorded replay: pass --detections <replay.npz> --resident")
@@ -179,7 +187,7 @@ def main(cmdline_args: argparse.Namespace) -> None:
         raise ValueError("--resident replays a detections file: pass --detections <replay.npz>")
     with TrajectoryWriter(str(out_dir / "trajectory.txt")) as cam_traj_writer:
         if resident:
-            replay_resident(tracker, cmdline_args.detections, cam_traj_writer, scales, motion, smooth)
+            replay_resident(tracker, cmdline_args.detections, cam_traj_writer, scales, motion, smooth, smooth_cov)
         elif cmdline_args.detections:
             offs = np.load(cmdline_args.detections, allow_pickle=False)["offsets"]
             for f, (timestamp, ids, poses) in enumerate(detection_frames(cmdline_args.detections)):
@@ -245,6 +253,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="with --detections --resident: write the smoothed trajectory (a Rauch-Tung-Striebel backward "
                              "pass over the recorded replay: every pose uses the whole log; the filter runs with the "
                              "scalar-first quaternion update)")
+    parser.add_argument("--smooth-cov", dest="smooth_cov", type=str, default=None, metavar="OUT.npz",
+                        help="with --smooth: also form the smoothed covariances and write the camera blocks of every frame, "
+                             "smoothed_cov and filtered_cov [F, 10, 10], to OUT.npz (NaN before the first update)")
     return parser
 
 

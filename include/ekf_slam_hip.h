@@ -826,7 +826,8 @@ int ekf_batch_get_map_frozen(const ekf_batch *b, int32_t *out /* [B] */);
 
 /* ---- Offline smoothing: a Rauch-Tung-Striebel backward pass over a recorded log replay.  A recorded replay
  * keeps, on the device, the filter as it was right after every frame that changed it; the backward pass turns those records
- * into the trajectory that ALL the data supports.  Only the smoothed state is formed -- no smoothed covariance.
+ * into the trajectory that ALL the data supports.  ekf_smooth_history forms the smoothed state only; ekf_smooth_history_cov
+ * ("Smoothed covariances" below) forms the smoothed covariance with it.
  *
  * The smoothing rules.
  *   A RECORD r holds the state x_r (N_r doubles) and P_r right after a frame that changed the filter: a frame that was
@@ -875,8 +876,30 @@ int ekf_batch_get_map_frozen(const ekf_batch *b, int32_t *out /* [B] */);
  *   resident   every N_r <= 160 (n <= 50): ONE launch of ONE workgroup runs the whole pass, P_p as a packed triangle in LDS
  *   blocked    any larger N_r (up to 8064 dims), or flags bit 0: per step a short launch sequence around the blocked f64
  *              Cholesky of the wide frames
- * Not in this interface: recording from per-frame ekf_observe calls, smoothed covariances (ekf_batch: "Batch smoothing"
- * below). */
+ *
+ * Smoothed covariances.  ekf_smooth_history_cov runs the same backward pass and the covariance recursion with it.
+ *   The covariance rule.  Records, transitions, F~, Q_eff, P_p and the dropping of dims that a later frame added are those
+ *   of the smoothing rules.  With N = N_r and G_r = P_r F~^T P_p^-1:
+ *     P^s_{R-1} = P_{R-1},   P^s_r = P_r + G_r (P^s_{r+1}[0:N, 0:N] - P_p) G_r^T,   r = R-2 .. 0
+ *   (restricting P^s_{r+1} to the first N_r dims is exact: first sightings are appended block-diagonally).  The device
+ *   evaluates the subtraction-of-products form, with L L^T = P_p, W = L^-1 F~ P_r and Z = L^-T W (= G_r^T):
+ *     P^s_r = P_r - W^T W + Z^T (P^s_{r+1}[0:N, 0:N] Z)
+ *   Only the lower triangle is computed and then mirrored: P^s_r is bitwise symmetric.  Every sum is one chain in a fixed
+ *   order: two runs over the same history give the same bits.  Outputs for frame t come from the last record at or before
+ *   t, as the poses; frames BEFORE THE FIRST RECORD get NaN in the covariance outputs (the history header keeps only the
+ *   camera state of the call's start).
+ *   Outputs: smoothed_dev [frames][7], bit for bit what ekf_smooth_history writes with flags bit 0 (the blocked tier);
+ *   cam_cov_dev [frames][10][10] = P^s[0:10, 0:10]; filt_cam_cov_dev [frames][10][10] = P_r[0:10, 0:10] (or NULL);
+ *   first_cov_dev [N_0][N_0] = P^s_0, mirrored (or NULL).  The last record's cam_cov rows are its filtered ones.
+ *   Preconditions and refusals are those of ekf_smooth_history (the handle's last recorded call; EKF_MODEL_EKF, f64
+ *   covariance, scalar-first, not frozen, not touched by removal), checked before anything is enqueued; a workspace
+ *   smaller than ekf_smooth_cov_workspace_bytes is EKF_ERR_INVALID.  The pass has its own status word and never writes
+ *   the filter: a P_p that is not positive definite returns EKF_ERR_NUMERIC and leaves nothing sticky.  One tier for every
+ *   N: a launch sequence per step (the right-hand sides F~ P_r ride along the blocked f64 Cholesky, then a block backward
+ *   substitution and three N x N x N products on the f64 matrix cores); records of up to 8064 dims, larger ones
+ *   EKF_ERR_CAPACITY.  `flags` is reserved (0).
+ * Not in this interface: recording from per-frame ekf_observe calls; for the covariances: ekf_batch, a resident
+ * one-workgroup form, EKF_MODEL_ROTATIONS and the f32 covariance (ekf_batch: "Batch smoothing" below). */
 int ekf_observe_log_recorded(ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames,
                              const double *poses_dev, const double *rows_dev, const double *scale, const double *motion,
                              void *log_ws, size_t log_ws_bytes, double *trajectory_dev, double *mahal_dev,
@@ -889,6 +912,12 @@ int ekf_history_record(ekf_filter *f, const void *history_dev, int32_t r, double
 int ekf_smooth_workspace_bytes(const ekf_filter *f, size_t *bytes);
 int ekf_smooth_history(ekf_filter *f, const void *history_dev, size_t history_bytes, void *ws, size_t ws_bytes, int32_t flags,
                        double *smoothed_dev /* [frames][7] */);
+int ekf_smooth_cov_workspace_bytes(const ekf_filter *f, size_t *bytes);
+int ekf_smooth_history_cov(ekf_filter *f, const void *history_dev, size_t history_bytes, void *ws, size_t ws_bytes,
+                           int32_t flags, double *smoothed_dev        /* [frames][7]                           */,
+                           double *cam_cov_dev                        /* [frames][10][10]  P^s[0:10,0:10]       */,
+                           double *filt_cam_cov_dev                   /* [frames][10][10]  P_r[0:10,0:10], NULL */,
+                           double *first_cov_dev                      /* [N_0][N_0]  P^s_0 mirrored, or NULL    */);
 
 /* ---- Batch smoothing: recorded replays of an ekf_batch, one backward pass per member.  The smoothing rules
  * above, applied per member with the member's own q_cam / q_err / q_lm, with these additions.

@@ -23,6 +23,10 @@ updates/s is steady frames per second of the steady segment; the bootstrap segme
                                                    # the backward pass in us per record, next to the plain by-frame replay
                                                    # and the recorded replay of the same log on the same build (us per
                                                    # frame); writes profiles/smooth/summary.json
+    python tools/replay_bench.py --smooth --cov    # smoothed covariances: at the same four map sizes the covariance pass
+                                                   # (HipEkf.smooth_history_cov) and the forced-blocked state pass of the same
+                                                   # run, us per record, and the f64 matrix-core rate of the pass's N^3 terms;
+                                                   # writes profiles/smooth/cov_summary.json
 """
 from __future__ import annotations
 
@@ -135,6 +139,54 @@ def _smooth_bench(args):
     (out / "summary.json").write_text(json.dumps({"steady_frames": args.steady, "rows": rows}, indent=1) + "\n")
 
 
+def _smooth_cov_bench(args):
+    """--smooth --cov: per map size one recorded replay, then per round the forced-blocked state pass and the covariance
+    pass over the same history (host clock around calls that end in a synchronisation).  One untimed round, then `reps`
+    timed ones; median and range.  flop_per_record counts the N^3 terms of a step at the padded size p (W = L^-1 A: p^3,
+    Z = L^-T W: p^3, T = P^s Z: 2 p^3, the lower tiles of -W^T W + Z^T T: 2 p^3 (1 + 64 / p)), the factorisation left out."""
+    import torch
+    from aruco_slam_amd.filters.base_filter import plan_detection_log
+    from aruco_slam_amd.filters.extended_kalman_filter import EKF
+    from aruco_slam_amd.synthetic import ragged_log
+    rows = []
+    for n in (10, 50, 51, 338):
+        m = (min(4, n), min(12, n))
+        log = ragged_log(n, m, args.steady, seed=args.seed)
+        frames = len(log["has_detections"])
+        flt = EKF(INIT, max_landmarks=n, max_visible=m[1], cov_dtype="float64", quat_update="scalar_first", motion=True)
+        b = flt.backend
+        plan = plan_detection_log(flt.landmarks, flt.num_landmarks, log["ids"], log["offsets"], log["has_detections"])
+        history = b.new_history(plan.index, plan.offsets)
+        traj = torch.empty((frames, 7), dtype=torch.float64, device=b.device)
+        b.observe_log(plan.index, plan.offsets, log["poses"], traj, motion=np.zeros((frames, 6)), history=history)
+        b.sync()
+        records = len(b.history_info()["frame"])
+        t_state, t_cov = [], []
+        for rep in range(args.reps + 1):
+            torch.cuda.synchronize(b.device)
+            t = time.perf_counter()
+            b.smooth_history(history, frames, blocked=True)
+            t_state.append(time.perf_counter() - t)
+            t = time.perf_counter()
+            b.smooth_history_cov(history, frames)
+            t_cov.append(time.perf_counter() - t)
+        def stat(v):
+            v = 1e6 * np.array(v[1:]) / records
+            return {"median_us": float(np.median(v)), "min_us": float(v.min()), "max_us": float(v.max())}
+        dims = 3 * n + 10
+        pad = -(-dims // 64) * 64
+        flop = 4.0 * pad ** 3 + 2.0 * pad ** 3 * (1.0 + 64.0 / pad)
+        row = {"n": n, "dims": dims, "padded": pad, "frames": frames, "records": records, "m_range": list(m), "reps": args.reps,
+               "cov_per_record": stat(t_cov), "state_blocked_per_record": stat(t_state), "flop_per_record": flop}
+        row["cov_pass_gflops"] = flop / (1e3 * row["cov_per_record"]["median_us"])
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del flt, b, history
+    out = Path(__file__).resolve().parent.parent / "profiles" / "smooth"
+    out.mkdir(parents=True, exist_ok=True)
+    (out / "cov_summary.json").write_text(json.dumps({"steady_frames": args.steady, "rows": rows}, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--n", type=int, default=1024)
@@ -151,10 +203,14 @@ def main():
                     help="replay the steady segment on a frozen map and as mapping frames in serial order, instead of the variants")
     ap.add_argument("--smooth", action="store_true",
                     help="offline smoothing: backward pass per record vs by-frame replay per frame, four map sizes")
+    ap.add_argument("--cov", action="store_true",
+                    help="with --smooth: the covariance pass next to the forced-blocked state pass, four map sizes")
     ap.add_argument("--reps", type=int, default=5, help="--smooth: timed rounds (after one untimed)")
     args = ap.parse_args()
+    if args.cov and not args.smooth:
+        ap.error("--cov goes with --smooth")
     if args.smooth:
-        _smooth_bench(args)
+        (_smooth_cov_bench if args.cov else _smooth_bench)(args)
         return
     import torch
     from aruco_slam_amd.synthetic import SyntheticStream, ragged_log

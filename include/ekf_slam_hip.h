@@ -857,8 +857,10 @@ int ekf_batch_get_map_frozen(const ekf_batch *b, int32_t *out /* [B] */);
  * frame-by-frame serial replay (ekf_last_sequence_mode: 1) and enqueues, behind every frame that changed the filter, ONE
  * pack launch that copies state[0:N] and the lower triangle of P -- packed column by column, f64 -- into the next record
  * (256-byte aligned).  Bit rule: trajectory, final state, final P, d^2 and ekf_last_log_stats are bit for bit those of the
- * same call through ekf_observe_log_moved / ekf_observe_log_gated: recording only reads.  The handle keeps the table of the
- * call on the host (per record: frame, N_r, offset, s_eff, motion; per frame: its record).
+ * same call through ekf_observe_log_moved / ekf_observe_log_gated: recording only reads.  (Of the stats, frames_pipelined
+ * and pipelined_runs are 0 in a recorded call: a plain call without gate and motions may run pipelined, with the same
+ * bits.)  The handle keeps the table of the call on the host (per record: frame, N_r, offset, s_eff, motion; per frame:
+ * its record).
  *   history layout  [256 B: state[0:7] at the start of the call | record 0 | record 1 | ...], record = [state N | triangle
  *                   N (N + 1) / 2] doubles, rounded up to 256 bytes (ekf_history_record_bytes)
  *   ekf_history_bytes   an upper bound from the log alone: the header and one record per frame at the dims that frame
@@ -872,7 +874,10 @@ int ekf_batch_get_map_frozen(const ekf_batch *b, int32_t *out /* [B] */);
  * The backward pass.  ekf_smooth_history runs on the handle's stream, over the handle's LAST recorded call and that buffer
  * (anything else: EKF_ERR_STATE), and writes smoothed_dev [frames][7].  It never writes the filter: state and P keep their
  * bits, and its status word is its own -- a P_p that is not positive definite returns EKF_ERR_NUMERIC and leaves no sticky
- * error on the filter.  It waits for the stream before it returns.  Two tiers, chosen per call by the largest record:
+ * error on the filter.  The pass ends at that step r: the rows written until then stay (the frames before the first record
+ * and the frames of the records behind r), the rows of the records up to r are left unwritten, in both tiers and in every
+ * output of ekf_smooth_history_cov, first_cov_dev included.  It waits for the stream before it returns.  Two tiers, chosen
+ * per call by the largest record:
  *   resident   every N_r <= 160 (n <= 50): ONE launch of ONE workgroup runs the whole pass, P_p as a packed triangle in LDS
  *   blocked    any larger N_r (up to 8064 dims), or flags bit 0: per step a short launch sequence around the blocked f64
  *              Cholesky of the wide frames

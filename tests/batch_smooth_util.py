@@ -130,6 +130,100 @@ def table_from_flags(lib, member_frames, slot, dims, flag, s_eff, motion, noise)
     return rows, rec_member[:r], rec_rows[:r], rec_q[:r], rec_moved[:r]
 
 
+# --------------------------------------------------------------------------------------------------------------------
+# the mixed batch, the words at the tail of a batch history, and the pass through the library itself
+# --------------------------------------------------------------------------------------------------------------------
+MIXED_NOISE = {"q_cam": [0.3, 0.1, 0.3, 0.5], "q_lm": [0.01, 0.02, 0.01, 0.005]}
+
+
+def mixed_logs():
+    """The mixed batch of ``test_batch_smooth.py``: tracking, ragged, growing (N = 160) and another ragged world."""
+    return [scene_log("tracking", with_motion=True, with_scale=True), scene_log("ragged"),
+            scene_log("growing", with_motion=True, with_scale=True), scene_log("ragged", seed=6)]
+
+
+def new_batch(members, **kw):
+    from aruco_slam_amd.batch import EKFBatch
+    kw.setdefault("quat_update", "scalar_first")
+    kw.setdefault("max_landmarks", 50)
+    kw.setdefault("max_visible", 16)
+    poses = kw.pop("poses", None)
+    return EKFBatch(members, initial_poses(members) if poses is None else poses, **kw)
+
+
+def tail_offsets(total, members, frames, with_motion):
+    """Byte offsets of the words of the call at the tail of a batch history of ``total`` bytes, counted back from its end by
+    the header's layout: {"head" [B] i64, "slot" [Ftot] i64, "flag" [Ftot] i32, "s_eff" [Ftot] f64, "motion" [Ftot][6]}."""
+    up = lambda n: -(-n // 256) * 256
+    at = {}
+    at["motion"] = total - (up(48 * frames) if with_motion else 0)
+    at["s_eff"] = at["motion"] - up(8 * frames)
+    at["flag"] = at["s_eff"] - up(4 * frames)
+    at["slot"] = at["flag"] - up(8 * frames)
+    at["head"] = at["slot"] - up(8 * members)
+    return at
+
+
+def member_record_offset(batch, member, frame):
+    """Byte offset of the slot of ``frame`` (within the member's log) in ``batch.last_history``, read from the slots' offsets
+    words at the tail of the history (they count doubles from the start of the buffer)."""
+    import torch
+    history, mf = batch.last_history, batch._history_frames
+    total = history.numel()
+    at = tail_offsets(total, batch.members, int(mf[-1]), batch.motion)
+    batch.stream.synchronize()
+    slots = history[at["slot"]:at["slot"] + 8 * int(mf[-1])].view(torch.int64).cpu().numpy()
+    heads = history[at["head"]:at["head"] + 8 * batch.members].view(torch.int64).cpu().numpy()
+    slot = int(slots[int(mf[member]) + frame])
+    assert slot > int(heads[member]) >= 0 and (member + 1 == batch.members or slot < int(heads[member + 1]))
+    return 8 * slot
+
+
+def tamper_member(batch, member, r, k, value=-1e3):
+    """``smooth_util.tamper`` on record r of a member of the last recorded call; the read-back check is against
+    ``history_records(member)``."""
+    rec = batch.history_records(member)[r]
+    return su.tamper(batch.last_history, batch.stream.synchronize, member_record_offset(batch, member, rec["frame"]),
+                     rec["x"], rec["P"], k, value)
+
+
+def direct_batch_smooth(batch, poison=False):
+    """``ekf_batch_smooth_history`` through the library itself: a workspace of exactly ``ekf_batch_smooth_workspace_bytes``
+    (zeros, or with ``poison`` 0xFF bytes) and an output pre-filled with ``smooth_util.SENTINEL``.  Returns (rc, per-member
+    rows, status [B])."""
+    import ctypes as C
+
+    import torch
+    from aruco_slam_amd.batch import _iptr
+    need = C.c_size_t()
+    assert batch.lib.ekf_batch_smooth_workspace_bytes(batch.h, C.byref(need)) == 0
+    mf, history = batch._history_frames, batch.last_history
+    ws = torch.full((need.value,), 0xFF if poison else 0, dtype=torch.uint8, device=batch.device)
+    out = torch.full((int(mf[-1]), 7), su.SENTINEL, dtype=torch.float64, device=batch.device)
+    status = np.full(batch.members, 99, dtype=np.int32)
+    torch.cuda.synchronize(batch.device)
+    rc = batch.lib.ekf_batch_smooth_history(batch.h, history.data_ptr(), history.numel(), ws.data_ptr(), need.value,
+                                            out.data_ptr(), _iptr(status))
+    batch.stream.synchronize()
+    torch.cuda.synchronize(batch.device)
+    rows = out.cpu().numpy()
+    return rc, [rows[mf[b]:mf[b + 1]] for b in range(batch.members)], status
+
+
+def record_into_poison(batch, size):
+    """From now on a recorded call of ``batch`` records into a buffer of ``size`` bytes that holds 0xFF bytes (every double a
+    NaN, every flag word -1) before the call."""
+    import torch
+    plain = batch.observe_indexed
+
+    def observe_indexed(*args, **kw):
+        if kw.get("record") is True:
+            kw["record"] = torch.full((size,), 0xFF, dtype=torch.uint8, device=batch.device)
+            torch.cuda.synchronize(batch.device)
+        return plain(*args, **kw)
+    batch.observe_indexed = observe_indexed
+
+
 def replica_logs():
     """The tracking log as replicas 0 .. REPLICAS - 1 consume it in ``smooth_replicas(log, REPLICA_SIGMA, REPLICA_SEED)``: the
     host mirror of the device's noise (``replica_util``)."""

@@ -24,8 +24,8 @@ LD = su.LD
 U = su.U
 INIT = sw.INIT
 GROWING = "g17_3"      # growing_scene(17, 3, tail=2): dims 61, 64, 67, 70 -- npad changes 64 -> 128 inside the pass
-CPU_SCENES = su.SCENES + (GROWING,)
-GPU_SCENES = ("n18", "n19", GROWING, "ragged", "tracking", "n49_52")
+CPU_SCENES = su.SCENES + (GROWING,)      # (with n82 and g81_2: four blocks without a padding row, and 4 -> 5 blocks)
+GPU_SCENES = ("n18", "n19", GROWING, "ragged", "tracking", "n49_52", "n82", "g81_2")
 
 
 def scene(name):
@@ -149,8 +149,9 @@ def new_filter(n=8, m=8, **kw):
     return EKF(INIT, max_landmarks=n, max_visible=m, **kw)
 
 
-def recorded_replay(flt, log, motion=None, scale=None, record=True):
-    """One log call on the back end; returns (trajectory, history | None)."""
+def recorded_replay(flt, log, motion=None, scale=None, record=True, mahal=False, poison=False):
+    """One log call on the back end; returns (trajectory, history | None), with ``mahal`` (trajectory, history | None, d2
+    [D]).  ``poison``: the history holds 0xFF bytes (every double a NaN) before the call."""
     import torch
     from aruco_slam_amd.filters.base_filter import plan_detection_log
     b = flt.backend
@@ -161,12 +162,40 @@ def recorded_replay(flt, log, motion=None, scale=None, record=True):
         b.grow(new_max_visible=plan.widest)
     frames = len(plan.offsets) - 1
     traj = torch.empty((frames, 7), dtype=torch.float64, device=b.device)
+    d2 = torch.empty((len(plan.index),), dtype=torch.float64, device=b.device) if mahal else None
     history = b.new_history(plan.index, plan.offsets) if record else None
-    b.observe_log(plan.index, plan.offsets, log["poses"], traj, None, None, scale, motion, **({"history": history} if record else {}))
+    if poison:
+        history.fill_(0xFF)
+        torch.cuda.synchronize(b.device)
+    b.observe_log(plan.index, plan.offsets, log["poses"], traj, d2, None, scale, motion, **({"history": history} if record else {}))
     b.sync()
     flt.landmarks.update(plan.new_landmarks)
     flt.num_landmarks = plan.num_landmarks
+    if mahal:
+        return traj.cpu().numpy(), history, d2.cpu().numpy()
     return traj.cpu().numpy(), history
+
+
+def direct_smooth_cov(b, history, frames, n0, poison=False):
+    """``ekf_smooth_history_cov`` through the library itself: a workspace of exactly ``ekf_smooth_cov_workspace_bytes``
+    (zeros, or with ``poison`` 0xFF bytes: every double a NaN) and outputs pre-filled with ``smooth_util.SENTINEL``.
+    Returns (rc, {"smoothed", "cam_cov", "filt_cam_cov", "first_cov" [n0, n0]} as arrays)."""
+    import ctypes as C
+
+    import torch
+    need = C.c_size_t()
+    assert b.lib.ekf_smooth_cov_workspace_bytes(b.h, C.byref(need)) == 0
+    ws = torch.full((need.value,), 0xFF if poison else 0, dtype=torch.uint8, device=b.device)
+    out = {key: torch.full(shape, su.SENTINEL, dtype=torch.float64, device=b.device)
+           for key, shape in (("smoothed", (frames, 7)), ("cam_cov", (frames, 10, 10)), ("filt_cam_cov", (frames, 10, 10)),
+                              ("first_cov", (n0, n0)))}
+    torch.cuda.synchronize(b.device)
+    rc = b.lib.ekf_smooth_history_cov(b.h, history.data_ptr(), history.numel(), ws.data_ptr(), need.value, 0,
+                                      out["smoothed"].data_ptr(), out["cam_cov"].data_ptr(), out["filt_cam_cov"].data_ptr(),
+                                      out["first_cov"].data_ptr())
+    b.sync()
+    torch.cuda.synchronize(b.device)
+    return rc, {key: v.cpu().numpy() for key, v in out.items()}
 
 
 @functools.lru_cache(maxsize=None)

@@ -227,6 +227,10 @@ def scene(name):
         return growing_scene(51, 0, tail=4), None, None
     if name == "n49_52":            # the tier choice sees a mixed history
         return growing_scene(49, 3, tail=2), None, None
+    if name == "n82":               # N = 256: exactly four blocks, no padding row at all, behind an 82-detection frame
+        return growing_scene(82, 0, tail=3), None, None
+    if name == "g81_2":             # dims 253, 256, 259, 259: npad goes 256 -> 320 (4 -> 5 blocks) inside the pass
+        return growing_scene(81, 2, tail=1), None, None
     raise KeyError(name)
 
 
@@ -243,8 +247,10 @@ def _n50():
             "offsets": np.concatenate(([0], np.cumsum(counts))).astype(np.int64)}
 
 
-SCENES = ("tracking", "ragged", "n50", "n18", "n19", "n51", "n49_52")
-EXPECTED_DIMS = {"tracking": 40, "ragged": 34, "n50": 160, "n18": 64, "n19": 67, "n51": 163, "n49_52": 166}
+SCENES = ("tracking", "ragged", "n50", "n18", "n19", "n51", "n49_52", "n82", "g81_2")
+EXPECTED_DIMS = {"tracking": 40, "ragged": 34, "n50": 160, "n18": 64, "n19": 67, "n51": 163, "n49_52": 166, "n82": 256,
+                 "g81_2": 259}
+BLOCKED_SCENES = ("n51", "n49_52", "n82", "g81_2")      # a record past RESIDENT_DIMS: the blocked tier without being asked
 
 # the table of ekf_history_info for the ragged log with its motions and RAGGED_SCALE: (frame, dims, stepped, s_eff) of every
 # record -- frame 0 is empty but moved, frames 4 .. 6 and 10 are empty and moved (their scales stay pending: 0.5 + 1 + 1.5
@@ -252,6 +258,104 @@ EXPECTED_DIMS = {"tracking": 40, "ragged": 34, "n50": 160, "n18": 64, "n19": 67,
 RAGGED_TABLE = [(0, 10, False, 0.0), (1, 22, True, 1.5), (2, 22, True, 1.5), (3, 28, True, 2.0), (4, 28, False, 0.0),
                 (5, 28, False, 0.0), (6, 28, False, 0.0), (7, 28, True, 5.0), (8, 34, True, 0.5), (9, 34, True, 1.0),
                 (10, 34, False, 0.0), (11, 34, True, 3.5), (12, 34, True, 0.5), (13, 34, True, 1.0)]
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# the table under a gate, the layout of a history, and the pass through the library itself (``test_smooth_edges*.py``)
+# --------------------------------------------------------------------------------------------------------------------
+def expected_table(log, motion, scale, rejected):
+    """The record table of a recorded replay by the header's rules, from the log and the gate's verdicts alone.  rejected:
+    bool [D], indexed like the log's detections (first sightings are exempt, so never rejected).  A frame is stepped iff a
+    detection survives; the scale of a frame that is not stepped stays pending and folds into the next stepped frame; a
+    record exists iff the frame was moved by a non-zero motion or stepped; dims come from the landmarks known after the
+    frame.  Returns (rows [(frame, dims, stepped, s_eff)], motions [R, 6], frame_record [F])."""
+    offs = np.asarray(log["offsets"], dtype=np.int64)
+    frames = len(offs) - 1
+    rejected = np.asarray(rejected, dtype=bool)
+    known, rows, motions, frame_record, pending = set(), [], [], np.full(frames, -1, dtype=np.int64), 0.0
+    for t in range(frames):
+        u = np.zeros(6) if motion is None else np.asarray(motion[t], dtype=np.float64)
+        sl = slice(int(offs[t]), int(offs[t + 1]))
+        known.update(int(i) for i in log["ids"][sl])
+        s_eff = 1.0 if scale is None else pending + float(scale[t])
+        stepped = bool((~rejected[sl]).any())
+        if scale is not None:
+            pending = 0.0 if stepped else s_eff
+        if stepped or u.any():
+            rows.append((t, 10 + 3 * len(known), stepped, s_eff if stepped else 0.0))
+            motions.append(u)
+        frame_record[t] = len(rows) - 1
+    return rows, np.array(motions).reshape(-1, 6), frame_record
+
+
+def record_bytes(dims):
+    """``ekf_history_record_bytes`` restated: state [N] and the packed triangle in f64, rounded up to 256 bytes."""
+    return -(-(dims + dims * (dims + 1) // 2) * 8 // 256) * 256
+
+
+def record_offset(dims, r):
+    """Byte offset of record r of a single filter's history whose records have ``dims`` [R]: the 256-byte header, then the
+    records one behind the other."""
+    return 256 + sum(record_bytes(int(n)) for n in dims[:r])
+
+
+def diag_word(n, k):
+    """Double index of P[k][k] within a record of n dims: the state, then the lower triangle column by column."""
+    return n + k * (2 * n - k + 1) // 2
+
+
+def tamper(history, sync, byte_offset, want_x, want_p, k, value=-1e3):
+    """Write ``value`` over P[k][k] of the packed record at ``byte_offset`` of the caller's history buffer (a uint8 device
+    tensor).  BEFORE it writes, the state doubles and that diagonal word are compared bit for bit with ``want_x`` [N] and
+    ``want_p`` [N, N] (``history_record``): the check of the layout arithmetic.  ``sync()`` waits for the handle.  Returns
+    a function that puts the original word back."""
+    import torch
+    n = int(np.asarray(want_x).shape[0])
+    words = history.view(torch.float64)
+    first = byte_offset // 8
+    assert byte_offset % 256 == 0 and 0 <= k < n and first + diag_word(n, k) < words.numel()
+    sync()
+    torch.cuda.synchronize(history.device)
+    assert np.array_equal(words[first:first + n].cpu().numpy(), want_x)
+    at = first + diag_word(n, k)
+    old = words[at:at + 1].clone()
+    assert np.array_equal(old.cpu().numpy(), np.asarray(want_p)[k:k + 1, k])
+    words[at] = value
+    torch.cuda.synchronize(history.device)
+
+    def restore():
+        words[at:at + 1] = old
+        torch.cuda.synchronize(history.device)
+    return restore
+
+
+# a pivot that fails inside the pass: (scene, blocked flag, r_bad, the k whose P[k][k] of record r_bad becomes -1e3)
+#   tracking: the resident tier, first and last pivot; n19 forced blocked (N = 67): the first pivot of block 0 and the last
+#   of the ragged block 1; n51 natural blocked (N = 163): a pivot of block 2
+FAIL_STATE = (("tracking", False, 20, (0, 39)), ("n19", True, 2, (0, 66)), ("n51", False, 2, (162,)))
+# the covariance pass: n19 as above, n49_52 with k = N_r - 1 of record 2 (N_r = 163)
+FAIL_COV = (("n19", 2, (0, 66)), ("n49_52", 2, (162,)))
+TAMPER_VALUE = -1e3
+EKF_ERR_NUMERIC = -5
+SENTINEL = 7.0      # what the outputs of a direct call hold before it: a row that still holds it was not written
+
+
+def direct_smooth(b, history, frames, blocked, poison=False):
+    """``ekf_smooth_history`` through the library itself: a workspace of exactly ``ekf_smooth_workspace_bytes`` (zeros, or
+    with ``poison`` 0xFF bytes: every double a NaN) and an output pre-filled with SENTINEL.  Returns (rc, smoothed [F, 7])."""
+    import ctypes as C
+
+    import torch
+    need = C.c_size_t()
+    assert b.lib.ekf_smooth_workspace_bytes(b.h, C.byref(need)) == 0
+    ws = torch.full((need.value,), 0xFF if poison else 0, dtype=torch.uint8, device=b.device)
+    out = torch.full((frames, 7), SENTINEL, dtype=torch.float64, device=b.device)
+    torch.cuda.synchronize(b.device)
+    rc = b.lib.ekf_smooth_history(b.h, history.data_ptr(), history.numel(), ws.data_ptr(), need.value, int(bool(blocked)),
+                                  out.data_ptr())
+    b.sync()
+    torch.cuda.synchronize(b.device)
+    return rc, out.cpu().numpy()
 
 
 def build_host_program(out_dir):

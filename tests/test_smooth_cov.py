@@ -17,9 +17,11 @@ pytestmark = pytest.mark.gpu
 def test_covariances_against_the_oracle_under_the_bound(name):
     """cam_cov on every frame and first_cov on all entries: n18 (N = 64, one block), n19 (N = 67, ragged second block), the
     growing log (dims 61, 64, 67, 70: npad 64 -> 128 inside the pass, P^s_{r+1} cut to N_r), ragged (motions, moved-only
-    records with s_eff = 0, scales), tracking (40 steps) and n49_52 (three blocks).  Measured worst error / bound on one
-    MI355X (cam_cov / first_cov): 0.0032 / 0.0050, 0.0041 / 0.0065, 0.0016 / 0.0053, 0.0080 / 0.0000, 0.0061 / 0.0006,
-    0.0017 / 0.0043.  (NaN rows before the first record and frames that share a record: the next test.)"""
+    records with s_eff = 0, scales), tracking (40 steps), n49_52 (three blocks), n82 (N = 256: four blocks, no padding row)
+    and g81_2 (dims 253, 256, 259, 259: npad 256 -> 320 inside the pass).  Measured worst error / bound on one MI355X
+    (cam_cov / first_cov): 0.0032 / 0.0050, 0.0041 / 0.0065, 0.0016 / 0.0053, 0.0080 / 0.0000, 0.0061 / 0.0006,
+    0.0017 / 0.0043, 0.0018 / 0.0078, 0.0015 / 0.0078.  (NaN rows before the first record and frames that share a
+    record: the next test.)"""
     case = sc.device_case(name)
     out, records, ref, frames = case["out"], case["records"], case["ref"], case["frames"]
     cam, fb, rec_of = sc.frame_rows(ref, records, frames)
@@ -66,7 +68,7 @@ def test_frames_before_the_first_record_and_frames_that_share_a_record():
 
 
 # ---- 2. bit rules ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["ragged", sc.GROWING])
+@pytest.mark.parametrize("name", ["ragged", sc.GROWING, "g81_2"])
 def test_bit_rules(name):
     case = sc.device_case(name)
     out, records, frames, flt, history = case["out"], case["records"], case["frames"], case["flt"], case["history"]

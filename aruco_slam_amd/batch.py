@@ -42,6 +42,8 @@ Offline studies ask for the trajectory that a whole log supports: ``smooth_detec
 the window kernel packs every member behind each frame that changed it -- and runs one Rauch-Tung-Striebel backward pass per
 member, one workgroup each ("Batch smoothing" in ``include/ekf_slam_hip.h``; ``EKF.smooth_detection_log`` per member, in one
 call).  ``smooth_replicas`` does the same for Monte-Carlo replicas of one log, ``history_records`` returns what was recorded.
+With ``cov=True`` both also return the camera blocks of the filtered and the smoothed covariance per frame
+(``smooth_history_cov``: the same launch forms ``P^s`` of every member, "Batch smoothing, covariances" in the header).
 ``model="ekf"`` with ``quat_update="scalar_first"``, at most 50 landmarks per member, without ``large_maps`` / ``wide_frames``.
 """
 from __future__ import annotations
@@ -845,7 +847,7 @@ class EKFBatch:
                                    cov_t.cpu().numpy() if cam_cov else None, full, rej, flipped)
 
     # -- offline smoothing ---------------------------------------------------------------------------------------------
-    def smooth_detection_logs(self, logs, *, mahal: bool = False):
+    def smooth_detection_logs(self, logs, *, mahal: bool = False, cov: bool = False):
         """``process_detection_logs(logs)`` recorded, then one Rauch-Tung-Striebel backward pass per member on the device
         ("Batch smoothing" in ``include/ekf_slam_hip.h``): returns ``(filtered, smoothed)``, per-member lists of
         ``(F_b, 7)``.  ``filtered`` has the bits of ``process_detection_logs`` and the batch is left where that call
@@ -855,12 +857,21 @@ class EKFBatch:
         A member that failed in the replay has NaN rows from its failing frame on; ``last_smooth_status[b]`` is
         EKF_ERR_NUMERIC (-5) for a member whose backward pass met a covariance that is not positive definite (all its rows
         NaN), else 0.  A batch of ``model="ekf"``, ``quat_update="scalar_first"``, without ``large_maps`` / ``wide_frames``,
-        mapping members of at most 50 landmarks; anything else raises ``EkfError`` (EKF_ERR_STATE) and nothing changes."""
+        mapping members of at most 50 landmarks; anything else raises ``EkfError`` (EKF_ERR_STATE) and nothing changes.
+
+        Keyword-only ``cov=True`` (default False): the pass forms the smoothed covariances as well (``smooth_history_cov``) and
+        the call returns ``(filtered, smoothed, filtered_cov, smoothed_cov)`` (plus ``(mahal, rejected)``), as
+        ``EKF.smooth_detection_log(cov=True)`` does: per-member lists of ``(F_b, 10, 10)``, the camera blocks of ``P`` and
+        ``P^s`` per frame, NaN before a member's first record."""
         gated = mahal or self.gate is not None
         out = self.process_detection_logs(logs, mahal=mahal, record=True)
         filtered = out.trajectory if gated else out
-        smoothed = self.smooth_history()
-        return (filtered, smoothed, (out.mahal, out.rejected)) if gated else (filtered, smoothed)
+        if cov:
+            smoothed, smoothed_cov, filtered_cov = self.smooth_history_cov()
+            res = (filtered, smoothed, filtered_cov, smoothed_cov)
+        else:
+            res = (filtered, self.smooth_history())
+        return res + ((out.mahal, out.rejected),) if gated else res
 
     def smooth_history(self, history=None) -> list:
         """The backward pass over the last recorded call (``ekf_batch_smooth_history``; ``history``: its buffer, default
@@ -885,6 +896,52 @@ class EKFBatch:
         rows = out.cpu().numpy()
         return [rows[mf[b]:mf[b + 1]] for b in range(self.members)]
 
+    def smooth_history_cov(self, history=None, first: bool = False):
+        """The backward pass with the smoothed covariances over the last recorded call (``ekf_batch_smooth_history_cov``,
+        "Batch smoothing, covariances" in ``include/ekf_slam_hip.h``): ``(smoothed, cam_cov, filt_cam_cov)``, per-member
+        lists of ``(F_b, 7)``, ``(F_b, 10, 10)`` and ``(F_b, 10, 10)`` -- the rows of ``smooth_history``, bit for bit, the camera
+        block of ``P^s`` and the one of the filtered ``P`` of the record a frame belongs to (NaN before the first record).  With
+        ``first`` a fourth list follows: ``P^s_0`` of every member, ``(N_0, N_0)`` (``(0, 0)`` for a member without a record).
+        Sets ``last_smooth_status``; a member with EKF_ERR_NUMERIC there has NaN everywhere.  Reads the members only."""
+        torch = self._torch
+        history = self.last_history if history is None else history
+        if history is None:
+            raise ValueError("no recorded call yet (smooth_detection_logs, or observe_indexed(record=True))")
+        nbytes = C.c_size_t()
+        self._check(self.lib.ekf_batch_smooth_cov_workspace_bytes(self.h, C.byref(nbytes)))
+        mf = self._history_frames
+        frames = int(mf[-1])
+        n0 = np.zeros(self.members, dtype=np.int64)
+        if first:
+            count = C.c_int32()
+            for b in range(self.members):
+                self._check(self.lib.ekf_batch_history_info(self.h, b, C.byref(count), 0, None, None, None, None, None, None))
+                if count.value > 0:
+                    dims = np.zeros(count.value, dtype=np.int32)
+                    self._check(self.lib.ekf_batch_history_info(self.h, b, C.byref(count), count.value, None, _iptr(dims),
+                                                                None, None, None, None))
+                    n0[b] = dims[0]
+        first_ld = int(n0.max()) if first and self.members else 0
+        status = np.zeros(self.members, dtype=np.int32)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            ws = torch.empty((max(nbytes.value, 256),), dtype=torch.uint8, device=self.device)
+            out = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
+            cam = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device)
+            filt = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device)
+            slab = torch.empty((self.members, first_ld, first_ld), dtype=torch.float64, device=self.device) if first_ld else None
+            self._check(self.lib.ekf_batch_smooth_history_cov(
+                self.h, history.data_ptr(), history.numel(), ws.data_ptr(), ws.numel(), 0, out.data_ptr() if frames else None,
+                cam.data_ptr() if frames else None, filt.data_ptr() if frames else None,
+                slab.data_ptr() if slab is not None else None, first_ld, _iptr(status)))
+            self.stream.synchronize()
+        self.last_smooth_status = status
+        rows, cam, filt = out.cpu().numpy(), cam.cpu().numpy(), filt.cpu().numpy()
+        cut = lambda a: [a[mf[b]:mf[b + 1]] for b in range(self.members)]
+        if not first:
+            return cut(rows), cut(cam), cut(filt)
+        slabs = slab.cpu().numpy() if slab is not None else np.zeros((self.members, 0, 0))
+        return cut(rows), cut(cam), cut(filt), [slabs[b, :n0[b], :n0[b]].copy() for b in range(self.members)]
+
     def history_records(self, b) -> list:
         """The records of member b in the last recorded call, as ``tests/smooth_util.device_records`` lists a single filter's:
         dicts ``frame`` (within the member's log), ``dims``, ``s_eff``, ``u`` [6], ``stepped``, ``x`` [N], ``P`` [N, N]."""
@@ -907,11 +964,13 @@ class EKFBatch:
                             "stepped": bool(stepped[i]), "x": x, "P": p})
         return records
 
-    def smooth_replicas(self, log, sigma, seed: int, *, first_replica: int = 0):
+    def smooth_replicas(self, log, sigma, seed: int, *, first_replica: int = 0, cov: bool = False):
         """``replay_replicas(log, sigma, seed)`` recorded and smoothed: every member replays ONE log as replica
         ``first_replica + b`` (the poses of ``replica_poses``, drawn on the device) and gets its own backward pass.  Returns
         ``(filtered [B, F, 7], smoothed [B, F, 7])``; ``filtered`` has the bits of ``replay_replicas``' trajectories on an
-        equal batch.  "How much does smoothing buy at this noise level, this gate, these noise constants" is one call."""
+        equal batch.  "How much does smoothing buy at this noise level, this gate, these noise constants" is one call.
+        Keyword-only ``cov=True``: ``(filtered, smoothed, filtered_cov [B, F, 10, 10], smoothed_cov [B, F, 10, 10])`` -- "is the
+        smoothed uncertainty honest" (the NEES of the smoothed pose over the replicas) is the same call."""
         torch = self._torch
         B = self.members
         sig = replica_sigma(sigma, B)
@@ -930,7 +989,10 @@ class EKFBatch:
         traj = self.observe_indexed(np.tile(idx, B), offsets, F * np.arange(B + 1, dtype=np.int64), noisy, record=True)
         self._adopt_plans([plan] * B)
         self.last_ignored = [tuple(plan.ignored)] * B
-        return traj.reshape(B, F, 7), np.stack(self.smooth_history()) if B else np.zeros((0, F, 7))
+        if not cov:
+            return traj.reshape(B, F, 7), np.stack(self.smooth_history()) if B else np.zeros((0, F, 7))
+        smoothed, smoothed_cov, filtered_cov = self.smooth_history_cov()
+        return traj.reshape(B, F, 7), np.stack(smoothed), np.stack(filtered_cov), np.stack(smoothed_cov)
 
     def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False,
                         mahal: bool = False, noise=None, scale=None, motion=None, record: bool = False):

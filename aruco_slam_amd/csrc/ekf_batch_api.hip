@@ -408,6 +408,33 @@ BatchSmoothLayout batch_smooth_layout(size_t records, int32_t B) {
     return {tables, members, w.end};
 }
 
+// covariance workspace: the smoothing workspace, then [cov members | member 0: W Z T P^s | member 1: ...], a member's four
+// matrices [ld][ld] with ld = the dims of its largest record rounded up to the tile (nothing for a member without a record)
+struct BatchSmoothCovLayout {
+    BatchSmoothLayout base;
+    size_t cov_members, regions, total;
+    std::vector<EkfBatchSmoothCovMember> members;      // region: doubles from `regions`
+};
+BatchSmoothCovLayout batch_smooth_cov_layout(const BatchSmoothTables& tab, int32_t B) {
+    BatchSmoothCovLayout L;
+    L.base = batch_smooth_layout(tab.tables.size(), B);
+    Carve w;
+    w.end = L.base.total;
+    L.cov_members = w.take((size_t)B * sizeof(EkfBatchSmoothCovMember));
+    L.regions = w.end;
+    for (int32_t m = 0; m < B; ++m) {
+        const EkfBatchSmoothMember& mem = tab.members[m];
+        int32_t nmax = 0;
+        for (int32_t r = 0; r < mem.records; ++r) nmax = std::max(nmax, tab.tables[(size_t)mem.table + r].dims);
+        EkfBatchSmoothCovMember cm{};
+        cm.ld = (nmax + EKF_SMOOTH_COV_TILE - 1) / EKF_SMOOTH_COV_TILE * EKF_SMOOTH_COV_TILE;
+        cm.region = (int64_t)((w.take((size_t)4 * cm.ld * cm.ld * 8) - L.regions) / 8);
+        L.members.push_back(cm);
+    }
+    L.total = w.end;
+    return L;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1099,6 +1126,72 @@ int ekf_batch_smooth_history(ekf_batch* b, const void* history_dev, size_t histo
     // every member has its own status word: a P_p that is not positive definite is reported there and nowhere else
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (status_out) HIP_TRY(hipMemcpy(status_out, status, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return EKF_OK;
+}
+
+// ---- batch smoothing, covariances (include/ekf_slam_hip.h, "Batch smoothing, covariances"; ekf_batch_smooth_cov.hip) ------
+int ekf_batch_smooth_cov_workspace_bytes(ekf_batch* b, size_t* bytes) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if (!bytes) return fail(EKF_ERR_INVALID, "bytes is NULL");
+    if ((rc = batch_history_fetch(b))) return rc;
+    *bytes = batch_smooth_cov_layout(b->hist.tab, b->members).total;
+    return EKF_OK;
+}
+
+int ekf_batch_smooth_history_cov(ekf_batch* b, const void* history_dev, size_t history_bytes, void* ws, size_t ws_bytes,
+                                 int32_t flags, double* smoothed_dev, double* cam_cov_dev, double* filt_cam_cov_dev,
+                                 double* first_cov_dev, int32_t first_ld, int32_t* status_out) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if ((rc = batch_smoothing_supported(b))) return rc;
+    if (!b->hist.valid)
+        return fail(EKF_ERR_STATE, "no recorded call (ekf_batch_observe_logs_recorded), or a member has been reset, set or pruned since");
+    if (history_dev != b->hist.buf || history_bytes < b->hist.plan.total)
+        return fail(EKF_ERR_STATE, "not the history of this handle's last recorded call");
+    if (flags != 0) return fail(EKF_ERR_INVALID, "flags is reserved (0)");
+    if ((rc = batch_history_fetch(b))) return rc;
+    const int32_t B = b->members;
+    const BatchSmoothTables& tab = b->hist.tab;
+    if (first_cov_dev)
+        for (int32_t m = 0; m < B; ++m)
+            if (tab.members[m].records > 0 && first_ld < tab.tables[(size_t)tab.members[m].table].dims)
+                return fail(EKF_ERR_INVALID, "first_ld is below member " + std::to_string(m) + "'s first record (N_0)");
+    const BatchSmoothCovLayout L = batch_smooth_cov_layout(tab, B);
+    if (ws_bytes < L.total) return fail(EKF_ERR_INVALID, "workspace smaller than ekf_batch_smooth_cov_workspace_bytes");
+    if (status_out) std::memset(status_out, 0, (size_t)B * 4);
+    if (b->hist.member_frames[B] == 0) return EKF_OK;
+    if (!smoothed_dev || !cam_cov_dev) return fail(EKF_ERR_INVALID, "smoothed_dev or cam_cov_dev is NULL");
+    if ((rc = check_device_buffers({ws}, ws_bytes, L.total, "ekf_batch_smooth_cov_workspace_bytes"))) return rc;
+    char* w = static_cast<char*>(ws);
+    EkfBatchSmoothCov a{};
+    a.history = static_cast<const double*>(history_dev);
+    a.status = reinterpret_cast<int32_t*>(w);
+    EkfSmoothRec* tables_dev = reinterpret_cast<EkfSmoothRec*>(w + L.base.tables);
+    EkfBatchSmoothMember* members_dev = reinterpret_cast<EkfBatchSmoothMember*>(w + L.base.members);
+    EkfBatchSmoothCovMember* cov_members_dev = reinterpret_cast<EkfBatchSmoothCovMember*>(w + L.cov_members);
+    a.tables = tables_dev;
+    a.members = members_dev;
+    a.cov_members = cov_members_dev;
+    a.regions = reinterpret_cast<double*>(w + L.regions);
+    a.smoothed = smoothed_dev;
+    a.cam_cov = cam_cov_dev;
+    a.filt_cam_cov = filt_cam_cov_dev;
+    a.first_cov = first_cov_dev;
+    a.first_ld = first_ld;
+    a.nmax = tab.nmax;
+    if (!tab.tables.empty())
+        HIP_TRY(hipMemcpyAsync(tables_dev, tab.tables.data(), tab.tables.size() * sizeof(EkfSmoothRec), hipMemcpyHostToDevice,
+                               b->stream));
+    HIP_TRY(hipMemcpyAsync(members_dev, tab.members.data(), (size_t)B * sizeof(EkfBatchSmoothMember), hipMemcpyHostToDevice,
+                           b->stream));
+    HIP_TRY(hipMemcpyAsync(cov_members_dev, L.members.data(), (size_t)B * sizeof(EkfBatchSmoothCovMember), hipMemcpyHostToDevice,
+                           b->stream));
+    // (L outlives the copies: the call waits for the stream below)
+    HIP_TRY(ekf_launch_batch_smooth_cov(a, B, b->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (status_out) HIP_TRY(hipMemcpy(status_out, a.status, (size_t)B * 4, hipMemcpyDeviceToHost));
     return EKF_OK;
 }
 

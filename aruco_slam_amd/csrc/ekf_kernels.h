@@ -371,6 +371,34 @@ struct EkfBatchSmoothMember {
 // nmax: the dims of the call's largest record (<= EKF_SMOOTH_RESIDENT_DIMS).  Returns the error of the attribute call.
 hipError_t ekf_launch_batch_smooth(const double* history, const EkfSmoothRec* tables_dev, const EkfBatchSmoothMember* members_dev,
                                    int32_t members, int32_t nmax, double* smoothed, int32_t* status, hipStream_t s);
+// Batch smoothing, covariances (ekf_batch_smooth_cov.hip; include/ekf_slam_hip.h, "Batch smoothing, covariances"): workgroup
+// b of ekf_batch_smooth_cov_kernel runs the resident pass over member b's records and, inside every backward step, the
+// covariance rule on the factor the state step has just formed in LDS.  A member's region of the workspace holds W, Z, T
+// and P^s, four [ld][ld] matrices of f64 with ld = the dims of its largest record rounded up to 16.
+#define EKF_SMOOTH_COV_TILE 16
+struct EkfBatchSmoothCovMember {
+    int64_t region;             // doubles from `regions`: W | Z | T | P^s, ld * ld each
+    int32_t ld;                 // 0 for a member without a record
+    int32_t pad;
+};
+struct EkfBatchSmoothCov {
+    const double* history;
+    const EkfSmoothRec* tables;
+    const EkfBatchSmoothMember* members;
+    const EkfBatchSmoothCovMember* cov_members;
+    double* regions;
+    double* smoothed;           // [Ftot][7]
+    double* cam_cov;            // [Ftot][10][10]
+    double* filt_cam_cov;       // [Ftot][10][10] or NULL
+    double* first_cov;          // [B][first_ld][first_ld] or NULL
+    int32_t first_ld;
+    int32_t nmax;               // the dims of the call's largest record (<= EKF_SMOOTH_RESIDENT_DIMS)
+    int32_t* status;            // [B]
+};
+// dynamic LDS of the kernel for a call whose largest record has nmax dims: the triangle, the inverses of the diagonal
+// blocks of L and ten rows of F P_r
+size_t ekf_batch_smooth_cov_lds(int32_t nmax);
+hipError_t ekf_launch_batch_smooth_cov(const EkfBatchSmoothCov& a, int32_t members, hipStream_t s);
 
 // Batch of independent filters (ekf_batch.hip: EKF, ekf_batch_rot.hip: EKF_Rotations; frame body ekf_batch_impl.h): one
 // workgroup per member, frames [member_frames[b] + window_first, + window_frames) of its log.  Everything is validated on

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "ekf_smooth_workspace_bytes", "ekf_smooth_history", "ekf_smooth_cov_workspace_bytes", "ekf_smooth_history_cov",
     "ekf_batch_history_bytes", "ekf_batch_observe_logs_recorded", "ekf_batch_history_info", "ekf_batch_history_record",
     "ekf_batch_history_table", "ekf_batch_smooth_workspace_bytes", "ekf_batch_smooth_history",
+    "ekf_batch_smooth_cov_workspace_bytes", "ekf_batch_smooth_history_cov",
 )
 
 
@@ -175,6 +176,8 @@ def load_library(path: str | Path | None = None):
                                     ip, ip, ip, dp, ip],
         "ekf_batch_smooth_workspace_bytes": [vp, C.POINTER(C.c_size_t)],
         "ekf_batch_smooth_history": [vp, vp, C.c_size_t, vp, C.c_size_t, vp, ip],
+        "ekf_batch_smooth_cov_workspace_bytes": [vp, C.POINTER(C.c_size_t)],
+        "ekf_batch_smooth_history_cov": [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int32, vp, vp, vp, vp, C.c_int32, ip],
         "ekf_remove_workspace_bytes": [vp, C.c_int32, C.POINTER(C.c_size_t)],
         "ekf_remove_markers": [vp, ip, C.c_int32, vp, C.c_int64, vp, vp, C.c_size_t],
         "ekf_batch_remove_workspace_bytes": [vp, C.c_int64, C.POINTER(C.c_size_t)],

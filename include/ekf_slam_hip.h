@@ -903,8 +903,9 @@ int ekf_batch_get_map_frozen(const ekf_batch *b, int32_t *out /* [B] */);
  *   N: a launch sequence per step (the right-hand sides F~ P_r ride along the blocked f64 Cholesky, then a block backward
  *   substitution and three N x N x N products on the f64 matrix cores); records of up to 8064 dims, larger ones
  *   EKF_ERR_CAPACITY.  `flags` is reserved (0).
- * Not in this interface: recording from per-frame ekf_observe calls; for the covariances: ekf_batch, a resident
- * one-workgroup form, EKF_MODEL_ROTATIONS and the f32 covariance (ekf_batch: "Batch smoothing" below). */
+ * Not in this interface: recording from per-frame ekf_observe calls; for the covariances of the single filter: a resident
+ * one-workgroup form, EKF_MODEL_ROTATIONS and the f32 covariance (ekf_batch has the resident form: "Batch smoothing,
+ * covariances" below). */
 int ekf_observe_log_recorded(ekf_filter *f, const int32_t *lm_index, const int64_t *offsets, int32_t frames,
                              const double *poses_dev, const double *rows_dev, const double *scale, const double *motion,
                              void *log_ws, size_t log_ws_bytes, double *trajectory_dev, double *mahal_dev,
@@ -973,8 +974,29 @@ int ekf_smooth_history_cov(ekf_filter *f, const void *history_dev, size_t histor
  *                                    per record in member order, its member, its rows [frame0, frame1), Q_eff [3], moved.
  *   ekf_batch_smooth_workspace_bytes, ekf_batch_smooth_history: the pass; smoothed_dev [Ftot][7], status_out [B] on the host
  *                                    (or NULL).  Waits for the stream before it returns.
+ * Batch smoothing, covariances.  ekf_batch_smooth_history_cov runs the same pass and, inside it, the covariance rule above
+ * (P^s_{R-1} = P_{R-1}, P^s_r = P_r + G_r (P^s_{r+1}[0:N, 0:N] - P_p) G_r^T, in its subtraction-of-products form) per member
+ * with the member's own Q_eff = fl(s_eff q): the smoothed covariances of every member in ONE launch, one workgroup per member.
+ * The factor L of P_p is the one the state step has just formed in LDS -- P_p is not factored twice and the state arithmetic is
+ * that of ekf_batch_smooth_history: smoothed_dev has its bits.  W = L^-1 F~ P_r, Z = L^-T W, T = P^s_{r+1} Z and P^s live in the
+ * member's own region of the workspace ([ld][ld] each, ld = the dims of the member's largest record rounded up to 16; at most
+ * 819 200 bytes per member); the products run on the f64 matrix cores, every sum is one chain in a fixed order in a fixed wave,
+ * and P^s is zeroed by the kernel before its first use: the bits of a member depend neither on the batch around it nor on
+ * what the workspace held.  Only the lower triangle is computed and mirrored: cam_cov and first_cov are bitwise symmetric.
+ *   Outputs: smoothed_dev [Ftot][7]; cam_cov_dev [Ftot][10][10] = P^s[0:10, 0:10] of the member's last record at or before the
+ *   frame; filt_cam_cov_dev [Ftot][10][10] = that record's P[0:10, 0:10] (or NULL); first_cov_dev [B][first_ld][first_ld]: member
+ *   b's slab holds P^s_0 in [0:N_0, 0:N_0] with leading dimension first_ld, the rest of the slab is not written (or NULL).  The
+ *   last record's cam_cov rows are its filtered ones.  Frames before a member's first record: the pose rows repeat the start
+ *   camera, the covariance rows are NaN.  A member with no record: its first_cov slab is NOT written.
+ *   Failures.  A member with a P_p that is not positive definite has NaN on all its rows of all three per-frame outputs, NaN in
+ *   [0:N_0, 0:N_0] of its first_cov slab and EKF_ERR_NUMERIC in its entry of status_out; no other member notices and the call
+ *   returns EKF_OK.  A member that failed in the replay has NaN from its failing frame on in all three outputs.  The pass
+ *   never writes state, P or the replay status of any member.
+ *   Binding and refusals are those of ekf_batch_smooth_history; in addition a workspace below
+ *   ekf_batch_smooth_cov_workspace_bytes, a first_ld below some member's N_0 (with first_cov_dev given) and non-zero flags
+ *   (reserved) are EKF_ERR_INVALID before anything is enqueued.  Waits for the stream before it returns.
  * Not in this interface: a blocked tier for batches (members beyond 50 landmarks), recording in the HBM-resident window
- * kernels (large maps, wide frames), smoothed covariances, smoothed landmark outputs. */
+ * kernels (large maps, wide frames), smoothed landmark outputs. */
 int ekf_batch_history_bytes(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets, const int64_t *member_frames,
                             int32_t with_motion, size_t *bytes);
 int ekf_batch_observe_logs_recorded(ekf_batch *b, const int32_t *lm_index, const int64_t *frame_offsets,
@@ -995,6 +1017,12 @@ int ekf_batch_history_table(int32_t members, const int64_t *member_frames, const
 int ekf_batch_smooth_workspace_bytes(ekf_batch *b, size_t *bytes);
 int ekf_batch_smooth_history(ekf_batch *b, const void *history_dev, size_t history_bytes, void *ws, size_t ws_bytes,
                              double *smoothed_dev /* [Ftot][7] */, int32_t *status_out /* [B] host, or NULL */);
+int ekf_batch_smooth_cov_workspace_bytes(ekf_batch *b, size_t *bytes);
+int ekf_batch_smooth_history_cov(ekf_batch *b, const void *history_dev, size_t history_bytes, void *ws, size_t ws_bytes,
+                                 int32_t flags /* reserved, 0 */, double *smoothed_dev /* [Ftot][7] */,
+                                 double *cam_cov_dev /* [Ftot][10][10] */, double *filt_cam_cov_dev /* or NULL */,
+                                 double *first_cov_dev /* [B][first_ld][first_ld], or NULL */, int32_t first_ld,
+                                 int32_t *status_out /* [B] host, or NULL */);
 
 const char *ekf_last_error_string(void);
 

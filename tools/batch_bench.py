@@ -39,6 +39,11 @@ and the batched backward pass (EKFBatch.smooth_history: us per record per member
 min .. max.  Beside them the same work the only way there was before: EKF.smooth_detection_log, one filter after the other,
 timed over --single-members of the logs and scaled to the batch size.  Default members: 16 256.  Lines go to
 profiles/batch_smooth/batch_bench.jsonl.
+--smooth --cov: the same rounds with the smoothed covariances: every round also times EKFBatch.smooth_history_cov over the
+same history (the state pass beside it is the first comparison), and the single-filter loop runs
+EKF.smooth_detection_log(cov=True) (the second).  The method's wall time includes the copies of its outputs to the host
+(200 doubles per frame); "state_call" / "cov_call" time the two library calls alone, on buffers allocated once.  Lines
+carry "cov": true; default members 1 16 256.
 """
 from __future__ import annotations
 
@@ -103,6 +108,9 @@ def main():
     ap.add_argument("--smooth", action="store_true",
                     help="batch smoothing: recorded against plain replay, the batched backward pass, and the same logs "
                          "through a loop of single filters (EKF.smooth_detection_log)")
+    ap.add_argument("--cov", action="store_true",
+                    help="--smooth: time the covariance pass (EKFBatch.smooth_history_cov) beside the state pass, and the "
+                         "single-filter loop with cov=True")
     ap.add_argument("--single-members", type=int, default=8,
                     help="--smooth: how many members the single-filter loop really runs (its time per member is reported)")
     args = ap.parse_args()
@@ -304,6 +312,33 @@ def frozen(args, n, m_hi, visible):
     append(args.out, lines)
 
 
+def _smooth_calls(batch, torch):
+    """(state, cov): closures that run ekf_batch_smooth_history / ekf_batch_smooth_history_cov on the batch's last history
+    with buffers allocated here, once -- the library call alone (it waits for the stream), without the copies to the host."""
+    import ctypes as C
+    from aruco_slam_amd.batch import _iptr
+    need, need_cov = C.c_size_t(), C.c_size_t()
+    batch._check(batch.lib.ekf_batch_smooth_workspace_bytes(batch.h, C.byref(need)))
+    batch._check(batch.lib.ekf_batch_smooth_cov_workspace_bytes(batch.h, C.byref(need_cov)))
+    frames, hist = int(batch._history_frames[-1]), batch.last_history
+    dev = batch.device
+    ws = torch.empty((max(need_cov.value, need.value, 256),), dtype=torch.uint8, device=dev)
+    rows = torch.empty((frames, 7), dtype=torch.float64, device=dev)
+    cam, filt = (torch.empty((frames, 10, 10), dtype=torch.float64, device=dev) for _ in range(2))
+    status = np.zeros(batch.members, dtype=np.int32)
+    torch.cuda.synchronize()
+
+    def state():
+        batch._check(batch.lib.ekf_batch_smooth_history(batch.h, hist.data_ptr(), hist.numel(), ws.data_ptr(), need.value,
+                                                        rows.data_ptr(), _iptr(status)))
+
+    def cov():
+        batch._check(batch.lib.ekf_batch_smooth_history_cov(batch.h, hist.data_ptr(), hist.numel(), ws.data_ptr(),
+                                                            need_cov.value, 0, rows.data_ptr(), cam.data_ptr(),
+                                                            filt.data_ptr(), None, 0, _iptr(status)))
+    return state, cov
+
+
 def smooth(args):
     """--smooth: see the module docstring."""
     import torch
@@ -317,7 +352,7 @@ def smooth(args):
     if n > 50 or m_hi > 16 or args.model != "ekf":
         raise SystemExit("--smooth: EKF, at most 50 landmarks and 16 detections per frame (the resident tier)")
     steady = args.steady if args.steady != 500 else 200
-    members = args.members or [16, 256]
+    members = args.members or ([1, 16, 256] if args.cov else [16, 256])
     logs = []
     for s in range(max(members)):
         lg = ragged_log(n, (1, m_hi), steady, seed=s)
@@ -331,13 +366,14 @@ def smooth(args):
         flt = EKF(INIT, max_landmarks=n, max_visible=16, cov_dtype="float64", quat_update="scalar_first")
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        flt.smooth_detection_log(lg["ids"], lg["poses"], lg["offsets"], lg["has_detections"])
+        flt.smooth_detection_log(lg["ids"], lg["poses"], lg["offsets"], lg["has_detections"], **({"cov": True} if args.cov else {}))
         single.append(time.perf_counter() - t0)
         del flt
     single = single[1:] or single
     for B in members:
         frames = sum(len(lg["offsets"]) - 1 for lg in logs[:B])
-        walls = {"plain": [], "recorded": [], "pass": []}
+        walls = {"plain": [], "recorded": [], "pass": [],
+                 **({"cov_pass": [], "state_call": [], "cov_call": []} if args.cov else {})}
         batch = EKFBatch(B, INIT, **kw)
         for rnd in range(6):      # one untimed round, five timed
             for name in ("plain", "recorded"):
@@ -351,6 +387,15 @@ def smooth(args):
             batch.smooth_history()
             walls["pass"].append(time.perf_counter() - t0)
             assert not batch.last_smooth_status.any()
+            if args.cov:
+                t0 = time.perf_counter()
+                batch.smooth_history_cov()
+                walls["cov_pass"].append(time.perf_counter() - t0)
+                assert not batch.last_smooth_status.any()
+                for name, call in zip(("state_call", "cov_call"), _smooth_calls(batch, torch)):
+                    t0 = time.perf_counter()
+                    call()
+                    walls[name].append(time.perf_counter() - t0)
         records = [len(batch.history_records(b)) for b in range(min(B, 4))]
         per_member = float(np.mean(records))      # (every frame of these logs is a record)
         hist_bytes = int(batch.last_history.numel())
@@ -368,6 +413,18 @@ def smooth(args):
                 "single_loop_s_for_these_members": round(median(single) * B, 4),
                 "batch_smooth_s": round(stat["recorded"][0] + stat["pass"][0], 6),
                 "speedup_over_single_loop": round(median(single) * B / (stat["recorded"][0] + stat["pass"][0]), 2)}
+        if args.cov:
+            cov = stat["cov_pass"]
+            line.update({"cov": True, "cov_pass_wall_s": [round(x, 6) for x in cov],
+                         "cov_pass_us_per_record_per_member": round(1e6 * cov[0] / per_member, 3),
+                         "cov_pass_over_state_pass": round(cov[0] / stat["pass"][0], 3),
+                         "state_call_wall_s": [round(x, 6) for x in stat["state_call"]],
+                         "cov_call_wall_s": [round(x, 6) for x in stat["cov_call"]],
+                         "state_call_us_per_record_per_member": round(1e6 * stat["state_call"][0] / per_member, 3),
+                         "cov_call_us_per_record_per_member": round(1e6 * stat["cov_call"][0] / per_member, 3),
+                         "cov_call_over_state_call": round(stat["cov_call"][0] / stat["state_call"][0], 3),
+                         "batch_smooth_s": round(stat["recorded"][0] + cov[0], 6),
+                         "speedup_over_single_loop": round(median(single) * B / (stat["recorded"][0] + cov[0]), 2)})
         print(json.dumps(line), flush=True)
         lines.append(line)
         del batch

@@ -10,13 +10,13 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB_DIR = PKG / "lib"
 LIB_PATH = LIB_DIR / "libekf_slam_hip.so"
-SOURCES = ["ekf_api.hip", "ekf_batch_api.hip", "ekf_small_kernels.hip", "ekf_front.hip", "ekf_front_f64.hip", "ekf_cov_update.hip", "ekf_cov_macro.hip", "ekf_cov_strip.hip", "ekf_pose_ippe.hip",
+SOURCES = ["ekf_api.hip", "ekf_frames.hip", "ekf_log_api.hip", "ekf_smooth_api.hip", "ekf_batch_api.hip", "ekf_small_kernels.hip", "ekf_front.hip", "ekf_front_f64.hip", "ekf_cov_update.hip", "ekf_cov_macro.hip", "ekf_cov_strip.hip", "ekf_pose_ippe.hip",
            "ekf_wide.hip", "ekf_log.hip", "ekf_gate.hip", "ekf_remove.hip", "ekf_motion.hip", "ekf_batch.hip", "ekf_batch_rot.hip", "ekf_batch_wide.hip", "ekf_batch_moved.hip", "ekf_batch_wide_moved.hip",
            "ekf_batch_frozen.hip", "ekf_batch_wide_frozen.hip",
            "ekf_batch_recorded.hip",
            "ekf_batch_replicas.hip", "ekf_batch_corner_replicas.hip", "ekf_smooth.hip", "ekf_smooth_cov.hip",
            "ekf_batch_smooth_cov.hip"]
-HEADERS = ["ekf_device.h", "ekf_kernels.h", "ekf_solve_device.h", "ekf_solve_big.h", "ekf_solve_cw.h", "ekf_front_impl.h", "ekf_markers.h", "ekf_host.h", "ekf_batch_impl.h", "ekf_gate_device.h", "ekf_motion_device.h", "ekf_ippe_device.h", "ekf_philox.h", "ekf_remove.h", "ekf_smooth_device.h", "ekf_batch_smooth_host.h", "ekf_smooth_resident.h",
+HEADERS = ["ekf_device.h", "ekf_kernels.h", "ekf_solve_device.h", "ekf_solve_big.h", "ekf_solve_cw.h", "ekf_front_impl.h", "ekf_markers.h", "ekf_host.h", "ekf_filter.h", "ekf_smooth_host.h", "ekf_batch_impl.h", "ekf_gate_device.h", "ekf_motion_device.h", "ekf_ippe_device.h", "ekf_philox.h", "ekf_remove.h", "ekf_smooth_device.h", "ekf_batch_smooth_host.h", "ekf_smooth_resident.h",
            "../../include/ekf_slam_hip.h"]
 
 

@@ -2,12 +2,9 @@
 // from the logs alone -- and the tables of the backward pass -- from the per-frame words the device wrote.  No device call in
 // here: ekf_batch_api.hip uses both, and ekf_batch_history_table exposes the second to callers without a handle.
 #pragma once
-#include "ekf_host.h"
+#include "ekf_smooth_host.h"
 
 namespace {
-
-// one record: state [dims] and the packed lower triangle, f64, in a 256-byte aligned piece (ekf_history_record_bytes)
-size_t batch_record_bytes(int64_t dims) { return align256((size_t)(dims + dims * (dims + 1) / 2) * 8); }
 
 // The history buffer of a recorded batch call:
 //   [member 0: 256 B header | slots] [member 1: ...] ... | head [B] i64 | slot [Ftot] i64 | flag [Ftot] i32 |
@@ -31,7 +28,7 @@ void batch_history_add_member(BatchHistoryPlan& p, const int64_t* offsets, int64
         const bool has = with_motion || offsets[t + 1] > offsets[t];
         p.dims.push_back((int32_t)dims);
         p.slot.push_back(has ? (int64_t)(p.total / 8) : -1);
-        if (has) p.total += batch_record_bytes(dims);
+        if (has) p.total += history_record_bytes(dims);      // (one record, as the filter handle's: ekf_smooth_host.h)
     }
 }
 

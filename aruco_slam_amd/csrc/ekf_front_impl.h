@@ -16,7 +16,7 @@
 //                  for its own columns (the only readers of the old state are workgroups 0 .. nS, which
 //                  the factorisation has waited for).  EKF_Rotations: the LAST chunk to finish injects
 //                  (every landmark carries a quaternion that straddles chunks).
-// Pipelined sequence mode (ekf_api.hip: ekf_observe_sequence_device): the launch runs BESIDE the covariance
+// Pipelined sequence mode (ekf_frames.hip: ekf_observe_sequence_device): the launch runs BESIDE the covariance
 // update of the previous frame, on the previous frame's input P: the S-block and chunk roles complete the
 // entries of the current P they read from (P_prev, W_prev) themselves, with the covariance update's own
 // per-element instruction sequence (same bits); the chunks leave the support columns of W the NEXT frame

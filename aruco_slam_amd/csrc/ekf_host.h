@@ -1,4 +1,5 @@
-// Host helpers shared by the C ABI translation units (ekf_api.hip: the filter handle, ekf_batch_api.hip: the batch handle).
+// Host helpers shared by the C ABI translation units (the filter handle, ekf_filter.h: ekf_api.hip, ekf_frames.hip,
+// ekf_log_api.hip, ekf_smooth_api.hip; the batch handle: ekf_batch_api.hip).
 // Not part of the public interface.
 #pragma once
 

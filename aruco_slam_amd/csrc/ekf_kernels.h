@@ -57,7 +57,7 @@ struct EkfFrame {
     long long* stamps;     // optional: s_memtime stamps of the solve kernel's phases (diagnostics)
     int32_t stamps_heavy;  // 0: only the stamps at the start / end of the roles (a stamp is a global store: the wave that takes it
                            // later waits for its acknowledgement), 1: also inside the factorisation and the chunk prologue
-    // Pipelined sequence mode (ekf_api.hip: ekf_observe_sequence_device).  The covariance lives in TWO buffers: the
+    // Pipelined sequence mode (ekf_frames.hip: ekf_observe_sequence_device).  The covariance lives in TWO buffers: the
     // update of frame t reads `cov` (P_t) and writes `cov_out` (P_{t+1}); the front kernel of frame t+1 runs beside it
     // and takes the entries of P_{t+1} it needs -- support rows only -- from P_t and W_t on the fly:
     //     P_{t+1}[r][c] = (P_t[r][c] + Q[r == c]) + sum_k fma(-W_t[k][r], W_t[k][c])     (k ascending, from zero)
@@ -70,7 +70,7 @@ struct EkfFrame {
     void* cov_out;             // covariance update: destination (null = in place)
     const void* wprev;         // front kernel: W panel of the previous frame [kpad][ldw] (null = `cov` is current)
     const void* wsup_prev;     // front kernel: [kpad][wsup_ld], see above
-    // device-side cross-stream ordering of the pipelined sequence mode (ekf_api.hip: run_pipelined):
+    // device-side cross-stream ordering of the pipelined sequence mode (ekf_frames.hip: run_pipelined):
     // la_sync[0] = "front kernel of frame n has started" counter, la_sync[1] = "covariance update of frame n is
     // complete" counter.  A front kernel stores la_signal into [0] when it starts (0 = no) and does not
     // finish before [1] >= la_gate (0 = no gate).  A covariance update stores cov_signal into [1] itself once all its

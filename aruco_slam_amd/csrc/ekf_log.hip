@@ -1,4 +1,4 @@
-// Kernels of the log replay (ekf_observe_log, ekf_api.hip): a whole ragged detection log in one call.
+// Kernels of the log replay (ekf_observe_log, ekf_log_api.hip): a whole ragged detection log in one call.
 //   prepare     : every detection's measurement z from its logged pose, once per call
 //   add_markers : first sightings of a frame, gathered from the logged poses (the add_marker arithmetic of ekf_markers.h)
 //   fill_rows   : trajectory rows of frames without detections (the filter is not stepped there)

@@ -14,7 +14,7 @@
 // The right-hand sides ride along: the rows of A (a copy in `aw`, so that A stays readable) become W = L^-1 A and the
 // residual becomes y = L^-1 (z - h), in place.  Then
 //   finish  : W to the covariance-dtype panel (and the f64 debug copy), dx = W^T y, state injection.
-// The covariance update P <- P + Q - W^T W is the existing launchers applied to row chunks of W (ekf_api.hip).
+// The covariance update P <- P + Q - W^T W is the existing launchers applied to row chunks of W (ekf_frames.hip).
 #include "ekf_kernels.h"
 #include "ekf_solve_device.h"
 

@@ -272,18 +272,18 @@ def f64_split_items():
 
 
 def macro_min_tiles():
-    return int(re.search(r"kMacroMinTiles = (\d+);", (CSRC / "ekf_api.hip").read_text()).group(1))
+    return int(re.search(r"kMacroMinTiles = (\d+);", (CSRC / "ekf_filter.h").read_text()).group(1))
 
 
 def instances_of(case):
     """The instances one frame of `case` runs -- a Python restatement of the dispatch:
-      ekf_api.hip enqueue_frame (:349-432): fused front kernel if use_front_kernel (:297: not flags bit 2, kpad <= 192);
-        else a wide frame (m > 64 / 50, visible_cap :31-32) -- blocked beyond kpad 384 (EKF_WIDE_REUSE_ROWS), else the
+      ekf_frames.hip enqueue_frame (:162-260): fused front kernel if use_front_kernel (:108: not flags bit 2, kpad <= 192);
+        else a wide frame (m > 64 / 50, visible_cap, ekf_filter.h:19-20) -- blocked beyond kpad 384 (EKF_WIDE_REUSE_ROWS), else the
         stage solve / panel; else gather + stage solve / panel.  The covariance update runs once, or per 384-row chunk.
       ekf_front_impl.h ekf_launch_front (:1419-1440): NU / MODEL / NB by model and m.
       ekf_small_kernels.hip ekf_launch_solve / ekf_launch_panel (:212-219, :302-311): NB = kpad / 16.
       ekf_cov_update.hip ekf_launch_cov_update (:396-430): VALU when forced; f32: macro-tile when the launch table exists
-        (ensure_tiles, ekf_api.hip:328-331: forced, or kMacroMinTiles lower-triangle tiles), else wave-per-tile KB;
+        (ensure_tiles, ekf_frames.hip:137-142: forced, or kMacroMinTiles lower-triangle tiles), else wave-per-tile KB;
         f64: split up to `items` 32 x 32 tiles, full above."""
     rd = 7 if case.model == "rot" else 3
     lmd = 10 if case.model == "rot" else 3

@@ -4,7 +4,7 @@ or serial?  Both orders, 2000 frames per call after a warm-up call of the same l
 also pays the one-time queue self-test), measured two ways in the same process:
   * device clock: start-to-start of the last 16 front kernels of the call (in-kernel stamps, s_memrealtime, no profiler);
   * host clock: wall time of the call / frames.
-Output: one line per shape; the table is committed under profiles/ and the size rule in ekf_api.hip follows it."""
+Output: one line per shape; the table is committed under profiles/ and the size rule in ekf_frames.hip (pipeline_wanted) follows it."""
 import sys
 import time
 import numpy as np

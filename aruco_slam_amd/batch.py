@@ -55,8 +55,8 @@ import numpy as np
 
 from .filters.base_filter import plan_detection_log
 from .hip_backend import (EKF_FLAG_BATCH_LARGE_MAPS, EKF_FLAG_BATCH_WIDE_FRAMES, EKF_FLAG_FRAME_SCALE, EKF_FLAG_MOTION,
-                          EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError, _dptr, frame_scale_array,
-                          load_library, motion_array, row_noise_array)
+                          EKF_QUAT_AS_WRITTEN, EKF_QUAT_SCALAR_FIRST, EkfConfig, EkfError, _dptr, _iptr, _lptr,
+                          frame_scale_array, load_library, motion_array, row_noise_array)
 
 NOISE_KEYS = ("initial_camera_uncertainty", "initial_landmark_uncertainty", "r_uncertainty", "q_cam", "q_err", "q_lm")
 EKF_ERR_NUMERIC = -5
@@ -220,6 +220,13 @@ def _replica_range(first_replica, replicas: int) -> int:
     return r0
 
 
+def _seed(seed) -> int:
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2**64)")
+    return seed
+
+
 def replica_poses(poses, sigma, seed: int, *, replicas: int | None = None, first_replica: int = 0,
                   device: str = "cuda:0") -> np.ndarray:
     """The noisy poses [R, D, 6] that replicas ``first_replica`` .. ``first_replica + R - 1`` of a log with ``poses`` [D, 6]
@@ -239,10 +246,7 @@ def replica_poses(poses, sigma, seed: int, *, replicas: int | None = None, first
             raise ValueError("give replicas= unless sigma is [R, 6]")
         replicas = s.shape[0]
     sig = replica_sigma(sigma, int(replicas))
-    r0 = _replica_range(first_replica, replicas)
-    seed = int(seed)
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("seed must be in [0, 2**64)")
+    r0, seed = _replica_range(first_replica, replicas), _seed(seed)
     dev = torch.device(device)
     with torch.cuda.device(dev):
         src = torch.from_numpy(poses).to(dev)
@@ -273,10 +277,7 @@ def _replica_corner_outputs(want, corners, sigma_px, seed, camera_matrix, dist_c
         replicas = np.shape(sigma_px)[0]
     R, D = int(replicas), corners.shape[0]
     sig = replica_sigma_px(sigma_px, R)
-    r0 = _replica_range(first_replica, R)
-    seed = int(seed)
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("seed must be in [0, 2**64)")
+    r0, seed = _replica_range(first_replica, R), _seed(seed)
     k, d, size = camera_arrays(camera_matrix, dist_coeffs, marker_size)
     dev = torch.device(device)
     shapes = {"poses": ((R, D, 6), torch.float64), "flipped": ((R, D), torch.uint8), "noisy": ((R, D, 4, 2), torch.float64)}
@@ -342,14 +343,6 @@ def replica_z(poses, model: str) -> np.ndarray:
     from .filters.ekf_with_rotations import euler_xyz_to_quat
     quat = euler_xyz_to_quat(poses[..., 3:6].reshape(-1, 3)).reshape(poses.shape[:-1] + (4,))
     return np.concatenate((poses[..., :3], quat), axis=-1)
-
-
-def _iptr(a: np.ndarray):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
-
-
-def _lptr(a: np.ndarray):
-    return a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
 class EKFBatch:
@@ -633,21 +626,21 @@ class EKFBatch:
         poses = np.ascontiguousarray(np.concatenate(poses) if poses else np.zeros((0, 6)))
         if sum(c.shape[0] for _, c in corner_parts):
             poses = self._estimate_corner_logs(poses, corner_parts)
-        with_rows = {"noise": np.concatenate(rows)} if any_rows and rows else {}      # (no rows: the call as it ever was)
+        # only what the caller set travels as a keyword (no rows: the call as it ever was)
+        given = {"noise": np.concatenate(rows)} if any_rows and rows else {}
         if scales:
-            with_rows["scale"] = np.concatenate(scales)
+            given["scale"] = np.concatenate(scales)
         if motions:
-            with_rows["motion"] = np.concatenate(motions)
+            given["motion"] = np.concatenate(motions)
         if record:      # (the recorded call: the same outputs, and the history in last_history)
-            with_rows["record"] = True
+            given["record"] = True
+        if gated or nis or cam_cov:
+            given.update(nis=nis, cam_cov=cam_cov)
         if gated:
-            traj, nis_v, cov_v, mahal_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses,
-                                                               nis=nis, cam_cov=cam_cov, mahal=True, **with_rows)
-        elif nis or cam_cov:
-            traj, nis_v, cov_v = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses, nis=nis,
-                                                      cam_cov=cam_cov, **with_rows)
-        else:
-            traj = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses, **with_rows)
+            given["mahal"] = True
+        out = self.observe_indexed(index, offsets, np.asarray(frames, dtype=np.int64), poses, **given)
+        # an array, (trajectory, nis, cam_cov) or (trajectory, nis, cam_cov, mahal)
+        traj, nis_v, cov_v, mahal_v = (tuple(out) + (None,))[:4] if isinstance(out, tuple) else (out, None, None, None)
         self._adopt_plans(plans)
         self.last_ignored = [() if plan is None else tuple(plan.ignored) for plan in plans]
         split = [slice(frames[b], frames[b + 1]) for b in range(self.members)]
@@ -724,41 +717,38 @@ class EKFBatch:
         each member's surviving detections, ``mahal`` [B, D] and ``rejected`` [B, D] aligned with the log's detections."""
         gated = mahal or self.gate is not None
         sig = replica_sigma(sigma, self.members)
-        r0 = _replica_range(first_replica, self.members)
-        seed = int(seed)
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError("seed must be in [0, 2**64)")
+        r0, seed = _replica_range(first_replica, self.members), _seed(seed)
         plan, poses, idx, fo = self._plan_replica_log(log, "poses", (6,), "replay_replicas")
+        out = self._run_replicas(plan, poses, idx, fo, nis, cam_cov, gated, lambda head, outputs:
+                                 self.lib.ekf_batch_observe_replicas_gated(*head, _dptr(sig), seed, r0, *outputs))
+        return GatedReplicaReplay(*out) if gated else ReplicaReplay(*out[:4])
+
+    def _run_replicas(self, plan, src, idx, fo, nis: bool, cam_cov: bool, gated: bool, launch):
+        """What the replica calls share once their arguments have passed and the log is planned: ``src`` (the kept poses or
+        corners) uploaded, the workspace and the outputs allocated on the batch's stream, ``launch(head, outputs)`` checked
+        -- head: (handle, indices, offsets, F, src); outputs: (workspace, its bytes, trajectory, nis, cam_cov, mahal), NULL for
+        what is not asked -- the stream synchronised and the plan adopted.  Returns the host arrays (trajectory, nis, dof,
+        cam_cov, mahal, rejected): ``dof`` [F] and no ``mahal`` / ``rejected``, or with ``gated`` ``_replica_gate_outputs``."""
         F, D, B = fo.shape[0] - 1, idx.shape[0], self.members
         torch = self._torch
         nbytes = C.c_size_t()
         self._check(self.lib.ekf_batch_replica_workspace_bytes(self.h, D, F, C.byref(nbytes)))
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            poses_t = torch.from_numpy(poses).to(self.device)
+            new = (lambda want, *shape: torch.empty(shape, dtype=torch.float64, device=self.device) if want else None)
+            src_t = torch.from_numpy(src).to(self.device)
             ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=self.device)
-            traj = torch.empty((B, F, 7), dtype=torch.float64, device=self.device)
-            nis_t = torch.empty((B, F), dtype=torch.float64, device=self.device) if nis else None
-            cov_t = torch.empty((B, F, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
-            mahal_t = torch.empty((B, D), dtype=torch.float64, device=self.device) if gated else None
+            traj, nis_t, cov_t, mahal_t = new(True, B, F, 7), new(nis, B, F), new(cam_cov, B, F, 10, 10), new(gated, B, D)
             ptr = (lambda t: t.data_ptr() if t is not None and F else None)
-            if gated:
-                self._check(self.lib.ekf_batch_observe_replicas_gated(
-                    self.h, _iptr(idx), _lptr(fo), F, ptr(poses_t) if D else None, _dptr(sig), seed, r0, ws.data_ptr(),
-                    nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t), mahal_t.data_ptr() if D else None))
-            else:
-                self._check(self.lib.ekf_batch_observe_replicas(self.h, _iptr(idx), _lptr(fo), F,
-                                                                ptr(poses_t) if D else None, _dptr(sig), seed, r0,
-                                                                ws.data_ptr(), nbytes.value, ptr(traj), ptr(nis_t),
-                                                                ptr(cov_t)))
+            self._check(launch((self.h, _iptr(idx), _lptr(fo), F, src_t.data_ptr() if D else None),
+                               (ws.data_ptr(), nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t),
+                                mahal_t.data_ptr() if gated and D else None)))
             self.stream.synchronize()
         self._adopt_plans([plan] * B)
         self.last_ignored = [tuple(plan.ignored)] * B
-        if gated:
-            full, rej, dof = self._replica_gate_outputs(plan, fo, mahal_t.cpu().numpy())
-            return GatedReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, dof,
-                                      cov_t.cpu().numpy() if cam_cov else None, full, rej)
-        return ReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None,
-                             RD[self.model] * np.diff(fo), cov_t.cpu().numpy() if cam_cov else None)
+        host = (lambda t: None if t is None else t.cpu().numpy())
+        full, rej, dof = self._replica_gate_outputs(plan, fo, host(mahal_t)) if gated else \
+            (None, None, RD[self.model] * np.diff(fo))
+        return host(traj), host(nis_t), dof, host(cov_t), full, rej
 
     def _plan_replica_log(self, log, key: str, tail: tuple, what: str):
         """The one log of a replica call planned on the members' common landmark table: (plan, the kept rows of
@@ -806,45 +796,26 @@ class EKFBatch:
         ``estimate_poses``, and the member stops there (``status``)."""
         gated = mahal or self.gate is not None
         sig = replica_sigma_px(sigma_px, self.members)
-        r0 = _replica_range(first_replica, self.members)
-        seed = int(seed)
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError("seed must be in [0, 2**64)")
+        r0, seed = _replica_range(first_replica, self.members), _seed(seed)
         if self.camera is None:
             raise ValueError("replay_corner_replicas needs set_camera() first")
         if "poses" in log:
             raise ValueError("replay_corner_replicas takes a log of corners [D,4,2], not of poses (replay_replicas)")
         plan, corners, idx, fo = self._plan_replica_log(log, "corners", (4, 2), "replay_corner_replicas")
         k, d, size = self.camera
-        F, D, B = fo.shape[0] - 1, idx.shape[0], self.members
-        torch = self._torch
-        nbytes = C.c_size_t()
-        self._check(self.lib.ekf_batch_replica_workspace_bytes(self.h, D, F, C.byref(nbytes)))
-        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            corners_t = torch.from_numpy(corners).to(self.device)
-            ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=self.device)
-            traj = torch.empty((B, F, 7), dtype=torch.float64, device=self.device)
-            nis_t = torch.empty((B, F), dtype=torch.float64, device=self.device) if nis else None
-            cov_t = torch.empty((B, F, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
-            mahal_t = torch.empty((B, D), dtype=torch.float64, device=self.device) if gated else None
-            flip_t = torch.zeros((B, D), dtype=torch.uint8, device=self.device)
-            ptr = (lambda t: t.data_ptr() if t is not None and F else None)
-            self._check(self.lib.ekf_batch_observe_corner_replicas(
-                self.h, _iptr(idx), _lptr(fo), F, corners_t.data_ptr() if D else None, _dptr(sig), seed, r0, size, _dptr(k),
-                _dptr(d) if d.size else None, int(d.size), ws.data_ptr(), nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t),
-                mahal_t.data_ptr() if gated and D else None, flip_t.data_ptr() if D else None))
-            self.stream.synchronize()
-        self._adopt_plans([plan] * B)
-        self.last_ignored = [tuple(plan.ignored)] * B
+        D, B = idx.shape[0], self.members
+        flip = []      # (allocated with the other outputs, on the batch's stream)
+
+        def launch(head, outputs):
+            flip.append(self._torch.zeros((B, D), dtype=self._torch.uint8, device=self.device))
+            return self.lib.ekf_batch_observe_corner_replicas(
+                *head, _dptr(sig), seed, r0, size, _dptr(k), _dptr(d) if d.size else None, int(d.size), *outputs,
+                flip[0].data_ptr() if D else None)
+        out = self._run_replicas(plan, corners, idx, fo, nis, cam_cov, gated, launch)
         keep = np.asarray(plan.keep, dtype=bool)
         flipped = np.zeros((B, keep.shape[0]), dtype=bool)
-        flipped[:, keep] = flip_t.cpu().numpy().astype(bool)
-        full = rej = None
-        dof = RD[self.model] * np.diff(fo)
-        if gated:
-            full, rej, dof = self._replica_gate_outputs(plan, fo, mahal_t.cpu().numpy())
-        return CornerReplicaReplay(traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, dof,
-                                   cov_t.cpu().numpy() if cam_cov else None, full, rej, flipped)
+        flipped[:, keep] = flip[0].cpu().numpy().astype(bool)
+        return CornerReplicaReplay(*out, flipped)
 
     # -- offline smoothing ---------------------------------------------------------------------------------------------
     def smooth_detection_logs(self, logs, *, mahal: bool = False, cov: bool = False):
@@ -873,28 +844,32 @@ class EKFBatch:
             res = (filtered, self.smooth_history())
         return res + ((out.mahal, out.rejected),) if gated else res
 
+    def _history_open(self, history, workspace_bytes):
+        """The opening of both backward passes: (the history buffer, workspace bytes from ``workspace_bytes``, a zeroed status
+        [B], the frames of the recorded call, the split of its rows per member)."""
+        history = self.last_history if history is None else history
+        if history is None:
+            raise ValueError("no recorded call yet (smooth_detection_logs, or observe_indexed(record=True))")
+        nbytes = C.c_size_t()
+        self._check(workspace_bytes(self.h, C.byref(nbytes)))
+        mf = self._history_frames
+        return (history, max(nbytes.value, 256), np.zeros(self.members, dtype=np.int32), int(mf[-1]),
+                lambda a: [a[mf[b]:mf[b + 1]] for b in range(self.members)])
+
     def smooth_history(self, history=None) -> list:
         """The backward pass over the last recorded call (``ekf_batch_smooth_history``; ``history``: its buffer, default
         ``self.last_history``): per member the smoothed rows ``(F_b, 7)``.  Sets ``last_smooth_status``.  Reads the members
         only; the same history gives the same bits every time."""
         torch = self._torch
-        history = self.last_history if history is None else history
-        if history is None:
-            raise ValueError("no recorded call yet (smooth_detection_logs, or observe_indexed(record=True))")
-        nbytes = C.c_size_t()
-        self._check(self.lib.ekf_batch_smooth_workspace_bytes(self.h, C.byref(nbytes)))
-        mf = self._history_frames
-        frames = int(mf[-1])
-        status = np.zeros(self.members, dtype=np.int32)
+        history, nbytes, status, frames, cut = self._history_open(history, self.lib.ekf_batch_smooth_workspace_bytes)
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            ws = torch.empty((max(nbytes.value, 256),), dtype=torch.uint8, device=self.device)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
             out = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
             self._check(self.lib.ekf_batch_smooth_history(self.h, history.data_ptr(), history.numel(), ws.data_ptr(),
                                                           ws.numel(), out.data_ptr() if frames else None, _iptr(status)))
             self.stream.synchronize()
         self.last_smooth_status = status
-        rows = out.cpu().numpy()
-        return [rows[mf[b]:mf[b + 1]] for b in range(self.members)]
+        return cut(out.cpu().numpy())
 
     def smooth_history_cov(self, history=None, first: bool = False):
         """The backward pass with the smoothed covariances over the last recorded call (``ekf_batch_smooth_history_cov``,
@@ -904,27 +879,15 @@ class EKFBatch:
         ``first`` a fourth list follows: ``P^s_0`` of every member, ``(N_0, N_0)`` (``(0, 0)`` for a member without a record).
         Sets ``last_smooth_status``; a member with EKF_ERR_NUMERIC there has NaN everywhere.  Reads the members only."""
         torch = self._torch
-        history = self.last_history if history is None else history
-        if history is None:
-            raise ValueError("no recorded call yet (smooth_detection_logs, or observe_indexed(record=True))")
-        nbytes = C.c_size_t()
-        self._check(self.lib.ekf_batch_smooth_cov_workspace_bytes(self.h, C.byref(nbytes)))
-        mf = self._history_frames
-        frames = int(mf[-1])
+        history, nbytes, status, frames, cut = self._history_open(history, self.lib.ekf_batch_smooth_cov_workspace_bytes)
         n0 = np.zeros(self.members, dtype=np.int64)
         if first:
-            count = C.c_int32()
             for b in range(self.members):
-                self._check(self.lib.ekf_batch_history_info(self.h, b, C.byref(count), 0, None, None, None, None, None, None))
-                if count.value > 0:
-                    dims = np.zeros(count.value, dtype=np.int32)
-                    self._check(self.lib.ekf_batch_history_info(self.h, b, C.byref(count), count.value, None, _iptr(dims),
-                                                                None, None, None, None))
-                    n0[b] = dims[0]
+                dims = self._history_info(b)[1]
+                n0[b] = dims[0] if dims.size else 0
         first_ld = int(n0.max()) if first and self.members else 0
-        status = np.zeros(self.members, dtype=np.int32)
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            ws = torch.empty((max(nbytes.value, 256),), dtype=torch.uint8, device=self.device)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
             out = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
             cam = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device)
             filt = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device)
@@ -936,32 +899,34 @@ class EKFBatch:
             self.stream.synchronize()
         self.last_smooth_status = status
         rows, cam, filt = out.cpu().numpy(), cam.cpu().numpy(), filt.cpu().numpy()
-        cut = lambda a: [a[mf[b]:mf[b + 1]] for b in range(self.members)]
         if not first:
             return cut(rows), cut(cam), cut(filt)
         slabs = slab.cpu().numpy() if slab is not None else np.zeros((self.members, 0, 0))
         return cut(rows), cut(cam), cut(filt), [slabs[b, :n0[b], :n0[b]].copy() for b in range(self.members)]
 
-    def history_records(self, b) -> list:
-        """The records of member b in the last recorded call, as ``tests/smooth_util.device_records`` lists a single filter's:
-        dicts ``frame`` (within the member's log), ``dims``, ``s_eff``, ``u`` [6], ``stepped``, ``x`` [N], ``P`` [N, N]."""
-        b = self._member(b)
-        ip = C.POINTER(C.c_int32)
+    def _history_info(self, b: int):
+        """(frame, dims, s_eff, motion [R, 6], stepped) of member b's R records in the last recorded call
+        (``ekf_batch_history_info``: the count first, then the arrays)."""
         count = C.c_int32()
         self._check(self.lib.ekf_batch_history_info(self.h, b, C.byref(count), 0, None, None, None, None, None, None))
         r = count.value
         frame, dims, stepped = (np.zeros(max(r, 1), dtype=np.int32) for _ in range(3))
         s_eff, motion = np.zeros(max(r, 1)), np.zeros((max(r, 1), 6))
-        self._check(self.lib.ekf_batch_history_info(self.h, b, C.byref(count), max(r, 1), frame.ctypes.data_as(ip),
-                                                    dims.ctypes.data_as(ip), _dptr(s_eff), _dptr(motion),
-                                                    stepped.ctypes.data_as(ip), None))
+        self._check(self.lib.ekf_batch_history_info(self.h, b, C.byref(count), max(r, 1), _iptr(frame), _iptr(dims),
+                                                    _dptr(s_eff), _dptr(motion), _iptr(stepped), None))
+        return frame[:r], dims[:r], s_eff[:r], motion[:r], stepped[:r]
+
+    def history_records(self, b) -> list:
+        """The records of member b in the last recorded call, as ``tests/smooth_util.device_records`` lists a single filter's:
+        dicts ``frame`` (within the member's log), ``dims``, ``s_eff``, ``u`` [6], ``stepped``, ``x`` [N], ``P`` [N, N]."""
+        b = self._member(b)
         records = []
-        for i in range(r):
-            n = int(dims[i])
+        for i, (frame, n, s_eff, motion, stepped) in enumerate(zip(*self._history_info(b))):
             x, p = np.empty(n), np.empty((n, n))
-            self._check(self.lib.ekf_batch_history_record(self.h, self.last_history.data_ptr(), b, i, _dptr(x), _dptr(p), n))
-            records.append({"frame": int(frame[i]), "dims": n, "s_eff": float(s_eff[i]), "u": motion[i].copy(),
-                            "stepped": bool(stepped[i]), "x": x, "P": p})
+            self._check(self.lib.ekf_batch_history_record(self.h, self.last_history.data_ptr(), b, i, _dptr(x), _dptr(p),
+                                                          int(n)))
+            records.append({"frame": int(frame), "dims": int(n), "s_eff": float(s_eff), "u": motion.copy(),
+                            "stepped": bool(stepped), "x": x, "P": p})
         return records
 
     def smooth_replicas(self, log, sigma, seed: int, *, first_replica: int = 0, cov: bool = False):
@@ -974,10 +939,7 @@ class EKFBatch:
         torch = self._torch
         B = self.members
         sig = replica_sigma(sigma, B)
-        r0 = _replica_range(first_replica, B)
-        seed = int(seed)
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError("seed must be in [0, 2**64)")
+        r0, seed = _replica_range(first_replica, B), _seed(seed)
         plan, poses, idx, fo = self._plan_replica_log(log, "poses", (6,), "smooth_replicas")
         F, D = fo.shape[0] - 1, idx.shape[0]
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
@@ -996,16 +958,16 @@ class EKFBatch:
 
     def observe_indexed(self, lm_index, frame_offsets, member_frames, poses, *, nis: bool = False, cam_cov: bool = False,
                         mahal: bool = False, noise=None, scale=None, motion=None, record: bool = False):
-        """The C call behind ``process_detection_logs`` (landmark indices already assigned; ``landmarks`` is not
-        touched): lm_index [D], frame_offsets [Ftot+1], member_frames [B+1] on the host, poses [D,6] on the host or a contiguous
-        float64 tensor on the batch's device, produced on the batch's stream.  Returns the
-        trajectory [Ftot, 7]; with ``nis`` or ``cam_cov`` the tuple (trajectory, nis [Ftot] or None, cam_cov [Ftot, 10, 10]
+        """The C call behind ``process_detection_logs`` (ekf_batch_observe_logs_moved, NULL for what is not given or not
+        asked; landmark indices already assigned; ``landmarks`` is not touched): lm_index [D], frame_offsets [Ftot+1],
+        member_frames [B+1] on the host, poses [D,6] on the host or a contiguous float64 tensor on the batch's device,
+        produced on the batch's stream.  Returns the trajectory [Ftot, 7]; with ``nis`` or ``cam_cov`` the tuple (trajectory, nis [Ftot] or None, cam_cov [Ftot, 10, 10]
         or None); with ``mahal`` the tuple (trajectory, nis or None, cam_cov or None, mahal [D]).  A gate that is set acts
         on every call, whatever it returns.  ``noise``: [D] or [D, RD] row variances indexed like lm_index (a batch built
-        with ``row_noise=True``; ekf_batch_observe_logs_rows), or None: every member's ``r_uncertainty``.  ``scale``:
-        [Ftot] process-noise scales, one per frame, indexed like frame_offsets (a batch built with ``frame_scale=True``;
-        ekf_batch_observe_logs_scaled), or None: no frame carries one.  ``motion``: [Ftot, 6] camera motions, one per
-        frame, indexed like frame_offsets (a batch built with ``motion=True``; ekf_batch_observe_logs_moved), or None.
+        with ``row_noise=True``), or None: every member's ``r_uncertainty``.  ``scale``: [Ftot] process-noise scales, one
+        per frame, indexed like frame_offsets (a batch built with ``frame_scale=True``), or None: no frame carries one.
+        ``motion``: [Ftot, 6] camera motions, one per frame, indexed like frame_offsets (a batch built with
+        ``motion=True``), or None.
         ``record``: the recorded call (ekf_batch_observe_logs_recorded): the same outputs, bit for bit, and the history of
         the call in ``self.last_history`` for ``smooth_history`` / ``history_records`` (True: a buffer of
         ``ekf_batch_history_bytes`` is allocated; a uint8 tensor on the batch's device: that buffer)."""
@@ -1039,8 +1001,9 @@ class EKFBatch:
             scale = frame_scale_array(scale, frames)
         if motion is not None:
             motion = motion_array(motion, frames)
+        D = idx.shape[0]
         nbytes = C.c_size_t()
-        self._check(self.lib.ekf_batch_log_workspace_bytes(self.h, idx.shape[0], frames, C.byref(nbytes)))
+        self._check(self.lib.ekf_batch_log_workspace_bytes(self.h, D, frames, C.byref(nbytes)))
         hbytes = C.c_size_t()
         recording = isinstance(record, torch.Tensor) or bool(record)
         if recording:
@@ -1050,53 +1013,29 @@ class EKFBatch:
             # (a device tensor comes from this batch's stream: _estimate_corner_logs)
             poses_t = poses if on_device else torch.from_numpy(poses).to(self.device)
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
-            traj = torch.empty((frames, 7), dtype=torch.float64, device=self.device)
-            if noise is not None or scale is not None or motion is not None or recording:
-                rows_t = torch.from_numpy(noise).to(self.device) if noise is not None else None
-                scale_t = torch.from_numpy(scale).to(self.device) if scale is not None else None
-                motion_t = torch.from_numpy(motion).to(self.device) if motion is not None else None
-                nis_t = torch.empty((frames,), dtype=torch.float64, device=self.device) if nis else None
-                cov_t = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
-                mahal_t = torch.empty((idx.shape[0],), dtype=torch.float64, device=self.device) if mahal else None
-                ptr = (lambda t: t.data_ptr() if t is not None and frames else None)
-                args = (self.h, _iptr(idx), _lptr(fo), _lptr(mf), poses_t.data_ptr() if idx.shape[0] else None,
-                        rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None, ptr(scale_t), ptr(motion_t),
-                        ws.data_ptr(), nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t),
-                        mahal_t.data_ptr() if mahal and idx.shape[0] else None)
-                if recording:
-                    history = record if isinstance(record, torch.Tensor) else \
-                        torch.empty((max(hbytes.value, 256),), dtype=torch.uint8, device=self.device)
-                    self._check(self.lib.ekf_batch_observe_logs_recorded(*args, history.data_ptr(), history.numel()))
-                    self.last_history, self._history_frames = history, mf.copy()
-                else:
-                    self._check(self.lib.ekf_batch_observe_logs_moved(*args))
-                self.stream.synchronize()
-                out = (traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, cov_t.cpu().numpy() if cam_cov else None)
-                if mahal:
-                    return out + (mahal_t.cpu().numpy(),)
-                return out if (nis or cam_cov) else out[0]
-            if not (nis or cam_cov or mahal):
-                self._check(self.lib.ekf_batch_observe_logs(self.h, _iptr(idx), _lptr(fo), _lptr(mf),
-                                                            poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
-                                                            nbytes.value, traj.data_ptr() if frames else None))
-                self.stream.synchronize()
-                return traj.cpu().numpy()
-            nis_t = torch.empty((frames,), dtype=torch.float64, device=self.device) if nis else None
-            cov_t = torch.empty((frames, 10, 10), dtype=torch.float64, device=self.device) if cam_cov else None
-            ptr = (lambda t: t.data_ptr() if t is not None and frames else None)
-            if mahal:
-                mahal_t = torch.empty((idx.shape[0],), dtype=torch.float64, device=self.device)
-                self._check(self.lib.ekf_batch_observe_logs_gated(
-                    self.h, _iptr(idx), _lptr(fo), _lptr(mf), poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
-                    nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t), mahal_t.data_ptr() if idx.shape[0] else None))
-                self.stream.synchronize()
-                return (traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None,
-                        cov_t.cpu().numpy() if cam_cov else None, mahal_t.cpu().numpy())
-            self._check(self.lib.ekf_batch_observe_logs_diag(self.h, _iptr(idx), _lptr(fo), _lptr(mf),
-                                                             poses_t.data_ptr() if idx.shape[0] else None, ws.data_ptr(),
-                                                             nbytes.value, ptr(traj), ptr(nis_t), ptr(cov_t)))
+            new = (lambda want, *shape: torch.empty(shape, dtype=torch.float64, device=self.device) if want else None)
+            up = (lambda a: torch.from_numpy(a).to(self.device) if a is not None else None)
+            rows_t, scale_t, motion_t = up(noise), up(scale), up(motion)
+            traj, nis_t, cov_t, mahal_t = new(True, frames, 7), new(nis, frames), new(cam_cov, frames, 10, 10), new(mahal, D)
+            # one call path: NULL for every input and output that is not given or not asked (what the narrower entry points
+            # of the C ABI forward), per frame only with frames and per detection only with detections
+            ptr = (lambda t, count: t.data_ptr() if t is not None and count else None)
+            args = (self.h, _iptr(idx), _lptr(fo), _lptr(mf), ptr(poses_t, D), ptr(rows_t, D), ptr(scale_t, frames),
+                    ptr(motion_t, frames), ws.data_ptr(), nbytes.value, ptr(traj, frames), ptr(nis_t, frames),
+                    ptr(cov_t, frames), ptr(mahal_t, D))
+            if recording:
+                history = record if isinstance(record, torch.Tensor) else \
+                    torch.empty((max(hbytes.value, 256),), dtype=torch.uint8, device=self.device)
+                self._check(self.lib.ekf_batch_observe_logs_recorded(*args, history.data_ptr(), history.numel()))
+                self.last_history, self._history_frames = history, mf.copy()
+            else:
+                self._check(self.lib.ekf_batch_observe_logs_moved(*args))
             self.stream.synchronize()
-        return (traj.cpu().numpy(), nis_t.cpu().numpy() if nis else None, cov_t.cpu().numpy() if cam_cov else None)
+        host = (lambda t: None if t is None else t.cpu().numpy())
+        out = (host(traj), host(nis_t), host(cov_t))
+        if mahal:
+            return out + (host(mahal_t),)
+        return out if (nis or cam_cov) else out[0]
 
     # -- per-member state ---------------------------------------------------------------------------------------------
     def _num_landmarks_device(self) -> np.ndarray:

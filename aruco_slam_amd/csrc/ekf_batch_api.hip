@@ -220,15 +220,35 @@ BatchReplicaLayout batch_replica_layout(int64_t D, int64_t F, int32_t B, bool ga
     return {log.total, log, log.total + align256((size_t)B * D * 6 * 8)};
 }
 
-// The windows of a call whose indices and offsets are on the device (ws, layout LL): every member's frames
+// One call of the log replay: the arguments of ekf_batch_observe_logs_recorded (record: false from every other entry point;
+// ekf_batch_history_bytes gives the log alone), then what batch_log_validate leaves for the staging and the windows.  A
+// replica call fills what the windows read: log_ws and LL of its tiled log, sh, its noisy poses and the outputs.
+struct BatchLogCall {
+    const int32_t* lm_index;
+    const int64_t *frame_offsets, *member_frames;
+    const double *poses_dev, *rows_dev, *scale_dev, *motion_dev;
+    void* log_ws;
+    size_t log_ws_bytes;
+    double *trajectory_dev, *nis_dev, *cam_cov_dev, *mahal_dev;
+    bool record;
+    void* history_dev;
+    size_t history_bytes;
+    // batch_log_validate: frames and detections of the call, where they go, what the logs ask of the kernels' layout, and of
+    // a recorded (or sized) call where its records go
+    bool with_motion = false;
+    int64_t F = 0, D = 0;
+    BatchLogLayout LL{};
+    BatchShape sh;
+    BatchHistoryPlan plan;
+};
+
+// The windows of a call whose indices and offsets are on the device (c.log_ws, layout c.LL): every member's frames
 // [w, w + window) of its log per launch, state carried in HBM.  LDS is sized for the widest frame and the largest map of
 // the call (a layout choice only: the arithmetic is the same)
-int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, const BatchShape& sh, const double* poses_dev,
-                      double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev,
-                      const double* rows_dev = nullptr, const double* scale_dev = nullptr,
-                      const double* motion_dev = nullptr, const EkfBatchRecord* record = nullptr) {
+int batch_run_windows(ekf_batch* b, const BatchLogCall& c, const EkfBatchRecord* record = nullptr) {
     const int32_t B = b->members;
     const BatchLayout L = batch_layout(b->cfg, B);
+    const char* ws = static_cast<const char*>(c.log_ws);
     EkfBatchWindow a{};
     a.P = b->cov;
     a.ld = b->ld;
@@ -237,36 +257,36 @@ int batch_run_windows(ekf_batch* b, const char* ws, const BatchLogLayout& LL, co
     a.status = reinterpret_cast<int32_t*>(b->ws + L.status);
     a.nlm = reinterpret_cast<int32_t*>(b->ws + L.nlm);
     a.lm_index = reinterpret_cast<const int32_t*>(ws);
-    a.frame_offsets = reinterpret_cast<const int64_t*>(ws + LL.frames);
-    a.member_frames = reinterpret_cast<const int64_t*>(ws + LL.members);
-    a.poses = poses_dev;
-    a.traj = trajectory_dev;
-    a.nis = nis_dev;
-    a.cam_cov = cam_cov_dev;
+    a.frame_offsets = reinterpret_cast<const int64_t*>(ws + c.LL.frames);
+    a.member_frames = reinterpret_cast<const int64_t*>(ws + c.LL.members);
+    a.poses = c.poses_dev;
+    a.traj = c.trajectory_dev;
+    a.nis = c.nis_dev;
+    a.cam_cov = c.cam_cov_dev;
     a.quat_mode = b->cfg.quat_mode;
-    a.gate = batch_gated(b) ? reinterpret_cast<const double*>(ws + LL.gate) : nullptr;
-    a.mahal = mahal_dev;
-    a.row_noise = rows_dev;      // (per-detection noise: data of the call, no workspace of its own)
+    a.gate = batch_gated(b) ? reinterpret_cast<const double*>(ws + c.LL.gate) : nullptr;
+    a.mahal = c.mahal_dev;
+    a.row_noise = c.rows_dev;      // (per-detection noise: data of the call, no workspace of its own)
     a.pending = batch_scaled(b->cfg) ? reinterpret_cast<double*>(b->ws + L.pending) : nullptr;
-    a.scale = scale_dev;         // (per-frame scales: data of the call; checked by the caller: the flag is set)
-    a.motion = motion_dev;       // (per-frame camera motions: data of the call, likewise)
+    a.scale = c.scale_dev;        // (per-frame scales: data of the call; checked by the caller: the flag is set)
+    a.motion = c.motion_dev;      // (per-frame camera motions: data of the call, likewise)
     // (no member frozen: null, and every launcher runs the instance it ran before the flag existed)
     a.frozen = batch_any_frozen(b) ? reinterpret_cast<const int32_t*>(b->ws + L.frozen) : nullptr;
     const int rd = batch_rd(b->cfg);
-    a.kmax = std::max(rd, rd * sh.widest);
-    a.lda = (int32_t)round_up(batch_lmd(b->cfg) * sh.n_max + EKF_CAM + 1, 4);
+    a.kmax = std::max(rd, rd * c.sh.widest);
+    a.lda = (int32_t)round_up(batch_lmd(b->cfg) * c.sh.n_max + EKF_CAM + 1, 4);
     const bool rot = b->cfg.model == EKF_MODEL_ROTATIONS;
     // a frame of m detections costs about ceil(m / block) sweeps of P in ekf_batch_wide.hip (block = 16 / 8 detections), so
     // the window shrinks with the call's widest frame and every launch stays about as long.  Without the wide flag no frame
     // is wider than one block: 64 frames
     const int block = rot ? EKF_BATCH_ROT_MAX_VISIBLE : EKF_BATCH_MAX_VISIBLE;
-    const int window = std::max(1, kBatchWindow / ((std::max(sh.widest, 1) + block - 1) / block));
+    const int window = std::max(1, kBatchWindow / ((std::max(c.sh.widest, 1) + block - 1) / block));
     a.window_frames = window;
     // large maps or wide frames: every call runs ekf_batch_wide.hip, whatever the map size and the frame widths (A / W in
     // the workspace)
     const bool hbm = batch_large(b->cfg) || batch_wide(b->cfg);
     EkfBatchLargeWindow g{a, reinterpret_cast<double*>(b->ws + L.w), batch_w_stride(b->cfg)};
-    for (int64_t w = 0; w < sh.frames_max; w += window) {
+    for (int64_t w = 0; w < c.sh.frames_max; w += window) {
         a.window_first = (int32_t)w;
         g.w.window_first = (int32_t)w;
         if (record)      // (a recorded call: EKF, the one-column kernel, no frozen member -- checked by the caller)
@@ -293,65 +313,65 @@ int check_corner_noise(const double* sigma_px, int64_t rows, double marker_size,
 }
 
 // The replica calls: the log is checked for every member, its indices and offsets are tiled B times into ws, `launch` writes
-// the B D poses the members consume into ws, and the windows run on them.  `input_dev`: the log's poses or corners;
-// `check_noise_args`: the call's own noise arguments (host side, before anything is enqueued).
+// the B D poses the members consume into ws, and the windows run on them.  `c`: the log (lm_index, frame_offsets), the
+// workspace and the outputs; `input_dev`: the log's poses or corners; `check_noise_args`: the call's own noise arguments (host
+// side, before anything is enqueued).
 template <typename Check, typename Launch>
-int batch_observe_replicas(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, int64_t frames,
-                           const void* input_dev, uint32_t first_replica, void* ws, size_t ws_bytes, double* trajectory_dev,
-                           double* nis_dev, double* cam_cov_dev, double* mahal_dev, Check check_noise_args, Launch launch) {
+int batch_observe_replicas(ekf_batch* b, BatchLogCall c, int64_t frames, const void* input_dev, uint32_t first_replica,
+                           Check check_noise_args, Launch launch) {
     int rc = batch_ready(b);
     if (rc) return rc;
     // ---- validation on the host: nothing is enqueued before the log has passed for every member
     const int32_t B = b->members;
     if (frames < 0) return fail(EKF_ERR_INVALID, "frames must be >= 0");
-    if (!frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
-    if ((rc = check_offsets(frame_offsets, frames, "frame_offsets"))) return rc;
-    const int64_t D = frame_offsets[frames];
-    if (D > 0 && (!lm_index || !input_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
+    if (!c.frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
+    if ((rc = check_offsets(c.frame_offsets, frames, "frame_offsets"))) return rc;
+    const int64_t D = c.frame_offsets[frames];
+    if (D > 0 && (!c.lm_index || !input_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
     if ((rc = check_noise_args(B))) return rc;
     if ((uint64_t)first_replica + (uint64_t)B > (1ull << 32))
         return fail(EKF_ERR_INVALID, "first_replica + members must not exceed 2^32");
     const BatchReplicaLayout RL = batch_replica_layout(D, frames, B, batch_gated(b));
-    if ((rc = check_device_buffers({ws}, ws_bytes, RL.total, "ekf_batch_replica_workspace_bytes"))) return rc;
+    if ((rc = check_device_buffers({c.log_ws}, c.log_ws_bytes, RL.total, "ekf_batch_replica_workspace_bytes"))) return rc;
     if ((rc = batch_refresh(b))) return rc;
-    BatchShape sh;
     LogCheck lc;
     for (int32_t m = 0; m < B; ++m) {
         if (m > 0 && b->nlm[m] == b->nlm[m - 1] && b->frozen[m] == b->frozen[m - 1]) {      // (the same log on the same landmark count and flag: the same verdict)
-            sh.add(lc, frames);
+            c.sh.add(lc, frames);
             continue;
         }
-        if (b->frozen[m] && (rc = check_frozen_log(lm_index, frame_offsets, frames, b->nlm[m], "the log (member " + std::to_string(m) + ")")))
+        if (b->frozen[m] && (rc = check_frozen_log(c.lm_index, c.frame_offsets, frames, b->nlm[m], "the log (member " + std::to_string(m) + ")")))
             return rc;
-        rc = check_log(lm_index, frame_offsets, frames, b->nlm[m], b->cfg, "the log (member " + std::to_string(m) + ")", &lc);
+        rc = check_log(c.lm_index, c.frame_offsets, frames, b->nlm[m], b->cfg, "the log (member " + std::to_string(m) + ")", &lc);
         if (rc) return rc;
-        sh.add(lc, frames);
+        c.sh.add(lc, frames);
     }
     if (frames == 0) return EKF_OK;
 
     // ---- staging: the log's indices and offsets tiled member after member (member b: detections b D .., frames b F ..)
     const int64_t Ft = (int64_t)B * frames, Dt = (int64_t)B * D;
-    const BatchLogLayout& LL = RL.log;
+    const BatchLogLayout& LL = c.LL = RL.log;
     if ((rc = b->pin.reserve(LL.total))) return rc;
     int32_t* idx = b->pin.at<int32_t>(0);
     int64_t* fo = b->pin.at<int64_t>(LL.frames);
     int64_t* mf = b->pin.at<int64_t>(LL.members);
     for (int32_t m = 0; m < B; ++m) {
-        if (D > 0) std::memcpy(idx + (size_t)m * D, lm_index, (size_t)D * 4);
-        for (int64_t t = 0; t < frames; ++t) fo[(size_t)m * frames + t] = (int64_t)m * D + frame_offsets[t];
+        if (D > 0) std::memcpy(idx + (size_t)m * D, c.lm_index, (size_t)D * 4);
+        for (int64_t t = 0; t < frames; ++t) fo[(size_t)m * frames + t] = (int64_t)m * D + c.frame_offsets[t];
         mf[m] = (int64_t)m * frames;
     }
     fo[Ft] = Dt;
     mf[B] = Ft;
     if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
-    char* w = static_cast<char*>(ws);
+    char* w = static_cast<char*>(c.log_ws);
     HIP_TRY(hipMemcpyAsync(w, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
     double* noisy = reinterpret_cast<double*>(w + RL.poses);
     if (D > 0) {
         launch(D, noisy);
         HIP_TRY(hipGetLastError());
     }
-    return batch_run_windows(b, w, LL, sh, noisy, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev);
+    c.poses_dev = noisy;
+    return batch_run_windows(b, c);
 }
 
 // ---- batch smoothing (include/ekf_slam_hip.h, "Batch smoothing": the refusals) ------------------------------------------
@@ -396,6 +416,105 @@ int batch_history_fetch(ekf_batch* b) {
     return EKF_OK;
 }
 
+// ---- validation on the host: nothing is enqueued before every log has passed.  A recorded call also plans its history and
+// begins it.  sizing (ekf_batch_history_bytes): the logs alone, as far as the plan -- no poses, no workspace, and what
+// batch_recordable refuses is left to the recorded call.
+int batch_log_validate(ekf_batch* b, BatchLogCall& c, bool sizing) {
+    int rc;
+    if (!sizing) {
+        if (c.record && (rc = batch_smoothing_supported(b))) return rc;
+        if (c.motion_dev && (b->cfg.flags & EKF_FLAG_MOTION) == 0)
+            return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_MOTION");
+        if (c.scale_dev && !batch_scaled(b->cfg)) return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_FRAME_SCALE");
+        c.with_motion = c.motion_dev != nullptr;
+    }
+    const int32_t B = b->members;
+    if (!c.member_frames || !c.frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
+    if ((rc = check_offsets(c.member_frames, B, "member_frames"))) return rc;
+    c.F = c.member_frames[B];
+    if ((rc = check_offsets(c.frame_offsets, c.F, "frame_offsets"))) return rc;
+    c.D = c.frame_offsets[c.F];
+    if (c.D > 0 && (!c.lm_index || (!sizing && !c.poses_dev))) return fail(EKF_ERR_INVALID, "NULL detections");
+    c.LL = batch_log_layout(c.D, c.F, B, batch_gated(b));
+    if (!sizing && (rc = check_device_buffers({c.log_ws}, c.log_ws_bytes, c.LL.total, "ekf_batch_log_workspace_bytes"))) return rc;
+    if ((rc = batch_refresh(b))) return rc;      // (landmark counts as the previous call left them)
+    const bool planned = sizing || c.record;
+    LogCheck lc;
+    for (int32_t m = 0; m < B; ++m) {
+        const int64_t* offsets = c.frame_offsets + c.member_frames[m];
+        const int64_t frames = c.member_frames[m + 1] - c.member_frames[m];
+        const std::string log = "member " + std::to_string(m) + "'s log";
+        if (b->frozen[m] && (rc = check_frozen_log(c.lm_index, offsets, frames, b->nlm[m], log))) return rc;
+        if ((rc = check_log(c.lm_index, offsets, frames, b->nlm[m], b->cfg, log, &lc))) return rc;
+        c.sh.add(lc, frames);
+        if (c.record && (rc = batch_recordable(b, m, frames, lc))) return rc;
+        if (planned) batch_history_add_member(c.plan, offsets, frames, batch_lmd(b->cfg), b->nlm[m], lc, c.with_motion);
+    }
+    if (planned) batch_history_finish(c.plan, c.with_motion);
+    if (!c.record) return EKF_OK;
+    if (c.history_dev && c.history_bytes < c.plan.total)
+        return fail(EKF_ERR_CAPACITY, "history smaller than ekf_batch_history_bytes");
+    if ((rc = check_device_buffers({c.history_dev}, c.history_bytes, c.plan.total, "ekf_batch_history_bytes"))) return rc;
+    b->hist = ekf_batch::History{};
+    b->hist.valid = true;
+    b->hist.with_motion = c.with_motion;
+    b->hist.buf = c.history_dev;
+    b->hist.member_frames.assign(c.member_frames, c.member_frames + B + 1);
+    b->hist.plan = std::move(c.plan);
+    return EKF_OK;
+}
+
+// The log call.  record: the RECORDED window kernels, which pack the member into the frame's slot of the history behind every
+// frame that changed it (recording only reads the members: every output has the bits of the plain call).
+int batch_observe_logs(ekf_batch* b, BatchLogCall c) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if ((rc = batch_log_validate(b, c, false))) return rc;
+    const int32_t B = b->members;
+    const int64_t F = c.F, D = c.D;
+    if (F == 0) return EKF_OK;
+
+    // ---- staging: one copy of indices and offsets (the stream is idle: batch_refresh synchronised it); a recorded call: the
+    // headers' and slots' offsets behind them, into the history's own pieces
+    const BatchLogLayout& LL = c.LL;
+    const BatchHistoryPlan& hp = b->hist.plan;
+    const size_t pin_head = LL.total, pin_slot = pin_head + align256((size_t)B * 8);
+    if ((rc = b->pin.reserve(c.record ? pin_slot + align256((size_t)F * 8) : LL.total))) return rc;
+    if (D > 0) std::memcpy(b->pin.get(), c.lm_index, (size_t)D * 4);
+    std::memcpy(b->pin.get() + LL.frames, c.frame_offsets, (size_t)(F + 1) * 8);
+    std::memcpy(b->pin.get() + LL.members, c.member_frames, (size_t)(B + 1) * 8);
+    if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
+    HIP_TRY(hipMemcpyAsync(c.log_ws, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
+    if (!c.record) return batch_run_windows(b, c);
+    char* hist = static_cast<char*>(c.history_dev);
+    std::memcpy(b->pin.get() + pin_head, hp.head.data(), (size_t)B * 8);
+    std::memcpy(b->pin.get() + pin_slot, hp.slot.data(), (size_t)F * 8);
+    HIP_TRY(hipMemcpyAsync(hist + hp.head_at, b->pin.get() + pin_head, (size_t)B * 8, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(hist + hp.slot_at, b->pin.get() + pin_slot, (size_t)F * 8, hipMemcpyHostToDevice, b->stream));
+    if (c.motion_dev)      // (the tables need the motions on the host: they come back with the flags, from the history)
+        HIP_TRY(hipMemcpyAsync(hist + hp.motion_at, c.motion_dev, (size_t)F * 48, hipMemcpyDeviceToDevice, b->stream));
+    const EkfBatchRecord r{reinterpret_cast<double*>(hist), reinterpret_cast<const int64_t*>(hist + hp.head_at),
+                           reinterpret_cast<const int64_t*>(hist + hp.slot_at), reinterpret_cast<int32_t*>(hist + hp.flag_at),
+                           reinterpret_cast<double*>(hist + hp.seff_at)};
+    rc = batch_run_windows(b, c, &r);
+    if (rc) b->hist.valid = false;      // (a recorded call that failed leaves no history)
+    return rc;
+}
+
+// The front of both smoothing calls, the refusals in the header's order: the batch, the recording, the history given against
+// the recorded one, `flags` (the reserved word of the covariance call; the plain call has none: 0), then the device's words.
+int batch_smooth_open(ekf_batch* b, const void* history_dev, size_t history_bytes, int32_t flags) {
+    int rc = batch_ready(b);
+    if (rc) return rc;
+    if ((rc = batch_smoothing_supported(b))) return rc;
+    if (!b->hist.valid)
+        return fail(EKF_ERR_STATE, "no recorded call (ekf_batch_observe_logs_recorded), or a member has been reset, set or pruned since");
+    if (history_dev != b->hist.buf || history_bytes < b->hist.plan.total)
+        return fail(EKF_ERR_STATE, "not the history of this handle's last recorded call");
+    if (flags != 0) return fail(EKF_ERR_INVALID, "flags is reserved (0)");
+    return batch_history_fetch(b);
+}
+
 // smoothing workspace: [status [B] | tables | members]
 struct BatchSmoothLayout {
     size_t tables, members, total;
@@ -406,6 +525,24 @@ BatchSmoothLayout batch_smooth_layout(size_t records, int32_t B) {
     const size_t tables = w.take(std::max<size_t>(records, 1) * sizeof(EkfSmoothRec));
     const size_t members = w.take((size_t)B * sizeof(EkfBatchSmoothMember));
     return {tables, members, w.end};
+}
+
+// the pieces of a smoothing workspace `w`, the tables of the fetched history enqueued into them
+struct BatchSmoothDev {
+    int32_t* status;
+    EkfSmoothRec* tables;
+    EkfBatchSmoothMember* members;
+};
+int batch_smooth_upload(ekf_batch* b, char* w, const BatchSmoothLayout& L, BatchSmoothDev* d) {
+    const BatchSmoothTables& tab = b->hist.tab;
+    *d = {reinterpret_cast<int32_t*>(w), reinterpret_cast<EkfSmoothRec*>(w + L.tables),
+          reinterpret_cast<EkfBatchSmoothMember*>(w + L.members)};
+    if (!tab.tables.empty())
+        HIP_TRY(hipMemcpyAsync(d->tables, tab.tables.data(), tab.tables.size() * sizeof(EkfSmoothRec), hipMemcpyHostToDevice,
+                               b->stream));
+    HIP_TRY(hipMemcpyAsync(d->members, tab.members.data(), (size_t)b->members * sizeof(EkfBatchSmoothMember),
+                           hipMemcpyHostToDevice, b->stream));
+    return EKF_OK;
 }
 
 // covariance workspace: the smoothing workspace, then [cov members | member 0: W Z T P^s | member 1: ...], a member's four
@@ -438,12 +575,6 @@ BatchSmoothCovLayout batch_smooth_cov_layout(const BatchSmoothTables& tab, int32
 }  // namespace
 
 extern "C" {
-
-static int batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, const int64_t* member_frames,
-                              const double* poses_dev, const double* rows_dev, const double* scale_dev,
-                              const double* motion_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev,
-                              double* nis_dev, double* cam_cov_dev, double* mahal_dev, bool record, void* history_dev,
-                              size_t history_bytes);
 
 int ekf_batch_query_sizes(const ekf_config* cfg, int32_t members, int64_t* ld, size_t* cov_bytes, size_t* state_bytes,
                           size_t* workspace_bytes) {
@@ -692,8 +823,9 @@ int ekf_batch_observe_logs_moved(ekf_batch* b, const int32_t* lm_index, const in
                                  const int64_t* member_frames, const double* poses_dev, const double* rows_dev,
                                  const double* scale_dev, const double* motion_dev, void* log_ws, size_t log_ws_bytes,
                                  double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev) {
-    return batch_observe_logs(b, lm_index, frame_offsets, member_frames, poses_dev, rows_dev, scale_dev, motion_dev, log_ws,
-                              log_ws_bytes, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, false, nullptr, 0);
+    return batch_observe_logs(b, BatchLogCall{lm_index, frame_offsets, member_frames, poses_dev, rows_dev, scale_dev, motion_dev,
+                                              log_ws, log_ws_bytes, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, false,
+                                              nullptr, 0});
 }
 
 int ekf_batch_observe_logs_recorded(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets,
@@ -701,91 +833,9 @@ int ekf_batch_observe_logs_recorded(ekf_batch* b, const int32_t* lm_index, const
                                     const double* scale_dev, const double* motion_dev, void* log_ws, size_t log_ws_bytes,
                                     double* trajectory_dev, double* nis_dev, double* cam_cov_dev, double* mahal_dev,
                                     void* history_dev, size_t history_bytes) {
-    return batch_observe_logs(b, lm_index, frame_offsets, member_frames, poses_dev, rows_dev, scale_dev, motion_dev, log_ws,
-                              log_ws_bytes, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, true, history_dev, history_bytes);
-}
-
-// The log call.  record: the RECORDED window kernels, which pack the member into the frame's slot of the history behind every
-// frame that changed it (recording only reads the members: every output has the bits of the plain call).
-static int batch_observe_logs(ekf_batch* b, const int32_t* lm_index, const int64_t* frame_offsets, const int64_t* member_frames,
-                              const double* poses_dev, const double* rows_dev, const double* scale_dev,
-                              const double* motion_dev, void* log_ws, size_t log_ws_bytes, double* trajectory_dev,
-                              double* nis_dev, double* cam_cov_dev, double* mahal_dev, bool record, void* history_dev,
-                              size_t history_bytes) {
-    int rc = batch_ready(b);
-    if (rc) return rc;
-    if (record && (rc = batch_smoothing_supported(b))) return rc;
-    if (motion_dev && (b->cfg.flags & EKF_FLAG_MOTION) == 0)
-        return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_MOTION");
-    if (scale_dev && !batch_scaled(b->cfg)) return fail(EKF_ERR_STATE, "the batch was created without EKF_FLAG_FRAME_SCALE");
-    // ---- validation on the host: nothing is enqueued before every log has passed
-    const int32_t B = b->members;
-    if (!member_frames || !frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
-    if ((rc = check_offsets(member_frames, B, "member_frames"))) return rc;
-    const int64_t F = member_frames[B];
-    if ((rc = check_offsets(frame_offsets, F, "frame_offsets"))) return rc;
-    const int64_t D = frame_offsets[F];
-    if (D > 0 && (!lm_index || !poses_dev)) return fail(EKF_ERR_INVALID, "NULL detections");
-    const BatchLogLayout LL = batch_log_layout(D, F, B, batch_gated(b));
-    if ((rc = check_device_buffers({log_ws}, log_ws_bytes, LL.total, "ekf_batch_log_workspace_bytes"))) return rc;
-    if ((rc = batch_refresh(b))) return rc;      // (landmark counts as the previous call left them)
-    BatchShape sh;
-    LogCheck lc;
-    BatchHistoryPlan plan;
-    for (int32_t m = 0; m < B; ++m) {
-        const int64_t f0 = member_frames[m], frames = member_frames[m + 1] - f0;
-        if (b->frozen[m] && (rc = check_frozen_log(lm_index, frame_offsets + f0, frames, b->nlm[m], "member " + std::to_string(m) + "'s log")))
-            return rc;
-        rc = check_log(lm_index, frame_offsets + f0, frames, b->nlm[m], b->cfg, "member " + std::to_string(m) + "'s log", &lc);
-        if (rc) return rc;
-        sh.add(lc, frames);
-        if (record) {
-            if ((rc = batch_recordable(b, m, frames, lc))) return rc;
-            batch_history_add_member(plan, frame_offsets + f0, frames, batch_lmd(b->cfg), b->nlm[m], lc, motion_dev != nullptr);
-        }
-    }
-    if (record) {
-        batch_history_finish(plan, motion_dev != nullptr);
-        if (history_dev && history_bytes < plan.total)
-            return fail(EKF_ERR_CAPACITY, "history smaller than ekf_batch_history_bytes");
-        if ((rc = check_device_buffers({history_dev}, history_bytes, plan.total, "ekf_batch_history_bytes"))) return rc;
-        b->hist = ekf_batch::History{};
-        b->hist.valid = true;
-        b->hist.with_motion = motion_dev != nullptr;
-        b->hist.buf = history_dev;
-        b->hist.member_frames.assign(member_frames, member_frames + B + 1);
-        b->hist.plan = std::move(plan);
-    }
-    if (F == 0) return EKF_OK;
-
-    // ---- staging: one copy of indices and offsets (the stream is idle: batch_refresh synchronised it); a recorded call: the
-    // headers' and slots' offsets behind them, into the history's own pieces
-    const BatchHistoryPlan& hp = b->hist.plan;
-    const size_t pin_head = LL.total, pin_slot = pin_head + align256((size_t)B * 8);
-    if ((rc = b->pin.reserve(record ? pin_slot + align256((size_t)F * 8) : LL.total))) return rc;
-    if (D > 0) std::memcpy(b->pin.get(), lm_index, (size_t)D * 4);
-    std::memcpy(b->pin.get() + LL.frames, frame_offsets, (size_t)(F + 1) * 8);
-    std::memcpy(b->pin.get() + LL.members, member_frames, (size_t)(B + 1) * 8);
-    if (batch_gated(b)) std::memcpy(b->pin.get() + LL.gate, b->gate.data(), (size_t)B * 8);
-    char* ws = static_cast<char*>(log_ws);
-    HIP_TRY(hipMemcpyAsync(ws, b->pin.get(), LL.total, hipMemcpyHostToDevice, b->stream));
-    if (!record)
-        return batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev,
-                                 scale_dev, motion_dev);
-    char* hist = static_cast<char*>(history_dev);
-    std::memcpy(b->pin.get() + pin_head, hp.head.data(), (size_t)B * 8);
-    std::memcpy(b->pin.get() + pin_slot, hp.slot.data(), (size_t)F * 8);
-    HIP_TRY(hipMemcpyAsync(hist + hp.head_at, b->pin.get() + pin_head, (size_t)B * 8, hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(hist + hp.slot_at, b->pin.get() + pin_slot, (size_t)F * 8, hipMemcpyHostToDevice, b->stream));
-    if (motion_dev)      // (the tables need the motions on the host: they come back with the flags, from the history)
-        HIP_TRY(hipMemcpyAsync(hist + hp.motion_at, motion_dev, (size_t)F * 48, hipMemcpyDeviceToDevice, b->stream));
-    const EkfBatchRecord r{reinterpret_cast<double*>(hist), reinterpret_cast<const int64_t*>(hist + hp.head_at),
-                           reinterpret_cast<const int64_t*>(hist + hp.slot_at), reinterpret_cast<int32_t*>(hist + hp.flag_at),
-                           reinterpret_cast<double*>(hist + hp.seff_at)};
-    rc = batch_run_windows(b, ws, LL, sh, poses_dev, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, rows_dev, scale_dev,
-                           motion_dev, &r);
-    if (rc) b->hist.valid = false;      // (a recorded call that failed leaves no history)
-    return rc;
+    return batch_observe_logs(b, BatchLogCall{lm_index, frame_offsets, member_frames, poses_dev, rows_dev, scale_dev, motion_dev,
+                                              log_ws, log_ws_bytes, trajectory_dev, nis_dev, cam_cov_dev, mahal_dev, true,
+                                              history_dev, history_bytes});
 }
 
 // member = -1: every member, [B]; member >= 0: that one, [1].  Both wait for the batch's stream.
@@ -857,8 +907,9 @@ int ekf_batch_observe_replicas_gated(ekf_batch* b, const int32_t* lm_index, cons
                                      void* ws, size_t ws_bytes, double* trajectory_dev, double* nis_dev,
                                      double* cam_cov_dev, double* mahal_dev) {
     return batch_observe_replicas(
-        b, lm_index, frame_offsets, frames, poses_dev, first_replica, ws, ws_bytes, trajectory_dev, nis_dev, cam_cov_dev,
-        mahal_dev,
+        b, BatchLogCall{lm_index, frame_offsets, nullptr, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, trajectory_dev,
+                        nis_dev, cam_cov_dev, mahal_dev},
+        frames, poses_dev, first_replica,
         [&](int32_t B) {
             if (!sigma) return fail(EKF_ERR_INVALID, "sigma is NULL");
             return check_sigma(sigma, B);
@@ -895,8 +946,9 @@ int ekf_batch_observe_corner_replicas(ekf_batch* b, const int32_t* lm_index, con
                                       uint8_t* flipped_dev) {
     EkfCamera cam;
     return batch_observe_replicas(
-        b, lm_index, frame_offsets, frames, corners_dev, first_replica, ws, ws_bytes, trajectory_dev, nis_dev, cam_cov_dev,
-        mahal_dev,
+        b, BatchLogCall{lm_index, frame_offsets, nullptr, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, trajectory_dev,
+                        nis_dev, cam_cov_dev, mahal_dev},
+        frames, corners_dev, first_replica,
         [&](int32_t B) { return check_corner_noise(sigma_px, B, marker_size, camera_matrix, dist_coeffs, n_dist, &cam); },
         [&](int64_t D, double* noisy) {
             ekf_launch_corner_replicas(corners_dev, D, sigma_px, b->members, seed, first_replica, marker_size, cam, noisy,
@@ -975,25 +1027,10 @@ int ekf_batch_history_bytes(ekf_batch* b, const int32_t* lm_index, const int64_t
     int rc = batch_ready(b);
     if (rc) return rc;
     if (!bytes) return fail(EKF_ERR_INVALID, "bytes is NULL");
-    const int32_t B = b->members;
-    if (!member_frames || !frame_offsets) return fail(EKF_ERR_INVALID, "offsets are NULL");
-    if ((rc = check_offsets(member_frames, B, "member_frames"))) return rc;
-    const int64_t F = member_frames[B];
-    if ((rc = check_offsets(frame_offsets, F, "frame_offsets"))) return rc;
-    if (frame_offsets[F] > 0 && !lm_index) return fail(EKF_ERR_INVALID, "NULL detections");
-    if ((rc = batch_refresh(b))) return rc;
-    BatchHistoryPlan plan;
-    LogCheck lc;
-    for (int32_t m = 0; m < B; ++m) {
-        const int64_t f0 = member_frames[m], frames = member_frames[m + 1] - f0;
-        if (b->frozen[m] && (rc = check_frozen_log(lm_index, frame_offsets + f0, frames, b->nlm[m], "member " + std::to_string(m) + "'s log")))
-            return rc;
-        rc = check_log(lm_index, frame_offsets + f0, frames, b->nlm[m], b->cfg, "member " + std::to_string(m) + "'s log", &lc);
-        if (rc) return rc;
-        batch_history_add_member(plan, frame_offsets + f0, frames, batch_lmd(b->cfg), b->nlm[m], lc, with_motion != 0);
-    }
-    batch_history_finish(plan, with_motion != 0);
-    *bytes = plan.total;
+    BatchLogCall c{lm_index, frame_offsets, member_frames};
+    c.with_motion = with_motion != 0;
+    if ((rc = batch_log_validate(b, c, true))) return rc;
+    *bytes = c.plan.total;
     return EKF_OK;
 }
 
@@ -1096,14 +1133,8 @@ int ekf_batch_smooth_workspace_bytes(ekf_batch* b, size_t* bytes) {
 
 int ekf_batch_smooth_history(ekf_batch* b, const void* history_dev, size_t history_bytes, void* ws, size_t ws_bytes,
                              double* smoothed_dev, int32_t* status_out) {
-    int rc = batch_ready(b);
+    int rc = batch_smooth_open(b, history_dev, history_bytes, 0);
     if (rc) return rc;
-    if ((rc = batch_smoothing_supported(b))) return rc;
-    if (!b->hist.valid)
-        return fail(EKF_ERR_STATE, "no recorded call (ekf_batch_observe_logs_recorded), or a member has been reset, set or pruned since");
-    if (history_dev != b->hist.buf || history_bytes < b->hist.plan.total)
-        return fail(EKF_ERR_STATE, "not the history of this handle's last recorded call");
-    if ((rc = batch_history_fetch(b))) return rc;
     const int32_t B = b->members;
     const BatchSmoothTables& tab = b->hist.tab;
     if (status_out) std::memset(status_out, 0, (size_t)B * 4);
@@ -1111,21 +1142,14 @@ int ekf_batch_smooth_history(ekf_batch* b, const void* history_dev, size_t histo
     if (!smoothed_dev) return fail(EKF_ERR_INVALID, "smoothed_dev is NULL");
     const BatchSmoothLayout L = batch_smooth_layout(tab.tables.size(), B);
     if ((rc = check_device_buffers({ws}, ws_bytes, L.total, "ekf_batch_smooth_workspace_bytes"))) return rc;
-    char* w = static_cast<char*>(ws);
-    int32_t* status = reinterpret_cast<int32_t*>(w);
-    EkfSmoothRec* tables_dev = reinterpret_cast<EkfSmoothRec*>(w + L.tables);
-    EkfBatchSmoothMember* members_dev = reinterpret_cast<EkfBatchSmoothMember*>(w + L.members);
-    if (!tab.tables.empty())
-        HIP_TRY(hipMemcpyAsync(tables_dev, tab.tables.data(), tab.tables.size() * sizeof(EkfSmoothRec), hipMemcpyHostToDevice,
-                               b->stream));
-    HIP_TRY(hipMemcpyAsync(members_dev, tab.members.data(), (size_t)B * sizeof(EkfBatchSmoothMember), hipMemcpyHostToDevice,
-                           b->stream));
-    HIP_TRY(ekf_launch_batch_smooth(static_cast<const double*>(history_dev), tables_dev, members_dev, B, tab.nmax, smoothed_dev,
-                                    status, b->stream));
+    BatchSmoothDev d;
+    if ((rc = batch_smooth_upload(b, static_cast<char*>(ws), L, &d))) return rc;
+    HIP_TRY(ekf_launch_batch_smooth(static_cast<const double*>(history_dev), d.tables, d.members, B, tab.nmax, smoothed_dev,
+                                    d.status, b->stream));
     HIP_TRY(hipGetLastError());
     // every member has its own status word: a P_p that is not positive definite is reported there and nowhere else
     HIP_TRY(hipStreamSynchronize(b->stream));
-    if (status_out) HIP_TRY(hipMemcpy(status_out, status, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (status_out) HIP_TRY(hipMemcpy(status_out, d.status, (size_t)B * 4, hipMemcpyDeviceToHost));
     return EKF_OK;
 }
 
@@ -1142,15 +1166,8 @@ int ekf_batch_smooth_cov_workspace_bytes(ekf_batch* b, size_t* bytes) {
 int ekf_batch_smooth_history_cov(ekf_batch* b, const void* history_dev, size_t history_bytes, void* ws, size_t ws_bytes,
                                  int32_t flags, double* smoothed_dev, double* cam_cov_dev, double* filt_cam_cov_dev,
                                  double* first_cov_dev, int32_t first_ld, int32_t* status_out) {
-    int rc = batch_ready(b);
+    int rc = batch_smooth_open(b, history_dev, history_bytes, flags);
     if (rc) return rc;
-    if ((rc = batch_smoothing_supported(b))) return rc;
-    if (!b->hist.valid)
-        return fail(EKF_ERR_STATE, "no recorded call (ekf_batch_observe_logs_recorded), or a member has been reset, set or pruned since");
-    if (history_dev != b->hist.buf || history_bytes < b->hist.plan.total)
-        return fail(EKF_ERR_STATE, "not the history of this handle's last recorded call");
-    if (flags != 0) return fail(EKF_ERR_INVALID, "flags is reserved (0)");
-    if ((rc = batch_history_fetch(b))) return rc;
     const int32_t B = b->members;
     const BatchSmoothTables& tab = b->hist.tab;
     if (first_cov_dev)
@@ -1164,14 +1181,14 @@ int ekf_batch_smooth_history_cov(ekf_batch* b, const void* history_dev, size_t h
     if (!smoothed_dev || !cam_cov_dev) return fail(EKF_ERR_INVALID, "smoothed_dev or cam_cov_dev is NULL");
     if ((rc = check_device_buffers({ws}, ws_bytes, L.total, "ekf_batch_smooth_cov_workspace_bytes"))) return rc;
     char* w = static_cast<char*>(ws);
+    BatchSmoothDev d;
+    if ((rc = batch_smooth_upload(b, w, L.base, &d))) return rc;
     EkfBatchSmoothCov a{};
     a.history = static_cast<const double*>(history_dev);
-    a.status = reinterpret_cast<int32_t*>(w);
-    EkfSmoothRec* tables_dev = reinterpret_cast<EkfSmoothRec*>(w + L.base.tables);
-    EkfBatchSmoothMember* members_dev = reinterpret_cast<EkfBatchSmoothMember*>(w + L.base.members);
+    a.status = d.status;
     EkfBatchSmoothCovMember* cov_members_dev = reinterpret_cast<EkfBatchSmoothCovMember*>(w + L.cov_members);
-    a.tables = tables_dev;
-    a.members = members_dev;
+    a.tables = d.tables;
+    a.members = d.members;
     a.cov_members = cov_members_dev;
     a.regions = reinterpret_cast<double*>(w + L.regions);
     a.smoothed = smoothed_dev;
@@ -1180,11 +1197,6 @@ int ekf_batch_smooth_history_cov(ekf_batch* b, const void* history_dev, size_t h
     a.first_cov = first_cov_dev;
     a.first_ld = first_ld;
     a.nmax = tab.nmax;
-    if (!tab.tables.empty())
-        HIP_TRY(hipMemcpyAsync(tables_dev, tab.tables.data(), tab.tables.size() * sizeof(EkfSmoothRec), hipMemcpyHostToDevice,
-                               b->stream));
-    HIP_TRY(hipMemcpyAsync(members_dev, tab.members.data(), (size_t)B * sizeof(EkfBatchSmoothMember), hipMemcpyHostToDevice,
-                           b->stream));
     HIP_TRY(hipMemcpyAsync(cov_members_dev, L.members.data(), (size_t)B * sizeof(EkfBatchSmoothCovMember), hipMemcpyHostToDevice,
                            b->stream));
     // (L outlives the copies: the call waits for the stream below)

@@ -284,6 +284,14 @@ def _dptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _iptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _lptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
 def estimate_poses(corners, marker_size: float, camera_matrix, dist_coeffs=None, device="cuda:0") -> np.ndarray:
     """Batched IPPE-square pose of every detected marker on the GPU (ekf_estimate_poses; replaces the per-marker
     cv2.solvePnP loop of base_filter.py:92-171).  corners: array-like [m,4,2] (or cv2's list of [1,4,2]) of pixel
@@ -553,9 +561,8 @@ class HipEkf:
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.device)
-            self._check(self.lib.ekf_remove_markers(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.shape[0],
-                                                    cov_t.data_ptr(), self.ld, state_t.data_ptr(), ws.data_ptr(),
-                                                    nbytes.value))
+            self._check(self.lib.ekf_remove_markers(self.h, _iptr(idx), idx.shape[0], cov_t.data_ptr(), self.ld,
+                                                    state_t.data_ptr(), ws.data_ptr(), nbytes.value))
             if idx.shape[0] == 0:
                 return
             # (old and new tensors may come from another stream: the allocator keeps them until this one has passed the call)
@@ -600,8 +607,7 @@ class HipEkf:
                 self._check(self.lib.ekf_move(self.h, _dptr(motion)))
                 motion = None
         if exempt is None and not mahal and rows is None and scale is None:
-            self._check(self.lib.ekf_observe(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z),
-                                             idx.shape[0]))
+            self._check(self.lib.ekf_observe(self.h, _iptr(idx), _dptr(z), idx.shape[0]))
             return None
         ex = None
         if exempt is not None:
@@ -609,19 +615,18 @@ class HipEkf:
             assert ex.shape[0] == idx.shape[0]
         d2 = np.empty(idx.shape[0]) if mahal else None
         if scale is not None:
-            self._check(self.lib.ekf_observe_moved(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z),
+            self._check(self.lib.ekf_observe_moved(self.h, _iptr(idx), _dptr(z),
                                                    _dptr(rows) if rows is not None else None, idx.shape[0],
                                                    ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None,
                                                    _dptr(d2) if mahal else None, None, scale,
                                                    _dptr(motion) if motion is not None else None))
             return d2
         if rows is not None:
-            self._check(self.lib.ekf_observe_rows(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z), _dptr(rows),
-                                                  idx.shape[0],
+            self._check(self.lib.ekf_observe_rows(self.h, _iptr(idx), _dptr(z), _dptr(rows), idx.shape[0],
                                                   ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None,
                                                   _dptr(d2) if mahal else None, None))
             return d2
-        self._check(self.lib.ekf_observe_gated(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z), idx.shape[0],
+        self._check(self.lib.ekf_observe_gated(self.h, _iptr(idx), _dptr(z), idx.shape[0],
                                                ex.ctypes.data_as(C.POINTER(C.c_uint8)) if ex is not None else None,
                                                _dptr(d2) if mahal else None, None))
         return d2
@@ -630,48 +635,25 @@ class HipEkf:
         """idx_t int32 [F,m], z_t float64 [F,m,3] device tensors (resident
         detections); traj_t float64 [F,7] or None; rows: float64 device tensor [F,m,rd] of row variances (the caller's
         contract: finite, > 0; a filter built with ``row_noise=True``) or None; scale: [F] numbers >= 0 on the host (a
-        filter built with ``frame_scale=True``; ekf_observe_sequence_device_scaled) or None; motion: [F, 6] camera motions
-        on the host (a filter built with ``motion=True``; ekf_observe_sequence_device_moved: serial order) or None."""
+        filter built with ``frame_scale=True``) or None; motion: [F, 6] camera motions on the host (a filter built with
+        ``motion=True``: serial order) or None.  Every call is ekf_observe_sequence_device_moved, NULL for what is None."""
         frames, m = idx_t.shape
         assert idx_t.is_cuda and z_t.is_cuda and idx_t.is_contiguous() and z_t.is_contiguous()
         assert tuple(z_t.shape) == (frames, m, self.rows_per_detection)
         self._last_m = m
         if motion is not None:
             motion = self._motion(motion, frames)
-            if scale is not None:
-                scale = self._scale(scale, frames)
-            if rows is not None:
-                if not self.can_row_noise:
-                    raise ValueError("this filter was built without per-detection noise: construct it with row_noise=True")
-                assert rows.is_cuda and rows.dtype == self._torch.float64 and rows.is_contiguous()
-                assert tuple(rows.shape) == tuple(z_t.shape)
-            self._check(self.lib.ekf_observe_sequence_device_moved(
-                self.h, idx_t.data_ptr(), z_t.data_ptr(), rows.data_ptr() if rows is not None else None,
-                _dptr(scale) if scale is not None else None, _dptr(motion), m, frames,
-                traj_t.data_ptr() if traj_t is not None else None))
-            return
         if scale is not None:
             scale = self._scale(scale, frames)
-            if rows is not None:
-                if not self.can_row_noise:
-                    raise ValueError("this filter was built without per-detection noise: construct it with row_noise=True")
-                assert rows.is_cuda and rows.dtype == self._torch.float64 and rows.is_contiguous()
-                assert tuple(rows.shape) == tuple(z_t.shape)
-            self._check(self.lib.ekf_observe_sequence_device_scaled(
-                self.h, idx_t.data_ptr(), z_t.data_ptr(), rows.data_ptr() if rows is not None else None, _dptr(scale), m,
-                frames, traj_t.data_ptr() if traj_t is not None else None))
-            return
         if rows is not None:
             if not self.can_row_noise:
                 raise ValueError("this filter was built without per-detection noise: construct it with row_noise=True")
             assert rows.is_cuda and rows.dtype == self._torch.float64 and rows.is_contiguous()
             assert tuple(rows.shape) == tuple(z_t.shape)
-            self._check(self.lib.ekf_observe_sequence_device_rows(
-                self.h, idx_t.data_ptr(), z_t.data_ptr(), rows.data_ptr(), m, frames,
-                traj_t.data_ptr() if traj_t is not None else None))
-            return
-        self._check(self.lib.ekf_observe_sequence_device(
-            self.h, idx_t.data_ptr(), z_t.data_ptr(), m, frames,
+        # (the narrower entry points are this one with NULL for what they lack)
+        self._check(self.lib.ekf_observe_sequence_device_moved(
+            self.h, idx_t.data_ptr(), z_t.data_ptr(), rows.data_ptr() if rows is not None else None,
+            _dptr(scale) if scale is not None else None, _dptr(motion) if motion is not None else None, m, frames,
             traj_t.data_ptr() if traj_t is not None else None))
 
     def observe_log(self, lm_index, offsets, poses, traj=None, mahal=None, rows=None, scale=None, motion=None, history=None):
@@ -731,8 +713,7 @@ class HipEkf:
             if mahal is not None:
                 mahal.record_stream(self.stream)
             rows_t = torch.from_numpy(rows).to(self.device, non_blocking=False) if rows is not None else None
-            args = (self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), frames,
-                    poses_t.data_ptr() if idx.shape[0] else None,
+            args = (self.h, _iptr(idx), _lptr(offs), frames, poses_t.data_ptr() if idx.shape[0] else None,
                     rows_t.data_ptr() if rows_t is not None and idx.shape[0] else None,
                     _dptr(scale) if scale is not None and frames else None,
                     _dptr(motion) if motion is not None and frames else None, ws.data_ptr(), nbytes.value,
@@ -756,8 +737,7 @@ class HipEkf:
         idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
         offs = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         out = C.c_size_t()
-        self._check(self.lib.ekf_history_bytes(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               offs.ctypes.data_as(C.POINTER(C.c_int64)), offs.shape[0] - 1, C.byref(out)))
+        self._check(self.lib.ekf_history_bytes(self.h, _iptr(idx), _lptr(offs), offs.shape[0] - 1, C.byref(out)))
         return out.value
 
     def new_history(self, lm_index, offsets):
@@ -775,9 +755,8 @@ class HipEkf:
         frame, dims, stepped = (np.zeros(max(r, 1), dtype=np.int32) for _ in range(3))
         s_eff, motion = np.zeros(max(r, 1)), np.zeros((max(r, 1), 6))
         frec = np.zeros(max(self._history_frames, 1), dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
-        self._check(self.lib.ekf_history_info(self.h, C.byref(count), max(r, 1), frame.ctypes.data_as(ip), dims.ctypes.data_as(ip),
-                                              _dptr(s_eff), _dptr(motion), stepped.ctypes.data_as(ip), frec.ctypes.data_as(ip)))
+        self._check(self.lib.ekf_history_info(self.h, C.byref(count), max(r, 1), _iptr(frame), _iptr(dims), _dptr(s_eff),
+                                              _dptr(motion), _iptr(stepped), _iptr(frec)))
         return {"frame": frame[:r], "dims": dims[:r], "s_eff": s_eff[:r], "motion": motion[:r], "stepped": stepped[:r].astype(bool),
                 "frame_record": frec[:self._history_frames]}
 

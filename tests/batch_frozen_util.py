@@ -27,16 +27,6 @@ def batch(model, family, n, m, members=MEMBERS, **kw):
     return EKFBatch(members, INIT, model=model, max_landmarks=n, max_visible=m, **FAMILY[family], **kw)
 
 
-def snap(b):
-    return [(b.get_state(i), b.get_cov(i)) for i in range(b.members)]
-
-
-def same_snap(a, b, what):
-    for i, (x, y) in enumerate(zip(a, b)):
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and np.array_equal(u, v, equal_nan=True), (what, i)
-
-
 def raw_cov(b):
     """The whole device covariance [B, ld, ld], capacity padding included."""
     b.stream.synchronize()

@@ -16,6 +16,7 @@ import numpy as np
 import batch_smooth_util as bu
 import smooth_cov_util as scu
 import smooth_util as su
+import support as sp
 
 LD = su.LD
 WIDTH = 16                                            # batch.COLUMN_MAX_VISIBLE["ekf"]
@@ -60,14 +61,6 @@ def worst_ratios(cam_cov, first_cov, ref, records, frames):
     return float((err / fb[live]).max()), float(first)
 
 
-def snap(batch):
-    return [(batch.get_state(b), batch.get_cov(b), dict(batch.landmarks[b])) for b in range(batch.members)]
-
-
-def same(a, b):
-    return all(np.array_equal(u[0], v[0]) and np.array_equal(u[1], v[1]) and u[2] == v[2] for u, v in zip(a, b))
-
-
 def run_batch(logs, order=None, **kw):
     """A batch over ``logs`` (in ``order``: members permuted with their poses and noise) recorded, then: the state pass, the
     covariance pass with first_cov, the state pass again and the covariance pass again.  Returns {"batch", "order", "before",
@@ -79,13 +72,13 @@ def run_batch(logs, order=None, **kw):
     noise = {k: np.asarray(v, dtype=np.float64)[order] for k, v in kw.pop("noise", {}).items()}
     batch = bu.new_batch(len(order), poses=poses, noise=noise, **kw)
     filtered = batch.process_detection_logs([logs[i] for i in order], record=True)
-    before, status0 = snap(batch), batch.status()
+    before, status0 = sp.snap_batch(batch, tables=True), batch.status()
     state0 = batch.smooth_history()
     cov0 = batch.smooth_history_cov(first=True)
     smooth_status = batch.last_smooth_status.copy()
     state1 = batch.smooth_history()
     cov1 = batch.smooth_history_cov(first=True)
-    return {"batch": batch, "order": order, "poses": poses, "before": before, "after": snap(batch),
+    return {"batch": batch, "order": order, "poses": poses, "before": before, "after": sp.snap_batch(batch, tables=True),
             "status": (status0, batch.status()), "filtered": filtered, "state0": state0, "state1": state1, "cov0": cov0,
             "cov1": cov1, "smooth_status": smooth_status}
 

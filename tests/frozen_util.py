@@ -6,7 +6,9 @@ textbook Schmidt-Kalman update (Joseph form with the landmark rows of the gain z
 against."""
 import numpy as np
 
-INIT = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0], dtype=np.float64)
+import support as sp
+
+INIT = sp.INIT
 LMD = {"ekf": 3, "ekf_rotations": 10}
 CAM = 10
 

@@ -8,9 +8,10 @@ blocks are the S_d of the gate.  Free-running (``oracle_gated_replay``): the f64
 semantics, S_d formed from the support block of P + Q."""
 import numpy as np
 
+import support as sp
 from conftest import load_npz
 
-INIT = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0], dtype=np.float64)
+INIT = sp.INIT
 RD = {"ekf": 3, "ekf_rotations": 7}
 LMD = {"ekf": 3, "ekf_rotations": 10}
 # chi^2 99 % quantiles of 3 and 7 degrees of freedom: the gates of the teacher-forced and the free-running tests

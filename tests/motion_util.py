@@ -153,17 +153,6 @@ def step_ratios(ref, p_dev, x_dev, dtype):
     return float(r_p), float(r_c), float(r_q)
 
 
-def build_host_program(out_dir):
-    """Compile tests/host/motion_host_main.hip for the host against csrc/ekf_motion_device.h; returns the program's path."""
-    import subprocess
-    from pathlib import Path
-    from aruco_slam_amd import _build
-    exe = Path(out_dir) / "motion_host"
-    subprocess.run([_build.hipcc(), "--cuda-host-only", "-O3", "-std=c++17", f"-I{_build.CSRC}",
-                    str(sw.REPO / "tests" / "host" / "motion_host_main.hip"), "-o", str(exe)], check=True, capture_output=True)
-    return exe
-
-
 def run_host_program(exe, state, p, u, dtype):
     """(state[0:7], P') of the host build for one move, as a child process."""
     import subprocess

@@ -186,16 +186,6 @@ def worst(camera, r_r, r_t):
 # --------------------------------------------------------------------------------------------------------------------
 # host build of the device code (tests/host/ippe_host_main.hip)
 # --------------------------------------------------------------------------------------------------------------------
-def build_host_program(out_dir, include_first=None):
-    """Compile tests/host/ippe_host_main.hip for the host against csrc/ekf_ippe_device.h; returns the program's path."""
-    from aruco_slam_amd import _build
-    exe = Path(out_dir) / "ippe_host"
-    inc = ([f"-I{include_first}"] if include_first else []) + [f"-I{_build.CSRC}"]
-    subprocess.run([_build.hipcc(), "--cuda-host-only", "-O3", "-std=c++17", *inc,
-                    str(REPO / "tests" / "host" / "ippe_host_main.hip"), "-o", str(exe)], check=True, capture_output=True)
-    return exe
-
-
 def run_host_program(exe, corners, camera_matrix, dist, marker_size=MARKER):
     """(poses [n,6], chosen candidate [n]) of the host build, as a child process."""
     k = np.asarray(camera_matrix, dtype=np.float64).reshape(3, 3)

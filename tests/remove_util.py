@@ -3,7 +3,9 @@ removal, built by the restore path that existed before it: read state and P back
 host, and ``set_state_cov`` them into a fresh filter of the same configuration."""
 import numpy as np
 
-INIT = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0], dtype=np.float64)
+import support as sp
+
+INIT = sp.INIT
 LMD = {"ekf": 3, "ekf_rotations": 10}
 GATES = {"ekf": 11.345, "ekf_rotations": 18.475}
 

@@ -356,16 +356,3 @@ def direct_smooth(b, history, frames, blocked, poison=False):
     b.sync()
     torch.cuda.synchronize(b.device)
     return rc, out.cpu().numpy()
-
-
-def build_host_program(out_dir):
-    """Compile tests/host/smooth_host_main.hip for the host against csrc/ekf_smooth_device.h; returns the program's path."""
-    import subprocess
-    from pathlib import Path
-
-    import update_sweep_util as sw
-    from aruco_slam_amd import _build
-    exe = Path(out_dir) / "smooth_host"
-    subprocess.run([_build.hipcc(), "--cuda-host-only", "-O3", "-std=c++17", f"-I{_build.CSRC}",
-                    str(sw.REPO / "tests" / "host" / "smooth_host_main.hip"), "-o", str(exe)], check=True, capture_output=True)
-    return exe

@@ -6,9 +6,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import support as sp
+
 pytestmark = pytest.mark.gpu
 
-INIT = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0], dtype=np.float64)
+INIT = sp.INIT
 # member 0 (and the one log of the replicas): two first sightings, an empty frame, a re-observation and a first sighting
 LM_INDEX = np.array([0, 1, 0, 2], dtype=np.int32)
 FRAME_OFFSETS = np.array([0, 2, 2, 4], dtype=np.int64)
@@ -18,10 +20,6 @@ POSES = np.array([[0.3, -0.2, 2.0, 0.10, -0.20, 0.05], [-0.4, 0.1, 2.5, -0.10, 0
 ROWS = np.array([[1e-3, 2e-3, 4e-3], [2e-3, 1e-3, 3e-3], [5e-4, 1e-3, 2e-3], [3e-3, 3e-3, 1e-3]])
 SCALES = np.array([1.0, 0.5, 2.0])
 F, D = 3, 4
-
-
-def _same(a, b):
-    return all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b)) and len(a) == len(b)
 
 
 @pytest.fixture(scope="module")
@@ -85,7 +83,7 @@ def test_batch_log_entry_points_forward_to_the_widest(batch, name):
     sizes = lambda n: batch.lib.ekf_batch_log_workspace_bytes(batch.h, D, F, n)
     narrow = _run(batch, sizes, call(getattr(batch.lib, name), has), shapes)
     wide = _run(batch, sizes, call(batch.lib.ekf_batch_observe_logs_moved, WIDE), shapes)
-    assert _same(narrow, wide)
+    assert sp.same(narrow, wide, equal_nan=True)
     # (not vacuous: member 0 ran, with its three landmarks; member 1 did not)
     assert np.isfinite(narrow[0]).all() and list(narrow[-1]) == [3, 0] and not narrow[-2].any()
 
@@ -106,7 +104,7 @@ def test_batch_replica_entry_point_forwards_to_the_gated_one(batch):
     sizes = lambda n: batch.lib.ekf_batch_replica_workspace_bytes(batch.h, D, F, n)
     narrow = _run(batch, sizes, call(batch.lib.ekf_batch_observe_replicas, ()), shapes)
     wide = _run(batch, sizes, call(batch.lib.ekf_batch_observe_replicas_gated, (None,)), shapes)
-    assert _same(narrow, wide)
+    assert sp.same(narrow, wide, equal_nan=True)
     assert np.isfinite(narrow[0]).all() and list(narrow[-1]) == [3, 3]
     assert not np.array_equal(narrow[0][0], narrow[0][1])          # (the replicas drew their own noise)
 
@@ -145,7 +143,7 @@ def test_batch_refusals_of_the_log_call_and_of_the_history_size(batch):
                        lib.ekf_batch_observe_logs_recorded(*log, hist.data_ptr(), hist.numel())):
                 assert rc == code and lib.ekf_last_error_string().decode() == message
             batch.stream.synchronize()
-        assert _same(_members(batch), before)
+        assert sp.same(_members(batch), before, equal_nan=True)
     batch.reset()
 
 
@@ -185,5 +183,5 @@ def _sequence(name, has):
 def test_sequence_entry_points_forward_to_the_widest(name, has):
     narrow, narrow_mode = _sequence(name, has)
     wide, wide_mode = _sequence("ekf_observe_sequence_device_moved", has)
-    assert _same(narrow, wide) and narrow_mode == wide_mode and narrow_mode != "none"
+    assert sp.same(narrow, wide, equal_nan=True) and narrow_mode == wide_mode and narrow_mode != "none"
     assert np.isfinite(narrow[0]).all() and not np.array_equal(narrow[0][0], narrow[0][2])

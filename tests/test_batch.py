@@ -4,6 +4,7 @@ independence, the covariance invariants, failure isolation, host validation and 
 import numpy as np
 import pytest
 
+import support as sp
 from conftest import chaos_horizon, load_npz, rel_err, rel_err_elem, report
 
 pytestmark = pytest.mark.gpu
@@ -25,13 +26,6 @@ def _c1():
 def _frame_log(ids, poses):
     ids = np.asarray(ids, dtype=np.int32)
     return {"ids": ids, "poses": np.asarray(poses, dtype=np.float64), "offsets": np.array([0, len(ids)], dtype=np.int64)}
-
-
-def _sub(log, t0, t1):
-    offs = log["offsets"]
-    d0, d1 = int(offs[t0]), int(offs[t1])
-    return {"ids": log["ids"][d0:d1], "poses": log["poses"][d0:d1], "offsets": offs[t0:t1 + 1] - d0,
-            "has_detections": log["has_detections"][t0:t1]}
 
 
 def _ragged(n, m_range, steady, seed):
@@ -200,8 +194,8 @@ def test_continuation_across_calls_and_windows_is_bitwise():
     t_one = one.process_detection_logs([log, None])[0]
     two = _batch(2, max_landmarks=40, max_visible=16)
     cut = 100                                     # inside the second window
-    t_a = two.process_detection_logs([_sub(log, 0, cut), None])[0]
-    t_b = two.process_detection_logs([_sub(log, cut, frames), None])[0]
+    t_a = two.process_detection_logs([sp.sub_log(log, 0, cut), None])[0]
+    t_b = two.process_detection_logs([sp.sub_log(log, cut, frames), None])[0]
     assert np.array_equal(t_one, np.concatenate([t_a, t_b]))
     for a, b in zip(_snapshot(one, 0), _snapshot(two, 0)):
         assert np.array_equal(a, b)
@@ -224,8 +218,8 @@ def test_covariance_bitwise_symmetric_and_padding_zero():
 def test_failure_stays_inside_its_member():
     from aruco_slam_amd.batch import EKF_ERR_NUMERIC
     logs = [_ragged(20, (1, 8), 40, seed=s) for s in range(4)]
-    boot = [_sub(lg, 0, 10) for lg in logs]        # every landmark is sighted in the first 10 frames
-    rest = [_sub(lg, 10, len(lg["offsets"]) - 1) for lg in logs]
+    boot = [sp.sub_log(lg, 0, 10) for lg in logs]        # every landmark is sighted in the first 10 frames
+    rest = [sp.sub_log(lg, 10, len(lg["offsets"]) - 1) for lg in logs]
     ref = _batch(4, max_landmarks=20, max_visible=16)
     bad = _batch(4, max_landmarks=20, max_visible=16)
     for batch in (ref, bad):
@@ -314,7 +308,7 @@ def test_interop_with_ekf_and_empty_logs():
     assert np.array_equal(np.asarray(ekf.state), batch.get_state(0)) and np.array_equal(ekf.uncertainty, batch.get_cov(0))
     assert ekf.landmarks == batch.landmarks[0] and ekf.num_landmarks == batch.num_landmarks[0]
     more = _ragged(20, (1, 8), 5, seed=22)
-    nxt = _sub(more, len(more["offsets"]) - 4, len(more["offsets"]) - 1)
+    nxt = sp.sub_log(more, len(more["offsets"]) - 4, len(more["offsets"]) - 1)
     for t in range(3):
         sl = slice(int(nxt["offsets"][t]), int(nxt["offsets"][t + 1]))
         ekf.observe(nxt["ids"][sl], nxt["poses"][sl])
@@ -344,7 +338,7 @@ def test_load_filter_checks_the_filter_and_to_filter_keeps_the_member_noise():
     assert (ekf.backend.cfg.r_uncertainty, ekf.backend.cfg.q_lm) == (0.4, 0.03)
     assert np.array_equal(np.asarray(ekf.state), batch.get_state(1)) and np.array_equal(ekf.uncertainty, batch.get_cov(1))
     # the filter steps with the member's constants: one more frame, in the batch and in the filter
-    nxt = _sub(_ragged(12, (1, 6), 3, seed=5), 2, 3)
+    nxt = sp.sub_log(_ragged(12, (1, 6), 3, seed=5), 2, 3)
     ekf.observe(nxt["ids"], nxt["poses"])
     got = batch.process_detection_logs([None, nxt])[1][-1]
     assert rel_err(got, np.asarray(ekf.state)[:7]) <= 1e-10

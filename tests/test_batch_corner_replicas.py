@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import corner_replica_util as cu
+import support as sp
 from conftest import report, synthetic_marker_views
 
 pytestmark = pytest.mark.gpu
@@ -48,21 +49,6 @@ def _pose_log(log, poses):
 
 def _corner_only(log):
     return {k: v for k, v in log.items() if k != "poses_clean"}
-
-
-def _snap(batch):
-    return [(batch.get_state(b), batch.get_cov(b)) for b in range(batch.members)]
-
-
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
-def _assert_same(a, b, what):
-    assert len(a) == len(b), what
-    for x, y in zip(a, b):
-        for u, v in zip(x, y):
-            assert _same(u, v), what
 
 
 @pytest.mark.parametrize("sigma_px,flips", [(0.5, 59), (1.0, 124)])
@@ -137,15 +123,15 @@ def test_replicas_equal_explicit_logs_of_their_poses(camera, family, gate):
     if FAMILIES[family][0] == "ekf":
         assert batch.status() == [0] * B
     assert np.isfinite(got.trajectory).any()
-    assert _same(got.trajectory, np.stack(want.trajectory))
-    assert _same(got.nis, np.stack(want.nis))
-    assert _same(got.cam_cov, np.stack(want.cam_cov))
+    assert sp.same(got.trajectory, np.stack(want.trajectory), equal_nan=True)
+    assert sp.same(got.nis, np.stack(want.nis), equal_nan=True)
+    assert sp.same(got.cam_cov, np.stack(want.cam_cov), equal_nan=True)
     if gate is None:
         assert got.mahal is None and got.rejected is None and np.array_equal(got.dof, want.dof[0])
     else:
-        assert _same(got.mahal, np.stack(want.mahal)) and np.array_equal(got.rejected, np.stack(want.rejected))
+        assert sp.same(got.mahal, np.stack(want.mahal), equal_nan=True) and np.array_equal(got.rejected, np.stack(want.rejected))
         assert np.array_equal(got.dof, np.stack(want.dof)) and got.dof.shape == got.nis.shape
-    _assert_same(_snap(batch), _snap(explicit), "state / P")
+    sp.assert_same(sp.snap_batch(batch), sp.snap_batch(explicit), "state / P", equal_nan=True)
     assert batch.landmarks == explicit.landmarks
     assert not np.array_equal(got.trajectory[0], got.trajectory[1])      # (replicas differ: sigma_px > 0)
     report("corner_replicas_vs_explicit", family=family, gated=gate is not None, flipped=int(got.flipped.sum()),
@@ -163,9 +149,9 @@ def test_zero_sigma_is_the_plain_front_end(camera, family):
     want = plain.process_detection_logs([_pose_log(log, poses)] * B, nis=True, cam_cov=True)
     assert not got.flipped.any() and got.flipped.shape == (B, log["ids"].shape[0])
     assert np.isfinite(got.trajectory).any()
-    assert _same(got.trajectory, np.stack(want.trajectory))
-    assert _same(got.nis, np.stack(want.nis)) and _same(got.cam_cov, np.stack(want.cam_cov))
-    _assert_same(_snap(batch), _snap(plain), "state / P")
+    assert sp.same(got.trajectory, np.stack(want.trajectory), equal_nan=True)
+    assert sp.same(got.nis, np.stack(want.nis), equal_nan=True) and sp.same(got.cam_cov, np.stack(want.cam_cov), equal_nan=True)
+    sp.assert_same(sp.snap_batch(batch), sp.snap_batch(plain), "state / P", equal_nan=True)
 
 
 def test_corner_logs_in_process_detection_logs(camera):
@@ -184,7 +170,7 @@ def test_corner_logs_in_process_detection_logs(camera):
     for m in range(6):
         assert np.array_equal(got.trajectory[m], want.trajectory[m]) and np.array_equal(got.nis[m], want.nis[m])
         assert np.array_equal(got.cam_cov[m], want.cam_cov[m])
-    _assert_same(_snap(a), _snap(b), "state / P")
+    sp.assert_same(sp.snap_batch(a), sp.snap_batch(b), "state / P", equal_nan=True)
     assert a.landmarks == b.landmarks
     # every log a corner log: the plain return value
     c, d = _batch("ekf-column", 2, camera), _batch("ekf-column", 2, None)
@@ -199,7 +185,7 @@ def test_replica_identity_across_batch_sizes_and_calls(camera):
     log = _corner_only(_log("ekf-column", camera, seed=11))
     big = _batch("ekf-column", 16, camera)
     whole = big.replay_corner_replicas(log, sigma_px, seed, nis=True, cam_cov=True)
-    big_snap = _snap(big)
+    big_snap = sp.snap_batch(big)
     assert whole.flipped.any()
     for r0 in (0, 8, 4):
         part = _batch("ekf-column", 8, camera)
@@ -207,7 +193,7 @@ def test_replica_identity_across_batch_sizes_and_calls(camera):
         sl = slice(r0, r0 + 8)
         assert np.array_equal(out.trajectory, whole.trajectory[sl]) and np.array_equal(out.flipped, whole.flipped[sl])
         assert np.array_equal(out.nis, whole.nis[sl]) and np.array_equal(out.cam_cov, whole.cam_cov[sl])
-        _assert_same(_snap(part), big_snap[sl], f"members {r0}..{r0 + 7}")
+        sp.assert_same(sp.snap_batch(part), big_snap[sl], f"members {r0}..{r0 + 7}", equal_nan=True)
 
 
 def test_flipped_is_aligned_with_the_logs_own_detections(camera):
@@ -245,7 +231,7 @@ def test_bad_arguments_raise_before_anything_runs(camera):
     log = _corner_only(_log("ekf-column", camera, seed=2))
     batch = _batch("ekf-column", 3, camera)
     batch.replay_corner_replicas(log, 0.5, 1)
-    before, tables = _snap(batch), [dict(t) for t in batch.landmarks]
+    before, tables = sp.snap_batch(batch), [dict(t) for t in batch.landmarks]
     wide = _corner_only(corner_log(20, (17, 20), 2, 4, camera[0], camera[1], MARKER))
     pose_log = _pose_log(log, np.zeros((log["ids"].shape[0], 6)))
     cases = [
@@ -265,7 +251,7 @@ def test_bad_arguments_raise_before_anything_runs(camera):
         if exc is EkfError:
             assert info.value.code == -2, name
         assert batch.landmarks == tables, name
-        _assert_same(before, _snap(batch), name)
+        sp.assert_same(before, sp.snap_batch(batch), name, equal_nan=True)
         assert batch.status() == [0, 0, 0]
     no_camera = _batch("ekf-column", 3, None)
     with pytest.raises(ValueError, match="set_camera"):
@@ -276,4 +262,4 @@ def test_bad_arguments_raise_before_anything_runs(camera):
     batch.reset(1)
     with pytest.raises(ValueError, match="landmark table"):
         batch.replay_corner_replicas(log, 0.5, 1)
-    _assert_same(before[::2], _snap(batch)[::2], "unequal tables")
+    sp.assert_same(before[::2], sp.snap_batch(batch)[::2], "unequal tables", equal_nan=True)

@@ -3,25 +3,18 @@ noise stream, the flips and margins of the inputs the GPU test compares on, ``sy
 (declared, exported, validated before any device work), the register / LDS budget of the new kernel, and the host side of
 ``replay_corner_replicas`` and of corner logs in ``process_detection_logs``."""
 import ctypes
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import corner_replica_util as cu
 import replica_util as ru
+import support as sp
 from conftest import synthetic_marker_views
+from support import lib
 
 NEW_SYMBOLS = ("ekf_batch_replica_corners", "ekf_batch_observe_corner_replicas")
 VIEWS, REPLICAS, SEED, MARKER = 48, 16, 7, 0.16
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
 
 
 @pytest.fixture(scope="module")
@@ -134,12 +127,8 @@ def test_corner_log_flips_at_one_pixel():
 
 
 def test_new_symbols_are_declared_and_exported(lib):
-    from pathlib import Path
-    from aruco_slam_amd import hip_backend
-    header = (Path(__file__).resolve().parent.parent / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     for word in ("4 + i", "R_clean", "trace(R_a R_clean^T) < trace(R_b R_clean^T)"):
         assert word in header, word
 
@@ -179,26 +168,6 @@ def test_replica_corners_validates_before_any_device_work(lib):
     assert b"handle" in lib.ekf_last_error_string()
 
 
-def _kernel_resources(src, pattern):
-    from aruco_slam_amd import _build
-    import tempfile
-    from pathlib import Path
-    with tempfile.TemporaryDirectory() as tmp:
-        out = Path(tmp) / "k.s"
-        subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                        str(_build.CSRC / src), "-o", str(out)], check=True, capture_output=True)
-        text = out.read_text()
-    meta = text[text.index("amdhsa.kernels:"):text.index("amdhsa.target:")]
-    found = {}
-    for entry in re.split(r"\n  - ", meta)[1:]:        # one entry per kernel; its own fields are indented by 4
-        fields = dict(re.findall(r"^(?:  )?  \.([a-z_]+):\s+(\S+)", entry, re.M))
-        name = fields.get("name", "")
-        if re.search(pattern, name):
-            found[name] = {k: int(fields[k]) for k in ("private_segment_fixed_size", "vgpr_spill_count",
-                                                       "group_segment_fixed_size")}
-    return found
-
-
 @pytest.mark.parametrize("src,pattern", [
     ("ekf_batch_corner_replicas.hip", r"ekf_corner_replicas_kernel"),
     ("ekf_batch_replicas.hip", r"ekf_replica_poses_kernel"),
@@ -206,10 +175,10 @@ def _kernel_resources(src, pattern):
 ])
 def test_kernels_use_no_scratch_no_spill_no_static_lds(src, pattern):
     """The new kernel, and the two that now share its headers: no scratch memory, no VGPR spills, no static LDS."""
-    found = _kernel_resources(src, pattern)
+    found = sp.kernel_resources(src, pattern)
     assert len(found) == 1, found
     for name, res in found.items():
-        assert res == {"private_segment_fixed_size": 0, "vgpr_spill_count": 0, "group_segment_fixed_size": 0}, (name, res)
+        assert [res[k] for k in sp.BUDGET_FIELDS] == [0, 0, 0], (name, res)
 
 
 def test_the_shared_device_code_has_one_definition():

@@ -1,11 +1,11 @@
 """Batch of independent filters without a GPU: the host-side planning and validation of batch logs (what runs before the
 library), construction without a device, and the register / LDS budget of the batch kernel."""
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import support as sp
 from aruco_slam_amd.filters.base_filter import plan_detection_log
 
 
@@ -103,20 +103,13 @@ def test_bad_arguments_raise_value_errors():
 
 def test_batch_config_limits_are_checked():
     import ctypes
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    lib = hip_backend.load_library()
-    cfg = hip_backend.EkfConfig()
-    lib.ekf_default_config(ctypes.byref(cfg))
-    cfg.max_visible = 16
+    lib = sp.load_lib()
+    cfg = sp.config(lib, max_visible=16)
     ld = ctypes.c_int64()
     assert lib.ekf_batch_query_sizes(ctypes.byref(cfg), 8, ctypes.byref(ld), None, None, None) == 0
     assert ld.value % 32 == 0 and 160 <= ld.value < 192          # N = 3 * 50 + 10
     for field, value in (("max_landmarks", 83), ("max_visible", 17), ("model", 1), ("cov_dtype", 1)):
-        bad = hip_backend.EkfConfig()
-        lib.ekf_default_config(ctypes.byref(bad))
-        bad.max_visible = 16
-        setattr(bad, field, value)
+        bad = sp.config(lib, **{"max_visible": 16, field: value})
         assert lib.ekf_batch_query_sizes(ctypes.byref(bad), 8, None, None, None, None) == -1, field
         if field in ("max_landmarks", "max_visible"):      # (batch errors reach the library's one error slot)
             assert field.encode() in lib.ekf_last_error_string(), field
@@ -127,25 +120,17 @@ def test_batch_kernel_uses_no_scratch_and_fits_the_lds():
     """No scratch memory, no spills, no static LDS; and the dynamic LDS the library requests for the largest batch (k = 3
     EKF_BATCH_MAX_VISIBLE rows, A/W rows of round_up(3 EKF_BATCH_MAX_LANDMARKS + 10 + 1, 4)) fits the 160 KiB of a CU."""
     import ctypes
-    import tempfile
-    from pathlib import Path
-    from aruco_slam_amd import _build, hip_backend
-    with tempfile.TemporaryDirectory() as tmp:
-        out = Path(tmp) / "batch.s"
-        subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                        str(_build.CSRC / "ekf_batch.hip"), "-o", str(out)], check=True, capture_output=True)
-        text = out.read_text()
-    pat = r"\.name:\s+(\S*ekf_batch_window_kernel\S*)\n(?:.*\n)*?\s+\.{}:\s+(\d+)"
+    from aruco_slam_amd import _build
+    found = sp.kernel_resources("ekf_batch.hip", r"ekf_batch_window_kernel")
+    assert len(found) == 1, found
     for field in ("private_segment_fixed_size", "vgpr_spill_count"):
-        found = re.findall(pat.format(field), text)
-        assert len(found) == 1 and int(found[0][1]) == 0, (field, found)
-    static = re.findall(r"\.group_segment_fixed_size:\s+(\d+)", text)      # (the file's only kernel)
-    assert static == ["0"], static
+        assert [res[field] for res in found.values()] == [0], (field, found)
+    static = [res["group_segment_fixed_size"] for res in sp.kernel_resources("ekf_batch.hip").values()]
+    assert static == [0], static      # (the file's only kernel)
     header = (_build.CSRC / "ekf_kernels.h").read_text()
     max_lm = int(re.search(r"#define EKF_BATCH_MAX_LANDMARKS (\d+)", header).group(1))
     max_vis = int(re.search(r"#define EKF_BATCH_MAX_VISIBLE (\d+)", header).group(1))
-    _build.build()
-    lib = hip_backend.load_library()
+    lib = sp.load_lib()
     lds_bytes = lib.ekf_batch_lds_bytes
     lds_bytes.argtypes, lds_bytes.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_size_t
     kmax, lda = 3 * max_vis, -(-(3 * max_lm + 11) // 4) * 4

@@ -8,6 +8,7 @@ import pytest
 
 import frame_scale_util as fs
 import gating_util as gu
+import support as sp
 import update_sweep_util as sw
 from conftest import report
 
@@ -21,24 +22,6 @@ EXTRA = {"column": {}, "large": {"large_maps": True}, "wide": {"wide_frames": Tr
 STEP_MEMBERS = {"ekf": [(1, 1), (39, 3), (82, 8), (39, 16)], "ekf_rotations": [(1, 1), (12, 2), (24, 5), (12, 8)]}
 STEP_WIDE = {"ekf": [(40, 17), (40, 36)], "ekf_rotations": [(20, 9), (20, 18)]}
 Q_KEYS = ("q_cam", "q_err", "q_lm")
-
-
-def _batch(members, model, family, **extra):
-    from aruco_slam_amd.batch import EKFBatch
-    kw = dict(gu.FAMILIES[(model, family)][0])
-    kw.update(extra)
-    return EKFBatch(members, INIT, model=model, **kw)
-
-
-def _snap(batch):
-    return [(batch.get_state(b), batch.get_cov(b)) for b in range(batch.members)]
-
-
-def _same_snap(a, b, what):
-    assert len(a) == len(b), what
-    for x, y in zip(a, b):
-        for u, v in zip(x, y):
-            assert np.array_equal(u, v, equal_nan=True), what
 
 
 def _same_outputs(got, want, what, names=("trajectory", "nis", "cam_cov", "dof", "mahal", "rejected")):
@@ -55,12 +38,12 @@ def test_a_batch_log_is_its_folded_form(model, family):
     rows with nis 0; the trailing empty frame's scale is left pending."""
     pairs = [fs.ragged_scaled_log(model, seed=s) for s in (3, 4, 5)]
     folded = [fs.fold_log(log, scale) for log, scale in pairs]
-    full = _batch(3, model, family, frame_scale=True)
+    full = sp.family_batch(3, model, family, frame_scale=True)
     got = full.process_detection_logs([dict(log, scale=scale) for log, scale in pairs], nis=True, cam_cov=True)
-    short = _batch(3, model, family, frame_scale=True)
+    short = sp.family_batch(3, model, family, frame_scale=True)
     want = short.process_detection_logs([dict(log, scale=scale) for log, scale, _left in folded], nis=True, cam_cov=True)
     assert full.status() == short.status() == [0] * 3
-    _same_snap(_snap(full), _snap(short), "folded")
+    sp.assert_same(sp.snap_batch(full), sp.snap_batch(short), "folded", equal_nan=True)
     assert np.array_equal(full.pending_scale, [scale[-1] for _log, scale in pairs]) and not short.pending_scale.any()
     for b, (log, _scale) in enumerate(pairs):
         stepped = np.diff(log["offsets"]) > 0
@@ -71,7 +54,7 @@ def test_a_batch_log_is_its_folded_form(model, family):
             if not stepped[t]:
                 assert np.array_equal(got.trajectory[b][t], got.trajectory[b][t - 1])
                 assert np.array_equal(got.cam_cov[b][t], got.cam_cov[b][t - 1])
-    plain = _batch(3, model, family, frame_scale=True)      # (the scales are not ignored)
+    plain = sp.family_batch(3, model, family, frame_scale=True)      # (the scales are not ignored)
     plain.process_detection_logs([log for log, _scale in pairs])
     assert not np.array_equal(plain.get_cov(0), full.get_cov(0)) and not plain.pending_scale.any()
 
@@ -85,16 +68,16 @@ def test_a_constant_scale_is_the_members_products_bit_for_bit(model, family):
     consts = [0.0, 0.3, 1.0, 7.5]
     logs = [gu.clean_log(model, family, seed=s) for s in range(4)]
     assert all((np.diff(lg["offsets"]) > 0).all() for lg in logs)
-    scaled = _batch(4, model, family, frame_scale=True)
+    scaled = sp.family_batch(4, model, family, frame_scale=True)
     got = scaled.process_detection_logs([dict(lg, scale=np.full(len(lg["offsets"]) - 1, c)) for lg, c in zip(logs, consts)],
                                         nis=True, cam_cov=True, mahal=True)
     products = {k: np.array([fs.scaled_constants(model, c)[k] for c in consts]) for k in Q_KEYS}
-    twin = _batch(4, model, family, noise=products)
+    twin = sp.family_batch(4, model, family, noise=products)
     want = twin.process_detection_logs(logs, nis=True, cam_cov=True, mahal=True)
     assert scaled.status() == twin.status() == [0] * 4
     _same_outputs(got, want, "scale = c")
-    _same_snap(_snap(scaled), _snap(twin), "scale = c")
-    plain = _batch(4, model, family)      # (member 2, c = 1, is the plain member; the others are not)
+    sp.assert_same(sp.snap_batch(scaled), sp.snap_batch(twin), "scale = c", equal_nan=True)
+    plain = sp.family_batch(4, model, family)      # (member 2, c = 1, is the plain member; the others are not)
     ref = plain.process_detection_logs(logs)
     assert np.array_equal(ref[2], got.trajectory[2]) and not np.array_equal(ref[3], got.trajectory[3])
 
@@ -108,18 +91,18 @@ def test_the_flag_alone_and_scales_all_one_change_nothing(model, family):
     dirty = [gu.dirty_log(model, gu.clean_log(model, family, seed=s), seed=s)[0] for s in range(2)]
     outs = []
     for flag in (True, False):
-        batch = _batch(2, model, family, gate=gu.GATES[model], frame_scale=flag)
-        outs.append((batch.process_detection_logs(dirty, nis=True, cam_cov=True), _snap(batch)))
+        batch = sp.family_batch(2, model, family, gate=gu.GATES[model], frame_scale=flag)
+        outs.append((batch.process_detection_logs(dirty, nis=True, cam_cov=True), sp.snap_batch(batch)))
         assert not batch.pending_scale.any()
     _same_outputs(outs[0][0], outs[1][0], "flag")
-    _same_snap(outs[0][1], outs[1][1], "flag")
+    sp.assert_same(outs[0][1], outs[1][1], "flag", equal_nan=True)
     clean = [gu.clean_log(model, family, seed=s) for s in range(2)]
-    ones = _batch(2, model, family, frame_scale=True)
+    ones = sp.family_batch(2, model, family, frame_scale=True)
     got = ones.process_detection_logs([dict(lg, scale=np.ones(len(lg["offsets"]) - 1)) for lg in clean], nis=True)
-    none = _batch(2, model, family)
+    none = sp.family_batch(2, model, family)
     want = none.process_detection_logs(clean, nis=True)
     _same_outputs(got, want, "ones", names=("trajectory", "nis", "dof"))
-    _same_snap(_snap(ones), _snap(none), "ones")
+    sp.assert_same(sp.snap_batch(ones), sp.snap_batch(none), "ones", equal_nan=True)
 
 
 # ---- one step ---------------------------------------------------------------------------------------------------------------
@@ -171,12 +154,12 @@ def test_large_and_wide_kernels_are_bitwise_the_one_column_kernel_with_scales(mo
         kw = dict(gu.FAMILIES[(model, "column")][0], gate=gu.GATES[model], frame_scale=True)
         kw.update(EXTRA[family])
         batch = EKFBatch(2, INIT, model=model, **kw)
-        outs.append((batch.process_detection_logs(logs, nis=True, cam_cov=True), _snap(batch), batch.pending_scale))
+        outs.append((batch.process_detection_logs(logs, nis=True, cam_cov=True), sp.snap_batch(batch), batch.pending_scale))
         assert batch.status() == [0, 0]
     assert outs[0][0].rejected[0].any() and outs[0][2][1] == rscale[-1]
     for family, (out, snap, pending) in zip(("large", "wide"), outs[1:]):
         _same_outputs(out, outs[0][0], family)
-        _same_snap(snap, outs[0][1], family)
+        sp.assert_same(snap, outs[0][1], family, equal_nan=True)
         assert np.array_equal(pending, outs[0][2]), family
 
 
@@ -198,15 +181,15 @@ def test_gate_and_scales_compose(model, family):
     marks = [marks[0], np.concatenate((marks[1], np.ones(sl.stop - sl.start, dtype=bool)))]
     rng = np.random.default_rng(51)
     scales = [np.exp(rng.uniform(np.log(0.5), np.log(2.0), len(lg["offsets"]) - 1)) for lg in logs]
-    gated = _batch(2, model, family, gate=gu.GATES[model], frame_scale=True)
+    gated = sp.family_batch(2, model, family, gate=gu.GATES[model], frame_scale=True)
     got = gated.process_detection_logs([dict(lg, scale=s) for lg, s in zip(logs, scales)], nis=True, cam_cov=True)
     for b in range(2):
         assert np.array_equal(got.rejected[b], marks[b]), b
     cut = [dict(gu.delete(lg, mk), scale=s) for lg, mk, s in zip(logs, marks, scales)]
-    plain = _batch(2, model, family, frame_scale=True)
+    plain = sp.family_batch(2, model, family, frame_scale=True)
     want = plain.process_detection_logs(cut, nis=True, cam_cov=True)
     _same_outputs(got, want, "gated = cut", names=("trajectory", "nis", "cam_cov"))
-    _same_snap(_snap(gated), _snap(plain), "gated = cut")
+    sp.assert_same(sp.snap_batch(gated), sp.snap_batch(plain), "gated = cut", equal_nan=True)
     pending = gated.pending_scale
     assert np.array_equal(pending, plain.pending_scale) and pending[0] == 0.0 and pending[1] == scales[1][-1]
 
@@ -223,11 +206,11 @@ def test_lockout_fixture_in_a_batch(model):
     after = slice(int(offs[fa]), None)
     bare = {k: log[k] for k in ("ids", "poses", "offsets", "has_detections")}
     kw = {"quat_update": "scalar_first"} if model == "ekf" else {}
-    plain = _batch(1, model, "column", gate=gate, **kw).process_detection_logs([bare])
+    plain = sp.family_batch(1, model, "column", gate=gate, **kw).process_detection_logs([bare])
     assert plain.rejected[0][after].all() and not plain.rejected[0][:int(offs[fa])].any()
     assert (plain.dof[0][fa:] == 0).all() and (plain.mahal[0][after] >= 2.0 * gate).all()
     assert fs.position_error(plain.trajectory[0], log) > 0.9 * fs.LOCKOUT[model][1]
-    timed = _batch(2, model, "column", gate=gate, frame_scale=True, **kw)
+    timed = sp.family_batch(2, model, "column", gate=gate, frame_scale=True, **kw)
     got = timed.process_detection_logs([dict(bare, scale=log["scale"]),
                                         dict({k: still[k] for k in bare}, scale=still["scale"])])
     want = fs.oracle_scaled_replay(model, log, log["scale"], gate)
@@ -243,7 +226,7 @@ def test_lockout_fixture_in_a_batch(model):
 def test_pending_scale_of_a_member(model):
     family = "column"
     log = gu.clean_log(model, family, seed=2)
-    batch = _batch(3, model, family, frame_scale=True)
+    batch = sp.family_batch(3, model, family, frame_scale=True)
     assert batch.pending_scale.tolist() == [0.0, 0.0, 0.0]
     batch.process_detection_logs([log, log, log])
     batch.set_pending_scale([0.5, 1.25, 2.0])
@@ -262,17 +245,17 @@ def test_pending_scale_of_a_member(model):
     flt.advance(0.25)
     batch.load_filter(2, flt)
     assert batch.pending_scale.tolist() == [0.5, 1.25, 1.5]
-    _same_snap([_snap(batch)[2]], [_snap(batch)[1]], "load_filter")
+    sp.assert_same([sp.snap_batch(batch)[2]], [sp.snap_batch(batch)[1]], "load_filter", equal_nan=True)
     # the member and the filter step on with the same pending scale: a frame without a scale runs with p + 1
     head = int(log["offsets"][int(log["bootstrap_frames"]) + 1])
     t0 = int(log["bootstrap_frames"])
     frame = {"ids": log["ids"][int(log["offsets"][t0]):head], "poses": log["poses"][int(log["offsets"][t0]):head] + 0.0,
              "offsets": np.array([0, head - int(log["offsets"][t0])], np.int64)}
-    twin = _batch(1, model, family, noise={k: fs.scaled_constants(model, 2.25)[k] for k in Q_KEYS})
+    twin = sp.family_batch(1, model, family, noise={k: fs.scaled_constants(model, 2.25)[k] for k in Q_KEYS})
     twin.set_member(0, batch.get_state(1), batch.get_cov(1), [k for k, _ in sorted(batch.landmarks[1].items(), key=lambda kv: kv[1])])
     batch.process_detection_logs([None, frame, None])
     twin.process_detection_logs([frame])
-    _same_snap([_snap(batch)[1]], _snap(twin), "p + 1")
+    sp.assert_same([sp.snap_batch(batch)[1]], sp.snap_batch(twin), "p + 1", equal_nan=True)
     assert batch.pending_scale.tolist() == [0.5, 0.0, 1.5]
     batch.set_member(0, batch.get_state(0), batch.get_cov(0), [k for k, _ in sorted(batch.landmarks[0].items(), key=lambda kv: kv[1])])
     assert batch.pending_scale.tolist() == [0.0, 0.0, 1.5]
@@ -281,7 +264,7 @@ def test_pending_scale_of_a_member(model):
     batch.set_pending_scale(1.0)
     batch.reset()
     assert not batch.pending_scale.any()
-    plain = _batch(1, model, family)
+    plain = sp.family_batch(1, model, family)
     assert plain.pending_scale.tolist() == [0.0] and plain.to_filter(0).backend.can_frame_scale is False
     with pytest.raises(ValueError, match="frame_scale=True"):
         plain.load_filter(0, flt)
@@ -291,14 +274,14 @@ def test_scale_arguments_of_the_batch_are_validated():
     model, family = "ekf", "column"
     log = gu.clean_log(model, family, seed=0)
     frames = len(log["offsets"]) - 1
-    plain = _batch(1, model, family)
+    plain = sp.family_batch(1, model, family)
     with pytest.raises(ValueError, match="frame_scale=True"):
         plain.process_detection_logs([dict(log, scale=np.ones(frames))])
     with pytest.raises(ValueError, match="frame_scale=True"):
         plain.observe_indexed(np.zeros(1, np.int32), [0, 1], [0, 1], np.zeros((1, 6)), scale=[1.0])
     with pytest.raises(ValueError, match="frame_scale=True"):
         plain.set_pending_scale(1.0)
-    batch = _batch(2, model, family, frame_scale=True)
+    batch = sp.family_batch(2, model, family, frame_scale=True)
     for bad in (np.ones(frames - 1), np.ones((frames, 1)), np.full(frames, np.nan), np.full(frames, -1.0), np.full(frames, np.inf)):
         with pytest.raises(ValueError, match="scale"):
             batch.process_detection_logs([dict(log, scale=bad), dict(log, scale=np.ones(frames))])

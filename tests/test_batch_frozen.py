@@ -9,6 +9,7 @@ import pytest
 import batch_frozen_util as bu
 import frozen_util as fu
 import gating_util as gu
+import support as sp
 import update_sweep_util as sw
 from conftest import load_npz, rel_err, synthetic_marker_views
 
@@ -82,7 +83,7 @@ def test_one_frozen_frame_is_the_camera_strip_of_the_mapping_frame(family, model
     want = twin.process_detection_logs(frames, nis=True, cam_cov=True)
     assert batch.status() == twin.status() == [0] * MEMBERS
     assert batch.map_frozen.tolist() == [True, False, True, False]
-    twin_snap, raw, raw_twin = bu.snap(twin), bu.raw_cov(batch), bu.raw_cov(twin)
+    twin_snap, raw, raw_twin = sp.snap_batch(twin), bu.raw_cov(batch), bu.raw_cov(twin)
     for name in ("trajectory", "nis", "cam_cov"):      # (the per-frame outputs hold camera quantities only)
         for b in range(MEMBERS):
             assert np.array_equal(getattr(got, name)[b], getattr(want, name)[b]), (name, b)
@@ -112,11 +113,11 @@ def test_three_kernels_agree_and_a_member_is_its_per_frame_calls_and_the_oracle(
     for family in bu.FAMILY:
         batch = bu.batch(model, family, 8, 8)
         first = batch.process_detection_logs(a)
-        at_freeze = bu.snap(batch)
+        at_freeze = sp.snap_batch(batch)
         batch.freeze_map()
         out = batch.process_detection_logs(z, nis=True, cam_cov=True)
         assert batch.status() == [0] * MEMBERS and batch.last_ignored == [()] * MEMBERS
-        outs[family] = (first, out, bu.snap(batch))
+        outs[family] = (first, out, sp.snap_batch(batch))
         for (s0, p0), (s1, p1) in zip(at_freeze, outs[family][2]):
             assert np.array_equal(s1[CAM:], s0[CAM:]) and np.array_equal(p1[CAM:, CAM:], p0[CAM:, CAM:]), family
             assert not np.array_equal(p1[:CAM], p0[:CAM])
@@ -126,7 +127,7 @@ def test_three_kernels_agree_and_a_member_is_its_per_frame_calls_and_the_oracle(
         for name in ("trajectory", "nis", "cam_cov"):
             for b in range(MEMBERS):
                 assert np.array_equal(getattr(got, name)[b], getattr(want, name)[b]), (family, name, b)
-        bu.same_snap(snap, want_snap, family)
+        sp.assert_same(snap, want_snap, family, equal_nan=True)
     # one frame per call
     loop = bu.batch(model, "column", 8, 8)
     rows = [[] for _ in range(MEMBERS)]
@@ -135,7 +136,7 @@ def test_three_kernels_agree_and_a_member_is_its_per_frame_calls_and_the_oracle(
             loop.freeze_map()
         for b, tr in enumerate(loop.process_detection_logs([bu.part(log, t, t + 1) for log in logs])):
             rows[b].append(tr[0])
-    bu.same_snap(bu.snap(loop), want_snap, "per-frame calls")
+    sp.assert_same(sp.snap_batch(loop), want_snap, "per-frame calls", equal_nan=True)
     worst = 0.0
     for b, log in enumerate(logs):
         traj = np.concatenate((first[b], want.trajectory[b]))
@@ -197,13 +198,13 @@ def test_a_gated_frozen_frame_is_the_ungated_frozen_frame_on_the_survivors(model
         assert got.dof[b][0] == gu.RD[model] * (m - 2)
         for name in ("trajectory", "nis", "cam_cov"):
             assert np.array_equal(getattr(got, name)[b], getattr(want, name)[b]), (name, b)
-    bu.same_snap(bu.snap(gated), bu.snap(plain), "gated = ungated on the survivors")
+    sp.assert_same(sp.snap_batch(gated), sp.snap_batch(plain), "gated = ungated on the survivors", equal_nan=True)
     for b, (state, p, _ids) in enumerate(priors):      # (and the map did not move)
         assert np.array_equal(gated.get_cov(b)[CAM:, CAM:], p[CAM:, CAM:])
     # every detection rejected: not stepped
-    before = bu.snap(gated)
+    before = sp.snap_batch(gated)
     out = gated.process_detection_logs(all_out, nis=True)
-    bu.same_snap(bu.snap(gated), before, "a frame of outliers only")
+    sp.assert_same(sp.snap_batch(gated), before, "a frame of outliers only", equal_nan=True)
     for b in range(MEMBERS):
         assert out.rejected[b].all() and out.nis[b][0] == 0 and np.array_equal(out.trajectory[b][0], before[b][0][:7])
 
@@ -223,18 +224,18 @@ def test_frozen_frames_compose_with_noise_rows_scale_and_motion(model, family):
     rows.process_detection_logs([dict(f, noise=np.full(m, c)) for f in frames])
     const.process_detection_logs(frames)
     assert rows.status() == const.status() == [0] * MEMBERS
-    bu.same_snap(bu.snap(rows), bu.snap(const), "noise rows")
+    sp.assert_same(sp.snap_batch(rows), sp.snap_batch(const), "noise rows", equal_nan=True)
     # frame scale
     s1, s2 = 1.75, 0.6
     scaled = _frozen_batch(model, family, n, m, priors, frame_scale=True)
     summed = _frozen_batch(model, family, n, m, priors, frame_scale=True)
     scaled.process_detection_logs([dict(EMPTY, scale=np.array([s1]))] * MEMBERS)
     assert scaled.pending_scale.tolist() == [s1] * MEMBERS and scaled.map_frozen.all()
-    bu.same_snap(bu.snap(scaled), [(s, p) for s, p, _ in priors], "an unstepped frozen frame")
+    sp.assert_same(sp.snap_batch(scaled), [(s, p) for s, p, _ in priors], "an unstepped frozen frame", equal_nan=True)
     scaled.process_detection_logs([dict(f, scale=np.array([s2])) for f in frames])
     summed.process_detection_logs([dict(f, scale=np.array([s1 + s2])) for f in frames])
     assert scaled.pending_scale.tolist() == [0.0] * MEMBERS and scaled.status() == summed.status() == [0] * MEMBERS
-    bu.same_snap(bu.snap(scaled), bu.snap(summed), "pending scale")
+    sp.assert_same(sp.snap_batch(scaled), sp.snap_batch(summed), "pending scale", equal_nan=True)
     assert not np.array_equal(scaled.get_cov(0)[:CAM], const.get_cov(0)[:CAM])
     # motion
     moves = [dict(EMPTY, motion=u[None, :]) for u in mu.STEP_MOTIONS.values()]
@@ -246,7 +247,7 @@ def test_frozen_frames_compose_with_noise_rows_scale_and_motion(model, family):
     steps.process_detection_logs(frames)      # (no motions: the FROZEN instance without the stage)
     fused.process_detection_logs([dict(f, motion=mv["motion"]) for f, mv in zip(frames, moves)])
     assert steps.status() == fused.status() == [0] * MEMBERS
-    bu.same_snap(bu.snap(steps), bu.snap(fused), "moved frozen frame")
+    sp.assert_same(sp.snap_batch(steps), sp.snap_batch(fused), "moved frozen frame", equal_nan=True)
     for batch in (rows, scaled, fused):
         for b, (state, p, _ids) in enumerate(priors):
             assert np.array_equal(batch.get_state(b)[CAM:], state[CAM:]) and np.array_equal(batch.get_cov(b)[CAM:, CAM:], p[CAM:, CAM:])
@@ -271,10 +272,10 @@ def test_frozen_replicas_are_frozen_logs_of_the_poses_they_consumed(model):
     for bt in (batch, twin):
         _restore(bt, [(state, p, lm_ids)] * MEMBERS)
     batch.freeze_map(1)
-    before = bu.snap(batch)
+    before = sp.snap_batch(batch)
     with pytest.raises(ValueError, match="frozen"):
         batch.replay_replicas(log, sigma, 3)
-    bu.same_snap(bu.snap(batch), before, "mixed flags")
+    sp.assert_same(sp.snap_batch(batch), before, "mixed flags", equal_nan=True)
     for bt in (batch, twin):
         bt.freeze_map()
     got = batch.replay_replicas(log, sigma, 3, nis=True, cam_cov=True)
@@ -286,7 +287,7 @@ def test_frozen_replicas_are_frozen_logs_of_the_poses_they_consumed(model):
         assert np.array_equal(got.trajectory[b], want.trajectory[b]) and np.array_equal(got.nis[b], want.nis[b])
         assert np.array_equal(got.cam_cov[b], want.cam_cov[b])
         assert np.array_equal(batch.get_state(b)[CAM:], state[CAM:]) and np.array_equal(batch.get_cov(b)[CAM:, CAM:], p[CAM:, CAM:])
-    bu.same_snap(bu.snap(batch), bu.snap(twin), "replicas")
+    sp.assert_same(sp.snap_batch(batch), sp.snap_batch(twin), "replicas", equal_nan=True)
     assert not np.array_equal(got.trajectory[0], got.trajectory[1])
 
 
@@ -321,7 +322,7 @@ def test_frozen_corner_replicas_are_frozen_logs_of_the_poses_they_consumed():
     for b in range(MEMBERS):
         assert np.array_equal(got.trajectory[b], want.trajectory[b]) and np.array_equal(got.nis[b], want.nis[b])
         assert np.array_equal(batch.get_state(b)[CAM:], state[CAM:]) and np.array_equal(batch.get_cov(b)[CAM:, CAM:], p[CAM:, CAM:])
-    bu.same_snap(bu.snap(batch), bu.snap(twin), "corner replicas")
+    sp.assert_same(sp.snap_batch(batch), sp.snap_batch(twin), "corner replicas", equal_nan=True)
 
 
 # ---- 5. freeze -> unfreeze ------------------------------------------------------------------------------------------------------
@@ -339,14 +340,14 @@ def test_unfreezing_continues_like_a_restored_member(family):
     batch.unfreeze_map()
     assert not batch.map_frozen.any()
     twin = bu.batch(model, family, 8, 8)
-    for b, (s, p) in enumerate(bu.snap(batch)):
+    for b, (s, p) in enumerate(sp.snap_batch(batch)):
         twin.set_member(b, s, p, [i for i, _ in sorted(batch.landmarks[b].items(), key=lambda kv: kv[1])])
     rest = [bu.part(log, 12, 30) for log in logs]
     got, want = batch.process_detection_logs(rest), twin.process_detection_logs(rest)
     assert batch.num_landmarks == twin.num_landmarks == [8] * MEMBERS and batch.status() == [0] * MEMBERS
     for b in range(MEMBERS):
         assert np.array_equal(got[b], want[b]), b
-    bu.same_snap(bu.snap(batch), bu.snap(twin), "unfrozen")
+    sp.assert_same(sp.snap_batch(batch), sp.snap_batch(twin), "unfrozen", equal_nan=True)
 
 
 # ---- 6. first sightings -----------------------------------------------------------------------------------------------------------
@@ -358,7 +359,7 @@ def test_a_frozen_member_refuses_first_sightings(family):
     batch = bu.batch("ekf", family, n, m)
     _restore(batch, priors)
     batch.freeze_map(2)
-    before, counts = bu.snap(batch), batch._num_landmarks_device().tolist()
+    before, counts = sp.snap_batch(batch), batch._num_landmarks_device().tolist()
     idx = np.concatenate([f["ids"] for f in frames]).astype(np.int32)
     poses = np.vstack([f["poses"] for f in frames])
     fo, mf = np.arange(MEMBERS + 1) * m, np.arange(MEMBERS + 1)
@@ -367,7 +368,7 @@ def test_a_frozen_member_refuses_first_sightings(family):
     with pytest.raises(EkfError) as err:
         batch.observe_indexed(bad, fo, mf, poses)
     assert err.value.code == -4 and "frozen" in str(err.value)      # EKF_ERR_STATE
-    bu.same_snap(bu.snap(batch), before, "refused call")
+    sp.assert_same(sp.snap_batch(batch), before, "refused call", equal_nan=True)
     assert batch._num_landmarks_device().tolist() == counts and batch.status() == [0] * MEMBERS
     assert batch.map_frozen.tolist() == [False, False, True, False]
     bad = idx.copy()
@@ -386,7 +387,7 @@ def test_a_frozen_member_refuses_first_sightings(family):
     assert batch.last_ignored == [(900 + b,) for b in range(MEMBERS)] and batch.num_landmarks == [5] * MEMBERS
     for b in range(MEMBERS):
         assert np.isnan(out.mahal[b][b % m]) and np.isfinite(np.delete(out.mahal[b], b % m)).all() and not out.rejected[b].any()
-    bu.same_snap(bu.snap(batch), bu.snap(twin), "dropped row")
+    sp.assert_same(sp.snap_batch(batch), sp.snap_batch(twin), "dropped row", equal_nan=True)
 
 
 # ---- 7. a frozen member that fails -------------------------------------------------------------------------------------------------

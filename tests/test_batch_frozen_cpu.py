@@ -11,25 +11,17 @@ import numpy as np
 import pytest
 
 import batch_frozen_util as bu
+import support as sp
 from conftest import GOLDEN, REPO
+from support import lib
 
 NEW_SYMBOLS = ("ekf_batch_set_map_frozen", "ekf_batch_get_map_frozen")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_and_exported(lib):
-    from aruco_slam_amd import hip_backend
-    header = (REPO / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     assert "Localisation mode of a batch" in header and "(single filter)" not in header
     # no handle: EKF_ERR_INVALID, nothing touched
     out = np.zeros(4, np.int32)

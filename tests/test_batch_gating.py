@@ -9,30 +9,13 @@ import numpy as np
 import pytest
 
 import gating_util as gu
+import support as sp
 from conftest import report
 
 pytestmark = pytest.mark.gpu
 
 INIT = gu.INIT
 ALL = list(gu.FAMILIES)
-
-
-def _batch(members, model, family, **extra):
-    from aruco_slam_amd.batch import EKFBatch
-    kw = dict(gu.FAMILIES[(model, family)][0])
-    kw.update(extra)
-    return EKFBatch(members, INIT, model=model, **kw)
-
-
-def _snap(batch):
-    return [(batch.get_state(b), batch.get_cov(b)) for b in range(batch.members)]
-
-
-def _same_snap(a, b, what):
-    assert len(a) == len(b), what
-    for x, y in zip(a, b):
-        for u, v in zip(x, y):
-            assert np.array_equal(u, v, equal_nan=True), what
 
 
 def _same_outputs(got, want, what):
@@ -45,7 +28,7 @@ def _digest(batch, out):
     h = hashlib.sha256()
     for t in out:
         h.update(np.ascontiguousarray(t).tobytes())
-    for s, p in _snap(batch):
+    for s, p in sp.snap_batch(batch):
         h.update(s.tobytes())
         h.update(p.tobytes())
     return h.hexdigest()[:16]
@@ -66,14 +49,14 @@ PARENT_DIGESTS = {
 @pytest.mark.parametrize("model,family", ALL)
 def test_off_is_off(model, family):
     logs = [gu.dirty_log(model, gu.clean_log(model, family, seed=s), seed=s)[0] for s in range(3)] + [None]
-    plain = _batch(4, model, family)
+    plain = sp.family_batch(4, model, family)
     want = plain.process_detection_logs(logs, nis=True, cam_cov=True)
     for name, kw, call in (("gate=None", {"gate": None}, {}), ("gate=inf", {"gate": np.inf}, {}),
                            ("mahal only", {}, {"mahal": True})):
-        batch = _batch(4, model, family, **kw)
+        batch = sp.family_batch(4, model, family, **kw)
         got = batch.process_detection_logs(logs, nis=True, cam_cov=True, **call)
         _same_outputs(got, want, name)
-        _same_snap(_snap(batch), _snap(plain), name)
+        sp.assert_same(sp.snap_batch(batch), sp.snap_batch(plain), name, equal_nan=True)
         assert batch.status() == plain.status() and batch.landmarks == plain.landmarks, name
         if name != "gate=None":
             assert not any(r.any() for r in got.rejected), name
@@ -94,7 +77,7 @@ def test_only_the_first_occurrence_of_a_new_landmark_is_exempt(model, family):
     poses = np.vstack((log["poses"][:n0], log["poses"][:2] + np.array([0.3, -0.2, 0.1, 0, 0, 0])))
     frame = {"ids": ids.astype(np.int32), "poses": poses, "offsets": np.array([0, n0 + 2], np.int64)}
     for gate, rejected in ((None, False), (1e-6, True)):
-        out = _batch(1, model, family, gate=gate).process_detection_logs([frame], mahal=True)
+        out = sp.family_batch(1, model, family, gate=gate).process_detection_logs([frame], mahal=True)
         assert (out.mahal[0][:n0] == 0).all() and not out.rejected[0][:n0].any()
         assert np.isfinite(out.mahal[0][n0:]).all() and (out.mahal[0][n0:] > 1e-6).all()
         assert out.rejected[0][n0:].all() == rejected and out.dof[0][0] == gu.RD[model] * (n0 if rejected else n0 + 2)
@@ -105,11 +88,11 @@ def test_a_256_member_batch_hashes_as_before_the_gate(model, family):
     """The digest of trajectories, states and covariances of 256 members, gate off, is the one the library of the commit
     before the gate gave on an MI355X for the same logs (PARENT_DIGESTS, also in DESIGN 4.7.5)."""
     logs = [gu.clean_log(model, family, seed=s % 8) for s in range(256)]
-    batch = _batch(256, model, family)
+    batch = sp.family_batch(256, model, family)
     digest = _digest(batch, batch.process_detection_logs(logs))
     report(f"gating_hash_{model}_{family}", digest=digest)
     assert digest == PARENT_DIGESTS[(model, family)]
-    gated = _batch(256, model, family, gate=np.inf)
+    gated = sp.family_batch(256, model, family, gate=np.inf)
     assert _digest(gated, gated.process_detection_logs(logs).trajectory) == digest
 
 
@@ -119,7 +102,7 @@ def test_gated_replay_is_the_replay_of_the_log_without_the_rejected(model, famil
     logs, marks = zip(*(gu.dirty_log(model, gu.clean_log(model, family, seed=s), seed=s) for s in range(3)))
     # member 3: a tight gate that also rejects ordinary detections, so what is deleted is the device's own choice
     logs, gates = list(logs) + [logs[0]], np.array([gate, gate, gate, 1e-3])
-    gated = _batch(4, model, family, gate=gates)
+    gated = sp.family_batch(4, model, family, gate=gates)
     got = gated.process_detection_logs(logs, nis=True, cam_cov=True)
     assert gated.status() == [0] * 4
     for b in range(3):
@@ -130,10 +113,10 @@ def test_gated_replay_is_the_replay_of_the_log_without_the_rejected(model, famil
         offs = logs[0]["offsets"]
         assert any(offs[t + 1] - offs[t] > block and got.rejected[0][offs[t]:offs[t] + block].any()
                    for t in range(len(offs) - 1))
-    plain = _batch(4, model, family)
+    plain = sp.family_batch(4, model, family)
     want = plain.process_detection_logs([gu.delete(lg, rj) for lg, rj in zip(logs, got.rejected)], nis=True, cam_cov=True)
     _same_outputs(got, want, "deleted log")
-    _same_snap(_snap(gated), _snap(plain), "state / P")
+    sp.assert_same(sp.snap_batch(gated), sp.snap_batch(plain), "state / P", equal_nan=True)
     assert gated.landmarks == plain.landmarks and gated.num_landmarks == plain.num_landmarks
     # frames without a survivor are not stepped
     offs = logs[0]["offsets"]
@@ -181,15 +164,15 @@ def test_outliers_go_and_inliers_stay(model, family):
     clean = gu.clean_log(model, family, seed=0)
     dirty, marks = gu.dirty_log(model, clean, seed=0)
     empty = gu.extra_frames(dirty, marks)          # (the frames the dirty log has more: they are not stepped)
-    gated, loose, ref = (_batch(1, model, family, gate=gu.GATES[model]), _batch(1, model, family),
-                         _batch(1, model, family))
+    gated, loose, ref = (sp.family_batch(1, model, family, gate=gu.GATES[model]), sp.family_batch(1, model, family),
+                         sp.family_batch(1, model, family))
     got = gated.process_detection_logs([dirty], nis=True, cam_cov=True)
     bent = loose.process_detection_logs([dirty], nis=True, cam_cov=True)
     want = ref.process_detection_logs([clean], nis=True, cam_cov=True)
     assert np.array_equal(got.rejected[0], marks)
     for name in ("trajectory", "nis", "cam_cov", "dof"):
         assert np.array_equal(getattr(got, name)[0][~empty], getattr(want, name)[0]), name
-    _same_snap(_snap(gated), _snap(ref), "gated(dirty) = ungated(clean)")
+    sp.assert_same(sp.snap_batch(gated), sp.snap_batch(ref), "gated(dirty) = ungated(clean)", equal_nan=True)
     assert not np.array_equal(bent.trajectory[0][~empty], want.trajectory[0])
 
 
@@ -197,15 +180,15 @@ def test_neighbours_do_not_matter():
     model, family = "ekf", "column"
     log = gu.dirty_log(model, gu.clean_log(model, family, seed=1), seed=1)[0]
     gates = np.array([gu.GATES[model], np.inf, 1e-3, 50.0])
-    whole = _batch(4, model, family, gate=gates)
+    whole = sp.family_batch(4, model, family, gate=gates)
     got = whole.process_detection_logs([log] * 4, nis=True, cam_cov=True)
-    snap = _snap(whole)
+    snap = sp.snap_batch(whole)
     for b in range(4):
-        alone = _batch(1, model, family, gate=gates[b])
+        alone = sp.family_batch(1, model, family, gate=gates[b])
         one = alone.process_detection_logs([log], nis=True, cam_cov=True)
         for name in ("trajectory", "nis", "cam_cov", "dof", "mahal", "rejected"):
             assert np.array_equal(getattr(one, name)[0], getattr(got, name)[b], equal_nan=True), (b, name)
-        _same_snap(_snap(alone), snap[b:b + 1], b)
+        sp.assert_same(sp.snap_batch(alone), snap[b:b + 1], b, equal_nan=True)
     assert len({r.sum() for r in got.rejected}) >= 3
 
 
@@ -255,15 +238,15 @@ def test_replicas_with_a_gate_equal_explicit_logs(model, family):
     log = gu.dirty_log(model, gu.clean_log(model, family, seed=3), seed=3)[0]
     gates = np.array([gu.GATES[model], 2.0, np.inf, gu.GATES[model]])
     sigma = np.random.default_rng(2).uniform(0.002, 0.02, (B, 6))
-    batch = _batch(B, model, family, gate=gates)
+    batch = sp.family_batch(B, model, family, gate=gates)
     got = batch.replay_replicas(log, sigma, seed, nis=True, cam_cov=True)
     assert isinstance(got, GatedReplicaReplay)
     poses = replica_poses(log["poses"], sigma, seed)
-    explicit = _batch(B, model, family, gate=gates)
+    explicit = sp.family_batch(B, model, family, gate=gates)
     want = explicit.process_detection_logs([dict(log, poses=poses[b]) for b in range(B)], nis=True, cam_cov=True)
     for name in ("trajectory", "nis", "cam_cov", "dof", "mahal", "rejected"):
         assert np.array_equal(getattr(got, name), np.stack(getattr(want, name)), equal_nan=True), name
-    _same_snap(_snap(batch), _snap(explicit), "state / P")
+    sp.assert_same(sp.snap_batch(batch), sp.snap_batch(explicit), "state / P", equal_nan=True)
     assert got.rejected.any() and not got.rejected[2].any()
 
 
@@ -276,7 +259,7 @@ def test_failing_member_and_bad_gates():
              "offsets": lg["offsets"][:9]} for lg in logs]
     rest = [{"ids": lg["ids"][lg["offsets"][8]:], "poses": lg["poses"][lg["offsets"][8]:],
              "offsets": lg["offsets"][8:] - lg["offsets"][8]} for lg in logs]
-    ref, bad = _batch(3, model, family, gate=gu.GATES[model]), _batch(3, model, family, gate=gu.GATES[model])
+    ref, bad = sp.family_batch(3, model, family, gate=gu.GATES[model]), sp.family_batch(3, model, family, gate=gu.GATES[model])
     for batch in (ref, bad):
         batch.process_detection_logs(boot)
     ids = [k for k, _ in sorted(bad.landmarks[1].items(), key=lambda kv: kv[1])]
@@ -293,7 +276,7 @@ def test_failing_member_and_bad_gates():
         for name in ("trajectory", "nis", "dof", "mahal", "rejected"):
             assert np.array_equal(getattr(got, name)[b], getattr(want, name)[b], equal_nan=True), (b, name)
     # a joint S that is not positive definite under S_d that are: the failing frame keeps its distances, later ones NaN
-    late = _batch(1, model, family)
+    late = sp.family_batch(1, model, family)
     late.process_detection_logs(boot[:1])
     ids = [k for k, _ in sorted(late.landmarks[0].items(), key=lambda kv: kv[1])]
     s0 = late.get_state(0)
@@ -305,15 +288,15 @@ def test_failing_member_and_bad_gates():
     assert late.status() == [EKF_ERR_NUMERIC]
     assert np.isfinite(out.mahal[0][:2]).all() and (out.mahal[0][:2] > 0).all() and np.isnan(out.mahal[0][2:]).all()
     # bad gates raise before anything runs, and no member changes
-    before, gate0 = _snap(ref), ref.gate.copy()
+    before, gate0 = sp.snap_batch(ref), ref.gate.copy()
     for g in (np.nan, 0.0, -3.0, -np.inf, [1.0, 2.0], [1.0, np.nan, 3.0]):
         with pytest.raises(ValueError):
             ref.set_gate(g)
         with pytest.raises(ValueError):
-            _batch(3, model, family, gate=g)
+            sp.family_batch(3, model, family, gate=g)
     nan = np.full(3, np.nan)
     assert ref.lib.ekf_batch_set_gate(ref.h, nan.ctypes.data_as(ctypes.POINTER(ctypes.c_double))) == -1
     assert np.array_equal(ref.gate, gate0)
-    _same_snap(before, _snap(ref), "bad gates")
+    sp.assert_same(before, sp.snap_batch(ref), "bad gates", equal_nan=True)
     assert isinstance(EkfError, type)
     ref.set_gate(gate0)

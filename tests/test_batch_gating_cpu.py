@@ -1,31 +1,18 @@
 """The per-detection chi-square gate of EKFBatch without a GPU: the new C ABI is declared and exported, every batch
 translation unit still compiles without scratch, VGPR spills or static LDS, the host side of ``gate`` / ``mahal``, and the
 fixtures of ``test_batch_gating.py``: no expected distance lies within the comparison margin of its threshold."""
-import re
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import gating_util as gu
-from test_batch_replicas_cpu import _host_batch, _kernel_resources
+import support as sp
+from support import lib
 
 NEW_SYMBOLS = ("ekf_batch_set_gate", "ekf_batch_observe_logs_gated", "ekf_batch_observe_replicas_gated")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_new_symbols_are_declared_and_exported(lib):
-    from aruco_slam_amd import hip_backend
-    header = (Path(__file__).resolve().parent.parent / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
     assert lib.ekf_batch_set_gate(None, None) == -1          # (no handle: EKF_ERR_INVALID, nothing touched)
 
 
@@ -36,12 +23,12 @@ def test_new_symbols_are_declared_and_exported(lib):
     ("ekf_batch_wide.hip", r"ekf_batch_one_block_(rot_)?window_kernel", 2),
 ])
 def test_gated_kernels_use_no_scratch_no_spill_no_static_lds(src, pattern, count):
-    text = (Path(__file__).resolve().parent.parent / "aruco_slam_amd" / "csrc" / "ekf_batch_impl.h").read_text()
+    text = (sp.REPO / "aruco_slam_amd" / "csrc" / "ekf_batch_impl.h").read_text()
     assert "ekf_batch_gate" in text          # (the kernels compiled here hold the gate stage)
-    found = _kernel_resources(src, pattern)
+    found = sp.kernel_resources(src, pattern)
     assert len(found) == count, found
     for name, res in found.items():
-        assert res == {"private_segment_fixed_size": 0, "vgpr_spill_count": 0, "group_segment_fixed_size": 0}, (name, res)
+        assert [res[k] for k in sp.BUDGET_FIELDS] == [0, 0, 0], (name, res)
 
 
 def test_gate_array_shapes_and_values():
@@ -56,7 +43,7 @@ def test_gate_array_shapes_and_values():
 
 def test_process_detection_logs_returns_the_gated_type_only_when_asked():
     from aruco_slam_amd.batch import BatchReplay, GatedBatchReplay
-    batch = _host_batch(2, "ekf")
+    batch = sp.host_batch(2, "ekf")
     assert batch.gate is None          # (the class default: a batch has no gate until set_gate)
     plain = batch.observe_indexed
 

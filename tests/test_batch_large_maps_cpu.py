@@ -2,20 +2,19 @@
 the workspace it adds, the LDS budget of a large-map call and the Python choice of the flag."""
 import ctypes
 import re
-from pathlib import Path
 
 import pytest
 
+import support as sp
+
 
 def _lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend, hip_backend.load_library()
+    from aruco_slam_amd import hip_backend
+    return hip_backend, sp.load_lib()
 
 
 def _config(hb, lib, model, large=True, **fields):
-    cfg = hb.EkfConfig()
-    lib.ekf_default_config(ctypes.byref(cfg))
+    cfg = sp.config(lib)
     if model == 1:
         cfg.model, cfg.quat_mode, cfg.max_landmarks, cfg.max_visible = 1, hb.EKF_QUAT_SCALAR_FIRST, 101, 8
     else:
@@ -27,24 +26,17 @@ def _config(hb, lib, model, large=True, **fields):
     return cfg
 
 
-def _sizes(lib, cfg, members=4):
-    ld, cov, state, ws = ctypes.c_int64(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-    rc = lib.ekf_batch_query_sizes(ctypes.byref(cfg), members, ctypes.byref(ld), ctypes.byref(cov), ctypes.byref(state),
-                                   ctypes.byref(ws))
-    return rc, ld.value, cov.value, state.value, ws.value
-
-
 def test_flag_value():
     from aruco_slam_amd import hip_backend
     assert hip_backend.EKF_FLAG_BATCH_LARGE_MAPS == 16
-    header = (Path(__file__).resolve().parent.parent / "include" / "ekf_slam_hip.h").read_text()
+    header = sp.HEADER.read_text()
     assert re.search(r"EKF_FLAG_BATCH_LARGE_MAPS = 16\b", header)
 
 
 @pytest.mark.parametrize("model", [0, 1])
 def test_large_map_limits_are_checked(model):
     hb, lib = _lib()
-    rc, ld, cov, state, _ = _sizes(lib, _config(hb, lib, model))
+    rc, ld, cov, state, _ = sp.batch_query_sizes(lib, _config(hb, lib, model))
     assert rc == 0, lib.ekf_last_error_string()
     assert ld == 1024                       # EKF: N = 3 * 338 + 10 = 1024; EKF_Rotations: N = 10 * 101 + 10 = 1020
     assert cov == 4 * 1024 * 1024 * 8 and state == 4 * 1024 * 8
@@ -61,7 +53,7 @@ def test_large_map_limits_are_checked(model):
         assert lib.ekf_batch_create(ctypes.byref(bad), 4, ctypes.byref(handle)) == -1 and not handle.value, field
     # a map that the one-column kernel holds passes with the flag too, at that kernel's ld
     small = _config(hb, lib, model, max_landmarks=82 if model == 0 else 24)
-    assert _sizes(lib, small)[:2] == (0, 256)
+    assert sp.batch_query_sizes(lib, small)[:2] == (0, 256)
 
 
 @pytest.mark.parametrize("model", [0, 1])
@@ -74,14 +66,14 @@ def test_without_the_flag_nothing_changes(model):
     assert b"max_landmarks" in msg and (b"1..82" in msg if model == 0 else b"1..24" in msg), msg
     # workspace_bytes grows with the flag only: by members * rd * max_visible * ld * 8 (and its alignment)
     for lm in ((10, 82) if model == 0 else (3, 24)):
-        plain = _sizes(lib, _config(hb, lib, model, large=False, max_landmarks=lm))
-        large = _sizes(lib, _config(hb, lib, model, max_landmarks=lm))
+        plain = sp.batch_query_sizes(lib, _config(hb, lib, model, large=False, max_landmarks=lm))
+        large = sp.batch_query_sizes(lib, _config(hb, lib, model, max_landmarks=lm))
         assert plain[0] == large[0] == 0 and plain[1:4] == large[1:4]
         rd, vis, ld = (3, 16, plain[1]) if model == 0 else (7, 8, plain[1])
         w = 4 * rd * vis * ld * 8
         assert w <= large[4] - plain[4] < w + 256, (plain, large)
     # at the largest map: at most about 450 KiB of A / W per member
-    big = _sizes(lib, _config(hb, lib, model), members=1)
+    big = sp.batch_query_sizes(lib, _config(hb, lib, model), members=1)
     assert big[4] <= 460 * 1024 + 4096
 
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import motion_util as mu
+import support as sp
 import update_sweep_util as sw
 from conftest import rel_err, report
 
@@ -28,16 +29,6 @@ def _batch(model, family, n, m, **kw):
     return EKFBatch(MEMBERS, INIT, model=model, max_landmarks=n, max_visible=m, **FAMILY[family], **kw)
 
 
-def _snap(batch):
-    return [(batch.get_state(b), batch.get_cov(b)) for b in range(batch.members)]
-
-
-def _same_snap(a, b, what):
-    for x, y in zip(a, b):
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and np.array_equal(u, v, equal_nan=True), what
-
-
 def _logs(model):
     return [mu.ragged_motion_log(QM[model], seed=5 + b, step=STEPS[b]) for b in range(MEMBERS)]
 
@@ -55,7 +46,7 @@ def test_three_kernels_agree_bitwise_and_a_member_is_its_per_frame_calls(model):
     outs = {}
     for family in FAMILY:
         batch = _batch(model, family, n, m)
-        outs[family] = (batch.process_detection_logs(logs, nis=True, cam_cov=True), _snap(batch))
+        outs[family] = (batch.process_detection_logs(logs, nis=True, cam_cov=True), sp.snap_batch(batch))
         assert batch.status() == [0] * MEMBERS
     want, want_snap = outs["column"]
     for family in ("large", "wide"):
@@ -63,7 +54,7 @@ def test_three_kernels_agree_bitwise_and_a_member_is_its_per_frame_calls(model):
         for name in ("trajectory", "nis", "cam_cov"):
             for b in range(MEMBERS):
                 assert np.array_equal(getattr(got, name)[b], getattr(want, name)[b]), (family, name, b)
-        _same_snap(snap, want_snap, family)
+        sp.assert_same(snap, want_snap, family, equal_nan=True)
     # frame by frame
     loop = _batch(model, "column", n, m)
     frames = len(logs[0]["offsets"]) - 1
@@ -76,7 +67,7 @@ def test_three_kernels_agree_bitwise_and_a_member_is_its_per_frame_calls(model):
                         "offsets": np.array([0, sl.stop - sl.start], np.int64), "motion": log["motion"][t:t + 1]})
         for b, tr in enumerate(loop.process_detection_logs(one)):
             rows[b].append(tr[0])
-    _same_snap(_snap(loop), want_snap, "per-frame calls")
+    sp.assert_same(sp.snap_batch(loop), want_snap, "per-frame calls", equal_nan=True)
     for b, log in enumerate(logs):
         traj = want.trajectory[b]
         assert np.array_equal(np.array(rows[b]), traj), b
@@ -94,7 +85,7 @@ def test_three_kernels_agree_bitwise_and_a_member_is_its_per_frame_calls(model):
     t_zero, t_bare = plain.process_detection_logs(zeros), bare.process_detection_logs(stripped)
     for b in range(MEMBERS):
         assert np.array_equal(t_zero[b], t_bare[b]) and not np.array_equal(t_zero[b], want.trajectory[b])
-    _same_snap(_snap(plain), _snap(bare), "zero motions = no motions")
+    sp.assert_same(sp.snap_batch(plain), sp.snap_batch(bare), "zero motions = no motions", equal_nan=True)
 
 
 # ---- one move per kernel against the extended form ----------------------------------------------------------------------------
@@ -133,7 +124,7 @@ def test_one_move_per_kernel_against_the_extended_reference(model, family):
         batch.process_detection_logs(frames)
         twin.process_detection_logs([dict(f, motion=mv["motion"]) for f, mv in zip(frames, moves)])
         assert batch.status() == twin.status() == [0] * MEMBERS
-        _same_snap(_snap(batch), _snap(twin), (n, m))
+        sp.assert_same(sp.snap_batch(batch), sp.snap_batch(twin), (n, m), equal_nan=True)
     report(f"motion_batch_step[{model},{family}]", ratio_P=worst[0], ratio_c=worst[1], ratio_q=worst[2], bound=1.0)
     assert worst.max() <= 1.0, worst
 
@@ -167,7 +158,7 @@ def test_motion_arguments_of_the_batch_are_validated():
         bare.observe_indexed(np.zeros(0, np.int32), np.zeros(1, np.int64), np.zeros(MEMBERS + 1, np.int64), np.zeros((0, 6)),
                              motion=np.zeros((0, 6)))
     batch = _batch("ekf", "column", 8, 8)
-    before = _snap(batch)
+    before = sp.snap_batch(batch)
     partial = [dict(log) for log in logs]
     del partial[1]["motion"]
     with pytest.raises(ValueError, match="every log"):
@@ -175,7 +166,7 @@ def test_motion_arguments_of_the_batch_are_validated():
     for bad in (logs[0]["motion"][:-1], np.full_like(logs[0]["motion"], np.nan)):
         with pytest.raises(ValueError, match="motion"):
             batch.process_detection_logs([dict(logs[0], motion=bad)] + logs[1:])
-    _same_snap(_snap(batch), before, "nothing changed")
+    sp.assert_same(sp.snap_batch(batch), before, "nothing changed", equal_nan=True)
     assert all(len(lm) == 0 for lm in batch.landmarks)
     # to_filter / load_filter carry the capability
     batch.process_detection_logs(logs)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import replica_util as ru
+import support as sp
 from conftest import load_npz, rel_err_elem, report
 
 pytestmark = pytest.mark.gpu
@@ -40,24 +41,6 @@ def _family(model, family, members, steady=30, seed=0):
     return _batch(members, model, **kw), _ragged(model, n, m_range, steady, seed)
 
 
-def _snap(batch):
-    return [(batch.get_state(b), batch.get_cov(b)) for b in range(batch.members)]
-
-
-def _assert_same(a, b, what):
-    assert len(a) == len(b), what
-    for x, y in zip(a, b):
-        for u, v in zip(x, y):
-            assert np.array_equal(u, v, equal_nan=True), what
-
-
-def _sub(log, t0, t1):
-    offs = log["offsets"]
-    d0, d1 = int(offs[t0]), int(offs[t1])
-    return {"ids": log["ids"][d0:d1], "poses": log["poses"][d0:d1], "offsets": offs[t0:t1 + 1] - d0,
-            "has_detections": log["has_detections"][t0:t1]}
-
-
 @pytest.mark.parametrize("model,family", list(FAMILIES))
 def test_outputs_do_not_change_the_bits(model, family):
     kw, n, m_range = FAMILIES[(model, family)]
@@ -68,7 +51,7 @@ def test_outputs_do_not_change_the_bits(model, family):
     assert plain.status() == diag.status() == [0] * 6
     for a, b in zip(t_plain, out.trajectory):
         assert np.array_equal(a, b)
-    _assert_same(_snap(plain), _snap(diag), "state / P")
+    sp.assert_same(sp.snap_batch(plain), sp.snap_batch(diag), "state / P", equal_nan=True)
     for b in range(5):
         # (a bootstrap frame only first-sights its landmarks: each is placed at its detection, so z - h = 0 and NIS = 0)
         boot = logs[b]["bootstrap_frames"]
@@ -94,7 +77,7 @@ def test_replicas_equal_explicit_logs_of_their_poses(model, family):
     assert np.array_equal(got.nis, np.stack(want.nis))
     assert np.array_equal(got.cam_cov, np.stack(want.cam_cov))
     assert np.array_equal(got.dof, want.dof[0])
-    _assert_same(_snap(batch), _snap(explicit), "state / P")
+    sp.assert_same(sp.snap_batch(batch), sp.snap_batch(explicit), "state / P", equal_nan=True)
     assert batch.landmarks == explicit.landmarks
     # replicas differ from each other (sigma > 0)
     assert not np.array_equal(got.trajectory[0], got.trajectory[1])
@@ -109,7 +92,7 @@ def test_zero_sigma_is_the_plain_log_replay(model):
     want = plain.process_detection_logs([log] * B, nis=True, cam_cov=True)
     assert np.array_equal(got.trajectory, np.stack(want.trajectory))
     assert np.array_equal(got.nis, np.stack(want.nis)) and np.array_equal(got.cam_cov, np.stack(want.cam_cov))
-    _assert_same(_snap(batch), _snap(plain), "state / P")
+    sp.assert_same(sp.snap_batch(batch), sp.snap_batch(plain), "state / P", equal_nan=True)
 
 
 def test_replica_identity_across_batch_sizes_and_calls():
@@ -121,13 +104,13 @@ def test_replica_identity_across_batch_sizes_and_calls():
     for r0 in (0, 8, 4):
         part, _ = _family("ekf", "column", 8)
         parts.append(part.replay_replicas(log, sigma[r0:r0 + 8], seed, first_replica=r0, nis=True, cam_cov=True))
-        snaps.append(_snap(part))
-    big_snap = _snap(big)
+        snaps.append(sp.snap_batch(part))
+    big_snap = sp.snap_batch(big)
     for (r0, part, snap) in zip((0, 8, 4), parts, snaps):
         sl = slice(r0, r0 + 8)
         assert np.array_equal(part.trajectory, whole.trajectory[sl])
         assert np.array_equal(part.nis, whole.nis[sl]) and np.array_equal(part.cam_cov, whole.cam_cov[sl])
-        _assert_same(snap, big_snap[sl], f"members {r0}..{r0 + 7}")
+        sp.assert_same(snap, big_snap[sl], f"members {r0}..{r0 + 7}", equal_nan=True)
 
 
 def test_device_normals_match_the_mirror_and_are_standard_normal():
@@ -237,15 +220,15 @@ def test_cam_cov_is_the_covariance_after_each_frame(model, family):
     whole = _batch(1, model, **kw).process_detection_logs([log], cam_cov=True)
     step = _batch(1, model, **kw)
     for t in range(F):
-        step.process_detection_logs([_sub(log, t, t + 1)])
+        step.process_detection_logs([sp.sub_log(log, t, t + 1)])
         assert np.array_equal(whole.cam_cov[0][t], step.get_cov(0)[:10, :10]), t
 
 
 def test_empty_frames_and_failing_members():
     from aruco_slam_amd.batch import EKF_ERR_NUMERIC
     logs = [_ragged("ekf", 20, (1, 8), 30, seed=s) for s in range(4)]
-    boot = [_sub(lg, 0, 10) for lg in logs]
-    rest = [_sub(lg, 10, len(lg["offsets"]) - 1) for lg in logs]
+    boot = [sp.sub_log(lg, 0, 10) for lg in logs]
+    rest = [sp.sub_log(lg, 10, len(lg["offsets"]) - 1) for lg in logs]
     # empty frames: a leading one, and two in the middle
     lg = rest[0]
     offs = lg["offsets"]
@@ -279,8 +262,8 @@ def test_empty_frames_and_failing_members():
 def test_bad_replica_arguments_raise_before_anything_runs():
     from aruco_slam_amd.hip_backend import EkfError
     batch, log = _family("ekf", "column", 3, steady=5, seed=2)
-    batch.replay_replicas(_sub(log, 0, 4), 0.01, 1)
-    before, tables = _snap(batch), [dict(t) for t in batch.landmarks]
+    batch.replay_replicas(sp.sub_log(log, 0, 4), 0.01, 1)
+    before, tables = sp.snap_batch(batch), [dict(t) for t in batch.landmarks]
     wide = _ragged("ekf", 40, (20, 30), 2, seed=4)
     cases = [
         ("negative", lambda: batch.replay_replicas(log, -0.1, 1), ValueError),
@@ -295,10 +278,10 @@ def test_bad_replica_arguments_raise_before_anything_runs():
         if exc is EkfError:
             assert info.value.code == -2, name
         assert batch.landmarks == tables, name
-        _assert_same(before, _snap(batch), name)
+        sp.assert_same(before, sp.snap_batch(batch), name, equal_nan=True)
         assert batch.status() == [0, 0, 0]
     batch.reset(1)
     with pytest.raises(ValueError, match="landmark table"):
         batch.replay_replicas(log, 0.01, 1)
     assert batch.landmarks[0] == tables[0] and batch.num_landmarks[1] == 0
-    _assert_same(before[::2], _snap(batch)[::2], "unequal tables")
+    sp.assert_same(before[::2], sp.snap_batch(batch)[::2], "unequal tables", equal_nan=True)

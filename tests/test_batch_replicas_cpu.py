@@ -3,23 +3,16 @@ noise against the Philox4x32-10 known answers, the new C ABI (declared, exported
 register / LDS budget of the noise kernel and of the window kernels that write the new outputs, and the host side of
 ``replay_replicas`` / ``process_detection_logs(..., nis=, cam_cov=)``."""
 import ctypes
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import replica_util as ru
+import support as sp
+from support import lib
 
 NEW_SYMBOLS = ("ekf_batch_observe_logs_diag", "ekf_batch_replica_poses", "ekf_batch_replica_workspace_bytes",
                "ekf_batch_observe_replicas")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
 
 
 @pytest.mark.parametrize("counter,key,want", [
@@ -41,12 +34,7 @@ def test_mirror_noise_is_per_replica_and_detection():
 
 
 def test_new_symbols_are_declared_and_exported(lib):
-    from pathlib import Path
-    from aruco_slam_amd import hip_backend
-    header = (Path(__file__).resolve().parent.parent / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
 
 
 def test_replica_poses_validates_before_any_device_work(lib):
@@ -70,26 +58,6 @@ def test_replica_poses_validates_before_any_device_work(lib):
     assert lib.ekf_batch_replica_workspace_bytes(None, 1, 1, ctypes.byref(ctypes.c_size_t())) == -1
 
 
-def _kernel_resources(src, pattern):
-    from aruco_slam_amd import _build
-    import tempfile
-    from pathlib import Path
-    with tempfile.TemporaryDirectory() as tmp:
-        out = Path(tmp) / "k.s"
-        subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                        str(_build.CSRC / src), "-o", str(out)], check=True, capture_output=True)
-        text = out.read_text()
-    meta = text[text.index("amdhsa.kernels:"):text.index("amdhsa.target:")]
-    found = {}
-    for entry in re.split(r"\n  - ", meta)[1:]:        # one entry per kernel; its own fields are indented by 4
-        fields = dict(re.findall(r"^(?:  )?  \.([a-z_]+):\s+(\S+)", entry, re.M))
-        name = fields.get("name", "")
-        if re.search(pattern, name):
-            found[name] = {k: int(fields[k]) for k in ("private_segment_fixed_size", "vgpr_spill_count",
-                                                       "group_segment_fixed_size")}
-    return found
-
-
 @pytest.mark.parametrize("src,pattern,count", [
     ("ekf_batch_replicas.hip", r"ekf_replica_poses_kernel", 1),
     ("ekf_batch.hip", r"ekf_batch_window_kernel", 1),
@@ -99,10 +67,10 @@ def _kernel_resources(src, pattern):
 ])
 def test_kernels_use_no_scratch_no_spill_no_static_lds(src, pattern, count):
     """No scratch memory, no VGPR spills (SGPR spills go to VGPR lanes, as before these outputs), no static LDS."""
-    found = _kernel_resources(src, pattern)
+    found = sp.kernel_resources(src, pattern)
     assert len(found) == count, found
     for name, res in found.items():
-        assert res == {"private_segment_fixed_size": 0, "vgpr_spill_count": 0, "group_segment_fixed_size": 0}, (name, res)
+        assert [res[k] for k in sp.BUDGET_FIELDS] == [0, 0, 0], (name, res)
 
 
 def test_window_kernels_dynamic_lds_is_unchanged(lib):
@@ -136,34 +104,10 @@ def test_sigma_shapes_and_values():
             replica_sigma(bad, 4)
 
 
-def _host_batch(members=3, model="ekf"):
-    """An EKFBatch without device state: observe_indexed records what would reach the library."""
-    from aruco_slam_amd.batch import EKFBatch, LM_DIMS
-    batch = object.__new__(EKFBatch)
-    batch.members = members
-    batch.model = model
-    batch.lm_dims = LM_DIMS[model]
-    batch.landmarks = [{} for _ in range(members)]
-    batch.num_landmarks = [0] * members
-    batch.calls = []
-
-    def observe_indexed(index, frame_offsets, member_frames, poses, nis=False, cam_cov=False):
-        batch.calls.append((index, frame_offsets, member_frames, poses, nis, cam_cov))
-        f = int(member_frames[-1])
-        traj = np.zeros((f, 7))
-        if not (nis or cam_cov):
-            return traj
-        return traj, np.arange(f, dtype=np.float64) if nis else None, np.zeros((f, 10, 10)) if cam_cov else None
-
-    batch.observe_indexed = observe_indexed
-    batch._num_landmarks_device = lambda: np.zeros(members, dtype=np.int32)
-    return batch
-
-
 @pytest.mark.parametrize("model,rd", [("ekf", 3), ("ekf_rotations", 7)])
 def test_process_detection_logs_returns_per_member_statistics(model, rd):
     from aruco_slam_amd.batch import BatchReplay
-    batch = _host_batch(3, model)
+    batch = sp.host_batch(3, model)
     log = {"ids": np.array([4, 4, 9, 9], np.int32), "poses": np.zeros((4, 6)), "offsets": np.array([0, 2, 2, 4]),
            "has_detections": np.array([True, False, True])}
     plain = batch.process_detection_logs([log, None, log])
@@ -178,7 +122,7 @@ def test_process_detection_logs_returns_per_member_statistics(model, rd):
 
 
 def test_replay_replicas_checks_before_the_library():
-    batch = _host_batch(3)
+    batch = sp.host_batch(3)
     log = {"ids": np.array([1, 2], np.int32), "poses": np.zeros((2, 6)), "offsets": np.array([0, 1, 2])}
     batch.landmarks[1] = {5: 0}
     batch.num_landmarks[1] = 1

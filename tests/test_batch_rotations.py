@@ -5,6 +5,7 @@ interop with ``EKF_Rotations``."""
 import numpy as np
 import pytest
 
+import support as sp
 import update_sweep_util as sw
 from conftest import load_npz, rel_err, rel_err_elem, report
 
@@ -27,13 +28,6 @@ def _batch(members, **kw):
 def _frame_log(ids, poses):
     ids = np.asarray(ids, dtype=np.int32)
     return {"ids": ids, "poses": np.asarray(poses, dtype=np.float64), "offsets": np.array([0, len(ids)], dtype=np.int64)}
-
-
-def _sub(log, t0, t1):
-    offs = log["offsets"]
-    d0, d1 = int(offs[t0]), int(offs[t1])
-    return {"ids": log["ids"][d0:d1], "poses": log["poses"][d0:d1], "offsets": offs[t0:t1 + 1] - d0,
-            "has_detections": log["has_detections"][t0:t1]}
 
 
 def _ragged(n, m_range, steady, seed):
@@ -173,8 +167,8 @@ def test_continuation_across_calls_and_windows_is_bitwise():
     t_one = one.process_detection_logs([log, None])[0]
     two = _batch(2)
     cut = 100                                     # inside the second window
-    t_a = two.process_detection_logs([_sub(log, 0, cut), None])[0]
-    t_b = two.process_detection_logs([_sub(log, cut, frames), None])[0]
+    t_a = two.process_detection_logs([sp.sub_log(log, 0, cut), None])[0]
+    t_b = two.process_detection_logs([sp.sub_log(log, cut, frames), None])[0]
     assert np.array_equal(t_one, np.concatenate([t_a, t_b]))
     for a, b in zip(_snapshot(one, 0), _snapshot(two, 0)):
         assert np.array_equal(a, b)
@@ -271,7 +265,7 @@ def test_interop_with_ekf_rotations():
     assert np.array_equal(np.asarray(flt.state), batch.get_state(1)) and np.array_equal(flt.uncertainty, batch.get_cov(1))
     assert flt.landmarks == batch.landmarks[1] and flt.num_landmarks == batch.num_landmarks[1]
     # one more frame, in the filter and in the batch
-    nxt = _sub(_ragged(12, (1, 8), 3, seed=22), 3, 4)
+    nxt = sp.sub_log(_ragged(12, (1, 8), 3, seed=22), 3, 4)
     flt.observe(nxt["ids"], nxt["poses"])
     got = batch.process_detection_logs([None, nxt])[1][-1]
     assert rel_err(got, np.asarray(flt.state)[:7]) <= 1e-10

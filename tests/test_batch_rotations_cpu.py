@@ -3,29 +3,22 @@ Python argument checks of ``EKFBatch(model="ekf_rotations")`` and the register /
 kernel."""
 import ctypes
 import re
-import subprocess
-import tempfile
-from pathlib import Path
 
-import numpy as np
 import pytest
 
-INIT = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0])
+import support as sp
+
+INIT = sp.INIT
 
 
 def _lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend, hip_backend.load_library()
+    from aruco_slam_amd import hip_backend
+    return hip_backend, sp.load_lib()
 
 
 def _rot_config(hb, lib, **fields):
-    cfg = hb.EkfConfig()
-    lib.ekf_default_config(ctypes.byref(cfg))
-    cfg.model, cfg.quat_mode, cfg.max_landmarks, cfg.max_visible = 1, hb.EKF_QUAT_SCALAR_FIRST, 24, 8
-    for k, v in fields.items():
-        setattr(cfg, k, v)
-    return cfg
+    return sp.config(lib, **{"model": 1, "quat_mode": hb.EKF_QUAT_SCALAR_FIRST, "max_landmarks": 24, "max_visible": 8,
+                             **fields})
 
 
 def test_rotations_batch_config_limits_are_checked():
@@ -72,18 +65,10 @@ def test_rotations_batch_kernel_uses_no_scratch_and_fits_the_lds():
     requests for the largest rotations batch (k = 7 * 8 rows, A/W rows of round_up(10 * 24 + 10 + 1, 4)) fits the 160 KiB
     of a CU and grows with both arguments."""
     from aruco_slam_amd import _build
-    with tempfile.TemporaryDirectory() as tmp:
-        out = Path(tmp) / "batch_rot.s"
-        subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                        str(_build.CSRC / "ekf_batch_rot.hip"), "-o", str(out)], check=True, capture_output=True)
-        text = out.read_text()
-    names = re.findall(r"\.name:\s+(\S*_kernel\S*)\n", text)
+    found = sp.kernel_resources("ekf_batch_rot.hip")
+    names = list(found)
     assert len(names) == 1 and "ekf_batch_rot_window_kernel" in names[0], names
-    pat = r"\.name:\s+(\S*ekf_batch_rot_window_kernel\S*)\n(?:.*\n)*?\s+\.{}:\s+(\d+)"
-    for field in ("private_segment_fixed_size", "vgpr_spill_count"):
-        found = re.findall(pat.format(field), text)
-        assert len(found) == 1 and int(found[0][1]) == 0, (field, found)
-    assert re.findall(r"\.group_segment_fixed_size:\s+(\d+)", text) == ["0"]
+    assert [found[names[0]][k] for k in sp.BUDGET_FIELDS] == [0, 0, 0], found
     header = (_build.CSRC / "ekf_kernels.h").read_text()
     max_lm = int(re.search(r"#define EKF_BATCH_ROT_MAX_LANDMARKS (\d+)", header).group(1))
     max_vis = int(re.search(r"#define EKF_BATCH_ROT_MAX_VISIBLE (\d+)", header).group(1))

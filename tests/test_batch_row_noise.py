@@ -8,6 +8,7 @@ import pytest
 
 import gating_util as gu
 import row_noise_util as rn
+import support as sp
 import update_sweep_util as sw
 from conftest import load_npz, report
 
@@ -22,24 +23,6 @@ EXTRA = {"column": {}, "large": {"large_maps": True}, "wide": {"wide_frames": Tr
 # than one block of 16 / 8 detections
 STEP_MEMBERS = {"ekf": [(1, 1), (39, 3), (82, 8), (39, 16)], "ekf_rotations": [(1, 1), (12, 2), (24, 5), (12, 8)]}
 STEP_WIDE = {"ekf": [(40, 17), (40, 36)], "ekf_rotations": [(20, 9), (20, 18)]}
-
-
-def _batch(members, model, family, **extra):
-    from aruco_slam_amd.batch import EKFBatch
-    kw = dict(gu.FAMILIES[(model, family)][0])
-    kw.update(extra)
-    return EKFBatch(members, INIT, model=model, **kw)
-
-
-def _snap(batch):
-    return [(batch.get_state(b), batch.get_cov(b)) for b in range(batch.members)]
-
-
-def _same_snap(a, b, what):
-    assert len(a) == len(b), what
-    for x, y in zip(a, b):
-        for u, v in zip(x, y):
-            assert np.array_equal(u, v, equal_nan=True), what
 
 
 def _same_outputs(got, want, what, names=("trajectory", "nis", "cam_cov", "dof", "mahal", "rejected")):
@@ -62,14 +45,14 @@ def test_uniform_rows_are_the_members_constant_bit_for_bit(model, family):
     rd = gu.RD[model]
     noisy = [dict(lg, noise=np.full(len(lg["ids"]), c) if b % 2 else np.full((len(lg["ids"]), rd), c))
              for b, (lg, c) in enumerate(zip(logs[:3], consts))] + [logs[3]]
-    rows = _batch(4, model, family, row_noise=True)
+    rows = sp.family_batch(4, model, family, row_noise=True)
     got = rows.process_detection_logs(noisy, nis=True, cam_cov=True, mahal=True)
-    twin = _batch(4, model, family, noise={"r_uncertainty": consts})
+    twin = sp.family_batch(4, model, family, noise={"r_uncertainty": consts})
     want = twin.process_detection_logs(logs, nis=True, cam_cov=True, mahal=True)
     assert rows.status() == twin.status() == [0] * 4
     _same_outputs(got, want, "rows = c")
-    _same_snap(_snap(rows), _snap(twin), "rows = c")
-    plain = _batch(4, model, family)      # (the rows are not ignored)
+    sp.assert_same(sp.snap_batch(rows), sp.snap_batch(twin), "rows = c", equal_nan=True)
+    plain = sp.family_batch(4, model, family)      # (the rows are not ignored)
     assert not np.array_equal(plain.process_detection_logs(logs)[0], got.trajectory[0])
 
 
@@ -115,12 +98,12 @@ def test_large_and_wide_kernels_are_bitwise_the_one_column_kernel_with_rows(mode
         kw = dict(gu.FAMILIES[(model, "column")][0], gate=gu.GATES[model], row_noise=True)
         kw.update(EXTRA[family])
         batch = EKFBatch(2, INIT, model=model, **kw)
-        outs.append((batch.process_detection_logs(logs, nis=True, cam_cov=True), _snap(batch)))
+        outs.append((batch.process_detection_logs(logs, nis=True, cam_cov=True), sp.snap_batch(batch)))
         assert batch.status() == [0, 0]
     assert any(r.any() for r in outs[0][0].rejected)
     for family, (out, snap) in zip(("large", "wide"), outs[1:]):
         _same_outputs(out, outs[0][0], family)
-        _same_snap(snap, outs[0][1], family)
+        sp.assert_same(snap, outs[0][1], family, equal_nan=True)
 
 
 @pytest.mark.parametrize("model,family", ALL)
@@ -132,7 +115,7 @@ def test_a_one_member_batch_and_its_to_filter_give_the_same_distances(model, fam
     boot_frames = int(clean["bootstrap_frames"]) + 3
     end = int(clean["offsets"][boot_frames])
     head = {"ids": clean["ids"][:end], "poses": clean["poses"][:end], "offsets": clean["offsets"][:boot_frames + 1]}
-    batch = _batch(1, model, family, row_noise=True, gate=np.inf)
+    batch = sp.family_batch(1, model, family, row_noise=True, gate=np.inf)
     batch.process_detection_logs([_with_rows(model, head, 1)])
     flt, const = batch.to_filter(0), batch.to_filter(0)
     assert flt.backend.can_row_noise and flt.gate == np.inf
@@ -150,9 +133,9 @@ def test_a_one_member_batch_and_its_to_filter_give_the_same_distances(model, fam
 @pytest.mark.parametrize("model,family", ALL)
 def test_nis_and_cam_cov_come_with_rows_and_change_nothing_else(model, family):
     logs = [_with_rows(model, gu.clean_log(model, family, seed=s), s) for s in range(2)]
-    bare = _batch(2, model, family, row_noise=True)
+    bare = sp.family_batch(2, model, family, row_noise=True)
     traj = bare.process_detection_logs(logs)
-    full = _batch(2, model, family, row_noise=True)
+    full = sp.family_batch(2, model, family, row_noise=True)
     out = full.process_detection_logs(logs, nis=True, cam_cov=True, mahal=True)
     for b in range(2):
         assert np.array_equal(traj[b], out.trajectory[b])
@@ -163,9 +146,9 @@ def test_nis_and_cam_cov_come_with_rows_and_change_nothing_else(model, family):
         assert out.cam_cov[b].shape == (len(traj[b]), 10, 10) and np.isfinite(out.cam_cov[b]).all()
         assert np.array_equal(out.cam_cov[b][-1], full.get_cov(b)[:10, :10])
         assert np.isfinite(out.mahal[b]).all()
-    _same_snap(_snap(bare), _snap(full), "asking for outputs")
+    sp.assert_same(sp.snap_batch(bare), sp.snap_batch(full), "asking for outputs", equal_nan=True)
     # the rows matter: with rows ten times larger the steady frames' NIS per row is smaller
-    big = _batch(2, model, family, row_noise=True)
+    big = sp.family_batch(2, model, family, row_noise=True)
     out_big = big.process_detection_logs([dict(lg, noise=10.0 * lg["noise"]) for lg in logs], nis=True)
     t = int(logs[0]["bootstrap_frames"])
     assert 0 < out_big.nis[0][t:].sum() < out.nis[0][t:].sum()
@@ -174,10 +157,10 @@ def test_nis_and_cam_cov_come_with_rows_and_change_nothing_else(model, family):
 def test_noise_arguments_of_the_batch_are_validated():
     model, family = "ekf", "column"
     log = gu.clean_log(model, family, seed=0)
-    plain = _batch(1, model, family)
+    plain = sp.family_batch(1, model, family)
     with pytest.raises(ValueError, match="row_noise=True"):
         plain.process_detection_logs([dict(log, noise=np.full(len(log["ids"]), 0.9))])
-    batch = _batch(1, model, family, row_noise=True)
+    batch = sp.family_batch(1, model, family, row_noise=True)
     for bad in (np.full(len(log["ids"]) - 1, 0.9), np.full((len(log["ids"]), 2), 0.9), np.zeros(len(log["ids"])),
                 np.full(len(log["ids"]), np.nan)):
         with pytest.raises(ValueError, match="noise"):

@@ -8,6 +8,7 @@ import pytest
 import batch_smooth_util as bu
 import motion_util as mu
 import smooth_util as su
+import support as sp
 
 pytestmark = pytest.mark.gpu
 EKF_ERR_CAPACITY, EKF_ERR_STATE, EKF_ERR_NUMERIC = -2, -4, -5
@@ -22,18 +23,6 @@ def _batch(members, **kw):
     return EKFBatch(members, bu.initial_poses(members) if poses is None else poses, **kw)
 
 
-def _snap(batch):
-    return [(batch.get_state(b), batch.get_cov(b), dict(batch.landmarks[b])) for b in range(batch.members)]
-
-
-def _same(a, b):
-    return all(np.array_equal(u[0], v[0]) and np.array_equal(u[1], v[1]) and u[2] == v[2] for u, v in zip(a, b))
-
-
-def _eq(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
 # ---- 1. recorded = plain ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", ["motion", "scale", "gate"])
 def test_recorded_call_is_the_plain_call_bit_for_bit(case):
@@ -45,15 +34,16 @@ def test_recorded_call_is_the_plain_call_bit_for_bit(case):
     for record in (False, True):
         batch = _batch(4, **kw)
         rep = batch.process_detection_logs(logs, nis=True, cam_cov=True, mahal=case == "gate", record=record)
-        out.append((rep, _snap(batch), list(batch.num_landmarks), batch.pending_scale, batch.status()))
+        out.append((rep, sp.snap_batch(batch, tables=True), list(batch.num_landmarks), batch.pending_scale, batch.status()))
         assert (batch.last_history is not None) == record
     (plain, snap0, n0, pend0, st0), (rec, snap1, n1, pend1, st1) = out
     for b in range(4):
-        assert _eq(plain.trajectory[b], rec.trajectory[b]) and _eq(plain.nis[b], rec.nis[b])
-        assert _eq(plain.cam_cov[b], rec.cam_cov[b]) and np.array_equal(plain.dof[b], rec.dof[b])
+        assert sp.same(plain.trajectory[b], rec.trajectory[b], equal_nan=True)
+        assert sp.same(plain.nis[b], rec.nis[b], equal_nan=True)
+        assert sp.same(plain.cam_cov[b], rec.cam_cov[b], equal_nan=True) and np.array_equal(plain.dof[b], rec.dof[b])
         if case == "gate":
-            assert _eq(plain.mahal[b], rec.mahal[b]) and np.array_equal(plain.rejected[b], rec.rejected[b])
-    assert _same(snap0, snap1) and n0 == n1 and np.array_equal(pend0, pend1) and st0 == st1 == [0] * 4
+            assert sp.same(plain.mahal[b], rec.mahal[b], equal_nan=True) and np.array_equal(plain.rejected[b], rec.rejected[b])
+    assert sp.same(snap0, snap1) and n0 == n1 and np.array_equal(pend0, pend1) and st0 == st1 == [0] * 4
     assert rec.trajectory[1].shape == (0, 7)
     if case == "gate":      # the gate leaves frames without a detection: they are not stepped
         assert sum(int(r.sum()) for r in rec.rejected) > 0
@@ -166,9 +156,9 @@ def test_mixed_batch_against_the_oracle_under_the_bound(mixed):
 def test_a_member_does_not_depend_on_the_batch_around_it(mixed):
     logs, result, batch = mixed
     # the pass is read-only and repeatable
-    before, status = _snap(batch), batch.status()
+    before, status = sp.snap_batch(batch, tables=True), batch.status()
     again = batch.smooth_history()
-    assert _same(before, _snap(batch)) and batch.status() == status
+    assert sp.same(before, sp.snap_batch(batch, tables=True)) and batch.status() == status
     for i in range(4):
         assert np.array_equal(again[i], result[i][1])
     # another order of the members, and every member alone
@@ -206,11 +196,11 @@ def test_a_failed_member_stays_alone():
 # ---- 6. refusals ------------------------------------------------------------------------------------------------------------
 def _refused(batch, call, code=EKF_ERR_STATE):
     from aruco_slam_amd.hip_backend import EkfError
-    before = _snap(batch)
+    before = sp.snap_batch(batch, tables=True)
     with pytest.raises(EkfError) as err:
         call()
     assert err.value.code == code, err.value
-    assert _same(before, _snap(batch))
+    assert sp.same(before, sp.snap_batch(batch, tables=True))
 
 
 @pytest.mark.parametrize("kw", [{"model": "ekf_rotations", "quat_update": None, "max_landmarks": 10, "max_visible": 8},
@@ -275,7 +265,8 @@ def test_smooth_replicas_filters_like_replay_replicas_and_smoothing_pays_on_ever
     want = plain.replay_replicas(log, bu.REPLICA_SIGMA, bu.REPLICA_SEED).trajectory
     filtered, smoothed = batch.smooth_replicas(log, bu.REPLICA_SIGMA, bu.REPLICA_SEED)
     assert filtered.shape == smoothed.shape == (bu.REPLICAS, 40, 7) and np.array_equal(filtered, want)
-    assert _same(_snap(plain), _snap(batch)) and batch.last_smooth_status.tolist() == [0] * bu.REPLICAS
+    assert sp.same(sp.snap_batch(plain, tables=True), sp.snap_batch(batch, tables=True))
+    assert batch.last_smooth_status.tolist() == [0] * bu.REPLICAS
     for r in range(bu.REPLICAS):
         e0, e1 = mu.mean_position_error(filtered[r], log), mu.mean_position_error(smoothed[r], log)
         print(f"replica {r} on the device: filtered {e0:.4f} m, smoothed {e1:.4f} m, ratio {e1 / e0:.3f}")

@@ -10,13 +10,10 @@ import batch_smooth_cov_util as bcu
 import batch_smooth_util as bu
 import smooth_cov_util as scu
 import smooth_util as su
+import support as sp
 
 pytestmark = pytest.mark.gpu
 EKF_ERR_INVALID, EKF_ERR_STATE, EKF_ERR_NUMERIC = -1, -4, -5
-
-
-def _eq(a, b):
-    return np.array_equal(a, b, equal_nan=True)
 
 
 def _check_bit_rules(case, members):
@@ -30,7 +27,7 @@ def _check_bit_rules(case, members):
         assert np.array_equal(smoothed[b], case["state0"][b]) and np.array_equal(case["state1"][b], case["state0"][b]), b
         # two passes give the same bits
         for u, v in zip(case["cov0"], case["cov1"]):
-            assert _eq(u[b], v[b]), b
+            assert sp.same(u[b], v[b], equal_nan=True), b
         # filt_cam_cov is the record's camera block; rows before the first record are NaN; the last record's rows are filtered
         rec_of = np.full(frames, -1)
         for r, rec in enumerate(records):
@@ -48,7 +45,7 @@ def _check_bit_rules(case, members):
         assert np.array_equal(cam[b][live], cam[b][live].transpose(0, 2, 1)) and np.array_equal(first[b], first[b].T), b
         assert first[b].shape == (records[0]["dims"],) * 2 and np.array_equal(first[b][:10, :10], cam[b][records[0]["frame"]])
     # members, status() and P are untouched
-    assert bcu.same(case["before"], case["after"]) and case["status"][0] == case["status"][1] == [0] * members
+    assert sp.same(case["before"], case["after"]) and case["status"][0] == case["status"][1] == [0] * members
     assert case["smooth_status"].tolist() == [0] * members and batch.last_smooth_status.tolist() == [0] * members
 
 
@@ -111,11 +108,11 @@ def test_a_member_does_not_depend_on_the_batch_around_it():
     other = bcu.run_batch(logs, order=[2, 3, 0, 1], noise=bu.MIXED_NOISE, motion=True, frame_scale=True)
     for slot, i in enumerate(other["order"]):
         for u, v in zip(other["cov0"], case["cov0"]):
-            assert _eq(u[slot], v[i]), i
+            assert sp.same(u[slot], v[i], equal_nan=True), i
     for i in range(4):
         alone = bcu.run_batch(logs, order=[i], noise=bu.MIXED_NOISE, motion=True, frame_scale=True)
         for u, v in zip(alone["cov0"], case["cov0"]):
-            assert _eq(u[0], v[i]), i
+            assert sp.same(u[0], v[i], equal_nan=True), i
 
 
 def test_more_members_than_compute_units_all_have_member_zeros_bits():
@@ -126,13 +123,13 @@ def test_more_members_than_compute_units_all_have_member_zeros_bits():
     assert batch.last_smooth_status.tolist() == [0] * 300
     for part in (*out, first):
         stack = np.stack(part)
-        assert _eq(stack, np.broadcast_to(stack[0], stack.shape))
+        assert sp.same(stack, np.broadcast_to(stack[0], stack.shape), equal_nan=True)
     assert not np.isnan(out[3][0]).any() and first[0].shape == (40, 40)
     # and they are the bits of the same member in a batch of three copies
     three = bu.new_batch(3, poses=bu.INIT, max_landmarks=10)
     small = three.smooth_detection_logs([log] * 3, cov=True)
     for u, v in zip(out, small):
-        assert _eq(u[0], v[0])
+        assert sp.same(u[0], v[0], equal_nan=True)
 
 
 # ---- 3. failures --------------------------------------------------------------------------------------------------------------
@@ -146,7 +143,7 @@ def test_a_bad_pivot_stays_with_its_member():
         for k, part in enumerate(got):
             assert np.isnan(part[1]).all() and part[1].size > 0
             for b in (0, 2):
-                assert _eq(part[b], case["cov0"][k][b])
+                assert sp.same(part[b], case["cov0"][k][b], equal_nan=True)
         assert got[3][1].shape == (40, 40)
     finally:
         restore()
@@ -154,8 +151,8 @@ def test_a_bad_pivot_stays_with_its_member():
     assert batch.last_smooth_status.tolist() == [0, 0, 0]
     for u, v in zip(again, case["cov0"]):
         for b in range(3):
-            assert _eq(u[b], v[b])
-    assert bcu.same(case["before"], bcu.snap(batch)) and batch.status() == [0, 0, 0]
+            assert sp.same(u[b], v[b], equal_nan=True)
+    assert sp.same(case["before"], sp.snap_batch(batch, tables=True)) and batch.status() == [0, 0, 0]
 
 
 def test_a_member_that_failed_in_the_replay_is_nan_from_its_failing_frame_on():
@@ -179,7 +176,7 @@ def test_a_member_that_failed_in_the_replay_is_nan_from_its_failing_frame_on():
     assert got[3][1].shape == (0, 0)      # (no record: nothing of its first_cov slab is written)
     for part, want in zip(got, good):
         for b in (0, 2):
-            assert _eq(part[b], want[b]) and not np.isnan(part[b][-1]).any()
+            assert sp.same(part[b], want[b], equal_nan=True) and not np.isnan(part[b][-1]).any()
 
 
 # ---- 4. dirty buffers ---------------------------------------------------------------------------------------------------------
@@ -192,7 +189,8 @@ def test_dirty_workspace_and_outputs_give_the_same_bits(name):
     smoothed, cam, filt, first = case["cov0"]
     for b in range(3):
         rows = slice(int(mf[b]), int(mf[b + 1]))
-        assert _eq(out["smoothed"][rows], smoothed[b]) and _eq(out["cam_cov"][rows], cam[b]) and _eq(out["filt_cam_cov"][rows], filt[b])
+        for key, want in (("smoothed", smoothed), ("cam_cov", cam), ("filt_cam_cov", filt)):
+            assert sp.same(out[key][rows], want[b], equal_nan=True), (b, key)
         n0 = first[b].shape[0]
         assert np.array_equal(out["first_cov"][b, :n0, :n0], first[b])
         # what the rules do not write keeps the sentinel: the slab beyond [0:N_0, 0:N_0]
@@ -210,7 +208,7 @@ def test_refusals_come_before_anything_is_enqueued():
     log = bu.scene_log("ragged", with_motion=False, with_scale=False)
     batch = bu.new_batch(2)
     batch.smooth_detection_logs([bu.prefix(log, 9), bu.prefix(log, 9)])
-    before = bcu.snap(batch)
+    before = sp.snap_batch(batch, tables=True)
     need = C.c_size_t()
     assert batch.lib.ekf_batch_smooth_cov_workspace_bytes(batch.h, C.byref(need)) == 0
     n0 = batch.history_records(0)[0]["dims"]
@@ -227,7 +225,7 @@ def test_refusals_come_before_anything_is_enqueued():
     with pytest.raises(EkfError) as err:
         batch.smooth_history_cov()
     assert err.value.code == EKF_ERR_STATE
-    assert bcu.same(before[1:], bcu.snap(batch)[1:])
+    assert sp.same(before[1:], sp.snap_batch(batch, tables=True)[1:])
 
 
 @pytest.mark.parametrize("kw", [{"large_maps": True}, {"model": "ekf_rotations", "quat_update": None, "max_landmarks": 10,

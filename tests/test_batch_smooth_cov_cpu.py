@@ -2,8 +2,6 @@
 the margin the oracle's bound leaves to plain f64 on the members the GPU tests run, the facts those tests lean on (record 0
 of ``g17_3`` moves, the smoothed block lies below the filtered one on consistent records), and the compiler's resource
 report of the three resident kernels.  ``test_batch_smooth_cov.py`` runs the device against the same helpers."""
-import re
-
 import numpy as np
 import pytest
 
@@ -11,24 +9,17 @@ import batch_smooth_cov_util as bcu
 import batch_smooth_util as bu
 import smooth_cov_util as scu
 import smooth_util as su
+import support as sp
 import update_sweep_util as sw
+from support import lib
 
 NEW_SYMBOLS = ("ekf_batch_smooth_cov_workspace_bytes", "ekf_batch_smooth_history_cov")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_new_symbols_are_declared_exported_and_refuse_a_null_handle(lib):
     from aruco_slam_amd import _build, hip_backend
-    header = (sw.REPO / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     assert "ekf_batch_smooth_cov.hip" in _build.SOURCES and "ekf_smooth_resident.h" in _build.HEADERS
     block = header[header.index("Batch smoothing: recorded replays"):]
     assert "Batch smoothing, covariances." in block
@@ -143,9 +134,8 @@ def test_record_zero_of_the_growing_scene_moves_and_the_smoothed_block_lies_belo
 def test_resident_smooth_kernels_use_no_scratch_and_no_vgpr_spill():
     """The new kernel and the two state kernels that share the pass with it: no scratch memory, no VGPR spill; the static LDS
     of the pass (six vectors of 160 doubles, F and the 10 x 10 block) is the same 8 840 bytes in all three."""
-    from test_batch_replicas_cpu import _kernel_resources
-    found = _kernel_resources("ekf_batch_smooth_cov.hip", r"ekf_batch_smooth_cov_kernel")
-    found.update(_kernel_resources("ekf_smooth.hip", r"ekf_smooth_resident_kernel|ekf_batch_smooth_kernel"))
+    found = sp.kernel_resources("ekf_batch_smooth_cov.hip", r"ekf_batch_smooth_cov_kernel")
+    found.update(sp.kernel_resources("ekf_smooth.hip", r"ekf_smooth_resident_kernel|ekf_batch_smooth_kernel"))
     assert len(found) == 3, found
     for name, res in found.items():
-        assert res == {"private_segment_fixed_size": 0, "vgpr_spill_count": 0, "group_segment_fixed_size": 8840}, (name, res)
+        assert [res[k] for k in sp.BUDGET_FIELDS] == [0, 0, 8840], (name, res)

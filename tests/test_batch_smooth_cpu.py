@@ -2,34 +2,23 @@
 the words a recorded call leaves (``ekf_batch_history_table``: no handle, no device), the resources of the recording kernels,
 and the fixtures the GPU tests judge the device by -- the growing scene under the bound, the replica condition on the oracle.
 ``test_batch_smooth.py`` runs the device against the same helpers."""
-import re
-
 import numpy as np
-import pytest
 
 import batch_smooth_util as bu
 import motion_util as mu
 import smooth_util as su
-import update_sweep_util as sw
+import support as sp
+from support import lib
 
 NEW_SYMBOLS = ("ekf_batch_history_bytes", "ekf_batch_observe_logs_recorded", "ekf_batch_history_info",
                "ekf_batch_history_record", "ekf_batch_history_table", "ekf_batch_smooth_workspace_bytes",
                "ekf_batch_smooth_history")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_new_symbols_are_declared_exported_and_refuse_a_null_handle(lib):
     from aruco_slam_amd import _build, hip_backend
-    header = (sw.REPO / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     assert "ekf_batch_recorded.hip" in _build.SOURCES and "ekf_batch_smooth_host.h" in _build.HEADERS
     block = header[header.index("Batch smoothing: recorded replays"):]
     for word in ("EKF_MODEL_ROTATIONS", "EKF_QUAT_AS_WRITTEN", "EKF_FLAG_BATCH_LARGE_MAPS", "EKF_FLAG_BATCH_WIDE_FRAMES",
@@ -95,11 +84,10 @@ def test_table_from_the_flags_of_a_call(lib):
 
 def test_recording_kernels_use_no_scratch_and_no_vgpr_spill():
     """The two RECORDED instances, like the instances they are built from: no scratch memory, no VGPR spill, no static LDS."""
-    from test_batch_replicas_cpu import _kernel_resources
-    found = _kernel_resources("ekf_batch_recorded.hip", r"ekf_batch_recorded_(moved_)?window_kernel")
+    found = sp.kernel_resources("ekf_batch_recorded.hip", r"ekf_batch_recorded_(moved_)?window_kernel")
     assert len(found) == 2, found
     for name, res in found.items():
-        assert res == {"private_segment_fixed_size": 0, "vgpr_spill_count": 0, "group_segment_fixed_size": 0}, (name, res)
+        assert [res[k] for k in sp.BUDGET_FIELDS] == [0, 0, 0], (name, res)
 
 
 def test_growing_scene_reaches_the_resident_limit_with_room_under_the_bound():

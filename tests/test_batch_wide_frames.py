@@ -5,6 +5,7 @@ interop with ``EKF``."""
 import numpy as np
 import pytest
 
+import support as sp
 import update_sweep_util as sw
 from conftest import rel_err, report
 
@@ -35,13 +36,6 @@ def _ragged(model, n, m_range, steady, seed, **kw):
 def _frame_log(ids, poses):
     ids = np.asarray(ids, dtype=np.int32)
     return {"ids": ids, "poses": np.asarray(poses, dtype=np.float64), "offsets": np.array([0, len(ids)], dtype=np.int64)}
-
-
-def _sub(log, t0, t1):
-    offs = log["offsets"]
-    d0, d1 = int(offs[t0]), int(offs[t1])
-    return {"ids": log["ids"][d0:d1], "poses": log["poses"][d0:d1], "offsets": offs[t0:t1 + 1] - d0,
-            "has_detections": log["has_detections"][t0:t1]}
 
 
 def _snapshot(batch, b):
@@ -210,7 +204,7 @@ def test_a_pivot_failing_in_a_later_block_leaves_the_member_as_it_was(model):
     frame = _frame_log(ids, poses)
     first_block = _frame_log(ids[:blk], poses[:blk])
     more = _ragged(model, n, (1, 30), 10, seed=8)
-    more = _sub(more, more["bootstrap_frames"], len(more["offsets"]) - 1)
+    more = sp.sub_log(more, more["bootstrap_frames"], len(more["offsets"]) - 1)
     bad = {"ids": np.concatenate([frame["ids"], more["ids"]]), "poses": np.concatenate([frame["poses"], more["poses"]]),
            "offsets": np.concatenate([[0], len(ids) + more["offsets"]]).astype(np.int64)}
     others = [_ragged(model, 60, (1, min(60, WIDE[model])), 40, seed=9), _ragged(model, 30, (1, 20), 40, seed=10)]
@@ -279,8 +273,8 @@ def test_continuation_across_calls_and_windows_is_bitwise(model, n):
     t_one = one.process_detection_logs([log, None])[0]
     two = _batch(2, model, max_landmarks=n)
     cut = 37                                      # inside a window of the wide batch (16 / 9 frames)
-    t_a = two.process_detection_logs([_sub(log, 0, cut), None])[0]
-    t_b = two.process_detection_logs([_sub(log, cut, frames), None])[0]
+    t_a = two.process_detection_logs([sp.sub_log(log, 0, cut), None])[0]
+    t_b = two.process_detection_logs([sp.sub_log(log, cut, frames), None])[0]
     assert one.status() == [0, 0]
     assert np.array_equal(t_one, np.concatenate([t_a, t_b]))
     for a, b in zip(_snapshot(one, 0), _snapshot(two, 0)):
@@ -319,7 +313,7 @@ def test_to_filter_continues_as_an_ordinary_ekf():
     assert np.array_equal(np.asarray(flt.state), batch.get_state(0)) and np.array_equal(flt.uncertainty, batch.get_cov(0))
     more = _ragged("ekf", n, (40, 64), 3, seed=22)
     frames = len(more["offsets"]) - 1
-    nxt = _sub(more, frames - 1, frames)                            # one steady wide frame of known markers
+    nxt = sp.sub_log(more, frames - 1, frames)                            # one steady wide frame of known markers
     assert len(nxt["ids"]) > 16
     flt.observe(nxt["ids"], nxt["poses"])
     got = batch.process_detection_logs([nxt, None])[0][-1]

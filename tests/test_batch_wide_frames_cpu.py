@@ -2,25 +2,21 @@
 workspace it adds, the register / LDS budget of the wide-frame kernels and the Python choice of the flag."""
 import ctypes
 import re
-import subprocess
-import tempfile
-from pathlib import Path
 
 import pytest
+
+import support as sp
 
 TOP = {0: (338, 64, 3), 1: (101, 50, 7)}      # model: (max_landmarks, max_visible, rows per detection) with the flag
 
 
 def _lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend, hip_backend.load_library()
+    from aruco_slam_amd import hip_backend
+    return hip_backend, sp.load_lib()
 
 
 def _config(hb, lib, model, wide=True, large=False, **fields):
-    cfg = hb.EkfConfig()
-    lib.ekf_default_config(ctypes.byref(cfg))
-    cfg.model, cfg.max_landmarks, cfg.max_visible = model, TOP[model][0], TOP[model][1]
+    cfg = sp.config(lib, model=model, max_landmarks=TOP[model][0], max_visible=TOP[model][1])
     if model == 1:
         cfg.quat_mode = hb.EKF_QUAT_SCALAR_FIRST
     if wide:
@@ -32,17 +28,10 @@ def _config(hb, lib, model, wide=True, large=False, **fields):
     return cfg
 
 
-def _sizes(lib, cfg, members=4):
-    ld, cov, state, ws = ctypes.c_int64(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-    rc = lib.ekf_batch_query_sizes(ctypes.byref(cfg), members, ctypes.byref(ld), ctypes.byref(cov), ctypes.byref(state),
-                                   ctypes.byref(ws))
-    return rc, ld.value, cov.value, state.value, ws.value
-
-
 def test_flag_value():
     from aruco_slam_amd import hip_backend
     assert hip_backend.EKF_FLAG_BATCH_WIDE_FRAMES == 32
-    header = (Path(__file__).resolve().parent.parent / "include" / "ekf_slam_hip.h").read_text()
+    header = sp.HEADER.read_text()
     assert re.search(r"EKF_FLAG_BATCH_WIDE_FRAMES = 32\b", header)
 
 
@@ -50,7 +39,7 @@ def test_flag_value():
 @pytest.mark.parametrize("large", [False, True])
 def test_wide_frame_limits_are_checked(model, large):
     hb, lib = _lib()
-    rc, ld, cov, state, _ = _sizes(lib, _config(hb, lib, model, large=large))
+    rc, ld, cov, state, _ = sp.batch_query_sizes(lib, _config(hb, lib, model, large=large))
     assert rc == 0, lib.ekf_last_error_string()
     assert ld == 1024 and cov == 4 * 1024 * 1024 * 8 and state == 4 * 1024 * 8
     lm, vis, _ = TOP[model]
@@ -82,7 +71,7 @@ def test_without_the_flag_nothing_changes(model):
         assert b"max_visible" in msg and f"1..{vis}".encode() in msg and b"WIDE" not in msg, msg
     # sizes without the flag: as the one-column and the large-map kernels define them
     for large, lm in ((False, 10), (True, 10), (True, TOP[model][0])):
-        rc, ld, cov, state, ws = _sizes(lib, _config(hb, lib, model, wide=False, large=large, max_landmarks=lm,
+        rc, ld, cov, state, ws = sp.batch_query_sizes(lib, _config(hb, lib, model, wide=False, large=large, max_landmarks=lm,
                                                       max_visible=vis))
         assert rc == 0
         lmd, rd = (3, 3) if model == 0 else (10, 7)
@@ -100,12 +89,13 @@ def test_workspace_growth_follows_the_formula(model):
     for lm in (1, 30, TOP[model][0]):
         for vis in (1, 17, top_vis):
             for members in (1, 5):
-                plain = _sizes(lib, _config(hb, lib, model, wide=False, large=True, max_landmarks=lm, max_visible=1),
-                               members)
+                plain = sp.batch_query_sizes(lib, _config(hb, lib, model, wide=False, large=True, max_landmarks=lm,
+                                                          max_visible=1), members)
                 assert plain[0] == 0
                 w_plain = members * rd * 1 * plain[1] * 8
                 for large in (False, True):
-                    wide = _sizes(lib, _config(hb, lib, model, large=large, max_landmarks=lm, max_visible=vis), members)
+                    wide = sp.batch_query_sizes(lib, _config(hb, lib, model, large=large, max_landmarks=lm, max_visible=vis),
+                                                members)
                     assert wide[0] == 0 and wide[1:4] == plain[1:4]
                     w = members * rd * vis * wide[1] * 8
                     assert w <= wide[4] - (plain[4] - w_plain) < w + 256, (lm, vis, members, large)
@@ -117,23 +107,19 @@ def test_wide_frame_kernels_use_no_scratch_and_fit_the_lds():
     160 KiB of a CU."""
     from aruco_slam_amd import _build
     assert "ekf_batch_wide.hip" in _build.SOURCES
-    with tempfile.TemporaryDirectory() as tmp:
-        out = Path(tmp) / "batch_wide.s"
-        subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                        str(_build.CSRC / "ekf_batch_wide.hip"), "-o", str(out)], check=True, capture_output=True)
-        text = out.read_text()
-    names = re.findall(r"\.name:\s+(\S*_kernel\S*)\n", text)
+    resources = sp.kernel_resources("ekf_batch_wide.hip")
+    names = list(resources)
     kernels = ("ekf_batch_wide_window_kernel", "ekf_batch_wide_rot_window_kernel", "ekf_batch_one_block_window_kernel",
                "ekf_batch_one_block_rot_window_kernel")
     assert len(names) == 4, names
     for kernel in kernels:
         assert any(kernel in n for n in names), kernel
     for kernel in kernels:
-        pat = r"\.name:\s+(\S*" + kernel + r"\S*)\n(?:.*\n)*?\s+\.{}:\s+(\d+)"
+        found = sp.kernel_resources("ekf_batch_wide.hip", kernel)
+        assert len(found) == 1, (kernel, found)
         for field in ("private_segment_fixed_size", "vgpr_spill_count"):
-            found = re.findall(pat.format(field), text)
-            assert len(found) == 1 and int(found[0][1]) == 0, (kernel, field, found)
-    assert re.findall(r"\.group_segment_fixed_size:\s+(\d+)", text) == ["0"] * 4
+            assert [res[field] for res in found.values()] == [0], (kernel, field, found)
+    assert [res["group_segment_fixed_size"] for res in resources.values()] == [0] * 4
     _, lib = _lib()
     lds = lib.ekf_batch_wide_lds_bytes
     lds.argtypes, lds.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_size_t

@@ -7,6 +7,8 @@ Run with ``-m gpu`` on an MI355X."""
 import numpy as np
 import pytest
 
+import support as sp
+
 pytestmark = pytest.mark.gpu
 
 INIT = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0])
@@ -62,11 +64,6 @@ def _run_calls(flt, idx, z, calls, want_mode):
     return traj.cpu().numpy(), flt.state, flt.uncertainty
 
 
-def _assert_same(a, b):
-    for x, y in zip(a, b):
-        assert np.array_equal(x, y)
-
-
 @pytest.mark.parametrize("frames", [2, 3, 7])
 @pytest.mark.parametrize("shape", ["f32_tile_odd", "f64_split", "f32_macro", "f64_tile"])
 def test_signalling_update_is_bitwise_the_serial_order(shape, frames):
@@ -78,7 +75,7 @@ def test_signalling_update_is_bitwise_the_serial_order(shape, frames):
         flt, s = _filter(shape, lookahead, seed=5)
         idx, z = _resident(list(s.steady(sum(calls))))
         out.append(_run_calls(flt, idx, z, calls, PIPELINED if lookahead else "serial"))
-    _assert_same(out[0], out[1])
+    sp.assert_same(out[0], out[1], "trajectory, state, covariance")
     assert np.array_equal(out[0][2], out[0][2].T)
 
 
@@ -94,9 +91,9 @@ def test_counter_is_armed_again_when_another_handle_takes_the_token_over():
     first_a = _run_calls(a, ia[:5], za[:5], (5,), PIPELINED)
     got_b = _run_calls(b, ib, zb, (5,), PIPELINED)
     again_a = _run_calls(a, ia[5:], za[5:], (3,), PIPELINED)
-    _assert_same(first_a, _run_calls(ref_a, ia[:5], za[:5], (5,), "serial"))
-    _assert_same(got_b, _run_calls(ref_b, ib, zb, (5,), "serial"))
-    _assert_same(again_a, _run_calls(ref_a, ia[5:], za[5:], (3,), "serial"))
+    sp.assert_same(first_a, _run_calls(ref_a, ia[:5], za[:5], (5,), "serial"), "trajectory, state, covariance")
+    sp.assert_same(got_b, _run_calls(ref_b, ib, zb, (5,), "serial"), "trajectory, state, covariance")
+    sp.assert_same(again_a, _run_calls(ref_a, ia[5:], za[5:], (3,), "serial"), "trajectory, state, covariance")
 
 
 def test_pipelined_call_after_a_sticky_error_and_reset_is_bitwise_the_serial_order():
@@ -126,4 +123,4 @@ def test_pipelined_call_after_a_sticky_error_and_reset_is_bitwise_the_serial_ord
             flt.observe(ids, poses)
         i2, z2 = _resident(list(s2.steady(6)))
         out.append(_run_calls(flt, i2, z2, (3, 3), PIPELINED if flt is bad else "serial"))
-    _assert_same(out[0], out[1])
+    sp.assert_same(out[0], out[1], "trajectory, state, covariance")

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import gating_util as gu
+import support as sp
 from conftest import load_npz, report
 
 pytestmark = pytest.mark.gpu
@@ -34,15 +35,6 @@ def _load_prior(flt, state, p, lm_ids):
     flt.backend.set_state_cov(state, p)
     flt.landmarks = {int(k): i for i, k in enumerate(lm_ids)}
     flt.num_landmarks = len(lm_ids)
-
-
-def _snap(flt):
-    return np.array(flt.state, dtype=np.float64), flt.uncertainty
-
-
-def _same(a, b, what):
-    for name, u, v in zip(("state", "covariance"), a, b):
-        assert u.shape == v.shape and np.array_equal(u, v), (what, name)
 
 
 def _log_family(model):
@@ -125,14 +117,14 @@ def _per_frame_gated(model, dtype):
     rows, unstepped = [], []
     for t, sl, ids, poses in _frames(dirty):
         if len(ids):
-            before = _snap(flt) if flt.num_landmarks and _outliers_only(model, t) else None
+            before = sp.snap_filter(flt) if flt.num_landmarks and _outliers_only(model, t) else None
             flt.observe(ids, poses)
             d2[sl], rej[sl] = flt.last_mahal, flt.last_rejected
             if before is not None:
-                _same(_snap(flt), before, f"frame {t}: no survivor, so no predict")
+                sp.assert_same(sp.snap_filter(flt), before, f"frame {t}: no survivor, so no predict")
                 unstepped.append(t)
         rows.append(np.asarray(flt.get_poses()[0], dtype=np.float64)[:7])
-    state, cov = _snap(flt)
+    state, cov = sp.snap_filter(flt)
     return np.array(rows), d2, rej, state, cov, dict(flt.landmarks), unstepped
 
 
@@ -159,7 +151,7 @@ def test_a_gated_frame_is_the_frame_without_the_rejected_detections(model, dtype
             plain.observe(ids, poses)
         rows.append(np.asarray(plain.get_poses()[0], dtype=np.float64)[:7])
     assert np.array_equal(traj, np.array(rows))
-    _same((state, cov), _snap(plain), "gated loop = loop without the rejected")
+    sp.assert_same((state, cov), sp.snap_filter(plain), "gated loop = loop without the rejected")
     assert landmarks == plain.landmarks
     # inserted outlier-only frames are not stepped: the row repeats (and P was unchanged, checked in the loop)
     offs = dirty["offsets"]
@@ -198,13 +190,13 @@ def test_gated_log_replay(model, dtype):
     cut = gu.delete(dirty, rej)
     want = plain.process_detection_log(cut["ids"], cut["poses"], cut["offsets"])
     assert np.array_equal(traj, want)
-    _same(_snap(flt), _snap(plain), "gated replay = replay without the rejected")
+    sp.assert_same(sp.snap_filter(flt), sp.snap_filter(plain), "gated replay = replay without the rejected")
     assert flt.landmarks == plain.landmarks
     traj_pf, d2_pf, rej_pf, state_pf, cov_pf, lm_pf, _ = _per_frame_gated(model, dtype)
     assert np.array_equal(rej, rej_pf) and flt.landmarks == lm_pf
     if model == "ekf":
         assert np.array_equal(traj, traj_pf) and np.array_equal(d2, d2_pf)
-        _same(_snap(flt), (state_pf, cov_pf), "gated replay = gated per-frame loop")
+        sp.assert_same(sp.snap_filter(flt), (state_pf, cov_pf), "gated replay = gated per-frame loop")
     else:
         tested = d2_pf > 0
         assert np.array_equal(d2 > 0, tested)
@@ -218,7 +210,7 @@ def test_gated_log_replay(model, dtype):
 def _oracle_frame(model, flt, lm_ids, ids, poses):
     """Expected (d^2, kappa) of a frame from the support blocks of the prior the device holds."""
     from update_sweep_util import oracle_at
-    state, cov = _snap(flt)
+    state, cov = sp.snap_filter(flt)
     return gu.block_distances(model, oracle_at(QM[model], state, cov, lm_ids), ids, poses)
 
 
@@ -237,7 +229,7 @@ def _check_frame(model, dtype, n, m, outliers, max_visible=None, seed=5, capacit
     for f in (flt, plain):
         _load_prior(f, state, p, lm)
     want, kappa = _oracle_frame(model, flt, lm, ids, poses)
-    before = _snap(flt)
+    before = sp.snap_filter(flt)
     flt.observe(ids, poses)
     flt.backend.sync()
     got, rej = flt.last_mahal, flt.last_rejected
@@ -253,9 +245,9 @@ def _check_frame(model, dtype, n, m, outliers, max_visible=None, seed=5, capacit
     if keep.any():
         plain.observe([i for i, s in zip(ids, keep) if s], poses[keep])
         plain.backend.sync()
-        _same(_snap(flt), _snap(plain), "gated frame = frame without the rejected")
+        sp.assert_same(sp.snap_filter(flt), sp.snap_filter(plain), "gated frame = frame without the rejected")
     else:
-        _same(_snap(flt), before, "no survivor: not stepped")
+        sp.assert_same(sp.snap_filter(flt), before, "no survivor: not stepped")
     return got, rej
 
 
@@ -317,7 +309,7 @@ def test_duplicates_of_one_landmark_only_the_outlier_goes(model):
     assert flt.last_rejected.tolist() == [False, False, True, False]
     assert flt.last_mahal[0] == flt.last_mahal[3] > 0          # (a detection's distance does not depend on its neighbours)
     plain.observe([2, 4, 2], frame[[0, 1, 3]])
-    _same(_snap(flt), _snap(plain), "only the outlier is rejected")
+    sp.assert_same(sp.snap_filter(flt), sp.snap_filter(plain), "only the outlier is rejected")
 
 
 @pytest.mark.parametrize("model", MODELS)
@@ -335,7 +327,7 @@ def test_every_detection_rejected_and_first_sightings_only(model):
     assert len(flt.landmarks) == len(each) >= 1
     assert (flt.last_mahal == 0).all() and not flt.last_rejected.any()
     assert flt.backend.last_gate_stats() == {"tested": 0, "rejected": 0}
-    _same(_snap(flt), _snap(plain), "first sightings only")
+    sp.assert_same(sp.snap_filter(flt), sp.snap_filter(plain), "first sightings only")
 
 
 # ---- 5. gate off is the filter without the gate ----------------------------------------------------------------------------
@@ -362,16 +354,16 @@ def test_gate_off_is_the_filter_without_the_gate(name, model, dtype):
     assert off.backend.ws_t.numel() > plain.backend.ws_t.numel()
     want = per_frame(plain)
     assert np.array_equal(per_frame(off), want)          # (through ekf_observe_gated: distances reported, gate off)
-    _same(_snap(off), _snap(plain), "per frame, gate off")
+    sp.assert_same(sp.snap_filter(off), sp.snap_filter(plain), "per frame, gate off")
     assert off.last_mahal is not None and not off.last_rejected.any()
     plain2, off2, off3 = make(), make(gate=np.inf), make(gate=np.inf)
     want2 = replay(plain2)
     assert np.array_equal(replay(off2), want2)          # (mahal not asked for: ekf_observe_log, pipelined runs included)
     assert off2.backend.last_log_stats() == plain2.backend.last_log_stats()
-    _same(_snap(off2), _snap(plain2), "replay, gate off")
+    sp.assert_same(sp.snap_filter(off2), sp.snap_filter(plain2), "replay, gate off")
     traj3, d2 = replay(off3, mahal=True)          # (distances asked for: serial, nothing rejected, the same bits)
     assert np.array_equal(traj3, want2)
-    _same(_snap(off3), _snap(plain2), "replay with mahal, gate off")
+    sp.assert_same(sp.snap_filter(off3), sp.snap_filter(plain2), "replay with mahal, gate off")
     assert off3.backend.last_gate_stats()["rejected"] == 0 and off3.backend.last_log_stats()["frames_pipelined"] == 0
     has = np.repeat(log["has_detections"], np.diff(log["offsets"]))
     assert np.isnan(d2[~has]).all() and np.isfinite(d2[has]).all() and (d2[has] >= 0).all() and (d2[has] > 0).any()

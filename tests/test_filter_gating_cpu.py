@@ -6,53 +6,23 @@ side of ``gate=`` / ``set_gate``, and the fixtures of ``test_filter_gating.py``:
 comparison margin of its gate."""
 import ctypes as C
 import re
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import gating_util as gu
-from test_batch_replicas_cpu import _kernel_resources
+import support as sp
+from support import lib
 
 NEW_SYMBOLS = ("ekf_set_gate", "ekf_observe_gated", "ekf_observe_log_gated", "ekf_last_gate_stats")
 # the seed of the free-running logs of test_filter_gating.py (gating_util.clean_log / dirty_log, family "column")
 LOG_SEED = 0
 
-# (model, max_landmarks, max_visible, cov_dtype, flags) -> (ld, cov, state, workspace bytes) of ekf_query_sizes, taken from
-# the library of the commit before the gate
-PARENT_SIZES = (
-    ((0, 50, 50, 0, 8), (256, 524288, 2048, 3279872)),
-    ((0, 1024, 32, 1, 8), (3200, 40960000, 25600, 48925184)),
-    ((1, 63, 55, 0, 8), (640, 3276800, 5120, 25851904)),
-    ((0, 82, 64, 1, 0), (256, 262144, 2048, 3217920)),
-    ((1, 24, 27, 0, 4), (256, 524288, 2048, 3885312)),
-    ((0, 4000, 1024, 1, 10), (12032, 579076096, 96256, 2143691520)),
-)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
-def _sizes(lib, model, n, mv, dtype, flags):
-    from aruco_slam_amd import hip_backend
-    cfg = hip_backend.EkfConfig()
-    assert lib.ekf_default_config(C.byref(cfg)) == 0
-    cfg.model, cfg.max_landmarks, cfg.max_visible, cfg.cov_dtype, cfg.flags = model, n, mv, dtype, flags
-    ld, cb, sb, wb = C.c_int64(), C.c_size_t(), C.c_size_t(), C.c_size_t()
-    assert lib.ekf_query_sizes(C.byref(cfg), C.byref(ld), C.byref(cb), C.byref(sb), C.byref(wb)) == 0
-    return ld.value, cb.value, sb.value, wb.value
-
 
 def test_new_symbols_are_declared_and_exported(lib):
     from aruco_slam_amd import hip_backend
-    header = (Path(__file__).resolve().parent.parent / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     assert re.search(r"EKF_FLAG_GATE = 64\b", header) and hip_backend.EKF_FLAG_GATE == 64
     # no handle: EKF_ERR_INVALID, nothing touched
     assert lib.ekf_set_gate(None, 11.345) == -1
@@ -67,9 +37,9 @@ def test_sizes_without_the_flag_are_the_parents_and_the_flag_adds_the_gate_scrat
     def pad(v):
         return -(-v // 256) * 256
 
-    for (model, n, mv, dtype, flags), want in PARENT_SIZES:
-        assert _sizes(lib, model, n, mv, dtype, flags) == want, (model, n, mv, dtype, flags)
-        ld, cb, sb, wb = _sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_GATE)
+    for (model, n, mv, dtype, flags), want in sp.PARENT_SIZES:
+        assert sp.sizes(lib, model, n, mv, dtype, flags) == want, (model, n, mv, dtype, flags)
+        ld, cb, sb, wb = sp.sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_GATE)
         # survivors' indices and z (7 doubles per detection, as the staging of z) and the distances
         assert (ld, cb, sb) == want[:3] and wb == want[3] + pad(4 * mv) + pad(56 * mv) + pad(8 * mv)
 
@@ -77,14 +47,14 @@ def test_sizes_without_the_flag_are_the_parents_and_the_flag_adds_the_gate_scrat
 def test_gate_kernel_uses_no_scratch_and_no_spill_and_its_own_lds_only():
     """Four instances (f32 / f64 covariance x two models): no scratch, no VGPR spill; the static LDS is what ekf_gate.hip
     declares: CHUNK detections of 90 (EKF, 64 per chunk) / 336 (EKF_Rotations, 16 per chunk) doubles and CHUNK ints."""
-    found = _kernel_resources("ekf_gate.hip", r"ekf_frame_gate_kernel")
+    found = sp.kernel_resources("ekf_gate.hip", r"ekf_frame_gate_kernel")
     assert len(found) == 4, found
     lds = {"Li0E": 64 * 90 * 8 + 64 * 4, "Li1E": 16 * 336 * 8 + 16 * 4}
     for name, res in found.items():
         want = next(v for k, v in lds.items() if k in name)
         assert res["private_segment_fixed_size"] == 0 and res["vgpr_spill_count"] == 0, (name, res)
         assert res["group_segment_fixed_size"] == want, (name, res)
-    csrc = Path(__file__).resolve().parent.parent / "aruco_slam_amd" / "csrc"
+    csrc = sp.REPO / "aruco_slam_amd" / "csrc"
     # (the kernel's measurement stage is the shared core's, and that one's model is ekf_device.h's, not a copy)
     assert "ekf_gate_measure<MODEL>" in (csrc / "ekf_gate.hip").read_text()
     assert "ekf_measure_model<MODEL>" in (csrc / "ekf_gate_device.h").read_text()
@@ -108,7 +78,7 @@ def test_run_slam_and_replay_bench_take_a_gate():
     from aruco_slam_amd.main import run_slam
     assert run_slam.build_parser().parse_args([]).gate is None
     assert run_slam.build_parser().parse_args(["--gate", "11.345"]).gate == 11.345
-    assert "--gate" in (Path(__file__).resolve().parent.parent / "tools" / "replay_bench.py").read_text()
+    assert "--gate" in (sp.REPO / "tools" / "replay_bench.py").read_text()
 
 
 @pytest.mark.parametrize("model", ["ekf", "ekf_rotations"])

@@ -9,6 +9,7 @@ import pytest
 import frame_scale_util as fs
 import gating_util as gu
 import row_noise_util as rn
+import support as sp
 import update_sweep_util as sw
 from conftest import load_npz, report
 
@@ -29,22 +30,6 @@ def _filter(model, n, m, dtype="float64", **kw):
         return EKF_Rotations(INIT, max_landmarks=n, max_visible=m, cov_dtype=dtype, **kw)
     from aruco_slam_amd.filters.extended_kalman_filter import EKF
     return EKF(INIT, max_landmarks=n, max_visible=m, cov_dtype=dtype, **kw)
-
-
-def _restore(flt, prior):
-    state, p, lm_ids = prior[:3]
-    flt.landmarks = {int(k): i for i, k in enumerate(lm_ids)}
-    flt.num_landmarks = len(lm_ids)
-    flt.backend.set_state_cov(state, p)
-
-
-def _snap(flt):
-    return np.array(flt.state, dtype=np.float64), flt.uncertainty
-
-
-def _same(a, b, what):
-    for name, u, v in zip(("state", "covariance"), a, b):
-        assert u.shape == v.shape and np.array_equal(u, v), (what, name)
 
 
 def _loop(flt, log, scale=None, rows=None):
@@ -86,9 +71,9 @@ def test_one_step_with_a_scale_against_the_extended_reference(group, step_refs):
             if key not in filters:
                 filters[key] = _filter(model, n, mv, dt, fused=fused, lookahead=False)
             flt = filters[key]
-            _restore(flt, prior)
+            sp.restore(flt, prior)
             flt.observe(prior[3], prior[4], scale=s)
-            x, p = _snap(flt)
+            x, p = sp.snap_filter(flt)
             assert np.array_equal(p, p.T), (case, dt)
             r_p, r_x = sw.ratios(ref, p, x, dt)
             worst = [max(worst[0], r_p), max(worst[1], r_x), max(worst[2], ref["kappa"])]
@@ -121,8 +106,8 @@ def test_a_scaled_frame_is_the_plain_frame_with_the_products(model, dtype, fused
         prior = sw.dense_prior(model, n, m, 500 + m, dtype)
         seen = []
         for s, twin in twins.items():
-            _restore(flt, prior)
-            _restore(twin, prior)
+            sp.restore(flt, prior)
+            sp.restore(twin, prior)
             if s == a + b:
                 flt.advance(a)
                 assert flt.pending_scale == a
@@ -131,8 +116,8 @@ def test_a_scaled_frame_is_the_plain_frame_with_the_products(model, dtype, fused
                 flt.observe(prior[3], prior[4], scale=s)
             assert flt.pending_scale == 0.0
             twin.observe(prior[3], prior[4])
-            got = _snap(flt)
-            _same(got, _snap(twin), (model, dtype, fused, gated, m, s))
+            got = sp.snap_filter(flt)
+            sp.assert_same(got, sp.snap_filter(twin), (model, dtype, fused, gated, m, s))
             if gated:
                 assert flt.last_mahal.shape == (m,) and (flt.last_mahal > 0).all()
                 assert np.array_equal(flt.last_mahal, twin.last_mahal), (m, s)
@@ -162,19 +147,19 @@ def test_a_log_is_its_folded_form(model, dtype):
             traj = _loop(full, log, scale)[0]
             want = _loop(short, folded, fscale)[0]
         assert full.pending_scale == left == scale[-1] and short.pending_scale == 0.0
-        _same(_snap(full), _snap(short), (how, "folded"))
+        sp.assert_same(sp.snap_filter(full), sp.snap_filter(short), (how, "folded"))
         assert np.array_equal(traj[stepped], want)
         first = int(np.argmax(stepped))
         for t in range(first + 1, len(stepped)):      # (a frame that is not stepped repeats the row before it)
             if not stepped[t]:
                 assert np.array_equal(traj[t], traj[t - 1]), t
-        ends[how] = (_snap(full), traj)
+        ends[how] = (sp.snap_filter(full), traj)
         # the scales matter: the same log without them ends elsewhere
         plain = _filter(model, n, m, dtype)
         plain.process_detection_log(log["ids"], log["poses"], log["offsets"], log["has_detections"])
         assert not np.array_equal(plain.uncertainty, ends[how][0][1])
     if model == "ekf":
-        _same(ends["log"][0], ends["loop"][0], "log = loop")
+        sp.assert_same(ends["log"][0], ends["loop"][0], "log = loop")
         first = int(np.argmax(stepped))
         assert np.array_equal(ends["log"][1][first:], ends["loop"][1][first:])
     else:      # (the replay forms z on the device)
@@ -213,7 +198,7 @@ def test_pipelined_sequence_with_a_scale_per_frame_is_the_serial_order(model, dt
     for (ids, poses), s in zip(frames, scale):
         loop.observe(ids, poses, scale=s)
         want_traj.append(np.asarray(loop.get_poses()[0], dtype=np.float64)[:7])
-    want_traj, want = np.array(want_traj), _snap(loop)
+    want_traj, want = np.array(want_traj), sp.snap_filter(loop)
     plain = booted(False)
     for ids, poses in frames:
         plain.observe(ids, poses)
@@ -232,7 +217,7 @@ def test_pipelined_sequence_with_a_scale_per_frame_is_the_serial_order(model, dt
                                      scale=scale)
         assert seq.backend.last_sequence_mode() == mode
         assert seq.pending_scale == 0.0
-        _same(_snap(seq), want, mode)
+        sp.assert_same(sp.snap_filter(seq), want, mode)
         assert np.array_equal(traj_t.cpu().numpy(), want_traj), mode
 
     # the log replay plans pipelined runs of its own: with scales they are still the loop (EKF: bit for bit)
@@ -243,10 +228,10 @@ def test_pipelined_sequence_with_a_scale_per_frame_is_the_serial_order(model, dt
     stats = rep.backend.last_log_stats()
     assert stats["frames_pipelined"] > 0 and stats["frames_stepped"] == steady, stats
     if model == "ekf":
-        _same(_snap(rep), want, "log")
+        sp.assert_same(sp.snap_filter(rep), want, "log")
         assert np.array_equal(got_traj, want_traj)
     else:
-        got = _snap(rep)
+        got = sp.snap_filter(rep)
         tol = 1e-9 if dtype == "float64" else 1e-5
         assert np.abs(got_traj - want_traj).max() <= 1e-9 and np.abs(got[1] - want[1]).max() <= tol
 
@@ -271,10 +256,10 @@ def test_the_flag_without_scales_is_the_filter_without_the_flag(name, model):
         rep = _filter(model, n, m, frame_scale=flag)
         traj = rep.process_detection_log(log["ids"], log["poses"], log["offsets"], log["has_detections"])
         assert flt.pending_scale == 0.0 and rep.pending_scale == 0.0
-        runs.append((np.array(rows), _snap(flt), traj, _snap(rep), rep.backend.last_log_stats()))
+        runs.append((np.array(rows), sp.snap_filter(flt), traj, sp.snap_filter(rep), rep.backend.last_log_stats()))
     assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][2], runs[1][2]) and runs[0][4] == runs[1][4]
-    _same(runs[0][1], runs[1][1], "per frame")
-    _same(runs[0][3], runs[1][3], "log")
+    sp.assert_same(runs[0][1], runs[1][1], "per frame")
+    sp.assert_same(runs[0][3], runs[1][3], "log")
 
 
 @pytest.mark.parametrize("model", MODELS)
@@ -291,11 +276,11 @@ def test_scales_all_one_are_no_scale(model):
     tb = b.process_detection_log(log["ids"], log["poses"], log["offsets"])
     assert a.backend.last_log_stats() == b.backend.last_log_stats()
     assert np.array_equal(ta, tb)
-    _same(_snap(a), _snap(b), "log")
+    sp.assert_same(sp.snap_filter(a), sp.snap_filter(b), "log")
     c, d = _filter(model, n, kw["max_visible"]), _filter(model, n, kw["max_visible"], frame_scale=False)
     tc, td = _loop(c, log, ones)[0], _loop(d, log)[0]
     assert np.array_equal(tc, td)
-    _same(_snap(c), _snap(d), "loop")
+    sp.assert_same(sp.snap_filter(c), sp.snap_filter(d), "loop")
 
 
 # ---- 6. gate and rows compose -----------------------------------------------------------------------------------------------
@@ -337,7 +322,7 @@ def test_gate_rows_and_scales_compose(model, dtype):
     plain = _filter(model, n, m, dtype, row_noise=True, quat_update="scalar_first")
     traj_p = _loop(plain, cut, scale, cut_rows)[0]
     assert np.array_equal(np.array(traj)[1:], traj_p[1:])
-    _same(_snap(flt), _snap(plain), "gated loop = loop without the rejected")
+    sp.assert_same(sp.snap_filter(flt), sp.snap_filter(plain), "gated loop = loop without the rejected")
     # ... and as a log
     glog = _filter(model, n, m, dtype, gate=gate, row_noise=True, quat_update="scalar_first")
     g_traj, g_d2 = glog.process_detection_log(dirty["ids"], dirty["poses"], dirty["offsets"], mahal=True, noise=rows, scale=scale)
@@ -345,10 +330,10 @@ def test_gate_rows_and_scales_compose(model, dtype):
     plog = _filter(model, n, m, dtype, row_noise=True, quat_update="scalar_first")
     p_traj = plog.process_detection_log(cut["ids"], cut["poses"], cut["offsets"], noise=cut_rows, scale=scale)
     assert np.array_equal(g_traj, p_traj)
-    _same(_snap(glog), _snap(plog), "gated log = log without the rejected")
+    sp.assert_same(sp.snap_filter(glog), sp.snap_filter(plog), "gated log = log without the rejected")
     assert glog.pending_scale == plog.pending_scale == flt.pending_scale
     if model == "ekf":
-        _same(_snap(glog), _snap(flt), "log = loop")
+        sp.assert_same(sp.snap_filter(glog), sp.snap_filter(flt), "log = loop")
 
 
 # ---- 7. the lock-out fixture ------------------------------------------------------------------------------------------------
@@ -407,7 +392,7 @@ def test_pending_scale_survives_grow_remove_and_checkpoints(tmp_path):
     flt.observe(ids, poses, scale=2.0)      # grows landmarks and detections per frame: s_eff = 2.75
     big = _filter("ekf", 16, 8, frame_scale=False, noise=fs.scaled_constants("ekf", 2.75))
     big.observe(ids, poses)
-    _same(_snap(flt), _snap(big), "a grown filter used its pending scale")
+    sp.assert_same(sp.snap_filter(flt), sp.snap_filter(big), "a grown filter used its pending scale")
     assert flt.pending_scale == 0.0 and flt.backend.can_frame_scale
     flt.advance(1.5)
     flt.backend.grow(32)
@@ -426,7 +411,7 @@ def test_pending_scale_survives_grow_remove_and_checkpoints(tmp_path):
     keep = [i for i in ids if i != 4]
     back.observe(keep, poses[keep], scale=0.5)
     flt.observe(keep, poses[keep], scale=0.5)
-    _same(_snap(back), _snap(flt), "checkpoint")
+    sp.assert_same(sp.snap_filter(back), sp.snap_filter(flt), "checkpoint")
     # a checkpoint without the key leaves the pending scale 0
     with np.load(tmp_path / "ck.npz") as ck:
         old = {k: ck[k] for k in ck.files if k not in ("frame_scale", "pending_scale")}
@@ -470,7 +455,7 @@ def test_scales_are_validated_before_the_frame_changes_anything():
     pb, fb = plain.backend, flt.backend
     assert pb.lib.ekf_observe_scaled(pb.h, *args, 1.0) == -4 and pb.lib.ekf_advance(pb.h, 1.0) == -4
     assert pb.lib.ekf_set_pending_scale(pb.h, 1.0) == -4
-    before = _snap(flt)
+    before = sp.snap_filter(flt)
     one = np.array([np.nan])
     for bad in (np.nan, np.inf, -1.0):
         one[0] = bad
@@ -478,7 +463,7 @@ def test_scales_are_validated_before_the_frame_changes_anything():
         assert fb.lib.ekf_set_pending_scale(fb.h, bad) == -1
         assert fb.lib.ekf_observe_sequence_device_scaled(fb.h, 8, 8, None, one.ctypes.data_as(dp), 2, 1, None) == -1
     assert flt.pending_scale == 0.0
-    _same(_snap(flt), before, "a rejected call enqueues nothing")
+    sp.assert_same(sp.snap_filter(flt), before, "a rejected call enqueues nothing")
 
 
 # ---- run_slam --frame-period ------------------------------------------------------------------------------------------------

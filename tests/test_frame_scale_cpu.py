@@ -7,6 +7,7 @@ import pytest
 import frame_scale_util as fs
 import gating_util as gu
 import row_noise_util as rn
+import support as sp
 import update_sweep_util as sw
 from conftest import report
 
@@ -170,7 +171,7 @@ def test_run_slam_scales_from_timestamps(tmp_path):
 
 def test_the_abi_declares_the_new_entry_points():
     from aruco_slam_amd import hip_backend
-    header = (sw.REPO / "include" / "ekf_slam_hip.h").read_text()
+    header = sp.HEADER.read_text()
     for name in ("ekf_advance", "ekf_get_pending_scale", "ekf_set_pending_scale", "ekf_observe_scaled",
                  "ekf_observe_sequence_device_scaled", "ekf_observe_log_scaled", "ekf_batch_observe_logs_scaled",
                  "ekf_batch_get_pending_scale", "ekf_batch_set_pending_scale"):

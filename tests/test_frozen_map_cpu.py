@@ -10,7 +10,9 @@ import numpy as np
 import pytest
 
 import frozen_util as fu
+import support as sp
 from conftest import REPO
+from support import lib
 
 NEW_SYMBOLS = ("ekf_set_map_frozen", "ekf_get_map_frozen")
 
@@ -46,19 +48,9 @@ def test_schmidt_step_is_the_joseph_form_schmidt_kalman_update(model, n, m_range
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_new_symbols_are_declared_and_exported(lib):
-    from aruco_slam_amd import hip_backend
-    header = (REPO / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     assert "Localisation mode" in header and "does not accumulate" in header
     # no handle: EKF_ERR_INVALID, nothing touched
     assert lib.ekf_set_map_frozen(None, 1) == -1 and lib.ekf_get_map_frozen(None) == -1

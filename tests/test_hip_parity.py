@@ -11,6 +11,7 @@ Tolerances (relative = max|a-b| / max(1, max|b|)):
 import numpy as np
 import pytest
 
+import support as sp
 from conftest import chaos_horizon, load_npz, rel_err, rel_err_elem, report
 
 pytestmark = pytest.mark.gpu
@@ -496,18 +497,6 @@ def test_add_marker_with_uncertainty_and_duplicates():
     assert rel_err(flt.get_lm_uncertainties(), orc.get_lm_uncertainties()) <= 1e-10
 
 
-def _parse_traj(text):
-    return np.array([[float(t) for t in line.split()] for line in text.splitlines()])
-
-
-def _parse_map(text):
-    lines = text.splitlines()[4:]
-    ids = [int(lines[i]) for i in range(0, len(lines) - 2, 4)]
-    xyz = np.array([[float(t) for t in lines[i + 1].split(", ")] for i in range(0, len(lines) - 2, 4)])
-    unc = np.array([[float(t) for t in lines[i + 2].split(", ")] for i in range(0, len(lines) - 2, 4)])
-    return ids, xyz, unc
-
-
 def test_c1_run_slam_outputs_vs_reference_files(tmp_path, golden_dir):
     """C1: `run_slam --filter ekf` on the 200-frame replay; outputs/trajectory.txt and
     outputs/map.txt against the files the reference wrote for the same frames."""
@@ -523,7 +512,7 @@ def test_c1_run_slam_outputs_vs_reference_files(tmp_path, golden_dir):
     # format: same line count, timestamps and token counts; integer pose before the first marker
     assert got_t.splitlines()[0] == ref_t.splitlines()[0] == "0.0333 0 0 0 1 0 0 0"
     assert [ln.split()[0] for ln in got_t.splitlines()] == [ln.split()[0] for ln in ref_t.splitlines()]
-    a, b = _parse_traj(got_t), _parse_traj(ref_t)
+    a, b = sp.parse_trajectory(got_t), sp.parse_trajectory(ref_t)
     assert a.shape == b.shape == (200, 8)
     hz = chaos_horizon(load_npz("g3_free_run.npz"))
     err = rel_err(a[:hz + 1], b[:hz + 1])
@@ -535,8 +524,8 @@ def test_c1_run_slam_outputs_vs_reference_files(tmp_path, golden_dir):
     # beyond the horizon -> format and ids only, values must be finite
     got_m, ref_m = (tmp_path / "map.txt").read_text(), (golden_dir / "g3_map.txt").read_text()
     assert got_m.splitlines()[:4] == ref_m.splitlines()[:4]
-    gi, gx, gu = _parse_map(got_m)
-    ri, rx, ru = _parse_map(ref_m)
+    gi, gx, gu = sp.parse_map(got_m)
+    ri, rx, ru = sp.parse_map(ref_m)
     assert gi == ri and gx.shape == rx.shape and gu.shape == ru.shape
     assert np.isfinite(gx).all() and (gu > 0).all()
 
@@ -555,7 +544,7 @@ def test_run_slam_ekf_rotations_outputs_vs_reference_files(tmp_path, golden_dir)
     got_t, ref_t = (tmp_path / "trajectory.txt").read_text(), (golden_dir / "g5_trajectory.txt").read_text()
     assert got_t.splitlines()[0] == ref_t.splitlines()[0] == "0.0333 0 0 0 1 0 0 0"
     assert [ln.split()[0] for ln in got_t.splitlines()] == [ln.split()[0] for ln in ref_t.splitlines()]
-    a, b = _parse_traj(got_t), _parse_traj(ref_t)
+    a, b = sp.parse_trajectory(got_t), sp.parse_trajectory(ref_t)
     assert a.shape == b.shape == (120, 8)
     got_m, ref_m = (tmp_path / "map.txt").read_text(), (golden_dir / "g5_map.txt").read_text()
     assert got_m.splitlines()[:4] == ref_m.splitlines()[:4]
@@ -589,7 +578,7 @@ def test_c1_map_txt_matches_reference_at_the_horizon(tmp_path, golden_dir):
         if ids is not None:
             orc.observe(list(ids), poses)
     flt.save_map(str(tmp_path / "map.txt"))
-    gi, gx, gu = _parse_map((tmp_path / "map.txt").read_text())
+    gi, gx, gu = sp.parse_map((tmp_path / "map.txt").read_text())
     assert gi == [k for k, _ in sorted(orc.landmarks.items(), key=lambda kv: kv[1])]
     assert rel_err(gx, orc.state[10:].reshape(-1, 3)) <= 1e-4
     assert rel_err(gu, orc.get_lm_uncertainties()) <= 1e-4

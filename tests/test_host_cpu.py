@@ -2,24 +2,18 @@
 declares, host logic, file formats, synthetic streams.  No GPU compute."""
 import ctypes
 import re
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import support as sp
 from conftest import REPO, load_npz
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
+from support import lib
 
 
 def test_header_symbols_are_exported(lib):
     from aruco_slam_amd import hip_backend
-    header = (REPO / "include" / "ekf_slam_hip.h").read_text()
+    header = sp.HEADER.read_text()
     declared = set(re.findall(r"\b(ekf_[a-z_0-9]+)\s*\(", header))
     assert declared == set(hip_backend.EXPORTED_SYMBOLS)
     for name in declared:
@@ -38,25 +32,17 @@ def test_config_struct_matches_header_and_defaults(lib):
 
 @pytest.mark.parametrize("n,m,dtype,elem", [(1024, 32, 1, 4), (256, 16, 0, 8), (4096, 64, 1, 4)])
 def test_query_sizes(lib, n, m, dtype, elem):
-    from aruco_slam_amd.hip_backend import EkfConfig
-    cfg = EkfConfig()
-    lib.ekf_default_config(ctypes.byref(cfg))
-    cfg.max_landmarks, cfg.max_visible, cfg.cov_dtype = n, m, dtype
-    ld, cb, sb, wb = ctypes.c_int64(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-    assert lib.ekf_query_sizes(ctypes.byref(cfg), ctypes.byref(ld), ctypes.byref(cb),
-                               ctypes.byref(sb), ctypes.byref(wb)) == 0
+    rc, ld, cb, sb, wb = sp.query_sizes(lib, max_landmarks=n, max_visible=m, cov_dtype=dtype)
+    assert rc == 0
     dims = 3 * n + 10
-    assert ld.value % 128 == 0 and dims <= ld.value < dims + 128
-    assert cb.value == ld.value * ld.value * elem
-    assert sb.value == ld.value * 8
-    assert wb.value > 3 * m * ld.value * 8
+    assert ld % 128 == 0 and dims <= ld < dims + 128
+    assert cb == ld * ld * elem
+    assert sb == ld * 8
+    assert wb > 3 * m * ld * 8
 
 
 def test_bad_config_is_rejected_with_message(lib):
-    from aruco_slam_amd.hip_backend import EkfConfig
-    cfg = EkfConfig()
-    lib.ekf_default_config(ctypes.byref(cfg))
-    cfg.max_visible = 65
+    cfg = sp.config(lib, max_visible=65)
     assert lib.ekf_query_sizes(ctypes.byref(cfg), None, None, None, None) == -1
     assert b"max_visible" in lib.ekf_last_error_string()
 
@@ -251,29 +237,16 @@ def test_dictionary_sizes_and_default():
     assert dictionary_size(7) == 1000 and dictionary_size(16) == 1024 and dictionary_size("x") == 50
 
 
-def test_hand_counted_kernels_do_not_spill(tmp_path):
+def test_hand_counted_kernels_do_not_spill():
     """ekf_cov_update_mfma_f32 issues its loads as inline asm and counts them for s_waitcnt by hand: a
     register spill (scratch traffic on the same counter) would silently break the counting."""
-    import re
-    import subprocess
-    from aruco_slam_amd import _build
-    src = _build.CSRC / "ekf_cov_update.hip"
-    out = tmp_path / "cov.s"
-    subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                    str(src), "-o", str(out)], check=True, capture_output=True)
-    text = out.read_text()
-    kernels = re.findall(r"\.name:\s+(\S*ekf_cov_update_mfma_f32\S*)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", text)
+    kernels = sp.kernel_resources("ekf_cov_update.hip", r"ekf_cov_update_mfma_f32")
     assert len(kernels) >= 12
-    assert all(int(spills) == 0 for _, spills in kernels), kernels
-    scratch = re.findall(r"\.name:\s+(\S*ekf_cov_update_mfma_f32\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", text)
-    assert all(int(b) == 0 for _, b in scratch), scratch
+    assert all(res["vgpr_spill_count"] == 0 for res in kernels.values()), kernels
+    assert all(res["private_segment_fixed_size"] == 0 for res in kernels.values()), kernels
     # the macro-tile kernel counts its LDS-DMAs and P loads by hand too (scratch accesses would sit in the same counter)
-    out2 = tmp_path / "macro.s"
-    subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                    str(_build.CSRC / "ekf_cov_macro.hip"), "-o", str(out2)], check=True, capture_output=True)
-    text2 = out2.read_text()
-    macro = re.findall(r"\.name:\s+(\S*ekf_cov_update_macro_f32\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", text2)
-    assert len(macro) >= 24 and all(int(b) == 0 for _, b in macro), macro
+    macro = sp.kernel_resources("ekf_cov_macro.hip", r"ekf_cov_update_macro_f32")
+    assert len(macro) >= 24 and all(res["private_segment_fixed_size"] == 0 for res in macro.values()), macro
 
 
 def test_hand_issued_loads_are_not_touched_before_their_wait(tmp_path):

@@ -7,6 +7,7 @@ import argparse
 import numpy as np
 import pytest
 
+import support as sp
 from conftest import chaos_horizon, load_npz, rel_err, rel_err_elem, report
 
 pytestmark = pytest.mark.gpu
@@ -41,26 +42,14 @@ def _per_frame(flt, log, frames=None):
     return np.array(rows).reshape(-1, 7)
 
 
-def _sub(log, t0, t1):
-    offs = log["offsets"]
-    d0, d1 = int(offs[t0]), int(offs[t1])
-    return {"ids": log["ids"][d0:d1], "poses": log["poses"][d0:d1], "offsets": offs[t0:t1 + 1] - d0,
-            "has_detections": log["has_detections"][t0:t1]}
-
-
 def _replay(flt, log):
     return flt.process_detection_log(log["ids"], log["poses"], log["offsets"], log["has_detections"])
 
 
-def _assert_same(a, b, what):
-    assert a.shape == b.shape, what
-    assert np.array_equal(a, b), (what, float(np.abs(a - b).max()))
-
-
 def _assert_filters_equal(fa, fb):
     assert fa.landmarks == fb.landmarks and fa.num_landmarks == fb.num_landmarks
-    _assert_same(np.asarray(fa.state, np.float64), np.asarray(fb.state, np.float64), "state")
-    _assert_same(fa.uncertainty, fb.uncertainty, "covariance")
+    sp.assert_same(np.asarray(fa.state, np.float64), np.asarray(fb.state, np.float64), "state")
+    sp.assert_same(fa.uncertainty, fb.uncertainty, "covariance")
 
 
 @pytest.fixture(scope="module")
@@ -79,7 +68,7 @@ def test_c1_log_bitwise_equals_per_frame_loop(c1, dtype):
     want = _per_frame(ref, c1)
     flt = _ekf(dtype)
     got = _replay(flt, c1)
-    _assert_same(got, want, "trajectory")
+    sp.assert_same(got, want, "trajectory")
     _assert_filters_equal(flt, ref)
     stats = flt.backend.last_log_stats()
     counts = np.diff(c1["offsets"])
@@ -98,7 +87,6 @@ def _run_slam(tmp_path, name, log_path, filt, resident, kwargs):
 
 
 def test_run_slam_resident_c1_matches_per_frame_run(tmp_path, golden_dir):
-    from test_hip_parity import _parse_map, _parse_traj
     kw = {"max_landmarks": 16, "max_visible": 8}
     log = golden_dir / "c1_detections.npz"
     t_res, m_res = _run_slam(tmp_path, "resident", log, "ekf", True, kw)
@@ -108,14 +96,14 @@ def test_run_slam_resident_c1_matches_per_frame_run(tmp_path, golden_dir):
     ref_t = (golden_dir / "g3_trajectory.txt").read_text()
     assert t_res.splitlines()[0] == ref_t.splitlines()[0] == "0.0333 0 0 0 1 0 0 0"
     assert [ln.split()[0] for ln in t_res.splitlines()] == [ln.split()[0] for ln in ref_t.splitlines()]
-    a, b = _parse_traj(t_res), _parse_traj(ref_t)
+    a, b = sp.parse_trajectory(t_res), sp.parse_trajectory(ref_t)
     assert a.shape == b.shape == (200, 8)
     hz = chaos_horizon(load_npz("g3_free_run.npz"))
     assert rel_err(a[:hz + 1], b[:hz + 1]) <= 1e-4
     ref_m = (golden_dir / "g3_map.txt").read_text()
     assert m_res.splitlines()[:4] == ref_m.splitlines()[:4]
-    gi, gx, gu = _parse_map(m_res)
-    ri, rx, ru = _parse_map(ref_m)
+    gi, gx, gu = sp.parse_map(m_res)
+    ri, rx, ru = sp.parse_map(ref_m)
     assert gi == ri and gx.shape == rx.shape and gu.shape == ru.shape
     assert np.isfinite(gx).all() and (gu > 0).all()
 
@@ -167,7 +155,7 @@ def test_rotations_device_quaternion_matches_host():
     flt = _rot()
     flt.process_detection_log(np.full(count, 7, dtype=np.int32), poses, np.arange(count + 1), np.ones(count, dtype=bool))
     z = flt.backend._log_keep[1][:count * 7 * 8].view(torch.float64).reshape(count, 7).cpu().numpy()
-    _assert_same(z[:, 0:3], poses[:, 0:3], "z position")
+    sp.assert_same(z[:, 0:3], poses[:, 0:3], "z position")
     err = float(np.abs(z[:, 3:7] - euler_xyz_to_quat(poses[:, 3:6])).max())
     report("log_rot_quaternion", max_abs=err)
     # (device sin / cos are not always correctly rounded: a component may land one or two units in the last place away,
@@ -219,7 +207,7 @@ def test_ragged_synthetic_log_bitwise(dtype):
     want = _per_frame(ref, log)
     flt = _ekf(dtype, n=256, m=64)
     got = _replay(flt, log)
-    _assert_same(got, want, "trajectory")
+    sp.assert_same(got, want, "trajectory")
     _assert_filters_equal(flt, ref)
     stats = flt.backend.last_log_stats()
     report(f"log_ragged_{dtype}", **stats)
@@ -244,30 +232,30 @@ def test_log_split_and_interop(c1):
     want = _per_frame(ref, c1)
     # one call == three calls back to back
     flt = _ekf()
-    got = np.concatenate([_replay(flt, _sub(c1, a, b)) for a, b in ((0, 70), (70, 71), (71, 200))])
-    _assert_same(got, want, "trajectory, three calls")
+    got = np.concatenate([_replay(flt, sp.sub_log(c1, a, b)) for a, b in ((0, 70), (70, 71), (71, 200))])
+    sp.assert_same(got, want, "trajectory, three calls")
     _assert_filters_equal(flt, ref)
     # per-frame observe before and after a log call
     mix = _ekf()
-    rows = [_per_frame(mix, c1, range(0, 40)), _replay(mix, _sub(c1, 40, 150)), _per_frame(mix, c1, range(150, 200))]
-    _assert_same(np.concatenate(rows), want, "trajectory, per-frame / log / per-frame")
+    rows = [_per_frame(mix, c1, range(0, 40)), _replay(mix, sp.sub_log(c1, 40, 150)), _per_frame(mix, c1, range(150, 200))]
+    sp.assert_same(np.concatenate(rows), want, "trajectory, per-frame / log / per-frame")
     _assert_filters_equal(mix, ref)
     # a small filter that grows through process_detection_log == one created large
     small, large = _ekf(n=8, m=4), _ekf(n=64, m=32)
-    _assert_same(_replay(small, c1), _replay(large, c1), "trajectory, grown")
+    sp.assert_same(_replay(small, c1), _replay(large, c1), "trajectory, grown")
     _assert_filters_equal(small, large)
     # a device tensor for the poses == the NumPy form
     dev = _ekf()
     poses_t = torch.from_numpy(c1["poses"]).to(dev.backend.device)
     got_t = dev.process_detection_log(c1["ids"], poses_t, c1["offsets"], c1["has_detections"])
-    _assert_same(got_t, want, "trajectory, tensor poses")
+    sp.assert_same(got_t, want, "trajectory, tensor poses")
     _assert_filters_equal(dev, ref)
 
 
 def test_rejected_log_leaves_the_filter_unchanged(c1):
     from aruco_slam_amd.hip_backend import EkfError
     flt = _ekf()
-    _replay(flt, _sub(c1, 0, 120))
+    _replay(flt, sp.sub_log(c1, 0, 120))
     state, cov, known = flt.state.copy(), flt.uncertainty.copy(), dict(flt.landmarks)
     b = flt.backend
     n = flt.num_landmarks
@@ -290,14 +278,14 @@ def test_rejected_log_leaves_the_filter_unchanged(c1):
         b.observe_log(np.array([0, 1, 2]), offs_bad, poses)
     assert err.value.code == -1
     b.sync()
-    _assert_same(flt.state, state, "state after rejected logs")
-    _assert_same(flt.uncertainty, cov, "covariance after rejected logs")
+    sp.assert_same(flt.state, state, "state after rejected logs")
+    sp.assert_same(flt.uncertainty, cov, "covariance after rejected logs")
     assert flt.landmarks == known
     # and the filter goes on exactly like one that never saw them
     ref = _ekf()
-    _replay(ref, _sub(c1, 0, 120))
-    _replay(flt, _sub(c1, 120, 200))
-    _replay(ref, _sub(c1, 120, 200))
+    _replay(ref, sp.sub_log(c1, 0, 120))
+    _replay(flt, sp.sub_log(c1, 120, 200))
+    _replay(ref, sp.sub_log(c1, 120, 200))
     _assert_filters_equal(flt, ref)
 
 
@@ -333,8 +321,8 @@ def test_state_getter_right_after_observe_log(c1):
     got = b.get_state()                                          # straight after the call
     got_cam = b.get_state(10)
     stats = b.last_log_stats()
-    _assert_same(got, want, "state right after observe_log")
-    _assert_same(got_cam, want[:10], "camera right after observe_log")
+    sp.assert_same(got, want, "state right after observe_log")
+    sp.assert_same(got_cam, want[:10], "camera right after observe_log")
     report("log_getter_after_call", **stats)
     if stats["frames_pipelined"] == 0:
         pytest.skip("the pipelined mode is not available on this handle; the getter was checked on serial frames only")
@@ -349,11 +337,11 @@ def test_first_sighting_after_odd_run_following_a_smaller_checkpoint(c1, tmp_pat
     big = _ekf()
     _replay(big, c1)
     def landmarks_after(t):
-        part = _sub(c1, 0, t)
+        part = sp.sub_log(c1, 0, t)
         return plan_detection_log({}, 0, part["ids"], part["offsets"], part["has_detections"]).num_landmarks
     k = next(t for t in range(1, 200) if landmarks_after(t) >= 3)
     small = _ekf()
-    _replay(small, _sub(c1, 0, k))
+    _replay(small, sp.sub_log(c1, 0, k))
     assert 3 <= small.num_landmarks < big.num_landmarks
     ck = tmp_path / "small.npz"
     small.save_checkpoint(str(ck))
@@ -364,7 +352,7 @@ def test_first_sighting_after_odd_run_following_a_smaller_checkpoint(c1, tmp_pat
     tail = _frames([known[:2], known[:3], known[:1], [known[0], 777, known[1]], known[:2], known[:3]], c1["poses"])
     got = _replay(big, tail)
     want = _per_frame(ref, tail)
-    _assert_same(got, want, "trajectory")
+    sp.assert_same(got, want, "trajectory")
     _assert_filters_equal(big, ref)
     report("log_after_smaller_checkpoint", **big.backend.last_log_stats())
 
@@ -380,7 +368,7 @@ def test_back_to_back_log_calls_queue_without_waiting(c1):
     import torch
     trajs, landmarks, n = [], {}, 0
     for a, e in ((0, 50), (50, 100), (100, 150), (150, 200)):
-        part = _sub(c1, a, e)
+        part = sp.sub_log(c1, a, e)
         plan = plan_detection_log(landmarks, n, part["ids"], part["offsets"], part["has_detections"])
         landmarks.update(plan.new_landmarks)
         n = plan.num_landmarks
@@ -389,6 +377,6 @@ def test_back_to_back_log_calls_queue_without_waiting(c1):
         trajs.append(traj)
     b.sync()
     got = torch.cat(trajs).cpu().numpy()
-    _assert_same(got, want, "trajectory, four calls")
-    _assert_same(b.get_state(), ref.state, "state, four calls")
-    _assert_same(b.get_cov(), ref.uncertainty, "covariance, four calls")
+    sp.assert_same(got, want, "trajectory, four calls")
+    sp.assert_same(b.get_state(), ref.state, "state, four calls")
+    sp.assert_same(b.get_cov(), ref.uncertainty, "covariance, four calls")

@@ -1,13 +1,12 @@
 """Log replay (ekf_observe_log / BaseFilter.process_detection_log) without a GPU: the host-side planning of a ragged log
 against the per-frame ``observe`` rules, rejection of malformed logs, the register budget of the new kernels and the
 exported C ABI."""
-import re
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
+import support as sp
 from aruco_slam_amd.filters.base_filter import BaseFilter, plan_detection_log
 
 
@@ -117,29 +116,22 @@ def test_malformed_logs_are_rejected_before_anything_runs(case):
     assert flt.landmarks == {3: 0, 8: 1} and flt.num_landmarks == 2
 
 
-def test_log_kernels_do_not_spill(tmp_path):
+def test_log_kernels_do_not_spill():
     """No scratch memory and no spills in the kernels of the log replay (ekf_log.hip)."""
-    from aruco_slam_amd import _build
-    out = tmp_path / "log.s"
-    subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                    str(_build.CSRC / "ekf_log.hip"), "-o", str(out)], check=True, capture_output=True)
-    text = out.read_text()
-    spills = re.findall(r"\.name:\s+(\S*ekf_log_\S*)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", text)
-    scratch = re.findall(r"\.name:\s+(\S*ekf_log_\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", text)
-    names = {n for n, _ in spills}
+    found = sp.kernel_resources("ekf_log.hip", r"ekf_log_")
     for kind in ("prepare", "add_markers", "fill_rows"):
-        assert any(kind in n for n in names), kind
-    assert len(spills) >= 6 and all(int(v) == 0 for _, v in spills), spills
-    assert len(scratch) == len(spills) and all(int(v) == 0 for _, v in scratch), scratch
+        assert any(kind in n for n in found), kind
+    assert len(found) >= 6, sorted(found)
+    for name, res in found.items():
+        assert res["vgpr_spill_count"] == 0 and res["private_segment_fixed_size"] == 0, (name, res)
 
 
 def test_log_entry_points_are_exported():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    lib = hip_backend.load_library()
+    from aruco_slam_amd import hip_backend
+    lib = sp.load_lib()
     for name in ("ekf_observe_log", "ekf_log_workspace_bytes", "ekf_last_log_stats"):
         assert name in hip_backend.EXPORTED_SYMBOLS
         assert hasattr(lib, name), name
-    header = (_build.PKG.parent / "include" / "ekf_slam_hip.h").read_text()
+    header = sp.HEADER.read_text()
     for name in ("ekf_observe_log(", "ekf_log_workspace_bytes(", "ekf_last_log_stats("):
         assert name in header

@@ -7,6 +7,7 @@ import pytest
 import gating_util as gu
 import motion_util as mu
 import row_noise_util as rn
+import support as sp
 import update_sweep_util as sw
 from conftest import rel_err, report
 
@@ -29,22 +30,6 @@ def _filter(model, n, m, dtype="float64", **kw):
     return EKF(INIT, max_landmarks=max(n, 1), max_visible=max(m, 1), cov_dtype=dtype, **kw)
 
 
-def _restore(flt, prior):
-    state, p, lm_ids = prior[:3]
-    flt.landmarks = {int(k): i for i, k in enumerate(lm_ids)}
-    flt.num_landmarks = len(lm_ids)
-    flt.backend.set_state_cov(state, p)
-
-
-def _snap(flt):
-    return flt.backend.get_state(), flt.backend.get_cov()
-
-
-def _same(a, b, what):
-    for name, u, v in zip(("state", "covariance"), a, b):
-        assert u.shape == v.shape and np.array_equal(u, v), (what, name)
-
-
 # ---- 1. one move against the extended form, and the invariants ------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("model", ["ekf", "rot"])
@@ -59,9 +44,9 @@ def test_one_move_against_the_extended_reference(model, dtype):
         prior = mu.step_prior(model, n, dtype)
         dims = len(prior[0])
         for name, u in mu.STEP_MOTIONS.items():
-            _restore(flt, prior)
+            sp.restore(flt, prior)
             flt.move(u[0:3], u[3:6])
-            x, p = _snap(flt)
+            x, p = sp.snap_backend(flt.backend)
             ref = mu.extended_move(prior[0], prior[1], u)
             r = mu.step_ratios(ref, p, x, dtype)
             worst = [max(a, b) for a, b in zip(worst, r)]
@@ -89,11 +74,11 @@ def test_a_large_map_moves_with_many_workgroups():
     f = rng.normal(size=(10 + 3 * n, 3))
     p = (0.05 * (f @ f.T) + np.diag(rng.uniform(0.5, 1.0, 10 + 3 * n))).astype(np.float32).astype(np.float64)
     p = np.tril(p) + np.tril(p, -1).T
-    _restore(flt, (state, p, list(range(n))))
+    sp.restore(flt, (state, p, list(range(n))))
     flt.move(U[0:3], U[3:6])
     cam = flt.get_poses()[0]
     ref = mu.extended_move(state, p, U)
-    x, got = _snap(flt)
+    x, got = sp.snap_backend(flt.backend)
     assert np.array_equal(cam[:7], x[:7]) and not np.array_equal(x[:7], state[:7])
     r = mu.step_ratios(ref, got, x, "float32")
     assert max(r) <= 1.0, r
@@ -119,20 +104,20 @@ def test_zero_motion_is_no_motion_and_a_moved_frame_is_move_then_observe(model, 
     for m in (1, 16, 17, wide_m):
         prior = sw.dense_prior(model, n, m, 700 + m, dtype)
         # (a)
-        _restore(bare, prior)
+        sp.restore(bare, prior)
         bare.observe(prior[3], prior[4])
-        want = _snap(bare)
+        want = sp.snap_backend(bare.backend)
         for u in (None, np.zeros(6), np.array([0.0, -0.0, 0.0, 0.0, 0.0, -0.0])):
-            _restore(flt, prior)
+            sp.restore(flt, prior)
             flt.observe(prior[3], prior[4], motion=u)
-            _same(_snap(flt), want, ("6a", m, u))
+            sp.assert_same(sp.snap_backend(flt.backend), want, ("6a", m, u))
             if gated:
                 assert np.array_equal(flt.last_mahal, bare.last_mahal)
         # (b), without and with a scale
         for scale in (None, 2.5):
             kw = {} if scale is None else {"scale": scale}
-            _restore(flt, prior)
-            _restore(two, prior)
+            sp.restore(flt, prior)
+            sp.restore(two, prior)
             if scale is None:
                 flt.observe(prior[3], prior[4], motion=U)
             else:      # ekf_observe_moved itself, under the filter layer (whose motion= is move() and then the frame)
@@ -143,17 +128,17 @@ def test_zero_motion_is_no_motion_and_a_moved_frame_is_move_then_observe(model, 
                     flt.last_mahal = d2
             two.move(U[0:3], U[3:6])
             two.observe(prior[3], prior[4], **kw)
-            _same(_snap(flt), _snap(two), ("6b", m, scale))
+            sp.assert_same(sp.snap_backend(flt.backend), sp.snap_backend(two.backend), ("6b", m, scale))
             assert not np.array_equal(flt.backend.get_cov(), want[1])      # (the motion is not ignored)
             if gated:
                 assert np.array_equal(flt.last_mahal, two.last_mahal) and (flt.last_mahal > 0).all()
     # (e)
     prior = sw.dense_prior(model, n, 1, 701, dtype)
     t = mu.STEP_MOTIONS["translation"]
-    _restore(flt, prior)
-    x0, p0 = _snap(flt)
+    sp.restore(flt, prior)
+    x0, p0 = sp.snap_backend(flt.backend)
     flt.move(t[0:3], t[3:6])
-    x, p = _snap(flt)
+    x, p = sp.snap_backend(flt.backend)
     assert np.array_equal(x[3:], x0[3:]) and not np.array_equal(x[0:3], x0[0:3])
     assert np.array_equal(p[3:10, 3:], p0[3:10, 3:]) and np.array_equal(p[3:, 3:10], p0[3:, 3:10])
     assert not np.array_equal(p[0:3], p0[0:3])
@@ -196,9 +181,9 @@ def test_a_log_replay_with_motions_is_the_per_frame_loop(model, dtype):
     assert not np.array_equal(traj[0], INIT[:7]) and len({tuple(traj[t]) for t in (3, 4, 5, 6)}) == 4
     if model == "ekf":
         assert np.array_equal(traj, want_traj)
-        _same(_snap(rep), _snap(loop), "log = loop")
+        sp.assert_same(sp.snap_backend(rep.backend), sp.snap_backend(loop.backend), "log = loop")
     else:
-        a, b = _snap(rep), _snap(loop)
+        a, b = sp.snap_backend(rep.backend), sp.snap_backend(loop.backend)
         assert np.abs(traj - want_traj).max() <= 1e-9 and np.abs(a[0] - b[0]).max() <= 1e-9
         assert np.abs(a[1] - b[1]).max() <= (1e-9 if dtype == "float64" else 1e-5)
     # the oracle wrapper agrees (the tolerance of the per-frame parity tests)
@@ -245,7 +230,7 @@ def test_a_sequence_call_with_motions_is_the_per_frame_loop(model, dtype):
                                      motion=motion if with_motion else None)
         if with_motion:
             assert seq.backend.last_sequence_mode() == "serial"
-            _same(_snap(seq), _snap(loop), "sequence = loop")
+            sp.assert_same(sp.snap_backend(seq.backend), sp.snap_backend(loop.backend), "sequence = loop")
             assert np.array_equal(traj_t.cpu().numpy(), np.array(want_traj))
         else:
             assert seq.backend.last_sequence_mode() == "pipelined"
@@ -271,7 +256,7 @@ def test_an_all_zero_motion_array_is_the_pipelined_call_without_it(model, dtype)
         traj = flt.process_detection_log(*seg, motion=np.zeros((12, 6)) if zero else None)
         stats = flt.backend.last_log_stats()
         assert (stats["frames_pipelined"] == 0) if zero else (stats["frames_pipelined"] > 0), stats
-        runs[zero] = (traj, _snap(flt))
+        runs[zero] = (traj, sp.snap_backend(flt.backend))
         seq = _filter(model, 10, 10, dtype, lookahead=True)
         seq.observe(scene["ids"][:d0], scene["poses"][:d0])
         idx = np.array([seq.landmarks[int(i)] for i in seg[0]], dtype=np.int32).reshape(12, 4)
@@ -281,11 +266,11 @@ def test_an_all_zero_motion_array_is_the_pipelined_call_without_it(model, dtype)
         seq.backend.observe_sequence(torch.tensor(idx, device=dev), torch.tensor(z.reshape(12, 4, -1), dtype=torch.float64, device=dev),
                                      traj_t, motion=np.zeros((12, 6)) if zero else None)
         assert seq.backend.last_sequence_mode() == ("serial" if zero else "pipelined")
-        snap = _snap(seq)      # (the getters wait for the call; the trajectory tensor is complete behind them)
+        snap = sp.snap_backend(seq.backend)      # (the getters wait for the call; the trajectory tensor is complete behind them)
         runs[("seq", zero)] = (traj_t.cpu().numpy(), snap)
     for a, b in ((True, False), (("seq", True), ("seq", False))):
         assert np.array_equal(runs[a][0], runs[b][0]), a
-        _same(runs[a][1], runs[b][1], a)
+        sp.assert_same(runs[a][1], runs[b][1], a)
 
 
 # ---- 4. bit rule 6(f): gate, rows and scales compose -------------------------------------------------------------------------
@@ -330,7 +315,7 @@ def test_gate_rows_scales_and_motions_compose(model, dtype):
     plain = _filter(model, n, m, dtype, row_noise=True, frame_scale=True)
     traj_p = _loop(plain, cut, motion, scale, cut_rows)
     assert np.array_equal(np.array(traj), traj_p)
-    _same(_snap(flt), _snap(plain), "gated loop = loop without the rejected")
+    sp.assert_same(sp.snap_backend(flt.backend), sp.snap_backend(plain.backend), "gated loop = loop without the rejected")
     glog = _filter(model, n, m, dtype, gate=gate, row_noise=True, frame_scale=True)
     g_traj, g_d2 = glog.process_detection_log(dirty["ids"], dirty["poses"], dirty["offsets"], mahal=True, noise=rows,
                                               scale=scale, motion=motion)
@@ -338,10 +323,10 @@ def test_gate_rows_scales_and_motions_compose(model, dtype):
     plog = _filter(model, n, m, dtype, row_noise=True, frame_scale=True)
     p_traj = plog.process_detection_log(cut["ids"], cut["poses"], cut["offsets"], noise=cut_rows, scale=scale, motion=motion)
     assert np.array_equal(g_traj, p_traj)
-    _same(_snap(glog), _snap(plog), "gated log = log without the rejected")
+    sp.assert_same(sp.snap_backend(glog.backend), sp.snap_backend(plog.backend), "gated log = log without the rejected")
     assert glog.pending_scale == plog.pending_scale == flt.pending_scale
     if model == "ekf":
-        _same(_snap(glog), _snap(flt), "log = loop")
+        sp.assert_same(sp.snap_backend(glog.backend), sp.snap_backend(flt.backend), "log = loop")
         assert np.array_equal(g_traj, np.array(traj))
 
 
@@ -351,11 +336,11 @@ def test_a_scaled_moved_frame_is_the_plain_moved_frame_with_the_products():
     prior = sw.dense_prior("ekf", 40, 16, 716)
     flt = _filter("ekf", 40, 16, frame_scale=True, quat_update="as_written")
     twin = _filter("ekf", 40, 16, noise=fs.scaled_constants("ekf", 2.5), quat_update="as_written")
-    _restore(flt, prior)
-    _restore(twin, prior)
+    sp.restore(flt, prior)
+    sp.restore(twin, prior)
     flt.observe(prior[3], prior[4], scale=2.5, motion=U)
     twin.observe(prior[3], prior[4], motion=U)
-    _same(_snap(flt), _snap(twin), "5(b) on a moved frame")
+    sp.assert_same(sp.snap_backend(flt.backend), sp.snap_backend(twin.backend), "5(b) on a moved frame")
 
 
 # ---- 5. the tracking fixture ---------------------------------------------------------------------------------------------
@@ -385,8 +370,8 @@ def test_motions_are_validated_before_anything_changes(tmp_path):
     from aruco_slam_amd.hip_backend import EkfError, _dptr
     prior = sw.dense_prior("ekf", 12, 4, 91)
     flt = _filter("ekf", 12, 4)
-    _restore(flt, prior)
-    before = _snap(flt)
+    sp.restore(flt, prior)
+    before = sp.snap_backend(flt.backend)
     for bad in (np.full(6, np.nan), [0, 0, 0, np.inf, 0, 0], np.zeros(5), np.zeros((2, 6))):
         with pytest.raises(ValueError, match="motion"):
             flt.observe(prior[3], prior[4], motion=bad)
@@ -399,14 +384,14 @@ def test_motions_are_validated_before_anything_changes(tmp_path):
     nan = np.array([0.1, 0, 0, 0, np.nan, 0])
     assert lib.ekf_move(h, _dptr(nan)) == -1
     bare = _filter("ekf", 12, 4, motion=False)
-    _restore(bare, prior)
+    sp.restore(bare, prior)
     assert lib.ekf_move(bare.backend.h, _dptr(U.copy())) == -4
     with pytest.raises(ValueError, match="motion=True"):
         bare.move(U[0:3], U[3:6])
     with pytest.raises(ValueError, match="motion=True"):
         bare.observe(prior[3], prior[4], motion=U)
-    _same(_snap(flt), before, "nothing changed")
-    _same(_snap(bare), before, "nothing changed")
+    sp.assert_same(sp.snap_backend(flt.backend), before, "nothing changed")
+    sp.assert_same(sp.snap_backend(bare.backend), before, "nothing changed")
     # grow, remove_markers and checkpoints keep the capability
     flt.backend.grow(24)
     flt.remove_markers([prior[2][0]])
@@ -417,7 +402,7 @@ def test_motions_are_validated_before_anything_changes(tmp_path):
         bare.load_checkpoint(str(tmp_path / "ck.npz"))
     again = _filter("ekf", 12, 4)
     again.load_checkpoint(str(tmp_path / "ck.npz"))
-    _same(_snap(again), _snap(flt), "checkpoint")
+    sp.assert_same(sp.snap_backend(again.backend), sp.snap_backend(flt.backend), "checkpoint")
     assert isinstance(EkfError(-1, "x"), RuntimeError)
 
 
@@ -426,7 +411,7 @@ def test_a_failed_filter_ignores_motions():
     import torch
     prior = sw.dense_prior("ekf", 12, 4, 92)
     flt = _filter("ekf", 12, 4)
-    _restore(flt, prior)
+    sp.restore(flt, prior)
     dev = flt.backend.device
     idx = torch.tensor([[0, 1, 2, 99]], dtype=torch.int32, device=dev)
     z = torch.tensor(np.asarray(prior[4])[None, :, :3], dtype=torch.float64, device=dev)

@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 import motion_util as mu
+import support as sp
 import update_sweep_util as sw
+from support import lib
 
 NEW_SYMBOLS = ("ekf_move", "ekf_observe_moved", "ekf_observe_sequence_device_moved", "ekf_observe_log_moved",
                "ekf_batch_observe_logs_moved")
@@ -89,7 +91,7 @@ def test_step_sizes_name_the_workgroup_boundary():
 # ---- the stage functions, compiled for the host ----------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    return mu.build_host_program(tmp_path_factory.mktemp("motion_host"))
+    return sp.build_host_program("motion_host_main", tmp_path_factory.mktemp("motion_host"))
 
 
 @pytest.mark.parametrize("model", MODELS)
@@ -168,19 +170,10 @@ def test_motion_on_a_filter_built_without_it_is_a_value_error_before_anything_ch
     assert flt._moved and np.array_equal(flt.backend.moved[0], [0.1, 0, 0, 0, 0, 0.2])
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_new_symbols_and_the_flag_are_declared_and_exported(lib):
     from aruco_slam_amd import hip_backend
-    header = (sw.REPO / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     assert re.search(r"EKF_FLAG_MOTION = 512\b", header) and hip_backend.EKF_FLAG_MOTION == 512
     # no handle: EKF_ERR_INVALID, nothing touched
     u = np.zeros(6)
@@ -194,9 +187,8 @@ def test_new_symbols_and_the_flag_are_declared_and_exported(lib):
 
 def test_the_flag_changes_no_size(lib):
     from aruco_slam_amd.hip_backend import EKF_FLAG_MOTION
-    from test_filter_gating_cpu import PARENT_SIZES, _sizes
-    for (model, n, mv, dtype, flags), want in PARENT_SIZES:
-        assert _sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_MOTION) == want
+    for (model, n, mv, dtype, flags), want in sp.PARENT_SIZES:
+        assert sp.sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_MOTION) == want
 
 
 def test_python_layer_takes_motion():

@@ -9,16 +9,11 @@ import pytest
 
 import pose_sweep_util as pu
 from conftest import report
+from support import lib
 
 pytestmark = pytest.mark.gpu
 CAMERAS = ("none", "calib5", "calib4", "rational8")
 SENTINEL = -7.25e300
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import hip_backend
-    return hip_backend.load_library()
 
 
 @pytest.fixture(scope="module")

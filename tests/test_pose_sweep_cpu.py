@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import pose_sweep_util as pu
+import support as sp
 from conftest import report
 from oracle import ippe_extended as xt
 
@@ -18,7 +19,7 @@ C_TRUTH = 4.0
 
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    return pu.build_host_program(tmp_path_factory.mktemp("ippe_host"))
+    return sp.build_host_program("ippe_host_main", tmp_path_factory.mktemp("ippe_host"))
 
 
 def test_reference_recovers_the_projected_truth():

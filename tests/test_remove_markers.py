@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 MODELS = ("ekf", "ekf_rotations")
 DTYPES = ("float64", "float32")
+STEP_TOL_F64 = 1e-10      # one f64 step against the oracle: test_hip_parity.STEP_TOL["float64"]
 
 
 def _traj_frames(flt, frames):
@@ -117,7 +118,6 @@ def test_removal_against_the_numpy_oracle(model):
     """The oracle runs a log; the filter is restored from it, removes on the device while the oracle's arrays lose the same
     rows and columns on the host; five more frames on both."""
     from oracle.ekf_numpy import OracleEKF, OracleEKFRotations
-    from test_hip_parity import STEP_TOL
     n, m, removed = 10, 4, (7, 2, 3)
     scene = ru.Scene(model, n, m, seed=3)
     orc = OracleEKFRotations(ru.INIT, mode="fast") if model == "ekf_rotations" else \
@@ -139,7 +139,7 @@ def test_removal_against_the_numpy_oracle(model):
         flt.observe(ids, poses)
     es, ep = rel_err(flt.state, orc.state), rel_err(flt.uncertainty, orc.uncertainty)
     print(f"oracle[{model}]: state {es:.3e} cov {ep:.3e}")
-    assert es <= STEP_TOL["float64"] and ep <= STEP_TOL["float64"], (es, ep)
+    assert es <= STEP_TOL_F64 and ep <= STEP_TOL_F64, (es, ep)
 
 
 # ---- one large shape ------------------------------------------------------------------------------------------------------

@@ -3,35 +3,22 @@ and exported and validate what they can without a handle, ``ekf_query_sizes`` is
 resources, the ``TentativeLandmarks`` policy on hand-written sequences and the id-table renumbering against ``np.delete``."""
 import ctypes as C
 import re
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from test_filter_gating_cpu import PARENT_SIZES, _sizes
+import support as sp
+from support import lib
 
-REPO = Path(__file__).resolve().parent.parent
 NEW_SYMBOLS = ("ekf_remove_workspace_bytes", "ekf_remove_markers", "ekf_batch_remove_workspace_bytes",
                "ekf_batch_remove_markers")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_new_symbols_are_declared_and_exported(lib):
     from aruco_slam_amd import hip_backend
-    header = (REPO / "include" / "ekf_slam_hip.h").read_text()
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(ekf_\w+)\(", header, re.M))
+    declared = set(re.findall(r"^(?:int|const char \*)\s*(ekf_\w+)\(", sp.HEADER.read_text(), re.M))
     assert declared == set(hip_backend.EXPORTED_SYMBOLS)
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
     # no handle: EKF_ERR_INVALID, nothing touched
     nbytes = C.c_size_t(77)
     assert lib.ekf_remove_workspace_bytes(None, 1, C.byref(nbytes)) == -1
@@ -44,26 +31,13 @@ def test_new_symbols_are_declared_and_exported(lib):
 def test_query_sizes_are_what_they_were(lib):
     """A pin, not a test of the feature: it passes before the removal calls exist as well, and keeps passing only while the
     removal needs nothing from the workspace."""
-    for (model, n, mv, dtype, flags), want in PARENT_SIZES:
-        assert _sizes(lib, model, n, mv, dtype, flags) == want, (model, n, mv, dtype, flags)
+    for (model, n, mv, dtype, flags), want in sp.PARENT_SIZES:
+        assert sp.sizes(lib, model, n, mv, dtype, flags) == want, (model, n, mv, dtype, flags)
 
 
 def test_gather_kernel_uses_no_scratch_and_no_spill():
     """Two instances (f32 / f64 covariance): no scratch, no VGPR spill, no LDS; the register counts are printed."""
-    from aruco_slam_amd import _build
-    with tempfile.TemporaryDirectory() as tmp:
-        out = Path(tmp) / "k.s"
-        subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                        str(_build.CSRC / "ekf_remove.hip"), "-o", str(out)], check=True, capture_output=True)
-        text = out.read_text()
-    meta = text[text.index("amdhsa.kernels:"):text.index("amdhsa.target:")]
-    found = {}
-    for entry in re.split(r"\n  - ", meta)[1:]:
-        fields = dict(re.findall(r"^(?:  )?  \.([a-z_]+):\s+(\S+)", entry, re.M))
-        if "ekf_remove_gather_kernel" in fields.get("name", ""):
-            found[fields["name"]] = {k: int(fields[k]) for k in ("private_segment_fixed_size", "vgpr_spill_count",
-                                                                 "sgpr_spill_count", "group_segment_fixed_size",
-                                                                 "vgpr_count", "sgpr_count")}
+    found = sp.kernel_resources("ekf_remove.hip", r"ekf_remove_gather_kernel")
     assert len(found) == 2, found
     for name, res in found.items():
         print(f"{name}: {res['vgpr_count']} VGPRs, {res['sgpr_count']} SGPRs")

@@ -10,6 +10,7 @@ import pytest
 
 import gating_util as gu
 import row_noise_util as rn
+import support as sp
 import update_sweep_util as sw
 from conftest import load_npz, report
 
@@ -30,22 +31,6 @@ def _filter(model, n, m, dtype="float64", **kw):
         return EKF_Rotations(INIT, max_landmarks=n, max_visible=m, cov_dtype=dtype, **kw)
     from aruco_slam_amd.filters.extended_kalman_filter import EKF
     return EKF(INIT, max_landmarks=n, max_visible=m, cov_dtype=dtype, **kw)
-
-
-def _restore(flt, prior):
-    state, p, lm_ids = prior[:3]
-    flt.landmarks = {int(k): i for i, k in enumerate(lm_ids)}
-    flt.num_landmarks = len(lm_ids)
-    flt.backend.set_state_cov(state, p)
-
-
-def _snap(flt):
-    return np.array(flt.state, dtype=np.float64), flt.uncertainty
-
-
-def _same(a, b, what):
-    for name, u, v in zip(("state", "covariance"), a, b):
-        assert u.shape == v.shape and np.array_equal(u, v), (what, name)
 
 
 # ---- 1. one step against the extended reference ---------------------------------------------------------------------------
@@ -69,9 +54,9 @@ def test_one_step_with_rows_against_the_extended_reference(group, step_refs):
             if key not in filters:
                 filters[key] = _filter(model, n, mv, dt, fused=fused, lookahead=False, row_noise=True)
             flt = filters[key]
-            _restore(flt, prior)
+            sp.restore(flt, prior)
             flt.observe(prior[3], prior[4], noise=rows)
-            x, p = _snap(flt)
+            x, p = sp.snap_filter(flt)
             assert np.array_equal(p, p.T), (case, dt)
             r_p, r_x = sw.ratios(ref, p, x, dt)
             worst = [max(worst[0], r_p), max(worst[1], r_x), max(worst[2], ref["kappa"])]
@@ -100,16 +85,16 @@ def test_uniform_rows_are_the_constant_bit_for_bit(model, dtype, fused, gated):
     rd = rn.RD[model]
     for m in (1, 16, 17, wide_m):
         prior = sw.dense_prior(model, n, m, 300 + m, dtype)
-        _restore(with_rows, prior)
-        _restore(constant, prior)
+        sp.restore(with_rows, prior)
+        sp.restore(constant, prior)
         with_rows.observe(prior[3], prior[4], noise=np.full(m, c) if m % 2 else np.full((m, rd), c))
         constant.observe(prior[3], prior[4])
-        _same(_snap(with_rows), _snap(constant), (model, dtype, fused, gated, m))
+        sp.assert_same(sp.snap_filter(with_rows), sp.snap_filter(constant), (model, dtype, fused, gated, m))
         if gated:
             assert with_rows.last_mahal.shape == (m,) and (with_rows.last_mahal > 0).all()
             assert np.array_equal(with_rows.last_mahal, constant.last_mahal), m
         # ... and the rows are not ignored: the filter's own constant gives other bits
-        _restore(with_rows, prior)
+        sp.restore(with_rows, prior)
         with_rows.observe(prior[3], prior[4])
         assert not np.array_equal(with_rows.uncertainty, constant.uncertainty), m
 
@@ -129,16 +114,16 @@ def test_the_flag_without_noise_is_the_filter_without_the_flag(name, model):
             sl = slice(int(offs[t]), int(offs[t + 1]))
             _, cam, _, _ = flt.process_detections(log["ids"][sl] if has[t] else None, log["poses"][sl])
             rows.append(np.asarray(cam, dtype=np.float64)[:7])
-        per_frame.append((np.array(rows), _snap(flt), dict(flt.landmarks)))
+        per_frame.append((np.array(rows), sp.snap_filter(flt), dict(flt.landmarks)))
     assert np.array_equal(per_frame[0][0], per_frame[1][0]) and per_frame[0][2] == per_frame[1][2]
-    _same(per_frame[0][1], per_frame[1][1], "per frame")
+    sp.assert_same(per_frame[0][1], per_frame[1][1], "per frame")
     replay = []
     for flag in (True, False):
         flt = _filter(model, n, m, row_noise=flag)
         traj = flt.process_detection_log(log["ids"], log["poses"], log["offsets"], log["has_detections"])
-        replay.append((traj, _snap(flt), flt.backend.last_log_stats()))
+        replay.append((traj, sp.snap_filter(flt), flt.backend.last_log_stats()))
     assert np.array_equal(replay[0][0], replay[1][0]) and replay[0][2] == replay[1][2]
-    _same(replay[0][1], replay[1][1], "log")
+    sp.assert_same(replay[0][1], replay[1][1], "log")
     assert replay[0][1][0].tobytes() == replay[1][1][0].tobytes() and replay[0][1][1].tobytes() == replay[1][1][1].tobytes()
 
 
@@ -170,7 +155,7 @@ def test_sequence_log_and_per_frame_loop_agree_with_rows_in_the_pipelined_mode(m
         loop.observe(ids, poses, noise=r)
         want_traj.append(np.asarray(loop.get_poses()[0], dtype=np.float64)[:7])
     want_traj = np.array(want_traj)
-    want = _snap(loop)
+    want = sp.snap_filter(loop)
     plain = booted()      # (the rows matter: the same frames without them end elsewhere)
     for ids, poses in frames:
         plain.observe(ids, poses)
@@ -187,7 +172,7 @@ def test_sequence_log_and_per_frame_loop_agree_with_rows_in_the_pipelined_mode(m
     seq.backend.observe_sequence(torch.tensor(idx, device=dev), torch.tensor(z, dtype=torch.float64, device=dev), traj_t,
                                  rows=torch.tensor(rows, dtype=torch.float64, device=dev))
     assert seq.backend.last_sequence_mode() == "pipelined"
-    _same(_snap(seq), want, "sequence")
+    sp.assert_same(sp.snap_filter(seq), want, "sequence")
     assert np.array_equal(traj_t.cpu().numpy(), want_traj)
 
     rep = booted()
@@ -198,10 +183,10 @@ def test_sequence_log_and_per_frame_loop_agree_with_rows_in_the_pipelined_mode(m
     stats = rep.backend.last_log_stats()
     assert stats["frames_pipelined"] > 0 and stats["frames_stepped"] == steady, stats
     if model == "ekf":
-        _same(_snap(rep), want, "log")
+        sp.assert_same(sp.snap_filter(rep), want, "log")
         assert np.array_equal(got_traj, want_traj)
     else:
-        got = _snap(rep)
+        got = sp.snap_filter(rep)
         assert np.abs(got_traj - want_traj).max() <= 1e-9 and np.abs(got[0] - want[0]).max() <= 1e-9
         assert np.abs(got[1] - want[1]).max() <= 1e-9
 
@@ -260,7 +245,7 @@ def test_gated_log_with_rows(model, dtype):
             plain.observe(cut["ids"][sl], cut["poses"][sl], noise=cut_rows[sl])
         rows_p.append(np.asarray(plain.get_poses()[0], dtype=np.float64)[:7])
     assert np.array_equal(np.array(traj), np.array(rows_p))
-    _same(_snap(flt), _snap(plain), "gated loop = loop without the rejected")
+    sp.assert_same(sp.snap_filter(flt), sp.snap_filter(plain), "gated loop = loop without the rejected")
     # ... and as a log
     glog = _filter(model, n, m, dtype, gate=gate, row_noise=True, quat_update="scalar_first")
     g_traj, g_d2 = glog.process_detection_log(dirty["ids"], dirty["poses"], dirty["offsets"], mahal=True, noise=rows)
@@ -268,10 +253,10 @@ def test_gated_log_with_rows(model, dtype):
     plog = _filter(model, n, m, dtype, row_noise=True, quat_update="scalar_first")
     p_traj = plog.process_detection_log(cut["ids"], cut["poses"], cut["offsets"], noise=cut_rows)
     assert np.array_equal(g_traj, p_traj)
-    _same(_snap(glog), _snap(plog), "gated log = log without the rejected")
+    sp.assert_same(sp.snap_filter(glog), sp.snap_filter(plog), "gated log = log without the rejected")
     if model == "ekf":      # (the EKF replay takes z from the log as the loop does: the same bits, d^2 included)
         assert np.array_equal(g_d2, d2)
-        _same(_snap(glog), _snap(flt), "log = loop")
+        sp.assert_same(sp.snap_filter(glog), sp.snap_filter(flt), "log = loop")
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "stage"])
@@ -285,17 +270,17 @@ def test_rows_reach_the_gate_both_ways(model, dtype, fused):
     m = len(frame["ids"])
     flt = _filter(model, 12, m, dtype, gate=gate, fused=fused, row_noise=True)
     prior = frame["prior"]
-    _restore(flt, prior)
+    sp.restore(flt, prior)
     flt.observe(frame["ids"], frame["poses"])
     assert flt.last_rejected.tolist() == [True, False] + [False] * (m - 2)
     assert np.allclose(flt.last_mahal, frame["d2_const"], rtol=1e-3 if dtype == "float32" else 1e-9)
-    after_const = _snap(flt)
-    _restore(flt, prior)
+    after_const = sp.snap_filter(flt)
+    sp.restore(flt, prior)
     flt.observe(frame["ids"], frame["poses"], noise=frame["rows"])
     assert flt.last_rejected.tolist() == [False, True] + [False] * (m - 2)
     assert np.allclose(flt.last_mahal, frame["d2_rows"], rtol=1e-3 if dtype == "float32" else 1e-9)
     assert flt.backend.last_gate_stats() == {"tested": m, "rejected": 1}
-    assert not np.array_equal(_snap(flt)[1], after_const[1])
+    assert not np.array_equal(sp.snap_filter(flt)[1], after_const[1])
 
 
 # ---- argument checks that need a handle ----------------------------------------------------------------------------------
@@ -322,11 +307,11 @@ def test_noise_is_validated_before_the_frame_changes_anything():
     dp = C.POINTER(C.c_double)
     args = (idx.ctypes.data_as(C.POINTER(C.c_int32)), z.ctypes.data_as(dp))
     assert b.lib.ekf_observe_rows(b.h, *args, r.ctypes.data_as(dp), 2, None, None, None) == -4
-    before = _snap(flt)
+    before = sp.snap_filter(flt)
     for bad in (0.0, -1.0, np.nan, np.inf):
         r[1, 2] = bad
         assert flt.backend.lib.ekf_observe_rows(flt.backend.h, *args, r.ctypes.data_as(dp), 2, None, None, None) == -1
-    _same(_snap(flt), before, "a rejected call enqueues nothing")
+    sp.assert_same(sp.snap_filter(flt), before, "a rejected call enqueues nothing")
 
 
 def test_checkpoint_and_grow_carry_the_capability(tmp_path):
@@ -339,7 +324,7 @@ def test_checkpoint_and_grow_carry_the_capability(tmp_path):
     big = _filter("ekf", 16, 8, row_noise=True)
     big.observe(stream_ids, poses, noise=np.linspace(0.4, 2.0, 6))
     big.observe(stream_ids, poses, noise=np.linspace(0.4, 2.0, 6))
-    _same(_snap(flt), _snap(big), "a grown filter continues as one built large")
+    sp.assert_same(sp.snap_filter(flt), sp.snap_filter(big), "a grown filter continues as one built large")
     flt.save_checkpoint(tmp_path / "ck.npz")
     with pytest.raises(ValueError, match="row_noise=True"):
         _filter("ekf", 8, 8).load_checkpoint(tmp_path / "ck.npz")
@@ -347,7 +332,7 @@ def test_checkpoint_and_grow_carry_the_capability(tmp_path):
     back.load_checkpoint(tmp_path / "ck.npz")
     back.observe(stream_ids, poses, noise=np.linspace(0.4, 2.0, 6))
     flt.observe(stream_ids, poses, noise=np.linspace(0.4, 2.0, 6))
-    _same(_snap(back), _snap(flt), "checkpoint")
+    sp.assert_same(sp.snap_filter(back), sp.snap_filter(flt), "checkpoint")
 
 
 # ---- run_slam: the optional noise array of a replay file ------------------------------------------------------------------

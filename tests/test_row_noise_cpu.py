@@ -2,16 +2,16 @@
 constant, the GPU cases of ``test_row_noise.py`` keep kappa(S) under the limit the componentwise bounds assume, their gate
 cases are clear of the gate, the host side validates ``noise=`` / ``rows=``, and the header declares the entry points."""
 import re
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import gating_util as gu
 import row_noise_util as rn
+import support as sp
 import update_sweep_util as sw
+from support import lib
 
-REPO = Path(__file__).resolve().parent.parent
 NEW_SYMBOLS = ("ekf_observe_rows", "ekf_observe_sequence_device_rows", "ekf_observe_log_rows", "ekf_batch_observe_logs_rows")
 LOG_SEED = 0
 
@@ -116,19 +116,10 @@ def test_noise_on_a_filter_built_without_row_noise_is_a_value_error():
         flt._frame_noise([0.9] * 3, 4)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_new_symbols_and_the_flag_are_declared_and_exported(lib):
     from aruco_slam_amd import hip_backend
-    header = (REPO / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     assert re.search(r"EKF_FLAG_ROW_NOISE = 128\b", header) and hip_backend.EKF_FLAG_ROW_NOISE == 128
     # no handle: EKF_ERR_INVALID, nothing touched
     assert lib.ekf_observe_rows(None, None, None, None, 1, None, None, None) == -1
@@ -139,21 +130,20 @@ def test_new_symbols_and_the_flag_are_declared_and_exported(lib):
 
 def test_sizes_without_the_flag_are_the_parents_and_the_flag_adds_the_survivors_rows(lib):
     """Bit rule 2, the sizes: a configuration without EKF_FLAG_ROW_NOISE has the workspace it had before the flag existed
-    (test_filter_gating_cpu.PARENT_SIZES).  The flag alone adds nothing to the device workspace (host rows are staged in
+    (support.PARENT_SIZES).  The flag alone adds nothing to the device workspace (host rows are staged in
     the pinned slot, device rows are read where they are); with the gate it adds the survivors' rows, 8 RD max_visible
     bytes padded to 256."""
     from aruco_slam_amd.hip_backend import EKF_FLAG_GATE, EKF_FLAG_ROW_NOISE
-    from test_filter_gating_cpu import PARENT_SIZES, _sizes
 
     def pad(v):
         return -(-v // 256) * 256
 
-    for (model, n, mv, dtype, flags), want in PARENT_SIZES:
+    for (model, n, mv, dtype, flags), want in sp.PARENT_SIZES:
         rd = 7 if model == 1 else 3
-        assert _sizes(lib, model, n, mv, dtype, flags) == want
-        assert _sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_ROW_NOISE) == want
-        gated = _sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_GATE)
-        both = _sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_GATE | EKF_FLAG_ROW_NOISE)
+        assert sp.sizes(lib, model, n, mv, dtype, flags) == want
+        assert sp.sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_ROW_NOISE) == want
+        gated = sp.sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_GATE)
+        both = sp.sizes(lib, model, n, mv, dtype, flags | EKF_FLAG_GATE | EKF_FLAG_ROW_NOISE)
         assert both[:3] == gated[:3] and both[3] == gated[3] + pad(8 * rd * mv)
 
 

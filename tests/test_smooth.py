@@ -7,6 +7,7 @@ import pytest
 
 import motion_util as mu
 import smooth_util as su
+import support as sp
 import update_sweep_util as sw
 
 pytestmark = pytest.mark.gpu
@@ -44,10 +45,6 @@ def _replay(flt, log, record, motion=None, scale=None, mahal=False):
     return traj.cpu().numpy(), None if d2 is None else d2.cpu().numpy(), history
 
 
-def _snap(flt):
-    return flt.backend.get_state(), flt.backend.get_cov()
-
-
 # ---- 1. recorded replay = plain replay ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", ["motion", "scale", "gate"])
 def test_recorded_replay_is_the_plain_replay_bit_for_bit(case):
@@ -58,7 +55,8 @@ def test_recorded_replay_is_the_plain_replay_bit_for_bit(case):
     for record in (False, True):
         flt = _filter(**kw)
         traj, d2, _h = _replay(flt, log, record, **args)
-        out.append((traj, d2, *_snap(flt), flt.backend.last_log_stats(), flt.backend.last_gate_stats() if case == "gate" else None))
+        out.append((traj, d2, *sp.snap_backend(flt.backend), flt.backend.last_log_stats(),
+                    flt.backend.last_gate_stats() if case == "gate" else None))
     plain, rec = out
     assert np.array_equal(plain[0], rec[0]) and np.array_equal(plain[2], rec[2]) and np.array_equal(plain[3], rec[3])
     assert plain[4] == rec[4] and plain[5] == rec[5]
@@ -89,7 +87,7 @@ def test_records_are_the_filter_and_the_table_is_the_plan():
                   "has_detections": log["has_detections"][:t1]}
         twin = _filter(motion=True, frame_scale=True)
         _replay(twin, prefix, False, motion=log["motion"][:t1], scale=su.RAGGED_SCALE[:t1])
-        state, cov = _snap(twin)
+        state, cov = sp.snap_backend(twin.backend)
         assert np.array_equal(records[r]["x"], state) and np.array_equal(records[r]["P"], cov), r
     # ekf_history_bytes: by hand for a 3-frame log that adds 2, 0 and 1 markers to an empty filter (N = 16, 16, 19)
     fresh = _filter()
@@ -101,10 +99,10 @@ def _smoothed_case(name, blocked):
     log, motion, scale = su.scene(name)
     flt = _filter(motion=motion is not None, frame_scale=scale is not None)
     traj, _d2, history = _replay(flt, log, True, motion=motion, scale=scale)
-    before = _snap(flt)
+    before = sp.snap_backend(flt.backend)
     frames = traj.shape[0]
     got = flt.backend.smooth_history(history, frames, blocked=blocked).cpu().numpy()
-    after = _snap(flt)
+    after = sp.snap_backend(flt.backend)
     assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])      # read-only
     records, _info = su.device_records(flt.backend, history)
     ref = su.smooth_records(records, frames, INIT)
@@ -172,11 +170,11 @@ def test_the_c_entry_points_refuse_what_is_not_supported(kw):
     from aruco_slam_amd.hip_backend import EkfError
     log = mu.ragged_motion_log("ekf")
     flt = _filter(motion=True, **kw)
-    before = _snap(flt)
+    before = sp.snap_backend(flt.backend)
     with pytest.raises(EkfError) as err:
         _replay(flt, log, True, motion=log["motion"])
     assert err.value.code == -4 and flt.backend.num_landmarks == 0
-    after = _snap(flt)
+    after = sp.snap_backend(flt.backend)
     assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])
 
 
@@ -190,17 +188,18 @@ def test_smooth_detection_log_meets_the_tracking_condition_and_feeds_get_cam_est
     filtered, smoothed = flt.smooth_detection_log(scene["ids"], scene["poses"], scene["offsets"])
     plain = twin.process_detection_log(scene["ids"], scene["poses"], scene["offsets"])
     assert np.array_equal(filtered, plain)
-    for u, v in zip(_snap(flt), _snap(twin)):      # the filter is where process_detection_log leaves it
+    # the filter is where process_detection_log leaves it
+    for u, v in zip(sp.snap_backend(flt.backend), sp.snap_backend(twin.backend)):
         assert np.array_equal(u, v)
     e0, e1 = mu.mean_position_error(filtered, scene), mu.mean_position_error(smoothed, scene)
     print(f"tracking scene on the device: filtered {e0:.4f} m, smoothed {e1:.4f} m")
     assert e1 <= su.TRACK_SMOOTH_RATIO * e0
     # process_detections(should_filter=False, iteration=i) returns the smoothed pose and steps nothing
-    before = _snap(flt)
+    before = sp.snap_backend(flt.backend)
     sl = slice(int(scene["offsets"][7]), int(scene["offsets"][8]))
     _, cam, _markers, _ = flt.process_detections(scene["ids"][sl], scene["poses"][sl], should_filter=False, iteration=7)
     assert cam.shape == (10,) and np.array_equal(cam[:7], smoothed[7]) and not cam[7:].any()
-    assert np.array_equal(before[0], _snap(flt)[0])
+    assert np.array_equal(before[0], sp.snap_backend(flt.backend)[0])
     with pytest.raises(IndexError):
         flt.get_cam_estimate(40)
     with pytest.raises(NotImplementedError):

@@ -2,14 +2,14 @@
 room under the bound, the two forms against each other, P_r - P^s_r positive semi-definite -- on every fixture of the GPU
 tests, then the header, the exported symbols and the Python layer with a fake back end.  ``test_smooth_cov.py`` runs the
 device against the same helpers."""
-import re
-
 import numpy as np
 import pytest
 
 import smooth_cov_util as sc
 import smooth_util as su
+import support as sp
 import update_sweep_util as sw
+from support import lib
 
 NEW_SYMBOLS = ("ekf_smooth_cov_workspace_bytes", "ekf_smooth_history_cov")
 
@@ -83,19 +83,10 @@ def test_many_right_hand_sides_solve_like_the_single_one():
 
 
 # ---- symbols and the header -------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_new_symbols_are_declared_exported_and_refuse_a_null_handle(lib):
     from aruco_slam_amd import _build, hip_backend
-    header = (sw.REPO / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     assert "ekf_smooth_cov.hip" in _build.SOURCES
     block = header[header.index("Smoothed covariances."):header.index("int ekf_observe_log_recorded(")]
     for word in ("The covariance rule", "bitwise symmetric", "BEFORE THE FIRST RECORD", "EKF_ERR_NUMERIC", "8064",

@@ -12,7 +12,9 @@ import pytest
 
 import motion_util as mu
 import smooth_util as su
+import support as sp
 import update_sweep_util as sw
+from support import lib
 
 NEW_SYMBOLS = ("ekf_observe_log_recorded", "ekf_history_record_bytes", "ekf_history_bytes", "ekf_history_info",
                "ekf_history_record", "ekf_smooth_workspace_bytes", "ekf_smooth_history")
@@ -85,7 +87,7 @@ def test_a_p_p_that_is_not_positive_definite_is_an_error():
 # ---- the step functions, compiled for the host ------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    return su.build_host_program(tmp_path_factory.mktemp("smooth_host"))
+    return sp.build_host_program("smooth_host_main", tmp_path_factory.mktemp("smooth_host"))
 
 
 def _host(exe, text):
@@ -114,19 +116,10 @@ def test_host_build_injection_after_residual_returns_the_smoothed_quaternion(hos
 
 
 # ---- symbols, sizes and host checks -----------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_new_symbols_are_declared_and_exported(lib):
     from aruco_slam_amd import _build, hip_backend
-    header = (sw.REPO / "include" / "ekf_slam_hip.h").read_text()
-    for name in NEW_SYMBOLS:
-        assert re.search(rf"\bint {name}\(", header), name
-        assert name in hip_backend.EXPORTED_SYMBOLS and hasattr(lib, name), name
+    sp.assert_abi(lib, NEW_SYMBOLS)
+    header = sp.HEADER.read_text()
     assert "ekf_smooth.hip" in _build.SOURCES and "ekf_smooth_device.h" in _build.HEADERS
     # the refusals are stated in the header
     block = header[header.index("Offline smoothing"):]

@@ -11,16 +11,13 @@ import pytest
 import batch_smooth_util as bu
 import smooth_cov_util as sc
 import smooth_util as su
+import support as sp
 
 pytestmark = pytest.mark.gpu
 INIT = sc.INIT
 GATE = 1e-3
 GATE_TIGHT = 1e-4      # under the ragged log's scales d^2 is a few 1e-4: this gate leaves whole frames without a survivor
 OUT_KEYS = ("smoothed", "cam_cov", "filt_cam_cov", "first_cov")
-
-
-def _eq(a, b):
-    return np.array_equal(a, b, equal_nan=True)
 
 
 def _fresh(name):
@@ -105,23 +102,16 @@ def test_a_failed_pivot_in_the_covariance_pass(name, r_bad, ks):
         rc, got = sc.direct_smooth_cov(b, history, frames, n0)
         assert rc == su.EKF_ERR_NUMERIC, (k, rc)
         for key in ("smoothed", "cam_cov", "filt_cam_cov"):
-            assert _eq(got[key][lead], ref[key][lead]) and np.array_equal(got[key][later], ref[key][later]), (k, key)
+            assert sp.same(got[key][lead], ref[key][lead], equal_nan=True), (k, key)
+            assert np.array_equal(got[key][later], ref[key][later]), (k, key)
             assert (got[key][upto] == su.SENTINEL).all(), (k, key)
         assert (got["first_cov"] == su.SENTINEL).all(), k
         for u, v in zip(before, _filter_snap(flt)):
             assert np.array_equal(u, v)
         restore()
         rc, again = sc.direct_smooth_cov(b, history, frames, n0)
-        assert rc == 0 and all(_eq(again[key], ref[key]) for key in OUT_KEYS), k
+        assert rc == 0 and all(sp.same(again[key], ref[key], equal_nan=True) for key in OUT_KEYS), k
     _nothing_sticky(name, log, flt)
-
-
-def _batch_snap(batch):
-    return [(batch.get_state(b), batch.get_cov(b), dict(batch.landmarks[b])) for b in range(batch.members)]
-
-
-def _same(a, b):
-    return all(np.array_equal(u[0], v[0]) and np.array_equal(u[1], v[1]) and u[2] == v[2] for u, v in zip(a, b))
 
 
 def test_a_failed_pivot_in_one_member_of_a_batch():
@@ -138,7 +128,7 @@ def test_a_failed_pivot_in_one_member_of_a_batch():
     assert rc == 0 and status.tolist() == [0, 0, 0] and not any((r == su.SENTINEL).any() or np.isnan(r).any() for r in ref)
     records = batch.history_records(1)
     assert len(records) == 40 and records[20]["frame"] == 21 and records[0]["frame"] == 1
-    snap, replay_status = _batch_snap(batch), batch.status()
+    snap, replay_status = sp.snap_batch(batch, tables=True), batch.status()
     for k in (0, 39):
         restore = bu.tamper_member(batch, 1, 20, k, su.TAMPER_VALUE)
         rc, got, status = bu.direct_batch_smooth(batch)
@@ -146,8 +136,9 @@ def test_a_failed_pivot_in_one_member_of_a_batch():
         assert got[1].shape == (41, 7) and np.isnan(got[1]).all(), k
         assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2]), k
         wrapped = batch.smooth_history()
-        assert batch.last_smooth_status.tolist() == [0, su.EKF_ERR_NUMERIC, 0] and all(_eq(wrapped[b], got[b]) for b in range(3))
-        assert batch.status() == replay_status == [0, 0, 0] and _same(snap, _batch_snap(batch))
+        assert batch.last_smooth_status.tolist() == [0, su.EKF_ERR_NUMERIC, 0]
+        assert all(sp.same(wrapped[b], got[b], equal_nan=True) for b in range(3))
+        assert batch.status() == replay_status == [0, 0, 0] and sp.same(snap, sp.snap_batch(batch, tables=True))
         restore()
         rc, again, status = bu.direct_batch_smooth(batch)
         assert rc == 0 and status.tolist() == [0, 0, 0] and all(np.array_equal(again[b], ref[b]) for b in range(3)), k
@@ -177,7 +168,7 @@ def test_covariance_pass_on_a_poisoned_workspace(name):
     rc, got = sc.direct_smooth_cov(b, case["history"], case["frames"], case["records"][0]["dims"], poison=True)
     assert rc == 0
     for key in OUT_KEYS:
-        assert _eq(got[key], case["out"][key]), key
+        assert sp.same(got[key], case["out"][key], equal_nan=True), key
         assert not (got[key] == su.SENTINEL).any(), key
     assert np.isfinite(got["first_cov"]).all() and np.isfinite(got["smoothed"]).all()
 
@@ -226,7 +217,7 @@ def test_a_single_filter_records_into_a_poisoned_history():
     assert np.array_equal(b.smooth_history(history, frames, blocked=True).cpu().numpy(), case["blocked"])
     out = b.smooth_history_cov(history, frames)
     for key in OUT_KEYS:
-        assert _eq(out[key].cpu().numpy(), case["out"][key]), key
+        assert sp.same(out[key].cpu().numpy(), case["out"][key], equal_nan=True), key
 
 
 def test_a_batch_records_into_a_poisoned_history(mixed):
@@ -287,7 +278,7 @@ def test_four_and_five_blocks_behind_a_wide_frame(name):
 def _shared_rows_repeat(rows, frame_record):
     for t in range(1, len(frame_record)):
         if frame_record[t] == frame_record[t - 1] >= 0:
-            assert _eq(rows[t], rows[t - 1]), t
+            assert sp.same(rows[t], rows[t - 1], equal_nan=True), t
 
 
 def _gate_unstepped(log, rejected):

@@ -8,6 +8,7 @@ import pytest
 import batch_smooth_util as bu
 import smooth_cov_util as sc
 import smooth_util as su
+from support import lib
 
 BIG = ("n82", "g81_2")
 BIG_DIMS = {"n82": [256] * 4, "g81_2": [253, 256, 259, 259]}
@@ -88,13 +89,6 @@ def test_a_tampered_record_fails_the_oracle_at_its_own_step(oracle, monkeypatch,
 
 
 # ---- the layout arithmetic of the tamper helper ------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
-
-
 def test_record_offsets_and_diagonal_words_follow_the_header(lib):
     """Record r starts at 256 + sum of ``ekf_history_record_bytes`` of the records before it; the state comes first, then the
     triangle column by column, so P[k][k] is double N + k (2 N - k + 1) / 2: compared with the packing written out."""

@@ -12,8 +12,9 @@ derives them).  The constants (update_sweep_util.C_BOUNDS) are the worst ratios 
 import numpy as np
 import pytest
 
-from conftest import report
+import support as sp
 import update_sweep_util as sw
+from conftest import report
 
 pytestmark = pytest.mark.gpu
 
@@ -37,16 +38,9 @@ def _filter(case):
     return EKF(sw.INIT, quat_update=case.quat, **kw)
 
 
-def _restore(flt, prior):
-    state, p, lm_ids = prior[:3]
-    flt.landmarks = {int(k): i for i, k in enumerate(lm_ids)}
-    flt.num_landmarks = len(lm_ids)
-    flt.backend.set_state_cov(state, p)
-
-
 def _step(flt, prior):
     """One production step from the prior; returns (state, P) and checks the capacity padding of cov_t."""
-    _restore(flt, prior)
+    sp.restore(flt, prior)
     flt.observe(prior[3], prior[4])
     x, p = flt.state, flt.uncertainty
     cov = flt.backend.cov_t.cpu().numpy()
@@ -137,7 +131,7 @@ def test_pipelined_sequence_mode_at_every_nb_is_bitwise_the_serial_calls(model, 
             rng = np.random.default_rng(m)
             frames = [poses + np.hstack((rng.normal(0.0, 0.01, (m, 3)), np.zeros((m, 3)))) for _ in range(3)]
             for flt in (pip, ser):
-                _restore(flt, (state, p, lm_ids))
+                sp.restore(flt, (state, p, lm_ids))
             for z in frames:
                 ser.observe(ids, z)
             idx = torch.tensor(np.array([ids] * 3), dtype=torch.int32, device="cuda:0")
@@ -195,7 +189,7 @@ def test_set_fused_then_growth_equals_a_filter_built_that_way_and_large(start_fu
                   fused=start_fused if small else not start_fused)
         if small:
             flt.backend.set_fused(not start_fused)
-        _restore(flt, (state, p, lm_ids))
+        sp.restore(flt, (state, p, lm_ids))
         flt.observe(ids, poses)
         if grow_by == "add_markers":
             flt.add_marker(1000, np.array([0.3, -0.2, 1.5]))
@@ -204,7 +198,7 @@ def test_set_fused_then_growth_equals_a_filter_built_that_way_and_large(start_fu
             more = list(range(6)) * 2
             flt.observe(more, np.vstack((poses, poses)))
         else:
-            _restore(flt, (big_state, big_p, big_ids))
+            sp.restore(flt, (big_state, big_p, big_ids))
             flt.observe(ids + [30, 31], np.vstack((poses, big_poses[:2])))
         out.append((flt.state, flt.uncertainty))
     assert np.array_equal(out[0][0], out[1][0])

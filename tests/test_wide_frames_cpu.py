@@ -1,27 +1,14 @@
 """Wide frames (ekf_config.flags bit 3, EKF_FLAG_WIDE_FRAMES) without a GPU: the configuration check and sizes of the C ABI,
 and the register budget of the wide-frame kernels (ekf_wide.hip)."""
-import ctypes
-import re
-import subprocess
-
 import pytest
 
-
-@pytest.fixture(scope="module")
-def lib():
-    from aruco_slam_amd import _build, hip_backend
-    _build.build()
-    return hip_backend.load_library()
+import support as sp
+from support import lib
 
 
 def _sizes(lib, model, m, flags, n=100):
-    from aruco_slam_amd.hip_backend import EkfConfig
-    cfg = EkfConfig()
-    lib.ekf_default_config(ctypes.byref(cfg))
-    cfg.max_landmarks, cfg.max_visible, cfg.model, cfg.flags = n, m, model, flags
-    ld, cb, sb, wb = ctypes.c_int64(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-    rc = lib.ekf_query_sizes(ctypes.byref(cfg), ctypes.byref(ld), ctypes.byref(cb), ctypes.byref(sb), ctypes.byref(wb))
-    return rc, wb.value
+    rc, _ld, _cov, _state, ws = sp.query_sizes(lib, max_landmarks=n, max_visible=m, model=model, flags=flags)
+    return rc, ws
 
 
 @pytest.mark.parametrize("model,ok,cap", [(0, (65, 300, 1024), 64), (1, (51, 1024), 50)])
@@ -44,17 +31,11 @@ def test_wide_flag_admits_up_to_1024_detections(lib, model, ok, cap):
         assert _sizes(lib, model, m, EKF_FLAG_WIDE_FRAMES)[1] == _sizes(lib, model, m, 0)[1]
 
 
-def test_wide_kernels_do_not_spill(tmp_path):
+def test_wide_kernels_do_not_spill():
     """No scratch memory and no spills in any kernel of the wide-frame translation unit."""
-    from aruco_slam_amd import _build
-    out = tmp_path / "wide.s"
-    subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                    str(_build.CSRC / "ekf_wide.hip"), "-o", str(out)], check=True, capture_output=True)
-    text = out.read_text()
-    spills = re.findall(r"\.name:\s+(\S*ekf_wide_\S*)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", text)
-    scratch = re.findall(r"\.name:\s+(\S*ekf_wide_\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", text)
-    names = {n for n, _ in spills}
+    found = sp.kernel_resources("ekf_wide.hip", r"ekf_wide_")
     for kind in ("measure", "amat", "s_kernel", "potrf", "panel", "update", "finish"):
-        assert any(kind in n for n in names), kind
-    assert len(spills) >= 15 and all(int(v) == 0 for _, v in spills), spills
-    assert len(scratch) == len(spills) and all(int(v) == 0 for _, v in scratch), scratch
+        assert any(kind in n for n in found), kind
+    assert len(found) >= 15, sorted(found)
+    for name, res in found.items():
+        assert res["vgpr_spill_count"] == 0 and res["private_segment_fixed_size"] == 0, (name, res)

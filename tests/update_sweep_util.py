@@ -28,9 +28,11 @@ from pathlib import Path
 
 import numpy as np
 
+import support as sp
+
 REPO = Path(__file__).resolve().parent.parent
 CSRC = REPO / "aruco_slam_amd" / "csrc"
-INIT = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0], dtype=np.float64)
+INIT = sp.INIT
 U = {"float64": 2.0 ** -53, "float32": 2.0 ** -24}
 KAPPA_MAX = 1e3
 # (c_P, c_x) per path and covariance dtype: the worst ratio measured on an MI355X (profiles/update_sweep/summary.json) times
